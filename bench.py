@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- grad-steps/sec of the OSRL train step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config c1|c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c1|c2|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 N > 1 without a torchrun environment re-executes itself under ``python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1`` (one rank per GPU, RCCL); launched BY torchrun it reads
@@ -20,11 +20,14 @@ per-GPU batch, one optimizer step per iteration, gradient all-reduce over RCCL),
 = per-GPU-batch gradient steps per second over the whole job ("scaling": "weak"); ``optimizer_steps_per_s`` and
 ``transitions_per_s`` are printed beside it.
 
-Timing: probes -> [W warm-up steps -> barrier + synchronize -> EXACTLY K steps -> barrier + synchronize] reported as
-``no_preroll`` -> ``--preroll-ms`` (40) of untimed GEMM work (the device's power state needs ~25 ms of load after any idle
-gap, see preroll()) -> the same W + K sequence again = ``value``; max over ranks.  Both protocols are in every line.
+Timing: graph priming -> ``--preroll-ms`` (40) of untimed GEMM work (the device's power state needs ~25 ms of load after
+any idle gap, see preroll()) -> [W warm-up steps -> barrier + synchronize -> EXACTLY K steps -> barrier + synchronize] =
+``value``; max over ranks.  ``--dump-outputs DIR`` then writes what the last timed step computed (dump_outputs()).
 
-Prints ONE JSON line (rank 0) with the driver's contract plus ``roofline`` and ``cpu_baseline``.
+A plain run does only that and prints ONE JSON line (rank 0) with the driver's contract.  ``--full`` adds everything
+else, as the line carried it before: in front of the timed region the box's diagnostics (``lease``), the ``roofline``
+probes and the same W + K steps timed without the pre-roll (``no_preroll``); behind it the data-parallel collectives
+probe and C4 line (N > 1), ``api_path``, ``other_configs``, ``cost_return_gap`` and ``cpu_baseline``.
 Nothing here reads /root/reference.
 """
 from __future__ import annotations
@@ -826,6 +829,43 @@ def cost_return_gap(device) -> dict:
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+STATE_ATTRS = ("log_alpha", "pid_state", "log_temperature")  # trained tensors kept beside the state_dict
+
+
+def dump_outputs(out_dir: str, model, stats) -> None:
+    """What the last timed step hands its caller: every tensor of the model's state_dict (the parameters the step
+    updated, target nets included) as ``param.<key>.npy``, the trained scalars the models keep as plain tensor attributes
+    outside it (STATE_ATTRS: CPQ's / BEAR-L's ``log_alpha``, the PID state, CDT's temperature) as ``state.<name>.npy``,
+    and each of the step's statistics as ``stat.<key>.npy`` ('/' -> '.').  Floating tensors keep float32 / float64,
+    integer and bool ones are written as float64.  Over DUMP_LIMIT_BYTES in all, the larger tensors are cut to a fixed, seeded sample of their elements (flattened, in
+    index order) of half that size, so that the files with their headers and the small tensors kept whole stay under it;
+    the samples are the same from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {}
+    for k, v in model.state_dict().items():
+        a = v.detach().cpu().numpy()
+        arrays["param." + k] = a.astype(a.dtype if a.dtype in (np.float32, np.float64) else np.float64, copy=False)
+    for k in STATE_ATTRS:
+        v = getattr(model, k, None)
+        if isinstance(v, torch.Tensor) and "param." + k not in arrays:
+            arrays["state." + k] = v.detach().cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32)
+    for k, v in stats.items():
+        arrays["stat." + k.replace("/", ".")] = np.asarray([v], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES / (2.0 * total)
+        rs = np.random.RandomState(0)
+        for k in sorted(arrays):
+            a = arrays[k].reshape(-1)
+            n = int(a.size * keep)
+            if a.size > 1024 and n < a.size:
+                arrays[k] = a[np.sort(rs.choice(a.size, n, replace=False))]
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+
+
 def free_port() -> int:
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -851,7 +891,17 @@ def main():
     ap.add_argument("--steps-per-graph", type=int, default=DEFAULT_STEPS_PER_GRAPH,
                     help="train steps per replayed hipGraph, software-pipelined across steps (CPQ / BCQ-Lag, one GPU; 0 = the "
                          "plan's choice, 1 = one step per graph).  K timed steps = K // n graphs + K %% n single-step replays")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure as well: the box's diagnostics, the roofline probes, the "
+                         "timed region without pre-roll (no_preroll), the collectives probe and C4 line (N > 1), api_path, "
+                         "other_configs, cost_return_gap and the CPU baselines (the --no-* switches trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the model's parameters and the "
+                         "step's statistics) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set-up, warm-up, the K timed steps, the outputs, the line -- nothing else
+        args.no_roofline = args.no_cold = args.no_extras = args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the N-rank job (one process per GPU over RCCL)
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
@@ -911,7 +961,7 @@ def main():
     # 4.5 % below a long one on the same box (2059 vs 2155 steps/s, profiles/r2_bench_driver_cmd.json vs r2_bench.json:
     # idle clocks / first replays suspected).  Every rank runs them (no collectives inside: under data parallelism only
     # the isolated launches are timed), rank 0 reports.
-    lease = lease_diagnostics(device) if rank == 0 else None
+    lease = lease_diagnostics(device) if rank == 0 and args.full else None
     roof = None
     if not args.no_roofline and cfg["algo"] == "cpq":
         try:
@@ -927,8 +977,8 @@ def main():
             return float(t.item())
         return x
 
-    # Both protocols are measured and reported: first W warm-up + K timed steps straight after the probes
-    # (`no_preroll`: what the same command measured in rounds 1-3's records), then the pre-roll + W + K again: `value`.
+    # With --full both protocols are measured and reported: first W warm-up + K timed steps straight after the
+    # probes (`no_preroll`: what the same command measured in rounds 1-3's records), then the pre-roll + W + K again: `value`.
     spg = wl.build_pipe(args.steps_per_graph) if dp is None else 1  # (graphs captured here, outside the timed regions)
     n_done = 0
     # Graph priming (untimed, counted in the step total): the FIRST time several replays are in flight at once the runtime
@@ -954,6 +1004,8 @@ def main():
     stats = eng.st.read_stats()
     assert all(np.isfinite(v) for v in stats.values()), stats
     assert eng.st.device_step() == n_done
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.model, stats)
 
     # ---- the headline measurement is done.  Everything below is side information; under data parallelism it holds
     # collectives (the per-collective probe, the C4 line), i.e. a rank that fails or stalls there would hang its peers and
@@ -983,7 +1035,7 @@ def main():
 
     # data parallel: how long each of the step's collectives takes inside the step (every rank runs the probe)
     coll = None
-    if dp is not None and cfg["algo"] == "cpq":
+    if args.full and dp is not None and cfg["algo"] == "cpq":
         try:
             coll = collectives_in_step(eng, dp)
         except Exception as e:

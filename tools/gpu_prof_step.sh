@@ -1,11 +1,12 @@
 #!/bin/bash
-# rocprofv3 kernel trace of bench.py (the driver's command line), summaries -> gpurun_out/prof_step/
-cd "$GRAFT_REPO_ROOT" || exit 1
-export TMPDIR=/tmp
-OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_step
-rm -rf $OUT; mkdir -p $OUT
-cd /tmp && rocprofv3 --kernel-trace --stats -f csv -d $OUT -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-extras ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
-cd $GRAFT_REPO_ROOT
+# rocprofv3 kernel trace of `bench.py --full` (the roofline probes included), summaries -> OUTDIR/prof_step/
+#   bash tools/gpu_prof_step.sh OUTDIR
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+mkdir -p "${1:?usage: tools/gpu_prof_step.sh OUTDIR}" || exit 1
+OUT=$(cd "$1" && pwd)/prof_step
+rm -rf "$OUT"; mkdir -p "$OUT"
+cd "$OUT" && timeout -k 10 900 rocprofv3 --kernel-trace --stats -f csv -d "$OUT" -o bench -- python "$ROOT/bench.py" --full --steps 300 --warmup 20 --no-cpu-baseline --no-extras ${BENCH_ARGS} > "$OUT/bench.json" 2> "$OUT/bench.err"
+cd "$ROOT"
 T=$(find $OUT -name "*kernel_trace.csv" | head -1); S=$(find $OUT -name "*kernel_stats.csv" | head -1)
 python tools/timeline.py $T > $OUT/timeline.txt 2>&1
 python tools/trace_summary.py $T > $OUT/trace_summary.txt 2>&1

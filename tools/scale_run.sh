@@ -19,7 +19,7 @@ for C in c2 c4; do
   for N in $NS; do
     if [ "$N" -gt "$NGPU" ]; then echo "skip $C N=$N: only $NGPU GPU(s) visible"; continue; fi
     F=$OUT/scale_${C}_n${N}.json
-    timeout 900 python bench.py --gpus $N --config $C --steps 300 --warmup 30 --no-cpu-baseline --no-extras > $F 2> $OUT/scale_${C}_n${N}.err
+    timeout 900 python bench.py --gpus $N --config $C --steps 300 --warmup 30 --full --no-cpu-baseline --no-extras > $F 2> $OUT/scale_${C}_n${N}.err
     rc=$?
     if [ $rc -ne 0 ] || [ ! -s $F ]; then echo "FAIL $C N=$N rc=$rc"; tail -5 $OUT/scale_${C}_n${N}.err; continue; fi
     python - "$F" "$N" "$OUT/scale_${C}_n${N}.err" <<'PY'
@@ -43,7 +43,7 @@ if n > 1 and not g:
     sys.exit(7)
 PY
     if [ $? -eq 7 ]; then
-      OSRL_DP_EAGER=1 timeout 900 python bench.py --gpus $N --config $C --steps 300 --warmup 30 --no-cpu-baseline --no-extras > $OUT/scale_${C}_n${N}_eager.json 2>> $OUT/scale_${C}_n${N}.err
+      OSRL_DP_EAGER=1 timeout 900 python bench.py --gpus $N --config $C --steps 300 --warmup 30 --full --no-cpu-baseline --no-extras > $OUT/scale_${C}_n${N}_eager.json 2>> $OUT/scale_${C}_n${N}.err
       python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(f\"  eager: {d['value']:.1f} grad-steps/s\")" $OUT/scale_${C}_n${N}_eager.json
     fi
   done
