@@ -339,11 +339,14 @@ int osrl_vae_ns_backward(const osrl_vae_ns_t* v, void* stream);
 
 /* General linear layer on packed weights: Y[M,N] = A[M,K] * P (+ bias[N]) (+ resid[M,N]).  P is the forward
  * pack of W[N,K] (y = x W^T; Np = round16(N), col0 = 0) or the backward pack of W[N',K'] for dx = dy W
- * (then K = N', N = K' or a column slice starting at col0, Np = round16(K')+16).  K <= 1024; N is
+ * (then K = N', N = K' or a column slice starting at col0, Np = round16(K')+16).  K <= 4096 (above 1024 the
+ * register-streamed tile form stages A in 1024-column chunks inside one workgroup); N is
  * unbounded (column groups).  Replaces nn.Linear / addmm + residual adds of the CDT block
  * (osrl/common/net.py:406-415,439-440, osrl/algorithms/cdt.py:96-141) and their input gradients. */
 int osrl_linear(const float* A, int64_t lda, int32_t M, int32_t K, const float* P, int32_t Np, int32_t col0,
                 int32_t N, const float* bias, const float* resid, int64_t ldr, float* Y, int64_t ldy, void* stream);
+/* dynamic LDS per workgroup of that chunked form (K > 1024 where the big-M kernels do not take the shape) */
+int64_t osrl_linear_kchunk_lds_bytes(void);
 /* Refresh the packed copies of `n_entries` weights (entries in DEVICE memory).  Sizes in floats:
  * forward round16(in)*round16(out), backward round16(out)*(round16(in)+16).  max_elems = the largest
  * packed size among the entries (grid sizing).  Must run after every change of the canonical weights. */
@@ -673,6 +676,23 @@ int osrl_attention_fwd_keep(const float* qkv, const float* mask, int32_t B, int3
 int osrl_attention_bwd_keep(const float* qkv, const float* mask, const float* dout, int32_t B, int32_t S, int32_t E,
                             int32_t H, int32_t rep, int32_t prefix, const osrl_dropout_t* drop, float* dqkv,
                             const unsigned char* keep, void* stream);
+/* The same function for long sequences and wide heads: S <= 1024 tokens, head_dim = E / H <= 128 (any width; zero padded
+ * to 16 / 32 / 64 / 128 inside).  Tiled kernels: 64-key tiles streamed through LDS with an online softmax, deterministic
+ * (dQ by query tiles, dK / dV by key tiles, no atomics), the same dropout decisions as the pair above.
+ * osrl_attention_ws_bytes(B, S, E, H) = 0 where osrl_attention_fwd / _bwd take the shape (S <= 128, head_dim <= 64);
+ * otherwise, like osrl_attention_tiled_ws_bytes (which answers for every shape the _ws pair takes, 0 = not taken), it is
+ * 4 * B * H * S: the size of `ws` of the backward AND of `lse`.  _fwd_ws writes o [B,S,E] and, when lse != NULL, the
+ * per-row softmax statistics lse [B*H, S] (log2 domain of the scaled scores; +inf for a row without a valid key) that
+ * _bwd_ws reads beside the forward's o (D_i = rowsum(dO o O) goes to ws).  lse = NULL: inference. */
+int64_t osrl_attention_ws_bytes(int32_t B, int32_t S, int32_t E, int32_t H);
+int64_t osrl_attention_tiled_ws_bytes(int32_t B, int32_t S, int32_t E, int32_t H);
+/* dynamic LDS per workgroup of the tiled kernels at a head width: pass 0 forward, 1 dQ, 2 dK / dV (0 = not taken) */
+int64_t osrl_attention_tiled_lds_bytes(int32_t head_dim, int32_t pass);
+int osrl_attention_fwd_ws(const float* qkv, const float* mask, int32_t B, int32_t S, int32_t E, int32_t H, int32_t rep,
+                          int32_t prefix, const osrl_dropout_t* drop, float* o, float* lse, void* stream);
+int osrl_attention_bwd_ws(const float* qkv, const float* mask, const float* dout, int32_t B, int32_t S, int32_t E,
+                          int32_t H, int32_t rep, int32_t prefix, const osrl_dropout_t* drop, const float* o,
+                          const float* lse, float* ws, float* dqkv, void* stream);
 /* nn.Dropout in training mode (cdt.py:87,222 embedding; net.py:404,439 residual; net.py:414 MLP tail):
  * y[i] = x[i] * keep_i / (1-p), may run in place.  keep_i is a pure function of (seed, st->step, site, i)
  * (Philox4x32-10), so calling it again on the incoming gradient IS the backward pass; nothing is stored.

@@ -259,6 +259,13 @@ PROTOTYPES = {
     "osrl_attention_keep_bytes": [_i32, _i32, _i32, _i32],
     "osrl_attention_fwd_keep": [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _P(DropoutT), _fp, _vp, _vp],
     "osrl_attention_bwd_keep": [_fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _P(DropoutT), _fp, _vp, _vp],
+    "osrl_attention_ws_bytes": [_i32, _i32, _i32, _i32],
+    "osrl_attention_tiled_ws_bytes": [_i32, _i32, _i32, _i32],
+    "osrl_attention_tiled_lds_bytes": [_i32, _i32],
+    "osrl_linear_kchunk_lds_bytes": [],
+    "osrl_attention_fwd_ws": [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _P(DropoutT), _fp, _fp, _vp],
+    "osrl_attention_bwd_ws": [_fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _P(DropoutT), _fp, _fp, _fp, _fp,
+                              _vp],
     "osrl_dropout": [_fp, _fp, _i64, _P(DropoutT), _vp],
     "osrl_gelu_fwd": [_fp, _fp, _i64, _vp],
     "osrl_gelu_bwd": [_fp, _fp, _fp, _i64, _vp],
@@ -287,7 +294,9 @@ _LIB: Optional[C.CDLL] = None
 
 LOSS_WS = 132  # floats of scratch for the grid loss kernels (include/osrl_amd.h OSRL_LOSS_WS)
 QUANTILE_WS = 1032  # uint32 elements of scratch for osrl_quantile_ws (include/osrl_amd.h OSRL_QUANTILE_WS)
-RESTYPES = {"osrl_ingest_ws_elems": C.c_int64, "osrl_attention_keep_bytes": C.c_int64}  # everything else returns int (0 = ok)
+RESTYPES = {"osrl_ingest_ws_elems": C.c_int64, "osrl_attention_keep_bytes": C.c_int64,
+            "osrl_attention_ws_bytes": C.c_int64, "osrl_attention_tiled_ws_bytes": C.c_int64,
+            "osrl_attention_tiled_lds_bytes": C.c_int64, "osrl_linear_kchunk_lds_bytes": C.c_int64}  # everything else returns int (0 = ok)
 
 
 def lib_path() -> str:

@@ -5,7 +5,9 @@ are created in the same order, so a seeded construction reproduces the reference
 ``CDTTrainer.train_one_step`` keeps the signature of cdt.py:343.  Supported configuration = the reference's
 every constructor variant of cdt.py:45-141: any subset of the return / cost tokens, with or without the timestep
 embedding, the cost-prefix token, the add / mul / cat cost features on the state feature, deeper action heads,
-stochastic or deterministic, dropout.  Limits: <= 128 tokens per sequence, embedding_dim <= 256.
+stochastic or deterministic, dropout.  Limits: <= 1024 tokens per sequence (seq_repeat * seq_len + cost_prefix),
+embedding_dim <= 1024 with head_dim = embedding_dim / num_heads <= 128; past them the constructor raises
+NotImplementedError naming the limit.
 """
 from __future__ import annotations
 
@@ -40,14 +42,14 @@ class CDT(nn.Module):
             raise ValueError("action_head_layers must be >= 1")
         seq_repeat = 2 + int(bool(use_cost)) + int(bool(use_rew))  # cdt.py:96-105
         S = seq_repeat * seq_len + int(bool(cost_prefix))           # cdt.py:107-112
-        if embedding_dim % num_heads or embedding_dim > 512 or 4 * embedding_dim > 1024 or S > 128:
-            unsupported.append("embedding_dim > 256 or more than 128 tokens per sequence")
-        else:  # the attention backward keeps two [S, head_dim] tiles, row statistics and the keep flags in LDS
-            r16 = lambda x: (x + 15) // 16 * 16  # noqa: E731
-            sp, dp = r16(S), r16(embedding_dim // num_heads)
-            if 4 * (2 * sp * (dp + 8) + 4 * sp) + sp * sp > 160 * 1024:
-                unsupported.append(f"{S} tokens with head_dim {embedding_dim // num_heads} "
-                                   "(attention backward tiles > 160 KB LDS)")
+        if embedding_dim % num_heads:
+            unsupported.append(f"embedding_dim {embedding_dim} not divisible by num_heads {num_heads}")
+        elif embedding_dim > 1024:  # (row kernels: 16 features per lane; the MLP's K = 4E <= 4096 of osrl_linear)
+            unsupported.append(f"embedding_dim {embedding_dim} > 1024")
+        elif embedding_dim // num_heads > 128:  # the tiled attention kernels' widest head
+            unsupported.append(f"head_dim {embedding_dim // num_heads} > 128")
+        if S > 1024:
+            unsupported.append(f"{S} tokens per sequence > 1024 (seq_repeat * seq_len + cost_prefix)")
         if unsupported:
             raise NotImplementedError("osrl_amd CDT does not support: " + "; ".join(unsupported))
         self.seq_len, self.embedding_dim = seq_len, embedding_dim

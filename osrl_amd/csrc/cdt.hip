@@ -11,7 +11,7 @@
 //     accuracy, and the gradients that seed the backward pass                        cdt.py:357-394
 //   * timestep-embedding gradient scatter, global grad-norm clip factor              cdt.py:398-399
 //   * temperature (log_temperature) Adam step                                        cdt.py:402-407
-// All fp32.  Row-wise kernels use one wave64 per token row (E <= 512) with shuffle reductions; these
+// All fp32.  Row-wise kernels use one wave64 per token row (E <= 1024) with shuffle reductions; these
 // are HBM-streaming kernels (LayerNorm: 2 reads + 1-2 writes of [tokens, E] per call).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -26,6 +26,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 constexpr int kMaxEPL = 8;  // features per lane: E <= 512
+constexpr int kMaxEPL2 = 16;  // the second instantiation of the generic row kernels: E <= 1024
 constexpr float kLnEps = 1e-5f;
 
 // 64-lane sum, result in every lane: four DPP steps inside each 16-lane row (VALU, no LDS round trip), then two
@@ -58,21 +59,22 @@ __device__ __forceinline__ float block_sum1024(float v, float* sm) {
 }
 
 // LayerNorm of one row held as v[j] (feature lane + 64 j); returns mean / rstd, writes y
-__device__ __forceinline__ void ln_row(const float (&v)[kMaxEPL], int E, int lane, const float* __restrict__ g,
+template <int EPL>
+__device__ __forceinline__ void ln_row(const float (&v)[EPL], int E, int lane, const float* __restrict__ g,
                                        const float* __restrict__ b, float* __restrict__ y, float* mean_o,
                                        float* rstd_o) {
   float s = 0.f;
 #pragma unroll
-  for (int j = 0; j < kMaxEPL; ++j)
+  for (int j = 0; j < EPL; ++j)
     if (lane + 64 * j < E) s += v[j];
   const float mean = wsum(s) / (float)E;
   float q = 0.f;
 #pragma unroll
-  for (int j = 0; j < kMaxEPL; ++j)
+  for (int j = 0; j < EPL; ++j)
     if (lane + 64 * j < E) q += (v[j] - mean) * (v[j] - mean);
   const float rstd = 1.0f / sqrtf(wsum(q) / (float)E + kLnEps);
 #pragma unroll
-  for (int j = 0; j < kMaxEPL; ++j) {
+  for (int j = 0; j < EPL; ++j) {
     const int f = lane + 64 * j;
     if (f < E) y[f] = (v[j] - mean) * rstd * g[f] + b[f];
   }
@@ -92,6 +94,7 @@ struct EmbedArgs {
 // one wave per token.  Token order per timestep: [return] [cost] state action (cdt.py:185-200: costs are inserted in
 // front of the state token, returns in front of those); with a cost prefix one more token leads each sequence
 // (cdt.py:207-218: Linear(1, E) of the episode's cost budget, no timestep embedding).  te == NULL: time_emb = False.
+template <int EPL>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const EmbedArgs a) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -106,13 +109,13 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const EmbedArgs a) {
   int which = slot + (4 - a.R);
   if (a.R == 3 && a.use_rew) which = slot == 0 ? 0 : slot + 1;
   const float* __restrict__ te = (a.te && !is_prefix) ? a.te + (size_t)a.time_steps[bt] * a.E : nullptr;
-  float v[kMaxEPL];
+  float v[EPL];
   const float ret = a.use_rew ? a.returns[bt] : 0.f;
   const float ctg = a.use_cost ? (a.cost_transform ? 50.0f - a.ctg[bt] : a.ctg[bt]) : 0.f;  // cdt.py:78-81,187-188
   if (!is_prefix && which == 1 && lane == 0) a.ctg_t[bt] = ctg;
   const float ec = is_prefix ? a.episode_cost[b] : 0.f;
 #pragma unroll
-  for (int j = 0; j < kMaxEPL; ++j) {
+  for (int j = 0; j < EPL; ++j) {
     const int f = lane + 64 * j;
     float x = 0.f;
     if (f < a.E) {
@@ -252,7 +255,7 @@ __device__ __forceinline__ float drop_keep(const DropSite& d, uint32_t step, uin
 // (net.py:414,439): the keep-multiplier is applied on the way in -- x + (delta * m), product rounded before the add,
 // i.e. the bits of osrl_dropout followed by the plain kernel -- and one read + one write pass over [M, E] and a launch
 // per residual branch disappear (0.36 ms of the 15 ms C5 step)
-template <bool DROP>
+template <bool DROP, int EPL>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ delta,
                                                      const float* __restrict__ g, const float* __restrict__ b,
                                                      float* __restrict__ xout, float* __restrict__ y,
@@ -262,9 +265,9 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
   if (row >= M) return;
   uint32_t step = 0;
   if constexpr (DROP) step = ds.st ? (uint32_t)ds.st->step : 0u;
-  float v[kMaxEPL];
+  float v[EPL];
 #pragma unroll
-  for (int j = 0; j < kMaxEPL; ++j) {
+  for (int j = 0; j < EPL; ++j) {
     const int f = lane + 64 * j;
     float t = 0.f;
     if (f < E) {
@@ -289,25 +292,25 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 // dx = rstd*(dxhat - mean(dxhat) - xhat*mean(dxhat*xhat)) (+ dres); per-workgroup partial dgamma/dbeta
 // DROP (round 3): also dxd = dx * keep-multiplier of a dropout site -- the gradient entering the residual branch
 // behind the dropout that follows this LayerNorm's input (what a separate osrl_dropout pass over dx produced)
-template <bool DROP>
+template <bool DROP, int EPL>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                      const float* __restrict__ stats, const float* __restrict__ g,
                                                      const float* __restrict__ dres, float* __restrict__ dx,
                                                      float* __restrict__ partial, int M, int E,
                                                      float* __restrict__ dxd, const DropSite ds) {
-  __shared__ float sm[4][2 * 64 * kMaxEPL];
+  __shared__ float sm[4][2 * 64 * EPL];
   uint32_t step = 0;
   if constexpr (DROP) step = ds.st ? (uint32_t)ds.st->step : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float dg[kMaxEPL], db[kMaxEPL];
+  float dg[EPL], db[EPL];
 #pragma unroll
-  for (int j = 0; j < kMaxEPL; ++j) dg[j] = db[j] = 0.f;
+  for (int j = 0; j < EPL; ++j) dg[j] = db[j] = 0.f;
   for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
     const float mean = stats[2 * row], rstd = stats[2 * row + 1];
-    float xh[kMaxEPL], dxh[kMaxEPL];
+    float xh[EPL], dxh[EPL];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int j = 0; j < kMaxEPL; ++j) {
+    for (int j = 0; j < EPL; ++j) {
       const int f = lane + 64 * j;
       xh[j] = dxh[j] = 0.f;
       if (f < E) {
@@ -323,7 +326,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
     s1 = wsum(s1) / (float)E;
     s2 = wsum(s2) / (float)E;
 #pragma unroll
-    for (int j = 0; j < kMaxEPL; ++j) {
+    for (int j = 0; j < EPL; ++j) {
       const int f = lane + 64 * j;
       if (f < E) {
         float v = rstd * (dxh[j] - s1 - xh[j] * s2);
@@ -334,13 +337,13 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
     }
   }
 #pragma unroll
-  for (int j = 0; j < kMaxEPL; ++j) {
+  for (int j = 0; j < EPL; ++j) {
     sm[wave][lane + 64 * j] = dg[j];
-    sm[wave][64 * kMaxEPL + lane + 64 * j] = db[j];
+    sm[wave][64 * EPL + lane + 64 * j] = db[j];
   }
   __syncthreads();
   for (int i = threadIdx.x; i < 2 * E; i += 256) {
-    const int f = i < E ? i : 64 * kMaxEPL + (i - E);
+    const int f = i < E ? i : 64 * EPL + (i - E);
     partial[(size_t)blockIdx.x * 2 * E + i] = (sm[0][f] + sm[1][f]) + (sm[2][f] + sm[3][f]);
   }
 }
@@ -1541,6 +1544,414 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_v_kernel(const AttnArgs a) {
   ATTN_STAMP(5);
 }
 
+// ======================================================================================================================
+// Tiled attention for long sequences and wide heads (S <= 1024 tokens, head_dim <= 128): the flash-attention scheme in
+// fp32 MFMA.  The kernels above hold every [S, S] quantity of one (sample, head) in registers and stop at S = 128 /
+// head_dim 64; these stream 64-key tiles through LDS with an online (running max / running sum) softmax instead.
+// Same function: causal mask, key padding, the cost-prefix token, probability dropout with the decisions of
+// attn_drop_mult4 (logical mask [B*H, S, Sp]: osrl_dropout on a ones tensor exports the same mask), rows without a valid
+// key give zero output and zero gradient.  Template DP = the head width padded to 16 / 32 / 64 / 128 (zero columns).
+//   forward  (one workgroup per (sample, head, 64-query tile), 4 waves x 16 query rows): S^T = K Q^T in the transposed
+//            accumulator layout of attn_fwd_kernel (lane: query m, keys q4 .. q4+3), so the probabilities are the A
+//            fragments of O += P V; writes O and, for training, lse_i = max_i + log2(sum_i) (base-2 domain of the
+//            scaled scores; +inf for a row without a valid key, which makes every rebuilt probability 0).
+//   backward D_i = rowsum(dO o O) from the stored O (attn_rowdot_kernel), then two kernels without atomics:
+//            dQ by 64-query tiles (sweeping key tiles 0 .. the diagonal), dK / dV by 64-key tiles (sweeping query
+//            tiles from the diagonal to the end), each rebuilding P = exp2(s - lse) from the stored statistics.
+// LDS per workgroup: two [64, DP+8] tiles (or K + V^T) and 64-128 row statistics: 70-72 KB at DP = 128.
+constexpr int kAttnTile = 64;
+
+// rows [row0, row0 + 64) x columns [0, DP) of a [S, d] slice with row stride rs -> LDS, zero outside [0, S) x [0, d);
+// TR: stored transposed (dst[c * ld + r]).  vec: d % 4 == 0 and 16-byte aligned rows (float4 loads).
+template <int DP, bool TR>
+__device__ __forceinline__ void attn_tile_load_t(const float* __restrict__ src, size_t rs, int row0, int S_, int d, bool vec,
+                                                 float* dst, int ld) {
+  constexpr int C4 = DP / 4, PER = kAttnTile * C4 / 256;
+  f32x4 v[PER];
+#pragma unroll
+  for (int p = 0; p < PER; ++p) {
+    const int idx = p * 256 + (int)threadIdx.x;
+    const int r = idx / C4, c = 4 * (idx % C4), gr = row0 + r;
+    v[p] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (gr < S_) {
+      const float* q = src + (size_t)gr * rs + c;
+      if (vec) {
+        if (c < d) v[p] = *reinterpret_cast<const f32x4*>(q);
+      } else {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          if (c + t < d) v[p][t] = q[t];
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < PER; ++p) {
+    const int idx = p * 256 + (int)threadIdx.x;
+    const int r = idx / C4, c = 4 * (idx % C4);
+    if (TR) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) dst[(c + t) * ld + r] = v[p][t];
+    } else {
+      *reinterpret_cast<f32x4*>(dst + r * ld + c) = v[p];
+    }
+  }
+}
+// additive key-padding bias of key j (0 valid, -inf padded or past S), as attn_key_bias
+__device__ __forceinline__ float attn_kbias_at(const AttnArgs& a, int b, int j) {
+  const int T = (a.S - a.prefix) / a.rep;
+  const int t = j < a.prefix ? 0 : (j - a.prefix) / a.rep;
+  return (j < a.S && a.mask[(size_t)b * T + t] > 0.f) ? 0.f : -INFINITY;
+}
+__device__ __forceinline__ bool attn_vec_rows(const AttnArgs& a, const void* p) {
+  const int d = a.E / a.H;
+  return (d & 3) == 0 && (a.E & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+}
+
+template <int DP>
+__global__ __launch_bounds__(256) void attn_fwd_t_kernel(const AttnArgs a, float* __restrict__ lse) {
+  constexpr int NCB = DP / 16, LDK = DP + 8, LDV = kAttnTile + 8;
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float *Ks = sm, *Vt = Ks + kAttnTile * LDK, *kb = Vt + DP * LDV;
+  const int d = a.E / a.H, Sp = (a.S + 15) & ~15, nqt = (a.S + kAttnTile - 1) / kAttnTile, BH = a.B * a.H;
+  const int qt = nqt - 1 - (int)(blockIdx.x / BH), bh = (int)(blockIdx.x % BH);  // the longest rows first
+  const int b = bh / a.H, h = bh - b * a.H;
+  const int lane = threadIdx.x & 63, q4 = 4 * (lane >> 4), m = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const size_t ldg = 3 * (size_t)a.E;
+  const float* __restrict__ base = a.qkv + (size_t)b * a.S * ldg + h * d;
+  const bool vec = attn_vec_rows(a, a.qkv);
+  const int ib = qt * 4 + wave, i = ib * 16 + m;
+  const bool active = ib * 16 < a.S;  // wave-uniform
+  const float sc2 = kLog2e / sqrtf((float)d);
+  const f32x4 dbias = {q4 + 0 <= m ? 0.f : -INFINITY, q4 + 1 <= m ? 0.f : -INFINITY, q4 + 2 <= m ? 0.f : -INFINITY,
+                       q4 + 3 <= m ? 0.f : -INFINITY};
+  f32x4 qf[NCB], acc[NCB];
+#pragma unroll
+  for (int c = 0; c < NCB; ++c) {
+    qf[c] = active ? gfrag_row(base, ldg, ib * 16, a.S, c * 16, d, lane) : f32x4{0.f, 0.f, 0.f, 0.f};
+    acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  float mrow = -INFINITY, lrow = 0.f;
+  for (int kt = 0; kt <= qt; ++kt) {
+    __syncthreads();  // every wave is done with the previous tile
+    attn_tile_load_t<DP, false>(base + a.E, ldg, kt * kAttnTile, a.S, d, vec, Ks, LDK);
+    attn_tile_load_t<DP, true>(base + 2 * a.E, ldg, kt * kAttnTile, a.S, d, vec, Vt, LDV);
+    if (threadIdx.x < kAttnTile) kb[threadIdx.x] = attn_kbias_at(a, b, kt * kAttnTile + threadIdx.x);
+    __syncthreads();
+    if (!active) continue;
+    const bool diag = kt == qt;
+    const int nj = diag ? wave + 1 : 4;  // key blocks of the tile at or below this wave's row block
+    f32x4 s[4];
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      s[jj] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (jj < nj) {
+#pragma unroll
+        for (int c = 0; c < NCB; ++c) mfma4(s[jj], frag_row(Ks, LDK, jj * 16, c * 16, lane), qf[c]);
+        f32x4 kbv = *reinterpret_cast<const f32x4*>(kb + jj * 16 + q4);
+        if (diag && jj == wave) kbv += dbias;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          s[jj][r] = __builtin_fmaf(s[jj][r], sc2, kbv[r]);
+          tmax = fmaxf(tmax, s[jj][r]);
+        }
+      }
+    }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+    const float mnew = fmaxf(mrow, tmax);
+    const float mxs = mnew > -INFINITY ? mnew : 0.f;  // no valid key yet: every exp2 below is 0
+    const float alpha = exp2_fast(mrow - mxs);        // (mrow = -inf: 0; the accumulators are 0 then anyway)
+    float sum = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj)
+      if (jj < nj) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = exp2_fast(s[jj][r] - mxs);
+          s[jj][r] = e;
+          sum += e;
+        }
+      }
+    sum += __shfl_xor(sum, 16);
+    sum += __shfl_xor(sum, 32);
+    lrow = lrow * alpha + sum;
+    mrow = mnew;
+    if (a.drop_thresh && i < a.S) {  // P' = P M / (1-p); the softmax sum above is of the undropped P
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj)
+        if (jj < nj) s[jj] *= attn_drop_mult4(a, bh, i, kt * kAttnTile + jj * 16 + q4, Sp);
+    }
+    // the accumulator rows are q4 .. q4+3: their rescale factors live in lanes q4 + r
+    f32x4 al;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) al[r] = __shfl(alpha, q4 + r);
+#pragma unroll
+    for (int c = 0; c < NCB; ++c) {
+      acc[c] *= al;
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj)
+        if (jj < nj) mfma4(acc[c], s[jj], frag_row(Vt, LDV, c * 16, jj * 16, lane));
+    }
+  }
+  if (!active) return;
+  const bool live = i < a.S && mrow > -INFINITY;
+  const float inv = live ? 1.0f / lrow : 0.f;
+  if (lse && q4 == 0 && i < a.S) lse[(size_t)bh * a.S + i] = live ? mrow + __log2f(lrow) : INFINITY;
+  f32x4 iv;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) iv[r] = __shfl(inv, q4 + r);
+#pragma unroll
+  for (int c = 0; c < NCB; ++c) {
+    const int col = c * 16 + m;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int io = ib * 16 + q4 + r;
+      if (io < a.S && col < d) a.o[((size_t)b * a.S + io) * a.E + h * d + col] = acc[c][r] * iv[r];
+    }
+  }
+}
+
+// D[bh * S + i] = sum_c dO[b, i, h, c] O[b, i, h, c]: one 16-lane group per (token, head)
+__global__ __launch_bounds__(256) void attn_rowdot_kernel(const AttnArgs a, const float* __restrict__ o,
+                                                          float* __restrict__ D) {
+  const int d = a.E / a.H;
+  const int64_t g = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4), n = (int64_t)a.B * a.S * a.H;
+  const int l = threadIdx.x & 15;
+  float s = 0.f;
+  if (g < n) {
+    const int64_t bi = g / a.H;  // b * S + i
+    const int h = (int)(g - bi * a.H);
+    const size_t off = (size_t)bi * a.E + (size_t)h * d;
+    for (int c = l; c < d; c += 16) s += a.dout[off + c] * o[off + c];
+  }
+  s = row16_sum(s);
+  if (g < n && l == 0) {
+    const int64_t bi = g / a.H;
+    const int h = (int)(g - bi * a.H);
+    const int64_t b = bi / a.S, i = bi - b * a.S;
+    D[((size_t)b * a.H + h) * a.S + i] = s;
+  }
+}
+
+template <int DP>
+__global__ __launch_bounds__(256) void attn_bwd_dq_t_kernel(const AttnArgs a, const float* __restrict__ lse,
+                                                            const float* __restrict__ D) {
+  constexpr int NCB = DP / 16, LDK = DP + 8;
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float *Ks = sm, *Vs = Ks + kAttnTile * LDK, *kb = Vs + kAttnTile * LDK;
+  const int d = a.E / a.H, Sp = (a.S + 15) & ~15, nqt = (a.S + kAttnTile - 1) / kAttnTile, BH = a.B * a.H;
+  const int qt = nqt - 1 - (int)(blockIdx.x / BH), bh = (int)(blockIdx.x % BH);
+  const int b = bh / a.H, h = bh - b * a.H;
+  const int lane = threadIdx.x & 63, q4 = 4 * (lane >> 4), m = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const size_t ldg = 3 * (size_t)a.E;
+  const float* __restrict__ base = a.qkv + (size_t)b * a.S * ldg + h * d;
+  const float* __restrict__ dob = a.dout + (size_t)b * a.S * a.E + h * d;
+  const bool vec = attn_vec_rows(a, a.qkv);
+  const int ib = qt * 4 + wave, i = ib * 16 + m;
+  const bool active = ib * 16 < a.S;
+  const float scale = 1.0f / sqrtf((float)d), sc2 = kLog2e * scale;
+  const f32x4 dbias = {q4 + 0 <= m ? 0.f : -INFINITY, q4 + 1 <= m ? 0.f : -INFINITY, q4 + 2 <= m ? 0.f : -INFINITY,
+                       q4 + 3 <= m ? 0.f : -INFINITY};
+  f32x4 qf[NCB], dof[NCB], acc[NCB];
+#pragma unroll
+  for (int c = 0; c < NCB; ++c) {
+    qf[c] = dof[c] = acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (active) {
+      qf[c] = gfrag_row(base, ldg, ib * 16, a.S, c * 16, d, lane);
+      dof[c] = gfrag_row(dob, (size_t)a.E, ib * 16, a.S, c * 16, d, lane);
+    }
+  }
+  const float li = (active && i < a.S) ? lse[(size_t)bh * a.S + i] : INFINITY;
+  const float Di = (active && i < a.S) ? D[(size_t)bh * a.S + i] : 0.f;
+  for (int kt = 0; kt <= qt; ++kt) {
+    __syncthreads();
+    attn_tile_load_t<DP, false>(base + a.E, ldg, kt * kAttnTile, a.S, d, vec, Ks, LDK);
+    attn_tile_load_t<DP, false>(base + 2 * a.E, ldg, kt * kAttnTile, a.S, d, vec, Vs, LDK);
+    if (threadIdx.x < kAttnTile) kb[threadIdx.x] = attn_kbias_at(a, b, kt * kAttnTile + threadIdx.x);
+    __syncthreads();
+    if (!active) continue;
+    const bool diag = kt == qt;
+    const int nj = diag ? wave + 1 : 4;
+    f32x4 ds[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      ds[jj] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (jj < nj) {
+        f32x4 s = {0.f, 0.f, 0.f, 0.f}, g = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < NCB; ++c) {
+          mfma4(s, frag_row(Ks, LDK, jj * 16, c * 16, lane), qf[c]);
+          mfma4(g, frag_row(Vs, LDK, jj * 16, c * 16, lane), dof[c]);  // dP'[i][j] = dO_i . V_j
+        }
+        f32x4 kbv = *reinterpret_cast<const f32x4*>(kb + jj * 16 + q4);
+        if (diag && jj == wave) kbv += dbias;
+        f32x4 km = {1.f, 1.f, 1.f, 1.f};
+        if (a.drop_thresh && i < a.S) km = attn_drop_mult4(a, bh, i, kt * kAttnTile + jj * 16 + q4, Sp);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float P = exp2_fast(__builtin_fmaf(s[r], sc2, kbv[r]) - li);
+          ds[jj][r] = P * (km[r] * g[r] - Di);  // dS = P (dP - D), dP = dP' M / (1-p)
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NCB; ++c)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj)
+        if (jj < nj) mfma4(acc[c], ds[jj], frag_col(Ks, LDK, jj * 16, c * 16, lane));  // dQ += dS K
+  }
+  if (!active) return;
+  float* __restrict__ dq = a.dqkv + (size_t)b * a.S * ldg + h * d;
+#pragma unroll
+  for (int c = 0; c < NCB; ++c) {
+    const int col = c * 16 + m;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int io = ib * 16 + q4 + r;
+      if (io < a.S && col < d) dq[(size_t)io * ldg + col] = acc[c][r] * scale;
+    }
+  }
+}
+
+template <int DP>
+__global__ __launch_bounds__(256) void attn_bwd_dkv_t_kernel(const AttnArgs a, const float* __restrict__ lse,
+                                                             const float* __restrict__ D) {
+  constexpr int NCB = DP / 16, LDQ = DP + 8;
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float *Qs = sm, *dOs = Qs + kAttnTile * LDQ, *Ls = dOs + kAttnTile * LDQ, *Ds = Ls + kAttnTile;
+  const int d = a.E / a.H, Sp = (a.S + 15) & ~15, nqt = (a.S + kAttnTile - 1) / kAttnTile, BH = a.B * a.H;
+  const int kt = (int)(blockIdx.x / BH), bh = (int)(blockIdx.x % BH);  // key tile kt sweeps nqt - kt query tiles
+  const int b = bh / a.H, h = bh - b * a.H;
+  const int lane = threadIdx.x & 63, q4 = 4 * (lane >> 4), m = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const size_t ldg = 3 * (size_t)a.E;
+  const float* __restrict__ base = a.qkv + (size_t)b * a.S * ldg + h * d;
+  const float* __restrict__ dob = a.dout + (size_t)b * a.S * a.E + h * d;
+  const bool vec = attn_vec_rows(a, a.qkv) && (reinterpret_cast<uintptr_t>(a.dout) & 15) == 0;
+  const int jb = kt * 4 + wave, j = jb * 16 + m;
+  const bool active = jb * 16 < a.S;
+  const float scale = 1.0f / sqrtf((float)d), sc2 = kLog2e * scale;
+  const f32x4 dbias = {m <= q4 + 0 ? 0.f : -INFINITY, m <= q4 + 1 ? 0.f : -INFINITY, m <= q4 + 2 ? 0.f : -INFINITY,
+                       m <= q4 + 3 ? 0.f : -INFINITY};
+  f32x4 kf[NCB], vf[NCB], accK[NCB], accV[NCB];
+#pragma unroll
+  for (int c = 0; c < NCB; ++c) {
+    kf[c] = vf[c] = accK[c] = accV[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (active) {
+      kf[c] = gfrag_row(base + a.E, ldg, jb * 16, a.S, c * 16, d, lane);
+      vf[c] = gfrag_row(base + 2 * a.E, ldg, jb * 16, a.S, c * 16, d, lane);
+    }
+  }
+  const float kbj = attn_kbias_at(a, b, j);
+  for (int qt = kt; qt < nqt; ++qt) {
+    __syncthreads();
+    attn_tile_load_t<DP, false>(base, ldg, qt * kAttnTile, a.S, d, vec, Qs, LDQ);
+    attn_tile_load_t<DP, false>(dob, (size_t)a.E, qt * kAttnTile, a.S, d, vec, dOs, LDQ);
+    if (threadIdx.x < kAttnTile) {
+      const int r = qt * kAttnTile + threadIdx.x;
+      Ls[threadIdx.x] = r < a.S ? lse[(size_t)bh * a.S + r] : INFINITY;
+      Ds[threadIdx.x] = r < a.S ? D[(size_t)bh * a.S + r] : 0.f;
+    }
+    __syncthreads();
+    if (!active) continue;
+    const bool diag = qt == kt;
+    const int i0 = diag ? wave : 0;  // query blocks of the tile at or below this wave's key block
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii) {
+      if (ii < i0) continue;
+      f32x4 sv = {0.f, 0.f, 0.f, 0.f}, gp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < NCB; ++c) {
+        mfma4(sv, frag_row(Qs, LDQ, ii * 16, c * 16, lane), kf[c]);   // S[i][j] (lane: rows q4 + r, key m)
+        mfma4(gp, frag_row(dOs, LDQ, ii * 16, c * 16, lane), vf[c]);  // dP'[i][j]
+      }
+      const f32x4 lv = *reinterpret_cast<const f32x4*>(Ls + ii * 16 + q4);
+      const f32x4 dv = *reinterpret_cast<const f32x4*>(Ds + ii * 16 + q4);
+      f32x4 kbv = {kbj, kbj, kbj, kbj};
+      if (diag && ii == wave) kbv += dbias;
+      // keep decisions: this lane holds rows q4 + r x key m, one Philox call covers one row x four keys.  Lane
+      // (q4, m) draws row q4 + (m & 3), keys (m & ~3) .. +3 of the block; the four lanes of a quad then hold every
+      // row of the quad's four keys, and lane (lane & ~3) | r hands row q4 + r's bits over: 1 call + 4 shuffles
+      unsigned kbits = 0xFu;
+      if (a.drop_thresh)
+        kbits = attn_keep_bits(attn_drop_mult4(a, bh, qt * kAttnTile + ii * 16 + q4 + (m & 3), jb * 16 + (m & ~3), Sp));
+      f32x4 pp, dsv;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float P = exp2_fast(__builtin_fmaf(sv[r], sc2, kbv[r]) - lv[r]);
+        const unsigned rb = (unsigned)__shfl((int)kbits, (lane & ~3) | r);
+        const float km = a.drop_thresh ? (((rb >> (m & 3)) & 1u) ? a.drop_scale : 0.f) : 1.0f;
+        pp[r] = P * km;                    // P'
+        dsv[r] = P * (km * gp[r] - dv[r]);  // dS
+      }
+#pragma unroll
+      for (int c = 0; c < NCB; ++c) {
+        mfma4(accV[c], pp, frag_col(dOs, LDQ, ii * 16, c * 16, lane));  // dV[j][c] += P'[i][j] dO[i][c]
+        mfma4(accK[c], dsv, frag_col(Qs, LDQ, ii * 16, c * 16, lane));  // dK[j][c] += dS[i][j] Q[i][c]
+      }
+    }
+  }
+  if (!active) return;
+  float* __restrict__ dk = a.dqkv + (size_t)b * a.S * ldg + h * d + a.E;
+#pragma unroll
+  for (int c = 0; c < NCB; ++c) {
+    const int col = c * 16 + m;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int jo = jb * 16 + q4 + r;
+      if (jo < a.S && col < d) {
+        dk[(size_t)jo * ldg + col] = accK[c][r] * scale;
+        dk[(size_t)jo * ldg + a.E + col] = accV[c][r];
+      }
+    }
+  }
+}
+
+template <int DP>
+constexpr size_t attn_t_lds(int which) {  // 0 forward, 1 dQ, 2 dK / dV
+  return sizeof(float) * (which == 0 ? kAttnTile * (DP + 8) + DP * (kAttnTile + 8) + kAttnTile
+                                     : 2 * kAttnTile * (DP + 8) + (which == 1 ? 1 : 2) * kAttnTile);
+}
+static_assert(attn_t_lds<128>(0) <= 160 * 1024 && attn_t_lds<128>(1) <= 160 * 1024 && attn_t_lds<128>(2) <= 160 * 1024,
+              "tiled attention: LDS per workgroup");
+template <int DP>
+static int attn_launch_t(const AttnArgs& a, const float* o, float* lse, float* D, bool fwd, hipStream_t stream) {
+  const unsigned nqt = (unsigned)((a.S + kAttnTile - 1) / kAttnTile), BH = (unsigned)(a.B * a.H);
+  const dim3 grid(nqt * BH), blk(256);
+  if (fwd) {
+    constexpr size_t l0 = attn_t_lds<DP>(0);
+    if (l0 > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_t_kernel<DP>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)l0);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(attn_fwd_t_kernel<DP>, grid, blk, l0, stream, a, lse);
+    return (int)hipGetLastError();
+  }
+  constexpr size_t l1 = attn_t_lds<DP>(1), l2 = attn_t_lds<DP>(2);
+  if (l1 > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_t_kernel<DP>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1);
+  if (l2 > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_t_kernel<DP>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
+  (void)hipGetLastError();
+  const int64_t rows = (int64_t)a.B * a.S * a.H;
+  hipLaunchKernelGGL(attn_rowdot_kernel, dim3((unsigned)((rows + 15) / 16)), blk, 0, stream, a, o, D);
+  hipLaunchKernelGGL(attn_bwd_dq_t_kernel<DP>, grid, blk, l1, stream, a, lse, (const float*)D);
+  hipLaunchKernelGGL(attn_bwd_dkv_t_kernel<DP>, grid, blk, l2, stream, a, lse, (const float*)D);
+  return (int)hipGetLastError();
+}
+static int attn_launch_tiled(const AttnArgs& a, const float* o, float* lse, float* D, bool fwd, hipStream_t stream) {
+  const int d = a.E / a.H;
+  if (d <= 16) return attn_launch_t<16>(a, o, lse, D, fwd, stream);
+  if (d <= 32) return attn_launch_t<32>(a, o, lse, D, fwd, stream);
+  if (d <= 64) return attn_launch_t<64>(a, o, lse, D, fwd, stream);
+  return attn_launch_t<128>(a, o, lse, D, fwd, stream);
+}
+
 // ---------------- dropout (nn.Dropout: cdt.py:87,222; net.py:404,414,439)
 // y = x * keep/(1-p); the same call on the incoming gradient is the backward pass (the mask is a pure function of
 // (seed, step, site, element), philox.h).  HBM-streaming: one Philox call per float4.
@@ -1833,7 +2244,7 @@ int osrl_cdt_embed_ln(const float* states, const float* actions, const float* re
                       const float* ln_b, int32_t B, int32_t T, int32_t od, int32_t ad, int32_t E,
                       int32_t cost_transform, int32_t use_rew, int32_t use_cost, int32_t prefix, float* seq, float* x0,
                       float* stats, float* ctg_t, void* stream) {
-  if (!states || !actions || !time_steps || !seq || !x0 || !stats || B < 1 || T < 1 || E < 1 || E > 64 * kMaxEPL)
+  if (!states || !actions || !time_steps || !seq || !x0 || !stats || B < 1 || T < 1 || E < 1 || E > 64 * kMaxEPL2)
     return -1;
   if ((use_rew && (!returns || !Wr || !br)) || (use_cost && (!costs_to_go || !Wc || !bc || !ctg_t)) ||
       (prefix && (!episode_cost || !Wp || !bp)))
@@ -1861,7 +2272,10 @@ int osrl_cdt_embed_ln(const float* states, const float* actions, const float* re
       DONE();
     }
   }
-  hipLaunchKernelGGL(embed_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, S, a);
+  if (E <= 64 * kMaxEPL)
+    hipLaunchKernelGGL(embed_ln_kernel<kMaxEPL>, dim3((rows + 3) / 4), dim3(256), 0, S, a);
+  else
+    hipLaunchKernelGGL(embed_ln_kernel<kMaxEPL2>, dim3((rows + 3) / 4), dim3(256), 0, S, a);
   DONE();
 }
 
@@ -1875,7 +2289,7 @@ static bool ln_v4_ok(int E, const void* a, const void* b, const void* c, const v
 
 int osrl_layernorm_fwd(const float* x, const float* delta, const float* gamma, const float* beta, float* xout,
                        float* y, float* stats, int32_t M, int32_t E, void* stream) {
-  if (!x || !gamma || !beta || !y || !stats || M < 1 || E < 1 || E > 64 * kMaxEPL) return -1;
+  if (!x || !gamma || !beta || !y || !stats || M < 1 || E < 1 || E > 64 * kMaxEPL2) return -1;
   CLEAR();
   if (ln_v4_ok(E, x, delta, gamma, beta, xout, y)) {
     if (E == 256)
@@ -1886,8 +2300,10 @@ int osrl_layernorm_fwd(const float* x, const float* delta, const float* gamma, c
                          stats, M, DropSite{});
     DONE();
   }
-  hipLaunchKernelGGL(ln_fwd_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, S, x, delta, gamma, beta, xout, y, stats, M,
-                     E, DropSite{});
+  if (E <= 64 * kMaxEPL)
+    hipLaunchKernelGGL((ln_fwd_kernel<false, kMaxEPL>), dim3((M + 3) / 4), dim3(256), 0, S, x, delta, gamma, beta, xout, y, stats, M, E, DropSite{});
+  else
+    hipLaunchKernelGGL((ln_fwd_kernel<false, kMaxEPL2>), dim3((M + 3) / 4), dim3(256), 0, S, x, delta, gamma, beta, xout, y, stats, M, E, DropSite{});
   DONE();
 }
 
@@ -1901,7 +2317,7 @@ static bool drop_site(const osrl_dropout_t* dr, DropSite* d) {
 int osrl_layernorm_fwd_drop(const float* x, const float* delta, const osrl_dropout_t* drop, const float* gamma,
                             const float* beta, float* xout, float* y, float* stats, int32_t M, int32_t E,
                             void* stream) {
-  if (!x || !delta || !gamma || !beta || !y || !stats || M < 1 || E < 1 || E > 64 * kMaxEPL) return -1;
+  if (!x || !delta || !gamma || !beta || !y || !stats || M < 1 || E < 1 || E > 64 * kMaxEPL2) return -1;
   DropSite d{};
   // p = 0 (or no descriptor): the plain call.  p >= 1 would have to zero the branch (torch does) while the backward's
   // twin rejects it: both reject it -- no reference config drops everything, the engine validates p < 1
@@ -1917,15 +2333,17 @@ int osrl_layernorm_fwd_drop(const float* x, const float* delta, const osrl_dropo
                          stats, M, d);
     DONE();
   }
-  hipLaunchKernelGGL(ln_fwd_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, S, x, delta, gamma, beta, xout, y, stats, M, E,
-                     d);
+  if (E <= 64 * kMaxEPL)
+    hipLaunchKernelGGL((ln_fwd_kernel<true, kMaxEPL>), dim3((M + 3) / 4), dim3(256), 0, S, x, delta, gamma, beta, xout, y, stats, M, E, d);
+  else
+    hipLaunchKernelGGL((ln_fwd_kernel<true, kMaxEPL2>), dim3((M + 3) / 4), dim3(256), 0, S, x, delta, gamma, beta, xout, y, stats, M, E, d);
   DONE();
 }
 
 int osrl_layernorm_bwd(const float* dy, const float* x, const float* stats, const float* gamma, const float* dres,
                        float* dx, float* partial_ws, int32_t n_parts, int32_t M, int32_t E, float* slab,
                        int64_t g_off, int64_t b_off, void* stream) {
-  if (!dy || !x || !stats || !gamma || !dx || !partial_ws || n_parts < 1 || M < 1 || E > 64 * kMaxEPL)
+  if (!dy || !x || !stats || !gamma || !dx || !partial_ws || n_parts < 1 || M < 1 || E > 64 * kMaxEPL2)
     return -1;
   CLEAR();
   if (ln_v4_ok(E, dy, x, gamma, dres, dx, dx)) {
@@ -1936,8 +2354,12 @@ int osrl_layernorm_bwd(const float* dy, const float* x, const float* stats, cons
       hipLaunchKernelGGL((ln_bwd_v4_kernel<false, 2>), dim3(n_parts), dim3(256), 0, S, dy, x, stats, gamma, dres, dx,
                          partial_ws, M, nullptr, DropSite{}, n_parts);
   } else
-  hipLaunchKernelGGL(ln_bwd_kernel<false>, dim3(n_parts), dim3(256), 0, S, dy, x, stats, gamma, dres, dx, partial_ws, M,
-                     E, nullptr, DropSite{});
+  if (E <= 64 * kMaxEPL)
+    hipLaunchKernelGGL((ln_bwd_kernel<false, kMaxEPL>), dim3(n_parts), dim3(256), 0, S, dy, x, stats, gamma, dres, dx,
+                       partial_ws, M, E, nullptr, DropSite{});
+  else
+    hipLaunchKernelGGL((ln_bwd_kernel<false, kMaxEPL2>), dim3(n_parts), dim3(256), 0, S, dy, x, stats, gamma, dres, dx,
+                       partial_ws, M, E, nullptr, DropSite{});
   if (slab)
     hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * E + 63) / 64), dim3(1024), 0, S, partial_ws, n_parts, E, slab,
                        g_off, b_off);
@@ -1964,7 +2386,7 @@ int osrl_layernorm_bwd_drop(const float* dy, const float* x, const float* stats,
                             float* dx, float* dx_dropped, const osrl_dropout_t* drop, float* partial_ws, int32_t n_parts,
                             int32_t M, int32_t E, float* slab, int64_t g_off, int64_t b_off, void* stream) {
   if (!dy || !x || !stats || !gamma || !dx || !dx_dropped || !partial_ws || n_parts < 1 || M < 1 ||
-      E > 64 * kMaxEPL)
+      E > 64 * kMaxEPL2)
     return -1;
   DropSite d{};
   if (!drop_site(drop, &d)) return -1;
@@ -1977,8 +2399,12 @@ int osrl_layernorm_bwd_drop(const float* dy, const float* x, const float* stats,
       hipLaunchKernelGGL((ln_bwd_v4_kernel<true, 2>), dim3(n_parts), dim3(256), 0, S, dy, x, stats, gamma, dres, dx,
                          partial_ws, M, dx_dropped, d, n_parts);
   } else
-  hipLaunchKernelGGL(ln_bwd_kernel<true>, dim3(n_parts), dim3(256), 0, S, dy, x, stats, gamma, dres, dx, partial_ws, M, E,
-                     dx_dropped, d);
+  if (E <= 64 * kMaxEPL)
+    hipLaunchKernelGGL((ln_bwd_kernel<true, kMaxEPL>), dim3(n_parts), dim3(256), 0, S, dy, x, stats, gamma, dres, dx,
+                       partial_ws, M, E, dx_dropped, d);
+  else
+    hipLaunchKernelGGL((ln_bwd_kernel<true, kMaxEPL2>), dim3(n_parts), dim3(256), 0, S, dy, x, stats, gamma, dres, dx,
+                       partial_ws, M, E, dx_dropped, d);
   if (slab)
     hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * E + 63) / 64), dim3(1024), 0, S, partial_ws, n_parts, E, slab,
                        g_off, b_off);
@@ -2089,6 +2515,57 @@ int osrl_attention_bwd_keep(const float* qkv, const float* mask, const float* do
   else
     hipLaunchKernelGGL(attn_bwd_kernel<8>, dim3(B * H), dim3(256), lds, S, a);
   DONE();
+}
+
+// ---- the tiled kernels (long sequences, wide heads) -------------------------------------------------------------------
+constexpr int kAttnMaxS = 1024, kAttnMaxD = 128;
+static bool attn_tiled_ok(int32_t B, int32_t S_, int32_t E, int32_t H, int32_t rep, int32_t prefix) {
+  return B >= 1 && S_ >= 1 && S_ <= kAttnMaxS && H >= 1 && E >= H && E % H == 0 && E / H <= kAttnMaxD && rep >= 1 &&
+         S_ - prefix >= rep && (S_ - prefix) % rep == 0;
+}
+// what the current entry points (osrl_attention_fwd / _bwd and their _keep forms) take
+static bool attn_old_ok(int32_t S_, int32_t E, int32_t H) {
+  return S_ >= 1 && S_ <= 128 && H >= 1 && E % H == 0 && E / H <= 64 && attn_lds(S_, E / H, true) <= kMaxLds;
+}
+
+int64_t osrl_attention_tiled_ws_bytes(int32_t B, int32_t S_, int32_t E, int32_t H) {
+  if (!attn_tiled_ok(B, S_, E, H, 1, 0)) return 0;
+  return (int64_t)sizeof(float) * B * H * S_;
+}
+
+int64_t osrl_attention_tiled_lds_bytes(int32_t head_dim, int32_t pass) {
+  if (head_dim < 1 || head_dim > kAttnMaxD || pass < 0 || pass > 2) return 0;
+  const int w = pass;
+  if (head_dim <= 16) return (int64_t)attn_t_lds<16>(w);
+  if (head_dim <= 32) return (int64_t)attn_t_lds<32>(w);
+  if (head_dim <= 64) return (int64_t)attn_t_lds<64>(w);
+  return (int64_t)attn_t_lds<128>(w);
+}
+
+int64_t osrl_attention_ws_bytes(int32_t B, int32_t S_, int32_t E, int32_t H) {
+  if (attn_old_ok(S_, E, H)) return 0;
+  return osrl_attention_tiled_ws_bytes(B, S_, E, H);
+}
+
+int osrl_attention_fwd_ws(const float* qkv, const float* mask, int32_t B, int32_t S_, int32_t E, int32_t H, int32_t rep,
+                          int32_t prefix, const osrl_dropout_t* drop, float* o, float* lse, void* stream) {
+  prefix = prefix ? 1 : 0;
+  if (!qkv || !mask || !o || !attn_tiled_ok(B, S_, E, H, rep, prefix)) return -1;
+  AttnArgs a{qkv, mask, o, nullptr, nullptr, B, S_, E, H, rep, prefix};
+  if (!attn_drop_args(drop, &a)) return -1;
+  a.keep = nullptr;
+  return attn_launch_tiled(a, nullptr, lse, nullptr, true, S);
+}
+
+int osrl_attention_bwd_ws(const float* qkv, const float* mask, const float* dout, int32_t B, int32_t S_, int32_t E,
+                          int32_t H, int32_t rep, int32_t prefix, const osrl_dropout_t* drop, const float* o,
+                          const float* lse, float* ws, float* dqkv, void* stream) {
+  prefix = prefix ? 1 : 0;
+  if (!qkv || !mask || !dout || !o || !lse || !ws || !dqkv || !attn_tiled_ok(B, S_, E, H, rep, prefix)) return -1;
+  AttnArgs a{qkv, mask, nullptr, dout, dqkv, B, S_, E, H, rep, prefix};
+  if (!attn_drop_args(drop, &a)) return -1;
+  a.keep = nullptr;
+  return attn_launch_tiled(a, o, const_cast<float*>(lse), ws, false, S);
 }
 
 int osrl_gelu_fwd(const float* x, float* y, int64_t n, void* stream) {

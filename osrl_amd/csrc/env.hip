@@ -110,8 +110,23 @@ struct CdtWin {
   int E, T, od, ad;
 };
 
-// after the env step: store the action taken, append (s', R - r, C - c, t+1) -- sliding the window when it is full
-__global__ __launch_bounds__(256) void cdt_push_kernel(CdtWin w, const float* __restrict__ act,
+// in-place left shift dst[i] = dst[sh + i], i < n, through registers: chunks of blockDim elements, each read completely
+// before any of it is written (a chunk's sources lie past everything written so far) -- for windows whose slide does not
+// fit the LDS staging of cdt_push_kernel
+__device__ __forceinline__ void slide_left(float* p, int sh, int n) {
+  for (int c = 0; c < n; c += blockDim.x) {
+    const int i = c + (int)threadIdx.x;
+    const float v = i < n ? p[sh + i] : 0.f;
+    __syncthreads();
+    if (i < n) p[i] = v;
+    __syncthreads();
+  }
+}
+
+// after the env step: store the action taken, append (s', R - r, C - c, t+1) -- sliding the window when it is full.
+// LDS_SLIDE: the rows 1..T-1 are staged through (T-1)*(od+ad) floats of dynamic LDS; otherwise slid through registers
+template <bool LDS_SLIDE>
+__global__ __launch_bounds__(LDS_SLIDE ? 256 : 1024) void cdt_push_kernel(CdtWin w, const float* __restrict__ act,
                                                        const float* __restrict__ obs, int obs_ld,
                                                        const float* __restrict__ step_out, float cost_scale,
                                                        int cost_reverse, const int* __restrict__ cursor,
@@ -137,8 +152,13 @@ __global__ __launch_bounds__(256) void cdt_push_kernel(CdtWin w, const float* __
   if (n == T) {  // full window: slide rows 1..T-1 to 0..T-2 (staged through LDS: source and target overlap)
     float* sb = buf;
     float* ab = buf + (size_t)(T - 1) * od;
-    for (int i = t; i < (T - 1) * od; i += blockDim.x) sb[i] = S[od + i];
-    for (int i = t; i < (T - 1) * ad; i += blockDim.x) ab[i] = A[ad + i];
+    if (LDS_SLIDE) {
+      for (int i = t; i < (T - 1) * od; i += blockDim.x) sb[i] = S[od + i];
+      for (int i = t; i < (T - 1) * ad; i += blockDim.x) ab[i] = A[ad + i];
+    } else {
+      slide_left(S, od, (T - 1) * od);
+      slide_left(A, ad, (T - 1) * ad);
+    }
     float rr = 0.f, cc = 0.f;
     int64_t ts = 0;
     if (t < T - 1) {
@@ -147,8 +167,10 @@ __global__ __launch_bounds__(256) void cdt_push_kernel(CdtWin w, const float* __
       ts = TS[t + 1];
     }
     __syncthreads();
-    for (int i = t; i < (T - 1) * od; i += blockDim.x) S[i] = sb[i];
-    for (int i = t; i < (T - 1) * ad; i += blockDim.x) A[i] = ab[i];
+    if (LDS_SLIDE) {
+      for (int i = t; i < (T - 1) * od; i += blockDim.x) S[i] = sb[i];
+      for (int i = t; i < (T - 1) * ad; i += blockDim.x) A[i] = ab[i];
+    }
     if (t < T - 1) {
       R[t] = rr;
       C[t] = cc;
@@ -202,14 +224,18 @@ extern "C" int osrl_cdt_rollout_push(float* states, float* actions, float* retur
                                      int32_t obs_ld, const float* step_out, float cost_scale, int32_t cost_reverse,
                                      int32_t* cursor, int32_t episode_len, void* stream) {
   if (!states || !actions || !returns || !costs_to_go || !time_steps || !mask || !act || !obs || !step_out || !cursor ||
-      episodes < 1 || seq_len < 1 || seq_len > 256 || state_dim < 1 || action_dim < 1 || obs_ld < state_dim)
+      episodes < 1 || seq_len < 1 || seq_len > 1024 || state_dim < 1 || action_dim < 1 || obs_ld < state_dim)
     return -1;
   const size_t lds = (size_t)(seq_len - 1) * (state_dim + action_dim) * sizeof(float);
-  if (lds > 64 * 1024) return -1;
   (void)hipGetLastError();
   CdtWin w{states, actions, returns, costs_to_go, time_steps, mask, episodes, seq_len, state_dim, action_dim};
-  hipLaunchKernelGGL(cdt_push_kernel, dim3(episodes), dim3(256), lds, (hipStream_t)stream, w, act, obs, obs_ld,
-                     step_out, cost_scale, cost_reverse, cursor, episode_len);
+  // (the rows' thread t < T - 1 carries R / C / time step t + 1 of the slide: 256 threads cover T <= 257)
+  if (lds <= 64 * 1024 && seq_len <= 256)
+    hipLaunchKernelGGL(cdt_push_kernel<true>, dim3(episodes), dim3(256), lds, (hipStream_t)stream, w, act, obs, obs_ld,
+                       step_out, cost_scale, cost_reverse, cursor, episode_len);
+  else
+    hipLaunchKernelGGL(cdt_push_kernel<false>, dim3(episodes), dim3(1024), 0, (hipStream_t)stream, w, act, obs, obs_ld,
+                       step_out, cost_scale, cost_reverse, cursor, episode_len);
   hipLaunchKernelGGL(cursor_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, cursor, episode_len);
   return (int)hipGetLastError();
 }

@@ -1130,6 +1130,102 @@ __global__ __launch_bounds__(256) void linear_kernel(const LinArgs a) {
   }
 }
 
+// K > 1024 (the CDT's MLP down-projection and its dX GEMM at embedding_dim > 256: K = 4E up to 4096): linear_kernel with
+// the activation tile staged in 1024-column chunks.  One workgroup accumulates every chunk into the same registers --
+// no split-K, no atomics; per chunk: stage A[row0 : row0+16, k0 : k0+1024] -> LDS, then the same weight-streaming MFMA
+// loop (layer_prefetch / layer_run) over the chunk's rows of the packed weights (P + k0 * Np).
+constexpr int kLinKChunk = 1024, kLinMaxK = 4096;
+constexpr size_t kLinKChunkLds = sizeof(float) * 16 * (kLinKChunk + 8);  // one 16-row chunk of A
+static_assert(kLinKChunkLds <= 160 * 1024, "linear_kchunk_kernel: LDS per workgroup");
+template <int NCB>
+__global__ __launch_bounds__(256) void linear_kchunk_kernel(const LinArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int BM = 16;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int row0 = blockIdx.x * BM, M = a.M, K = a.K, N = a.N, lda = a.lda;
+  const int nblk_tot = (N + 15) >> 4;
+  constexpr int GB = 4 * NCB;
+  const int gb0 = blockIdx.y * GB;
+  int nblk = nblk_tot - gb0;
+  nblk = nblk > GB ? GB : nblk;
+  int cb0 = 0, cnt = 0;
+  wave_blocks(nblk, wave, &cb0, &cnt);
+  const bool vec = ((K & 3) == 0) && ((a.lda_g & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.A) & 15) == 0);
+  f32x4 ring[kRing][NCB];
+  f32x4 acc[1][NCB];
+  zero_acc<1, NCB>(acc);
+  const int cl = tid & 15, rl = tid >> 4;  // 16 rows x 16 lanes
+  const int gr = row0 + rl;
+  const bool rok = gr < M;
+  const float* __restrict__ src = a.A + (size_t)(rok ? gr : M - 1) * a.lda_g;
+  for (int k0 = 0; k0 < K; k0 += kLinKChunk) {
+    const int kc = K - k0 < kLinKChunk ? K - k0 : kLinKChunk, kcp = round16(kc), nk = kcp >> 4;
+    __syncthreads();  // every wave is done reading the previous chunk
+    if (vec) {
+      for (int cbase = 0; cbase < kcp; cbase += 64 * 4) {
+        f32x4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int c = cbase + j * 64 + cl * 4;
+          const bool ok = rok && c < kc;
+          v[j] = *reinterpret_cast<const f32x4*>(src + k0 + (ok ? c : 0));
+          if (!ok) v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int c = cbase + j * 64 + cl * 4;
+          if (c < kcp) *reinterpret_cast<f32x4*>(lds + rl * lda + c) = v[j];
+        }
+      }
+    } else {
+      for (int cbase = 0; cbase < kcp; cbase += 16 * 8) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int c = cbase + j * 16 + cl;
+          const bool ok = rok && c < kc;
+          v[j] = src[k0 + (ok ? c : 0)];
+          v[j] = ok ? v[j] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int c = cbase + j * 16 + cl;
+          if (c < kcp) lds[rl * lda + c] = v[j];
+        }
+      }
+    }
+    __syncthreads();
+    if (cnt > 0) {
+      const float* __restrict__ Pk = a.P + (size_t)k0 * a.Np;
+      layer_prefetch<1, NCB>(ring, nk, Pk, a.Np, a.col0 + (gb0 + cb0) * 16, cnt);
+      layer_run<1, NCB>(lds, lda, nk, Pk, a.Np, a.col0 + (gb0 + cb0) * 16, cnt, acc, ring);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < NCB; ++c) {
+    if (c < cnt) {
+      const int col = (cb0 + c) * 16 + (lane & 15);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) lds[((lane >> 4) * 4 + r) * lda + col] = acc[0][c][r];
+    }
+  }
+  __syncthreads();
+  const int ncols = (nblk * 16 < N - gb0 * 16) ? nblk * 16 : N - gb0 * 16;
+  const int gcol0 = gb0 * 16;
+  for (int idx = tid; idx < BM * ncols; idx += 256) {
+    const int r = idx / ncols, c = idx - r * ncols;
+    const int g = row0 + r;
+    if (g < M) {
+      float v = lds[r * lda + c];
+      if (a.bias) v += a.bias[gcol0 + c];
+      if (a.resid) v += a.resid[(size_t)g * a.ldr + gcol0 + c];
+      a.Y[(size_t)g * a.ldy + gcol0 + c] = v;
+    }
+  }
+}
+
 // ---- weight packing ------------------------------------------------------------------------------
 // ---- big-M linear layer: both operands staged through LDS ------------------------------------------------
 // linear_kernel keeps the whole [BM, K] activation tile in LDS and streams the packed weights from L2 into
@@ -2292,10 +2388,36 @@ static int launch_linear_tiles(const float* A, int64_t lda, int32_t M, int32_t K
   return (int)hipGetLastError();
 }
 
+// K > 1024: the chunked tile kernel (16-row tiles, the column-group choice of launch_linear_tiles)
+static int launch_linear_kchunk(const float* A, int64_t lda, int32_t M, int32_t K, const float* P, int32_t Np, int32_t col0,
+                                int32_t N, const float* bias, const float* resid, int64_t ldr, float* Y, int64_t ldy,
+                                void* stream) {
+  LinArgs a;
+  a.A = A; a.P = P; a.bias = bias; a.resid = resid; a.Y = Y;
+  a.lda_g = lda; a.ldr = ldr; a.ldy = ldy;
+  a.M = M; a.K = K; a.N = N; a.Np = Np; a.col0 = col0;
+  const int nblk = (N + 15) / 16;
+  const int ncb = nblk >= 16 ? 4 : ((nblk + 3) / 4 <= 1 ? 1 : (nblk + 3) / 4 <= 2 ? 2 : (nblk + 3) / 4 <= 4 ? 4 : 7);
+  a.lda = kLinKChunk + 8;  // >= every column group's 16 * 4 * ncb <= 448 output columns
+  const size_t lds_bytes = kLinKChunkLds;
+  dim3 grid((M + 15) / 16, (nblk + 4 * ncb - 1) / (4 * ncb), 1);
+  (void)hipGetLastError();
+#define OSRL_LINK_LAUNCH(C)                                                                                     \
+  do {                                                                                                          \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(linear_kchunk_kernel<C>),                          \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                      \
+    hipLaunchKernelGGL((linear_kchunk_kernel<C>), grid, dim3(256), lds_bytes, (hipStream_t)stream, a);         \
+  } while (0)
+  if (ncb == 1) OSRL_LINK_LAUNCH(1); else if (ncb == 2) OSRL_LINK_LAUNCH(2); else if (ncb == 4) OSRL_LINK_LAUNCH(4);
+  else OSRL_LINK_LAUNCH(7);
+#undef OSRL_LINK_LAUNCH
+  return (int)hipGetLastError();
+}
+
 extern "C" int osrl_linear(const float* A, int64_t lda, int32_t M, int32_t K, const float* P, int32_t Np, int32_t col0,
                            int32_t N, const float* bias, const float* resid, int64_t ldr, float* Y, int64_t ldy,
                            void* stream) {
-  if (!A || !P || !Y || M < 1 || K < 1 || K > 1024 || N < 1 || Np < 16) return -1;
+  if (!A || !P || !Y || M < 1 || K < 1 || K > kLinMaxK || N < 1 || Np < 16) return -1;
   if (M >= 4096 && (K & 15) == 0 && (N & 255) == 0 && (lda & 3) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0) {
     LinBigArgs b;
     b.A = A; b.P = P; b.bias = bias; b.resid = resid; b.Y = Y;
@@ -2362,8 +2484,11 @@ extern "C" int osrl_linear(const float* A, int64_t lda, int32_t M, int32_t K, co
                          (hipStream_t)stream, b);
     return (int)hipGetLastError();
   }
+  if (K > 1024) return launch_linear_kchunk(A, lda, M, K, P, Np, col0, N, bias, resid, ldr, Y, ldy, stream);
   return launch_linear_tiles(A, lda, M, K, P, Np, col0, N, bias, resid, ldr, Y, ldy, stream);
 }
+
+extern "C" int64_t osrl_linear_kchunk_lds_bytes(void) { return (int64_t)kLinKChunkLds; }
 
 extern "C" int osrl_pack_weights(const float* src_flat, float* pf, float* pb, const osrl_pack_entry_t* d_entries,
                                  int32_t n_entries, int32_t max_elems, void* stream) {

@@ -25,6 +25,8 @@ from .core import DwPlan, FlatGroup, StepState, capture_step, cur_stream, load_i
 LN_BATCH = _plan.knob("OSRL_CDT_LN_BATCH", "1", "CDT: the LayerNorm parameter reductions of a step in one launch") == "1"
 ATTN_KEEP = _plan.knob("OSRL_CDT_ATTN_KEEP", "1", "CDT: attention dropout decisions handed from forward to backward") == "1"
 SLAB_COUNTS = _plan.knob("OSRL_CDT_SLAB_COUNTS", "1", "CDT: gradient slabs summed per range by its own split count") == "1"
+ATTN_TILED = _plan.knob("OSRL_CDT_ATTN_TILED", "0", "CDT: the tiled attention kernels (osrl_attention_*_ws) also for shapes "
+                        "the register-tile kernels take (A/B comparison)") == "1"
 FUSE_DROP = _plan.knob("OSRL_CDT_FUSE_DROP", "1", "residual-branch dropout inside the LayerNorm launches") == "1"  # residual-branch dropout inside the LayerNorm launches
 STAT_KEYS = ["nll", "ent", "ent_reg", "all_loss", "act_loss", "cost_loss", "cost_acc", "state_loss", "train_lr"]
 
@@ -75,6 +77,20 @@ class CDTEngine:
         kb = int(L.load().osrl_attention_keep_bytes(B, self.S, E, self.H)) if (ATTN_KEEP and not inference) else 0
         if kb > 0 and m.attention_dropout > 0:
             self.attn_keep = [torch.zeros(kb, dtype=torch.uint8, device=dev) for _ in range(NL)]
+        # long sequences / wide heads (S > 128 or head_dim > 64): the tiled attention kernels, which keep per-row softmax
+        # statistics (lse, per layer, from the forward to the backward) and a row-dot workspace -- sized by the library's
+        # own queries and allocated only where the shape needs them (or the lab switch asks for them)
+        lib = L.load()
+        ws_b = int(lib.osrl_attention_ws_bytes(B, self.S, E, self.H))
+        if ws_b == 0 and ATTN_TILED:
+            ws_b = int(lib.osrl_attention_tiled_ws_bytes(B, self.S, E, self.H))
+        self.attn_tiled = ws_b > 0
+        self.attn_lse, self.attn_ws = None, None
+        if self.attn_tiled:
+            self.attn_keep = None  # (the keep hand-off belongs to the register-tile kernels)
+            if not inference:
+                self.attn_lse = [torch.zeros(ws_b // 4, **f) for _ in range(NL)]
+                self.attn_ws = torch.zeros(ws_b // 4, **f)
         self.o = [z(M, E) for _ in range(NL)]
         self.att = z(M, E)
         self.xmid = [z(M, E) for _ in range(NL)]
@@ -345,10 +361,16 @@ class CDTEngine:
                 self._ln_fwd(self.xin[0], None, p + "norm1", None, self.n1[0], self.st1[0])
             self._lin(self.n1[l], E, M, p + "attention.in_proj_weight", self.qkv[l], 3 * E)
             da = self._site(1 + 3 * l, p_attn)
-            keep = self.attn_keep[l].data_ptr() if (train and self.attn_keep is not None and p_attn > 0) else None
-            L.check(lib.osrl_attention_fwd_keep(self.qkv[l].data_ptr(), self.mask.data_ptr(), self.B, self.S, E, self.H,
-                                                self.R, self.P, ctypes.byref(da) if p_attn > 0 else None,
-                                                self.o[l].data_ptr(), keep, cur_stream()), "osrl_attention_fwd")
+            if self.attn_tiled:
+                lse = self.attn_lse[l].data_ptr() if (train and self.attn_lse is not None) else None
+                L.check(lib.osrl_attention_fwd_ws(self.qkv[l].data_ptr(), self.mask.data_ptr(), self.B, self.S, E, self.H,
+                                                  self.R, self.P, ctypes.byref(da) if p_attn > 0 else None,
+                                                  self.o[l].data_ptr(), lse, cur_stream()), "osrl_attention_fwd_ws")
+            else:
+                keep = self.attn_keep[l].data_ptr() if (train and self.attn_keep is not None and p_attn > 0) else None
+                L.check(lib.osrl_attention_fwd_keep(self.qkv[l].data_ptr(), self.mask.data_ptr(), self.B, self.S, E,
+                                                    self.H, self.R, self.P, ctypes.byref(da) if p_attn > 0 else None,
+                                                    self.o[l].data_ptr(), keep, cur_stream()), "osrl_attention_fwd")
             self._lin(self.o[l], E, M, p + "attention.out_proj.weight", self.att, E)
             self._ln_fwd(self.xin[l], self.att, p + "norm2", self.xmid[l], self.n2[l], self.st2[l],
                          drop=(2 + 3 * l, p_res))
@@ -458,11 +480,18 @@ class CDTEngine:
                          drop=(2 + 3 * l, self.p_res), dx_dropped=self.datt[l])
             self._lin_dx(self.datt[l], E, M, p + "attention.out_proj.weight", self.do, E)
             da = self._site(1 + 3 * l, self.p_attn)
-            keep = self.attn_keep[l].data_ptr() if (self.attn_keep is not None and self.p_attn > 0) else None
-            L.check(lib.osrl_attention_bwd_keep(self.qkv[l].data_ptr(), self.mask.data_ptr(), self.do.data_ptr(), self.B,
-                                                self.S, E, self.H, self.R, self.P,
-                                                ctypes.byref(da) if self.p_attn > 0 else None,
-                                                self.dqkv[l].data_ptr(), keep, cur_stream()), "attn_bwd")
+            if self.attn_tiled:
+                L.check(lib.osrl_attention_bwd_ws(self.qkv[l].data_ptr(), self.mask.data_ptr(), self.do.data_ptr(), self.B,
+                                                  self.S, E, self.H, self.R, self.P,
+                                                  ctypes.byref(da) if self.p_attn > 0 else None, self.o[l].data_ptr(),
+                                                  self.attn_lse[l].data_ptr(), self.attn_ws.data_ptr(),
+                                                  self.dqkv[l].data_ptr(), cur_stream()), "attn_bwd_ws")
+            else:
+                keep = self.attn_keep[l].data_ptr() if (self.attn_keep is not None and self.p_attn > 0) else None
+                L.check(lib.osrl_attention_bwd_keep(self.qkv[l].data_ptr(), self.mask.data_ptr(), self.do.data_ptr(),
+                                                    self.B, self.S, E, self.H, self.R, self.P,
+                                                    ctypes.byref(da) if self.p_attn > 0 else None,
+                                                    self.dqkv[l].data_ptr(), keep, cur_stream()), "attn_bwd")
             self._lin_dx(self.dqkv[l], 3 * E, M, p + "attention.in_proj_weight", self.dn, E)
             if l > 0:
                 self._ln_bwd(self.dn, self.xin[l], self.st1[l], p + "norm1", self.dxm[l], self.dxo[l],

@@ -1,0 +1,575 @@
+"""CDT at long sequences and wide embeddings (S <= 1024 tokens, embedding_dim <= 1024, head_dim <= 128): the tiled attention
+kernels (osrl_attention_*_ws), osrl_linear with K up to 4096, the 16-features-per-lane row kernels and the long rollout
+window -- against fp64 numpy and the numpy oracle (oracle/cdt_oracle.py)."""
+import ctypes as C
+import dataclasses
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from cases import CDT_CASES, CDTCase, make_cdt_batch
+from test_gpu_cdt import C5_SLICE, build_cdt_gpu
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def t(x):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
+
+
+def _attn_problem(B, S, E, H, rep, prefix, seed):
+    rs = np.random.RandomState(seed)
+    T = (S - prefix) // rep
+    qkv = (0.7 * rs.randn(B, S, 3 * E)).astype(np.float32)
+    mk = np.ones((B, T), np.float32)
+    for b in range(B):
+        pad = int(rs.randint(0, max(T - 1, 1)))
+        if b % 3 == 0:
+            mk[b, T - pad:] = 0
+        elif b % 3 == 1:
+            mk[b, :pad] = 0
+    if B > 3:
+        mk[3] = 0  # a fully padded sample: every row without a valid key
+    do = rs.randn(B, S, E).astype(np.float32)
+    return qkv, mk, do
+
+
+def _attn_ref(qkv, mk, do, B, S, E, H, rep, prefix, Mk):
+    d = E // H
+    key_ok = np.repeat(mk > 0, rep, 1)
+    if prefix:
+        key_ok = np.concatenate([key_ok[:, :1], key_ok], 1)
+    q64 = qkv.astype(np.float64)
+    q, k, v = (q64[..., i * E:(i + 1) * E].reshape(B, S, H, d).transpose(0, 2, 1, 3) for i in range(3))
+    blocked = np.triu(np.ones((S, S), bool), 1)[None, None] | ~key_ok[:, None, None, :]
+    sc = np.where(blocked, -np.inf, q @ k.transpose(0, 1, 3, 2) / math.sqrt(d))
+    mx = sc.max(-1, keepdims=True)
+    dead = ~np.isfinite(mx)
+    P = np.exp(sc - np.where(dead, 0.0, mx))
+    P = np.where(dead, 0.0, P / np.where(dead, 1.0, P.sum(-1, keepdims=True)))
+    Pd = P * Mk
+    oref = (Pd @ v).transpose(0, 2, 1, 3).reshape(B, S, E)
+    dO = do.astype(np.float64).reshape(B, S, H, d).transpose(0, 2, 1, 3)
+    dP = (dO @ v.transpose(0, 1, 3, 2)) * Mk
+    dv = Pd.transpose(0, 1, 3, 2) @ dO
+    dS = P * (dP - (dP * P).sum(-1, keepdims=True))
+    dq, dk = dS @ k / math.sqrt(d), dS.transpose(0, 1, 3, 2) @ q / math.sqrt(d)
+    ref = np.concatenate([x.transpose(0, 2, 1, 3).reshape(B, S, E) for x in (dq, dk, dv)], -1)
+    return oref, ref
+
+
+def _run_tiled(lib, L, qt, mt, dot, B, S, E, H, rep, prefix, drp, cur_stream):
+    n = int(lib.osrl_attention_tiled_ws_bytes(B, S, E, H)) // 4
+    assert n == B * H * S
+    o, dqkv = torch.full((B, S, E), 7.0, device=DEV), torch.full((B, S, 3 * E), 7.0, device=DEV)
+    lse, ws = torch.full((n,), 7.0, device=DEV), torch.full((n,), 7.0, device=DEV)
+    L.check(lib.osrl_attention_fwd_ws(qt.data_ptr(), mt.data_ptr(), B, S, E, H, rep, prefix, drp, o.data_ptr(),
+                                      lse.data_ptr(), cur_stream()), "fwd_ws")
+    o_inf = torch.full((B, S, E), 7.0, device=DEV)  # inference form: no statistics
+    L.check(lib.osrl_attention_fwd_ws(qt.data_ptr(), mt.data_ptr(), B, S, E, H, rep, prefix, drp, o_inf.data_ptr(),
+                                      None, cur_stream()), "fwd_ws inference")
+    L.check(lib.osrl_attention_bwd_ws(qt.data_ptr(), mt.data_ptr(), dot.data_ptr(), B, S, E, H, rep, prefix, drp,
+                                      o.data_ptr(), lse.data_ptr(), ws.data_ptr(), dqkv.data_ptr(), cur_stream()),
+            "bwd_ws")
+    assert torch.equal(o, o_inf)
+    return o, dqkv
+
+
+def _mask(lib, L, drp, B, H, S, cur_stream):
+    Sp = (S + 15) // 16 * 16
+    raw, ones = torch.empty(B * H, S, Sp, device=DEV), torch.ones(B * H, S, Sp, device=DEV)
+    L.check(lib.osrl_dropout(ones.data_ptr(), raw.data_ptr(), raw.numel(), drp, cur_stream()), "m")
+    return raw.cpu().numpy()[:, :, :S].reshape(B, H, S, S).astype(np.float64)
+
+
+@pytest.mark.parametrize("S,d,rep,prefix,p", [
+    (129, 16, 3, 0, 0.1), (129, 128, 3, 0, 0.0), (200, 32, 4, 0, 0.1), (200, 64, 4, 0, 0.0), (257, 64, 4, 1, 0.1),
+    (257, 128, 2, 1, 0.0), (512, 32, 2, 0, 0.1), (512, 128, 4, 0, 0.1), (1024, 64, 4, 0, 0.0), (1024, 16, 2, 0, 0.1),
+    (160, 48, 4, 0, 0.1), (144, 80, 3, 0, 0.0)])
+def test_tiled_attention_matches_fp64(S, d, rep, prefix, p):
+    """Tiled forward / backward vs fp64 numpy: tail and front key padding, a fully padded sample (zero rows), the
+    cost-prefix token, probability dropout with the mask osrl_dropout exports, head widths 16-128 (48 / 80: zero-padded
+    to 64 / 128)."""
+    from osrl_amd import _lib as L
+    from osrl_amd.engine.core import StepState, cur_stream
+    lib = L.load()
+    st = StepState(torch.device(DEV), ["x"])
+    st.tick()
+    H = 2
+    E, B = H * d, (5 if S <= 512 else 4)
+    qkv, mk, do = _attn_problem(B, S, E, H, rep, prefix, S * 7 + d)
+    qt, mt, dot = t(qkv), t(mk), t(do)
+    dr = L.DropoutT(p, 9, 13, st.ptr)
+    drp = C.byref(dr) if p > 0 else None
+    o, dqkv = _run_tiled(lib, L, qt, mt, dot, B, S, E, H, rep, prefix, drp, cur_stream)
+    Mk = _mask(lib, L, drp, B, H, S, cur_stream) if p > 0 else np.ones((B, H, S, S))
+    oref, ref = _attn_ref(qkv, mk, do, B, S, E, H, rep, prefix, Mk)
+    assert np.abs(o.cpu().numpy() - oref).max() < 3e-5, "o"
+    assert np.abs(o.cpu().numpy()[3]).max() == 0.0, "a sample without a valid key gives zero rows"
+    g = dqkv.cpu().numpy()
+    assert np.abs(g - ref).max() < 5e-5 * max(1, np.abs(ref).max()), "dqkv"
+    assert np.abs(g[3]).max() == 0.0, "... and zero gradient"
+
+
+@pytest.mark.parametrize("S,E,H,rep,prefix,p", [(40, 128, 8, 4, 0, 0.1), (80, 256, 8, 4, 0, 0.1), (81, 128, 4, 4, 1, 0.2),
+                                                 (128, 256, 8, 2, 0, 0.1), (128, 512, 8, 4, 0, 0.0)])
+def test_tiled_attention_equals_register_tile_kernels_at_old_shapes(S, E, H, rep, prefix, p):
+    """At shapes the register-tile kernels take, the tiled ones compute the same (same gates) with the same dropout
+    decisions: the exported mask is the one both read, and the old pair's output under it is the reference too."""
+    from osrl_amd import _lib as L
+    from osrl_amd.engine.core import StepState, cur_stream
+    lib = L.load()
+    st = StepState(torch.device(DEV), ["x"])
+    st.tick()
+    B = 7
+    assert lib.osrl_attention_ws_bytes(B, S, E, H) == 0
+    qkv, mk, do = _attn_problem(B, S, E, H, rep, prefix, S + E)
+    qt, mt, dot = t(qkv), t(mk), t(do)
+    dr = L.DropoutT(p, 9, 13, st.ptr)
+    drp = C.byref(dr) if p > 0 else None
+    o_old, d_old = torch.zeros(B, S, E, device=DEV), torch.zeros(B, S, 3 * E, device=DEV)
+    L.check(lib.osrl_attention_fwd(qt.data_ptr(), mt.data_ptr(), B, S, E, H, rep, prefix, drp, o_old.data_ptr(),
+                                   cur_stream()), "fwd")
+    L.check(lib.osrl_attention_bwd(qt.data_ptr(), mt.data_ptr(), dot.data_ptr(), B, S, E, H, rep, prefix, drp,
+                                   d_old.data_ptr(), cur_stream()), "bwd")
+    o, dqkv = _run_tiled(lib, L, qt, mt, dot, B, S, E, H, rep, prefix, drp, cur_stream)
+    Mk = _mask(lib, L, drp, B, H, S, cur_stream) if p > 0 else np.ones((B, H, S, S))
+    oref, ref = _attn_ref(qkv, mk, do, B, S, E, H, rep, prefix, Mk)
+    for got_o, got_d, nm in ((o, dqkv, "tiled"), (o_old, d_old, "register-tile")):
+        assert np.abs(got_o.cpu().numpy() - oref).max() < 3e-5, (nm, "o")
+        assert np.abs(got_d.cpu().numpy() - ref).max() < 5e-5 * max(1, np.abs(ref).max()), (nm, "dqkv")
+    assert (o - o_old).abs().max().item() < 3e-5 and (dqkv - d_old).abs().max().item() < 5e-5 * max(1, np.abs(ref).max())
+
+
+@pytest.mark.parametrize("M", [300, 4096 + 128])
+@pytest.mark.parametrize("K", [1040, 2048, 3072, 4096])
+def test_linear_large_k_matches_fp64(M, K):
+    """osrl_linear with K > 1024 (the CDT MLP's K = 4E): forward pack with bias + residual, a column slice (col0), and
+    dX through the backward pack (its K is the layer's N); M below 4096 (the chunked tile kernel) and at / above it
+    (the LDS-tiled / persistent kernels)."""
+    from osrl_amd import _lib as L
+    from osrl_amd.engine.core import FlatGroup, cur_stream
+    lib = L.load()
+    rs = np.random.RandomState(K + M)
+    r16 = lambda x: (x + 15) // 16 * 16  # noqa: E731
+    gate = 3e-5 * K / 1024
+    for N in (256, 200):
+        g = FlatGroup("t", DEV)
+        g.add("w", (N, K))
+        g.mark_weight("w")
+        g.add("b", (N,))
+        g.finalize()
+        W = (rs.randn(N, K) * 0.03).astype(np.float32)
+        b = rs.randn(N).astype(np.float32)
+        g.view("w").copy_(t(W))
+        g.view("b").copy_(t(b))
+        g.repack()
+        A = rs.randn(M, K).astype(np.float32)
+        R = rs.randn(M, N).astype(np.float32)
+        At, Rt, Y = t(A), t(R), torch.zeros(M, N, device=DEV)
+        L.check(lib.osrl_linear(At.data_ptr(), K, M, K, g.pf.data_ptr(), r16(N), 0, N, g.view("b").data_ptr(),
+                                Rt.data_ptr(), N, Y.data_ptr(), N, cur_stream()), "lin")
+        ref = A.astype(np.float64) @ W.T.astype(np.float64) + b + R
+        assert np.abs(Y.cpu().numpy() - ref).max() < gate * max(1, np.abs(ref).max()), (M, K, N, "fwd")
+        # columns [col0, col0 + n) of the same packed weight
+        col0, n = 48, N - 64
+        bs = t(b[col0:col0 + n].copy())
+        Ys = torch.zeros(M, n, device=DEV)
+        L.check(lib.osrl_linear(At.data_ptr(), K, M, K, g.pf.data_ptr(), r16(N), col0, n, bs.data_ptr(), None, 0,
+                                Ys.data_ptr(), n, cur_stream()), "lin col0")
+        ref_s = A.astype(np.float64) @ W[col0:col0 + n].T.astype(np.float64) + b[col0:col0 + n]
+        assert np.abs(Ys.cpu().numpy() - ref_s).max() < gate * max(1, np.abs(ref_s).max()), (M, K, N, "col0")
+        # dX = dY W: a GEMM with K' = N and N' = K (the MLP dX of mlp.2 has K' = 4E: the transposed layer below)
+        dY = rs.randn(M, N).astype(np.float32)
+        dX = torch.zeros(M, K, device=DEV)
+        L.check(lib.osrl_linear(t(dY).data_ptr(), N, M, N, g.pb.data_ptr(), r16(K) + 16, 0, K, None, None, 0,
+                                dX.data_ptr(), K, cur_stream()), "lin dx")
+        ref = dY.astype(np.float64) @ W.astype(np.float64)
+        assert np.abs(dX.cpu().numpy() - ref).max() < 3e-5 * max(1, np.abs(ref).max()), (M, K, N, "dx")
+    # the backward pack with a K > 1024 contraction: layer [K, N] -> dX [M, N] from dY [M, K]
+    g = FlatGroup("t2", DEV)
+    g.add("w", (K, 256))
+    g.mark_weight("w")
+    g.finalize()
+    W = (rs.randn(K, 256) * 0.03).astype(np.float32)
+    g.view("w").copy_(t(W))
+    g.repack()
+    dY = rs.randn(M, K).astype(np.float32)
+    dX = torch.zeros(M, 256, device=DEV)
+    L.check(lib.osrl_linear(t(dY).data_ptr(), K, M, K, g.pb.data_ptr(), r16(256) + 16, 0, 256, None, None, 0,
+                            dX.data_ptr(), 256, cur_stream()), "lin dx big K")
+    ref = dY.astype(np.float64) @ W.astype(np.float64)
+    assert np.abs(dX.cpu().numpy() - ref).max() < gate * max(1, np.abs(ref).max()), (M, K, "dx K")
+
+
+def test_linear_persistent_kernel_at_large_k_matches_fp64():
+    """M = 16384, N = 512, K = 2048: 512 tiles of 128 x 128 (a whole number of rounds of the CUs) -- the persistent
+    kernel that carries the CDT MLP down-projection at user sizes, with and without the residual."""
+    from osrl_amd import _lib as L
+    from osrl_amd.engine.core import FlatGroup, cur_stream
+    lib = L.load()
+    rs = np.random.RandomState(77)
+    M, K, N = 16384, 2048, 512
+    g = FlatGroup("t", DEV)
+    g.add("w", (N, K))
+    g.mark_weight("w")
+    g.add("b", (N,))
+    g.finalize()
+    W = (rs.randn(N, K) * 0.03).astype(np.float32)
+    b = rs.randn(N).astype(np.float32)
+    g.view("w").copy_(t(W))
+    g.view("b").copy_(t(b))
+    g.repack()
+    A = rs.randn(M, K).astype(np.float32)
+    R = rs.randn(M, N).astype(np.float32)
+    At, Rt = t(A), t(R)
+    base = A.astype(np.float64) @ W.T.astype(np.float64) + b
+    for resid in (None, Rt):
+        Y = torch.zeros(M, N, device=DEV)
+        L.check(lib.osrl_linear(At.data_ptr(), K, M, K, g.pf.data_ptr(), N, 0, N, g.view("b").data_ptr(),
+                                None if resid is None else resid.data_ptr(), N, Y.data_ptr(), N, cur_stream()), "lin")
+        ref = base + (0 if resid is None else R)
+        assert np.abs(Y.cpu().numpy() - ref).max() < 3e-5 * K / 1024 * max(1, np.abs(ref).max()), resid is None
+
+
+@pytest.mark.parametrize("E", [640, 768, 1024])
+def test_wide_layernorm_kernels_match_oracle(E):
+    """The 16-features-per-lane LayerNorm kernels against oracle/cdt_oracle.py: forward (+ residual add) and backward
+    (+ dres, dgamma / dbeta through the slab), and the dropout forms with the keep mask exported by osrl_dropout
+    (x + delta * m in, dx * m out)."""
+    from oracle.cdt_oracle import layer_norm, layer_norm_bwd
+    from osrl_amd import _lib as L
+    from osrl_amd.engine.core import StepState, cur_stream
+    lib = L.load()
+    st = StepState(torch.device(DEV), ["x"])
+    st.tick()
+    rs = np.random.RandomState(E)
+    M, nparts, p = 301, 7, 0.1
+    f32 = lambda a: np.asarray(a, np.float32)  # noqa: E731
+    x, dl = f32(rs.randn(M, E)), f32(rs.randn(M, E) * 0.3)
+    gm, bt = f32(1 + 0.1 * rs.randn(E)), f32(0.1 * rs.randn(E))
+    dy, dres = f32(rs.randn(M, E)), f32(rs.randn(M, E))
+    xt, dlt, gt, btt, dyt, drt = (t(v) for v in (x, dl, gm, bt, dy, dres))
+    d = L.DropoutT(p, 6, 31, st.ptr)
+    ones, mk = torch.ones(M * E, device=DEV), torch.zeros(M * E, device=DEV)
+    L.check(lib.osrl_dropout(ones.data_ptr(), mk.data_ptr(), M * E, C.byref(d), cur_stream()), "mask")
+    Mk = mk.cpu().numpy().reshape(M, E).astype(np.float64)
+    assert 0.05 < (Mk == 0).mean() < 0.15
+    for drop in (False, True):
+        xo, y, stt = torch.zeros(M, E, device=DEV), torch.zeros(M, E, device=DEV), torch.zeros(M, 2, device=DEV)
+        if drop:
+            L.check(lib.osrl_layernorm_fwd_drop(xt.data_ptr(), dlt.data_ptr(), C.byref(d), gt.data_ptr(), btt.data_ptr(),
+                                                xo.data_ptr(), y.data_ptr(), stt.data_ptr(), M, E, cur_stream()), "lnf")
+            xs = x.astype(np.float64) + (dl * Mk.astype(np.float32)).astype(np.float64)
+        else:
+            L.check(lib.osrl_layernorm_fwd(xt.data_ptr(), dlt.data_ptr(), gt.data_ptr(), btt.data_ptr(), xo.data_ptr(),
+                                           y.data_ptr(), stt.data_ptr(), M, E, cur_stream()), "lnf")
+            xs = x.astype(np.float64) + dl.astype(np.float64)
+        yr, cache = layer_norm(xs, gm.astype(np.float64), bt.astype(np.float64))
+        assert np.abs(xo.cpu().numpy() - xs).max() < 1e-6, (E, drop, "xout")
+        assert np.abs(y.cpu().numpy() - yr).max() < 2e-5, (E, drop, "y")
+        dx, dxd = torch.zeros(M, E, device=DEV), torch.zeros(M, E, device=DEV)
+        ws, slab = torch.zeros(nparts, 2 * E, device=DEV), torch.zeros(4 * E + 8, device=DEV)
+        if drop:
+            L.check(lib.osrl_layernorm_bwd_drop(dyt.data_ptr(), xo.data_ptr(), stt.data_ptr(), gt.data_ptr(),
+                                                drt.data_ptr(), dx.data_ptr(), dxd.data_ptr(), C.byref(d), ws.data_ptr(),
+                                                nparts, M, E, slab.data_ptr(), 4, 4 + 2 * E, cur_stream()), "lnb")
+        else:
+            L.check(lib.osrl_layernorm_bwd(dyt.data_ptr(), xo.data_ptr(), stt.data_ptr(), gt.data_ptr(), drt.data_ptr(),
+                                           dx.data_ptr(), ws.data_ptr(), nparts, M, E, slab.data_ptr(), 4, 4 + 2 * E,
+                                           cur_stream()), "lnb")
+        dxr, dgr, dbr = layer_norm_bwd(dy.astype(np.float64), cache, gm.astype(np.float64))
+        dxr = dxr + dres
+        assert np.abs(dx.cpu().numpy() - dxr).max() < 5e-5 * max(1, np.abs(dxr).max()), (E, drop, "dx")
+        if drop:
+            assert np.abs(dxd.cpu().numpy() - dxr * Mk).max() < 5e-5 * max(1, np.abs(dxr * Mk).max()), (E, "dx dropped")
+        sl = slab.cpu().numpy()
+        assert np.abs(sl[4:4 + E] - dgr).max() < 1e-3 * max(1, np.abs(dgr).max()), (E, drop, "dgamma")
+        assert np.abs(sl[4 + 2 * E:4 + 3 * E] - dbr).max() < 1e-3 * max(1, np.abs(dbr).max()), (E, drop, "dbeta")
+
+
+@pytest.mark.parametrize("E,use_rew,use_cost,prefix", [(640, 1, 1, 0), (768, 0, 1, 1), (1024, 1, 0, 0)])
+def test_wide_embed_layernorm_matches_oracle(E, use_rew, use_cost, prefix):
+    """osrl_cdt_embed_ln at E = 640 / 768 / 1024 (the 16-features-per-lane kernel): token embeddings interleaved as
+    [return] [cost] state action per timestep (cdt.py:178-218; the cost token of 50 - ctg with cost_transform, the
+    prefix token without a timestep embedding), then the emb LayerNorm (oracle layer_norm)."""
+    from oracle.cdt_oracle import layer_norm
+    from osrl_amd import _lib as L
+    from osrl_amd.engine.core import cur_stream
+    lib = L.load()
+    rs = np.random.RandomState(E + 3)
+    B, T, od, ad = 5, 12, 7, 3
+    R = 2 + use_rew + use_cost
+    S = R * T + prefix
+    g32 = lambda *shape: (rs.randn(*shape) * 0.5).astype(np.float32)  # noqa: E731
+    states, actions, returns, ctg, ec = g32(B, T, od), g32(B, T, ad), g32(B, T), g32(B, T), g32(B)
+    ts = rs.randint(0, 50, size=(B, T)).astype(np.int64)
+    Ws, bs, Wa, ba, Wc, bc, Wr, br, Wp, bp = g32(E, od), g32(E), g32(E, ad), g32(E), g32(E), g32(E), g32(E), g32(E), \
+        g32(E), g32(E)
+    te, gm, bt = g32(50, E), g32(E), g32(E)
+    T_ = {k: t(v) for k, v in dict(states=states, actions=actions, returns=returns, ctg=ctg, ec=ec, ts=ts, Ws=Ws, bs=bs,
+                                   Wa=Wa, ba=ba, Wc=Wc, bc=bc, Wr=Wr, br=br, Wp=Wp, bp=bp, te=te, g=gm, b=bt).items()}
+    P = lambda k, on=True: T_[k].data_ptr() if on else None  # noqa: E731
+    seq, x0 = torch.zeros(B * S, E, device=DEV), torch.zeros(B * S, E, device=DEV)
+    stats, ctg_t = torch.zeros(B * S, 2, device=DEV), torch.zeros(B * T, device=DEV)
+    L.check(lib.osrl_cdt_embed_ln(P("states"), P("actions"), P("returns", use_rew), P("ctg", use_cost),
+                                  P("ec", prefix), P("ts"), P("Ws"), P("bs"), P("Wa"), P("ba"), P("Wc", use_cost),
+                                  P("bc", use_cost), P("Wr", use_rew), P("br", use_rew), P("Wp", prefix), P("bp", prefix),
+                                  P("te"), P("g"), P("b"), B, T, od, ad, E, 1, use_rew, use_cost, prefix, seq.data_ptr(),
+                                  x0.data_ptr(), stats.data_ptr(), ctg_t.data_ptr() if use_cost else None, cur_stream()),
+            "embed")
+    f64 = lambda a: a.astype(np.float64)  # noqa: E731
+    tok = []
+    if use_rew:
+        tok.append(f64(returns)[..., None] * f64(Wr) + f64(br))
+    c2 = 50.0 - f64(ctg)
+    if use_cost:
+        tok.append(c2[..., None] * f64(Wc) + f64(bc))
+    tok.append(f64(states) @ f64(Ws).T + f64(bs))
+    tok.append(f64(actions) @ f64(Wa).T + f64(ba))
+    ref = np.stack([x + f64(te)[ts] for x in tok], 2).reshape(B, R * T, E)
+    if prefix:
+        ref = np.concatenate([(f64(ec)[:, None] * f64(Wp) + f64(bp))[:, None], ref], 1)
+    ref = ref.reshape(B * S, E)
+    assert np.abs(seq.cpu().numpy() - ref).max() < 2e-5 * max(1, np.abs(ref).max()), "seq"
+    yr, _ = layer_norm(ref, f64(gm), f64(bt))
+    assert np.abs(x0.cpu().numpy() - yr).max() < 5e-5 * max(1, np.abs(yr).max()), "x0"
+    if use_cost:
+        assert np.abs(ctg_t.cpu().numpy().reshape(B, T) - c2).max() < 1e-5
+
+
+LONG_CASES = {
+    # E = 512, 8 heads (head_dim 64), return + cost tokens, T = 50 -> S = 200, 2 layers
+    "long_e512_s200": CDTCase("long_e512_s200", od=11, ad=3, B=4, T=50, E=512, heads=8, layers=2, episode_len=200,
+                              steps=3, seed=21),
+    # E = 1024, 8 heads (head_dim 128), T = 40 -> S = 160
+    "long_e1024_s160": CDTCase("long_e1024_s160", od=7, ad=2, B=3, T=40, E=1024, heads=8, layers=1, episode_len=100,
+                               steps=3, seed=22),
+    # the cost-prefix token: S = 4 * 33 + 1 = 133 (odd, > 128)
+    "long_prefix_s133": CDTCase("long_prefix_s133", od=5, ad=2, B=4, T=33, E=128, heads=4, layers=2, episode_len=80,
+                                steps=3, seed=23, cost_prefix=True),
+    # E = 384 (not a multiple of 256: the tile / chunked linear kernels), 6 heads of 64, K = 1536
+    "long_e384": CDTCase("long_e384", od=6, ad=2, B=4, T=36, E=384, heads=6, layers=2, episode_len=80, steps=3,
+                         seed=24),
+    # cat_cost_feat: a 2E = 1024-wide action head at E = 512
+    "long_cat_e512": CDTCase("long_cat_e512", od=6, ad=2, B=4, T=10, E=512, heads=8, layers=1, episode_len=60,
+                             steps=3, seed=25, cat_cost_feat=True),
+    # E = 640 (10 features per lane: the 16-per-lane row kernels), head_dim 128 at S = 40 (tiled: head_dim > 64)
+    "long_e640": CDTCase("long_e640", od=6, ad=2, B=4, T=10, E=640, heads=5, layers=1, episode_len=60, steps=3,
+                         seed=26),
+}
+# dropout 0.1 at every site at E > 512: the _drop LayerNorm forms at 16 features per lane, head_dim 128, K = 3072
+DROP_WIDE = CDTCase("long_drop_e768", od=6, ad=2, B=3, T=10, E=768, heads=6, layers=2, episode_len=60, steps=3,
+                    seed=29, dropout=0.1)
+DROP_LONG = CDTCase("long_drop_s200", od=8, ad=3, B=3, T=50, E=256, heads=4, layers=2, episode_len=200, steps=3,
+                    seed=27, dropout=0.1)
+
+
+def _oracle_parity(c, use_graph, drop, tiled=None):
+    from test_oracle_cdt_golden import build_cdt_oracle
+    m, tr, lg = build_cdt_gpu(c, use_graph=use_graph, seed=1234)
+    o = build_cdt_oracle(c)
+    bn = make_cdt_batch(c)
+    b = {k: t(v) for k, v in bn.items()}
+    for s in range(c.steps):
+        tr.train_one_step(b["states"], b["actions"], b["returns"], b["costs_return"], b["time_steps"], b["mask"],
+                          b["episode_cost"], b["costs"])
+        kw = {}
+        if drop:
+            kw["drop"] = {k: v.cpu().numpy() for k, v in m.engine(c.B).dropout_masks().items()}
+        ost = o.train_one_step(bn["states"], bn["actions"], bn["returns"], bn["costs_return"], bn["time_steps"],
+                               bn["mask"], bn["episode_cost"], bn["costs"], **kw)
+        S = (2 + int(c.use_rew) + int(c.use_cost)) * c.T + int(c.cost_prefix)
+        assert m.engine(c.B).attn_tiled == (tiled if tiled is not None else (S > 128 or c.E // c.heads > 64))
+        tol = 1e-5 if (s == 0 and not drop) else 1e-4
+        for k, r in ost.items():
+            got = lg.last("train/" + k)
+            assert abs(got - r) <= tol * max(1.0, abs(r)), f"{c.name} step {s} {k}: gpu {got} vs oracle {r}"
+        assert abs(m.log_temperature.item() - o.log_temperature) < 1e-6
+        for k, v in m.state_dict().items():
+            if v.dtype != torch.bool:
+                d = np.abs(v.cpu().numpy() - o.p[k]).max()
+                assert d <= 2e-5, f"{c.name} step {s + 1} param {k}: max diff {d:.3e}"
+    m.eval()
+    ap, _, _ = m(b["states"], b["actions"], b["returns"], b["costs_return"], b["time_steps"],
+                 ~b["mask"].to(torch.bool), b["episode_cost"])
+    ref = o.act_mean(bn["states"], bn["actions"], bn["returns"], bn["costs_return"], bn["time_steps"], bn["mask"],
+                     bn["episode_cost"])
+    assert np.abs((ap.mean if c.stochastic else ap).cpu().numpy() - ref).max() <= 1e-4
+
+
+@pytest.mark.parametrize("name", sorted(LONG_CASES))
+def test_long_cdt_train_step_matches_oracle(name):
+    _oracle_parity(LONG_CASES[name], use_graph=False, drop=False)
+
+
+@pytest.mark.parametrize("name", ["long_e512_s200", "long_prefix_s133"])
+def test_long_cdt_graph_replayed_train_step_matches_oracle(name):
+    _oracle_parity(LONG_CASES[name], use_graph=True, drop=False)
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_long_cdt_dropout_train_step_matches_oracle(use_graph):
+    """Dropout 0.1 at every site at S = 200: the attention masks are exported from the same logical [B*H, S, Sp] layout
+    the tiled kernels draw from, and the oracle replays them."""
+    _oracle_parity(DROP_LONG, use_graph=use_graph, drop=True)
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_wide_cdt_dropout_train_step_matches_oracle(use_graph):
+    """Dropout 0.1 at every site at E = 768 (the reference configs' dropout on the wide row kernels)."""
+    _oracle_parity(DROP_WIDE, use_graph=use_graph, drop=True)
+
+
+def test_lab_switch_routes_old_shapes_through_the_tiled_kernels(monkeypatch):
+    """OSRL_LAB=1 OSRL_CDT_ATTN_TILED=1: an old shape runs the tiled kernels and still matches the oracle (dropout
+    on); without OSRL_LAB the switch is ignored."""
+    import importlib
+    import osrl_amd.engine.cdt as ec
+    c = dataclasses.replace(CDT_CASES["cdt_drop"], name="cdt_drop_tiled")
+    monkeypatch.setenv("OSRL_CDT_ATTN_TILED", "1")
+    monkeypatch.delenv("OSRL_LAB", raising=False)
+    try:
+        importlib.reload(ec)
+        assert not ec.ATTN_TILED
+        monkeypatch.setenv("OSRL_LAB", "1")
+        importlib.reload(ec)
+        assert ec.ATTN_TILED
+        _oracle_parity(c, use_graph=False, drop=True, tiled=True)
+    finally:
+        monkeypatch.delenv("OSRL_LAB", raising=False)
+        monkeypatch.delenv("OSRL_CDT_ATTN_TILED", raising=False)
+        importlib.reload(ec)
+    assert not ec.ATTN_TILED
+
+
+def test_old_shapes_allocate_no_tiled_workspace():
+    """Every CDT_CASES shape and C5's (T = 20, E = 256, H = 8, 80 tokens) stays on the register-tile kernels: the size
+    query says 0 and the engine allocates neither lse nor the row-dot workspace."""
+    from osrl_amd import _lib as L
+    lib = L.load()
+    for c in list(CDT_CASES.values()) + [C5_SLICE, dataclasses.replace(C5_SLICE, B=1024)]:
+        R = 2 + int(c.use_rew) + int(c.use_cost)
+        S = R * c.T + int(c.cost_prefix)
+        assert lib.osrl_attention_ws_bytes(c.B, S, c.E, c.heads) == 0, c.name
+    c = dataclasses.replace(C5_SLICE, dropout=0.1)
+    m, tr, lg = build_cdt_gpu(c)
+    b = {k: t(v) for k, v in make_cdt_batch(c).items()}
+    tr.train_one_step(b["states"], b["actions"], b["returns"], b["costs_return"], b["time_steps"], b["mask"],
+                      b["episode_cost"], b["costs"])
+    e = m.engine(c.B)
+    assert not e.attn_tiled and e.attn_lse is None and e.attn_ws is None
+    assert e.attn_keep is not None  # (the keep hand-off of the register-tile kernels stays)
+    # a long shape does allocate them, sized by the query
+    assert lib.osrl_attention_ws_bytes(4, 200, 512, 8) == 4 * 4 * 8 * 200
+
+
+def test_long_window_evaluate_matches_oracle_rollout():
+    """CDTTrainer.evaluate (CDTBatchedRollout) with seq_len = 256, od = 64, ad = 8 and no return / cost token (S = 512):
+    the window's slide, 255 * 72 * 4 = 73 KB, is past the 64 KB LDS staging -- the register slide.  Episodes longer than
+    the window, against the oracle re-slicing a full history per env step."""
+    from osrl_amd.common.synthetic_env import SyntheticSafeEnv, VecSyntheticSafeEnv
+    from test_oracle_cdt_golden import build_cdt_oracle
+    c = CDTCase("long_eval", od=64, ad=8, B=2, T=256, E=128, heads=4, layers=1, episode_len=300, steps=1, seed=28,
+                use_rew=False, use_cost=False, stochastic=False)
+    m, tr, lg = build_cdt_gpu(c, use_graph=False)
+    o = build_cdt_oracle(c)
+    NE, EL, T = 2, c.T + 6, c.T
+    m.episode_len = EL
+    tr.cost_scale = 2.0
+    env = SyntheticSafeEnv(c.od, c.ad, EL, seed=2, init_noise=0.6)
+    tr.env = VecSyntheticSafeEnv(env, NE, DEV, base_seed=40)
+    tr.evaluate(NE, target_return=30.0, target_cost=5.0)
+    rets, costs, lens = tr._rollout[1].run(30.0, 5.0)
+    for e in range(NE):
+        S, A = np.zeros((EL + 1, c.od), np.float32), np.zeros((EL, c.ad), np.float32)
+        R, Cc = np.zeros(EL + 1, np.float32), np.zeros(EL + 1, np.float32)
+        obs, _ = env.reset(seed=40 + e)
+        S[0], R[0], Cc[0] = obs, 30.0, 5.0
+        r0 = c0 = 0.0
+        for step in range(EL):
+            lo = max(0, step + 1 - T)
+            n = step + 1 - lo
+            pad = lambda x: np.concatenate([x, np.zeros((T - n,) + x.shape[1:], x.dtype)])[None]  # noqa: E731
+            acts = o.act_mean(pad(S[lo:step + 1]), pad(A[lo:step + 1]), pad(R[lo:step + 1]), pad(Cc[lo:step + 1]),
+                              pad(np.arange(lo, step + 1)), pad(np.ones(n, np.float32)), np.array([5.0], np.float32))
+            act = np.clip(acts[0, n - 1], -1, 1)
+            obs, reward, term, trunc, info = env.step(act)
+            A[step], S[step + 1] = act, obs
+            R[step + 1], Cc[step + 1] = R[step] - reward, Cc[step] - info["cost"] * 2.0
+            r0 += reward
+            c0 += info["cost"]
+        assert lens[e] == EL and abs(rets[e] - r0) < 1e-3 * max(1, abs(r0)) and abs(costs[e] - c0) <= 1.0, \
+            (e, rets[e], r0, costs[e], c0)
+
+
+def test_long_checkpoint_resume_is_bit_identical(tmp_path):
+    """E = 512, S = 200 with dropout: save -> load -> continue == an uninterrupted run, bit for bit."""
+    from osrl_amd.common.checkpoint import load_checkpoint, save_checkpoint
+    c = dataclasses.replace(LONG_CASES["long_e512_s200"], name="long_ckpt", dropout=0.1, layers=1)
+    b = {k: t(v) for k, v in make_cdt_batch(c).items()}
+
+    def run(tr, n):
+        for _ in range(n):
+            tr.train_one_step(b["states"], b["actions"], b["returns"], b["costs_return"], b["time_steps"], b["mask"],
+                              b["episode_cost"], b["costs"])
+
+    m_a, tr_a, _ = build_cdt_gpu(c)
+    run(tr_a, 4)
+    m_b, tr_b, _ = build_cdt_gpu(c)
+    run(tr_b, 2)
+    path = str(tmp_path / "cdt_long.pt")
+    save_checkpoint(m_b, path)
+    m_c, tr_c, _ = build_cdt_gpu(c)
+    load_checkpoint(m_c, path)
+    run(tr_c, 2)
+    torch.cuda.synchronize()
+    for k, v in m_a.state_dict().items():
+        assert torch.equal(v, m_c.state_dict()[k]), k
+    assert torch.equal(m_a.log_temperature, m_c.log_temperature)
+
+
+def test_issue_config_s768_trains_evaluates_and_round_trips(tmp_path):
+    """CDT(embedding_dim=1024, num_heads=8, seq_len=256, use_rew=True, use_cost=False): S = 768 tokens."""
+    from osrl_amd.algorithms import CDT, CDTTrainer
+    from osrl_amd.common.checkpoint import load_checkpoint, save_checkpoint
+    from osrl_amd.common.logger import DummyLogger
+    from osrl_amd.common.synthetic_env import SyntheticSafeEnv, VecSyntheticSafeEnv
+    od, ad, T, B = 6, 2, 256, 2
+
+    def build():
+        torch.manual_seed(0)
+        m = CDT(od, ad, 1.0, seq_len=T, episode_len=300, embedding_dim=1024, num_layers=1, num_heads=8,
+                use_rew=True, use_cost=False, device=DEV)
+        tr = CDTTrainer(m, None, DummyLogger(), device=DEV, stats_mode="sync", use_graph=False)
+        return m, tr
+
+    m, tr = build()
+    rs = np.random.RandomState(3)
+    b = dict(states=t(rs.randn(B, T, od).astype(np.float32)), actions=t(rs.uniform(-1, 1, (B, T, ad)).astype(np.float32)),
+             returns=t(rs.uniform(0, 10, (B, T)).astype(np.float32)), costs_return=t(rs.uniform(0, 20, (B, T)).astype(np.float32)),
+             time_steps=t(np.tile(np.arange(T), (B, 1)).astype(np.int64)), mask=t(np.ones((B, T), np.float32)),
+             episode_cost=t(np.full(B, 5.0, np.float32)), costs=t((rs.rand(B, T) < 0.1).astype(np.float32)))
+    keys = ("states", "actions", "returns", "costs_return", "time_steps", "mask", "episode_cost", "costs")
+    for _ in range(2):
+        tr.train_one_step(*(b[k] for k in keys))
+    assert m.engine(B).S == 768 and m.engine(B).attn_tiled
+    path = str(tmp_path / "s768.pt")
+    save_checkpoint(m, path)
+    m2, tr2 = build()
+    load_checkpoint(m2, path)
+    for k, v in m.state_dict().items():
+        assert torch.equal(v, m2.state_dict()[k]), k
+    tr.train_one_step(*(b[k] for k in keys))
+    tr2.train_one_step(*(b[k] for k in keys))
+    torch.cuda.synchronize()
+    for k, v in m.state_dict().items():
+        assert torch.equal(v, m2.state_dict()[k]), k
+    env = SyntheticSafeEnv(od, ad, 260, seed=2, init_noise=0.6)
+    m.episode_len = 260
+    tr.env = VecSyntheticSafeEnv(env, 2, DEV, base_seed=40)
+    ret, cost, ln = tr.evaluate(2, target_return=30.0, target_cost=5.0)
+    assert ln == 260 and np.isfinite(ret) and np.isfinite(cost)
