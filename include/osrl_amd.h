@@ -32,7 +32,19 @@ extern "C" {
 
 #define OSRL_MAX_LAYERS 4 /* Linear layers per MLP */
 #define OSRL_MAX_NETS 8   /* ensemble members sharing one input tile */
-#define OSRL_MAX_WIDTH 448 /* widest hidden layer supported by the fused kernels */
+#define OSRL_MAX_WIDTH 1024 /* widest layer (input, hidden or output) of an MLP */
+/* MLP widths: nets whose dims are all <= 448 run on the fused 16-row-tile kernels (a whole net per tile in LDS, four
+ * waves of at most 7 column blocks of 16).  A net with any dims[l] in 449..1024 takes the WIDE PATH of osrl_mlp_*:
+ * one launch per layer (grid = row tile x column group x net, ensembles in one launch), fp32 MFMA on the same packed
+ * Wf / Wb copies, bias + activation + out_scale (forward) or act'(h) (backward) in the launch's epilogue, layer 0 read
+ * from the virtual input (osrl_rows_t: maps, src1) directly.  Its contract differs from the fused one in three
+ * points:
+ *   - every intermediate output is the next launch's input: forward needs h[e][l] for every l < n_layers - 1 and
+ *     backward needs dz[e][l] for every layer above the lowest one asked for (dz or dx); else OSRL_E_UNSUPPORTED;
+ *   - tails run as their own launches behind the layers (the named glue calls), forward2 is two launches, row_list
+ *     returns -3, the wg_cap / tile_rows / share0 hints are ignored;
+ *   - osrl_mlp_backward_dz_seed honours the seed (dY by the tile kernel on the output layer alone, outputs <= 448
+ *     wide; wider: OSRL_E_UNSUPPORTED); osrl_mlp_regress_step returns OSRL_E_UNSUPPORTED. */
 
 enum { OSRL_ACT_ID = 0, OSRL_ACT_RELU = 1, OSRL_ACT_TANH = 2 };
 /* row r of the virtual input maps to source row: r | r % div | r / div
@@ -347,6 +359,8 @@ int osrl_linear(const float* A, int64_t lda, int32_t M, int32_t K, const float* 
                 int32_t N, const float* bias, const float* resid, int64_t ldr, float* Y, int64_t ldy, void* stream);
 /* dynamic LDS per workgroup of that chunked form (K > 1024 where the big-M kernels do not take the shape) */
 int64_t osrl_linear_kchunk_lds_bytes(void);
+/* dynamic LDS per workgroup of a wide-path MLP layer launch with K inputs and N outputs (0: K outside 1..OSRL_MAX_WIDTH) */
+int64_t osrl_mlp_wide_lds_bytes(int32_t K, int32_t N);
 /* Refresh the packed copies of `n_entries` weights (entries in DEVICE memory).  Sizes in floats:
  * forward round16(in)*round16(out), backward round16(out)*(round16(in)+16).  max_elems = the largest
  * packed size among the entries (grid sizing).  Must run after every change of the canonical weights. */

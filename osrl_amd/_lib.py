@@ -15,7 +15,8 @@ import torch  # noqa: F401  (import order matters)
 
 MAX_LAYERS = 4
 MAX_NETS = 8
-MAX_WIDTH = 448
+MAX_WIDTH = 1024       # widest MLP layer (include/osrl_amd.h OSRL_MAX_WIDTH)
+TILE_MAX_WIDTH = 448  # nets wider than this take the per-layer wide path of osrl_mlp_*
 MAX_FIELDS = 8
 
 ACT_ID, ACT_RELU, ACT_TANH = 0, 1, 2
@@ -263,6 +264,7 @@ PROTOTYPES = {
     "osrl_attention_tiled_ws_bytes": [_i32, _i32, _i32, _i32],
     "osrl_attention_tiled_lds_bytes": [_i32, _i32],
     "osrl_linear_kchunk_lds_bytes": [],
+    "osrl_mlp_wide_lds_bytes": [_i32, _i32],
     "osrl_attention_fwd_ws": [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _P(DropoutT), _fp, _fp, _vp],
     "osrl_attention_bwd_ws": [_fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _P(DropoutT), _fp, _fp, _fp, _fp,
                               _vp],
@@ -296,7 +298,8 @@ LOSS_WS = 132  # floats of scratch for the grid loss kernels (include/osrl_amd.h
 QUANTILE_WS = 1032  # uint32 elements of scratch for osrl_quantile_ws (include/osrl_amd.h OSRL_QUANTILE_WS)
 RESTYPES = {"osrl_ingest_ws_elems": C.c_int64, "osrl_attention_keep_bytes": C.c_int64,
             "osrl_attention_ws_bytes": C.c_int64, "osrl_attention_tiled_ws_bytes": C.c_int64,
-            "osrl_attention_tiled_lds_bytes": C.c_int64, "osrl_linear_kchunk_lds_bytes": C.c_int64}  # everything else returns int (0 = ok)
+            "osrl_attention_tiled_lds_bytes": C.c_int64, "osrl_linear_kchunk_lds_bytes": C.c_int64,
+            "osrl_mlp_wide_lds_bytes": C.c_int64}  # everything else returns int (0 = ok)
 
 
 def lib_path() -> str:

@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from ..common.logger import store_stats
-from ..common.net import MLPActor, bind_group, plan_group
+from ..common.net import MLPActor, bind_group, check_mlp_limits, plan_group
 from ..engine.core import FlatGroup, require_cuda
 
 
@@ -22,6 +22,7 @@ class BC(nn.Module):
         self.a_hidden_sizes = list(a_hidden_sizes)
         self.episode_len = episode_len
         self.device = str(device)
+        check_mlp_limits("BC", actor=[state_dim] + self.a_hidden_sizes + [action_dim])
         dev = require_cuda(device)
         self.actor = MLPActor(state_dim, action_dim, self.a_hidden_sizes, nn.ReLU, max_action)
         g = FlatGroup("actor", dev)

@@ -9,7 +9,8 @@ import torch
 import torch.nn as nn
 
 from ..common.logger import store_stats
-from ..common.net import (VAE, EnsembleDoubleQCritic, MLPGaussianPerturbationActor, bind_group, plan_group)
+from ..common.net import (VAE, EnsembleDoubleQCritic, MLPGaussianPerturbationActor, bind_group, check_mlp_limits,
+                          plan_group)
 from ..engine.core import FlatGroup, require_cuda
 
 
@@ -50,6 +51,10 @@ class BCQL(nn.Module):
         self.num_q, self.num_qc = num_q, num_qc
         self.cost_limit, self.episode_len = cost_limit, episode_len
         self.device = str(device)
+        check_mlp_limits("BCQL", actor=[state_dim + action_dim] + self.a_hidden_sizes + [action_dim],
+                         critic=[state_dim + action_dim] + self.c_hidden_sizes + [1],
+                         vae_encoder=[state_dim + action_dim, vae_hidden_sizes, vae_hidden_sizes, 2 * self.latent_dim],
+                         vae_decoder=[state_dim + self.latent_dim, vae_hidden_sizes, vae_hidden_sizes, action_dim])
         dev = require_cuda(device)
 
         # creation order of bcql.py:86-100 (actor, critic, cost_critic, vae)

@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from ..common.logger import store_stats
-from ..common.net import VAE, EnsembleDoubleQCritic, SquashedGaussianMLPActor, bind_group, plan_group
+from ..common.net import VAE, EnsembleDoubleQCritic, SquashedGaussianMLPActor, bind_group, check_mlp_limits, plan_group
 from ..engine.core import FlatGroup, require_cuda
 from .bcql import LagrangianPIDController
 
@@ -42,6 +42,10 @@ class BEARL(nn.Module):
         self.num_q, self.num_qc = num_q, num_qc
         self.cost_limit, self.episode_len = cost_limit, episode_len
         self.device = str(device)
+        check_mlp_limits("BEARL", actor=[state_dim] + self.a_hidden_sizes + [2 * action_dim],
+                         critic=[state_dim + action_dim] + self.c_hidden_sizes + [1],
+                         vae_encoder=[state_dim + action_dim, vae_hidden_sizes, vae_hidden_sizes, 2 * self.latent_dim],
+                         vae_decoder=[state_dim + self.latent_dim, vae_hidden_sizes, vae_hidden_sizes, action_dim])
         dev = require_cuda(device)
 
         # creation order of bearl.py:97-109 (actor, critic, cost_critic, vae) => same init under the same seed

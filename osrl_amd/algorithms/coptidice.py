@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from ..common.logger import store_stats
-from ..common.net import EnsembleQCritic, SquashedGaussianMLPActor, bind_group, plan_group
+from ..common.net import EnsembleQCritic, SquashedGaussianMLPActor, bind_group, check_mlp_limits, plan_group
 from ..engine.core import FlatGroup, require_cuda
 
 F_TYPES = ("chi2", "softchi", "kl")
@@ -34,6 +34,8 @@ class COptiDICE(nn.Module):
         self.cost_limit, self.episode_len = cost_limit, episode_len
         self.init_state_propotion = float(init_state_propotion)
         self.device = str(device)
+        check_mlp_limits("COptiDICE", actor=[state_dim] + self.a_hidden_sizes + [2 * action_dim],
+                         nu=[state_dim] + self.c_hidden_sizes + [1], chi=[state_dim] + self.c_hidden_sizes + [1])
         dev = require_cuda(device)
         self.qc_thres = cost_limit * (1 - self.gamma ** self.episode_len) / (1 - self.gamma) / self.episode_len
 

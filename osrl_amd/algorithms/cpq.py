@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..common.net import (VAE, EnsembleQCritic, SquashedGaussianMLPActor, bind_group, plan_group)
+from ..common.net import (VAE, EnsembleQCritic, SquashedGaussianMLPActor, bind_group, check_mlp_limits, plan_group)
 from ..engine.core import FlatGroup, require_cuda
 
 
@@ -52,6 +52,10 @@ class CPQ(nn.Module):
         self.episode_len = episode_len
         self.max_action = max_action
         self.device = str(device)
+        check_mlp_limits("CPQ", actor=[state_dim] + self.a_hidden_sizes + [2 * action_dim],
+                         critic=[state_dim + action_dim] + self.c_hidden_sizes + [1],
+                         vae_encoder=[state_dim + action_dim, vae_hidden_sizes, vae_hidden_sizes, 2 * self.latent_dim],
+                         vae_decoder=[state_dim + self.latent_dim, vae_hidden_sizes, vae_hidden_sizes, action_dim])
         dev = require_cuda(device)
 
         # same creation order as the reference (cpq.py:78-92) => same init under the same seed

@@ -27,6 +27,21 @@ from ..engine.core import FlatGroup, LayerRef, NetDesc
 _ACT_NAME = {nn.ReLU: "relu", nn.Tanh: "tanh", nn.Identity: "id"}
 
 
+def check_mlp_limits(algo: str, **nets: Sequence[int]) -> None:
+    """Refuse, at construction and without a device, an MLP the kernels do not take: ``nets`` maps a network's name to
+    its layer sizes [in, hidden..., out] as the kernels see it (an actor's mu / log_std heads are one 2 * act_dim-wide
+    layer).  Limits: OSRL_MAX_LAYERS Linear layers and OSRL_MAX_WIDTH units in every dimension (include/osrl_amd.h)."""
+    from .. import _lib as L
+    for name, sizes in nets.items():
+        sizes = [int(s) for s in sizes]
+        if len(sizes) - 1 > L.MAX_LAYERS:
+            raise ValueError(f"{algo}: {name} has {len(sizes) - 1} Linear layers; at most {L.MAX_LAYERS} are supported "
+                             f"(sizes {sizes})")
+        if max(sizes) > L.MAX_WIDTH:
+            raise ValueError(f"{algo}: {name} has a layer {max(sizes)} wide; at most {L.MAX_WIDTH} units per layer are "
+                             f"supported (sizes {sizes})")
+
+
 def mlp(sizes: Sequence[int], activation, output_activation=nn.Identity) -> nn.Sequential:
     """Linear/activation stack with the reference's Sequential indexing (net.py:12-30):
     Linear layers sit at even indices, so keys are ``{0,2,4,...}.{weight,bias}``."""

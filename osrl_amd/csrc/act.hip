@@ -31,7 +31,9 @@ namespace {
 
 constexpr int kThreads = 1024, kWaves = 16;
 constexpr int kMaxRows = OSRL_POLICY_MAX_ROWS;
-constexpr int kW = 512;  // LDS row stride (floats) >= widest layer (OSRL_MAX_WIDTH = 448) and obs+act inputs
+// LDS row stride (floats) >= widest layer and obs+act inputs: 512 for nets whose layers are all <= 512 wide (every net of
+// the fused-kernel widths), 1024 = OSRL_MAX_WIDTH for the wider ones (a second instantiation: twice the LDS)
+constexpr int kW = 512, kWideW = OSRL_MAX_WIDTH;
 constexpr float kLogStdMin = -20.0f, kLogStdMax = 2.0f;  // net.py:148-149
 
 __device__ __forceinline__ float softplus(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
@@ -68,7 +70,7 @@ struct ActArgs {
   float obs[kInline];
 };
 
-// y[r][n] = act(b[n] + sum_k W[n][k] x[r][k]) * scale for r < R rows; x, y in LDS (stride kW), `red` = LDS scratch.
+// y[r][n] = act(b[n] + sum_k W[n][k] x[r][k]) * scale for r < R rows; x, y in LDS (stride W), `red` = LDS scratch.
 // The weights are read from the PACKED forward copy PF[k/4][n][k%4] (osrl_pack_weights: zero padded to multiples of 16
 // in both dims) with LANES OWNING OUTPUT NEURONS: for a fixed k-quad consecutive n are consecutive 16-byte words, so
 // every wave load is 1 KB contiguous and a dot product needs NO cross-lane reduction (a per-neuron wave reduction is a
@@ -77,7 +79,7 @@ struct ActArgs {
 // in LDS.
 __device__ __forceinline__ int round16(int x) { return (x + 15) & ~15; }
 
-template <int R>
+template <int R, int W>
 __device__ __forceinline__ void gemv_layer(const float* __restrict__ PF, const float* __restrict__ b, int in, int out,
                                            int act, float scale, const float* x, float* y, float* red) {
   const int tid = threadIdx.x;
@@ -87,18 +89,20 @@ __device__ __forceinline__ void gemv_layer(const float* __restrict__ PF, const f
   const int KS = kThreads / NL;
   const int ks = tid / NL, nl = tid - ks * NL;
   const int q0 = (nq * ks) / KS, q1 = (nq * (ks + 1)) / KS;
-  const int rs = Np > 256 ? 512 : NL;  // row stride of `red`: KS * R * rs <= 2048 * R floats
+  const int rs = Np > 256 ? W : NL;  // row stride of `red`: KS * R * rs <= 4 * W * R floats
   const float4* __restrict__ P4 = reinterpret_cast<const float4*>(PF);
   for (int n = nl; n < Np; n += 256) {
     float acc[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = 0.f;
-#pragma unroll 8
+    // (unrolled 8-deep at W = 512; the W = 1024 form spills there at 4 rows, and 4-deep keeps it in registers)
+    constexpr int kUnroll = W > 512 ? 4 : 8;
+#pragma unroll kUnroll
     for (int q = q0; q < q1; ++q) {
       const float4 w = P4[(size_t)q * Np + n];
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        const float4 xv = *reinterpret_cast<const float4*>(x + r * kW + 4 * q);  // same address across the wave
+        const float4 xv = *reinterpret_cast<const float4*>(x + r * W + 4 * q);  // same address across the wave
         acc[r] = fmaf(w.x, xv.x, fmaf(w.y, xv.y, fmaf(w.z, xv.z, fmaf(w.w, xv.w, acc[r]))));
       }
     }
@@ -110,18 +114,18 @@ __device__ __forceinline__ void gemv_layer(const float* __restrict__ PF, const f
     const int r = i / Np, n = i - r * Np;
     float s = 0.f;
     for (int k = 0; k < KS; ++k) s += red[(k * R + r) * rs + n];
-    y[r * kW + n] = n < out ? act_fwd(act, s + b[n]) * scale : 0.f;  // zero = the next layer's k padding
+    y[r * W + n] = n < out ? act_fwd(act, s + b[n]) * scale : 0.f;  // zero = the next layer's k padding
   }
   __syncthreads();
 }
 
 // one MLP: input (zero padded to a multiple of 16 columns) in buf[0]; returns the index of the buffer with the output
-template <int R>
-__device__ __forceinline__ int run_net(const osrl_gemv_net_t& n, float (*buf)[kMaxRows * kW], float* red) {
+template <int R, int W>
+__device__ __forceinline__ int run_net(const osrl_gemv_net_t& n, float (*buf)[kMaxRows * W], float* red) {
   int cur = 0;
   for (int l = 0; l < n.n_layers; ++l) {
     const float sc = l == n.n_layers - 1 ? n.out_scale : 1.0f;
-    gemv_layer<R>(n.Wf[l], n.b[l], n.dims[l], n.dims[l + 1], n.acts[l], sc, buf[cur], buf[cur ^ 1], red);
+    gemv_layer<R, W>(n.Wf[l], n.b[l], n.dims[l], n.dims[l + 1], n.acts[l], sc, buf[cur], buf[cur ^ 1], red);
     cur ^= 1;
   }
   return cur;
@@ -147,10 +151,11 @@ __device__ __forceinline__ float draw_normal(const ActArgs& a, int idx) {
 #define ACT_STAMP(i)
 #endif
 
-template <int R>
+template <int R, int W = kW>
 __global__ __launch_bounds__(kThreads) void policy_act_kernel(const ActArgs a) {
-  __shared__ __attribute__((aligned(16))) float buf[2][kMaxRows * kW];
-  __shared__ __attribute__((aligned(16))) float red[2048 * R];  // [KS][R][stride] partial sums of a layer
+  static_assert(sizeof(float) * (2 * kMaxRows * W + 4 * W * R) <= 160 * 1024, "policy_act_kernel: LDS per workgroup");
+  __shared__ __attribute__((aligned(16))) float buf[2][kMaxRows * W];
+  __shared__ __attribute__((aligned(16))) float red[4 * W * R];  // [KS][R][stride] partial sums of a layer
 #ifdef OSRL_ACT_STAMPS
   long long stamp_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -159,8 +164,8 @@ __global__ __launch_bounds__(kThreads) void policy_act_kernel(const ActArgs a) {
   const osrl_policy_t& p = a.p;
   const int od = p.obs_dim, ad = p.act_dim, rows = a.rows;
   // ---- stage the observation rows (host-mapped memory) + the second input segment of stage 0
-  for (int i = tid; i < R * kW; i += kThreads) {
-    const int r = i / kW, c = i - r * kW;
+  for (int i = tid; i < R * W; i += kThreads) {
+    const int r = i / W, c = i - r * W;
     float v = 0.f;
     if (r < rows) {
       if (c < od) {
@@ -177,14 +182,14 @@ __global__ __launch_bounds__(kThreads) void policy_act_kernel(const ActArgs a) {
   }
   __syncthreads();
   ACT_STAMP(1);
-  int cur = run_net<R>(p.net[0], buf, red);
+  int cur = run_net<R, W>(p.net[0], buf, red);
   ACT_STAMP(2);
   if (p.kind == OSRL_POLICY_MLP) {  // BC: act_limit * tanh(mlp(obs)) -- tanh + scale are the net's last layer
-    for (int i = tid; i < rows * ad; i += kThreads) a.io.act[i] = buf[cur][(i / ad) * kW + (i % ad)];
+    for (int i = tid; i < rows * ad; i += kThreads) a.io.act[i] = buf[cur][(i / ad) * W + (i % ad)];
   } else if (p.kind == OSRL_POLICY_GAUSS) {
     // SquashedGaussianMLPActor tail (net.py:176-201): head = (mu | log_std)
     if (tid < rows) {
-      const float* h = buf[cur] + tid * kW;
+      const float* h = buf[cur] + tid * W;
       float lp = 0.f;
       for (int j = 0; j < ad; ++j) {
         const float mu = h[j];
@@ -201,25 +206,25 @@ __global__ __launch_bounds__(kThreads) void policy_act_kernel(const ActArgs a) {
   } else {  // OSRL_POLICY_BCQ: a0 = decoder([obs, z]); t = pi([obs, a0]); a = clamp(a0 + phi*max_a*t)  (net.py:58-62)
     float* nxt = buf[cur ^ 1];
     const float* dec = buf[cur];
-    for (int i = tid; i < R * kW; i += kThreads) {
-      const int r = i / kW, c = i - r * kW;
+    for (int i = tid; i < R * W; i += kThreads) {
+      const int r = i / W, c = i - r * W;
       float v = 0.f;
       if (r < rows)
-        v = c < od ? (a.obs_inline ? a.obs[r * od + c] : a.io.obs[r * od + c]) : (c < od + ad ? dec[r * kW + (c - od)] : 0.f);
+        v = c < od ? (a.obs_inline ? a.obs[r * od + c] : a.io.obs[r * od + c]) : (c < od + ad ? dec[r * W + (c - od)] : 0.f);
       nxt[i] = v;
     }
     __syncthreads();
     // keep a0 (rows x ad) in registers of the first threads across the second net
     float a0 = 0.f;
-    if (tid < rows * ad) a0 = dec[(tid / ad) * kW + (tid % ad)];
+    if (tid < rows * ad) a0 = dec[(tid / ad) * W + (tid % ad)];
     __syncthreads();
     if (cur == 0) {  // run_net expects its input in buf[0]
-      for (int i = tid; i < R * kW; i += kThreads) buf[0][i] = buf[1][i];
+      for (int i = tid; i < R * W; i += kThreads) buf[0][i] = buf[1][i];
       __syncthreads();
     }
-    const int c2 = run_net<R>(p.net[1], buf, red);
+    const int c2 = run_net<R, W>(p.net[1], buf, red);
     if (tid < rows * ad) {
-      const float t = buf[c2][(tid / ad) * kW + (tid % ad)];
+      const float t = buf[c2][(tid / ad) * W + (tid % ad)];
       a.io.act[tid] = fminf(fmaxf(a0 + p.phi * p.max_action * t, -p.max_action), p.max_action);
     }
   }
@@ -250,10 +255,19 @@ struct Handle {
 bool valid_gemv(const osrl_gemv_net_t& n) {
   if (n.n_layers < 1 || n.n_layers > OSRL_MAX_LAYERS || n.out_scale == 0.f) return false;
   for (int l = 0; l <= n.n_layers; ++l)
-    if (n.dims[l] < 1 || n.dims[l] > kW) return false;
+    if (n.dims[l] < 1 || n.dims[l] > kWideW) return false;
   for (int l = 0; l < n.n_layers; ++l)
     if (!n.Wf[l] || !n.b[l]) return false;
   return true;
+}
+
+// a layer or a staged input row wider than kW: the kWideW instantiation
+bool needs_wide(const osrl_policy_t& p) {
+  const int nn = p.kind == OSRL_POLICY_BCQ ? 2 : 1;
+  for (int i = 0; i < nn; ++i)
+    for (int l = 0; l <= p.net[i].n_layers; ++l)
+      if (p.net[i].dims[l] > kW) return true;
+  return p.kind == OSRL_POLICY_BCQ && (p.obs_dim + p.latent_dim > kW || p.obs_dim + p.act_dim > kW);
 }
 
 }  // namespace
@@ -272,7 +286,7 @@ extern "C" int osrl_policy_create(const osrl_policy_t* desc, void** handle) {
   } else {
     if (!valid_gemv(p.net[1]) || p.latent_dim < 1 || p.net[0].dims[0] != p.obs_dim + p.latent_dim ||
         p.net[0].dims[p.net[0].n_layers] != p.act_dim || p.net[1].dims[0] != p.obs_dim + p.act_dim ||
-        p.net[1].dims[p.net[1].n_layers] != p.act_dim || p.obs_dim + p.latent_dim > kW || p.obs_dim + p.act_dim > kW)
+        p.net[1].dims[p.net[1].n_layers] != p.act_dim || p.obs_dim + p.latent_dim > kWideW || p.obs_dim + p.act_dim > kWideW)
       return -1;
     noise_dim = p.latent_dim;
   }
@@ -335,10 +349,16 @@ extern "C" int osrl_policy_act(void* handle, int32_t rows, int32_t deterministic
   a.obs_inline = rows * h->p.obs_dim <= kInline;
   if (a.obs_inline) memcpy(a.obs, h->host.obs, sizeof(float) * rows * h->p.obs_dim);
   (void)hipGetLastError();
-  if (rows == 1)
+  if (needs_wide(h->p)) {
+    if (rows == 1)
+      hipLaunchKernelGGL((policy_act_kernel<1, kWideW>), dim3(1), dim3(kThreads), 0, (hipStream_t)stream, a);
+    else
+      hipLaunchKernelGGL((policy_act_kernel<kMaxRows, kWideW>), dim3(1), dim3(kThreads), 0, (hipStream_t)stream, a);
+  } else if (rows == 1) {
     hipLaunchKernelGGL(policy_act_kernel<1>, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, a);
-  else
+  } else {
     hipLaunchKernelGGL(policy_act_kernel<kMaxRows>, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, a);
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   // fast path: spin on the sequence number the kernel publishes (system-scope release) -- a stream synchronise costs

@@ -1740,6 +1740,167 @@ bool valid_net(const osrl_mlp_t* n) {
   return true;
 }
 
+// ---- the wide path: nets with any dims[l] > kTileMaxWidth, one launch per layer ----------------------------------
+// The 16-row tile kernels keep a whole net in LDS and give each of 4 waves at most 7 column blocks of 16: 4 x 7 x 16 =
+// 448 columns.  Walking a 1024-wide layer per 16-row tile that way would make every workgroup stream the whole net.  A
+// wide net instead runs as one launch per layer on linear_kernel's structure (A tile staged in LDS once, column groups
+// of 16 * 4 * NCB columns on blockIdx.y, weights streamed from the packed copies by the same MFMA core), with the net
+// index on blockIdx.z (ensembles in one launch), the virtual input of osrl_rows_t as layer 0's A operand, and the
+// layer's element-wise work in the copy-out:
+//   WIDE_FWD   Y = act(A P + b) * oscale                      (forward layer, packed Wf)
+//   WIDE_BWD   Y = (A P) * act'(h)                            (dZ_{l-1} = (dZ_l W_l) * act'(h_{l-1}), packed Wb)
+//   WIDE_PLAIN Y = A P                                        (the dX slice)
+constexpr int kTileMaxWidth = 448;
+bool wide_net(const osrl_mlp_t* n) {
+  for (int l = 0; l <= n->n_layers; ++l)
+    if (n->dims[l] > kTileMaxWidth) return true;
+  return false;
+}
+enum { WIDE_FWD = 0, WIDE_BWD = 1, WIDE_PLAIN = 2 };
+struct WideArgs {
+  const float* A[OSRL_MAX_NETS];     // [M, K] per net, row stride K; NULL: the virtual input `in` (forward layer 0)
+  const float* P[OSRL_MAX_NETS];     // packed weights (Np columns, from column col0)
+  const float* bias[OSRL_MAX_NETS];  // WIDE_FWD
+  const float* h[OSRL_MAX_NETS];     // WIDE_BWD: [M, N] saved activation
+  float* Y[OSRL_MAX_NETS];           // [M, N]; NULL: this net has no such step (its workgroups leave)
+  osrl_rows_t in;
+  float* x;                          // layer 0: the staged input is written here too (may be NULL)
+  int32_t M, K, N, Np, col0, lda, act, mode;
+  float oscale;
+};
+constexpr int kWideMaxK = OSRL_MAX_WIDTH;
+static_assert(sizeof(float) * 16 * (kWideMaxK + 8) <= kLdsMax && sizeof(float) * 32 * (512 + 8) <= kLdsMax,
+              "wide_layer_kernel: LDS per workgroup");
+
+template <int NRB, int NCB>
+__global__ __launch_bounds__(256) void wide_layer_kernel(const WideArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int BM = 16 * NRB;
+  const int e = blockIdx.z;
+  float* __restrict__ Y = a.Y[e];
+  if (!Y) return;
+  const float* __restrict__ P = a.P[e];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int row0 = blockIdx.x * BM, M = a.M, K = a.K, N = a.N, lda = a.lda;
+  const int Kp = round16(K);
+  const int nk = Kp >> 4;
+  const int nblk_tot = (N + 15) >> 4;
+  constexpr int GB = 4 * NCB;  // column blocks per workgroup
+  const int gb0 = blockIdx.y * GB;
+  int nblk = nblk_tot - gb0;
+  nblk = nblk > GB ? GB : nblk;
+  const bool narrow = nblk_tot <= 2 && nk >= 4 && lda >= 64;
+  int cb0 = 0, cnt = 0;
+  f32x4 ring[kRing][NCB];
+  if (narrow) {  // first weight loads go out before the A tile is staged
+    narrow_prefetch<NCB>(ring, nk, P, a.Np, a.col0, nblk_tot, wave);
+  } else {
+    wave_blocks(nblk, wave, &cb0, &cnt);
+    layer_prefetch<NRB, NCB>(ring, nk, P, a.Np, a.col0 + (gb0 + cb0) * 16, cnt);
+  }
+  {  // stage A[row0 : row0+BM, 0:K] zero padded; 16 lanes per row
+    const int cl = tid & 15, rl = tid >> 4;
+    const float* __restrict__ A = a.A[e];
+    float* __restrict__ x = (a.x && blockIdx.y == 0 && e == 0) ? a.x : nullptr;
+    const bool vec = A && (K & 3) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0;
+#pragma unroll 1
+    for (int r = rl; r < BM; r += 16) {
+      const int gr = row0 + r;
+      const bool rok = gr < M;
+      const int grc = rok ? gr : M - 1;
+      if (vec) {
+        const float* __restrict__ src = A + (size_t)grc * K;
+        for (int c = cl * 4; c < Kp; c += 64) {
+          const bool ok = rok && c < K;
+          f32x4 v = *reinterpret_cast<const f32x4*>(src + (ok ? c : 0));
+          if (!ok) v = f32x4{0.f, 0.f, 0.f, 0.f};
+          *reinterpret_cast<f32x4*>(lds + r * lda + c) = v;
+        }
+      } else if (A) {
+        const float* __restrict__ src = A + (size_t)grc * K;
+        for (int c = cl; c < Kp; c += 16) {
+          const bool ok = rok && c < K;
+          const float v = src[ok ? c : 0];
+          lds[r * lda + c] = ok ? v : 0.f;
+        }
+      } else {  // the virtual input: cat(src0[map0(r)], src1[map1(r)])
+        const osrl_rows_t& in = a.in;
+        const float* __restrict__ s0 = in.src0 + (size_t)map_row(grc, in.map0, in.div0) * in.d0;
+        const float* __restrict__ s1 = in.d1 > 0 ? in.src1 + (size_t)map_row(grc, in.map1, in.div1) * in.d1 : s0;
+        for (int c = cl; c < Kp; c += 16) {
+          const bool ok = rok && c < K;
+          float v = 0.f;
+          if (ok) v = c < in.d0 ? s0[c] : s1[c - in.d0];
+          lds[r * lda + c] = v;
+          if (x && ok) x[(size_t)gr * K + c] = v;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (narrow) {
+    narrow_layer_splitk<NRB, NCB>(lds, lda, nk, P, a.Np, a.col0, nblk_tot, wave, ring);
+  } else {
+    f32x4 acc[NRB][NCB];
+    zero_acc<NRB, NCB>(acc);
+    if (cnt > 0) layer_run<NRB, NCB>(lds, lda, nk, P, a.Np, a.col0 + (gb0 + cb0) * 16, cnt, acc, ring);
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < NCB; ++c) {
+      if (c < cnt) {
+        const int col = (cb0 + c) * 16 + (lane & 15);  // column inside this group's LDS tile
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) lds[(rb * 16 + (lane >> 4) * 4 + r) * lda + col] = acc[rb][c][r];
+      }
+    }
+    __syncthreads();
+  }
+  // copy out with the layer's element-wise epilogue, coalesced
+  const int ncols = (nblk * 16 < N - gb0 * 16) ? nblk * 16 : N - gb0 * 16;
+  const int gcol0 = gb0 * 16;
+  const float* __restrict__ bias = a.bias[e];
+  const float* __restrict__ h = a.h[e];
+  for (int idx = tid; idx < BM * ncols; idx += 256) {
+    const int r = idx / ncols, c = idx - r * ncols;
+    const int gr = row0 + r;
+    if (gr < M) {
+      const size_t o = (size_t)gr * N + gcol0 + c;
+      float v = lds[r * lda + c];
+      if (a.mode == WIDE_FWD)
+        v = act_fwd(a.act, v + bias[gcol0 + c]) * a.oscale;
+      else if (a.mode == WIDE_BWD)
+        v *= act_bwd(a.act, h[o]);
+      Y[o] = v;
+    }
+  }
+}
+
+// dZ_{L-1} = dY * out_scale * act'(Y / out_scale) of the wide path (the expression of mlp_bwd_dz_body's first stage)
+struct WideDyArgs {
+  const float* dy[OSRL_MAX_NETS];
+  const float* y[OSRL_MAX_NETS];
+  float* dz[OSRL_MAX_NETS];
+  int64_t n;
+  int32_t act;
+  float oscale;
+};
+__global__ __launch_bounds__(256) void wide_dy_kernel(const WideDyArgs a) {
+  const int e = blockIdx.y;
+  float* __restrict__ dz = a.dz[e];
+  if (!dz) return;
+  const float* __restrict__ dy = a.dy[e];
+  const float* __restrict__ y = a.y[e];
+  const float inv_oscale = 1.0f / a.oscale;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
+    float v = dy[i] * a.oscale;
+    if (a.act != OSRL_ACT_ID) v *= act_bwd(a.act, y[i] * inv_oscale);
+    dz[i] = v;
+  }
+}
+
 
 // ---- one supervised regression step of one MLP in ONE launch (osrl_mlp_regress_step) ---------------------------
 // BC at B = 256 (bc.py:45-55,103-109) is six dependent launches of 2-8 us of work each: the step is its launch gaps.
@@ -2029,6 +2190,85 @@ static int fwd_tail_as_launches(const osrl_mlp_tail_t* t, const float* head, int
   return rc;
 }
 
+// one layer launch of the wide path: linear_kernel's tile choice (K <= 512: 32-row tiles)
+struct WideTile {
+  int ncb, nrb, lda;
+  size_t lds_bytes;
+};
+static WideTile wide_tile(int K, int N) {
+  WideTile t;
+  const int nblk = (N + 15) / 16;
+  t.ncb = nblk >= 16 ? 4 : ((nblk + 3) / 4 <= 1 ? 1 : (nblk + 3) / 4 <= 2 ? 2 : 4);
+  const int gcols = nblk >= 16 ? 256 : nblk * 16;
+  const int wmax = round16h(K) > gcols ? round16h(K) : gcols;
+  t.lda = (wmax < 64 ? 64 : wmax) + 8;
+  t.nrb = K > 512 ? 1 : 2;
+  t.lds_bytes = (size_t)16 * t.nrb * t.lda * sizeof(float);
+  return t;
+}
+static int launch_wide_layer(WideArgs& a, int nets, hipStream_t stream) {
+  const WideTile t = wide_tile(a.K, a.N);
+  const int nblk = (a.N + 15) / 16, ncb = t.ncb, nrb = t.nrb;
+  a.lda = t.lda;
+  const int BM = 16 * nrb;
+  const size_t lds_bytes = t.lds_bytes;
+  if (a.K < 1 || a.K > kWideMaxK || lds_bytes > kLdsMax) return -1;
+  const dim3 grid((a.M + BM - 1) / BM, (nblk + 4 * ncb - 1) / (4 * ncb), nets);
+  (void)hipGetLastError();
+#define OSRL_WIDE_LAUNCH(R, C)                                                                                  \
+  do {                                                                                                          \
+    if (lds_bytes > 64 * 1024) {                                                                                \
+      const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(wide_layer_kernel<R, C>),        \
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);    \
+      if (e0 != hipSuccess) return (int)e0;                                                                     \
+    }                                                                                                           \
+    hipLaunchKernelGGL((wide_layer_kernel<R, C>), grid, dim3(256), lds_bytes, stream, a);                       \
+  } while (0)
+  if (nrb == 2) {
+    if (ncb == 1) OSRL_WIDE_LAUNCH(2, 1); else if (ncb == 2) OSRL_WIDE_LAUNCH(2, 2); else OSRL_WIDE_LAUNCH(2, 4);
+  } else {
+    if (ncb == 1) OSRL_WIDE_LAUNCH(1, 1); else if (ncb == 2) OSRL_WIDE_LAUNCH(1, 2); else OSRL_WIDE_LAUNCH(1, 4);
+  }
+#undef OSRL_WIDE_LAUNCH
+  return (int)hipGetLastError();
+}
+
+// forward of a wide net: one launch per layer (every intermediate h[e][l] is the next launch's input, so it must be
+// given), then any tail as its own launch
+static int mlp_forward_wide(const osrl_mlp_t* net, const osrl_rows_t* in, const osrl_mlp_acts_t* out,
+                            const osrl_mlp_tail_t* tail, void* stream) {
+  if (in->row_list || in->n_rows_dev) return -3;  // (share0 is a hint: ignored)
+  const int L = net->n_layers, E = net->n_nets;
+  if (in->d0 < 1 || !in->src0 || (in->d1 > 0 && !in->src1)) return -1;
+  for (int e = 0; e < E; ++e)
+    for (int l = 0; l < L - 1; ++l)
+      if (!out->h[e][l]) return OSRL_E_UNSUPPORTED;
+  for (int l = 0; l < L; ++l) {
+    WideArgs a{};
+    for (int e = 0; e < E; ++e) {
+      a.A[e] = l == 0 ? nullptr : out->h[e][l - 1];
+      a.P[e] = net->Wf[e][l];
+      a.bias[e] = net->b[e][l];
+      a.Y[e] = out->h[e][l];
+    }
+    if (l == 0) {
+      a.in = *in;
+      a.x = out->x;
+    }
+    a.M = in->rows;
+    a.K = net->dims[l];
+    a.N = net->dims[l + 1];
+    a.Np = round16h(a.N);
+    a.act = net->acts[l];
+    a.mode = WIDE_FWD;
+    a.oscale = l == L - 1 ? net->out_scale : 1.0f;
+    const int rc = launch_wide_layer(a, E, (hipStream_t)stream);
+    if (rc != 0) return rc;
+  }
+  if (tail && tail->kind != OSRL_TAIL_NONE) return fwd_tail_as_launches(tail, out->h[0][L - 1], in->rows, stream);
+  return 0;
+}
+
 static int mlp_forward_impl(const osrl_mlp_t* net, const osrl_rows_t* in, const osrl_mlp_acts_t* out,
                             const osrl_mlp_tail_t* tail, void* stream) {
   if (!valid_net(net) || net->out_scale == 0.f || !in || !out || in->rows < 1 || in->d0 + in->d1 != net->dims[0]) return -1;
@@ -2039,6 +2279,7 @@ static int mlp_forward_impl(const osrl_mlp_t* net, const osrl_rows_t* in, const 
   }
   const bool want_tail = tail && tail->kind != OSRL_TAIL_NONE;
   if (want_tail && !fwd_tail_ok(tail, net)) return -1;
+  if (wide_net(net)) return mlp_forward_wide(net, in, out, tail, stream);
   {
     const bool kl_tail = want_tail && tail->kind == OSRL_TAIL_VAE_KL;  // the one tail the 80-row kernel runs itself
     const int rc = osrl_launch_fwd_nb(net, in, out, (hipStream_t)stream, kl_tail ? tail->out : nullptr, kl_tail ? tail->L : 0);
@@ -2122,6 +2363,10 @@ static int mlp_forward2_impl(const osrl_mlp_t* net0, const osrl_rows_t* in0, con
   if (!valid_net(net0) || !valid_net(net1) || !in0 || !in1 || !out0 || !out1) return -1;
   if (in0->row_list || in0->n_rows_dev || in1->row_list || in1->n_rows_dev) return -3;  // (osrl_mlp_forward only)
   if (!fwd_tail_ok(tail0, net0) || !fwd_tail_ok(tail1, net1)) return -1;
+  if (wide_net(net0) || wide_net(net1)) {  // no pair launch on the wide path
+    const int rc = mlp_forward_impl(net0, in0, out0, tail0, stream);
+    return rc != 0 ? rc : mlp_forward_impl(net1, in1, out1, tail1, stream);
+  }
   TileChoice t0 = choose_tile(net0, in0->rows, 0), t1 = choose_tile(net1, in1->rows, 0);
   // pair only 16-row-tile launches of equal tile shape; anything else runs as two launches
   // a KL tail exists on the single-launch path only (80-row kernel or a follow-up osrl_vae_kl_rows launch)
@@ -2196,7 +2441,124 @@ static bool seed_ok(const osrl_mlp_seed_t* s, const osrl_mlp_t* net, const osrl_
 
 static int mlp_backward_dz_impl(const osrl_mlp_t* net, int32_t rows, const osrl_mlp_acts_t* saved,
                                 const osrl_mlp_grads_t* g, const osrl_mlp_tail_t* tail, void* stream,
-                                const osrl_mlp_seed_t* seed = nullptr) {
+                                const osrl_mlp_seed_t* seed = nullptr);
+
+// backward-dz of a wide net (arguments checked by the caller).  dZ_{L-1}: a seeded launch computes it with the tile
+// kernel on the output layer alone (a one-layer net [dims[L], dims[L]] whose only step is the seed stage: the same dY
+// bits and statistic as the fused launch), otherwise wide_dy_kernel; then one launch per layer down to the lowest one
+// asked for (dz[e][l] given, or the dX slice), then the VAE_LATENT_BWD tail as its own launch.  Every dZ a lower step
+// reads must be given.
+static int mlp_backward_dz_wide(const osrl_mlp_t* net, int32_t rows, const osrl_mlp_acts_t* saved,
+                                const osrl_mlp_grads_t* g, const osrl_mlp_tail_t* tail, void* stream,
+                                const osrl_mlp_seed_t* seed) {
+  const int L = net->n_layers, E = net->n_nets;
+  // lowest[e] = the lowest dZ index net e asks for (-1: the dX slice as well)
+  int lowest[OSRL_MAX_NETS];
+  for (int e = 0; e < E; ++e) {
+    int lo = L - 1;
+    for (int l = 0; l < L - 1; ++l)
+      if (g->dz[e][l]) {
+        lo = l;
+        break;
+      }
+    if (g->dx[e]) lo = -1;
+    lowest[e] = lo;
+    // every dZ that feeds a lower step is an input of a launch: it must exist
+    for (int l = (lo < 0 ? 0 : lo + 1); l < L; ++l)
+      if (!g->dz[e][l]) return OSRL_E_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int NL = net->dims[L];
+  if (seed) {
+    if (NL > kTileMaxWidth) return OSRL_E_UNSUPPORTED;
+    osrl_mlp_t sub = *net;
+    sub.n_layers = 1;
+    sub.dims[0] = sub.dims[1] = NL;
+    sub.acts[0] = net->acts[L - 1];
+    sub.tile_rows = 0;
+    sub.wg_cap = 0;
+    osrl_mlp_acts_t ss{};
+    osrl_mlp_grads_t gs{};
+    for (int e = 0; e < E; ++e) {
+      sub.Wf[e][0] = net->Wf[e][L - 1];
+      sub.Wb[e][0] = net->Wb[e][L - 1];
+      sub.b[e][0] = net->b[e][L - 1];
+      ss.h[e][0] = saved->h[e][L - 1];
+      gs.dy[e] = g->dy[e];
+      gs.dz[e][0] = g->dz[e][L - 1];
+    }
+    const int rc = mlp_backward_dz_impl(&sub, rows, &ss, &gs, nullptr, stream, seed);
+    if (rc != 0) return rc;
+  } else {
+    WideDyArgs d{};
+    for (int e = 0; e < E; ++e) {
+      d.dy[e] = g->dy[e];
+      d.y[e] = net->acts[L - 1] != OSRL_ACT_ID ? saved->h[e][L - 1] : g->dy[e];
+      d.dz[e] = g->dz[e][L - 1];
+    }
+    d.n = (int64_t)rows * NL;
+    d.act = net->acts[L - 1];
+    d.oscale = net->out_scale;
+    long blocks = (d.n + 255) / 256;
+    blocks = blocks > 1024 ? 1024 : blocks;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(wide_dy_kernel, dim3((unsigned)blocks, E), dim3(256), 0, st, d);
+    const int rc = (int)hipGetLastError();
+    if (rc != 0) return rc;
+  }
+  for (int l = L - 1; l >= 1; --l) {  // dZ_{l-1} = (dZ_l W_l) * act'(h_{l-1})
+    WideArgs a{};
+    bool any = false;
+    for (int e = 0; e < E; ++e) {
+      if (lowest[e] > l - 1) continue;
+      a.A[e] = g->dz[e][l];
+      a.P[e] = net->Wb[e][l];
+      a.h[e] = saved->h[e][l - 1];
+      a.Y[e] = g->dz[e][l - 1];
+      any = any || a.Y[e] != nullptr;
+    }
+    if (!any) continue;
+    a.M = rows;
+    a.K = net->dims[l + 1];
+    a.N = net->dims[l];
+    a.Np = round16h(a.N) + 16;
+    a.act = net->acts[l - 1];
+    a.mode = WIDE_BWD;
+    a.oscale = 1.0f;
+    const int rc = launch_wide_layer(a, E, st);
+    if (rc != 0) return rc;
+  }
+  {  // dX[:, c0 : c0 + nc] = dZ_0 W_0[:, c0 : c0 + nc]
+    WideArgs a{};
+    bool any = false;
+    for (int e = 0; e < E; ++e) {
+      if (!g->dx[e]) continue;
+      a.A[e] = g->dz[e][0];
+      a.P[e] = net->Wb[e][0];
+      a.Y[e] = g->dx[e];
+      any = true;
+    }
+    if (any) {
+      a.M = rows;
+      a.K = net->dims[1];
+      a.N = g->dx_cols;
+      a.Np = round16h(net->dims[0]) + 16;
+      a.col0 = g->dx_col0;
+      a.mode = WIDE_PLAIN;
+      a.oscale = 1.0f;
+      const int rc = launch_wide_layer(a, E, st);
+      if (rc != 0) return rc;
+    }
+  }
+  if (tail)
+    return osrl_vae_latent_bwd(tail->head, tail->eps, g->dx[0], rows, tail->L, tail->beta, tail->rows_global, tail->out,
+                               stream);
+  return 0;
+}
+
+static int mlp_backward_dz_impl(const osrl_mlp_t* net, int32_t rows, const osrl_mlp_acts_t* saved,
+                                const osrl_mlp_grads_t* g, const osrl_mlp_tail_t* tail, void* stream,
+                                const osrl_mlp_seed_t* seed) {
   if (!valid_net(net) || !saved || !g || rows < 1) return -1;
   const bool seeded = seed && seed->kind != OSRL_SEED_NONE;
   if (seeded && !seed_ok(seed, net, saved)) return -1;
@@ -2212,6 +2574,7 @@ static int mlp_backward_dz_impl(const osrl_mlp_t* net, int32_t rows, const osrl_
   if (want_tail && (tail->kind != OSRL_TAIL_VAE_LATENT_BWD || tail->L < 1 || !g->dx[0] || g->dx_cols != tail->L ||
                     !tail->eps || !tail->head || !tail->out))
     return -1;
+  if (wide_net(net)) return mlp_backward_dz_wide(net, rows, saved, g, want_tail ? tail : nullptr, stream, seeded ? seed : nullptr);
   BwdArgs a{};
   a.net = *net;
   a.saved = *saved;
@@ -2284,6 +2647,7 @@ extern "C" int osrl_debug_step_phases(long long* host_out /* [OSRL_STEP_MAX_WG][
 extern "C" int osrl_mlp_regress_step(const osrl_mlp_step_t* s, void* stream) {
   if (!s || !s->st || !valid_net(&s->net) || !s->target || !s->entries || !s->work || !s->p || !s->m || !s->v || !s->ws)
     return -1;
+  if (wide_net(&s->net)) return OSRL_E_UNSUPPORTED;  // (the one-launch step is built on the 16-row tile)
   const osrl_mlp_t* net = &s->net;
   const int L = net->n_layers, rows = s->in.rows;
   if (rows < 1 || s->in.d0 + s->in.d1 != net->dims[0] || !s->in.src0 || (s->in.d1 > 0 && !s->in.src1) || s->n_work < 1)
@@ -2489,6 +2853,10 @@ extern "C" int osrl_linear(const float* A, int64_t lda, int32_t M, int32_t K, co
 }
 
 extern "C" int64_t osrl_linear_kchunk_lds_bytes(void) { return (int64_t)kLinKChunkLds; }
+extern "C" int64_t osrl_mlp_wide_lds_bytes(int32_t K, int32_t N) {
+  if (K < 1 || K > kWideMaxK || N < 1) return 0;
+  return (int64_t)wide_tile(K, N).lds_bytes;
+}
 
 extern "C" int osrl_pack_weights(const float* src_flat, float* pf, float* pb, const osrl_pack_entry_t* d_entries,
                                  int32_t n_entries, int32_t max_elems, void* stream) {

@@ -44,7 +44,7 @@ class BCEngine:
         # a row-tile count that fit the resident grid; the library has the last word (OSRL_E_UNSUPPORTED -> the plan)
         self.one_launch = (_plan.knob("OSRL_BC_ONE_LAUNCH", "1", "the BC step as one launch", operator=True) == "1" and dist is None and self.plan.tile_blocks == 4
                            and self.plan.n_splits == 1 and 0 < self.plan.n_work <= L.STEP_MAX_WG
-                           and B <= 16 * L.STEP_MAX_WG)
+                           and B <= 16 * L.STEP_MAX_WG and _plan.bc_one_launch_shape(self.d_pi.dims))
         self.step_ws = torch.zeros(L.STEP_WS, **f) if self.one_launch else None
         if self.one_launch:
             self.st.health_checks.append(self.check_health)

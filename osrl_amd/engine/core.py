@@ -298,8 +298,11 @@ class NetDesc:
         self.E, self.nl = E, nl
         dims = [nets[0][0].W.shape[1]] + [nets[0][l].W.shape[0] for l in range(nl)]
         if max(dims) > L.MAX_WIDTH:
-            raise ValueError(f"layer width {max(dims)} > {L.MAX_WIDTH} unsupported by the fused MLP kernels")
+            raise ValueError(f"layer width {max(dims)} > {L.MAX_WIDTH} unsupported by the MLP kernels")
         self.dims = dims
+        # any layer wider than the 16-row tile kernels take: the per-layer wide path (include/osrl_amd.h), whose
+        # launches read every intermediate activation / dZ from memory -- MlpRun gives it all of them
+        self.wide = max(dims) > L.TILE_MAX_WIDTH
         self.acts = [L.ACT_CODES[a] for a in acts]
         self.out_scale = float(out_scale)
         self.nets = nets
@@ -375,7 +378,7 @@ class MlpRun:
             self.acts_c.x = self.x.data_ptr()
         for e in range(E):
             for l in range(nl - 1):
-                if e in sn:
+                if e in sn or net.wide:  # (a wide net's layer launches read the previous layer's output from memory)
                     self.h[e][l] = torch.zeros(rows, dims[l + 1], **f)
                     self.acts_c.h[e][l] = self.h[e][l].data_ptr()
             self.h[e][nl - 1] = self.y[e]
@@ -480,7 +483,7 @@ class MlpRun:
             row = []
             for l in range(net.nl):
                 sv.h[j][l] = self.h[e][l].data_ptr()
-                if need_dz:
+                if need_dz or (net.wide and dx_cols is not None):  # (the wide path's dX launch reads dZ_0 from memory)
                     t = torch.zeros(self.rows, net.dims[l + 1], **f)
                     g.dz[j][l] = t.data_ptr()
                     row.append(t)

@@ -80,6 +80,20 @@ class CPQPlan:
     #                              ("head"): covered by the main chain's wait for the critic's Adam
 
 
+TILE_MAX_WIDTH = 448  # == _lib.TILE_MAX_WIDTH: wider MLPs run layer by layer (include/osrl_amd.h, the wide path)
+
+
+def tile_widths(*widths) -> bool:
+    """Every width fits the fused 16-row-tile / 80-row MLP kernels -- the forms that exist only there (the one-launch BC
+    step, shared-observation tiles, row sets, all-CU VAE launches) need this; a wider net runs layer by layer."""
+    return all(int(w) <= TILE_MAX_WIDTH for w in widths)
+
+
+def bc_one_launch_shape(dims) -> bool:
+    """The BC step as one launch (osrl_mlp_regress_step) exists for nets of the 16-row tile only."""
+    return tile_widths(*dims)
+
+
 def ood_rows_ok(od: int, ad: int, B: int, N: int, c_hidden) -> bool:
     """Shapes on which the row-set form of the N*B-row target-cost-critic launch exists (csrc/mlp_nb.hip, LIST
     instantiation of the 4-wave 80-row kernel): every hidden layer 13..16 column blocks wide, input <= 128 columns, the
@@ -165,7 +179,8 @@ def cpq_plan(od: int, ad: int, B: int, vae_hidden: int, N: int, seeds: bool = Tr
     # (gpurun_out/r6share).  The outputs differ from the plain launch by fp32 rounding (another order of a row's sum); they
     # feed qc_ood / the KL quantile only -- no gradient to any network (cpq.py:155-186) -- so parameters are the same bits.
     ood_share = knob("OSRL_OOD_SHARE", "1", "N*B-row launches on tiles of shared observations (observation part of layer 0 once per observation): 1 / 0") == "1" \
-        and ood_tile == 80 and od >= 16 and B % 16 == 0 and N % 5 == 0
+        and ood_tile == 80 and od >= 16 and B % 16 == 0 and N % 5 == 0 \
+        and tile_widths(vae_hidden, *(c_hidden if c_hidden is not None else ()))
     return CPQPlan(head_tails=bool(head_tails), vae_dw_tile=vt, vae_dw_splits=splits, small_dw=B >= 1024,
                    ood_tile=ood_tile, vae_ns=bool(vae_ns), vae_adam_side=bool(side), steps_per_graph=spg,
                    ood_rows=bool(ood_rows), ood_rows_late=bool(rows_late), ood_share=bool(ood_share), pipe_no_join=bool(no_join), pipe_prologue=pro)
