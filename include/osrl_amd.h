@@ -853,6 +853,65 @@ int osrl_bc_select(const float* cost_returns, int64_t n, int32_t mode, float t0,
 int osrl_gather_rows(const float* src, int32_t width, const int64_t* idx, int64_t n_rows, float* dst, int32_t dst_ld,
                      const float* extra, void* stream);
 
+/* ---- Pareto-frontier augmentation (osrl/common/dataset.py:186-396, :557-630, :47-92) ----
+ * The CDT dataset recipe (augmentation / random_augmentation) and process_bc_dataset's "frontier" mode over the
+ * tables above, fp64 per trajectory as numpy.  Each `ws` is a workspace of the matching *_ws_elems() 8-byte
+ * elements.  Random draws come from Philox keyed by `seed` unless an injected array (any may be NULL) is given: then
+ * its values are used in the reference's order of use -- pick_in: the positions random.sample keeps inside every
+ * overfull bin ([overfull bins][max_per_bin], dict order); u_rew / u_part / u_cr: the random_sample() doubles that
+ * np.random.uniform / np.random.choice consume; noise_c / noise_r: the np.random.normal rows, [augmented rows]. */
+/* r0[e] = returns[traj_start[e]], c0[e] = cost_returns[traj_start[e]], widened to fp64 */
+int osrl_traj_returns(const float* ret, const float* cret, const int64_t* traj_start, int32_t n_traj, double* r0,
+                      double* c0, void* stream);
+/* grid_filter (dataset.py:239-272) with the data's own bounds: numpy floor_divide bin keys, bins in dict order
+ * (first member), members in index order, > max_per_bin -> max_per_bin drawn, <= min_per_bin -> dropped.
+ * filt[0..*count) = kept indices (n sized), fx / fy = x / y at them; *count = -1 when a bin width is 0.
+ * n <= 2^20, (xbins+1)(ybins+1) <= 576, max_per_bin <= 32. */
+int64_t osrl_grid_filter_ws_elems(int64_t n);
+int osrl_grid_filter(const double* x, const double* y, int32_t n, int32_t xbins, int32_t ybins, int32_t max_per_bin,
+                     int32_t min_per_bin, const int32_t* pick_in, uint64_t seed, int32_t* filt, double* fx, double* fy,
+                     int32_t* count, void* ws, void* stream);
+/* oapackage ParetoDoubleLong over (-c, r): flag[i] = 1 iff no point is >= in both and > in one; n <= 2^20 */
+int osrl_pareto_mask(const double* c, const double* r, int32_t n, int32_t* flag, void* stream);
+/* np.polyfit(x[P], y[P], deg), P = flagged indices in order (flag NULL: all): coef[0..deg] highest power first,
+ * pidx[0..*pcount) = P.  pick != 0: process_bc_dataset's rule, deg 0, 1, 2 until r^2 >= 0.9 (*deg_out = the one
+ * kept).  stats[5] = {r2 deg 0, 1, 2 (NaN if not tried), max y, min y over all n}.  deg <= 7. */
+int64_t osrl_polyfit_ws_elems(int64_t n, int32_t deg);
+int osrl_polyfit(const double* x, const double* y, const int32_t* flag, int32_t n, int32_t deg, int32_t pick,
+                 double* coef, int32_t* deg_out, int32_t* pidx, int32_t* pcount, double* stats, void* ws, void* stream);
+/* augmentation()'s targets + get_nearest_point (dataset.py:186-236, :350-366) over the F filtered points:
+ * tc = linspace(min fx, max fx, S), tr = U[pf(tc) + min_reward, max_reward]; nearest[0..S) = get_nearest_point's
+ * index list (unique nearest indices in first-occurrence order, each followed by its drawn partners).  F <= 8000. */
+int64_t osrl_augment_targets_ws_elems(int64_t F, int64_t S);
+int osrl_augment_targets(const double* coef, const int32_t* deg, const double* fx, const double* fy, int32_t F,
+                         int32_t S, double min_reward, double max_reward, double max_rew_decrease, double beta,
+                         const double* u_rew, const double* u_part, uint64_t seed, double* tc, double* tr,
+                         int32_t* nearest, void* ws, void* stream);
+/* random_augmentation's targets (dataset.py:586-615): (tc, tr) uniform in [aug_cmin, aug_cmax] x [aug_rmin,
+ * aug_rmax]; nearest[k] = masked argmin of hypot over c0 <= max(tc - cgap, min c0 + 1). */
+int osrl_random_aug_targets(const double* c0, const double* r0, int32_t n, int32_t S, double aug_cmin, double aug_cmax,
+                            double aug_rmin, double aug_rmax, double cgap, const double* u_cr, uint64_t seed,
+                            double* tc, double* tr, int32_t* nearest, void* stream);
+/* combined trajectory table: the n_traj originals, then one copy of src[k] = map[nearest[k]] (map NULL: nearest[k])
+ * per sample, rows appended after n_rows; new_* are [n_traj + S]; *total = rows of the combined tables. */
+int osrl_augment_layout(const int32_t* nearest, const int32_t* map, int32_t S, const int64_t* traj_start,
+                        const int32_t* traj_len, int32_t n_traj, int64_t n_rows, int64_t* new_start, int32_t* new_len,
+                        int32_t* src, int64_t* total, void* stream);
+/* the augmented rows of the combined tables (the original rows are the caller's copy): observations, actions,
+ * rewards, costs bit for bit; returns / cost_returns = fp32(fp64(x) + ((target - fp64(x[0])) [+ noise])), noise
+ * (random_augmentation) N(0, cstd) / N(0, rstd) per row. */
+int osrl_augment_gather(const float* obs, const float* act, const float* rew, const float* cost, const float* ret,
+                        const float* cret, int32_t od, int32_t ad, const int64_t* traj_start, const int32_t* src,
+                        int32_t S, const int64_t* new_start, const int32_t* new_len, int32_t n_traj, const double* tc,
+                        const double* tr, int32_t noise, double cstd, double rstd, const double* noise_c,
+                        const double* noise_r, uint64_t seed, float* o_obs, float* o_act, float* o_rew, float* o_cost,
+                        float* o_ret, float* o_cret, void* stream);
+/* process_bc_dataset "frontier" (dataset.py:91-93, :111): keep transition i iff |rr_i - pf(cr_i)| <= (rmax-rmin)/5
+ * (coef / deg / stats from osrl_polyfit with pick); mask [n] floats of scratch; then osrl_bc_select's compaction. */
+int osrl_bc_frontier_select(const float* cost_returns, const float* rew_returns, int64_t n, const double* coef,
+                            const int32_t* deg, const double* stats, float* mask, int64_t* idx, int32_t* n_keep,
+                            int32_t* ws, void* stream);
+
 /* ---- batched on-device evaluation ----
  * The reference's Trainer.rollout (cpq.py:330-347, bcql.py:323-340, bc.py:125-145) steps ONE gym env per policy
  * call and crosses host<->device every env step.  No gym env exists in either container, so the build owns a

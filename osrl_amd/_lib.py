@@ -154,6 +154,7 @@ class StepStateT(C.Structure):
 
 
 _i32, _i64, _f32, _u32, _u64, _vp = C.c_int32, C.c_int64, C.c_float, C.c_uint32, C.c_uint64, C.c_void_p
+_f64 = C.c_double
 _P = C.POINTER
 
 # name -> argtypes  (all return int except osrl_version); must match include/osrl_amd.h
@@ -187,6 +188,20 @@ PROTOTYPES = {
     "osrl_start_index_prob": [_vp, _vp, _vp, _i32, C.c_double, _vp, _vp, _vp],
     "osrl_bc_select": [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp],
     "osrl_gather_rows": [_vp, _i32, _vp, _i64, _vp, _i32, _vp, _vp],
+    "osrl_traj_returns": [_vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    "osrl_grid_filter_ws_elems": [_i64],
+    "osrl_grid_filter": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "osrl_pareto_mask": [_vp, _vp, _i32, _vp, _vp],
+    "osrl_polyfit_ws_elems": [_i64, _i32],
+    "osrl_polyfit": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "osrl_augment_targets_ws_elems": [_i64, _i64],
+    "osrl_augment_targets": [_vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _f64, _f64, _vp, _vp, _u64, _vp, _vp, _vp,
+                             _vp, _vp],
+    "osrl_random_aug_targets": [_vp, _vp, _i32, _i32, _f64, _f64, _f64, _f64, _f64, _vp, _u64, _vp, _vp, _vp, _vp],
+    "osrl_augment_layout": [_vp, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp],
+    "osrl_augment_gather": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32,
+                            _f64, _f64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "osrl_bc_frontier_select": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "osrl_vae_ns_supported": [_P(VaeNsT)],
     "osrl_vae_ns_forward": [_P(VaeNsT), _vp],
     "osrl_vae_ns_backward": [_P(VaeNsT), _vp],
@@ -296,7 +311,8 @@ _LIB: Optional[C.CDLL] = None
 
 LOSS_WS = 132  # floats of scratch for the grid loss kernels (include/osrl_amd.h OSRL_LOSS_WS)
 QUANTILE_WS = 1032  # uint32 elements of scratch for osrl_quantile_ws (include/osrl_amd.h OSRL_QUANTILE_WS)
-RESTYPES = {"osrl_ingest_ws_elems": C.c_int64, "osrl_attention_keep_bytes": C.c_int64,
+RESTYPES = {"osrl_ingest_ws_elems": C.c_int64, "osrl_grid_filter_ws_elems": C.c_int64,
+            "osrl_polyfit_ws_elems": C.c_int64, "osrl_augment_targets_ws_elems": C.c_int64, "osrl_attention_keep_bytes": C.c_int64,
             "osrl_attention_ws_bytes": C.c_int64, "osrl_attention_tiled_ws_bytes": C.c_int64,
             "osrl_attention_tiled_lds_bytes": C.c_int64, "osrl_linear_kchunk_lds_bytes": C.c_int64,
             "osrl_mlp_wide_lds_bytes": C.c_int64}  # everything else returns int (0 = ok)

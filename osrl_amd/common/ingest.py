@@ -114,13 +114,13 @@ def compute_start_index_sample_prob(tables: Dict[str, torch.Tensor], prob: float
 
 def process_bc_dataset(dataset: Dict[str, "np.ndarray | torch.Tensor"], cost_limit: float, gamma: float, bc_mode: str,
                        device="cuda") -> Dict[str, torch.Tensor]:
-    """dataset.py:30-134 on device (all modes but "frontier", which needs oapackage's Pareto search): per-episode
-    discounted returns broadcast to every transition, the mode's selection as a stable compaction, every array
-    filtered, the cost return appended to the observation for "multi-task".  Returns NEW device tensors keyed like
-    the input (plus ``cost_returns`` / ``rew_returns``); the reference edits its dict in place."""
-    if bc_mode == "frontier":
-        raise NotImplementedError('bc_mode="frontier" needs the oapackage Pareto search (not in this build)')
-    if bc_mode not in BC_MODES:
+    """dataset.py:30-134 on device: per-episode discounted returns broadcast to every transition, the mode's
+    selection as a stable compaction, every array filtered, the cost return appended to the observation for
+    "multi-task".  "frontier" fits the Pareto frontier of the episode returns (csrc/augment.hip) and keeps the
+    transitions within (rmax - rmin) / 5 of it; it needs every transition inside a complete episode and raises
+    NotImplementedError for a trailing partial episode.  Returns NEW device tensors keyed like the input (plus
+    ``cost_returns`` / ``rew_returns``); the reference edits its dict in place."""
+    if bc_mode not in BC_MODES and bc_mode != "frontier":
         raise NotImplementedError(bc_mode)
     ep = Episodes(dataset, device)
     dev, n = ep.device, ep.n
@@ -134,8 +134,11 @@ def process_bc_dataset(dataset: Dict[str, "np.ndarray | torch.Tensor"], cost_lim
     idx = torch.zeros(n, dtype=torch.int64, device=dev)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
     lib = L.load()
-    L.check(lib.osrl_bc_select(d["cost_returns"].data_ptr(), n, BC_MODES[bc_mode], t0, t1, idx.data_ptr(),
-                               cnt.data_ptr(), ep.ws.data_ptr(), cur_stream()), "osrl_bc_select")
+    if bc_mode == "frontier":
+        _bc_frontier_select(ep, d["cost_returns"], d["rew_returns"], idx, cnt)
+    else:
+        L.check(lib.osrl_bc_select(d["cost_returns"].data_ptr(), n, BC_MODES[bc_mode], t0, t1, idx.data_ptr(),
+                                   cnt.data_ptr(), ep.ws.data_ptr(), cur_stream()), "osrl_bc_select")
     keep = int(cnt.item())
     out: Dict[str, torch.Tensor] = {}
     for k, v in d.items():
@@ -148,3 +151,235 @@ def process_bc_dataset(dataset: Dict[str, "np.ndarray | torch.Tensor"], cost_lim
         out[k] = dst
     out["index"] = idx[:keep].clone()
     return out
+
+
+# --------------------------------------------------------------------------------------------------------------- #
+# Pareto-frontier augmentation (dataset.py:186-396, :557-630; csrc/augment.hip)
+# --------------------------------------------------------------------------------------------------------------- #
+FILTER_BINS = (10, 50)      # augmentation()'s grid_filter: cost x reward bins (dataset.py:320)
+FILTER_PER_BIN = (10, 2)    # at most 10 per bin, bins with 2 or fewer dropped (dataset.py:321)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _injected(draws: Optional[dict], name: str, dev, dtype=torch.float64) -> Optional[torch.Tensor]:
+    """One array of injected draws (``draws[name]``, numpy or device) as a device tensor, or None (Philox)."""
+    if not draws or draws.get(name) is None:
+        return None
+    return _dev(draws[name], dev, dtype).reshape(-1)
+
+
+class Frontier:
+    """A Pareto frontier fitted on device: ``coef`` float64[deg+1] (highest power first, as np.polyfit),
+    ``pareto_idx`` int32 indices of the Pareto set, ``stats`` = (r2 deg 0..2, max y, min y).  ``poly`` reads the
+    coefficients back (one small copy) as the ``np.poly1d`` the reference keeps."""
+
+    def __init__(self, coef, deg, pareto_idx, pcount, stats):
+        self.coef_dev, self.deg_dev, self._pidx, self._pcount, self.stats = coef, deg, pareto_idx, pcount, stats
+
+    @property
+    def deg(self) -> int:
+        return int(self.deg_dev.item())
+
+    @property
+    def pareto_idx(self) -> torch.Tensor:
+        return self._pidx[:int(self._pcount.item())]
+
+    @property
+    def poly(self) -> np.poly1d:
+        return np.poly1d(self.coef_dev[:self.deg + 1].cpu().numpy())
+
+
+def _fit_frontier(c: torch.Tensor, r: torch.Tensor, deg: int, pick: bool = False) -> Frontier:
+    """Pareto set of (-c, r) then np.polyfit on it, all on device (fp64 inputs of length n)."""
+    lib, dev, n = L.load(), c.device, int(c.shape[0])
+    flag = torch.zeros(n, dtype=torch.int32, device=dev)
+    L.check(lib.osrl_pareto_mask(c.data_ptr(), r.data_ptr(), n, flag.data_ptr(), cur_stream()), "osrl_pareto_mask")
+    coef = torch.zeros(8, dtype=torch.float64, device=dev)
+    dego = torch.zeros(1, dtype=torch.int32, device=dev)
+    pidx = torch.zeros(n, dtype=torch.int32, device=dev)
+    pcnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    stats = torch.zeros(5, dtype=torch.float64, device=dev)
+    ws = torch.empty(int(lib.osrl_polyfit_ws_elems(n, 2 if pick else int(deg))), dtype=torch.float64, device=dev)
+    L.check(lib.osrl_polyfit(c.data_ptr(), r.data_ptr(), flag.data_ptr(), n, int(deg), int(pick), coef.data_ptr(),
+                             dego.data_ptr(), pidx.data_ptr(), pcnt.data_ptr(), stats.data_ptr(), ws.data_ptr(),
+                             cur_stream()), "osrl_polyfit")
+    return Frontier(coef, dego, pidx, pcnt, stats)
+
+
+def pareto_frontier(cost, rew, deg: int = 3, device="cuda") -> Frontier:
+    """``np.poly1d(np.polyfit(cost[P], rew[P], deg))`` over the Pareto set P of (-cost, rew) (oapackage's
+    ParetoDoubleLong in the reference, dataset.py:329-340), on device in fp64."""
+    if not 0 <= int(deg) <= 7:
+        raise ValueError(f"deg must be in 0..7, got {deg}")
+    dev = cost.device if torch.is_tensor(cost) else require_cuda(device)
+    c, r = _dev(cost, dev, torch.float64).reshape(-1), _dev(rew, dev, torch.float64).reshape(-1)
+    if c.shape != r.shape or c.numel() < 1:
+        raise ValueError("cost and rew must be non-empty and of one length")
+    return _fit_frontier(c, r, int(deg))
+
+
+def _bc_frontier_select(ep: "Episodes", cost_returns: torch.Tensor, rew_returns: torch.Tensor, idx, cnt) -> None:
+    """process_bc_dataset "frontier" (dataset.py:73-93): Pareto set of the episode returns, polyfit deg 0, 1, 2 until
+    r^2 >= 0.9, keep the transitions within (rmax - rmin) / 5 of the frontier."""
+    if ep.n_episodes < 1:
+        raise ValueError('bc_mode="frontier" needs at least one complete episode')
+    if ep.n_covered != ep.n:
+        # the reference leaves zero returns on these transitions and keeps or drops them by comparing 0 with the
+        # frontier at cost 0 -- an artefact of its loop, not a selection; cut the dataset at its last done flag
+        raise NotImplementedError(f'bc_mode="frontier" on a dataset whose last {ep.n - ep.n_covered} transitions '
+                                  "belong to no complete episode (no done flag after them)")
+    lib, dev = L.load(), ep.device
+    c0 = torch.empty(ep.n_episodes, dtype=torch.float64, device=dev)
+    r0 = torch.empty_like(c0)
+    L.check(lib.osrl_traj_returns(rew_returns.data_ptr(), cost_returns.data_ptr(), ep.start.data_ptr(), ep.n_episodes,
+                                  r0.data_ptr(), c0.data_ptr(), cur_stream()), "osrl_traj_returns")
+    fr = _fit_frontier(c0, r0, 2, pick=True)
+    mask = torch.empty(ep.n, dtype=torch.float32, device=dev)
+    L.check(lib.osrl_bc_frontier_select(cost_returns.data_ptr(), rew_returns.data_ptr(), ep.n, fr.coef_dev.data_ptr(),
+                                        fr.deg_dev.data_ptr(), fr.stats.data_ptr(), mask.data_ptr(), idx.data_ptr(),
+                                        cnt.data_ptr(), ep.ws.data_ptr(), cur_stream()), "osrl_bc_frontier_select")
+
+
+SEQ_KEYS = ("observations", "actions", "rewards", "costs", "returns", "cost_returns")
+
+
+def _traj_returns(tables):
+    lib, dev = L.load(), tables["returns"].device
+    n = int(tables["traj_start"].shape[0])
+    r0 = torch.empty(n, dtype=torch.float64, device=dev)
+    c0 = torch.empty_like(r0)
+    L.check(lib.osrl_traj_returns(tables["returns"].data_ptr(), tables["cost_returns"].data_ptr(),
+                                  tables["traj_start"].data_ptr(), n, r0.data_ptr(), c0.data_ptr(), cur_stream()),
+            "osrl_traj_returns")
+    return r0, c0
+
+
+def _combine(tables, nearest, map_, S: int, tc, tr, noise: bool = False, cstd: float = 0.0, rstd: float = 0.0,
+             draws: Optional[dict] = None, seed: int = 0):
+    """The original trajectories followed by one relabelled copy per sample (osrl_augment_layout / _gather)."""
+    lib, dev = L.load(), tables["returns"].device
+    n_traj = int(tables["traj_start"].shape[0])
+    n_rows = int(tables["returns"].shape[0])
+    new_start = torch.empty(n_traj + S, dtype=torch.int64, device=dev)
+    new_len = torch.empty(n_traj + S, dtype=torch.int32, device=dev)
+    src = torch.empty(max(S, 1), dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    L.check(lib.osrl_augment_layout(_ptr(nearest), _ptr(map_), S, tables["traj_start"].data_ptr(),
+                                    tables["traj_len"].data_ptr(), n_traj, n_rows, new_start.data_ptr(),
+                                    new_len.data_ptr(), src.data_ptr(), total.data_ptr(), cur_stream()),
+            "osrl_augment_layout")
+    rows = int(total.item())  # host read: sizes the combined tables
+    out = {}
+    for k in SEQ_KEYS:
+        v = tables[k]
+        t = torch.empty((rows,) + tuple(v.shape[1:]), dtype=torch.float32, device=dev)
+        t[:n_rows].copy_(v)
+        out[k] = t
+    nc = _injected(draws, "noise_c", dev) if noise else None
+    nr = _injected(draws, "noise_r", dev) if noise else None
+    if (nc is None) != (nr is None):
+        raise ValueError("inject both noise_c and noise_r, or neither")
+    if nc is not None and (nc.numel() < rows - n_rows or nr.numel() < rows - n_rows):
+        raise ValueError(f"injected noise rows: {rows - n_rows} needed")
+    obs, act = tables["observations"], tables["actions"]
+    od, ad = int(obs[0].numel()), int(act[0].numel())
+    L.check(lib.osrl_augment_gather(obs.data_ptr(), act.data_ptr(), tables["rewards"].data_ptr(),
+                                    tables["costs"].data_ptr(), tables["returns"].data_ptr(),
+                                    tables["cost_returns"].data_ptr(), od, ad, tables["traj_start"].data_ptr(),
+                                    src.data_ptr(), S, new_start.data_ptr(), new_len.data_ptr(), n_traj, _ptr(tc),
+                                    _ptr(tr), int(noise), float(cstd), float(rstd), _ptr(nc), _ptr(nr),
+                                    int(seed) & 0xFFFFFFFFFFFFFFFF, out["observations"].data_ptr(),
+                                    out["actions"].data_ptr(), out["rewards"].data_ptr(), out["costs"].data_ptr(),
+                                    out["returns"].data_ptr(), out["cost_returns"].data_ptr(), cur_stream()),
+            "osrl_augment_gather")
+    out["traj_start"], out["traj_len"] = new_start, new_len
+    return out
+
+
+def augmentation(tables: Dict[str, torch.Tensor], deg: int = 3, max_rew_decrease: float = 1.0, beta: float = 1.0,
+                 augment_percent: float = 0.3, max_reward: float = 1000.0, min_reward: float = 0.0, seed: int = 0,
+                 draws: Optional[dict] = None):
+    """``augmentation()`` (dataset.py:282-396) on the flat tables of ``process_sequence_dataset``: grid filter of the
+    trajectory returns, Pareto frontier polyfit, ``int(augment_percent * filtered)`` targets above the frontier, each
+    relabelling a copy of its nearest trajectory (or a drawn partner).  Returns ``(combined tables, info)``: the
+    tables hold the originals followed by the copies; ``info`` holds ``idx`` (the reference's nearest_idx, indices
+    into the filtered set), ``indices`` (filtered -> original trajectory), ``frontier`` (a ``Frontier``),
+    ``targets`` (cost, reward fp64) and the trajectory counts.  ``draws`` injects the random stream (see
+    include/osrl_amd.h): ``pick``, ``u_rew``, ``u_part``; otherwise Philox keyed by ``seed``."""
+    if not 0 <= int(deg) <= 7:
+        raise ValueError(f"deg must be in 0..7, got {deg}")
+    lib, dev = L.load(), tables["returns"].device
+    n_traj = int(tables["traj_start"].shape[0])
+    if n_traj < 1:
+        raise ValueError("augmentation needs at least one trajectory")
+    r0, c0 = _traj_returns(tables)
+    filt = torch.empty(n_traj, dtype=torch.int32, device=dev)
+    fx = torch.empty(n_traj, dtype=torch.float64, device=dev)
+    fy = torch.empty_like(fx)
+    cnt = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.osrl_grid_filter_ws_elems(n_traj)), dtype=torch.float64, device=dev)
+    pick = _injected(draws, "pick", dev, torch.int32)
+    L.check(lib.osrl_grid_filter(c0.data_ptr(), r0.data_ptr(), n_traj, FILTER_BINS[0], FILTER_BINS[1],
+                                 FILTER_PER_BIN[0], FILTER_PER_BIN[1], _ptr(pick), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                 filt.data_ptr(), fx.data_ptr(), fy.data_ptr(), cnt.data_ptr(), ws.data_ptr(),
+                                 cur_stream()), "osrl_grid_filter")
+    F = int(cnt.item())  # host read: the filtered count sizes everything after it
+    if F < 0:
+        raise ValueError("augmentation: every trajectory has the same cost return or the same return "
+                         "(the grid filter's bin width is 0)")
+    if F == 0:
+        raise ValueError("augmentation: the grid filter kept no trajectory (every bin holds 2 or fewer)")
+    fx, fy, filt = fx[:F], fy[:F], filt[:F]
+    fr = _fit_frontier(fx, fy, int(deg))
+    S = int(augment_percent * F)
+    tc = torch.empty(max(S, 1), dtype=torch.float64, device=dev)
+    tr = torch.empty_like(tc)
+    nearest = torch.empty(max(S, 1), dtype=torch.int32, device=dev)
+    if S > 0:
+        u_rew, u_part = _injected(draws, "u_rew", dev), _injected(draws, "u_part", dev)
+        if u_rew is not None and u_rew.numel() < S:
+            raise ValueError(f"injected u_rew: {S} draws needed")
+        ws2 = torch.empty(int(lib.osrl_augment_targets_ws_elems(F, S)), dtype=torch.float64, device=dev)
+        L.check(lib.osrl_augment_targets(fr.coef_dev.data_ptr(), fr.deg_dev.data_ptr(), fx.data_ptr(), fy.data_ptr(), F,
+                                         S, float(min_reward), float(max_reward), float(max_rew_decrease), float(beta),
+                                         _ptr(u_rew), _ptr(u_part), int(seed) & 0xFFFFFFFFFFFFFFFF, tc.data_ptr(),
+                                         tr.data_ptr(), nearest.data_ptr(), ws2.data_ptr(), cur_stream()),
+                "osrl_augment_targets")
+    out = _combine(tables, nearest if S else None, filt, S, tc, tr, seed=seed)
+    info = dict(idx=nearest[:S], indices=filt, frontier=fr, targets=(tc[:S], tr[:S]), n_original=n_traj,
+                n_augmented=S)
+    return out, info
+
+
+def random_augmentation(tables: Dict[str, torch.Tensor], augment_percent: float = 0.3, aug_rmin: float = 0,
+                        aug_rmax: float = 600, aug_cmin: float = 5, aug_cmax: float = 50, cgap: float = 5,
+                        rstd: float = 1, cstd: float = 0.25, seed: int = 0, draws: Optional[dict] = None):
+    """``random_augmentation()`` (dataset.py:557-630): ``int(augment_percent * n_traj)`` uniform (cost, reward)
+    targets, each relabelling a copy of the nearest trajectory below ``max(c - cgap, min c + 1)``, plus per-row
+    Gaussian noise.  Returns ``(combined tables, info)`` like ``augmentation``; ``draws``: ``u_cr``
+    ([samples, 2] uniforms), ``noise_c`` / ``noise_r`` (the normal rows, [augmented rows])."""
+    lib, dev = L.load(), tables["returns"].device
+    n_traj = int(tables["traj_start"].shape[0])
+    if n_traj < 1:
+        raise ValueError("random_augmentation needs at least one trajectory")
+    r0, c0 = _traj_returns(tables)
+    S = int(augment_percent * n_traj)
+    tc = torch.empty(max(S, 1), dtype=torch.float64, device=dev)
+    tr = torch.empty_like(tc)
+    nearest = torch.empty(max(S, 1), dtype=torch.int32, device=dev)
+    if S > 0:
+        u_cr = _injected(draws, "u_cr", dev)
+        if u_cr is not None and u_cr.numel() < 2 * S:
+            raise ValueError(f"injected u_cr: {2 * S} draws needed")
+        L.check(lib.osrl_random_aug_targets(c0.data_ptr(), r0.data_ptr(), n_traj, S, float(aug_cmin), float(aug_cmax),
+                                            float(aug_rmin), float(aug_rmax), float(cgap), _ptr(u_cr),
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF, tc.data_ptr(), tr.data_ptr(),
+                                            nearest.data_ptr(), cur_stream()), "osrl_random_aug_targets")
+    out = _combine(tables, nearest if S else None, None, S, tc, tr, noise=True, cstd=cstd, rstd=rstd, draws=draws,
+                   seed=seed)
+    info = dict(idx=nearest[:S], indices=None, frontier=None, targets=(tc[:S], tr[:S]), n_original=n_traj,
+                n_augmented=S)
+    return out, info

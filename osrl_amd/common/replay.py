@@ -128,7 +128,7 @@ def synthetic_transitions(n: int, od: int, ad: int, seed: int = 1, max_action: f
 
 class SequenceStore:
     """Device-resident trajectory store + on-device window sampler for CDT: replaces ``SequenceDataset``
-    (osrl/common/dataset.py:633-787; augmentation / Pareto constructor paths are out of scope) + DataLoader.
+    (osrl/common/dataset.py:633-787; ``from_dataset`` covers its augmentation paths) + DataLoader.
     ``trajectories``: list of dicts with observations [L,od], actions [L,ad], returns [L] (return-to-go),
     cost_returns [L] (cost-to-go), costs [L].  ``sample_prob``: optional per-trajectory probabilities
     (dataset.py:439-459 ``compute_cost_sample_prob`` output); None = uniform."""
@@ -195,13 +195,64 @@ class SequenceStore:
     def from_dataset(cls, dataset, seq_len: int, device, reward_scale: float = 1.0, cost_scale: float = 1.0,
                      cost_reverse: bool = False, cost_sample: bool = False,
                      cost_transform=("affine", -1.0, 50.0), seed: int = 0, rank: int = 0,
-                     start_sampling: bool = False, prob: float = 0.4) -> "SequenceStore":
-        """``SequenceDataset(dataset, seq_len, reward_scale, cost_scale, cost_reverse=, cost_sample=,
-        cost_transform=)`` (dataset.py:633-741, no augmentation) with the whole preprocessing on device."""
-        from .ingest import compute_cost_sample_prob, process_sequence_dataset
+                     start_sampling: bool = False, prob: float = 0.4, deg: int = 3, pf_sample: bool = False,
+                     max_rew_decrease: float = 1.0, beta: float = 1.0, augment_percent: float = 0,
+                     max_reward: float = 1000.0, min_reward: float = 5, pf_only: bool = False, rmin: float = 0,
+                     cost_bins: int = 60, npb: int = 5, random_aug: float = 0, aug_rmin: float = 0,
+                     aug_rmax: float = 600, aug_cmin: float = 5, aug_cmax: float = 50, cgap: float = 5,
+                     rstd: float = 1, cstd: float = 0.2, draws: Optional[dict] = None) -> "SequenceStore":
+        """``SequenceDataset(dataset, seq_len, reward_scale, cost_scale, ...)`` (dataset.py:633-747) with the whole
+        preprocessing on device.  The constructor's branches run in the reference's order: ``pf_only`` (which only
+        suppresses the augmentations: the reference discards select_optimal_trajectory's result), else
+        ``random_aug > 0`` (``common.ingest.random_augmentation``), else ``augment_percent > 0``
+        (``common.ingest.augmentation``); cost / start sampling then act on the original + augmented trajectories.
+        The random draws are keyed by ``seed`` (never the rank), so every data-parallel rank builds the same tables;
+        ``draws`` injects them instead (tests).  ``rmin``, ``cost_bins``, ``npb`` only feed the reference's discarded
+        ``pf_only`` selection and are accepted for signature parity."""
+        from .ingest import augmentation, compute_cost_sample_prob, process_sequence_dataset, random_augmentation
+        if pf_sample:
+            raise NotImplementedError("pf_sample=True (compute_sample_prob: a scipy BFGS solve per trajectory against "
+                                      "the Pareto frontier, dataset.py:399-436) is not supported; use cost_sample")
         tables = process_sequence_dataset(dataset, cost_reverse, device)
+        n_orig = int(tables["traj_start"].shape[0])
+        info = None
+        if pf_only:
+            pass
+        elif random_aug > 0:
+            tables, info = random_augmentation(tables, random_aug, aug_rmin, aug_rmax, aug_cmin, aug_cmax, cgap, rstd,
+                                               cstd, seed=seed, draws=draws)
+        elif augment_percent > 0:
+            tables, info = augmentation(tables, deg, max_rew_decrease, beta, augment_percent, max_reward, min_reward,
+                                        seed=seed, draws=draws)
         cdf = compute_cost_sample_prob(tables, cost_transform, with_cdf=True)[1] if cost_sample else None
-        return cls.from_tables(tables, seq_len, reward_scale, cost_scale, cdf, seed, rank, start_sampling, prob)
+        self = cls.from_tables(tables, seq_len, reward_scale, cost_scale, cdf, seed, rank, start_sampling, prob)
+        self.n_original = n_orig
+        self.n_augmented = 0 if info is None else int(info["n_augmented"])
+        self.aug_info = info
+        return self
+
+    # what SequenceDataset keeps after augmentation (dataset.py:718-738); read back from the device on access
+    @property
+    def idx(self):
+        info = getattr(self, "aug_info", None)
+        return None if info is None else info["idx"].cpu().numpy().astype(np.int64)
+
+    @property
+    def indices(self):
+        info = getattr(self, "aug_info", None)
+        return None if info is None or info["indices"] is None else info["indices"].cpu().numpy().astype(np.int64)
+
+    @property
+    def pareto_frontier(self):
+        info = getattr(self, "aug_info", None)
+        return None if info is None or info["frontier"] is None else info["frontier"].poly
+
+    def compute_pareto_return(self, cost):
+        """SequenceDataset.compute_pareto_return (dataset.py:746-747)."""
+        pf = self.pareto_frontier
+        if pf is None:
+            raise AttributeError("no Pareto frontier: the store was built without augment_percent")
+        return pf(cost)
 
     def gather(self, states, actions, returns, cost_returns, time_steps, mask, episode_cost, costs, st_ptr,
                idx_out=None, stream_id: int = 2, idx_in=None) -> None:
