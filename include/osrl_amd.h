@@ -987,6 +987,50 @@ int osrl_policy_io(void* handle, float** obs, float** noise, float** act, float*
 int osrl_policy_act(void* handle, int32_t rows, int32_t deterministic, int32_t host_noise, uint64_t seed, void* stream);
 int osrl_policy_destroy(void* handle);
 
+/* ---- CDT act latency path (cdt_act.hip) ----------------------------------------------------------------------
+ * CDTTrainer.rollout (cdt.py:436-518) on a host environment: one action per env step from the window of the last
+ * seq_len timesteps.  Falls under the policy-handle exception above: a handle owns a pinned, device-mapped I/O block
+ * (observation, taken action, returned action, reward / cost, sequence number) plus the device-resident window and
+ * every token's cached hidden state, and _reset / _step RETURN AFTER the action has been published.  Per env step only
+ * the work that changed runs: the new tokens while the window grows; from layer-0 attention on
+ * while it slides (layer-0 q / k / v stay cached); the cost-prefix token once per episode.
+ * Every weight pointer is a DEVICE pointer into the model's flat group: w_* / head_w = PACKED forward weights
+ * PF[k/4][n][k%4] (kept current by the fused optimizer step and repack()), the rest canonical row-major tensors.
+ * Domain: repeat * seq_len + cost_prefix <= 256 tokens, embedding_dim <= 512, head_dim <= 128, head_layers <= 4,
+ * head input / output widths <= 1024; outside it _create returns -1. */
+typedef struct {
+  const float *ln1_g, *ln1_b, *w_qkv, *b_qkv, *w_o, *b_o, *ln2_g, *ln2_b, *w_1, *b_1, *w_2, *b_2;
+} osrl_cdt_layer_t;
+typedef struct {
+  int32_t state_dim, action_dim, seq_len, embedding_dim, num_layers, num_heads;
+  int32_t use_rew, use_cost, cost_prefix, cost_transform; /* cost_transform: the cost token embeds 50 - ctg */
+  int32_t add_cost_feat, mul_cost_feat, cat_cost_feat;    /* effective flags (each implies use_cost) */
+  int32_t head_layers;    /* Linear layers of the action head (GELU between them) */
+  int32_t head_out_width; /* rows of the last head weight: action_dim, or 2 * action_dim for (mu | log_std) */
+  int32_t te_rows;        /* rows of the timestep embedding table */
+  float max_action;
+  int32_t pad_;
+  const float* te; /* timestep embedding [te_rows, E]; NULL = time_emb off */
+  const float *state_w, *state_b, *action_w, *action_b, *return_w, *return_b, *cost_w, *cost_b, *prefix_w, *prefix_b;
+  const float *emb_g, *emb_b, *out_g, *out_b;
+  const float* head_w[OSRL_MAX_LAYERS];
+  const float* head_b[OSRL_MAX_LAYERS];
+} osrl_cdt_policy_t;
+/* layers: [num_layers] (copied) */
+int osrl_cdt_policy_create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, void** handle);
+/* HOST pointers into the pinned block: obs [state_dim] and act_in [action_dim] (caller writes), act_out [action_dim] */
+int osrl_cdt_policy_io(void* handle, float** obs, float** act_in, float** act_out);
+/* starts an episode at timestep 0 with the observation in obs; the prefix token embeds target_cost */
+int osrl_cdt_policy_reset(void* handle, float target_return, float target_cost, void* stream);
+/* the previous step's action (act_in when host_action = 1, else the one returned), then obs / reward / cost of the new
+ * timestep: returns[t+1] = returns[t] - reward, costs[t+1] = costs[t] - cost (fp32).  -1 past the timestep table. */
+int osrl_cdt_policy_step(void* handle, float reward, float cost, int32_t host_action, void* stream);
+/* the current window, oldest timestep first: states [n, state_dim], actions [n, action_dim], returns / costs [n],
+ * time_steps [n]; n = min(t + 1, seq_len) (0 before the first reset).  Synchronises the stream. */
+int osrl_cdt_policy_window(void* handle, float* states, float* actions, float* returns, float* costs,
+                           int64_t* time_steps, int32_t* n, void* stream);
+int osrl_cdt_policy_destroy(void* handle);
+
 /* ---- data-parallel exchanges through IPC-mapped device buffers (ipc.hip, round 6; nothing to mirror in the reference: it
  * has no distributed code).  What the ranks of a data-parallel step exchange (flat
  * gradients per optimizer phase, CPQ's KL values, statistics) is latency-bound; a collective-library launch costs 16-19 us

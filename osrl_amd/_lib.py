@@ -148,6 +148,22 @@ POLICY_MLP, POLICY_GAUSS, POLICY_BCQ = 0, 1, 2
 POLICY_MAX_ROWS = 4
 
 
+class CdtLayerT(C.Structure):  # osrl_cdt_layer_t
+    _fields_ = [(n, C.c_void_p) for n in ("ln1_g", "ln1_b", "w_qkv", "b_qkv", "w_o", "b_o", "ln2_g", "ln2_b", "w_1",
+                                          "b_1", "w_2", "b_2")]
+
+
+class CdtPolicyT(C.Structure):  # osrl_cdt_policy_t
+    _fields_ = [(n, C.c_int32) for n in ("state_dim", "action_dim", "seq_len", "embedding_dim", "num_layers",
+                                         "num_heads", "use_rew", "use_cost", "cost_prefix", "cost_transform",
+                                         "add_cost_feat", "mul_cost_feat", "cat_cost_feat", "head_layers",
+                                         "head_out_width", "te_rows")] + \
+        [("max_action", C.c_float), ("pad_", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("te", "state_w", "state_b", "action_w", "action_b", "return_w", "return_b", "cost_w",
+                                   "cost_b", "prefix_w", "prefix_b", "emb_g", "emb_b", "out_g", "out_b")] + \
+        [("head_w", C.c_void_p * MAX_LAYERS), ("head_b", C.c_void_p * MAX_LAYERS)]
+
+
 class StepStateT(C.Structure):
     _fields_ = [("step", C.c_int64), ("bc1", C.c_float), ("bc2_sqrt", C.c_float),
                 ("lr_scale", C.c_float), ("arrive_", C.c_uint32)]
@@ -184,6 +200,12 @@ PROTOTYPES = {
     "osrl_policy_io": [_vp, _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float))],
     "osrl_policy_act": [_vp, _i32, _i32, _i32, _u64, _vp],
     "osrl_policy_destroy": [_vp],
+    "osrl_cdt_policy_create": [_P(CdtPolicyT), _P(CdtLayerT), _P(C.c_void_p)],
+    "osrl_cdt_policy_io": [_vp, _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float))],
+    "osrl_cdt_policy_reset": [_vp, _f32, _f32, _vp],
+    "osrl_cdt_policy_step": [_vp, _f32, _f32, _i32, _vp],
+    "osrl_cdt_policy_window": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "osrl_cdt_policy_destroy": [_vp],
     "osrl_cost_sample_prob": [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp],
     "osrl_start_index_prob": [_vp, _vp, _vp, _i32, C.c_double, _vp, _vp, _vp],
     "osrl_bc_select": [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp],

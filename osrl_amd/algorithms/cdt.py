@@ -118,6 +118,21 @@ class CDT(nn.Module):
             self.log_temperature = torch.full((1,), float(np.log(init_temperature)), dtype=torch.float32, device=dev)
             self.target_entropy = target_entropy
         self._engine = None
+        self._fast = None
+
+    def fast_policy(self):
+        """The act latency path for the episode loop on a host environment (engine/cdt_act.py ``CDTFastPolicy``), built
+        once per model.  Raises NotImplementedError naming the limit outside its domain."""
+        if getattr(self, "_fast", None) is None:
+            from ..engine.cdt_act import CDTFastPolicy
+            self._fast = CDTFastPolicy(self)
+        return self._fast
+
+    def fast_eligible(self) -> bool:
+        """The fast path computes the eval-mode forward: a model left in train() mode with dropout draws masks."""
+        from ..engine.cdt_act import unsupported
+        no_drop = max(self.attention_dropout, self.residual_dropout, self.embedding_dropout) == 0
+        return (not self.training or no_drop) and unsupported(self) is None
 
     @staticmethod
     def _init_weights(module: nn.Module):
@@ -214,7 +229,7 @@ class CDTTrainer:
                  lr_warmup_steps: int = 10000, reward_scale: float = 1.0, cost_scale: float = 1.0,
                  loss_cost_weight: float = 0.0, loss_state_weight: float = 0.0, cost_reverse: bool = False,
                  no_entropy: bool = False, device="cuda", stats_mode: str = "lazy", use_graph: bool = True,
-                 seed: int = 0) -> None:
+                 seed: int = 0, fast_rollout: bool = True) -> None:
         self.model, self.logger, self.env = model, logger, env
         self.clip_grad, self.reward_scale, self.cost_scale, self.device = clip_grad, reward_scale, cost_scale, device
         self.cost_weight, self.state_weight = loss_cost_weight, loss_state_weight
@@ -222,6 +237,7 @@ class CDTTrainer:
         self.stochastic = model.stochastic
         self.max_action = model.max_action
         self.stats_mode, self.use_graph = stats_mode, use_graph
+        self.fast_rollout = bool(fast_rollout)  # rollout() on host envs through CDT.fast_policy() when eligible
         self.cfg = dict(learning_rate=learning_rate, weight_decay=weight_decay, betas=tuple(betas),
                         clip_grad=clip_grad, lr_warmup_steps=lr_warmup_steps, loss_cost_weight=loss_cost_weight,
                         loss_state_weight=loss_state_weight, no_entropy=no_entropy, seed=int(seed))
@@ -261,7 +277,11 @@ class CDTTrainer:
 
     @torch.no_grad()
     def rollout(self, model: CDT, env, target_return: float, target_cost: float):
-        """cdt.py:436-518: autoregressive rollout on a sliding window of the last seq_len steps."""
+        """cdt.py:436-518: autoregressive rollout on a sliding window of the last seq_len steps.  With
+        ``fast_rollout`` and an eligible model (eval mode or no dropout, inside the act path's domain) the window lives
+        on the device and each env step is one C call (``CDT.fast_policy()``); otherwise the loop below."""
+        if self.fast_rollout and model.fast_eligible():
+            return self._rollout_fast(model, env, target_return, target_cost)
         dev = torch.device(model.device)
         EL, T = model.episode_len, model.seq_len
         states = torch.zeros(1, EL + 1, model.state_dim, device=dev)
@@ -293,4 +313,21 @@ class CDTTrainer:
             ep_cost += info["cost"]
             if terminated or truncated:
                 break
+        return ep_ret, ep_len, ep_cost
+
+    def _rollout_fast(self, model: CDT, env, target_return: float, target_cost: float):
+        pol = model.fast_policy()
+        obs, info = env.reset()
+        act = pol.reset(obs, target_return, target_cost)
+        ep_ret, ep_cost, ep_len = 0.0, 0.0, 0
+        EL = model.episode_len
+        for step in range(EL):
+            obs_next, reward, terminated, truncated, info = env.step(act)
+            cost = ((1.0 - info["cost"]) if self.cost_reverse else info["cost"]) * self.cost_scale
+            ep_ret += reward
+            ep_len += 1
+            ep_cost += info["cost"]
+            if terminated or truncated or step + 1 == EL:
+                break
+            act = pol.step(obs_next, reward, cost)
         return ep_ret, ep_len, ep_cost

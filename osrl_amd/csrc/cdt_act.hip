@@ -1,0 +1,713 @@
+// cdt_act.hip -- the B = 1 act latency path of the Constrained Decision Transformer's episode loop on gfx950.
+//
+// CDTTrainer.rollout (cdt.py:436-518) asks the model for one action per env step over a sliding window of the last
+// seq_len timesteps.  Run as a training-shaped forward that is ~30 launches over a window padded to seq_len plus a
+// host round trip per step.  A policy handle here keeps the window ON THE DEVICE together with every token's hidden
+// state, and per env step runs only the work that changed ("B = 1 act()"):
+//   * growth (t < seq_len): attention is causal, so no earlier token changes at any layer: only the previous
+//     step's action token (a zero dummy until now) and the new [return] [cost] state tokens go through the layers;
+//   * sliding (t >= seq_len): the blocks are pre-norm, so a token's layer-0 q / k / v depend on its own embedding
+//     (value + absolute timestep) alone and stay cached; layer-0 attention onward is recomputed for the window
+//     (every token lost the dropped keys), and the last layer runs past its q / k / v for the newest state token
+//     only;
+//   * the cost-prefix token attends to itself alone: its hidden states are computed once at reset.
+// One env step = one ingest/embed launch, five launches per layer (LN1+QKV, attention, out-proj+residual,
+// LN2+MLP-up+GELU, MLP-down+residual) and one head launch, which writes the action into pinned, device-mapped memory
+// and publishes a sequence number (system-scope release) the host spins on, as act.hip does.  No launch waits on
+// another workgroup.  The projections are fp32 MFMA (v_mfma_f32_16x16x4f32) over 16-row tiles of the packed forward
+// weights PF[k/4][n][k%4] (the copies the fused AdamW step and repack() keep current), split-K over the four waves
+// of a workgroup and summed in LDS in a fixed order: results do not depend on scheduling.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <atomic>
+#include <chrono>
+#include <new>
+#include <vector>
+
+#include "../../include/osrl_amd.h"
+#include "gelu.h"
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+constexpr int kMaxE = 512, kMaxD = 128, kMaxTok = 256, kMaxHead = 1024;
+constexpr float kLnEps = 1e-5f;
+
+__device__ __forceinline__ int r16(int x) { return (x + 15) & ~15; }
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
+// mean / rstd of one row of E <= 512 floats, by one wave (two passes, as the training LayerNorm)
+__device__ __forceinline__ void row_stats(const float* __restrict__ x, int E, int lane, float* mean_o, float* rstd_o) {
+  float v[kMaxE / 64];
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < kMaxE / 64; ++j) {
+    const int f = lane + 64 * j;
+    v[j] = f < E ? x[f] : 0.f;
+    s += v[j];
+  }
+  const float mean = wave_sum(s) / (float)E;
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < kMaxE / 64; ++j)
+    if (lane + 64 * j < E) q += (v[j] - mean) * (v[j] - mean);
+  *mean_o = mean;
+  *rstd_o = 1.0f / sqrtf(wave_sum(q) / (float)E + kLnEps);
+}
+
+// ring row of entry i of a row set: (first + i) mod ring
+__device__ __forceinline__ int ring_row(int first, int i, int ring) {
+  const int r = first + i;
+  return r < ring ? r : r - ring;
+}
+
+struct Dev {  // device view of a handle's buffers
+  float *win_s, *win_a, *win_r, *win_c;  // ring [T, od] / [T, ad] / [T] / [T]: slot = timestep mod T
+  int32_t* win_t;                        // [T] absolute timestep
+  float* last_act;                       // [ad] the action the head returned last
+  float* raw;                            // [NR, ldE] pre-LayerNorm embeddings (cost features read the cost token's)
+};
+
+struct Io {  // pinned + device-mapped
+  float *obs, *act_in, *act_out, *scalars;  // scalars: reward, cost, target_return, target_cost
+  uint64_t* seq;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// ingest + embedding: update the device window from the I/O block, then embed + LayerNorm the listed token rows.
+struct IngestArgs {
+  osrl_cdt_policy_t p;
+  Dev d;
+  Io io;
+  float* x0;  // [NR, ldE] emb LayerNorm output
+  int32_t ldE, R, TR, t, reset, host_action;
+  int32_t first, count, ring;  // token rows to embed
+};
+
+__global__ __launch_bounds__(256) void cdt_act_ingest_kernel(const IngestArgs a) {
+  const osrl_cdt_policy_t& p = a.p;
+  const int tid = threadIdx.x, T = p.seq_len, od = p.state_dim, ad = p.action_dim;
+  const int cur = a.t % T;
+  if (a.reset) {
+    for (int i = tid; i < od; i += blockDim.x) a.d.win_s[i] = a.io.obs[i];
+    if (tid == 0) {
+      a.d.win_r[0] = a.io.scalars[2];
+      a.d.win_c[0] = a.io.scalars[3];
+      a.d.win_t[0] = 0;
+    }
+  } else {
+    const int prv = (a.t - 1) % T;
+    for (int i = tid; i < ad && T > 1; i += blockDim.x)  // (seq_len 1: the previous timestep left the window)
+      a.d.win_a[prv * ad + i] = a.host_action ? a.io.act_in[i] : a.d.last_act[i];
+    for (int i = tid; i < od; i += blockDim.x) a.d.win_s[cur * od + i] = a.io.obs[i];
+    if (tid == 0) {  // returns[t+1] = returns[t] - float(reward); costs[t+1] = costs[t] - cost  (fp32, cdt.py:506-507)
+      a.d.win_r[cur] = a.d.win_r[prv] - a.io.scalars[0];
+      a.d.win_c[cur] = a.d.win_c[prv] - a.io.scalars[1];
+      a.d.win_t[cur] = a.t;
+    }
+  }
+  for (int i = tid; i < ad; i += blockDim.x) a.d.win_a[cur * ad + i] = 0.f;  // the newest action slot: zero dummy
+  __syncthreads();
+  const int lane = tid & 63, E = p.embedding_dim;
+  for (int i = tid >> 6; i < a.count; i += blockDim.x >> 6) {
+    const int row = ring_row(a.first, i, a.ring);
+    const bool is_prefix = row == a.TR;
+    const int ts = is_prefix ? 0 : row / a.R, slot = is_prefix ? 0 : row - ts * a.R;
+    int which = slot + (4 - a.R);  // 0 return, 1 cost, 2 state, 3 action (cdt.py:185-200)
+    if (a.R == 3 && p.use_rew) which = slot == 0 ? 0 : slot + 1;
+    const float* te = (p.te && !is_prefix) ? p.te + (size_t)a.d.win_t[ts] * E : nullptr;
+    const float ret = a.d.win_r[ts];
+    const float ctg = p.cost_transform ? 50.0f - a.d.win_c[ts] : a.d.win_c[ts];
+    const float ec = a.io.scalars[3];
+    float v[kMaxE / 64];
+#pragma unroll
+    for (int j = 0; j < kMaxE / 64; ++j) {
+      const int f = lane + 64 * j;
+      float x = 0.f;
+      if (f < E) {
+        if (is_prefix) {
+          x = ec * p.prefix_w[f] + p.prefix_b[f];
+        } else if (which == 0) {
+          x = ret * p.return_w[f] + p.return_b[f];
+        } else if (which == 1) {
+          x = ctg * p.cost_w[f] + p.cost_b[f];
+        } else if (which == 2) {
+          x = p.state_b[f];
+#pragma unroll 4
+          for (int k = 0; k < od; ++k) x += a.d.win_s[ts * od + k] * p.state_w[(size_t)f * od + k];
+        } else {
+          x = p.action_b[f];
+          for (int k = 0; k < ad; ++k) x += a.d.win_a[ts * ad + k] * p.action_w[(size_t)f * ad + k];
+        }
+        if (te) x += te[f];
+        a.d.raw[(size_t)row * a.ldE + f] = x;
+      }
+      v[j] = x;
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < kMaxE / 64; ++j) s += v[j];
+    const float mean = wave_sum(s) / (float)E;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < kMaxE / 64; ++j)
+      if (lane + 64 * j < E) q += (v[j] - mean) * (v[j] - mean);
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)E + kLnEps);
+#pragma unroll
+    for (int j = 0; j < kMaxE / 64; ++j) {
+      const int f = lane + 64 * j;
+      if (f < E) a.x0[(size_t)row * a.ldE + f] = (v[j] - mean) * rstd * p.emb_g[f] + p.emb_b[f];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Y[r] = epi(LN?(X[r]) W^T + b) for the rows of a row set: one workgroup = one 16-row x 16-column tile, four waves
+// split K and meet in LDS.  epi: optional exact GELU, then an optional residual add.
+struct LinArgs {
+  const float* X;
+  const float *ln_g, *ln_b;  // LayerNorm of the input rows (K = E) or null
+  const float* W;            // packed PF[k/4][n][k%4], Np = r16(N) columns
+  const float* bias;
+  const float* res;  // residual rows (same row index) or null
+  float* Y;
+  int32_t ldx, ldr, ldy, K, N, gelu;
+  int32_t first, count, ring;
+};
+
+__global__ __launch_bounds__(256) void cdt_act_linear_kernel(const LinArgs a) {
+  __shared__ float red[4][64][4];
+  __shared__ float st[16][2];
+  __shared__ int rows[16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int r0 = blockIdx.y * 16, n0 = blockIdx.x * 16;
+  if (tid < 16) rows[tid] = r0 + tid < a.count ? ring_row(a.first, r0 + tid, a.ring) : -1;
+  __syncthreads();
+  if (a.ln_g) {
+    for (int i = w; i < 16; i += 4) {
+      float mean = 0.f, rstd = 0.f;
+      if (rows[i] >= 0) row_stats(a.X + (size_t)rows[i] * a.ldx, a.K, lane, &mean, &rstd);
+      if (lane == 0) {
+        st[i][0] = mean;
+        st[i][1] = rstd;
+      }
+    }
+    __syncthreads();
+  }
+  const int ar = lane & 15, kq = lane >> 4;
+  const int row = rows[ar];
+  const float* __restrict__ xr = row >= 0 ? a.X + (size_t)row * a.ldx : nullptr;
+  const float mean = a.ln_g ? st[ar][0] : 0.f, rstd = a.ln_g ? st[ar][1] : 1.f;
+  const int Np = r16(a.N), nkb = r16(a.K) >> 4;
+  const int kb0 = (nkb * w) >> 2, kb1 = (nkb * (w + 1)) >> 2;
+  const f32x4* __restrict__ W4 = reinterpret_cast<const f32x4*>(a.W);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  // kC k-blocks per round: every load of the round is issued before the first MFMA (the loop is latency-bound:
+  // a few k-blocks per wave at these row counts).  Rows' padding columns are zero (never written, zeroed at create).
+  constexpr int kC = 8;
+  for (int kc = kb0; kc < kb1; kc += kC) {
+    f32x4 bv[kC], av[kC], gv[kC], be[kC];
+#pragma unroll
+    for (int u = 0; u < kC; ++u) {
+      const int kb = kc + u, k0 = 16 * kb + 4 * kq;
+      bv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      av[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      gv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      be[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (kb < kb1) {
+        bv[u] = W4[(size_t)(4 * kb + kq) * Np + n0 + ar];
+        if (xr) av[u] = *reinterpret_cast<const f32x4*>(xr + k0);
+        if (a.ln_g) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+            if (k0 + t < a.K) {
+              gv[u][t] = a.ln_g[k0 + t];
+              be[u][t] = a.ln_b[k0 + t];
+            }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kC; ++u) {
+      if (a.ln_g && xr) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) av[u][t] = (av[u][t] - mean) * rstd * gv[u][t] + be[u][t];  // (0 past K: g = b = 0)
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][t], bv[u][t], acc, 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[w][lane][i] = acc[i];
+  __syncthreads();
+  if (w == 0) {
+    const int col = n0 + (lane & 15);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int rr = (lane >> 4) * 4 + i;
+      const int orow = rows[rr];
+      if (orow < 0 || col >= a.N) continue;
+      float v = ((red[0][lane][i] + red[1][lane][i]) + red[2][lane][i]) + red[3][lane][i];
+      v += a.bias[col];
+      if (a.gelu) v = gelu_f(v);
+      if (a.res) v += a.res[(size_t)orow * a.ldr + col];
+      a.Y[(size_t)orow * a.ldy + col] = v;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// causal softmax attention of the listed query rows over the window (+ the prefix token): one wave per (row, head).
+struct AttnArgs {
+  const float* qkv;  // [NR, ldq]: q | k | v
+  float* o;          // [NR, ldo]
+  int32_t ldq, ldo, E, H, d, P, TR, ws;  // ws: ring row of the window's first token
+  float scale;
+  int32_t first, count, ring;
+};
+
+__global__ __launch_bounds__(64) void cdt_act_attn_kernel(const AttnArgs a) {
+  __shared__ float pr[kMaxTok];
+  const int lane = threadIdx.x, h = blockIdx.y;
+  const int row = ring_row(a.first, blockIdx.x, a.ring);
+  // keys: the prefix (ring row TR) first, then the window's tokens up to and including the query
+  const int nk = row == a.TR ? 1 : a.P + (row - a.ws + a.TR) % a.TR + 1;
+  const float* __restrict__ q = a.qkv + (size_t)row * a.ldq + h * a.d;
+  float s[kMaxTok / 64];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < kMaxTok / 64; ++c) {
+    const int j = lane + 64 * c;
+    s[c] = -INFINITY;
+    if (j < nk) {
+      const int kr = j < a.P ? a.TR : (a.ws + j - a.P) % a.TR;
+      const float* __restrict__ k = a.qkv + (size_t)kr * a.ldq + a.E + h * a.d;
+      float acc = 0.f;
+#pragma unroll 8
+      for (int i = 0; i < a.d; ++i) acc = fmaf(q[i], k[i], acc);
+      s[c] = acc * a.scale;
+      mx = fmaxf(mx, s[c]);
+    }
+  }
+  mx = wave_max(mx);
+  float sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < kMaxTok / 64; ++c) {
+    const int j = lane + 64 * c;
+    if (j < nk) {
+      const float e = expf(s[c] - mx);
+      pr[j] = e;
+      sum += e;
+    }
+  }
+  const float inv = 1.0f / wave_sum(sum);
+  __syncthreads();
+  for (int i = lane; i < a.d; i += 64) {
+    float acc = 0.f;
+#pragma unroll 4
+    for (int j = 0; j < nk; ++j) {
+      const int kr = j < a.P ? a.TR : (a.ws + j - a.P) % a.TR;
+      acc = fmaf(pr[j], a.qkv[(size_t)kr * a.ldq + 2 * a.E + h * a.d + i], acc);
+    }
+    a.o[(size_t)row * a.ldo + h * a.d + i] = acc * inv;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// head: out LayerNorm of the newest state token, cost features, the action head's Linear (+ GELU) layers as GEMVs
+// (lanes own outputs over the packed weights, as act.hip), clamp, publish.
+struct HeadArgs {
+  osrl_cdt_policy_t p;
+  Dev d;
+  Io io;
+  const float* x;  // [NR, ldE] the last block's output
+  int32_t ldE, srow, crow;  // newest state token row, its cost token row (-1: none)
+  uint64_t seq;
+};
+
+constexpr int kHeadThreads = 1024;
+
+__global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadArgs a) {
+  __shared__ __attribute__((aligned(16))) float buf[2][kMaxHead];
+  __shared__ float red[kHeadThreads];
+  __shared__ float st[2];
+  const osrl_cdt_policy_t& p = a.p;
+  const int tid = threadIdx.x, E = p.embedding_dim;
+  if (tid < 64) {
+    float mean, rstd;
+    row_stats(a.x + (size_t)a.srow * a.ldE, E, tid, &mean, &rstd);
+    if (tid == 0) {
+      st[0] = mean;
+      st[1] = rstd;
+    }
+  }
+  __syncthreads();
+  const int Eh = p.cat_cost_feat ? 2 * E : E;
+  for (int f = tid; f < kMaxHead; f += kHeadThreads) {
+    float v = 0.f;
+    if (f < E) {
+      v = (a.x[(size_t)a.srow * a.ldE + f] - st[0]) * st[1] * p.out_g[f] + p.out_b[f];
+      if (a.crow >= 0) {  // cdt.py:243-250, the detached (pre-LayerNorm) cost embedding
+        const float ce = a.d.raw[(size_t)a.crow * a.ldE + f];
+        if (p.add_cost_feat) {
+          v = v + ce;
+          if (p.mul_cost_feat) v = v * ce;
+        } else if (p.mul_cost_feat) {
+          v = v * ce;
+        }
+      }
+    } else if (f < Eh) {
+      v = a.d.raw[(size_t)a.crow * a.ldE + (f - E)];
+    }
+    buf[0][f] = v;
+  }
+  __syncthreads();
+  int cur = 0, in = Eh;
+  const int nl = p.head_layers;
+  for (int l = 0; l < nl; ++l) {
+    const bool last = l == nl - 1;
+    const int out = last ? p.action_dim : Eh;
+    const int Np = last ? r16(p.head_out_width) : r16(Eh);
+    const int nq = r16(in) >> 2;
+    const f32x4* __restrict__ W4 = reinterpret_cast<const f32x4*>(p.head_w[l]);
+    // 1024 threads = KS k-splits x NL neuron lanes
+    int NL = 16;
+    while (NL < r16(out) && NL < 256) NL <<= 1;
+    const int KS = kHeadThreads / NL, ks = tid / NL, nl_ = tid - ks * NL;
+    const int q0 = (nq * ks) / KS, q1 = (nq * (ks + 1)) / KS;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};  // neurons nl_ + 256 j (out <= 1024)
+    for (int q = q0; q < q1; ++q) {
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(&buf[cur][4 * q]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int n = nl_ + 256 * j;
+        if (n < NL * (j + 1) && n < r16(out)) {
+          const f32x4 wv = W4[(size_t)q * Np + n];
+          acc[j] = fmaf(wv[0], xv[0], fmaf(wv[1], xv[1], fmaf(wv[2], xv[2], fmaf(wv[3], xv[3], acc[j]))));
+        }
+      }
+    }
+    // partials [KS][NL] per 256-neuron chunk, summed in k-split order
+    float* nxt = buf[cur ^ 1];
+    for (int j = 0; j < 4; ++j) {
+      if (256 * j >= r16(out)) break;
+      __syncthreads();
+      red[tid] = acc[j];
+      __syncthreads();
+      for (int n = 256 * j + tid; n < 256 * (j + 1) && n < r16(out) && tid < NL; n += kHeadThreads) {
+        float s = 0.f;
+        for (int k = 0; k < KS; ++k) s += red[k * NL + (n - 256 * j)];
+        float v = 0.f;
+        if (n < out) {
+          v = s + p.head_b[l][n];
+          if (!last) v = gelu_f(v);
+        }
+        nxt[n] = v;
+      }
+    }
+    __syncthreads();
+    for (int f = r16(out) + tid; f < kMaxHead; f += kHeadThreads) nxt[f] = 0.f;  // the next layer's k padding
+    __syncthreads();
+    cur ^= 1;
+    in = out;
+  }
+  if (tid < p.action_dim) {
+    const float v = fminf(fmaxf(buf[cur][tid], -p.max_action), p.max_action);
+    a.io.act_out[tid] = v;
+    a.d.last_act[tid] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence_system();
+    __hip_atomic_store(a.io.seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+struct Handle {
+  osrl_cdt_policy_t p;
+  std::vector<osrl_cdt_layer_t> layers;
+  int R, P, TR, NR, ldE, ld3, ld4;
+  int t;  // timestep of the newest window entry; -1 before the first reset
+  Io host, dev;
+  void* pinned;
+  Dev d;
+  void* dmem;
+  float *x, *qkv, *o, *xmid, *h;  // x: [NL + 1][NR, ldE], qkv: [NL][NR, ld3]
+  uint64_t seq;
+};
+
+int launch_linear(const Handle* h, const float* X, int ldx, const float* g, const float* b, const float* W,
+                  const float* bias, const float* res, int ldr, float* Y, int ldy, int K, int N, int gelu, int first,
+                  int count, int ring, hipStream_t s) {
+  if (count <= 0) return 0;
+  LinArgs a{X, g, b, W, bias, res, Y, ldx, ldr, ldy, K, N, gelu, first, count, ring};
+  hipLaunchKernelGGL(cdt_act_linear_kernel, dim3((N + 15) / 16, (count + 15) / 16), dim3(256), 0, s, a);
+  return 0;
+}
+
+// one block over the rows `first, count` (mod ring); `out_rows` = the rows past the q / k / v stage (null = the same)
+void run_layer(const Handle* h, int l, int first, int count, int ring, int ofirst, int ocount, int oring, int ws,
+               hipStream_t s) {
+  const osrl_cdt_policy_t& p = h->p;
+  const osrl_cdt_layer_t& L = h->layers[l];
+  const int E = p.embedding_dim;
+  const size_t xs = (size_t)h->NR * h->ldE;
+  const float* xin = h->x + l * xs;
+  float* xout = h->x + (l + 1) * xs;
+  float* qkv = h->qkv + (size_t)l * h->NR * h->ld3;
+  launch_linear(h, xin, h->ldE, L.ln1_g, L.ln1_b, L.w_qkv, L.b_qkv, nullptr, 0, qkv, h->ld3, E, 3 * E, 0, first, count,
+                ring, s);
+  if (ocount <= 0) return;
+  const int d = E / p.num_heads;
+  AttnArgs at{qkv, h->o, h->ld3, h->ldE, E, p.num_heads, d, h->P, h->TR, ws, 1.0f / sqrtf((float)d), ofirst, ocount,
+              oring};
+  hipLaunchKernelGGL(cdt_act_attn_kernel, dim3(ocount, p.num_heads), dim3(64), 0, s, at);
+  launch_linear(h, h->o, h->ldE, nullptr, nullptr, L.w_o, L.b_o, xin, h->ldE, h->xmid, h->ldE, E, E, 0, ofirst, ocount,
+                oring, s);
+  launch_linear(h, h->xmid, h->ldE, L.ln2_g, L.ln2_b, L.w_1, L.b_1, nullptr, 0, h->h, h->ld4, E, 4 * E, 1, ofirst,
+                ocount, oring, s);
+  launch_linear(h, h->h, h->ld4, nullptr, nullptr, L.w_2, L.b_2, h->xmid, h->ldE, xout, h->ldE, 4 * E, E, 0, ofirst,
+                ocount, oring, s);
+}
+
+int spin(Handle* h, hipStream_t s) {
+  volatile uint64_t* seq = h->host.seq;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (uint32_t it = 0;; ++it) {
+    if (*seq >= h->seq) break;
+    if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
+      const hipError_t e = hipStreamSynchronize(s);
+      if (e != hipSuccess) return (int)e;
+      if (*seq < h->seq) return -2;  // the chain ran but did not publish: should be impossible
+      break;
+    }
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return 0;
+}
+
+// the chain of one env step (t = h->t already advanced); reset: the prefix row joins the embedded rows
+int run_step(Handle* h, int reset, int host_action, hipStream_t s) {
+  const osrl_cdt_policy_t& p = h->p;
+  const int T = p.seq_len, R = h->R, TR = h->TR, t = h->t, NL = p.num_layers;
+  const int cur = (t % T) * R;
+  // rows whose embedding (and, in growth, every layer) is new: the previous action token + this step's tokens
+  int first, count, ring = TR;
+  if (t == 0) {
+    first = h->P && reset ? TR : 0;
+    count = R - 1 + (h->P && reset ? 1 : 0);
+    ring = TR + 1;
+  } else {
+    first = (cur - 1 + TR) % TR;
+    count = R;
+  }
+  IngestArgs ia{p, h->d, h->dev, h->x, h->ldE, R, TR, t, reset, host_action, first, count, ring};
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(cdt_act_ingest_kernel, dim3(1), dim3(256), 0, s, ia);
+  const int n = t + 1 < T ? t + 1 : T;            // timesteps in the window
+  const int ws = ((t + 1 - n) % T) * R;            // ring row of its first token
+  const int srow = cur + R - 2;                    // the newest state token
+  const int wcount = n * R - 1;                    // window tokens without the newest (dummy) action token
+  const bool sliding = t >= T;
+  for (int l = 0; l < NL; ++l) {
+    const bool lastl = l == NL - 1;
+    int qf = first, qc = count, qr = ring;         // rows through LN1 + q / k / v
+    int of = first, oc = count, orr = ring;        // rows through attention .. MLP
+    if (sliding) {
+      of = ws, oc = wcount, orr = TR;
+      if (l > 0) qf = ws, qc = wcount, qr = TR;
+    }
+    if (lastl) of = srow, oc = 1, orr = TR;
+    run_layer(h, l, qf, qc, qr, of, oc, orr, ws, s);
+  }
+  HeadArgs ha{p, h->d, h->dev, h->x + (size_t)NL * h->NR * h->ldE, h->ldE, srow,
+              (p.add_cost_feat || p.mul_cost_feat || p.cat_cost_feat) ? cur + (p.use_rew ? 1 : 0) : -1, ++h->seq};
+  hipLaunchKernelGGL(cdt_act_head_kernel, dim3(1), dim3(kHeadThreads), 0, s, ha);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  return spin(h, s);
+}
+
+bool valid(const osrl_cdt_policy_t& p, const osrl_cdt_layer_t* layers) {
+  if (p.state_dim < 1 || p.action_dim < 1 || p.seq_len < 1 || p.num_layers < 1 || p.num_heads < 1) return false;
+  const int E = p.embedding_dim, R = 2 + (p.use_rew ? 1 : 0) + (p.use_cost ? 1 : 0);
+  if (E < 1 || E > kMaxE || E % p.num_heads || E / p.num_heads > kMaxD) return false;
+  if (R * p.seq_len + (p.cost_prefix ? 1 : 0) > kMaxTok) return false;
+  if (p.head_layers < 1 || p.head_layers > OSRL_MAX_LAYERS || p.head_out_width < p.action_dim) return false;
+  if ((p.cat_cost_feat ? 2 * E : E) > kMaxHead || p.head_out_width > kMaxHead) return false;
+  if ((p.add_cost_feat || p.mul_cost_feat || p.cat_cost_feat) && !p.use_cost) return false;
+  if (!layers || !p.state_w || !p.state_b || !p.action_w || !p.action_b || !p.emb_g || !p.emb_b || !p.out_g ||
+      !p.out_b)
+    return false;
+  if ((p.use_rew && (!p.return_w || !p.return_b)) || (p.use_cost && (!p.cost_w || !p.cost_b)) ||
+      (p.cost_prefix && (!p.prefix_w || !p.prefix_b)))
+    return false;
+  for (int l = 0; l < p.head_layers; ++l)
+    if (!p.head_w[l] || !p.head_b[l]) return false;
+  for (int l = 0; l < p.num_layers; ++l) {
+    const osrl_cdt_layer_t& L = layers[l];
+    if (!L.ln1_g || !L.ln1_b || !L.w_qkv || !L.b_qkv || !L.w_o || !L.b_o || !L.ln2_g || !L.ln2_b || !L.w_1 || !L.b_1 ||
+        !L.w_2 || !L.b_2)
+      return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int osrl_cdt_policy_create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, void** handle) {
+  if (!desc || !handle || !valid(*desc, layers)) return -1;
+  const osrl_cdt_policy_t& p = *desc;
+  Handle* h = new (std::nothrow) Handle;
+  if (!h) return -1;
+  h->p = p;
+  h->layers.assign(layers, layers + p.num_layers);
+  h->R = 2 + (p.use_rew ? 1 : 0) + (p.use_cost ? 1 : 0);
+  h->P = p.cost_prefix ? 1 : 0;
+  h->TR = h->R * p.seq_len;
+  h->NR = h->TR + 1;
+  auto up16 = [](int x) { return (x + 15) & ~15; };
+  const int E = p.embedding_dim, T = p.seq_len, od = p.state_dim, ad = p.action_dim, NL = p.num_layers;
+  h->ldE = up16(E), h->ld3 = up16(3 * E), h->ld4 = up16(4 * E);
+  h->t = -1;
+  h->seq = 0;
+  auto r256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
+  // pinned block: obs, act_in, act_out, scalars, seq
+  const size_t o_obs = 0, o_ain = o_obs + r256(4 * od), o_aout = o_ain + r256(4 * ad), o_sc = o_aout + r256(4 * ad),
+               o_seq = o_sc + 256, pbytes = o_seq + 256;
+  hipError_t e = hipHostMalloc(&h->pinned, pbytes, hipHostMallocMapped | hipHostMallocPortable);
+  if (e != hipSuccess) {
+    delete h;
+    return (int)e;
+  }
+  memset(h->pinned, 0, pbytes);
+  void* dptr = nullptr;
+  e = hipHostGetDevicePointer(&dptr, h->pinned, 0);
+  if (e != hipSuccess) {
+    (void)hipHostFree(h->pinned);
+    delete h;
+    return (int)e;
+  }
+  auto at = [](void* base, size_t off) { return reinterpret_cast<char*>(base) + off; };
+  h->host = Io{(float*)at(h->pinned, o_obs), (float*)at(h->pinned, o_ain), (float*)at(h->pinned, o_aout),
+               (float*)at(h->pinned, o_sc), (uint64_t*)at(h->pinned, o_seq)};
+  h->dev = Io{(float*)at(dptr, o_obs), (float*)at(dptr, o_ain), (float*)at(dptr, o_aout), (float*)at(dptr, o_sc),
+              (uint64_t*)at(dptr, o_seq)};
+  // device block: window ring, last action, raw embeddings, activations (zeroed: the row strides' padding stays 0)
+  const size_t NR = h->NR;
+  size_t off = 0;
+  auto take = [&](size_t floats) {
+    const size_t o = off;
+    off += r256(4 * floats);
+    return o;
+  };
+  const size_t o_s = take((size_t)T * od), o_a = take((size_t)T * ad), o_r = take(T), o_c = take(T), o_t = take(T),
+               o_la = take(ad), o_raw = take(NR * h->ldE), o_x = take((size_t)(NL + 1) * NR * h->ldE),
+               o_q = take((size_t)NL * NR * h->ld3), o_o = take(NR * h->ldE), o_m = take(NR * h->ldE),
+               o_h = take(NR * h->ld4);
+  e = hipMalloc(&h->dmem, off);
+  if (e == hipSuccess) e = hipMemset(h->dmem, 0, off);
+  if (e != hipSuccess) {
+    if (h->dmem) (void)hipFree(h->dmem);
+    (void)hipHostFree(h->pinned);
+    delete h;
+    return (int)e;
+  }
+  char* base = (char*)h->dmem;
+  h->d = Dev{(float*)(base + o_s), (float*)(base + o_a), (float*)(base + o_r), (float*)(base + o_c),
+             (int32_t*)(base + o_t), (float*)(base + o_la), (float*)(base + o_raw)};
+  h->x = (float*)(base + o_x);
+  h->qkv = (float*)(base + o_q);
+  h->o = (float*)(base + o_o);
+  h->xmid = (float*)(base + o_m);
+  h->h = (float*)(base + o_h);
+  *handle = h;
+  return 0;
+}
+
+extern "C" int osrl_cdt_policy_io(void* handle, float** obs, float** act_in, float** act_out) {
+  if (!handle) return -1;
+  Handle* h = static_cast<Handle*>(handle);
+  if (obs) *obs = h->host.obs;
+  if (act_in) *act_in = h->host.act_in;
+  if (act_out) *act_out = h->host.act_out;
+  return 0;
+}
+
+extern "C" int osrl_cdt_policy_reset(void* handle, float target_return, float target_cost, void* stream) {
+  if (!handle) return -1;
+  Handle* h = static_cast<Handle*>(handle);
+  h->host.scalars[2] = target_return;
+  h->host.scalars[3] = target_cost;
+  h->t = 0;
+  return run_step(h, 1, 0, (hipStream_t)stream);
+}
+
+extern "C" int osrl_cdt_policy_step(void* handle, float reward, float cost, int32_t host_action, void* stream) {
+  if (!handle) return -1;
+  Handle* h = static_cast<Handle*>(handle);
+  if (h->t < 0) return -1;  // no episode started
+  if (h->p.te && h->t + 1 >= h->p.te_rows) return -1;  // past the timestep embedding table
+  h->host.scalars[0] = reward;
+  h->host.scalars[1] = cost;
+  ++h->t;
+  return run_step(h, 0, host_action ? 1 : 0, (hipStream_t)stream);
+}
+
+extern "C" int osrl_cdt_policy_window(void* handle, float* states, float* actions, float* returns, float* costs,
+                                      int64_t* time_steps, int32_t* n_out, void* stream) {
+  if (!handle) return -1;
+  Handle* h = static_cast<Handle*>(handle);
+  const osrl_cdt_policy_t& p = h->p;
+  const int T = p.seq_len, od = p.state_dim, ad = p.action_dim;
+  if (h->t < 0) {
+    if (n_out) *n_out = 0;
+    return 0;
+  }
+  std::vector<float> s((size_t)T * od), a((size_t)T * ad), r(T), c(T);
+  std::vector<int32_t> ts(T);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemcpyAsync(s.data(), h->d.win_s, 4 * s.size(), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(a.data(), h->d.win_a, 4 * a.size(), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(r.data(), h->d.win_r, 4 * T, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(c.data(), h->d.win_c, 4 * T, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(ts.data(), h->d.win_t, 4 * T, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return (int)e;
+  const int n = h->t + 1 < T ? h->t + 1 : T, t0 = h->t + 1 - n;
+  for (int i = 0; i < n; ++i) {
+    const int k = (t0 + i) % T;
+    if (states) memcpy(states + (size_t)i * od, &s[(size_t)k * od], 4 * od);
+    if (actions) memcpy(actions + (size_t)i * ad, &a[(size_t)k * ad], 4 * ad);
+    if (returns) returns[i] = r[k];
+    if (costs) costs[i] = c[k];
+    if (time_steps) time_steps[i] = ts[k];
+  }
+  if (n_out) *n_out = n;
+  return 0;
+}
+
+extern "C" int osrl_cdt_policy_destroy(void* handle) {
+  if (!handle) return -1;
+  Handle* h = static_cast<Handle*>(handle);
+  (void)hipDeviceSynchronize();  // no launch of this handle may still be running
+  hipError_t e = hipFree(h->dmem);
+  const hipError_t e2 = hipHostFree(h->pinned);
+  delete h;
+  return (int)(e != hipSuccess ? e : e2);
+}
