@@ -735,6 +735,15 @@ int osrl_cdt_mask_counts(const float* mask, int32_t BT, float* out, void* stream
  * scatter) */
 int osrl_cdt_timestep_scatter(const float* dseq, const int64_t* time_steps, int32_t B, int32_t T, int32_t R,
                               int32_t prefix, int32_t E, float* dte, void* stream);
+/* Input gradients of the token embeddings (cdt.py:178-213) from dseq [B, R*T + prefix, E], the gradient of the
+ * pre-LayerNorm sequence: dstates [B*T, od] = dseq(state tokens) W_state, dactions [B*T, ad] likewise, dreturns /
+ * dcosts_to_go [B*T] and depisode_cost [B] = the dot products with the 1-wide return / cost / prefix embeddings
+ * (dcosts_to_go is the gradient of the cost embedding's input).  An output pointer may be NULL (not computed); every
+ * output element is written by one lane in a fixed order (no atomics).  E <= 1024. */
+int osrl_cdt_embed_input_grad(const float* dseq, const float* Ws, const float* Wa, const float* Wr, const float* Wc,
+                              const float* Wp, int32_t B, int32_t T, int32_t od, int32_t ad, int32_t E, int32_t use_rew,
+                              int32_t use_cost, int32_t prefix, float* dstates, float* dactions, float* dreturns,
+                              float* dcosts_to_go, float* depisode_cost, void* stream);
 /* torch.nn.utils.clip_grad_norm_ (cdt.py:398-399): out[0] = min(1, clip/(||grad||+1e-6)), out[1] = ||grad|| */
 int osrl_clip_grad_scale(const float* grad, int64_t n, float clip, float* partial_ws, int32_t n_parts, float* out,
                          void* stream);

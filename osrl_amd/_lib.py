@@ -311,6 +311,7 @@ PROTOTYPES = {
     "osrl_cdt_loss": [_fp] * 7 + [_i32] * 6 + [_fp, _f32, _f32, _f32, _i32, _vp, _fp, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _vp],
     "osrl_cdt_mask_counts": [_fp, _i32, _fp, _vp],
     "osrl_cdt_timestep_scatter": [_fp, _vp, _i32, _i32, _i32, _i32, _i32, _fp, _vp],
+    "osrl_cdt_embed_input_grad": [_fp] * 6 + [_i32] * 8 + [_fp] * 5 + [_vp],
     "osrl_clip_grad_scale": [_fp, _i64, _f32, _fp, _i32, _fp, _vp],
     "osrl_cdt_temperature_step": [_fp, _fp, _fp, _f32, _f32, _f32, _f32, _f32, _vp, _vp],
     "osrl_kernarg_probe": [_vp, _P(_i32), _P(_u64), _vp],

@@ -33,7 +33,7 @@ class CDT(nn.Module):
                  time_emb: bool = True, use_rew: bool = False, use_cost: bool = False, cost_transform: bool = False,
                  add_cost_feat: bool = False, mul_cost_feat: bool = False, cat_cost_feat: bool = False,
                  action_head_layers: int = 1, cost_prefix: bool = False, stochastic: bool = False,
-                 init_temperature=0.1, target_entropy=None, device: str = "cuda"):
+                 init_temperature=0.1, target_entropy=None, device: str = "cuda", differentiable: bool = False):
         super().__init__()
         unsupported = []
         if not all(0.0 <= p < 1.0 for p in (attention_dropout, residual_dropout, embedding_dropout)):
@@ -119,6 +119,8 @@ class CDT(nn.Module):
             self.target_entropy = target_entropy
         self._engine = None
         self._fast = None
+        # forward() under grad mode records an autograd graph through the HIP kernels (ops.cdt_apply); off: inference only
+        self.differentiable = bool(differentiable)
 
     def fast_policy(self):
         """The act latency path for the episode loop on a host environment (engine/cdt_act.py ``CDTFastPolicy``), built
@@ -174,27 +176,22 @@ class CDT(nn.Module):
             engine_handoff(self, self._engine, old)
         return self._engine
 
-    @torch.no_grad()
-    def forward(self, states, actions, returns_to_go, costs_to_go, time_steps, padding_mask=None,
-                episode_cost=None):
-        """Inference forward (cdt.py:166-265): returns (action_preds, cost_preds, state_preds) where
-        action_preds is ``torch.distributions.Normal(mu, std)`` for a stochastic head."""
-        B = states.shape[0]
-        cfg = self._engine.cfg if self._engine is not None else dict(
+    def _default_cfg(self) -> dict:
+        return self._engine.cfg if self._engine is not None else dict(
             learning_rate=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), clip_grad=0.25, lr_warmup_steps=1,
             loss_cost_weight=0.0, loss_state_weight=0.0, no_entropy=False)
-        from ..engine.cdt import CDTEngine
-        Tin, T = states.shape[1], self.seq_len
+
+    def load_window(self, e, states, actions, returns_to_go, costs_to_go, time_steps, padding_mask=None,
+                    episode_cost=None) -> int:
+        """Copy one forward's inputs into engine ``e``; returns the window length Tin.  Shorter windows (early rollout
+        steps, cdt.py:485-489) are left-aligned and zero-padded to seq_len: with the causal mask the first Tin positions
+        are exactly the short-sequence result."""
+        B, Tin, T = states.shape[0], states.shape[1], self.seq_len
         if Tin > T:
             raise ValueError(f"window of {Tin} steps > seq_len {T}")
-        if getattr(self, "_infer", None) is None or self._infer.B != B:
-            self._infer = CDTEngine(self, B, cfg, inference=True)
-        e = self._infer
         mask = torch.ones(B, Tin, device=states.device) if padding_mask is None else \
             (~padding_mask.to(torch.bool)).float()
         if Tin < T:
-            # shorter windows (early rollout steps, cdt.py:485-489): left-align and zero-pad the tail; with the
-            # causal mask the first Tin positions are exactly the short-sequence result
             def pad(x, val=0):
                 out = torch.full((B, T) + tuple(x.shape[2:]), val, dtype=x.dtype, device=x.device)
                 out[:, :Tin] = x
@@ -206,6 +203,53 @@ class CDT(nn.Module):
         e.load_batch(states, actions, returns_to_go, costs_to_go, time_steps, mask, torch.zeros_like(mask),
                      torch.as_tensor(episode_cost, dtype=torch.float32, device=states.device).reshape(B)
                      if self.cost_prefix else None)
+        return Tin
+
+    def forward(self, states, actions, returns_to_go, costs_to_go, time_steps, padding_mask=None,
+                episode_cost=None):
+        """cdt.py:166-265: returns (action_preds, cost_preds, state_preds) where action_preds is
+        ``torch.distributions.Normal(mu, std)`` for a stochastic head.  With ``differentiable`` set and grad mode on, the
+        outputs are attached to the autograd graph (ops.cdt_apply: forward and backward on the HIP kernels); otherwise
+        this is the inference forward and nothing is recorded."""
+        if self.differentiable and torch.is_grad_enabled():
+            return self._forward_grad(states, actions, returns_to_go, costs_to_go, time_steps, padding_mask,
+                                      episode_cost)
+        return self._forward_infer(states, actions, returns_to_go, costs_to_go, time_steps, padding_mask, episode_cost)
+
+    def grad_engine(self, batch_size: int):
+        """The engine of the differentiable forward for this batch size and the current mode (train() with dropout > 0
+        draws masks, every other case runs without): one per mode, rebuilt when the batch size changes.  Separate from
+        the trainer's ``_engine`` (own gradient slabs; no optimizer state is touched)."""
+        from ..engine.cdt import CDTEngine
+        drop = self.training and max(self.attention_dropout, self.residual_dropout, self.embedding_dropout) > 0
+        cache = self.__dict__.setdefault("_grad_engines", {})
+        e = cache.get(drop)
+        if e is None or e.B != batch_size:
+            cache[drop] = None  # (the old engine's buffers go before the new ones are allocated)
+            e = cache[drop] = CDTEngine(self, batch_size, self._default_cfg(), grad=True, dropout=drop)
+        return e
+
+    def _forward_grad(self, states, actions, returns_to_go, costs_to_go, time_steps, padding_mask, episode_cost):
+        from ..ops import cdt_apply
+        e = self.grad_engine(states.shape[0])
+        head, logits, sp = cdt_apply(self, e, states, actions, returns_to_go, costs_to_go, time_steps, padding_mask,
+                                     episode_cost)
+        if self.stochastic:
+            ad = self.action_dim
+            ap = torch.distributions.Normal(head[..., :ad], head[..., ad:].exp())
+        else:
+            ap = head
+        return ap, torch.log_softmax(logits, -1), sp
+
+    @torch.no_grad()
+    def _forward_infer(self, states, actions, returns_to_go, costs_to_go, time_steps, padding_mask=None,
+                       episode_cost=None):
+        B, T = states.shape[0], self.seq_len
+        from ..engine.cdt import CDTEngine
+        if getattr(self, "_infer", None) is None or self._infer.B != B:
+            self._infer = CDTEngine(self, B, self._default_cfg(), inference=True)
+        e = self._infer
+        Tin = self.load_window(e, states, actions, returns_to_go, costs_to_go, time_steps, padding_mask, episode_cost)
         self.repack()
         if self.training and max(self.attention_dropout, self.residual_dropout, self.embedding_dropout) > 0:
             e.st.tick()  # a model left in train() mode draws a fresh dropout mask per call, like nn.Dropout
@@ -245,6 +289,8 @@ class CDTTrainer:
     def train_one_step(self, states, actions, returns, costs_return, time_steps, mask, episode_cost, costs):
         """cdt.py:343-418 (``episode_cost`` only feeds the cost-prefix variant)."""
         eng = self.model.engine(states.shape[0], self.cfg)
+        if self.model.__dict__.get("_grad_engines"):  # a user optimizer may have edited the parameters in place since
+            self.model.repack()                        # the last differentiable forward: refresh the packed copies
         eng.step(states, actions, returns, costs_return, time_steps, mask, costs, use_graph=self.use_graph,
                  episode_cost=episode_cost if self.model.cost_prefix else None)
         keys = None if self.stochastic else ["all_loss", "act_loss", "cost_loss", "cost_acc", "state_loss", "train_lr"]

@@ -36,7 +36,12 @@ def _r16(x: int) -> int:
 
 
 class CDTEngine:
-    def __init__(self, model, batch_size: int, trainer_cfg: dict, dist=None, inference: bool = False):
+    def __init__(self, model, batch_size: int, trainer_cfg: dict, dist=None, inference: bool = False,
+                 grad: bool = False, dropout: bool = True):
+        """``inference``: forward only (no dW plans, no gradient slabs).  ``grad``: the engine of the differentiable
+        forward (ops.cdt_apply): forward + backward from caller-supplied output gradients into gradient slabs of its
+        OWN (``FlatGroup.grad_shadow``), so a trainer's engine on the same model keeps its slabs, plans and graphs;
+        never steps the optimizer.  ``dropout=False``: every dropout probability is 0 (an eval-mode forward)."""
         m = self.model = model
         self.cfg = trainer_cfg
         self.dist = dist
@@ -59,8 +64,9 @@ class CDTEngine:
         f = dict(dtype=torch.float32, device=dev)
         z = lambda *s: torch.zeros(*s, **f)  # noqa: E731
         self.st = StepState(dev, STAT_KEYS, betas=tuple(trainer_cfg["betas"]), warmup=trainer_cfg["lr_warmup_steps"])
-        g: FlatGroup = m.groups["cdt"]
+        g: FlatGroup = m.groups["cdt"].grad_shadow() if grad else m.groups["cdt"]
         self.g = g
+        self.grad = bool(grad)
         # static inputs
         self.states, self.actions = z(B, T, od), z(B, T, ad)
         self.returns, self.ctg, self.mask, self.costs = z(B, T), z(B, T), z(B, T), z(B, T)
@@ -133,7 +139,8 @@ class CDTEngine:
         self.dhh_pre = [z(BT, Eh) for _ in range(nhid)]
         # dropout: probabilities, generator seed; gradients of the dropped branches need their own buffers
         # (the undropped gradient keeps flowing along the residual path)
-        self.p_emb, self.p_attn, self.p_res = m.embedding_dropout, m.attention_dropout, m.residual_dropout
+        self.p_emb, self.p_attn, self.p_res = ((m.embedding_dropout, m.attention_dropout, m.residual_dropout) if dropout
+                                               else (0.0, 0.0, 0.0))
         for name, pv in (("embedding_dropout", self.p_emb), ("attention_dropout", self.p_attn),
                          ("residual_dropout", self.p_res)):
             if not (0.0 <= float(pv) < 1.0):  # p = 1 drops everything: the kernels' keep scale 1 / (1 - p) has no value
@@ -409,19 +416,26 @@ class CDTEngine:
         self._lin(af, R * E, BT, "cdt.cost_pred_head.weight", self.logits, 2)
         self._lin(af, R * E, BT, "cdt.state_pred_head.weight", self.sp, m.state_dim)
 
-    # ---- one full train step -------------------------------------------------------------------
+    # ---- one full train step: forward -> loss (the gradient seeds) -> backward -> optimizer --------------------------
     def body(self) -> None:
-        m, lib, cfg, g = self.model, L.load(), self.cfg, self.g
-        E, M, BT, NL = self.E, self.M, self.BT, self.NL
         st = self.st
         if self.inference:
             raise RuntimeError("this CDTEngine was built for inference (no dW plans): it cannot run a train step")
-        self._ln_pending = []  # (a step that raised half way must not leave sites behind)
+        if self.grad:
+            raise RuntimeError("this CDTEngine belongs to the differentiable forward: it runs no optimizer step")
         st.tick()
         if self.store is not None:  # draw the minibatch of windows on device (SequenceDataset, dataset.py:749-787)
             self.store.gather(self.states, self.actions, self.returns, self.ctg, self.time_steps, self.mask,
                               self.episode_cost, self.costs, st.ptr)
         self.forward(train=True)
+        self.loss()
+        self.backward()
+        self.optimizer_step()
+
+    def loss(self) -> None:
+        """CDTTrainer's losses (cdt.py:357-394) into the step statistics, and their gradients into the seeds ``dhead`` /
+        ``dlogits`` / ``dsp`` that ``backward()`` starts from."""
+        m, lib, cfg, st, BT = self.model, L.load(), self.cfg, self.st, self.BT
         counts, world = None, 1
         big = BT > 1024  # multi-workgroup loss: the normalisers are needed before the per-token gradients
         if self.dist is not None or big:  # count-normalisers (over the GLOBAL batch, SURVEY.md 8e item 3)
@@ -439,7 +453,16 @@ class CDTEngine:
                                   counts, world, self.dhead.data_ptr(), self.dlogits.data_ptr(), self.dsp.data_ptr(),
                                   st.stats.data_ptr(), self.ent.data_ptr(), self.loss_ws.data_ptr() if big else None,
                                   cur_stream()), "osrl_cdt_loss")
-        # ---- backward: heads -> dout (only the state / action token rows are non-zero)
+
+    def backward(self) -> None:
+        """Backward of the latest ``forward(train=True)`` from the seeds ``dhead`` [B*T, head width], ``dlogits`` [B*T, 2]
+        and ``dsp`` [B*T, state_dim] (row b*T + t): leaves ``dseq`` (the gradient of the pre-LayerNorm token embeddings)
+        and the parameter gradients, row-split, in this engine's gradient slabs (``reduce_grads()`` sums them).  The
+        dropout masks are regenerated from the step counter, which must not have moved since that forward."""
+        m, lib, g = self.model, L.load(), self.g
+        E, M, BT, NL = self.E, self.M, self.BT, self.NL
+        self._ln_pending = []  # (a step that raised half way must not leave sites behind)
+        # ---- heads -> dout (only the state / action token rows are non-zero)
         R, B, T, Eh = self.R, self.B, self.T, self.Eh
         # dout / doutc: the rows of the return / cost (/ prefix) tokens carry no gradient from the heads and are never
         # written by anything -- they keep the zeros they were allocated with; the state / action rows are fully
@@ -515,9 +538,10 @@ class CDTEngine:
         self.p_tok.launch()
         self.p_bt.launch()
         g.cur_splits = self.n_splits
-        # ---- clip_grad_norm_ + AdamW (cdt.py:396-400)
-        if self._slab_probe is not None:  # tests: the complete slabs of a real step, before they are summed in place
-            self._slab_probe(g.slabs, self.n_splits, self.slab_counts)
+
+    def reduce_grads(self) -> None:
+        """The row splits of the gradient slabs summed into slab 0, in place: the complete gradient of the backward."""
+        lib, g = L.load(), self.g
         if self.slab_counts is not None:
             L.check(lib.osrl_reduce_slabs_counts(g.slabs.data_ptr(), g.slabs.data_ptr(), self.slab_counts.data_ptr(), g.n,
                                                  g.n, cur_stream()), "osrl_reduce_slabs_counts")
@@ -525,6 +549,14 @@ class CDTEngine:
             L.check(lib.osrl_reduce_slabs(g.slabs.data_ptr(), g.slabs.data_ptr(), g.cur_splits, g.n, g.n, cur_stream()),
                     "osrl_reduce_slabs")
         g.cur_splits = 1
+
+    def optimizer_step(self) -> None:
+        """Slab sum -> (data parallel: all-reduce) -> clip_grad_norm_ -> AdamW with the warm-up LR -> temperature Adam
+        (cdt.py:396-407)."""
+        m, lib, cfg, g, st = self.model, L.load(), self.cfg, self.g, self.st
+        if self._slab_probe is not None:  # tests: the complete slabs of a real step, before they are summed in place
+            self._slab_probe(g.slabs, self.n_splits, self.slab_counts)
+        self.reduce_grads()
         if self.dist is not None:  # ONE all-reduce of the flat gradient; the clip norm is of the reduced gradient
             self.dist.all_reduce_(g.slabs[0])
             self.dist.all_reduce_(self.ent)

@@ -13,6 +13,7 @@ PyTorch is used for device memory and streams only; all arithmetic is in libosrl
 from __future__ import annotations
 
 import os
+import copy
 import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -166,6 +167,14 @@ class FlatGroup:
         else:
             self.slabs.zero_()
             self.slab_epoch += 1
+
+    def grad_shadow(self) -> "FlatGroup":
+        """The same group (parameters, Adam moments, packed weight copies: the very tensors) with gradient slabs of its
+        own: dW plans attached to the shadow never re-zero, outgrow or re-epoch the slabs the group's step engines and
+        their captured graphs use (the differentiable CDT forward, ops.cdt_apply)."""
+        s = copy.copy(self)
+        s.slabs, s.n_splits, s.slab_epoch, s._retired_slabs, s.cur_splits = None, 0, 0, [], 1
+        return s
 
     def offset(self, key: str) -> int:
         return self.layout[key][0]

@@ -2,7 +2,8 @@
 (``model.act``, module ``forward`` methods, user losses).
 
 ``mlp_apply`` is a ``torch.autograd.Function`` whose forward AND backward are the fused HIP
-kernels of csrc/mlp.hip (forward, backward-dz with dX, split-K dW).  Nothing here falls back to
+kernels of csrc/mlp.hip (forward, backward-dz with dX, split-K dW).  ``cdt_apply`` is the same for
+the CDT transformer (engine/cdt.py forward / backward, csrc/cdt_grad.hip for the input gradients).  Nothing here falls back to
 aten arithmetic; without the library (or without a HIP device) every call raises.
 """
 from __future__ import annotations
@@ -13,7 +14,7 @@ import torch
 
 from . import _lib as L
 from .engine import glue as G
-from .engine.core import DwPlan, FlatGroup, MlpRun, NetDesc, randn_fill
+from .engine.core import DwPlan, FlatGroup, MlpRun, NetDesc, cur_stream, randn_fill
 
 
 def _chk(x: torch.Tensor) -> torch.Tensor:
@@ -86,6 +87,104 @@ class _FusedMLP(torch.autograd.Function):
         dx = run.dx.sum(0)
         d0 = ctx.d0
         return (None, dx[:, :d0].contiguous(), dx[:, d0:].contiguous() if ctx.has_x1 else None, *grads)
+
+
+class _CDTApply(torch.autograd.Function):
+    """The CDT forward (cdt.py:166-265, without the aten tail: log_softmax, exp of log_std) on a grad engine of the
+    model (``CDT.grad_engine``), and its backward on the same engine's HIP kernels."""
+
+    @staticmethod
+    def forward(ctx, model, eng, time_steps, padding_mask, states, actions, returns, costs_to_go, episode_cost,
+                *params):
+        Tin = model.load_window(eng, states, actions, returns, costs_to_go, time_steps, padding_mask, episode_cost)
+        model.repack()  # parameters may have been edited (a user optimizer) since the last pack
+        if eng.p_emb > 0 or eng.p_attn > 0 or eng.p_res > 0:
+            eng.st.tick()  # fresh dropout masks per call, like nn.Dropout; the backward regenerates the same ones
+        eng.forward(train=True)  # (train=True also keeps what the backward reads: attention row statistics, keep bits)
+        eng.fwd_count = getattr(eng, "fwd_count", 0) + 1
+        ctx.eng, ctx.fwd_count, ctx.Tin, ctx.model = eng, eng.fwd_count, Tin, model
+        ctx.in_shapes = [(x.shape, x.dtype) if torch.is_tensor(x) else None
+                         for x in (states, actions, returns, costs_to_go, episode_cost)]
+        ctx.save_for_backward(*params)  # autograd's version check: parameters edited in place before backward() raise
+        B, T = eng.B, eng.T
+        return tuple(buf.view(B, T, buf.shape[1])[:, :Tin].clone() for buf in (eng.head, eng.logits, eng.sp))
+
+    @staticmethod
+    def backward(ctx, dhead, dlogits, dsp):
+        if torch.is_grad_enabled():
+            raise RuntimeError("CDT differentiable forward: double backward (create_graph=True) is not supported")
+        eng, Tin, m = ctx.eng, ctx.Tin, ctx.model
+        if getattr(eng, "fwd_count", 0) != ctx.fwd_count:
+            raise RuntimeError("CDT differentiable forward: this graph's activations were overwritten by a later "
+                               "forward on the same engine (same batch size and mode); call backward() before the next "
+                               "forward, or recompute the forward")
+        ctx.saved_tensors  # noqa: B018  (raises if a parameter was modified in place since the forward)
+        B, T = eng.B, eng.T
+        for buf, gr in ((eng.dhead, dhead), (eng.dlogits, dlogits), (eng.dsp, dsp)):  # seeds in row b*T + t
+            v = buf.view(B, T, buf.shape[1])
+            if Tin < T:
+                v[:, Tin:].zero_()
+            v[:, :Tin].copy_(gr)
+        eng.backward()
+        eng.reduce_grads()
+        need = ctx.needs_input_grad
+        g = eng.g
+        flat = g.slabs[0].clone()  # (the slabs are this engine's scratch: the next backward overwrites them)
+        grads = []
+        for i, (name, _) in enumerate(m.named_parameters()):
+            if not need[9 + i]:
+                grads.append(None)
+                continue
+            off, shape = g.layout["cdt." + name]
+            n = 1
+            for d in shape:
+                n *= d
+            grads.append(flat[off:off + n].view(shape))
+        # inputs (cdt.py:178-213): the reference detaches costs_to_go under cost_transform (cdt.py:187-188); returns,
+        # costs and the episode cost only feed a token where the model has one
+        want = [need[4], need[5], need[6] and m.use_rew, need[7] and m.use_cost and not m.cost_transform_on,
+                need[8] and m.cost_prefix]
+        dins = [None] * 5
+        if any(want):
+            f = dict(dtype=torch.float32, device=eng.dev)
+            od, ad = m.state_dim, m.action_dim
+            outs = [torch.empty(B, T, od, **f) if want[0] else None, torch.empty(B, T, ad, **f) if want[1] else None,
+                    torch.empty(B, T, **f) if want[2] else None, torch.empty(B, T, **f) if want[3] else None,
+                    torch.empty(B, **f) if want[4] else None]
+            v = eng._v
+            L.check(L.load().osrl_cdt_embed_input_grad(
+                eng.dseq.data_ptr(), v("cdt.state_emb.weight"), v("cdt.action_emb.weight"),
+                v("cdt.return_emb.weight") if m.use_rew else None, v("cdt.cost_emb.weight") if m.use_cost else None,
+                v("cdt.prefix_emb.weight") if m.cost_prefix else None, B, T, od, ad, eng.E, int(m.use_rew),
+                int(m.use_cost), int(m.cost_prefix), *[None if o is None else o.data_ptr() for o in outs],
+                cur_stream()), "osrl_cdt_embed_input_grad")
+            for k, o in enumerate(outs):
+                if o is not None:
+                    shape, dtype = ctx.in_shapes[k]
+                    dins[k] = (o if k == 4 else o[:, :Tin]).reshape(shape).to(dtype)
+        return (None, None, None, None, *dins, *grads)
+
+
+def cdt_apply(model, eng, states, actions, returns_to_go, costs_to_go, time_steps, padding_mask=None,
+              episode_cost=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Differentiable CDT forward (``CDT(..., differentiable=True)``): (head [B, Tin, 2*ad (mu | log_std) or ad],
+    cost logits [B, Tin, 2], state predictions [B, Tin, od]) attached to the autograd graph.  Forward, backward and the
+    input gradients run on the HIP kernels of the fused train step (engine/cdt.py ``forward`` / ``backward``) plus one
+    launch for the input gradients (osrl_cdt_embed_input_grad); only the seeds' copies and the slab read-out are aten.
+
+    * Gradients: one per parameter (``None`` where ``requires_grad`` is off), accumulated into ``.grad`` by autograd;
+      ``states`` / ``actions`` / ``returns_to_go`` / ``costs_to_go`` / ``episode_cost`` as the reference's nn.Linear
+      embeddings give them -- ``costs_to_go`` only without ``cost_transform`` (the reference detaches it, cdt.py:187),
+      and through the token embedding only (the cost features use the detached embedding, cdt.py:243-250).
+      ``time_steps`` and the padding mask get none; window positions past Tin (the padding of a short window) neither.
+    * Activations live in the engine, not per call: a forward on the same engine (same batch size and mode) overwrites
+      them, and the backward of an earlier graph then raises RuntimeError instead of returning wrong gradients.
+    * Dropout (train() mode, p > 0): fresh masks per call; the backward regenerates exactly those masks.
+    * Not supported: double backward (``create_graph=True`` raises), data parallelism, hipGraph capture of this path,
+      gradients of ``log_temperature`` (not an input of the forward).  ``CDTTrainer`` stays the fused training path."""
+    params = [p for _, p in model.named_parameters()]
+    return _CDTApply.apply(model, eng, time_steps, padding_mask, states, actions, returns_to_go, costs_to_go,
+                           episode_cost, *params)
 
 
 def mlp_apply(desc: NetDesc, x0: torch.Tensor, x1: Optional[torch.Tensor] = None) -> torch.Tensor:
