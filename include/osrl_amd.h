@@ -1039,6 +1039,26 @@ int osrl_cdt_policy_step(void* handle, float reward, float cost, int32_t host_ac
 int osrl_cdt_policy_window(void* handle, float* states, float* actions, float* returns, float* costs,
                            int64_t* time_steps, int32_t* n, void* stream);
 int osrl_cdt_policy_destroy(void* handle);
+/* N episodes per handle, advanced in LOCKSTEP: every episode is at the same timestep, so one _reset_n / _step_n call runs
+ * the same 2 + 5 * layers launches as the one-episode calls, over the rows of all N episodes (a projection's 16-row
+ * tiles fill up with rows of several episodes), and returns after all N actions have been published.  An episode's
+ * results do not depend on N or on its slot.  A slot whose episode has ended keeps running on whatever its rows of the
+ * pinned block hold; the caller ignores its action.  The HANDLE owns the pinned block; the caller writes obs [N,
+ * state_dim], act_in [N, action_dim] and scalars [N, 4] = (reward, cost, target_return, target_cost) per episode
+ * between calls and reads act_out [N, action_dim] after a call; the pointers die with _destroy.
+ * 1 <= n_env <= OSRL_CDT_POLICY_MAX_ENVS, else -1.  _create is _create_n with n_env = 1; _reset / _step serve handles
+ * of one episode only (-1 otherwise); _io, _window (episode 0) and _destroy serve both. */
+#define OSRL_CDT_POLICY_MAX_ENVS 64
+int osrl_cdt_policy_create_n(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int32_t n_env,
+                             void** handle);
+int osrl_cdt_policy_io_n(void* handle, float** obs, float** act_in, float** act_out, float** scalars);
+/* starts N episodes at timestep 0: observations from obs, targets from scalars[e][2..3] */
+int osrl_cdt_policy_reset_n(void* handle, void* stream);
+/* as _step for every episode: reward and cost from scalars[e][0..1] (scalars[e][2..3] must keep the targets) */
+int osrl_cdt_policy_step_n(void* handle, int32_t host_action, void* stream);
+/* as _window, of episode env (0 <= env < n_env, else -1) */
+int osrl_cdt_policy_window_n(void* handle, int32_t env, float* states, float* actions, float* returns, float* costs,
+                             int64_t* time_steps, int32_t* n, void* stream);
 
 /* ---- data-parallel exchanges through IPC-mapped device buffers (ipc.hip, round 6; nothing to mirror in the reference: it
  * has no distributed code).  What the ranks of a data-parallel step exchange (flat

@@ -146,6 +146,7 @@ class PolicyT(C.Structure):
 
 POLICY_MLP, POLICY_GAUSS, POLICY_BCQ = 0, 1, 2
 POLICY_MAX_ROWS = 4
+CDT_POLICY_MAX_ENVS = 64  # OSRL_CDT_POLICY_MAX_ENVS
 
 
 class CdtLayerT(C.Structure):  # osrl_cdt_layer_t
@@ -206,6 +207,11 @@ PROTOTYPES = {
     "osrl_cdt_policy_step": [_vp, _f32, _f32, _i32, _vp],
     "osrl_cdt_policy_window": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "osrl_cdt_policy_destroy": [_vp],
+    "osrl_cdt_policy_create_n": [_P(CdtPolicyT), _P(CdtLayerT), _i32, _P(C.c_void_p)],
+    "osrl_cdt_policy_io_n": [_vp, _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float))],
+    "osrl_cdt_policy_reset_n": [_vp, _vp],
+    "osrl_cdt_policy_step_n": [_vp, _i32, _vp],
+    "osrl_cdt_policy_window_n": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "osrl_cost_sample_prob": [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp],
     "osrl_start_index_prob": [_vp, _vp, _vp, _i32, C.c_double, _vp, _vp, _vp],
     "osrl_bc_select": [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp],

@@ -122,9 +122,18 @@ class CDT(nn.Module):
         # forward() under grad mode records an autograd graph through the HIP kernels (ops.cdt_apply); off: inference only
         self.differentiable = bool(differentiable)
 
-    def fast_policy(self):
+    def fast_policy(self, num_envs: Optional[int] = None):
         """The act latency path for the episode loop on a host environment (engine/cdt_act.py ``CDTFastPolicy``), built
-        once per model.  Raises NotImplementedError naming the limit outside its domain."""
+        once per model.  With ``num_envs`` an integer: the lockstep form for that many host environments
+        (``CDTVecFastPolicy``), built once per model and ``num_envs``.  Raises NotImplementedError naming the limit
+        outside the path's domain."""
+        if num_envs is not None:
+            from ..engine.cdt_act import CDTVecFastPolicy, _vec_args
+            cache = self.__dict__.setdefault("_fast_vec", {})
+            n = _vec_args(num_envs)
+            if cache.get(n) is None:  # (a copied / unpickled model holds None here: the handle is not copyable)
+                cache[n] = CDTVecFastPolicy(self, n)
+            return cache[n]
         if getattr(self, "_fast", None) is None:
             from ..engine.cdt_act import CDTFastPolicy
             self._fast = CDTFastPolicy(self)
@@ -298,8 +307,11 @@ class CDTTrainer:
 
     def evaluate(self, num_rollouts, target_return, target_cost):
         """cdt.py:420-434.  With a ``VecSyntheticSafeEnv`` as ``self.env`` the ``num_rollouts`` episodes run as one
-        batch on device (engine/rollout.py ``CDTBatchedRollout``)."""
+        batch on device (engine/rollout.py ``CDTBatchedRollout``).  With a list or tuple of N host environments rollout
+        ``j`` runs on environment ``j % N``, N rollouts at a time in lockstep (``rollout_many``)."""
         from ..common.synthetic_env import VecSyntheticSafeEnv
+        if isinstance(self.env, (list, tuple)):
+            return self.evaluate_targets(num_rollouts, [(target_return, target_cost)])[0]
         if isinstance(self.env, VecSyntheticSafeEnv):
             from ..engine.rollout import CDTBatchedRollout
             if self.env.E != num_rollouts:
@@ -360,6 +372,86 @@ class CDTTrainer:
             if terminated or truncated:
                 break
         return ep_ret, ep_len, ep_cost
+
+    def evaluate_targets(self, num_rollouts, targets):
+        """``evaluate`` for each ``(target_return, target_cost)`` pair of ``targets``: a list of ``(return, cost,
+        length)`` triples.  With a list or tuple of N host environments as ``self.env`` the ``len(targets) *
+        num_rollouts`` rollouts are laid out target-major and job ``q`` runs in wave ``q // N`` on environment
+        ``q % N``, so rollouts for different targets share a wave; with any other environment this is one
+        ``evaluate`` per pair."""
+        targets = [(float(tr), float(tc)) for tr, tc in targets]
+        if not isinstance(self.env, (list, tuple)):
+            return [self.evaluate(num_rollouts, tr, tc) for tr, tc in targets]
+        envs = list(self.env)
+        N = len(envs)
+        if N == 0:
+            raise ValueError("evaluate over an empty list of environments")
+        jobs = [t for t in targets for _ in range(int(num_rollouts))]
+        self.model.eval()
+        rets, lens, costs = [], [], []
+        for q0 in range(0, len(jobs), N):
+            wave = jobs[q0:q0 + N]
+            r, l, c = self.rollout_many(self.model, envs[:len(wave)], [t[0] for t in wave], [t[1] for t in wave],
+                                        num_slots=N)
+            rets += list(r)
+            lens += list(l)
+            costs += list(c)
+        self.model.train()
+        out, k = [], int(num_rollouts)
+        for i in range(len(targets)):
+            sl = slice(i * k, (i + 1) * k)
+            out.append((np.mean(rets[sl]) / self.reward_scale, np.mean(costs[sl]) / self.cost_scale,
+                        np.mean(lens[sl])))
+        return out
+
+    @torch.no_grad()
+    def rollout_many(self, model: CDT, envs, target_returns, target_costs, num_slots: Optional[int] = None):
+        """``rollout`` on each of the host environments ``envs`` at once: three arrays (return, length, raw cost sum),
+        one entry per environment, equal to what ``rollout`` returns for each environment alone.  The targets are
+        scalars or one per environment.  With ``fast_rollout`` and an eligible model the episodes run in lockstep
+        through ``CDT.fast_policy(num_envs)``, one C call per env step for all of them, and a slot leaves the loop when
+        its environment terminates, truncates or reaches ``episode_len``; otherwise one ``rollout`` per environment.
+        ``num_slots`` (default ``len(envs)``): the width of the policy to use, the slots past ``len(envs)`` idle."""
+        envs = list(envs)
+        n = len(envs)
+        trs = np.broadcast_to(np.asarray(target_returns, dtype=np.float64), (n,))
+        tcs = np.broadcast_to(np.asarray(target_costs, dtype=np.float64), (n,))
+        N = n if num_slots is None else int(num_slots)
+        if N < n:
+            raise ValueError(f"{n} environments do not fit {N} slots")
+        ep_ret, ep_len, ep_cost = [0.0] * n, np.zeros(n, np.int64), [0.0] * n
+        if n == 0:
+            return np.asarray(ep_ret), ep_len, np.asarray(ep_cost)
+        if not (self.fast_rollout and model.fast_eligible()):
+            for e, env in enumerate(envs):
+                ep_ret[e], ep_len[e], ep_cost[e] = self.rollout(model, env, float(trs[e]), float(tcs[e]))
+            return np.asarray(ep_ret), ep_len, np.asarray(ep_cost)
+        pol = model.fast_policy(num_envs=N)
+        obs = np.zeros((N, model.state_dim), np.float32)
+        reward, cost = np.zeros(N, np.float64), np.zeros(N, np.float64)
+        tr_n, tc_n = np.zeros(N, np.float64), np.zeros(N, np.float64)
+        tr_n[:n], tc_n[:n] = trs, tcs
+        active = np.zeros(N, bool)
+        active[:n] = True
+        for e, env in enumerate(envs):
+            obs[e], _ = env.reset()
+        act = pol.reset(obs, tr_n, tc_n)
+        EL = model.episode_len
+        for step in range(EL):
+            for e in np.flatnonzero(active):
+                obs_next, r, terminated, truncated, info = envs[e].step(act[e])
+                ep_ret[e] += r
+                ep_len[e] += 1
+                ep_cost[e] += info["cost"]
+                if terminated or truncated or step + 1 == EL:
+                    active[e] = False
+                    continue
+                obs[e], reward[e] = obs_next, r
+                cost[e] = ((1.0 - info["cost"]) if self.cost_reverse else info["cost"]) * self.cost_scale
+            if not active.any():
+                break
+            act = pol.step(obs, reward, cost, active=active)
+        return np.asarray(ep_ret), ep_len, np.asarray(ep_cost)
 
     def _rollout_fast(self, model: CDT, env, target_return: float, target_cost: float):
         pol = model.fast_policy()

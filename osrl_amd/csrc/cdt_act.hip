@@ -1,4 +1,5 @@
-// cdt_act.hip -- the B = 1 act latency path of the Constrained Decision Transformer's episode loop on gfx950.
+// cdt_act.hip -- the act latency path of the Constrained Decision Transformer's episode loop on gfx950: one episode
+// per handle (B = 1), or N episodes advanced in lockstep by the same launches.
 //
 // CDTTrainer.rollout (cdt.py:436-518) asks the model for one action per env step over a sliding window of the last
 // seq_len timesteps.  Run as a training-shaped forward that is ~30 launches over a window padded to seq_len plus a
@@ -17,6 +18,11 @@
 // another workgroup.  The projections are fp32 MFMA (v_mfma_f32_16x16x4f32) over 16-row tiles of the packed forward
 // weights PF[k/4][n][k%4] (the copies the fused AdamW step and repack() keep current), split-K over the four waves
 // of a workgroup and summed in LDS in a fixed order: results do not depend on scheduling.
+// A handle of N episodes (osrl_cdt_policy_create_n) keeps N such windows, one per-episode block of `es` floats each in
+// the handle's device allocation.  The episodes share the timestep, hence the phase and every row set, so a step is the
+// SAME 2 + 5 * layers launches: ingest and head run one workgroup per episode, attention one wave per (row, head,
+// episode), and a projection's row list is the concatenation over the episodes, so that its 16-row tiles fill up with
+// rows of several episodes.  No arithmetic crosses rows: an episode's results do not depend on N or on its slot.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -82,7 +88,12 @@ struct Dev {  // device view of a handle's buffers
   float* raw;                            // [NR, ldE] pre-LayerNorm embeddings (cost features read the cost token's)
 };
 
-struct Io {  // pinned + device-mapped
+// episode e's view: every per-episode buffer sits at the same offset of its episode's block of `es` floats
+__device__ __forceinline__ Dev dev_at(const Dev& d, size_t off) {
+  return Dev{d.win_s + off, d.win_a + off, d.win_r + off, d.win_c + off, d.win_t + off, d.last_act + off, d.raw + off};
+}
+
+struct Io {  // pinned + device-mapped; one row per episode
   float *obs, *act_in, *act_out, *scalars;  // scalars: reward, cost, target_return, target_cost
   uint64_t* seq;
 };
@@ -96,31 +107,37 @@ struct IngestArgs {
   float* x0;  // [NR, ldE] emb LayerNorm output
   int32_t ldE, R, TR, t, reset, host_action;
   int32_t first, count, ring;  // token rows to embed
+  int64_t es;                  // floats per episode block (grid: one workgroup per episode)
 };
 
 __global__ __launch_bounds__(256) void cdt_act_ingest_kernel(const IngestArgs a) {
   const osrl_cdt_policy_t& p = a.p;
   const int tid = threadIdx.x, T = p.seq_len, od = p.state_dim, ad = p.action_dim;
   const int cur = a.t % T;
+  const size_t eoff = (size_t)blockIdx.x * (size_t)a.es;
+  const Dev d = dev_at(a.d, eoff);
+  const Io io{a.io.obs + (size_t)blockIdx.x * od, a.io.act_in + (size_t)blockIdx.x * ad, nullptr,
+              a.io.scalars + (size_t)blockIdx.x * 4, nullptr};
+  float* __restrict__ x0 = a.x0 + eoff;
   if (a.reset) {
-    for (int i = tid; i < od; i += blockDim.x) a.d.win_s[i] = a.io.obs[i];
+    for (int i = tid; i < od; i += blockDim.x) d.win_s[i] = io.obs[i];
     if (tid == 0) {
-      a.d.win_r[0] = a.io.scalars[2];
-      a.d.win_c[0] = a.io.scalars[3];
-      a.d.win_t[0] = 0;
+      d.win_r[0] = io.scalars[2];
+      d.win_c[0] = io.scalars[3];
+      d.win_t[0] = 0;
     }
   } else {
     const int prv = (a.t - 1) % T;
     for (int i = tid; i < ad && T > 1; i += blockDim.x)  // (seq_len 1: the previous timestep left the window)
-      a.d.win_a[prv * ad + i] = a.host_action ? a.io.act_in[i] : a.d.last_act[i];
-    for (int i = tid; i < od; i += blockDim.x) a.d.win_s[cur * od + i] = a.io.obs[i];
+      d.win_a[prv * ad + i] = a.host_action ? io.act_in[i] : d.last_act[i];
+    for (int i = tid; i < od; i += blockDim.x) d.win_s[cur * od + i] = io.obs[i];
     if (tid == 0) {  // returns[t+1] = returns[t] - float(reward); costs[t+1] = costs[t] - cost  (fp32, cdt.py:506-507)
-      a.d.win_r[cur] = a.d.win_r[prv] - a.io.scalars[0];
-      a.d.win_c[cur] = a.d.win_c[prv] - a.io.scalars[1];
-      a.d.win_t[cur] = a.t;
+      d.win_r[cur] = d.win_r[prv] - io.scalars[0];
+      d.win_c[cur] = d.win_c[prv] - io.scalars[1];
+      d.win_t[cur] = a.t;
     }
   }
-  for (int i = tid; i < ad; i += blockDim.x) a.d.win_a[cur * ad + i] = 0.f;  // the newest action slot: zero dummy
+  for (int i = tid; i < ad; i += blockDim.x) d.win_a[cur * ad + i] = 0.f;  // the newest action slot: zero dummy
   __syncthreads();
   const int lane = tid & 63, E = p.embedding_dim;
   for (int i = tid >> 6; i < a.count; i += blockDim.x >> 6) {
@@ -129,10 +146,10 @@ __global__ __launch_bounds__(256) void cdt_act_ingest_kernel(const IngestArgs a)
     const int ts = is_prefix ? 0 : row / a.R, slot = is_prefix ? 0 : row - ts * a.R;
     int which = slot + (4 - a.R);  // 0 return, 1 cost, 2 state, 3 action (cdt.py:185-200)
     if (a.R == 3 && p.use_rew) which = slot == 0 ? 0 : slot + 1;
-    const float* te = (p.te && !is_prefix) ? p.te + (size_t)a.d.win_t[ts] * E : nullptr;
-    const float ret = a.d.win_r[ts];
-    const float ctg = p.cost_transform ? 50.0f - a.d.win_c[ts] : a.d.win_c[ts];
-    const float ec = a.io.scalars[3];
+    const float* te = (p.te && !is_prefix) ? p.te + (size_t)d.win_t[ts] * E : nullptr;
+    const float ret = d.win_r[ts];
+    const float ctg = p.cost_transform ? 50.0f - d.win_c[ts] : d.win_c[ts];
+    const float ec = io.scalars[3];
     float v[kMaxE / 64];
 #pragma unroll
     for (int j = 0; j < kMaxE / 64; ++j) {
@@ -148,13 +165,13 @@ __global__ __launch_bounds__(256) void cdt_act_ingest_kernel(const IngestArgs a)
         } else if (which == 2) {
           x = p.state_b[f];
 #pragma unroll 4
-          for (int k = 0; k < od; ++k) x += a.d.win_s[ts * od + k] * p.state_w[(size_t)f * od + k];
+          for (int k = 0; k < od; ++k) x += d.win_s[ts * od + k] * p.state_w[(size_t)f * od + k];
         } else {
           x = p.action_b[f];
-          for (int k = 0; k < ad; ++k) x += a.d.win_a[ts * ad + k] * p.action_w[(size_t)f * ad + k];
+          for (int k = 0; k < ad; ++k) x += d.win_a[ts * ad + k] * p.action_w[(size_t)f * ad + k];
         }
         if (te) x += te[f];
-        a.d.raw[(size_t)row * a.ldE + f] = x;
+        d.raw[(size_t)row * a.ldE + f] = x;
       }
       v[j] = x;
     }
@@ -170,14 +187,15 @@ __global__ __launch_bounds__(256) void cdt_act_ingest_kernel(const IngestArgs a)
 #pragma unroll
     for (int j = 0; j < kMaxE / 64; ++j) {
       const int f = lane + 64 * j;
-      if (f < E) a.x0[(size_t)row * a.ldE + f] = (v[j] - mean) * rstd * p.emb_g[f] + p.emb_b[f];
+      if (f < E) x0[(size_t)row * a.ldE + f] = (v[j] - mean) * rstd * p.emb_g[f] + p.emb_b[f];
     }
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Y[r] = epi(LN?(X[r]) W^T + b) for the rows of a row set: one workgroup = one 16-row x 16-column tile, four waves
-// split K and meet in LDS.  epi: optional exact GELU, then an optional residual add.
+// split K and meet in LDS.  epi: optional exact GELU, then an optional residual add.  With nenv episodes the launch's
+// row list is the row set of episode 0, then of episode 1, ...: entry g is local row g % count of episode g / count.
 struct LinArgs {
   const float* X;
   const float *ln_g, *ln_b;  // LayerNorm of the input rows (K = E) or null
@@ -187,20 +205,37 @@ struct LinArgs {
   float* Y;
   int32_t ldx, ldr, ldy, K, N, gelu;
   int32_t first, count, ring;
+  int32_t nenv;
+  int64_t es;    // floats per episode block (X, res and Y are episode 0's)
+  uint64_t rcp;  // ceil(2^32 / count): g / count = (g * rcp) >> 32, exact for g < 2^16 and count <= 2^8
 };
 
 __global__ __launch_bounds__(256) void cdt_act_linear_kernel(const LinArgs a) {
   __shared__ float red[4][64][4];
   __shared__ float st[16][2];
   __shared__ int rows[16];
+  __shared__ long long xo[16], ro[16], yo[16];  // float offsets of the tile's rows in X, res and Y
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int r0 = blockIdx.y * 16, n0 = blockIdx.x * 16;
-  if (tid < 16) rows[tid] = r0 + tid < a.count ? ring_row(a.first, r0 + tid, a.ring) : -1;
+  if (tid < 16) {
+    const int g = r0 + tid;
+    int r = -1;
+    long long eo = 0;
+    if (g < a.count * a.nenv) {
+      const int e = (int)(((uint64_t)(uint32_t)g * a.rcp) >> 32);
+      r = ring_row(a.first, g - e * a.count, a.ring);
+      eo = (long long)e * a.es;
+    }
+    rows[tid] = r;
+    xo[tid] = eo + (long long)r * a.ldx;
+    ro[tid] = eo + (long long)r * a.ldr;
+    yo[tid] = eo + (long long)r * a.ldy;
+  }
   __syncthreads();
   if (a.ln_g) {
     for (int i = w; i < 16; i += 4) {
       float mean = 0.f, rstd = 0.f;
-      if (rows[i] >= 0) row_stats(a.X + (size_t)rows[i] * a.ldx, a.K, lane, &mean, &rstd);
+      if (rows[i] >= 0) row_stats(a.X + xo[i], a.K, lane, &mean, &rstd);
       if (lane == 0) {
         st[i][0] = mean;
         st[i][1] = rstd;
@@ -210,7 +245,7 @@ __global__ __launch_bounds__(256) void cdt_act_linear_kernel(const LinArgs a) {
   }
   const int ar = lane & 15, kq = lane >> 4;
   const int row = rows[ar];
-  const float* __restrict__ xr = row >= 0 ? a.X + (size_t)row * a.ldx : nullptr;
+  const float* __restrict__ xr = row >= 0 ? a.X + xo[ar] : nullptr;
   const float mean = a.ln_g ? st[ar][0] : 0.f, rstd = a.ln_g ? st[ar][1] : 1.f;
   const int Np = r16(a.N), nkb = r16(a.K) >> 4;
   const int kb0 = (nkb * w) >> 2, kb1 = (nkb * (w + 1)) >> 2;
@@ -264,20 +299,23 @@ __global__ __launch_bounds__(256) void cdt_act_linear_kernel(const LinArgs a) {
       float v = ((red[0][lane][i] + red[1][lane][i]) + red[2][lane][i]) + red[3][lane][i];
       v += a.bias[col];
       if (a.gelu) v = gelu_f(v);
-      if (a.res) v += a.res[(size_t)orow * a.ldr + col];
-      a.Y[(size_t)orow * a.ldy + col] = v;
+      if (a.res) v += a.res[ro[rr] + col];
+      a.Y[yo[rr] + col] = v;
     }
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// causal softmax attention of the listed query rows over the window (+ the prefix token): one wave per (row, head).
+// causal softmax attention of the listed query rows over the window (+ the prefix token): one wave per (row, head,
+// episode); keys and values are the query's own episode's.
 struct AttnArgs {
   const float* qkv;  // [NR, ldq]: q | k | v
   float* o;          // [NR, ldo]
   int32_t ldq, ldo, E, H, d, P, TR, ws;  // ws: ring row of the window's first token
   float scale;
-  int32_t first, count, ring;
+  int32_t first, ring;  // query rows: grid x entries from `first` (mod ring)
+  int32_t es;           // floats per episode block (grid z: episode).  (The struct stays within the 16 dwords a
+                        // launch hands over in registers.)
 };
 
 __global__ __launch_bounds__(64) void cdt_act_attn_kernel(const AttnArgs a) {
@@ -286,7 +324,9 @@ __global__ __launch_bounds__(64) void cdt_act_attn_kernel(const AttnArgs a) {
   const int row = ring_row(a.first, blockIdx.x, a.ring);
   // keys: the prefix (ring row TR) first, then the window's tokens up to and including the query
   const int nk = row == a.TR ? 1 : a.P + (row - a.ws + a.TR) % a.TR + 1;
-  const float* __restrict__ q = a.qkv + (size_t)row * a.ldq + h * a.d;
+  const float* __restrict__ qkv = a.qkv + (size_t)blockIdx.z * (size_t)a.es;
+  float* __restrict__ o = a.o + (size_t)blockIdx.z * (size_t)a.es;
+  const float* __restrict__ q = qkv + (size_t)row * a.ldq + h * a.d;
   float s[kMaxTok / 64];
   float mx = -INFINITY;
 #pragma unroll
@@ -295,7 +335,7 @@ __global__ __launch_bounds__(64) void cdt_act_attn_kernel(const AttnArgs a) {
     s[c] = -INFINITY;
     if (j < nk) {
       const int kr = j < a.P ? a.TR : (a.ws + j - a.P) % a.TR;
-      const float* __restrict__ k = a.qkv + (size_t)kr * a.ldq + a.E + h * a.d;
+      const float* __restrict__ k = qkv + (size_t)kr * a.ldq + a.E + h * a.d;
       float acc = 0.f;
 #pragma unroll 8
       for (int i = 0; i < a.d; ++i) acc = fmaf(q[i], k[i], acc);
@@ -321,15 +361,18 @@ __global__ __launch_bounds__(64) void cdt_act_attn_kernel(const AttnArgs a) {
 #pragma unroll 4
     for (int j = 0; j < nk; ++j) {
       const int kr = j < a.P ? a.TR : (a.ws + j - a.P) % a.TR;
-      acc = fmaf(pr[j], a.qkv[(size_t)kr * a.ldq + 2 * a.E + h * a.d + i], acc);
+      acc = fmaf(pr[j], qkv[(size_t)kr * a.ldq + 2 * a.E + h * a.d + i], acc);
     }
-    a.o[(size_t)row * a.ldo + h * a.d + i] = acc * inv;
+    o[(size_t)row * a.ldo + h * a.d + i] = acc * inv;
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // head: out LayerNorm of the newest state token, cost features, the action head's Linear (+ GELU) layers as GEMVs
-// (lanes own outputs over the packed weights, as act.hip), clamp, publish.
+// (lanes own outputs over the packed weights, as act.hip), clamp, publish.  One workgroup per episode; the sequence
+// number is published once, by the last workgroup to arrive at the handle's device counter: every workgroup makes its
+// act_out stores visible at system scope and then increments the counter; the one that sees nenv - 1 re-arms it and
+// does the release store.  Nobody waits for anybody.
 struct HeadArgs {
   osrl_cdt_policy_t p;
   Dev d;
@@ -337,6 +380,9 @@ struct HeadArgs {
   const float* x;  // [NR, ldE] the last block's output
   int32_t ldE, srow, crow;  // newest state token row, its cost token row (-1: none)
   uint64_t seq;
+  int64_t es;         // floats per episode block (grid: one workgroup per episode)
+  uint32_t* arrived;  // device counter of the workgroups that have stored their action (0 between launches)
+  int32_t nenv;
 };
 
 constexpr int kHeadThreads = 1024;
@@ -347,9 +393,12 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
   __shared__ float st[2];
   const osrl_cdt_policy_t& p = a.p;
   const int tid = threadIdx.x, E = p.embedding_dim;
+  const size_t eoff = (size_t)blockIdx.x * (size_t)a.es;
+  const float* __restrict__ x = a.x + eoff;
+  const float* __restrict__ raw = a.d.raw + eoff;
   if (tid < 64) {
     float mean, rstd;
-    row_stats(a.x + (size_t)a.srow * a.ldE, E, tid, &mean, &rstd);
+    row_stats(x + (size_t)a.srow * a.ldE, E, tid, &mean, &rstd);
     if (tid == 0) {
       st[0] = mean;
       st[1] = rstd;
@@ -360,9 +409,9 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
   for (int f = tid; f < kMaxHead; f += kHeadThreads) {
     float v = 0.f;
     if (f < E) {
-      v = (a.x[(size_t)a.srow * a.ldE + f] - st[0]) * st[1] * p.out_g[f] + p.out_b[f];
+      v = (x[(size_t)a.srow * a.ldE + f] - st[0]) * st[1] * p.out_g[f] + p.out_b[f];
       if (a.crow >= 0) {  // cdt.py:243-250, the detached (pre-LayerNorm) cost embedding
-        const float ce = a.d.raw[(size_t)a.crow * a.ldE + f];
+        const float ce = raw[(size_t)a.crow * a.ldE + f];
         if (p.add_cost_feat) {
           v = v + ce;
           if (p.mul_cost_feat) v = v * ce;
@@ -371,7 +420,7 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
         }
       }
     } else if (f < Eh) {
-      v = a.d.raw[(size_t)a.crow * a.ldE + (f - E)];
+      v = raw[(size_t)a.crow * a.ldE + (f - E)];
     }
     buf[0][f] = v;
   }
@@ -427,13 +476,21 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
   }
   if (tid < p.action_dim) {
     const float v = fminf(fmaxf(buf[cur][tid], -p.max_action), p.max_action);
-    a.io.act_out[tid] = v;
-    a.d.last_act[tid] = v;
+    a.io.act_out[(size_t)blockIdx.x * p.action_dim + tid] = v;
+    a.d.last_act[eoff + tid] = v;
   }
   __syncthreads();
   if (tid == 0) {
     __threadfence_system();
-    __hip_atomic_store(a.io.seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    bool last = a.nenv == 1;
+    if (!last) {
+      last = __hip_atomic_fetch_add(a.arrived, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)(a.nenv - 1);
+      if (last) {
+        __hip_atomic_store(a.arrived, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence_system();
+      }
+    }
+    if (last) __hip_atomic_store(a.io.seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -442,12 +499,15 @@ struct Handle {
   osrl_cdt_policy_t p;
   std::vector<osrl_cdt_layer_t> layers;
   int R, P, TR, NR, ldE, ld3, ld4;
-  int t;  // timestep of the newest window entry; -1 before the first reset
+  int nenv;    // episodes advanced in lockstep
+  int64_t es;  // floats per episode block of dmem
+  int t;       // timestep of the newest window entry (every episode's); -1 before the first reset
   Io host, dev;
   void* pinned;
   Dev d;
   void* dmem;
-  float *x, *qkv, *o, *xmid, *h;  // x: [NL + 1][NR, ldE], qkv: [NL][NR, ld3]
+  float *x, *qkv, *o, *xmid, *h;  // episode 0's; x: [NL + 1][NR, ldE], qkv: [NL][NR, ld3]
+  uint32_t* arrived;              // the head workgroups' arrival counter (past the episode blocks)
   uint64_t seq;
 };
 
@@ -455,8 +515,9 @@ int launch_linear(const Handle* h, const float* X, int ldx, const float* g, cons
                   const float* bias, const float* res, int ldr, float* Y, int ldy, int K, int N, int gelu, int first,
                   int count, int ring, hipStream_t s) {
   if (count <= 0) return 0;
-  LinArgs a{X, g, b, W, bias, res, Y, ldx, ldr, ldy, K, N, gelu, first, count, ring};
-  hipLaunchKernelGGL(cdt_act_linear_kernel, dim3((N + 15) / 16, (count + 15) / 16), dim3(256), 0, s, a);
+  LinArgs a{X, g, b, W, bias, res, Y, ldx, ldr, ldy, K, N, gelu, first, count, ring, h->nenv, h->es,
+            (((uint64_t)1 << 32) + (uint64_t)count - 1) / (uint64_t)count};
+  hipLaunchKernelGGL(cdt_act_linear_kernel, dim3((N + 15) / 16, (count * h->nenv + 15) / 16), dim3(256), 0, s, a);
   return 0;
 }
 
@@ -474,9 +535,9 @@ void run_layer(const Handle* h, int l, int first, int count, int ring, int ofirs
                 ring, s);
   if (ocount <= 0) return;
   const int d = E / p.num_heads;
-  AttnArgs at{qkv, h->o, h->ld3, h->ldE, E, p.num_heads, d, h->P, h->TR, ws, 1.0f / sqrtf((float)d), ofirst, ocount,
-              oring};
-  hipLaunchKernelGGL(cdt_act_attn_kernel, dim3(ocount, p.num_heads), dim3(64), 0, s, at);
+  AttnArgs at{qkv, h->o, h->ld3, h->ldE, E, p.num_heads, d, h->P, h->TR, ws, 1.0f / sqrtf((float)d), ofirst, oring,
+              (int32_t)h->es};
+  hipLaunchKernelGGL(cdt_act_attn_kernel, dim3(ocount, p.num_heads, h->nenv), dim3(64), 0, s, at);
   launch_linear(h, h->o, h->ldE, nullptr, nullptr, L.w_o, L.b_o, xin, h->ldE, h->xmid, h->ldE, E, E, 0, ofirst, ocount,
                 oring, s);
   launch_linear(h, h->xmid, h->ldE, L.ln2_g, L.ln2_b, L.w_1, L.b_1, nullptr, 0, h->h, h->ld4, E, 4 * E, 1, ofirst,
@@ -516,9 +577,9 @@ int run_step(Handle* h, int reset, int host_action, hipStream_t s) {
     first = (cur - 1 + TR) % TR;
     count = R;
   }
-  IngestArgs ia{p, h->d, h->dev, h->x, h->ldE, R, TR, t, reset, host_action, first, count, ring};
+  IngestArgs ia{p, h->d, h->dev, h->x, h->ldE, R, TR, t, reset, host_action, first, count, ring, h->es};
   (void)hipGetLastError();
-  hipLaunchKernelGGL(cdt_act_ingest_kernel, dim3(1), dim3(256), 0, s, ia);
+  hipLaunchKernelGGL(cdt_act_ingest_kernel, dim3(h->nenv), dim3(256), 0, s, ia);
   const int n = t + 1 < T ? t + 1 : T;            // timesteps in the window
   const int ws = ((t + 1 - n) % T) * R;            // ring row of its first token
   const int srow = cur + R - 2;                    // the newest state token
@@ -536,8 +597,9 @@ int run_step(Handle* h, int reset, int host_action, hipStream_t s) {
     run_layer(h, l, qf, qc, qr, of, oc, orr, ws, s);
   }
   HeadArgs ha{p, h->d, h->dev, h->x + (size_t)NL * h->NR * h->ldE, h->ldE, srow,
-              (p.add_cost_feat || p.mul_cost_feat || p.cat_cost_feat) ? cur + (p.use_rew ? 1 : 0) : -1, ++h->seq};
-  hipLaunchKernelGGL(cdt_act_head_kernel, dim3(1), dim3(kHeadThreads), 0, s, ha);
+              (p.add_cost_feat || p.mul_cost_feat || p.cat_cost_feat) ? cur + (p.use_rew ? 1 : 0) : -1, ++h->seq,
+              h->es, h->arrived, h->nenv};
+  hipLaunchKernelGGL(cdt_act_head_kernel, dim3(h->nenv), dim3(kHeadThreads), 0, s, ha);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   return spin(h, s);
@@ -568,10 +630,8 @@ bool valid(const osrl_cdt_policy_t& p, const osrl_cdt_layer_t* layers) {
   return true;
 }
 
-}  // namespace
-
-extern "C" int osrl_cdt_policy_create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, void** handle) {
-  if (!desc || !handle || !valid(*desc, layers)) return -1;
+int create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int n_env, void** handle) {
+  if (!desc || !handle || n_env < 1 || n_env > OSRL_CDT_POLICY_MAX_ENVS || !valid(*desc, layers)) return -1;
   const osrl_cdt_policy_t& p = *desc;
   Handle* h = new (std::nothrow) Handle;
   if (!h) return -1;
@@ -581,15 +641,18 @@ extern "C" int osrl_cdt_policy_create(const osrl_cdt_policy_t* desc, const osrl_
   h->P = p.cost_prefix ? 1 : 0;
   h->TR = h->R * p.seq_len;
   h->NR = h->TR + 1;
+  h->nenv = n_env;
   auto up16 = [](int x) { return (x + 15) & ~15; };
   const int E = p.embedding_dim, T = p.seq_len, od = p.state_dim, ad = p.action_dim, NL = p.num_layers;
+  const size_t NE = (size_t)n_env;
   h->ldE = up16(E), h->ld3 = up16(3 * E), h->ld4 = up16(4 * E);
   h->t = -1;
   h->seq = 0;
+  h->dmem = nullptr;
   auto r256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
-  // pinned block: obs, act_in, act_out, scalars, seq
-  const size_t o_obs = 0, o_ain = o_obs + r256(4 * od), o_aout = o_ain + r256(4 * ad), o_sc = o_aout + r256(4 * ad),
-               o_seq = o_sc + 256, pbytes = o_seq + 256;
+  // pinned block: obs [N, od], act_in [N, ad], act_out [N, ad], scalars [N, 4], seq
+  const size_t o_obs = 0, o_ain = o_obs + r256(4 * NE * od), o_aout = o_ain + r256(4 * NE * ad),
+               o_sc = o_aout + r256(4 * NE * ad), o_seq = o_sc + r256(16 * NE), pbytes = o_seq + 256;
   hipError_t e = hipHostMalloc(&h->pinned, pbytes, hipHostMallocMapped | hipHostMallocPortable);
   if (e != hipSuccess) {
     delete h;
@@ -608,7 +671,8 @@ extern "C" int osrl_cdt_policy_create(const osrl_cdt_policy_t* desc, const osrl_
                (float*)at(h->pinned, o_sc), (uint64_t*)at(h->pinned, o_seq)};
   h->dev = Io{(float*)at(dptr, o_obs), (float*)at(dptr, o_ain), (float*)at(dptr, o_aout), (float*)at(dptr, o_sc),
               (uint64_t*)at(dptr, o_seq)};
-  // device block: window ring, last action, raw embeddings, activations (zeroed: the row strides' padding stays 0)
+  // device block, one per episode: window ring, last action, raw embeddings, activations (zeroed: the row strides'
+  // padding stays 0); then the head's arrival counter
   const size_t NR = h->NR;
   size_t off = 0;
   auto take = [&](size_t floats) {
@@ -620,8 +684,15 @@ extern "C" int osrl_cdt_policy_create(const osrl_cdt_policy_t* desc, const osrl_
                o_la = take(ad), o_raw = take(NR * h->ldE), o_x = take((size_t)(NL + 1) * NR * h->ldE),
                o_q = take((size_t)NL * NR * h->ld3), o_o = take(NR * h->ldE), o_m = take(NR * h->ldE),
                o_h = take(NR * h->ld4);
-  e = hipMalloc(&h->dmem, off);
-  if (e == hipSuccess) e = hipMemset(h->dmem, 0, off);
+  if (off / 4 > (size_t)INT32_MAX) {  // (the attention launch passes the episode stride as 32 bits)
+    (void)hipHostFree(h->pinned);
+    delete h;
+    return -1;
+  }
+  h->es = (int64_t)(off / 4);
+  const size_t total = off * NE + 256;
+  e = hipMalloc(&h->dmem, total);
+  if (e == hipSuccess) e = hipMemset(h->dmem, 0, total);
   if (e != hipSuccess) {
     if (h->dmem) (void)hipFree(h->dmem);
     (void)hipHostFree(h->pinned);
@@ -636,57 +707,40 @@ extern "C" int osrl_cdt_policy_create(const osrl_cdt_policy_t* desc, const osrl_
   h->o = (float*)(base + o_o);
   h->xmid = (float*)(base + o_m);
   h->h = (float*)(base + o_h);
+  h->arrived = (uint32_t*)(base + off * NE);
   *handle = h;
   return 0;
 }
 
-extern "C" int osrl_cdt_policy_io(void* handle, float** obs, float** act_in, float** act_out) {
-  if (!handle) return -1;
-  Handle* h = static_cast<Handle*>(handle);
-  if (obs) *obs = h->host.obs;
-  if (act_in) *act_in = h->host.act_in;
-  if (act_out) *act_out = h->host.act_out;
-  return 0;
-}
-
-extern "C" int osrl_cdt_policy_reset(void* handle, float target_return, float target_cost, void* stream) {
-  if (!handle) return -1;
-  Handle* h = static_cast<Handle*>(handle);
-  h->host.scalars[2] = target_return;
-  h->host.scalars[3] = target_cost;
+int reset_all(Handle* h, hipStream_t s) {
   h->t = 0;
-  return run_step(h, 1, 0, (hipStream_t)stream);
+  return run_step(h, 1, 0, s);
 }
 
-extern "C" int osrl_cdt_policy_step(void* handle, float reward, float cost, int32_t host_action, void* stream) {
-  if (!handle) return -1;
-  Handle* h = static_cast<Handle*>(handle);
+int step_all(Handle* h, int host_action, hipStream_t s) {
   if (h->t < 0) return -1;  // no episode started
   if (h->p.te && h->t + 1 >= h->p.te_rows) return -1;  // past the timestep embedding table
-  h->host.scalars[0] = reward;
-  h->host.scalars[1] = cost;
   ++h->t;
-  return run_step(h, 0, host_action ? 1 : 0, (hipStream_t)stream);
+  return run_step(h, 0, host_action ? 1 : 0, s);
 }
 
-extern "C" int osrl_cdt_policy_window(void* handle, float* states, float* actions, float* returns, float* costs,
-                                      int64_t* time_steps, int32_t* n_out, void* stream) {
-  if (!handle) return -1;
-  Handle* h = static_cast<Handle*>(handle);
+int window_of(Handle* h, int env, float* states, float* actions, float* returns, float* costs, int64_t* time_steps,
+              int32_t* n_out, hipStream_t st) {
+  if (env < 0 || env >= h->nenv) return -1;
   const osrl_cdt_policy_t& p = h->p;
   const int T = p.seq_len, od = p.state_dim, ad = p.action_dim;
   if (h->t < 0) {
     if (n_out) *n_out = 0;
     return 0;
   }
+  const size_t eoff = (size_t)env * (size_t)h->es;
   std::vector<float> s((size_t)T * od), a((size_t)T * ad), r(T), c(T);
   std::vector<int32_t> ts(T);
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemcpyAsync(s.data(), h->d.win_s, 4 * s.size(), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(a.data(), h->d.win_a, 4 * a.size(), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(r.data(), h->d.win_r, 4 * T, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(c.data(), h->d.win_c, 4 * T, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(ts.data(), h->d.win_t, 4 * T, hipMemcpyDeviceToHost, st);
+  hipError_t e = hipMemcpyAsync(s.data(), h->d.win_s + eoff, 4 * s.size(), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(a.data(), h->d.win_a + eoff, 4 * a.size(), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(r.data(), h->d.win_r + eoff, 4 * T, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(c.data(), h->d.win_c + eoff, 4 * T, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(ts.data(), h->d.win_t + eoff, 4 * T, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return (int)e;
   const int n = h->t + 1 < T ? h->t + 1 : T, t0 = h->t + 1 - n;
@@ -700,6 +754,74 @@ extern "C" int osrl_cdt_policy_window(void* handle, float* states, float* action
   }
   if (n_out) *n_out = n;
   return 0;
+}
+
+}  // namespace
+
+extern "C" int osrl_cdt_policy_create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, void** handle) {
+  return create(desc, layers, 1, handle);
+}
+
+extern "C" int osrl_cdt_policy_create_n(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int32_t n_env,
+                                        void** handle) {
+  return create(desc, layers, n_env, handle);
+}
+
+extern "C" int osrl_cdt_policy_io(void* handle, float** obs, float** act_in, float** act_out) {
+  return osrl_cdt_policy_io_n(handle, obs, act_in, act_out, nullptr);
+}
+
+extern "C" int osrl_cdt_policy_io_n(void* handle, float** obs, float** act_in, float** act_out, float** scalars) {
+  if (!handle) return -1;
+  Handle* h = static_cast<Handle*>(handle);
+  if (obs) *obs = h->host.obs;
+  if (act_in) *act_in = h->host.act_in;
+  if (act_out) *act_out = h->host.act_out;
+  if (scalars) *scalars = h->host.scalars;
+  return 0;
+}
+
+// the one-episode calls pass their scalars as arguments: they serve handles of one episode only
+extern "C" int osrl_cdt_policy_reset(void* handle, float target_return, float target_cost, void* stream) {
+  if (!handle) return -1;
+  Handle* h = static_cast<Handle*>(handle);
+  if (h->nenv != 1) return -1;
+  h->host.scalars[2] = target_return;
+  h->host.scalars[3] = target_cost;
+  return reset_all(h, (hipStream_t)stream);
+}
+
+extern "C" int osrl_cdt_policy_step(void* handle, float reward, float cost, int32_t host_action, void* stream) {
+  if (!handle) return -1;
+  Handle* h = static_cast<Handle*>(handle);
+  if (h->nenv != 1 || h->t < 0) return -1;
+  h->host.scalars[0] = reward;
+  h->host.scalars[1] = cost;
+  return step_all(h, host_action, (hipStream_t)stream);
+}
+
+extern "C" int osrl_cdt_policy_reset_n(void* handle, void* stream) {
+  if (!handle) return -1;
+  return reset_all(static_cast<Handle*>(handle), (hipStream_t)stream);
+}
+
+extern "C" int osrl_cdt_policy_step_n(void* handle, int32_t host_action, void* stream) {
+  if (!handle) return -1;
+  return step_all(static_cast<Handle*>(handle), host_action, (hipStream_t)stream);
+}
+
+extern "C" int osrl_cdt_policy_window(void* handle, float* states, float* actions, float* returns, float* costs,
+                                      int64_t* time_steps, int32_t* n_out, void* stream) {
+  if (!handle) return -1;
+  return window_of(static_cast<Handle*>(handle), 0, states, actions, returns, costs, time_steps, n_out,
+                   (hipStream_t)stream);
+}
+
+extern "C" int osrl_cdt_policy_window_n(void* handle, int32_t env, float* states, float* actions, float* returns,
+                                        float* costs, int64_t* time_steps, int32_t* n_out, void* stream) {
+  if (!handle) return -1;
+  return window_of(static_cast<Handle*>(handle), env, states, actions, returns, costs, time_steps, n_out,
+                   (hipStream_t)stream);
 }
 
 extern "C" int osrl_cdt_policy_destroy(void* handle) {

@@ -8,11 +8,15 @@ Window updates use the existing loop's fp32 expressions (``returns - float(rewar
 
 The kernels read the packed forward weight copies and the biases of the model's flat group -- the buffers the fused
 AdamW step, ``load_state_dict`` and ``repack()`` keep current -- so training between evaluations needs no rebuild.
+
+``CDTVecFastPolicy`` is the same for ``num_envs`` episodes on as many host environments, advanced in lockstep by one C
+call per env step (``osrl_cdt_policy_*_n``): the step's launches run over the rows of all the episodes, and an
+episode's actions do not depend on how many ran beside it.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -21,6 +25,7 @@ from .. import _lib as L
 from .core import cur_stream
 
 MAX_TOKENS, MAX_E, MAX_HEAD_DIM = 256, 512, 128
+MAX_ENVS = L.CDT_POLICY_MAX_ENVS
 
 
 def unsupported(model) -> Optional[str]:
@@ -39,50 +44,56 @@ def unsupported(model) -> Optional[str]:
     return None
 
 
+def _descriptor(m) -> Tuple["L.CdtPolicyT", object]:
+    """The C descriptor of ``m`` and its per-layer array: device pointers into the model's flat group."""
+    g = m.groups["cdt"]
+    pk = lambda key: g.pf.data_ptr() + 4 * g.f_off[key]  # noqa: E731  packed forward copy
+    cv = lambda key: g.view(key).data_ptr()  # noqa: E731  canonical tensor
+    d = L.CdtPolicyT()
+    d.state_dim, d.action_dim, d.seq_len = m.state_dim, m.action_dim, m.seq_len
+    d.embedding_dim, d.num_layers, d.num_heads = m.embedding_dim, m.num_layers, m.num_heads
+    d.use_rew, d.use_cost, d.cost_prefix = int(m.use_rew), int(m.use_cost), int(m.cost_prefix)
+    d.cost_transform = int(m.cost_transform_on)
+    d.add_cost_feat, d.mul_cost_feat, d.cat_cost_feat = int(m.add_cost_feat), int(m.mul_cost_feat), int(m.cat_cost_feat)
+    chain = list(m.head_hidden_keys) + [m.head_out_key]
+    d.head_layers = len(chain)
+    d.head_out_width = 2 * m.action_dim if m.stochastic else m.action_dim
+    d.max_action = float(m.max_action)
+    if m.time_emb:
+        d.te = cv("cdt.timestep_emb.weight")
+        d.te_rows = g.layout["cdt.timestep_emb.weight"][1][0]
+    d.state_w, d.state_b = cv("cdt.state_emb.weight"), cv("cdt.state_emb.bias")
+    d.action_w, d.action_b = cv("cdt.action_emb.weight"), cv("cdt.action_emb.bias")
+    if m.use_rew:
+        d.return_w, d.return_b = cv("cdt.return_emb.weight"), cv("cdt.return_emb.bias")
+    if m.use_cost:
+        d.cost_w, d.cost_b = cv("cdt.cost_emb.weight"), cv("cdt.cost_emb.bias")
+    if m.cost_prefix:
+        d.prefix_w, d.prefix_b = cv("cdt.prefix_emb.weight"), cv("cdt.prefix_emb.bias")
+    d.emb_g, d.emb_b = cv("cdt.emb_norm.weight"), cv("cdt.emb_norm.bias")
+    d.out_g, d.out_b = cv("cdt.out_norm.weight"), cv("cdt.out_norm.bias")
+    for i, key in enumerate(chain):
+        d.head_w[i], d.head_b[i] = pk(key), cv(key[:-len("weight")] + "bias")
+    layers = (L.CdtLayerT * m.num_layers)()
+    for l in range(m.num_layers):
+        p, y = f"cdt.blocks.{l}.", layers[l]
+        y.ln1_g, y.ln1_b = cv(p + "norm1.weight"), cv(p + "norm1.bias")
+        y.w_qkv, y.b_qkv = pk(p + "attention.in_proj_weight"), cv(p + "attention.in_proj_bias")
+        y.w_o, y.b_o = pk(p + "attention.out_proj.weight"), cv(p + "attention.out_proj.bias")
+        y.ln2_g, y.ln2_b = cv(p + "norm2.weight"), cv(p + "norm2.bias")
+        y.w_1, y.b_1 = pk(p + "mlp.0.weight"), cv(p + "mlp.0.bias")
+        y.w_2, y.b_2 = pk(p + "mlp.2.weight"), cv(p + "mlp.2.bias")
+    return d, layers
+
+
 class CDTFastPolicy:
     def __init__(self, model):
         why = unsupported(model)
         if why is not None:
             raise NotImplementedError("the CDT act latency path does not support: " + why)
         m = self.model = model
-        g = m.groups["cdt"]
         self.device = torch.device(m.device)
-        pk = lambda key: g.pf.data_ptr() + 4 * g.f_off[key]  # noqa: E731  packed forward copy
-        cv = lambda key: g.view(key).data_ptr()  # noqa: E731  canonical tensor
-        d = L.CdtPolicyT()
-        d.state_dim, d.action_dim, d.seq_len = m.state_dim, m.action_dim, m.seq_len
-        d.embedding_dim, d.num_layers, d.num_heads = m.embedding_dim, m.num_layers, m.num_heads
-        d.use_rew, d.use_cost, d.cost_prefix = int(m.use_rew), int(m.use_cost), int(m.cost_prefix)
-        d.cost_transform = int(m.cost_transform_on)
-        d.add_cost_feat, d.mul_cost_feat, d.cat_cost_feat = int(m.add_cost_feat), int(m.mul_cost_feat), int(m.cat_cost_feat)
-        chain = list(m.head_hidden_keys) + [m.head_out_key]
-        d.head_layers = len(chain)
-        d.head_out_width = 2 * m.action_dim if m.stochastic else m.action_dim
-        d.max_action = float(m.max_action)
-        if m.time_emb:
-            d.te = cv("cdt.timestep_emb.weight")
-            d.te_rows = g.layout["cdt.timestep_emb.weight"][1][0]
-        d.state_w, d.state_b = cv("cdt.state_emb.weight"), cv("cdt.state_emb.bias")
-        d.action_w, d.action_b = cv("cdt.action_emb.weight"), cv("cdt.action_emb.bias")
-        if m.use_rew:
-            d.return_w, d.return_b = cv("cdt.return_emb.weight"), cv("cdt.return_emb.bias")
-        if m.use_cost:
-            d.cost_w, d.cost_b = cv("cdt.cost_emb.weight"), cv("cdt.cost_emb.bias")
-        if m.cost_prefix:
-            d.prefix_w, d.prefix_b = cv("cdt.prefix_emb.weight"), cv("cdt.prefix_emb.bias")
-        d.emb_g, d.emb_b = cv("cdt.emb_norm.weight"), cv("cdt.emb_norm.bias")
-        d.out_g, d.out_b = cv("cdt.out_norm.weight"), cv("cdt.out_norm.bias")
-        for i, key in enumerate(chain):
-            d.head_w[i], d.head_b[i] = pk(key), cv(key[:-len("weight")] + "bias")
-        layers = (L.CdtLayerT * m.num_layers)()
-        for l in range(m.num_layers):
-            p, y = f"cdt.blocks.{l}.", layers[l]
-            y.ln1_g, y.ln1_b = cv(p + "norm1.weight"), cv(p + "norm1.bias")
-            y.w_qkv, y.b_qkv = pk(p + "attention.in_proj_weight"), cv(p + "attention.in_proj_bias")
-            y.w_o, y.b_o = pk(p + "attention.out_proj.weight"), cv(p + "attention.out_proj.bias")
-            y.ln2_g, y.ln2_b = cv(p + "norm2.weight"), cv(p + "norm2.bias")
-            y.w_1, y.b_1 = pk(p + "mlp.0.weight"), cv(p + "mlp.0.bias")
-            y.w_2, y.b_2 = pk(p + "mlp.2.weight"), cv(p + "mlp.2.bias")
+        d, layers = _descriptor(m)
         lib = L.load()
         h = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -166,6 +177,144 @@ class CDTFastPolicy:
         if getattr(self, "_h", None) is not None:
             self._lib.osrl_cdt_policy_destroy(self._h)
             self._h = None
+
+    def __del__(self):  # pragma: no cover - interpreter shutdown order
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _vec_args(num_envs) -> int:
+    if isinstance(num_envs, bool) or not isinstance(num_envs, (int, np.integer)):
+        raise ValueError(f"num_envs must be an integer from 1 to {MAX_ENVS}, got {num_envs!r}")
+    if not 1 <= int(num_envs) <= MAX_ENVS:
+        raise ValueError(f"num_envs {int(num_envs)} is outside 1 .. {MAX_ENVS} (OSRL_CDT_POLICY_MAX_ENVS)")
+    return int(num_envs)
+
+
+class CDTVecFastPolicy:
+    """``num_envs`` episodes on as many host environments, in lockstep: all slots share the timestep, ``reset`` starts
+    all of them and ``step`` advances all of them with one C call.  A slot's actions are those a ``CDTFastPolicy`` returns
+    for the same inputs, bit for bit, whatever ``num_envs`` is.
+
+    A slot whose episode has ended is passed as inactive (``active[e] = False``): its rows of ``obs / reward / cost /
+    action`` are not read and its row of the result is zero.  Its device rows keep running on the stale inputs of its
+    last active step (lockstep: the launches cover every slot); nothing of that reaches the other slots."""
+
+    def __init__(self, model, num_envs: int):
+        N = self.num_envs = _vec_args(num_envs)
+        why = unsupported(model)
+        if why is not None:
+            raise NotImplementedError("the CDT act latency path does not support: " + why)
+        m = self.model = model
+        self.device = torch.device(m.device)
+        d, layers = _descriptor(m)
+        lib = L.load()
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(lib.osrl_cdt_policy_create_n(C.byref(d), layers, N, C.byref(h)), "osrl_cdt_policy_create_n")
+        self._h, self._lib = h, lib
+        ptrs = [C.POINTER(C.c_float)() for _ in range(4)]
+        L.check(lib.osrl_cdt_policy_io_n(h, *[C.byref(p) for p in ptrs]), "osrl_cdt_policy_io_n")
+        od, ad = m.state_dim, m.action_dim
+        self.od, self.ad, self.T = od, ad, m.seq_len
+        self._obs = np.ctypeslib.as_array(ptrs[0], shape=(N, od))  # numpy views of PINNED memory
+        self._act_in = np.ctypeslib.as_array(ptrs[1], shape=(N, ad))
+        self._act_out = np.ctypeslib.as_array(ptrs[2], shape=(N, ad))
+        self._scalars = np.ctypeslib.as_array(ptrs[3], shape=(N, 4))  # reward, cost, target_return, target_cost
+        self._t, self._episode_len = -1, 0
+        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+    __deepcopy__ = CDTFastPolicy.__deepcopy__
+    __reduce__ = CDTFastPolicy.__reduce__
+    _stream = CDTFastPolicy._stream
+
+    def _rows(self, name, x, tail) -> np.ndarray:
+        want = (self.num_envs,) + tail
+        if np.shape(x) != want:  # numpy would broadcast silently
+            raise ValueError(f"expected {name} of shape {want}, got {np.shape(x)}")
+        return np.asarray(x)
+
+    def _target(self, name, x) -> np.ndarray:
+        if np.ndim(x) != 0 and np.shape(x) != (self.num_envs,):
+            raise ValueError(f"expected {name} as a scalar or of shape ({self.num_envs},), got shape {np.shape(x)}")
+        return np.broadcast_to(np.asarray(x, dtype=np.float64), (self.num_envs,))
+
+    def reset(self, obs, target_return, target_cost) -> np.ndarray:
+        """Starts ``num_envs`` episodes from ``obs [N, state_dim]``; the targets are scalars or one per slot.  Returns
+        the first actions ``[N, action_dim]``."""
+        if self._h is None:
+            raise RuntimeError("CDTVecFastPolicy is closed")
+        obs = self._rows("obs", obs, (self.od,))
+        tr, tc = self._target("target_return", target_return), self._target("target_cost", target_cost)
+        self._episode_len = int(self.model.episode_len)
+        self.model.repack()  # in-place edits of the parameters since the last step (CDT.forward does the same)
+        self._obs[:] = obs  # float32 (round to nearest), as torch.as_tensor(obs) written into the fp32 window
+        self._scalars[:, 2] = tr  # float(target) -> fp32, as the one-episode call's float arguments
+        self._scalars[:, 3] = tc
+        self._t = 0
+        rc = self._lib.osrl_cdt_policy_reset_n(self._h, self._stream())
+        if rc != 0:
+            self._t = -1
+            L.check(rc, "osrl_cdt_policy_reset_n")
+        return self._act_out.copy()
+
+    def step(self, obs, reward, cost, action=None, active=None) -> np.ndarray:
+        """Per slot as ``CDTFastPolicy.step``: ``obs [N, state_dim]``, ``reward [N]``, ``cost [N]``, the actions taken at
+        the previous step (``action [N, action_dim]``, default: the ones returned) and ``active`` (bool ``[N]``, default:
+        all).  Returns the next actions ``[N, action_dim]``, zero in the rows of inactive slots."""
+        if self._t < 0:
+            raise RuntimeError("call reset() before step()")
+        if self._t + 1 >= self._episode_len:
+            raise RuntimeError(f"the episode is over: {self._episode_len} steps (model.episode_len)")
+        N = self.num_envs
+        obs = self._rows("obs", obs, (self.od,))
+        reward, cost = self._rows("reward", reward, ()), self._rows("cost", cost, ())
+        if action is not None:
+            action = self._rows("action", action, (self.ad,))
+        if active is not None:
+            active = self._rows("active", active, ())
+            if active.dtype != np.bool_:
+                raise ValueError(f"expected active as booleans, got dtype {active.dtype}")
+        if active is None:
+            self._obs[:] = obs
+            self._scalars[:, 0] = reward  # float(reward) -> fp32, as the one-episode call's float arguments
+            self._scalars[:, 1] = cost
+            if action is not None:
+                self._act_in[:] = action
+        else:
+            self._obs[active] = obs[active]
+            self._scalars[active, 0] = reward[active]
+            self._scalars[active, 1] = cost[active]
+            if action is not None:
+                self._act_in[active] = action[active]
+        rc = self._lib.osrl_cdt_policy_step_n(self._h, 0 if action is None else 1, self._stream())
+        if rc != 0:
+            L.check(rc, "osrl_cdt_policy_step_n")
+        self._t += 1
+        out = self._act_out.copy()
+        if active is not None:
+            out[~active] = 0.0
+        return out
+
+    def window(self, env: int) -> Dict[str, np.ndarray]:
+        """numpy copies of slot ``env``'s current window (oldest timestep first)."""
+        if not 0 <= int(env) < self.num_envs:
+            raise ValueError(f"env {env} is outside 0 .. {self.num_envs - 1}")
+        T, od, ad = self.T, self.od, self.ad
+        s, a = np.zeros((T, od), np.float32), np.zeros((T, ad), np.float32)
+        r, c, ts = np.zeros(T, np.float32), np.zeros(T, np.float32), np.zeros(T, np.int64)
+        n = C.c_int32(0)
+        f = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+        L.check(self._lib.osrl_cdt_policy_window_n(self._h, int(env), f(s), f(a), f(r), f(c), f(ts), C.byref(n),
+                                                   self._stream()), "osrl_cdt_policy_window_n")
+        k = n.value
+        return dict(states=s[:k].copy(), actions=a[:k].copy(), returns=r[:k].copy(), costs=c[:k].copy(),
+                    time_steps=ts[:k].copy())
+
+    close = CDTFastPolicy.close
 
     def __del__(self):  # pragma: no cover - interpreter shutdown order
         try:

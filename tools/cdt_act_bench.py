@@ -3,7 +3,13 @@
 (fast_rollout=True, csrc/cdt_act.hip) against the existing loop (fast_rollout=False), in one process on one device.
 Shapes: C5's CDT (od 11, ad 3, seq_len 20, E 256, 3 layers, 8 heads, all tokens, cost_transform, stochastic) with
 100-step episodes, and the reference's default model (E 128, seq_len 10) with 300-step episodes.
-Writes profiles/cdt_act_bench.json (--out).  --trace: one fast C5 episode only (for rocprofv3 --kernel-trace)."""
+Writes profiles/cdt_act_bench.json (--out).  --trace: one fast C5 episode only (for rocprofv3 --kernel-trace).
+
+--envs 1,2,4,...: the lockstep form instead (CDTTrainer.rollout_many over N host environments, CDTVecFastPolicy): per
+shape and N the aggregate env-steps/s, the time inside ``pol.step`` alone (the C call: launches + the wait for the
+published actions) and the time inside the environments' ``step`` (host numpy), each over --repeats runs, written to
+profiles/cdt_act_vec_bench.json (--vec-out) together with the one-episode fast rows of the same process.
+--trace --envs N: one lockstep C5 wave of N episodes only."""
 import argparse
 import json
 import os
@@ -47,13 +53,98 @@ def rate(m, fast, episodes):
     return steps / dt, steps, dt
 
 
+class TimedEnv:
+    """A host environment whose step() time is accumulated in ``clock[0]``."""
+
+    def __init__(self, env, clock):
+        self.env, self.clock = env, clock
+
+    def reset(self):
+        return self.env.reset()
+
+    def step(self, action):
+        t0 = time.perf_counter()
+        out = self.env.step(action)
+        self.clock[0] += time.perf_counter() - t0
+        return out
+
+
+def vec_rate(m, n_envs, waves):
+    """``waves`` lockstep waves of ``n_envs`` full episodes: (aggregate env steps, wall s, s inside pol.step, calls of
+    pol.step, s inside env.step)."""
+    env_clock, pol_clock = [0.0], [0.0, 0]
+    envs = [TimedEnv(SyntheticSafeEnv(11, 3, m.episode_len, seed=1 + e), env_clock) for e in range(n_envs)]
+    tr = CDTTrainer(m, None, DummyLogger(), use_graph=False)
+    pol = m.fast_policy(num_envs=n_envs)
+    inner = type(pol).step
+
+    def timed_step(*a, **k):
+        t0 = time.perf_counter()
+        out = inner(pol, *a, **k)
+        pol_clock[0] += time.perf_counter() - t0
+        pol_clock[1] += 1
+        return out
+
+    pol.step = timed_step
+    try:
+        tr.rollout_many(m, envs, 300.0, 10.0)  # warm-up
+        torch.cuda.synchronize()
+        env_clock[0], pol_clock[0], pol_clock[1] = 0.0, 0.0, 0
+        steps = 0
+        t0 = time.perf_counter()
+        for _ in range(waves):
+            steps += int(tr.rollout_many(m, envs, 300.0, 10.0)[1].sum())
+        dt = time.perf_counter() - t0
+    finally:
+        del pol.step
+    return steps, dt, pol_clock[0], pol_clock[1], env_clock[0]
+
+
+def vec_main(a):
+    ns = [int(x) for x in a.envs.split(",")]
+    if a.trace:
+        m = make("c5")
+        steps, dt, ps, pc, es = vec_rate(m, ns[0], 1)
+        print(f"traced lockstep C5 wave: {ns[0]} episodes, {steps} env steps in {dt * 1e3:.2f} ms = "
+              f"{steps / dt:.0f} env-steps/s; pol.step {ps / pc * 1e6:.1f} us per call")
+        return
+    res = dict(device=torch.cuda.get_device_name(0), repeats=a.repeats, one_episode={}, rows={})
+    for shape in SHAPES:
+        m = make(shape)
+        runs = [rate(m, True, a.fast_episodes)[0] for _ in range(a.repeats)]
+        res["one_episode"][shape] = dict(fast_env_steps_per_s=[round(r, 1) for r in runs])
+        print(shape, "one episode", json.dumps(res["one_episode"][shape]), flush=True)
+        res["rows"][shape] = {}
+        for n in ns:
+            waves = max(1, a.fast_episodes // n)
+            agg, step_us, env_us = [], [], []
+            for _ in range(a.repeats):
+                steps, dt, ps, pc, es = vec_rate(m, n, waves)
+                agg.append(round(steps / dt, 1))
+                step_us.append(round(ps / pc * 1e6, 2))
+                env_us.append(round(es / steps * 1e6, 2))
+            row = dict(envs=n, waves=waves, env_steps_per_s=agg, pol_step_us_per_call=step_us,
+                       pol_step_us_per_env_step=[round(x / n, 2) for x in step_us], env_step_us_per_env_step=env_us)
+            res["rows"][shape][str(n)] = row
+            print(shape, json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(a.vec_out), exist_ok=True)
+    with open(a.vec_out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cdt_act_bench.json"))
     ap.add_argument("--fast-episodes", type=int, default=20)
     ap.add_argument("--loop-episodes", type=int, default=2)
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--envs", default=None, help="comma-separated episode counts: the lockstep rows")
+    ap.add_argument("--vec-out", default=os.path.join(ROOT, "profiles", "cdt_act_vec_bench.json"))
+    ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
+    if a.envs:
+        return vec_main(a)
     if a.trace:
         m = make("c5")
         r, n, dt = rate(m, True, 1)
