@@ -996,6 +996,24 @@ int osrl_policy_io(void* handle, float** obs, float** noise, float** act, float*
 int osrl_policy_act(void* handle, int32_t rows, int32_t deterministic, int32_t host_noise, uint64_t seed, void* stream);
 int osrl_policy_destroy(void* handle);
 
+/* ---- lockstep act() path of the same policies (act_vec.hip): n_env episodes on as many host environments, ONE call per
+ * environment step for all of them.  Same descriptor, kinds and limits as osrl_policy_create (layers up to
+ * OSRL_MAX_WIDTH, OSRL_MAX_LAYERS); falls under the policy-handle exception above.  The slots are padded to 16-row
+ * tiles and every layer runs on fp32 MFMA, one workgroup per tile; no arithmetic crosses rows and a dot product's
+ * k-order is fixed by the layer shape, so a slot's action does not depend on n_env, on the slot or on its neighbours.
+ * 1 <= n_env <= OSRL_POLICY_MAX_ENVS, else -1. */
+#define OSRL_POLICY_MAX_ENVS 64
+int osrl_policy_create_n(const osrl_policy_t* desc, int32_t n_env, void** handle);
+/* HOST pointers into ONE pinned, device-mapped block: obs [n_env, obs_dim], noise [n_env, act_dim | latent_dim] (read
+ * when host_noise = 1), active [n_env] (0: the slot idles) and meta [n_env, 2] = (episode id, step) are the caller's
+ * to write; act [n_env, act_dim] and logp [n_env] are written by the kernel, for active slots only. */
+int osrl_policy_io_n(void* handle, float** obs, float** noise, float** act, float** logp, int32_t** active,
+                     int32_t** meta);
+/* one environment step of every active slot; returns after all actions have been published.  deterministic / host_noise
+ * as osrl_policy_act; noise drawn on the device is Philox keyed by (seed, meta[e][0], meta[e][1], element) only. */
+int osrl_policy_act_n(void* handle, int32_t deterministic, int32_t host_noise, uint64_t seed, void* stream);
+int osrl_policy_destroy_n(void* handle);
+
 /* ---- CDT act latency path (cdt_act.hip) ----------------------------------------------------------------------
  * CDTTrainer.rollout (cdt.py:436-518) on a host environment: one action per env step from the window of the last
  * seq_len timesteps.  Falls under the policy-handle exception above: a handle owns a pinned, device-mapped I/O block

@@ -146,6 +146,7 @@ class PolicyT(C.Structure):
 
 POLICY_MLP, POLICY_GAUSS, POLICY_BCQ = 0, 1, 2
 POLICY_MAX_ROWS = 4
+POLICY_MAX_ENVS = 64  # OSRL_POLICY_MAX_ENVS
 CDT_POLICY_MAX_ENVS = 64  # OSRL_CDT_POLICY_MAX_ENVS
 
 
@@ -201,6 +202,11 @@ PROTOTYPES = {
     "osrl_policy_io": [_vp, _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float))],
     "osrl_policy_act": [_vp, _i32, _i32, _i32, _u64, _vp],
     "osrl_policy_destroy": [_vp],
+    "osrl_policy_create_n": [_P(PolicyT), _i32, _P(C.c_void_p)],
+    "osrl_policy_io_n": [_vp, _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float)),
+                         _P(_P(C.c_int32)), _P(_P(C.c_int32))],
+    "osrl_policy_act_n": [_vp, _i32, _i32, _u64, _vp],
+    "osrl_policy_destroy_n": [_vp],
     "osrl_cdt_policy_create": [_P(CdtPolicyT), _P(CdtLayerT), _P(C.c_void_p)],
     "osrl_cdt_policy_io": [_vp, _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float))],
     "osrl_cdt_policy_reset": [_vp, _f32, _f32, _vp],

@@ -64,8 +64,16 @@ class BC(nn.Module):
         return self._engine
 
     @torch.no_grad()
-    def fast_policy(self):
-        """The B = 1 latency path (engine/act.py): one kernel launch per ``act()``, pinned-memory I/O."""
+    def fast_policy(self, num_envs: Optional[int] = None):
+        """The B = 1 latency path (engine/act.py): one kernel launch per ``act()``, pinned-memory I/O.
+        With ``num_envs`` an integer: the lockstep form for that many host environments (``VecFastPolicy``), built once
+        per model and ``num_envs``."""
+        if num_envs is not None:
+            from ..common.net import net_desc_seq
+            from ..engine.act import VecFastPolicy, cached_vec_policy
+            return cached_vec_policy(self, num_envs, lambda n: VecFastPolicy(
+                "mlp", self.device, self.actor.pi[0].in_features, self.action_dim,
+                net_desc_seq([self.actor.pi], float(self.actor.act_limit)), num_envs=n))
         if getattr(self, "_fast", None) is None:
             from ..common.net import net_desc_seq
             from ..engine.act import FastPolicy
@@ -105,6 +113,10 @@ class BCTrainer:
             from ..engine.rollout import evaluate_batched
             extra = float(self.cost_limit) if self.bc_mode == "multi-task" else None
             return evaluate_batched(self, "bc", eval_episodes, 1.0, extra)
+        if isinstance(self.env, (list, tuple)):  # N host environments: episode q on environment q % N, in lockstep
+            from ..engine.act import evaluate_lockstep
+            r, c, n = evaluate_lockstep(self, eval_episodes)
+            return r, c, n  # bc.py:123 does not rescale
         self.model.eval()
         rets, costs, lens = [], [], []
         for _ in range(eval_episodes):
@@ -112,6 +124,16 @@ class BCTrainer:
             rets.append(r); lens.append(l); costs.append(c)
         self.model.train()
         return np.mean(rets), np.mean(costs), np.mean(lens)  # bc.py:123 does not rescale
+
+    @torch.no_grad()
+    def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):
+        """``rollout`` on each of the host environments ``envs`` at once, in lockstep through
+        ``model.fast_policy(num_envs)`` (engine/act.py ``rollout_lockstep``): three arrays (return, length, cost sum), one
+        entry per environment.  ``num_slots`` (default ``len(envs)``): the width of the policy to use, the slots past
+        ``len(envs)`` idle.  In ``multi-task`` mode the cost limit is appended to every observation."""
+        from ..engine.act import rollout_lockstep
+        return rollout_lockstep(self.model, envs, num_slots, episode_ids,
+                                append=self.cost_limit if self.bc_mode == "multi-task" else None)
 
     @torch.no_grad()
     def rollout(self):

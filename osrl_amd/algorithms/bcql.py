@@ -118,17 +118,27 @@ class BCQL(nn.Module):
         """bcql.py:228-234 -- fused into the per-group optimizer kernels of train_one_step."""
         return None
 
+    def fast_policy(self, num_envs: Optional[int] = None):
+        """The B = 1 latency path (engine/act.py): one kernel launch per ``act()``, pinned-memory I/O.
+        With ``num_envs`` an integer: the lockstep form for that many host environments (``VecFastPolicy``), built once
+        per model and ``num_envs``."""
+        from ..common.net import net_desc_seq, vae_dec_desc
+        kw = dict(max_action=float(self.actor.act_limit), net1=net_desc_seq([self.actor.pi], 1.0),
+                  latent_dim=self.latent_dim, phi=float(self.actor.phi))
+        if num_envs is not None:
+            from ..engine.act import VecFastPolicy, cached_vec_policy
+            return cached_vec_policy(self, num_envs, lambda n: VecFastPolicy(
+                "bcq", self.device, self.state_dim, self.action_dim, vae_dec_desc(self.vae), num_envs=n, **kw))
+        if getattr(self, "_fast", None) is None:
+            from ..engine.act import FastPolicy
+            self._fast = FastPolicy("bcq", self.device, self.state_dim, self.action_dim, vae_dec_desc(self.vae), **kw)
+        return self._fast
+
     @torch.no_grad()
     def act(self, obs, deterministic=False, with_logprob=False, z=None):
         """bcql.py:236-243 (stochastic: decode draws z unless given)."""
-        if getattr(self, "_fast", None) is None:
-            from ..common.net import net_desc_seq, vae_dec_desc
-            from ..engine.act import FastPolicy
-            self._fast = FastPolicy("bcq", self.device, self.state_dim, self.action_dim, vae_dec_desc(self.vae),
-                                    max_action=float(self.actor.act_limit), net1=net_desc_seq([self.actor.pi], 1.0),
-                                    latent_dim=self.latent_dim, phi=float(self.actor.phi))
         zz = None if z is None else (z.detach().cpu().numpy() if torch.is_tensor(z) else np.asarray(z))
-        return self._fast.act(obs, deterministic, noise=zz)[0], None
+        return self.fast_policy().act(obs, deterministic, noise=zz)[0], None
 
 
 class BCQLTrainer:
@@ -156,6 +166,10 @@ class BCQLTrainer:
             from ..engine.rollout import evaluate_batched
             r, c, n = evaluate_batched(self, "bcql", eval_episodes, self.cost_scale)
             return r / self.reward_scale, c / self.cost_scale, n
+        if isinstance(self.env, (list, tuple)):  # N host environments: episode q on environment q % N, in lockstep
+            from ..engine.act import evaluate_lockstep
+            r, c, n = evaluate_lockstep(self, eval_episodes)
+            return r / self.reward_scale, c / self.cost_scale, n
         self.model.eval()
         rets, costs, lens = [], [], []
         for _ in range(eval_episodes):
@@ -163,6 +177,16 @@ class BCQLTrainer:
             rets.append(r); lens.append(l); costs.append(c)
         self.model.train()
         return np.mean(rets) / self.reward_scale, np.mean(costs) / self.cost_scale, np.mean(lens)
+
+    @torch.no_grad()
+    def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):
+        """``rollout`` on each of the host environments ``envs`` at once, in lockstep through
+        ``model.fast_policy(num_envs)`` (engine/act.py ``rollout_lockstep``): three arrays (return, length, cost sum), one
+        entry per environment.  ``num_slots`` (default ``len(envs)``): the width of the policy to use, the slots past
+        ``len(envs)`` idle.  The decode noise z of every step is drawn on the device, keyed by the episode id
+        (``episode_ids``, default 0 .. len(envs) - 1) and the step."""
+        from ..engine.act import rollout_lockstep
+        return rollout_lockstep(self.model, envs, num_slots, episode_ids, cost_scale=self.cost_scale)
 
     @torch.no_grad()
     def rollout(self):

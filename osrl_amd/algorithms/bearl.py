@@ -115,15 +115,26 @@ class BEARL(nn.Module):
         """bearl.py:329-335.  Fused into each group's optimizer kernel inside train_one_step."""
         return None
 
-    @torch.no_grad()
-    def act(self, obs: np.ndarray, deterministic: bool = False, with_logprob: bool = False):
-        """bearl.py:337-350: single observation -> (max_action * tanh(u), logp)."""
+    def fast_policy(self, num_envs: Optional[int] = None):
+        """The B = 1 latency path (engine/act.py): one kernel launch per ``act()``, pinned-memory I/O.
+        With ``num_envs`` an integer: the lockstep form for that many host environments (``VecFastPolicy``), built once
+        per model and ``num_envs``."""
+        from ..common.net import actor_head_desc
+        if num_envs is not None:
+            from ..engine.act import VecFastPolicy, cached_vec_policy
+            return cached_vec_policy(self, num_envs, lambda n: VecFastPolicy(
+                "gauss", self.device, self.state_dim, self.action_dim, actor_head_desc(self.actor),
+                max_action=self.max_action, num_envs=n))
         if getattr(self, "_fast", None) is None:
-            from ..common.net import actor_head_desc
             from ..engine.act import FastPolicy
             self._fast = FastPolicy("gauss", self.device, self.state_dim, self.action_dim, actor_head_desc(self.actor),
                                     max_action=self.max_action)
-        return self._fast.act(obs, deterministic)
+        return self._fast
+
+    @torch.no_grad()
+    def act(self, obs: np.ndarray, deterministic: bool = False, with_logprob: bool = False):
+        """bearl.py:337-350: single observation -> (max_action * tanh(u), logp)."""
+        return self.fast_policy().act(obs, deterministic)
 
 
 class BEARLTrainer:
@@ -153,6 +164,10 @@ class BEARLTrainer:
             from ..engine.rollout import evaluate_batched
             r, c, n = evaluate_batched(self, "cpq", eval_episodes, self.cost_scale)
             return r / self.reward_scale, c / self.cost_scale, n
+        if isinstance(self.env, (list, tuple)):  # N host environments: episode q on environment q % N, in lockstep
+            from ..engine.act import evaluate_lockstep
+            r, c, n = evaluate_lockstep(self, eval_episodes)
+            return r / self.reward_scale, c / self.cost_scale, n
         self.model.eval()
         rets, costs, lens = [], [], []
         for _ in range(eval_episodes):
@@ -160,6 +175,15 @@ class BEARLTrainer:
             rets.append(r); lens.append(l); costs.append(c)
         self.model.train()
         return np.mean(rets) / self.reward_scale, np.mean(costs) / self.cost_scale, np.mean(lens)
+
+    @torch.no_grad()
+    def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):
+        """``rollout`` on each of the host environments ``envs`` at once, in lockstep through
+        ``model.fast_policy(num_envs)`` (engine/act.py ``rollout_lockstep``): three arrays (return, length, cost sum), one
+        entry per environment.  ``num_slots`` (default ``len(envs)``): the width of the policy to use, the slots past
+        ``len(envs)`` idle.  The policy acts deterministically."""
+        from ..engine.act import rollout_lockstep
+        return rollout_lockstep(self.model, envs, num_slots, episode_ids, cost_scale=self.cost_scale)
 
     @torch.no_grad()
     def rollout(self):

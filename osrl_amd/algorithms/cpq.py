@@ -124,8 +124,16 @@ class CPQ(nn.Module):
         train_one_step (same result: no target is read between its group's step and the step end)."""
         return None
 
-    def fast_policy(self):
-        """The B = 1 latency path (engine/act.py): one kernel launch per ``act()``, pinned-memory I/O."""
+    def fast_policy(self, num_envs: Optional[int] = None):
+        """The B = 1 latency path (engine/act.py): one kernel launch per ``act()``, pinned-memory I/O.
+        With ``num_envs`` an integer: the lockstep form for that many host environments (``VecFastPolicy``), built once
+        per model and ``num_envs``."""
+        if num_envs is not None:
+            from ..common.net import actor_head_desc
+            from ..engine.act import VecFastPolicy, cached_vec_policy
+            return cached_vec_policy(self, num_envs, lambda n: VecFastPolicy(
+                "gauss", self.device, self.state_dim, self.action_dim, actor_head_desc(self.actor),
+                max_action=self.max_action, num_envs=n))
         if self._fast is None:
             from ..common.net import actor_head_desc
             from ..engine.act import FastPolicy
@@ -173,11 +181,16 @@ class CPQTrainer:
 
     def evaluate(self, eval_episodes):
         """cpq.py:315-328.  With a ``VecSyntheticSafeEnv`` as ``self.env`` the episodes run as one batch on device
-        (engine/rollout.py); any other (gym-style) env takes the reference's episode-by-episode loop."""
+        (engine/rollout.py); a list or tuple of N host (gym-style) environments runs episode ``q`` on environment
+        ``q % N``, N at a time in lockstep (``rollout_many``); any other (gym-style) env takes the reference's episode-by-episode loop."""
         from ..common.synthetic_env import VecSyntheticSafeEnv
         if isinstance(self.env, VecSyntheticSafeEnv):
             from ..engine.rollout import evaluate_batched
             r, c, n = evaluate_batched(self, "cpq", eval_episodes, self.cost_scale)
+            return r / self.reward_scale, c / self.cost_scale, n
+        if isinstance(self.env, (list, tuple)):  # N host environments: episode q on environment q % N, in lockstep
+            from ..engine.act import evaluate_lockstep
+            r, c, n = evaluate_lockstep(self, eval_episodes)
             return r / self.reward_scale, c / self.cost_scale, n
         self.model.eval()
         rets, costs, lens = [], [], []
@@ -188,6 +201,15 @@ class CPQTrainer:
             costs.append(c)
         self.model.train()
         return np.mean(rets) / self.reward_scale, np.mean(costs) / self.cost_scale, np.mean(lens)
+
+    @torch.no_grad()
+    def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):
+        """``rollout`` on each of the host environments ``envs`` at once, in lockstep through
+        ``model.fast_policy(num_envs)`` (engine/act.py ``rollout_lockstep``): three arrays (return, length, cost sum), one
+        entry per environment.  ``num_slots`` (default ``len(envs)``): the width of the policy to use, the slots past
+        ``len(envs)`` idle.  The policy acts deterministically."""
+        from ..engine.act import rollout_lockstep
+        return rollout_lockstep(self.model, envs, num_slots, episode_ids, cost_scale=self.cost_scale)
 
     @torch.no_grad()
     def rollout(self):

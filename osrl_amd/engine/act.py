@@ -10,6 +10,10 @@ The kernel reads the packed forward weight copies of the flat optimizer groups -
 and ``load_state_dict`` keep in step with the parameters -- and the canonical biases; the flat buffers never move, so a
 ``FastPolicy`` built once stays valid for the model's lifetime (in-place edits of parameters from outside the trainer
 need ``model.repack()``, as for training).
+
+``VecFastPolicy`` is the same for ``num_envs`` episodes on as many host environments, advanced in lockstep by one C call
+per environment step (csrc/act_vec.hip, ``osrl_policy_*_n``): the slots are rows of 16-row fp32-MFMA tiles, and a
+slot's action does not depend on how many ran beside it.
 """
 from __future__ import annotations
 
@@ -131,3 +135,216 @@ class FastPolicy:
             self.close()
         except Exception:
             pass
+
+
+MAX_ENVS = L.POLICY_MAX_ENVS
+
+
+def _vec_args(num_envs) -> int:
+    if isinstance(num_envs, bool) or not isinstance(num_envs, (int, np.integer)):
+        raise ValueError(f"num_envs must be an integer from 1 to {MAX_ENVS}, got {num_envs!r}")
+    if not 1 <= int(num_envs) <= MAX_ENVS:
+        raise ValueError(f"num_envs {int(num_envs)} is outside 1 .. {MAX_ENVS} (OSRL_POLICY_MAX_ENVS)")
+    return int(num_envs)
+
+
+class VecFastPolicy:
+    """``num_envs`` episodes of one policy on as many host environments, in lockstep: ``reset`` starts episodes and
+    ``step`` advances them, one C call each for all slots.  Same kinds and descriptors as ``FastPolicy``.  A slot's
+    action is the same bits whatever ``num_envs`` is, whichever slot it is and whatever the other slots hold.
+
+    A slot passed as inactive (``active[e] = False``) idles: its row of ``obs`` / ``noise`` is not read, its step does
+    not advance and its rows of the results keep the values of its last active call.
+
+    Noise the kernel draws itself (no ``noise`` argument: z of "bcq", eps of a stochastic "gauss") is keyed by the
+    policy's seed, the slot's episode id and its step within the episode only, so an episode replays identically in any
+    slot of a policy of any width."""
+
+    KINDS = FastPolicy.KINDS
+
+    def __init__(self, kind: str, device, obs_dim: int, act_dim: int, net0: NetDesc, max_action: float = 1.0,
+                 net1: Optional[NetDesc] = None, latent_dim: int = 0, phi: float = 0.0, seed: int = 0,
+                 num_envs: int = 1):
+        N = self.num_envs = _vec_args(num_envs)
+        require_cuda(device)
+        self.device = torch.device(device)
+        d = L.PolicyT()
+        d.kind, d.obs_dim, d.act_dim, d.latent_dim = self.KINDS[kind], obs_dim, act_dim, latent_dim
+        d.max_action, d.phi = float(max_action), float(phi)
+        _gemv_net(d.net[0], net0)
+        if net1 is not None:
+            _gemv_net(d.net[1], net1)
+        self._keep = (net0, net1)  # the descriptors hold the parameter views alive
+        self.kind, self.obs_dim, self.act_dim, self.seed = kind, obs_dim, act_dim, int(seed)
+        self.noise_dim = {"mlp": 0, "gauss": act_dim, "bcq": latent_dim}[kind]
+        lib = L.load()
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(lib.osrl_policy_create_n(C.byref(d), N, C.byref(h)), "osrl_policy_create_n")
+        self._h, self._lib = h, lib
+        fp = [C.POINTER(C.c_float)() for _ in range(4)]
+        ip = [C.POINTER(C.c_int32)() for _ in range(2)]
+        L.check(lib.osrl_policy_io_n(h, *[C.byref(p) for p in fp + ip]), "osrl_policy_io_n")
+        view = lambda p, shape: np.ctypeslib.as_array(p, shape=shape)  # noqa: E731  numpy views of PINNED memory
+        self.obs = view(fp[0], (N, obs_dim))
+        self.noise = view(fp[1], (N, max(self.noise_dim, 1)))
+        self.act_out = view(fp[2], (N, act_dim))
+        self.logp_out = view(fp[3], (N,))
+        self._active = view(ip[0], (N,))
+        self._meta = view(ip[1], (N, 2))  # (episode id, step) of each slot
+        self._started = False
+        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+    __deepcopy__ = FastPolicy.__deepcopy__
+    __reduce__ = FastPolicy.__reduce__
+
+    def _rows(self, name, x, tail, dtype=None) -> np.ndarray:
+        want = (self.num_envs,) + tail
+        if np.shape(x) != want:  # numpy would broadcast silently
+            raise ValueError(f"expected {name} of shape {want}, got {np.shape(x)}")
+        return np.asarray(x, dtype=dtype)
+
+    def _checked(self, obs, active, noise):
+        obs = self._rows("obs", obs, (self.obs_dim,))
+        if active is not None:
+            active = self._rows("active", active, ())
+            if active.dtype != np.bool_:
+                raise ValueError(f"expected active as booleans, got dtype {active.dtype}")
+        if noise is not None:
+            if not self.noise_dim:
+                raise ValueError(f'a "{self.kind}" policy takes no noise')
+            noise = self._rows("noise", noise, (self.noise_dim,), np.float32)
+        return obs, active, noise
+
+    def _call(self, obs, active, noise, deterministic) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        if active is None:
+            self.obs[:] = obs  # converts dtype
+            self._active[:] = 1
+            if noise is not None:
+                self.noise[:, :self.noise_dim] = noise
+        else:
+            self.obs[active] = obs[active]
+            self._active[:] = active
+            if noise is not None:
+                self.noise[active, :self.noise_dim] = noise[active]
+        st = self._raw_stream(self._dev_index) if self._raw_stream is not None else cur_stream()
+        rc = self._lib.osrl_policy_act_n(self._h, 1 if deterministic else 0, 0 if noise is None else 1, self.seed, st)
+        if rc != 0:
+            L.check(rc, "osrl_policy_act_n")
+        return self.act_out.copy(), (self.logp_out.copy() if self.kind == "gauss" else None)
+
+    def reset(self, obs, episode_ids=None, active=None, noise=None, deterministic: bool = True):
+        """Starts an episode in every active slot from ``obs [N, obs_dim]`` (``episode_ids``: ``[N]`` integers, default
+        the slot numbers; ``active``: bool ``[N]``, default all) and returns the first ``(actions [N, act_dim],
+        log-probs [N] or None)``."""
+        if self._h is None:
+            raise RuntimeError("VecFastPolicy is closed")
+        obs, active, noise = self._checked(obs, active, noise)
+        if episode_ids is None:
+            ids = np.arange(self.num_envs, dtype=np.int64)
+        else:
+            ids = self._rows("episode_ids", episode_ids, ())
+            if ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 0x7FFFFFFF).any():
+                raise ValueError("expected episode_ids as integers in 0 .. 2^31 - 1")
+        sel = slice(None) if active is None else active
+        self._meta[sel, 0] = ids[sel]
+        self._meta[sel, 1] = 0
+        self._started = True
+        return self._call(obs, active, noise, deterministic)
+
+    def step(self, obs, active=None, noise=None, deterministic: bool = True):
+        """The next ``(actions, log-probs or None)`` of every active slot from its new observation.  ``noise``:
+        explicit standard-normal draws ``[N, act_dim]`` (eps of "gauss") or ``[N, latent_dim]`` (z of "bcq")."""
+        if self._h is None:
+            raise RuntimeError("VecFastPolicy is closed")
+        if not self._started:
+            raise RuntimeError("call reset() before step()")
+        obs, active, noise = self._checked(obs, active, noise)
+        self._meta[slice(None) if active is None else active, 1] += 1
+        return self._call(obs, active, noise, deterministic)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            self._lib.osrl_policy_destroy_n(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover - interpreter shutdown order
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cached_vec_policy(model, num_envs, make):
+    """``model``'s ``VecFastPolicy`` of width ``num_envs`` (one per width, built by ``make(num_envs)`` on first use)."""
+    N = _vec_args(num_envs)
+    cache = model.__dict__.setdefault("_fast_vec", {})
+    if cache.get(N) is None:  # (None: the slot of a copied / unpickled model)
+        cache[N] = make(N)
+    return cache[N]
+
+
+def rollout_lockstep(model, envs, num_slots=None, episode_ids=None, cost_scale=None, append=None):
+    """The MLP trainers' ``rollout()`` on each of the host environments ``envs`` at once, through
+    ``model.fast_policy(num_envs)``: one C call per environment step for all of them.  Returns three arrays (return,
+    length, cost sum), one entry per environment.  A slot leaves the loop when its environment terminates, truncates or
+    reaches ``model.episode_len``; the slots past ``len(envs)`` idle.  ``cost_scale``: factor on ``info["cost"]`` (None:
+    summed as it is); ``append``: a value appended to every observation (BC's multi-task cost limit); ``episode_ids``
+    (default 0 .. len(envs) - 1) key the noise the policy draws on the device."""
+    envs = list(envs)
+    n = len(envs)
+    N = n if num_slots is None else int(num_slots)
+    if N < n:
+        raise ValueError(f"{n} environments do not fit {N} slots")
+    ep_ret, ep_len, ep_cost = [0.0] * n, np.zeros(n, np.int64), [0.0] * n
+    if episode_ids is not None and np.shape(episode_ids) != (n,):
+        raise ValueError(f"expected episode_ids of shape ({n},), got {np.shape(episode_ids)}")
+    if n == 0:
+        return np.asarray(ep_ret), ep_len, np.asarray(ep_cost)
+    ids = np.zeros(N, np.int64)
+    ids[:n] = np.arange(n) if episode_ids is None else episode_ids
+    pol = model.fast_policy(num_envs=N)
+    obs = np.zeros((N, pol.obs_dim), np.float32)
+    active = np.zeros(N, bool)
+    active[:n] = True
+    put = (lambda o: o) if append is None else (lambda o: np.append(o, append))  # noqa: E731
+    for e, env in enumerate(envs):
+        o, _ = env.reset()
+        obs[e] = put(o)
+    act, _ = pol.reset(obs, episode_ids=ids, active=active)
+    EL = model.episode_len
+    for step in range(EL):
+        for e in np.flatnonzero(active):
+            o, r, terminated, truncated, info = envs[e].step(act[e])
+            ep_ret[e] += r
+            ep_len[e] += 1
+            ep_cost[e] += info["cost"] if cost_scale is None else info["cost"] * cost_scale
+            if terminated or truncated or step + 1 == EL:
+                active[e] = False
+                continue
+            obs[e] = put(o)
+        if not active.any():
+            break
+        act, _ = pol.step(obs, active=active)
+    return np.asarray(ep_ret), ep_len, np.asarray(ep_cost)
+
+
+def evaluate_lockstep(trainer, eval_episodes):
+    """``eval_episodes`` rollouts over the list of host environments ``trainer.env``: episode ``q`` runs in wave
+    ``q // N`` on environment ``q % N`` with episode id ``q``.  Returns the means (return, cost sum, length), not
+    rescaled."""
+    envs = list(trainer.env)
+    N = len(envs)
+    if N == 0:
+        raise ValueError("evaluate over an empty list of environments")
+    trainer.model.eval()
+    rets, lens, costs = [], [], []
+    for q0 in range(0, int(eval_episodes), N):
+        k = min(N, int(eval_episodes) - q0)
+        r, l, c = trainer.rollout_many(envs[:k], num_slots=N, episode_ids=np.arange(q0, q0 + k))
+        rets += list(r)
+        lens += list(l)
+        costs += list(c)
+    trainer.model.train()
+    return np.mean(rets), np.mean(costs), np.mean(lens)
