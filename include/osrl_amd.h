@@ -920,6 +920,20 @@ int osrl_augment_gather(const float* obs, const float* act, const float* rew, co
 int osrl_bc_frontier_select(const float* cost_returns, const float* rew_returns, int64_t n, const double* coef,
                             const int32_t* deg, const double* stats, float* mask, int64_t* idx, int32_t* n_keep,
                             int32_t* ws, void* stream);
+/* compute_sample_prob (dataset.py:399-436, SequenceDataset(pf_sample=True)): w_i = 1 / (dist_i + beta), dist_i the
+ * distance of (c, r) = (cost_returns, returns)[traj_start[i]] to the frontier p (coef / deg from osrl_polyfit) as the
+ * reference's BFGS solve arrives at it: with f(x) = (x-c)^2 + (p(x)-r)^2 and g = f'/2, x* = c if g(c) == 0, else the
+ * first root of g with a sign change downhill from c (below c if g(c) > 0, above if g(c) < 0); x = max(0, x*),
+ * dist = sqrt(f(x)).  The roots are isolated through the derivative chain and bisected to fp64 resolution
+ * (csrc/pf_dist.h); fp64 throughout, one thread per trajectory.  prob = w / sum w and cdf (optional) = its inclusive
+ * running sum, fp32, summed in fp64 in a fixed order (the same bits on every run).  dist (optional): [n_traj] fp64.
+ * ws: [n_traj] doubles.  n_traj <= 2^20, deg <= 7, beta > 0. */
+int osrl_pf_sample_prob(const float* returns, const float* cost_returns, const int64_t* traj_start, int32_t n_traj,
+                        const double* coef, const int32_t* deg, double beta, float* prob, float* cdf, double* dist,
+                        double* ws, void* stream);
+/* prob[i] = max(weights[i], 0) / sum, cdf (optional) = inclusive running sum / sum, from any per-trajectory fp64
+ * weights on device (SequenceStore.set_sample_prob; a python cost_transform applied on the host); n <= 2^20. */
+int osrl_weights_sample_prob(const double* weights, int32_t n, float* prob, float* cdf, void* stream);
 
 /* ---- batched on-device evaluation ----
  * The reference's Trainer.rollout (cpq.py:330-347, bcql.py:323-340, bc.py:125-145) steps ONE gym env per policy

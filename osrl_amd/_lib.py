@@ -236,6 +236,8 @@ PROTOTYPES = {
     "osrl_augment_gather": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32,
                             _f64, _f64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "osrl_bc_frontier_select": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "osrl_pf_sample_prob": [_vp, _vp, _vp, _i32, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp],
+    "osrl_weights_sample_prob": [_vp, _i32, _vp, _vp, _vp],
     "osrl_vae_ns_supported": [_P(VaeNsT)],
     "osrl_vae_ns_forward": [_P(VaeNsT), _vp],
     "osrl_vae_ns_backward": [_P(VaeNsT), _vp],

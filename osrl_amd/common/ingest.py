@@ -1,14 +1,15 @@
 """Dataset ingestion on device: the reference's pre-training host passes over a DSRL dataset --
 ``process_sequence_dataset`` (osrl/common/dataset.py:137-183), ``compute_cost_sample_prob`` (:439-459),
-``process_bc_dataset`` (:30-134) -- run as HIP kernels (csrc/ingest.hip) on arrays uploaded once, and hand their
-results straight to the on-device samplers (``SequenceStore`` / ``ReplayStore``) without a trip back to the host.
+``compute_sample_prob`` (:399-436), ``process_bc_dataset`` (:30-134) -- run as HIP kernels (csrc/ingest.hip,
+csrc/augment.hip) on arrays uploaded once, and hand their results straight to the on-device samplers
+(``SequenceStore`` / ``ReplayStore``) without a trip back to the host.
 
 Same function names and argument meaning as the reference; inputs are the DSRL dict of numpy arrays (or device
 tensors), outputs are device tensors.  There is no CPU path: a missing HIP library raises.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple, Union
+from typing import Callable, Dict, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -75,20 +76,42 @@ def process_sequence_dataset(dataset: Dict[str, "np.ndarray | torch.Tensor"], co
                 cost_returns=cret[:n], traj_start=ep.start, traj_len=ep.length)
 
 
-CostTransform = Union[Tuple[str, float, float], Tuple[str, float]]
+CostTransform = Union[Tuple[str, float, float], Tuple[str, float], Callable]
+
+
+def sample_prob_from_weights(weights, with_cdf: bool = False, device=None):
+    """Any per-trajectory weights (numpy or tensor, host or device) -> fp32 ``prob = max(w, 0) / sum`` (and the
+    inclusive cdf the window sampler reads), normalised on device in fp64 in a fixed order of additions."""
+    dev = weights.device if torch.is_tensor(weights) and weights.is_cuda else require_cuda(device or "cuda")
+    w = _dev(weights, dev, torch.float64).reshape(-1)
+    n = int(w.shape[0])
+    if not 1 <= n <= 1 << 20:
+        raise ValueError(f"1 .. 2^20 trajectory weights, got {n}")
+    prob = torch.zeros(n, dtype=torch.float32, device=dev)
+    cdf = torch.zeros(n, dtype=torch.float32, device=dev)
+    L.check(L.load().osrl_weights_sample_prob(w.data_ptr(), n, prob.data_ptr(), cdf.data_ptr(), cur_stream()),
+            "osrl_weights_sample_prob")
+    return (prob, cdf) if with_cdf else prob
 
 
 def compute_cost_sample_prob(tables: Dict[str, torch.Tensor], cost_transform: CostTransform = ("affine", -1.0, 50.0),
                              with_cdf: bool = False):
-    """dataset.py:439-459 on device.  ``cost_transform`` names the two forms the reference's scripts use instead of a
-    python callable: ``("affine", a, b)`` = ``a*x + b`` (the default ``50 - x``; train_cdt.py:139 ``70 - x``) or
-    ``("reciprocal", b)`` = ``1 / (x + b)`` (train_cdt.py:139).  Returns prob (and the cdf the sampler reads)."""
+    """dataset.py:439-459 on device.  ``cost_transform`` names the two forms the reference's scripts use:
+    ``("affine", a, b)`` = ``a*x + b`` (the default ``50 - x``; train_cdt.py:139 ``70 - x``) or
+    ``("reciprocal", b)`` = ``1 / (x + b)`` (train_cdt.py:139); those stay on device end to end.  A python callable
+    (the reference's own argument) is applied on the host to the ``n_traj`` first cost returns, one fp32 scalar at a
+    time as the reference applies it, negatives set to 0, and the weights are normalised on device.  Returns prob
+    (and the cdf the sampler reads)."""
+    n_traj = int(tables["traj_start"].shape[0])
+    dev = tables["cost_returns"].device
+    if callable(cost_transform):
+        c0 = tables["cost_returns"][tables["traj_start"]].cpu().numpy()  # one small copy: [n_traj] fp32
+        w = np.array([cost_transform(x) for x in c0])
+        return sample_prob_from_weights(np.where(w < 0, 0, w), with_cdf, dev)
     kind, a, b = (COST_AFFINE, float(cost_transform[1]), float(cost_transform[2])) if cost_transform[0] == "affine" \
         else (COST_RECIPROCAL, 0.0, float(cost_transform[1]))
     if cost_transform[0] not in ("affine", "reciprocal"):
         raise ValueError(cost_transform)
-    n_traj = int(tables["traj_start"].shape[0])
-    dev = tables["cost_returns"].device
     prob = torch.zeros(n_traj, dtype=torch.float32, device=dev)
     cdf = torch.zeros(n_traj, dtype=torch.float32, device=dev)
     L.check(L.load().osrl_cost_sample_prob(tables["cost_returns"].data_ptr(), tables["traj_start"].data_ptr(), n_traj,
@@ -219,6 +242,35 @@ def pareto_frontier(cost, rew, deg: int = 3, device="cuda") -> Frontier:
     if c.shape != r.shape or c.numel() < 1:
         raise ValueError("cost and rew must be non-empty and of one length")
     return _fit_frontier(c, r, int(deg))
+
+
+def compute_sample_prob(tables: Dict[str, torch.Tensor], frontier: Frontier, beta: float = 1.0, with_cdf: bool = False,
+                        with_dist: bool = False):
+    """``compute_sample_prob`` (dataset.py:399-436, what ``SequenceDataset(pf_sample=True)`` samples trajectories
+    by) on device: ``prob_i ~ 1 / (dist_i + beta)``, ``dist_i`` the distance of trajectory i's (cost return, return) to
+    ``frontier`` (an ``ingest.Frontier``).  The reference gets the distance from one scipy BFGS solve per trajectory
+    started at the cost return; that solve does not find the nearest point of the curve but the stationary point
+    downhill from its start, and that is the definition here (csrc/pf_dist.h): the first root, with a sign change,
+    of ``(x - c) + (p(x) - r) p'(x)`` on the downhill side of ``c``, clamped at 0.  Where the reference's line
+    search jumps into another basin or stops early its result depends on the solver's path and differs.
+    Returns prob fp32 [n_traj]; ``with_cdf`` adds the inclusive cdf the window sampler reads, ``with_dist`` the fp64
+    distances (in that order)."""
+    if not float(beta) > 0.0:
+        raise ValueError(f"beta must be > 0, got {beta}")
+    n_traj = int(tables["traj_start"].shape[0])
+    if not 1 <= n_traj <= 1 << 20:
+        raise ValueError(f"1 .. 2^20 trajectories, got {n_traj}")
+    dev = tables["cost_returns"].device
+    prob = torch.zeros(n_traj, dtype=torch.float32, device=dev)
+    cdf = torch.zeros(n_traj, dtype=torch.float32, device=dev)
+    dist = torch.zeros(n_traj, dtype=torch.float64, device=dev)
+    ws = torch.empty(n_traj, dtype=torch.float64, device=dev)
+    L.check(L.load().osrl_pf_sample_prob(tables["returns"].data_ptr(), tables["cost_returns"].data_ptr(),
+                                         tables["traj_start"].data_ptr(), n_traj, frontier.coef_dev.data_ptr(),
+                                         frontier.deg_dev.data_ptr(), float(beta), prob.data_ptr(), cdf.data_ptr(),
+                                         dist.data_ptr(), ws.data_ptr(), cur_stream()), "osrl_pf_sample_prob")
+    out = (prob,) + ((cdf,) if with_cdf else ()) + ((dist,) if with_dist else ())
+    return out if len(out) > 1 else prob
 
 
 def _bc_frontier_select(ep: "Episodes", cost_returns: torch.Tensor, rew_returns: torch.Tensor, idx, cnt) -> None:

@@ -164,6 +164,39 @@ class SequenceStore:
         tables = dict(costs=self.cost, traj_start=self.traj_start, traj_len=self.traj_len)
         self.start_cdf = compute_start_index_sample_prob(tables, prob, with_cdf=True)[1]
 
+    def set_sample_prob(self, weights) -> None:
+        """Sample trajectories in proportion to ``weights``: any non-negative per-trajectory values (numpy or
+        tensor, host or device), normalised and turned into the cdf the sampler reads on device.  Replaces any
+        earlier trajectory distribution (``sample_prob``, ``cost_sample``, ``enable_pf_sampling``)."""
+        from .ingest import sample_prob_from_weights
+        w = weights if torch.is_tensor(weights) else torch.as_tensor(np.asarray(weights, np.float64))
+        w = w.reshape(-1)
+        if int(w.shape[0]) != self.n_traj:
+            raise ValueError(f"{self.n_traj} trajectory weights expected, got {int(w.shape[0])}")
+        w = w.to(device=self.device, dtype=torch.float64)
+        lo, total = float(w.min()), float(w.sum())  # host reads, once per distribution
+        if not (lo >= 0.0 and 0.0 < total < float("inf")):
+            raise ValueError("the weights must be non-negative and finite, with a positive sum")
+        self.cdf = sample_prob_from_weights(w, with_cdf=True)[1]
+
+    def enable_pf_sampling(self, beta: float = 1.0, frontier=None) -> None:
+        """``SequenceDataset(pf_sample=True)`` (dataset.py:736-737): trajectories are drawn with probability
+        ~ ``1 / (distance to the Pareto frontier + beta)`` (``common.ingest.compute_sample_prob``, csrc/pf_dist.h),
+        over the original and the augmented trajectories.  ``frontier``: an ``ingest.Frontier`` (e.g. from
+        ``ingest.pareto_frontier``) for a store built without augmentation; by default the one the augmentation
+        fitted (``aug_info["frontier"]``), else AttributeError as ``compute_pareto_return``.  Replaces any other
+        trajectory distribution.  Two things the reference's constructor does differently: there ``cost_sample``
+        wins when both flags are set (pf_sample is then ignored), and beta is hard-wired to 1 (:737) whatever
+        the ``beta`` argument -- which only feeds the augmentation's partner draws -- says."""
+        from .ingest import compute_sample_prob
+        if frontier is None:
+            info = getattr(self, "aug_info", None)
+            frontier = None if info is None else info["frontier"]
+        if frontier is None:
+            raise AttributeError("no Pareto frontier: the store was built without augment_percent (pass frontier=)")
+        tables = dict(returns=self.ret, cost_returns=self.cret, traj_start=self.traj_start)
+        self.cdf = compute_sample_prob(tables, frontier, beta, with_cdf=True)[1]
+
     def set_rank(self, rank: int) -> None:
         """Data parallel: every rank draws its own windows (same mixing as ReplayStore); the CDT engine calls this
         from ``attach_store`` when it runs under a DataParallel hook."""
@@ -208,11 +241,15 @@ class SequenceStore:
         (``common.ingest.augmentation``); cost / start sampling then act on the original + augmented trajectories.
         The random draws are keyed by ``seed`` (never the rank), so every data-parallel rank builds the same tables;
         ``draws`` injects them instead (tests).  ``rmin``, ``cost_bins``, ``npb`` only feed the reference's discarded
-        ``pf_only`` selection and are accepted for signature parity."""
+        ``pf_only`` selection and are accepted for signature parity.  ``cost_transform`` is one of the two tuple forms
+        of ``common.ingest.compute_cost_sample_prob`` (all on device) or a python callable as in the reference
+        (applied on the host to the per-trajectory cost returns).  ``pf_sample=True`` raises: the frontier-distance
+        distribution is installed afterwards with ``enable_pf_sampling()`` (in the reference ``cost_sample`` wins
+        over ``pf_sample``, and its beta is hard-wired to 1, dataset.py:734-737)."""
         from .ingest import augmentation, compute_cost_sample_prob, process_sequence_dataset, random_augmentation
         if pf_sample:
-            raise NotImplementedError("pf_sample=True (compute_sample_prob: a scipy BFGS solve per trajectory against "
-                                      "the Pareto frontier, dataset.py:399-436) is not supported; use cost_sample")
+            raise NotImplementedError("pf_sample=True is not built by from_dataset: build the store without it and "
+                                      "call enable_pf_sampling() (compute_sample_prob, dataset.py:399-436, on device)")
         tables = process_sequence_dataset(dataset, cost_reverse, device)
         n_orig = int(tables["traj_start"].shape[0])
         info = None

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "../../include/osrl_amd.h"
+#include "pf_dist.h"
 #include "philox.h"
 
 namespace {
@@ -758,6 +759,71 @@ __global__ void bc_frontier_mask_kernel(const float* __restrict__ cr, const floa
   }
 }
 
+// compute_sample_prob (dataset.py:399-436): w_i = 1 / (distance of trajectory i's (cost return, return) to the
+// frontier + beta), the distance as pf_dist.h defines it (the stationary point downhill from the cost return, not the
+// nearest point).  One thread per trajectory, fp64; the per-thread tables of the root isolation live in an LDS slice
+// [slot][thread] (consecutive threads hit consecutive banks), so nothing is indexed dynamically in registers.
+constexpr int kPfThreads = 64;
+
+__global__ __launch_bounds__(kPfThreads) void pf_dist_kernel(const float* __restrict__ ret,
+                                                             const float* __restrict__ cret,
+                                                             const int64_t* __restrict__ start, int n,
+                                                             const double* __restrict__ coef,
+                                                             const int32_t* __restrict__ deg, double beta,
+                                                             double* __restrict__ w, double* __restrict__ dist) {
+  __shared__ double tab[osrl_pf::kSlots][kPfThreads];
+  __shared__ double cf[kMaxCoef];
+  __shared__ int lead;
+  if (threadIdx.x == 0) {  // leading zeros stripped, as np.poly1d does
+    const int d = min(max(*deg, 0), kMaxCoef - 1);
+    int z = 0;
+    while (z < d && coef[z] == 0.0) ++z;
+    lead = z;
+    for (int k = 0; k < kMaxCoef; ++k) cf[k] = k + z <= d ? coef[k + z] : 0.0;
+  }
+  __syncthreads();
+  const int d = min(max(*deg, 0), kMaxCoef - 1) - lead;
+  const int i = blockIdx.x * kPfThreads + threadIdx.x;
+  if (i >= n) return;
+  const int64_t s = start[i];
+  const double c = (double)cret[s], r = (double)ret[s];
+  const double dd = osrl_pf::pf_distance(cf, d, c, r, &tab[0][threadIdx.x], kPfThreads);
+  w[i] = 1.0 / (dd + beta);
+  if (dist) dist[i] = dd;
+}
+
+// prob = max(w, 0) / sum, cdf = inclusive running sum / sum, from fp64 weights: one workgroup, every thread a
+// contiguous chunk, the chunk totals scanned in LDS -- a fixed order of additions, so the result is the same bits on
+// every run.  (The layout of ingest.hip's cost_sample_prob_kernel, on weights computed elsewhere.)
+__global__ __launch_bounds__(kWg) void weights_prob_kernel(const double* __restrict__ w, int n,
+                                                           float* __restrict__ prob, float* __restrict__ cdf) {
+  __shared__ double part[kWg];
+  const int chunk = (n + kWg - 1) / kWg;
+  const int e0 = min(n, (int)threadIdx.x * chunk), e1 = min(n, e0 + chunk);
+  auto weight = [&](int e) {
+    const double v = w[e];
+    return v > 0.0 ? v : 0.0;
+  };
+  double mine = 0.0;
+  for (int e = e0; e < e1; ++e) mine += weight(e);
+  part[threadIdx.x] = mine;
+  __syncthreads();
+  for (int o = 1; o < kWg; o <<= 1) {  // inclusive Hillis-Steele scan
+    const double t = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0.0;
+    __syncthreads();
+    part[threadIdx.x] += t;
+    __syncthreads();
+  }
+  const double total = part[kWg - 1];
+  double run = part[threadIdx.x] - mine;
+  for (int e = e0; e < e1; ++e) {
+    const double v = weight(e);
+    run += v;
+    prob[e] = (float)(v / total);
+    if (cdf) cdf[e] = (float)(run / total);
+  }
+}
+
 inline int grid_for(int64_t n, int threads) {
   const int64_t g = (n + threads - 1) / threads;
   return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g));
@@ -881,6 +947,27 @@ extern "C" int osrl_augment_gather(const float* obs, const float* act, const flo
                      traj_start, src, S, new_start, new_len, n_traj, tc, tr, noise, cstd, rstd, noise_c, noise_r, seed,
                      o_obs, o_act, o_rew, o_cost, o_ret, o_cret);
   return (int)hipGetLastError();
+}
+
+extern "C" int osrl_weights_sample_prob(const double* weights, int32_t n, float* prob, float* cdf, void* stream) {
+  if (!weights || !prob || n < 1 || n > (1 << 20)) return -1;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(weights_prob_kernel, dim3(1), dim3(kWg), 0, S_, weights, n, prob, cdf);
+  return (int)hipGetLastError();
+}
+
+extern "C" int osrl_pf_sample_prob(const float* returns, const float* cost_returns, const int64_t* traj_start,
+                                   int32_t n_traj, const double* coef, const int32_t* deg, double beta, float* prob,
+                                   float* cdf, double* dist, double* ws, void* stream) {
+  if (!returns || !cost_returns || !traj_start || n_traj < 1 || n_traj > (1 << 20) || !coef || !deg || !(beta > 0.0) ||
+      !prob || !ws)
+    return -1;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(pf_dist_kernel, dim3((n_traj + kPfThreads - 1) / kPfThreads), dim3(kPfThreads), 0, S_, returns,
+                     cost_returns, traj_start, n_traj, coef, deg, beta, ws, dist);
+  const int rc = (int)hipGetLastError();
+  if (rc) return rc;
+  return osrl_weights_sample_prob(ws, n_traj, prob, cdf, stream);
 }
 
 extern "C" int osrl_bc_frontier_select(const float* cost_returns, const float* rew_returns, int64_t n,
