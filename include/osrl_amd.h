@@ -366,6 +366,28 @@ int64_t osrl_mlp_wide_lds_bytes(int32_t K, int32_t N);
  * packed size among the entries (grid sizing).  Must run after every change of the canonical weights. */
 int osrl_pack_weights(const float* src_flat, float* pf, float* pb, const osrl_pack_entry_t* d_entries,
                       int32_t n_entries, int32_t max_elems, void* stream);
+/* The opt-in "bf16x3" form of osrl_linear (linear_split.hip; new, no counterpart in the reference): the same
+ * Y[M,N] = A[M,K] * W^T (+ bias[N]) (+ resid[M,N]) with W[N,K] given as THREE bf16 planes (osrl_split_planes), each
+ * [N,K] row-major, plane_stride elements apart (>= N*K, a multiple of 8).  Every fp32 value is the exact sum of three
+ * bf16 pieces (truncation split); the six piece products that matter run on v_mfma_f32_32x32x16_bf16 and are summed in
+ * fp32 in a fixed order (a function of K alone: same bits on every launch), the three dropped ones are <= 2^-23 |a||w|
+ * per product -- fp32-class, NOT bit-equal to osrl_linear.  Any M (the row tail is masked).  Takes the shapes for which
+ * osrl_linear_split_supported returns 1 (K % 32 == 0, N % 128 == 0); A and Wp 16-byte aligned, lda % 4 == 0; anything else
+ * is -1 and the caller keeps osrl_linear.  The input gradient dX = dY W is the same call on the planes of W^T.
+ * Non-finite inputs: the split of +-Inf is (Inf, NaN, NaN), so every output fed by an Inf or NaN element of A or W is
+ * NaN (never a finite number; also where fp32 arithmetic would give +-Inf).  Values below 2^-110 in magnitude: their
+ * bits under 2^-133 (bf16's smallest subnormal) are not representable in any piece and are dropped. */
+int osrl_linear_split(const float* A, int64_t lda, int32_t M, int32_t K, const uint16_t* Wp, int64_t plane_stride,
+                      int32_t N, const float* bias, const float* resid, int64_t ldr, float* Y, int64_t ldy, void* stream);
+int osrl_linear_split_supported(int32_t M, int32_t K, int32_t N);   /* 1 / 0; no launch */
+int64_t osrl_linear_split_lds_bytes(void);                            /* dynamic LDS per workgroup of that kernel */
+/* Refresh the bf16 planes of `n_entries` canonical weights in ONE launch (entries in DEVICE memory, as for
+ * osrl_pack_weights; offsets in bf16 ELEMENTS): f_off = where the three planes of W[out,in] go in planes_w, b_off = where
+ * the three planes of W^T[in,out] go in planes_t (what dX reads); the planes of one matrix are out*in elements apart;
+ * a negative offset or a NULL buffer skips that orientation.  max_elems = the largest out*in (grid sizing).
+ * hipGraph-capturable.  Must run after every change of the canonical weights. */
+int osrl_split_planes(const float* src_flat, uint16_t* planes_w, uint16_t* planes_t, const osrl_pack_entry_t* d_entries,
+                      int32_t n_entries, int32_t max_elems, void* stream);
 /* entries/items live in DEVICE memory (static plan): items[i] = {entry, o_tile, i_tile, 0} with
  * 64x64 tiles; slabs = [n_splits][slab_stride] partial gradients (deterministic split-K over rows). */
 int osrl_mlp_backward_dw(const osrl_dw_entry_t* d_entries, const int32_t* d_items, int32_t n_items,

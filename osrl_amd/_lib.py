@@ -249,6 +249,10 @@ PROTOTYPES = {
     "osrl_mlp_backward_dz_seed": [_P(MlpT), _i32, _P(ActsT), _P(GradsT), _P(TailT), _P(SeedT), _vp],
     "osrl_linear": [_fp, _i64, _i32, _i32, _fp, _i32, _i32, _i32, _fp, _fp, _i64, _fp, _i64, _vp],
     "osrl_pack_weights": [_fp, _fp, _fp, _vp, _i32, _i32, _vp],
+    "osrl_linear_split": [_fp, _i64, _i32, _i32, _vp, _i64, _i32, _fp, _fp, _i64, _fp, _i64, _vp],
+    "osrl_linear_split_supported": [_i32, _i32, _i32],
+    "osrl_linear_split_lds_bytes": [],
+    "osrl_split_planes": [_fp, _vp, _vp, _vp, _i32, _i32, _vp],
     "osrl_mlp_backward_dw": [_vp, _vp, _i32, _i32, _i32, _fp, _i64, _vp],
     "osrl_mlp_backward_dw_tiles": [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp],
     "osrl_mlp_backward_dw_big": [_vp, _vp, _i32, _i32, _i32, _fp, _i64, _vp],
@@ -352,7 +356,7 @@ RESTYPES = {"osrl_ingest_ws_elems": C.c_int64, "osrl_grid_filter_ws_elems": C.c_
             "osrl_polyfit_ws_elems": C.c_int64, "osrl_augment_targets_ws_elems": C.c_int64, "osrl_attention_keep_bytes": C.c_int64,
             "osrl_attention_ws_bytes": C.c_int64, "osrl_attention_tiled_ws_bytes": C.c_int64,
             "osrl_attention_tiled_lds_bytes": C.c_int64, "osrl_linear_kchunk_lds_bytes": C.c_int64,
-            "osrl_mlp_wide_lds_bytes": C.c_int64}  # everything else returns int (0 = ok)
+            "osrl_mlp_wide_lds_bytes": C.c_int64, "osrl_linear_split_lds_bytes": C.c_int64}  # everything else returns int (0 = ok)
 
 
 def lib_path() -> str:

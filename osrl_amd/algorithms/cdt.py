@@ -282,7 +282,14 @@ class CDTTrainer:
                  lr_warmup_steps: int = 10000, reward_scale: float = 1.0, cost_scale: float = 1.0,
                  loss_cost_weight: float = 0.0, loss_state_weight: float = 0.0, cost_reverse: bool = False,
                  no_entropy: bool = False, device="cuda", stats_mode: str = "lazy", use_graph: bool = True,
-                 seed: int = 0, fast_rollout: bool = True) -> None:
+                 seed: int = 0, fast_rollout: bool = True, matmul: str = "f32") -> None:
+        """``matmul``: "f32" (default) runs the projection GEMMs of the train step and their input gradients on the
+        f32-MFMA kernels; "bf16x3" runs them as exact bf16 triples on the bf16 matrix cores (osrl_linear_split) wherever
+        that kernel takes the layer's shape -- same model, checkpoints and parity bound, fp32-class but not bit-equal to
+        "f32".  Weight gradients, attention, LayerNorm, GELU, the loss and AdamW are the same in both; the inference
+        forward, ``differentiable=True`` and the act path (``fast_policy``) always run "f32"."""
+        from ..engine.plan import check_matmul
+        check_matmul(matmul)  # (before any device work)
         self.model, self.logger, self.env = model, logger, env
         self.clip_grad, self.reward_scale, self.cost_scale, self.device = clip_grad, reward_scale, cost_scale, device
         self.cost_weight, self.state_weight = loss_cost_weight, loss_state_weight
@@ -293,7 +300,7 @@ class CDTTrainer:
         self.fast_rollout = bool(fast_rollout)  # rollout() on host envs through CDT.fast_policy() when eligible
         self.cfg = dict(learning_rate=learning_rate, weight_decay=weight_decay, betas=tuple(betas),
                         clip_grad=clip_grad, lr_warmup_steps=lr_warmup_steps, loss_cost_weight=loss_cost_weight,
-                        loss_state_weight=loss_state_weight, no_entropy=no_entropy, seed=int(seed))
+                        loss_state_weight=loss_state_weight, no_entropy=no_entropy, seed=int(seed), matmul=matmul)
 
     def train_one_step(self, states, actions, returns, costs_return, time_steps, mask, episode_cost, costs):
         """cdt.py:343-418 (``episode_cost`` only feeds the cost-prefix variant)."""

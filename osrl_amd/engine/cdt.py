@@ -5,7 +5,9 @@ Follows ``CDTTrainer.train_one_step`` (osrl/algorithms/cdt.py:343-418) around ``
 num_layers x [LN, QKV, causal+padding attention, out-proj, residual, LN, Linear-GELU-Linear, residual]
 -> out LayerNorm -> heads -> losses -> backward of all of it -> clip_grad_norm_ -> AdamW (warm-up LR)
 -> temperature Adam.  Projections and their dX / dW GEMMs run on the packed-weight fp32-MFMA kernels
-(csrc/mlp.hip: osrl_linear, osrl_mlp_backward_dw); everything else is csrc/cdt.hip.
+(csrc/mlp.hip: osrl_linear, osrl_mlp_backward_dw); everything else is csrc/cdt.hip.  Opt-in (trainer_cfg["matmul"] =
+"bf16x3", engine/plan.py CDTPlan): projections and dX as exact bf16 triples on the bf16 matrix cores
+(csrc/linear_split.hip: osrl_linear_split) for the layers that kernel takes; dW and everything else unchanged.
 Dropout (embedding cdt.py:222, attention probabilities net.py:406-409, residual net.py:414,439; train-config
 default 0.1, examples/configs/cdt_configs.py:28-30) uses stateless Philox masks keyed by (seed, step, site, element):
 the backward kernels regenerate them, nothing is stored; with p = 0 no extra kernel is launched.
@@ -44,6 +46,10 @@ class CDTEngine:
         never steps the optimizer.  ``dropout=False``: every dropout probability is 0 (an eval-mode forward)."""
         m = self.model = model
         self.cfg = trainer_cfg
+        # the matmul plan (engine/plan.py): only a train engine opts in; the inference forward and the differentiable
+        # forward stay on the f32 kernels whatever the trainer of the same model runs
+        req = _plan.check_matmul(trainer_cfg.get("matmul", "f32"))
+        self.matmul = "f32" if (inference or grad) else _plan.cdt_matmul(req)
         self.dist = dist
         B, T, E, H, NL = int(batch_size), m.seq_len, m.embedding_dim, m.num_heads, m.num_layers
         self.B, self.T, self.E, self.H, self.NL = B, T, E, H, NL
@@ -225,7 +231,49 @@ class CDTEngine:
         self._slab_probe = None
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.store = None
+        self._plan_matmul()
         m.repack()
+
+    def _gemms(self):
+        """Every projection / input-gradient GEMM of a step as (parameter key, dx?, rows, residual?)."""
+        M, BT = self.M, self.BT
+        out = []
+        for l in range(self.NL):
+            p = f"cdt.blocks.{l}."
+            for k in ("attention.in_proj_weight", "attention.out_proj.weight", "mlp.0.weight", "mlp.2.weight"):
+                out += [(p + k, False, M, False), (p + k, True, M, False)]
+        for k in self.head_hidden + [self.head_out]:
+            out += [(k, False, BT, False), (k, True, BT, False)]
+        out += [("cdt.cost_pred_head.weight", False, BT, False), ("cdt.cost_pred_head.weight", True, BT, False),
+                ("cdt.state_pred_head.weight", False, BT, False), ("cdt.state_pred_head.weight", True, BT, True)]
+        return out
+
+    def _plan_matmul(self) -> None:
+        """Which GEMMs of the step run osrl_linear_split (matmul="bf16x3": wherever the kernel takes the shape and the
+        chooser keeps it), the bf16 planes they read, and the plan this engine reports."""
+        lib, g = L.load(), self.g
+        self._split_f, self._split_b = set(), set()
+        n = [0, 0, 0, 0]  # split fwd, split dx, f32 fwd, f32 dx
+        for key, bwd, rows, resid in self._gemms():
+            N, K = g.layout[key][1]
+            if bwd:
+                K, N = N, K
+            use = self.matmul == "bf16x3" and _plan.cdt_split_use(
+                int(lib.osrl_linear_split_supported(rows, K, N)) == 1, rows, K, N, resid)
+            if use:
+                (self._split_b if bwd else self._split_f).add(key)
+            n[(0 if use else 2) + (1 if bwd else 0)] += 1
+        if self.matmul == "bf16x3":
+            g.enable_planes(self._split_f, self._split_b)
+        self.plan = _plan.CDTPlan(matmul=self.matmul, split_fwd=n[0], split_dx=n[1], f32_fwd=n[2], f32_dx=n[3])
+
+    def linear_kernel(self, key: str, dx: bool = False) -> str:
+        """The entry point the projection (``dx``: the input gradient) of parameter ``key`` runs under this plan."""
+        return "osrl_linear_split" if key in (self._split_b if dx else self._split_f) else "osrl_linear"
+
+    def _PL(self, key: str, bwd: bool) -> int:
+        g = self.g
+        return (g.planes_t if bwd else g.planes_w).data_ptr() + 2 * (g.pt_off if bwd else g.pw_off)[key]
 
     # ---- thin launch helpers -------------------------------------------------------------------
     def _P(self, key: str, bwd: bool) -> int:
@@ -242,6 +290,11 @@ class CDTEngine:
         y = Y if isinstance(Y, int) else Y.data_ptr()
         r = None if resid is None else (resid if isinstance(resid, int) else resid.data_ptr())
         bkey = key[:-len("weight")] + "bias" if key.endswith("weight") else key.replace("in_proj_weight", "in_proj_bias")
+        if key in self._split_f:
+            L.check(L.load().osrl_linear_split(a, lda, Mrows, K, self._PL(key, False), N * K, N,
+                                               self._v(bkey) if bias else None, r, ldr, y, ldy, cur_stream()),
+                    "osrl_linear_split")
+            return
         L.check(L.load().osrl_linear(a, lda, Mrows, K, self._P(key, False), _r16(N), 0, N,
                                      self._v(bkey) if bias else None, r, ldr, y, ldy, cur_stream()), "osrl_linear")
 
@@ -251,6 +304,10 @@ class CDTEngine:
         a = dY if isinstance(dY, int) else dY.data_ptr()
         y = Y if isinstance(Y, int) else Y.data_ptr()
         r = None if resid is None else (resid if isinstance(resid, int) else resid.data_ptr())
+        if key in self._split_b:  # the planes of W^T [K,N]: dX [M,K] = dY [M,N] (W^T)^T
+            L.check(L.load().osrl_linear_split(a, ldd, Mrows, N, self._PL(key, True), N * K, K, None, r, ldr, y, ldy,
+                                               cur_stream()), "osrl_linear_split(dx)")
+            return
         L.check(L.load().osrl_linear(a, ldd, Mrows, N, self._P(key, True), _r16(K) + 16, 0, K, None, r, ldr, y, ldy,
                                      cur_stream()), "osrl_linear(dx)")
 

@@ -75,6 +75,9 @@ class FlatGroup:
         self.f_off: Dict[str, int] = {}
         self.b_off: Dict[str, int] = {}
         self.aliases: set = set()
+        self.planes_w = self.planes_t = None  # bf16 planes of W [out,in] / W^T [in,out] (enable_planes), 3 per key
+        self.pw_off: Dict[str, int] = {}      # key -> element offset of its first plane
+        self.pt_off: Dict[str, int] = {}
         self._retired_slabs: list = []        # see ensure_slabs
         # bumped whenever another plan is attached to slabs that an earlier engine's plans (and captured graphs) use: that
         # engine's "rows beyond my split count stay zero" no longer holds once the newcomer writes there, so engines
@@ -147,6 +150,51 @@ class FlatGroup:
         if target and self.tgt is not None:
             L.check(lib.osrl_pack_weights(self.tgt.data_ptr(), self.tf.data_ptr(), None, self._ents.data_ptr(),
                                           len(self.weights), self._max_pack, cur_stream()), "osrl_pack_weights")
+        if params:
+            self.refresh_planes()
+
+    # ---- bf16 planes of the weights (the "bf16x3" projections, csrc/linear_split.hip): derived state like pf / pb,
+    # allocated only when an engine asks for them and then refreshed wherever the packed copies are ----
+    def enable_planes(self, fwd_keys: Sequence[str], bwd_keys: Sequence[str]) -> None:
+        """Allocate (grow-only: the union with what earlier engines asked for) the bf16 planes of W for ``fwd_keys`` and
+        of W^T for ``bwd_keys`` and fill them from the current parameters.  From here on ``repack()`` and ``adam_step()``
+        refresh them with one osrl_split_planes launch behind the packed copies' refresh."""
+        fk = sorted(set(fwd_keys) | set(self.pw_off))
+        bk = sorted(set(bwd_keys) | set(self.pt_off))
+        if not fk and not bk:
+            return
+        if fk == sorted(self.pw_off) and bk == sorted(self.pt_off) and self.planes_w is not None:
+            return
+        if self.planes_w is not None:  # a captured graph of an earlier engine holds the raw addresses (cf. ensure_slabs)
+            self.__dict__.setdefault("_retired_planes", []).append((self.planes_w, self.planes_t, self._plane_ents))
+        keys = sorted(set(fk) | set(bk))
+        a8 = lambda x: (x + 7) // 8 * 8  # noqa: E731  (the kernel reads 16-byte chunks)
+        ents = (L.PackEntryT * len(keys))()
+        pw_off, pt_off, nw, nt, mx = {}, {}, 0, 0, 1
+        for i, k in enumerate(keys):
+            off, (o, ii) = self.layout[k]
+            ents[i].src_off, ents[i].out, ents[i].in_, ents[i].f_off, ents[i].b_off = off, o, ii, -1, -1
+            if k in fk:
+                ents[i].f_off = pw_off[k] = nw
+                nw += a8(3 * o * ii)
+            if k in bk:
+                ents[i].b_off = pt_off[k] = nt
+                nt += a8(3 * o * ii)
+            mx = max(mx, o * ii)
+        zu = lambda n: torch.zeros(max(n, 8), dtype=torch.int16, device=self.device)  # noqa: E731
+        self.planes_w, self.planes_t = zu(nw), zu(nt)
+        self.pw_off, self.pt_off, self._plane_max = pw_off, pt_off, mx
+        self._plane_ents = torch.frombuffer(bytearray(bytes(ents)), dtype=torch.uint8).to(self.device)
+        self._plane_n = len(keys)
+        self.refresh_planes()
+
+    def refresh_planes(self) -> None:
+        if self.planes_w is None:
+            return
+        L.check(L.load().osrl_split_planes(self.p.data_ptr(), self.planes_w.data_ptr() if self.pw_off else None,
+                                           self.planes_t.data_ptr() if self.pt_off else None,
+                                           self._plane_ents.data_ptr(), self._plane_n, self._plane_max, cur_stream()),
+                "osrl_split_planes")
 
     def ensure_slabs(self, n_splits: int) -> None:
         """Grow-only.  A hipGraph captured by an earlier engine on this group holds the RAW address of the slab
@@ -241,6 +289,7 @@ class FlatGroup:
                                               self._map_f.data_ptr(), self._map_b.data_ptr(), self.pf.data_ptr(),
                                               self.pb.data_ptr(), _ptr(self.tf) if tgt is not None else None,
                                               cur_stream()), "osrl_adam_step_packed")
+            self.refresh_planes()  # (no planes: no launch)
         else:
             L.check(lib.osrl_adam_step(self.p.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), tgt,
                                        self.slabs.data_ptr(), self.cur_splits, self.n, self.n, lr, betas[0],

@@ -229,6 +229,41 @@ def bcql_plan(od: int, ad: int, B: int, vae_hidden: int, N: int, seeds: bool = T
                     vae_ns=bool(vae_ns), dw_splits=dws, steps_per_graph=spg)
 
 
+MATMUL_MODES = ("f32", "bf16x3")
+
+
+@dataclass(frozen=True)
+class CDTPlan:
+    """What the CDT step plan decides (engine/cdt.py reads these).  ``matmul``: "f32" = every projection and input
+    gradient on the f32-MFMA kernels (osrl_linear; the default, bit-stable across releases) / "bf16x3" = on the split
+    bf16 kernel (osrl_linear_split) wherever it takes the shape, osrl_linear elsewhere -- fp32-class, not bit-equal."""
+    matmul: str
+    split_fwd: int = 0        # projections of a step that run osrl_linear_split (launches, heads included)
+    split_dx: int = 0         # input-gradient GEMMs of a step that do
+    f32_fwd: int = 0          # ... and those that stay on osrl_linear under this plan
+    f32_dx: int = 0
+
+
+def check_matmul(mode) -> str:
+    if mode not in MATMUL_MODES:
+        raise ValueError(f"matmul={mode!r}: one of {MATMUL_MODES}")
+    return mode
+
+
+def cdt_matmul(requested: str = "f32") -> str:
+    """The matmul mode of a CDT train engine: what the trainer asked for, unless a lab run forces one (bench.py builds
+    its trainer without the keyword: OSRL_LAB=1 OSRL_CDT_MATMUL=bf16x3 python bench.py --config c5)."""
+    forced = knob("OSRL_CDT_MATMUL", "auto", "CDT train step projections: f32 / bf16x3 (exact bf16 triples on the bf16 "
+                  "matrix cores) / auto = what CDTTrainer(matmul=) asked for")
+    return check_matmul(requested if forced == "auto" else forced)
+
+
+def cdt_split_use(supported: bool, rows: int, K: int, N: int, resid: bool) -> bool:
+    """Under matmul="bf16x3": does this GEMM (rows x K -> N) take the split kernel?  Every shape the kernel supports;
+    the A/B of tools/cdt_split_gemm_ab.py (profiles/cdt_split_gemm_ab.json) is where a losing shape would be sent back."""
+    return bool(supported)
+
+
 # BASELINE.json configs -> the plan the chooser must give (tests/test_host_cpu.py::test_plan_rows_are_pinned); a changed
 # rule that moves one of these rows is a deliberate act with a measurement behind it (DESIGN_LOG)
 PINNED = {
