@@ -1,0 +1,149 @@
+"""What the six model classes and the five MLP trainers share.  The constructors stay in the algorithm files: their
+argument lists and creation order mirror the reference line by line."""
+from __future__ import annotations
+
+from importlib import import_module
+from typing import Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+
+class FlatModel(nn.Module):
+    """A model whose parameters are views into flat HBM optimizer groups (``self.groups``)."""
+
+    ENGINE = ""  # "<module under osrl_amd.engine>.<class>" of the training engine
+
+    def repack(self) -> None:
+        """Refresh the fragment-ordered weight copies the kernels read; call after modifying parameters
+        in place from outside the trainer (load_state_dict does it automatically)."""
+        for g in self.groups.values():
+            if g.device.type == "cuda":
+                g.repack()
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        if assign:
+            raise RuntimeError("assign=True would detach parameters from their flat HBM groups")
+        res = super().load_state_dict(state_dict, strict=strict)
+        self.repack()
+        return res
+
+    def _apply(self, fn, *a, **k):  # parameters are views into flat HBM buffers: moving them breaks the engine
+        raise RuntimeError("osrl_amd models are bound to their HIP device at construction; .to()/.cuda()/.cpu() "
+                           "are unsupported (pass device= to the constructor)")
+
+    def _engine_class(self):
+        mod, cls = self.ENGINE.split(".")
+        return getattr(import_module("..engine." + mod, __package__), cls)
+
+    def engine(self, batch_size: int, **kw):
+        from ..common.checkpoint import engine_handoff
+        if self._engine is None or self._engine.B != batch_size or kw:
+            if self._lrs is None:
+                raise RuntimeError(f"call setup_optimizers() (or build a {type(self).__name__}Trainer) before training")
+            old, self._engine = self._engine, self._engine_class()(self, batch_size, **kw)
+            engine_handoff(self, self._engine, old)
+        return self._engine
+
+    def _policy_spec(self):
+        """``(kind, obs_dim, net0, kwargs)`` of the model's ``FastPolicy`` / ``VecFastPolicy``."""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def fast_policy(self, num_envs: Optional[int] = None):
+        """The B = 1 latency path (engine/act.py): one kernel launch per ``act()``, pinned-memory I/O.
+        With ``num_envs`` an integer: the lockstep form for that many host environments (``VecFastPolicy``), built once
+        per model and ``num_envs``."""
+        if num_envs is not None:
+            from ..engine.act import VecFastPolicy, cached_vec_policy
+
+            def make(n):
+                kind, obs_dim, net0, kw = self._policy_spec()
+                return VecFastPolicy(kind, self.device, obs_dim, self.action_dim, net0, num_envs=n, **kw)
+            return cached_vec_policy(self, num_envs, make)
+        if getattr(self, "_fast", None) is None:
+            from ..engine.act import FastPolicy
+            kind, obs_dim, net0, kw = self._policy_spec()
+            self._fast = FastPolicy(kind, self.device, obs_dim, self.action_dim, net0, **kw)
+        return self._fast
+
+
+class RolloutMixin:
+    """``evaluate`` / ``rollout_many`` / ``rollout`` of the MLP trainers (``self.model``, ``self.env``,
+    ``self.reward_scale``, ``self.cost_scale``).  Where a trainer differs from the rest it overrides one of the hooks."""
+
+    EVAL_KIND = ""  # the policy kind of engine/rollout.py ``evaluate_batched``
+
+    def _before_evaluate(self) -> None:
+        pass
+
+    def _eval_extra(self) -> Optional[float]:
+        """A value appended to every observation the policy sees (None: nothing)."""
+        return None
+
+    def _act_for_rollout(self, obs):
+        return self.model.act(obs, True, True)[0]
+
+    def _cost_scale(self) -> Optional[float]:
+        """Factor on ``info["cost"]`` in the episode sums (None: summed as it is)."""
+        return self.cost_scale
+
+    def _scale_results(self, r, c, n):
+        return r / self.reward_scale, c / self.cost_scale, n
+
+    def evaluate(self, eval_episodes):
+        """The reference's ``evaluate``: (mean return, mean cost, mean length).  With a ``VecSyntheticSafeEnv`` as
+        ``self.env`` the episodes run as one batch on device (engine/rollout.py); a list or tuple of N host (gym-style)
+        environments runs episode ``q`` on environment ``q % N``, N at a time in lockstep (``rollout_many``); any other
+        (gym-style) env takes the reference's episode-by-episode loop."""
+        from ..common.synthetic_env import VecSyntheticSafeEnv
+        self._before_evaluate()
+        if isinstance(self.env, VecSyntheticSafeEnv):
+            from ..engine.rollout import evaluate_batched
+            cs = self._cost_scale()
+            return self._scale_results(*evaluate_batched(self, self.EVAL_KIND, eval_episodes,
+                                                         1.0 if cs is None else cs, self._eval_extra()))
+        if isinstance(self.env, (list, tuple)):
+            from ..engine.act import evaluate_lockstep
+            return self._scale_results(*evaluate_lockstep(self, eval_episodes))
+        self.model.eval()
+        rets, costs, lens = [], [], []
+        for _ in range(eval_episodes):
+            r, l, c = self.rollout()
+            rets.append(r)
+            lens.append(l)
+            costs.append(c)
+        self.model.train()
+        return self._scale_results(np.mean(rets), np.mean(costs), np.mean(lens))
+
+    @torch.no_grad()
+    def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):
+        """``rollout`` on each of the host environments ``envs`` at once, in lockstep through
+        ``model.fast_policy(num_envs)`` (engine/act.py ``rollout_lockstep``): three arrays (return, length, cost sum), one
+        entry per environment.  ``num_slots`` (default ``len(envs)``): the width of the policy to use, the slots past
+        ``len(envs)`` idle.  The policy acts deterministically; noise it still draws on the device (BCQ-L's decode
+        noise z) is keyed by the episode id (``episode_ids``, default 0 .. len(envs) - 1) and the step.  BC in
+        ``multi-task`` mode appends the cost limit to every observation (``_eval_extra``)."""
+        from ..engine.act import rollout_lockstep
+        return rollout_lockstep(self.model, envs, num_slots, episode_ids, cost_scale=self._cost_scale(),
+                                append=self._eval_extra())
+
+    @torch.no_grad()
+    def rollout(self):
+        """The reference's episode loop on ``self.env``: (return, length, cost sum)."""
+        cs, extra = self._cost_scale(), self._eval_extra()
+        put = (lambda o: o) if extra is None else (lambda o: np.append(o, extra))  # noqa: E731
+        obs, info = self.env.reset()
+        obs = put(obs)
+        ep_ret, ep_cost, ep_len = 0.0, 0.0, 0
+        for _ in range(self.model.episode_len):
+            act = self._act_for_rollout(obs)
+            obs_next, reward, terminated, truncated, info = self.env.step(act)
+            obs = put(obs_next)
+            ep_ret += reward
+            ep_len += 1
+            ep_cost += info["cost"] if cs is None else info["cost"] * cs
+            if terminated or truncated:
+                break
+        return ep_ret, ep_len, ep_cost

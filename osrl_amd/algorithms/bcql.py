@@ -12,6 +12,7 @@ from ..common.logger import store_stats
 from ..common.net import (VAE, EnsembleDoubleQCritic, MLPGaussianPerturbationActor, bind_group, check_mlp_limits,
                           plan_group)
 from ..engine.core import FlatGroup, require_cuda
+from ._base import FlatModel, RolloutMixin
 
 
 class LagrangianPIDController:
@@ -32,8 +33,10 @@ class LagrangianPIDController:
         return float(self.state[1].item())
 
 
-class BCQL(nn.Module):
+class BCQL(FlatModel):
     """bcql.py:15-112."""
+
+    ENGINE = "bcql.BCQLEngine"
 
     def __init__(self, state_dim: int, action_dim: int, max_action: float, a_hidden_sizes: list = [128, 128],
                  c_hidden_sizes: list = [128, 128], vae_hidden_sizes: int = 64, sample_action_num: int = 10,
@@ -83,56 +86,19 @@ class BCQL(nn.Module):
         self._engine = None
         self._lrs: Optional[dict] = None
 
-    def repack(self) -> None:
-        """Refresh the fragment-ordered weight copies the kernels read; call after modifying parameters
-        in place from outside the trainer (load_state_dict does it automatically)."""
-        for g in self.groups.values():
-            if g.device.type == "cuda":
-                g.repack()
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        if assign:
-            raise RuntimeError("assign=True would detach parameters from their flat HBM groups")
-        res = super().load_state_dict(state_dict, strict=strict)
-        self.repack()
-        return res
-
-    def _apply(self, fn, *a, **k):
-        raise RuntimeError("osrl_amd models are bound to their HIP device at construction (pass device=)")
-
     def setup_optimizers(self, actor_lr, critic_lr, vae_lr):
         """bcql.py:218-226."""
         self._lrs = dict(actor=actor_lr, critic=critic_lr, cost_critic=critic_lr, vae=vae_lr)
-
-    def engine(self, batch_size: int, **kw):
-        from ..common.checkpoint import engine_handoff
-        from ..engine.bcql import BCQLEngine
-        if self._engine is None or self._engine.B != batch_size or kw:
-            if self._lrs is None:
-                raise RuntimeError("call setup_optimizers() (or build a BCQLTrainer) before training")
-            old, self._engine = self._engine, BCQLEngine(self, batch_size, **kw)
-            engine_handoff(self, self._engine, old)
-        return self._engine
 
     def sync_weight(self):
         """bcql.py:228-234 -- fused into the per-group optimizer kernels of train_one_step."""
         return None
 
-    def fast_policy(self, num_envs: Optional[int] = None):
-        """The B = 1 latency path (engine/act.py): one kernel launch per ``act()``, pinned-memory I/O.
-        With ``num_envs`` an integer: the lockstep form for that many host environments (``VecFastPolicy``), built once
-        per model and ``num_envs``."""
+    def _policy_spec(self):
         from ..common.net import net_desc_seq, vae_dec_desc
-        kw = dict(max_action=float(self.actor.act_limit), net1=net_desc_seq([self.actor.pi], 1.0),
-                  latent_dim=self.latent_dim, phi=float(self.actor.phi))
-        if num_envs is not None:
-            from ..engine.act import VecFastPolicy, cached_vec_policy
-            return cached_vec_policy(self, num_envs, lambda n: VecFastPolicy(
-                "bcq", self.device, self.state_dim, self.action_dim, vae_dec_desc(self.vae), num_envs=n, **kw))
-        if getattr(self, "_fast", None) is None:
-            from ..engine.act import FastPolicy
-            self._fast = FastPolicy("bcq", self.device, self.state_dim, self.action_dim, vae_dec_desc(self.vae), **kw)
-        return self._fast
+        return "bcq", self.state_dim, vae_dec_desc(self.vae), dict(
+            max_action=float(self.actor.act_limit), net1=net_desc_seq([self.actor.pi], 1.0), latent_dim=self.latent_dim,
+            phi=float(self.actor.phi))
 
     @torch.no_grad()
     def act(self, obs, deterministic=False, with_logprob=False, z=None):
@@ -141,7 +107,7 @@ class BCQL(nn.Module):
         return self.fast_policy().act(obs, deterministic, noise=zz)[0], None
 
 
-class BCQLTrainer:
+class BCQLTrainer(RolloutMixin):
     """bcql.py:246-340."""
 
     def __init__(self, model: BCQL, env=None, logger=None, actor_lr: float = 1e-4,
@@ -158,48 +124,9 @@ class BCQLTrainer:
                  use_graph=self.use_graph and noise is None)
         store_stats(self.logger, eng.st, self.stats_mode)
 
-    def evaluate(self, eval_episodes):
-        """bcql.py:308-321.  A ``VecSyntheticSafeEnv`` as ``self.env`` runs the episodes as one batch on device
-        (the decode noise z is then drawn per env step from the device Philox stream)."""
-        from ..common.synthetic_env import VecSyntheticSafeEnv
-        if isinstance(self.env, VecSyntheticSafeEnv):
-            from ..engine.rollout import evaluate_batched
-            r, c, n = evaluate_batched(self, "bcql", eval_episodes, self.cost_scale)
-            return r / self.reward_scale, c / self.cost_scale, n
-        if isinstance(self.env, (list, tuple)):  # N host environments: episode q on environment q % N, in lockstep
-            from ..engine.act import evaluate_lockstep
-            r, c, n = evaluate_lockstep(self, eval_episodes)
-            return r / self.reward_scale, c / self.cost_scale, n
-        self.model.eval()
-        rets, costs, lens = [], [], []
-        for _ in range(eval_episodes):
-            r, l, c = self.rollout()
-            rets.append(r); lens.append(l); costs.append(c)
-        self.model.train()
-        return np.mean(rets) / self.reward_scale, np.mean(costs) / self.cost_scale, np.mean(lens)
+    # bcql.py:308-340: rollout() acts through the stochastic decode (z drawn per step; in the batched and lockstep forms
+    # from the device Philox stream, keyed by the episode id and the step)
+    EVAL_KIND = "bcql"
 
-    @torch.no_grad()
-    def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):
-        """``rollout`` on each of the host environments ``envs`` at once, in lockstep through
-        ``model.fast_policy(num_envs)`` (engine/act.py ``rollout_lockstep``): three arrays (return, length, cost sum), one
-        entry per environment.  ``num_slots`` (default ``len(envs)``): the width of the policy to use, the slots past
-        ``len(envs)`` idle.  The decode noise z of every step is drawn on the device, keyed by the episode id
-        (``episode_ids``, default 0 .. len(envs) - 1) and the step."""
-        from ..engine.act import rollout_lockstep
-        return rollout_lockstep(self.model, envs, num_slots, episode_ids, cost_scale=self.cost_scale)
-
-    @torch.no_grad()
-    def rollout(self):
-        obs, info = self.env.reset()
-        ep_ret, ep_cost, ep_len = 0.0, 0.0, 0
-        for _ in range(self.model.episode_len):
-            act, _ = self.model.act(obs)
-            obs_next, reward, terminated, truncated, info = self.env.step(act)
-            cost = info["cost"] * self.cost_scale
-            obs = obs_next
-            ep_ret += reward
-            ep_len += 1
-            ep_cost += cost
-            if terminated or truncated:
-                break
-        return ep_ret, ep_len, ep_cost
+    def _act_for_rollout(self, obs):
+        return self.model.act(obs)[0]

@@ -11,12 +11,15 @@ import torch.nn as nn
 from ..common.logger import store_stats
 from ..common.net import VAE, EnsembleDoubleQCritic, SquashedGaussianMLPActor, bind_group, check_mlp_limits, plan_group
 from ..engine.core import FlatGroup, require_cuda
+from ._base import FlatModel, RolloutMixin
 from .bcql import LagrangianPIDController
 
 
-class BEARL(nn.Module):
+class BEARL(FlatModel):
     """bearl.py:15-126: squashed-Gaussian actor, twin Q / Qc ensembles, VAE behaviour model, MMD support constraint
     with a dual variable ``log_alpha`` and a PID Lagrangian on the cost critic."""
+
+    ENGINE = "bearl.BEARLEngine"
 
     def __init__(self, state_dim: int, action_dim: int, max_action: float, a_hidden_sizes: list = [128, 128],
                  c_hidden_sizes: list = [128, 128], vae_hidden_sizes: int = 64, sample_action_num: int = 10,
@@ -81,55 +84,18 @@ class BEARL(nn.Module):
         from ..common.checkpoint import train_step_count
         return train_step_count(self)
 
-    def repack(self) -> None:
-        for g in self.groups.values():
-            if g.device.type == "cuda":
-                g.repack()
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        if assign:
-            raise RuntimeError("assign=True would detach parameters from their flat HBM groups")
-        res = super().load_state_dict(state_dict, strict=strict)
-        self.repack()
-        return res
-
-    def _apply(self, fn, *a, **k):
-        raise RuntimeError("osrl_amd models are bound to their HIP device at construction (pass device=)")
-
     def setup_optimizers(self, actor_lr, critic_lr, vae_lr, alpha_lr):
         """bearl.py:314-321 (note the argument order: vae_lr before alpha_lr)."""
         self._lrs = dict(actor=actor_lr, critic=critic_lr, cost_critic=critic_lr, vae=vae_lr)
         self.alpha_lr = alpha_lr
 
-    def engine(self, batch_size: int, **kw):
-        from ..common.checkpoint import engine_handoff
-        from ..engine.bearl import BEARLEngine
-        if self._engine is None or self._engine.B != batch_size or kw:
-            if self._lrs is None:
-                raise RuntimeError("call setup_optimizers() (or build a BEARLTrainer) before training")
-            old, self._engine = self._engine, BEARLEngine(self, batch_size, **kw)
-            engine_handoff(self, self._engine, old)
-        return self._engine
-
     def sync_weight(self):
         """bearl.py:329-335.  Fused into each group's optimizer kernel inside train_one_step."""
         return None
 
-    def fast_policy(self, num_envs: Optional[int] = None):
-        """The B = 1 latency path (engine/act.py): one kernel launch per ``act()``, pinned-memory I/O.
-        With ``num_envs`` an integer: the lockstep form for that many host environments (``VecFastPolicy``), built once
-        per model and ``num_envs``."""
+    def _policy_spec(self):
         from ..common.net import actor_head_desc
-        if num_envs is not None:
-            from ..engine.act import VecFastPolicy, cached_vec_policy
-            return cached_vec_policy(self, num_envs, lambda n: VecFastPolicy(
-                "gauss", self.device, self.state_dim, self.action_dim, actor_head_desc(self.actor),
-                max_action=self.max_action, num_envs=n))
-        if getattr(self, "_fast", None) is None:
-            from ..engine.act import FastPolicy
-            self._fast = FastPolicy("gauss", self.device, self.state_dim, self.action_dim, actor_head_desc(self.actor),
-                                    max_action=self.max_action)
-        return self._fast
+        return "gauss", self.state_dim, actor_head_desc(self.actor), dict(max_action=self.max_action)
 
     @torch.no_grad()
     def act(self, obs: np.ndarray, deterministic: bool = False, with_logprob: bool = False):
@@ -137,7 +103,7 @@ class BEARL(nn.Module):
         return self.fast_policy().act(obs, deterministic)
 
 
-class BEARLTrainer:
+class BEARLTrainer(RolloutMixin):
     """bearl.py:353-455."""
 
     def __init__(self, model: BEARL, env=None, logger=None, actor_lr: float = 1e-3, critic_lr: float = 1e-3,
@@ -156,48 +122,4 @@ class BEARLTrainer:
                  use_graph=self.use_graph and noise is None)
         store_stats(self.logger, eng.st, self.stats_mode)
 
-    def evaluate(self, eval_episodes):
-        """bearl.py:419-432.  A ``VecSyntheticSafeEnv`` as ``self.env`` runs the episodes as one batch on device (the
-        deterministic policy max_action * tanh(mu) is CPQ's, engine/rollout.py)."""
-        from ..common.synthetic_env import VecSyntheticSafeEnv
-        if isinstance(self.env, VecSyntheticSafeEnv):
-            from ..engine.rollout import evaluate_batched
-            r, c, n = evaluate_batched(self, "cpq", eval_episodes, self.cost_scale)
-            return r / self.reward_scale, c / self.cost_scale, n
-        if isinstance(self.env, (list, tuple)):  # N host environments: episode q on environment q % N, in lockstep
-            from ..engine.act import evaluate_lockstep
-            r, c, n = evaluate_lockstep(self, eval_episodes)
-            return r / self.reward_scale, c / self.cost_scale, n
-        self.model.eval()
-        rets, costs, lens = [], [], []
-        for _ in range(eval_episodes):
-            r, l, c = self.rollout()
-            rets.append(r); lens.append(l); costs.append(c)
-        self.model.train()
-        return np.mean(rets) / self.reward_scale, np.mean(costs) / self.cost_scale, np.mean(lens)
-
-    @torch.no_grad()
-    def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):
-        """``rollout`` on each of the host environments ``envs`` at once, in lockstep through
-        ``model.fast_policy(num_envs)`` (engine/act.py ``rollout_lockstep``): three arrays (return, length, cost sum), one
-        entry per environment.  ``num_slots`` (default ``len(envs)``): the width of the policy to use, the slots past
-        ``len(envs)`` idle.  The policy acts deterministically."""
-        from ..engine.act import rollout_lockstep
-        return rollout_lockstep(self.model, envs, num_slots, episode_ids, cost_scale=self.cost_scale)
-
-    @torch.no_grad()
-    def rollout(self):
-        """bearl.py:434-455."""
-        obs, info = self.env.reset()
-        ep_ret, ep_cost, ep_len = 0.0, 0.0, 0
-        for _ in range(self.model.episode_len):
-            act, _ = self.model.act(obs, True, True)
-            obs_next, reward, terminated, truncated, info = self.env.step(act)
-            cost = info["cost"] * self.cost_scale
-            obs = obs_next
-            ep_ret += reward
-            ep_len += 1
-            ep_cost += cost
-            if terminated or truncated:
-                break
-        return ep_ret, ep_len, ep_cost
+    EVAL_KIND = "cpq"  # (bearl.py:419-455; the deterministic policy max_action * tanh(mu) is CPQ's, engine/rollout.py)

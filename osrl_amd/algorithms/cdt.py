@@ -20,13 +20,14 @@ import torch.nn as nn
 from ..common.logger import store_stats
 from ..common.net import DiagGaussianActor, TransformerBlock, bind_group, mlp, plan_group
 from ..engine.core import FlatGroup, require_cuda
+from ._base import FlatModel
 
 
 class _Params(nn.Module):
     """Holds the reference-named submodules so that plan_group/bind_group see keys without a prefix."""
 
 
-class CDT(nn.Module):
+class CDT(FlatModel):
     def __init__(self, state_dim: int, action_dim: int, max_action: float, seq_len: int = 10,
                  episode_len: int = 1000, embedding_dim: int = 128, num_layers: int = 4, num_heads: int = 8,
                  attention_dropout: float = 0.0, residual_dropout: float = 0.0, embedding_dropout: float = 0.0,
@@ -128,12 +129,9 @@ class CDT(nn.Module):
         (``CDTVecFastPolicy``), built once per model and ``num_envs``.  Raises NotImplementedError naming the limit
         outside the path's domain."""
         if num_envs is not None:
-            from ..engine.cdt_act import CDTVecFastPolicy, _vec_args
-            cache = self.__dict__.setdefault("_fast_vec", {})
-            n = _vec_args(num_envs)
-            if cache.get(n) is None:  # (a copied / unpickled model holds None here: the handle is not copyable)
-                cache[n] = CDTVecFastPolicy(self, n)
-            return cache[n]
+            from ..engine.act import cached_vec_policy
+            from ..engine.cdt_act import CDTVecFastPolicy
+            return cached_vec_policy(self, num_envs, lambda n: CDTVecFastPolicy(self, n), CDTVecFastPolicy.LIMIT)
         if getattr(self, "_fast", None) is None:
             from ..engine.cdt_act import CDTFastPolicy
             self._fast = CDTFastPolicy(self)
@@ -158,21 +156,6 @@ class CDT(nn.Module):
 
     def temperature(self):
         return self.log_temperature.exp() if self.stochastic else None
-
-    def repack(self) -> None:
-        for g in self.groups.values():
-            if g.device.type == "cuda":
-                g.repack()
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        if assign:
-            raise RuntimeError("assign=True would detach parameters from their flat HBM group")
-        res = super().load_state_dict(state_dict, strict=strict)
-        self.repack()
-        return res
-
-    def _apply(self, fn, *a, **k):
-        raise RuntimeError("osrl_amd models are bound to their HIP device at construction (pass device=)")
 
     def engine(self, batch_size: int, cfg: Optional[dict] = None, dist=None):
         from ..common.checkpoint import engine_handoff

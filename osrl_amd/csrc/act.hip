@@ -13,40 +13,17 @@
 //     weights PF[k/4][n][k%4] -- the copies the optimizer kernel keeps fresh -- so every wave load is 1 KB contiguous
 //     and no dot product needs a cross-lane reduction; the 1024 threads split k as well, partials meet in LDS;
 // HBM/L2-bound on one CU by design (latency, not throughput): ~345 KB at the per-CU L2 rate is ~3 us.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-
-#include <atomic>
-#include <chrono>
 #include <new>
 
-#include "../../include/osrl_amd.h"
-#include "philox.h"
+#include "policy_common.h"
 
 using osrl_rng::U4;
 using osrl_rng::philox4x32_10;
 
 namespace {
 
-constexpr int kThreads = 1024, kWaves = 16;
-constexpr int kMaxRows = OSRL_POLICY_MAX_ROWS;
-// LDS row stride (floats) >= widest layer and obs+act inputs: 512 for nets whose layers are all <= 512 wide (every net of
-// the fused-kernel widths), 1024 = OSRL_MAX_WIDTH for the wider ones (a second instantiation: twice the LDS)
-constexpr int kW = 512, kWideW = OSRL_MAX_WIDTH;
-constexpr float kLogStdMin = -20.0f, kLogStdMax = 2.0f;  // net.py:148-149
-
-__device__ __forceinline__ float softplus(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
-__device__ __forceinline__ float act_fwd(int act, float x) {
-  if (act == OSRL_ACT_RELU) return fmaxf(x, 0.0f);
-  if (act == OSRL_ACT_TANH) return tanhf(x);
-  return x;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
+constexpr int kThreads = 1024;
+constexpr int kMaxRows = OSRL_POLICY_MAX_ROWS;  // (the LDS row stride kW / kWideW >= the widest layer and obs+act inputs)
 
 struct Io {  // pinned + device-mapped; the host writes obs / noise, the kernel writes act / logp / seq
   float* obs;     // [kMaxRows, obs_dim]
@@ -77,8 +54,6 @@ struct ActArgs {
 // chain of six ds_bpermute: measured 5 us per layer).  The 1024 threads = KS k-splits x NL neuron lanes
 // (NL = min(256, Np rounded up to a power of two)); each thread issues all its loads back to back; the KS partials meet
 // in LDS.
-__device__ __forceinline__ int round16(int x) { return (x + 15) & ~15; }
-
 template <int R, int W>
 __device__ __forceinline__ void gemv_layer(const float* __restrict__ PF, const float* __restrict__ b, int in, int out,
                                            int act, float scale, const float* x, float* y, float* red) {
@@ -133,16 +108,8 @@ __device__ __forceinline__ int run_net(const osrl_gemv_net_t& n, float (*buf)[kM
 
 __device__ __forceinline__ float draw_normal(const ActArgs& a, int idx) {
   // Philox4x32-10 keyed like csrc/rng.hip (counter = (element/4, call counter lo, hi, stream 0xAC7)), Box-Muller
-  const U4 r = philox4x32_10(U4{(uint32_t)(idx >> 2), (uint32_t)a.counter, (uint32_t)(a.counter >> 32), 0xAC7u}, a.k0,
-                             a.k1);
-  const uint32_t u[4] = {r.x, r.y, r.z, r.w};
-  const int pair = (idx & 3) >> 1;
-  const float u1 = ((float)(u[2 * pair] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float u2 = ((float)(u[2 * pair + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float rad = sqrtf(-2.0f * logf(u1));
-  float s, c;
-  sincosf(6.283185307179586f * u2, &s, &c);
-  return (idx & 1) ? rad * s : rad * c;
+  return normal_from_words(
+      philox4x32_10(U4{(uint32_t)(idx >> 2), (uint32_t)a.counter, (uint32_t)(a.counter >> 32), 0xAC7u}, a.k0, a.k1), idx);
 }
 
 #ifdef OSRL_ACT_STAMPS  // debug: 100 MHz wall-clock stamps of thread 0 into logp[1..7] (rows = 1 runs only)
@@ -192,14 +159,10 @@ __global__ __launch_bounds__(kThreads) void policy_act_kernel(const ActArgs a) {
       const float* h = buf[cur] + tid * W;
       float lp = 0.f;
       for (int j = 0; j < ad; ++j) {
-        const float mu = h[j];
-        const float ls = fminf(fmaxf(h[ad + j], kLogStdMin), kLogStdMax);
+        const float mu = h[j], raw_ls = h[ad + j];
         float e = 0.f;
         if (!a.deterministic) e = a.host_noise ? a.io.noise[tid * ad + j] : draw_normal(a, tid * ad + j);
-        const float u = mu + expf(ls) * e;
-        a.io.act[tid * ad + j] = p.max_action * tanhf(u);
-        lp += -0.5f * e * e - ls - 0.9189385332046727f;
-        lp -= 2.0f * (0.6931471805599453f - u - softplus(-2.0f * u));
+        squashed_gauss(mu, raw_ls, e, p.max_action, &a.io.act[tid * ad + j], lp);
       }
       a.io.logp[tid] = lp;
     }
@@ -225,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void policy_act_kernel(const ActArgs a) {
     const int c2 = run_net<R, W>(p.net[1], buf, red);
     if (tid < rows * ad) {
       const float t = buf[c2][(tid / ad) * W + (tid % ad)];
-      a.io.act[tid] = fminf(fmaxf(a0 + p.phi * p.max_action * t, -p.max_action), p.max_action);
+      a.io.act[tid] = bcq_clamp(a0, p.phi, p.max_action, t);
     }
   }
   // ---- publish: results must be visible to the host before the sequence number
@@ -245,79 +208,37 @@ __global__ __launch_bounds__(kThreads) void policy_act_kernel(const ActArgs a) {
 
 struct Handle {
   osrl_policy_t p;
+  PinnedBlock blk;
   Io host, dev;
-  void* pinned;
-  size_t bytes;
   uint64_t seq, calls;
   int noise_dim;
 };
 
-bool valid_gemv(const osrl_gemv_net_t& n) {
-  if (n.n_layers < 1 || n.n_layers > OSRL_MAX_LAYERS || n.out_scale == 0.f) return false;
-  for (int l = 0; l <= n.n_layers; ++l)
-    if (n.dims[l] < 1 || n.dims[l] > kWideW) return false;
-  for (int l = 0; l < n.n_layers; ++l)
-    if (!n.Wf[l] || !n.b[l]) return false;
-  return true;
-}
-
-// a layer or a staged input row wider than kW: the kWideW instantiation
-bool needs_wide(const osrl_policy_t& p) {
-  const int nn = p.kind == OSRL_POLICY_BCQ ? 2 : 1;
-  for (int i = 0; i < nn; ++i)
-    for (int l = 0; l <= p.net[i].n_layers; ++l)
-      if (p.net[i].dims[l] > kW) return true;
-  return p.kind == OSRL_POLICY_BCQ && (p.obs_dim + p.latent_dim > kW || p.obs_dim + p.act_dim > kW);
-}
-
 }  // namespace
 
 extern "C" int osrl_policy_create(const osrl_policy_t* desc, void** handle) {
-  if (!desc || !handle) return -1;
-  const osrl_policy_t& p = *desc;
-  if (p.kind < OSRL_POLICY_MLP || p.kind > OSRL_POLICY_BCQ || p.obs_dim < 1 || p.act_dim < 1 || !valid_gemv(p.net[0]))
-    return -1;
   int noise_dim = 0;
-  if (p.kind == OSRL_POLICY_MLP) {
-    if (p.net[0].dims[0] != p.obs_dim || p.net[0].dims[p.net[0].n_layers] != p.act_dim) return -1;
-  } else if (p.kind == OSRL_POLICY_GAUSS) {
-    if (p.net[0].dims[0] != p.obs_dim || p.net[0].dims[p.net[0].n_layers] != 2 * p.act_dim) return -1;
-    noise_dim = p.act_dim;
-  } else {
-    if (!valid_gemv(p.net[1]) || p.latent_dim < 1 || p.net[0].dims[0] != p.obs_dim + p.latent_dim ||
-        p.net[0].dims[p.net[0].n_layers] != p.act_dim || p.net[1].dims[0] != p.obs_dim + p.act_dim ||
-        p.net[1].dims[p.net[1].n_layers] != p.act_dim || p.obs_dim + p.latent_dim > kWideW || p.obs_dim + p.act_dim > kWideW)
-      return -1;
-    noise_dim = p.latent_dim;
-  }
+  if (!desc || !handle || !valid_policy(*desc, &noise_dim)) return -1;
+  const osrl_policy_t& p = *desc;
   Handle* h = new (std::nothrow) Handle;
   if (!h) return -1;
   h->p = p;
   h->noise_dim = noise_dim;
   h->seq = h->calls = 0;
-  auto r256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
-  const size_t o_obs = 0, o_noise = o_obs + r256(sizeof(float) * kMaxRows * p.obs_dim),
-               o_act = o_noise + r256(sizeof(float) * kMaxRows * (noise_dim > 0 ? noise_dim : 1)),
-               o_logp = o_act + r256(sizeof(float) * kMaxRows * p.act_dim), o_seq = o_logp + r256(sizeof(float) * kMaxRows);
-  h->bytes = o_seq + 256;
-  hipError_t e = hipHostMalloc(&h->pinned, h->bytes, hipHostMallocMapped | hipHostMallocPortable);
+  const size_t R = sizeof(float) * kMaxRows;
+  const size_t bytes[] = {R * p.obs_dim, R * (noise_dim > 0 ? noise_dim : 1), R * p.act_dim, R, sizeof(uint64_t)};
+  const hipError_t e = h->blk.alloc(bytes, 5);
   if (e != hipSuccess) {
     delete h;
     return (int)e;
   }
-  memset(h->pinned, 0, h->bytes);
-  void* dptr = nullptr;
-  e = hipHostGetDevicePointer(&dptr, h->pinned, 0);
-  if (e != hipSuccess) {
-    (void)hipHostFree(h->pinned);
-    delete h;
-    return (int)e;
-  }
-  auto at = [](void* base, size_t off) { return reinterpret_cast<char*>(base) + off; };
-  h->host = Io{(float*)at(h->pinned, o_obs), (float*)at(h->pinned, o_noise), (float*)at(h->pinned, o_act),
-               (float*)at(h->pinned, o_logp), (uint64_t*)at(h->pinned, o_seq)};
-  h->dev = Io{(float*)at(dptr, o_obs), (float*)at(dptr, o_noise), (float*)at(dptr, o_act), (float*)at(dptr, o_logp),
-              (uint64_t*)at(dptr, o_seq)};
+  auto io = [&](bool dev) {
+    const PinnedBlock& b = h->blk;
+    return Io{b.seg<float>(0, dev), b.seg<float>(1, dev), b.seg<float>(2, dev), b.seg<float>(3, dev),
+              b.seg<uint64_t>(4, dev)};
+  };
+  h->host = io(false);
+  h->dev = io(true);
   *handle = h;
   return 0;
 }
@@ -359,31 +280,16 @@ extern "C" int osrl_policy_act(void* handle, int32_t rows, int32_t deterministic
   } else {
     hipLaunchKernelGGL(policy_act_kernel<kMaxRows>, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, a);
   }
-  hipError_t e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-  // fast path: spin on the sequence number the kernel publishes (system-scope release) -- a stream synchronise costs
-  // more than the kernel; after 2 ms fall back to it (also surfaces a faulted launch instead of spinning forever)
-  volatile uint64_t* seq = h->host.seq;
-  const auto t0 = std::chrono::steady_clock::now();
-  for (uint32_t it = 0;; ++it) {
-    if (*seq >= a.seq) break;
-    if ((it & 1023) == 1023 &&
-        std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-      e = hipStreamSynchronize((hipStream_t)stream);
-      if (e != hipSuccess) return (int)e;
-      if (*seq < a.seq) return -2;  // the kernel ran but did not publish: should be impossible
-      break;
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return 0;
+  return wait_published(h->host.seq, 1, 1, a.seq, (hipStream_t)stream);
 }
 
 extern "C" int osrl_policy_destroy(void* handle) {
   if (!handle) return -1;
   Handle* h = static_cast<Handle*>(handle);
   (void)hipDeviceSynchronize();  // no launch of this handle may still be writing the pinned block
-  const hipError_t e = hipHostFree(h->pinned);
+  const hipError_t e = h->blk.release();
   delete h;
   return (int)e;
 }

@@ -15,16 +15,9 @@
 //     log-probs are written to it, and each workgroup publishes a sequence number of its own that the host spins on;
 //   * noise drawn on the device is Philox keyed by (seed, the slot's episode id, the slot's step, element): an episode
 //     replays identically in any wave and slot.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-
-#include <atomic>
-#include <chrono>
 #include <new>
 
-#include "../../include/osrl_amd.h"
-#include "philox.h"
+#include "policy_common.h"
 
 using osrl_rng::philox4x32_10;
 using osrl_rng::U4;
@@ -35,17 +28,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 512, kWaves = 8;
 constexpr int kMaxEnvs = OSRL_POLICY_MAX_ENVS, kTile = 16, kMaxTiles = (kMaxEnvs + kTile - 1) / kTile;
-constexpr int kW = 512, kWideW = OSRL_MAX_WIDTH;  // LDS row widths of the two instantiations (as act.hip)
 constexpr int kPad = 4;  // floats: rows 16 bytes apart in the banks, a tile's 16 A reads of one k-quad do not collide
-constexpr float kLogStdMin = -20.0f, kLogStdMax = 2.0f;  // net.py:148-149
-
-__device__ __forceinline__ float softplus(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
-__device__ __forceinline__ float act_fwd(int act, float x) {
-  if (act == OSRL_ACT_RELU) return fmaxf(x, 0.0f);
-  if (act == OSRL_ACT_TANH) return tanhf(x);
-  return x;
-}
-__device__ __forceinline__ int round16(int x) { return (x + 15) & ~15; }
 
 struct Io {  // pinned + device-mapped; the host writes obs / noise / active / meta, the kernel writes act / logp / seq
   float* obs;       // [n_env, obs_dim]
@@ -140,15 +123,8 @@ __device__ __forceinline__ int run_net(const osrl_gemv_net_t& n, float (*buf)[kT
 // step, stream 0xAC8) and the seed as key, Box-Muller on the word pair idx selects.  Nothing of the handle, of n_env or
 // of the slot enters.
 __device__ __forceinline__ float draw_normal(const VecArgs& a, int32_t episode, int32_t step, int idx) {
-  const U4 r = philox4x32_10(U4{(uint32_t)(idx >> 2), (uint32_t)episode, (uint32_t)step, 0xAC8u}, a.k0, a.k1);
-  const uint32_t u[4] = {r.x, r.y, r.z, r.w};
-  const int pair = (idx & 3) >> 1;
-  const float u1 = ((float)(u[2 * pair] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float u2 = ((float)(u[2 * pair + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float rad = sqrtf(-2.0f * logf(u1));
-  float s, c;
-  sincosf(6.283185307179586f * u2, &s, &c);
-  return (idx & 1) ? rad * s : rad * c;
+  return normal_from_words(
+      philox4x32_10(U4{(uint32_t)(idx >> 2), (uint32_t)episode, (uint32_t)step, 0xAC8u}, a.k0, a.k1), idx);
 }
 
 template <int W>
@@ -196,14 +172,10 @@ __global__ __launch_bounds__(kThreads) void policy_vec_kernel(const VecArgs a) {
       const int32_t episode = a.io.meta[2 * s], step = a.io.meta[2 * s + 1];
       float lp = 0.f;
       for (int j = 0; j < ad; ++j) {
-        const float mu = h[j];
-        const float ls = fminf(fmaxf(h[ad + j], kLogStdMin), kLogStdMax);
+        const float mu = h[j], raw_ls = h[ad + j];
         float e = 0.f;
         if (!a.deterministic) e = a.host_noise ? a.io.noise[(size_t)s * ad + j] : draw_normal(a, episode, step, j);
-        const float u = mu + expf(ls) * e;
-        a.io.act[(size_t)s * ad + j] = p.max_action * tanhf(u);
-        lp += -0.5f * e * e - ls - 0.9189385332046727f;
-        lp -= 2.0f * (0.6931471805599453f - u - softplus(-2.0f * u));
+        squashed_gauss(mu, raw_ls, e, p.max_action, &a.io.act[(size_t)s * ad + j], lp);
       }
       a.io.logp[s] = lp;
     }
@@ -233,8 +205,7 @@ __global__ __launch_bounds__(kThreads) void policy_vec_kernel(const VecArgs a) {
       if (i < kTile * ad) {
         const int r = i / ad, j = i - r * ad;
         const float t = buf[c2][r * S + j];
-        if (live[r])
-          a.io.act[(size_t)(s0 + r) * ad + j] = fminf(fmaxf(a0[q] + p.phi * p.max_action * t, -p.max_action), p.max_action);
+        if (live[r]) a.io.act[(size_t)(s0 + r) * ad + j] = bcq_clamp(a0[q], p.phi, p.max_action, t);
       }
     }
   }
@@ -248,53 +219,19 @@ __global__ __launch_bounds__(kThreads) void policy_vec_kernel(const VecArgs a) {
 
 struct Handle {
   osrl_policy_t p;
+  PinnedBlock blk;
   Io host, dev;
-  void* pinned;
-  size_t bytes;
   uint64_t seq;
   int n_env, noise_dim;
   bool wide;
 };
 
-bool valid_net(const osrl_gemv_net_t& n) {
-  if (n.n_layers < 1 || n.n_layers > OSRL_MAX_LAYERS || n.out_scale == 0.f) return false;
-  for (int l = 0; l <= n.n_layers; ++l)
-    if (n.dims[l] < 1 || n.dims[l] > kWideW) return false;
-  for (int l = 0; l < n.n_layers; ++l)
-    if (!n.Wf[l] || !n.b[l]) return false;
-  return true;
-}
-
-// a layer or a staged input row wider than kW: the kWideW instantiation
-bool needs_wide(const osrl_policy_t& p) {
-  const int nn = p.kind == OSRL_POLICY_BCQ ? 2 : 1;
-  for (int i = 0; i < nn; ++i)
-    for (int l = 0; l <= p.net[i].n_layers; ++l)
-      if (p.net[i].dims[l] > kW) return true;
-  return false;
-}
-
 }  // namespace
 
 extern "C" int osrl_policy_create_n(const osrl_policy_t* desc, int32_t n_env, void** handle) {
-  if (!desc || !handle || n_env < 1 || n_env > kMaxEnvs) return -1;
-  const osrl_policy_t& p = *desc;
-  if (p.kind < OSRL_POLICY_MLP || p.kind > OSRL_POLICY_BCQ || p.obs_dim < 1 || p.act_dim < 1 || !valid_net(p.net[0]))
-    return -1;
   int noise_dim = 0;
-  if (p.kind == OSRL_POLICY_MLP) {
-    if (p.net[0].dims[0] != p.obs_dim || p.net[0].dims[p.net[0].n_layers] != p.act_dim) return -1;
-  } else if (p.kind == OSRL_POLICY_GAUSS) {
-    if (p.net[0].dims[0] != p.obs_dim || p.net[0].dims[p.net[0].n_layers] != 2 * p.act_dim) return -1;
-    noise_dim = p.act_dim;
-  } else {
-    // (the staged rows [obs, z] and [obs, a0] are the nets' inputs: dims[0] <= OSRL_MAX_WIDTH bounds them)
-    if (!valid_net(p.net[1]) || p.latent_dim < 1 || p.net[0].dims[0] != p.obs_dim + p.latent_dim ||
-        p.net[0].dims[p.net[0].n_layers] != p.act_dim || p.net[1].dims[0] != p.obs_dim + p.act_dim ||
-        p.net[1].dims[p.net[1].n_layers] != p.act_dim)
-      return -1;
-    noise_dim = p.latent_dim;
-  }
+  if (!desc || !handle || n_env < 1 || n_env > kMaxEnvs || !valid_policy(*desc, &noise_dim)) return -1;
+  const osrl_policy_t& p = *desc;
   Handle* h = new (std::nothrow) Handle;
   if (!h) return -1;
   h->p = p;
@@ -302,33 +239,21 @@ extern "C" int osrl_policy_create_n(const osrl_policy_t* desc, int32_t n_env, vo
   h->noise_dim = noise_dim;
   h->seq = 0;
   h->wide = needs_wide(p);
-  auto r256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
-  const size_t N = (size_t)n_env;
-  const size_t o_obs = 0, o_noise = o_obs + r256(sizeof(float) * N * p.obs_dim),
-               o_act = o_noise + r256(sizeof(float) * N * (noise_dim > 0 ? noise_dim : 1)),
-               o_logp = o_act + r256(sizeof(float) * N * p.act_dim), o_active = o_logp + r256(sizeof(float) * N),
-               o_meta = o_active + r256(sizeof(int32_t) * N), o_seq = o_meta + r256(sizeof(int32_t) * 2 * N);
-  h->bytes = o_seq + r256(sizeof(uint64_t) * kSeqStride * kMaxTiles);
-  hipError_t e = hipHostMalloc(&h->pinned, h->bytes, hipHostMallocMapped | hipHostMallocPortable);
+  const size_t N = (size_t)n_env, F = sizeof(float) * N, I = sizeof(int32_t) * N;
+  const size_t bytes[] = {F * p.obs_dim, F * (noise_dim > 0 ? noise_dim : 1), F * p.act_dim, F, I, 2 * I,
+                          sizeof(uint64_t) * kSeqStride * kMaxTiles};
+  const hipError_t e = h->blk.alloc(bytes, 7);
   if (e != hipSuccess) {
     delete h;
     return (int)e;
   }
-  memset(h->pinned, 0, h->bytes);
-  void* dptr = nullptr;
-  e = hipHostGetDevicePointer(&dptr, h->pinned, 0);
-  if (e != hipSuccess) {
-    (void)hipHostFree(h->pinned);
-    delete h;
-    return (int)e;
-  }
-  auto at = [](void* base, size_t off) { return reinterpret_cast<char*>(base) + off; };
-  auto io = [&](void* base) {
-    return Io{(float*)at(base, o_obs),        (float*)at(base, o_noise),  (float*)at(base, o_act),  (float*)at(base, o_logp),
-              (int32_t*)at(base, o_active), (int32_t*)at(base, o_meta), (uint64_t*)at(base, o_seq)};
+  auto io = [&](bool dev) {
+    const PinnedBlock& b = h->blk;
+    return Io{b.seg<float>(0, dev),   b.seg<float>(1, dev),   b.seg<float>(2, dev),   b.seg<float>(3, dev),
+              b.seg<int32_t>(4, dev), b.seg<int32_t>(5, dev), b.seg<uint64_t>(6, dev)};
   };
-  h->host = io(h->pinned);
-  h->dev = io(dptr);
+  h->host = io(false);
+  h->dev = io(true);
   for (int i = 0; i < n_env; ++i) h->host.active[i] = 1;
   *handle = h;
   return 0;
@@ -366,35 +291,16 @@ extern "C" int osrl_policy_act_n(void* handle, int32_t deterministic, int32_t ho
     hipLaunchKernelGGL(policy_vec_kernel<kWideW>, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(policy_vec_kernel<kW>, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-  // fast path: spin on the sequence numbers the workgroups publish (system-scope release), as osrl_policy_act does;
-  // after 2 ms fall back to a stream synchronise (also surfaces a faulted launch instead of spinning forever)
-  volatile uint64_t* seq = h->host.seq;
-  const auto t0 = std::chrono::steady_clock::now();
-  int t = 0;
-  for (uint32_t it = 0; t < tiles; ++it) {
-    if (seq[kSeqStride * t] >= a.seq) {
-      ++t;
-      continue;
-    }
-    if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-      e = hipStreamSynchronize((hipStream_t)stream);
-      if (e != hipSuccess) return (int)e;
-      for (int u = t; u < tiles; ++u)
-        if (seq[kSeqStride * u] < a.seq) return -2;  // the kernel ran but did not publish: should be impossible
-      break;
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return 0;
+  return wait_published(h->host.seq, kSeqStride, tiles, a.seq, (hipStream_t)stream);
 }
 
 extern "C" int osrl_policy_destroy_n(void* handle) {
   if (!handle) return -1;
   Handle* h = static_cast<Handle*>(handle);
   (void)hipDeviceSynchronize();  // no launch of this handle may still be writing the pinned block
-  const hipError_t e = hipHostFree(h->pinned);
+  const hipError_t e = h->blk.release();
   delete h;
   return (int)e;
 }

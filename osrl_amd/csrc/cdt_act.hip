@@ -23,18 +23,13 @@
 // SAME 2 + 5 * layers launches: ingest and head run one workgroup per episode, attention one wave per (row, head,
 // episode), and a projection's row list is the concatenation over the episodes, so that its 16-row tiles fill up with
 // rows of several episodes.  No arithmetic crosses rows: an episode's results do not depend on N or on its slot.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
-#include <string.h>
 
-#include <atomic>
-#include <chrono>
 #include <new>
 #include <vector>
 
-#include "../../include/osrl_amd.h"
 #include "gelu.h"
+#include "policy_common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -42,8 +37,6 @@ namespace {
 
 constexpr int kMaxE = 512, kMaxD = 128, kMaxTok = 256, kMaxHead = 1024;
 constexpr float kLnEps = 1e-5f;
-
-__device__ __forceinline__ int r16(int x) { return (x + 15) & ~15; }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -199,7 +192,7 @@ __global__ __launch_bounds__(256) void cdt_act_ingest_kernel(const IngestArgs a)
 struct LinArgs {
   const float* X;
   const float *ln_g, *ln_b;  // LayerNorm of the input rows (K = E) or null
-  const float* W;            // packed PF[k/4][n][k%4], Np = r16(N) columns
+  const float* W;            // packed PF[k/4][n][k%4], Np = round16(N) columns
   const float* bias;
   const float* res;  // residual rows (same row index) or null
   float* Y;
@@ -247,7 +240,7 @@ __global__ __launch_bounds__(256) void cdt_act_linear_kernel(const LinArgs a) {
   const int row = rows[ar];
   const float* __restrict__ xr = row >= 0 ? a.X + xo[ar] : nullptr;
   const float mean = a.ln_g ? st[ar][0] : 0.f, rstd = a.ln_g ? st[ar][1] : 1.f;
-  const int Np = r16(a.N), nkb = r16(a.K) >> 4;
+  const int Np = round16(a.N), nkb = round16(a.K) >> 4;
   const int kb0 = (nkb * w) >> 2, kb1 = (nkb * (w + 1)) >> 2;
   const f32x4* __restrict__ W4 = reinterpret_cast<const f32x4*>(a.W);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -430,12 +423,12 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
   for (int l = 0; l < nl; ++l) {
     const bool last = l == nl - 1;
     const int out = last ? p.action_dim : Eh;
-    const int Np = last ? r16(p.head_out_width) : r16(Eh);
-    const int nq = r16(in) >> 2;
+    const int Np = last ? round16(p.head_out_width) : round16(Eh);
+    const int nq = round16(in) >> 2;
     const f32x4* __restrict__ W4 = reinterpret_cast<const f32x4*>(p.head_w[l]);
     // 1024 threads = KS k-splits x NL neuron lanes
     int NL = 16;
-    while (NL < r16(out) && NL < 256) NL <<= 1;
+    while (NL < round16(out) && NL < 256) NL <<= 1;
     const int KS = kHeadThreads / NL, ks = tid / NL, nl_ = tid - ks * NL;
     const int q0 = (nq * ks) / KS, q1 = (nq * (ks + 1)) / KS;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};  // neurons nl_ + 256 j (out <= 1024)
@@ -444,7 +437,7 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int n = nl_ + 256 * j;
-        if (n < NL * (j + 1) && n < r16(out)) {
+        if (n < NL * (j + 1) && n < round16(out)) {
           const f32x4 wv = W4[(size_t)q * Np + n];
           acc[j] = fmaf(wv[0], xv[0], fmaf(wv[1], xv[1], fmaf(wv[2], xv[2], fmaf(wv[3], xv[3], acc[j]))));
         }
@@ -453,11 +446,11 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
     // partials [KS][NL] per 256-neuron chunk, summed in k-split order
     float* nxt = buf[cur ^ 1];
     for (int j = 0; j < 4; ++j) {
-      if (256 * j >= r16(out)) break;
+      if (256 * j >= round16(out)) break;
       __syncthreads();
       red[tid] = acc[j];
       __syncthreads();
-      for (int n = 256 * j + tid; n < 256 * (j + 1) && n < r16(out) && tid < NL; n += kHeadThreads) {
+      for (int n = 256 * j + tid; n < 256 * (j + 1) && n < round16(out) && tid < NL; n += kHeadThreads) {
         float s = 0.f;
         for (int k = 0; k < KS; ++k) s += red[k * NL + (n - 256 * j)];
         float v = 0.f;
@@ -469,7 +462,7 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
       }
     }
     __syncthreads();
-    for (int f = r16(out) + tid; f < kMaxHead; f += kHeadThreads) nxt[f] = 0.f;  // the next layer's k padding
+    for (int f = round16(out) + tid; f < kMaxHead; f += kHeadThreads) nxt[f] = 0.f;  // the next layer's k padding
     __syncthreads();
     cur ^= 1;
     in = out;
@@ -502,8 +495,8 @@ struct Handle {
   int nenv;    // episodes advanced in lockstep
   int64_t es;  // floats per episode block of dmem
   int t;       // timestep of the newest window entry (every episode's); -1 before the first reset
+  PinnedBlock blk;
   Io host, dev;
-  void* pinned;
   Dev d;
   void* dmem;
   float *x, *qkv, *o, *xmid, *h;  // episode 0's; x: [NL + 1][NR, ldE], qkv: [NL][NR, ld3]
@@ -546,22 +539,6 @@ void run_layer(const Handle* h, int l, int first, int count, int ring, int ofirs
                 ocount, oring, s);
 }
 
-int spin(Handle* h, hipStream_t s) {
-  volatile uint64_t* seq = h->host.seq;
-  const auto t0 = std::chrono::steady_clock::now();
-  for (uint32_t it = 0;; ++it) {
-    if (*seq >= h->seq) break;
-    if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-      const hipError_t e = hipStreamSynchronize(s);
-      if (e != hipSuccess) return (int)e;
-      if (*seq < h->seq) return -2;  // the chain ran but did not publish: should be impossible
-      break;
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return 0;
-}
-
 // the chain of one env step (t = h->t already advanced); reset: the prefix row joins the embedded rows
 int run_step(Handle* h, int reset, int host_action, hipStream_t s) {
   const osrl_cdt_policy_t& p = h->p;
@@ -602,7 +579,7 @@ int run_step(Handle* h, int reset, int host_action, hipStream_t s) {
   hipLaunchKernelGGL(cdt_act_head_kernel, dim3(h->nenv), dim3(kHeadThreads), 0, s, ha);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-  return spin(h, s);
+  return wait_published(h->host.seq, 1, 1, h->seq, s);
 }
 
 bool valid(const osrl_cdt_policy_t& p, const osrl_cdt_layer_t* layers) {
@@ -649,35 +626,27 @@ int create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int n_
   h->t = -1;
   h->seq = 0;
   h->dmem = nullptr;
-  auto r256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
   // pinned block: obs [N, od], act_in [N, ad], act_out [N, ad], scalars [N, 4], seq
-  const size_t o_obs = 0, o_ain = o_obs + r256(4 * NE * od), o_aout = o_ain + r256(4 * NE * ad),
-               o_sc = o_aout + r256(4 * NE * ad), o_seq = o_sc + r256(16 * NE), pbytes = o_seq + 256;
-  hipError_t e = hipHostMalloc(&h->pinned, pbytes, hipHostMallocMapped | hipHostMallocPortable);
+  const size_t pbytes[] = {4 * NE * od, 4 * NE * ad, 4 * NE * ad, 16 * NE, sizeof(uint64_t)};
+  hipError_t e = h->blk.alloc(pbytes, 5);
   if (e != hipSuccess) {
     delete h;
     return (int)e;
   }
-  memset(h->pinned, 0, pbytes);
-  void* dptr = nullptr;
-  e = hipHostGetDevicePointer(&dptr, h->pinned, 0);
-  if (e != hipSuccess) {
-    (void)hipHostFree(h->pinned);
-    delete h;
-    return (int)e;
-  }
-  auto at = [](void* base, size_t off) { return reinterpret_cast<char*>(base) + off; };
-  h->host = Io{(float*)at(h->pinned, o_obs), (float*)at(h->pinned, o_ain), (float*)at(h->pinned, o_aout),
-               (float*)at(h->pinned, o_sc), (uint64_t*)at(h->pinned, o_seq)};
-  h->dev = Io{(float*)at(dptr, o_obs), (float*)at(dptr, o_ain), (float*)at(dptr, o_aout), (float*)at(dptr, o_sc),
-              (uint64_t*)at(dptr, o_seq)};
+  auto io = [&](bool dev) {
+    const PinnedBlock& b = h->blk;
+    return Io{b.seg<float>(0, dev), b.seg<float>(1, dev), b.seg<float>(2, dev), b.seg<float>(3, dev),
+              b.seg<uint64_t>(4, dev)};
+  };
+  h->host = io(false);
+  h->dev = io(true);
   // device block, one per episode: window ring, last action, raw embeddings, activations (zeroed: the row strides'
   // padding stays 0); then the head's arrival counter
   const size_t NR = h->NR;
   size_t off = 0;
   auto take = [&](size_t floats) {
     const size_t o = off;
-    off += r256(4 * floats);
+    off += (4 * floats + 255) & ~(size_t)255;
     return o;
   };
   const size_t o_s = take((size_t)T * od), o_a = take((size_t)T * ad), o_r = take(T), o_c = take(T), o_t = take(T),
@@ -685,7 +654,6 @@ int create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int n_
                o_q = take((size_t)NL * NR * h->ld3), o_o = take(NR * h->ldE), o_m = take(NR * h->ldE),
                o_h = take(NR * h->ld4);
   if (off / 4 > (size_t)INT32_MAX) {  // (the attention launch passes the episode stride as 32 bits)
-    (void)hipHostFree(h->pinned);
     delete h;
     return -1;
   }
@@ -695,7 +663,6 @@ int create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int n_
   if (e == hipSuccess) e = hipMemset(h->dmem, 0, total);
   if (e != hipSuccess) {
     if (h->dmem) (void)hipFree(h->dmem);
-    (void)hipHostFree(h->pinned);
     delete h;
     return (int)e;
   }
@@ -829,7 +796,7 @@ extern "C" int osrl_cdt_policy_destroy(void* handle) {
   Handle* h = static_cast<Handle*>(handle);
   (void)hipDeviceSynchronize();  // no launch of this handle may still be running
   hipError_t e = hipFree(h->dmem);
-  const hipError_t e2 = hipHostFree(h->pinned);
+  const hipError_t e2 = h->blk.release();
   delete h;
   return (int)(e != hipSuccess ? e : e2);
 }

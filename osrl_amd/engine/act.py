@@ -42,31 +42,92 @@ def _gemv_net(dst: "L.GemvNetT", desc: NetDesc) -> None:
         dst.Wf[l], dst.b[l] = r.wf_ptr, r.b.data_ptr()
 
 
-class FastPolicy:
+KINDS = {"mlp": L.POLICY_MLP, "gauss": L.POLICY_GAUSS, "bcq": L.POLICY_BCQ}
+MAX_ENVS = L.POLICY_MAX_ENVS
+
+
+def _policy_desc(kind: str, obs_dim: int, act_dim: int, net0: NetDesc, max_action: float, net1: Optional[NetDesc],
+                 latent_dim: int, phi: float) -> "L.PolicyT":
+    d = L.PolicyT()
+    d.kind, d.obs_dim, d.act_dim, d.latent_dim = KINDS[kind], obs_dim, act_dim, latent_dim
+    d.max_action, d.phi = float(max_action), float(phi)
+    _gemv_net(d.net[0], net0)
+    if net1 is not None:
+        _gemv_net(d.net[1], net1)
+    return d
+
+
+def _vec_args(num_envs, limit: int, limit_name: str) -> int:
+    if isinstance(num_envs, bool) or not isinstance(num_envs, (int, np.integer)):
+        raise ValueError(f"num_envs must be an integer from 1 to {limit}, got {num_envs!r}")
+    if not 1 <= int(num_envs) <= limit:
+        raise ValueError(f"num_envs {int(num_envs)} is outside 1 .. {limit} ({limit_name})")
+    return int(num_envs)
+
+
+class PinnedHandle:
+    """A handle to a pinned, device-mapped I/O block behind a ctypes pointer; ``DESTROY`` names the C call that frees
+    it.  It cannot be copied or pickled: a copied / unpickled model simply has no fast policy yet and builds its own on
+    first use (the models test ``_fast is None``)."""
+
+    DESTROY = ""
+
+    def _open(self, device, entry: str, *args):
+        """Creates the handle on ``device`` by ``entry(*args, &handle)``; returns the library."""
+        self.device = torch.device(device)
+        lib = L.load()
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(getattr(lib, entry)(*args, C.byref(h)), entry)
+        self._h, self._lib = h, lib
+        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+        return lib
+
+    def __deepcopy__(self, memo):
+        return None
+
+    def __reduce__(self):
+        return (type(None), ())
+
+    def _stream(self):
+        return self._raw_stream(self._dev_index) if self._raw_stream is not None else cur_stream()
+
+    def _rows(self, name, x, tail, dtype=None) -> np.ndarray:
+        """``x`` as an array of shape ``(num_envs,) + tail``: for the lockstep handles, which set ``num_envs``."""
+        want = (self.num_envs,) + tail
+        if np.shape(x) != want:  # numpy would broadcast silently
+            raise ValueError(f"expected {name} of shape {want}, got {np.shape(x)}")
+        return np.asarray(x, dtype=dtype)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            getattr(self._lib, self.DESTROY)(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover - interpreter shutdown order
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FastPolicy(PinnedHandle):
     """``kind``: "mlp" (BC), "gauss" (squashed-Gaussian actor), "bcq" (VAE decoder + perturbation actor)."""
 
-    KINDS = {"mlp": L.POLICY_MLP, "gauss": L.POLICY_GAUSS, "bcq": L.POLICY_BCQ}
+    KINDS = KINDS
+    DESTROY = "osrl_policy_destroy"
 
     def __init__(self, kind: str, device, obs_dim: int, act_dim: int, net0: NetDesc, max_action: float = 1.0,
                  net1: Optional[NetDesc] = None, latent_dim: int = 0, phi: float = 0.0, seed: int = 0):
         require_cuda(device)
-        self.device = torch.device(device)
-        d = L.PolicyT()
-        d.kind, d.obs_dim, d.act_dim, d.latent_dim = self.KINDS[kind], obs_dim, act_dim, latent_dim
-        d.max_action, d.phi = float(max_action), float(phi)
-        _gemv_net(d.net[0], net0)
-        if net1 is not None:
-            _gemv_net(d.net[1], net1)
+        d = _policy_desc(kind, obs_dim, act_dim, net0, max_action, net1, latent_dim, phi)
         self._keep = (net0, net1)  # the descriptors hold the parameter views alive
         self.kind, self.obs_dim, self.act_dim, self.seed = kind, obs_dim, act_dim, int(seed)
         self.noise_dim = {"mlp": 0, "gauss": act_dim, "bcq": latent_dim}[kind]
-        lib = L.load()
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            L.check(lib.osrl_policy_create(C.byref(d), C.byref(h)), "osrl_policy_create")
-        self._h, self._lib = h, lib
+        lib = self._open(device, "osrl_policy_create", C.byref(d))
         ptrs = [C.POINTER(C.c_float)() for _ in range(4)]
-        L.check(lib.osrl_policy_io(h, *[C.byref(p) for p in ptrs]), "osrl_policy_io")
+        L.check(lib.osrl_policy_io(self._h, *[C.byref(p) for p in ptrs]), "osrl_policy_io")
         R = L.POLICY_MAX_ROWS
         view = lambda p, shape: np.ctypeslib.as_array(p, shape=shape)  # noqa: E731  numpy views of PINNED memory
         self.obs = view(ptrs[0], (R, obs_dim))
@@ -76,16 +137,6 @@ class FastPolicy:
         self._act1, self._obs1, self._lp1 = self.act_out[0], self.obs[0], self.logp_out[0:1].reshape(())
         self._fn = lib.osrl_policy_act
         self._gauss = kind == "gauss"
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-    # The handle wraps a ctypes pointer to a pinned, device-mapped block: it cannot be copied or pickled.  A copied /
-    # unpickled model simply has no fast policy yet and builds its own on its first act() (the models test `_fast is None`).
-    def __deepcopy__(self, memo):
-        return None
-
-    def __reduce__(self):
-        return (type(None), ())
 
     def act1(self, obs, deterministic: bool = True):
         """The hot call of the episode loop: ONE observation [obs_dim], no explicit noise.  Everything a call does on
@@ -125,30 +176,8 @@ class FastPolicy:
             return self._act1.copy(), (self.logp_out[0].copy() if self.kind == "gauss" else None)
         return self.act_out[:rows].copy(), (self.logp_out[:rows].copy() if self.kind == "gauss" else None)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            self._lib.osrl_policy_destroy(self._h)
-            self._h = None
 
-    def __del__(self):  # pragma: no cover - interpreter shutdown order
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-MAX_ENVS = L.POLICY_MAX_ENVS
-
-
-def _vec_args(num_envs) -> int:
-    if isinstance(num_envs, bool) or not isinstance(num_envs, (int, np.integer)):
-        raise ValueError(f"num_envs must be an integer from 1 to {MAX_ENVS}, got {num_envs!r}")
-    if not 1 <= int(num_envs) <= MAX_ENVS:
-        raise ValueError(f"num_envs {int(num_envs)} is outside 1 .. {MAX_ENVS} (OSRL_POLICY_MAX_ENVS)")
-    return int(num_envs)
-
-
-class VecFastPolicy:
+class VecFastPolicy(PinnedHandle):
     """``num_envs`` episodes of one policy on as many host environments, in lockstep: ``reset`` starts episodes and
     ``step`` advances them, one C call each for all slots.  Same kinds and descriptors as ``FastPolicy``.  A slot's
     action is the same bits whatever ``num_envs`` is, whichever slot it is and whatever the other slots hold.
@@ -160,28 +189,21 @@ class VecFastPolicy:
     policy's seed, the slot's episode id and its step within the episode only, so an episode replays identically in any
     slot of a policy of any width."""
 
-    KINDS = FastPolicy.KINDS
+    KINDS = KINDS
+    DESTROY = "osrl_policy_destroy_n"
+    LIMIT = (MAX_ENVS, "OSRL_POLICY_MAX_ENVS")
 
     def __init__(self, kind: str, device, obs_dim: int, act_dim: int, net0: NetDesc, max_action: float = 1.0,
                  net1: Optional[NetDesc] = None, latent_dim: int = 0, phi: float = 0.0, seed: int = 0,
                  num_envs: int = 1):
-        N = self.num_envs = _vec_args(num_envs)
+        N = self.num_envs = _vec_args(num_envs, *self.LIMIT)
         require_cuda(device)
-        self.device = torch.device(device)
-        d = L.PolicyT()
-        d.kind, d.obs_dim, d.act_dim, d.latent_dim = self.KINDS[kind], obs_dim, act_dim, latent_dim
-        d.max_action, d.phi = float(max_action), float(phi)
-        _gemv_net(d.net[0], net0)
-        if net1 is not None:
-            _gemv_net(d.net[1], net1)
+        d = _policy_desc(kind, obs_dim, act_dim, net0, max_action, net1, latent_dim, phi)
         self._keep = (net0, net1)  # the descriptors hold the parameter views alive
         self.kind, self.obs_dim, self.act_dim, self.seed = kind, obs_dim, act_dim, int(seed)
         self.noise_dim = {"mlp": 0, "gauss": act_dim, "bcq": latent_dim}[kind]
-        lib = L.load()
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            L.check(lib.osrl_policy_create_n(C.byref(d), N, C.byref(h)), "osrl_policy_create_n")
-        self._h, self._lib = h, lib
+        lib = self._open(device, "osrl_policy_create_n", C.byref(d), N)
+        h = self._h
         fp = [C.POINTER(C.c_float)() for _ in range(4)]
         ip = [C.POINTER(C.c_int32)() for _ in range(2)]
         L.check(lib.osrl_policy_io_n(h, *[C.byref(p) for p in fp + ip]), "osrl_policy_io_n")
@@ -193,17 +215,6 @@ class VecFastPolicy:
         self._active = view(ip[0], (N,))
         self._meta = view(ip[1], (N, 2))  # (episode id, step) of each slot
         self._started = False
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-    __deepcopy__ = FastPolicy.__deepcopy__
-    __reduce__ = FastPolicy.__reduce__
-
-    def _rows(self, name, x, tail, dtype=None) -> np.ndarray:
-        want = (self.num_envs,) + tail
-        if np.shape(x) != want:  # numpy would broadcast silently
-            raise ValueError(f"expected {name} of shape {want}, got {np.shape(x)}")
-        return np.asarray(x, dtype=dtype)
 
     def _checked(self, obs, active, noise):
         obs = self._rows("obs", obs, (self.obs_dim,))
@@ -264,21 +275,11 @@ class VecFastPolicy:
         self._meta[slice(None) if active is None else active, 1] += 1
         return self._call(obs, active, noise, deterministic)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            self._lib.osrl_policy_destroy_n(self._h)
-            self._h = None
 
-    def __del__(self):  # pragma: no cover - interpreter shutdown order
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def cached_vec_policy(model, num_envs, make):
-    """``model``'s ``VecFastPolicy`` of width ``num_envs`` (one per width, built by ``make(num_envs)`` on first use)."""
-    N = _vec_args(num_envs)
+def cached_vec_policy(model, num_envs, make, limit=VecFastPolicy.LIMIT):
+    """``model``'s lockstep policy of width ``num_envs`` (one per width, built by ``make(num_envs)`` on first use);
+    ``limit``: the policy class's ``LIMIT``."""
+    N = _vec_args(num_envs, *limit)
     cache = model.__dict__.setdefault("_fast_vec", {})
     if cache.get(N) is None:  # (None: the slot of a copied / unpickled model)
         cache[N] = make(N)

@@ -19,10 +19,9 @@ import ctypes as C
 from typing import Dict, Optional, Tuple
 
 import numpy as np
-import torch
 
 from .. import _lib as L
-from .core import cur_stream
+from .act import PinnedHandle, _vec_args
 
 MAX_TOKENS, MAX_E, MAX_HEAD_DIM = 256, 512, 128
 MAX_ENVS = L.CDT_POLICY_MAX_ENVS
@@ -86,39 +85,44 @@ def _descriptor(m) -> Tuple["L.CdtPolicyT", object]:
     return d, layers
 
 
-class CDTFastPolicy:
-    def __init__(self, model):
+class _CDTHandle(PinnedHandle):
+    """What the one-episode and the lockstep policy share: the handle of ``model`` and the window read-back."""
+
+    DESTROY = "osrl_cdt_policy_destroy"
+
+    def _create(self, model, entry: str, *width):
         why = unsupported(model)
         if why is not None:
             raise NotImplementedError("the CDT act latency path does not support: " + why)
         m = self.model = model
-        self.device = torch.device(m.device)
         d, layers = _descriptor(m)
-        lib = L.load()
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            L.check(lib.osrl_cdt_policy_create(C.byref(d), layers, C.byref(h)), "osrl_cdt_policy_create")
-        self._h, self._lib = h, lib
+        lib = self._open(m.device, entry, C.byref(d), layers, *width)
+        self.od, self.ad, self.T = m.state_dim, m.action_dim, m.seq_len
+        self._t, self._episode_len = -1, 0
+        return lib
+
+    def _window(self, entry: str, *env) -> Dict[str, np.ndarray]:
+        T, od, ad = self.T, self.od, self.ad
+        s, a = np.zeros((T, od), np.float32), np.zeros((T, ad), np.float32)
+        r, c, ts = np.zeros(T, np.float32), np.zeros(T, np.float32), np.zeros(T, np.int64)
+        n = C.c_int32(0)
+        f = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+        L.check(getattr(self._lib, entry)(self._h, *env, f(s), f(a), f(r), f(c), f(ts), C.byref(n), self._stream()),
+                entry)
+        k = n.value
+        return dict(states=s[:k].copy(), actions=a[:k].copy(), returns=r[:k].copy(), costs=c[:k].copy(),
+                    time_steps=ts[:k].copy())
+
+
+class CDTFastPolicy(_CDTHandle):
+    def __init__(self, model):
+        lib = self._create(model, "osrl_cdt_policy_create")
         ptrs = [C.POINTER(C.c_float)() for _ in range(3)]
-        L.check(lib.osrl_cdt_policy_io(h, *[C.byref(p) for p in ptrs]), "osrl_cdt_policy_io")
-        od, ad = m.state_dim, m.action_dim
-        self.od, self.ad, self.T = od, ad, m.seq_len
+        L.check(lib.osrl_cdt_policy_io(self._h, *[C.byref(p) for p in ptrs]), "osrl_cdt_policy_io")
+        od, ad = self.od, self.ad
         self._obs = np.ctypeslib.as_array(ptrs[0], shape=(od,))  # numpy views of PINNED memory
         self._act_in = np.ctypeslib.as_array(ptrs[1], shape=(ad,))
         self._act_out = np.ctypeslib.as_array(ptrs[2], shape=(ad,))
-        self._t, self._episode_len = -1, 0
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-    # a pinned, device-mapped block behind a ctypes pointer: not copyable; a copied / unpickled model builds its own
-    def __deepcopy__(self, memo):
-        return None
-
-    def __reduce__(self):
-        return (type(None), ())
-
-    def _stream(self):
-        return self._raw_stream(self._dev_index) if self._raw_stream is not None else cur_stream()
 
     def _put_obs(self, obs) -> None:
         if np.shape(obs) != self._obs.shape:  # numpy would broadcast a scalar silently
@@ -162,38 +166,10 @@ class CDTFastPolicy:
 
     def window(self) -> Dict[str, np.ndarray]:
         """numpy copies of the current window (oldest timestep first), as the model saw it for the last action."""
-        T, od, ad = self.T, self.od, self.ad
-        s, a = np.zeros((T, od), np.float32), np.zeros((T, ad), np.float32)
-        r, c, ts = np.zeros(T, np.float32), np.zeros(T, np.float32), np.zeros(T, np.int64)
-        n = C.c_int32(0)
-        f = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        L.check(self._lib.osrl_cdt_policy_window(self._h, f(s), f(a), f(r), f(c), f(ts), C.byref(n), self._stream()),
-                "osrl_cdt_policy_window")
-        k = n.value
-        return dict(states=s[:k].copy(), actions=a[:k].copy(), returns=r[:k].copy(), costs=c[:k].copy(),
-                    time_steps=ts[:k].copy())
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            self._lib.osrl_cdt_policy_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover - interpreter shutdown order
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._window("osrl_cdt_policy_window")
 
 
-def _vec_args(num_envs) -> int:
-    if isinstance(num_envs, bool) or not isinstance(num_envs, (int, np.integer)):
-        raise ValueError(f"num_envs must be an integer from 1 to {MAX_ENVS}, got {num_envs!r}")
-    if not 1 <= int(num_envs) <= MAX_ENVS:
-        raise ValueError(f"num_envs {int(num_envs)} is outside 1 .. {MAX_ENVS} (OSRL_CDT_POLICY_MAX_ENVS)")
-    return int(num_envs)
-
-
-class CDTVecFastPolicy:
+class CDTVecFastPolicy(_CDTHandle):
     """``num_envs`` episodes on as many host environments, in lockstep: all slots share the timestep, ``reset`` starts
     all of them and ``step`` advances all of them with one C call.  A slot's actions are those a ``CDTFastPolicy`` returns
     for the same inputs, bit for bit, whatever ``num_envs`` is.
@@ -202,40 +178,18 @@ class CDTVecFastPolicy:
     action`` are not read and its row of the result is zero.  Its device rows keep running on the stale inputs of its
     last active step (lockstep: the launches cover every slot); nothing of that reaches the other slots."""
 
+    LIMIT = (MAX_ENVS, "OSRL_CDT_POLICY_MAX_ENVS")
+
     def __init__(self, model, num_envs: int):
-        N = self.num_envs = _vec_args(num_envs)
-        why = unsupported(model)
-        if why is not None:
-            raise NotImplementedError("the CDT act latency path does not support: " + why)
-        m = self.model = model
-        self.device = torch.device(m.device)
-        d, layers = _descriptor(m)
-        lib = L.load()
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            L.check(lib.osrl_cdt_policy_create_n(C.byref(d), layers, N, C.byref(h)), "osrl_cdt_policy_create_n")
-        self._h, self._lib = h, lib
+        N = self.num_envs = _vec_args(num_envs, *self.LIMIT)
+        lib = self._create(model, "osrl_cdt_policy_create_n", N)
         ptrs = [C.POINTER(C.c_float)() for _ in range(4)]
-        L.check(lib.osrl_cdt_policy_io_n(h, *[C.byref(p) for p in ptrs]), "osrl_cdt_policy_io_n")
-        od, ad = m.state_dim, m.action_dim
-        self.od, self.ad, self.T = od, ad, m.seq_len
+        L.check(lib.osrl_cdt_policy_io_n(self._h, *[C.byref(p) for p in ptrs]), "osrl_cdt_policy_io_n")
+        od, ad = self.od, self.ad
         self._obs = np.ctypeslib.as_array(ptrs[0], shape=(N, od))  # numpy views of PINNED memory
         self._act_in = np.ctypeslib.as_array(ptrs[1], shape=(N, ad))
         self._act_out = np.ctypeslib.as_array(ptrs[2], shape=(N, ad))
         self._scalars = np.ctypeslib.as_array(ptrs[3], shape=(N, 4))  # reward, cost, target_return, target_cost
-        self._t, self._episode_len = -1, 0
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-    __deepcopy__ = CDTFastPolicy.__deepcopy__
-    __reduce__ = CDTFastPolicy.__reduce__
-    _stream = CDTFastPolicy._stream
-
-    def _rows(self, name, x, tail) -> np.ndarray:
-        want = (self.num_envs,) + tail
-        if np.shape(x) != want:  # numpy would broadcast silently
-            raise ValueError(f"expected {name} of shape {want}, got {np.shape(x)}")
-        return np.asarray(x)
 
     def _target(self, name, x) -> np.ndarray:
         if np.ndim(x) != 0 and np.shape(x) != (self.num_envs,):
@@ -303,21 +257,4 @@ class CDTVecFastPolicy:
         """numpy copies of slot ``env``'s current window (oldest timestep first)."""
         if not 0 <= int(env) < self.num_envs:
             raise ValueError(f"env {env} is outside 0 .. {self.num_envs - 1}")
-        T, od, ad = self.T, self.od, self.ad
-        s, a = np.zeros((T, od), np.float32), np.zeros((T, ad), np.float32)
-        r, c, ts = np.zeros(T, np.float32), np.zeros(T, np.float32), np.zeros(T, np.int64)
-        n = C.c_int32(0)
-        f = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        L.check(self._lib.osrl_cdt_policy_window_n(self._h, int(env), f(s), f(a), f(r), f(c), f(ts), C.byref(n),
-                                                   self._stream()), "osrl_cdt_policy_window_n")
-        k = n.value
-        return dict(states=s[:k].copy(), actions=a[:k].copy(), returns=r[:k].copy(), costs=c[:k].copy(),
-                    time_steps=ts[:k].copy())
-
-    close = CDTFastPolicy.close
-
-    def __del__(self):  # pragma: no cover - interpreter shutdown order
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._window("osrl_cdt_policy_window_n", int(env))
