@@ -1110,9 +1110,20 @@ int osrl_cdt_policy_io_n(void* handle, float** obs, float** act_in, float** act_
 int osrl_cdt_policy_reset_n(void* handle, void* stream);
 /* as _step for every episode: reward and cost from scalars[e][0..1] (scalars[e][2..3] must keep the targets) */
 int osrl_cdt_policy_step_n(void* handle, int32_t host_action, void* stream);
-/* as _window, of episode env (0 <= env < n_env, else -1) */
+/* as _window, of episode env (0 <= env < n_env, else -1), at that episode's own timestep */
 int osrl_cdt_policy_window_n(void* handle, int32_t env, float* states, float* actions, float* returns, float* costs,
                              int64_t* time_steps, int32_t* n, void* stream);
+/* Slots at INDEPENDENT timesteps: one call in which every episode idles (mode[e] = 0), steps (1) or restarts (2), still
+ * 2 + 5 * layers launches.  A restarting episode begins at timestep 0 from obs[e] and scalars[e][2..3] (the prefix token
+ * is embedded again); a stepping one reads scalars[e][0..1] and, with host_action = 1, act_in[e]; an idle one runs no
+ * rows, keeps its window and timestep and can be continued by a later call, and its row of act_out is not written.
+ * Every episode contributes the rows of its own phase (the host derives them per call from the episodes' timesteps), so
+ * an episode's results are the bits the one-episode handle returns for the same inputs, whatever the others do.
+ * _reset_n is this call with every mode 2, _step_n with every mode 1.  Returns -1, and changes nothing, if a stepping
+ * episode was never started or is past the timestep table, or on a mode outside 0 .. 2; 0 at once if all idle. */
+int osrl_cdt_policy_step_slots(void* handle, const int32_t* mode, int32_t host_action, void* stream);
+/* t [n_env]: the timestep of each episode's newest window entry, -1 = never started */
+int osrl_cdt_policy_timesteps(void* handle, int32_t* t);
 
 /* ---- data-parallel exchanges through IPC-mapped device buffers (ipc.hip, round 6; nothing to mirror in the reference: it
  * has no distributed code).  What the ranks of a data-parallel step exchange (flat

@@ -218,6 +218,8 @@ PROTOTYPES = {
     "osrl_cdt_policy_reset_n": [_vp, _vp],
     "osrl_cdt_policy_step_n": [_vp, _i32, _vp],
     "osrl_cdt_policy_window_n": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "osrl_cdt_policy_step_slots": [_vp, _P(_i32), _i32, _vp],
+    "osrl_cdt_policy_timesteps": [_vp, _P(_i32)],
     "osrl_cost_sample_prob": [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp],
     "osrl_start_index_prob": [_vp, _vp, _vp, _i32, C.c_double, _vp, _vp, _vp],
     "osrl_bc_select": [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp],

@@ -92,12 +92,16 @@ class RolloutMixin:
     def _scale_results(self, r, c, n):
         return r / self.reward_scale, c / self.cost_scale, n
 
-    def evaluate(self, eval_episodes):
+    def evaluate(self, eval_episodes, schedule: str = "waves"):
         """The reference's ``evaluate``: (mean return, mean cost, mean length).  With a ``VecSyntheticSafeEnv`` as
         ``self.env`` the episodes run as one batch on device (engine/rollout.py); a list or tuple of N host (gym-style)
         environments runs episode ``q`` on environment ``q % N``, N at a time in lockstep (``rollout_many``); any other
-        (gym-style) env takes the reference's episode-by-episode loop."""
+        (gym-style) env takes the reference's episode-by-episode loop.  ``schedule`` matters for a list of environments
+        only: "waves" (default) starts N episodes and waits for the longest; "refill" gives a slot whose episode ended
+        the next episode at once (``rollout_jobs``)."""
         from ..common.synthetic_env import VecSyntheticSafeEnv
+        from ..engine.act import check_schedule
+        check_schedule(schedule)
         self._before_evaluate()
         if isinstance(self.env, VecSyntheticSafeEnv):
             from ..engine.rollout import evaluate_batched
@@ -105,7 +109,9 @@ class RolloutMixin:
             return self._scale_results(*evaluate_batched(self, self.EVAL_KIND, eval_episodes,
                                                          1.0 if cs is None else cs, self._eval_extra()))
         if isinstance(self.env, (list, tuple)):
-            from ..engine.act import evaluate_lockstep
+            from ..engine.act import evaluate_lockstep, evaluate_refill
+            if schedule == "refill":
+                return self._scale_results(*evaluate_refill(self, eval_episodes))
             return self._scale_results(*evaluate_lockstep(self, eval_episodes))
         self.model.eval()
         rets, costs, lens = [], [], []
@@ -127,6 +133,17 @@ class RolloutMixin:
         ``multi-task`` mode appends the cost limit to every observation (``_eval_extra``)."""
         from ..engine.act import rollout_lockstep
         return rollout_lockstep(self.model, envs, num_slots, episode_ids, cost_scale=self._cost_scale(),
+                                append=self._eval_extra())
+
+    @torch.no_grad()
+    def rollout_jobs(self, envs, num_jobs, episode_ids=None):
+        """``num_jobs`` episodes over the host environments ``envs`` on the refill schedule (engine/act.py
+        ``rollout_refill``): job ``q`` starts in slot ``q`` while slots are free, and a slot whose episode has ended takes
+        the next job in the policy call in which the others step.  Returns a ``RefillResult``: per job (return, length,
+        cost sum) and the slot it ran in, and the number of policy calls.  Job ``q`` has episode id ``episode_ids[q]``
+        (default ``q``) and equals that episode run alone through ``rollout_many`` on the same environment."""
+        from ..engine.act import rollout_jobs_mlp
+        return rollout_jobs_mlp(self.model, envs, num_jobs, episode_ids, cost_scale=self._cost_scale(),
                                 append=self._eval_extra())
 
     @torch.no_grad()

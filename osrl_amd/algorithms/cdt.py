@@ -295,13 +295,16 @@ class CDTTrainer:
         keys = None if self.stochastic else ["all_loss", "act_loss", "cost_loss", "cost_acc", "state_loss", "train_lr"]
         store_stats(self.logger, eng.st, self.stats_mode, tab="train", keys=keys)
 
-    def evaluate(self, num_rollouts, target_return, target_cost):
+    def evaluate(self, num_rollouts, target_return, target_cost, schedule: str = "waves"):
         """cdt.py:420-434.  With a ``VecSyntheticSafeEnv`` as ``self.env`` the ``num_rollouts`` episodes run as one
         batch on device (engine/rollout.py ``CDTBatchedRollout``).  With a list or tuple of N host environments rollout
-        ``j`` runs on environment ``j % N``, N rollouts at a time in lockstep (``rollout_many``)."""
+        ``j`` runs on environment ``j % N``, N rollouts at a time in lockstep (``rollout_many``), or with
+        ``schedule="refill"`` as one job queue (``evaluate_targets``)."""
         from ..common.synthetic_env import VecSyntheticSafeEnv
+        from ..engine.act import check_schedule
+        check_schedule(schedule)
         if isinstance(self.env, (list, tuple)):
-            return self.evaluate_targets(num_rollouts, [(target_return, target_cost)])[0]
+            return self.evaluate_targets(num_rollouts, [(target_return, target_cost)], schedule=schedule)[0]
         if isinstance(self.env, VecSyntheticSafeEnv):
             from ..engine.rollout import CDTBatchedRollout
             if self.env.E != num_rollouts:
@@ -363,12 +366,15 @@ class CDTTrainer:
                 break
         return ep_ret, ep_len, ep_cost
 
-    def evaluate_targets(self, num_rollouts, targets):
+    def evaluate_targets(self, num_rollouts, targets, schedule: str = "waves"):
         """``evaluate`` for each ``(target_return, target_cost)`` pair of ``targets``: a list of ``(return, cost,
         length)`` triples.  With a list or tuple of N host environments as ``self.env`` the ``len(targets) *
         num_rollouts`` rollouts are laid out target-major and job ``q`` runs in wave ``q // N`` on environment
         ``q % N``, so rollouts for different targets share a wave; with any other environment this is one
-        ``evaluate`` per pair."""
+        ``evaluate`` per pair.  ``schedule="refill"`` (list of environments): the same jobs as one queue, where a slot
+        whose episode has ended takes the next job at once (``rollout_jobs``; the run is kept as ``last_refill``)."""
+        from ..engine.act import check_schedule
+        check_schedule(schedule)
         targets = [(float(tr), float(tc)) for tr, tc in targets]
         if not isinstance(self.env, (list, tuple)):
             return [self.evaluate(num_rollouts, tr, tc) for tr, tc in targets]
@@ -379,13 +385,17 @@ class CDTTrainer:
         jobs = [t for t in targets for _ in range(int(num_rollouts))]
         self.model.eval()
         rets, lens, costs = [], [], []
-        for q0 in range(0, len(jobs), N):
-            wave = jobs[q0:q0 + N]
-            r, l, c = self.rollout_many(self.model, envs[:len(wave)], [t[0] for t in wave], [t[1] for t in wave],
-                                        num_slots=N)
-            rets += list(r)
-            lens += list(l)
-            costs += list(c)
+        if schedule == "refill":
+            res = self.last_refill = self.rollout_jobs(self.model, envs, [t[0] for t in jobs], [t[1] for t in jobs])
+            rets, lens, costs = list(res.returns), list(res.lengths), list(res.costs)
+        else:
+            for q0 in range(0, len(jobs), N):
+                wave = jobs[q0:q0 + N]
+                r, l, c = self.rollout_many(self.model, envs[:len(wave)], [t[0] for t in wave], [t[1] for t in wave],
+                                            num_slots=N)
+                rets += list(r)
+                lens += list(l)
+                costs += list(c)
         self.model.train()
         out, k = [], int(num_rollouts)
         for i in range(len(targets)):
@@ -443,6 +453,31 @@ class CDTTrainer:
             act = pol.step(obs, reward, cost, active=active)
         return np.asarray(ep_ret), ep_len, np.asarray(ep_cost)
 
+    @torch.no_grad()
+    def rollout_jobs(self, model: CDT, envs, target_returns, target_costs):
+        """One rollout per ``(target_returns[q], target_costs[q])`` over the host environments ``envs`` on the refill
+        schedule (engine/act.py ``rollout_refill``): job ``q`` starts in slot ``q`` while slots are free, and a slot
+        whose episode has ended takes the next job in the policy call in which the others step
+        (``CDTVecFastPolicy.step(restart=...)``).  Returns a ``RefillResult``: per job (return, length, raw cost sum),
+        each equal to ``rollout`` alone on the job's environment in that environment's job order, the slot (environment)
+        each job ran in, and the number of policy calls.  Without ``fast_rollout`` or an eligible model job ``q`` runs
+        through ``rollout`` on environment ``q % len(envs)`` (no policy calls are counted)."""
+        from ..engine.act import RefillResult, rollout_refill
+        envs = list(envs)
+        trs, tcs = np.asarray(target_returns, dtype=np.float64), np.asarray(target_costs, dtype=np.float64)
+        if trs.ndim != 1 or trs.shape != tcs.shape:
+            raise ValueError(f"expected target_returns and target_costs as two lists of one length, got shapes "
+                             f"{trs.shape} and {tcs.shape}")
+        J, N = len(trs), len(envs)
+        if J and N == 0:
+            raise ValueError("jobs over an empty list of environments")
+        if J and not (self.fast_rollout and model.fast_eligible()):
+            out = [self.rollout(model, envs[q % N], float(trs[q]), float(tcs[q])) for q in range(J)]
+            return RefillResult(np.asarray([o[0] for o in out]), np.asarray([o[1] for o in out], np.int64),
+                                np.asarray([o[2] for o in out]), np.arange(J) % N, 0)
+        adapter = _CDTRefillAdapter(self, model, N) if J else None
+        return rollout_refill(adapter, envs, list(zip(trs.tolist(), tcs.tolist())), model.episode_len)
+
     def _rollout_fast(self, model: CDT, env, target_return: float, target_cost: float):
         pol = model.fast_policy()
         obs, info = env.reset()
@@ -459,3 +494,26 @@ class CDTTrainer:
                 break
             act = pol.step(obs_next, reward, cost)
         return ep_ret, ep_len, ep_cost
+
+
+class _CDTRefillAdapter:
+    """engine/act.py ``rollout_refill`` over ``CDT.fast_policy(num_envs)``: a job is a ``(target_return, target_cost)``
+    pair."""
+
+    def __init__(self, trainer: CDTTrainer, model: CDT, num_envs: int):
+        self.pol = model.fast_policy(num_envs=num_envs)
+        self.obs_dim, self.N = model.state_dim, num_envs
+        self.reverse, self.scale = trainer.cost_reverse, trainer.cost_scale
+
+    def observe(self, o):
+        return o
+
+    def costs(self, info):
+        return ((1.0 - info["cost"]) if self.reverse else info["cost"]) * self.scale, info["cost"]
+
+    def act(self, obs, reward, cost, step, restart, jobs):
+        tr, tc = np.zeros(self.N, np.float64), np.zeros(self.N, np.float64)
+        for e, j in enumerate(jobs):
+            if j is not None:
+                tr[e], tc[e] = j
+        return self.pol.step(obs, reward, cost, active=step, restart=restart, target_return=tr, target_cost=tc)

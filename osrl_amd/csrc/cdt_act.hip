@@ -1,5 +1,5 @@
 // cdt_act.hip -- the act latency path of the Constrained Decision Transformer's episode loop on gfx950: one episode
-// per handle (B = 1), or N episodes advanced in lockstep by the same launches.
+// per handle (B = 1), or N episodes advanced by the same launches, in lockstep or each slot at its own timestep.
 //
 // CDTTrainer.rollout (cdt.py:436-518) asks the model for one action per env step over a sliding window of the last
 // seq_len timesteps.  Run as a training-shaped forward that is ~30 launches over a window padded to seq_len plus a
@@ -19,10 +19,23 @@
 // weights PF[k/4][n][k%4] (the copies the fused AdamW step and repack() keep current), split-K over the four waves
 // of a workgroup and summed in LDS in a fixed order: results do not depend on scheduling.
 // A handle of N episodes (osrl_cdt_policy_create_n) keeps N such windows, one per-episode block of `es` floats each in
-// the handle's device allocation.  The episodes share the timestep, hence the phase and every row set, so a step is the
-// SAME 2 + 5 * layers launches: ingest and head run one workgroup per episode, attention one wave per (row, head,
-// episode), and a projection's row list is the concatenation over the episodes, so that its 16-row tiles fill up with
-// rows of several episodes.  No arithmetic crosses rows: an episode's results do not depend on N or on its slot.
+// the handle's device allocation.  A step is the SAME 2 + 5 * layers launches: ingest and head run one workgroup per
+// episode, attention one wave per (row, head, episode), and a projection's row list is the concatenation over the
+// episodes, so that its 16-row tiles fill up with rows of several episodes.  No arithmetic crosses rows: an episode's
+// results do not depend on N, on its slot or on what the other slots are doing.
+// While the episodes share the timestep (lockstep: _reset_n / _step_n on slots that all stand at the same t) they share
+// the phase and every row set, and the launches take one (first, count, ring) per stage from their arguments.  When they
+// do not (osrl_cdt_policy_step_slots: a slot restarts or idles while the others step) every episode contributes the rows
+// of ITS phase -- restart: R - 1 rows + the prefix row; growth: the previous action token + the new tokens; sliding:
+// layer-0 q / k / v of the new rows, the whole window from there on; idle: nothing -- and the launches take them from a
+// per-call TABLE the host derives (it knows every slot's timestep): per episode its mode, timestep, window start and
+// newest state row, and per row-set class (new rows / rows past layer-0 q k v / newest state token) the episode's
+// (first, count, ring) and the exclusive prefix sum of the counts.  The host writes the table into a segment of the
+// pinned block, the ingest launch copies each episode's entries to device memory, the later launches read that copy;
+// a call returns only after publication, so the host never rewrites the table under a running chain.  A projection maps
+// entry g of its row list to (episode, local row) by one ballot + popcount over the prefix sums; attention's grid x is
+// the largest count and workgroups past their episode's count exit at once.  Grids are sized by the totals: an idle
+// slot costs no rows.
 #include <math.h>
 
 #include <new>
@@ -37,6 +50,13 @@ namespace {
 
 constexpr int kMaxE = 512, kMaxD = 128, kMaxTok = 256, kMaxHead = 1024;
 constexpr float kLnEps = 1e-5f;
+
+// the per-call table of a call whose episodes are at different timesteps: int32 [kTabFields][kTabStride], entry
+// [field][episode].  Row-set class c (0: the rows whose embedding is new; 1: the rows through the layers past layer-0
+// q / k / v; 2: the newest state token) has its first / count / ring / exclusive count prefix at kTabSet + 4 c ...
+constexpr int kTabStride = OSRL_CDT_POLICY_MAX_ENVS;
+constexpr int kTabMode = 0, kTabT = 1, kTabWs = 2, kTabSrow = 3, kTabSet = 4, kTabFields = 16;
+constexpr int kIdle = 0, kStep = 1, kRestart = 2;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -101,18 +121,32 @@ struct IngestArgs {
   int32_t ldE, R, TR, t, reset, host_action;
   int32_t first, count, ring;  // token rows to embed
   int64_t es;                  // floats per episode block (grid: one workgroup per episode)
+  const int32_t* htab;         // the call's table in the pinned block, or null: t / reset / rows above serve every episode
+  int32_t* dtab;               // its device copy, for the later launches
 };
 
 __global__ __launch_bounds__(256) void cdt_act_ingest_kernel(const IngestArgs a) {
   const osrl_cdt_policy_t& p = a.p;
   const int tid = threadIdx.x, T = p.seq_len, od = p.state_dim, ad = p.action_dim;
-  const int cur = a.t % T;
+  int t = a.t, reset = a.reset, first = a.first, count = a.count, ring = a.ring;
+  if (a.htab) {  // this episode's own timestep, mode and rows
+    const int32_t* __restrict__ ht = a.htab + blockIdx.x;
+    if (tid < kTabFields) a.dtab[tid * kTabStride + blockIdx.x] = ht[tid * kTabStride];
+    const int mode = ht[kTabMode * kTabStride];
+    if (mode == kIdle) return;
+    t = ht[kTabT * kTabStride];
+    reset = mode == kRestart;
+    first = ht[kTabSet * kTabStride];
+    count = ht[(kTabSet + 1) * kTabStride];
+    ring = ht[(kTabSet + 2) * kTabStride];
+  }
+  const int cur = t % T;
   const size_t eoff = (size_t)blockIdx.x * (size_t)a.es;
   const Dev d = dev_at(a.d, eoff);
   const Io io{a.io.obs + (size_t)blockIdx.x * od, a.io.act_in + (size_t)blockIdx.x * ad, nullptr,
               a.io.scalars + (size_t)blockIdx.x * 4, nullptr};
   float* __restrict__ x0 = a.x0 + eoff;
-  if (a.reset) {
+  if (reset) {
     for (int i = tid; i < od; i += blockDim.x) d.win_s[i] = io.obs[i];
     if (tid == 0) {
       d.win_r[0] = io.scalars[2];
@@ -120,21 +154,21 @@ __global__ __launch_bounds__(256) void cdt_act_ingest_kernel(const IngestArgs a)
       d.win_t[0] = 0;
     }
   } else {
-    const int prv = (a.t - 1) % T;
+    const int prv = (t - 1) % T;
     for (int i = tid; i < ad && T > 1; i += blockDim.x)  // (seq_len 1: the previous timestep left the window)
       d.win_a[prv * ad + i] = a.host_action ? io.act_in[i] : d.last_act[i];
     for (int i = tid; i < od; i += blockDim.x) d.win_s[cur * od + i] = io.obs[i];
     if (tid == 0) {  // returns[t+1] = returns[t] - float(reward); costs[t+1] = costs[t] - cost  (fp32, cdt.py:506-507)
       d.win_r[cur] = d.win_r[prv] - io.scalars[0];
       d.win_c[cur] = d.win_c[prv] - io.scalars[1];
-      d.win_t[cur] = a.t;
+      d.win_t[cur] = t;
     }
   }
   for (int i = tid; i < ad; i += blockDim.x) d.win_a[cur * ad + i] = 0.f;  // the newest action slot: zero dummy
   __syncthreads();
   const int lane = tid & 63, E = p.embedding_dim;
-  for (int i = tid >> 6; i < a.count; i += blockDim.x >> 6) {
-    const int row = ring_row(a.first, i, a.ring);
+  for (int i = tid >> 6; i < count; i += blockDim.x >> 6) {
+    const int row = ring_row(first, i, ring);
     const bool is_prefix = row == a.TR;
     const int ts = is_prefix ? 0 : row / a.R, slot = is_prefix ? 0 : row - ts * a.R;
     int which = slot + (4 - a.R);  // 0 return, 1 cost, 2 state, 3 action (cdt.py:185-200)
@@ -188,7 +222,9 @@ __global__ __launch_bounds__(256) void cdt_act_ingest_kernel(const IngestArgs a)
 // ---------------------------------------------------------------------------------------------------------------
 // Y[r] = epi(LN?(X[r]) W^T + b) for the rows of a row set: one workgroup = one 16-row x 16-column tile, four waves
 // split K and meet in LDS.  epi: optional exact GELU, then an optional residual add.  With nenv episodes the launch's
-// row list is the row set of episode 0, then of episode 1, ...: entry g is local row g % count of episode g / count.
+// row list is the row set of episode 0, then of episode 1, ...: entry g is local row g % count of episode g / count;
+// with a table (tab: the class's first / count / ring / prefix entries) the episodes' counts differ and entry g belongs
+// to the last episode whose prefix is <= g.
 struct LinArgs {
   const float* X;
   const float *ln_g, *ln_b;  // LayerNorm of the input rows (K = E) or null
@@ -201,6 +237,7 @@ struct LinArgs {
   int32_t nenv;
   int64_t es;    // floats per episode block (X, res and Y are episode 0's)
   uint64_t rcp;  // ceil(2^32 / count): g / count = (g * rcp) >> 32, exact for g < 2^16 and count <= 2^8
+  const int32_t* tab;  // or null.  With a table `count` is the total over the episodes; first / ring / rcp are unused
 };
 
 __global__ __launch_bounds__(256) void cdt_act_linear_kernel(const LinArgs a) {
@@ -210,7 +247,31 @@ __global__ __launch_bounds__(256) void cdt_act_linear_kernel(const LinArgs a) {
   __shared__ long long xo[16], ro[16], yo[16];  // float offsets of the tile's rows in X, res and Y
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int r0 = blockIdx.y * 16, n0 = blockIdx.x * 16;
-  if (tid < 16) {
+  if (a.tab) {
+    if (tid < 64) {  // wave 0: lane e holds episode e's prefix, lane i < 16 resolves tile row i
+      const int pv = tid < a.nenv ? a.tab[3 * kTabStride + tid] : 0x7fffffff;
+      int e = 0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const unsigned long long m = __ballot(pv <= r0 + i);  // (prefix[0] = 0: never empty)
+        if (tid == i) e = __popcll(m) - 1;
+      }
+      const int pe = __shfl(pv, e);
+      if (tid < 16) {
+        const int g = r0 + tid;
+        int r = -1;
+        long long eo = 0;
+        if (g < a.count) {
+          r = ring_row(a.tab[e], g - pe, a.tab[2 * kTabStride + e]);
+          eo = (long long)e * a.es;
+        }
+        rows[tid] = r;
+        xo[tid] = eo + (long long)r * a.ldx;
+        ro[tid] = eo + (long long)r * a.ldr;
+        yo[tid] = eo + (long long)r * a.ldy;
+      }
+    }
+  } else if (tid < 16) {
     const int g = r0 + tid;
     int r = -1;
     long long eo = 0;
@@ -304,7 +365,8 @@ __global__ __launch_bounds__(256) void cdt_act_linear_kernel(const LinArgs a) {
 struct AttnArgs {
   const float* qkv;  // [NR, ldq]: q | k | v
   float* o;          // [NR, ldo]
-  int32_t ldq, ldo, E, H, d, P, TR, ws;  // ws: ring row of the window's first token
+  const int32_t* tab;  // the call's table or null.  With a table `first` is the row-set class; ring and ws are unused
+  int32_t ldq, E, d, P, TR, ws;  // ws: ring row of the window's first token.  (o's row stride is round16(E))
   float scale;
   int32_t first, ring;  // query rows: grid x entries from `first` (mod ring)
   int32_t es;           // floats per episode block (grid z: episode).  (The struct stays within the 16 dwords a
@@ -313,10 +375,18 @@ struct AttnArgs {
 
 __global__ __launch_bounds__(64) void cdt_act_attn_kernel(const AttnArgs a) {
   __shared__ float pr[kMaxTok];
-  const int lane = threadIdx.x, h = blockIdx.y;
-  const int row = ring_row(a.first, blockIdx.x, a.ring);
+  const int lane = threadIdx.x, h = blockIdx.y, ldo = round16(a.E);
+  int first = a.first, ring = a.ring, ws = a.ws;
+  if (a.tab) {  // the query's episode's rows and window start; grid x covers the largest count
+    const int32_t* __restrict__ st = a.tab + (kTabSet + 4 * a.first) * kTabStride + blockIdx.z;
+    if ((int)blockIdx.x >= st[kTabStride]) return;
+    first = st[0];
+    ring = st[2 * kTabStride];
+    ws = a.tab[kTabWs * kTabStride + blockIdx.z];
+  }
+  const int row = ring_row(first, blockIdx.x, ring);
   // keys: the prefix (ring row TR) first, then the window's tokens up to and including the query
-  const int nk = row == a.TR ? 1 : a.P + (row - a.ws + a.TR) % a.TR + 1;
+  const int nk = row == a.TR ? 1 : a.P + (row - ws + a.TR) % a.TR + 1;
   const float* __restrict__ qkv = a.qkv + (size_t)blockIdx.z * (size_t)a.es;
   float* __restrict__ o = a.o + (size_t)blockIdx.z * (size_t)a.es;
   const float* __restrict__ q = qkv + (size_t)row * a.ldq + h * a.d;
@@ -327,7 +397,7 @@ __global__ __launch_bounds__(64) void cdt_act_attn_kernel(const AttnArgs a) {
     const int j = lane + 64 * c;
     s[c] = -INFINITY;
     if (j < nk) {
-      const int kr = j < a.P ? a.TR : (a.ws + j - a.P) % a.TR;
+      const int kr = j < a.P ? a.TR : (ws + j - a.P) % a.TR;
       const float* __restrict__ k = qkv + (size_t)kr * a.ldq + a.E + h * a.d;
       float acc = 0.f;
 #pragma unroll 8
@@ -353,10 +423,10 @@ __global__ __launch_bounds__(64) void cdt_act_attn_kernel(const AttnArgs a) {
     float acc = 0.f;
 #pragma unroll 4
     for (int j = 0; j < nk; ++j) {
-      const int kr = j < a.P ? a.TR : (a.ws + j - a.P) % a.TR;
+      const int kr = j < a.P ? a.TR : (ws + j - a.P) % a.TR;
       acc = fmaf(pr[j], qkv[(size_t)kr * a.ldq + 2 * a.E + h * a.d + i], acc);
     }
-    o[(size_t)row * a.ldo + h * a.d + i] = acc * inv;
+    o[(size_t)row * ldo + h * a.d + i] = acc * inv;
   }
 }
 
@@ -365,7 +435,8 @@ __global__ __launch_bounds__(64) void cdt_act_attn_kernel(const AttnArgs a) {
 // (lanes own outputs over the packed weights, as act.hip), clamp, publish.  One workgroup per episode; the sequence
 // number is published once, by the last workgroup to arrive at the handle's device counter: every workgroup makes its
 // act_out stores visible at system scope and then increments the counter; the one that sees nenv - 1 re-arms it and
-// does the release store.  Nobody waits for anybody.
+// does the release store.  Nobody waits for anybody.  With a table an idle episode's workgroup writes no action and
+// only arrives, so the sequence number is still published once.
 struct HeadArgs {
   osrl_cdt_policy_t p;
   Dev d;
@@ -376,7 +447,21 @@ struct HeadArgs {
   int64_t es;         // floats per episode block (grid: one workgroup per episode)
   uint32_t* arrived;  // device counter of the workgroups that have stored their action (0 between launches)
   int32_t nenv;
+  const int32_t* tab;  // the call's table or null.  With a table srow is the episode's own and crow < 0 means "none"
 };
+
+__device__ __forceinline__ void head_arrive(const HeadArgs& a) {  // by one thread, after the workgroup's stores
+  __threadfence_system();
+  bool last = a.nenv == 1;
+  if (!last) {
+    last = __hip_atomic_fetch_add(a.arrived, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)(a.nenv - 1);
+    if (last) {
+      __hip_atomic_store(a.arrived, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __threadfence_system();
+    }
+  }
+  if (last) __hip_atomic_store(a.io.seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 constexpr int kHeadThreads = 1024;
 
@@ -389,9 +474,18 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
   const size_t eoff = (size_t)blockIdx.x * (size_t)a.es;
   const float* __restrict__ x = a.x + eoff;
   const float* __restrict__ raw = a.d.raw + eoff;
+  int srow = a.srow, crow = a.crow;
+  if (a.tab) {
+    if (a.tab[kTabMode * kTabStride + blockIdx.x] == kIdle) {
+      if (tid == 0) head_arrive(a);
+      return;
+    }
+    srow = a.tab[kTabSrow * kTabStride + blockIdx.x];
+    crow = a.crow >= 0 ? srow - 1 : -1;  // the cost token precedes the state token (the cost features imply use_cost)
+  }
   if (tid < 64) {
     float mean, rstd;
-    row_stats(x + (size_t)a.srow * a.ldE, E, tid, &mean, &rstd);
+    row_stats(x + (size_t)srow * a.ldE, E, tid, &mean, &rstd);
     if (tid == 0) {
       st[0] = mean;
       st[1] = rstd;
@@ -402,9 +496,9 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
   for (int f = tid; f < kMaxHead; f += kHeadThreads) {
     float v = 0.f;
     if (f < E) {
-      v = (x[(size_t)a.srow * a.ldE + f] - st[0]) * st[1] * p.out_g[f] + p.out_b[f];
-      if (a.crow >= 0) {  // cdt.py:243-250, the detached (pre-LayerNorm) cost embedding
-        const float ce = raw[(size_t)a.crow * a.ldE + f];
+      v = (x[(size_t)srow * a.ldE + f] - st[0]) * st[1] * p.out_g[f] + p.out_b[f];
+      if (crow >= 0) {  // cdt.py:243-250, the detached (pre-LayerNorm) cost embedding
+        const float ce = raw[(size_t)crow * a.ldE + f];
         if (p.add_cost_feat) {
           v = v + ce;
           if (p.mul_cost_feat) v = v * ce;
@@ -413,7 +507,7 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
         }
       }
     } else if (f < Eh) {
-      v = raw[(size_t)a.crow * a.ldE + (f - E)];
+      v = raw[(size_t)crow * a.ldE + (f - E)];
     }
     buf[0][f] = v;
   }
@@ -473,18 +567,7 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
     a.d.last_act[eoff + tid] = v;
   }
   __syncthreads();
-  if (tid == 0) {
-    __threadfence_system();
-    bool last = a.nenv == 1;
-    if (!last) {
-      last = __hip_atomic_fetch_add(a.arrived, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)(a.nenv - 1);
-      if (last) {
-        __hip_atomic_store(a.arrived, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence_system();
-      }
-    }
-    if (last) __hip_atomic_store(a.io.seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if (tid == 0) head_arrive(a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -492,11 +575,13 @@ struct Handle {
   osrl_cdt_policy_t p;
   std::vector<osrl_cdt_layer_t> layers;
   int R, P, TR, NR, ldE, ld3, ld4;
-  int nenv;    // episodes advanced in lockstep
-  int64_t es;  // floats per episode block of dmem
-  int t;       // timestep of the newest window entry (every episode's); -1 before the first reset
+  int nenv;            // episodes per call
+  int64_t es;          // floats per episode block of dmem
+  std::vector<int> t;  // [nenv] timestep of each episode's newest window entry; -1 before its first (re)start
   PinnedBlock blk;
   Io host, dev;
+  int32_t *htab, *htab_dev;  // the per-call table in the pinned block (host / device address) ...
+  int32_t* dtab;             // ... and the copy the ingest launch makes of it in device memory
   Dev d;
   void* dmem;
   float *x, *qkv, *o, *xmid, *h;  // episode 0's; x: [NL + 1][NR, ldE], qkv: [NL][NR, ld3]
@@ -504,19 +589,68 @@ struct Handle {
   uint64_t seq;
 };
 
-int launch_linear(const Handle* h, const float* X, int ldx, const float* g, const float* b, const float* W,
-                  const float* bias, const float* res, int ldr, float* Y, int ldy, int K, int N, int gelu, int first,
-                  int count, int ring, hipStream_t s) {
-  if (count <= 0) return 0;
-  LinArgs a{X, g, b, W, bias, res, Y, ldx, ldr, ldy, K, N, gelu, first, count, ring, h->nenv, h->es,
-            (((uint64_t)1 << 32) + (uint64_t)count - 1) / (uint64_t)count};
-  hipLaunchKernelGGL(cdt_act_linear_kernel, dim3((N + 15) / 16, (count * h->nenv + 15) / 16), dim3(256), 0, s, a);
+struct Rows {
+  int first, count, ring;
+};
+
+// what an episode at timestep t runs: the row-set classes of the table (kTabSet), the window start and the newest
+// state token's row
+struct Plan {
+  Rows set[3];
+  int ws, srow;
+};
+
+Plan plan_of(const Handle* h, int t, bool restart) {
+  const int T = h->p.seq_len, R = h->R, TR = h->TR;
+  const int cur = (t % T) * R;
+  Plan pl;
+  // rows whose embedding (and, in growth, every layer) is new: the previous action token + this step's tokens
+  if (t == 0) {
+    const int pre = h->P && restart ? 1 : 0;  // the prefix row joins the embedded rows
+    pl.set[0] = Rows{pre ? TR : 0, R - 1 + pre, TR + 1};
+  } else {
+    pl.set[0] = Rows{(cur - 1 + TR) % TR, R, TR};
+  }
+  const int n = t + 1 < T ? t + 1 : T;  // timesteps in the window
+  pl.ws = ((t + 1 - n) % T) * R;        // ring row of its first token
+  pl.srow = cur + R - 2;                // the newest state token
+  // sliding: layer-0 attention onward (and q / k / v past layer 0) run over the window's tokens, without the newest
+  // (dummy) action token
+  pl.set[1] = t >= T ? Rows{pl.ws, n * R - 1, TR} : pl.set[0];
+  pl.set[2] = Rows{pl.srow, 1, TR};
+  return pl;
+}
+
+// one call's launches: either one plan for every episode (lockstep), or the table (tot / mx: the classes' total and
+// largest counts over the episodes)
+struct Call {
+  bool table;
+  Plan pl;
+  int t, reset;
+  int tot[3], mx[3];
+};
+
+int launch_linear(const Handle* h, const Call& c, int cls, const float* X, int ldx, const float* g, const float* b,
+                  const float* W, const float* bias, const float* res, int ldr, float* Y, int ldy, int K, int N,
+                  int gelu, hipStream_t s) {
+  if (c.table) {
+    const int total = c.tot[cls];
+    if (total <= 0) return 0;
+    LinArgs a{X, g, b, W, bias, res, Y, ldx, ldr, ldy, K, N, gelu, 0, total, 1, h->nenv, h->es, 0,
+              h->dtab + (kTabSet + 4 * cls) * kTabStride};
+    hipLaunchKernelGGL(cdt_act_linear_kernel, dim3((N + 15) / 16, (total + 15) / 16), dim3(256), 0, s, a);
+    return 0;
+  }
+  const Rows& r = c.pl.set[cls];
+  if (r.count <= 0) return 0;
+  LinArgs a{X, g, b, W, bias, res, Y, ldx, ldr, ldy, K, N, gelu, r.first, r.count, r.ring, h->nenv, h->es,
+            (((uint64_t)1 << 32) + (uint64_t)r.count - 1) / (uint64_t)r.count, nullptr};
+  hipLaunchKernelGGL(cdt_act_linear_kernel, dim3((N + 15) / 16, (r.count * h->nenv + 15) / 16), dim3(256), 0, s, a);
   return 0;
 }
 
-// one block over the rows `first, count` (mod ring); `out_rows` = the rows past the q / k / v stage (null = the same)
-void run_layer(const Handle* h, int l, int first, int count, int ring, int ofirst, int ocount, int oring, int ws,
-               hipStream_t s) {
+// one block: the rows of class `qc` through LN1 + q / k / v, the rows of class `oc` through attention .. MLP
+void run_layer(const Handle* h, const Call& c, int l, int qc, int oc, hipStream_t s) {
   const osrl_cdt_policy_t& p = h->p;
   const osrl_cdt_layer_t& L = h->layers[l];
   const int E = p.embedding_dim;
@@ -524,58 +658,35 @@ void run_layer(const Handle* h, int l, int first, int count, int ring, int ofirs
   const float* xin = h->x + l * xs;
   float* xout = h->x + (l + 1) * xs;
   float* qkv = h->qkv + (size_t)l * h->NR * h->ld3;
-  launch_linear(h, xin, h->ldE, L.ln1_g, L.ln1_b, L.w_qkv, L.b_qkv, nullptr, 0, qkv, h->ld3, E, 3 * E, 0, first, count,
-                ring, s);
-  if (ocount <= 0) return;
+  launch_linear(h, c, qc, xin, h->ldE, L.ln1_g, L.ln1_b, L.w_qkv, L.b_qkv, nullptr, 0, qkv, h->ld3, E, 3 * E, 0, s);
+  const Rows& r = c.pl.set[oc];
+  const int gx = c.table ? c.mx[oc] : r.count;
+  if (gx <= 0) return;
   const int d = E / p.num_heads;
-  AttnArgs at{qkv, h->o, h->ld3, h->ldE, E, p.num_heads, d, h->P, h->TR, ws, 1.0f / sqrtf((float)d), ofirst, oring,
-              (int32_t)h->es};
-  hipLaunchKernelGGL(cdt_act_attn_kernel, dim3(ocount, p.num_heads, h->nenv), dim3(64), 0, s, at);
-  launch_linear(h, h->o, h->ldE, nullptr, nullptr, L.w_o, L.b_o, xin, h->ldE, h->xmid, h->ldE, E, E, 0, ofirst, ocount,
-                oring, s);
-  launch_linear(h, h->xmid, h->ldE, L.ln2_g, L.ln2_b, L.w_1, L.b_1, nullptr, 0, h->h, h->ld4, E, 4 * E, 1, ofirst,
-                ocount, oring, s);
-  launch_linear(h, h->h, h->ld4, nullptr, nullptr, L.w_2, L.b_2, h->xmid, h->ldE, xout, h->ldE, 4 * E, E, 0, ofirst,
-                ocount, oring, s);
+  AttnArgs at{qkv, h->o, c.table ? h->dtab : nullptr, h->ld3, E, d, h->P, h->TR, c.table ? 0 : c.pl.ws,
+              1.0f / sqrtf((float)d), c.table ? oc : r.first, c.table ? 1 : r.ring, (int32_t)h->es};
+  hipLaunchKernelGGL(cdt_act_attn_kernel, dim3(gx, p.num_heads, h->nenv), dim3(64), 0, s, at);
+  launch_linear(h, c, oc, h->o, h->ldE, nullptr, nullptr, L.w_o, L.b_o, xin, h->ldE, h->xmid, h->ldE, E, E, 0, s);
+  launch_linear(h, c, oc, h->xmid, h->ldE, L.ln2_g, L.ln2_b, L.w_1, L.b_1, nullptr, 0, h->h, h->ld4, E, 4 * E, 1, s);
+  launch_linear(h, c, oc, h->h, h->ld4, nullptr, nullptr, L.w_2, L.b_2, h->xmid, h->ldE, xout, h->ldE, 4 * E, E, 0, s);
 }
 
-// the chain of one env step (t = h->t already advanced); reset: the prefix row joins the embedded rows
-int run_step(Handle* h, int reset, int host_action, hipStream_t s) {
+// the chain of one call (h->t already advanced)
+int run_step(Handle* h, const Call& c, int host_action, hipStream_t s) {
   const osrl_cdt_policy_t& p = h->p;
-  const int T = p.seq_len, R = h->R, TR = h->TR, t = h->t, NL = p.num_layers;
-  const int cur = (t % T) * R;
-  // rows whose embedding (and, in growth, every layer) is new: the previous action token + this step's tokens
-  int first, count, ring = TR;
-  if (t == 0) {
-    first = h->P && reset ? TR : 0;
-    count = R - 1 + (h->P && reset ? 1 : 0);
-    ring = TR + 1;
-  } else {
-    first = (cur - 1 + TR) % TR;
-    count = R;
-  }
-  IngestArgs ia{p, h->d, h->dev, h->x, h->ldE, R, TR, t, reset, host_action, first, count, ring, h->es};
+  const int NL = p.num_layers;
+  const Rows& emb = c.pl.set[0];
+  IngestArgs ia{p,         h->d,      h->dev,   h->x,  h->ldE, h->R, h->TR, c.t, c.reset, host_action, emb.first,
+                emb.count, emb.ring,  h->es,    c.table ? h->htab_dev : nullptr, h->dtab};
   (void)hipGetLastError();
   hipLaunchKernelGGL(cdt_act_ingest_kernel, dim3(h->nenv), dim3(256), 0, s, ia);
-  const int n = t + 1 < T ? t + 1 : T;            // timesteps in the window
-  const int ws = ((t + 1 - n) % T) * R;            // ring row of its first token
-  const int srow = cur + R - 2;                    // the newest state token
-  const int wcount = n * R - 1;                    // window tokens without the newest (dummy) action token
-  const bool sliding = t >= T;
-  for (int l = 0; l < NL; ++l) {
-    const bool lastl = l == NL - 1;
-    int qf = first, qc = count, qr = ring;         // rows through LN1 + q / k / v
-    int of = first, oc = count, orr = ring;        // rows through attention .. MLP
-    if (sliding) {
-      of = ws, oc = wcount, orr = TR;
-      if (l > 0) qf = ws, qc = wcount, qr = TR;
-    }
-    if (lastl) of = srow, oc = 1, orr = TR;
-    run_layer(h, l, qf, qc, qr, of, oc, orr, ws, s);
-  }
-  HeadArgs ha{p, h->d, h->dev, h->x + (size_t)NL * h->NR * h->ldE, h->ldE, srow,
-              (p.add_cost_feat || p.mul_cost_feat || p.cat_cost_feat) ? cur + (p.use_rew ? 1 : 0) : -1, ++h->seq,
-              h->es, h->arrived, h->nenv};
+  // layer 0 keeps its cached q / k / v in the sliding phase (class 0: the new rows only); the last layer runs past
+  // its q / k / v for the newest state token only
+  for (int l = 0; l < NL; ++l) run_layer(h, c, l, l == 0 ? 0 : 1, l == NL - 1 ? 2 : 1, s);
+  const bool feat = p.add_cost_feat || p.mul_cost_feat || p.cat_cost_feat;
+  HeadArgs ha{p,     h->d,       h->dev,  h->x + (size_t)NL * h->NR * h->ldE,
+              h->ldE, c.pl.srow, feat ? c.pl.srow - h->R + 2 + (p.use_rew ? 1 : 0) : -1,
+              ++h->seq, h->es,   h->arrived, h->nenv, c.table ? h->dtab : nullptr};
   hipLaunchKernelGGL(cdt_act_head_kernel, dim3(h->nenv), dim3(kHeadThreads), 0, s, ha);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
@@ -623,12 +734,13 @@ int create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int n_
   const int E = p.embedding_dim, T = p.seq_len, od = p.state_dim, ad = p.action_dim, NL = p.num_layers;
   const size_t NE = (size_t)n_env;
   h->ldE = up16(E), h->ld3 = up16(3 * E), h->ld4 = up16(4 * E);
-  h->t = -1;
+  h->t.assign(n_env, -1);
   h->seq = 0;
   h->dmem = nullptr;
-  // pinned block: obs [N, od], act_in [N, ad], act_out [N, ad], scalars [N, 4], seq
-  const size_t pbytes[] = {4 * NE * od, 4 * NE * ad, 4 * NE * ad, 16 * NE, sizeof(uint64_t)};
-  hipError_t e = h->blk.alloc(pbytes, 5);
+  // pinned block: obs [N, od], act_in [N, ad], act_out [N, ad], scalars [N, 4], seq, the per-call table
+  constexpr size_t kTabBytes = 4 * (size_t)kTabFields * kTabStride;
+  const size_t pbytes[] = {4 * NE * od, 4 * NE * ad, 4 * NE * ad, 16 * NE, sizeof(uint64_t), kTabBytes};
+  hipError_t e = h->blk.alloc(pbytes, 6);
   if (e != hipSuccess) {
     delete h;
     return (int)e;
@@ -640,8 +752,10 @@ int create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int n_
   };
   h->host = io(false);
   h->dev = io(true);
+  h->htab = h->blk.seg<int32_t>(5, false);
+  h->htab_dev = h->blk.seg<int32_t>(5, true);
   // device block, one per episode: window ring, last action, raw embeddings, activations (zeroed: the row strides'
-  // padding stays 0); then the head's arrival counter
+  // padding stays 0); then the head's arrival counter and the device copy of the per-call table
   const size_t NR = h->NR;
   size_t off = 0;
   auto take = [&](size_t floats) {
@@ -658,7 +772,7 @@ int create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int n_
     return -1;
   }
   h->es = (int64_t)(off / 4);
-  const size_t total = off * NE + 256;
+  const size_t total = off * NE + 256 + kTabBytes;
   e = hipMalloc(&h->dmem, total);
   if (e == hipSuccess) e = hipMemset(h->dmem, 0, total);
   if (e != hipSuccess) {
@@ -675,28 +789,85 @@ int create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int n_
   h->xmid = (float*)(base + o_m);
   h->h = (float*)(base + o_h);
   h->arrived = (uint32_t*)(base + off * NE);
+  h->dtab = (int32_t*)(base + off * NE + 256);
   *handle = h;
   return 0;
 }
 
-int reset_all(Handle* h, hipStream_t s) {
-  h->t = 0;
-  return run_step(h, 1, 0, s);
+// one call: every episode idles, steps or restarts (mode[e]).  -1, and nothing changed, if a stepping episode was never
+// started or would leave the timestep embedding table.
+int step_modes(Handle* h, const int32_t* mode, int host_action, hipStream_t s) {
+  const int N = h->nenv;
+  int nt[OSRL_CDT_POLICY_MAX_ENVS];
+  int lead = -1;  // the first episode that runs
+  bool same = true;
+  for (int e = 0; e < N; ++e) {
+    nt[e] = h->t[e];
+    if (mode[e] == kIdle) {
+      same = false;
+      continue;
+    }
+    if (mode[e] == kStep) {
+      if (h->t[e] < 0) return -1;                                 // no episode started
+      if (h->p.te && h->t[e] + 1 >= h->p.te_rows) return -1;  // past the timestep embedding table
+      nt[e] = h->t[e] + 1;
+    } else if (mode[e] == kRestart) {
+      nt[e] = 0;
+    } else {
+      return -1;
+    }
+    if (lead < 0) lead = e;
+    if (mode[e] != mode[lead] || nt[e] != nt[lead]) same = false;
+  }
+  if (lead < 0) return 0;  // nothing to run
+  h->t.assign(nt, nt + N);
+  Call c;
+  c.table = !same;
+  c.pl = plan_of(h, nt[lead], mode[lead] == kRestart);
+  c.t = nt[lead];
+  c.reset = mode[lead] == kRestart;
+  if (c.table) {
+    int32_t* tb = h->htab;
+    for (int k = 0; k < 3; ++k) c.tot[k] = c.mx[k] = 0;
+    for (int e = 0; e < N; ++e) {
+      const bool run = mode[e] != kIdle;
+      Plan pl = plan_of(h, run ? nt[e] : 0, mode[e] == kRestart);
+      tb[kTabMode * kTabStride + e] = mode[e];
+      tb[kTabT * kTabStride + e] = run ? nt[e] : 0;
+      tb[kTabWs * kTabStride + e] = pl.ws;
+      tb[kTabSrow * kTabStride + e] = pl.srow;
+      for (int k = 0; k < 3; ++k) {
+        const int cnt = run ? pl.set[k].count : 0;
+        int32_t* f = tb + (kTabSet + 4 * k) * kTabStride + e;
+        f[0] = pl.set[k].first;
+        f[kTabStride] = cnt;
+        f[2 * kTabStride] = pl.set[k].ring;
+        f[3 * kTabStride] = c.tot[k];  // exclusive prefix sum
+        c.tot[k] += cnt;
+        if (cnt > c.mx[k]) c.mx[k] = cnt;
+      }
+    }
+  }
+  return run_step(h, c, host_action ? 1 : 0, s);
 }
 
-int step_all(Handle* h, int host_action, hipStream_t s) {
-  if (h->t < 0) return -1;  // no episode started
-  if (h->p.te && h->t + 1 >= h->p.te_rows) return -1;  // past the timestep embedding table
-  ++h->t;
-  return run_step(h, 0, host_action ? 1 : 0, s);
+int all_modes(Handle* h, int mode, int host_action, hipStream_t s) {
+  int32_t m[OSRL_CDT_POLICY_MAX_ENVS];
+  for (int e = 0; e < h->nenv; ++e) m[e] = mode;
+  return step_modes(h, m, host_action, s);
 }
+
+int reset_all(Handle* h, hipStream_t s) { return all_modes(h, kRestart, 0, s); }
+
+int step_all(Handle* h, int host_action, hipStream_t s) { return all_modes(h, kStep, host_action, s); }
 
 int window_of(Handle* h, int env, float* states, float* actions, float* returns, float* costs, int64_t* time_steps,
               int32_t* n_out, hipStream_t st) {
   if (env < 0 || env >= h->nenv) return -1;
   const osrl_cdt_policy_t& p = h->p;
   const int T = p.seq_len, od = p.state_dim, ad = p.action_dim;
-  if (h->t < 0) {
+  const int t = h->t[env];
+  if (t < 0) {
     if (n_out) *n_out = 0;
     return 0;
   }
@@ -710,7 +881,7 @@ int window_of(Handle* h, int env, float* states, float* actions, float* returns,
   if (e == hipSuccess) e = hipMemcpyAsync(ts.data(), h->d.win_t + eoff, 4 * T, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return (int)e;
-  const int n = h->t + 1 < T ? h->t + 1 : T, t0 = h->t + 1 - n;
+  const int n = t + 1 < T ? t + 1 : T, t0 = t + 1 - n;
   for (int i = 0; i < n; ++i) {
     const int k = (t0 + i) % T;
     if (states) memcpy(states + (size_t)i * od, &s[(size_t)k * od], 4 * od);
@@ -761,7 +932,7 @@ extern "C" int osrl_cdt_policy_reset(void* handle, float target_return, float ta
 extern "C" int osrl_cdt_policy_step(void* handle, float reward, float cost, int32_t host_action, void* stream) {
   if (!handle) return -1;
   Handle* h = static_cast<Handle*>(handle);
-  if (h->nenv != 1 || h->t < 0) return -1;
+  if (h->nenv != 1 || h->t[0] < 0) return -1;
   h->host.scalars[0] = reward;
   h->host.scalars[1] = cost;
   return step_all(h, host_action, (hipStream_t)stream);
@@ -775,6 +946,18 @@ extern "C" int osrl_cdt_policy_reset_n(void* handle, void* stream) {
 extern "C" int osrl_cdt_policy_step_n(void* handle, int32_t host_action, void* stream) {
   if (!handle) return -1;
   return step_all(static_cast<Handle*>(handle), host_action, (hipStream_t)stream);
+}
+
+extern "C" int osrl_cdt_policy_step_slots(void* handle, const int32_t* mode, int32_t host_action, void* stream) {
+  if (!handle || !mode) return -1;
+  return step_modes(static_cast<Handle*>(handle), mode, host_action, (hipStream_t)stream);
+}
+
+extern "C" int osrl_cdt_policy_timesteps(void* handle, int32_t* t) {
+  if (!handle || !t) return -1;
+  Handle* h = static_cast<Handle*>(handle);
+  for (int e = 0; e < h->nenv; ++e) t[e] = h->t[e];
+  return 0;
 }
 
 extern "C" int osrl_cdt_policy_window(void* handle, float* states, float* actions, float* returns, float* costs,

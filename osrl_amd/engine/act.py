@@ -14,10 +14,16 @@ need ``model.repack()``, as for training).
 ``VecFastPolicy`` is the same for ``num_envs`` episodes on as many host environments, advanced in lockstep by one C call
 per environment step (csrc/act_vec.hip, ``osrl_policy_*_n``): the slots are rows of 16-row fp32-MFMA tiles, and a
 slot's action does not depend on how many ran beside it.
+
+``rollout_refill`` is the host-side scheduler both trainer families use for ``schedule="refill"``: a queue of jobs over
+N environments, where a slot whose episode has ended takes the next job in the same policy call in which the others step
+(``VecFastPolicy.step(restart=...)``, ``CDTVecFastPolicy.step(restart=...)``) instead of waiting for the longest episode
+of its wave.
 """
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from typing import Optional, Tuple
 
 import numpy as np
@@ -228,6 +234,14 @@ class VecFastPolicy(PinnedHandle):
             noise = self._rows("noise", noise, (self.noise_dim,), np.float32)
         return obs, active, noise
 
+    def _ids(self, episode_ids) -> np.ndarray:
+        if episode_ids is None:
+            return np.arange(self.num_envs, dtype=np.int64)
+        ids = self._rows("episode_ids", episode_ids, ())
+        if ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 0x7FFFFFFF).any():
+            raise ValueError("expected episode_ids as integers in 0 .. 2^31 - 1")
+        return ids
+
     def _call(self, obs, active, noise, deterministic) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         if active is None:
             self.obs[:] = obs  # converts dtype
@@ -252,28 +266,42 @@ class VecFastPolicy(PinnedHandle):
         if self._h is None:
             raise RuntimeError("VecFastPolicy is closed")
         obs, active, noise = self._checked(obs, active, noise)
-        if episode_ids is None:
-            ids = np.arange(self.num_envs, dtype=np.int64)
-        else:
-            ids = self._rows("episode_ids", episode_ids, ())
-            if ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 0x7FFFFFFF).any():
-                raise ValueError("expected episode_ids as integers in 0 .. 2^31 - 1")
+        ids = self._ids(episode_ids)
         sel = slice(None) if active is None else active
         self._meta[sel, 0] = ids[sel]
         self._meta[sel, 1] = 0
         self._started = True
         return self._call(obs, active, noise, deterministic)
 
-    def step(self, obs, active=None, noise=None, deterministic: bool = True):
+    def step(self, obs, active=None, noise=None, deterministic: bool = True, restart=None, episode_ids=None):
         """The next ``(actions, log-probs or None)`` of every active slot from its new observation.  ``noise``:
-        explicit standard-normal draws ``[N, act_dim]`` (eps of "gauss") or ``[N, latent_dim]`` (z of "bcq")."""
+        explicit standard-normal draws ``[N, act_dim]`` (eps of "gauss") or ``[N, latent_dim]`` (z of "bcq").
+        ``restart`` (bool ``[N]``): the masked slots start a new episode from ``obs[e]`` instead of stepping -- they
+        count as active and take ``episode_ids[e]`` (``[N]`` integers, default the slot numbers) at step 0, as ``reset``
+        gives them -- while the other active slots step."""
         if self._h is None:
             raise RuntimeError("VecFastPolicy is closed")
-        if not self._started:
+        if restart is not None:
+            restart = self._rows("restart", restart, ())
+            if restart.dtype != np.bool_:
+                raise ValueError(f"expected restart as booleans, got dtype {restart.dtype}")
+            ids = self._ids(episode_ids)
+            if not restart.any():
+                restart = None
+        elif episode_ids is not None:
+            raise ValueError("episode_ids belong to the slots that restart: pass restart")
+        if not self._started and restart is None:
             raise RuntimeError("call reset() before step()")
         obs, active, noise = self._checked(obs, active, noise)
-        self._meta[slice(None) if active is None else active, 1] += 1
-        return self._call(obs, active, noise, deterministic)
+        if restart is None:
+            self._meta[slice(None) if active is None else active, 1] += 1
+            return self._call(obs, active, noise, deterministic)
+        stepping = ~restart if active is None else active & ~restart
+        self._meta[stepping, 1] += 1
+        self._meta[restart, 0] = ids[restart]
+        self._meta[restart, 1] = 0
+        self._started = True
+        return self._call(obs, None if active is None else active | restart, noise, deterministic)
 
 
 def cached_vec_policy(model, num_envs, make, limit=VecFastPolicy.LIMIT):
@@ -349,3 +377,127 @@ def evaluate_lockstep(trainer, eval_episodes):
         costs += list(c)
     trainer.model.train()
     return np.mean(rets), np.mean(costs), np.mean(lens)
+
+
+SCHEDULES = ("waves", "refill")
+
+
+def check_schedule(schedule) -> str:
+    if schedule not in SCHEDULES:
+        raise ValueError(f'schedule must be "waves" or "refill", got {schedule!r}')
+    return schedule
+
+
+RefillResult = namedtuple("RefillResult", "returns lengths costs slots calls")
+RefillResult.__doc__ = """What ``rollout_refill`` returns: per job its return, length and cost sum (arrays, job order) and
+the slot (= index of the environment) it ran in; ``calls``: the policy calls the schedule took."""
+
+
+def rollout_refill(adapter, envs, jobs, episode_len) -> RefillResult:
+    """Runs every job of the queue ``jobs`` to completion on the host environments ``envs``, one slot per environment
+    and ONE policy call per loop iteration for all slots.  Job ``e`` starts in slot ``e``; after every iteration the
+    slots are scanned in ascending order and each slot whose episode ended (its environment terminated or truncated, or
+    the episode reached ``episode_len`` steps) takes the next queued job: it is reset and passed as ``restart`` in the
+    next iteration's policy call, in which the other slots step.  With the queue empty a finished slot idles.  The
+    number of policy calls is the makespan of that list schedule, not the sum over waves of the longest episode.
+
+    ``adapter`` ties the loop to a policy: ``obs_dim``; ``observe(o)`` -> the policy's observation row; ``costs(info)``
+    -> (the cost the policy is told, the cost summed into the result); ``act(obs, reward, cost, step, restart, jobs)``
+    -> actions ``[N, ..]``, where ``step`` / ``restart`` are bool ``[N]`` masks and ``jobs[e]`` is the queue entry of a
+    restarting slot (None elsewhere)."""
+    envs, jobs = list(envs), list(jobs)
+    N, J, EL = len(envs), len(jobs), int(episode_len)
+    if J and N == 0:
+        raise ValueError("jobs over an empty list of environments")
+    ep_ret, ep_len, ep_cost = [0.0] * J, np.zeros(J, np.int64), [0.0] * J
+    slot_of = np.full(J, -1, np.int64)
+    if J == 0:
+        return RefillResult(np.asarray(ep_ret), ep_len, np.asarray(ep_cost), slot_of, 0)
+    obs = np.zeros((N, adapter.obs_dim), np.float32)
+    reward, cost = np.zeros(N, np.float64), np.zeros(N, np.float64)
+    active, restart = np.zeros(N, bool), np.zeros(N, bool)
+    job_in = [-1] * N
+    queued = 0
+
+    def take(e):
+        nonlocal queued
+        q, queued = queued, queued + 1
+        job_in[e], slot_of[q] = q, e
+        o, _ = envs[e].reset()
+        obs[e] = adapter.observe(o)
+        active[e] = restart[e] = True
+
+    for e in range(min(N, J)):
+        take(e)
+    calls = 0
+    while active.any():
+        act = adapter.act(obs, reward, cost, active & ~restart, restart.copy(),
+                          [jobs[job_in[e]] if restart[e] else None for e in range(N)])
+        calls += 1
+        restart[:] = False
+        for e in np.flatnonzero(active):
+            q = job_in[e]
+            o, r, terminated, truncated, info = envs[e].step(act[e])
+            told, summed = adapter.costs(info)
+            ep_ret[q] += r
+            ep_len[q] += 1
+            ep_cost[q] += summed
+            if terminated or truncated or ep_len[q] == EL:
+                active[e] = False
+                continue
+            obs[e], reward[e], cost[e] = adapter.observe(o), r, told
+        for e in range(N):  # ascending: the lowest finished slot takes the earliest queued job
+            if not active[e] and queued < J:
+                take(e)
+    return RefillResult(np.asarray(ep_ret), ep_len, np.asarray(ep_cost), slot_of, calls)
+
+
+class MLPRefillAdapter:
+    """``rollout_refill`` over ``model.fast_policy(num_envs)`` of an MLP model: a job is an episode id (the key, with
+    the step, of the noise the policy draws on the device)."""
+
+    def __init__(self, model, num_envs, cost_scale=None, append=None):
+        self.pol = model.fast_policy(num_envs=num_envs)
+        self.obs_dim, self.cost_scale, self.append = self.pol.obs_dim, cost_scale, append
+
+    def observe(self, o):
+        return o if self.append is None else np.append(o, self.append)
+
+    def costs(self, info):
+        return 0.0, info["cost"] if self.cost_scale is None else info["cost"] * self.cost_scale
+
+    def act(self, obs, reward, cost, step, restart, jobs):
+        ids = np.asarray([0 if j is None else j for j in jobs], dtype=np.int64)
+        return self.pol.step(obs, active=step, restart=restart, episode_ids=ids)[0]
+
+
+def rollout_jobs_mlp(model, envs, num_jobs, episode_ids=None, cost_scale=None, append=None) -> RefillResult:
+    """``num_jobs`` episodes over the host environments ``envs`` on the refill schedule (``rollout_refill``); job ``q``
+    carries episode id ``episode_ids[q]`` (default ``q``)."""
+    J = int(num_jobs)
+    if episode_ids is None:
+        ids = np.arange(J, dtype=np.int64)
+    else:
+        if np.shape(episode_ids) != (J,):
+            raise ValueError(f"expected episode_ids of shape ({J},), got {np.shape(episode_ids)}")
+        ids = np.asarray(episode_ids)
+        if ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 0x7FFFFFFF).any():
+            raise ValueError("expected episode_ids as integers in 0 .. 2^31 - 1")
+    envs = list(envs)
+    if J and not envs:
+        raise ValueError("jobs over an empty list of environments")
+    if J == 0:
+        return rollout_refill(None, envs, [], model.episode_len)
+    return rollout_refill(MLPRefillAdapter(model, len(envs), cost_scale, append), envs, [int(i) for i in ids],
+                          model.episode_len)
+
+
+def evaluate_refill(trainer, eval_episodes):
+    """``evaluate_lockstep`` on the refill schedule: episode ``q`` (episode id ``q``) is job ``q`` of one queue over the
+    environments ``trainer.env``.  Returns the means (return, cost sum, length), not rescaled."""
+    if len(list(trainer.env)) == 0:
+        raise ValueError("evaluate over an empty list of environments")
+    trainer.model.eval()
+    res = trainer.rollout_jobs(list(trainer.env), int(eval_episodes))
+    trainer.model.train()
+    return np.mean(res.returns), np.mean(res.costs), np.mean(res.lengths)

@@ -9,9 +9,11 @@ Window updates use the existing loop's fp32 expressions (``returns - float(rewar
 The kernels read the packed forward weight copies and the biases of the model's flat group -- the buffers the fused
 AdamW step, ``load_state_dict`` and ``repack()`` keep current -- so training between evaluations needs no rebuild.
 
-``CDTVecFastPolicy`` is the same for ``num_envs`` episodes on as many host environments, advanced in lockstep by one C
-call per env step (``osrl_cdt_policy_*_n``): the step's launches run over the rows of all the episodes, and an
-episode's actions do not depend on how many ran beside it.
+``CDTVecFastPolicy`` is the same for ``num_envs`` episodes on as many host environments, advanced by one C call per env
+step (``osrl_cdt_policy_*_n``): the step's launches run over the rows of all the episodes, and an episode's actions do
+not depend on how many ran beside it.  The slots run in lockstep (``reset`` starts all of them) or, once a slot has been
+restarted on its own (``step(..., restart=mask)``, ``osrl_cdt_policy_step_slots``), each at its own timestep: a finished
+slot takes a new episode while the others go on, and an inactive slot costs no device rows.
 """
 from __future__ import annotations
 
@@ -99,6 +101,7 @@ class _CDTHandle(PinnedHandle):
         lib = self._open(m.device, entry, C.byref(d), layers, *width)
         self.od, self.ad, self.T = m.state_dim, m.action_dim, m.seq_len
         self._t, self._episode_len = -1, 0
+        self._te_rows = int(d.te_rows) if m.time_emb else None
         return lib
 
     def _window(self, entry: str, *env) -> Dict[str, np.ndarray]:
@@ -170,13 +173,19 @@ class CDTFastPolicy(_CDTHandle):
 
 
 class CDTVecFastPolicy(_CDTHandle):
-    """``num_envs`` episodes on as many host environments, in lockstep: all slots share the timestep, ``reset`` starts
-    all of them and ``step`` advances all of them with one C call.  A slot's actions are those a ``CDTFastPolicy`` returns
-    for the same inputs, bit for bit, whatever ``num_envs`` is.
+    """``num_envs`` episodes on as many host environments, one C call per env step for all of them.  A slot's actions
+    are those a ``CDTFastPolicy`` returns for the same inputs, bit for bit, whatever ``num_envs`` is and whatever the
+    other slots are doing.
 
+    Lockstep (the default): ``reset`` starts all slots and ``step`` advances all of them, so they share the timestep.
     A slot whose episode has ended is passed as inactive (``active[e] = False``): its rows of ``obs / reward / cost /
     action`` are not read and its row of the result is zero.  Its device rows keep running on the stale inputs of its
-    last active step (lockstep: the launches cover every slot); nothing of that reaches the other slots."""
+    last active step (the launches cover every slot); nothing of that reaches the other slots.
+
+    Independent slots: ``step(..., restart=mask)`` starts a new episode in the masked slots, at timestep 0, while the
+    others step.  From the first such call until the next ``reset`` every slot has its own timestep (``timesteps``) and
+    episode length, and an inactive slot is FROZEN: it runs no device rows, its timestep does not advance, and a later
+    call continues it where it stood."""
 
     LIMIT = (MAX_ENVS, "OSRL_CDT_POLICY_MAX_ENVS")
 
@@ -191,14 +200,34 @@ class CDTVecFastPolicy(_CDTHandle):
         self._act_out = np.ctypeslib.as_array(ptrs[2], shape=(N, ad))
         self._scalars = np.ctypeslib.as_array(ptrs[3], shape=(N, 4))  # reward, cost, target_return, target_cost
 
+    # Per-slot state lives beside the scalars ``_t`` / ``_episode_len``: ``_ts`` / ``_els`` ([N] arrays) and ``_slots``
+    # (True once a slot has been restarted on its own).  In lockstep the scalars are every slot's; with independent
+    # slots ``_t`` is the furthest slot's timestep and ``_episode_len`` the length read at the latest (re)start.
+    def _slot_state(self) -> Tuple[np.ndarray, np.ndarray]:
+        if not self.__dict__.get("_slots", False):
+            N = self.num_envs
+            return np.full(N, self._t, np.int64), np.full(N, self._episode_len, np.int64)
+        return self._ts, self._els
+
+    @property
+    def timesteps(self) -> np.ndarray:
+        """``[N]`` integers: the timestep of each slot's newest window entry, -1 for a slot never started."""
+        return self._slot_state()[0].copy()
+
     def _target(self, name, x) -> np.ndarray:
         if np.ndim(x) != 0 and np.shape(x) != (self.num_envs,):
             raise ValueError(f"expected {name} as a scalar or of shape ({self.num_envs},), got shape {np.shape(x)}")
         return np.broadcast_to(np.asarray(x, dtype=np.float64), (self.num_envs,))
 
+    def _mask(self, name, x) -> np.ndarray:
+        x = self._rows(name, x, ())
+        if x.dtype != np.bool_:
+            raise ValueError(f"expected {name} as booleans, got dtype {x.dtype}")
+        return x
+
     def reset(self, obs, target_return, target_cost) -> np.ndarray:
         """Starts ``num_envs`` episodes from ``obs [N, state_dim]``; the targets are scalars or one per slot.  Returns
-        the first actions ``[N, action_dim]``."""
+        the first actions ``[N, action_dim]``.  The slots are in lockstep again from here."""
         if self._h is None:
             raise RuntimeError("CDTVecFastPolicy is closed")
         obs = self._rows("obs", obs, (self.od,))
@@ -208,49 +237,101 @@ class CDTVecFastPolicy(_CDTHandle):
         self._obs[:] = obs  # float32 (round to nearest), as torch.as_tensor(obs) written into the fp32 window
         self._scalars[:, 2] = tr  # float(target) -> fp32, as the one-episode call's float arguments
         self._scalars[:, 3] = tc
-        self._t = 0
+        self._t, self._slots = 0, False
         rc = self._lib.osrl_cdt_policy_reset_n(self._h, self._stream())
         if rc != 0:
             self._t = -1
             L.check(rc, "osrl_cdt_policy_reset_n")
         return self._act_out.copy()
 
-    def step(self, obs, reward, cost, action=None, active=None) -> np.ndarray:
+    def step(self, obs, reward, cost, action=None, active=None, restart=None, target_return=None,
+             target_cost=None) -> np.ndarray:
         """Per slot as ``CDTFastPolicy.step``: ``obs [N, state_dim]``, ``reward [N]``, ``cost [N]``, the actions taken at
         the previous step (``action [N, action_dim]``, default: the ones returned) and ``active`` (bool ``[N]``, default:
-        all).  Returns the next actions ``[N, action_dim]``, zero in the rows of inactive slots."""
-        if self._t < 0:
-            raise RuntimeError("call reset() before step()")
-        if self._t + 1 >= self._episode_len:
-            raise RuntimeError(f"the episode is over: {self._episode_len} steps (model.episode_len)")
+        all).  Returns the next actions ``[N, action_dim]``, zero in the rows of inactive slots.
+
+        ``restart`` (bool ``[N]``): the masked slots begin a new episode at timestep 0 from ``obs[e]`` with
+        ``target_return`` / ``target_cost`` (scalars or ``[N]``; required when any slot restarts) instead of stepping:
+        their ``reward / cost / action`` rows are not read, they count as active, and their row of the result is the
+        new episode's first action (what ``reset`` returns for it)."""
         N = self.num_envs
+        if restart is not None:
+            restart = self._mask("restart", restart)
+            if not restart.any():
+                restart = None
+        if self._t < 0 and restart is None:
+            raise RuntimeError("call reset() before step()")
+        slots = restart is not None or self.__dict__.get("_slots", False)
+        if not slots and self._t + 1 >= self._episode_len:
+            raise RuntimeError(f"the episode is over: {self._episode_len} steps (model.episode_len)")
         obs = self._rows("obs", obs, (self.od,))
         reward, cost = self._rows("reward", reward, ()), self._rows("cost", cost, ())
         if action is not None:
             action = self._rows("action", action, (self.ad,))
         if active is not None:
-            active = self._rows("active", active, ())
-            if active.dtype != np.bool_:
-                raise ValueError(f"expected active as booleans, got dtype {active.dtype}")
-        if active is None:
-            self._obs[:] = obs
-            self._scalars[:, 0] = reward  # float(reward) -> fp32, as the one-episode call's float arguments
-            self._scalars[:, 1] = cost
-            if action is not None:
-                self._act_in[:] = action
-        else:
-            self._obs[active] = obs[active]
-            self._scalars[active, 0] = reward[active]
-            self._scalars[active, 1] = cost[active]
-            if action is not None:
-                self._act_in[active] = action[active]
-        rc = self._lib.osrl_cdt_policy_step_n(self._h, 0 if action is None else 1, self._stream())
+            active = self._mask("active", active)
+        if not slots:
+            if active is None:
+                self._obs[:] = obs
+                self._scalars[:, 0] = reward  # float(reward) -> fp32, as the one-episode call's float arguments
+                self._scalars[:, 1] = cost
+                if action is not None:
+                    self._act_in[:] = action
+            else:
+                self._obs[active] = obs[active]
+                self._scalars[active, 0] = reward[active]
+                self._scalars[active, 1] = cost[active]
+                if action is not None:
+                    self._act_in[active] = action[active]
+            rc = self._lib.osrl_cdt_policy_step_n(self._h, 0 if action is None else 1, self._stream())
+            if rc != 0:
+                L.check(rc, "osrl_cdt_policy_step_n")
+            self._t += 1
+            out = self._act_out.copy()
+            if active is not None:
+                out[~active] = 0.0
+            return out
+        # independent slots
+        rs = np.zeros(N, bool) if restart is None else restart
+        if rs.any():
+            if target_return is None or target_cost is None:
+                raise ValueError("target_return and target_cost are required when a slot restarts")
+            tr, tc = self._target("target_return", target_return), self._target("target_cost", target_cost)
+        st = (np.ones(N, bool) if active is None else active) & ~rs
+        ts, els = self._slot_state()
+        te = self.__dict__.get("_te_rows")
+        for e in np.flatnonzero(st):
+            if ts[e] < 0:
+                raise RuntimeError(f"slot {e}: no episode was started (call reset(), or restart the slot)")
+            if ts[e] + 1 >= els[e]:
+                raise RuntimeError(f"slot {e}: the episode is over: {els[e]} steps (model.episode_len)")
+            if te is not None and ts[e] + 1 >= te:
+                raise RuntimeError(f"slot {e}: timestep {ts[e] + 1} is past the timestep embedding table ({te} rows)")
+        if self._h is None:
+            raise RuntimeError("CDTVecFastPolicy is closed")
+        ts, els = ts.copy(), els.copy()
+        if rs.any():
+            els[rs] = self._episode_len = int(self.model.episode_len)
+            self.model.repack()  # as reset()
+            self._scalars[rs, 2] = tr[rs]
+            self._scalars[rs, 3] = tc[rs]
+        run = st | rs
+        self._obs[run] = obs[run]
+        self._scalars[st, 0] = reward[st]
+        self._scalars[st, 1] = cost[st]
+        if action is not None:
+            self._act_in[st] = action[st]
+        mode = np.where(rs, 2, np.where(st, 1, 0)).astype(np.int32)
+        rc = self._lib.osrl_cdt_policy_step_slots(self._h, mode.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  0 if action is None else 1, self._stream())
         if rc != 0:
-            L.check(rc, "osrl_cdt_policy_step_n")
-        self._t += 1
+            L.check(rc, "osrl_cdt_policy_step_slots")
+        ts[st] += 1
+        ts[rs] = 0
+        self._ts, self._els, self._slots = ts, els, True
+        self._t = int(ts.max())
         out = self._act_out.copy()
-        if active is not None:
-            out[~active] = 0.0
+        out[~run] = 0.0
         return out
 
     def window(self, env: int) -> Dict[str, np.ndarray]:
