@@ -12,12 +12,15 @@ from .. import _lib as L
 from . import plan as _plan
 from ..common.net import net_desc_seq
 from . import glue as G
-from .core import ArgArena, DwPlan, MlpRun, StepState, capture_step, cur_stream, load_into, check_plans_current
+from ._step import StepEngine
+from .core import ArgArena, DwPlan, MlpRun, StepState, cur_stream, check_plans_current
 
 STAT_KEYS = ["loss/actor_loss"]
 
 
-class BCEngine:
+class BCEngine(StepEngine):
+    BATCH = ("obs", "act")
+
     def __init__(self, model, batch_size: int, rows_global: int = 0, dist=None):
         m = self.model = model
         B = self.B = int(batch_size)
@@ -33,12 +36,7 @@ class BCEngine:
         self.du = torch.zeros(1, B, m.action_dim, **f)
         self.r_pi.setup_backward(self.du)
         self.plan = DwPlan(m.groups["actor"], self.r_pi.dw_entries(), B, dev)
-        # every dW plan of this engine is built: the slab epochs they were built against are recorded NOW (not at the
-        # first step), so an engine that is constructed directly, never stepped and then superseded is flagged stale
-        from .core import slab_epochs
-        self._slab_epochs = slab_epochs(self.model)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.replay = None
+        self._plans_built()
         # gather -> forward -> MSE -> backward -> dW -> Adam -> tick as one launch (include/osrl_amd.h
         # osrl_mlp_regress_step): single device, one row split per dW tile (no gradient slabs to sum), a work list and
         # a row-tile count that fit the resident grid; the library has the last word (OSRL_E_UNSUPPORTED -> the plan)
@@ -126,12 +124,12 @@ class BCEngine:
         if store is not None and store.widths[0] != self.obs.shape[1]:
             raise ValueError(f"the store's observations have {store.widths[0]} columns, the policy reads "
                              f"{self.obs.shape[1]} (bc_mode='multi-task' appends the cost return: process_bc_dataset)")
-        self.replay = store
-        self.graph = None
+        super().attach_replay(store)
         self._step_c = None
         self._arena_direct = None
 
     def _run(self, use_graph: bool) -> None:
+        """The one-launch step is launched directly; everything else is the base's captured / eager step."""
         check_plans_current(self)  # (also before the replay of an already captured graph)
         if use_graph and self.dist is None and self.one_launch and self.direct:
             if self._arena_direct is None:  # this step records the launch's descriptor; the later ones read it from HBM
@@ -146,17 +144,10 @@ class BCEngine:
                 with self._arena_direct.replay():
                     self.body()
             return
-        if use_graph and self.dist is None:
-            if self.graph is None:
-                self._capture()
-            self.graph.replay()
-            self.st.host_step += 1
-        else:
-            self.body()
+        super()._run(use_graph)
 
-    def step_replay(self, use_graph: bool = True) -> None:
-        assert self.replay is not None
-        self._run(use_graph)
+    def _issue(self, par=None) -> None:
+        self.body()
 
     def body(self) -> None:
         check_plans_current(self)
@@ -174,29 +165,6 @@ class BCEngine:
         ng = (self.rows_global or B) * ad
         G.mse_loss(pred, self.act, B * ad, ng, self.du, self.st.stat_ptr("loss/actor_loss"))
         self.r_pi.backward_dz()
-        self.plan.launch()
-        grp = m.groups["actor"]
-        if self.dist is not None:
-            self.dist.allreduce_group(grp)
-        grp.adam_step(m._lrs["actor"], self.st.ptr)
+        self._optim("actor", self.plan)
         if self.dist is not None:  # per-rank partial of the globally normalised loss -> the global value
             self.dist.all_reduce_(self.st.stats)
-
-    def step(self, observations, actions, use_graph: bool = True) -> None:
-        if self.replay is not None:
-            raise RuntimeError("a replay store is attached: call step_replay() (or attach_replay(None))")
-        load_into(((self.obs, observations), (self.act, actions)))
-        self._run(use_graph)
-
-    def _capture(self) -> None:
-        check_plans_current(self)
-        g = self.model.groups["actor"]
-        snap = (g.p.clone(), g.m.clone(), g.v.clone(), self.st.state.clone(), self.st.stats.clone(),
-                self.st.ring.clone(), self.st.host_step)
-        gr, self._arena = capture_step(self.st.state.device, self.body, self.body)
-        torch.cuda.synchronize()
-        g.p.copy_(snap[0]); g.m.copy_(snap[1]); g.v.copy_(snap[2])
-        self.st.state.copy_(snap[3]); self.st.stats.copy_(snap[4]); self.st.ring.copy_(snap[5])
-        self.st.host_step = snap[6]
-        self.model.repack()
-        self.graph = gr

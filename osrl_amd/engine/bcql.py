@@ -8,9 +8,7 @@ materialises the repeated observations: the MLP kernels read ``next_obs[r / N]``
 """
 from __future__ import annotations
 
-import os
-
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
@@ -18,14 +16,17 @@ from .. import _lib as L
 from ..common.net import net_desc_seq, vae_dec_desc, vae_enc_desc
 from . import glue as G
 from . import plan as P
-from .core import Branches, DwPlan, MlpRun, StepState, capture_step, concat_nets, load_into, check_plans_current
+from ._step import PipelinedReplay, StepEngine, VaePhase
+from .core import Branches, DwPlan, MlpRun, StepState, concat_nets
 
 STAT_KEYS = ["loss/loss_vae", "loss/critic_loss", "loss/cost_critic_loss", "loss/actor_loss", "loss/qc_penalty",
              "loss/lagrangian"]
 NOISE_KEYS = ["eps_vae", "z_c", "z_cc", "z_actor"]
 
 
-class BCQLEngine:
+class BCQLEngine(PipelinedReplay, VaePhase, StepEngine):
+    SIDE_STREAMS, PICK_FASTEST = 1, True
+
     def __init__(self, model, batch_size: int, rows_global: int = 0, seed: int = 0, dist=None):
         m = self.model = model
         B = self.B = int(batch_size)
@@ -42,17 +43,11 @@ class BCQLEngine:
         self.obs, self.nobs, self.act = z(B, od), z(B, od), z(B, ad)
         self.rew, self.cost, self.done = z(B), z(B), z(B)
         shapes = {"eps_vae": (B, Lz), "z_c": (N * B, Lz), "z_cc": (N * B, Lz), "z_actor": (B, Lz)}
-        tot = sum(int(torch.Size(s).numel()) for s in shapes.values())
-        self.noise_flat = z((tot + 3) // 4 * 4)
-        self.noise: Dict[str, torch.Tensor] = {}
-        o = 0
-        for k in NOISE_KEYS:
-            n = int(torch.Size(shapes[k]).numel())
-            self.noise[k] = self.noise_flat[o:o + n].view(shapes[k])
-            o += n
-
-        z0 = int(torch.Size(shapes["eps_vae"]).numel())
-        self._z_all = self.noise_flat[z0:z0 + sum(int(torch.Size(shapes[k]).numel()) for k in ("z_c", "z_cc", "z_actor"))]
+        assert list(shapes) == NOISE_KEYS
+        self.noise_flat, self.noise = self.noise_layout(shapes, dev)
+        # the three latent draws the step clamps (head()), adjacent in the flat buffer
+        z0 = self.noise["eps_vae"].numel()
+        self._z_all = self.noise_flat[z0:z0 + sum(self.noise[k].numel() for k in ("z_c", "z_cc", "z_actor"))]
         assert self._z_all.data_ptr() == self.noise["z_c"].data_ptr()
         twin = lambda mod: net_desc_seq(mod.all_nets(), 1.0)  # noqa: E731
         self.d_actor = net_desc_seq([m.actor.pi], 1.0)
@@ -64,10 +59,7 @@ class BCQLEngine:
         m.repack()
 
         # vae phase
-        self.r_enc, self.r_dec = MlpRun(self.d_enc, B, True, dev), MlpRun(self.d_dec, B, True, dev)
-        self.z, self.du, self.dhead_enc = z(B, Lz), z(1, B, ad), z(1, B, 2 * Lz)
-        self.r_dec.setup_backward(self.du, dx_cols=(od, Lz))
-        self.r_enc.setup_backward(self.dhead_enc)
+        self._vae_runs(dev)
         pl = self.plan = P.bcql_plan(od, ad, B, int(m.vae_hidden_sizes), N, seeds=G.SEEDS and G.VAE_TAILS and G.VAE_NS_AUTO)
         if pl.vae_dw_tile:
             # 400-wide layers = 5 x 5 column blocks: 80 x 80 tiles, 3 row splits per 2048 rows (engine/cpq.py)
@@ -118,8 +110,7 @@ class BCQLEngine:
         self.seeds = None
         if G.SEEDS and G.VAE_TAILS:
             self.seeds = {
-                "vae": G.seed_vae(self.act, self.r_enc.y[0], B, ad, Lz, m.beta, self.rows_global, G.SeedStat(dev, 1, B),
-                                  self.st.stat_ptr("loss/loss_vae")),
+                "vae": self._vae_seed(dev),
                 "critic": G.seed_bcq_critic(self.r_qold_t.y, nq, nq, N, self.rew, self.done, B, m.gamma, m.lmbda,
                                             self.rows_global, G.SeedStat(dev, 2 * nq, B),
                                             self.st.stat_ptr("loss/critic_loss")),
@@ -127,24 +118,8 @@ class BCQLEngine:
                                           self.rows_global, G.SeedStat(dev, 2 * nqc, B),
                                           self.st.stat_ptr("loss/cost_critic_loss")),
             }
-        # round 5: the VAE phase as all-CU layer launches where the library takes the shape (glue.VaeNs, engine/cpq.py)
-        self.vae_ns = None
-        if self.seeds is not None and pl.vae_ns:
-            self.vae_ns = G.VaeNs.build(self.r_enc, self.r_dec, self.obs, self.act, self.noise["eps_vae"], self.z,
-                                        m.latent_dim, m.beta, self.rows_global, self.st.stat_ptr("loss/loss_vae"))
-        # every dW plan of this engine is built: the slab epochs they were built against are recorded NOW (not at the
-        # first step), so an engine that is constructed directly, never stepped and then superseded is flagged stale
-        from .core import slab_epochs
-        self._slab_epochs = slab_epochs(self.model)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.replay = None
-
-    def _optim(self, name: str, plan: DwPlan, tau: float) -> None:
-        plan.launch()
-        grp = self.model.groups[name]
-        if self.dist is not None:
-            self.dist.allreduce_group(grp)
-        grp.adam_step(self.model._lrs[name], self.st.ptr, tau=tau)
+        self._vae_all_cu()  # (round 5, as in engine/cpq.py)
+        self._plans_built()
 
     def _targets(self, zkey: str, r_q: MlpRun, second: bool = False) -> torch.Tensor:
         """bcql.py:138-142: Q_old(obs', actor_old(obs', vae.decode(obs'))) on the N*B repeated rows."""
@@ -155,12 +130,6 @@ class BCQLEngine:
         t = r_act.forward(self.nobs, dec, map0=L.MAP_DIV, div0=N)[0]
         G.bcq_perturb(dec, t, NB, m.action_dim, m.phi, m.max_action, a_t)
         return r_q.forward(self.nobs, a_t, map0=L.MAP_DIV, div0=N)
-
-    def _update(self, name: str, tau: float) -> None:
-        grp = self.model.groups[name]
-        if self.dist is not None:
-            self.dist.allreduce_group(grp)
-        grp.adam_step(self.model._lrs[name], self.st.ptr, tau=tau)
 
     def head(self, device_noise: bool) -> None:
         """The part of a step that depends on nothing the PREVIOUS step's critic / actor phases write: prologue (tick +
@@ -176,23 +145,7 @@ class BCQLEngine:
         # over the range instead of three (round 5: 3 x 5.2 us on the step's head, profiles/r4_bcql_timeline.txt)
         G.clamp_(self._z_all, -0.5, 0.5)
 
-        sd = self.seeds
-        if self.vae_ns is not None:
-            self.vae_ns.forward()
-            self.vae_ns.backward()
-        else:
-            head = G.vae_encode(self.r_enc, self.obs, self.act, nz["eps_vae"], Lz, self.z)
-            u = self.r_dec.forward(self.obs, self.z)[0]
-        if self.vae_ns is not None:
-            pass
-        elif sd is not None:
-            self.r_dec.backward_dz(tail=G.vae_latent_bwd_tail(head, nz["eps_vae"], Lz, m.beta, rg, self.dhead_enc),
-                                   seed=sd["vae"])
-        else:
-            G.vae_loss(u, self.act, head, B, ad, Lz, m.beta, rg, self.du, st.stat_ptr("loss/loss_vae"), ws=self.ws_vae)
-            G.vae_decoder_backward(self.r_dec, head, nz["eps_vae"], Lz, m.beta, rg, self.dhead_enc)
-        if self.vae_ns is None:
-            self.r_enc.backward_dz()
+        self._vae_phase(self.seeds, ws=self.ws_vae)
         self._optim("vae", self.p_vae, 0.0)
 
     def body(self, device_noise: bool, par: Optional[Branches] = None, nxt: Optional["BCQLEngine"] = None,
@@ -259,10 +212,7 @@ class BCQLEngine:
         if self.dist is None:
             self._update("cost_critic", m.tau)
         else:
-            gc, gcc = m.groups["critic"], m.groups["cost_critic"]
-            self.dist.all_reduce_many_([self.dist.reduce_local(gc), self.dist.reduce_local(gcc)])
-            gc.adam_step(m._lrs["critic"], st.ptr, tau=m.tau)
-            gcc.adam_step(m._lrs["cost_critic"], st.ptr, tau=m.tau)
+            self._update_critics_dp()
 
         y = self.r_pi_q.forward(self.obs, self.a_pi)
         means, share = None, 1.0
@@ -275,105 +225,7 @@ class BCQLEngine:
         self.r_pi_q.backward_dz()
         G.bcq_perturb_bwd(dec, t, self.r_pi_q.dx, 2 * nq + 2 * nqc, B, ad, m.phi, m.max_action, self.dt)
         self.r_actor.backward_dz()
-        if self.dist is None:
-            self._optim("actor", self.p_actor, m.tau)
-        else:  # actor gradient and the per-rank partial statistics in one collective
-            self.p_actor.launch()
-            ga = m.groups["actor"]
-            self.dist.all_reduce_many_([self.dist.reduce_local(ga), st.stats])
-            ga.adam_step(m._lrs["actor"], st.ptr, tau=m.tau)
+        # (data parallel: the actor gradient and the per-rank partial statistics in one collective)
+        self._optim("actor", self.p_actor, m.tau, extra=[st.stats])
         if nxt is not None:
             par.join(0)  # the next step's critic / actor phases need its head (the VAE's optimizer step)
-
-    def load_batch(self, observations, next_observations, actions, rewards, costs, done) -> None:
-        load_into(((self.obs, observations), (self.nobs, next_observations), (self.act, actions),
-                   (self.rew, rewards), (self.cost, costs), (self.done, done)))
-
-    def _snapshot(self):
-        m = self.model
-        snap = {"pid": m.pid_state.clone(), "state": self.st.state.clone(), "host": self.st.host_step,
-                "stats": self.st.stats.clone(), "ring": self.st.ring.clone()}
-        for n, g in m.groups.items():
-            snap[n] = (g.p.clone(), g.m.clone(), g.v.clone(), None if g.tgt is None else g.tgt.clone())
-        return snap
-
-    def _restore(self, snap) -> None:
-        m = self.model
-        m.pid_state.copy_(snap["pid"])
-        self.st.state.copy_(snap["state"]); self.st.stats.copy_(snap["stats"]); self.st.ring.copy_(snap["ring"])
-        self.st.host_step = snap["host"]
-        for n, g in m.groups.items():
-            p, mm, v, t = snap[n]
-            g.p.copy_(p); g.m.copy_(mm); g.v.copy_(v)
-            if t is not None:
-                g.tgt.copy_(t)
-        m.repack()
-
-    def capture(self) -> None:
-        """(A few captures, the fastest graph kept: core.pick_fastest.)"""
-        from .core import CAPTURE_TRIES, pick_fastest
-
-        def once():
-            snap = self._snapshot()
-            par = Branches(True, 1)
-            g, arena = capture_step(self.st.state.device, lambda: self.body(True), lambda: self.body(True, par))
-            torch.cuda.synchronize()
-            self._restore(snap)
-            return g, par, arena  # (the side stream and the argument blocks stay alive with the graph)
-
-        (self.graph, self._par, self._arena), self.capture_ms = pick_fastest(once, lambda c: c[0].replay(), self._snapshot,
-                                                                              self._restore, CAPTURE_TRIES)
-
-    def attach_replay(self, store) -> None:
-        """Sample minibatches on device from ``store`` (common/replay.py) inside the step itself."""
-        self.replay = store
-        self.graph = None
-        self._pipe = None
-
-    def steps_replay(self, n: int, steps_per_graph: Optional[int] = None) -> None:
-        """EXACTLY ``n`` train steps on minibatches drawn on device from the attached replay store.  Where the plan says so
-        (``plan.steps_per_graph`` > 1, single GPU) whole multiples go through graphs of that many steps, software-pipelined
-        across steps (engine/pipeline.py: bit-equal to ``n`` calls of ``step_replay()``); the remainder through the
-        one-step graph.  The loop of examples/train/train_cpq.py:138-144 / train_bcql.py:142-148 with the DataLoader
-        folded into the step."""
-        spg = int(self.plan.steps_per_graph if steps_per_graph is None else steps_per_graph)
-        if spg <= 1 or self.dist is not None:
-            for _ in range(int(n)):
-                self.step_replay(True)
-            return
-        pipe = getattr(self, "_pipe", None)
-        if pipe is None or pipe.n != spg:
-            from .pipeline import PipelinedSteps
-            pipe = self._pipe = PipelinedSteps(self, spg)
-        pipe.run(n)
-
-    def step_replay(self, use_graph: bool = True) -> None:
-        """One train step on a minibatch drawn on device from the attached replay store."""
-        check_plans_current(self)
-        assert self.replay is not None
-        if use_graph and self.dist is None:
-            if self.graph is None:
-                self.capture()
-            self.graph.replay()
-            self.st.host_step += 1
-        else:
-            self.body(True)
-
-    def step(self, observations, next_observations, actions, rewards, costs, done, noise=None,
-             use_graph: bool = True) -> None:
-        check_plans_current(self)
-        if self.replay is not None:
-            raise RuntimeError("a replay store is attached: call step_replay() (or attach_replay(None))")
-        self.load_batch(observations, next_observations, actions, rewards, costs, done)
-        if noise is not None:
-            for k in NOISE_KEYS:
-                self.noise[k].copy_(torch.as_tensor(noise[k]).reshape(self.noise[k].shape), non_blocking=True)
-            self.body(False)
-            return
-        if use_graph and self.dist is None:
-            if self.graph is None:
-                self.capture()
-            self.graph.replay()
-            self.st.host_step += 1
-        else:
-            self.body(True)

@@ -8,14 +8,15 @@ observations: the MLP kernels read ``obs[r / N]`` / ``obs[r / M]`` directly.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
 from .. import _lib as L
 from ..common.net import actor_head_desc, net_desc_seq, vae_dec_desc, vae_dec_raw_desc, vae_enc_desc
 from . import glue as G
-from .core import Branches, DwPlan, MlpRun, StepState, capture_step, concat_nets, cur_stream, load_into, check_plans_current
+from ._step import StepEngine, VaePhase
+from .core import Branches, DwPlan, MlpRun, StepState, concat_nets, cur_stream
 
 STAT_KEYS = ["loss/loss_vae", "loss/critic_loss", "loss/cost_critic_loss", "loss/actor_loss", "loss/mmd_loss",
              "loss/qc_penalty", "loss/lagrangian", "loss/alpha_value"]
@@ -23,7 +24,9 @@ NOISE_KEYS = ["eps_vae", "eps_c", "eps_cc", "z_mmd", "eps_pi"]
 KERNELS = {"gaussian": 0, "laplacian": 1}  # include/osrl_amd.h OSRL_MMD_*
 
 
-class BEARLEngine:
+class BEARLEngine(VaePhase, StepEngine):
+    SIDE_STREAMS = 1
+
     def __init__(self, model, batch_size: int, rows_global: int = 0, seed: int = 0, dist=None):
         m = self.model = model
         B = self.B = int(batch_size)
@@ -43,15 +46,8 @@ class BEARLEngine:
         self.rew, self.cost, self.done = z(B), z(B), z(B)
         shapes = {"eps_vae": (B, Lz), "eps_c": (N * B, ad), "eps_cc": (N * B, ad), "z_mmd": (B * M, Lz),
                   "eps_pi": (B * M, ad)}
-        tot = sum(int(torch.Size(s).numel()) for s in shapes.values())
-        self.noise_flat = z((tot + 3) // 4 * 4)
-        self.noise: Dict[str, torch.Tensor] = {}
-        o = 0
-        for k in NOISE_KEYS:
-            n = int(torch.Size(shapes[k]).numel())
-            self.noise[k] = self.noise_flat[o:o + n].view(shapes[k])
-            o += n
-
+        assert list(shapes) == NOISE_KEYS
+        self.noise_flat, self.noise = self.noise_layout(shapes, dev)
         twin = lambda mod: net_desc_seq(mod.all_nets(), 1.0)  # noqa: E731
         self.d_actor, self.d_actor_old = actor_head_desc(m.actor), actor_head_desc(m.actor_old)
         self.d_critic, self.d_cost = twin(m.critic), twin(m.cost_critic)
@@ -61,10 +57,7 @@ class BEARLEngine:
         m.repack()
 
         # vae phase
-        self.r_enc, self.r_dec = MlpRun(self.d_enc, B, True, dev), MlpRun(self.d_dec, B, True, dev)
-        self.z, self.du, self.dhead_enc = z(B, Lz), z(1, B, ad), z(1, B, 2 * Lz)
-        self.r_dec.setup_backward(self.du, dx_cols=(od, Lz))
-        self.r_enc.setup_backward(self.dhead_enc)
+        self._vae_runs(dev)
         self.p_vae = DwPlan(g["vae"], self.r_enc.dw_entries() + self.r_dec.dw_entries(), B, dev)
 
         # target pipelines (critic on the capture stream, cost critic on the side branch: two buffer sets)
@@ -94,22 +87,7 @@ class BEARLEngine:
         self.coef, self.pi_means = z(4), z(4)
         self.r_actor.setup_backward(self.dhead)
         self.p_actor = DwPlan(g["actor"], self.r_actor.dw_entries(), BM, dev)
-        # every dW plan of this engine is built: the slab epochs they were built against are recorded NOW (not at the
-        # first step), so an engine that is constructed directly, never stepped and then superseded is flagged stale
-        from .core import slab_epochs
-        self._slab_epochs = slab_epochs(self.model)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.replay = None
-
-    def _optim(self, name: str, plan: DwPlan, tau: float) -> None:
-        plan.launch()
-        self._update(name, tau)
-
-    def _update(self, name: str, tau: float) -> None:
-        grp = self.model.groups[name]
-        if self.dist is not None:
-            self.dist.allreduce_group(grp)
-        grp.adam_step(self.model._lrs[name], self.st.ptr, tau=tau)
+        self._plans_built()
 
     def _targets(self, eps_key: str, r_q: MlpRun, which: int) -> torch.Tensor:
         """bearl.py:158-164: Q_old(obs', tanh(actor_old sample)) on the N*B repeated rows; the sampled action is NOT
@@ -127,8 +105,7 @@ class BEARLEngine:
             self._seed_cache = None
             if G.SEEDS and G.VAE_TAILS:
                 self._seed_cache = {
-                    "vae": G.seed_vae(self.act, self.r_enc.y[0], B, m.action_dim, m.latent_dim, m.beta, rg,
-                                      G.SeedStat(dev, 1, B), self.st.stat_ptr("loss/loss_vae")),
+                    "vae": self._vae_seed(dev),
                     "critic": G.seed_bcq_critic(self.r_qold_t.y, nq, nq, N, self.rew, self.done, B, m.gamma, m.lmbda, rg,
                                                 G.SeedStat(dev, 2 * nq, B), self.st.stat_ptr("loss/critic_loss")),
                     "cost": G.seed_bcq_critic(self.r_qcold_t.y, nqc, nqc, N, self.cost, None, B, m.gamma, m.lmbda, rg,
@@ -147,16 +124,8 @@ class BEARLEngine:
         st.prologue(self.replay, (self.obs, self.nobs, self.act, self.rew, self.cost, self.done), self.noise_flat, self.seed, device_noise)
         G.clamp_(nz["z_mmd"], -0.5, 0.5)  # decode_multiple clamps its latent draw (net.py:343-346)
 
-        head = G.vae_encode(self.r_enc, self.obs, self.act, nz["eps_vae"], Lz, self.z)
-        u = self.r_dec.forward(self.obs, self.z)[0]
-        sd = self._seeds()
-        if sd is not None:  # (round 4) the backward launches compute the gradient they start from, as in engine/cpq.py
-            self.r_dec.backward_dz(tail=G.vae_latent_bwd_tail(head, nz["eps_vae"], Lz, m.beta, rg, self.dhead_enc),
-                                   seed=sd["vae"])
-        else:
-            G.vae_loss(u, self.act, head, B, ad, Lz, m.beta, rg, self.du, st.stat_ptr("loss/loss_vae"))
-            G.vae_decoder_backward(self.r_dec, head, nz["eps_vae"], Lz, m.beta, rg, self.dhead_enc)
-        self.r_enc.backward_dz()
+        sd = self._seeds()  # (round 4) the backward launches compute the gradient they start from, as in engine/cpq.py
+        self._vae_phase(sd)
         self._optim("vae", self.p_vae, 0.0)
 
         par.fork(0)
@@ -194,10 +163,7 @@ class BEARLEngine:
         if self.dist is None:
             self._update("cost_critic", m.tau)
         else:
-            gc, gcc = m.groups["critic"], m.groups["cost_critic"]
-            self.dist.all_reduce_many_([self.dist.reduce_local(gc), self.dist.reduce_local(gcc)])
-            gc.adam_step(m._lrs["critic"], st.ptr, tau=m.tau)
-            gcc.adam_step(m._lrs["cost_critic"], st.ptr, tau=m.tau)
+            self._update_critics_dp()
 
         y = self.r_pi_q.forward(self.obs, self.a0)
         yq, yqc = y[:2 * nq], y[2 * nq:]
@@ -221,77 +187,5 @@ class BEARLEngine:
                                        2 * nq + 2 * nqc, B, M, ad, self.dhead.data_ptr(), cur_stream()),
                 "osrl_bear_head_bwd")
         self.r_actor.backward_dz()
-        if self.dist is None:
-            self._optim("actor", self.p_actor, m.tau)
-        else:  # actor gradient and the per-rank partial statistics in one collective
-            self.p_actor.launch()
-            ga = m.groups["actor"]
-            self.dist.all_reduce_many_([self.dist.reduce_local(ga), st.stats])
-            ga.adam_step(m._lrs["actor"], st.ptr, tau=m.tau)
-
-    def load_batch(self, observations, next_observations, actions, rewards, costs, done) -> None:
-        load_into(((self.obs, observations), (self.nobs, next_observations), (self.act, actions),
-                   (self.rew, rewards), (self.cost, costs), (self.done, done)))
-
-    def _snapshot(self):
-        m = self.model
-        snap = {"pid": m.pid_state.clone(), "la": m.log_alpha.clone(), "state": self.st.state.clone(),
-                "host": self.st.host_step, "stats": self.st.stats.clone(), "ring": self.st.ring.clone()}
-        for n, g in m.groups.items():
-            snap[n] = (g.p.clone(), g.m.clone(), g.v.clone(), None if g.tgt is None else g.tgt.clone())
-        return snap
-
-    def _restore(self, snap) -> None:
-        m = self.model
-        m.pid_state.copy_(snap["pid"]); m.log_alpha.copy_(snap["la"])
-        self.st.state.copy_(snap["state"]); self.st.stats.copy_(snap["stats"]); self.st.ring.copy_(snap["ring"])
-        self.st.host_step = snap["host"]
-        for n, g in m.groups.items():
-            p, mm, v, t = snap[n]
-            g.p.copy_(p); g.m.copy_(mm); g.v.copy_(v)
-            if t is not None:
-                g.tgt.copy_(t)
-        m.repack()
-
-    def capture(self) -> None:
-        snap = self._snapshot()
-        par = Branches(True, 1)
-        g, self._arena = capture_step(self.st.state.device, lambda: self.body(True), lambda: self.body(True, par))
-        self._par = par  # keep the side stream alive with the graph
-        torch.cuda.synchronize()
-        self._restore(snap)
-        self.graph = g
-
-    def attach_replay(self, store) -> None:
-        self.replay = store
-        self.graph = None
-
-    def step_replay(self, use_graph: bool = True) -> None:
-        check_plans_current(self)
-        assert self.replay is not None
-        if use_graph and self.dist is None:
-            if self.graph is None:
-                self.capture()
-            self.graph.replay()
-            self.st.host_step += 1
-        else:
-            self.body(True)
-
-    def step(self, observations, next_observations, actions, rewards, costs, done, noise=None,
-             use_graph: bool = True) -> None:
-        check_plans_current(self)
-        if self.replay is not None:
-            raise RuntimeError("a replay store is attached: call step_replay() (or attach_replay(None))")
-        self.load_batch(observations, next_observations, actions, rewards, costs, done)
-        if noise is not None:
-            for k in NOISE_KEYS:
-                self.noise[k].copy_(torch.as_tensor(noise[k]).reshape(self.noise[k].shape), non_blocking=True)
-            self.body(False)
-            return
-        if use_graph and self.dist is None:
-            if self.graph is None:
-                self.capture()
-            self.graph.replay()
-            self.st.host_step += 1
-        else:
-            self.body(True)
+        # (data parallel: the actor gradient and the per-rank partial statistics in one collective)
+        self._optim("actor", self.p_actor, m.tau, extra=[st.stats])

@@ -16,13 +16,14 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List
 
 import torch
 
 from .. import _lib as L
 from . import plan as _plan
-from .core import DwPlan, FlatGroup, StepState, capture_step, cur_stream, load_into, check_plans_current
+from ._step import StepEngine
+from .core import DwPlan, FlatGroup, StepState, cur_stream, load_into, check_plans_current
 
 LN_BATCH = _plan.knob("OSRL_CDT_LN_BATCH", "1", "CDT: the LayerNorm parameter reductions of a step in one launch") == "1"
 ATTN_KEEP = _plan.knob("OSRL_CDT_ATTN_KEEP", "1", "CDT: attention dropout decisions handed from forward to backward") == "1"
@@ -37,7 +38,11 @@ def _r16(x: int) -> int:
     return (x + 15) // 16 * 16
 
 
-class CDTEngine:
+class CDTEngine(StepEngine):
+    DP_CAPTURE = True
+    # a store of sequences, not of transitions: attach_store / step_store / load_batch below take the base's place
+    attach_replay = step_replay = None
+
     def __init__(self, model, batch_size: int, trainer_cfg: dict, dist=None, inference: bool = False,
                  grad: bool = False, dropout: bool = True):
         """``inference``: forward only (no dW plans, no gradient slabs).  ``grad``: the engine of the differentiable
@@ -167,7 +172,6 @@ class CDTEngine:
         self.temp_mv = z(2)
         self.counts = z(4)
         self.loss_ws = z(8 * ((BT + 1023) // 1024) + 8)
-        self._graph_failed = False
         self._ln_pending: List[str] = []
 
         # dW plans
@@ -224,12 +228,8 @@ class CDTEngine:
                     for ch in range(off // 1024, (off + max(ln, 1) - 1) // 1024 + 1):
                         cnt[ch] = max(cnt[ch], min(ns, self.n_splits))
             self.slab_counts = torch.tensor(cnt, dtype=torch.uint8, device=dev)
-        # every dW plan of this engine is built: the slab epochs they were built against are recorded NOW (not at the
-        # first step), so an engine that is constructed directly, never stepped and then superseded is flagged stale
-        from .core import slab_epochs
-        self._slab_epochs = slab_epochs(self.model)
+        self._plans_built()
         self._slab_probe = None
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.store = None
         self._plan_matmul()
         m.repack()
@@ -651,7 +651,7 @@ class CDTEngine:
         """One train step on windows sampled on device from the attached SequenceStore."""
         check_plans_current(self)
         assert self.store is not None
-        self._go(use_graph)
+        self._run(use_graph)
 
     def step(self, states, actions, returns, costs_return, time_steps, mask, costs, use_graph: bool = True,
              episode_cost=None) -> None:
@@ -659,42 +659,10 @@ class CDTEngine:
         if self.store is not None:
             raise RuntimeError("a SequenceStore is attached: call step_store()")
         self.load_batch(states, actions, returns, costs_return, time_steps, mask, costs, episode_cost)
-        self._go(use_graph)
+        self._run(use_graph)
 
-    def _go(self, use_graph: bool) -> None:
-        if use_graph and not self._graph_failed:
-            if self.graph is None:
-                ok = True
-                try:
-                    self._capture()
-                except Exception as e:  # pragma: no cover - depends on the RCCL build
-                    if self.dist is None:
-                        raise
-                    import warnings
-                    warnings.warn(f"hipGraph capture of the data-parallel CDT step failed ({e!r}); running eagerly")
-                    ok = False
-                if self.dist is not None and not self.dist.all_agree(ok, self.dev):
-                    self._graph_failed, self.graph = True, None  # every rank runs eagerly, or none does
-            if self.graph is not None:
-                self.graph.replay()
-                self.st.host_step += 1
-                return
+    def _snap_groups(self):
+        return [self.g]  # (the gradient shadow in grad mode)
+
+    def _issue(self, par=None) -> None:
         self.body()
-
-    def _capture(self) -> None:
-        m, g = self.model, self.g
-        snap = (g.p.clone(), g.m.clone(), g.v.clone(), self.st.state.clone(), self.st.stats.clone(),
-                self.st.ring.clone(), self.st.host_step, m.log_temperature.clone() if m.stochastic else None,
-                self.temp_mv.clone())
-        try:  # warm-up + capture both run a real step: the snapshot goes back even when the capture is refused
-            gr, self._arena = capture_step(self.st.state.device, self.body, self.body)
-        finally:
-            torch.cuda.synchronize()
-            g.p.copy_(snap[0]); g.m.copy_(snap[1]); g.v.copy_(snap[2])
-            self.st.state.copy_(snap[3]); self.st.stats.copy_(snap[4]); self.st.ring.copy_(snap[5])
-            self.st.host_step = snap[6]
-            if m.stochastic:
-                m.log_temperature.copy_(snap[7])
-            self.temp_mv.copy_(snap[8])
-            m.repack()
-        self.graph = gr

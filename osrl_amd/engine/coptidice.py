@@ -13,13 +13,12 @@ step identically everywhere); collectives per step: the ell gather, [chi grads |
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
-
 import torch
 
 from .. import _lib as L
 from ..common.net import actor_head_desc, net_desc_seq
-from .core import DwPlan, MlpRun, StepState, capture_step, cur_stream, load_into, check_plans_current
+from ._step import StepEngine
+from .core import DwPlan, MlpRun, StepState, cur_stream
 
 STAT_KEYS = ["loss/chi_loss", "loss/tau_loss", "loss/D_kl", "loss/Df", "loss/td_error", "loss/nu_loss",
              "loss/lmbda_loss", "loss/actor_loss", "loss/tau", "loss/lmbda"]
@@ -27,7 +26,9 @@ NOISE_KEYS = ["obs_eps", "act_eps"]
 F_TYPES = {"chi2": 0, "softchi": 1, "kl": 2}  # include/osrl_amd.h OSRL_F_*
 
 
-class COptiDICEEngine:
+class COptiDICEEngine(StepEngine):
+    BATCH = StepEngine.BATCH + ("init",)
+
     def __init__(self, model, batch_size: int, rows_global: int = 0, seed: int = 0, dist=None):
         m = self.model = model
         B = self.B = int(batch_size)
@@ -44,10 +45,8 @@ class COptiDICEEngine:
         self.x2 = z(2 * B, od)  # [obs; next_obs]
         self.obs, self.nobs = self.x2[:B], self.x2[B:]
         self.act, self.rew, self.cost, self.done, self.init = z(B, ad), z(B), z(B), z(B), z(B)
-        tot = B * od + B * ad
-        self.noise_flat = z((tot + 3) // 4 * 4)
-        self.noise: Dict[str, torch.Tensor] = {"obs_eps": self.noise_flat[:B * od].view(B, od),
-                                               "act_eps": self.noise_flat[B * od:tot].view(B, ad)}
+        self.noise_flat, self.noise = self.noise_layout({"obs_eps": (B, od), "act_eps": (B, ad)}, dev)
+        assert list(self.noise) == NOISE_KEYS
         self.d_nu = net_desc_seq(list(m.nu_network.q_nets), 1.0)
         self.d_chi = net_desc_seq(list(m.chi_network.q_nets), 1.0)
         self.d_actor = actor_head_desc(m.actor)
@@ -72,20 +71,7 @@ class COptiDICEEngine:
         self.dhead = z(1, B, 2 * ad)
         self.r_actor.setup_backward(self.dhead)
         self.p_actor = DwPlan(g["actor"], self.r_actor.dw_entries(), B, dev)
-        # every dW plan of this engine is built: the slab epochs they were built against are recorded NOW (not at the
-        # first step), so an engine that is constructed directly, never stepped and then superseded is flagged stale
-        from .core import slab_epochs
-        self._slab_epochs = slab_epochs(self.model)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.replay = None
-
-    def _adam(self, name: str, plan: DwPlan, extra=()) -> None:
-        """dW, (data parallel: all-reduce of the flat gradient and of ``extra`` in one collective), Adam."""
-        plan.launch()
-        grp = self.model.groups[name]
-        if self.dist is not None:
-            self.dist.all_reduce_many_([self.dist.reduce_local(grp), *extra])
-        grp.adam_step(self.model._lrs[name], self.st.ptr)
+        self._plans_built()
 
     def body(self, device_noise: bool) -> None:
         m, st, B, lib = self.model, self.st, self.B, L.load()
@@ -118,7 +104,7 @@ class COptiDICEEngine:
         wc = self.work[2:3]  # this rank's share of weighted_c -> global
         if self.use_chi:
             self.r_chi.backward_dz()
-            self._adam("chi_network", self.p_chi, extra=(wc,) if dp is not None else ())
+            self._optim("chi_network", self.p_chi, extra=(wc,))  # (data parallel: with this rank's share, one collective)
         elif dp is not None:
             dp.all_reduce_(wc)
         L.check(lib.osrl_dice_nu_step(p(nu2), nn_, B, p(self.e), p(self.w), p(self.done), p(self.init), ft,
@@ -126,7 +112,7 @@ class COptiDICEEngine:
                                       float(m.scalar_lr), rg, share, st.ptr, p(leaves), p(self.work), p(self.dnu),
                                       st.stat_ptr("loss/Df"), s()), "osrl_dice_nu_step")
         self.r_nu.backward_dz()
-        self._adam("nu_network", self.p_nu)
+        self._optim("nu_network", self.p_nu, extra=())
 
         # 2. policy extraction: noisy observations / actions, w* re-evaluated with the updated nu network
         L.check(lib.osrl_dice_perturb(p(self.obs), p(self.noise["obs_eps"]), p(m.observations_std), B, od, 0.1,
@@ -141,70 +127,10 @@ class COptiDICEEngine:
         L.check(lib.osrl_dice_actor_loss(p(head), p(self.act_n), p(self.w2), B, ad, rg, p(self.dhead),
                                          st.stat_ptr("loss/actor_loss"), s()), "osrl_dice_actor_loss")
         self.r_actor.backward_dz()
-        self._adam("actor", self.p_actor, extra=(st.stats,) if dp is not None else ())
-
-    def load_batch(self, observations, next_observations, actions, rewards, costs, done, is_init) -> None:
-        load_into(((self.obs, observations), (self.nobs, next_observations), (self.act, actions),
-                   (self.rew, rewards), (self.cost, costs), (self.done, done), (self.init, is_init)))
-
-    def _snapshot(self):
-        m = self.model
-        snap = {"leaves": m.scalar_leaves.clone(), "state": self.st.state.clone(), "host": self.st.host_step,
-                "stats": self.st.stats.clone(), "ring": self.st.ring.clone()}
-        for n, g in m.groups.items():
-            snap[n] = (g.p.clone(), g.m.clone(), g.v.clone())
-        return snap
-
-    def _restore(self, snap) -> None:
-        m = self.model
-        m.scalar_leaves.copy_(snap["leaves"])
-        self.st.state.copy_(snap["state"]); self.st.stats.copy_(snap["stats"]); self.st.ring.copy_(snap["ring"])
-        self.st.host_step = snap["host"]
-        for n, g in m.groups.items():
-            pp, mm, v = snap[n]
-            g.p.copy_(pp); g.m.copy_(mm); g.v.copy_(v)
-        m.repack()
-
-    def capture(self) -> None:
-        snap = self._snapshot()
-        g, self._arena = capture_step(self.st.state.device, lambda: self.body(True), lambda: self.body(True))
-        torch.cuda.synchronize()
-        self._restore(snap)
-        self.graph = g
+        self._optim("actor", self.p_actor, extra=(st.stats,))
 
     def attach_replay(self, store) -> None:
         """Sample minibatches on device from ``store`` (a ``ReplayStore(..., state_init=True)``) inside the step."""
         if store is not None and not store.state_init:
             raise ValueError("COptiDICE needs the is_init flag: build the ReplayStore with state_init=True")
-        self.replay = store
-        self.graph = None
-
-    def step_replay(self, use_graph: bool = True) -> None:
-        check_plans_current(self)
-        assert self.replay is not None
-        if use_graph and self.dist is None:
-            if self.graph is None:
-                self.capture()
-            self.graph.replay()
-            self.st.host_step += 1
-        else:
-            self.body(True)
-
-    def step(self, observations, next_observations, actions, rewards, costs, done, is_init, noise=None,
-             use_graph: bool = True) -> None:
-        check_plans_current(self)
-        if self.replay is not None:
-            raise RuntimeError("a replay store is attached: call step_replay() (or attach_replay(None))")
-        self.load_batch(observations, next_observations, actions, rewards, costs, done, is_init)
-        if noise is not None:
-            for k in NOISE_KEYS:
-                self.noise[k].copy_(torch.as_tensor(noise[k]).reshape(self.noise[k].shape), non_blocking=True)
-            self.body(False)
-            return
-        if use_graph and self.dist is None:
-            if self.graph is None:
-                self.capture()
-            self.graph.replay()
-            self.st.host_step += 1
-        else:
-            self.body(True)
+        super().attach_replay(store)

@@ -976,13 +976,16 @@ def pick_fastest(build, replay, snapshot, restore, tries: int, reps: int = 12):
     return cands[min(range(tries), key=lambda i: times[i])], times
 
 
-def capture_step(device, warm, captured):
+def capture_step(device, warm, captured, capacity: int = 1 << 18):
     """hipGraph capture of one step: ``warm()`` runs eagerly on a side stream (torch's warm-up requirement) while
-    the fused-MLP launches' argument blocks are recorded, the blocks go to HBM, then ``captured()`` is captured with
-    those launches reading their descriptors from there (ArgArena).  Returns (graph, arena); keep both alive."""
+    the fused-MLP launches' argument blocks are recorded, the blocks go to HBM (an arena of ``capacity`` bytes), then
+    ``captured()`` is captured with those launches reading their descriptors from there (ArgArena).  Returns
+    (graph, arena); keep both alive.  The only place that does warm-up, upload and capture.
+    (Capturing on a high-priority stream to favour the critical chain halves the throughput: measured 980 vs 1755
+    steps/s on the CPQ step -- every kernel of the step ran ~2x slower.)"""
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
-    arena = ArgArena(device)
+    arena = ArgArena(device, capacity)
     with torch.cuda.stream(s), arena.record():
         warm()
     torch.cuda.current_stream().wait_stream(s)
@@ -991,6 +994,29 @@ def capture_step(device, warm, captured):
     with graph_capture(g), arena.replay():
         captured()
     return g, arena
+
+
+def capture_restoring(device, issue, snapshot, restore, capacity: int = 1 << 18):
+    """``capture_step`` of ``issue()`` around a snapshot of the training state: the warm-up pass and the capture pass both
+    advance it, so ``restore(snapshot())`` ALWAYS runs -- also when the warm-up or the capture raises (a refused
+    data-parallel capture after which the caller falls back to eager launches, a failing body)."""
+    snap = snapshot()
+    try:
+        return capture_step(device, issue, issue, capacity)
+    finally:
+        torch.cuda.synchronize()
+        restore(snap)
+
+
+def scalar_state(model, engine=None) -> List[torch.Tensor]:
+    """The scalar training state beside the flat groups -- the one list of it: the dual variable, the PID integrators,
+    CDT's temperature, COptiDICE's scalar leaves (whichever the model has), and CDT's temperature moments, which live on
+    the engine.  What a capture snapshots (engine/_step.py) and what ``DataParallel.broadcast_model`` broadcasts."""
+    out = [t for t in (getattr(model, n, None) for n in ("log_alpha", "pid_state", "log_temperature", "scalar_leaves"))
+           if isinstance(t, torch.Tensor)]
+    if getattr(engine, "temp_mv", None) is not None:
+        out.append(engine.temp_mv)
+    return out
 
 
 FUSED_BEGIN = _plan.knob("OSRL_FUSED_BEGIN", "1", "tick + minibatch gather + noise as one prologue launch") == "1"

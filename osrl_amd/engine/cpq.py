@@ -12,8 +12,7 @@ Common sub-expressions the reference recomputes are evaluated once (exact, not a
 """
 from __future__ import annotations
 
-import os
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
@@ -21,7 +20,8 @@ from .. import _lib as L
 from ..common.net import actor_head_desc, net_desc_seq, vae_dec_desc, vae_enc_desc
 from . import glue as G
 from . import plan as P
-from .core import ArgArena, Branches, DwPlan, MlpRun, StepState, concat_nets, load_into, check_plans_current, graph_capture
+from ._step import PipelinedReplay, StepEngine, VaePhase
+from .core import Branches, DwPlan, MlpRun, StepState, concat_nets
 
 # Plan choices that depend on the shape live in engine/plan.py (cpq_plan: head tails, dW tiles, the all-CU VAE launches;
 # the measurements behind each rule are in DESIGN_LOG.md).  What is left here are lab switches of the plan's STRUCTURE:
@@ -58,7 +58,9 @@ STAT_KEYS = ["loss/loss_vae", "loss/critic_loss", "loss/cost_critic_loss", "loss
 NOISE_KEYS = ["eps_vae", "eps_next_c", "eps_next_cc", "eps_ood", "eps_actor"]
 
 
-class CPQEngine:
+class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
+    SIDE_STREAMS, PICK_FASTEST, DP_CAPTURE = 1, True, True
+
     def __init__(self, model, batch_size: int, rows_global: int = 0, seed: int = 0, dist=None):
         m = self.model = model
         B = self.B = int(batch_size)
@@ -97,14 +99,8 @@ class CPQEngine:
         # one flat noise buffer -> one Philox launch per step
         shapes = {"eps_vae": (B, Lz), "eps_next_c": (B, ad), "eps_next_cc": (B, ad), "eps_ood": (N, B, ad),
                   "eps_actor": (B, ad)}
-        tot = sum(int(torch.Size(s).numel()) for s in shapes.values())
-        self.noise_flat = z((tot + 3) // 4 * 4)
-        self.noise: Dict[str, torch.Tensor] = {}
-        o = 0
-        for k in NOISE_KEYS:
-            n = int(torch.Size(shapes[k]).numel())
-            self.noise[k] = self.noise_flat[o:o + n].view(shapes[k])
-            o += n
+        assert list(shapes) == NOISE_KEYS
+        self.noise_flat, self.noise = self.noise_layout(shapes, dev)
 
         # network descriptors (pointers into the flat groups)
         self.d_actor = actor_head_desc(m.actor)
@@ -118,13 +114,7 @@ class CPQEngine:
         m.repack()
 
         # ---- vae phase
-        self.r_enc = MlpRun(self.d_enc, B, True, dev)
-        self.r_dec = MlpRun(self.d_dec, B, True, dev)
-        self.z = z(B, Lz)
-        self.du = z(1, B, ad)
-        self.dhead_enc = z(1, B, 2 * Lz)
-        self.r_dec.setup_backward(self.du, dx_cols=(od, Lz))
-        self.r_enc.setup_backward(self.dhead_enc)
+        self._vae_runs(dev)
         # 1024 rows per split-K slab (the default policy gives 256): 140 tiles x 2 splits = 280 workgroups fit the 512
         # resident slots in one round (x 4 splits = 560: a second, almost empty round), and the Adam kernel sums two
         # slabs instead of four.  In the step: 2175 steps/s vs 2135 (4 splits), 2140 (3), 2015 (1); the other groups
@@ -209,8 +199,7 @@ class CPQEngine:
         if G.SEEDS and G.VAE_TAILS and max(nq, nqc) <= 4:
             y_old, y_pi = self.r_old_next.y, self.r_pi_q.y
             self.seeds = {
-                "vae": G.seed_vae(self.act, self.r_enc.y[0], B, ad, Lz, m.beta, rg, G.SeedStat(dev, 1, B),
-                                  st.stat_ptr("loss/loss_vae")),
+                "vae": self._vae_seed(dev),
                 "critic": G.seed_cpq_critic(y_old[:nq], nq, y_old[nq:], nqc, self.rew, self.done, B, m.gamma, m.q_thres,
                                             rg, G.SeedStat(dev, nq, B), st.stat_ptr("loss/critic_loss")),
                 "cost": G.seed_cpq_cost(self.r_costold_next.y, nqc, self.cost, B, m.gamma, rg, G.SeedStat(dev, nqc, B),
@@ -220,33 +209,14 @@ class CPQEngine:
                 "head": G.seed_gauss_head(self.noise["eps_actor"], self.tanh_u, self.r_pi_q.dx, nq, B, m.max_action),
             }
 
-        # round 5: the VAE phase's forward / backward as all-CU layer launches (csrc/vae_ns.hip, glue.VaeNs) where the plan
-        # says so (engine/plan.py vae_ns_auto: by measurement) and the library takes the shape
-        self.vae_ns = None
-        if self.seeds is not None and pl.vae_ns:
-            self.vae_ns = G.VaeNs.build(self.r_enc, self.r_dec, self.obs, self.act, self.noise["eps_vae"], self.z, Lz,
-                                        m.beta, rg, st.stat_ptr("loss/loss_vae"))
-
-        # every dW plan of this engine is built: the slab epochs they were built against are recorded NOW (not at the
-        # first step), so an engine that is constructed directly, never stepped and then superseded is flagged stale
-        from .core import slab_epochs
-        self._slab_epochs = slab_epochs(self.model)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.replay = None
+        self._vae_all_cu()  # (round 5)
+        self._plans_built()
         self.parallel_branches = True
-        self._graph_failed = False
         self._probe = None
 
     # ------------------------------------------------------------------ #
-    def _update(self, name: str, tau: float) -> None:
-        """(data parallel: all-reduce of the flat gradient, then) the fused Adam + Polyak + repack of one group."""
-        m = self.model
-        grp = m.groups[name]
-        if self.dist is not None:
-            self.dist.allreduce_group(grp)
-        grp.adam_step(m._lrs[name], self.st.ptr, tau=tau)
-
-    def _optim(self, name: str, plan: DwPlan, tau: float) -> None:
+    def _optim(self, name: str, plan: DwPlan, tau: float = 0.0, extra=None) -> None:
+        """(the base's, plus bench.py's ``vae_dw`` probe and the fused dW + Adam launch)"""
         if name == "vae":
             self._pr("vae_dw", 0)
         if self.dist is None and plan.can_fuse_adam():  # dW and the optimizer step in one launch (same bits)
@@ -257,7 +227,7 @@ class CPQEngine:
         plan.launch()
         if name == "vae":
             self._pr("vae_dw", 1)
-        self._update(name, tau)
+        self._update(name, tau, extra)
 
     def _pr(self, site: str, i: int) -> None:
         """bench.py's in-step probe: HIP events (on the launching stream) around a named launch of the step body."""
@@ -329,23 +299,7 @@ class CPQEngine:
             torch.cuda._sleep(self._stress_spin)  # (tests: the main chain arrives late)
         # ---- main: vae_loss  (cpq.py:125-135)
         sd = self.seeds
-        if self.vae_ns is not None:  # five all-CU layer launches instead of the four fused ones (same buffers)
-            self.vae_ns.forward()
-            self.vae_ns.backward()
-            head = self.r_enc.y[0]
-        else:
-            head = G.vae_encode(self.r_enc, self.obs, self.act, nz["eps_vae"], Lz, self.z)
-            u = self.r_dec.forward(self.obs, self.z)[0]
-        if self.vae_ns is not None:
-            pass
-        elif sd is not None:  # reconstruction gradient + the logged loss by the decoder's backward launch itself
-            self.r_dec.backward_dz(tail=G.vae_latent_bwd_tail(head, nz["eps_vae"], Lz, m.beta, rg, self.dhead_enc),
-                                   seed=sd["vae"])
-        else:
-            G.vae_loss(u, self.act, head, B, ad, Lz, m.beta, rg, self.du, st.stat_ptr("loss/loss_vae"))
-            G.vae_decoder_backward(self.r_dec, head, nz["eps_vae"], Lz, m.beta, rg, self.dhead_enc)
-        if self.vae_ns is None:
-            self.r_enc.backward_dz()
+        head = self._vae_phase(sd)
         if dp is not None and par.enabled and len(par.side) > 1 and DP_SIDE_COLL:
             # data parallel, round 5: nothing on the main branch reads the VAE's parameters in this step (its only reader
             # is the N*B-row encoder launch of the side branch), so the gradient's all-reduce and the optimizer step
@@ -481,11 +435,8 @@ class CPQEngine:
             m.groups["cost_critic"].adam_step(m._lrs["cost_critic"], st.ptr, tau=m.tau, polyak=False)
         elif dp is None:
             self._update("cost_critic", m.tau)
-        else:  # both critic groups' gradients in ONE collective (neither update reads the other's result)
-            gc, gcc = m.groups["critic"], m.groups["cost_critic"]
-            dp.all_reduce_many_([dp.reduce_local(gc), dp.reduce_local(gcc)])
-            gc.adam_step(m._lrs["critic"], st.ptr, tau=m.tau)
-            gcc.adam_step(m._lrs["cost_critic"], st.ptr, tau=m.tau)
+        else:
+            self._update_critics_dp()
 
         # ---- side branch, second half: the OOD statistic with the UPDATED vae
         # (round 4, measured and dropped: letting this launch wait for the cost critics' optimizer step instead -- so that it
@@ -601,9 +552,7 @@ class CPQEngine:
         else:  # actor gradient, the per-rank partial statistics and the partial qc_ood mean in one collective
             self.p_actor.launch()
             par.join(0)
-            ga = m.groups["actor"]
-            dp.all_reduce_many_([dp.reduce_local(ga), st.stats, self.ood_mean])
-            ga.adam_step(m._lrs["actor"], st.ptr, tau=m.tau)
+            self._update("actor", m.tau, extra=[st.stats, self.ood_mean])
         # dual step + the OOD term of the logged loss (cpq.py:186-195): after the join, so that the side branch has no
         # incoming edge from the main branch after the VAE's Adam (the graph executor keeps two linear chains); under
         # data parallelism the statistics are already the global ones here, so the global term is added once
@@ -620,138 +569,7 @@ class CPQEngine:
         G.cpq_alpha_step(self.ood_mean, m.qc_thres, m.alpha_lr, 1.0, m.log_alpha, self.st.stat_ptr("loss/cost_critic_loss"))
         self._dual_pending = False
 
-    # ------------------------------------------------------------------ #
-    def load_batch(self, observations, next_observations, actions, rewards, costs, done) -> None:
-        load_into(((self.obs, observations), (self.nobs, next_observations), (self.act, actions),
-                   (self.rew, rewards), (self.cost, costs), (self.done, done)))
-
-    def load_noise(self, noise: Dict[str, torch.Tensor]) -> None:
-        for k in NOISE_KEYS:
-            self.noise[k].copy_(torch.as_tensor(noise[k]).reshape(self.noise[k].shape), non_blocking=True)
-
-    def capture(self) -> None:
-        """Capture one step into a hipGraph -- on one GPU a few times over, keeping the graph whose replays are fastest
-        (core.pick_fastest: the branch -> hardware-queue mapping of a capture depends on the streams created before it)."""
-        from .core import CAPTURE_TRIES, pick_fastest
-
-        def replay(c):
-            c[0].replay()
-
-        tries = CAPTURE_TRIES if (self.dist is None and self.parallel_branches) else 1
-        (self.graph, self._par, self._arena), self.capture_ms = pick_fastest(self._capture_once, replay, self._snapshot,
-                                                                              self._restore, tries)
-
-    def _capture_once(self):
-        """Capture one step (device-drawn noise) into a hipGraph.  Warm-up launches run first on a
-        side stream as torch requires; the model state they advance is restored afterwards."""
-        snap = self._snapshot()
+    def _branches(self) -> Branches:
         # data parallel: the side branch holds no collective (the critic group's all-reduce + Adam run on the
         # capture stream after the join), so every rank issues its RCCL calls in the same order on one stream
-        par = Branches(self.parallel_branches, 2 if self.dist is not None else 1)
-        try:  # the warm-up pass and the capture pass both advance the model: ALWAYS put the snapshot back, also
-            # when the capture is refused and the caller falls back to eager launches
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            arena = ArgArena(self.dev)  # the fused-MLP launches' descriptors live in HBM (core.ArgArena)
-            with torch.cuda.stream(s), arena.record():
-                self.body(True, par)
-            torch.cuda.current_stream().wait_stream(s)
-            arena.upload()
-            g = torch.cuda.CUDAGraph()
-            # (capturing on a high-priority stream to favour the critical chain halves the throughput: measured 980
-            # vs 1755 steps/s -- every kernel of the step ran ~2x slower)
-            with graph_capture(g), arena.replay():
-                self.body(True, par)
-        finally:
-            torch.cuda.synchronize()
-            self._restore(snap)
-        return g, par, arena  # (the side streams and the argument blocks its kernels read stay alive with the graph)
-
-    def _snapshot(self):
-        m = self.model
-        snap = {"log_alpha": m.log_alpha.clone(), "state": self.st.state.clone(), "host": self.st.host_step,
-                "stats": self.st.stats.clone(), "ring": self.st.ring.clone()}
-        for n, g in m.groups.items():
-            snap[n] = (g.p.clone(), g.m.clone(), g.v.clone(), None if g.tgt is None else g.tgt.clone())
-        return snap
-
-    def _restore(self, snap) -> None:
-        m = self.model
-        m.log_alpha.copy_(snap["log_alpha"])
-        self.st.state.copy_(snap["state"])
-        self.st.stats.copy_(snap["stats"])
-        self.st.ring.copy_(snap["ring"])
-        self.st.host_step = snap["host"]
-        for n, g in m.groups.items():
-            p, mm, v, t = snap[n]
-            g.p.copy_(p)
-            g.m.copy_(mm)
-            g.v.copy_(v)
-            if t is not None:
-                g.tgt.copy_(t)
-        m.repack()
-
-    def attach_replay(self, store) -> None:
-        """Sample minibatches on device from ``store`` (common/replay.py) inside the step itself."""
-        self.replay = store
-        self.graph = None
-        self._pipe = None
-
-    def _run(self, use_graph: bool) -> None:
-        """Replay the captured step (capturing it first).  With a DataParallel hook the RCCL collectives
-        are captured into the same hipGraph; if the runtime refuses (older RCCL), fall back to eager."""
-        if self.dist is not None and os.environ.get("OSRL_DP_EAGER") == "1":
-            use_graph = False  # operator override: run the data-parallel step without capturing its collectives
-        if use_graph and not self._graph_failed:
-            if self.graph is None:
-                ok = True
-                try:
-                    self.capture()
-                except Exception as e:  # pragma: no cover - depends on the RCCL build
-                    if self.dist is None:
-                        raise
-                    import warnings
-                    warnings.warn(f"hipGraph capture of the data-parallel step failed ({e!r}); running eagerly")
-                    ok = False
-                if self.dist is not None and not self.dist.all_agree(ok, self.dev):
-                    self._graph_failed, self.graph = True, None  # every rank runs eagerly, or none does
-            if self.graph is not None:
-                self.graph.replay()
-                self.st.host_step += 1
-                return
-        self.body(True)
-
-    def steps_replay(self, n: int, steps_per_graph: Optional[int] = None) -> None:
-        """EXACTLY ``n`` train steps on minibatches drawn on device from the attached replay store.  Where the plan says so
-        (``plan.steps_per_graph`` > 1, single GPU) whole multiples go through graphs of that many steps, software-pipelined
-        across steps (engine/pipeline.py: bit-equal to ``n`` calls of ``step_replay()``); the remainder through the
-        one-step graph.  The loop of examples/train/train_cpq.py:138-144 / train_bcql.py:142-148 with the DataLoader
-        folded into the step."""
-        spg = int(self.plan.steps_per_graph if steps_per_graph is None else steps_per_graph)
-        if spg <= 1 or self.dist is not None:
-            for _ in range(int(n)):
-                self.step_replay(True)
-            return
-        pipe = getattr(self, "_pipe", None)
-        if pipe is None or pipe.n != spg:
-            from .pipeline import PipelinedSteps
-            pipe = self._pipe = PipelinedSteps(self, spg)
-        pipe.run(n)
-
-    def step_replay(self, use_graph: bool = True) -> None:
-        """One train step on a minibatch drawn on device from the attached replay store."""
-        check_plans_current(self)
-        assert self.replay is not None
-        self._run(use_graph)
-
-    def step(self, observations, next_observations, actions, rewards, costs, done, noise=None,
-             use_graph: bool = True) -> None:
-        check_plans_current(self)
-        if self.replay is not None:
-            raise RuntimeError("a replay store is attached: call step_replay() (or attach_replay(None))")
-        self.load_batch(observations, next_observations, actions, rewards, costs, done)
-        if noise is not None:
-            self.load_noise(noise)
-            self.body(False)
-            return
-        self._run(use_graph)
+        return Branches(self.parallel_branches, 2 if self.dist is not None else 1)

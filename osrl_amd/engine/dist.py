@@ -25,7 +25,7 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib as L
-from .core import FlatGroup, cur_stream
+from .core import FlatGroup, cur_stream, scalar_state
 
 
 class DataParallel:
@@ -114,15 +114,12 @@ class DataParallel:
             for buf in (g.p, g.m, g.v, g.tgt):
                 if buf is not None:
                     self.broadcast_(buf)
-        for name in ("log_alpha", "pid_state", "log_temperature", "scalar_leaves"):
-            if isinstance(getattr(model, name, None), torch.Tensor):
-                self.broadcast_(getattr(model, name))
+        for t in scalar_state(model, engine):  # (the list a capture snapshots: engine/core.py)
+            self.broadcast_(t)
         if engine is not None:
             step = torch.tensor([engine.st.device_step()], dtype=torch.int64, device=engine.st.state.device)
             self.broadcast_(step)
             engine.st.set_step(int(step.item()))
-            if getattr(engine, "temp_mv", None) is not None:
-                self.broadcast_(engine.temp_mv)
         model.repack()  # the kernels read fragment-ordered copies of the weights: refresh them from the new values
 
     # ---- hooks used by the step engines ----

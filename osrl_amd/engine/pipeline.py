@@ -26,7 +26,7 @@ from typing import Optional
 
 import torch
 
-from .core import ArgArena, Branches, graph_capture, slab_epochs, check_plans_current
+from .core import Branches, capture_restoring, slab_epochs, check_plans_current
 
 STEPS_PER_GRAPH = 4  # (default of PipelinedSteps(engine); engines take their plan's steps_per_graph, engine/plan.py)
 
@@ -86,27 +86,9 @@ class PipelinedSteps:
                                                                               self._snapshot, self._restore, CAPTURE_TRIES)
 
     def _capture_once(self):
-        e0, e1 = self.e
-        dev = e0.st.state.device
-        snap = e0._snapshot()
-        snap1 = (e1.st.state.clone(), e1.st.stats.clone())
         par = Branches(True, 1)
-        try:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            arena = ArgArena(dev, capacity=1 << 20)
-            with torch.cuda.stream(s), arena.record():
-                self._issue(par)
-            torch.cuda.current_stream().wait_stream(s)
-            arena.upload()
-            g = torch.cuda.CUDAGraph()
-            with graph_capture(g), arena.replay():
-                self._issue(par)
-        finally:
-            torch.cuda.synchronize()
-            e0._restore(snap)
-            e1.st.state.copy_(snap1[0])
-            e1.st.stats.copy_(snap1[1])
+        g, arena = capture_restoring(self.e[0].st.state.device, lambda: self._issue(par), self._snapshot, self._restore,
+                                     capacity=1 << 20)  # (n steps' argument blocks)
         return g, par, arena
 
     def run(self, n_steps: int) -> None:
