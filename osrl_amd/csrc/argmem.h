@@ -18,7 +18,12 @@
 //                 make) is counted and launched by value -- correct, just not arena-resident.
 // The context is thread-local and opt-in (osrl_args_begin / osrl_args_end); without it every launch is by value as
 // before, so the stateless C ABI is unchanged for callers that do not use it.
+//
+// launch() below is the ONE launch path of every kernel that has a "_p" twin: look the descriptor up, pick the twin, raise
+// the dynamic-LDS limit where the launch needs it, launch one of the two.  The LDS rule: a launch may use up to 64 KB of
+// dynamic LDS as it is; only above that is hipFuncAttributeMaxDynamicSharedMemorySize set on the kernel about to start.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -75,6 +80,24 @@ inline const void* slot_bytes(const void* a, int64_t size) {
 template <class A>
 inline const void* slot(const A& a) {
   return slot_bytes(&a, (int64_t)sizeof(A));
+}
+
+// launch `k(a)` or, when the calling thread's arena holds an uploaded copy of `a`, `kp(address of that copy)`.
+// kp == nullptr: a kernel without a twin -- no lookup (so nothing is recorded), always by value.
+template <class K, class A>
+inline int launch(K k, void (*kp)(const void*), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const A& a) {
+  const void* dev = kp ? slot(a) : nullptr;
+  if (lds_bytes > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(dev ? reinterpret_cast<const void*>(kp) : reinterpret_cast<const void*>(k),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+  }
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  if (dev)
+    hipLaunchKernelGGL(kp, grid, block, lds_bytes, stream, dev);
+  else
+    hipLaunchKernelGGL(k, grid, block, lds_bytes, stream, a);
+  return (int)hipGetLastError();
 }
 
 }  // namespace osrl_argmem

@@ -203,18 +203,15 @@ __device__ __forceinline__ void vae_loss_body(const float* __restrict__ u, const
   kl = block_sum(kl, sm);
   if (threadIdx.x == 0 && stat) stat[0] = rec * ia + beta * (kl * il);
 }
-__global__ __launch_bounds__(kRed) void vae_loss_kernel(const float* __restrict__ u, const float* __restrict__ act,
-                                                        const float* __restrict__ head, int rows, int ad, int L,
-                                                        float beta, float inv_rows, float* __restrict__ du,
-                                                        float* __restrict__ stat) {
-  vae_loss_body(u, act, head, rows, ad, L, beta, inv_rows, du, stat);
-}
 struct VaeLossArgs {
   const float *u, *act, *head;
   float *du, *stat;
   int32_t rows, ad, L;
   float beta, inv_rows;
 };
+__global__ __launch_bounds__(kRed) void vae_loss_kernel(const VaeLossArgs a) {
+  vae_loss_body(a.u, a.act, a.head, a.rows, a.ad, a.L, a.beta, a.inv_rows, a.du, a.stat);
+}
 __global__ __launch_bounds__(kRed) void vae_loss_kernel_p(const void* p) {
   const OSRL_CAS VaeLossArgs& a = *(const OSRL_CAS VaeLossArgs*)p;
   vae_loss_body(a.u, a.act, a.head, a.rows, a.ad, a.L, a.beta, a.inv_rows, a.du, a.stat);
@@ -663,22 +660,17 @@ __device__ __forceinline__ void cpq_critic_loss_body(const float* __restrict__ q
   loss = block_sum(loss, sm);
   if (threadIdx.x == 0 && stat) stat[0] = loss * inv_rows;
 }
-template <bool SMALL>
-__global__ __launch_bounds__(kRed) void cpq_critic_loss_kernel(const float* __restrict__ q_old, int n_q_old,
-                                                               const float* __restrict__ qc_old, int n_qc_old,
-                                                               const float* __restrict__ q, int n_q,
-                                                               const float* __restrict__ rew,
-                                                               const float* __restrict__ done, int rows,
-                                                               float gamma, float q_thres, float inv_rows,
-                                                               float* __restrict__ dq, float* __restrict__ stat) {
-  cpq_critic_loss_body<SMALL>(q_old, n_q_old, qc_old, n_qc_old, q, n_q, rew, done, rows, gamma, q_thres, inv_rows, dq, stat);
-}
 struct CriticLossArgs {
   const float *q_old, *qc_old, *q, *rew, *done;
   float *dq, *stat;
   int32_t n_q_old, n_qc_old, n_q, rows;
   float gamma, q_thres, inv_rows;
 };
+template <bool SMALL>
+__global__ __launch_bounds__(kRed) void cpq_critic_loss_kernel(const CriticLossArgs a) {
+  cpq_critic_loss_body<SMALL>(a.q_old, a.n_q_old, a.qc_old, a.n_qc_old, a.q, a.n_q, a.rew, a.done, a.rows, a.gamma,
+                              a.q_thres, a.inv_rows, a.dq, a.stat);
+}
 template <bool SMALL>
 __global__ __launch_bounds__(kRed) void cpq_critic_loss_kernel_p(const void* p) {
   const OSRL_CAS CriticLossArgs& a = *(const OSRL_CAS CriticLossArgs*)p;
@@ -851,15 +843,6 @@ __device__ __forceinline__ void cpq_cost_loss_body(
     if (stat) stat[1] = stat_share * expf(la);
   }
 }
-template <bool SMALL>
-__global__ __launch_bounds__(kRed) void cpq_cost_loss_kernel(
-    const float* __restrict__ qc_old_next, int n_qc_old, const float* __restrict__ qc, int n_qc,
-    float* __restrict__ ood_mean_p, const float* __restrict__ cost, int rows, float gamma, float qc_thres,
-    float alpha_lr, float inv_rows, float stat_share, float* __restrict__ log_alpha, float* __restrict__ dq,
-    float* __restrict__ stat, const OodArgs oa) {
-  cpq_cost_loss_body<SMALL>(qc_old_next, n_qc_old, qc, n_qc, ood_mean_p, cost, rows, gamma, qc_thres, alpha_lr, inv_rows,
-                            stat_share, log_alpha, dq, stat, oa);
-}
 struct CostLossArgs {
   const float *qc_old_next, *qc, *cost;
   float *ood_mean_p, *log_alpha, *dq, *stat;
@@ -867,6 +850,11 @@ struct CostLossArgs {
   int32_t n_qc_old, n_qc, rows;
   float gamma, qc_thres, alpha_lr, inv_rows, stat_share;
 };
+template <bool SMALL>
+__global__ __launch_bounds__(kRed) void cpq_cost_loss_kernel(const CostLossArgs a) {
+  cpq_cost_loss_body<SMALL>(a.qc_old_next, a.n_qc_old, a.qc, a.n_qc, a.ood_mean_p, a.cost, a.rows, a.gamma, a.qc_thres,
+                            a.alpha_lr, a.inv_rows, a.stat_share, a.log_alpha, a.dq, a.stat, a.oa);
+}
 template <bool SMALL>
 __global__ __launch_bounds__(kRed) void cpq_cost_loss_kernel_p(const void* p) {
   const OSRL_CAS CostLossArgs& a = *(const OSRL_CAS CostLossArgs*)p;
@@ -1247,20 +1235,11 @@ int osrl_vae_latent(const float* head, const float* eps, int32_t rows, int32_t L
 int osrl_vae_loss(const float* u, const float* act, const float* head, int32_t rows, int32_t ad, int32_t L,
                   float beta, int32_t rows_global, float* du, float* stat, void* stream) {
   if (!u || !act || !head || !du || rows < 1) return -1;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  const float inv = 1.0f / (float)(rows_global > 0 ? rows_global : rows);
-  const void* dev_args = nullptr;
-  if (osrl_argmem::current()) {
-    VaeLossArgs a{};
-    a.u = u; a.act = act; a.head = head; a.du = du; a.stat = stat;
-    a.rows = rows; a.ad = ad; a.L = L; a.beta = beta; a.inv_rows = inv;
-    dev_args = osrl_argmem::slot(a);
-  }
-  if (dev_args)
-    hipLaunchKernelGGL(vae_loss_kernel_p, dim3(1), dim3(kRed), 0, S, dev_args);
-  else
-    hipLaunchKernelGGL(vae_loss_kernel, dim3(1), dim3(kRed), 0, S, u, act, head, rows, ad, L, beta, inv, du, stat);
-  LAUNCH_CHECK();
+  VaeLossArgs a{};
+  a.u = u; a.act = act; a.head = head; a.du = du; a.stat = stat;
+  a.rows = rows; a.ad = ad; a.L = L; a.beta = beta;
+  a.inv_rows = 1.0f / (float)(rows_global > 0 ? rows_global : rows);
+  return osrl_argmem::launch(vae_loss_kernel, vae_loss_kernel_p, dim3(1), dim3(kRed), 0, S, a);
 }
 
 int osrl_vae_latent_bwd(const float* head, const float* eps, const float* dz, int32_t rows, int32_t L, float beta,
@@ -1304,29 +1283,13 @@ int osrl_cpq_critic_loss(const float* q_old, int32_t n_q_old, const float* qc_ol
                          const float* q, int32_t n_q, const float* rew, const float* done, int32_t rows,
                          float gamma, float q_thres, int32_t rows_global, float* dq, float* stat, void* stream) {
   if (!q_old || !qc_old || !q || !rew || !done || !dq || rows < 1) return -1;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  const float inv = 1.0f / (float)(rows_global > 0 ? rows_global : rows);
-  const bool small = n_q_old <= kEns && n_qc_old <= kEns && n_q <= kEns;
-  if (osrl_argmem::current()) {
-    CriticLossArgs a{};
-    a.q_old = q_old; a.qc_old = qc_old; a.q = q; a.rew = rew; a.done = done; a.dq = dq; a.stat = stat;
-    a.n_q_old = n_q_old; a.n_qc_old = n_qc_old; a.n_q = n_q; a.rows = rows;
-    a.gamma = gamma; a.q_thres = q_thres; a.inv_rows = inv;
-    if (const void* dev_args = osrl_argmem::slot(a)) {
-      if (small)
-        hipLaunchKernelGGL(cpq_critic_loss_kernel_p<true>, dim3(1), dim3(kRed), 0, S, dev_args);
-      else
-        hipLaunchKernelGGL(cpq_critic_loss_kernel_p<false>, dim3(1), dim3(kRed), 0, S, dev_args);
-      LAUNCH_CHECK();
-    }
-  }
-  if (small)
-    hipLaunchKernelGGL(cpq_critic_loss_kernel<true>, dim3(1), dim3(kRed), 0, S, q_old, n_q_old, qc_old, n_qc_old, q, n_q,
-                       rew, done, rows, gamma, q_thres, inv, dq, stat);
-  else
-    hipLaunchKernelGGL(cpq_critic_loss_kernel<false>, dim3(1), dim3(kRed), 0, S, q_old, n_q_old, qc_old, n_qc_old, q,
-                       n_q, rew, done, rows, gamma, q_thres, inv, dq, stat);
-  LAUNCH_CHECK();
+  CriticLossArgs a{};
+  a.q_old = q_old; a.qc_old = qc_old; a.q = q; a.rew = rew; a.done = done; a.dq = dq; a.stat = stat;
+  a.n_q_old = n_q_old; a.n_qc_old = n_qc_old; a.n_q = n_q; a.rows = rows;
+  a.gamma = gamma; a.q_thres = q_thres; a.inv_rows = 1.0f / (float)(rows_global > 0 ? rows_global : rows);
+  if (n_q_old <= kEns && n_qc_old <= kEns && n_q <= kEns)
+    return osrl_argmem::launch(cpq_critic_loss_kernel<true>, cpq_critic_loss_kernel_p<true>, dim3(1), dim3(kRed), 0, S, a);
+  return osrl_argmem::launch(cpq_critic_loss_kernel<false>, cpq_critic_loss_kernel_p<false>, dim3(1), dim3(kRed), 0, S, a);
 }
 
 int osrl_cpq_ood_mean(const float* qc_sampled, int32_t n_qc_old, const float* kl, const float* quantile,
@@ -1380,32 +1343,14 @@ int osrl_cpq_cost_loss(const float* qc_old_next, int32_t n_qc_old, const float* 
                        float alpha_lr, int32_t rows_global, float stat_share, float* log_alpha, float* dq,
                        float* stat, void* stream) {
   if (!qc_old_next || !qc || !cost || (ood_mean && !log_alpha) || !dq || rows < 1) return -1;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  const float inv = 1.0f / (float)(rows_global > 0 ? rows_global : rows);
-  const bool small = n_qc_old <= kEns && n_qc <= kEns;
-  if (osrl_argmem::current()) {
-    CostLossArgs a{};
-    a.qc_old_next = qc_old_next; a.qc = qc; a.cost = cost; a.ood_mean_p = const_cast<float*>(ood_mean);
-    a.log_alpha = log_alpha; a.dq = dq; a.stat = stat; a.oa = OodArgs{nullptr, nullptr, nullptr, 0, 0};
-    a.n_qc_old = n_qc_old; a.n_qc = n_qc; a.rows = rows; a.gamma = gamma; a.qc_thres = qc_thres;
-    a.alpha_lr = alpha_lr; a.inv_rows = inv; a.stat_share = stat_share;
-    if (const void* dev_args = osrl_argmem::slot(a)) {
-      if (small)
-        hipLaunchKernelGGL(cpq_cost_loss_kernel_p<true>, dim3(1), dim3(kRed), 0, S, dev_args);
-      else
-        hipLaunchKernelGGL(cpq_cost_loss_kernel_p<false>, dim3(1), dim3(kRed), 0, S, dev_args);
-      LAUNCH_CHECK();
-    }
-  }
-  if (small)
-    hipLaunchKernelGGL(cpq_cost_loss_kernel<true>, dim3(1), dim3(kRed), 0, S, qc_old_next, n_qc_old, qc, n_qc,
-                       const_cast<float*>(ood_mean), cost, rows, gamma, qc_thres, alpha_lr, inv, stat_share, log_alpha,
-                       dq, stat, OodArgs{nullptr, nullptr, nullptr, 0, 0});
-  else
-    hipLaunchKernelGGL(cpq_cost_loss_kernel<false>, dim3(1), dim3(kRed), 0, S, qc_old_next, n_qc_old, qc, n_qc,
-                       const_cast<float*>(ood_mean), cost, rows, gamma, qc_thres, alpha_lr, inv, stat_share, log_alpha,
-                       dq, stat, OodArgs{nullptr, nullptr, nullptr, 0, 0});
-  LAUNCH_CHECK();
+  CostLossArgs a{};
+  a.qc_old_next = qc_old_next; a.qc = qc; a.cost = cost; a.ood_mean_p = const_cast<float*>(ood_mean);
+  a.log_alpha = log_alpha; a.dq = dq; a.stat = stat;
+  a.n_qc_old = n_qc_old; a.n_qc = n_qc; a.rows = rows; a.gamma = gamma; a.qc_thres = qc_thres;
+  a.alpha_lr = alpha_lr; a.inv_rows = 1.0f / (float)(rows_global > 0 ? rows_global : rows); a.stat_share = stat_share;
+  if (n_qc_old <= kEns && n_qc <= kEns)
+    return osrl_argmem::launch(cpq_cost_loss_kernel<true>, cpq_cost_loss_kernel_p<true>, dim3(1), dim3(kRed), 0, S, a);
+  return osrl_argmem::launch(cpq_cost_loss_kernel<false>, cpq_cost_loss_kernel_p<false>, dim3(1), dim3(kRed), 0, S, a);
 }
 
 int osrl_cpq_alpha_step(const float* ood_mean, float qc_thres, float alpha_lr, float stat_share, float* log_alpha,
@@ -1424,16 +1369,15 @@ int osrl_cpq_cost_loss_ood(const float* qc_sampled, int32_t n_qc_sampled, const 
   if (!qc_sampled || !kl || !quantile || n_samples < 1 || !qc_old_next || !qc || !ood_mean_out || !cost ||
       !log_alpha || !dq || rows < 1)
     return -1;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  CostLossArgs a{};
+  a.qc_old_next = qc_old_next; a.qc = qc; a.cost = cost; a.ood_mean_p = ood_mean_out;
+  a.log_alpha = log_alpha; a.dq = dq; a.stat = stat; a.oa = OodArgs{qc_sampled, kl, quantile, n_qc_sampled, n_samples};
+  a.n_qc_old = n_qc_old; a.n_qc = n_qc; a.rows = rows; a.gamma = gamma; a.qc_thres = qc_thres;
+  a.alpha_lr = alpha_lr; a.inv_rows = 1.0f / (float)rows; a.stat_share = 1.0f;
+  // always by value (no twin given): this launch has never gone through the argument arena
   if (n_qc_old <= kEns && n_qc <= kEns && n_qc_sampled <= kEns)
-    hipLaunchKernelGGL(cpq_cost_loss_kernel<true>, dim3(1), dim3(kRed), 0, S, qc_old_next, n_qc_old, qc, n_qc,
-                       ood_mean_out, cost, rows, gamma, qc_thres, alpha_lr, 1.0f / (float)rows, 1.0f, log_alpha, dq, stat,
-                       OodArgs{qc_sampled, kl, quantile, n_qc_sampled, n_samples});
-  else
-    hipLaunchKernelGGL(cpq_cost_loss_kernel<false>, dim3(1), dim3(kRed), 0, S, qc_old_next, n_qc_old, qc, n_qc,
-                       ood_mean_out, cost, rows, gamma, qc_thres, alpha_lr, 1.0f / (float)rows, 1.0f, log_alpha, dq, stat,
-                       OodArgs{qc_sampled, kl, quantile, n_qc_sampled, n_samples});
-  LAUNCH_CHECK();
+    return osrl_argmem::launch(cpq_cost_loss_kernel<true>, nullptr, dim3(1), dim3(kRed), 0, S, a);
+  return osrl_argmem::launch(cpq_cost_loss_kernel<false>, nullptr, dim3(1), dim3(kRed), 0, S, a);
 }
 
 int osrl_cpq_actor_loss(const float* q, int32_t n_q, const float* qc, int32_t n_qc, int32_t rows, float q_thres,

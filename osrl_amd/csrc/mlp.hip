@@ -594,21 +594,22 @@ __global__ __launch_bounds__(256, waves_per_simd(NRB, NCB)) void mlp_fwd_loop_ke
 // Two independent forward problems (different networks / inputs, same tile shape) in ONE launch: the 2048-row
 // training launches of a step are 128 row tiles x 1-4 nets each, i.e. at most one workgroup per CU and a serial
 // latency chain inside it; pairing two of them fills the idle CUs and removes a launch from the critical path.
-template <int NRB, int NCB, int NW = 4>
-__global__ __launch_bounds__(64 * NW, (NW == 8 ? (NCB <= 2 ? 4 : 2) : waves_per_simd(NRB, NCB))) void mlp_fwd2_kernel(
-    const FwdArgs a0, const FwdArgs a1, int nets0, int tiles0, int tiles1) {
-  if ((int)blockIdx.y < nets0) {
-    if ((int)blockIdx.x >= tiles0) return;  // whole workgroup leaves before any barrier
-    mlp_fwd_body<NRB, NCB, NW, const FwdArgs&>(a0, blockIdx.y, blockIdx.x);
-  } else {
-    if ((int)blockIdx.x >= tiles1) return;
-    mlp_fwd_body<NRB, NCB, NW, const FwdArgs&>(a1, blockIdx.y - nets0, blockIdx.x);
-  }
-}
-struct Fwd2Args {  // device-resident form of the pair launch (argmem.h)
+struct Fwd2Args {
   FwdArgs a0, a1;
   int32_t nets0, tiles0, tiles1, pad_;
 };
+template <int NRB, int NCB, int NW = 4>
+__global__ __launch_bounds__(64 * NW, (NW == 8 ? (NCB <= 2 ? 4 : 2) : waves_per_simd(NRB, NCB))) void mlp_fwd2_kernel(
+    const Fwd2Args f) {
+  if ((int)blockIdx.y < f.nets0) {
+    if ((int)blockIdx.x >= f.tiles0) return;  // whole workgroup leaves before any barrier
+    mlp_fwd_body<NRB, NCB, NW, const FwdArgs&>(f.a0, blockIdx.y, blockIdx.x);
+  } else {
+    if ((int)blockIdx.x >= f.tiles1) return;
+    mlp_fwd_body<NRB, NCB, NW, const FwdArgs&>(f.a1, blockIdx.y - f.nets0, blockIdx.x);
+  }
+}
+// (the twin spells the same branches out again: behind one shared template its scalar registers came out renumbered)
 template <int NRB, int NCB, int NW = 4>
 __global__ __launch_bounds__(64 * NW, (NW == 8 ? (NCB <= 2 ? 4 : 2) : waves_per_simd(NRB, NCB))) void mlp_fwd2_kernel_p(
     const void* p) {
@@ -1687,19 +1688,7 @@ int launch_tiles(K kernel, void (*kernel_p)(const void*), const Args& args, int 
   const size_t lds_bytes = (size_t)BM * lda * sizeof(float);
   int tiles = (rows + BM - 1) / BM;
   if (wg_cap > 0 && tiles * nets > wg_cap) tiles = (wg_cap + nets - 1) / nets;  // forward kernel loops over tiles
-  dim3 grid(tiles, nets, 1);
-  const void* dev_args = kernel_p ? osrl_argmem::slot(args) : nullptr;
-  if (lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(dev_args ? reinterpret_cast<const void*>(kernel_p) : reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (dev_args)
-    hipLaunchKernelGGL(kernel_p, grid, dim3(threads), lds_bytes, stream, dev_args);
-  else
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds_bytes, stream, args);
-  return (int)hipGetLastError();
+  return osrl_argmem::launch(kernel, kernel_p, dim3(tiles, nets, 1), dim3(threads), lds_bytes, stream, args);
 }
 template <typename Args, typename K>
 int launch_tiles(K kernel, const Args& args, int rows, int nets, int nrb, int lda, hipStream_t stream,
@@ -2332,29 +2321,14 @@ static int launch_fwd2(const FwdArgs& a0, const FwdArgs& a1, int nets0, int nets
   const int BM = 16 * NRB;
   const int t0 = (rows0 + BM - 1) / BM, t1 = (rows1 + BM - 1) / BM;
   const size_t lds_bytes = (size_t)BM * lda * sizeof(float);
-  const void* dev_args = nullptr;
-  if (osrl_argmem::current()) {
-    Fwd2Args f{};
-    f.a0 = a0;
-    f.a1 = a1;
-    f.nets0 = nets0;
-    f.tiles0 = t0;
-    f.tiles1 = t1;
-    dev_args = osrl_argmem::slot(f);
-  }
-  if (lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(dev_args ? reinterpret_cast<const void*>(mlp_fwd2_kernel_p<NRB, NCB, NW>)
-                                                : reinterpret_cast<const void*>(mlp_fwd2_kernel<NRB, NCB, NW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  (void)hipGetLastError();
-  const dim3 grid(t0 > t1 ? t0 : t1, nets0 + nets1, 1);
-  if (dev_args)
-    hipLaunchKernelGGL((mlp_fwd2_kernel_p<NRB, NCB, NW>), grid, dim3(64 * NW), lds_bytes, stream, dev_args);
-  else
-    hipLaunchKernelGGL((mlp_fwd2_kernel<NRB, NCB, NW>), grid, dim3(64 * NW), lds_bytes, stream, a0, a1, nets0, t0, t1);
-  return (int)hipGetLastError();
+  Fwd2Args f{};
+  f.a0 = a0;
+  f.a1 = a1;
+  f.nets0 = nets0;
+  f.tiles0 = t0;
+  f.tiles1 = t1;
+  return osrl_argmem::launch(mlp_fwd2_kernel<NRB, NCB, NW>, mlp_fwd2_kernel_p<NRB, NCB, NW>,
+                             dim3(t0 > t1 ? t0 : t1, nets0 + nets1, 1), dim3(64 * NW), lds_bytes, stream, f);
 }
 
 static int mlp_forward2_impl(const osrl_mlp_t* net0, const osrl_rows_t* in0, const osrl_mlp_acts_t* out0,
@@ -2622,17 +2596,8 @@ extern "C" int osrl_mlp_backward_dz_seed(const osrl_mlp_t* net, int32_t rows, co
 // ---- host side of mlp_step_kernel ---------------------------------------------------------------------------------
 template <int NCB>
 static int launch_step(const StepArgs& k, size_t lds_bytes, hipStream_t stream) {
-  const void* dev_args = osrl_argmem::slot(k);
-  hipError_t e = hipFuncSetAttribute(dev_args ? reinterpret_cast<const void*>(mlp_step_kernel_p<NCB>)
-                                              : reinterpret_cast<const void*>(mlp_step_kernel<NCB>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (e != hipSuccess) return (int)e;
-  (void)hipGetLastError();
-  if (dev_args)
-    hipLaunchKernelGGL(mlp_step_kernel_p<NCB>, dim3(k.n_wg), dim3(kStepThreads), lds_bytes, stream, dev_args);
-  else
-    hipLaunchKernelGGL(mlp_step_kernel<NCB>, dim3(k.n_wg), dim3(kStepThreads), lds_bytes, stream, k);
-  return (int)hipGetLastError();
+  return osrl_argmem::launch(mlp_step_kernel<NCB>, mlp_step_kernel_p<NCB>, dim3(k.n_wg), dim3(kStepThreads), lds_bytes,
+                             stream, k);
 }
 
 #ifdef OSRL_STEP_STAMPS

@@ -754,17 +754,7 @@ extern "C" int osrl_mlp_backward_dw_tiles(const osrl_dw_entry_t* d_entries, cons
 
 template <int T>
 static int launch_dwt_adam(const DwAdamArgs& a, int32_t n_work, hipStream_t stream) {
-  const void* dev_args = osrl_argmem::slot(a);
-  hipError_t e = hipFuncSetAttribute(dev_args ? reinterpret_cast<const void*>(mlp_dwt_adam_kernel_p<T>)
-                                              : reinterpret_cast<const void*>(mlp_dwt_adam_kernel<T>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)dwt_lds<T>());
-  if (e != hipSuccess) return (int)e;
-  (void)hipGetLastError();
-  if (dev_args)
-    hipLaunchKernelGGL(mlp_dwt_adam_kernel_p<T>, dim3(n_work), dim3(256), dwt_lds<T>(), stream, dev_args);
-  else
-    hipLaunchKernelGGL(mlp_dwt_adam_kernel<T>, dim3(n_work), dim3(256), dwt_lds<T>(), stream, a);
-  return (int)hipGetLastError();
+  return osrl_argmem::launch(mlp_dwt_adam_kernel<T>, mlp_dwt_adam_kernel_p<T>, dim3(n_work), dim3(256), dwt_lds<T>(), stream, a);
 }
 
 extern "C" int osrl_mlp_backward_dw_tiles_adam(const osrl_dw_entry_t* d_entries, const int32_t* d_work,

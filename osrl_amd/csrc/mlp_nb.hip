@@ -769,17 +769,8 @@ __global__ __launch_bounds__(512, 2) void mlp_fwd_nb8n_kernel_p(const void* p) {
 // ---- host side of mlp_fwd_nb_kernel: eligibility + launch (tile_rows = 80) ------------------------------------
 template <int NCB, bool SHARED = false, bool LIST = false, bool PREFIX = false>
 static int launch_nb(const NbArgs& a, int tiles, int nets, size_t lds_bytes, hipStream_t stream) {
-  const void* dev_args = osrl_argmem::slot(a);
-  hipError_t e = hipFuncSetAttribute(dev_args ? reinterpret_cast<const void*>(mlp_fwd_nb_kernel_p<NCB, SHARED, LIST, PREFIX>)
-                                              : reinterpret_cast<const void*>(mlp_fwd_nb_kernel<NCB, SHARED, LIST, PREFIX>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (e != hipSuccess) return (int)e;
-  (void)hipGetLastError();
-  if (dev_args)
-    hipLaunchKernelGGL((mlp_fwd_nb_kernel_p<NCB, SHARED, LIST, PREFIX>), dim3(tiles, nets, 1), dim3(256), lds_bytes, stream, dev_args);
-  else
-    hipLaunchKernelGGL((mlp_fwd_nb_kernel<NCB, SHARED, LIST, PREFIX>), dim3(tiles, nets, 1), dim3(256), lds_bytes, stream, a);
-  return (int)hipGetLastError();
+  return osrl_argmem::launch(mlp_fwd_nb_kernel<NCB, SHARED, LIST, PREFIX>, mlp_fwd_nb_kernel_p<NCB, SHARED, LIST, PREFIX>,
+                             dim3(tiles, nets, 1), dim3(256), lds_bytes, stream, a);
 }
 
 }  // namespace
@@ -846,24 +837,9 @@ __attribute__((visibility("hidden"))) int OSRL_NB_LAUNCH(const osrl_mlp_t* net, 
   const bool nb8 = !(nb_env && atoi(nb_env) == 4);
   if (shared && nb8 && lda >= 8 * ((NL + 15) & ~15)) {
     a.in.share0 = share ? 1 : 0;
-    const void* dev_args = osrl_argmem::slot(a);
-    const void* fn = share ? (dev_args ? reinterpret_cast<const void*>(mlp_fwd_nb8_pre_kernel_p)
-                                         : reinterpret_cast<const void*>(mlp_fwd_nb8_pre_kernel))
-                             : (dev_args ? reinterpret_cast<const void*>(mlp_fwd_nb8_kernel_p)
-                                         : reinterpret_cast<const void*>(mlp_fwd_nb8_kernel));
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
-    (void)hipGetLastError();
-    if (share) {
-      if (dev_args)
-        hipLaunchKernelGGL(mlp_fwd_nb8_pre_kernel_p, dim3(tiles, nets, 1), dim3(512), lds_bytes, stream, dev_args);
-      else
-        hipLaunchKernelGGL(mlp_fwd_nb8_pre_kernel, dim3(tiles, nets, 1), dim3(512), lds_bytes, stream, a);
-    } else if (dev_args)
-      hipLaunchKernelGGL(mlp_fwd_nb8_kernel_p, dim3(tiles, nets, 1), dim3(512), lds_bytes, stream, dev_args);
-    else
-      hipLaunchKernelGGL(mlp_fwd_nb8_kernel, dim3(tiles, nets, 1), dim3(512), lds_bytes, stream, a);
-    return (int)hipGetLastError();
+    const dim3 grid(tiles, nets, 1);
+    return share ? osrl_argmem::launch(mlp_fwd_nb8_pre_kernel, mlp_fwd_nb8_pre_kernel_p, grid, dim3(512), lds_bytes, stream, a)
+                 : osrl_argmem::launch(mlp_fwd_nb8_kernel, mlp_fwd_nb8_kernel_p, grid, dim3(512), lds_bytes, stream, a);
   }
   if (ncb == 4 && lda >= 8 * ((NL + 15) & ~15)) {
     // 13..16-block (<= 256-wide) nets.  The 4-wave 80-row form runs ONE wave per SIMD (its 84.5 KB activation tile allows one
@@ -881,19 +857,8 @@ __attribute__((visibility("hidden"))) int OSRL_NB_LAUNCH(const osrl_mlp_t* net, 
       if (use64) return osrl_launch_fwd_nb64(net, in, out, stream, kl, kl_L);
     }
 #endif
-    if (eight) {
-      const void* dev_args = osrl_argmem::slot(a);
-      hipError_t e = hipFuncSetAttribute(dev_args ? reinterpret_cast<const void*>(mlp_fwd_nb8n_kernel_p)
-                                                  : reinterpret_cast<const void*>(mlp_fwd_nb8n_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      if (e != hipSuccess) return (int)e;
-      (void)hipGetLastError();
-      if (dev_args)
-        hipLaunchKernelGGL(mlp_fwd_nb8n_kernel_p, dim3(tiles, nets, 1), dim3(512), lds_bytes, stream, dev_args);
-      else
-        hipLaunchKernelGGL(mlp_fwd_nb8n_kernel, dim3(tiles, nets, 1), dim3(512), lds_bytes, stream, a);
-      return (int)hipGetLastError();
-    }
+    if (eight)
+      return osrl_argmem::launch(mlp_fwd_nb8n_kernel, mlp_fwd_nb8n_kernel_p, dim3(tiles, nets, 1), dim3(512), lds_bytes, stream, a);
   }
   if (share && ncb == 4 && !shared) {  // (the shared-row forms: 4-wave 13..16-block nets here, 8-wave 25-block nets above)
     a.in.share0 = 1;

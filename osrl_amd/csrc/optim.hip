@@ -153,17 +153,8 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, float* __restri
   }
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ m,
-                                                   float* __restrict__ v, float* __restrict__ tgt,
-                                                   const float* __restrict__ slabs, int n_splits,
-                                                   int64_t slab_stride, int64_t n4, float lr, float b1, float b2,
-                                                   float eps, float wd, float tau, const float* __restrict__ gscale,
-                                                   const osrl_step_state_t* __restrict__ st, const PackMap pk) {
-  adam_body(p, m, v, tgt, slabs, n_splits, slab_stride, n4, lr, b1, b2, eps, wd, tau, gscale, st, pk,
-            (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
-}
-// the same step with its 36 dwords of arguments in a device-resident block (argmem.h): no hidden launch-geometry
-// arguments either, so a wave's only kernarg traffic is the preloaded pointer
+// (the stride of the loop is a field, not gridDim * blockDim: no hidden launch-geometry arguments, so a wave of the "_p"
+// twin -- the 36 dwords in a device-resident block, argmem.h -- has the preloaded pointer as its only kernarg traffic)
 struct AdamArgs {
   float *p, *m, *v, *tgt;
   const float* slabs;
@@ -176,6 +167,10 @@ struct AdamArgs {
   int32_t pad_;  // (explicit: the arena looks descriptors up by memcmp over the whole struct -- no implicit padding bytes)
 };
 static_assert(sizeof(AdamArgs) == 8 * 4 + 8 + 3 * 8 + 2 * 8 + sizeof(PackMap) + 8 * 4, "AdamArgs has implicit padding");
+__global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
+  adam_body(a.p, a.m, a.v, a.tgt, a.slabs, a.n_splits, a.slab_stride, a.n4, a.lr, a.b1, a.b2, a.eps, a.wd, a.tau,
+            a.gscale, a.st, a.pk, (int64_t)blockIdx.x * 256 + threadIdx.x, a.stride);
+}
 __global__ __launch_bounds__(256) void adam_kernel_p(const void* ptr) {
   OSRL_TRACE_BEGIN(11, ptr);
   const OSRL_CAS AdamArgs& a = *(const OSRL_CAS AdamArgs*)ptr;
@@ -252,23 +247,13 @@ static int adam_launch(float* p, float* m, float* v, float* tgt, const float* sl
                        float weight_decay, float tau, const float* gscale, const osrl_step_state_t* st,
                        const PackMap& pk, void* stream) {
   if (!p || !m || !v || !slabs || !st || n < 4 || (n & 3) || (slab_stride & 3) || n_splits < 1) return -1;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   const int grid = stream_grid(n / 4);
-  const void* dev_args = nullptr;
-  if (osrl_argmem::current()) {
-    AdamArgs a{};
-    a.p = p; a.m = m; a.v = v; a.tgt = tgt; a.slabs = slabs;
-    a.slab_stride = slab_stride; a.n4 = n / 4; a.stride = (int64_t)grid * 256;
-    a.gscale = gscale; a.st = st; a.pk = pk; a.n_splits = n_splits;
-    a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.tau = tau;
-    dev_args = osrl_argmem::slot(a);
-  }
-  if (dev_args)
-    hipLaunchKernelGGL(adam_kernel_p, dim3(grid), dim3(256), 0, (hipStream_t)stream, dev_args);
-  else
-    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, m, v, tgt, slabs,
-                       n_splits, slab_stride, n / 4, lr, beta1, beta2, eps, weight_decay, tau, gscale, st, pk);
-  return (int)hipGetLastError();
+  AdamArgs a{};
+  a.p = p; a.m = m; a.v = v; a.tgt = tgt; a.slabs = slabs;
+  a.slab_stride = slab_stride; a.n4 = n / 4; a.stride = (int64_t)grid * 256;
+  a.gscale = gscale; a.st = st; a.pk = pk; a.n_splits = n_splits;
+  a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.tau = tau;
+  return osrl_argmem::launch(adam_kernel, adam_kernel_p, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
 }
 
 extern "C" int osrl_adam_step(float* p, float* m, float* v, float* tgt, const float* slabs, int32_t n_splits,

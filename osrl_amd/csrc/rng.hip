@@ -130,13 +130,13 @@ __device__ __forceinline__ void step_begin_body(BR b, AR a) {
     }
   }
 }
-__global__ __launch_bounds__(kBeginThreads) void step_begin_kernel(const BeginArgs b, const GatherArgs a) {
-  step_begin_body<const BeginArgs&, const GatherArgs&>(b, a);
-}
-struct BeginPack {  // both descriptors as one device-resident block (argmem.h): the first launch of every step
+struct BeginPack {  // both descriptors as one block (device-resident for the "_p" twin, argmem.h): the first launch of every step
   BeginArgs b;
   GatherArgs a;
 };
+__global__ __launch_bounds__(kBeginThreads) void step_begin_kernel(const BeginPack k) {
+  step_begin_body<const BeginArgs&, const GatherArgs&>(k.b, k.a);
+}
 __global__ __launch_bounds__(kBeginThreads) void step_begin_kernel_p(const void* p) {
   OSRL_TRACE_BEGIN(1, p);
   const OSRL_CAS BeginPack& k = *(const OSRL_CAS BeginPack*)p;
@@ -342,10 +342,6 @@ extern "C" int osrl_step_begin_peer(osrl_step_state_t* st, const osrl_step_state
   int64_t rb = noise ? ((noise_n + 3) / 4 + kBeginThreads - 1) / kBeginThreads : 0;
   b.r_blocks = (int32_t)(rb > 256 ? 256 : rb);
   const int grid = b.g_blocks + b.r_blocks > 0 ? b.g_blocks + b.r_blocks : 1;
-  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
-  if (const void* dev_args = osrl_argmem::slot(k))
-    hipLaunchKernelGGL(step_begin_kernel_p, dim3(grid), dim3(kBeginThreads), 0, (hipStream_t)stream, dev_args);
-  else
-    hipLaunchKernelGGL(step_begin_kernel, dim3(grid), dim3(kBeginThreads), 0, (hipStream_t)stream, b, a);
-  return (int)hipGetLastError();
+  return osrl_argmem::launch(step_begin_kernel, step_begin_kernel_p, dim3(grid), dim3(kBeginThreads), 0,
+                             (hipStream_t)stream, k);
 }

@@ -746,18 +746,8 @@ bool fill(const osrl_vae_ns_t* v, NsArgs* a, bool backward) {
 constexpr size_t kWideLds = sizeof(float) * kKS * kBM * kLD;  // 64512 B >= S + 4 private regions (59136 B)
 static_assert(sizeof(float) * (kBM * kSL + kKS * kBM * kPL) <= kWideLds, "the partial buffers must cover the A regions");
 
-template <class K, class KP>
-int launch(K k, KP kp, int grid, int threads, size_t ldsb, hipStream_t st, const NsArgs& a) {
-  const void* dev = osrl_argmem::slot(a);
-  hipError_t e = dev ? hipFuncSetAttribute(reinterpret_cast<const void*>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb)
-                     : hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-  if (e != hipSuccess) return (int)e;
-  (void)hipGetLastError();
-  if (dev) hipLaunchKernelGGL(kp, dim3(grid), dim3(threads), ldsb, st, dev);
-  else hipLaunchKernelGGL(k, dim3(grid), dim3(threads), ldsb, st, a);
-  return (int)hipGetLastError();
-}
-#define NS_LAUNCH(K, ...) launch(K<__VA_ARGS__>, K##_p<__VA_ARGS__>
+// NS_LAUNCH(kernel, template arguments...), grid, threads, LDS bytes, stream, args): the kernel or its "_p" twin
+#define NS_LAUNCH(K, ...) osrl_argmem::launch(K<__VA_ARGS__>, K##_p<__VA_ARGS__>
 
 int wide_grid(const NsArgs& a) { return ((a.row_tiles + 7) / 8) * 8 * a.col_groups; }
 
@@ -766,7 +756,7 @@ int wide_grid(const NsArgs& a) { return ((a.row_tiles + 7) / 8) * 8 * a.col_grou
 extern "C" int osrl_vae_ns_supported(const osrl_vae_ns_t* v) { return shape_ok(v) ? 1 : 0; }
 
 extern "C" int osrl_vae_ns_forward(const osrl_vae_ns_t* v, void* stream) {
-  NsArgs a;
+  NsArgs a{};
   if (!fill(v, &a, false)) return -1;
   hipStream_t st = (hipStream_t)stream;
   const int Kpe = (a.od + a.ad + 15) & ~15;
@@ -786,7 +776,7 @@ extern "C" int osrl_vae_ns_forward(const osrl_vae_ns_t* v, void* stream) {
 }
 
 extern "C" int osrl_vae_ns_backward(const osrl_vae_ns_t* v, void* stream) {
-  NsArgs a;
+  NsArgs a{};
   if (!fill(v, &a, true)) return -1;
   hipStream_t st = (hipStream_t)stream;
   int rc = NS_LAUNCH(vae_ns_gen_kernel, MODE_DEC_BWD, 1), wide_grid(a), 256, kWideLds, st, a);

@@ -1341,3 +1341,135 @@ def test_vae_ns_launches_equal_the_fused_launches(rows, od, ad, hid, rg):
             assert n_bad <= max(2, a.numel() // 2000), (k, n_bad, float(diff.max()), scale)
         else:
             assert float(diff.max()) <= 2e-5 * scale, (k, float(diff.max()), scale)
+
+
+# ---- by-value kernels and their "_p" twins (csrc/argmem.h), one pair at a time -----------------------------------------
+def _randn(gen, *shape):
+    return torch.randn(*shape, generator=gen, device=_dev())
+
+
+def _twin_vae_loss(rows):
+    from osrl_amd.engine import glue as G
+    ad, Lz = 3, 2
+
+    def make():
+        g = torch.Generator(device=_dev()).manual_seed(5)
+        return [_randn(g, rows, ad), _randn(g, rows, ad), _randn(g, rows, 2 * Lz), torch.zeros(rows, ad, device=_dev()),
+                torch.zeros(2, device=_dev())]
+
+    return make, lambda b: G.vae_loss(b[0], b[1], b[2], rows, ad, Lz, 0.5, 0, b[3], b[4])
+
+
+def _twin_critic_loss(rows, n):
+    from osrl_amd.engine import glue as G
+
+    def make():
+        g = torch.Generator(device=_dev()).manual_seed(6)
+        return [_randn(g, n, rows), _randn(g, n, rows), _randn(g, n, rows), _randn(g, rows),
+                (_randn(g, rows) > 1.0).float(), torch.zeros(n, rows, device=_dev()), torch.zeros(2, device=_dev())]
+
+    return make, lambda b: G.cpq_critic_loss(b[0], n, b[1], n, b[2], n, b[3], b[4], rows, 0.99, 0.1, 0, b[5], b[6])
+
+
+def _twin_cost_loss(rows, n):  # with the dual step: ood_mean given, log_alpha updated in place
+    from osrl_amd.engine import glue as G
+
+    def make():
+        g = torch.Generator(device=_dev()).manual_seed(7)
+        return [_randn(g, n, rows), _randn(g, n, rows), _randn(g, 1), _randn(g, rows).abs(),
+                torch.full((1,), 0.3, device=_dev()), torch.zeros(n, rows, device=_dev()), torch.zeros(2, device=_dev())]
+
+    return make, lambda b: G.cpq_cost_loss(b[0], n, b[1], n, b[2], b[3], rows, 0.99, 0.2, 1e-2, 0, 1.0, b[4], b[5], b[6])
+
+
+def _twin_adam():
+    """4 * (2048 * 256 + 3) floats: more float4s than the capped grid of 2048 x 256 threads holds, so the stride loop runs a
+    second, partial pass; two slabs, a Polyak target and the packed copies."""
+    from osrl_amd import _lib as L
+    from osrl_amd.engine.core import StepState, cur_stream
+    dev = _dev()
+    n = 4 * (2048 * 256 + 3)
+    st = StepState(dev, ["x"])
+    st.tick()
+    i = torch.arange(n, dtype=torch.int32, device=dev)
+    map_f = torch.where(i % 3 == 0, torch.full_like(i, -1), i)
+    map_b = torch.where(i % 5 == 0, torch.full_like(i, -1), n - 1 - i)
+
+    def make():  # p, m, v, tgt, pf, pb, tf, slabs
+        g = torch.Generator(device=dev).manual_seed(8)
+        return [_randn(g, n), _randn(g, n) * 0.1, _randn(g, n).abs() * 0.01, _randn(g, n), torch.zeros(n, device=dev),
+                torch.zeros(n, device=dev), torch.zeros(n, device=dev), _randn(g, 2, n)]
+
+    def run(b):
+        p, m, v, tgt, pf, pb, tf, slabs = (t.data_ptr() for t in b)
+        L.check(L.load().osrl_adam_step_packed(p, m, v, tgt, slabs, 2, n, n, 1e-3, 0.9, 0.999, 1e-8, 1e-4, 0.005, None, st.ptr,
+                                               map_f.data_ptr(), map_b.data_ptr(), pf, pb, tf, cur_stream()),
+                "osrl_adam_step_packed")
+        return st, map_f, map_b  # (alive until the caller has synchronised)
+
+    return make, run
+
+
+def _twin_step_begin():
+    """One gathered field of a few rows plus a noise buffer: the launch has a gather workgroup and a noise workgroup."""
+    import ctypes as C
+    from osrl_amd import _lib as L
+    from osrl_amd.engine.core import cur_stream
+    dev = _dev()
+    n_rows, B, w = 50, 5, 3
+    table = torch.arange(n_rows * w, device=dev, dtype=torch.float32).view(n_rows, w)
+
+    def make():  # step state, statistics, ring, noise, gathered rows
+        return [torch.zeros(24, dtype=torch.uint8, device=dev), torch.tensor([1.5, -2.0], device=dev),
+                torch.zeros(4, 2, device=dev), torch.zeros(1001, device=dev), torch.zeros(B, w, device=dev)]
+
+    def run(b):
+        state, stats, ring, noise, dst = b
+        src, d = (C.c_void_p * 1)(table.data_ptr()), (C.c_void_p * 1)(dst.data_ptr())
+        L.check(L.load().osrl_step_begin(state.data_ptr(), 0.9, 0.999, 10, stats.data_ptr(), ring.data_ptr(), 2, 4,
+                                         noise.data_ptr(), noise.numel(), 4321, 0, 1, src, d, (C.c_int32 * 1)(w),
+                                         (C.c_float * 1)(0.5), n_rows, B, 99, 1, cur_stream()), "osrl_step_begin")
+        return table
+
+    return make, run
+
+
+# rows: fewer than one workgroup's 1024 threads / not a multiple of four strides of the workgroup (vae_loss walks
+# rows * ad and rows * L elements four strides per pass, the CPQ losses one row per thread and pass).
+# ensemble members: one count on each side of kEns = 4 (glue.hip), so that both SMALL instantiations launch
+_TWIN_ROWS = (37, 4 * 1024 + 37)
+TWIN_CASES = {f"vae_loss-{r}": (_twin_vae_loss, r) for r in _TWIN_ROWS}
+TWIN_CASES.update({f"critic_loss-{r}x{n}": (_twin_critic_loss, r, n) for r in _TWIN_ROWS for n in (2, 5)})
+TWIN_CASES.update({f"cost_loss-{r}x{n}": (_twin_cost_loss, r, n) for r in _TWIN_ROWS for n in (2, 5)})
+TWIN_CASES.update({"adam": (_twin_adam,), "step_begin": (_twin_step_begin,)})
+
+
+@pytest.mark.parametrize("case", list(TWIN_CASES))
+def test_by_value_kernel_and_arena_twin_agree(monkeypatch, case):
+    """An entry point called plainly starts its by-value kernel; under ArgArena.record() -> upload() -> replay() it starts
+    the "_p" twin, which reads the same descriptor from the arena.  Every buffer must come out bit-equal, and the replay
+    pass must have found its one descriptor.  (The arena finds a descriptor by its bytes, pointers included, so the record
+    and the replay pass run on the SAME buffers; their contents are put back between the two, because several of these
+    kernels update in place.)"""
+    from osrl_amd.engine.core import ArgArena
+    monkeypatch.setattr(ArgArena, "ENABLED", True)
+    build, *shape = TWIN_CASES[case]
+    make, run = build(*shape)
+    plain = make()
+    run(plain)
+    bufs = make()
+    pristine = [t.clone() for t in bufs]
+    arena = ArgArena(_dev())
+    with arena.record():
+        run(bufs)
+    arena.upload()
+    for t, t0 in zip(bufs, pristine):
+        t.copy_(t0)
+    with arena.replay():
+        keep = run(bufs)
+    torch.cuda.synchronize()
+    del keep
+    assert (arena.blocks, arena.hits, arena.misses) == (1, 1, 0)
+    assert any(not torch.equal(b, t0) for b, t0 in zip(bufs, pristine)), "the launch wrote nothing"
+    for i, (a, b) in enumerate(zip(plain, bufs)):
+        assert torch.equal(a, b), i

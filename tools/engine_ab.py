@@ -56,6 +56,10 @@ def digests(m, eng, n_steps: int) -> dict:
     rows = np.asarray([stats[s] for s in range(1, n_steps + 1)], np.float32)
     out["stats"] = hashlib.sha256(rows.tobytes()).hexdigest()
     out["steps"] = eng.st.device_step()
+    # [blocks, hits, misses] of every argument arena (core.ArgArena) this path captured with: all zero under OSRL_ARG_ARENA=0
+    arenas = {"step": getattr(eng, "_arena", None), "direct": getattr(eng, "_arena_direct", None),
+              "pipelined": getattr(getattr(eng, "_pipe", None), "_arena", None)}
+    out["arena"] = {k: [a.blocks, a.hits, a.misses] for k, a in arenas.items() if a is not None}
     return out
 
 
@@ -124,7 +128,7 @@ def main() -> None:
             res["cases"][name] = run_cdt(CDT_CASES[name])
         else:
             res["cases"][name] = run_mlp({**MLP, **BEARL_CASES, **COPTIDICE_CASES}[name])
-        print(name, {p: d["stats"][:12] for p, d in res["cases"][name].items()}, flush=True)
+        print(name, {p: (d["stats"][:12], d["arena"]) for p, d in res["cases"][name].items()}, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1, sort_keys=True)
