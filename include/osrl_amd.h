@@ -305,6 +305,8 @@ typedef struct {
   float *pf, *pb;
   float lr, eps;
   float* ws;
+  /* osrl_replay_gather_w's table (device uint64[n_rows], osrl_weights_cum_u64); NULL (zero) = uniform draws */
+  const uint64_t* cum;
 } osrl_mlp_step_t;
 int osrl_mlp_regress_step(const osrl_mlp_step_t* s, void* stream);
 
@@ -460,6 +462,18 @@ int osrl_step_begin_peer(osrl_step_state_t* st, const osrl_step_state_t* peer, f
                          int64_t noise_n, uint64_t noise_seed, uint32_t noise_stream, int32_t n_fields,
                          const float* const* src, float* const* dst, const int32_t* width, const float* scale,
                          int64_t n_rows, int32_t batch, uint64_t gather_seed, uint32_t gather_stream, void* stream);
+/* The two prologues with osrl_replay_gather_w's table (cum == NULL: exactly the calls above). */
+int osrl_step_begin_w(osrl_step_state_t* st, float beta1, float beta2, int32_t warmup, const float* stats_cur,
+                      float* ring, int32_t n_stats, int32_t ring_len, float* noise, int64_t noise_n,
+                      uint64_t noise_seed, uint32_t noise_stream, int32_t n_fields, const float* const* src,
+                      float* const* dst, const int32_t* width, const float* scale, int64_t n_rows, int32_t batch,
+                      uint64_t gather_seed, uint32_t gather_stream, const uint64_t* cum, void* stream);
+int osrl_step_begin_peer_w(osrl_step_state_t* st, const osrl_step_state_t* peer, float beta1, float beta2, int32_t warmup,
+                           const float* stats_cur, float* ring, int32_t n_stats, int32_t ring_len, float* noise,
+                           int64_t noise_n, uint64_t noise_seed, uint32_t noise_stream, int32_t n_fields,
+                           const float* const* src, float* const* dst, const int32_t* width, const float* scale,
+                           int64_t n_rows, int32_t batch, uint64_t gather_seed, uint32_t gather_stream,
+                           const uint64_t* cum, void* stream);
 /* g = sum_s slabs[s][i] (* *gscale if gscale != NULL); AdamW decay if weight_decay != 0;
  * then tgt = tau*p + (1-tau)*tgt if tgt != NULL.  n and slab_stride must be multiples of 4. */
 int osrl_adam_step(float* p, float* m, float* v, float* tgt, const float* slabs, int32_t n_splits,
@@ -515,6 +529,30 @@ int osrl_randn_fill(float* out, int64_t n, uint64_t seed, uint32_t stream_id, co
 int osrl_replay_gather(int32_t n_fields, const float* const* src, float* const* dst, const int32_t* width,
                        const float* scale, int64_t n_rows, int32_t batch, int32_t* idx_out, uint64_t seed,
                        uint32_t stream_id, const osrl_step_state_t* st, void* stream);
+/* Weighted transition sampling (ReplayStore.set_sample_prob; the reference draws uniformly, dataset.py:846, and offers
+ * only the hard filters of process_bc_dataset).  `weights`: one non-negative finite fp64 value per row, positive sum.
+ *   The table.  cum[i] (device uint64[n_rows]) = floor(2^64 * S_i / S_n) saturated at 2^64 - 1, S_i the fp64 inclusive
+ *     prefix sum of the weights in index order: S_i = O_b + (T_j + L_e), with L_e the running sum inside a thread's 16
+ *     consecutive rows, T_j the running sum of the thread totals inside a workgroup's 4096 rows and O_b the running sum
+ *     of the workgroup totals, each of the three chains added left to right from 0 -- one fixed association, so two
+ *     builds give the same bits, S is non-decreasing, and a zero-weight row has exactly its predecessor's entry (0 for
+ *     leading rows).  cum[n_rows - 1] = 2^64 - 1 always.  A weight below 2^-64 of the total (2^-53 of it near the end of the
+ *     table, where fp64 resolves no finer) may share its predecessor's entry and is then never drawn.  Negative and NaN
+ *     weights count as 0; a sum that is not positive gives the table that always draws row 0.
+ *   The draw.  Row b's word is the one the uniform draw maps: u = (r.x << 32) | r.y of
+ *     philox4x32_10({b, 0x5eed, step, stream_id}, seed).  idx[b] = the FIRST i with cum[i] > min(u, 2^64 - 2): the word
+ *     2^64 - 1, which no entry exceeds, draws what 2^64 - 2 draws.  So a zero-weight row is never drawn, whatever the
+ *     word (leading rows hold 0, later ones repeat their predecessor and are never the first), and the index depends on
+ *     (table, word) only.  The lanes that hold a row search together: 64 (32 in osrl_mlp_regress_step) evenly spaced
+ *     probes and a ballot per round, ceil(log_65 n) (log_33) dependent loads.
+ *   cum == NULL: the uniform draw, bit for bit the calls without the table.
+ * osrl_weights_cum_u64 builds the table (3 launches, n <= 2^28, rewritten in place: a captured graph that holds the address
+ * draws from the new weights at its next replay); ws: osrl_weights_cum_u64_ws_elems(n) doubles of device scratch. */
+int64_t osrl_weights_cum_u64_ws_elems(int64_t n);
+int osrl_weights_cum_u64(const double* weights, int64_t n, uint64_t* cum, double* ws, void* stream);
+int osrl_replay_gather_w(int32_t n_fields, const float* const* src, float* const* dst, const int32_t* width,
+                         const float* scale, int64_t n_rows, int32_t batch, int32_t* idx_out, uint64_t seed,
+                         uint32_t stream_id, const osrl_step_state_t* st, const uint64_t* cum, void* stream);
 
 /* CDT minibatch source -- SequenceDataset.__iter__/__prepare_sample (dataset.py:749-787) on device: per sample
  * draw a trajectory (inverse CDF of `cdf`, or uniform when NULL) and a start ~ U{0..len-1}, slice seq_len steps

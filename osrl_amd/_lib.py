@@ -107,7 +107,7 @@ class MlpStepT(C.Structure):  # osrl_mlp_step_t
                 ("target", _fp), ("n_global", C.c_int64), ("stat", _fp),
                 ("entries", C.c_void_p), ("work", C.c_void_p), ("n_work", C.c_int32), ("tile_blocks", C.c_int32),
                 ("p", _fp), ("m", _fp), ("v", _fp), ("map_f", C.c_void_p), ("map_b", C.c_void_p), ("pf", _fp),
-                ("pb", _fp), ("lr", C.c_float), ("eps", C.c_float), ("ws", _fp)]
+                ("pb", _fp), ("lr", C.c_float), ("eps", C.c_float), ("ws", _fp), ("cum", C.c_void_p)]
 
 
 class PackEntryT(C.Structure):
@@ -240,6 +240,8 @@ PROTOTYPES = {
     "osrl_bc_frontier_select": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "osrl_pf_sample_prob": [_vp, _vp, _vp, _i32, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp],
     "osrl_weights_sample_prob": [_vp, _i32, _vp, _vp, _vp],
+    "osrl_weights_cum_u64_ws_elems": [_i64],
+    "osrl_weights_cum_u64": [_vp, _i64, _vp, _vp, _vp],
     "osrl_vae_ns_supported": [_P(VaeNsT)],
     "osrl_vae_ns_forward": [_P(VaeNsT), _vp],
     "osrl_vae_ns_backward": [_P(VaeNsT), _vp],
@@ -263,6 +265,10 @@ PROTOTYPES = {
     "osrl_step_tick": [_vp, _f32, _f32, _i32, _fp, _fp, _i32, _i32, _vp],
     "osrl_step_begin": [_vp, _f32, _f32, _i32, _fp, _fp, _i32, _i32, _fp, _i64, _u64, _u32, _i32, _P(_fp), _P(_fp),
                         _P(_i32), _P(_f32), _i64, _i32, _u64, _u32, _vp],
+    "osrl_step_begin_w": [_vp, _f32, _f32, _i32, _fp, _fp, _i32, _i32, _fp, _i64, _u64, _u32, _i32, _P(_fp), _P(_fp),
+                          _P(_i32), _P(_f32), _i64, _i32, _u64, _u32, _vp, _vp],
+    "osrl_step_begin_peer_w": [_vp, _vp, _f32, _f32, _i32, _fp, _fp, _i32, _i32, _fp, _i64, _u64, _u32, _i32, _P(_fp), _P(_fp),
+                               _P(_i32), _P(_f32), _i64, _i32, _u64, _u32, _vp, _vp],
     "osrl_step_tick_peer": [_vp, _vp, _f32, _f32, _i32, _fp, _fp, _i32, _i32, _vp],
     "osrl_step_begin_peer": [_vp, _vp, _f32, _f32, _i32, _fp, _fp, _i32, _i32, _fp, _i64, _u64, _u32, _i32, _P(_fp), _P(_fp),
                              _P(_i32), _P(_f32), _i64, _i32, _u64, _u32, _vp],
@@ -276,6 +282,7 @@ PROTOTYPES = {
     "osrl_layernorm_param_reduce": [_fp, _i64, _i32, _i32, _i32, _fp, _vp, _vp, _vp],
     "osrl_randn_fill": [_fp, _i64, _u64, _u32, _vp, _vp],
     "osrl_replay_gather": [_i32, _P(_fp), _P(_fp), _P(_i32), _P(_f32), _i64, _i32, _vp, _u64, _u32, _vp, _vp],
+    "osrl_replay_gather_w": [_i32, _P(_fp), _P(_fp), _P(_i32), _P(_f32), _i64, _i32, _vp, _u64, _u32, _vp, _vp, _vp],
     "osrl_seq_window_gather": [_fp, _fp, _fp, _fp, _fp, _vp, _vp, _fp, _fp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _fp, _fp,
                                _fp, _fp, _vp, _fp, _fp, _fp, _vp, _u64, _u32, _vp, _vp],
     "osrl_gauss_head": [_fp, _fp, _i32, _i32, _f32, _fp, _fp, _fp, _vp],
@@ -355,7 +362,7 @@ _LIB: Optional[C.CDLL] = None
 LOSS_WS = 132  # floats of scratch for the grid loss kernels (include/osrl_amd.h OSRL_LOSS_WS)
 QUANTILE_WS = 1032  # uint32 elements of scratch for osrl_quantile_ws (include/osrl_amd.h OSRL_QUANTILE_WS)
 RESTYPES = {"osrl_ingest_ws_elems": C.c_int64, "osrl_grid_filter_ws_elems": C.c_int64,
-            "osrl_polyfit_ws_elems": C.c_int64, "osrl_augment_targets_ws_elems": C.c_int64, "osrl_attention_keep_bytes": C.c_int64,
+            "osrl_polyfit_ws_elems": C.c_int64, "osrl_weights_cum_u64_ws_elems": C.c_int64, "osrl_augment_targets_ws_elems": C.c_int64, "osrl_attention_keep_bytes": C.c_int64,
             "osrl_attention_ws_bytes": C.c_int64, "osrl_attention_tiled_ws_bytes": C.c_int64,
             "osrl_attention_tiled_lds_bytes": C.c_int64, "osrl_linear_kchunk_lds_bytes": C.c_int64,
             "osrl_mlp_wide_lds_bytes": C.c_int64, "osrl_linear_split_lds_bytes": C.c_int64}  # everything else returns int (0 = ok)

@@ -1,4 +1,4 @@
-"""Device-resident transition store + on-device uniform sampler.
+"""Device-resident transition store + on-device sampler (uniform, or in proportion to per-transition weights).
 
 Replaces the reference's minibatch source -- ``TransitionDataset`` (osrl/common/dataset.py:790-847:
 ``done = terminals | timeouts`` as fp32 :815-816, ``rewards*reward_scale``, ``costs*cost_scale``,
@@ -8,6 +8,10 @@ kernel (csrc/rng.hip ``osrl_replay_gather``) that draws the indices on device in
 train step.  In the data-parallel setting every rank holds its own shard of the transitions
 (``shard(rank, world)``) and samples locally: with random partitions this is distributionally the
 same as global uniform sampling.
+
+``sample_prob`` / ``set_sample_prob``: rows are drawn with probability weight / sum instead (with replacement, the same
+Philox words as the uniform draw) through a fixed-point cdf table in HBM that the gather kernels search
+(include/osrl_amd.h ``osrl_replay_gather_w``, DESIGN.md "Weighted transition sampling").
 """
 from __future__ import annotations
 
@@ -25,11 +29,13 @@ FIELDS = ("observations", "next_observations", "actions", "rewards", "costs", "d
 
 class ReplayStore:
     def __init__(self, data: Dict[str, "np.ndarray | torch.Tensor"], device, reward_scale: float = 1.0,
-                 cost_scale: float = 1.0, seed: int = 0, rank: int = 0, world: int = 1, state_init: bool = False):
+                 cost_scale: float = 1.0, seed: int = 0, rank: int = 0, world: int = 1, state_init: bool = False,
+                 sample_prob=None):
         """``data`` uses the DSRL dataset keys (observations, next_observations, actions, rewards, costs,
         and either ``done`` or ``terminals``+``timeouts``).  ``state_init`` (TransitionDataset(state_init=True),
         dataset.py:817-820, used by COptiDICE): a 7th table ``is_init`` = ``done`` shifted by one transition with
-        ``is_init[0] = 1``, computed on the FULL dataset before any sharding."""
+        ``is_init[0] = 1``, computed on the FULL dataset before any sharding.  ``sample_prob``: per-transition sampling
+        weights of the FULL dataset (``set_sample_prob``); None = uniform."""
         d = dict(data)
         self.state_init = bool(state_init)
         if "done" not in d:
@@ -52,7 +58,8 @@ class ReplayStore:
             self.init_state_propotion = float(init.mean())
             self.observations_std = as_np(d["observations"]).std(0, keepdims=True)
             self.actions_std = as_np(d["actions"]).std(0, keepdims=True)
-        sl = slice(rank, n, world) if world > 1 else slice(None)
+        sl = self._shard = slice(rank, n, world) if world > 1 else slice(None)
+        self.n_total = n
         self.tables = []
         for k in fields:
             t = torch.as_tensor(np.asarray(d[k])[sl] if not torch.is_tensor(d[k]) else d[k][sl])
@@ -68,6 +75,70 @@ class ReplayStore:
         self._w = (C.c_int32 * nf)(*self.widths)
         self._s = (C.c_float * nf)(*self.scales)
         self.bytes_per_row = 4 * sum(self.widths)
+        # weighted sampling: the table and its scratch are allocated at the first set_sample_prob and then only ever
+        # rewritten (captured graphs hold the address); sample_epoch counts the uniform <-> weighted switches, which
+        # change the launches' arguments -- the engines compare it before every replay (StepEngine._sync_replay)
+        self._cum_buf: Optional[torch.Tensor] = None
+        self._cum_ws: Optional[torch.Tensor] = None
+        self._w64: Optional[torch.Tensor] = None
+        self.weighted = False
+        self.sample_epoch = 0
+        if sample_prob is not None:
+            self.set_sample_prob(sample_prob)
+
+    @property
+    def cum(self) -> Optional[torch.Tensor]:
+        """The sampler's table -- int64 storage of the uint64 fixed-point cdf, [n_rows] -- or None while uniform."""
+        return self._cum_buf if self.weighted else None
+
+    def _cum_ptr(self) -> Optional[int]:
+        return self._cum_buf.data_ptr() if self.weighted else None
+
+    def set_sample_prob(self, weights) -> None:
+        """Draw row i with probability ``weights[i] / sum`` from now on (with replacement); None: back to uniform.
+        ``weights``: one non-negative finite value per transition of the FULL dataset (numpy or tensor, host or device),
+        with a positive sum; ValueError otherwise -- for host inputs before any device work.  Data parallel: the weights
+        are sliced like the rows (``[rank::world]``) and every rank normalises its own shard, which is global weighted
+        sampling only as far as the shards' weight masses are equal (the caveat of uniform sampling from random
+        partitions, for masses instead of row counts).
+        The table is rewritten in place on the current stream: a captured step draws from the new weights at its next
+        replay, nothing is recaptured.  Switching between uniform and weighted changes the launches' arguments instead;
+        the engines notice (``sample_epoch``) and rebuild their graphs / descriptors before the next step."""
+        if weights is None:
+            if self.weighted:
+                self.weighted = False
+                self.sample_epoch += 1
+            return
+        if torch.is_tensor(weights) and weights.is_cuda:
+            w = weights.reshape(-1)
+            if int(w.shape[0]) != self.n_total:
+                raise ValueError(f"{self.n_total} transition weights expected, got {int(w.shape[0])}")
+            w = w[self._shard].to(device=self.device, dtype=torch.float64).contiguous()
+            lo, total = float(w.min()), float(w.sum())  # host reads, once per distribution (NaN fails both tests)
+            ok = lo >= 0.0 and 0.0 < total < float("inf")
+        else:
+            w = weights.detach().cpu().numpy() if torch.is_tensor(weights) else np.asarray(weights)
+            w = np.asarray(w, np.float64).reshape(-1)
+            if w.shape[0] != self.n_total:
+                raise ValueError(f"{self.n_total} transition weights expected, got {w.shape[0]}")
+            w = np.ascontiguousarray(w[self._shard])
+            total = float(w.sum()) if np.isfinite(w).all() else float("nan")
+            ok = bool((w >= 0.0).all()) and 0.0 < total < float("inf")
+        if not ok:
+            raise ValueError("the weights must be non-negative and finite, with a positive sum"
+                             + (" on this rank's shard" if self._shard != slice(None) else ""))
+        lib = L.load()
+        if self._cum_buf is None:
+            self._cum_buf = torch.zeros(self.n_rows, dtype=torch.int64, device=self.device)
+            self._cum_ws = torch.zeros(int(lib.osrl_weights_cum_u64_ws_elems(self.n_rows)), dtype=torch.float64,
+                                       device=self.device)
+            self._w64 = torch.zeros(self.n_rows, dtype=torch.float64, device=self.device)
+        self._w64.copy_(w if torch.is_tensor(w) else torch.from_numpy(w))
+        L.check(lib.osrl_weights_cum_u64(self._w64.data_ptr(), self.n_rows, self._cum_buf.data_ptr(),
+                                         self._cum_ws.data_ptr(), cur_stream()), "osrl_weights_cum_u64")
+        if not self.weighted:
+            self.weighted = True
+            self.sample_epoch += 1
 
     def get_dataset_states(self):
         """(init_state_propotion, observations_std, actions_std) -- dataset.py:822-830; needs ``state_init``."""
@@ -82,14 +153,14 @@ class ReplayStore:
         if len(dst) != self.n_fields:
             raise ValueError(f"the store holds {self.n_fields} tables, {len(dst)} destination buffers were given")
         d = (C.c_void_p * self.n_fields)(*[t.data_ptr() for t in dst])
-        L.check(L.load().osrl_replay_gather(self.n_fields, self._src, d, self._w, self._s, self.n_rows, B,
-                                            None if idx_out is None else idx_out.data_ptr(), self.seed, stream_id,
-                                            st_ptr, cur_stream()), "osrl_replay_gather")
-
+        L.check(L.load().osrl_replay_gather_w(self.n_fields, self._src, d, self._w, self._s, self.n_rows, B,
+                                              None if idx_out is None else idx_out.data_ptr(), self.seed, stream_id,
+                                              st_ptr, self._cum_ptr(), cur_stream()), "osrl_replay_gather")
 
     def gather_args(self, dst: Sequence[torch.Tensor], fields: Optional[Sequence[int]] = None, stream_id: int = 1):
         """The arguments of ``gather`` / ``gather_fields`` as the tuple ``StepState.begin(gather=...)`` takes (the
-        fused step prologue draws the same rows: the indices are a function of (seed, step, row) only)."""
+        fused step prologue draws the same rows: the indices are a function of (seed, step, row) and the weight table
+        only); the last element is the table's address, None while uniform."""
         if fields is None:
             fields = range(self.n_fields)
         fields = list(fields)
@@ -100,7 +171,7 @@ class ReplayStore:
         d = (C.c_void_p * n)(*[t.data_ptr() for t in dst])
         w = (C.c_int32 * n)(*[self.widths[i] for i in fields])
         sc = (C.c_float * n)(*[self.scales[i] for i in fields])
-        return (n, src, d, w, sc, self.n_rows, dst[0].shape[0], self.seed, stream_id, list(dst))
+        return (n, src, d, w, sc, self.n_rows, dst[0].shape[0], self.seed, stream_id, list(dst), self._cum_ptr())
 
     def gather_fields(self, fields: Sequence[int], dst: Sequence[torch.Tensor], st_ptr: Optional[int],
                       stream_id: int = 1) -> None:
@@ -111,9 +182,8 @@ class ReplayStore:
         d = (C.c_void_p * n)(*[t.data_ptr() for t in dst])
         w = (C.c_int32 * n)(*[self.widths[i] for i in fields])
         sc = (C.c_float * n)(*[self.scales[i] for i in fields])
-        L.check(L.load().osrl_replay_gather(n, src, d, w, sc, self.n_rows, B, None, self.seed, stream_id, st_ptr,
-                                            cur_stream()), "osrl_replay_gather")
-
+        L.check(L.load().osrl_replay_gather_w(n, src, d, w, sc, self.n_rows, B, None, self.seed, stream_id, st_ptr,
+                                              self._cum_ptr(), cur_stream()), "osrl_replay_gather")
 
 def synthetic_transitions(n: int, od: int, ad: int, seed: int = 1, max_action: float = 1.0) -> Dict[str, np.ndarray]:
     """Synthetic DSRL-shaped data: obs~N(0,1), act~U(-1,1), rew~N(0,1), cost~Bern(.1),

@@ -22,7 +22,35 @@ struct GatherArgs {
   int32_t* idx_out;
   uint32_t k0, k1, stream_id;
   const osrl_step_state_t* st;
+  const uint64_t* cum;  // [n_rows] fixed-point inclusive cdf of the sampling weights (include/osrl_amd.h), or NULL = uniform
 };
+
+// The weighted draw: the first i in [0, n) with cum[i] > min(u, 2^64 - 2), found by the L lanes that hold the row (lane id l;
+// every one of them returns the index).  cum is non-decreasing, so that index is the number of entries <= the word.  A
+// k-ary search: each round the lanes probe L evenly spaced entries of the open range and a ballot counts the ones that do
+// not exceed the word, which cuts the range to one of L + 1 segments -- ceil(log_(L+1) n) dependent loads (3 at 2^18 rows
+// and 4 at 2^22 with a wave, 4 and 5 with half a wave) where one lane bisecting takes 18 / 22.  Whatever the table
+// holds, the result is inside [0, n).  All lanes of the wave may call it with different rows per half (L = 32): the
+// loop runs until both halves are done, a finished half probes nothing.
+template <int L>
+__device__ __forceinline__ int64_t search_cum(const uint64_t* __restrict__ cum, int64_t n, uint64_t u, int l, int half) {
+  const uint64_t word = u < ~0ull - 1 ? u : ~0ull - 1;
+  int64_t lo = 0, hi = n - 1;  // the index lies in [lo, hi]; entries [lo, hi) are still to be looked at
+  while (__any(hi > lo)) {
+    const int64_t len = hi - lo;
+    const int64_t s = (len + L) / (L + 1);  // segment length: probes at lo + s - 1, lo + 2 s - 1, ...
+    const int64_t p = lo + (int64_t)(l + 1) * s - 1;
+    const bool below = len > 0 && p < hi && cum[p] <= word;
+    const uint64_t m = __ballot(below);
+    const int c = L == 64 ? __popcll(m) : __popc((uint32_t)(m >> (32 * half)));
+    if (len > 0) {
+      const int64_t top = lo + (int64_t)(c + 1) * s - 1;  // the first probe that exceeded the word, if there was one
+      hi = (c < L && top < hi) ? top : hi;
+      lo += (int64_t)c * s;
+    }
+  }
+  return lo;
+}
 
 // One row of every table, index `idx` -> batch row `b`, by L lanes (lane id l): ALL fields' loads are requested before
 // the first store.  (As a loop "for each field: load, scale, store" the fields were one dependent round trip each --
@@ -65,17 +93,18 @@ __device__ __forceinline__ void gather_row(AR a, int64_t idx, int b, int l) {
 
 // one wave per sampled row; lanes stride over the row's columns (coalesced both sides)
 // AR: `const GatherArgs&` (kernel argument by value) or `const OSRL_CAS GatherArgs&` (device-resident block, argmem.h)
-// NT: the workgroup size when it is a compile-time constant (0: read blockDim -- an s_load from the hidden kernarg block)
-template <class AR, int NT = 0>
+// NT: the workgroup size (a compile-time constant: no kernel here reads blockDim)
+template <class AR, int NT>
 __device__ __forceinline__ void gather_body(AR a, uint32_t step, int block) {
   using namespace osrl_rng;
   const int lane = threadIdx.x & 63;
-  const int b = block * (NT ? NT / 64 : (int)(blockDim.x >> 6)) + (threadIdx.x >> 6);
+  const int b = block * (NT / 64) + (threadIdx.x >> 6);
   if (b >= a.batch) return;
   const U4 r = philox4x32_10(U4{(uint32_t)b, 0x5eedu, step, a.stream_id}, a.k0, a.k1);
   // 64-bit multiply-shift maps a 64-bit uniform onto [0, n_rows) (bias < 2^-40 for n_rows < 2^24)
   const uint64_t u = ((uint64_t)r.x << 32) | r.y;
-  const int64_t idx = (int64_t)__umul64hi(u, (uint64_t)a.n_rows);
+  const uint64_t* __restrict__ cum = a.cum;
+  const int64_t idx = cum ? search_cum<64>(cum, a.n_rows, u, lane, 0) : (int64_t)__umul64hi(u, (uint64_t)a.n_rows);
   if (lane == 0 && a.idx_out) a.idx_out[b] = (int32_t)idx;
   gather_row<64, AR>(a, idx, b, lane);
 }
@@ -90,7 +119,8 @@ __device__ __forceinline__ void gather_tile16(AR a, uint32_t step, int tile) {
   if (b >= a.batch) return;
   const U4 r = philox4x32_10(U4{(uint32_t)b, 0x5eedu, step, a.stream_id}, a.k0, a.k1);
   const uint64_t u = ((uint64_t)r.x << 32) | r.y;
-  const int64_t idx = (int64_t)__umul64hi(u, (uint64_t)a.n_rows);
+  const uint64_t* __restrict__ cum = a.cum;
+  const int64_t idx = cum ? search_cum<32>(cum, a.n_rows, u, l, lane >> 5) : (int64_t)__umul64hi(u, (uint64_t)a.n_rows);
   if (l == 0 && a.idx_out) a.idx_out[b] = (int32_t)idx;
   gather_row<32, AR>(a, idx, b, l);
 }
@@ -98,7 +128,7 @@ __device__ __forceinline__ void gather_tile16(AR a, uint32_t step, int tile) {
 // host: the descriptor of osrl_replay_gather's arguments (false: invalid)
 inline bool fill(GatherArgs& a, int32_t n_fields, const float* const* src, float* const* dst, const int32_t* width,
                  const float* scale, int64_t n_rows, int32_t batch, uint64_t seed, uint32_t stream_id,
-                 const osrl_step_state_t* st) {
+                 const osrl_step_state_t* st, const uint64_t* cum = nullptr) {
   for (int f = 0; f < OSRL_MAX_FIELDS; ++f) {
     a.src[f] = f < n_fields ? src[f] : nullptr;
     a.dst[f] = f < n_fields ? dst[f] : nullptr;
@@ -114,6 +144,7 @@ inline bool fill(GatherArgs& a, int32_t n_fields, const float* const* src, float
   a.k1 = (uint32_t)(seed >> 32);
   a.stream_id = stream_id;
   a.st = st;
+  a.cum = cum;
   return true;
 }
 

@@ -267,6 +267,94 @@ __global__ void gather_rows_kernel(const float* __restrict__ src, int width, con
   }
 }
 
+// ---- the replay sampler's weight table (osrl_weights_cum_u64; semantics in include/osrl_amd.h) ----------------------
+// S_i = O_b + (T_j + L_e): three chains of fp64 additions, each left to right from 0 -- inside a thread's kCumItems rows,
+// over the thread totals of a workgroup, over the workgroup totals.  A chain's last value IS the next level's summand
+// (t_j = the last L of thread j, B_b = T_255 + t_255), so the prefix that ends a thread / a workgroup equals the offset
+// the next one starts from, bit for bit: S is non-decreasing and a zero weight repeats its predecessor.
+constexpr int kCumThreads = 256;
+constexpr int kCumItems = 16;
+constexpr int kCumTile = kCumThreads * kCumItems;
+constexpr int kCumOffThreads = 1024;
+
+__device__ __forceinline__ double cum_weight(const double* __restrict__ w, int64_t e, int64_t n) {
+  const double v = e < n ? w[e] : 0.0;
+  return v > 0.0 ? v : 0.0;  // (negative and NaN weights count as 0)
+}
+
+// thread totals t_j into LDS, then their exclusive running sums T_j in place (one lane, left to right); returns B_b
+__device__ __forceinline__ double cum_thread_offsets(const double* __restrict__ w, int64_t n, int64_t e0, double* t /*[256] LDS*/,
+                                                     double* total /*LDS*/) {
+  double mine = 0.0;
+  for (int k = 0; k < kCumItems; ++k) mine += cum_weight(w, e0 + k, n);
+  t[threadIdx.x] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double run = 0.0;
+    for (int j = 0; j < kCumThreads; ++j) {
+      const double v = t[j];
+      t[j] = run;
+      run += v;
+    }
+    *total = run;
+  }
+  __syncthreads();
+  return *total;
+}
+
+__global__ __launch_bounds__(kCumThreads) void cum_tile_totals_kernel(const double* __restrict__ w, int64_t n,
+                                                                      double* __restrict__ btot) {
+  __shared__ double t[kCumThreads];
+  __shared__ double total;
+  const int64_t e0 = (int64_t)blockIdx.x * kCumTile + (int64_t)threadIdx.x * kCumItems;
+  const double b = cum_thread_offsets(w, n, e0, t, &total);
+  if (threadIdx.x == 0) btot[blockIdx.x] = b;
+}
+
+// in place: off[b] = B_0 + ... + B_(b-1) left to right, off[nb] = the total (one workgroup; a tile at a time through LDS)
+__global__ __launch_bounds__(kCumOffThreads) void cum_tile_offsets_kernel(double* __restrict__ off, int nb) {
+  __shared__ double v[kCumOffThreads];
+  __shared__ double carry;
+  if (threadIdx.x == 0) carry = 0.0;
+  for (int b0 = 0; b0 < nb; b0 += kCumOffThreads) {
+    const int b = b0 + threadIdx.x;
+    v[threadIdx.x] = b < nb ? off[b] : 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double run = carry;
+      const int m = nb - b0 < kCumOffThreads ? nb - b0 : kCumOffThreads;
+      for (int j = 0; j < m; ++j) {
+        const double x = v[j];
+        v[j] = run;
+        run += x;
+      }
+      carry = run;
+    }
+    __syncthreads();
+    if (b < nb) off[b] = v[threadIdx.x];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) off[nb] = carry;
+}
+
+__global__ __launch_bounds__(kCumThreads) void cum_write_kernel(const double* __restrict__ w, int64_t n,
+                                                                const double* __restrict__ off, int nb,
+                                                                uint64_t* __restrict__ cum) {
+  __shared__ double t[kCumThreads];
+  __shared__ double total;
+  const int64_t e0 = (int64_t)blockIdx.x * kCumTile + (int64_t)threadIdx.x * kCumItems;
+  cum_thread_offsets(w, n, e0, t, &total);
+  const double ob = off[blockIdx.x], tj = t[threadIdx.x], all = off[nb];
+  double run = 0.0;
+  for (int k = 0; k < kCumItems; ++k) {
+    const int64_t e = e0 + k;
+    if (e >= n) break;
+    run += cum_weight(w, e, n);
+    const double x = all > 0.0 ? (ob + (tj + run)) / all * 18446744073709551616.0 : 18446744073709551616.0;  // x 2^64
+    cum[e] = x >= 18446744073709551616.0 ? ~0ull : (uint64_t)x;
+  }
+}
+
 inline int grid_for(int64_t n, int threads) {
   const int64_t g = (n + threads - 1) / threads;
   return (int)(g < 1 ? 1 : (g > 65535 * 16 ? 65535 * 16 : g));
@@ -277,6 +365,18 @@ inline int grid_for(int64_t n, int threads) {
 #define S ((hipStream_t)stream)
 
 extern "C" int64_t osrl_ingest_ws_elems(int64_t n) { return (n + kScanTile - 1) / kScanTile + 8; }
+
+extern "C" int64_t osrl_weights_cum_u64_ws_elems(int64_t n) { return (n + kCumTile - 1) / kCumTile + 8; }
+
+extern "C" int osrl_weights_cum_u64(const double* weights, int64_t n, uint64_t* cum, double* ws, void* stream) {
+  if (!weights || !cum || !ws || n < 1 || n > (int64_t)1 << 28) return -1;
+  const int nb = (int)((n + kCumTile - 1) / kCumTile);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(cum_tile_totals_kernel, dim3(nb), dim3(kCumThreads), 0, S, weights, n, ws);
+  hipLaunchKernelGGL(cum_tile_offsets_kernel, dim3(1), dim3(kCumOffThreads), 0, S, ws, nb);
+  hipLaunchKernelGGL(cum_write_kernel, dim3(nb), dim3(kCumThreads), 0, S, weights, n, ws, nb, cum);
+  return (int)hipGetLastError();
+}
 
 extern "C" int osrl_episode_segments(const float* terminals, const float* timeouts, int64_t n, int64_t* ep_end,
                                      int64_t* ep_start, int32_t* ep_len, int32_t* n_episodes, int32_t* ws,

@@ -57,7 +57,7 @@ using osrl_gather::GatherArgs;
 using osrl_gather::gather_body;
 
 __global__ __launch_bounds__(256) void gather_kernel(const GatherArgs a) {
-  gather_body<const GatherArgs&>(a, a.st ? (uint32_t)a.st->step : 0u, blockIdx.x);
+  gather_body<const GatherArgs&, 256>(a, a.st ? (uint32_t)a.st->step : 0u, blockIdx.x);
 }
 
 // 1024-thread workgroups: every workgroup signs in with one atomic on ONE address (those serialise at ~20 ns each:
@@ -265,23 +265,18 @@ extern "C" int osrl_replay_gather(int32_t n_fields, const float* const* src, flo
                                   const int32_t* width, const float* scale, int64_t n_rows, int32_t batch,
                                   int32_t* idx_out, uint64_t seed, uint32_t stream_id,
                                   const osrl_step_state_t* st, void* stream) {
+  return osrl_replay_gather_w(n_fields, src, dst, width, scale, n_rows, batch, idx_out, seed, stream_id, st, nullptr,
+                              stream);
+}
+
+extern "C" int osrl_replay_gather_w(int32_t n_fields, const float* const* src, float* const* dst,
+                                    const int32_t* width, const float* scale, int64_t n_rows, int32_t batch,
+                                    int32_t* idx_out, uint64_t seed, uint32_t stream_id,
+                                    const osrl_step_state_t* st, const uint64_t* cum, void* stream) {
   if (n_fields < 1 || n_fields > OSRL_MAX_FIELDS || !src || !dst || !width || n_rows < 1 || batch < 1) return -1;
   GatherArgs a;
-  for (int f = 0; f < OSRL_MAX_FIELDS; ++f) {
-    a.src[f] = f < n_fields ? src[f] : nullptr;
-    a.dst[f] = f < n_fields ? dst[f] : nullptr;
-    a.width[f] = f < n_fields ? width[f] : 0;
-    a.scale[f] = (f < n_fields && scale) ? scale[f] : 1.0f;
-    if (f < n_fields && (!a.src[f] || !a.dst[f] || a.width[f] < 1)) return -1;
-  }
-  a.n_fields = n_fields;
-  a.batch = batch;
-  a.n_rows = n_rows;
+  if (!osrl_gather::fill(a, n_fields, src, dst, width, scale, n_rows, batch, seed, stream_id, st, cum)) return -1;
   a.idx_out = idx_out;
-  a.k0 = (uint32_t)seed;
-  a.k1 = (uint32_t)(seed >> 32);
-  a.stream_id = stream_id;
-  a.st = st;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(gather_kernel, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
@@ -292,9 +287,20 @@ extern "C" int osrl_step_begin(osrl_step_state_t* st, float beta1, float beta2, 
                                uint64_t noise_seed, uint32_t noise_stream, int32_t n_fields, const float* const* src,
                                float* const* dst, const int32_t* width, const float* scale, int64_t n_rows,
                                int32_t batch, uint64_t gather_seed, uint32_t gather_stream, void* stream) {
-  return osrl_step_begin_peer(st, nullptr, beta1, beta2, warmup, stats_cur, ring, n_stats, ring_len, noise, noise_n,
-                              noise_seed, noise_stream, n_fields, src, dst, width, scale, n_rows, batch, gather_seed,
-                              gather_stream, stream);
+  return osrl_step_begin_peer_w(st, nullptr, beta1, beta2, warmup, stats_cur, ring, n_stats, ring_len, noise, noise_n,
+                                noise_seed, noise_stream, n_fields, src, dst, width, scale, n_rows, batch, gather_seed,
+                                gather_stream, nullptr, stream);
+}
+
+extern "C" int osrl_step_begin_w(osrl_step_state_t* st, float beta1, float beta2, int32_t warmup, const float* stats_cur,
+                                 float* ring, int32_t n_stats, int32_t ring_len, float* noise, int64_t noise_n,
+                                 uint64_t noise_seed, uint32_t noise_stream, int32_t n_fields, const float* const* src,
+                                 float* const* dst, const int32_t* width, const float* scale, int64_t n_rows,
+                                 int32_t batch, uint64_t gather_seed, uint32_t gather_stream, const uint64_t* cum,
+                                 void* stream) {
+  return osrl_step_begin_peer_w(st, nullptr, beta1, beta2, warmup, stats_cur, ring, n_stats, ring_len, noise, noise_n,
+                                noise_seed, noise_stream, n_fields, src, dst, width, scale, n_rows, batch, gather_seed,
+                                gather_stream, cum, stream);
 }
 
 extern "C" int osrl_step_begin_peer(osrl_step_state_t* st, const osrl_step_state_t* peer, float beta1, float beta2,
@@ -303,26 +309,26 @@ extern "C" int osrl_step_begin_peer(osrl_step_state_t* st, const osrl_step_state
                                     uint32_t noise_stream, int32_t n_fields, const float* const* src, float* const* dst,
                                     const int32_t* width, const float* scale, int64_t n_rows, int32_t batch,
                                     uint64_t gather_seed, uint32_t gather_stream, void* stream) {
+  return osrl_step_begin_peer_w(st, peer, beta1, beta2, warmup, stats_cur, ring, n_stats, ring_len, noise, noise_n,
+                                noise_seed, noise_stream, n_fields, src, dst, width, scale, n_rows, batch, gather_seed,
+                                gather_stream, nullptr, stream);
+}
+
+extern "C" int osrl_step_begin_peer_w(osrl_step_state_t* st, const osrl_step_state_t* peer, float beta1, float beta2,
+                                      int32_t warmup, const float* stats_cur, float* ring, int32_t n_stats,
+                                      int32_t ring_len, float* noise, int64_t noise_n, uint64_t noise_seed,
+                                      uint32_t noise_stream, int32_t n_fields, const float* const* src,
+                                      float* const* dst, const int32_t* width, const float* scale, int64_t n_rows,
+                                      int32_t batch, uint64_t gather_seed, uint32_t gather_stream, const uint64_t* cum,
+                                      void* stream) {
   if (!st || peer == st || n_fields < 0 || n_fields > OSRL_MAX_FIELDS || (noise && noise_n < 1)) return -1;
   if (n_fields > 0 && (!src || !dst || !width || n_rows < 1 || batch < 1)) return -1;
   BeginPack k{};
   GatherArgs& a = k.a;
   BeginArgs& b = k.b;
-  for (int f = 0; f < OSRL_MAX_FIELDS; ++f) {
-    a.src[f] = f < n_fields ? src[f] : nullptr;
-    a.dst[f] = f < n_fields ? dst[f] : nullptr;
-    a.width[f] = f < n_fields ? width[f] : 0;
-    a.scale[f] = (f < n_fields && scale) ? scale[f] : 1.0f;
-    if (f < n_fields && (!a.src[f] || !a.dst[f] || a.width[f] < 1)) return -1;
-  }
-  a.n_fields = n_fields;
-  a.batch = n_fields > 0 ? batch : 0;
-  a.n_rows = n_rows;
-  a.idx_out = nullptr;
-  a.k0 = (uint32_t)gather_seed;
-  a.k1 = (uint32_t)(gather_seed >> 32);
-  a.stream_id = gather_stream;
-  a.st = st;
+  if (!osrl_gather::fill(a, n_fields, src, dst, width, scale, n_rows, batch, gather_seed, gather_stream, st,
+                         n_fields > 0 ? cum : nullptr))
+    return -1;
   b.st = st;
   b.beta1 = beta1;
   b.beta2 = beta2;

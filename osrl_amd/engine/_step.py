@@ -28,6 +28,7 @@ class StepEngine:
     parallel_branches = True
     graph: Optional[torch.cuda.CUDAGraph] = None
     replay = None
+    _replay_epoch = 0
     _graph_failed = False
 
     @staticmethod
@@ -134,11 +135,24 @@ class StepEngine:
         """Sample minibatches on device from ``store`` (common/replay.py) inside the step itself."""
         self.replay = store
         self.graph = None
+        self._replay_epoch = getattr(store, "sample_epoch", 0)
+
+    def _replay_mode_changed(self) -> None:
+        """The store switched between uniform and weighted sampling (``ReplayStore.set_sample_prob``): what was captured
+        holds the old mode's arguments, so it is dropped and captured again by the step that is about to run."""
+        self.graph = None
+
+    def _sync_replay(self) -> None:
+        epoch = getattr(self.replay, "sample_epoch", 0)
+        if epoch != self._replay_epoch:
+            self._replay_mode_changed()
+            self._replay_epoch = epoch
 
     def step_replay(self, use_graph: bool = True) -> None:
         """One train step on a minibatch drawn on device from the attached replay store."""
         check_plans_current(self)
         assert self.replay is not None
+        self._sync_replay()
         self._run(use_graph)
 
     def step(self, *batch, noise=None, use_graph: bool = True) -> None:

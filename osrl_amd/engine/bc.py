@@ -75,8 +75,8 @@ class BCEngine(StepEngine):
         k.n_stats, k.ring_len = st.n_stats, st.ring_len
         k.stats_cur, k.ring = st.stats.data_ptr(), st.ring.data_ptr()
         if self.replay is not None:
-            n_f, src, dst, w, sc, n_rows, _B, g_seed, g_stream, keep = self.replay.gather_args((self.obs, self.act), (0, 2))
-            k.n_fields, k.n_rows, k.gather_seed, k.gather_stream = n_f, n_rows, g_seed, g_stream
+            n_f, src, dst, w, sc, n_rows, _B, g_seed, g_stream, keep, cum = self.replay.gather_args((self.obs, self.act), (0, 2))
+            k.n_fields, k.n_rows, k.gather_seed, k.gather_stream, k.cum = n_f, n_rows, g_seed, g_stream, cum
             for i in range(n_f):
                 k.src[i], k.dst[i], k.width[i], k.scale[i] = src[i], dst[i], w[i], sc[i]
             self._step_keep = keep
@@ -126,6 +126,11 @@ class BCEngine(StepEngine):
                              f"{self.obs.shape[1]} (bc_mode='multi-task' appends the cost return: process_bc_dataset)")
         super().attach_replay(store)
         self._step_c = None
+        self._arena_direct = None
+
+    def _replay_mode_changed(self) -> None:
+        super()._replay_mode_changed()
+        self._step_c = None  # (the descriptor holds the table's address, or NULL)
         self._arena_direct = None
 
     def _run(self, use_graph: bool) -> None:

@@ -57,6 +57,7 @@ class PipelinedSteps:
         self.e = (e0, e1)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._par = self._arena = None
+        self._replay_epoch = getattr(engine.replay, "sample_epoch", 0)
 
     # ------------------------------------------------------------------ #
     def _issue(self, par: Branches) -> None:
@@ -95,6 +96,9 @@ class PipelinedSteps:
         e0 = self.e[0]
         check_plans_current(e0)
         check_plans_current(self.e[1])
+        epoch = getattr(e0.replay, "sample_epoch", 0)
+        if epoch != self._replay_epoch:  # uniform <-> weighted sampling: the captured prologues hold the old arguments
+            self.graph, self._replay_epoch = None, epoch
         q, r = divmod(int(n_steps), self.n)
         if q:
             if self.graph is None:
