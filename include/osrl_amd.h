@@ -226,10 +226,18 @@ int osrl_mlp_backward_dz_tail(const osrl_mlp_t* net, int32_t rows, const osrl_ml
  *                        n_samples target samples j of row r (a = [n_a + n_b, rows * n_samples] target outputs, row-major by
  *                        sample: r * n_samples + j; q1 = min over the first n_a, q2 over the last n_b; thres = lambda of
  *                        bcql.py:144-146; x1 may be NULL: no (1 - done)); dy_e = 2 (y_e - backup) inv      (== osrl_bcq_critic_loss)
+ *   OSRL_SEED_FQE        fitted Q evaluation of a frozen policy: the launch's nets are n_a reward critics followed by n_b cost
+ *                        critics (n_a + n_b = n_nets, each <= 4), a = their targets' outputs [n_a + n_b, rows] on (s', pi(s'));
+ *                        net e bootstraps from target e alone (no minimum over members: they stay independent estimates):
+ *                          backup_e = (e < n_a ? x0[r] : b[r]) + gamma (1 - x1[r]) a[e rows + r];  dy_e = 2 (y_e - backup_e) scale
+ *                        (x0 = rewards, b = costs, x1 = done, scale = stat_scale = inv).  TWO statistics: the squared errors
+ *                        of the reward nets are the tile's first partial, those of the cost nets its second;
+ *                          stat[0] = stat_scale sum_{e < n_a, r} (y_e - backup_e)^2,  stat2[0] = stat_scale sum_{e >= n_a, r} (.)^2
+ *                        (either may be NULL) = the sum over members of the batch-mean squared error (net.py:240-242)
  * partials: >= 2 * n_nets * ceil(rows / 16) floats of scratch; counter: one uint32, ZERO before the first launch
  * (re-armed by the launch).  HOST struct. */
 enum { OSRL_SEED_NONE = 0, OSRL_SEED_MSE = 1, OSRL_SEED_CPQ_CRITIC = 2, OSRL_SEED_CPQ_COST = 3, OSRL_SEED_CPQ_ACTOR = 4,
-       OSRL_SEED_GAUSS_HEAD = 5, OSRL_SEED_BCQ_CRITIC = 6 };
+       OSRL_SEED_GAUSS_HEAD = 5, OSRL_SEED_BCQ_CRITIC = 6, OSRL_SEED_FQE = 7 };
 typedef struct {
   int32_t kind;
   int32_t n_a, n_b;
@@ -244,6 +252,7 @@ typedef struct {
   float* partials;
   uint32_t* counter;
   float* stat;
+  float* stat2; /* OSRL_SEED_FQE only: the second statistic (every other kind ignores it) */
 } osrl_mlp_seed_t;
 int osrl_mlp_backward_dz_seed(const osrl_mlp_t* net, int32_t rows, const osrl_mlp_acts_t* saved,
                               const osrl_mlp_grads_t* g, const osrl_mlp_tail_t* tail, const osrl_mlp_seed_t* seed,
@@ -659,6 +668,11 @@ int osrl_cpq_actor_loss(const float* q, int32_t n_q, const float* qc, int32_t n_
 int osrl_mse_loss(const float* u, const float* target, int64_t n, int64_t n_global, float* du, float* stat,
                   void* stream);
 
+/* Value read-out of fitted Q evaluation: acc[e] += sum_r q[e * rows + r] in fp64 (q = [n_nets, rows] critic outputs, acc =
+ * n_nets device doubles that the caller zeroes once and then accumulates into chunk by chunk).  ONE workgroup, one fixed
+ * summation order per net (each lane a contiguous chunk of rows, lanes by the butterfly, waves in order), so a value is
+ * reproducible bit for bit; n_nets <= OSRL_MAX_NETS, rows >= 1. */
+int osrl_fqe_value_sums(const float* q, int32_t n_nets, int32_t rows, double* acc, void* stream);
 /* in-place clamp: the `.clamp(-0.5, 0.5)` of VAE.decode's latent draw (net.py:334-335) */
 int osrl_clamp(float* x, int64_t n, float lo, float hi, void* stream);
 /* BCQ-Lag perturbation tail net.py:61-62: a = clamp(dec + phi*max_a*t, +-max_a) */

@@ -67,10 +67,11 @@ class SeedT(C.Structure):  # osrl_mlp_seed_t
                 ("kl_L", C.c_int32), ("n_samples", C.c_int32), ("gamma", C.c_float), ("thres", C.c_float),
                 ("scale", C.c_float), ("max_action", C.c_float), ("stat_scale", C.c_float),
                 ("stat_scale2", C.c_float), ("kl_beta", C.c_float), ("pad2_", C.c_float), ("partials", _fp),
-                ("counter", C.c_void_p), ("stat", _fp)]
+                ("counter", C.c_void_p), ("stat", _fp), ("stat2", _fp)]
 
 
 SEED_NONE, SEED_MSE, SEED_CPQ_CRITIC, SEED_CPQ_COST, SEED_CPQ_ACTOR, SEED_GAUSS_HEAD, SEED_BCQ_CRITIC = 0, 1, 2, 3, 4, 5, 6
+SEED_FQE = 7
 
 
 class VaeNsT(C.Structure):  # osrl_vae_ns_t
@@ -306,6 +307,7 @@ PROTOTYPES = {
     "osrl_cpq_actor_loss": [_fp, _i32, _fp, _i32, _i32, _f32, _i32, _fp, _fp, _vp],
     "osrl_mse_loss": [_fp, _fp, _i64, _i64, _fp, _fp, _vp],
     "osrl_clamp": [_fp, _i64, _f32, _f32, _vp],
+    "osrl_fqe_value_sums": [_fp, _i32, _i32, _vp, _vp],
     "osrl_bcq_perturb": [_fp, _fp, _i32, _i32, _f32, _f32, _fp, _vp],
     "osrl_bcq_perturb_bwd": [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _f32, _fp, _vp],
     "osrl_bcq_critic_loss": [_fp, _i32, _i32, _i32, _fp, _i32, _fp, _fp, _i32, _f32, _f32, _i32, _fp, _fp, _vp],

@@ -4,6 +4,7 @@ from .bearl import BEARL, BEARLTrainer
 from .cdt import CDT, CDTTrainer
 from .coptidice import COptiDICE, COptiDICETrainer
 from .cpq import CPQ, CPQTrainer
+from .fqe import FQE, FQEEstimate, FQETrainer
 
 __all__ = ["BC", "BCTrainer", "BCQL", "BCQLTrainer", "BEARL", "BEARLTrainer", "CDT", "CDTTrainer", "COptiDICE",
-           "COptiDICETrainer", "CPQ", "CPQTrainer"]
+           "COptiDICETrainer", "CPQ", "CPQTrainer", "FQE", "FQEEstimate", "FQETrainer"]

@@ -927,6 +927,32 @@ __global__ __launch_bounds__(kRed) void mse_loss_kernel(const float* __restrict_
   if (threadIdx.x == 0 && stat) stat[0] = loss * inv_n;
 }
 
+// ---------------- fitted Q evaluation: the value read-out ----------------
+// acc[e] += sum_r q[e * rows + r] in fp64, one workgroup: each lane a contiguous chunk of rows, lanes by the butterfly,
+// waves in order -- one summation order per (net, rows), so FQETrainer.estimate() is reproducible bit for bit.
+constexpr int kFqeThreads = 256;
+__global__ __launch_bounds__(kFqeThreads) void fqe_value_sums_kernel(const float* __restrict__ q, int n_nets, int rows,
+                                                                     double* __restrict__ acc) {
+  __shared__ double s_w[kFqeThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int per = (rows + kFqeThreads - 1) / kFqeThreads;
+  for (int e = 0; e < n_nets; ++e) {
+    const float* __restrict__ qe = q + (size_t)e * rows;
+    double t = 0.0;
+    for (int i = tid * per; i < (tid + 1) * per && i < rows; ++i) t += (double)qe[i];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o);
+    if (lane == 0) s_w[wave] = t;
+    __syncthreads();
+    if (tid == 0) {
+      double u = 0.0;
+      for (int w = 0; w < kFqeThreads / 64; ++w) u += s_w[w];
+      acc[e] += u;
+    }
+    __syncthreads();
+  }
+}
+
 // ---------------- BCQ-Lag ----------------
 __global__ void clamp_kernel(float* __restrict__ x, int64_t n, float lo, float hi) {
   const int64_t i = (int64_t)blockIdx.x * kEw + threadIdx.x;
@@ -1400,6 +1426,13 @@ int osrl_mse_loss(const float* u, const float* target, int64_t n, int64_t n_glob
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(mse_loss_kernel, dim3(1), dim3(kRed), 0, S, u, target, (int)n,
                      1.0f / (float)(n_global > 0 ? n_global : n), du, stat);
+  LAUNCH_CHECK();
+}
+
+int osrl_fqe_value_sums(const float* q, int32_t n_nets, int32_t rows, double* acc, void* stream) {
+  if (!q || !acc || n_nets < 1 || n_nets > OSRL_MAX_NETS || rows < 1) return -1;
+  (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
+  hipLaunchKernelGGL(fqe_value_sums_kernel, dim3(1), dim3(kFqeThreads), 0, S, q, n_nets, rows, acc);
   LAUNCH_CHECK();
 }
 

@@ -714,6 +714,13 @@ __device__ __forceinline__ float seed_dy(SR s, const int e, const int r, const i
     if (ok) l0 += d * d;
     return 2.0f * d * s.scale;
   }
+  if (kind == OSRL_SEED_FQE) {  // net e against its own target member (e is uniform per workgroup: no divergence)
+    const float* __restrict__ xs = e < s.n_a ? s.x0 : s.b;
+    const float backup = xs[r] + s.gamma * (1.0f - s.x1[r]) * s.a[(size_t)e * rows + r];
+    const float d = yv - backup;
+    if (ok) l0 += d * d;  // (the caller moves a cost net's sum to the second partial)
+    return 2.0f * d * s.scale;
+  }
   // OSRL_SEED_GAUSS_HEAD: yrow = (mu | log_std) of the row, NL = 2 ad
   const int ad = NL >> 1;
   const int j = c < ad ? c : c - ad;
@@ -797,6 +804,10 @@ __device__ __forceinline__ void mlp_bwd_dz_body(AR a, const int e, const int til
         float v = dyv * oscale;
         if (act != OSRL_ACT_ID) v *= act_bwd(act, yv * inv_oscale);
         lds[r * lda + c] = ok ? v : 0.f;
+      }
+      if (a.seed.kind == OSRL_SEED_FQE && e >= a.seed.n_a) {  // a cost net: its squared errors are the second statistic
+        l1 = l0;
+        l0 = 0.f;
       }
       if (a.seed.kl_head && e == 0) {  // the KL term of the VAE statistic (vae_loss_body) over this tile's rows
         const int Lz = a.seed.kl_L;
@@ -1001,6 +1012,11 @@ __device__ __forceinline__ void mlp_bwd_dz_body(AR a, const int e, const int til
           u1 += s_seed[1][w];
         }
         a.seed.stat[0] = u0 * a.seed.stat_scale + a.seed.kl_beta * (u1 * a.seed.stat_scale2);
+      }
+      if (tid == 0 && a.seed.kind == OSRL_SEED_FQE && a.seed.stat2) {  // (waves in order, as above)
+        float u1 = 0.f;
+        for (int w = 0; w < NW; ++w) u1 += s_seed[1][w];
+        a.seed.stat2[0] = u1 * a.seed.stat_scale;
       }
     }
   }
@@ -2407,6 +2423,9 @@ static bool seed_ok(const osrl_mlp_seed_t* s, const osrl_mlp_t* net, const osrl_
       return NL == 1 && s->a && s->b && s->n_a >= 1 && s->n_a <= kSeedEns && s->n_b >= 1 && s->n_b <= kSeedEns;
     case OSRL_SEED_BCQ_CRITIC:
       return NL == 1 && s->a && s->x0 && s->n_a >= 1 && s->n_b >= 1 && s->n_samples >= 1;
+    case OSRL_SEED_FQE:
+      return NL == 1 && s->a && s->b && s->x0 && s->x1 && s->n_a >= 1 && s->n_a <= kSeedEns && s->n_b >= 1 && s->n_b <= kSeedEns &&
+             s->n_a + s->n_b == net->n_nets && s->kl_head == nullptr;
     case OSRL_SEED_GAUSS_HEAD:
       return (NL & 1) == 0 && net->n_nets == 1 && s->a && s->eps && s->tanh_u && s->n_a >= 1 && s->n_a <= kSeedEns && !s->partials;
     default: return false;

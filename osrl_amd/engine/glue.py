@@ -359,3 +359,16 @@ def seed_bcq_critic(q_t, n1, n2, n_samples, base, done, rows, gamma, lmbda, rows
     s.scale = s.stat_scale = float(_inv(rows, rows_global))
     s._keep += [q_t, base, done]
     return s
+
+
+def seed_fqe(q_t, n_r, n_c, rew, cost, done, rows, gamma, ws, stat_r, stat_c):
+    """Fitted Q evaluation (OSRL_SEED_FQE): the launch's nets are ``n_r`` reward critics then ``n_c`` cost critics, ``q_t``
+    [n_r + n_c, rows] their targets' outputs on (s', pi(s')); net e bootstraps from target e alone.  ``stat_r`` / ``stat_c``:
+    the sum over the reward / cost members of the batch-mean squared error."""
+    s = _seed(L.SEED_FQE, rows, 0, ws, stat_r)
+    s.stat2 = _p(stat_c) if ws is not None else None
+    s.a, s.n_a, s.n_b, s.x0, s.b, s.x1 = _p(q_t), int(n_r), int(n_c), _p(rew), _p(cost), _p(done)
+    s.gamma = float(gamma)
+    s.scale = s.stat_scale = float(_inv(rows, 0))
+    s._keep += [q_t, rew, cost, done]
+    return s
