@@ -1029,6 +1029,37 @@ typedef struct {
 int osrl_env_step(const osrl_env_t* env, const float* act, float* state, float* obs, int32_t obs_ld, float* acc,
                   float* step_out /* optional [E,2]: this step's (reward, raw cost) */, int32_t episodes, void* stream);
 
+/* osrl_env_step with exploration noise, recording what it does: one launch perturbs the policy's action, steps the
+ * environment with osrl_env_step's arithmetic (bit for bit), writes the transition into DSRL-layout tables and keeps the
+ * discounted sums.  Episode ep at its own step t = acc[ep][2] (t < episode_len, done latch clear; otherwise the launch
+ * writes nothing for it):
+ *   a = clip(act[ep] + sigma[ep] * eps, +-max_action); sigma[ep] == 0 gives exactly clip(act[ep]) (eps is not read);
+ *   eps = eps_in[(t * episodes + ep) * action_dim + k] when eps_in is given, else word (k & 3) -> N(0,1) (the map of
+ *         osrl_randn_fill) of Philox4x32-10(counter {episode_base + ep, t, k >> 2, stream_id}, key *seed): a function of
+ *         (seed, episode id, step, column) alone;
+ *   row ep * episode_len + t of the tables: observations = s, actions = a, next_observations = s', rewards, costs (raw
+ *         0 / 1), terminals = 0, timeouts = (t + 1 >= episode_len);
+ *   disc[ep] = {sum gamma^t r, sum gamma^t cost * cost_scale, gamma^t (start: 1), unused}.
+ * seed, gamma and sigma are read from device memory: a captured launch follows their current values. */
+typedef struct {
+  float* observations;      /* [episodes * episode_len, state_dim] */
+  float* actions;           /* [episodes * episode_len, action_dim] */
+  float* next_observations; /* [episodes * episode_len, state_dim] */
+  float* rewards;           /* [episodes * episode_len] */
+  float* costs;
+  float* terminals;
+  float* timeouts;
+  float* disc;              /* [episodes, 4] */
+  const float* sigma;       /* [episodes] */
+  const float* gamma;       /* [1] */
+  const uint64_t* seed;     /* [1] */
+  const float* eps_in;      /* [episode_len, episodes, action_dim] or NULL */
+  uint32_t episode_base;
+  uint32_t stream_id;
+} osrl_collect_t;
+int osrl_env_collect(const osrl_env_t* env, const osrl_collect_t* rec, const float* act, float* state, float* obs,
+                     int32_t obs_ld, float* acc, int32_t episodes, void* stream);
+
 /* CDTTrainer.rollout (cdt.py:436-518) with E episodes as batch rows.  The reference keeps the whole history and
  * slices its last seq_len steps per env step; here the CDT engine's [E, seq_len] batch buffers are the window
  * itself: left-aligned and growing (mask = 1 on the filled prefix) until full, then sliding by one per env step.

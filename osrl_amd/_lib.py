@@ -135,6 +135,13 @@ class EnvT(C.Structure):
                 ("pad2_", C.c_float)]
 
 
+class CollectT(C.Structure):  # osrl_collect_t
+    _fields_ = [("observations", C.c_void_p), ("actions", C.c_void_p), ("next_observations", C.c_void_p),
+                ("rewards", C.c_void_p), ("costs", C.c_void_p), ("terminals", C.c_void_p), ("timeouts", C.c_void_p),
+                ("disc", C.c_void_p), ("sigma", C.c_void_p), ("gamma", C.c_void_p), ("seed", C.c_void_p),
+                ("eps_in", C.c_void_p), ("episode_base", C.c_uint32), ("stream_id", C.c_uint32)]
+
+
 class GemvNetT(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("dims", C.c_int32 * (MAX_LAYERS + 1)), ("acts", C.c_int32 * MAX_LAYERS),
                 ("out_scale", C.c_float), ("Wf", C.c_void_p * MAX_LAYERS), ("b", C.c_void_p * MAX_LAYERS)]
@@ -180,6 +187,7 @@ _P = C.POINTER
 PROTOTYPES = {
     "osrl_mlp_forward": [_P(MlpT), _P(RowsT), _P(ActsT), _vp],
     "osrl_env_step": [_P(EnvT), _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp],
+    "osrl_env_collect": [_P(EnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _i32, _vp],
     "osrl_cdt_rollout_pick": [_vp, _i32, _i32, _i32, _i32, _vp, _f32, _vp, _vp],
     "osrl_cdt_rollout_push": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _f32, _i32,
                               _vp, _i32, _vp],

@@ -123,6 +123,23 @@ class RolloutMixin:
         self.model.train()
         return self._scale_results(np.mean(rets), np.mean(costs), np.mean(lens))
 
+    def collect(self, noise_std=0.0, gamma: Optional[float] = None, seed: int = 0, noise=None):
+        """The ``evaluate`` rollout on a ``VecSyntheticSafeEnv``, recorded: every episode of ``self.env`` runs to its end
+        with ``a = clip(pi(s) + sigma_e * eps)`` and comes back as a DSRL-layout dataset on device plus the per-episode
+        (discounted) returns -- a ``Collected`` (engine/collect.py).  ``noise_std``: one sigma or one per episode;
+        ``gamma`` (None: 1) weighs the discounted sums; ``seed`` keys the noise drawn on device; ``noise``
+        ``[episode_len, E, action_dim]`` injects it instead.  The policy, the appended cost limit of BC multi-task and
+        the cost scale are ``evaluate``'s.  Any other kind of environment: TypeError."""
+        from ..common.synthetic_env import VecSyntheticSafeEnv
+        if not isinstance(self.env, VecSyntheticSafeEnv):
+            raise TypeError(f"collect() records the batched on-device rollout: self.env must be a VecSyntheticSafeEnv, "
+                            f"not {type(self.env).__name__}")
+        self._before_evaluate()
+        from ..engine.collect import collect_batched
+        cs = self._cost_scale()
+        return collect_batched(self, self.EVAL_KIND, 1.0 if cs is None else cs, self._eval_extra(),
+                               noise_std=noise_std, gamma=gamma, seed=seed, noise=noise)
+
     @torch.no_grad()
     def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):
         """``rollout`` on each of the host environments ``envs`` at once, in lockstep through

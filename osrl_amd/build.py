@@ -14,7 +14,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libosrl_amd.so")
-SOURCES = ["mlp.hip", "linear_split.hip", "mlp_nb.hip", "mlp_nb64.hip", "mlp_dw.hip", "vae_ns.hip", "optim.hip", "rng.hip", "glue.hip", "cdt.hip", "cdt_grad.hip", "env.hip", "ingest.hip", "augment.hip", "bear.hip", "dice.hip", "act.hip", "act_vec.hip", "cdt_act.hip", "ipc.hip", "diag.hip"]
+SOURCES = ["mlp.hip", "linear_split.hip", "mlp_nb.hip", "mlp_nb64.hip", "mlp_dw.hip", "vae_ns.hip", "optim.hip", "rng.hip", "glue.hip", "cdt.hip", "cdt_grad.hip", "env.hip", "collect.hip", "ingest.hip", "augment.hip", "bear.hip", "dice.hip", "act.hip", "act_vec.hip", "cdt_act.hip", "ipc.hip", "diag.hip"]
 
 
 def _hipcc() -> str:
@@ -24,7 +24,7 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (needed to build libosrl_amd.so for gfx950)")
 
 
-HEADERS = ["philox.h", "step.h", "argmem.h", "adam.h", "gather.h", "mlp_common.h", "dwt.h", "gelu.h", "trace.h", "pf_dist.h", "policy_common.h"]  # csrc headers shared between translation units
+HEADERS = ["philox.h", "step.h", "argmem.h", "adam.h", "gather.h", "mlp_common.h", "dwt.h", "gelu.h", "trace.h", "pf_dist.h", "policy_common.h", "env_step.h"]  # csrc headers shared between translation units
 
 
 def _common_deps():

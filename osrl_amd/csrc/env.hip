@@ -8,69 +8,35 @@
 #include <cstdint>
 
 #include "../../include/osrl_amd.h"
+#include "env_step.h"
 
 namespace {
 
-constexpr int kMaxDim = 256;
+using osrl_env::kMaxDim;
 
 __global__ __launch_bounds__(256) void env_step_kernel(osrl_env_t e, const float* __restrict__ act,
                                                        float* __restrict__ state, float* __restrict__ obs,
                                                        int obs_ld, float* __restrict__ acc /*[E,4]*/,
                                                        float* __restrict__ step_out /*[E,2] or null*/) {
-  __shared__ float s[kMaxDim];
-  __shared__ float a[64];
-  __shared__ float red[2][4];
+  __shared__ osrl_env::Lds l;
   const int ep = blockIdx.x, t = threadIdx.x;
   const int od = e.state_dim, ad = e.action_dim;
   float* st = state + (size_t)ep * od;
   float* ac = acc + (size_t)ep * 4;
   const bool alive = ac[3] == 0.f;  // finished episodes keep their state and totals (uniform per workgroup)
-  if (t < od) s[t] = st[t];
-  if (t < ad) a[t] = fminf(fmaxf(act[(size_t)ep * ad + t], -e.max_action), e.max_action);
+  if (t < od) l.s[t] = st[t];
+  if (t < ad) l.a[t] = osrl_env::clip_action(act[(size_t)ep * ad + t], e.max_action);
   __syncthreads();
-  float sn = 0.f, d2 = 0.f, sw = 0.f;
-  if (t < od) {
-    // At / Bt are stored transposed: lane t reads column t of each row -> coalesced, L2-resident for all episodes
-    float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-    int j = 0;
-    for (; j + 4 <= od; j += 4) {
-      p0 = fmaf(e.At[(size_t)(j + 0) * od + t], s[j + 0], p0);
-      p1 = fmaf(e.At[(size_t)(j + 1) * od + t], s[j + 1], p1);
-      p2 = fmaf(e.At[(size_t)(j + 2) * od + t], s[j + 2], p2);
-      p3 = fmaf(e.At[(size_t)(j + 3) * od + t], s[j + 3], p3);
-    }
-    for (; j < od; ++j) p0 = fmaf(e.At[(size_t)j * od + t], s[j], p0);
-    float sb = 0.f;
-    for (int k = 0; k < ad; ++k) sb = fmaf(e.Bt[(size_t)k * od + t], a[k], sb);
-    sn = ((p0 + p1) + (p2 + p3)) + sb;
-    const float d = sn - e.goal[t];
-    d2 = d * d;
-    sw = sn * e.w[t];
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    d2 += __shfl_xor(d2, o);
-    sw += __shfl_xor(sw, o);
-  }
-  if ((t & 63) == 0) {
-    red[0][t >> 6] = d2;
-    red[1][t >> 6] = sw;
-  }
-  __syncthreads();
+  const float sn = osrl_env::advance(e, l, t);  // (csrc/env_step.h: shared with the collecting kernel)
   if (!alive) return;
   if (t < od) {
     st[t] = sn;
     obs[(size_t)ep * obs_ld + t] = sn;
   }
   if (t == 0) {
-    const int nw = (blockDim.x + 63) >> 6;
-    float D = 0.f, W = 0.f;
-    for (int i = 0; i < nw; ++i) {
-      D += red[0][i];
-      W += red[1][i];
-    }
+    float rew, cost;
+    osrl_env::outcome(e, l, rew, cost);
     const float len = ac[2] + 1.f;
-    const float rew = 1.f - 0.1f * D, cost = W > e.cost_threshold ? 1.f : 0.f;
     ac[0] += rew;
     ac[1] += cost * e.cost_scale;
     if (step_out) {
@@ -197,7 +163,7 @@ __global__ void cursor_inc_kernel(int* cursor, int episode_len) {
 extern "C" int osrl_env_step(const osrl_env_t* env, const float* act, float* state, float* obs, int32_t obs_ld,
                              float* acc, float* step_out, int32_t episodes, void* stream) {
   if (!env || !act || !state || !obs || !acc || episodes < 1) return -1;
-  if (env->state_dim < 1 || env->state_dim > kMaxDim || env->action_dim < 1 || env->action_dim > 64 ||
+  if (env->state_dim < 1 || env->state_dim > kMaxDim || env->action_dim < 1 || env->action_dim > osrl_env::kMaxAct ||
       obs_ld < env->state_dim || !env->At || !env->Bt || !env->w || !env->goal)
     return -1;
   (void)hipGetLastError();

@@ -33,11 +33,8 @@ __device__ __forceinline__ void randn_body(float* __restrict__ out, int64_t n, u
   const int64_t nt = kConst ? NT : (int64_t)blockDim.x;
   for (int64_t i = block * nt + threadIdx.x; i < n4; i += n_blocks * nt) {
     const U4 r = philox4x32_10(U4{(uint32_t)i, (uint32_t)(i >> 32), step, stream_id}, k0, k1);
-    const float r0 = sqrtf(-2.0f * __logf(u01(r.x))), r1 = sqrtf(-2.0f * __logf(u01(r.z)));
-    float s0, c0, s1, c1;
-    __sincosf(6.283185307179586f * u01(r.y), &s0, &c0);
-    __sincosf(6.283185307179586f * u01(r.w), &s1, &c1);
-    const float z[4] = {r0 * c0, r0 * s0, r1 * c1, r1 * s1};
+    float z[4];
+    normal4(r, z);
     const int64_t base = i * 4;
     if (base + 3 < n && ((reinterpret_cast<uintptr_t>(out) & 15) == 0)) {
       *reinterpret_cast<float4*>(out + base) = make_float4(z[0], z[1], z[2], z[3]);

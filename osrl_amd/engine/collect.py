@@ -1,0 +1,167 @@
+"""Datasets made on device: the batched rollout of ``engine/rollout.py`` with per-episode exploration noise, every
+transition recorded in HBM under the seven DSRL keys ("Collecting datasets on device").
+
+``Collector`` is a ``BatchedRollout`` whose step ends in ``osrl_env_collect`` (csrc/collect.hip) instead of
+``osrl_env_step``: same policy launches, same environment arithmetic, plus the noise on the action, one table row per
+episode and step, and the discounted sums.  What comes out goes into ``ReplayStore`` / ``SequenceStore.from_dataset`` /
+``process_bc_dataset`` as it is -- collect -> store -> train -> evaluate -> FQE without leaving the device.
+
+Noise: ``a = clip(pi(s) + sigma_e * eps)``.  ``eps`` is Philox4x32-10 keyed by (seed, episode id = base_seed + e, the
+episode's own step, action column) on stream ``_EPS_STREAM``: it does not depend on E, on the graph chunking or on which
+replay a step falls in.  Seed, gamma and sigma live in device memory, so a captured graph follows them.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+from .core import cur_stream
+from .rollout import _CHUNK, BatchedRollout
+
+_EPS_STREAM = 13   # Philox stream id of the exploration noise (11 / 12: the BCQL decode noise of rollout.py / fqe.py)
+_GUARD_ROWS = 4    # sentinel rows before and after every table (``Collector.guards_intact``)
+_SENTINEL = 0x5EA7BEEF
+KEYS = ("observations", "actions", "next_observations", "rewards", "costs", "terminals", "timeouts")
+
+
+class Collected(NamedTuple):
+    """``dataset``: fresh device tensors under the seven DSRL keys, ``E * L`` rows, episode-major (row ``e * L + t``);
+    costs raw 0 / 1, ``terminals`` all 0, ``timeouts`` 1 on each episode's last row.  The per-episode sums are numpy
+    fp64 ``[E]``; the two cost sums carry the collector's ``cost_scale`` (as ``BatchedRollout.run``'s do), the discounted
+    ones weigh step t by ``gamma ** t``."""
+    dataset: Dict[str, torch.Tensor]
+    returns: np.ndarray
+    cost_returns: np.ndarray
+    lengths: np.ndarray
+    disc_returns: np.ndarray
+    disc_cost_returns: np.ndarray
+
+
+def merge_datasets(datasets: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
+    """Several collections as one dataset: a ``torch.cat`` per key, in the order given."""
+    if not datasets:
+        raise ValueError("merge_datasets needs at least one dataset")
+    return {k: torch.cat([d[k] for d in datasets], 0) for k in datasets[0]}
+
+
+class Collector(BatchedRollout):
+    """``run`` = all ``venv.E`` episodes to completion, recorded.  The tables are this object's (sized at the first run,
+    again when the episode length changes); ``run`` hands out copies."""
+
+    def __init__(self, model, venv, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None,
+                 seed: int = 0, z: Optional[torch.Tensor] = None, use_graph: bool = True):
+        super().__init__(model, venv, kind, cost_scale, extra_obs, seed, z, use_graph)
+        dev, E = self.obs.device, venv.E
+        self.disc = torch.zeros(E, 4, dtype=torch.float32, device=dev)
+        self.sigma = torch.zeros(E, dtype=torch.float32, device=dev)
+        self.gamma = torch.ones(1, dtype=torch.float32, device=dev)
+        self.seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.bufs: Dict[str, torch.Tensor] = {}
+        self.tables: Dict[str, torch.Tensor] = {}
+        self.rec: Optional[L.CollectT] = None
+        self._eps: Optional[torch.Tensor] = None  # the injected noise of the run in progress
+
+    def _alloc(self, steps: int) -> None:
+        E, od, ad, dev = self.venv.E, self.venv.state_dim, self.model.action_dim, self.obs.device
+        n, g = E * steps, _GUARD_ROWS
+        self.bufs, self.tables = {}, {}
+        for k in KEYS:
+            w = {"observations": od, "next_observations": od, "actions": ad}.get(k, 0)  # 0: a 1-D table, as DSRL's are
+            buf = torch.full(((n + 2 * g) * max(w, 1),), _SENTINEL, dtype=torch.int32, device=dev).view(torch.float32)
+            body = buf[g * max(w, 1):(g + n) * max(w, 1)]
+            self.bufs[k], self.tables[k] = buf, body.view(n, w) if w else body
+        r = self.rec = L.CollectT()
+        for k in KEYS:
+            setattr(r, k, self.tables[k].data_ptr())
+        r.disc, r.sigma, r.gamma = self.disc.data_ptr(), self.sigma.data_ptr(), self.gamma.data_ptr()
+        r.seed, r.eps_in = self.seed_dev.data_ptr(), None
+        r.episode_base, r.stream_id = self.venv.base_seed & 0xFFFFFFFF, _EPS_STREAM
+
+    def guards_intact(self) -> bool:
+        """True while the sentinel rows around every table hold their pattern (one host sync: a diagnostic)."""
+        ok = torch.ones((), dtype=torch.bool, device=self.obs.device)
+        for k, buf in self.bufs.items():
+            w = buf.numel() // (self.tables[k].shape[0] + 2 * _GUARD_ROWS)
+            i = buf.view(torch.int32)
+            ok = ok & (i[:_GUARD_ROWS * w] == _SENTINEL).all() & (i[-_GUARD_ROWS * w:] == _SENTINEL).all()
+        return bool(ok.item())
+
+    def body(self) -> None:
+        act = self.policy()
+        rec = self.rec
+        if self._eps is not None:  # an eager run with injected noise: the same descriptor with the tensor's address
+            rec = L.CollectT.from_buffer_copy(self.rec)
+            rec.eps_in = self._eps.data_ptr()
+        v = self.venv
+        L.check(L.load().osrl_env_collect(self.env_c, rec, act.data_ptr(), v.state.data_ptr(), self.obs.data_ptr(),
+                                          self.obs.stride(0), v.acc.data_ptr(), v.E, cur_stream()), "osrl_env_collect")
+
+    def _snapshot(self):
+        return super()._snapshot() + [(self.disc, self.disc.clone())]
+
+    @torch.no_grad()
+    def run(self, noise_std=0.0, gamma: Optional[float] = None, seed: Optional[int] = None,
+            noise: Optional[torch.Tensor] = None) -> Collected:
+        """``noise_std``: one sigma for all episodes or ``[E]`` of them.  ``gamma`` (None: 1.0) weighs the discounted
+        sums.  ``seed`` (None: keep the current one) keys the noise drawn on device.  ``noise``: ``[L, E, action_dim]``
+        injected instead (the run is then eager); rows of episodes whose sigma is 0 are not read."""
+        v, m = self.venv, self.model
+        E, ad, dev = v.E, m.action_dim, self.obs.device
+        steps = min(m.episode_len, v.episode_len or m.episode_len)
+        if self.env_c.episode_len != steps or self.rec is None:  # descriptors are by-value arguments of the graph
+            self.env_c.episode_len, self.graph = steps, None
+            self._alloc(steps)
+        if seed is not None and int(seed) != self.seed:
+            self.seed = int(seed)
+            if self.kind == "bcql" and not self.z_fixed:
+                self.graph = None  # (the decode noise's seed is a by-value argument of its launch)
+        if (noise_std.dim() if torch.is_tensor(noise_std) else np.ndim(noise_std)) == 0:
+            self.sigma.fill_(float(noise_std))
+        else:
+            sg = torch.as_tensor(noise_std, dtype=torch.float32).reshape(-1)
+            if sg.numel() != E:
+                raise ValueError(f"noise_std holds {sg.numel()} values, the environment {E} episodes")
+            self.sigma.copy_(sg, non_blocking=True)
+        self.gamma.fill_(1.0 if gamma is None else float(gamma))
+        s64 = self.seed & 0xFFFFFFFFFFFFFFFF
+        self.seed_dev.fill_(s64 - (1 << 64) if s64 >= (1 << 63) else s64)
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32).to(dev).contiguous()
+            if tuple(noise.shape) != (steps, E, ad):
+                raise ValueError(f"noise must be [{steps}, {E}, {ad}] (episode_len, episodes, action_dim), "
+                                 f"got {tuple(noise.shape)}")
+        v.reset(self.obs)
+        self.disc.zero_()
+        self.disc[:, 2] = 1.0
+        graph = self.use_graph and noise is None
+        if graph and self.graph is None:
+            self._capture()
+        self._eps = noise
+        try:
+            if graph:
+                for _ in range((steps + _CHUNK - 1) // _CHUNK):
+                    self.graph.replay()
+            else:
+                for _ in range(steps):
+                    self.body()
+        finally:
+            self._eps = None
+        data = {k: t.clone() for k, t in self.tables.items()}
+        tot = torch.cat([v.acc, self.disc], 1).cpu().numpy().astype(np.float64)  # the one host sync of the run
+        return Collected(data, tot[:, 0], tot[:, 1], tot[:, 2], tot[:, 4], tot[:, 5])
+
+
+def collect_batched(trainer, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None, **run_kw) -> Collected:
+    """``Trainer.collect`` on a ``VecSyntheticSafeEnv``; the collector (buffers, tables, captured graph) is cached on the
+    trainer like ``evaluate``'s rollout, and reads the model's packed weights in place."""
+    venv = trainer.env
+    key = (id(venv), kind, float(cost_scale), extra_obs)
+    co = getattr(trainer, "_collector", None)
+    if co is None or co[0] != key:
+        co = (key, Collector(trainer.model, venv, kind, cost_scale, extra_obs,
+                             use_graph=getattr(trainer, "use_graph", True)))
+        trainer._collector = co
+    return co[1].run(**run_kw)

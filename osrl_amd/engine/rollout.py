@@ -66,7 +66,8 @@ class BatchedRollout:
                 G.clamp_(self.z, -0.5, 0.5)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
 
-    def body(self) -> None:
+    def policy(self) -> torch.Tensor:
+        """The policy's launches on ``self.obs`` -> the [E, action_dim] actions (a buffer of this object)."""
         m, E, ad = self.model, self.venv.E, self.model.action_dim
         if self.kind == "bc":
             act = self.r_pi.forward(self.obs)[0]
@@ -83,11 +84,17 @@ class BatchedRollout:
             t = self.r_pi.forward(self.obs, dec)[0]
             G.bcq_perturb(dec, t, E, ad, float(m.actor.phi), float(m.max_action), self.a)
             act = self.a
-        self.venv.step(self.env_c, act, self.obs)
+        return act
+
+    def body(self) -> None:
+        self.venv.step(self.env_c, self.policy(), self.obs)
+
+    def _snapshot(self):
+        """What one ``body`` changes, cloned: ``_capture`` runs the body once for real before it records."""
+        return [(t, t.clone()) for t in (self.venv.state, self.venv.acc, self.obs, self.st.state)]
 
     def _capture(self) -> None:
-        snap = (self.venv.state.clone(), self.venv.acc.clone(), self.obs.clone(), self.st.state.clone(),
-                self.st.host_step)
+        snap, host_step = self._snapshot(), self.st.host_step
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -98,9 +105,9 @@ class BatchedRollout:
             for _ in range(_CHUNK):
                 self.body()
         torch.cuda.synchronize()
-        self.venv.state.copy_(snap[0]); self.venv.acc.copy_(snap[1]); self.obs.copy_(snap[2])
-        self.st.state.copy_(snap[3])
-        self.st.host_step = snap[4]
+        for t, saved in snap:
+            t.copy_(saved)
+        self.st.host_step = host_step
         self.graph = gr
 
     @torch.no_grad()
