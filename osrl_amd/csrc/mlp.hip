@@ -194,6 +194,21 @@ __device__ __forceinline__ void layer_run(const float* lds, int lda, int nk, con
   }
 }
 
+// A copy of a loop-invariant value that the compiler cannot see through (ON; else the value itself).  Whatever an
+// epilogue computes from such a copy -- row and column addresses of the LDS tile -- is computed again in every layer
+// instead of being hoisted out of the layer loop and held in registers across the k-loops.  The 8-wave chain kernels
+// use it to fit 80 registers (6 waves per SIMD, a third workgroup per CU); a handful of VALU instructions per layer.
+template <bool ON>
+__device__ __forceinline__ int fresh_v(int x) {
+  if (ON) asm volatile("" : "+v"(x));
+  return x;
+}
+template <bool ON>
+__device__ __forceinline__ int fresh_s(int x) {
+  if (ON) asm volatile("" : "+s"(x));
+  return x;
+}
+
 // Narrow layer (N <= 32, e.g. the 1-wide Q head or the 2*ad-wide policy head): instead of one wave
 // walking all of K alone, the 4 waves split K; partial tiles are summed through the (free) LDS
 // activation buffer.  On return lds[row][c], c < nblk*16, holds the raw sums (no bias/activation).
@@ -226,10 +241,13 @@ __device__ __forceinline__ void narrow_layer_splitk(float* lds, int lda, int nk,
   for (int rb = 0; rb < NRB; ++rb) t[rb][0] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (np.k_n > 0) mm_run<NRB, 1, NCB, 1, 3>(lds, lda, np.k_n, P, Np, np.col, t, ring, np.k_lo);
   __syncthreads();  // all reads of the input activations are done
+  {
+    const int ln = fresh_v<NW == 8>(lane), ld = fresh_s<NW == 8>(lda);
 #pragma unroll
-  for (int rb = 0; rb < NRB; ++rb)
+    for (int rb = 0; rb < NRB; ++rb)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) lds[(rb * 16 + (lane >> 4) * 4 + r) * lda + wave * 16 + (lane & 15)] = t[rb][0][r];
+      for (int r = 0; r < 4; ++r) lds[(rb * 16 + (ln >> 4) * 4 + r) * ld + wave * 16 + (ln & 15)] = t[rb][0][r];
+  }
   __syncthreads();
   constexpr int BM = 16 * NRB;
   const int ncol = nblk * 16;
@@ -425,6 +443,16 @@ struct FwdArgs {
 constexpr int waves_per_simd(int nrb, int ncb) {
   return nrb * ncb >= 14 ? 2 : nrb * ncb == 8 ? OSRL_WPS_8 : nrb * ncb >= 4 ? 3 : 4;
 }
+// The 8-wave chain kernels (NW == 8: a workgroup puts 2 waves on every SIMD) at NCB <= 2, i.e. the 256-wide Q networks on
+// the training rows: 6 waves per SIMD = 80 registers = THREE workgroups per CU, so a 6-net launch (768 workgroups) is one
+// round of the chip's 768 slots instead of 1.5 rounds of 512.  At 4 the same sources take 85-89 registers (5 waves by
+// registers, of which an 8-wave workgroup can use 4).  The fit is spill-free only with fresh_v / fresh_s above
+// (profiles/q_chain_regfit.txt); in the step it is worth about +2 % at C2, and the economy alone, at 4, nothing
+// (profiles/q_ns_bench_ab.json)
+#ifndef OSRL_CHAIN_WPS
+#define OSRL_CHAIN_WPS 6
+#endif
+constexpr int chain_wps(int ncb) { return ncb <= 2 ? OSRL_CHAIN_WPS : 2; }
 // the backward kernel also holds the prefetched activations of the epilogue: one wave less
 constexpr int waves_per_simd_bwd(int nrb, int ncb) { return nrb * ncb >= 7 ? 2 : 3; }
 
@@ -543,15 +571,16 @@ __device__ __forceinline__ void mlp_fwd_body(AR a, const int e, const int tile) 
       PHASE_STAMP(2 + 4 * l);
       __syncthreads();  // every wave finished reading the previous activations
       PHASE_STAMP(3 + 4 * l);
+      const int lane_e = fresh_v<NW == 8>(lane), lda_e = fresh_s<NW == 8>(lda);
       // the activation switch is hoisted out of the element loop: with a per-element runtime switch every one of
       // the NRB*NCB*4 values jumped over an inlined tanhf body (4 scalar branches each, ~14 KB of sparse code):
       // measured 10-11k cycles per epilogue vs 17k for the whole first-layer k-loop (tools/mlp_phase.hip)
       if (act == OSRL_ACT_RELU)
-        fwd_epilogue<NRB, NCB, OSRL_ACT_RELU>(lds, lda, acc, cb0, cnt, N, oscale, lane);
+        fwd_epilogue<NRB, NCB, OSRL_ACT_RELU>(lds, lda_e, acc, cb0, cnt, N, oscale, lane_e);
       else if (act == OSRL_ACT_TANH)
-        fwd_epilogue<NRB, NCB, OSRL_ACT_TANH>(lds, lda, acc, cb0, cnt, N, oscale, lane);
+        fwd_epilogue<NRB, NCB, OSRL_ACT_TANH>(lds, lda_e, acc, cb0, cnt, N, oscale, lane_e);
       else
-        fwd_epilogue<NRB, NCB, OSRL_ACT_ID>(lds, lda, acc, cb0, cnt, N, oscale, lane);
+        fwd_epilogue<NRB, NCB, OSRL_ACT_ID>(lds, lda_e, acc, cb0, cnt, N, oscale, lane_e);
     }
     PHASE_STAMP(4 + 4 * l);
     __syncthreads();
@@ -569,12 +598,12 @@ __device__ __forceinline__ void mlp_fwd_body(AR a, const int e, const int tile) 
 }
 
 template <int NRB, int NCB, int NW = 4>
-__global__ __launch_bounds__(64 * NW, (NW == 8 ? (NCB <= 2 ? 4 : 2) : waves_per_simd(NRB, NCB))) void mlp_fwd_kernel(const FwdArgs a) {
+__global__ __launch_bounds__(64 * NW, (NW == 8 ? chain_wps(NCB) : waves_per_simd(NRB, NCB))) void mlp_fwd_kernel(const FwdArgs a) {
   mlp_fwd_body<NRB, NCB, NW, const FwdArgs&>(a, blockIdx.y, blockIdx.x);
 }
 // the same kernel with its descriptor in device memory (argmem.h)
 template <int NRB, int NCB, int NW = 4>
-__global__ __launch_bounds__(64 * NW, (NW == 8 ? (NCB <= 2 ? 4 : 2) : waves_per_simd(NRB, NCB))) void mlp_fwd_kernel_p(const void* p) {
+__global__ __launch_bounds__(64 * NW, (NW == 8 ? chain_wps(NCB) : waves_per_simd(NRB, NCB))) void mlp_fwd_kernel_p(const void* p) {
   OSRL_TRACE_BEGIN(5, p);
   mlp_fwd_body<NRB, NCB, NW, const OSRL_CAS FwdArgs&>(*(const OSRL_CAS FwdArgs*)p, blockIdx.y, blockIdx.x);
 }
@@ -599,7 +628,7 @@ struct Fwd2Args {
   int32_t nets0, tiles0, tiles1, pad_;
 };
 template <int NRB, int NCB, int NW = 4>
-__global__ __launch_bounds__(64 * NW, (NW == 8 ? (NCB <= 2 ? 4 : 2) : waves_per_simd(NRB, NCB))) void mlp_fwd2_kernel(
+__global__ __launch_bounds__(64 * NW, (NW == 8 ? chain_wps(NCB) : waves_per_simd(NRB, NCB))) void mlp_fwd2_kernel(
     const Fwd2Args f) {
   if ((int)blockIdx.y < f.nets0) {
     if ((int)blockIdx.x >= f.tiles0) return;  // whole workgroup leaves before any barrier
@@ -611,7 +640,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? (NCB <= 2 ? 4 : 2) : waves_per_
 }
 // (the twin spells the same branches out again: behind one shared template its scalar registers came out renumbered)
 template <int NRB, int NCB, int NW = 4>
-__global__ __launch_bounds__(64 * NW, (NW == 8 ? (NCB <= 2 ? 4 : 2) : waves_per_simd(NRB, NCB))) void mlp_fwd2_kernel_p(
+__global__ __launch_bounds__(64 * NW, (NW == 8 ? chain_wps(NCB) : waves_per_simd(NRB, NCB))) void mlp_fwd2_kernel_p(
     const void* p) {
   OSRL_TRACE_BEGIN(6, p);
   const OSRL_CAS Fwd2Args& f = *(const OSRL_CAS Fwd2Args*)p;
@@ -772,9 +801,10 @@ __device__ __forceinline__ void mlp_bwd_dz_body(AR a, const int e, const int til
       layer_prefetch<NRB, NCB>(ring, round16(K) >> 4, a.net.Wb[e][l], round16(N) + 16, cb0 * 16, cnt);
     } else if (a.g.dx[e]) {
       const int nblk = (a.g.dx_cols + 15) >> 4, nk = round16(a.net.dims[1]) >> 4;
-      const int Npb = round16(a.net.dims[0]) + 16;
+      // (opaque: this step's lane offsets and k split are worked out when it begins, not held across the layer loop)
+      const int Npb = fresh_s<NW == 8>(round16(a.net.dims[0]) + 16);
       if (nblk <= 2 && nk >= 4 && lda >= 16 * NW) {
-        narrow_prefetch<NCB, NW>(ring, nk, a.net.Wb[e][0], Npb, a.g.dx_col0, nblk, wave);
+        narrow_prefetch<NCB, NW>(ring, nk, a.net.Wb[e][0], Npb, a.g.dx_col0, nblk, fresh_s<NW == 8>(wave));
       } else {
         int cb0, cnt;
         wave_blocks<NW>(nblk, wave, &cb0, &cnt);
@@ -903,17 +933,18 @@ __device__ __forceinline__ void mlp_bwd_dz_body(AR a, const int e, const int til
     __syncthreads();
     BWD_STAMP(3 + 3 * (L - 1 - l));  // barrier
     // activation switch hoisted out of the element loop (see fwd_epilogue)
+    const int lane_e = fresh_v<NW == 8>(lane), lda_e = fresh_s<NW == 8>(lda);
     auto epilogue = [&](auto act_c) {
       constexpr int ACT = decltype(act_c)::value;
 #pragma unroll
       for (int c = 0; c < NCB; ++c) {
         if (c < cnt) {
-          const int col = (cb0 + c) * 16 + (lane & 15);
+          const int col = (cb0 + c) * 16 + (lane_e & 15);
 #pragma unroll
           for (int rb = 0; rb < NRB; ++rb) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              const int row = rb * 16 + (lane >> 4) * 4 + r;
+              const int row = rb * 16 + (lane_e >> 4) * 4 + r;
               const int gr = row0 + row;
               float v = 0.f;
               if (PREFETCH_H) {
@@ -921,7 +952,7 @@ __device__ __forceinline__ void mlp_bwd_dz_body(AR a, const int e, const int til
               } else if (col < N && gr < rows) {
                 v = acc[rb][c][r] * act_bwd(ACT, h[(size_t)gr * N + col]);
               }
-              lds[row * lda + col] = v;
+              lds[row * lda_e + col] = v;
             }
           }
         }
@@ -1022,11 +1053,11 @@ __device__ __forceinline__ void mlp_bwd_dz_body(AR a, const int e, const int til
   }
 }
 template <int NRB, int NCB, int NW = 4>
-__global__ __launch_bounds__(64 * NW, (NW == 8 ? (NCB <= 2 ? 4 : 2) : waves_per_simd_bwd(NRB, NCB))) void mlp_bwd_dz_kernel(const BwdArgs a) {
+__global__ __launch_bounds__(64 * NW, (NW == 8 ? chain_wps(NCB) : waves_per_simd_bwd(NRB, NCB))) void mlp_bwd_dz_kernel(const BwdArgs a) {
   mlp_bwd_dz_body<NRB, NCB, NW, const BwdArgs&>(a, blockIdx.y, blockIdx.x);
 }
 template <int NRB, int NCB, int NW = 4>
-__global__ __launch_bounds__(64 * NW, (NW == 8 ? (NCB <= 2 ? 4 : 2) : waves_per_simd_bwd(NRB, NCB))) void mlp_bwd_dz_kernel_p(const void* p) {
+__global__ __launch_bounds__(64 * NW, (NW == 8 ? chain_wps(NCB) : waves_per_simd_bwd(NRB, NCB))) void mlp_bwd_dz_kernel_p(const void* p) {
   OSRL_TRACE_BEGIN(7, p);
   mlp_bwd_dz_body<NRB, NCB, NW, const OSRL_CAS BwdArgs&>(*(const OSRL_CAS BwdArgs*)p, blockIdx.y, blockIdx.x);
 }
