@@ -293,6 +293,8 @@ typedef struct {
   int64_t n_rows;
   uint64_t gather_seed;
   uint32_t gather_stream, pad0_;
+  /* osrl_replay_gather_n's live row count (device int64; n_rows is then the tables' capacity); NULL (zero) = n_rows */
+  const int64_t* n_rows_dev;
   /* osrl_mlp_forward / osrl_mlp_backward_dz's arguments (grads.dy[0] = the loss gradient buffer, written here) */
   osrl_mlp_t net;
   osrl_rows_t in;
@@ -483,6 +485,13 @@ int osrl_step_begin_peer_w(osrl_step_state_t* st, const osrl_step_state_t* peer,
                            const float* const* src, float* const* dst, const int32_t* width, const float* scale,
                            int64_t n_rows, int32_t batch, uint64_t gather_seed, uint32_t gather_stream,
                            const uint64_t* cum, void* stream);
+/* The prologue over a store that grows (osrl_replay_gather_n; n_rows_dev == NULL: exactly osrl_step_begin_peer_w). */
+int osrl_step_begin_peer_n(osrl_step_state_t* st, const osrl_step_state_t* peer, float beta1, float beta2, int32_t warmup,
+                           const float* stats_cur, float* ring, int32_t n_stats, int32_t ring_len, float* noise,
+                           int64_t noise_n, uint64_t noise_seed, uint32_t noise_stream, int32_t n_fields,
+                           const float* const* src, float* const* dst, const int32_t* width, const float* scale,
+                           int64_t n_rows, int32_t batch, uint64_t gather_seed, uint32_t gather_stream,
+                           const uint64_t* cum, const int64_t* n_rows_dev, void* stream);
 /* g = sum_s slabs[s][i] (* *gscale if gscale != NULL); AdamW decay if weight_decay != 0;
  * then tgt = tau*p + (1-tau)*tgt if tgt != NULL.  n and slab_stride must be multiples of 4. */
 int osrl_adam_step(float* p, float* m, float* v, float* tgt, const float* slabs, int32_t n_splits,
@@ -562,6 +571,17 @@ int osrl_weights_cum_u64(const double* weights, int64_t n, uint64_t* cum, double
 int osrl_replay_gather_w(int32_t n_fields, const float* const* src, float* const* dst, const int32_t* width,
                          const float* scale, int64_t n_rows, int32_t batch, int32_t* idx_out, uint64_t seed,
                          uint32_t stream_id, const osrl_step_state_t* st, const uint64_t* cum, void* stream);
+/* A store that grows (ReplayStore(capacity=); the reference's datasets are fixed, dataset.py:790-847).  The tables (and
+ * cum) are allocated for n_rows = the capacity; n_rows_dev (device int64, one word) holds the live row count.  Every row
+ * of the batch reads the word once and draws over n = min(max(*n_rows_dev, 1), n_rows): the uniform draw is
+ * umul64hi(u, n), the weighted one the first i in [0, n) with cum[i] > the word of osrl_replay_gather_w, over the first
+ * n entries.  Whatever the word holds, the index lies inside [0, n_rows).  The kernels only read the word: the caller
+ * writes it on the stream between launches, so a captured graph that holds its address follows the store at its next
+ * replay.  n_rows_dev == NULL: exactly osrl_replay_gather_w, bit for bit. */
+int osrl_replay_gather_n(int32_t n_fields, const float* const* src, float* const* dst, const int32_t* width,
+                         const float* scale, int64_t n_rows, int32_t batch, int32_t* idx_out, uint64_t seed,
+                         uint32_t stream_id, const osrl_step_state_t* st, const uint64_t* cum,
+                         const int64_t* n_rows_dev, void* stream);
 
 /* CDT minibatch source -- SequenceDataset.__iter__/__prepare_sample (dataset.py:749-787) on device: per sample
  * draw a trajectory (inverse CDF of `cdf`, or uniform when NULL) and a start ~ U{0..len-1}, slice seq_len steps
@@ -579,6 +599,17 @@ int osrl_seq_window_gather(const float* obs, const float* act, const float* retu
                            float* o_cost_returns, int64_t* o_time_steps, float* o_mask, float* o_episode_cost,
                            float* o_costs, int32_t* idx_out, uint64_t seed, uint32_t stream_id,
                            const osrl_step_state_t* st, void* stream);
+/* The same over a store that grows: traj_start / traj_len / cdf are allocated for n_traj = the capacity, n_traj_dev
+ * (device int32, one word, only read here) holds the live trajectory count, and the uniform draw and the cdf bisection run
+ * over min(max(*n_traj_dev, 1), n_traj) trajectories.  n_traj_dev == NULL: exactly osrl_seq_window_gather. */
+int osrl_seq_window_gather_n(const float* obs, const float* act, const float* returns, const float* cost_returns,
+                             const float* costs, const int64_t* traj_start, const int32_t* traj_len, const float* cdf,
+                             const float* start_cdf, const int32_t* idx_in,
+                             int32_t n_traj, int32_t B, int32_t T, int32_t od, int32_t ad, float reward_scale,
+                             float cost_scale, float* o_states, float* o_actions, float* o_returns,
+                             float* o_cost_returns, int64_t* o_time_steps, float* o_mask, float* o_episode_cost,
+                             float* o_costs, int32_t* idx_out, uint64_t seed, uint32_t stream_id,
+                             const osrl_step_state_t* st, const int32_t* n_traj_dev, void* stream);
 
 /* ---- glue (glue.hip): the elementwise / reduction tails of the loss functions ----
  * `rows_global` (0 = rows) is the data-parallel global batch used in every 1/B normalisation.

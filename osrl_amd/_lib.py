@@ -103,7 +103,7 @@ class MlpStepT(C.Structure):  # osrl_mlp_step_t
                 ("n_stats", C.c_int32), ("ring_len", C.c_int32), ("n_fields", C.c_int32),
                 ("stats_cur", _fp), ("ring", _fp), ("src", _fp * 8), ("dst", _fp * 8), ("width", C.c_int32 * 8),
                 ("scale", C.c_float * 8), ("n_rows", C.c_int64), ("gather_seed", C.c_uint64),
-                ("gather_stream", C.c_uint32), ("pad0_", C.c_uint32),
+                ("gather_stream", C.c_uint32), ("pad0_", C.c_uint32), ("n_rows_dev", C.c_void_p),
                 ("net", MlpT), ("in_", RowsT), ("acts", ActsT), ("grads", GradsT),
                 ("target", _fp), ("n_global", C.c_int64), ("stat", _fp),
                 ("entries", C.c_void_p), ("work", C.c_void_p), ("n_work", C.c_int32), ("tile_blocks", C.c_int32),
@@ -278,6 +278,8 @@ PROTOTYPES = {
                           _P(_i32), _P(_f32), _i64, _i32, _u64, _u32, _vp, _vp],
     "osrl_step_begin_peer_w": [_vp, _vp, _f32, _f32, _i32, _fp, _fp, _i32, _i32, _fp, _i64, _u64, _u32, _i32, _P(_fp), _P(_fp),
                                _P(_i32), _P(_f32), _i64, _i32, _u64, _u32, _vp, _vp],
+    "osrl_step_begin_peer_n": [_vp, _vp, _f32, _f32, _i32, _fp, _fp, _i32, _i32, _fp, _i64, _u64, _u32, _i32, _P(_fp), _P(_fp),
+                               _P(_i32), _P(_f32), _i64, _i32, _u64, _u32, _vp, _vp, _vp],
     "osrl_step_tick_peer": [_vp, _vp, _f32, _f32, _i32, _fp, _fp, _i32, _i32, _vp],
     "osrl_step_begin_peer": [_vp, _vp, _f32, _f32, _i32, _fp, _fp, _i32, _i32, _fp, _i64, _u64, _u32, _i32, _P(_fp), _P(_fp),
                              _P(_i32), _P(_f32), _i64, _i32, _u64, _u32, _vp],
@@ -292,6 +294,9 @@ PROTOTYPES = {
     "osrl_randn_fill": [_fp, _i64, _u64, _u32, _vp, _vp],
     "osrl_replay_gather": [_i32, _P(_fp), _P(_fp), _P(_i32), _P(_f32), _i64, _i32, _vp, _u64, _u32, _vp, _vp],
     "osrl_replay_gather_w": [_i32, _P(_fp), _P(_fp), _P(_i32), _P(_f32), _i64, _i32, _vp, _u64, _u32, _vp, _vp, _vp],
+    "osrl_replay_gather_n": [_i32, _P(_fp), _P(_fp), _P(_i32), _P(_f32), _i64, _i32, _vp, _u64, _u32, _vp, _vp, _vp, _vp],
+    "osrl_seq_window_gather_n": [_fp, _fp, _fp, _fp, _fp, _vp, _vp, _fp, _fp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _fp,
+                                 _fp, _fp, _fp, _vp, _fp, _fp, _fp, _vp, _u64, _u32, _vp, _vp, _vp],
     "osrl_seq_window_gather": [_fp, _fp, _fp, _fp, _fp, _vp, _vp, _fp, _fp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _fp, _fp,
                                _fp, _fp, _vp, _fp, _fp, _fp, _vp, _u64, _u32, _vp, _vp],
     "osrl_gauss_head": [_fp, _fp, _i32, _i32, _f32, _fp, _fp, _fp, _vp],

@@ -123,13 +123,16 @@ class RolloutMixin:
         self.model.train()
         return self._scale_results(np.mean(rets), np.mean(costs), np.mean(lens))
 
-    def collect(self, noise_std=0.0, gamma: Optional[float] = None, seed: int = 0, noise=None):
+    def collect(self, noise_std=0.0, gamma: Optional[float] = None, seed: int = 0, noise=None, into=None):
         """The ``evaluate`` rollout on a ``VecSyntheticSafeEnv``, recorded: every episode of ``self.env`` runs to its end
         with ``a = clip(pi(s) + sigma_e * eps)`` and comes back as a DSRL-layout dataset on device plus the per-episode
         (discounted) returns -- a ``Collected`` (engine/collect.py).  ``noise_std``: one sigma or one per episode;
         ``gamma`` (None: 1) weighs the discounted sums; ``seed`` keys the noise drawn on device; ``noise``
         ``[episode_len, E, action_dim]`` injects it instead.  The policy, the appended cost limit of BC multi-task and
-        the cost scale are ``evaluate``'s.  Any other kind of environment: TypeError."""
+        the cost scale are ``evaluate``'s.  Any other kind of environment: TypeError.  ``into``: a ``ReplayStore`` built
+        with ``capacity`` that takes the rows directly (``store.append``: engines attached to it draw from them at their
+        next step, nothing is recaptured); the result's ``dataset`` is then None, and a store of other widths (BC
+        multi-task) is a ValueError before the run."""
         from ..common.synthetic_env import VecSyntheticSafeEnv
         if not isinstance(self.env, VecSyntheticSafeEnv):
             raise TypeError(f"collect() records the batched on-device rollout: self.env must be a VecSyntheticSafeEnv, "
@@ -138,7 +141,7 @@ class RolloutMixin:
         from ..engine.collect import collect_batched
         cs = self._cost_scale()
         return collect_batched(self, self.EVAL_KIND, 1.0 if cs is None else cs, self._eval_extra(),
-                               noise_std=noise_std, gamma=gamma, seed=seed, noise=noise)
+                               noise_std=noise_std, gamma=gamma, seed=seed, noise=noise, into=into)
 
     @torch.no_grad()
     def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):

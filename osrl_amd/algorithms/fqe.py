@@ -143,9 +143,10 @@ class FQETrainer:
         if not getattr(store, "state_init", False):
             raise ValueError("estimate() reads the dataset's initial states: build the ReplayStore with state_init=True")
         hit = self._init_idx.get(id(store))
-        if hit is None or hit[0] is not store:
-            idx = torch.nonzero(store.tables[6].reshape(-1) == 1.0).reshape(-1).to(torch.int64).contiguous()
-            hit = self._init_idx[id(store)] = (store, idx)
+        version = getattr(store, "version", 0)  # (a store that grows: every append moves it)
+        if hit is None or hit[0] is not store or hit[2] != version:
+            idx = torch.nonzero(store.live(6).reshape(-1) == 1.0).reshape(-1).to(torch.int64).contiguous()
+            hit = self._init_idx[id(store)] = (store, idx, version)
         return hit[1]
 
     @torch.no_grad()

@@ -9,6 +9,11 @@ train step.  In the data-parallel setting every rank holds its own shard of the 
 (``shard(rank, world)``) and samples locally: with random partitions this is distributionally the
 same as global uniform sampling.
 
+``capacity`` / ``append``: a store that grows in place.  The tables are allocated once for ``capacity`` rows and the live
+row count sits in one device word that the sampling kernels read (include/osrl_amd.h ``osrl_replay_gather_n``), so a
+captured train step follows ``append`` at its next replay -- nothing is re-uploaded, nothing is recaptured
+(DESIGN.md "Stores that grow").
+
 ``sample_prob`` / ``set_sample_prob``: rows are drawn with probability weight / sum instead (with replacement, the same
 Philox words as the uniform draw) through a fixed-point cdf table in HBM that the gather kernels search
 (include/osrl_amd.h ``osrl_replay_gather_w``, DESIGN.md "Weighted transition sampling").
@@ -27,30 +32,68 @@ from ..engine.core import cur_stream
 FIELDS = ("observations", "next_observations", "actions", "rewards", "costs", "done")
 
 
+def ring_spans(cursor: int, m: int, capacity: int):
+    """Where ``m`` new rows land in a ring of ``capacity`` rows whose next free slot is ``cursor``: row ``i`` of the chunk
+    goes to ``(cursor + i) % capacity``, later rows winning where a chunk longer than the ring laps itself.  Returns at
+    most two ``(dst, src, length)`` triples of contiguous copies ``ring[dst:dst + length] = chunk[src:src + length]``."""
+    cursor, m, capacity = int(cursor), int(m), int(capacity)
+    if capacity < 1 or not 0 <= cursor < capacity or m < 0:
+        raise ValueError(f"ring_spans({cursor}, {m}, {capacity})")
+    src = max(m - capacity, 0)  # (rows before this are overwritten by the chunk's own later rows)
+    n = m - src
+    if n == 0:
+        return []
+    dst = (cursor + src) % capacity
+    first = min(n, capacity - dst)
+    return [(dst, src, first)] + ([(0, src + first, n - first)] if n > first else [])
+
+
+def _done_of(d):
+    if "done" in d:
+        return d["done"]
+    if torch.is_tensor(d["terminals"]):  # device tables of common.ingest.process_bc_dataset
+        return torch.logical_or(d["terminals"] == 1, d["timeouts"] == 1)
+    return np.logical_or(np.asarray(d["terminals"]) == 1, np.asarray(d["timeouts"]) == 1)
+
+
+def _shift_done(dn) -> np.ndarray:
+    """``is_init`` of a run of transitions that starts at an episode start: ``done`` shifted by one, 1 on the first row."""
+    dn = dn.detach().cpu().numpy() if torch.is_tensor(dn) else np.asarray(dn)
+    init = np.asarray(dn, np.float32).reshape(-1).copy()
+    init[1:] = init[:-1]
+    if init.shape[0]:
+        init[0] = 1.0
+    return init
+
+
 class ReplayStore:
     def __init__(self, data: Dict[str, "np.ndarray | torch.Tensor"], device, reward_scale: float = 1.0,
                  cost_scale: float = 1.0, seed: int = 0, rank: int = 0, world: int = 1, state_init: bool = False,
-                 sample_prob=None):
+                 capacity: Optional[int] = None, sample_prob=None):
         """``data`` uses the DSRL dataset keys (observations, next_observations, actions, rewards, costs,
         and either ``done`` or ``terminals``+``timeouts``).  ``state_init`` (TransitionDataset(state_init=True),
         dataset.py:817-820, used by COptiDICE): a 7th table ``is_init`` = ``done`` shifted by one transition with
         ``is_init[0] = 1``, computed on the FULL dataset before any sharding.  ``sample_prob``: per-transition sampling
-        weights of the FULL dataset (``set_sample_prob``); None = uniform."""
+        weights of the FULL dataset (``set_sample_prob``); None = uniform.
+        ``capacity`` (None: a fixed store, exactly as before): allocate the tables for that many rows (>= ``len(data)``,
+        zero past the data) so that ``append`` can add transitions in place; single rank only (ValueError with
+        ``world > 1``).  ``n_rows`` is then the LIVE row count, ``capacity`` the allocation; the launches carry the
+        capacity and the address of the device word that holds the live count.  With ``state_init``,
+        ``init_state_propotion`` and the two ``*_std`` are those of the construction-time data and are not updated by
+        ``append``."""
         d = dict(data)
         self.state_init = bool(state_init)
-        if "done" not in d:
-            if torch.is_tensor(d["terminals"]):  # device tables of common.ingest.process_bc_dataset
-                d["done"] = torch.logical_or(d["terminals"] == 1, d["timeouts"] == 1)
-            else:
-                d["done"] = np.logical_or(np.asarray(d["terminals"]) == 1, np.asarray(d["timeouts"]) == 1)
+        d["done"] = _done_of(d)
         n = len(d["observations"])
+        if capacity is not None:
+            capacity = int(capacity)
+            if world > 1:
+                raise ValueError("capacity= with world > 1: a sharded store does not grow (build one store per rank)")
+            if capacity < max(n, 1):
+                raise ValueError(f"capacity {capacity} is below the {n} rows of the data")
         fields = FIELDS
         if self.state_init:
-            dn = d["done"]
-            dn = dn.detach().cpu().numpy() if torch.is_tensor(dn) else np.asarray(dn)
-            init = np.asarray(dn, np.float32).reshape(-1).copy()
-            init[1:] = init[:-1]
-            init[0] = 1.0
+            init = _shift_done(d["done"])
             d["is_init"] = init
             fields = FIELDS + ("is_init",)
             # TransitionDataset.get_dataset_states (dataset.py:822-830): what COptiDICE's constructor is fed
@@ -64,8 +107,16 @@ class ReplayStore:
         for k in fields:
             t = torch.as_tensor(np.asarray(d[k])[sl] if not torch.is_tensor(d[k]) else d[k][sl])
             t = t.to(device=device, dtype=torch.float32).reshape(t.shape[0], -1).contiguous()
+            if capacity is not None:  # one allocation for the store's life: captured graphs hold these addresses
+                full = torch.zeros(capacity, t.shape[1], dtype=torch.float32, device=device)
+                full[:n].copy_(t)
+                t = full
             self.tables.append(t)
-        self.n_rows = self.tables[0].shape[0]
+        self.n_rows = n if capacity is not None else self.tables[0].shape[0]
+        self.capacity = capacity
+        self.version = 0  # incremented by every append (caches keyed on the store's contents compare it)
+        self._cursor = 0 if capacity is None else n % capacity  # the ring's next slot
+        self._live = None if capacity is None else torch.full((1,), n, dtype=torch.int64, device=device)
         self.widths = [t.shape[1] for t in self.tables]
         self.scales = [1.0, 1.0, 1.0, float(reward_scale), float(cost_scale), 1.0] + ([1.0] if self.state_init else [])
         self.seed = int(seed) * 1000003 + rank
@@ -88,8 +139,21 @@ class ReplayStore:
 
     @property
     def cum(self) -> Optional[torch.Tensor]:
-        """The sampler's table -- int64 storage of the uint64 fixed-point cdf, [n_rows] -- or None while uniform."""
+        """The sampler's table -- int64 storage of the uint64 fixed-point cdf, [n_rows] ([capacity] on a store that
+        grows, valid over the live rows) -- or None while uniform."""
         return self._cum_buf if self.weighted else None
+
+    @property
+    def _alloc_rows(self) -> int:
+        """The row count the launches carry: the allocation (the draw itself runs over the live word, if there is one)."""
+        return self.n_rows if self.capacity is None else self.capacity
+
+    def _live_ptr(self) -> Optional[int]:
+        return None if self._live is None else self._live.data_ptr()
+
+    def live(self, i: int) -> torch.Tensor:
+        """Table ``i`` sliced to the live rows (the whole table on a fixed store)."""
+        return self.tables[i][:self.n_rows]
 
     def _cum_ptr(self) -> Optional[int]:
         return self._cum_buf.data_ptr() if self.weighted else None
@@ -103,7 +167,8 @@ class ReplayStore:
         partitions, for masses instead of row counts).
         The table is rewritten in place on the current stream: a captured step draws from the new weights at its next
         replay, nothing is recaptured.  Switching between uniform and weighted changes the launches' arguments instead;
-        the engines notice (``sample_epoch``) and rebuild their graphs / descriptors before the next step."""
+        the engines notice (``sample_epoch``) and rebuild their graphs / descriptors before the next step.
+        A store built with ``capacity``: one weight per LIVE row, in physical (table) order."""
         if weights is None:
             if self.weighted:
                 self.weighted = False
@@ -128,17 +193,100 @@ class ReplayStore:
             raise ValueError("the weights must be non-negative and finite, with a positive sum"
                              + (" on this rank's shard" if self._shard != slice(None) else ""))
         lib = L.load()
-        if self._cum_buf is None:
-            self._cum_buf = torch.zeros(self.n_rows, dtype=torch.int64, device=self.device)
-            self._cum_ws = torch.zeros(int(lib.osrl_weights_cum_u64_ws_elems(self.n_rows)), dtype=torch.float64,
-                                       device=self.device)
-            self._w64 = torch.zeros(self.n_rows, dtype=torch.float64, device=self.device)
-        self._w64.copy_(w if torch.is_tensor(w) else torch.from_numpy(w))
-        L.check(lib.osrl_weights_cum_u64(self._w64.data_ptr(), self.n_rows, self._cum_buf.data_ptr(),
-                                         self._cum_ws.data_ptr(), cur_stream()), "osrl_weights_cum_u64")
+        self._alloc_weights()
+        self._w64[:self.n_rows].copy_(w if torch.is_tensor(w) else torch.from_numpy(w))
+        self._build_cum()
         if not self.weighted:
             self.weighted = True
             self.sample_epoch += 1
+
+    def _alloc_weights(self) -> None:
+        if self._cum_buf is None:
+            cap = self._alloc_rows
+            self._cum_buf = torch.zeros(cap, dtype=torch.int64, device=self.device)
+            self._cum_ws = torch.zeros(int(L.load().osrl_weights_cum_u64_ws_elems(cap)), dtype=torch.float64,
+                                       device=self.device)
+            self._w64 = torch.zeros(cap, dtype=torch.float64, device=self.device)
+
+    def _build_cum(self) -> None:
+        """The table over the live rows, in place (one osrl_weights_cum_u64 call on the current stream)."""
+        L.check(L.load().osrl_weights_cum_u64(self._w64.data_ptr(), self.n_rows, self._cum_buf.data_ptr(),
+                                              self._cum_ws.data_ptr(), cur_stream()), "osrl_weights_cum_u64")
+
+    # ---- growth -------------------------------------------------------------------------------------------------------
+    def check_append_widths(self, **widths: int) -> None:
+        """ValueError unless a chunk with these column counts (``observations=17, actions=6, ...``) fits the tables."""
+        names = FIELDS + ("is_init",)
+        for k, w in widths.items():
+            i = names.index(k)
+            if i < self.n_fields and int(w) != self.widths[i]:
+                raise ValueError(f"the store's {k} have {self.widths[i]} columns, the new rows {int(w)}")
+
+    def append(self, data: Dict[str, "np.ndarray | torch.Tensor"], sample_prob=None) -> None:
+        """Add the transitions of ``data`` (the DSRL keys, as the constructor takes them: numpy or tensors, host or
+        device) to a store built with ``capacity``.  Values are stored raw (the scales stay in the gather).  Row ``i`` of
+        the chunk lands at ``(cursor + i) % capacity``: a full store overwrites its oldest rows, the live count
+        saturates at the capacity.  At most two contiguous copies per table (``ring_spans``) and one write of the live
+        word, all on the current stream: a captured step that draws from this store sees the new rows at its next
+        replay, and nothing is recaptured.  ``version`` is incremented.
+        ``state_init`` stores: the chunk's ``is_init`` is its ``done`` shifted by one row with 1 on its first row, so a
+        chunk must START at an episode start (a chunk that continues the previous one's last episode would mark a
+        spurious initial state); ``init_state_propotion`` / ``observations_std`` / ``actions_std`` stay as constructed.
+        Weighted stores need ``sample_prob``: the new rows' weights (they join the others in physical row order and the
+        table is rebuilt over the live rows); ValueError without it, and on a uniform store with it.  Widths and keys
+        are checked before any device work (ValueError)."""
+        if self.capacity is None:
+            raise ValueError("this store is fixed: build it with capacity= to append")
+        d = dict(data)
+        missing = [k for k in FIELDS[:5] if k not in d] + \
+            ([] if "done" in d or ("terminals" in d and "timeouts" in d) else ["done (or terminals + timeouts)"])
+        if missing:
+            raise ValueError(f"append: missing {', '.join(missing)}")
+        shape = lambda x: tuple(x.shape) if torch.is_tensor(x) else np.shape(x)  # noqa: E731
+        m = int(shape(d["observations"])[0])
+        lead = ("done",) if "done" in d else ("terminals", "timeouts")
+        for k in FIELDS[:5] + lead:
+            sh = shape(d[k])
+            if len(sh) < 1 or int(sh[0]) != m:
+                raise ValueError(f"append: {k} holds {sh[0] if sh else 0} rows, observations {m}")
+            w = int(np.prod(sh[1:], dtype=np.int64))
+            want = self.widths[FIELDS.index(k)] if k in FIELDS else 1
+            if w != want:
+                raise ValueError(f"the store's {k} have {want} columns, the new rows {w}")
+        if self.weighted and sample_prob is None:
+            raise ValueError("the store draws by weight: append(data, sample_prob=) needs the new rows' weights")
+        if not self.weighted and sample_prob is not None:
+            raise ValueError("the store draws uniformly: call set_sample_prob() over the live rows instead")
+        w_new = None
+        if sample_prob is not None:
+            w_new = sample_prob if torch.is_tensor(sample_prob) else torch.from_numpy(
+                np.ascontiguousarray(np.asarray(sample_prob, np.float64).reshape(-1)))
+            w_new = w_new.reshape(-1)
+            if int(w_new.shape[0]) != m:
+                raise ValueError(f"{m} transition weights expected, got {int(w_new.shape[0])}")
+            if m and not (bool(torch.isfinite(w_new).all()) and float(w_new.min()) >= 0.0):
+                raise ValueError("the weights must be non-negative and finite")
+        if m == 0:
+            return
+        d["done"] = _done_of(d)
+        if self.state_init:
+            d["is_init"] = _shift_done(d["done"])
+        spans = ring_spans(self._cursor, m, self.capacity)
+        names = FIELDS + (("is_init",) if self.state_init else ())
+        for k, table in zip(names, self.tables):
+            x = d[k] if torch.is_tensor(d[k]) else torch.from_numpy(np.ascontiguousarray(np.asarray(d[k])))
+            x = x.reshape(m, -1)
+            for dst, src, n in spans:
+                table[dst:dst + n].copy_(x[src:src + n], non_blocking=True)  # (casts to fp32, host or device source)
+        if w_new is not None:
+            for dst, src, n in spans:
+                self._w64[dst:dst + n].copy_(w_new[src:src + n], non_blocking=True)
+        self._cursor = (self._cursor + m) % self.capacity
+        self.n_rows = self.n_total = min(self.n_rows + m, self.capacity)
+        self._live.fill_(self.n_rows)
+        self.version += 1
+        if w_new is not None:
+            self._build_cum()
 
     def get_dataset_states(self):
         """(init_state_propotion, observations_std, actions_std) -- dataset.py:822-830; needs ``state_init``."""
@@ -153,14 +301,24 @@ class ReplayStore:
         if len(dst) != self.n_fields:
             raise ValueError(f"the store holds {self.n_fields} tables, {len(dst)} destination buffers were given")
         d = (C.c_void_p * self.n_fields)(*[t.data_ptr() for t in dst])
-        L.check(L.load().osrl_replay_gather_w(self.n_fields, self._src, d, self._w, self._s, self.n_rows, B,
-                                              None if idx_out is None else idx_out.data_ptr(), self.seed, stream_id,
-                                              st_ptr, self._cum_ptr(), cur_stream()), "osrl_replay_gather")
+        self._gather(self.n_fields, self._src, d, self._w, self._s, B, None if idx_out is None else idx_out.data_ptr(),
+                     stream_id, st_ptr)
+
+    def _gather(self, n, src, d, w, sc, B, idx_ptr, stream_id, st_ptr) -> None:
+        lib = L.load()
+        if self._live is None:  # a fixed store: the entry point and the arguments it always had
+            rc = lib.osrl_replay_gather_w(n, src, d, w, sc, self.n_rows, B, idx_ptr, self.seed, stream_id, st_ptr,
+                                          self._cum_ptr(), cur_stream())
+        else:
+            rc = lib.osrl_replay_gather_n(n, src, d, w, sc, self.capacity, B, idx_ptr, self.seed, stream_id, st_ptr,
+                                          self._cum_ptr(), self._live.data_ptr(), cur_stream())
+        L.check(rc, "osrl_replay_gather")
 
     def gather_args(self, dst: Sequence[torch.Tensor], fields: Optional[Sequence[int]] = None, stream_id: int = 1):
         """The arguments of ``gather`` / ``gather_fields`` as the tuple ``StepState.begin(gather=...)`` takes (the
         fused step prologue draws the same rows: the indices are a function of (seed, step, row) and the weight table
-        only); the last element is the table's address, None while uniform."""
+        only); the last two elements are the weight table's address, None while uniform, and the live-count word's, None
+        on a fixed store (the row count is then the store's capacity)."""
         if fields is None:
             fields = range(self.n_fields)
         fields = list(fields)
@@ -171,7 +329,8 @@ class ReplayStore:
         d = (C.c_void_p * n)(*[t.data_ptr() for t in dst])
         w = (C.c_int32 * n)(*[self.widths[i] for i in fields])
         sc = (C.c_float * n)(*[self.scales[i] for i in fields])
-        return (n, src, d, w, sc, self.n_rows, dst[0].shape[0], self.seed, stream_id, list(dst), self._cum_ptr())
+        return (n, src, d, w, sc, self._alloc_rows, dst[0].shape[0], self.seed, stream_id, list(dst), self._cum_ptr(),
+                self._live_ptr())
 
     def gather_fields(self, fields: Sequence[int], dst: Sequence[torch.Tensor], st_ptr: Optional[int],
                       stream_id: int = 1) -> None:
@@ -182,8 +341,7 @@ class ReplayStore:
         d = (C.c_void_p * n)(*[t.data_ptr() for t in dst])
         w = (C.c_int32 * n)(*[self.widths[i] for i in fields])
         sc = (C.c_float * n)(*[self.scales[i] for i in fields])
-        L.check(L.load().osrl_replay_gather_w(n, src, d, w, sc, self.n_rows, B, None, self.seed, stream_id, st_ptr,
-                                              self._cum_ptr(), cur_stream()), "osrl_replay_gather")
+        self._gather(n, src, d, w, sc, B, None, stream_id, st_ptr)
 
 def synthetic_transitions(n: int, od: int, ad: int, seed: int = 1, max_action: float = 1.0) -> Dict[str, np.ndarray]:
     """Synthetic DSRL-shaped data: obs~N(0,1), act~U(-1,1), rew~N(0,1), cost~Bern(.1),
@@ -201,7 +359,25 @@ class SequenceStore:
     (osrl/common/dataset.py:633-787; ``from_dataset`` covers its augmentation paths) + DataLoader.
     ``trajectories``: list of dicts with observations [L,od], actions [L,ad], returns [L] (return-to-go),
     cost_returns [L] (cost-to-go), costs [L].  ``sample_prob``: optional per-trajectory probabilities
-    (dataset.py:439-459 ``compute_cost_sample_prob`` output); None = uniform."""
+    (dataset.py:439-459 ``compute_cost_sample_prob`` output); None = uniform.
+
+    A store that grows (``from_dataset`` / ``from_tables`` with ``capacity_rows`` / ``capacity_traj``): the row tables,
+    ``traj_start`` / ``traj_len``, ``cdf`` and ``start_cdf`` are allocated once at their capacities and rewritten in
+    place, the live trajectory count sits in one device word the window sampler reads (include/osrl_amd.h
+    ``osrl_seq_window_gather_n``), and ``append`` adds whole trajectories after the live ones -- a captured CDT step
+    follows at its next replay.  (Switching an attached store between a uniform and a non-uniform distribution, or start
+    sampling on and off, changes the launch's arguments as it always did: re-attach the store.)"""
+
+    # a fixed store (the constructor, from_tables without capacities): no live word, nothing remembered
+    _live: Optional[torch.Tensor] = None
+    capacity_rows: Optional[int] = None
+    capacity_traj: Optional[int] = None
+    _dist: Optional[tuple] = None        # how the trajectory distribution was made: ("cost", transform) | ("pf", beta,
+    _start_prob: Optional[float] = None  # frontier) | ("weights",) | ("cdf",); the ``prob`` of start sampling
+    _traj_w: Optional[torch.Tensor] = None
+    cost_reverse = False
+    n_appended = 0
+    version = 0
 
     def __init__(self, trajectories, seq_len: int, device, reward_scale: float = 1.0, cost_scale: float = 1.0,
                  sample_prob=None, seed: int = 0, rank: int = 0, start_sampling: bool = False, prob: float = 0.4):
@@ -214,11 +390,13 @@ class SequenceStore:
         self.traj_len = torch.as_tensor(lens.astype(np.int32), device=self.device)
         self.traj_start = torch.as_tensor(np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64), device=self.device)
         self.n_traj = len(trajectories)
+        self.n_rows = int(lens.sum())
         self.cdf = None
         if sample_prob is not None:
             c = np.cumsum(np.asarray(sample_prob, np.float64))
             c /= c[-1]
             self.cdf = torch.as_tensor(c.astype(np.float32), device=self.device)
+            self._dist = ("cdf",)
         self.reward_scale, self.cost_scale = float(reward_scale), float(cost_scale)
         self.base_seed = int(seed)
         self.set_rank(rank)
@@ -231,8 +409,28 @@ class SequenceStore:
         """``SequenceDataset(start_sampling=True, prob=...)`` (dataset.py:742-744,781-783): window starts are drawn
         from ``compute_start_index_sample_prob`` instead of uniformly (computed on device, csrc/ingest.hip)."""
         from .ingest import compute_start_index_sample_prob
-        tables = dict(costs=self.cost, traj_start=self.traj_start, traj_len=self.traj_len)
-        self.start_cdf = compute_start_index_sample_prob(tables, prob, with_cdf=True)[1]
+        t = self._live_tables()
+        tables = dict(costs=t["costs"], traj_start=t["traj_start"], traj_len=t["traj_len"])
+        self._start_prob = float(prob)
+        self._set_table("start_cdf", compute_start_index_sample_prob(tables, prob, with_cdf=True)[1], self.capacity_rows)
+
+    def _live_tables(self) -> Dict[str, torch.Tensor]:
+        """The tables sliced to the live rows / trajectories (the tables themselves on a fixed store)."""
+        r, n = self.n_rows, self.n_traj
+        return dict(observations=self.obs[:r], actions=self.act[:r], returns=self.ret[:r], cost_returns=self.cret[:r],
+                    costs=self.cost[:r], traj_start=self.traj_start[:n], traj_len=self.traj_len[:n])
+
+    def _set_table(self, name: str, new: torch.Tensor, cap: Optional[int]) -> None:
+        """``cdf`` / ``start_cdf``: a fresh tensor on a fixed store; on a store that grows one buffer at capacity,
+        allocated at the first use and then rewritten in place (captured graphs hold its address)."""
+        if self._live is None:
+            setattr(self, name, new)
+            return
+        buf = getattr(self, name)
+        if buf is None:
+            buf = torch.zeros(cap, dtype=torch.float32, device=self.device)
+            setattr(self, name, buf)
+        buf[:new.shape[0]].copy_(new)
 
     def set_sample_prob(self, weights) -> None:
         """Sample trajectories in proportion to ``weights``: any non-negative per-trajectory values (numpy or
@@ -247,7 +445,12 @@ class SequenceStore:
         lo, total = float(w.min()), float(w.sum())  # host reads, once per distribution
         if not (lo >= 0.0 and 0.0 < total < float("inf")):
             raise ValueError("the weights must be non-negative and finite, with a positive sum")
-        self.cdf = sample_prob_from_weights(w, with_cdf=True)[1]
+        self._dist = ("weights",)
+        if self._live is not None:  # kept, so that append(weights=) can extend them
+            if self._traj_w is None:
+                self._traj_w = torch.zeros(self.capacity_traj, dtype=torch.float64, device=self.device)
+            self._traj_w[:self.n_traj].copy_(w)
+        self._set_table("cdf", sample_prob_from_weights(w, with_cdf=True)[1], self.capacity_traj)
 
     def enable_pf_sampling(self, beta: float = 1.0, frontier=None) -> None:
         """``SequenceDataset(pf_sample=True)`` (dataset.py:736-737): trajectories are drawn with probability
@@ -264,8 +467,10 @@ class SequenceStore:
             frontier = None if info is None else info["frontier"]
         if frontier is None:
             raise AttributeError("no Pareto frontier: the store was built without augment_percent (pass frontier=)")
-        tables = dict(returns=self.ret, cost_returns=self.cret, traj_start=self.traj_start)
-        self.cdf = compute_sample_prob(tables, frontier, beta, with_cdf=True)[1]
+        t = self._live_tables()
+        tables = dict(returns=t["returns"], cost_returns=t["cost_returns"], traj_start=t["traj_start"])
+        self._dist = ("pf", float(beta), frontier)
+        self._set_table("cdf", compute_sample_prob(tables, frontier, beta, with_cdf=True)[1], self.capacity_traj)
 
     def set_rank(self, rank: int) -> None:
         """Data parallel: every rank draws its own windows (same mixing as ReplayStore); the CDT engine calls this
@@ -276,15 +481,38 @@ class SequenceStore:
     @classmethod
     def from_tables(cls, tables: Dict[str, torch.Tensor], seq_len: int, reward_scale: float = 1.0,
                     cost_scale: float = 1.0, cdf: Optional[torch.Tensor] = None, seed: int = 0,
-                    rank: int = 0, start_sampling: bool = False, prob: float = 0.4) -> "SequenceStore":
-        """Wrap the flat device tables of ``common.ingest.process_sequence_dataset`` (nothing is copied)."""
+                    rank: int = 0, start_sampling: bool = False, prob: float = 0.4,
+                    capacity_rows: Optional[int] = None, capacity_traj: Optional[int] = None) -> "SequenceStore":
+        """Wrap the flat device tables of ``common.ingest.process_sequence_dataset`` (nothing is copied).
+        ``capacity_rows`` / ``capacity_traj`` (either one; the other defaults to the tables' size): a store that grows --
+        the tables are COPIED into allocations of those sizes, zero past the data, and ``append`` adds trajectories."""
         self = cls.__new__(cls)
         self.T, self.device = int(seq_len), tables["observations"].device
         self.obs, self.act = tables["observations"].contiguous(), tables["actions"].contiguous()
         self.ret, self.cret, self.cost = tables["returns"], tables["cost_returns"], tables["costs"]
         self.traj_start, self.traj_len = tables["traj_start"], tables["traj_len"]
         self.n_traj = int(self.traj_start.shape[0])
+        self.n_rows = int(self.obs.shape[0])
+        if capacity_rows is not None or capacity_traj is not None:
+            cr = self.n_rows if capacity_rows is None else int(capacity_rows)
+            ct = self.n_traj if capacity_traj is None else int(capacity_traj)
+            if cr < max(self.n_rows, 1) or ct < max(self.n_traj, 1):
+                raise ValueError(f"capacities ({cr} rows, {ct} trajectories) below the data ({self.n_rows}, {self.n_traj})")
+            self.capacity_rows, self.capacity_traj = cr, ct
+
+            def grown(t, cap):
+                full = torch.zeros((cap,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device)
+                full[:t.shape[0]].copy_(t)
+                return full
+            self.obs, self.act = grown(self.obs, cr), grown(self.act, cr)
+            self.ret, self.cret, self.cost = grown(self.ret, cr), grown(self.cret, cr), grown(self.cost, cr)
+            self.traj_start, self.traj_len = grown(self.traj_start, ct), grown(self.traj_len, ct)
+            self._live = torch.full((1,), self.n_traj, dtype=torch.int32, device=self.device)
+            if cdf is not None:
+                cdf = grown(cdf.to(torch.float32), ct)
         self.cdf = cdf
+        if cdf is not None:
+            self._dist = ("cdf",)
         self.reward_scale, self.cost_scale = float(reward_scale), float(cost_scale)
         self.base_seed = int(seed)
         self.set_rank(rank)
@@ -303,7 +531,8 @@ class SequenceStore:
                      max_reward: float = 1000.0, min_reward: float = 5, pf_only: bool = False, rmin: float = 0,
                      cost_bins: int = 60, npb: int = 5, random_aug: float = 0, aug_rmin: float = 0,
                      aug_rmax: float = 600, aug_cmin: float = 5, aug_cmax: float = 50, cgap: float = 5,
-                     rstd: float = 1, cstd: float = 0.2, draws: Optional[dict] = None) -> "SequenceStore":
+                     rstd: float = 1, cstd: float = 0.2, draws: Optional[dict] = None,
+                     capacity_rows: Optional[int] = None, capacity_traj: Optional[int] = None) -> "SequenceStore":
         """``SequenceDataset(dataset, seq_len, reward_scale, cost_scale, ...)`` (dataset.py:633-747) with the whole
         preprocessing on device.  The constructor's branches run in the reference's order: ``pf_only`` (which only
         suppresses the augmentations: the reference discards select_optimal_trajectory's result), else
@@ -315,7 +544,9 @@ class SequenceStore:
         of ``common.ingest.compute_cost_sample_prob`` (all on device) or a python callable as in the reference
         (applied on the host to the per-trajectory cost returns).  ``pf_sample=True`` raises: the frontier-distance
         distribution is installed afterwards with ``enable_pf_sampling()`` (in the reference ``cost_sample`` wins
-        over ``pf_sample``, and its beta is hard-wired to 1, dataset.py:734-737)."""
+        over ``pf_sample``, and its beta is hard-wired to 1, dataset.py:734-737).
+        ``capacity_rows`` / ``capacity_traj``: a store that grows (``append``); the capacities count the augmented
+        trajectories too."""
         from .ingest import augmentation, compute_cost_sample_prob, process_sequence_dataset, random_augmentation
         if pf_sample:
             raise NotImplementedError("pf_sample=True is not built by from_dataset: build the store without it and "
@@ -332,7 +563,10 @@ class SequenceStore:
             tables, info = augmentation(tables, deg, max_rew_decrease, beta, augment_percent, max_reward, min_reward,
                                         seed=seed, draws=draws)
         cdf = compute_cost_sample_prob(tables, cost_transform, with_cdf=True)[1] if cost_sample else None
-        self = cls.from_tables(tables, seq_len, reward_scale, cost_scale, cdf, seed, rank, start_sampling, prob)
+        self = cls.from_tables(tables, seq_len, reward_scale, cost_scale, cdf, seed, rank, start_sampling, prob,
+                               capacity_rows, capacity_traj)
+        self.cost_reverse = bool(cost_reverse)
+        self._dist = ("cost", cost_transform) if cost_sample else None
         self.n_original = n_orig
         self.n_augmented = 0 if info is None else int(info["n_augmented"])
         self.aug_info = info
@@ -365,11 +599,82 @@ class SequenceStore:
                idx_out=None, stream_id: int = 2, idx_in=None) -> None:
         """``idx_in``: optional int32 [B,2] device tensor of (trajectory, start) pairs to use instead of drawing."""
         B = states.shape[0]
-        L.check(L.load().osrl_seq_window_gather(
-            self.obs.data_ptr(), self.act.data_ptr(), self.ret.data_ptr(), self.cret.data_ptr(), self.cost.data_ptr(),
-            self.traj_start.data_ptr(), self.traj_len.data_ptr(), None if self.cdf is None else self.cdf.data_ptr(),
-            None if self.start_cdf is None else self.start_cdf.data_ptr(),
-            None if idx_in is None else idx_in.data_ptr(), self.n_traj, B, self.T, self.od, self.ad, self.reward_scale, self.cost_scale, states.data_ptr(),
-            actions.data_ptr(), returns.data_ptr(), cost_returns.data_ptr(), time_steps.data_ptr(), mask.data_ptr(),
-            episode_cost.data_ptr(), costs.data_ptr(), None if idx_out is None else idx_out.data_ptr(), self.seed,
-            stream_id, st_ptr, cur_stream()), "osrl_seq_window_gather")
+        lib = L.load()
+        args = (self.obs.data_ptr(), self.act.data_ptr(), self.ret.data_ptr(), self.cret.data_ptr(), self.cost.data_ptr(),
+                self.traj_start.data_ptr(), self.traj_len.data_ptr(), None if self.cdf is None else self.cdf.data_ptr(),
+                None if self.start_cdf is None else self.start_cdf.data_ptr(),
+                None if idx_in is None else idx_in.data_ptr(), self.n_traj if self._live is None else self.capacity_traj,
+                B, self.T, self.od, self.ad, self.reward_scale, self.cost_scale, states.data_ptr(),
+                actions.data_ptr(), returns.data_ptr(), cost_returns.data_ptr(), time_steps.data_ptr(), mask.data_ptr(),
+                episode_cost.data_ptr(), costs.data_ptr(), None if idx_out is None else idx_out.data_ptr(), self.seed,
+                stream_id, st_ptr)
+        L.check(lib.osrl_seq_window_gather(*args, cur_stream()) if self._live is None else
+                lib.osrl_seq_window_gather_n(*args, self._live.data_ptr(), cur_stream()), "osrl_seq_window_gather")
+
+    def append(self, dataset, weights=None) -> None:
+        """Add the complete episodes of ``dataset`` (DSRL keys, host or device) to a store built with capacities: the
+        chunk goes through ``process_sequence_dataset`` as a dataset of its own (with the store's ``cost_reverse``) and
+        its trajectories are appended after the live ones, in place, on the current stream.  There is no ring: a chunk
+        that does not fit raises ValueError and changes nothing.  New chunks are not augmented (``n_original`` /
+        ``n_augmented`` describe the construction-time data, ``n_appended`` counts the rest).
+        The trajectory distribution follows the data: ``cost_sample`` (its transform), ``enable_pf_sampling`` (its beta
+        and frontier) and start sampling (its ``prob``) are recomputed over the live trajectories into the same buffers.
+        After ``set_sample_prob`` the new trajectories need ``weights=`` (ValueError without); a store whose distribution
+        was given as a ready-made cdf cannot extend it (ValueError: call ``set_sample_prob`` first)."""
+        from .ingest import (compute_cost_sample_prob, compute_sample_prob, compute_start_index_sample_prob,
+                             process_sequence_dataset, sample_prob_from_weights)
+        if self._live is None:
+            raise ValueError("this store is fixed: build it with capacity_rows= / capacity_traj= to append")
+        shape = lambda x: tuple(x.shape) if torch.is_tensor(x) else np.shape(x)  # noqa: E731
+        for k, want in (("observations", self.od), ("actions", self.ad)):
+            sh = shape(dataset[k])
+            if int(np.prod(sh[1:], dtype=np.int64)) != want:
+                raise ValueError(f"the store's {k} have {want} columns, the new rows {int(np.prod(sh[1:]))}")
+        kind = None if self._dist is None else self._dist[0]
+        if kind == "cdf":
+            raise ValueError("the trajectory distribution was given as a cdf: call set_sample_prob(weights) before append")
+        if kind == "weights" and weights is None:
+            raise ValueError("the store draws by set_sample_prob's weights: append(dataset, weights=) needs the new "
+                             "trajectories' weights")
+        if kind != "weights" and weights is not None:
+            raise ValueError("weights= extends the weights of set_sample_prob, which this store does not draw by")
+        t = process_sequence_dataset(dataset, self.cost_reverse, self.device)
+        mt, mr = int(t["traj_start"].shape[0]), int(t["observations"].shape[0])
+        if self.n_traj + mt > self.capacity_traj or self.n_rows + mr > self.capacity_rows:
+            raise ValueError(f"the chunk ({mr} rows, {mt} trajectories) does not fit: {self.n_rows} of "
+                             f"{self.capacity_rows} rows and {self.n_traj} of {self.capacity_traj} trajectories are live")
+        w_new = None
+        if weights is not None:
+            w_new = (weights if torch.is_tensor(weights) else torch.as_tensor(np.asarray(weights, np.float64)))
+            w_new = w_new.reshape(-1).to(device=self.device, dtype=torch.float64)
+            if int(w_new.shape[0]) != mt:
+                raise ValueError(f"{mt} trajectory weights expected, got {int(w_new.shape[0])}")
+            if mt and not (bool(torch.isfinite(w_new).all()) and float(w_new.min()) >= 0.0):
+                raise ValueError("the weights must be non-negative and finite")
+        if mt == 0:
+            return
+        r0, n0 = self.n_rows, self.n_traj
+        self.obs[r0:r0 + mr].copy_(t["observations"].reshape(mr, -1))
+        self.act[r0:r0 + mr].copy_(t["actions"].reshape(mr, -1))
+        self.ret[r0:r0 + mr].copy_(t["returns"])
+        self.cret[r0:r0 + mr].copy_(t["cost_returns"])
+        self.cost[r0:r0 + mr].copy_(t["costs"])
+        self.traj_start[n0:n0 + mt].copy_(t["traj_start"] + r0)
+        self.traj_len[n0:n0 + mt].copy_(t["traj_len"])
+        self.n_rows, self.n_traj = r0 + mr, n0 + mt
+        self.n_appended += mt
+        self.version += 1
+        lt = self._live_tables()
+        if kind == "cost":
+            self._set_table("cdf", compute_cost_sample_prob(lt, self._dist[1], with_cdf=True)[1], self.capacity_traj)
+        elif kind == "pf":
+            self._set_table("cdf", compute_sample_prob(lt, self._dist[2], self._dist[1], with_cdf=True)[1],
+                            self.capacity_traj)
+        elif kind == "weights":
+            self._traj_w[n0:n0 + mt].copy_(w_new)
+            self._set_table("cdf", sample_prob_from_weights(self._traj_w[:self.n_traj], with_cdf=True)[1],
+                            self.capacity_traj)
+        if self._start_prob is not None:
+            self._set_table("start_cdf", compute_start_index_sample_prob(lt, self._start_prob, with_cdf=True)[1],
+                            self.capacity_rows)
+        self._live.fill_(self.n_traj)  # last: the tables and the distributions are in place when the count moves

@@ -23,7 +23,21 @@ struct GatherArgs {
   uint32_t k0, k1, stream_id;
   const osrl_step_state_t* st;
   const uint64_t* cum;  // [n_rows] fixed-point inclusive cdf of the sampling weights (include/osrl_amd.h), or NULL = uniform
+  // a store that grows (ReplayStore(capacity=)): the device word that holds the live row count -- n_rows is then the
+  // tables' capacity and the draw runs over clamp(*n_rows_dev, 1, n_rows); NULL = the draw over n_rows, as always
+  const int64_t* n_rows_dev;
 };
+
+// The row count the draw runs over.  Whatever the word holds, the result is inside [1, n_rows]: every index stays inside
+// the allocation.  One load ahead of the index (the address is uniform; the word only changes between launches).
+template <class AR>
+__device__ __forceinline__ int64_t live_rows(AR a) {
+  const int64_t cap = a.n_rows;
+  const int64_t* __restrict__ p = a.n_rows_dev;
+  if (!p) return cap;
+  const int64_t v = *p;
+  return v < 1 ? 1 : v < cap ? v : cap;
+}
 
 // The weighted draw: the first i in [0, n) with cum[i] > min(u, 2^64 - 2), found by the L lanes that hold the row (lane id l;
 // every one of them returns the index).  cum is non-decreasing, so that index is the number of entries <= the word.  A
@@ -104,7 +118,8 @@ __device__ __forceinline__ void gather_body(AR a, uint32_t step, int block) {
   // 64-bit multiply-shift maps a 64-bit uniform onto [0, n_rows) (bias < 2^-40 for n_rows < 2^24)
   const uint64_t u = ((uint64_t)r.x << 32) | r.y;
   const uint64_t* __restrict__ cum = a.cum;
-  const int64_t idx = cum ? search_cum<64>(cum, a.n_rows, u, lane, 0) : (int64_t)__umul64hi(u, (uint64_t)a.n_rows);
+  const int64_t n = live_rows<AR>(a);
+  const int64_t idx = cum ? search_cum<64>(cum, n, u, lane, 0) : (int64_t)__umul64hi(u, (uint64_t)n);
   if (lane == 0 && a.idx_out) a.idx_out[b] = (int32_t)idx;
   gather_row<64, AR>(a, idx, b, lane);
 }
@@ -120,7 +135,8 @@ __device__ __forceinline__ void gather_tile16(AR a, uint32_t step, int tile) {
   const U4 r = philox4x32_10(U4{(uint32_t)b, 0x5eedu, step, a.stream_id}, a.k0, a.k1);
   const uint64_t u = ((uint64_t)r.x << 32) | r.y;
   const uint64_t* __restrict__ cum = a.cum;
-  const int64_t idx = cum ? search_cum<32>(cum, a.n_rows, u, l, lane >> 5) : (int64_t)__umul64hi(u, (uint64_t)a.n_rows);
+  const int64_t n = live_rows<AR>(a);
+  const int64_t idx = cum ? search_cum<32>(cum, n, u, l, lane >> 5) : (int64_t)__umul64hi(u, (uint64_t)n);
   if (l == 0 && a.idx_out) a.idx_out[b] = (int32_t)idx;
   gather_row<32, AR>(a, idx, b, l);
 }
@@ -128,7 +144,7 @@ __device__ __forceinline__ void gather_tile16(AR a, uint32_t step, int tile) {
 // host: the descriptor of osrl_replay_gather's arguments (false: invalid)
 inline bool fill(GatherArgs& a, int32_t n_fields, const float* const* src, float* const* dst, const int32_t* width,
                  const float* scale, int64_t n_rows, int32_t batch, uint64_t seed, uint32_t stream_id,
-                 const osrl_step_state_t* st, const uint64_t* cum = nullptr) {
+                 const osrl_step_state_t* st, const uint64_t* cum = nullptr, const int64_t* n_rows_dev = nullptr) {
   for (int f = 0; f < OSRL_MAX_FIELDS; ++f) {
     a.src[f] = f < n_fields ? src[f] : nullptr;
     a.dst[f] = f < n_fields ? dst[f] : nullptr;
@@ -145,6 +161,7 @@ inline bool fill(GatherArgs& a, int32_t n_fields, const float* const* src, float
   a.stream_id = stream_id;
   a.st = st;
   a.cum = cum;
+  a.n_rows_dev = n_rows_dev;
   return true;
 }
 

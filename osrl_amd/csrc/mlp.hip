@@ -2674,7 +2674,7 @@ extern "C" int osrl_mlp_regress_step(const osrl_mlp_step_t* s, void* stream) {
   osrl_gather::GatherArgs ga{};
   if (s->n_fields < 0 || s->n_fields > OSRL_MAX_FIELDS ||
       !osrl_gather::fill(ga, s->n_fields, s->src, s->dst, s->width, s->scale, s->n_rows, rows, s->gather_seed, s->gather_stream,
-                         s->st, s->n_fields > 0 ? s->cum : nullptr) ||
+                         s->st, s->n_fields > 0 ? s->cum : nullptr, s->n_fields > 0 ? s->n_rows_dev : nullptr) ||
       (s->n_fields > 0 && s->n_rows < 1))
     return -1;
   // the shapes the fused launch is built for: everything else keeps the separate launches

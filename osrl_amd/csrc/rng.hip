@@ -154,6 +154,9 @@ struct SeqArgs {
   float reward_scale, cost_scale;
   uint32_t k0, k1, stream_id;
   const osrl_step_state_t* st;
+  // a store that grows (SequenceStore capacity_traj=): the device word that holds the live trajectory count -- n_traj is
+  // then the capacity of traj_start / traj_len / cdf, the draw runs over clamp(*n_traj_dev, 1, n_traj); NULL = n_traj
+  const int32_t* n_traj_dev;
 };
 
 // SequenceDataset.__iter__/__prepare_sample (dataset.py:749-787): trajectory ~ sample_prob, start ~ U{0..len-1},
@@ -164,19 +167,24 @@ __global__ __launch_bounds__(256) void seq_window_kernel(const SeqArgs a) {
   if (b >= a.B) return;
   const uint32_t step = a.st ? (uint32_t)a.st->step : 0u;
   const U4 r = philox4x32_10(U4{(uint32_t)b, 0x5e9u, step, a.stream_id}, a.k0, a.k1);
+  int n_traj = a.n_traj;
+  if (a.n_traj_dev) {  // whatever the word holds, the trajectory index stays inside the tables
+    const int v = *a.n_traj_dev;
+    n_traj = v < 1 ? 1 : v < n_traj ? v : n_traj;
+  }
   int traj;
   if (a.idx_in) {
     traj = a.idx_in[2 * b];
   } else if (a.cdf) {  // inverse-CDF draw: first index with cdf[i] > u
     const float u = (float)(r.x >> 8) * (1.0f / 16777216.0f);
-    int lo = 0, hi = a.n_traj - 1;
+    int lo = 0, hi = n_traj - 1;
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
       if (a.cdf[mid] > u) hi = mid; else lo = mid + 1;
     }
     traj = lo;
   } else {
-    traj = (int)__umul64hi(((uint64_t)r.x << 32) | r.y, (uint64_t)a.n_traj);
+    traj = (int)__umul64hi(((uint64_t)r.x << 32) | r.y, (uint64_t)n_traj);
   }
   const int len = a.traj_len[traj];
   const int64_t base = a.traj_start[traj];
@@ -235,12 +243,27 @@ extern "C" int osrl_seq_window_gather(const float* obs, const float* act, const 
                                       int64_t* o_time_steps, float* o_mask, float* o_episode_cost, float* o_costs,
                                       int32_t* idx_out, uint64_t seed, uint32_t stream_id,
                                       const osrl_step_state_t* st, void* stream) {
+  return osrl_seq_window_gather_n(obs, act, returns, cost_returns, costs, traj_start, traj_len, cdf, start_cdf, idx_in, n_traj,
+                                  B, T, od, ad, reward_scale, cost_scale, o_states, o_actions, o_returns, o_cost_returns,
+                                  o_time_steps, o_mask, o_episode_cost, o_costs, idx_out, seed, stream_id, st, nullptr,
+                                  stream);
+}
+
+extern "C" int osrl_seq_window_gather_n(const float* obs, const float* act, const float* returns,
+                                        const float* cost_returns, const float* costs, const int64_t* traj_start,
+                                        const int32_t* traj_len, const float* cdf, const float* start_cdf,
+                                        const int32_t* idx_in, int32_t n_traj, int32_t B, int32_t T,
+                                        int32_t od, int32_t ad, float reward_scale, float cost_scale, float* o_states,
+                                        float* o_actions, float* o_returns, float* o_cost_returns,
+                                        int64_t* o_time_steps, float* o_mask, float* o_episode_cost, float* o_costs,
+                                        int32_t* idx_out, uint64_t seed, uint32_t stream_id,
+                                        const osrl_step_state_t* st, const int32_t* n_traj_dev, void* stream) {
   if (!obs || !act || !returns || !cost_returns || !costs || !traj_start || !traj_len || n_traj < 1 || B < 1 || T < 1 ||
       !o_states || !o_actions || !o_returns || !o_cost_returns || !o_time_steps || !o_mask || !o_episode_cost || !o_costs)
     return -1;
   SeqArgs a{obs, act, returns, cost_returns, costs, traj_start, traj_len, cdf, start_cdf, idx_in, o_states, o_actions, o_returns,
             o_cost_returns, o_mask, o_episode_cost, o_costs, o_time_steps, idx_out, n_traj, B, T, od, ad,
-            reward_scale, cost_scale, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, st};
+            reward_scale, cost_scale, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, st, n_traj_dev};
   (void)hipGetLastError();
   hipLaunchKernelGGL(seq_window_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
@@ -270,9 +293,19 @@ extern "C" int osrl_replay_gather_w(int32_t n_fields, const float* const* src, f
                                     const int32_t* width, const float* scale, int64_t n_rows, int32_t batch,
                                     int32_t* idx_out, uint64_t seed, uint32_t stream_id,
                                     const osrl_step_state_t* st, const uint64_t* cum, void* stream) {
+  return osrl_replay_gather_n(n_fields, src, dst, width, scale, n_rows, batch, idx_out, seed, stream_id, st, cum, nullptr,
+                              stream);
+}
+
+extern "C" int osrl_replay_gather_n(int32_t n_fields, const float* const* src, float* const* dst,
+                                    const int32_t* width, const float* scale, int64_t n_rows, int32_t batch,
+                                    int32_t* idx_out, uint64_t seed, uint32_t stream_id,
+                                    const osrl_step_state_t* st, const uint64_t* cum, const int64_t* n_rows_dev,
+                                    void* stream) {
   if (n_fields < 1 || n_fields > OSRL_MAX_FIELDS || !src || !dst || !width || n_rows < 1 || batch < 1) return -1;
   GatherArgs a;
-  if (!osrl_gather::fill(a, n_fields, src, dst, width, scale, n_rows, batch, seed, stream_id, st, cum)) return -1;
+  if (!osrl_gather::fill(a, n_fields, src, dst, width, scale, n_rows, batch, seed, stream_id, st, cum, n_rows_dev))
+    return -1;
   a.idx_out = idx_out;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   hipLaunchKernelGGL(gather_kernel, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
@@ -318,13 +351,25 @@ extern "C" int osrl_step_begin_peer_w(osrl_step_state_t* st, const osrl_step_sta
                                       float* const* dst, const int32_t* width, const float* scale, int64_t n_rows,
                                       int32_t batch, uint64_t gather_seed, uint32_t gather_stream, const uint64_t* cum,
                                       void* stream) {
+  return osrl_step_begin_peer_n(st, peer, beta1, beta2, warmup, stats_cur, ring, n_stats, ring_len, noise, noise_n,
+                                noise_seed, noise_stream, n_fields, src, dst, width, scale, n_rows, batch, gather_seed,
+                                gather_stream, cum, nullptr, stream);
+}
+
+extern "C" int osrl_step_begin_peer_n(osrl_step_state_t* st, const osrl_step_state_t* peer, float beta1, float beta2,
+                                      int32_t warmup, const float* stats_cur, float* ring, int32_t n_stats,
+                                      int32_t ring_len, float* noise, int64_t noise_n, uint64_t noise_seed,
+                                      uint32_t noise_stream, int32_t n_fields, const float* const* src,
+                                      float* const* dst, const int32_t* width, const float* scale, int64_t n_rows,
+                                      int32_t batch, uint64_t gather_seed, uint32_t gather_stream, const uint64_t* cum,
+                                      const int64_t* n_rows_dev, void* stream) {
   if (!st || peer == st || n_fields < 0 || n_fields > OSRL_MAX_FIELDS || (noise && noise_n < 1)) return -1;
   if (n_fields > 0 && (!src || !dst || !width || n_rows < 1 || batch < 1)) return -1;
   BeginPack k{};
   GatherArgs& a = k.a;
   BeginArgs& b = k.b;
   if (!osrl_gather::fill(a, n_fields, src, dst, width, scale, n_rows, batch, gather_seed, gather_stream, st,
-                         n_fields > 0 ? cum : nullptr))
+                         n_fields > 0 ? cum : nullptr, n_fields > 0 ? n_rows_dev : nullptr))
     return -1;
   b.st = st;
   b.beta1 = beta1;

@@ -199,7 +199,13 @@ class PipelinedReplay:
 
     def attach_replay(self, store) -> None:
         super().attach_replay(store)
-        self._pipe = None
+        # Another store: the pipelined graphs go, the twin engine and the two linked step states stay.  (A new twin would
+        # be linked from this engine's state alone: when the last pipelined step ran on the old twin, its step count and
+        # its uncommitted statistics were lost and the next step repeated a step number.)
+        if self._pipe is not None and store is not None:
+            self._pipe.reattach(store)
+        else:
+            self._pipe = None
 
     def steps_replay(self, n: int, steps_per_graph: Optional[int] = None) -> None:
         """EXACTLY ``n`` train steps on minibatches drawn on device from the attached replay store.  Where the plan says so

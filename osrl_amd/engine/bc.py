@@ -75,8 +75,10 @@ class BCEngine(StepEngine):
         k.n_stats, k.ring_len = st.n_stats, st.ring_len
         k.stats_cur, k.ring = st.stats.data_ptr(), st.ring.data_ptr()
         if self.replay is not None:
-            n_f, src, dst, w, sc, n_rows, _B, g_seed, g_stream, keep, cum = self.replay.gather_args((self.obs, self.act), (0, 2))
+            n_f, src, dst, w, sc, n_rows, _B, g_seed, g_stream, keep, cum, live = \
+                self.replay.gather_args((self.obs, self.act), (0, 2))
             k.n_fields, k.n_rows, k.gather_seed, k.gather_stream, k.cum = n_f, n_rows, g_seed, g_stream, cum
+            k.n_rows_dev = live  # (a store that grows: n_rows is its capacity, the live count is read on device)
             for i in range(n_f):
                 k.src[i], k.dst[i], k.width[i], k.scale[i] = src[i], dst[i], w[i], sc[i]
             self._step_keep = keep

@@ -31,8 +31,8 @@ class Collected(NamedTuple):
     """``dataset``: fresh device tensors under the seven DSRL keys, ``E * L`` rows, episode-major (row ``e * L + t``);
     costs raw 0 / 1, ``terminals`` all 0, ``timeouts`` 1 on each episode's last row.  The per-episode sums are numpy
     fp64 ``[E]``; the two cost sums carry the collector's ``cost_scale`` (as ``BatchedRollout.run``'s do), the discounted
-    ones weigh step t by ``gamma ** t``."""
-    dataset: Dict[str, torch.Tensor]
+    ones weigh step t by ``gamma ** t``.  ``dataset`` is None when the run appended its rows to a store (``into=``)."""
+    dataset: Optional[Dict[str, torch.Tensor]]
     returns: np.ndarray
     cost_returns: np.ndarray
     lengths: np.ndarray
@@ -49,7 +49,7 @@ def merge_datasets(datasets: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.T
 
 class Collector(BatchedRollout):
     """``run`` = all ``venv.E`` episodes to completion, recorded.  The tables are this object's (sized at the first run,
-    again when the episode length changes); ``run`` hands out copies."""
+    again when the episode length changes); ``run`` hands out copies, or appends the tables to a store (``into=``)."""
 
     def __init__(self, model, venv, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None,
                  seed: int = 0, z: Optional[torch.Tensor] = None, use_graph: bool = True):
@@ -104,12 +104,21 @@ class Collector(BatchedRollout):
 
     @torch.no_grad()
     def run(self, noise_std=0.0, gamma: Optional[float] = None, seed: Optional[int] = None,
-            noise: Optional[torch.Tensor] = None) -> Collected:
+            noise: Optional[torch.Tensor] = None, into=None) -> Collected:
         """``noise_std``: one sigma for all episodes or ``[E]`` of them.  ``gamma`` (None: 1.0) weighs the discounted
         sums.  ``seed`` (None: keep the current one) keys the noise drawn on device.  ``noise``: ``[L, E, action_dim]``
-        injected instead (the run is then eager); rows of episodes whose sigma is 0 are not read."""
+        injected instead (the run is then eager); rows of episodes whose sigma is 0 are not read.  ``into``: a
+        ``ReplayStore`` built with ``capacity`` -- the tables go straight into ``into.append`` (one device copy per
+        table, no clone) and the result's ``dataset`` is None; a store whose widths differ from the environment's
+        (BC multi-task appends the cost return to the observations) is a ValueError before the run."""
         v, m = self.venv, self.model
         E, ad, dev = v.E, m.action_dim, self.obs.device
+        if into is not None:
+            if getattr(into, "capacity", None) is None:
+                raise ValueError("collect(into=): the store is fixed, build it with capacity=")
+            if into.weighted:
+                raise ValueError("collect(into=): the store draws by weight; collect a dataset and append it with sample_prob=")
+            into.check_append_widths(observations=v.state_dim, next_observations=v.state_dim, actions=ad)
         steps = min(m.episode_len, v.episode_len or m.episode_len)
         if self.env_c.episode_len != steps or self.rec is None:  # descriptors are by-value arguments of the graph
             self.env_c.episode_len, self.graph = steps, None
@@ -149,7 +158,11 @@ class Collector(BatchedRollout):
                     self.body()
         finally:
             self._eps = None
-        data = {k: t.clone() for k, t in self.tables.items()}
+        if into is not None:  # (every episode starts at an initial state: the chunk's is_init is right by construction)
+            into.append(self.tables)
+            data = None
+        else:
+            data = {k: t.clone() for k, t in self.tables.items()}
         tot = torch.cat([v.acc, self.disc], 1).cpu().numpy().astype(np.float64)  # the one host sync of the run
         return Collected(data, tot[:, 0], tot[:, 1], tot[:, 2], tot[:, 4], tot[:, 5])
 

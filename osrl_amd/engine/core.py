@@ -1092,13 +1092,16 @@ class StepState:
         """The step prologue in ONE launch (csrc/rng.hip ``step_begin_kernel``): this tick + the Philox fill of
         ``noise`` (flat fp32 buffer, the draws of ``randn_fill(noise, noise_seed, noise_stream, st)``) + the minibatch
         gather described by ``gather`` = ``store.gather_args(dst)``.  Same results as the three separate launches."""
-        n_f, src, dst, w, sc, n_rows, B, g_seed, g_stream, _keep, cum = gather if gather is not None else \
-            (0, None, None, None, None, 0, 0, 0, 0, None, None)
-        L.check(L.load().osrl_step_begin_peer_w(
-            self.ptr, self._peer_ptr(), self.betas[0], self.betas[1], self.warmup, self.stats.data_ptr(), self.ring.data_ptr(),
-            self.n_stats, self.ring_len, None if noise is None else noise.data_ptr(),
-            0 if noise is None else noise.numel(), noise_seed, noise_stream, n_f, src, dst, w, sc, n_rows, B, g_seed,
-            g_stream, cum, cur_stream()), "osrl_step_begin")
+        n_f, src, dst, w, sc, n_rows, B, g_seed, g_stream, _keep, cum, live = gather if gather is not None else \
+            (0, None, None, None, None, 0, 0, 0, 0, None, None, None)
+        lib = L.load()
+        args = (self.ptr, self._peer_ptr(), self.betas[0], self.betas[1], self.warmup, self.stats.data_ptr(),
+                self.ring.data_ptr(), self.n_stats, self.ring_len, None if noise is None else noise.data_ptr(),
+                0 if noise is None else noise.numel(), noise_seed, noise_stream, n_f, src, dst, w, sc, n_rows, B, g_seed,
+                g_stream, cum)
+        # (a store that grows adds the address of its live row count: ReplayStore(capacity=); n_rows is then its capacity)
+        L.check(lib.osrl_step_begin_peer_w(*args, cur_stream()) if live is None else
+                lib.osrl_step_begin_peer_n(*args, live, cur_stream()), "osrl_step_begin")
         self.host_step += 1
 
     def prologue(self, replay, dst, noise: Optional[torch.Tensor], seed: int, device_noise: bool,

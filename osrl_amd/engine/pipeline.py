@@ -59,6 +59,12 @@ class PipelinedSteps:
         self._par = self._arena = None
         self._replay_epoch = getattr(engine.replay, "sample_epoch", 0)
 
+    def reattach(self, store) -> None:
+        """The engine was attached to another store: the twin follows it, and what was captured is dropped."""
+        self.e[1].attach_replay(store)
+        self.graph = self._par = self._arena = None
+        self._replay_epoch = getattr(store, "sample_epoch", 0)
+
     # ------------------------------------------------------------------ #
     def _issue(self, par: Branches) -> None:
         """The n steps as they are captured: step k on engine k % 2, with step k+1's head issued from inside step k."""
