@@ -587,29 +587,31 @@ int osrl_replay_gather_n(int32_t n_fields, const float* const* src, float* const
  * draw a trajectory (inverse CDF of `cdf`, or uniform when NULL) and a start ~ U{0..len-1}, slice seq_len steps
  * of the concatenated trajectory tables (clipped at the trajectory end), zero-pad the tail, emit mask,
  * time_steps = start + arange(T), returns*reward_scale, cost_returns*cost_scale, episode_cost =
- * cost_returns[first step]*cost_scale.  idx_out (optional) receives (trajectory, start) per sample.
- * start_cdf (optional, [total rows]): inclusive cumulative start-index probabilities inside each trajectory
- * (SequenceDataset(start_sampling=True), dataset.py:742-744,781-783; osrl_start_index_prob) -- NULL = uniform starts.
- * idx_in (optional, [B,2]): (trajectory, start) pairs given by the caller instead of drawn (fixed evaluation windows). */
-int osrl_seq_window_gather(const float* obs, const float* act, const float* returns, const float* cost_returns,
-                           const float* costs, const int64_t* traj_start, const int32_t* traj_len, const float* cdf,
-                           const float* start_cdf, const int32_t* idx_in,
-                           int32_t n_traj, int32_t B, int32_t T, int32_t od, int32_t ad, float reward_scale,
-                           float cost_scale, float* o_states, float* o_actions, float* o_returns,
-                           float* o_cost_returns, int64_t* o_time_steps, float* o_mask, float* o_episode_cost,
-                           float* o_costs, int32_t* idx_out, uint64_t seed, uint32_t stream_id,
-                           const osrl_step_state_t* st, void* stream);
-/* The same over a store that grows: traj_start / traj_len / cdf are allocated for n_traj = the capacity, n_traj_dev
- * (device int32, one word, only read here) holds the live trajectory count, and the uniform draw and the cdf bisection run
- * over min(max(*n_traj_dev, 1), n_traj) trajectories.  n_traj_dev == NULL: exactly osrl_seq_window_gather. */
-int osrl_seq_window_gather_n(const float* obs, const float* act, const float* returns, const float* cost_returns,
-                             const float* costs, const int64_t* traj_start, const int32_t* traj_len, const float* cdf,
-                             const float* start_cdf, const int32_t* idx_in,
-                             int32_t n_traj, int32_t B, int32_t T, int32_t od, int32_t ad, float reward_scale,
-                             float cost_scale, float* o_states, float* o_actions, float* o_returns,
-                             float* o_cost_returns, int64_t* o_time_steps, float* o_mask, float* o_episode_cost,
-                             float* o_costs, int32_t* idx_out, uint64_t seed, uint32_t stream_id,
-                             const osrl_step_state_t* st, const int32_t* n_traj_dev, void* stream);
+ * cost_returns[first step]*cost_scale.  ONE descriptor (HOST struct, copied into the launch) and one entry point: an
+ * absent feature is a NULL field.  The seven tables and the eight outputs are required. */
+typedef struct {
+  const float *obs, *act, *returns, *cost_returns, *costs; /* concatenated trajectories [total rows, .] */
+  const int64_t* traj_start;
+  const int32_t* traj_len;
+  const float* cdf; /* inclusive cumulative trajectory-sampling probabilities, or NULL = uniform */
+  /* optional, [total rows]: inclusive cumulative start-index probabilities inside each trajectory
+   * (SequenceDataset(start_sampling=True), dataset.py:742-744,781-783; osrl_start_index_prob) -- NULL = uniform starts */
+  const float* start_cdf;
+  const int32_t* idx_in; /* optional, [B,2]: (trajectory, start) pairs given by the caller instead of drawn (fixed evaluation windows) */
+  /* A store that grows: traj_start / traj_len / cdf are allocated for n_traj = the capacity, n_traj_dev (device int32,
+   * one word, only read here) holds the live trajectory count, and the uniform draw and the cdf bisection run over
+   * min(max(*n_traj_dev, 1), n_traj) trajectories.  n_traj_dev == NULL: a fixed store, the draw over n_traj. */
+  const int32_t* n_traj_dev;
+  float *o_states, *o_actions, *o_returns, *o_cost_returns;
+  int64_t* o_time_steps;
+  float *o_mask, *o_episode_cost, *o_costs;
+  int32_t* idx_out; /* optional, [B,2]: receives (trajectory, start) per sample */
+  uint64_t seed;
+  int32_t n_traj, B, T, od, ad;
+  float reward_scale, cost_scale;
+  uint32_t stream_id;
+} osrl_seq_gather_t;
+int osrl_seq_window_gather(const osrl_seq_gather_t* g, const osrl_step_state_t* st /* NULL: step 0 */, void* stream);
 
 /* ---- glue (glue.hip): the elementwise / reduction tails of the loss functions ----
  * `rows_global` (0 = rows) is the data-parallel global batch used in every 1/B normalisation.

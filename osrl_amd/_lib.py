@@ -111,6 +111,16 @@ class MlpStepT(C.Structure):  # osrl_mlp_step_t
                 ("pb", _fp), ("lr", C.c_float), ("eps", C.c_float), ("ws", _fp), ("cum", C.c_void_p)]
 
 
+class SeqGatherT(C.Structure):  # osrl_seq_gather_t (cdf / start_cdf / idx_in / n_traj_dev / idx_out None = the feature is off)
+    _fields_ = [("obs", _fp), ("act", _fp), ("returns", _fp), ("cost_returns", _fp), ("costs", _fp),
+                ("traj_start", C.c_void_p), ("traj_len", C.c_void_p), ("cdf", _fp), ("start_cdf", _fp),
+                ("idx_in", C.c_void_p), ("n_traj_dev", C.c_void_p), ("o_states", _fp), ("o_actions", _fp),
+                ("o_returns", _fp), ("o_cost_returns", _fp), ("o_time_steps", C.c_void_p), ("o_mask", _fp),
+                ("o_episode_cost", _fp), ("o_costs", _fp), ("idx_out", C.c_void_p), ("seed", C.c_uint64),
+                ("n_traj", C.c_int32), ("B", C.c_int32), ("T", C.c_int32), ("od", C.c_int32), ("ad", C.c_int32),
+                ("reward_scale", C.c_float), ("cost_scale", C.c_float), ("stream_id", C.c_uint32)]
+
+
 class PackEntryT(C.Structure):
     _fields_ = [("src_off", C.c_int64), ("f_off", C.c_int64), ("b_off", C.c_int64),
                 ("out", C.c_int32), ("in_", C.c_int32)]
@@ -295,10 +305,7 @@ PROTOTYPES = {
     "osrl_replay_gather": [_i32, _P(_fp), _P(_fp), _P(_i32), _P(_f32), _i64, _i32, _vp, _u64, _u32, _vp, _vp],
     "osrl_replay_gather_w": [_i32, _P(_fp), _P(_fp), _P(_i32), _P(_f32), _i64, _i32, _vp, _u64, _u32, _vp, _vp, _vp],
     "osrl_replay_gather_n": [_i32, _P(_fp), _P(_fp), _P(_i32), _P(_f32), _i64, _i32, _vp, _u64, _u32, _vp, _vp, _vp, _vp],
-    "osrl_seq_window_gather_n": [_fp, _fp, _fp, _fp, _fp, _vp, _vp, _fp, _fp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _fp,
-                                 _fp, _fp, _fp, _vp, _fp, _fp, _fp, _vp, _u64, _u32, _vp, _vp, _vp],
-    "osrl_seq_window_gather": [_fp, _fp, _fp, _fp, _fp, _vp, _vp, _fp, _fp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _fp, _fp,
-                               _fp, _fp, _vp, _fp, _fp, _fp, _vp, _u64, _u32, _vp, _vp],
+    "osrl_seq_window_gather": [_P(SeqGatherT), _vp, _vp],
     "osrl_gauss_head": [_fp, _fp, _i32, _i32, _f32, _fp, _fp, _fp, _vp],
     "osrl_gauss_head_bwd": [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _f32, _fp, _vp],
     "osrl_gauss_ood_sample": [_fp, _fp, _i32, _i32, _i32, _fp, _vp],

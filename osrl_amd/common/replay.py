@@ -66,6 +66,29 @@ def _shift_done(dn) -> np.ndarray:
     return init
 
 
+def _checked_weights(weights, n: int, what: str, shard: slice = slice(None), positive_sum: bool = True) -> torch.Tensor:
+    """``weights`` (numpy or tensor, host or device) as a flat fp64 tensor ON THE DEVICE IT CAME FROM -- a host input is
+    judged on the host, before any device work -- cut to ``shard``.  ValueError unless there are ``n`` of them, one per
+    ``what``, non-negative and finite, and (``positive_sum``) with a positive finite sum over the shard."""
+    w = weights.detach() if torch.is_tensor(weights) else torch.from_numpy(
+        np.ascontiguousarray(np.asarray(weights, np.float64)))
+    w = w.reshape(-1)
+    if int(w.shape[0]) != n:
+        raise ValueError(f"{n} {what} weights expected, got {int(w.shape[0])}")
+    w = w[shard].to(torch.float64).contiguous()
+    ok = True
+    if w.shape[0] > 0:  # host reads, once per distribution (a NaN fails the first test, an infinity the second)
+        ok = float(w.min()) >= 0.0 and float(w.max()) < float("inf")
+    if not positive_sum:
+        if not ok:
+            raise ValueError("the weights must be non-negative and finite")
+        return w
+    if not (ok and w.shape[0] > 0 and 0.0 < float(w.sum()) < float("inf")):
+        raise ValueError("the weights must be non-negative and finite, with a positive sum"
+                         + (" on this rank's shard" if shard != slice(None) else ""))
+    return w
+
+
 class ReplayStore:
     def __init__(self, data: Dict[str, "np.ndarray | torch.Tensor"], device, reward_scale: float = 1.0,
                  cost_scale: float = 1.0, seed: int = 0, rank: int = 0, world: int = 1, state_init: bool = False,
@@ -174,27 +197,9 @@ class ReplayStore:
                 self.weighted = False
                 self.sample_epoch += 1
             return
-        if torch.is_tensor(weights) and weights.is_cuda:
-            w = weights.reshape(-1)
-            if int(w.shape[0]) != self.n_total:
-                raise ValueError(f"{self.n_total} transition weights expected, got {int(w.shape[0])}")
-            w = w[self._shard].to(device=self.device, dtype=torch.float64).contiguous()
-            lo, total = float(w.min()), float(w.sum())  # host reads, once per distribution (NaN fails both tests)
-            ok = lo >= 0.0 and 0.0 < total < float("inf")
-        else:
-            w = weights.detach().cpu().numpy() if torch.is_tensor(weights) else np.asarray(weights)
-            w = np.asarray(w, np.float64).reshape(-1)
-            if w.shape[0] != self.n_total:
-                raise ValueError(f"{self.n_total} transition weights expected, got {w.shape[0]}")
-            w = np.ascontiguousarray(w[self._shard])
-            total = float(w.sum()) if np.isfinite(w).all() else float("nan")
-            ok = bool((w >= 0.0).all()) and 0.0 < total < float("inf")
-        if not ok:
-            raise ValueError("the weights must be non-negative and finite, with a positive sum"
-                             + (" on this rank's shard" if self._shard != slice(None) else ""))
-        lib = L.load()
+        w = _checked_weights(weights, self.n_total, "transition", self._shard)
         self._alloc_weights()
-        self._w64[:self.n_rows].copy_(w if torch.is_tensor(w) else torch.from_numpy(w))
+        self._w64[:self.n_rows].copy_(w)
         self._build_cum()
         if not self.weighted:
             self.weighted = True
@@ -257,15 +262,7 @@ class ReplayStore:
             raise ValueError("the store draws by weight: append(data, sample_prob=) needs the new rows' weights")
         if not self.weighted and sample_prob is not None:
             raise ValueError("the store draws uniformly: call set_sample_prob() over the live rows instead")
-        w_new = None
-        if sample_prob is not None:
-            w_new = sample_prob if torch.is_tensor(sample_prob) else torch.from_numpy(
-                np.ascontiguousarray(np.asarray(sample_prob, np.float64).reshape(-1)))
-            w_new = w_new.reshape(-1)
-            if int(w_new.shape[0]) != m:
-                raise ValueError(f"{m} transition weights expected, got {int(w_new.shape[0])}")
-            if m and not (bool(torch.isfinite(w_new).all()) and float(w_new.min()) >= 0.0):
-                raise ValueError("the weights must be non-negative and finite")
+        w_new = None if sample_prob is None else _checked_weights(sample_prob, m, "transition", positive_sum=False)
         if m == 0:
             return
         d["done"] = _done_of(d)
@@ -364,7 +361,7 @@ class SequenceStore:
     A store that grows (``from_dataset`` / ``from_tables`` with ``capacity_rows`` / ``capacity_traj``): the row tables,
     ``traj_start`` / ``traj_len``, ``cdf`` and ``start_cdf`` are allocated once at their capacities and rewritten in
     place, the live trajectory count sits in one device word the window sampler reads (include/osrl_amd.h
-    ``osrl_seq_window_gather_n``), and ``append`` adds whole trajectories after the live ones -- a captured CDT step
+    ``osrl_seq_gather_t.n_traj_dev``), and ``append`` adds whole trajectories after the live ones -- a captured CDT step
     follows at its next replay.  (Switching an attached store between a uniform and a non-uniform distribution, or start
     sampling on and off, changes the launch's arguments as it always did: re-attach the store.)"""
 
@@ -381,29 +378,20 @@ class SequenceStore:
 
     def __init__(self, trajectories, seq_len: int, device, reward_scale: float = 1.0, cost_scale: float = 1.0,
                  sample_prob=None, seed: int = 0, rank: int = 0, start_sampling: bool = False, prob: float = 0.4):
-        self.T, self.device = int(seq_len), torch.device(device)
+        dev = torch.device(device)
         cat = lambda k: torch.as_tensor(np.concatenate([np.asarray(t[k], np.float32).reshape(len(t["costs"]), -1)  # noqa: E731
-                                                        for t in trajectories]), device=self.device).contiguous()
-        self.obs, self.act = cat("observations"), cat("actions")
-        self.ret, self.cret, self.cost = cat("returns").view(-1), cat("cost_returns").view(-1), cat("costs").view(-1)
+                                                        for t in trajectories]), device=dev).contiguous()
         lens = np.array([len(t["costs"]) for t in trajectories], np.int64)
-        self.traj_len = torch.as_tensor(lens.astype(np.int32), device=self.device)
-        self.traj_start = torch.as_tensor(np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64), device=self.device)
-        self.n_traj = len(trajectories)
-        self.n_rows = int(lens.sum())
-        self.cdf = None
+        tables = dict(observations=cat("observations"), actions=cat("actions"), returns=cat("returns").view(-1),
+                      cost_returns=cat("cost_returns").view(-1), costs=cat("costs").view(-1),
+                      traj_len=torch.as_tensor(lens.astype(np.int32), device=dev),
+                      traj_start=torch.as_tensor(np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64), device=dev))
+        cdf = None
         if sample_prob is not None:
             c = np.cumsum(np.asarray(sample_prob, np.float64))
             c /= c[-1]
-            self.cdf = torch.as_tensor(c.astype(np.float32), device=self.device)
-            self._dist = ("cdf",)
-        self.reward_scale, self.cost_scale = float(reward_scale), float(cost_scale)
-        self.base_seed = int(seed)
-        self.set_rank(rank)
-        self.od, self.ad = self.obs.shape[1], self.act.shape[1]
-        self.start_cdf = None
-        if start_sampling:
-            self.enable_start_sampling(prob)
+            cdf = torch.as_tensor(c.astype(np.float32), device=dev)
+        self._wrap(tables, seq_len, reward_scale, cost_scale, cdf, seed, rank, start_sampling, prob)
 
     def enable_start_sampling(self, prob: float = 0.4) -> None:
         """``SequenceDataset(start_sampling=True, prob=...)`` (dataset.py:742-744,781-783): window starts are drawn
@@ -422,14 +410,17 @@ class SequenceStore:
 
     def _set_table(self, name: str, new: torch.Tensor, cap: Optional[int]) -> None:
         """``cdf`` / ``start_cdf``: a fresh tensor on a fixed store; on a store that grows one buffer at capacity,
-        allocated at the first use and then rewritten in place (captured graphs hold its address)."""
+        allocated at the first use and then rewritten in place (captured graphs hold its address).  Either way the
+        gather's descriptor is rebuilt when the table's address changes."""
         if self._live is None:
             setattr(self, name, new)
+            self._describe()
             return
         buf = getattr(self, name)
         if buf is None:
             buf = torch.zeros(cap, dtype=torch.float32, device=self.device)
             setattr(self, name, buf)
+            self._describe()
         buf[:new.shape[0]].copy_(new)
 
     def set_sample_prob(self, weights) -> None:
@@ -437,14 +428,7 @@ class SequenceStore:
         tensor, host or device), normalised and turned into the cdf the sampler reads on device.  Replaces any
         earlier trajectory distribution (``sample_prob``, ``cost_sample``, ``enable_pf_sampling``)."""
         from .ingest import sample_prob_from_weights
-        w = weights if torch.is_tensor(weights) else torch.as_tensor(np.asarray(weights, np.float64))
-        w = w.reshape(-1)
-        if int(w.shape[0]) != self.n_traj:
-            raise ValueError(f"{self.n_traj} trajectory weights expected, got {int(w.shape[0])}")
-        w = w.to(device=self.device, dtype=torch.float64)
-        lo, total = float(w.min()), float(w.sum())  # host reads, once per distribution
-        if not (lo >= 0.0 and 0.0 < total < float("inf")):
-            raise ValueError("the weights must be non-negative and finite, with a positive sum")
+        w = _checked_weights(weights, self.n_traj, "trajectory").to(self.device)
         self._dist = ("weights",)
         if self._live is not None:  # kept, so that append(weights=) can extend them
             if self._traj_w is None:
@@ -487,6 +471,12 @@ class SequenceStore:
         ``capacity_rows`` / ``capacity_traj`` (either one; the other defaults to the tables' size): a store that grows --
         the tables are COPIED into allocations of those sizes, zero past the data, and ``append`` adds trajectories."""
         self = cls.__new__(cls)
+        self._wrap(tables, seq_len, reward_scale, cost_scale, cdf, seed, rank, start_sampling, prob, capacity_rows,
+                   capacity_traj)
+        return self
+
+    def _wrap(self, tables, seq_len, reward_scale, cost_scale, cdf, seed, rank, start_sampling, prob,
+              capacity_rows=None, capacity_traj=None) -> None:
         self.T, self.device = int(seq_len), tables["observations"].device
         self.obs, self.act = tables["observations"].contiguous(), tables["actions"].contiguous()
         self.ret, self.cret, self.cost = tables["returns"], tables["cost_returns"], tables["costs"]
@@ -518,9 +508,24 @@ class SequenceStore:
         self.set_rank(rank)
         self.od, self.ad = self.obs.shape[1], self.act.shape[1]
         self.start_cdf = None
+        self._describe()
         if start_sampling:
             self.enable_start_sampling(prob)
-        return self
+
+    def _describe(self) -> None:
+        """The table half of the window gather's descriptor (include/osrl_amd.h ``osrl_seq_gather_t``): rebuilt wherever
+        a table's address can change (construction, a new ``cdf`` / ``start_cdf``); ``gather`` fills in the rest.  A store
+        that grows carries its trajectory capacity and the address of the live-count word.
+        RULE: whoever gives the store another tensor for a table, ``cdf`` or ``start_cdf`` calls this afterwards
+        (``_set_table`` does); writing INTO the existing tensors, as ``append`` does, needs nothing."""
+        g = self._g = L.SeqGatherT()
+        g.obs, g.act, g.returns, g.cost_returns = self.obs.data_ptr(), self.act.data_ptr(), self.ret.data_ptr(), self.cret.data_ptr()
+        g.costs, g.traj_start, g.traj_len = self.cost.data_ptr(), self.traj_start.data_ptr(), self.traj_len.data_ptr()
+        g.cdf = None if self.cdf is None else self.cdf.data_ptr()
+        g.start_cdf = None if self.start_cdf is None else self.start_cdf.data_ptr()
+        g.n_traj = self.n_traj if self._live is None else self.capacity_traj
+        g.n_traj_dev = None if self._live is None else self._live.data_ptr()
+        g.T, g.od, g.ad, g.reward_scale, g.cost_scale = self.T, self.od, self.ad, self.reward_scale, self.cost_scale
 
     @classmethod
     def from_dataset(cls, dataset, seq_len: int, device, reward_scale: float = 1.0, cost_scale: float = 1.0,
@@ -598,18 +603,15 @@ class SequenceStore:
     def gather(self, states, actions, returns, cost_returns, time_steps, mask, episode_cost, costs, st_ptr,
                idx_out=None, stream_id: int = 2, idx_in=None) -> None:
         """``idx_in``: optional int32 [B,2] device tensor of (trajectory, start) pairs to use instead of drawing."""
-        B = states.shape[0]
-        lib = L.load()
-        args = (self.obs.data_ptr(), self.act.data_ptr(), self.ret.data_ptr(), self.cret.data_ptr(), self.cost.data_ptr(),
-                self.traj_start.data_ptr(), self.traj_len.data_ptr(), None if self.cdf is None else self.cdf.data_ptr(),
-                None if self.start_cdf is None else self.start_cdf.data_ptr(),
-                None if idx_in is None else idx_in.data_ptr(), self.n_traj if self._live is None else self.capacity_traj,
-                B, self.T, self.od, self.ad, self.reward_scale, self.cost_scale, states.data_ptr(),
-                actions.data_ptr(), returns.data_ptr(), cost_returns.data_ptr(), time_steps.data_ptr(), mask.data_ptr(),
-                episode_cost.data_ptr(), costs.data_ptr(), None if idx_out is None else idx_out.data_ptr(), self.seed,
-                stream_id, st_ptr)
-        L.check(lib.osrl_seq_window_gather(*args, cur_stream()) if self._live is None else
-                lib.osrl_seq_window_gather_n(*args, self._live.data_ptr(), cur_stream()), "osrl_seq_window_gather")
+        g = self._g
+        g.B, g.seed, g.stream_id = states.shape[0], self.seed, stream_id
+        g.idx_in = None if idx_in is None else idx_in.data_ptr()
+        g.idx_out = None if idx_out is None else idx_out.data_ptr()
+        g.o_states, g.o_actions, g.o_returns, g.o_cost_returns = (states.data_ptr(), actions.data_ptr(), returns.data_ptr(),
+                                                                  cost_returns.data_ptr())
+        g.o_time_steps, g.o_mask, g.o_episode_cost, g.o_costs = (time_steps.data_ptr(), mask.data_ptr(),
+                                                                 episode_cost.data_ptr(), costs.data_ptr())
+        L.check(L.load().osrl_seq_window_gather(g, st_ptr, cur_stream()), "osrl_seq_window_gather")
 
     def append(self, dataset, weights=None) -> None:
         """Add the complete episodes of ``dataset`` (DSRL keys, host or device) to a store built with capacities: the
@@ -643,14 +645,7 @@ class SequenceStore:
         if self.n_traj + mt > self.capacity_traj or self.n_rows + mr > self.capacity_rows:
             raise ValueError(f"the chunk ({mr} rows, {mt} trajectories) does not fit: {self.n_rows} of "
                              f"{self.capacity_rows} rows and {self.n_traj} of {self.capacity_traj} trajectories are live")
-        w_new = None
-        if weights is not None:
-            w_new = (weights if torch.is_tensor(weights) else torch.as_tensor(np.asarray(weights, np.float64)))
-            w_new = w_new.reshape(-1).to(device=self.device, dtype=torch.float64)
-            if int(w_new.shape[0]) != mt:
-                raise ValueError(f"{mt} trajectory weights expected, got {int(w_new.shape[0])}")
-            if mt and not (bool(torch.isfinite(w_new).all()) and float(w_new.min()) >= 0.0):
-                raise ValueError("the weights must be non-negative and finite")
+        w_new = None if weights is None else _checked_weights(weights, mt, "trajectory", positive_sum=False).to(self.device)
         if mt == 0:
             return
         r0, n0 = self.n_rows, self.n_traj

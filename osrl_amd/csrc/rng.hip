@@ -234,38 +234,17 @@ __global__ __launch_bounds__(256) void seq_window_kernel(const SeqArgs a) {
 
 }  // namespace
 
-extern "C" int osrl_seq_window_gather(const float* obs, const float* act, const float* returns,
-                                      const float* cost_returns, const float* costs, const int64_t* traj_start,
-                                      const int32_t* traj_len, const float* cdf, const float* start_cdf,
-                                      const int32_t* idx_in, int32_t n_traj, int32_t B, int32_t T,
-                                      int32_t od, int32_t ad, float reward_scale, float cost_scale, float* o_states,
-                                      float* o_actions, float* o_returns, float* o_cost_returns,
-                                      int64_t* o_time_steps, float* o_mask, float* o_episode_cost, float* o_costs,
-                                      int32_t* idx_out, uint64_t seed, uint32_t stream_id,
-                                      const osrl_step_state_t* st, void* stream) {
-  return osrl_seq_window_gather_n(obs, act, returns, cost_returns, costs, traj_start, traj_len, cdf, start_cdf, idx_in, n_traj,
-                                  B, T, od, ad, reward_scale, cost_scale, o_states, o_actions, o_returns, o_cost_returns,
-                                  o_time_steps, o_mask, o_episode_cost, o_costs, idx_out, seed, stream_id, st, nullptr,
-                                  stream);
-}
-
-extern "C" int osrl_seq_window_gather_n(const float* obs, const float* act, const float* returns,
-                                        const float* cost_returns, const float* costs, const int64_t* traj_start,
-                                        const int32_t* traj_len, const float* cdf, const float* start_cdf,
-                                        const int32_t* idx_in, int32_t n_traj, int32_t B, int32_t T,
-                                        int32_t od, int32_t ad, float reward_scale, float cost_scale, float* o_states,
-                                        float* o_actions, float* o_returns, float* o_cost_returns,
-                                        int64_t* o_time_steps, float* o_mask, float* o_episode_cost, float* o_costs,
-                                        int32_t* idx_out, uint64_t seed, uint32_t stream_id,
-                                        const osrl_step_state_t* st, const int32_t* n_traj_dev, void* stream) {
-  if (!obs || !act || !returns || !cost_returns || !costs || !traj_start || !traj_len || n_traj < 1 || B < 1 || T < 1 ||
-      !o_states || !o_actions || !o_returns || !o_cost_returns || !o_time_steps || !o_mask || !o_episode_cost || !o_costs)
+extern "C" int osrl_seq_window_gather(const osrl_seq_gather_t* g, const osrl_step_state_t* st, void* stream) {
+  if (!g || !g->obs || !g->act || !g->returns || !g->cost_returns || !g->costs || !g->traj_start || !g->traj_len ||
+      g->n_traj < 1 || g->B < 1 || g->T < 1 || !g->o_states || !g->o_actions || !g->o_returns || !g->o_cost_returns ||
+      !g->o_time_steps || !g->o_mask || !g->o_episode_cost || !g->o_costs)
     return -1;
-  SeqArgs a{obs, act, returns, cost_returns, costs, traj_start, traj_len, cdf, start_cdf, idx_in, o_states, o_actions, o_returns,
-            o_cost_returns, o_mask, o_episode_cost, o_costs, o_time_steps, idx_out, n_traj, B, T, od, ad,
-            reward_scale, cost_scale, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, st, n_traj_dev};
+  SeqArgs a{g->obs, g->act, g->returns, g->cost_returns, g->costs, g->traj_start, g->traj_len, g->cdf, g->start_cdf,
+            g->idx_in, g->o_states, g->o_actions, g->o_returns, g->o_cost_returns, g->o_mask, g->o_episode_cost,
+            g->o_costs, g->o_time_steps, g->idx_out, g->n_traj, g->B, g->T, g->od, g->ad, g->reward_scale,
+            g->cost_scale, (uint32_t)g->seed, (uint32_t)(g->seed >> 32), g->stream_id, st, g->n_traj_dev};
   (void)hipGetLastError();
-  hipLaunchKernelGGL(seq_window_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(seq_window_kernel, dim3((g->B + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
 

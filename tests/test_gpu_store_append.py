@@ -1,5 +1,5 @@
 """Stores that grow (ReplayStore(capacity=) / append, SequenceStore capacities / append, collect(into=); include/osrl_amd.h
-osrl_replay_gather_n / osrl_step_begin_peer_n / osrl_seq_window_gather_n): a captured step follows a store that was
+osrl_replay_gather_n / osrl_step_begin_peer_n / osrl_seq_gather_t.n_traj_dev): a captured step follows a store that was
 appended to, with the graph it already has.  Every comparison is exact: a draw is a pure function of (seed, step, row,
 live count, table), so a grown store draws what a fixed store with the same live rows draws, and an engine that kept its
 graph over an append ends where an engine that re-attached a freshly built store ends, bit for bit.  The reference has
