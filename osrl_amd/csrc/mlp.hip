@@ -275,6 +275,58 @@ __device__ __forceinline__ void narrow_layer_splitk(float* lds, int lda, int nk,
   __syncthreads();
 }
 
+// The one-output head (N == 1: the Q networks) of the 8-wave kernels off the matrix pipe.  narrow_layer_splitk spends a
+// 16-column MFMA pass, a weight round trip per wave and four barriers on 256 multiply-adds per row; here lane r < 16 of
+// wave p walks part p of row r as the fmaf chain the MFMA is (header of this file): the k-steps in the order of
+// mm_run on that wave (k_rot_w / k_at), inside a k-step t = 0..3 outside, k-slot kq = 0..3 inside, from +0; the partials
+// are then added in wave order from 0.f.  Same bits as narrow_layer_splitk<1, NCB, NW> with nblk == 1, same contract: on
+// return lds[row][0] holds the raw sum (the columns behind it are not written: the caller's element loop zeroes them).
+// The head's weight column, in k order, stands in LDS behind the 16-row tile (the caller fetched it layers ago; the
+// host launches the 8-wave kernels with kChainMaxK more floats: dynamic, because a static array in front of the tile
+// moves the tile off address 0 and every tile address then costs a register held across the k-loops).  The per-wave
+// partials go to the 8 floats of padding behind every row of the tile (lda = round16(widest layer) + 8: never staged,
+// read or saved).
+constexpr int kChainMaxK = 448;  // == kTileMaxWidth: the widest layer a tile kernel sees
+template <int NW>
+__device__ __forceinline__ void narrow_layer_chain(float* lds, int lda, int nk, int wave) {
+  static_assert(NW == 8, "one part per wave, one pad float per part");
+  // (opaque copies: none of this routine's addresses is worked out ahead of the layer loop and held across the k-loops)
+  const int tid = fresh_v<true>((int)threadIdx.x), lane = tid & 63;
+  lda = fresh_s<true>(lda);
+  const float* hw = lds + 16 * lda;
+  const int k_lo = (nk * wave) / NW, k_n = (nk * (wave + 1)) / NW - k_lo;
+  float* pad = lds + lda - 8;
+  if (lane < 16) {
+    float acc = 0.f;
+    if (k_n > 0) {
+      const int rot = k_rot_w(k_n, wave);
+      const float* arow = lds + lane * lda;
+      for (int kc = 0; kc < k_n; ++kc) {
+        const int k0 = k_at(kc, rot, k_n, k_lo) * 16;
+        f32x4 av[4], wv[4];
+#pragma unroll
+        for (int kq = 0; kq < 4; ++kq) {
+          av[kq] = *reinterpret_cast<const f32x4*>(arow + k0 + 4 * kq);
+          wv[kq] = *reinterpret_cast<const f32x4*>(hw + k0 + 4 * kq);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int kq = 0; kq < 4; ++kq) acc = __builtin_fmaf(av[kq][t], wv[kq][t], acc);
+      }
+    }
+    pad[lane * lda + wave] = acc;
+  }
+  __syncthreads();  // all reads of the input activations are done, the partials are visible
+  if (tid < 16) {
+    float sacc = 0.f;
+#pragma unroll
+    for (int q = 0; q < NW; ++q) sacc = sacc + pad[tid * lda + q];
+    lds[tid * lda] = sacc;
+  }
+  __syncthreads();
+}
+
 
 // copy the LDS tile [BM][N] (stride lda) to global dst[(row0+r)*N + c].  NT = the workgroup's thread count when the
 // caller knows it at compile time: `blockDim` is an s_load from the hidden block of the kernarg segment in every wave
@@ -431,6 +483,7 @@ struct FwdArgs {
   osrl_rows_t in;
   osrl_mlp_acts_t out;
   int32_t lda;
+  int32_t chain_head;  // OSRL_CHAIN_HEAD (host side, per launch): the one-output head as narrow_layer_chain
   osrl_mlp_tail_t tail;
 };
 
@@ -458,7 +511,10 @@ constexpr int waves_per_simd_bwd(int nrb, int ncb) { return nrb * ncb >= 7 ? 2 :
 
 // AR = how the descriptor is reached: `const FwdArgs&` (the by-value kernel argument, i.e. the kernarg segment) or
 // `const OSRL_CAS FwdArgs&` (a device-resident block, argmem.h); same member accesses, same scalar loads
-template <int NRB, int NCB, int NW, class AR>
+// CH = the body carries the chain form of the one-output head: the 8-wave launch kernels at two column blocks per wave
+// (the 256-wide Q networks).  Not the one-launch step, and not <1, 4, 8>: with the routine in it that kernel goes from 144
+// to 182 registers, i.e. from three waves per SIMD to two, and bound to three it spills (profiles/chain_head_regfit.txt)
+template <int NRB, int NCB, int NW, class AR, bool CH = (NW == 8 && NRB == 1 && NCB <= 2)>
 __device__ __forceinline__ void mlp_fwd_body(AR a, const int e, const int tile) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int BM = 16 * NRB;
@@ -467,6 +523,23 @@ __device__ __forceinline__ void mlp_fwd_body(AR a, const int e, const int tile) 
   const int row0 = tile * BM;
   const int rows = a.in.rows, lda = a.lda;
   const int L = a.net.n_layers;
+  // the head's weight column (n = 0 of the forward pack: one float4 per k-quad, quads round16(1) * 4 floats apart) is
+  // requested one float per thread behind the last wide layer's k-loop and parked in LDS, behind the tile, after that
+  // layer's epilogue
+  bool chain = false;
+  if constexpr (CH) {
+    const int nkh = round16(a.net.dims[L - 1]) >> 4;
+    chain = a.chain_head != 0 && a.net.dims[L] == 1 && nkh >= 4 && 16 * nkh <= kChainMaxK && lda >= 16 * NW;
+  }
+  float hwv = 0.f;
+  auto head_request = [&]() {
+    const int t = fresh_v<CH>(tid);
+    if (CH && chain && t < round16(a.net.dims[L - 1])) hwv = a.net.Wf[e][L - 1][(t >> 2) * 64 + (t & 3)];
+  };
+  auto head_park = [&]() {
+    const int t = fresh_v<CH>(tid);
+    if (CH && chain && t < round16(a.net.dims[L - 1])) lds[BM * fresh_s<CH>(lda) + t] = hwv;
+  };
 #if OSRL_CHAIN_PRIO > 0
   // latency-chain launches (training rows) outrank the N*B-row filler launches they share CUs with
   if (rows <= OSRL_CHAIN_PRIO) __builtin_amdgcn_s_setprio(3);
@@ -479,6 +552,10 @@ __device__ __forceinline__ void mlp_fwd_body(AR a, const int e, const int tile) 
   auto begin_layer = [&](int l) {
     const int K = a.net.dims[l], N = a.net.dims[l + 1];
     const int nblk = (N + 15) >> 4, nk = round16(K) >> 4;
+    if (CH && chain && l == L - 1) {  // no ring: the weight column, behind the barrier + epilogue this call stands before
+      head_request();
+      return;
+    }
     if (nblk <= 2 && nk >= 4 && lda >= 16 * NW) {
       narrow_prefetch<NCB, NW>(ring, nk, a.net.Wf[e][l], round16(N), 0, nblk, wave);
     } else {
@@ -520,6 +597,7 @@ __device__ __forceinline__ void mlp_fwd_body(AR a, const int e, const int tile) 
         }
       }
     }
+    if (L == 1) head_park();
     __syncthreads();
     if (e == 0 && a.out.x) tile_to_global<64 * NW>(lds, lda, BM, K0, a.out.x, row0, rows);
   }
@@ -527,7 +605,7 @@ __device__ __forceinline__ void mlp_fwd_body(AR a, const int e, const int tile) 
   constexpr bool kWarm = OSRL_L2_WARM && NW == 8;
   float warm[OSRL_MAX_LAYERS - 1][kWarmLines];
   if (kWarm) {
-    for (int l = 1; l < L; ++l)
+    for (int l = 1; l < (CH && chain ? L - 1 : L); ++l)
       l2_warm<64 * NW>(a.net.Wf[e][l], round16(a.net.dims[l]) * round16(a.net.dims[l + 1]), warm[l - 1]);
   }
 
@@ -540,7 +618,14 @@ __device__ __forceinline__ void mlp_fwd_body(AR a, const int e, const int tile) 
     const int nk = round16(K) >> 4;
     if (nblk <= 2 && nk >= 4 && lda >= 16 * NW) {
       // narrow layer: split K over the 4 waves, then bias/activation on the summed tile in LDS
-      narrow_layer_splitk<NRB, NCB, NW>(lds, lda, nk, a.net.Wf[e][l], round16(N), 0, nblk, wave, ring);
+      if constexpr (CH) {
+        if (chain && l == L - 1)
+          narrow_layer_chain<NW>(lds, lda, nk, wave);
+        else
+          narrow_layer_splitk<NRB, NCB, NW>(lds, lda, nk, a.net.Wf[e][l], round16(N), 0, nblk, wave, ring);
+      } else {
+        narrow_layer_splitk<NRB, NCB, NW>(lds, lda, nk, a.net.Wf[e][l], round16(N), 0, nblk, wave, ring);
+      }
       if (l + 1 < L) begin_layer(l + 1);
       PHASE_STAMP(2 + 4 * l);
       PHASE_STAMP(3 + 4 * l);
@@ -583,12 +668,13 @@ __device__ __forceinline__ void mlp_fwd_body(AR a, const int e, const int tile) 
         fwd_epilogue<NRB, NCB, OSRL_ACT_ID>(lds, lda_e, acc, cb0, cnt, N, oscale, lane_e);
     }
     PHASE_STAMP(4 + 4 * l);
+    if (l == L - 2) head_park();
     __syncthreads();
     float* save = a.out.h[e][l];
     if (save) tile_to_global<64 * NW>(lds, lda, BM, N, save, row0, rows);
     PHASE_STAMP(5 + 4 * l);
     if (kWarm && l == 0) {
-      for (int w = 1; w < L; ++w) l2_warm_done(warm[w - 1]);
+      for (int w = 1; w < (CH && chain ? L - 1 : L); ++w) l2_warm_done(warm[w - 1]);
     }
   }
   // the net's output tile [BM][dims[L]] is still in LDS (nothing wrote it since the last barrier)
@@ -1690,6 +1776,14 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ src
 
 inline int round16h(int x) { return (x + 15) & ~15; }
 
+// OSRL_CHAIN_HEAD (read per launch: a test flips it between calls; an A/B and test aid, not a plan field): 0 = the
+// one-output head of the 8-wave forward kernels as the layer it was (narrow_layer_splitk), 1 (default) = narrow_layer_chain.
+// Same bits either way.
+inline int chain_head_env() {
+  const char* v = getenv("OSRL_CHAIN_HEAD");
+  return (v && v[0] == '0') ? 0 : 1;
+}
+
 struct TileChoice {
   int nrb, ncb, lda, nw;  // row blocks per tile, column blocks per wave, LDS row stride, waves per workgroup
 };
@@ -1732,7 +1826,9 @@ template <typename Args, typename K>
 int launch_tiles(K kernel, void (*kernel_p)(const void*), const Args& args, int rows, int nets, int nrb, int lda,
                  hipStream_t stream, int threads = 256, int wg_cap = 0) {
   const int BM = 16 * nrb;
-  const size_t lds_bytes = (size_t)BM * lda * sizeof(float);
+  // (8-wave kernels: + the one-output head's weight column behind the tile, narrow_layer_chain; the backward shares this
+  // dispatch and leaves the 1.75 KB unused)
+  const size_t lds_bytes = (size_t)BM * lda * sizeof(float) + (threads == 512 ? kChainMaxK * sizeof(float) : 0);
   int tiles = (rows + BM - 1) / BM;
   if (wg_cap > 0 && tiles * nets > wg_cap) tiles = (wg_cap + nets - 1) / nets;  // forward kernel loops over tiles
   return osrl_argmem::launch(kernel, kernel_p, dim3(tiles, nets, 1), dim3(threads), lds_bytes, stream, args);
@@ -1787,6 +1883,7 @@ bool valid_net(const osrl_mlp_t* n) {
 //   WIDE_BWD   Y = (A P) * act'(h)                            (dZ_{l-1} = (dZ_l W_l) * act'(h_{l-1}), packed Wb)
 //   WIDE_PLAIN Y = A P                                        (the dX slice)
 constexpr int kTileMaxWidth = 448;
+static_assert(kTileMaxWidth <= kChainMaxK, "narrow_layer_chain parks the head's weight column in kChainMaxK floats");
 bool wide_net(const osrl_mlp_t* n) {
   for (int l = 0; l <= n->n_layers; ++l)
     if (n->dims[l] > kTileMaxWidth) return true;
@@ -2010,7 +2107,7 @@ __device__ __forceinline__ void mlp_step_body(AR a) {
       __syncthreads();  // (workgroup scope: the rows were written through this CU's L1)
     }
     STEP_STAMP(2);
-    mlp_fwd_body<1, NCB, 8, decltype((a.fwd))>(a.fwd, 0, wg);
+    mlp_fwd_body<1, NCB, 8, decltype((a.fwd)), false>(a.fwd, 0, wg);
     __syncthreads();
     STEP_STAMP(3);
     {  // F.mse_loss (bc.py:46-47) on this tile: du = 2 (u - target) / n, partial sum of squares
@@ -2338,6 +2435,7 @@ static int mlp_forward_impl(const osrl_mlp_t* net, const osrl_rows_t* in, const 
   if (want_tail) a.tail = *tail;
   const TileChoice t = choose_tile(net, in->rows, 0);
   a.lda = t.lda;
+  a.chain_head = chain_head_env();
   if (net->wg_cap > 0 && t.nw == 4 && (t.ncb == 4 || t.ncb == 7) && t.nrb <= 2 &&
       (long)((in->rows + 16 * t.nrb - 1) / (16 * t.nrb)) * net->n_nets > net->wg_cap) {
     hipStream_t st = (hipStream_t)stream;
@@ -2367,7 +2465,7 @@ static int launch_fwd2(const FwdArgs& a0, const FwdArgs& a1, int nets0, int nets
                        hipStream_t stream) {
   const int BM = 16 * NRB;
   const int t0 = (rows0 + BM - 1) / BM, t1 = (rows1 + BM - 1) / BM;
-  const size_t lds_bytes = (size_t)BM * lda * sizeof(float);
+  const size_t lds_bytes = (size_t)BM * lda * sizeof(float) + (NW == 8 ? kChainMaxK * sizeof(float) : 0);
   Fwd2Args f{};
   f.a0 = a0;
   f.a1 = a1;
@@ -2417,6 +2515,7 @@ static int mlp_forward2_impl(const osrl_mlp_t* net0, const osrl_rows_t* in0, con
   if (tail1) a1.tail = *tail1;
   const int lda = t0.lda > t1.lda ? t0.lda : t1.lda;
   a0.lda = a1.lda = lda;
+  a0.chain_head = a1.chain_head = chain_head_env();
   const int n0 = net0->n_nets, n1 = net1->n_nets, r0 = in0->rows, r1 = in1->rows;
   hipStream_t st = (hipStream_t)stream;
   if (t0.nw == 8) {

@@ -187,6 +187,10 @@ __device__ __forceinline__ int k_rot(int nk) {
   const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   return (int)((blockIdx.x * 5u + blockIdx.y * 3u + w) % (unsigned)nk);
 }
+// the walk of wave w of this block, for a thread that restates that wave's sum (narrow_layer_chain in mlp.hip)
+__device__ __forceinline__ int k_rot_w(int nk, int w) {
+  return (int)((blockIdx.x * 5u + blockIdx.y * 3u + (unsigned)w) % (unsigned)nk);
+}
 __device__ __forceinline__ int k_at(int kc, int rot, int nk, int kc0) {  // nk steps starting at kc0 (split-K sub-range)
   const int k = kc + rot;
   return kc0 + (k >= nk ? k - nk : k);
