@@ -380,7 +380,10 @@ __device__ __forceinline__ float quantile_rows(const float* __restrict__ x, int6
                                                uint32_t* s_min) {
   const double pos = (double)q * (double)(n - 1);
   const int64_t lo = (int64_t)floor(pos);
-  const int64_t hi = lo + 1 < n ? lo + 1 : n - 1;
+  // torch.quantile's upper neighbour is ceil(pos): at a whole position it is the element itself.  For finite values
+  // "lo + 1 with weight 0" gives the same bits (v + d * 0); with an INFINITE next order statistic it gave inf * 0 = NaN
+  // where torch returns the element (n = 5, q = 0.75, one +inf), and it ran the smallest-key-above pass for nothing.
+  const int64_t hi = (double)lo < pos && lo + 1 < n ? lo + 1 : lo;
   const float w = (float)(pos - (double)lo);
   if (threadIdx.x < 34) cnt[threadIdx.x] = 0;
   uint32_t kreg[ROWS];

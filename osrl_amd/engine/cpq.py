@@ -316,7 +316,13 @@ class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
             # (single GPU, plan.vae_adam_side: the VAE's optimizer step at the head of the side branch's second half, in
             # front of its only reader, instead of on the main chain -- +0.7 % at C2, DESIGN_LOG round 5)
             vae_adam_side = dp is None and par.enabled and self.plan.vae_adam_side and not self.p_vae.can_fuse_adam()
-            if vae_adam_side:
+            # (plan.vae_dw_side: the VAE group's dW too -- its only reader is that optimizer step; issued in the side branch's
+            # second half below.  Not where the lab switch OSRL_VAE_ADAM_EDGE=0 takes away the edge that orders it in a no-join
+            # graph)
+            vae_dw_side = vae_adam_side and self.ood_rows and self.plan.vae_dw_side and not (no_join and VAE_ADAM_EDGE == "0")
+            if vae_dw_side:
+                pass
+            elif vae_adam_side:
                 self._pr("vae_dw", 0)
                 self.p_vae.launch()
                 self._pr("vae_dw", 1)
@@ -448,10 +454,20 @@ class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
             if self._stress_spin and par.enabled and self._stress_at == "second":
                 torch.cuda._sleep(self._stress_spin)  # (tests: this branch's second half arrives LATE; results must not move)
             if dp is None and par.enabled and self.plan.vae_adam_side and not self.p_vae.can_fuse_adam():
+                if vae_dw_side:
+                    # (engine/plan.py vae_dw_side.  Reads the activation and dZ buffers the main chain's VAE phase wrote: this
+                    # branch waited for ev_vae above, recorded behind that phase -- or, with plan.ood_rows_late, further down
+                    # the same chain)
+                    self._pr("vae_dw", 0)
+                    self.p_vae.launch()
+                    self._pr("vae_dw", 1)
                 self._update("vae", 0.0)  # (engine/plan.py vae_adam_side: off the main chain, in front of its only reader)
                 if no_join and nxt is not None and VAE_ADAM_EDGE != "0":
                     # ... of THIS step: the next step's VAE phase, on the main chain, reads it too, and steps that are not
-                    # joined need an edge of their own for that
+                    # joined need an edge of their own for that.  With plan.vae_dw_side the same edge carries a second
+                    # dependency: the next step's VAE phase REWRITES the activation and dZ buffers this step's dW launch
+                    # reads.  The optimizer step follows the dW launch on this stream and the event is recorded behind it, so
+                    # whoever waits for it is behind both (a joined step, or the last step of a graph, has the join for that).
                     self._ev_vae_adam = par.mark(0)
             self._pr("enc_ood", 0)  # bench.py: HIP events around the dominant launch as it runs inside the step
             # (the KL rows of cpq.py:178-182 by the encoder launch itself: OSRL_TAIL_VAE_KL)

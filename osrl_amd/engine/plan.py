@@ -71,6 +71,7 @@ class CPQPlan:
     steps_per_graph: int      # engine.steps_replay(): train steps per replayed hipGraph (engine/pipeline.py); 1 = one step
     ood_rows: bool = False    # single GPU: the target cost critics of the OOD penalty on the SELECTED rows only (cpq.py:183-184)
     ood_rows_late: bool = True   # ... and the side branch's second half then starts behind the cost critics' dW launch
+    vae_dw_side: bool = False    # ... and (with vae_adam_side) the VAE group's dW launch in front of that optimizer step, off the main chain
     ood_share: bool = False   # the two N*B-row launches on tiles of shared observations: the observation part of layer 0 once
     #                           per observation of a tile (osrl_rows_t.share0)
     pipe_no_join: bool = False   # pipelined graphs: no join between the steps of a graph (the dual step of step k at the head
@@ -100,6 +101,9 @@ def ood_rows_ok(od: int, ad: int, B: int, N: int, c_hidden) -> bool:
     KL keys in one workgroup's registers."""
     return (c_hidden is not None and len(c_hidden) >= 1 and all(13 <= (int(h) + 15) // 16 <= 16 for h in c_hidden)
             and od + ad <= 128 and N * B <= 32768)
+
+
+VAE_DW_SIDE_DEFAULT = "1"  # (applies where vae_adam_side and ood_rows are on -- C2; profiles/ood_tail_bench_ab.json)
 
 
 def cpq_plan(od: int, ad: int, B: int, vae_hidden: int, N: int, seeds: bool = True, c_hidden=(256, 256)) -> CPQPlan:
@@ -172,6 +176,12 @@ def cpq_plan(od: int, ad: int, B: int, vae_hidden: int, N: int, seeds: bool = Tr
         and ood_tile == 80 and ood_rows_ok(od, ad, B, N, c_hidden)
     rows_late = knob("OSRL_OOD_ROWS_LATE", "1", "plan.ood_rows: the side branch's second half waits for the cost critics' dW "
                      "launch instead of the VAE's: 1 / 0") == "1"
+    # The VAE group's dW launch (31.6 us at C2) has one reader, the VAE's optimizer step, which vae_adam_side already runs at
+    # the head of the side branch's second half: the dW launch goes there too, off the main chain (engine/cpq.py).  C2, five
+    # alternating runs a side: 2661-2676 against 2499-2545 steps/s at K = 300, 2676-2692 against 2510-2553 on the 20-step
+    # command; with ood_rows_late off under this placement 2669-2676: left on (DESIGN_LOG "OOD tail").
+    dw_side = knob("OSRL_VAE_DW_SIDE", VAE_DW_SIDE_DEFAULT, "plan.vae_adam_side + plan.ood_rows: the VAE group's dW launch on the "
+                   "side branch in front of the VAE's optimizer step: 1 / 0") == "1" and bool(side) and bool(ood_rows)
     # the N*B rows of the two OOD launches are the B observations N times over (cpq.py:164-176): on tiles of [5 copies] x [16
     # observations] the observation columns of layer 0 are multiplied once per observation (osrl_rows_t.share0, csrc/mlp_nb.hip
     # nb_share_acc; second session of round 6).  Isolated launches at C2: cost critics 69.4 -> 60.9 us, encoder 72.1 -> 65.7;
@@ -183,7 +193,7 @@ def cpq_plan(od: int, ad: int, B: int, vae_hidden: int, N: int, seeds: bool = Tr
         and tile_widths(vae_hidden, *(c_hidden if c_hidden is not None else ()))
     return CPQPlan(head_tails=bool(head_tails), vae_dw_tile=vt, vae_dw_splits=splits, small_dw=B >= 1024,
                    ood_tile=ood_tile, vae_ns=bool(vae_ns), vae_adam_side=bool(side), steps_per_graph=spg,
-                   ood_rows=bool(ood_rows), ood_rows_late=bool(rows_late), ood_share=bool(ood_share), pipe_no_join=bool(no_join), pipe_prologue=pro)
+                   ood_rows=bool(ood_rows), ood_rows_late=bool(rows_late), vae_dw_side=bool(dw_side), ood_share=bool(ood_share), pipe_no_join=bool(no_join), pipe_prologue=pro)
 
 
 def vae_ns_auto(rows: int, od: int, ad: int, vae_hidden: int = 400) -> bool:
@@ -269,7 +279,7 @@ def cdt_split_use(supported: bool, rows: int, K: int, N: int, resid: bool) -> bo
 PINNED = {
     "c2": (cpq_plan, dict(od=76, ad=2, B=2048, vae_hidden=400, N=10),
            CPQPlan(head_tails=True, vae_dw_tile=5, vae_dw_splits=3, small_dw=True, ood_tile=80, vae_ns=True, vae_adam_side=True,
-                   steps_per_graph=20, ood_rows=True, ood_share=True, pipe_no_join=True, pipe_prologue="head")),
+                   steps_per_graph=20, ood_rows=True, vae_dw_side=True, ood_share=True, pipe_no_join=True, pipe_prologue="head")),
     "c4": (cpq_plan, dict(od=17, ad=6, B=2048, vae_hidden=400, N=10),
            CPQPlan(head_tails=False, vae_dw_tile=5, vae_dw_splits=3, small_dw=True, ood_tile=80, vae_ns=True, vae_adam_side=False,
                    steps_per_graph=20, ood_rows=True, ood_share=True, pipe_no_join=True, pipe_prologue="critic")),
