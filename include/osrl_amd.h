@@ -1109,6 +1109,38 @@ int osrl_cdt_rollout_push(float* states, float* actions, float* returns, float* 
                           int32_t cost_reverse, int32_t* cursor, int32_t episode_len /* no-op once cursor reaches it */,
                           void* stream);
 
+/* The CDT rollout step that records: pick, osrl_env_step, push and the cursor of the rollout above, plus what
+ * osrl_env_collect adds to a step, as ONE launch after the transformer forward (one workgroup per episode, no shared
+ * cursor).  Episode ep at its own step t = acc[ep][2] (t < episode_len, done latch clear; otherwise the launch writes
+ * nothing for it), its window holding n = min(t + 1, seq_len) filled positions:
+ *   mu = head[(ep * seq_len + n - 1) * head_width + k];  s = sample ? exp(head[... + action_dim + k]) (rows are
+ *         [mu | log_std], no log-std bounds, head_width >= 2 * action_dim) : rec->sigma[ep];
+ *   a = clip(mu + s * eps, +-max_action), eps as osrl_env_collect documents it; s == 0 gives exactly clip(mu) and eps
+ *         is not read;
+ *   the environment step, the table row ep * episode_len + t, acc (cost sum * env->cost_scale) and rec->disc:
+ *         osrl_env_collect's arithmetic, bit for bit;
+ *   the window: actions[n - 1] = a, then (sliding by one when n == seq_len) append s', returns - reward, costs_to_go -
+ *         cost * win->cost_scale [1 - cost under cost_reverse], time step t + 1, a zero dummy action, mask = 1 --
+ *         osrl_cdt_rollout_push's arithmetic.
+ * With sigma == 0 and sample == 0 the episode is osrl_cdt_rollout_pick / osrl_env_step / osrl_cdt_rollout_push's, bit
+ * for bit.  seq_len <= 1024. */
+typedef struct {
+  float* states;        /* [episodes, seq_len, state_dim] */
+  float* actions;       /* [episodes, seq_len, action_dim] */
+  float* returns;       /* [episodes, seq_len] */
+  float* costs_to_go;   /* [episodes, seq_len] */
+  int64_t* time_steps;  /* [episodes, seq_len] */
+  float* mask;          /* [episodes, seq_len] */
+  const float* head;    /* [episodes * seq_len, head_width] */
+  int32_t seq_len, head_width;
+  int32_t sample;       /* 0: s = rec->sigma[ep];  1: s = exp(log_std) of the head row */
+  int32_t cost_reverse;
+  float cost_scale;     /* of the costs-to-go (acc and disc carry env->cost_scale) */
+  float pad_;
+} osrl_cdt_window_t;
+int osrl_cdt_collect(const osrl_env_t* env, const osrl_collect_t* rec, const osrl_cdt_window_t* win, float* state,
+                     float* acc, int32_t episodes, void* stream);
+
 /* library identity */
 /* ---- B = 1 .. OSRL_POLICY_MAX_ROWS act() latency path (act.hip) -----------------------------------------------
  * Replaces one `model.act(obs)` of the reference's episode loop (XTrainer.rollout, cpq.py:330-347): H2D copy of the

@@ -152,6 +152,13 @@ class CollectT(C.Structure):  # osrl_collect_t
                 ("eps_in", C.c_void_p), ("episode_base", C.c_uint32), ("stream_id", C.c_uint32)]
 
 
+class CdtWindowT(C.Structure):  # osrl_cdt_window_t
+    _fields_ = [("states", C.c_void_p), ("actions", C.c_void_p), ("returns", C.c_void_p), ("costs_to_go", C.c_void_p),
+                ("time_steps", C.c_void_p), ("mask", C.c_void_p), ("head", C.c_void_p),
+                ("seq_len", C.c_int32), ("head_width", C.c_int32), ("sample", C.c_int32), ("cost_reverse", C.c_int32),
+                ("cost_scale", C.c_float), ("pad_", C.c_float)]
+
+
 class GemvNetT(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("dims", C.c_int32 * (MAX_LAYERS + 1)), ("acts", C.c_int32 * MAX_LAYERS),
                 ("out_scale", C.c_float), ("Wf", C.c_void_p * MAX_LAYERS), ("b", C.c_void_p * MAX_LAYERS)]
@@ -198,6 +205,7 @@ PROTOTYPES = {
     "osrl_mlp_forward": [_P(MlpT), _P(RowsT), _P(ActsT), _vp],
     "osrl_env_step": [_P(EnvT), _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp],
     "osrl_env_collect": [_P(EnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _i32, _vp],
+    "osrl_cdt_collect": [_P(EnvT), _P(CollectT), _P(CdtWindowT), _vp, _vp, _i32, _vp],
     "osrl_cdt_rollout_pick": [_vp, _i32, _i32, _i32, _i32, _vp, _f32, _vp, _vp],
     "osrl_cdt_rollout_push": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _f32, _i32,
                               _vp, _i32, _vp],

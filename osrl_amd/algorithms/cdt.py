@@ -306,15 +306,10 @@ class CDTTrainer:
         if isinstance(self.env, (list, tuple)):
             return self.evaluate_targets(num_rollouts, [(target_return, target_cost)], schedule=schedule)[0]
         if isinstance(self.env, VecSyntheticSafeEnv):
-            from ..engine.rollout import CDTBatchedRollout
             if self.env.E != num_rollouts:
                 raise ValueError(f"the vector environment holds {self.env.E} episodes, evaluate() was asked for "
                                  f"{num_rollouts}")
-            ro = getattr(self, "_rollout", None)
-            if ro is None or ro[0] != id(self.env):
-                ro = self._rollout = (id(self.env), CDTBatchedRollout(self.model, self.env, self.cost_scale,
-                                                                      self.cost_reverse, self.use_graph))
-            r, c, n = ro[1].run(target_return, target_cost)
+            r, c, n = self._batched_rollout().run(target_return, target_cost)
             return float(r.mean()) / self.reward_scale, float(c.mean()) / self.cost_scale, float(n.mean())
         self.model.eval()
         rets, costs, lens = [], [], []
@@ -325,6 +320,37 @@ class CDTTrainer:
             costs.append(c)
         self.model.train()
         return np.mean(rets) / self.reward_scale, np.mean(costs) / self.cost_scale, np.mean(lens)
+
+    def _batched_rollout(self):
+        """The ``CDTBatchedRollout`` on ``self.env`` (buffers + captured graph), cached on the trainer."""
+        from ..engine.rollout import CDTBatchedRollout
+        ro = getattr(self, "_rollout", None)
+        if ro is None or ro[0] != id(self.env):
+            ro = self._rollout = (id(self.env), CDTBatchedRollout(self.model, self.env, self.cost_scale,
+                                                                  self.cost_reverse, self.use_graph))
+        return ro[1]
+
+    def collect_targets(self, target_return, target_cost, noise_std=0.0, sample: bool = False,
+                        gamma: Optional[float] = None, seed: int = 0, noise=None, into=None):
+        """The ``evaluate`` rollout on a ``VecSyntheticSafeEnv``, recorded (the other trainers' ``collect``; here the
+        method carries the targets a CDT rollout cannot do without, and sits beside ``evaluate_targets``).  Every episode
+        of ``self.env`` runs to its end by the windowed autoregression, conditioned on ``(target_return, target_cost)`` --
+        one pair for all episodes or one value per episode -- and comes back as a ``Collected`` (engine/collect.py): the
+        DSRL-layout dataset on device plus the per-episode (discounted) sums.
+        The action is ``clip(mu + s * eps)``: ``s = noise_std`` (one sigma or one per episode), or with ``sample=True``
+        the Gaussian head's own ``exp(log_std)`` (ValueError on a ``stochastic=False`` model, and together with a non-zero
+        ``noise_std``); the window records the action taken.  ``gamma``, ``seed``, ``noise`` as ``collect`` takes them.
+        ``into``: a ``SequenceStore`` built with capacities (``store.append``: an attached CDT engine draws from the new
+        trajectories at its next ``step_store``) or a capacity ``ReplayStore``; the result's ``dataset`` is then None, and
+        a store that cannot take the run is a ValueError before the run.  Any other kind of environment: TypeError."""
+        from ..common.synthetic_env import VecSyntheticSafeEnv
+        from ..engine.collect import check_sampling, collect_cdt_batched
+        check_sampling(self.model, sample, noise_std)
+        if not isinstance(self.env, VecSyntheticSafeEnv):
+            raise TypeError(f"collect_targets() records the batched on-device rollout: self.env must be a "
+                            f"VecSyntheticSafeEnv, not {type(self.env).__name__}")
+        return collect_cdt_batched(self, target_return=target_return, target_cost=target_cost, noise_std=noise_std,
+                                   sample=sample, gamma=gamma, seed=seed, noise=noise, into=into)
 
     @torch.no_grad()
     def rollout(self, model: CDT, env, target_return: float, target_cost: float):
@@ -370,12 +396,29 @@ class CDTTrainer:
         """``evaluate`` for each ``(target_return, target_cost)`` pair of ``targets``: a list of ``(return, cost,
         length)`` triples.  With a list or tuple of N host environments as ``self.env`` the ``len(targets) *
         num_rollouts`` rollouts are laid out target-major and job ``q`` runs in wave ``q // N`` on environment
-        ``q % N``, so rollouts for different targets share a wave; with any other environment this is one
-        ``evaluate`` per pair.  ``schedule="refill"`` (list of environments): the same jobs as one queue, where a slot
+        ``q % N``, so rollouts for different targets share a wave.  With a ``VecSyntheticSafeEnv`` of
+        ``len(targets) * num_rollouts`` episodes (and more than one pair) the whole grid is ONE batched rollout, target-major:
+        episode ``j`` carries ``targets[j // num_rollouts]`` and starts at the environment's initial state ``base_seed +
+        j``, each triple is the mean over its own ``num_rollouts`` episodes; with ``num_rollouts`` episodes it is one
+        ``evaluate`` per pair, any other size is a ValueError.  With any other environment this is one ``evaluate`` per
+        pair.  ``schedule="refill"`` (list of environments): the same jobs as one queue, where a slot
         whose episode has ended takes the next job at once (``rollout_jobs``; the run is kept as ``last_refill``)."""
+        from ..common.synthetic_env import VecSyntheticSafeEnv
         from ..engine.act import check_schedule
         check_schedule(schedule)
         targets = [(float(tr), float(tc)) for tr, tc in targets]
+        if isinstance(self.env, VecSyntheticSafeEnv):
+            k, G = int(num_rollouts), len(targets)
+            if G > 1 and self.env.E == G * k:  # the whole grid as one batched rollout, target-major
+                ro = self._batched_rollout()
+                r, c, n = ro.run(np.repeat([t[0] for t in targets], k), np.repeat([t[1] for t in targets], k))
+                return [(float(r[i * k:(i + 1) * k].mean()) / self.reward_scale,
+                         float(c[i * k:(i + 1) * k].mean()) / self.cost_scale, float(n[i * k:(i + 1) * k].mean()))
+                        for i in range(G)]
+            if self.env.E != k:
+                raise ValueError(f"the vector environment holds {self.env.E} episodes: evaluate_targets() takes "
+                                 f"num_rollouts ({k}, one rollout per target pair) or len(targets) * num_rollouts "
+                                 f"({G * k}, the whole grid as one rollout)")
         if not isinstance(self.env, (list, tuple)):
             return [self.evaluate(num_rollouts, tr, tc) for tr, tc in targets]
         envs = list(self.env)

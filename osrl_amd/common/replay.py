@@ -613,6 +613,27 @@ class SequenceStore:
                                                                  episode_cost.data_ptr(), costs.data_ptr())
         L.check(L.load().osrl_seq_window_gather(g, st_ptr, cur_stream()), "osrl_seq_window_gather")
 
+    def check_append(self, n_traj: int, n_rows: int, **widths: int) -> None:
+        """ValueError unless ``append`` (without ``weights=``) would take a chunk of ``n_traj`` trajectories in ``n_rows``
+        rows with these column counts (``observations=17, actions=6``): the store grows, the chunk fits, the widths are
+        the tables', and the trajectory distribution can follow (not ``set_sample_prob`` weights, not a ready-made cdf).
+        Nothing is changed: for callers that produce the chunk on device and want the refusal first."""
+        if self._live is None:
+            raise ValueError("this store is fixed: build it with capacity_rows= / capacity_traj= to append")
+        for k, w in widths.items():
+            want = {"observations": self.od, "actions": self.ad}[k]
+            if int(w) != want:
+                raise ValueError(f"the store's {k} have {want} columns, the new rows {int(w)}")
+        kind = None if self._dist is None else self._dist[0]
+        if kind == "cdf":
+            raise ValueError("the trajectory distribution was given as a cdf: call set_sample_prob(weights) before append")
+        if kind == "weights":
+            raise ValueError("the store draws by set_sample_prob's weights: append(dataset, weights=) needs the new "
+                             "trajectories' weights")
+        if self.n_traj + int(n_traj) > self.capacity_traj or self.n_rows + int(n_rows) > self.capacity_rows:
+            raise ValueError(f"the chunk ({int(n_rows)} rows, {int(n_traj)} trajectories) does not fit: {self.n_rows} of "
+                             f"{self.capacity_rows} rows and {self.n_traj} of {self.capacity_traj} trajectories are live")
+
     def append(self, dataset, weights=None) -> None:
         """Add the complete episodes of ``dataset`` (DSRL keys, host or device) to a store built with capacities: the
         chunk goes through ``process_sequence_dataset`` as a dataset of its own (with the store's ``cost_reverse``) and

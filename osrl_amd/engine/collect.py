@@ -9,6 +9,10 @@ episode and step, and the discounted sums.  What comes out goes into ``ReplaySto
 Noise: ``a = clip(pi(s) + sigma_e * eps)``.  ``eps`` is Philox4x32-10 keyed by (seed, episode id = base_seed + e, the
 episode's own step, action column) on stream ``_EPS_STREAM``: it does not depend on E, on the graph chunking or on which
 replay a step falls in.  Seed, gamma and sigma live in device memory, so a captured graph follows them.
+
+``CDTCollector`` is the same for CDT (``CDTTrainer.collect_targets``): a ``CDTBatchedRollout`` whose step after the
+transformer forward is the one launch ``osrl_cdt_collect`` (csrc/cdt_collect.hip) instead of pick, environment, push and
+cursor, with per-episode targets and, with ``sample=True``, the Gaussian head's own standard deviation as the noise scale.
 """
 from __future__ import annotations
 
@@ -19,7 +23,7 @@ import torch
 
 from .. import _lib as L
 from .core import cur_stream
-from .rollout import _CHUNK, BatchedRollout
+from .rollout import _CHUNK, BatchedRollout, CDTBatchedRollout
 
 _EPS_STREAM = 13   # Philox stream id of the exploration noise (11 / 12: the BCQL decode noise of rollout.py / fqe.py)
 _GUARD_ROWS = 4    # sentinel rows before and after every table (``Collector.guards_intact``)
@@ -47,14 +51,23 @@ def merge_datasets(datasets: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.T
     return {k: torch.cat([d[k] for d in datasets], 0) for k in datasets[0]}
 
 
-class Collector(BatchedRollout):
-    """``run`` = all ``venv.E`` episodes to completion, recorded.  The tables are this object's (sized at the first run,
-    again when the episode length changes); ``run`` hands out copies, or appends the tables to a store (``into=``)."""
+def _check_replay_store(into, state_dim: int, action_dim: int) -> None:
+    """``into=`` a ``ReplayStore``: ValueError unless it grows, draws uniformly and has the environment's widths."""
+    if into is None:
+        return
+    if getattr(into, "capacity", None) is None:
+        raise ValueError("collect(into=): the store is fixed, build it with capacity=")
+    if into.weighted:
+        raise ValueError("collect(into=): the store draws by weight; collect a dataset and append it with sample_prob=")
+    into.check_append_widths(observations=state_dim, next_observations=state_dim, actions=action_dim)
 
-    def __init__(self, model, venv, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None,
-                 seed: int = 0, z: Optional[torch.Tensor] = None, use_graph: bool = True):
-        super().__init__(model, venv, kind, cost_scale, extra_obs, seed, z, use_graph)
-        dev, E = self.obs.device, venv.E
+
+class _Tables:
+    """What the two collectors share: the guarded tables, the ``osrl_collect_t`` descriptor, and the noise parameters
+    that live in device memory.  The host class provides ``venv``, ``model``, ``obs`` and ``seed``."""
+
+    def _init_tables(self) -> None:
+        dev, E = self.obs.device, self.venv.E
         self.disc = torch.zeros(E, 4, dtype=torch.float32, device=dev)
         self.sigma = torch.zeros(E, dtype=torch.float32, device=dev)
         self.gamma = torch.ones(1, dtype=torch.float32, device=dev)
@@ -89,44 +102,17 @@ class Collector(BatchedRollout):
             ok = ok & (i[:_GUARD_ROWS * w] == _SENTINEL).all() & (i[-_GUARD_ROWS * w:] == _SENTINEL).all()
         return bool(ok.item())
 
-    def body(self) -> None:
-        act = self.policy()
-        rec = self.rec
-        if self._eps is not None:  # an eager run with injected noise: the same descriptor with the tensor's address
-            rec = L.CollectT.from_buffer_copy(self.rec)
-            rec.eps_in = self._eps.data_ptr()
-        v = self.venv
-        L.check(L.load().osrl_env_collect(self.env_c, rec, act.data_ptr(), v.state.data_ptr(), self.obs.data_ptr(),
-                                          self.obs.stride(0), v.acc.data_ptr(), v.E, cur_stream()), "osrl_env_collect")
+    def _rec_now(self) -> L.CollectT:
+        """The descriptor of the step being issued: in an eager run with injected noise, a copy with the tensor's address."""
+        if self._eps is None:
+            return self.rec
+        rec = L.CollectT.from_buffer_copy(self.rec)
+        rec.eps_in = self._eps.data_ptr()
+        return rec
 
-    def _snapshot(self):
-        return super()._snapshot() + [(self.disc, self.disc.clone())]
-
-    @torch.no_grad()
-    def run(self, noise_std=0.0, gamma: Optional[float] = None, seed: Optional[int] = None,
-            noise: Optional[torch.Tensor] = None, into=None) -> Collected:
-        """``noise_std``: one sigma for all episodes or ``[E]`` of them.  ``gamma`` (None: 1.0) weighs the discounted
-        sums.  ``seed`` (None: keep the current one) keys the noise drawn on device.  ``noise``: ``[L, E, action_dim]``
-        injected instead (the run is then eager); rows of episodes whose sigma is 0 are not read.  ``into``: a
-        ``ReplayStore`` built with ``capacity`` -- the tables go straight into ``into.append`` (one device copy per
-        table, no clone) and the result's ``dataset`` is None; a store whose widths differ from the environment's
-        (BC multi-task appends the cost return to the observations) is a ValueError before the run."""
-        v, m = self.venv, self.model
-        E, ad, dev = v.E, m.action_dim, self.obs.device
-        if into is not None:
-            if getattr(into, "capacity", None) is None:
-                raise ValueError("collect(into=): the store is fixed, build it with capacity=")
-            if into.weighted:
-                raise ValueError("collect(into=): the store draws by weight; collect a dataset and append it with sample_prob=")
-            into.check_append_widths(observations=v.state_dim, next_observations=v.state_dim, actions=ad)
-        steps = min(m.episode_len, v.episode_len or m.episode_len)
-        if self.env_c.episode_len != steps or self.rec is None:  # descriptors are by-value arguments of the graph
-            self.env_c.episode_len, self.graph = steps, None
-            self._alloc(steps)
-        if seed is not None and int(seed) != self.seed:
-            self.seed = int(seed)
-            if self.kind == "bcql" and not self.z_fixed:
-                self.graph = None  # (the decode noise's seed is a by-value argument of its launch)
+    def _load_noise(self, noise_std, gamma: Optional[float], noise, steps: int) -> Optional[torch.Tensor]:
+        """sigma, gamma and ``self.seed`` into their device words; the injected noise checked and on the device."""
+        E, ad, dev = self.venv.E, self.model.action_dim, self.obs.device
         if (noise_std.dim() if torch.is_tensor(noise_std) else np.ndim(noise_std)) == 0:
             self.sigma.fill_(float(noise_std))
         else:
@@ -142,6 +128,58 @@ class Collector(BatchedRollout):
             if tuple(noise.shape) != (steps, E, ad):
                 raise ValueError(f"noise must be [{steps}, {E}, {ad}] (episode_len, episodes, action_dim), "
                                  f"got {tuple(noise.shape)}")
+        return noise
+
+    def _finish(self, into) -> Collected:
+        """The tables into the store or out as copies, and the per-episode sums (the one host sync of the run)."""
+        if into is not None:  # (every episode starts at an initial state: the chunk's is_init is right by construction)
+            into.append(self.tables)
+            data = None
+        else:
+            data = {k: t.clone() for k, t in self.tables.items()}
+        tot = torch.cat([self.venv.acc, self.disc], 1).cpu().numpy().astype(np.float64)
+        return Collected(data, tot[:, 0], tot[:, 1], tot[:, 2], tot[:, 4], tot[:, 5])
+
+
+class Collector(_Tables, BatchedRollout):
+    """``run`` = all ``venv.E`` episodes to completion, recorded.  The tables are this object's (sized at the first run,
+    again when the episode length changes); ``run`` hands out copies, or appends the tables to a store (``into=``)."""
+
+    def __init__(self, model, venv, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None,
+                 seed: int = 0, z: Optional[torch.Tensor] = None, use_graph: bool = True):
+        super().__init__(model, venv, kind, cost_scale, extra_obs, seed, z, use_graph)
+        self._init_tables()
+
+    def body(self) -> None:
+        act = self.policy()
+        v = self.venv
+        L.check(L.load().osrl_env_collect(self.env_c, self._rec_now(), act.data_ptr(), v.state.data_ptr(),
+                                          self.obs.data_ptr(), self.obs.stride(0), v.acc.data_ptr(), v.E, cur_stream()),
+                "osrl_env_collect")
+
+    def _snapshot(self):
+        return super()._snapshot() + [(self.disc, self.disc.clone())]
+
+    @torch.no_grad()
+    def run(self, noise_std=0.0, gamma: Optional[float] = None, seed: Optional[int] = None,
+            noise: Optional[torch.Tensor] = None, into=None) -> Collected:
+        """``noise_std``: one sigma for all episodes or ``[E]`` of them.  ``gamma`` (None: 1.0) weighs the discounted
+        sums.  ``seed`` (None: keep the current one) keys the noise drawn on device.  ``noise``: ``[L, E, action_dim]``
+        injected instead (the run is then eager); rows of episodes whose sigma is 0 are not read.  ``into``: a
+        ``ReplayStore`` built with ``capacity`` -- the tables go straight into ``into.append`` (one device copy per
+        table, no clone) and the result's ``dataset`` is None; a store whose widths differ from the environment's
+        (BC multi-task appends the cost return to the observations) is a ValueError before the run."""
+        v, m = self.venv, self.model
+        _check_replay_store(into, v.state_dim, m.action_dim)
+        steps = min(m.episode_len, v.episode_len or m.episode_len)
+        if self.env_c.episode_len != steps or self.rec is None:  # descriptors are by-value arguments of the graph
+            self.env_c.episode_len, self.graph = steps, None
+            self._alloc(steps)
+        if seed is not None and int(seed) != self.seed:
+            self.seed = int(seed)
+            if self.kind == "bcql" and not self.z_fixed:
+                self.graph = None  # (the decode noise's seed is a by-value argument of its launch)
+        noise = self._load_noise(noise_std, gamma, noise, steps)
         v.reset(self.obs)
         self.disc.zero_()
         self.disc[:, 2] = 1.0
@@ -158,13 +196,105 @@ class Collector(BatchedRollout):
                     self.body()
         finally:
             self._eps = None
-        if into is not None:  # (every episode starts at an initial state: the chunk's is_init is right by construction)
-            into.append(self.tables)
-            data = None
+        return self._finish(into)
+
+
+class CDTCollector(_Tables, CDTBatchedRollout):
+    """``CDTBatchedRollout`` recorded: the same transformer forward on the same window buffers, then ONE launch
+    (csrc/cdt_collect.hip ``osrl_cdt_collect``) where the evaluating rollout issues pick, environment, push and cursor.
+    Every episode advances by its own step count ``acc[e][2]``; without noise the run is ``CDTBatchedRollout.run``'s bit
+    for bit.  ``acc[:, 1]`` and the discounted cost sum carry ``cost_scale`` here (``Collected``'s contract); the window's
+    costs-to-go carry it as the evaluating rollout's do, with ``cost_reverse``."""
+
+    def __init__(self, model, venv, cost_scale: float = 1.0, cost_reverse: bool = False, seed: int = 0,
+                 use_graph: bool = True):
+        super().__init__(model, venv, cost_scale, cost_reverse, use_graph)
+        self.seed, self.sample = int(seed), False
+        self.env_c = venv.desc(model.episode_len, self.cost_scale)
+        self._init_tables()
+        e, w = self.eng, L.CdtWindowT()
+        w.states, w.actions, w.returns, w.costs_to_go = (e.states.data_ptr(), e.actions.data_ptr(), e.returns.data_ptr(),
+                                                         e.ctg.data_ptr())
+        w.time_steps, w.mask, w.head = e.time_steps.data_ptr(), e.mask.data_ptr(), e.head.data_ptr()
+        w.seq_len, w.head_width, w.sample = model.seq_len, e.head.shape[1], 0
+        w.cost_reverse, w.cost_scale = int(self.cost_reverse), self.cost_scale
+        self.win = w
+
+    def body(self) -> None:
+        v = self.venv
+        self.eng.forward(train=False)
+        L.check(L.load().osrl_cdt_collect(self.env_c, self._rec_now(), self.win, v.state.data_ptr(), v.acc.data_ptr(), v.E,
+                                          cur_stream()), "osrl_cdt_collect")
+
+    @torch.no_grad()
+    def run(self, target_return, target_cost, noise_std=0.0, sample: bool = False, gamma: Optional[float] = None,
+            seed: Optional[int] = None, noise: Optional[torch.Tensor] = None, into=None) -> Collected:
+        """The targets as ``CDTBatchedRollout.run`` takes them; ``noise_std``, ``gamma``, ``seed``, ``noise`` as
+        ``Collector.run`` does.  ``sample``: the noise scale is the Gaussian head's own ``exp(log_std)`` at the position
+        acted from (a by-value flag of the launch: switching it recaptures, nothing else does).  ``into``: a
+        ``SequenceStore`` built with capacities (``check_append`` refuses, before the run, a store that cannot take ``E``
+        trajectories of ``episode_len`` rows) or a ``ReplayStore`` under ``Collector.run``'s rules."""
+        from ..common.replay import SequenceStore
+        v, m = self.venv, self.model
+        check_sampling(m, sample, noise_std)
+        target_return, target_cost = self._targets(target_return, target_cost)
+        steps = min(m.episode_len, v.episode_len or m.episode_len)
+        if isinstance(into, SequenceStore):
+            into.check_append(v.E, v.E * steps, observations=v.state_dim, actions=m.action_dim)
         else:
-            data = {k: t.clone() for k, t in self.tables.items()}
-        tot = torch.cat([v.acc, self.disc], 1).cpu().numpy().astype(np.float64)  # the one host sync of the run
-        return Collected(data, tot[:, 0], tot[:, 1], tot[:, 2], tot[:, 4], tot[:, 5])
+            _check_replay_store(into, v.state_dim, m.action_dim)
+        if self.env_c.episode_len != steps or self.rec is None:  # descriptors are by-value arguments of the graph
+            self.env_c.episode_len, self.graph = steps, None
+            self._alloc(steps)
+        if bool(sample) != self.sample:
+            self.sample, self.graph = bool(sample), None
+            self.win.sample = int(self.sample)
+        if seed is not None:
+            self.seed = int(seed)
+        noise = self._load_noise(noise_std, gamma, noise, steps)
+        m.repack()
+        graph = self.use_graph and noise is None
+        if graph and self.graph is None:
+            self._capture()  # runs the body on scratch state; the reset below starts the real run
+        self._reset(target_return, target_cost)
+        self.disc.zero_()
+        self.disc[:, 2] = 1.0
+        self._eps = noise
+        try:
+            if graph:
+                for _ in range((steps + _CHUNK - 1) // _CHUNK):
+                    self.graph.replay()
+            else:
+                for _ in range(steps):
+                    self.body()
+        finally:
+            self._eps = None
+        return self._finish(into)
+
+
+def check_sampling(model, sample: bool, noise_std) -> None:
+    """``sample=True`` needs a Gaussian head and excludes ``noise_std``: ValueError otherwise (host work only)."""
+    if not sample:
+        return
+    if not model.stochastic:
+        raise ValueError("sample=True draws from the Gaussian head's own standard deviation: the model was built with "
+                         "stochastic=False")
+    nz = bool((noise_std != 0).any()) if torch.is_tensor(noise_std) else bool(np.any(np.asarray(noise_std) != 0))
+    if nz:
+        raise ValueError("sample=True and a non-zero noise_std are two noise scales for one action: pass one of them")
+
+
+def collect_cdt_batched(trainer, **run_kw) -> Collected:
+    """``CDTTrainer.collect_targets`` on a ``VecSyntheticSafeEnv``; the collector is cached on the trainer like
+    ``collect_batched``'s."""
+    venv = trainer.env
+    key = (id(venv), float(trainer.cost_scale), bool(trainer.cost_reverse))
+    co = getattr(trainer, "_collector", None)
+    if co is None or co[0] != key:
+        co = (key, CDTCollector(trainer.model, venv, trainer.cost_scale, trainer.cost_reverse,
+                                use_graph=getattr(trainer, "use_graph", True)))
+        trainer._collector = co
+    return co[1].run(**run_kw)
 
 
 def collect_batched(trainer, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None, **run_kw) -> Collected:

@@ -173,16 +173,35 @@ class CDTBatchedRollout:
         self.env_c = venv.desc(m.episode_len, 1.0)  # acc[:,1] = raw cost sum, as cdt.py:513 accumulates it
         self.graph: Optional[torch.cuda.CUDAGraph] = None
 
-    def _reset(self, target_return: float, target_cost: float) -> None:
+    def _targets(self, target_return, target_cost):
+        """Each target as a float (one for all episodes) or as ``[E]`` fp32 values on the device; any other length is a
+        ValueError."""
+        out = []
+        for name, x in (("target_return", target_return), ("target_cost", target_cost)):
+            if (x.dim() if torch.is_tensor(x) else np.ndim(x)) == 0:
+                out.append(float(x))
+                continue
+            v = torch.as_tensor(x, dtype=torch.float32).reshape(-1)
+            if v.numel() != self.venv.E:
+                raise ValueError(f"{name} holds {v.numel()} values, the environment {self.venv.E} episodes")
+            out.append(v.to(self.obs.device))
+        return out
+
+    def _reset(self, target_return, target_cost) -> None:
+        """The targets are what ``_targets`` returns.  They are data of the window buffers, not launch arguments: a
+        captured graph follows them."""
         e = self.eng
         self.venv.reset(self.obs)
         for t in (e.states, e.actions, e.returns, e.ctg, e.mask, e.costs):
             t.zero_()
         e.time_steps.zero_()
         e.states[:, 0].copy_(self.obs)
-        e.returns[:, 0] = float(target_return)
-        e.ctg[:, 0] = float(target_cost)
-        e.episode_cost.fill_(float(target_cost))  # the cost-prefix token's input (cdt.py:459,481)
+        e.returns[:, 0] = target_return
+        e.ctg[:, 0] = target_cost
+        if torch.is_tensor(target_cost):
+            e.episode_cost.copy_(target_cost)
+        else:
+            e.episode_cost.fill_(target_cost)  # the cost-prefix token's input (cdt.py:459,481)
         e.mask[:, 0] = 1.0
         self.cursor.zero_()
 
@@ -217,9 +236,11 @@ class CDTBatchedRollout:
         self.graph = gr
 
     @torch.no_grad()
-    def run(self, target_return: float, target_cost: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """Per-episode (return, raw cost sum, length)."""
+    def run(self, target_return, target_cost) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Per-episode (return, raw cost sum, length).  Each target is one value for all episodes or ``E`` of them
+        (episode ``e`` conditions on its own pair); a wrong length is a ValueError before anything runs."""
         m = self.model
+        target_return, target_cost = self._targets(target_return, target_cost)
         steps = min(m.episode_len, self.venv.episode_len or m.episode_len)
         if self.env_c.episode_len != steps:
             self.env_c.episode_len, self.graph = steps, None
