@@ -12,6 +12,7 @@ Common sub-expressions the reference recomputes are evaluated once (exact, not a
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -23,42 +24,70 @@ from . import plan as P
 from ._step import PipelinedReplay, StepEngine, VaePhase
 from .core import Branches, DwPlan, MlpRun, StepState, concat_nets
 
-# Plan choices that depend on the shape live in engine/plan.py (cpq_plan: head tails, dW tiles, the all-CU VAE launches;
-# the measurements behind each rule are in DESIGN_LOG.md).  What is left here are lab switches of the plan's STRUCTURE:
-# Data parallel, round 5: the two collectives that feed only the side branch (the VAE gradient's all-reduce, the KL values'
-# all-gather) issued from a branch of their own / the side branch instead of the main one.  Order-safe without a second
-# communicator: every rank ISSUES the four collectives in the same program order and RCCL executes them on its own stream
-# in that order; only the streams that wait for them differ.  Built, verified (world-2 / world-8 in-process capture tests)
-# and measured with forced data parallelism on one rank: SLOWER, C2 1991 vs 2021 steps/s, C4 2065 vs 2213
-# (gpurun_out/r5d): the extra branch and the collectives' fork / join edges on the side queue cost the graph executor more
-# than the two 17 us collectives they take off the main chain.  Default "0" = round 4's placement (all four on the main
-# branch).
-DP_SIDE_COLL = P.knob("OSRL_DP_SIDE_COLL", "0", "DP: VAE all-reduce / KL gather issued off the main branch") == "1"
-# (pipelined graphs: where the next prologue sits and whether the steps of a graph are joined are plan fields --
-# engine/plan.py pipe_prologue / pipe_no_join; the lab switch OSRL_PIPE_DUAL=side keeps round 6's side-branch dual step)
-PIPE_DUAL_SIDE = P.knob("OSRL_PIPE_DUAL", "auto") == "side"
-# (no-join graphs with plan.vae_adam_side: the edge from the VAE's optimizer step on step k's side branch to the main chain,
-# whose next VAE phase reads what it wrote -- in front of the actor group's Adam, the last launch of step k's main chain
-# (actor) / at the head of step k+1's main chain (next) / none (0: lab only -- the second session's graphs, ordered by ~100 us
-# of timing slack and nothing else))
-# (no-join graphs with the VAE's optimizer step on the MAIN chain -- C4: step k's N*B-row encoder launch, late on its side branch,
-# reads the weights step k+1's optimizer step rewrites ~280 us later, and the main chain's first edge from that branch is the
-# wait for the action draws BEHIND that optimizer step.  1: an event behind the encoder launch, waited for in front of the
-# optimizer step; 0 (lab): unordered, as the second session's graphs were)
-VAE_WAR_EDGE = P.knob("OSRL_VAE_WAR_EDGE", "actor", "no-join graphs, VAE Adam on the main chain: ordered behind the previous step's "
-                      "N*B-row encoder launch by an edge to that step's actor Adam (actor) / to the VAE Adam itself (vae) / by "
-                      "timing slack (0, lab)")
-VAE_ADAM_EDGE = P.knob("OSRL_VAE_ADAM_EDGE", "actor", "no-join graphs, VAE Adam on the side branch: its edge to the main chain "
-                       "in front of the actor group's Adam (actor) / at the head of the next step (next) / none (0, lab)")
-# (lab, no-join graphs: the actor group's dW + Adam of step k at the head of step k+1's side branch instead of the tail of
-# step k's main chain -- nothing on the main chain reads the actor before the next trunk launch, which is on that branch)
-PIPE_ACTOR_SIDE = P.knob("OSRL_PIPE_ACTOR", "main", "no-join pipelined steps: the actor group's dW + Adam on the main chain (main) / "
-                         "carried to the head of the next step's side branch (side)") == "side"
+# Plan choices that depend on the shape live in engine/plan.py (cpq_plan: head tails, dW tiles, the all-CU VAE launches, where
+# a pipelined graph's next prologue sits and whether its steps are joined; the measurements behind each rule are in
+# DESIGN_LOG.md, and so are the placements that were measured, lost and left the code).  Left here: the two lab switches the
+# ordering test (tests/test_gpu_pipeline.py) takes its control from -- a no-join graph built WITHOUT one of the two edges that
+# order step k's side branch against step k+1's main chain:
+#   * plan.vae_adam_side (C2): the VAE's optimizer step runs on step k's side branch, and step k+1's VAE phase, on the main
+#     chain, reads what it wrote;
+#   * the VAE's optimizer step on the main chain (C4): step k's N*B-row encoder launch, late on its side branch, reads the
+#     weights step k+1's optimizer step rewrites ~280 us later, and the main chain's first edge from that branch is the wait
+#     for the action draws BEHIND that optimizer step.
+# Either way an event behind the launch on the side branch, waited for in front of the actor group's Adam, the last launch of
+# step k's main chain.  Read per capture, not per process (_edge): the test builds graphs with and without them.
+P.knob("OSRL_VAE_ADAM_EDGE", "actor", "no-join graphs, VAE Adam on the side branch: its edge to the main chain in front of "
+       "the actor group's Adam (actor) / none: ordered by timing slack (0, lab)")
+P.knob("OSRL_VAE_WAR_EDGE", "actor", "no-join graphs, VAE Adam on the main chain: ordered behind the previous step's N*B-row "
+       "encoder launch by an edge to that step's actor Adam (actor) / by timing slack (0, lab)")
+
+
+def _edge(name: str) -> bool:
+    v = P.knob(name, "actor")
+    if v not in ("actor", "0"):
+        raise ValueError(f"{name}={v!r}: actor or 0")
+    return v == "actor"
+
+
+@dataclass
+class Carry:
+    """What step k of a pipelined graph leaves for step k+1 (``prev.carry``).  Step k+1 consumes it at the head of its two
+    streams: the prologue event in ``_main_vae``, the pending launches in ``_side_first``."""
+    dual: bool = False               # step k's dual step is still to be issued (``dual_step()`` clears it)
+    polyak: bool = False             # ... and, in front of it, the cost critics' target update (plan.ood_rows)
+    ev_prologue: Optional[torch.cuda.Event] = None  # behind step k+1's prologue on step k's side branch, where nothing else ...
+    prologue_covered: bool = False   # ... orders it: here the main chain's wait for the critic's Adam is behind it already
+
+
+@dataclass
+class _Step:
+    """One issue of the body: what is decided once at its top (``_decide``) and what one phase hands to a later one."""
+    par: Branches
+    device_noise: bool
+    nxt: Optional["CPQEngine"]       # pipelined graphs: the twin engine the NEXT step runs on
+    carried: Optional["CPQEngine"]   # ... and the previous step's, where that step left its ``carry`` to this one
+    no_join: bool                    # the steps of this graph are not joined (plan.pipe_no_join)
+    vae_adam_side: bool              # the VAE's optimizer step at the head of the side branch's second half
+    vae_dw_side: bool                # ... and the VAE group's dW launch in front of it
+    adam_edge: bool                  # OSRL_VAE_ADAM_EDGE / OSRL_VAE_WAR_EDGE (above)
+    war_edge: bool
+    ev_vae: Optional[torch.cuda.Event] = None       # main: behind the VAE phase (plan.ood_rows_late: behind the cost critics' dW)
+    ev_next2: Optional[torch.cuda.Event] = None     # side: behind the action draws
+    ev_critic: Optional[torch.cuda.Event] = None    # side: behind the critic's Adam, its last reader of cost_critic_old
+    ev_kl: Optional[torch.cuda.Event] = None        # side, data parallel: behind the KL rows
+    ev_vae_adam: Optional[torch.cuda.Event] = None  # side, the edges above: behind the VAE's Adam / the N*B-row encoder launch,
+    ev_enc_ood: Optional[torch.cuda.Event] = None   # ... for THIS step's actor phase (nothing of them is left to the next step)
+    head_obs: Optional[torch.Tensor] = None         # the actor's head on ``obs`` (the unseeded actor phase's backward reads it)
+    qc_s: Optional[torch.Tensor] = None             # the target cost critics on the N*B rows (None with plan.ood_rows)
+
+
 STAT_KEYS = ["loss/loss_vae", "loss/critic_loss", "loss/cost_critic_loss", "loss/alpha_value", "loss/actor_loss"]
 NOISE_KEYS = ["eps_vae", "eps_next_c", "eps_next_cc", "eps_ood", "eps_actor"]
 
 
 class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
+    # (one side branch.  Data parallel: it holds no collective -- every rank issues its RCCL calls from the capture stream,
+    # in one order)
     SIDE_STREAMS, PICK_FASTEST, DP_CAPTURE = 1, True, True
 
     def __init__(self, model, batch_size: int, rows_global: int = 0, seed: int = 0, dist=None):
@@ -74,18 +103,12 @@ class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
         f = dict(dtype=torch.float32, device=dev)
         z = lambda *s: torch.zeros(*s, **f)  # noqa: E731
         self.st = StepState(dev, STAT_KEYS)
-        self._prologue_covered = False
-        self._actor_pending = False
-        self._polyak_pending = False
-        self._ev_prologue = None    # (pipelined graphs, plan.pipe_no_join: event behind the next step's prologue)
+        self.carry = Carry()  # (pipelined graphs: what this engine's last step left to the next step of its graph)
         # (tests/test_gpu_pipeline.py test_unjoined_graphs_are_ordered_by_edges_not_by_timing: a spin kernel of this many
         # cycles on the side branch in front of its second half -- VAE Adam / N*B-row encoder launch -- of every step)
         self._stress_spin = int(P.knob("OSRL_STRESS_SPIN_CYCLES", "0", "tests: spin kernel (cycles) in front of the side branch's second half"))
         self._stress_at = P.knob("OSRL_STRESS_SPIN_AT", "second", "tests: ... (second) / at the head of the side branch (head) / at the "
                                  "head of the main chain (main)")
-        self._ev_vae_adam = None    # (... and behind this step's VAE Adam where that runs on the side branch)
-        self._ev_enc_ood = None     # (... and behind this step's N*B-row encoder launch where the VAE Adam runs on the main chain)
-        self._dual_pending = False  # (this step's dual step is still to be issued by the next step of the graph)
         nq, nqc = m.num_q, m.num_qc
         c_hidden = [int(l.out_features) for l in m.cost_critic_old.q_nets[0] if isinstance(l, torch.nn.Linear)][:-1]
         pl = self.plan = P.cpq_plan(od, ad, B, int(m.vae_hidden_sizes), N, seeds=G.SEEDS and G.VAE_TAILS and max(nq, nqc) <= 4
@@ -250,14 +273,6 @@ class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
              prologue_done: bool = False, prev: Optional["CPQEngine"] = None) -> None:
         """One step, single GPU or data parallel (``self.dist``): the launch plan below.
 
-        ``nxt`` / ``prologue_done`` (engine/pipeline.py, several steps per graph): the NEXT step's prologue -- into the
-        twin engine ``nxt``'s buffers and step state -- is issued at the tail of THIS step's side branch, between the N*B-row
-        encoder launch and the single-workgroup OOD statistic (C2: +1.2 .. +2.6 % against +0.5 % behind it, gpurun_out/r6e);
-        the next step is then run with ``prologue_done=True``.  (Measured and removed, round 6: the two streams SWAPPING roles from step to step, so that
-        no cross-queue edge stands in front of the next VAE phase -- the graph executor then opens a third queue for the
-        swapped main chain, C2 1884-2062 vs 2300-2325 steps/s, and a replay of that graph segfaulted in the runtime:
-        profiles/r6_timeline_4step_swap_c2.txt, DESIGN_LOG round 6.)
-
         What the plan exploits (cpq.py:155-201): everything the OOD penalty is made of -- the N*B sampled actions, the
         target cost critics on them, the VAE encoder on them, the KL rows, their 0.75-quantile, ``qc_ood`` -- sits
         under ``torch.no_grad()`` and enters the cost-critic loss as ``- exp(log_alpha) * (qc_ood.mean() - thres)``,
@@ -271,95 +286,106 @@ class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
 
         The side branch joins at the END of the step.  Ordering constraints kept by events: the cost-critic Adam also
         Polyak-updates ``cost_critic_old``, so it waits for the side branch's last reader of the targets; the encoder on
-        the N*B rows waits for the VAE's Adam; the actor phase waits for the critic's Adam."""
-        dp = self.dist
-        m, st, nz, B = self.model, self.st, self.noise, self.B
-        od, ad, Lz, N = m.state_dim, m.action_dim, m.latent_dim, m.sample_action_num
-        nq, nqc, rg = m.num_q, m.num_qc, self.rows_global
+        the N*B rows waits for the VAE's Adam; the actor phase waits for the critic's Adam.
+
+        ``nxt`` / ``prologue_done`` / ``prev`` (engine/pipeline.py, several steps per graph): the NEXT step's prologue --
+        into the twin engine ``nxt``'s buffers and step state -- is issued on THIS step's side branch (``_next_prologue``)
+        and the next step is run with ``prologue_done=True``; what else this step leaves to the next one is ``self.carry``,
+        which the next step reads through ``prev``."""
         par = par or Branches(False)
-        assert nxt is None or dp is None, "pipelined steps are a single-GPU plan"
+        assert nxt is None or self.dist is None, "pipelined steps are a single-GPU plan"
         if not prologue_done:
             self.prologue(device_noise)
+        s = self._decide(device_noise, par, nxt, prev)
+        self._main_vae(s)
+        self._side_first(s)
+        self._main_cost(s)
+        self._side_second(s)
+        self._main_actor(s)
+        self._tail(s)
+
+    def _decide(self, device_noise: bool, par: Branches, nxt, prev) -> _Step:
+        """Every plan flag of one issue, once."""
+        pl, single = self.plan, self.dist is None
         # plan.pipe_no_join (pipelined graphs): the steps of a graph are not joined.  The main chain of step k+1 waits for
-        # its prologue only (issued on step k's side branch: ``_ev_prologue``), and step k's dual step runs at the head of
-        # step k+1's side branch, right behind the fork -- the one place of the side branch that already has an edge from
+        # its prologue only (issued on step k's side branch: ``carry.ev_prologue``), and step k's dual step runs at the head
+        # of step k+1's side branch, right behind the fork -- the one place of the side branch that already has an edge from
         # the END of step k's main chain (so both halves of the logged cost loss are there) without a new mid-chain edge.
-        no_join = self.plan.pipe_no_join and par.enabled and dp is None
-        # (read per capture, not per process: the ordering test builds graphs with and without these edges)
-        VAE_ADAM_EDGE, VAE_WAR_EDGE = P.knob("OSRL_VAE_ADAM_EDGE", "actor"), P.knob("OSRL_VAE_WAR_EDGE", "actor")
-        carried = prev if (no_join and prev is not None and prev._dual_pending) else None
-        self._ev_prologue, self._prologue_covered = None, False
-        if carried is not None and carried._ev_prologue is not None:
-            par.wait(carried._ev_prologue)
-        if carried is not None and carried._ev_vae_adam is not None and VAE_ADAM_EDGE == "next":
-            par.wait(carried._ev_vae_adam)  # (this step's VAE phase reads what that optimizer step wrote)
-        self._ev_vae_adam = None
+        no_join = pl.pipe_no_join and par.enabled and single
+        # (single GPU, plan.vae_adam_side: the VAE's optimizer step at the head of the side branch's second half, in
+        # front of its only reader, instead of on the main chain -- +0.7 % at C2, DESIGN_LOG round 5)
+        vae_adam_side = single and par.enabled and pl.vae_adam_side and not self.p_vae.can_fuse_adam()
+        adam_edge, war_edge = _edge("OSRL_VAE_ADAM_EDGE"), _edge("OSRL_VAE_WAR_EDGE")
+        # (plan.vae_dw_side: the VAE group's dW too -- its only reader is that optimizer step.  Not where the lab switch
+        # OSRL_VAE_ADAM_EDGE=0 takes away the edge that orders it in a no-join graph)
+        vae_dw_side = bool(vae_adam_side and self.ood_rows and pl.vae_dw_side and not (no_join and not adam_edge))
+        carried = prev if (no_join and prev is not None and prev.carry.dual) else None
+        self.carry = Carry()
+        return _Step(par, device_noise, nxt, carried, no_join, vae_adam_side, vae_dw_side, adam_edge, war_edge)
+
+    def _next_prologue(self, s: _Step, site: str) -> None:
+        """Pipelined graphs: the next step's prologue (its minibatch + noise + tick, 14 us) at ``site`` of this step's side
+        branch, if that is where the plan puts it (plan.pipe_prologue; engine/plan.py has the measurements: where it sits
+        decides how the N*B-row launch behind it lines up with the main chain's all-CU VAE launches).  Called at every
+        candidate site, in issue order: "head" = first on the branch (the N*B-row launch behind it starts ~14 us later against
+        the main chain's VAE launches), "critic" = in front of the critic phase, "early" = in front of the OOD statistic (C2:
+        +1.2 .. +2.6 % against +0.5 % behind it, DESIGN_LOG round 6)."""
+        if s.nxt is None or self.plan.pipe_prologue != site:
+            return
+        s.nxt.prologue(s.device_noise)
+        if site in ("head", "critic"):
+            # the main chain waits for this branch's critic Adam (ev_critic), which is behind this launch: the next step's
+            # first launch needs no edge of its own from this branch
+            self.carry.prologue_covered = True
+        elif self.ood_rows:
+            # "early" with plan.ood_rows: issued, but NO event for the next step -- the step then has nothing to carry on
+            # (_tail) and stays JOINED, whatever plan.pipe_no_join says.  (A no-join graph with this placement would be a
+            # graph form of its own; the pinned plans put the prologue at "head" / "critic" wherever rows are selected.)
+            pass
+        else:
+            self.carry.ev_prologue = s.par.mark(0)
+
+    def _main_vae(self, s: _Step) -> None:
+        """Main: what the previous step left for this chain, the fork, vae_loss (cpq.py:125-135), and where the VAE group's
+        dW and Adam go."""
+        par = s.par
+        if s.carried is not None:
+            par.wait(s.carried.carry.ev_prologue)
         par.fork(0)
         if self._stress_spin and par.enabled and self._stress_at == "main":
             torch.cuda._sleep(self._stress_spin)  # (tests: the main chain arrives late)
-        # ---- main: vae_loss  (cpq.py:125-135)
-        sd = self.seeds
-        head = self._vae_phase(sd)
-        if dp is not None and par.enabled and len(par.side) > 1 and DP_SIDE_COLL:
-            # data parallel, round 5: nothing on the main branch reads the VAE's parameters in this step (its only reader
-            # is the N*B-row encoder launch of the side branch), so the gradient's all-reduce and the optimizer step
-            # leave the critical chain: a short branch of their own behind the dW launch.  The collective is still ISSUED
-            # here, first of the step's four, on every rank (RCCL runs them on its own stream in issue order)
+        self._vae_phase(self.seeds)
+        if not s.vae_adam_side:
+            self._optim("vae", self.p_vae, 0.0)
+        elif not s.vae_dw_side:  # (the optimizer step alone goes to the side branch's second half)
             self._pr("vae_dw", 0)
             self.p_vae.launch()
             self._pr("vae_dw", 1)
-            par.fork(1)
-            with par.on(1):
-                self._update("vae", 0.0)
-                ev_vae = par.mark(1)
-        else:
-            # (single GPU, plan.vae_adam_side: the VAE's optimizer step at the head of the side branch's second half, in
-            # front of its only reader, instead of on the main chain -- +0.7 % at C2, DESIGN_LOG round 5)
-            vae_adam_side = dp is None and par.enabled and self.plan.vae_adam_side and not self.p_vae.can_fuse_adam()
-            # (plan.vae_dw_side: the VAE group's dW too -- its only reader is that optimizer step; issued in the side branch's
-            # second half below.  Not where the lab switch OSRL_VAE_ADAM_EDGE=0 takes away the edge that orders it in a no-join
-            # graph)
-            vae_dw_side = vae_adam_side and self.ood_rows and self.plan.vae_dw_side and not (no_join and VAE_ADAM_EDGE == "0")
-            if vae_dw_side:
-                pass
-            elif vae_adam_side:
-                self._pr("vae_dw", 0)
-                self.p_vae.launch()
-                self._pr("vae_dw", 1)
-            else:
-                if carried is not None and carried._ev_enc_ood is not None:  # (OSRL_VAE_WAR_EDGE=vae)
-                    par.wait(carried._ev_enc_ood)  # (the previous step's last reader of the weights this step rewrites)
-                    carried._ev_enc_ood = None
-                self._optim("vae", self.p_vae, 0.0)
-            ev_vae = torch.cuda.Event() if par.enabled else None
-            if ev_vae is not None:
-                ev_vae.record()
+        if par.enabled:
+            s.ev_vae = torch.cuda.Event()
+            s.ev_vae.record()
 
-        # ---- side branch: the actor forwards + heads, the target cost critics on the N*B rows (beside the VAE phase,
-        # where the capped tile loop disturbs the chain least), then the critic phase
+    def _side_first(self, s: _Step) -> None:
+        """Side, first half: what the previous step carried over, the actor forwards + heads, the target cost critics on the
+        N*B rows (beside the VAE phase, where the capped tile loop disturbs the chain least), then the critic phase."""
+        m, st, nz, B, par, sd = self.model, self.st, self.noise, self.B, s.par, self.seeds
+        ad, N, nq, nqc = m.action_dim, m.sample_action_num, m.num_q, m.num_qc
         with par.on(0):
             if self._stress_spin and par.enabled and self._stress_at == "head":
                 torch.cuda._sleep(self._stress_spin)  # (tests: the side branch arrives late)
-            if carried is not None and carried._polyak_pending:
-                # (plan.ood_rows in a no-join graph: the cost critics' target update of the previous step -- behind its last
-                # reader, the forward on the selected rows at that step's side-branch tail, and behind its main chain's
-                # optimizer step, which this branch's fork waited for; in front of this step's readers of the targets: the
-                # critic phase on this branch, the cost phase on the main chain through its wait for the action draws)
-                m.groups["cost_critic"].polyak_step(m.tau)
-                carried._polyak_pending = False
-            if carried is not None and carried._actor_pending:
-                carried._optim("actor", carried.p_actor, m.tau)
-                carried._actor_pending = False
-            if carried is not None:
+            if s.carried is not None:
+                if s.carried.carry.polyak:
+                    # (plan.ood_rows in a no-join graph: the cost critics' target update of the previous step -- behind its last
+                    # reader, the forward on the selected rows at that step's side-branch tail, and behind its main chain's
+                    # optimizer step, which this branch's fork waited for; in front of this step's readers of the targets: the
+                    # critic phase on this branch, the cost phase on the main chain through its wait for the action draws)
+                    m.groups["cost_critic"].polyak_step(m.tau)
+                    s.carried.carry.polyak = False
                 # (created HERE, behind the main chain's VAE launches: the graph executor keeps the FIRST-created successor
                 # of a node on that node's queue -- issued right at the fork, the dual step was the first successor of the
                 # previous step's last Adam and the two chains swapped queues at every boundary: 2155 vs 2320 steps/s)
-                carried.dual_step()
-            if nxt is not None and self.plan.pipe_prologue == "head":
-                # (lab: the next step's prologue FIRST on this branch -- covered by ev_critic like "critic", and the N*B-row
-                # launch behind it starts ~14 us later against the main chain's VAE launches)
-                nxt.prologue(device_noise)
-                self._prologue_covered = True
+                s.carried.dual_step()
+            self._next_prologue(s, "head")
             if self.plan.head_tails:
                 # every action draw of the step (cpq.py:141 a_next, :159 a_next2, :164-176 the N OOD draws, :209 the
                 # actor-phase sample) by the actor trunks' own forward launch, from its LDS-resident head tiles: four
@@ -370,27 +396,22 @@ class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
                                       a2=self.a_next),
                     other_tail=G.gauss_tail(ad, m.max_action, eps2=nz["eps_actor"], a2=self.a_pi, tanh2=self.tanh_u,
                                             eps_ood=nz["eps_ood"], n_samples=N, sampled=self.sampled))
-                head_next, head_obs = hn[0], ho[0]
-                ev_next2 = par.mark(0)
+                s.head_obs = ho[0]
+                s.ev_next2 = par.mark(0)
             else:
                 hn, ho = self.r_actor_next.forward_with((self.nobs,), self.r_actor_obs, (self.obs,))
-                head_next, head_obs = hn[0], ho[0]
+                head_next, s.head_obs = hn[0], ho[0]
                 G.gauss_head(head_next, nz["eps_next_cc"], B, ad, m.max_action, a=self.a_next2)
-                ev_next2 = par.mark(0)
+                s.ev_next2 = par.mark(0)
                 G.gauss_head(head_next, nz["eps_next_c"], B, ad, m.max_action, a=self.a_next)
-                G.gauss_ood_sample(head_obs, nz["eps_ood"], N, B, ad, self.sampled)
+                G.gauss_ood_sample(s.head_obs, nz["eps_ood"], N, B, ad, self.sampled)
                 # the actor-phase sample (cpq.py:209) needs only this forward and its own noise
-                G.gauss_head(head_obs, nz["eps_actor"], B, ad, m.max_action, a=self.a_pi, tanh_u=self.tanh_u)
-            qc_s = None
+                G.gauss_head(s.head_obs, nz["eps_actor"], B, ad, m.max_action, a=self.a_pi, tanh_u=self.tanh_u)
             if not self.ood_rows:  # (plan.ood_rows: this forward runs BEHIND the KL quantile, on the rows that pass it)
                 self._pr("costold_ood", 0)
-                qc_s = self.r_costold_ood.forward(self.obs, self.sampled, map0=L.MAP_MOD, div0=B, share_k16=self.pre_cost)
+                s.qc_s = self.r_costold_ood.forward(self.obs, self.sampled, map0=L.MAP_MOD, div0=B, share_k16=self.pre_cost)
                 self._pr("costold_ood", 1)
-            if nxt is not None and self.plan.pipe_prologue == "critic":
-                # the next step's prologue HERE: the main chain waits for this branch's critic Adam below (ev_critic), so
-                # the next step's first launch needs no edge of its own from this branch
-                nxt.prologue(device_noise)
-                self._prologue_covered = True
+            self._next_prologue(s, "critic")
             # critic_loss (cpq.py:137-153)
             self._pr("critic_fwd", 0)
             y_old, q = self.r_old_next.forward_with((self.nobs, self.a_next), self.r_critic, (self.obs, self.act))
@@ -399,40 +420,38 @@ class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
                 self.r_critic.backward_dz(seed=sd["critic"])
             else:
                 G.cpq_critic_loss(y_old[:nq], nq, y_old[nq:], nqc, q, nq, self.rew, self.done, B, m.gamma, m.q_thres,
-                                  rg, self.dq, st.stat_ptr("loss/critic_loss"))
+                                  self.rows_global, self.dq, st.stat_ptr("loss/critic_loss"))
                 self.r_critic.backward_dz()
-            if dp is None:
+            if self.dist is None:
                 self._optim("critic", self.p_critic, m.tau)
             else:  # collectives stay on the capture stream (same order on every rank): reduced + stepped over there
                 self.p_critic.launch()
                 if P.knob("OSRL_DP_SIDE_REDUCE", "1", "DP: the critic group's slab sum on the side branch") == "1":
-                    dp.reduce_local(m.groups["critic"])  # the per-rank slab sum is no collective: off the main chain
-            ev_critic = par.mark(0)  # also: the side branch's last reader of cost_critic_old is enqueued
+                    self.dist.reduce_local(m.groups["critic"])  # the per-rank slab sum is no collective: off the main chain
+            s.ev_critic = par.mark(0)  # also: the side branch's last reader of cost_critic_old is enqueued
 
-        # ---- main: cost_critic_loss (cpq.py:155-201), the part with a gradient: Bellman MSE of the online cost critics
-        par.wait(ev_next2)
+    def _main_cost(self, s: _Step) -> None:
+        """Main: cost_critic_loss (cpq.py:155-201), the part with a gradient: Bellman MSE of the online cost critics."""
+        m, st, B, par, sd, dp = self.model, self.st, self.B, s.par, self.seeds, self.dist
+        nqc = m.num_qc
+        par.wait(s.ev_next2)
         qc_old_next, qc = self.r_costold_next.forward_with((self.nobs, self.a_next2), self.r_cost, (self.obs, self.act))
         if sd is not None:
             self.r_cost.backward_dz(seed=sd["cost"])
         else:
-            G.cpq_cost_loss(qc_old_next, nqc, qc, nqc, None, self.cost, B, m.gamma, m.qc_thres, m.alpha_lr, rg, 1.0,
-                            None, self.dqc, st.stat_ptr("loss/cost_critic_loss"))
+            G.cpq_cost_loss(qc_old_next, nqc, qc, nqc, None, self.cost, B, m.gamma, m.qc_thres, m.alpha_lr, self.rows_global,
+                            1.0, None, self.dqc, st.stat_ptr("loss/cost_critic_loss"))
             self.r_cost.backward_dz()
-        dual_on_side = nxt is not None and PIPE_DUAL_SIDE and par.enabled and not no_join
-        ev_cost_stat = None
-        if dual_on_side:  # (lab: the Bellman part of the logged cost loss is complete here)
-            ev_cost_stat = torch.cuda.Event()
-            ev_cost_stat.record()
         fuse_cost = dp is None and self.p_cost.can_fuse_adam() and not self.ood_rows
         if not fuse_cost:
             self.p_cost.launch()
-        if self.ood_rows and par.enabled and ev_vae is not None and self.plan.ood_rows_late:
+        if self.ood_rows and s.ev_vae is not None and self.plan.ood_rows_late:
             # (plan.ood_rows_late: without the N*B-row cost-critic launch in its first half the side branch reaches the VAE's
             # Adam + the N*B-row encoder launch ~70 us earlier -- beside THIS dW launch, whose 384 small workgroups then take
             # 70 instead of 25 us, gpurun_out/r6oodrows3; the side branch waits for this point instead of the VAE's dW)
-            ev_vae = torch.cuda.Event()
-            ev_vae.record()
-        par.wait(ev_critic)  # Adam + Polyak of this group rewrites cost_critic_old: after its readers on the side branch
+            s.ev_vae = torch.cuda.Event()
+            s.ev_vae.record()
+        par.wait(s.ev_critic)  # Adam + Polyak of this group rewrites cost_critic_old: after its readers on the side branch
         if fuse_cost:
             self.p_cost.launch_adam(m._lrs["cost_critic"], st.ptr, tau=m.tau)
         elif self.ood_rows:
@@ -444,17 +463,21 @@ class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
         else:
             self._update_critics_dp()
 
-        # ---- side branch, second half: the OOD statistic with the UPDATED vae
-        # (round 4, measured and dropped: letting this launch wait for the cost critics' optimizer step instead -- so that it
-        # does not stretch the cost phase it runs beside -- is SLOWER, 2161-2165 vs 2242-2244 steps/s at C2, 2257 vs 2285 at
-        # C4: the step is throughput-bound, the N*B-row work has to start as early as its inputs allow)
+    def _side_second(self, s: _Step) -> None:
+        """Side, second half: the OOD statistic with the UPDATED vae -- the VAE's dW and Adam where the plan puts them here,
+        the encoder on the N*B rows, the statistic in its three forms.
+        (Round 4, measured and dropped: letting this half wait for the cost critics' optimizer step instead -- so that it
+        does not stretch the cost phase it runs beside -- is SLOWER, 2161-2165 vs 2242-2244 steps/s at C2, 2257 vs 2285 at
+        C4: the step is throughput-bound, the N*B-row work has to start as early as its inputs allow.)"""
+        m, B, par = self.model, self.B, s.par
+        N, nqc, rg = m.sample_action_num, m.num_qc, self.rows_global
+        carries_on = s.no_join and s.nxt is not None
         with par.on(0):
-            if ev_vae is not None:
-                par.side[0].wait_event(ev_vae)
+            par.wait(s.ev_vae)
             if self._stress_spin and par.enabled and self._stress_at == "second":
                 torch.cuda._sleep(self._stress_spin)  # (tests: this branch's second half arrives LATE; results must not move)
-            if dp is None and par.enabled and self.plan.vae_adam_side and not self.p_vae.can_fuse_adam():
-                if vae_dw_side:
+            if s.vae_adam_side:
+                if s.vae_dw_side:
                     # (engine/plan.py vae_dw_side.  Reads the activation and dZ buffers the main chain's VAE phase wrote: this
                     # branch waited for ev_vae above, recorded behind that phase -- or, with plan.ood_rows_late, further down
                     # the same chain)
@@ -462,38 +485,29 @@ class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
                     self.p_vae.launch()
                     self._pr("vae_dw", 1)
                 self._update("vae", 0.0)  # (engine/plan.py vae_adam_side: off the main chain, in front of its only reader)
-                if no_join and nxt is not None and VAE_ADAM_EDGE != "0":
+                if carries_on and s.adam_edge:
                     # ... of THIS step: the next step's VAE phase, on the main chain, reads it too, and steps that are not
                     # joined need an edge of their own for that.  With plan.vae_dw_side the same edge carries a second
                     # dependency: the next step's VAE phase REWRITES the activation and dZ buffers this step's dW launch
                     # reads.  The optimizer step follows the dW launch on this stream and the event is recorded behind it, so
                     # whoever waits for it is behind both (a joined step, or the last step of a graph, has the join for that).
-                    self._ev_vae_adam = par.mark(0)
+                    s.ev_vae_adam = par.mark(0)
             self._pr("enc_ood", 0)  # bench.py: HIP events around the dominant launch as it runs inside the step
             # (the KL rows of cpq.py:178-182 by the encoder launch itself: OSRL_TAIL_VAE_KL)
-            self.r_enc_ood.forward(self.obs, self.sampled, map0=L.MAP_MOD, div0=B, tail=G.vae_kl_tail(Lz, self.kl),
+            self.r_enc_ood.forward(self.obs, self.sampled, map0=L.MAP_MOD, div0=B, tail=G.vae_kl_tail(m.latent_dim, self.kl),
                                    share_k16=self.pre_enc)
             self._pr("enc_ood", 1)
-            if no_join and nxt is not None and VAE_WAR_EDGE != "0" and not (self.plan.vae_adam_side and not self.p_vae.can_fuse_adam()):
-                self._ev_enc_ood = par.mark(0)  # (the next step's VAE Adam, on the main chain, rewrites what this launch read)
-            kl_on_side = dp is not None and par.enabled and DP_SIDE_COLL
-            if kl_on_side:
-                # the batch-GLOBAL quantile (cpq.py:183 over all world * N * B values): gather, selection and masked mean
-                # stay on this branch -- the third collective of the step in issue order on every rank (behind [critic |
-                # cost-critic gradients], which the main branch issued above); the main branch never waits for it
-                kl_all = dp.all_gather_concat(self.kl)
-                dp.quantile_select(kl_all, 0.75, self.quant)
-                G.cpq_ood_mean(qc_s, nqc, self.kl, self.quant, N, B, rg, self.ood_mean)
-            elif dp is not None:
-                ev_kl = par.mark(0)
+            if carries_on and s.war_edge and not s.vae_adam_side:
+                s.ev_enc_ood = par.mark(0)  # (the next step's VAE Adam, on the main chain, rewrites what this launch read)
+            self._next_prologue(s, "early")
+            if self.dist is not None:  # (the batch-GLOBAL quantile: gathered from the main branch, _main_actor)
+                s.ev_kl = par.mark(0)
             elif self.ood_rows:
                 # cpq.py:183-184 as a row SET: quantile + ascending list of the rows with KL >= quantile in one
                 # single-workgroup launch, the target cost critics on those rows (a quarter of N*B; the grid is sized for
                 # all of them, workgroups past the count leave at once), their sum.  The cost critics' target update follows
                 # on the MAIN branch behind the join (a main -> side edge this late makes the graph executor serialise the
                 # actor phase behind this branch: 500 vs 428 us per step, profiles/r6_ood_rows_timeline_side_polyak.txt).
-                if nxt is not None and self.plan.pipe_prologue == "early":
-                    nxt.prologue(device_noise)
                 G.cpq_ood_select(self.kl, N * B, 0.75, self.quant, self.ood_list, self.ood_count)
                 self._pr("costold_ood", 0)
                 qc_sel = self.r_costold_ood.forward(self.obs, self.sampled, map0=L.MAP_MOD, div0=B, row_list=self.ood_list,
@@ -501,91 +515,75 @@ class CPQEngine(PipelinedReplay, VaePhase, StepEngine):
                 self._pr("costold_ood", 1)
                 G.cpq_ood_sum(qc_sel, nqc, N * B, self.ood_count, 1.0 / (float(N) * float(rg if rg > 0 else B)), self.ood_mean)
             elif N * B <= 32768:  # quantile + masked mean in one single-workgroup launch (keys in registers)
-                if nxt is not None and self.plan.pipe_prologue == "early":
-                    nxt.prologue(device_noise)
-                    self._ev_prologue = par.mark(0)
-                G.cpq_ood_stat(qc_s, nqc, self.kl, 0.75, N, B, rg, self.quant, self.ood_mean)
+                G.cpq_ood_stat(s.qc_s, nqc, self.kl, 0.75, N, B, rg, self.quant, self.ood_mean)
             else:
                 G.quantile(self.kl, N * B, 0.75, self.quant)
-                G.cpq_ood_mean(qc_s, nqc, self.kl, self.quant, N, B, rg, self.ood_mean)
-            if dual_on_side:
-                par.side[0].wait_event(ev_cost_stat)
-                G.cpq_alpha_step(self.ood_mean, m.qc_thres, m.alpha_lr, 1.0, m.log_alpha, st.stat_ptr("loss/cost_critic_loss"))
-            if nxt is not None and self.plan.pipe_prologue == "side":
-                nxt.prologue(device_noise)  # (pipelined: the next step's minibatch + noise + tick, off the main chain)
+                G.cpq_ood_mean(s.qc_s, nqc, self.kl, self.quant, N, B, rg, self.ood_mean)
 
-        # ---- main: actor_loss  (cpq.py:203-222): needs the updated critic (side branch: this stream waited for
-        # ev_critic above -- a second wait on it is one more graph edge, ~6 us on the chain) and cost critic (here)
+    def _main_actor(self, s: _Step) -> None:
+        """Main: actor_loss (cpq.py:203-222): needs the updated critic (side branch: this stream waited for ev_critic in the
+        cost phase -- a second wait on it is one more graph edge, ~6 us on the chain) and cost critic (this chain)."""
+        m, st, nz, B, par, sd, dp = self.model, self.st, self.noise, self.B, s.par, self.seeds, self.dist
+        ad, N, nq, nqc, rg = m.action_dim, m.sample_action_num, m.num_q, m.num_qc, self.rows_global
         self._pr("actor_phase_fwd", 0)
         y = self.r_pi_q.forward(self.obs, self.a_pi)
         self._pr("actor_phase_fwd", 1)
-        if dp is not None and not kl_on_side:
-            # (OSRL_DP_SIDE_COLL=0 or no branches: round 4's placement)
+        if dp is not None:
             # the batch-GLOBAL quantile (cpq.py:183 over all world * N * B values): the gather is a collective, so it
             # is issued from the capture stream -- here, behind the actor phase's forward launch, which is about when
             # the side branch has its KL rows (profiles/r2_timeline.txt: 397 us vs 405 us); the selection and the
             # masked mean go back to the side branch and run beside the actor phase's backward
-            par.wait(ev_kl)
+            par.wait(s.ev_kl)
             kl_all = dp.all_gather_concat(self.kl)
-            if P.knob("OSRL_DP_SIDE_QUANT", "1", "DP: quantile + masked mean back on the side branch") == "1":
-                ev_g = torch.cuda.Event() if par.enabled else None
-                if ev_g is not None:
-                    ev_g.record()
-                with par.on(0):
-                    if ev_g is not None:
-                        par.side[0].wait_event(ev_g)
-                    dp.quantile_select(kl_all, 0.75, self.quant)
-                    G.cpq_ood_mean(qc_s, nqc, self.kl, self.quant, N, B, rg, self.ood_mean)
-            else:
+            ev_g = torch.cuda.Event() if par.enabled else None
+            if ev_g is not None:
+                ev_g.record()
+            with par.on(0):
+                par.wait(ev_g)
                 dp.quantile_select(kl_all, 0.75, self.quant)
-                G.cpq_ood_mean(qc_s, nqc, self.kl, self.quant, N, B, rg, self.ood_mean)
+                G.cpq_ood_mean(s.qc_s, nqc, self.kl, self.quant, N, B, rg, self.ood_mean)
         if sd is not None:
             self.r_pi_q.backward_dz(seed=sd["actor"])
             self.r_actor_obs.backward_dz(seed=sd["head"])
         else:
             G.cpq_actor_loss(y[:nq], nq, y[nq:], nqc, B, m.q_thres, rg, self.dq_pi, st.stat_ptr("loss/actor_loss"))
             self.r_pi_q.backward_dz()
-            G.gauss_head_bwd(head_obs, nz["eps_actor"], self.tanh_u, self.r_pi_q.dx, nq, B, ad, m.max_action,
+            G.gauss_head_bwd(s.head_obs, nz["eps_actor"], self.tanh_u, self.r_pi_q.dx, nq, B, ad, m.max_action,
                              self.dhead_actor)
             self.r_actor_obs.backward_dz()
         if dp is None:
-            carry = no_join and nxt is not None and (self._ev_prologue is not None or self._prologue_covered)
-            if self._ev_vae_adam is not None and (VAE_ADAM_EDGE == "actor" or not carry):
-                par.wait(self._ev_vae_adam)
-                self._ev_vae_adam = None
-            if self._ev_enc_ood is not None and (VAE_WAR_EDGE == "actor" or not carry):
-                par.wait(self._ev_enc_ood)
-                self._ev_enc_ood = None
-            if carry and PIPE_ACTOR_SIDE:
-                self._actor_pending = True  # (the next step issues it on its side branch, behind its fork)
-            else:
-                self._optim("actor", self.p_actor, m.tau)
-            if carry:
-                self._dual_pending = True  # (the next step of this graph runs it: dual_step())
-                self._polyak_pending = bool(self.ood_rows)
-                return
-            par.join(0)
-        else:  # actor gradient, the per-rank partial statistics and the partial qc_ood mean in one collective
+            # (no-join graphs: the two edges from this step's side branch, in front of the last launch of this chain)
+            par.wait(s.ev_vae_adam)
+            par.wait(s.ev_enc_ood)
+            self._optim("actor", self.p_actor, m.tau)
+        else:  # (its gradient is reduced behind the join: _tail)
             self.p_actor.launch()
-            par.join(0)
+
+    def _tail(self, s: _Step) -> None:
+        """Carry on into the next step of a no-join graph, or join the side branch and run the dual step."""
+        m, st, c = self.model, self.st, self.carry
+        if s.no_join and s.nxt is not None and (c.ev_prologue is not None or c.prologue_covered):
+            c.dual = True  # (the next step of this graph runs it: dual_step())
+            c.polyak = bool(self.ood_rows)
+            return
+        s.par.join(0)
+        if self.dist is not None:  # actor gradient, the per-rank partial statistics and the partial qc_ood mean in one collective
             self._update("actor", m.tau, extra=[st.stats, self.ood_mean])
         # dual step + the OOD term of the logged loss (cpq.py:186-195): after the join, so that the side branch has no
         # incoming edge from the main branch after the VAE's Adam (the graph executor keeps two linear chains); under
         # data parallelism the statistics are already the global ones here, so the global term is added once
         if self.ood_rows:  # the cost critics' target update: behind its last reader (side branch, joined above)
             m.groups["cost_critic"].polyak_step(m.tau)
-        if not dual_on_side:
-            self.dual_step()
-        if nxt is not None and self.plan.pipe_prologue == "main":
-            nxt.prologue(device_noise)  # (lab: the pipelined graph with the next prologue on the main chain, as a control)
+        self.dual_step()
 
     def dual_step(self) -> None:
         """log_alpha's ascent + the OOD term of this step's logged cost loss (cpq.py:186-195), on the current stream."""
         m = self.model
         G.cpq_alpha_step(self.ood_mean, m.qc_thres, m.alpha_lr, 1.0, m.log_alpha, self.st.stat_ptr("loss/cost_critic_loss"))
-        self._dual_pending = False
+        self.carry.dual = False
 
     def _branches(self) -> Branches:
-        # data parallel: the side branch holds no collective (the critic group's all-reduce + Adam run on the
-        # capture stream after the join), so every rank issues its RCCL calls in the same order on one stream
+        # (data parallel: a second stream that no launch uses since OSRL_DP_SIDE_COLL left -- kept, because the streams that
+        # exist at capture decide the branch -> hardware-queue mapping (core.pick_fastest): without it C2 under forced data
+        # parallelism 2149-2152 against 2154-2159 steps/s, with it 2165-2174 against 2160-2168, profiles/cpq_body_ab.json)
         return Branches(self.parallel_branches, 2 if self.dist is not None else 1)

@@ -147,11 +147,15 @@ def cpq_plan(od: int, ad: int, B: int, vae_hidden: int, N: int, seeds: bool = Tr
     side_long = not head_tails and B >= 1024
     spg = int(knob("OSRL_PIPE_STEPS", "0", "train steps per pipelined graph (0 = by rule)")) or \
         (20 if B >= 1024 else 1)
-    dual = knob("OSRL_PIPE_DUAL", "auto", "pipelined steps: the dual step behind the join (main) / on the side branch behind the "
-                "OOD statistic (side) / at the head of the NEXT step's side branch, no join between the steps of a graph (next)")
-    pro = knob("OSRL_PIPE_PROLOGUE", "auto", "pipelined steps: the next step's prologue behind the OOD statistic (side) / in "
-               "front of it (early) / on the main chain (main) / on the side branch in front of the critic phase (critic) or "
-               "first on it (head): the main chain's wait for the critic's Adam then covers it")
+    dual = knob("OSRL_PIPE_DUAL", "auto", "pipelined steps: the dual step behind the join (main) / at the head of the NEXT "
+                "step's side branch, no join between the steps of a graph (next) / auto = by rule")
+    pro = knob("OSRL_PIPE_PROLOGUE", "auto", "pipelined steps: the next step's prologue on this step's side branch in front of "
+               "the OOD statistic (early) / in front of the critic phase (critic) or first on it (head): the main chain's wait "
+               "for the critic's Adam then covers it / auto = by rule")
+    if dual not in ("auto", "next", "main"):
+        raise ValueError(f"OSRL_PIPE_DUAL={dual!r}: auto, next or main")
+    if pro not in ("auto", "early", "critic", "head"):  # (side / main were measured and retired: DESIGN_LOG)
+        raise ValueError(f"OSRL_PIPE_PROLOGUE={pro!r}: auto, early, critic or head")
     no_join = B >= 1024 if dual == "auto" else dual == "next"
     pro = ("critic" if side_long else "head" if B >= 1024 else "early") if pro == "auto" else pro
     ood_tile = int(knob("OSRL_OOD_TILE", "80", "row tile of the N*B-row launches (0 = 32-row tile loop)"))

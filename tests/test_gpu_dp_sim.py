@@ -336,22 +336,13 @@ def make_green(hub, rank):
     return GreenDist()
 
 
-# (side_coll=True -- OSRL_DP_SIDE_COLL=1, the round-5 variant that issues two of the four collectives off the main branch
-# -- is NOT in the list: the real 1-rank RCCL capture of it runs (bench.py under OSRL_FORCE_DP=1, gpurun_out/r5d), but THIS
-# in-process capture of W replicas x 3 streams + the hub's stream segfaults inside the HIP runtime's capture_end
-# (gpurun_out/r5e), which would take the whole GPU test session down.  The variant is off by default: measured slower.)
-@pytest.mark.parametrize("algo,W,side_coll", [("cpq", 2, False), ("cpq_c4", 2, False), ("cpq_c4_w8", 8, False)])
-def test_captured_data_parallel_graph_equals_concatenated_batch(algo, W, side_coll, monkeypatch):
+@pytest.mark.parametrize("algo,W", [("cpq", 2), ("cpq_c4", 2), ("cpq_c4_w8", 8)])
+def test_captured_data_parallel_graph_equals_concatenated_batch(algo, W):
     """W replicas' data-parallel step bodies in ONE captured graph == the single-device step on the concatenated batch.
     W = 8 is BASELINE.json's C4 job shape (8 x 2048 rows at (17, 6)): rows_global = 16384, the batch-global quantile
     over 163840 gathered KL values runs as the grid select inside the step; the single-device run's step-1 statistics
     are refereed by the fp64 oracle."""
-    from osrl_amd.engine import cpq as cpq_engine
     from osrl_amd.engine.core import Branches
-    # side_coll (round 5, OSRL_DP_SIDE_COLL=1; not the default plan: measured slower on one rank, DESIGN_LOG round 5): the
-    # VAE gradient's all-reduce issued from a branch of its own and the KL gather from the side branch -- same results,
-    # and the hub asserts at every exchange that all replicas are at the SAME collective (one total order)
-    monkeypatch.setattr(cpq_engine, "DP_SIDE_COLL", bool(side_coll))
     c = DP_CASES[algo]
     B, N = c.B, c.N
     Bl = B // W
@@ -395,8 +386,8 @@ def test_captured_data_parallel_graph_equals_concatenated_batch(algo, W, side_co
             raise
     torch.cuda.synchronize()
     # ONE total order of the step's collectives, the same on every replica (asserted per exchange in _Hub.run): the VAE
-    # gradient first (issued from its own branch), [critic | cost-critic] + the partial qc_ood mean... as all_reduce calls,
-    # the KL gather third (issued from the side branch), [actor | statistics | qc_ood] last
+    # gradient first, [critic | cost-critic] + the partial qc_ood mean... as all_reduce calls, the KL gather third,
+    # [actor | statistics | qc_ood] last -- all four issued from the main branch
     kinds = [k for k, _ in hub.log]
     assert kinds.count("all_gather") == 1 and kinds[0] == "all_reduce" and kinds[-1] == "all_reduce", kinds
     assert kinds.index("all_gather") > 1, kinds  # behind the VAE's and the critic groups' all-reduces

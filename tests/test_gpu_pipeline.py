@@ -131,7 +131,7 @@ def test_unjoined_pipelined_steps_equal_one_step_graph_replays(name, spg, total,
     torch.cuda.synchronize()
     pipe = e_b._pipe
     assert isinstance(pipe, PipelinedSteps) and pipe.n == spg and pipe.e[1].plan == e_b.plan
-    assert not pipe.e[0]._dual_pending and not pipe.e[1]._dual_pending, "a graph's last step runs its own dual step"
+    assert not pipe.e[0].carry.dual and not pipe.e[1].carry.dual, "a graph's last step runs its own dual step"
     assert e_b.st.device_step() == total
     got = _state(m_b, e_b)
     for k in ref:
@@ -144,6 +144,50 @@ def test_unjoined_pipelined_steps_equal_one_step_graph_replays(name, spg, total,
     many = e_b.st.read_stats_many(range(1, total + 1))
     for s in range(1, total + 1):
         assert many[s] == [ref_stats[s - 1][k] for k in e_b.st.keys], f"read_stats_many, step {s}"
+
+
+def test_grid_quantile_graph_issues_the_early_prologue(monkeypatch):
+    """``pipe_prologue == "early"`` where the OOD statistic is the grid quantile + masked mean (N * B = 40960 > 32768, no
+    row set at these widths): that form of the statistic had no prologue site, so step k+1 of a graph ran on step k's
+    minibatch and noise without a tick.  The joined graph (the simplest one) of 2 steps, twice, against four replays of
+    the one-step graph: state and every step's statistics bit-equal."""
+    from cases import Case
+    from osrl_amd.common.replay import ReplayStore, synthetic_transitions
+    c = Case("grid_early", "cpq", od=17, ad=6, B=4096, hidden=[64, 64], vae_hidden=96, N=10, steps=1, episode_len=1000)
+    monkeypatch.setenv("OSRL_LAB", "1")
+    monkeypatch.setenv("OSRL_PIPE_DUAL", "main")
+    monkeypatch.setenv("OSRL_PIPE_PROLOGUE", "early")
+
+    def build():
+        m, tr, lg = build_gpu(c, stats_mode="none", use_graph=True)
+        eng = m.engine(c.B)
+        eng.attach_replay(ReplayStore(synthetic_transitions(8192, c.od, c.ad, seed=7, max_action=c.max_action),
+                                      torch.device(DEV), reward_scale=0.1, cost_scale=1.0, seed=3))
+        assert not eng.plan.pipe_no_join and eng.plan.pipe_prologue == "early" and not eng.ood_rows and c.N * c.B > 32768
+        return m, eng
+
+    total = 4
+    m_a, e_a = build()
+    for _ in range(total):
+        e_a.step_replay(True)
+    torch.cuda.synchronize()
+    ref = _state(m_a, e_a)
+    ref_stats = [e_a.st.read_stats(s) for s in range(1, total + 1)]
+    del m_a, e_a
+    torch.cuda.empty_cache()
+
+    m_b, e_b = build()
+    e_b.steps_replay(total, steps_per_graph=2)
+    torch.cuda.synchronize()
+    assert e_b._pipe.graph is not None and e_b.st.device_step() == total
+    got = _state(m_b, e_b)
+    for k in ref:
+        assert torch.equal(ref[k], got[k]), f"grid quantile, early prologue: {k} differs after {total} steps " \
+                                             f"(max |d| = {(ref[k] - got[k]).abs().max().item():.3e})"
+    for s in range(1, total + 1):
+        st = e_b.st.read_stats(s)
+        for k, v in ref_stats[s - 1].items():
+            assert st[k] == v or (np.isnan(st[k]) and np.isnan(v)), f"grid quantile, early prologue: statistic {k} of step {s}: {st[k]} vs {v}"
 
 
 def _spin_cycles(us):

@@ -213,6 +213,20 @@ def test_plan_rows_are_pinned(monkeypatch):
     assert P.cpq_plan(76, 2, 2048, 400, 10).vae_adam_side and not P.cpq_plan(17, 6, 2048, 400, 10).vae_adam_side
 
 
+@pytest.mark.parametrize("value", ["side", "main"])
+def test_retired_prologue_placements_are_refused(value, monkeypatch):
+    """``OSRL_PIPE_PROLOGUE=side`` / ``=main`` were measured, lost and left the step body (DESIGN_LOG): a lab run that
+    still asks for one is told so instead of silently getting another placement; the three that stay are taken."""
+    from osrl_amd.engine import plan as P
+    monkeypatch.setenv("OSRL_LAB", "1")
+    monkeypatch.setenv("OSRL_PIPE_PROLOGUE", value)
+    with pytest.raises(ValueError, match="OSRL_PIPE_PROLOGUE"):
+        P.cpq_plan(76, 2, 2048, 400, 10)
+    for kept in ("early", "critic", "head"):
+        monkeypatch.setenv("OSRL_PIPE_PROLOGUE", kept)
+        assert P.cpq_plan(76, 2, 2048, 400, 10).pipe_prologue == kept
+
+
 def test_every_graph_capture_is_thread_local():
     """A process that holds an RCCL process group has a watchdog thread polling events; in torch's default (global) capture
     mode its queries make an open capture fail and abort the process (DESIGN_LOG round 5).  Every capture of the package
