@@ -1196,6 +1196,19 @@ int osrl_policy_io_n(void* handle, float** obs, float** noise, float** act, floa
 /* one environment step of every active slot; returns after all actions have been published.  deterministic / host_noise
  * as osrl_policy_act; noise drawn on the device is Philox keyed by (seed, meta[e][0], meta[e][1], element) only. */
 int osrl_policy_act_n(void* handle, int32_t deterministic, int32_t host_noise, uint64_t seed, void* stream);
+/* The same call with the EXPLORATION TAIL of the recording collectors on the action of every active slot e (all three
+ * kinds; a_pi is the action osrl_policy_act_n publishes -- for GAUSS the scaled, post-tanh one):
+ *   a = clip(a_pi + sigma[e] * eps, +-max_action)      (v = fmaf(sigma, eps, v), then the clip: osrl_env_collect's)
+ * sigma[e] == 0 publishes exactly a_pi's bits, and eps is not read.  eps is row e of the pinned eps [n_env, act_dim] when
+ * host_eps = 1 (injected noise: tests, replays), otherwise the draw osrl_env_collect documents:
+ *   word (k & 3) of philox4x32_10(counter = {meta[e][0] = episode id, meta[e][1] = step, k >> 2, stream 13},
+ *   key = explore_seed) through the library's word -> N(0,1) map,
+ * so a run on host environments records the noise the device collector draws for the same (seed, episode, step, column).
+ * This stream is apart from the one `seed` keys (GAUSS's own eps, BCQ's z: untouched).  sigma and eps are the caller's to
+ * write (HOST pointers into the handle's pinned block, from _explore_io_n); osrl_policy_act_n reads neither. */
+int osrl_policy_explore_io_n(void* handle, float** sigma, float** eps);
+int osrl_policy_act_explore_n(void* handle, int32_t deterministic, int32_t host_noise, uint64_t seed,
+                              uint64_t explore_seed, int32_t host_eps, void* stream);
 int osrl_policy_destroy_n(void* handle);
 
 /* ---- CDT act latency path (cdt_act.hip) ----------------------------------------------------------------------
@@ -1272,6 +1285,20 @@ int osrl_cdt_policy_window_n(void* handle, int32_t env, float* states, float* ac
 int osrl_cdt_policy_step_slots(void* handle, const int32_t* mode, int32_t host_action, void* stream);
 /* t [n_env]: the timestep of each episode's newest window entry, -1 = never started */
 int osrl_cdt_policy_timesteps(void* handle, int32_t* t);
+/* _step_slots with the EXPLORATION TAIL of osrl_cdt_collect on the action of every episode e that runs:
+ *   a = clip(mu + s * eps, +-max_action);  s = sample ? exp(log_std) of the head row (no log-std bounds; needs
+ *         head_out_width >= 2 * action_dim, else -1) : sigma[e];  s == 0 gives clip(mu) exactly and eps is not read;
+ *   eps = row e of the pinned eps [n_env, action_dim] when host_eps = 1, otherwise word (k & 3) of philox4x32_10(counter
+ *         = {episode_id[e], the episode's own timestep, k >> 2, stream 13}, key = explore_seed) through the library's word
+ *         -> N(0,1) map: osrl_env_collect's draw.
+ * mu is the evaluating call's bits (the log_std columns are computed in a pass of their own with the mean's k-split), and
+ * the action TAKEN is what the window records at the next step (unless host_action = 1 overrides it).  With sample = 1
+ * the head row (mu | log_std) of every episode that ran is written to head [n_env, 2 * action_dim], for the caller's
+ * behaviour log-probabilities.  sigma [n_env], eps, episode_id [n_env] and head are HOST pointers into the handle's pinned
+ * block (_explore_io); the calls without the tail read none of them. */
+int osrl_cdt_policy_explore_io(void* handle, float** sigma, float** eps, int32_t** episode_id, float** head);
+int osrl_cdt_policy_step_slots_explore(void* handle, const int32_t* mode, int32_t host_action, int32_t sample,
+                                       uint64_t explore_seed, int32_t host_eps, void* stream);
 
 /* ---- data-parallel exchanges through IPC-mapped device buffers (ipc.hip, round 6; nothing to mirror in the reference: it
  * has no distributed code).  What the ranks of a data-parallel step exchange (flat

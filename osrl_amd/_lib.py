@@ -233,6 +233,8 @@ PROTOTYPES = {
     "osrl_policy_io_n": [_vp, _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float)),
                          _P(_P(C.c_int32)), _P(_P(C.c_int32))],
     "osrl_policy_act_n": [_vp, _i32, _i32, _u64, _vp],
+    "osrl_policy_explore_io_n": [_vp, _P(_P(C.c_float)), _P(_P(C.c_float))],
+    "osrl_policy_act_explore_n": [_vp, _i32, _i32, _u64, _u64, _i32, _vp],
     "osrl_policy_destroy_n": [_vp],
     "osrl_cdt_policy_create": [_P(CdtPolicyT), _P(CdtLayerT), _P(C.c_void_p)],
     "osrl_cdt_policy_io": [_vp, _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_float))],
@@ -247,6 +249,8 @@ PROTOTYPES = {
     "osrl_cdt_policy_window_n": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "osrl_cdt_policy_step_slots": [_vp, _P(_i32), _i32, _vp],
     "osrl_cdt_policy_timesteps": [_vp, _P(_i32)],
+    "osrl_cdt_policy_explore_io": [_vp, _P(_P(C.c_float)), _P(_P(C.c_float)), _P(_P(C.c_int32)), _P(_P(C.c_float))],
+    "osrl_cdt_policy_step_slots_explore": [_vp, _P(_i32), _i32, _i32, _u64, _i32, _vp],
     "osrl_cost_sample_prob": [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp],
     "osrl_start_index_prob": [_vp, _vp, _vp, _i32, C.c_double, _vp, _vp, _vp],
     "osrl_bc_select": [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp],

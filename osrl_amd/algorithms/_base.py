@@ -167,6 +167,27 @@ class RolloutMixin:
                                 append=self._eval_extra())
 
     @torch.no_grad()
+    def collect_jobs(self, envs, num_jobs, noise_std=0.0, gamma: Optional[float] = None, seed: int = 0, noise=None,
+                     episode_ids=None, into=None):
+        """``rollout_jobs`` recorded, with exploration noise: ``num_jobs`` episodes over the host (gym-style) environments
+        ``envs`` on the refill schedule, every action ``a = clip(pi(s) + sigma_q * eps, +-max_action)`` computed by the
+        policy call itself (``VecFastPolicy.step(explore_std=...)``), every transition kept -- what ``collect`` does on a
+        ``VecSyntheticSafeEnv``, for real simulators.  Returns a ``Collected`` (engine/collect.py) whose rows are
+        job-major, each job with its true length (``terminals`` 1 where the environment terminated, ``timeouts`` 1 where
+        it truncated or reached ``episode_len``; ``observations`` are the environment's own, without BC multi-task's
+        appended cost limit) and whose dataset is on the device (one upload at the end).
+        ``noise_std``: one sigma or one per job; ``gamma`` (None: 1) weighs the discounted sums; job ``q``'s noise is
+        keyed by ``(seed, episode_ids[q], step, column)`` -- the device collectors' key, ``episode_ids`` defaulting to
+        ``q`` -- or injected as ``noise [num_jobs, episode_len, action_dim]``.  With ``noise_std=0`` job ``q`` is
+        ``rollout_jobs``'s, bit for bit.  ``into``: a ``ReplayStore`` built with ``capacity`` (``collect``'s rules), or a
+        ``SequenceStore`` built with capacities, refused BEFORE the run unless ``num_jobs`` trajectories of
+        ``episode_len`` rows fit; the rows go to its ``append`` and the result's ``dataset`` is None."""
+        from ..engine.act import collect_jobs_mlp
+        self._before_evaluate()
+        return collect_jobs_mlp(self.model, envs, num_jobs, noise_std, gamma, seed, noise, episode_ids, into,
+                                cost_scale=self._cost_scale(), append=self._eval_extra())
+
+    @torch.no_grad()
     def rollout(self):
         """The reference's episode loop on ``self.env``: (return, length, cost sum)."""
         cs, extra = self._cost_scale(), self._eval_extra()

@@ -39,7 +39,9 @@ class BC(FlatModel):
 
     def _policy_spec(self):
         from ..common.net import net_desc_seq
-        return "mlp", self.actor.pi[0].in_features, net_desc_seq([self.actor.pi], float(self.actor.act_limit)), {}
+        # (max_action: the clip of the exploration tail; the "mlp" kind's own action does not read it)
+        return ("mlp", self.actor.pi[0].in_features, net_desc_seq([self.actor.pi], float(self.actor.act_limit)),
+                dict(max_action=float(self.actor.act_limit)))
 
     def act(self, obs):
         """bc.py:57-64: single observation -> action (numpy)."""

@@ -521,6 +521,49 @@ class CDTTrainer:
         adapter = _CDTRefillAdapter(self, model, N) if J else None
         return rollout_refill(adapter, envs, list(zip(trs.tolist(), tcs.tolist())), model.episode_len)
 
+    @torch.no_grad()
+    def collect_jobs(self, model: CDT, envs, target_returns, target_costs, noise_std=0.0, sample: bool = False,
+                     gamma: Optional[float] = None, seed: int = 0, noise=None, episode_ids=None, into=None):
+        """``rollout_jobs`` recorded, with exploration noise (the other trainers' ``collect_jobs``; ``collect_targets``
+        for host environments): one episode per ``(target_returns[q], target_costs[q])`` on the refill schedule, every
+        action ``clip(mu + s * eps)`` computed by the act path's head launch -- ``s = noise_std`` (one sigma or one per
+        job) or, with ``sample=True``, the Gaussian head's own ``exp(log_std)`` (``check_sampling``'s rules) -- and the
+        window records the action taken.  Job ``q``'s noise is keyed by ``(seed, episode_ids[q], the episode's step,
+        column)``, ``collect_targets``' key, or injected as ``noise [jobs, episode_len, action_dim]``.  Returns a
+        ``Collected``: rows job-major with each job's true length, the dataset on device, the cost sums times
+        ``cost_scale``.  With ``sample=True`` the head rows ``(mu | log_std)`` of every step, job-major like the dataset,
+        are kept as ``self.last_head_rows`` (numpy ``[rows, 2 * action_dim]``) for behaviour log-probabilities.
+        ``into``: a ``SequenceStore`` with capacities (refused before the run unless every job could run to
+        ``episode_len``) or a capacity ``ReplayStore``.  A model outside the act path's domain: NotImplementedError."""
+        from ..engine.act import check_job_noise, check_jobs_store, collect_refill, finish_jobs
+        from ..engine.cdt_act import unsupported
+        from ..engine.collect import check_sampling
+        check_sampling(model, sample, noise_std)
+        envs = list(envs)
+        trs, tcs = np.asarray(target_returns, dtype=np.float64), np.asarray(target_costs, dtype=np.float64)
+        if trs.ndim != 1 or trs.shape != tcs.shape:
+            raise ValueError(f"expected target_returns and target_costs as two lists of one length, got shapes "
+                             f"{trs.shape} and {tcs.shape}")
+        J, N = len(trs), len(envs)
+        sg, noise, ids = check_job_noise(J, model.episode_len, model.action_dim, noise_std, noise, episode_ids)
+        check_jobs_store(into, J, model.episode_len, model.state_dim, model.action_dim)
+        why = unsupported(model)
+        if why is not None:
+            raise NotImplementedError("the CDT act latency path does not support: " + why)
+        if not model.fast_eligible():
+            raise NotImplementedError("collect_jobs runs the eval-mode forward of the act path: call model.eval() on a "
+                                      "model with dropout")
+        if J and N == 0:
+            raise ValueError("jobs over an empty list of environments")
+        adapter = _CDTCollectAdapter(self, model, N, bool(sample), int(seed), noise) if J else None
+        jobs = [(q, float(trs[q]), float(tcs[q]), int(ids[q]), float(sg[q])) for q in range(J)]
+        got = collect_refill(adapter, envs, jobs, model.episode_len, gamma, self.cost_scale)
+        if J == 0:
+            got.dataset["observations"] = got.dataset["next_observations"] = np.zeros((0, model.state_dim), np.float32)
+            got.dataset["actions"] = np.zeros((0, model.action_dim), np.float32)
+        self.last_head_rows = adapter.head_rows() if sample and J else None
+        return finish_jobs(got, model.device, into)
+
     def _rollout_fast(self, model: CDT, env, target_return: float, target_cost: float):
         pol = model.fast_policy()
         obs, info = env.reset()
@@ -560,3 +603,39 @@ class _CDTRefillAdapter:
             if j is not None:
                 tr[e], tc[e] = j
         return self.pol.step(obs, reward, cost, active=step, restart=restart, target_return=tr, target_cost=tc)
+
+
+class _CDTCollectAdapter(_CDTRefillAdapter):
+    """``_CDTRefillAdapter`` with the exploration tail: a job is ``(q, target_return, target_cost, episode id, sigma)``;
+    ``noise`` (None, or ``[J, episode_len, action_dim]``) is injected instead of the keyed draw."""
+
+    def __init__(self, trainer: CDTTrainer, model: CDT, num_envs: int, sample: bool, seed: int, noise):
+        super().__init__(trainer, model, num_envs)
+        N, ad = num_envs, model.action_dim
+        self.sample, self.seed, self.noise = sample, seed, noise
+        self.tr, self.tc = np.zeros(N, np.float64), np.zeros(N, np.float64)
+        self.ids, self.sigma = np.zeros(N, np.int64), np.zeros(N, np.float32)
+        self.job, self.t = np.zeros(N, np.int64), np.zeros(N, np.int64)
+        self.eps = None if noise is None else np.zeros((N, ad), np.float32)
+        self.heads = {}  # job -> list of head rows, in step order
+
+    def act(self, obs, reward, cost, step, restart, jobs):
+        for e, j in enumerate(jobs):
+            if j is not None:
+                self.job[e], self.tr[e], self.tc[e], self.ids[e], self.sigma[e] = j
+                self.t[e] = -1
+        run = step | restart
+        self.t[run] += 1
+        if self.eps is not None:
+            self.eps[run] = self.noise[self.job[run], self.t[run]]
+        act = self.pol.step(obs, reward, cost, active=step, restart=restart, target_return=self.tr, target_cost=self.tc,
+                            explore_std=self.sigma, sample=self.sample, explore_seed=self.seed, explore_noise=self.eps,
+                            episode_ids=self.ids)
+        if self.sample:
+            head = self.pol.last_head
+            for e in np.flatnonzero(run):
+                self.heads.setdefault(int(self.job[e]), []).append(head[e])
+        return act
+
+    def head_rows(self) -> np.ndarray:
+        return np.stack([h for q in sorted(self.heads) for h in self.heads[q]])

@@ -14,7 +14,10 @@
 //   * observations / noise / active mask / (episode id, step) are read from a pinned, device-mapped block, actions and
 //     log-probs are written to it, and each workgroup publishes a sequence number of its own that the host spins on;
 //   * noise drawn on the device is Philox keyed by (seed, the slot's episode id, the slot's step, element): an episode
-//     replays identically in any wave and slot.
+//     replays identically in any wave and slot;
+//   * the exploration tail (osrl_policy_act_explore_n): a = clip(a_pi + sigma[slot] * eps) on the action the kernel would
+//     publish, collect.hip's arithmetic with collect.hip's noise keys -- a run on host environments records what the
+//     device collector would have drawn for the same (seed, episode id, step, column).
 #include <new>
 
 #include "policy_common.h"
@@ -38,6 +41,8 @@ struct Io {  // pinned + device-mapped; the host writes obs / noise / active / m
   int32_t* active;  // [n_env] 0: the slot idles (its act / logp words are left alone)
   int32_t* meta;    // [n_env, 2] (episode id, step): the key of the slot's device-drawn noise
   uint64_t* seq;    // [kMaxTiles] (64 bytes apart) completion counter of each workgroup
+  float* sigma;     // [n_env] exploration scale of the slot (read by exploring calls only)
+  float* eps;       // [n_env, act_dim] injected exploration noise -- else drawn in the kernel
 };
 constexpr int kSeqStride = 8;  // uint64 words between two tiles' counters
 
@@ -47,6 +52,8 @@ struct VecArgs {
   int32_t n_env, deterministic, host_noise, pad_;
   uint32_t k0, k1;
   uint64_t seq;
+  int32_t explore, host_eps;  // explore = 0: the calls without the tail (sigma / eps are not read)
+  uint32_t x0, x1;            // the exploration seed
 };
 
 // y[r][n] = act(b[n] + sum_k W[n][k] x[r][k]) * scale for the tile's 16 rows; x, y in LDS (row stride W + kPad).
@@ -127,17 +134,40 @@ __device__ __forceinline__ float draw_normal(const VecArgs& a, int32_t episode, 
       philox4x32_10(U4{(uint32_t)(idx >> 2), (uint32_t)episode, (uint32_t)step, 0xAC8u}, a.k0, a.k1), idx);
 }
 
+constexpr uint32_t kExploreStream = 13;  // engine/collect.py _EPS_STREAM
+
+// The exploration tail on element j of slot s, whose scale is sg: v = fmaf(sg, eps, v), then the clip -- collect.hip's
+// arithmetic.  eps is the pinned row's, or normal_word(philox4x32_10({episode id, step, j >> 2, stream 13}, key =
+// explore seed), j & 3): the draw osrl_env_collect documents.  sg == 0 returns v as it is and reads no eps.
+__device__ __forceinline__ float explore_tail(const VecArgs& a, float sg, int s, int j, float v) {
+  if (sg == 0.f) return v;
+  float eps;
+  if (a.host_eps) {
+    eps = a.io.eps[(size_t)s * a.p.act_dim + j];
+  } else {
+    const U4 r = philox4x32_10(
+        U4{(uint32_t)a.io.meta[2 * s], (uint32_t)a.io.meta[2 * s + 1], (uint32_t)(j >> 2), kExploreStream}, a.x0, a.x1);
+    eps = osrl_rng::normal_word(r, j & 3);
+  }
+  v = fmaf(sg, eps, v);
+  return fminf(fmaxf(v, -a.p.max_action), a.p.max_action);
+}
+
 template <int W>
 __global__ __launch_bounds__(kThreads) void policy_vec_kernel(const VecArgs a) {
   constexpr int S = W + kPad;
   static_assert(sizeof(float) * 2 * kTile * S <= 160 * 1024, "policy_vec_kernel: LDS per workgroup");
   __shared__ __attribute__((aligned(16))) float buf[2][kTile * S];
   __shared__ int live[kTile];  // 1: the row's slot exists and is active
+  __shared__ float sig[kTile];  // the row's exploration scale; 0: the action is published as it is
   const int tid = threadIdx.x;
   const osrl_policy_t& p = a.p;
   const int od = p.obs_dim, ad = p.act_dim, ld = p.latent_dim;
   const int s0 = blockIdx.x * kTile;  // the tile's first slot
-  if (tid < kTile) live[tid] = s0 + tid < a.n_env && a.io.active[s0 + tid] != 0;
+  if (tid < kTile) {
+    live[tid] = s0 + tid < a.n_env && a.io.active[s0 + tid] != 0;
+    sig[tid] = a.explore && live[tid] ? a.io.sigma[s0 + tid] : 0.f;
+  }
   __syncthreads();
   // ---- stage the observation rows (host-mapped memory) + the second input segment of stage 0; idle rows are zero
   const int in0 = round16(p.net[0].dims[0]);
@@ -162,7 +192,7 @@ __global__ __launch_bounds__(kThreads) void policy_vec_kernel(const VecArgs a) {
   if (p.kind == OSRL_POLICY_MLP) {  // BC: act_limit * tanh(mlp(obs)) -- tanh + scale are the net's last layer
     for (int i = tid; i < kTile * ad; i += kThreads) {
       const int r = i / ad, j = i - r * ad;
-      if (live[r]) a.io.act[(size_t)(s0 + r) * ad + j] = buf[cur][r * S + j];
+      if (live[r]) a.io.act[(size_t)(s0 + r) * ad + j] = explore_tail(a, sig[r], s0 + r, j, buf[cur][r * S + j]);
     }
   } else if (p.kind == OSRL_POLICY_GAUSS) {
     // SquashedGaussianMLPActor tail (net.py:176-201): head = (mu | log_std); one thread per row, j ascending
@@ -175,7 +205,9 @@ __global__ __launch_bounds__(kThreads) void policy_vec_kernel(const VecArgs a) {
         const float mu = h[j], raw_ls = h[ad + j];
         float e = 0.f;
         if (!a.deterministic) e = a.host_noise ? a.io.noise[(size_t)s * ad + j] : draw_normal(a, episode, step, j);
-        squashed_gauss(mu, raw_ls, e, p.max_action, &a.io.act[(size_t)s * ad + j], lp);
+        float act;
+        squashed_gauss(mu, raw_ls, e, p.max_action, &act, lp);
+        a.io.act[(size_t)s * ad + j] = explore_tail(a, sig[tid], s, j, act);
       }
       a.io.logp[s] = lp;
     }
@@ -205,7 +237,9 @@ __global__ __launch_bounds__(kThreads) void policy_vec_kernel(const VecArgs a) {
       if (i < kTile * ad) {
         const int r = i / ad, j = i - r * ad;
         const float t = buf[c2][r * S + j];
-        if (live[r]) a.io.act[(size_t)(s0 + r) * ad + j] = bcq_clamp(a0[q], p.phi, p.max_action, t);
+        if (live[r])
+          a.io.act[(size_t)(s0 + r) * ad + j] =
+              explore_tail(a, sig[r], s0 + r, j, bcq_clamp(a0[q], p.phi, p.max_action, t));
       }
     }
   }
@@ -241,8 +275,8 @@ extern "C" int osrl_policy_create_n(const osrl_policy_t* desc, int32_t n_env, vo
   h->wide = needs_wide(p);
   const size_t N = (size_t)n_env, F = sizeof(float) * N, I = sizeof(int32_t) * N;
   const size_t bytes[] = {F * p.obs_dim, F * (noise_dim > 0 ? noise_dim : 1), F * p.act_dim, F, I, 2 * I,
-                          sizeof(uint64_t) * kSeqStride * kMaxTiles};
-  const hipError_t e = h->blk.alloc(bytes, 7);
+                          sizeof(uint64_t) * kSeqStride * kMaxTiles, F, F * p.act_dim};
+  const hipError_t e = h->blk.alloc(bytes, 9);
   if (e != hipSuccess) {
     delete h;
     return (int)e;
@@ -250,7 +284,8 @@ extern "C" int osrl_policy_create_n(const osrl_policy_t* desc, int32_t n_env, vo
   auto io = [&](bool dev) {
     const PinnedBlock& b = h->blk;
     return Io{b.seg<float>(0, dev),   b.seg<float>(1, dev),   b.seg<float>(2, dev),   b.seg<float>(3, dev),
-              b.seg<int32_t>(4, dev), b.seg<int32_t>(5, dev), b.seg<uint64_t>(6, dev)};
+              b.seg<int32_t>(4, dev), b.seg<int32_t>(5, dev), b.seg<uint64_t>(6, dev),
+              b.seg<float>(7, dev),   b.seg<float>(8, dev)};
   };
   h->host = io(false);
   h->dev = io(true);
@@ -272,9 +307,19 @@ extern "C" int osrl_policy_io_n(void* handle, float** obs, float** noise, float*
   return 0;
 }
 
-extern "C" int osrl_policy_act_n(void* handle, int32_t deterministic, int32_t host_noise, uint64_t seed, void* stream) {
+extern "C" int osrl_policy_explore_io_n(void* handle, float** sigma, float** eps) {
   if (!handle) return -1;
   Handle* h = static_cast<Handle*>(handle);
+  if (sigma) *sigma = h->host.sigma;
+  if (eps) *eps = h->host.eps;
+  return 0;
+}
+
+namespace {
+
+// one call; explore = 0: without the tail
+int act_n(Handle* h, int32_t deterministic, int32_t host_noise, uint64_t seed, int32_t explore, uint64_t explore_seed,
+          int32_t host_eps, void* stream) {
   VecArgs a;
   a.p = h->p;
   a.io = h->dev;
@@ -285,6 +330,10 @@ extern "C" int osrl_policy_act_n(void* handle, int32_t deterministic, int32_t ho
   a.k0 = (uint32_t)seed;
   a.k1 = (uint32_t)(seed >> 32);
   a.seq = ++h->seq;
+  a.explore = explore;
+  a.host_eps = host_eps;
+  a.x0 = (uint32_t)explore_seed;
+  a.x1 = (uint32_t)(explore_seed >> 32);
   const int tiles = (h->n_env + kTile - 1) / kTile;
   (void)hipGetLastError();
   if (h->wide)
@@ -294,6 +343,19 @@ extern "C" int osrl_policy_act_n(void* handle, int32_t deterministic, int32_t ho
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   return wait_published(h->host.seq, kSeqStride, tiles, a.seq, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" int osrl_policy_act_n(void* handle, int32_t deterministic, int32_t host_noise, uint64_t seed, void* stream) {
+  if (!handle) return -1;
+  return act_n(static_cast<Handle*>(handle), deterministic, host_noise, seed, 0, 0, 0, stream);
+}
+
+extern "C" int osrl_policy_act_explore_n(void* handle, int32_t deterministic, int32_t host_noise, uint64_t seed,
+                                         uint64_t explore_seed, int32_t host_eps, void* stream) {
+  if (!handle) return -1;
+  return act_n(static_cast<Handle*>(handle), deterministic, host_noise, seed, 1, explore_seed, host_eps ? 1 : 0, stream);
 }
 
 extern "C" int osrl_policy_destroy_n(void* handle) {

@@ -36,6 +36,9 @@
 // entry g of its row list to (episode, local row) by one ballot + popcount over the prefix sums; attention's grid x is
 // the largest count and workgroups past their episode's count exit at once.  Grids are sized by the totals: an idle
 // slot costs no rows.
+// The head launch can end in the recording collectors' exploration tail (osrl_cdt_policy_step_slots_explore): a = clip(mu
+// + s * eps) with cdt_collect.hip's arithmetic and noise keys, s a per-slot sigma or exp(log_std) of the head row; the
+// action taken is what the window records at the next step.  The calls without it read none of its arguments.
 #include <math.h>
 
 #include <new>
@@ -448,6 +451,14 @@ struct HeadArgs {
   uint32_t* arrived;  // device counter of the workgroups that have stored their action (0 between launches)
   int32_t nenv;
   const int32_t* tab;  // the call's table or null.  With a table srow is the episode's own and crow < 0 means "none"
+  // the exploration tail (osrl_cdt_policy_step_slots_explore; explore = 0: none of this is read): a = clip(mu + s * eps),
+  // cdt_collect.hip's arithmetic and noise keys.  s = sigma[episode], or with `sample` exp(log_std) of the head row
+  const float* sigma;         // [nenv] (pinned)
+  const float* eps;           // [nenv, action_dim] injected noise (pinned), read when host_eps
+  const int32_t* episode_id;  // [nenv] (pinned) the episode word of the noise key; the step word is the timestep
+  float* head_out;            // [nenv, 2 * action_dim] (pinned) the head row (mu | log_std), written when sampling
+  int32_t explore, sample, host_eps, t;  // t: every episode's timestep when there is no table
+  uint32_t x0, x1;                       // the exploration seed
 };
 
 __device__ __forceinline__ void head_arrive(const HeadArgs& a) {  // by one thread, after the workgroup's stores
@@ -469,6 +480,7 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
   __shared__ __attribute__((aligned(16))) float buf[2][kMaxHead];
   __shared__ float red[kHeadThreads];
   __shared__ float st[2];
+  __shared__ float lstd[kMaxHead / 2];  // the head row's log_std columns (a sampling call's second pass)
   const osrl_cdt_policy_t& p = a.p;
   const int tid = threadIdx.x, E = p.embedding_dim;
   const size_t eoff = (size_t)blockIdx.x * (size_t)a.es;
@@ -525,34 +537,46 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
     while (NL < round16(out) && NL < 256) NL <<= 1;
     const int KS = kHeadThreads / NL, ks = tid / NL, nl_ = tid - ks * NL;
     const int q0 = (nq * ks) / KS, q1 = (nq * (ks + 1)) / KS;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};  // neurons nl_ + 256 j (out <= 1024)
-    for (int q = q0; q < q1; ++q) {
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(&buf[cur][4 * q]);
+    float* nxt = buf[cur ^ 1];
+    // A sampling call runs the last layer twice: pass 0 is the evaluating call's (the mean keeps its bits), pass 1 the
+    // log_std columns action_dim .. 2 * action_dim - 1 with the SAME k-split, into lstd.  (One pass over 2 * action_dim
+    // columns would derive NL / KS from another width and sum the mean in another order.)
+    const int npass = last && a.explore && a.sample ? 2 : 1;
+    for (int pass = 0; pass < npass; ++pass) {
+      const int c0 = pass * out;  // first weight row / bias of the pass
+      const int live = pass ? out : round16(out);  // (pass 1 reads no column past the ones it keeps: c0 + n < Np)
+      float acc[4] = {0.f, 0.f, 0.f, 0.f};  // neurons nl_ + 256 j (out <= 1024)
+      for (int q = q0; q < q1; ++q) {
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(&buf[cur][4 * q]);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int n = nl_ + 256 * j;
-        if (n < NL * (j + 1) && n < round16(out)) {
-          const f32x4 wv = W4[(size_t)q * Np + n];
-          acc[j] = fmaf(wv[0], xv[0], fmaf(wv[1], xv[1], fmaf(wv[2], xv[2], fmaf(wv[3], xv[3], acc[j]))));
+        for (int j = 0; j < 4; ++j) {
+          const int n = nl_ + 256 * j;
+          if (n < NL * (j + 1) && n < live) {
+            const f32x4 wv = W4[(size_t)q * Np + c0 + n];
+            acc[j] = fmaf(wv[0], xv[0], fmaf(wv[1], xv[1], fmaf(wv[2], xv[2], fmaf(wv[3], xv[3], acc[j]))));
+          }
         }
       }
-    }
-    // partials [KS][NL] per 256-neuron chunk, summed in k-split order
-    float* nxt = buf[cur ^ 1];
-    for (int j = 0; j < 4; ++j) {
-      if (256 * j >= round16(out)) break;
-      __syncthreads();
-      red[tid] = acc[j];
-      __syncthreads();
-      for (int n = 256 * j + tid; n < 256 * (j + 1) && n < round16(out) && tid < NL; n += kHeadThreads) {
-        float s = 0.f;
-        for (int k = 0; k < KS; ++k) s += red[k * NL + (n - 256 * j)];
-        float v = 0.f;
-        if (n < out) {
-          v = s + p.head_b[l][n];
-          if (!last) v = gelu_f(v);
+      // partials [KS][NL] per 256-neuron chunk, summed in k-split order
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (256 * j >= round16(out)) break;
+        __syncthreads();
+        red[tid] = acc[j];
+        __syncthreads();
+        for (int n = 256 * j + tid; n < 256 * (j + 1) && n < round16(out) && tid < NL; n += kHeadThreads) {
+          float s = 0.f;
+          for (int k = 0; k < KS; ++k) s += red[k * NL + (n - 256 * j)];
+          float v = 0.f;
+          if (n < out) {
+            v = s + p.head_b[l][c0 + n];
+            if (!last) v = gelu_f(v);
+          }
+          if (pass == 0)
+            nxt[n] = v;
+          else if (n < out)
+            lstd[n] = v;
         }
-        nxt[n] = v;
       }
     }
     __syncthreads();
@@ -562,9 +586,34 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
     in = out;
   }
   if (tid < p.action_dim) {
-    const float v = fminf(fmaxf(buf[cur][tid], -p.max_action), p.max_action);
-    a.io.act_out[(size_t)blockIdx.x * p.action_dim + tid] = v;
-    a.d.last_act[eoff + tid] = v;
+    const int ad = p.action_dim;
+    float v = buf[cur][tid];
+    if (a.explore) {
+      float sg;
+      if (a.sample) {  // the head row goes out as it is: behaviour log-probabilities are the caller's
+        const float ls = lstd[tid];
+        a.head_out[(size_t)blockIdx.x * 2 * ad + tid] = v;
+        a.head_out[(size_t)blockIdx.x * 2 * ad + ad + tid] = ls;
+        sg = expf(ls);  // no log-std bounds, as osrl_cdt_collect
+      } else {
+        sg = a.sigma[blockIdx.x];
+      }
+      if (sg != 0.f) {  // (s == 0: clip(mu) exactly; eps is not even read)
+        float eps;
+        if (a.host_eps) {
+          eps = a.eps[(size_t)blockIdx.x * ad + tid];
+        } else {
+          const int t = a.tab ? a.tab[kTabT * kTabStride + blockIdx.x] : a.t;
+          const osrl_rng::U4 r = osrl_rng::philox4x32_10(
+              osrl_rng::U4{(uint32_t)a.episode_id[blockIdx.x], (uint32_t)t, (uint32_t)(tid >> 2), 13u}, a.x0, a.x1);
+          eps = osrl_rng::normal_word(r, tid & 3);
+        }
+        v = fmaf(sg, eps, v);
+      }
+    }
+    v = fminf(fmaxf(v, -p.max_action), p.max_action);
+    a.io.act_out[(size_t)blockIdx.x * ad + tid] = v;
+    a.d.last_act[eoff + tid] = v;  // the action taken: the next ingest records it in the window
   }
   __syncthreads();
   if (tid == 0) head_arrive(a);
@@ -580,6 +629,11 @@ struct Handle {
   std::vector<int> t;  // [nenv] timestep of each episode's newest window entry; -1 before its first (re)start
   PinnedBlock blk;
   Io host, dev;
+  struct Xio {  // the exploration tail's segments of the pinned block
+    float *sigma, *eps;
+    int32_t* episode_id;
+    float* head;
+  } xhost, xdev;
   int32_t *htab, *htab_dev;  // the per-call table in the pinned block (host / device address) ...
   int32_t* dtab;             // ... and the copy the ingest launch makes of it in device memory
   Dev d;
@@ -671,8 +725,14 @@ void run_layer(const Handle* h, const Call& c, int l, int qc, int oc, hipStream_
   launch_linear(h, c, oc, h->h, h->ld4, nullptr, nullptr, L.w_2, L.b_2, h->xmid, h->ldE, xout, h->ldE, 4 * E, E, 0, s);
 }
 
+// an exploring call's arguments (null: the calls without the tail)
+struct Explore {
+  int sample, host_eps;
+  uint64_t seed;
+};
+
 // the chain of one call (h->t already advanced)
-int run_step(Handle* h, const Call& c, int host_action, hipStream_t s) {
+int run_step(Handle* h, const Call& c, int host_action, const Explore* x, hipStream_t s) {
   const osrl_cdt_policy_t& p = h->p;
   const int NL = p.num_layers;
   const Rows& emb = c.pl.set[0];
@@ -686,7 +746,10 @@ int run_step(Handle* h, const Call& c, int host_action, hipStream_t s) {
   const bool feat = p.add_cost_feat || p.mul_cost_feat || p.cat_cost_feat;
   HeadArgs ha{p,     h->d,       h->dev,  h->x + (size_t)NL * h->NR * h->ldE,
               h->ldE, c.pl.srow, feat ? c.pl.srow - h->R + 2 + (p.use_rew ? 1 : 0) : -1,
-              ++h->seq, h->es,   h->arrived, h->nenv, c.table ? h->dtab : nullptr};
+              ++h->seq, h->es,   h->arrived, h->nenv, c.table ? h->dtab : nullptr,
+              h->xdev.sigma, h->xdev.eps, h->xdev.episode_id, h->xdev.head,
+              x ? 1 : 0, x ? x->sample : 0, x ? x->host_eps : 0, c.t,
+              x ? (uint32_t)x->seed : 0u, x ? (uint32_t)(x->seed >> 32) : 0u};
   hipLaunchKernelGGL(cdt_act_head_kernel, dim3(h->nenv), dim3(kHeadThreads), 0, s, ha);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
@@ -739,8 +802,10 @@ int create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int n_
   h->dmem = nullptr;
   // pinned block: obs [N, od], act_in [N, ad], act_out [N, ad], scalars [N, 4], seq, the per-call table
   constexpr size_t kTabBytes = 4 * (size_t)kTabFields * kTabStride;
-  const size_t pbytes[] = {4 * NE * od, 4 * NE * ad, 4 * NE * ad, 16 * NE, sizeof(uint64_t), kTabBytes};
-  hipError_t e = h->blk.alloc(pbytes, 6);
+  // ... and the exploration tail's: sigma [N], eps [N, ad], episode id [N], the head row [N, 2 ad]
+  const size_t pbytes[] = {4 * NE * od, 4 * NE * ad, 4 * NE * ad, 16 * NE, sizeof(uint64_t), kTabBytes,
+                           4 * NE,      4 * NE * ad, 4 * NE,      8 * NE * ad};
+  hipError_t e = h->blk.alloc(pbytes, 10);
   if (e != hipSuccess) {
     delete h;
     return (int)e;
@@ -752,6 +817,12 @@ int create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int n_
   };
   h->host = io(false);
   h->dev = io(true);
+  auto xio = [&](bool dev) {
+    const PinnedBlock& b = h->blk;
+    return Handle::Xio{b.seg<float>(6, dev), b.seg<float>(7, dev), b.seg<int32_t>(8, dev), b.seg<float>(9, dev)};
+  };
+  h->xhost = xio(false);
+  h->xdev = xio(true);
   h->htab = h->blk.seg<int32_t>(5, false);
   h->htab_dev = h->blk.seg<int32_t>(5, true);
   // device block, one per episode: window ring, last action, raw embeddings, activations (zeroed: the row strides'
@@ -796,8 +867,9 @@ int create(const osrl_cdt_policy_t* desc, const osrl_cdt_layer_t* layers, int n_
 
 // one call: every episode idles, steps or restarts (mode[e]).  -1, and nothing changed, if a stepping episode was never
 // started or would leave the timestep embedding table.
-int step_modes(Handle* h, const int32_t* mode, int host_action, hipStream_t s) {
+int step_modes(Handle* h, const int32_t* mode, int host_action, const Explore* x, hipStream_t s) {
   const int N = h->nenv;
+  if (x && x->sample && h->p.head_out_width < 2 * h->p.action_dim) return -1;  // no log_std columns to sample from
   int nt[OSRL_CDT_POLICY_MAX_ENVS];
   int lead = -1;  // the first episode that runs
   bool same = true;
@@ -848,13 +920,13 @@ int step_modes(Handle* h, const int32_t* mode, int host_action, hipStream_t s) {
       }
     }
   }
-  return run_step(h, c, host_action ? 1 : 0, s);
+  return run_step(h, c, host_action ? 1 : 0, x, s);
 }
 
 int all_modes(Handle* h, int mode, int host_action, hipStream_t s) {
   int32_t m[OSRL_CDT_POLICY_MAX_ENVS];
   for (int e = 0; e < h->nenv; ++e) m[e] = mode;
-  return step_modes(h, m, host_action, s);
+  return step_modes(h, m, host_action, nullptr, s);
 }
 
 int reset_all(Handle* h, hipStream_t s) { return all_modes(h, kRestart, 0, s); }
@@ -950,7 +1022,26 @@ extern "C" int osrl_cdt_policy_step_n(void* handle, int32_t host_action, void* s
 
 extern "C" int osrl_cdt_policy_step_slots(void* handle, const int32_t* mode, int32_t host_action, void* stream) {
   if (!handle || !mode) return -1;
-  return step_modes(static_cast<Handle*>(handle), mode, host_action, (hipStream_t)stream);
+  return step_modes(static_cast<Handle*>(handle), mode, host_action, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int osrl_cdt_policy_explore_io(void* handle, float** sigma, float** eps, int32_t** episode_id,
+                                          float** head) {
+  if (!handle) return -1;
+  Handle* h = static_cast<Handle*>(handle);
+  if (sigma) *sigma = h->xhost.sigma;
+  if (eps) *eps = h->xhost.eps;
+  if (episode_id) *episode_id = h->xhost.episode_id;
+  if (head) *head = h->xhost.head;
+  return 0;
+}
+
+extern "C" int osrl_cdt_policy_step_slots_explore(void* handle, const int32_t* mode, int32_t host_action,
+                                                  int32_t sample, uint64_t explore_seed, int32_t host_eps,
+                                                  void* stream) {
+  if (!handle || !mode) return -1;
+  const Explore x{sample ? 1 : 0, host_eps ? 1 : 0, explore_seed};
+  return step_modes(static_cast<Handle*>(handle), mode, host_action, &x, (hipStream_t)stream);
 }
 
 extern "C" int osrl_cdt_policy_timesteps(void* handle, int32_t* t) {

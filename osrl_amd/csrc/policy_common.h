@@ -64,7 +64,7 @@ __device__ __forceinline__ float bcq_clamp(float a0, float phi, float max_action
 // One pinned (mapped + portable), zeroed allocation carved into 256-byte-aligned segments; a segment is handed out as
 // its host or its device address.  Freed by release() (a handle's destroy, which reports the error) or with its owner.
 struct PinnedBlock {
-  static constexpr int kMaxSegs = 8;
+  static constexpr int kMaxSegs = 12;
   char *host = nullptr, *dev = nullptr;
   size_t off[kMaxSegs + 1] = {0};
 

@@ -18,7 +18,9 @@ slot's action does not depend on how many ran beside it.
 ``rollout_refill`` is the host-side scheduler both trainer families use for ``schedule="refill"``: a queue of jobs over
 N environments, where a slot whose episode has ended takes the next job in the same policy call in which the others step
 (``VecFastPolicy.step(restart=...)``, ``CDTVecFastPolicy.step(restart=...)``) instead of waiting for the longest episode
-of its wave.
+of its wave.  ``collect_refill`` is the same loop with a recorder: every job comes back as rows of a DSRL-layout
+dataset (``Trainer.collect_jobs``), with the collectors' exploration noise added by the policy call itself
+(``step(explore_std=...)``).
 """
 from __future__ import annotations
 
@@ -220,6 +222,10 @@ class VecFastPolicy(PinnedHandle):
         self.logp_out = view(fp[3], (N,))
         self._active = view(ip[0], (N,))
         self._meta = view(ip[1], (N, 2))  # (episode id, step) of each slot
+        xp = [C.POINTER(C.c_float)() for _ in range(2)]
+        L.check(lib.osrl_policy_explore_io_n(h, *[C.byref(p) for p in xp]), "osrl_policy_explore_io_n")
+        self._sigma = view(xp[0], (N,))        # exploration scale of each slot
+        self._eps = view(xp[1], (N, act_dim))  # injected exploration noise
         self._started = False
 
     def _checked(self, obs, active, noise):
@@ -242,7 +248,25 @@ class VecFastPolicy(PinnedHandle):
             raise ValueError("expected episode_ids as integers in 0 .. 2^31 - 1")
         return ids
 
-    def _call(self, obs, active, noise, deterministic) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    def _explore(self, explore_std, explore_seed, explore_noise):
+        """The checked exploration arguments of a call: None, or (sigma [N] fp32, seed, eps [N, act_dim] fp32 or None)."""
+        if explore_std is None:
+            if explore_noise is not None:
+                raise ValueError("explore_noise is the eps of explore_std: pass explore_std")
+            return None
+        sg = np.asarray(explore_std, dtype=np.float32)
+        if sg.ndim != 0 and sg.shape != (self.num_envs,):
+            raise ValueError(f"expected explore_std as a scalar or of shape ({self.num_envs},), got {sg.shape}")
+        if explore_noise is not None:
+            explore_noise = self._rows("explore_noise", explore_noise, (self.act_dim,), np.float32)
+        return np.broadcast_to(sg, (self.num_envs,)), int(explore_seed) & 0xFFFFFFFFFFFFFFFF, explore_noise
+
+    def _call(self, obs, active, noise, deterministic, explore=None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        if explore is not None:
+            sel = slice(None) if active is None else active
+            self._sigma[sel] = explore[0][sel]
+            if explore[2] is not None:
+                self._eps[sel] = explore[2][sel]
         if active is None:
             self.obs[:] = obs  # converts dtype
             self._active[:] = 1
@@ -254,31 +278,47 @@ class VecFastPolicy(PinnedHandle):
             if noise is not None:
                 self.noise[active, :self.noise_dim] = noise[active]
         st = self._raw_stream(self._dev_index) if self._raw_stream is not None else cur_stream()
-        rc = self._lib.osrl_policy_act_n(self._h, 1 if deterministic else 0, 0 if noise is None else 1, self.seed, st)
-        if rc != 0:
-            L.check(rc, "osrl_policy_act_n")
+        if explore is None:
+            rc = self._lib.osrl_policy_act_n(self._h, 1 if deterministic else 0, 0 if noise is None else 1, self.seed,
+                                             st)
+            if rc != 0:
+                L.check(rc, "osrl_policy_act_n")
+        else:
+            rc = self._lib.osrl_policy_act_explore_n(self._h, 1 if deterministic else 0, 0 if noise is None else 1,
+                                                     self.seed, explore[1], 0 if explore[2] is None else 1, st)
+            if rc != 0:
+                L.check(rc, "osrl_policy_act_explore_n")
         return self.act_out.copy(), (self.logp_out.copy() if self.kind == "gauss" else None)
 
-    def reset(self, obs, episode_ids=None, active=None, noise=None, deterministic: bool = True):
+    def reset(self, obs, episode_ids=None, active=None, noise=None, deterministic: bool = True, explore_std=None,
+              explore_seed: int = 0, explore_noise=None):
         """Starts an episode in every active slot from ``obs [N, obs_dim]`` (``episode_ids``: ``[N]`` integers, default
         the slot numbers; ``active``: bool ``[N]``, default all) and returns the first ``(actions [N, act_dim],
-        log-probs [N] or None)``."""
+        log-probs [N] or None)``.  ``explore_std`` / ``explore_seed`` / ``explore_noise``: as ``step`` takes them."""
         if self._h is None:
             raise RuntimeError("VecFastPolicy is closed")
         obs, active, noise = self._checked(obs, active, noise)
+        explore = self._explore(explore_std, explore_seed, explore_noise)
         ids = self._ids(episode_ids)
         sel = slice(None) if active is None else active
         self._meta[sel, 0] = ids[sel]
         self._meta[sel, 1] = 0
         self._started = True
-        return self._call(obs, active, noise, deterministic)
+        return self._call(obs, active, noise, deterministic, explore)
 
-    def step(self, obs, active=None, noise=None, deterministic: bool = True, restart=None, episode_ids=None):
+    def step(self, obs, active=None, noise=None, deterministic: bool = True, restart=None, episode_ids=None,
+             explore_std=None, explore_seed: int = 0, explore_noise=None):
         """The next ``(actions, log-probs or None)`` of every active slot from its new observation.  ``noise``:
         explicit standard-normal draws ``[N, act_dim]`` (eps of "gauss") or ``[N, latent_dim]`` (z of "bcq").
         ``restart`` (bool ``[N]``): the masked slots start a new episode from ``obs[e]`` instead of stepping -- they
         count as active and take ``episode_ids[e]`` (``[N]`` integers, default the slot numbers) at step 0, as ``reset``
-        gives them -- while the other active slots step."""
+        gives them -- while the other active slots step.
+        ``explore_std`` (None: off, the call is the one without these arguments): the collectors' exploration tail on
+        the returned action, ``clip(a + explore_std[e] * eps, +-max_action)`` with one sigma or ``[N]`` of them; a slot
+        whose sigma is 0 returns its action's bits unchanged.  ``eps`` is ``explore_noise [N, act_dim]`` when given,
+        else drawn in the kernel keyed by ``(explore_seed, the slot's episode id, its step, column)`` -- the device
+        collectors' draw (``Trainer.collect``), apart from the policy's own noise.  The log-probs stay those of the
+        policy's own action."""
         if self._h is None:
             raise RuntimeError("VecFastPolicy is closed")
         if restart is not None:
@@ -293,15 +333,16 @@ class VecFastPolicy(PinnedHandle):
         if not self._started and restart is None:
             raise RuntimeError("call reset() before step()")
         obs, active, noise = self._checked(obs, active, noise)
+        explore = self._explore(explore_std, explore_seed, explore_noise)
         if restart is None:
             self._meta[slice(None) if active is None else active, 1] += 1
-            return self._call(obs, active, noise, deterministic)
+            return self._call(obs, active, noise, deterministic, explore)
         stepping = ~restart if active is None else active & ~restart
         self._meta[stepping, 1] += 1
         self._meta[restart, 0] = ids[restart]
         self._meta[restart, 1] = 0
         self._started = True
-        return self._call(obs, None if active is None else active | restart, noise, deterministic)
+        return self._call(obs, None if active is None else active | restart, noise, deterministic, explore)
 
 
 def cached_vec_policy(model, num_envs, make, limit=VecFastPolicy.LIMIT):
@@ -405,6 +446,11 @@ def rollout_refill(adapter, envs, jobs, episode_len) -> RefillResult:
     -> (the cost the policy is told, the cost summed into the result); ``act(obs, reward, cost, step, restart, jobs)``
     -> actions ``[N, ..]``, where ``step`` / ``restart`` are bool ``[N]`` masks and ``jobs[e]`` is the queue entry of a
     restarting slot (None elsewhere)."""
+    return _refill(adapter, envs, jobs, episode_len, None)
+
+
+def _refill(adapter, envs, jobs, episode_len, rec) -> RefillResult:
+    """``rollout_refill``'s loop; ``rec`` (None, or a ``JobRecorder``) is shown every transition."""
     envs, jobs = list(envs), list(jobs)
     N, J, EL = len(envs), len(jobs), int(episode_len)
     if J and N == 0:
@@ -426,6 +472,8 @@ def rollout_refill(adapter, envs, jobs, episode_len) -> RefillResult:
         o, _ = envs[e].reset()
         obs[e] = adapter.observe(o)
         active[e] = restart[e] = True
+        if rec is not None:
+            rec.start(q, o)
 
     for e in range(min(N, J)):
         take(e)
@@ -442,6 +490,8 @@ def rollout_refill(adapter, envs, jobs, episode_len) -> RefillResult:
             ep_ret[q] += r
             ep_len[q] += 1
             ep_cost[q] += summed
+            if rec is not None:
+                rec.add(q, act[e], o, r, info["cost"], terminated, truncated or ep_len[q] == EL)
             if terminated or truncated or ep_len[q] == EL:
                 active[e] = False
                 continue
@@ -450,6 +500,124 @@ def rollout_refill(adapter, envs, jobs, episode_len) -> RefillResult:
             if not active[e] and queued < J:
                 take(e)
     return RefillResult(np.asarray(ep_ret), ep_len, np.asarray(ep_cost), slot_of, calls)
+
+
+class JobRecorder:
+    """What ``collect_refill`` keeps of every job: its transitions under the seven DSRL keys (host lists, one entry per
+    step) and its sums.  ``cost_scale`` multiplies the raw cost in the two cost sums only; the recorded costs are raw."""
+
+    def __init__(self, num_jobs: int, gamma: Optional[float] = None, cost_scale: Optional[float] = None):
+        J = int(num_jobs)
+        self.gamma = 1.0 if gamma is None else float(gamma)
+        self.cost_scale = 1.0 if cost_scale is None else cost_scale
+        self.rows = [[] for _ in range(J)]  # per job: (obs, action, next obs, reward, cost, terminal, timeout)
+        self.cur = [None] * J               # the observation the job's next action answers
+        self.ret, self.cret, self.dret, self.dcret = [0.0] * J, [0.0] * J, [0.0] * J, [0.0] * J
+
+    def start(self, q: int, o) -> None:
+        self.cur[q] = np.array(o, dtype=np.float32)
+
+    def add(self, q: int, a, o_next, r, cost, terminated, timeout) -> None:
+        t = len(self.rows[q])
+        o_next = np.array(o_next, dtype=np.float32)
+        self.rows[q].append((self.cur[q], np.array(a, dtype=np.float32), o_next, r, cost, bool(terminated), bool(timeout)))
+        self.cur[q] = o_next
+        pw, c = self.gamma ** t, cost * self.cost_scale
+        self.ret[q] += r
+        self.cret[q] += c
+        self.dret[q] += pw * float(r)
+        self.dcret[q] += pw * float(c)
+
+    def dataset(self):
+        """The rows job-major (job 0's, then job 1's, ..., each with its true length) as fp32 numpy arrays."""
+        rows = [x for job in self.rows for x in job]
+        n = len(rows)
+        col = lambda i, w: (np.stack([x[i] for x in rows]).astype(np.float32).reshape((n,) + w) if n  # noqa: E731
+                            else np.zeros((0,) + w, np.float32))
+        od = () if not n else rows[0][0].shape
+        ad = () if not n else rows[0][1].shape
+        return {"observations": col(0, od), "actions": col(1, ad), "next_observations": col(2, od),
+                "rewards": col(3, ()), "costs": col(4, ()), "terminals": col(5, ()), "timeouts": col(6, ())}
+
+
+CollectedJobs = namedtuple("CollectedJobs", "dataset returns cost_returns lengths disc_returns disc_cost_returns refill")
+CollectedJobs.__doc__ = """What ``collect_refill`` returns: ``dataset`` (numpy, on the host, job-major), the per-job sums in
+fp64 (``Collected``'s fields) and the ``RefillResult`` of the schedule."""
+
+
+def collect_refill(adapter, envs, jobs, episode_len, gamma: Optional[float] = None, cost_scale=None) -> CollectedJobs:
+    """``rollout_refill`` recorded: the same schedule, the same calls of ``adapter`` (which adds whatever noise it is
+    built to add), and of every job its transitions under the seven DSRL keys -- ``observations`` /
+    ``next_observations`` are the environment's own (not ``adapter.observe``'s row), ``actions`` the bits the policy
+    call returned, ``costs`` the raw ``info["cost"]``, ``terminals`` 1 where the environment terminated, ``timeouts`` 1
+    where it truncated or the episode reached ``episode_len`` -- plus return, cost return (times ``cost_scale``), length
+    and the two sums weighted by ``gamma ** t`` in fp64.  The rows are job-major with each job's true length: the layout
+    depends neither on ``len(envs)`` nor on the slot a job ran in."""
+    jobs = list(jobs)
+    rec = JobRecorder(len(jobs), gamma, cost_scale)
+    res = _refill(adapter, envs, jobs, episode_len, rec)
+    f = lambda x: np.asarray(x, dtype=np.float64)  # noqa: E731
+    return CollectedJobs(rec.dataset(), f(rec.ret), f(rec.cret), res.lengths.astype(np.float64), f(rec.dret),
+                         f(rec.dcret), res)
+
+
+def check_job_noise(num_jobs, episode_len, action_dim, noise_std, noise, episode_ids):
+    """``collect_jobs``'s per-job arguments, checked on the host: sigma ``[J]`` fp32 (one value or one per job), the
+    injected noise ``[J, episode_len, action_dim]`` fp32 or None, the episode ids ``[J]`` (default ``0 .. J - 1``)."""
+    J = int(num_jobs)
+    if J < 0:
+        raise ValueError(f"num_jobs must not be negative, got {J}")
+    if torch.is_tensor(noise_std):
+        noise_std = noise_std.detach().cpu().numpy()
+    sg = np.asarray(noise_std, dtype=np.float32)
+    if sg.ndim != 0 and sg.shape != (J,):
+        raise ValueError(f"noise_std holds {sg.size} values, the queue {J} jobs")
+    sg = np.ascontiguousarray(np.broadcast_to(sg, (J,)))
+    if noise is not None:
+        if torch.is_tensor(noise):
+            noise = noise.detach().cpu().numpy()
+        noise = np.asarray(noise, dtype=np.float32)
+        if noise.shape != (J, int(episode_len), int(action_dim)):
+            raise ValueError(f"noise must be [{J}, {int(episode_len)}, {int(action_dim)}] (jobs, episode_len, "
+                             f"action_dim), got {noise.shape}")
+    if episode_ids is None:
+        ids = np.arange(J, dtype=np.int64)
+    else:
+        if np.shape(episode_ids) != (J,):
+            raise ValueError(f"expected episode_ids of shape ({J},), got {np.shape(episode_ids)}")
+        ids = np.asarray(episode_ids)
+        if ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 0x7FFFFFFF).any():
+            raise ValueError("expected episode_ids as integers in 0 .. 2^31 - 1")
+    return sg, noise, ids
+
+
+def check_jobs_store(into, num_jobs, episode_len, state_dim, action_dim) -> None:
+    """``collect_jobs(into=)``, before the run: a ``SequenceStore`` must have room for ``num_jobs`` trajectories of
+    ``episode_len`` rows (the lengths are not known in advance, and the run must not be lost); a ``ReplayStore`` under
+    ``collect``'s rules."""
+    from ..common.replay import SequenceStore
+    from .collect import _check_replay_store
+    if isinstance(into, SequenceStore):
+        into.check_append(int(num_jobs), int(num_jobs) * int(episode_len), observations=state_dim, actions=action_dim)
+    else:
+        _check_replay_store(into, state_dim, action_dim)
+
+
+def finish_jobs(got: CollectedJobs, device, into):
+    """The host rows as a ``Collected``: ONE upload of all seven tables, then views of it as the dataset, or the store's
+    ``append``."""
+    from .collect import KEYS, Collected
+    d = got.dataset
+    flat = np.concatenate([d[k].reshape(-1) for k in KEYS]) if d["rewards"].size else np.zeros(0, np.float32)
+    dev = torch.from_numpy(flat).to(device)
+    data, off = {}, 0
+    for k in KEYS:
+        data[k] = dev[off:off + d[k].size].view(d[k].shape)
+        off += d[k].size
+    if into is not None:
+        into.append(data)
+        data = None
+    return Collected(data, got.returns, got.cost_returns, got.lengths, got.disc_returns, got.disc_cost_returns)
 
 
 class MLPRefillAdapter:
@@ -469,6 +637,55 @@ class MLPRefillAdapter:
     def act(self, obs, reward, cost, step, restart, jobs):
         ids = np.asarray([0 if j is None else j for j in jobs], dtype=np.int64)
         return self.pol.step(obs, active=step, restart=restart, episode_ids=ids)[0]
+
+
+class MLPCollectAdapter(MLPRefillAdapter):
+    """``MLPRefillAdapter`` with the exploration tail: a job is ``(q, episode id, sigma)``; ``noise`` (None, or ``[J,
+    episode_len, act_dim]``) is injected instead of the draw keyed by ``(seed, episode id, step, column)``."""
+
+    def __init__(self, model, num_envs, cost_scale=None, append=None, seed: int = 0, noise=None):
+        super().__init__(model, num_envs, cost_scale, append)
+        N = self.pol.num_envs
+        self.seed, self.noise = int(seed), noise
+        self.ids, self.sigma = np.zeros(N, np.int64), np.zeros(N, np.float32)
+        self.job, self.t = np.zeros(N, np.int64), np.zeros(N, np.int64)
+        self.eps = None if noise is None else np.zeros((N, self.pol.act_dim), np.float32)
+
+    def act(self, obs, reward, cost, step, restart, jobs):
+        for e, j in enumerate(jobs):
+            if j is not None:
+                self.job[e], self.ids[e], self.sigma[e] = j
+                self.t[e] = -1
+        run = step | restart
+        self.t[run] += 1
+        if self.eps is not None:
+            self.eps[run] = self.noise[self.job[run], self.t[run]]
+        return self.pol.step(obs, active=step, restart=restart, episode_ids=self.ids, explore_std=self.sigma,
+                             explore_seed=self.seed, explore_noise=self.eps)[0]
+
+
+def collect_jobs_mlp(model, envs, num_jobs, noise_std=0.0, gamma=None, seed: int = 0, noise=None, episode_ids=None,
+                     into=None, cost_scale=None, append=None):
+    """``RolloutMixin.collect_jobs``: ``rollout_jobs_mlp``'s queue through ``collect_refill`` with the exploration tail of
+    ``VecFastPolicy.step``.  Returns a ``Collected``."""
+    envs = list(envs)
+    J = int(num_jobs)
+    kind, obs_dim, _, _ = model._policy_spec()
+    state_dim = obs_dim - (0 if append is None else 1)
+    sg, noise, ids = check_job_noise(J, model.episode_len, model.action_dim, noise_std, noise, episode_ids)
+    check_jobs_store(into, J, model.episode_len, state_dim, model.action_dim)
+    if J and not envs:
+        raise ValueError("jobs over an empty list of environments")
+    if J == 0:
+        got = collect_refill(None, envs, [], model.episode_len, gamma, cost_scale)
+        d = got.dataset
+        d["observations"] = d["next_observations"] = np.zeros((0, state_dim), np.float32)
+        d["actions"] = np.zeros((0, model.action_dim), np.float32)
+    else:
+        adapter = MLPCollectAdapter(model, len(envs), cost_scale, append, seed, noise)
+        got = collect_refill(adapter, envs, [(q, int(ids[q]), float(sg[q])) for q in range(J)], model.episode_len,
+                             gamma, cost_scale)
+    return finish_jobs(got, model.device, into)
 
 
 def rollout_jobs_mlp(model, envs, num_jobs, episode_ids=None, cost_scale=None, append=None) -> RefillResult:

@@ -13,7 +13,8 @@ AdamW step, ``load_state_dict`` and ``repack()`` keep current -- so training bet
 step (``osrl_cdt_policy_*_n``): the step's launches run over the rows of all the episodes, and an episode's actions do
 not depend on how many ran beside it.  The slots run in lockstep (``reset`` starts all of them) or, once a slot has been
 restarted on its own (``step(..., restart=mask)``, ``osrl_cdt_policy_step_slots``), each at its own timestep: a finished
-slot takes a new episode while the others go on, and an inactive slot costs no device rows.
+slot takes a new episode while the others go on, and an inactive slot costs no device rows.  ``step(explore_std=...)`` /
+``step(sample=True)`` end the head launch in the collectors' exploration tail (``CDTTrainer.collect_jobs``).
 """
 from __future__ import annotations
 
@@ -199,6 +200,13 @@ class CDTVecFastPolicy(_CDTHandle):
         self._act_in = np.ctypeslib.as_array(ptrs[1], shape=(N, ad))
         self._act_out = np.ctypeslib.as_array(ptrs[2], shape=(N, ad))
         self._scalars = np.ctypeslib.as_array(ptrs[3], shape=(N, 4))  # reward, cost, target_return, target_cost
+        xp = [C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_float)()]
+        L.check(lib.osrl_cdt_policy_explore_io(self._h, *[C.byref(p) for p in xp]), "osrl_cdt_policy_explore_io")
+        self._sigma = np.ctypeslib.as_array(xp[0], shape=(N,))       # exploration scale of each slot
+        self._eps = np.ctypeslib.as_array(xp[1], shape=(N, ad))      # injected exploration noise
+        self._episode_id = np.ctypeslib.as_array(xp[2], shape=(N,))  # the episode word of the noise key
+        self._head = np.ctypeslib.as_array(xp[3], shape=(N, 2 * ad))  # (mu | log_std) of a sampling call
+        self.last_head = None
 
     # Per-slot state lives beside the scalars ``_t`` / ``_episode_len``: ``_ts`` / ``_els`` ([N] arrays) and ``_slots``
     # (True once a slot has been restarted on its own).  In lockstep the scalars are every slot's; with independent
@@ -245,7 +253,8 @@ class CDTVecFastPolicy(_CDTHandle):
         return self._act_out.copy()
 
     def step(self, obs, reward, cost, action=None, active=None, restart=None, target_return=None,
-             target_cost=None) -> np.ndarray:
+             target_cost=None, explore_std=None, sample: bool = False, explore_seed: int = 0, explore_noise=None,
+             episode_ids=None) -> np.ndarray:
         """Per slot as ``CDTFastPolicy.step``: ``obs [N, state_dim]``, ``reward [N]``, ``cost [N]``, the actions taken at
         the previous step (``action [N, action_dim]``, default: the ones returned) and ``active`` (bool ``[N]``, default:
         all).  Returns the next actions ``[N, action_dim]``, zero in the rows of inactive slots.
@@ -253,15 +262,40 @@ class CDTVecFastPolicy(_CDTHandle):
         ``restart`` (bool ``[N]``): the masked slots begin a new episode at timestep 0 from ``obs[e]`` with
         ``target_return`` / ``target_cost`` (scalars or ``[N]``; required when any slot restarts) instead of stepping:
         their ``reward / cost / action`` rows are not read, they count as active, and their row of the result is the
-        new episode's first action (what ``reset`` returns for it)."""
+        new episode's first action (what ``reset`` returns for it).
+
+        ``explore_std`` (None: off) or ``sample=True``: the collectors' exploration tail on the returned action,
+        ``clip(mu + s * eps)`` with ``s = explore_std`` (one sigma or ``[N]``) or, sampling, the Gaussian head's own
+        ``exp(log_std)``; ``s == 0`` returns the evaluating call's bits.  ``eps`` is ``explore_noise [N, action_dim]``
+        when given, else drawn in the kernel keyed by ``(explore_seed, the slot's episode id, its timestep, column)`` --
+        ``collect_targets``' draw; ``episode_ids`` (``[N]`` integers) gives the restarting slots theirs.  The window
+        records the action taken.  After a sampling call ``last_head`` holds ``(mu | log_std) [N, 2 * action_dim]`` (rows
+        of slots that did not run are stale).  An exploring call runs the slots independently, as ``restart`` does."""
         N = self.num_envs
+        explore = explore_std is not None or bool(sample)
+        if not explore and (explore_noise is not None or episode_ids is not None):
+            raise ValueError("explore_noise and episode_ids belong to an exploring call: pass explore_std or sample=True")
+        if explore:
+            sg = np.asarray(0.0 if explore_std is None else explore_std, dtype=np.float32)
+            if sg.ndim != 0 and sg.shape != (N,):
+                raise ValueError(f"expected explore_std as a scalar or of shape ({N},), got {sg.shape}")
+            sg = np.broadcast_to(sg, (N,))
+            if explore_noise is not None:
+                explore_noise = self._rows("explore_noise", explore_noise, (self.ad,), np.float32)
+            if episode_ids is not None:
+                episode_ids = self._rows("episode_ids", episode_ids, ())
+                if episode_ids.dtype.kind not in "iu" or (episode_ids < 0).any() or (episode_ids > 0x7FFFFFFF).any():
+                    raise ValueError("expected episode_ids as integers in 0 .. 2^31 - 1")
+            if sample and not self.model.stochastic:
+                raise ValueError("sample=True draws from the Gaussian head's own standard deviation: the model was built "
+                                 "with stochastic=False")
         if restart is not None:
             restart = self._mask("restart", restart)
             if not restart.any():
                 restart = None
         if self._t < 0 and restart is None:
             raise RuntimeError("call reset() before step()")
-        slots = restart is not None or self.__dict__.get("_slots", False)
+        slots = restart is not None or explore or self.__dict__.get("_slots", False)
         if not slots and self._t + 1 >= self._episode_len:
             raise RuntimeError(f"the episode is over: {self._episode_len} steps (model.episode_len)")
         obs = self._rows("obs", obs, (self.od,))
@@ -322,10 +356,24 @@ class CDTVecFastPolicy(_CDTHandle):
         if action is not None:
             self._act_in[st] = action[st]
         mode = np.where(rs, 2, np.where(st, 1, 0)).astype(np.int32)
-        rc = self._lib.osrl_cdt_policy_step_slots(self._h, mode.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                  0 if action is None else 1, self._stream())
-        if rc != 0:
-            L.check(rc, "osrl_cdt_policy_step_slots")
+        if explore:
+            self._sigma[run] = sg[run]
+            if explore_noise is not None:
+                self._eps[run] = explore_noise[run]
+            if episode_ids is not None:
+                self._episode_id[rs] = episode_ids[rs]
+            rc = self._lib.osrl_cdt_policy_step_slots_explore(
+                self._h, mode.ctypes.data_as(C.POINTER(C.c_int32)), 0 if action is None else 1, 1 if sample else 0,
+                int(explore_seed) & 0xFFFFFFFFFFFFFFFF, 0 if explore_noise is None else 1, self._stream())
+            if rc != 0:
+                L.check(rc, "osrl_cdt_policy_step_slots_explore")
+            if sample:
+                self.last_head = self._head.copy()
+        else:
+            rc = self._lib.osrl_cdt_policy_step_slots(self._h, mode.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      0 if action is None else 1, self._stream())
+            if rc != 0:
+                L.check(rc, "osrl_cdt_policy_step_slots")
         ts[st] += 1
         ts[rs] = 0
         self._ts, self._els, self._slots = ts, els, True

@@ -35,7 +35,10 @@ class Collected(NamedTuple):
     """``dataset``: fresh device tensors under the seven DSRL keys, ``E * L`` rows, episode-major (row ``e * L + t``);
     costs raw 0 / 1, ``terminals`` all 0, ``timeouts`` 1 on each episode's last row.  The per-episode sums are numpy
     fp64 ``[E]``; the two cost sums carry the collector's ``cost_scale`` (as ``BatchedRollout.run``'s do), the discounted
-    ones weigh step t by ``gamma ** t``.  ``dataset`` is None when the run appended its rows to a store (``into=``)."""
+    ones weigh step t by ``gamma ** t``.  ``dataset`` is None when the run appended its rows to a store (``into=``).
+    From ``collect_jobs`` (host environments, engine/act.py): one entry per JOB, the rows job-major with each job's true
+    length, ``terminals`` 1 where the environment terminated and ``timeouts`` 1 where it truncated or reached
+    ``episode_len``, and the sums accumulated on the host in fp64."""
     dataset: Optional[Dict[str, torch.Tensor]]
     returns: np.ndarray
     cost_returns: np.ndarray
