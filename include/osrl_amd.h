@@ -613,6 +613,21 @@ typedef struct {
 } osrl_seq_gather_t;
 int osrl_seq_window_gather(const osrl_seq_gather_t* g, const osrl_step_state_t* st /* NULL: step 0 */, void* stream);
 
+/* A store that evicts (SequenceStore evict="oldest", seq_ring.hip): drop the n_drop oldest of the n_live trajectories.
+ * Entries [n_drop, n_live) of traj_start, traj_len and (if given) traj_w move to [0, n_live - n_drop) IN PLACE, the
+ * vacated slots [n_live - n_drop, n_live) are zeroed, entries past n_live are not touched, and *n_traj_dev (the live
+ * word osrl_seq_window_gather reads) becomes n_live - n_drop.  One launch of one workgroup that walks the tables in
+ * ascending passes (load a pass, barrier, store it), so source and destination may overlap; no workspace, capturable.
+ * 0 <= n_drop <= n_live <= 2^20; -1 (nothing launched) otherwise or on a NULL traj_start / traj_len / n_traj_dev. */
+typedef struct {
+  int64_t* traj_start;
+  int32_t* traj_len;
+  double* traj_w; /* optional per-trajectory weights (set_sample_prob), NULL = none */
+  int32_t* n_traj_dev;
+  int32_t n_live, n_drop;
+} osrl_seq_evict_t;
+int osrl_seq_evict_front(const osrl_seq_evict_t* e, void* stream);
+
 /* ---- glue (glue.hip): the elementwise / reduction tails of the loss functions ----
  * `rows_global` (0 = rows) is the data-parallel global batch used in every 1/B normalisation.
  * `stat` pointers are device floats (logged statistics), may be NULL. */

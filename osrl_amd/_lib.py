@@ -121,6 +121,11 @@ class SeqGatherT(C.Structure):  # osrl_seq_gather_t (cdf / start_cdf / idx_in / 
                 ("reward_scale", C.c_float), ("cost_scale", C.c_float), ("stream_id", C.c_uint32)]
 
 
+class SeqEvictT(C.Structure):  # osrl_seq_evict_t (traj_w None = the store keeps no per-trajectory weights)
+    _fields_ = [("traj_start", C.c_void_p), ("traj_len", C.c_void_p), ("traj_w", C.c_void_p), ("n_traj_dev", C.c_void_p),
+                ("n_live", C.c_int32), ("n_drop", C.c_int32)]
+
+
 class PackEntryT(C.Structure):
     _fields_ = [("src_off", C.c_int64), ("f_off", C.c_int64), ("b_off", C.c_int64),
                 ("out", C.c_int32), ("in_", C.c_int32)]
@@ -318,6 +323,7 @@ PROTOTYPES = {
     "osrl_replay_gather_w": [_i32, _P(_fp), _P(_fp), _P(_i32), _P(_f32), _i64, _i32, _vp, _u64, _u32, _vp, _vp, _vp],
     "osrl_replay_gather_n": [_i32, _P(_fp), _P(_fp), _P(_i32), _P(_f32), _i64, _i32, _vp, _u64, _u32, _vp, _vp, _vp, _vp],
     "osrl_seq_window_gather": [_P(SeqGatherT), _vp, _vp],
+    "osrl_seq_evict_front": [_P(SeqEvictT), _vp],
     "osrl_gauss_head": [_fp, _fp, _i32, _i32, _f32, _fp, _fp, _fp, _vp],
     "osrl_gauss_head_bwd": [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _f32, _fp, _vp],
     "osrl_gauss_ood_sample": [_fp, _fp, _i32, _i32, _i32, _fp, _vp],

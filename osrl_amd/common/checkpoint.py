@@ -18,6 +18,10 @@ reference's loader ignores:
 
 The device noise streams are functions of (seed, step), so a resumed run draws the noise the uninterrupted run
 would have drawn: save -> load -> continue is bit-identical to not stopping (tests/test_gpu_train_step.py).
+
+Stores that grow are training state too (``save_store`` / ``load_store``): an online loop that appends what it collects
+resumes with the rows, the ring geometry and the sampling weights it stopped with, in a file of its own beside the
+model's (``ReplayStore.state_dict`` / ``SequenceStore.state_dict``, common/replay.py).
 """
 from __future__ import annotations
 
@@ -106,4 +110,20 @@ def load_checkpoint(model, ckpt, resume: bool = True, strict: bool = True) -> Di
         eng.st.set_step(model._resume_step)
         if hasattr(eng, "temp_mv") and "temperature_moments" in extra["scalars"]:
             eng.temp_mv.copy_(extra["scalars"]["temperature_moments"])
+    return ckpt
+
+
+def save_store(store, path: str) -> None:
+    """``torch.save`` of ``store.state_dict()``: a ``ReplayStore`` / ``SequenceStore`` built with capacities (ValueError on
+    a fixed store, which is rebuilt from its dataset).  Host tensors, numbers, strings, tuples, lists and dicts only."""
+    torch.save(store.state_dict(), path)
+
+
+def load_store(store, ckpt) -> Dict[str, Any]:
+    """``ckpt``: a path or an already loaded dict, into a store built with the saved capacities, widths and flags
+    (ValueError naming a difference): written into the store's own allocations, so an attached engine keeps its graph
+    and follows at its next replay.  Returns the loaded dict."""
+    if not isinstance(ckpt, dict):
+        ckpt = torch.load(ckpt, map_location="cpu", weights_only=True)
+    store.load_state_dict(ckpt)
     return ckpt

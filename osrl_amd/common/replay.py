@@ -48,6 +48,24 @@ def ring_spans(cursor: int, m: int, capacity: int):
     return [(dst, src, first)] + ([(0, src + first, n - first)] if n > first else [])
 
 
+def seq_ring_plan(starts, lens, tail: int, mr: int, mt: int, capacity_rows: int, capacity_traj: int):
+    """Where a chunk of ``mt`` whole trajectories in ``mr`` rows lands in a ``SequenceStore(evict="oldest")`` whose live
+    trajectories, oldest first, occupy rows ``[starts[i], starts[i] + lens[i])`` and whose newest one ends at ``tail``:
+    ``(p, n_evict, new_tail)``.  ValueError when the chunk can never fit (``mr > capacity_rows`` or
+    ``mt > capacity_traj``).  The chunk stays contiguous: ``p = tail`` while it fits behind the newest trajectory, else
+    ``p = 0`` (the rows from ``tail`` to the end stay unused for this lap); then the oldest trajectories go, one at a
+    time, while there are too many slots in use or any live trajectory still touches ``[p, p + mr)``."""
+    tail, mr, mt, cr, ct = int(tail), int(mr), int(mt), int(capacity_rows), int(capacity_traj)
+    if mr > cr or mt > ct:
+        raise ValueError(f"the chunk ({mr} rows, {mt} trajectories) is larger than the store ({cr} rows, {ct} "
+                         "trajectories)")
+    s, n = np.asarray(starts, np.int64).reshape(-1), np.asarray(lens, np.int64).reshape(-1)
+    p = tail if tail + mr <= cr else 0
+    hit = np.nonzero((s < p + mr) & (s + n > p))[0]  # evicting oldest first: everything up to the last one that touches
+    k = max(0, s.shape[0] + mt - ct, int(hit[-1]) + 1 if hit.shape[0] else 0)
+    return p, k, p + mr
+
+
 def _done_of(d):
     if "done" in d:
         return d["done"]
@@ -285,6 +303,64 @@ class ReplayStore:
         if w_new is not None:
             self._build_cum()
 
+    # ---- checkpointing (common.checkpoint.save_store / load_store) ------------------------------------------------------
+    def state_dict(self) -> dict:
+        """The contents of a store built with ``capacity``, as host tensors, numbers and strings: the tables over the
+        live rows IN PHYSICAL ORDER (the ring as it lies, not unrolled), the ring's cursor, the raw sampling weights
+        and, with ``state_init``, the construction-time statistics.  Seeds and ranks belong to the constructor.
+        ValueError on a fixed store: that one is rebuilt from its dataset."""
+        if self.capacity is None:
+            raise ValueError("this store is fixed: it is rebuilt from its dataset, only a store built with capacity= "
+                             "is saved")
+        n = self.n_rows
+        sd = dict(kind="ReplayStore", format=1, capacity=self.capacity, widths=list(self.widths),
+                  scales=[float(x) for x in self.scales], state_init=self.state_init, n_rows=n, cursor=self._cursor,
+                  weighted=bool(self.weighted), tables=[t[:n].detach().cpu().clone() for t in self.tables],
+                  w64=self._w64[:n].detach().cpu().clone() if self.weighted else None)
+        if self.state_init:
+            sd["init_state_propotion"] = float(self.init_state_propotion)
+            sd["observations_std"] = torch.from_numpy(np.array(self.observations_std))
+            sd["actions_std"] = torch.from_numpy(np.array(self.actions_std))
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Make this store the saved one, in the allocations it has: same tables, cursor, live count and weights, so it
+        draws the same minibatches and every later ``append`` lands the same.  The store must have been built with the
+        saved capacity, widths, ``state_init`` and scales (ValueError naming the difference, before any device work).
+        Everything is written in place on the current stream -- an attached engine follows at its next replay;
+        ``version`` is incremented, and ``sample_epoch`` when the load switches between uniform and weighted."""
+        if self.capacity is None:
+            raise ValueError("this store is fixed: build it with capacity= to load a saved store into it")
+        if sd.get("kind") != "ReplayStore" or sd.get("format") != 1:
+            raise ValueError(f"not a saved ReplayStore (kind {sd.get('kind')!r}, format {sd.get('format')!r})")
+        for what, mine, theirs in (("capacity", self.capacity, sd["capacity"]),
+                                   ("state_init", self.state_init, sd["state_init"]),
+                                   ("widths", list(self.widths), list(sd["widths"])),
+                                   ("scales", [float(x) for x in self.scales], [float(x) for x in sd["scales"]])):
+            if mine != theirs:
+                raise ValueError(f"the saved store's {what} is {theirs}, this store's {mine}")
+        n = int(sd["n_rows"])
+        for t, src in zip(self.tables, sd["tables"]):
+            t[:n].copy_(src, non_blocking=True)
+            t[n:].zero_()
+        if sd["weighted"]:
+            self._alloc_weights()
+            self._w64[:n].copy_(sd["w64"], non_blocking=True)
+            self._w64[n:].zero_()
+        self.n_rows = self.n_total = n
+        self._cursor = int(sd["cursor"])
+        self._live.fill_(n)
+        if self.state_init:
+            self.init_state_propotion = float(sd["init_state_propotion"])
+            self.observations_std = sd["observations_std"].numpy().copy()
+            self.actions_std = sd["actions_std"].numpy().copy()
+        self.version += 1
+        if sd["weighted"]:
+            self._build_cum()
+        if self.weighted != bool(sd["weighted"]):
+            self.weighted = bool(sd["weighted"])
+            self.sample_epoch += 1
+
     def get_dataset_states(self):
         """(init_state_propotion, observations_std, actions_std) -- dataset.py:822-830; needs ``state_init``."""
         if not self.state_init:
@@ -362,8 +438,13 @@ class SequenceStore:
     ``traj_start`` / ``traj_len``, ``cdf`` and ``start_cdf`` are allocated once at their capacities and rewritten in
     place, the live trajectory count sits in one device word the window sampler reads (include/osrl_amd.h
     ``osrl_seq_gather_t.n_traj_dev``), and ``append`` adds whole trajectories after the live ones -- a captured CDT step
-    follows at its next replay.  (Switching an attached store between a uniform and a non-uniform distribution, or start
-    sampling on and off, changes the launch's arguments as it always did: re-attach the store.)"""
+    follows at its next replay.  With ``evict="oldest"`` a full store drops its oldest trajectories to make room
+    (``append``, ``evict_oldest``): the live trajectories stay dense and in age order in slots ``[0, n_traj)``, each one
+    contiguous in the row tables, ``tail`` is the row behind the newest one, and ``n_rows`` is the sum of the live
+    lengths -- the live rows are no longer a prefix of the row tables.  ``state_dict`` / ``load_state_dict`` save and
+    restore a store built with capacities.
+    (Switching an attached store between a uniform and a non-uniform distribution, or start sampling on and off, changes
+    the launch's arguments as it always did: re-attach the store.)"""
 
     # a fixed store (the constructor, from_tables without capacities): no live word, nothing remembered
     _live: Optional[torch.Tensor] = None
@@ -375,6 +456,10 @@ class SequenceStore:
     cost_reverse = False
     n_appended = 0
     version = 0
+    evict: Optional[str] = None          # "oldest": append makes room by dropping whole trajectories, oldest first
+    n_evicted = 0
+    tail: Optional[int] = None           # (evicting stores) the row after the newest trajectory's last row
+    _mirror: Optional[tuple] = None      # (evicting stores) host copy of the live (traj_start, traj_len), int64 arrays
 
     def __init__(self, trajectories, seq_len: int, device, reward_scale: float = 1.0, cost_scale: float = 1.0,
                  sample_prob=None, seed: int = 0, rank: int = 0, start_sampling: bool = False, prob: float = 0.4):
@@ -403,8 +488,11 @@ class SequenceStore:
         self._set_table("start_cdf", compute_start_index_sample_prob(tables, prob, with_cdf=True)[1], self.capacity_rows)
 
     def _live_tables(self) -> Dict[str, torch.Tensor]:
-        """The tables sliced to the live rows / trajectories (the tables themselves on a fixed store)."""
+        """The tables sliced to the live rows / trajectories (the tables themselves on a fixed store; the whole row tables
+        and the live trajectories on a store that evicts)."""
         r, n = self.n_rows, self.n_traj
+        if self.evict is not None:  # the live rows are wherever traj_start points: the whole row tables
+            r = self.capacity_rows
         return dict(observations=self.obs[:r], actions=self.act[:r], returns=self.ret[:r], cost_returns=self.cret[:r],
                     costs=self.cost[:r], traj_start=self.traj_start[:n], traj_len=self.traj_len[:n])
 
@@ -466,17 +554,23 @@ class SequenceStore:
     def from_tables(cls, tables: Dict[str, torch.Tensor], seq_len: int, reward_scale: float = 1.0,
                     cost_scale: float = 1.0, cdf: Optional[torch.Tensor] = None, seed: int = 0,
                     rank: int = 0, start_sampling: bool = False, prob: float = 0.4,
-                    capacity_rows: Optional[int] = None, capacity_traj: Optional[int] = None) -> "SequenceStore":
+                    capacity_rows: Optional[int] = None, capacity_traj: Optional[int] = None,
+                    evict: Optional[str] = None) -> "SequenceStore":
         """Wrap the flat device tables of ``common.ingest.process_sequence_dataset`` (nothing is copied).
         ``capacity_rows`` / ``capacity_traj`` (either one; the other defaults to the tables' size): a store that grows --
-        the tables are COPIED into allocations of those sizes, zero past the data, and ``append`` adds trajectories."""
+        the tables are COPIED into allocations of those sizes, zero past the data, and ``append`` adds trajectories.
+        ``evict="oldest"`` (only with capacities, ValueError otherwise): a full store drops its oldest trajectories."""
         self = cls.__new__(cls)
         self._wrap(tables, seq_len, reward_scale, cost_scale, cdf, seed, rank, start_sampling, prob, capacity_rows,
-                   capacity_traj)
+                   capacity_traj, evict)
         return self
 
     def _wrap(self, tables, seq_len, reward_scale, cost_scale, cdf, seed, rank, start_sampling, prob,
-              capacity_rows=None, capacity_traj=None) -> None:
+              capacity_rows=None, capacity_traj=None, evict=None) -> None:
+        if evict not in (None, "oldest"):
+            raise ValueError(f'evict must be None or "oldest", got {evict!r}')
+        if evict is not None and capacity_rows is None and capacity_traj is None:
+            raise ValueError('evict="oldest" needs a store built with capacity_rows= / capacity_traj=')
         self.T, self.device = int(seq_len), tables["observations"].device
         self.obs, self.act = tables["observations"].contiguous(), tables["actions"].contiguous()
         self.ret, self.cret, self.cost = tables["returns"], tables["cost_returns"], tables["costs"]
@@ -500,6 +594,10 @@ class SequenceStore:
             self._live = torch.full((1,), self.n_traj, dtype=torch.int32, device=self.device)
             if cdf is not None:
                 cdf = grown(cdf.to(torch.float32), ct)
+            if evict is not None:
+                self.evict, self.tail = evict, self.n_rows
+                self._mirror = (tables["traj_start"].cpu().numpy().astype(np.int64).reshape(-1),
+                                tables["traj_len"].cpu().numpy().astype(np.int64).reshape(-1))
         self.cdf = cdf
         if cdf is not None:
             self._dist = ("cdf",)
@@ -537,7 +635,8 @@ class SequenceStore:
                      cost_bins: int = 60, npb: int = 5, random_aug: float = 0, aug_rmin: float = 0,
                      aug_rmax: float = 600, aug_cmin: float = 5, aug_cmax: float = 50, cgap: float = 5,
                      rstd: float = 1, cstd: float = 0.2, draws: Optional[dict] = None,
-                     capacity_rows: Optional[int] = None, capacity_traj: Optional[int] = None) -> "SequenceStore":
+                     capacity_rows: Optional[int] = None, capacity_traj: Optional[int] = None,
+                     evict: Optional[str] = None) -> "SequenceStore":
         """``SequenceDataset(dataset, seq_len, reward_scale, cost_scale, ...)`` (dataset.py:633-747) with the whole
         preprocessing on device.  The constructor's branches run in the reference's order: ``pf_only`` (which only
         suppresses the augmentations: the reference discards select_optimal_trajectory's result), else
@@ -551,8 +650,12 @@ class SequenceStore:
         distribution is installed afterwards with ``enable_pf_sampling()`` (in the reference ``cost_sample`` wins
         over ``pf_sample``, and its beta is hard-wired to 1, dataset.py:734-737).
         ``capacity_rows`` / ``capacity_traj``: a store that grows (``append``); the capacities count the augmented
-        trajectories too."""
+        trajectories too.  ``evict="oldest"`` (only with capacities): see ``append``."""
         from .ingest import augmentation, compute_cost_sample_prob, process_sequence_dataset, random_augmentation
+        if evict not in (None, "oldest"):
+            raise ValueError(f'evict must be None or "oldest", got {evict!r}')
+        if evict is not None and capacity_rows is None and capacity_traj is None:
+            raise ValueError('evict="oldest" needs a store built with capacity_rows= / capacity_traj=')
         if pf_sample:
             raise NotImplementedError("pf_sample=True is not built by from_dataset: build the store without it and "
                                       "call enable_pf_sampling() (compute_sample_prob, dataset.py:399-436, on device)")
@@ -569,7 +672,7 @@ class SequenceStore:
                                         seed=seed, draws=draws)
         cdf = compute_cost_sample_prob(tables, cost_transform, with_cdf=True)[1] if cost_sample else None
         self = cls.from_tables(tables, seq_len, reward_scale, cost_scale, cdf, seed, rank, start_sampling, prob,
-                               capacity_rows, capacity_traj)
+                               capacity_rows, capacity_traj, evict)
         self.cost_reverse = bool(cost_reverse)
         self._dist = ("cost", cost_transform) if cost_sample else None
         self.n_original = n_orig
@@ -617,6 +720,7 @@ class SequenceStore:
         """ValueError unless ``append`` (without ``weights=``) would take a chunk of ``n_traj`` trajectories in ``n_rows``
         rows with these column counts (``observations=17, actions=6``): the store grows, the chunk fits, the widths are
         the tables', and the trajectory distribution can follow (not ``set_sample_prob`` weights, not a ready-made cdf).
+        A store that evicts makes room: only a chunk larger than the store itself does not fit.
         Nothing is changed: for callers that produce the chunk on device and want the refusal first."""
         if self._live is None:
             raise ValueError("this store is fixed: build it with capacity_rows= / capacity_traj= to append")
@@ -630,6 +734,11 @@ class SequenceStore:
         if kind == "weights":
             raise ValueError("the store draws by set_sample_prob's weights: append(dataset, weights=) needs the new "
                              "trajectories' weights")
+        if self.evict is not None:
+            if int(n_rows) > self.capacity_rows or int(n_traj) > self.capacity_traj:
+                raise ValueError(f"the chunk ({int(n_rows)} rows, {int(n_traj)} trajectories) is larger than the store "
+                                 f"({self.capacity_rows} rows, {self.capacity_traj} trajectories)")
+            return
         if self.n_traj + int(n_traj) > self.capacity_traj or self.n_rows + int(n_rows) > self.capacity_rows:
             raise ValueError(f"the chunk ({int(n_rows)} rows, {int(n_traj)} trajectories) does not fit: {self.n_rows} of "
                              f"{self.capacity_rows} rows and {self.n_traj} of {self.capacity_traj} trajectories are live")
@@ -637,15 +746,18 @@ class SequenceStore:
     def append(self, dataset, weights=None) -> None:
         """Add the complete episodes of ``dataset`` (DSRL keys, host or device) to a store built with capacities: the
         chunk goes through ``process_sequence_dataset`` as a dataset of its own (with the store's ``cost_reverse``) and
-        its trajectories are appended after the live ones, in place, on the current stream.  There is no ring: a chunk
-        that does not fit raises ValueError and changes nothing.  New chunks are not augmented (``n_original`` /
+        its trajectories are appended after the live ones, in place, on the current stream.  Without ``evict`` there is no
+        ring: a chunk that does not fit raises ValueError and changes nothing.  New chunks are not augmented (``n_original`` /
         ``n_augmented`` describe the construction-time data, ``n_appended`` counts the rest).
         The trajectory distribution follows the data: ``cost_sample`` (its transform), ``enable_pf_sampling`` (its beta
         and frontier) and start sampling (its ``prob``) are recomputed over the live trajectories into the same buffers.
         After ``set_sample_prob`` the new trajectories need ``weights=`` (ValueError without); a store whose distribution
-        was given as a ready-made cdf cannot extend it (ValueError: call ``set_sample_prob`` first)."""
-        from .ingest import (compute_cost_sample_prob, compute_sample_prob, compute_start_index_sample_prob,
-                             process_sequence_dataset, sample_prob_from_weights)
+        was given as a ready-made cdf cannot extend it (ValueError: call ``set_sample_prob`` first).
+        ``evict="oldest"``: a chunk that does not fit makes room instead (``seq_ring_plan``, DESIGN.md "Stores that
+        grow"): it lands behind the newest trajectory, or at row 0 when it does not fit there, and the oldest
+        trajectories are dropped, whole, until none touches its rows and there are slots for its trajectories; only a
+        chunk larger than the store raises.  ``n_evicted`` counts the dropped trajectories."""
+        from .ingest import process_sequence_dataset
         if self._live is None:
             raise ValueError("this store is fixed: build it with capacity_rows= / capacity_traj= to append")
         shape = lambda x: tuple(x.shape) if torch.is_tensor(x) else np.shape(x)  # noqa: E731
@@ -663,13 +775,28 @@ class SequenceStore:
             raise ValueError("weights= extends the weights of set_sample_prob, which this store does not draw by")
         t = process_sequence_dataset(dataset, self.cost_reverse, self.device)
         mt, mr = int(t["traj_start"].shape[0]), int(t["observations"].shape[0])
-        if self.n_traj + mt > self.capacity_traj or self.n_rows + mr > self.capacity_rows:
+        if self.evict is not None:
+            if mr > self.capacity_rows or mt > self.capacity_traj:
+                raise ValueError(f"the chunk ({mr} rows, {mt} trajectories) is larger than the store "
+                                 f"({self.capacity_rows} rows, {self.capacity_traj} trajectories)")
+        elif self.n_traj + mt > self.capacity_traj or self.n_rows + mr > self.capacity_rows:
             raise ValueError(f"the chunk ({mr} rows, {mt} trajectories) does not fit: {self.n_rows} of "
                              f"{self.capacity_rows} rows and {self.n_traj} of {self.capacity_traj} trajectories are live")
         w_new = None if weights is None else _checked_weights(weights, mt, "trajectory", positive_sum=False).to(self.device)
         if mt == 0:
             return
         r0, n0 = self.n_rows, self.n_traj
+        if self.evict is not None:
+            # the plan on the host mirror (one small copy of the chunk's lengths), then in stream order: drop the oldest
+            # entries and lower the live word (one launch), write the rows, add the entries -- a sampler replayed on this
+            # stream never sees an entry that points at overwritten rows
+            lens = t["traj_len"].cpu().numpy().astype(np.int64)
+            r0, k, tail = seq_ring_plan(*self._mirror, self.tail, mr, mt, self.capacity_rows, self.capacity_traj)
+            self._drop_front(k)
+            n0 = self.n_traj
+            self._mirror = (np.concatenate([self._mirror[0], r0 + np.cumsum(lens) - lens]),
+                            np.concatenate([self._mirror[1], lens]))
+            self.tail = tail
         self.obs[r0:r0 + mr].copy_(t["observations"].reshape(mr, -1))
         self.act[r0:r0 + mr].copy_(t["actions"].reshape(mr, -1))
         self.ret[r0:r0 + mr].copy_(t["returns"])
@@ -677,9 +804,20 @@ class SequenceStore:
         self.cost[r0:r0 + mr].copy_(t["costs"])
         self.traj_start[n0:n0 + mt].copy_(t["traj_start"] + r0)
         self.traj_len[n0:n0 + mt].copy_(t["traj_len"])
-        self.n_rows, self.n_traj = r0 + mr, n0 + mt
+        self.n_rows, self.n_traj = (r0 + mr, n0 + mt) if self.evict is None else (int(self._mirror[1].sum()), n0 + mt)
         self.n_appended += mt
         self.version += 1
+        if kind == "weights":
+            self._traj_w[n0:n0 + mt].copy_(w_new)
+        self._redistribute()
+        self._live.fill_(self.n_traj)  # last: the tables and the distributions are in place when the count moves
+
+    def _redistribute(self) -> None:
+        """The trajectory distribution and the start distribution over the live trajectories, from the recipe the store
+        remembers (``_dist``, ``_start_prob``), into the buffers the sampler already reads."""
+        from .ingest import (compute_cost_sample_prob, compute_sample_prob, compute_start_index_sample_prob,
+                             sample_prob_from_weights)
+        kind = None if self._dist is None else self._dist[0]
         lt = self._live_tables()
         if kind == "cost":
             self._set_table("cdf", compute_cost_sample_prob(lt, self._dist[1], with_cdf=True)[1], self.capacity_traj)
@@ -687,10 +825,152 @@ class SequenceStore:
             self._set_table("cdf", compute_sample_prob(lt, self._dist[2], self._dist[1], with_cdf=True)[1],
                             self.capacity_traj)
         elif kind == "weights":
-            self._traj_w[n0:n0 + mt].copy_(w_new)
             self._set_table("cdf", sample_prob_from_weights(self._traj_w[:self.n_traj], with_cdf=True)[1],
                             self.capacity_traj)
         if self._start_prob is not None:
             self._set_table("start_cdf", compute_start_index_sample_prob(lt, self._start_prob, with_cdf=True)[1],
                             self.capacity_rows)
-        self._live.fill_(self.n_traj)  # last: the tables and the distributions are in place when the count moves
+
+    # ---- eviction -----------------------------------------------------------------------------------------------------
+    def _drop_front(self, k: int) -> None:
+        """The ``k`` oldest trajectories leave the tables, the host mirror and the counts: one ``osrl_seq_evict_front``
+        launch on the current stream shifts ``traj_start`` / ``traj_len`` (and the ``set_sample_prob`` weights) to slot
+        0 in place, zeroes the vacated slots and lowers the live word.  The rows stay where they are."""
+        if k == 0:
+            return
+        e = L.SeqEvictT()
+        e.traj_start, e.traj_len, e.n_traj_dev = self.traj_start.data_ptr(), self.traj_len.data_ptr(), self._live.data_ptr()
+        e.traj_w = None if self._traj_w is None else self._traj_w.data_ptr()
+        e.n_live, e.n_drop = self.n_traj, k
+        L.check(L.load().osrl_seq_evict_front(e, cur_stream()), "osrl_seq_evict_front")
+        self._mirror = (self._mirror[0][k:], self._mirror[1][k:])
+        self.n_traj -= k
+        self.n_rows = int(self._mirror[1].sum())
+        self.n_evicted += k
+
+    def evict_oldest(self, k: int) -> None:
+        """Drop the ``k`` oldest trajectories of a store built with ``evict="oldest"``, in place on the current stream
+        (their rows are simply no longer referenced), and recompute the distributions over the rest.
+        ``0 <= k < n_traj`` -- the store never becomes empty this way -- ValueError otherwise, nothing changed.
+        ``n_evicted`` and, unless ``k`` is 0, ``version`` move."""
+        if self.evict is None:
+            raise ValueError('this store does not evict: build it with evict="oldest"')
+        k = int(k)
+        if not 0 <= k < self.n_traj:
+            raise ValueError(f"evict_oldest({k}): 0 .. {self.n_traj - 1} of the {self.n_traj} live trajectories can go")
+        if k == 0:
+            return
+        kind = None if self._dist is None else self._dist[0]
+        if kind == "cdf":
+            raise ValueError("the trajectory distribution was given as a cdf: call set_sample_prob(weights) before "
+                             "evict_oldest")
+        self._drop_front(k)
+        self.version += 1
+        self._redistribute()
+
+    # ---- checkpointing (common.checkpoint.save_store / load_store) ------------------------------------------------------
+    def _recipe(self):
+        """``_dist`` as plain data: the tuple forms as they are, a frontier as its tensors."""
+        d = self._dist
+        if d is None or d[0] in ("weights", "cdf"):
+            return None if d is None else (d[0],)
+        if d[0] == "cost":
+            if callable(d[1]):
+                raise ValueError('a python callable cost_transform cannot be saved: use ("affine", a, b) or '
+                                 '("reciprocal", b)')
+            return ("cost", tuple(d[1]))
+        f = d[2]
+        cpu = lambda x: x.detach().cpu().clone()  # noqa: E731
+        return ("pf", float(d[1]), dict(coef=cpu(f.coef_dev), deg=cpu(f.deg_dev), pareto_idx=cpu(f._pidx),
+                                        pcount=cpu(f._pcount), stats=cpu(f.stats)))
+
+    def _config(self) -> dict:
+        return dict(capacity_rows=self.capacity_rows, capacity_traj=self.capacity_traj, seq_len=self.T,
+                    observations=self.od, actions=self.ad, reward_scale=self.reward_scale, cost_scale=self.cost_scale,
+                    evict=self.evict)
+
+    def state_dict(self) -> dict:
+        """The contents of a store built with capacities, as host tensors, numbers, strings and tuples: the row tables as
+        they lie up to the last used row (the physical layout: where the next chunk lands and what it evicts depends on
+        it), the live trajectory tables, ``tail`` and the counters, the ``set_sample_prob`` weights, the cdf tables, and
+        the recipe of the trajectory distribution (a frontier as its tensors).  Seeds and ranks belong to the constructor.
+        ValueError on a fixed store (it is rebuilt from its dataset) and with a python callable ``cost_transform``."""
+        if self._live is None:
+            raise ValueError("this store is fixed: it is rebuilt from its dataset, only a store built with capacity_rows= "
+                             "/ capacity_traj= is saved")
+        recipe = self._recipe()
+        n = self.n_traj
+        used = self.n_rows if self.evict is None else int((self._mirror[0] + self._mirror[1]).max())
+        cpu = lambda x, m: None if x is None else x[:m].detach().cpu().clone()  # noqa: E731
+        return dict(kind="SequenceStore", format=1, config=self._config(), n_traj=n, n_rows=self.n_rows, used_rows=used,
+                    tail=self.tail, n_evicted=self.n_evicted, n_appended=self.n_appended,
+                    n_original=getattr(self, "n_original", None), n_augmented=getattr(self, "n_augmented", None),
+                    cost_reverse=bool(self.cost_reverse), start_prob=self._start_prob, dist=recipe,
+                    tables=dict(observations=cpu(self.obs, used), actions=cpu(self.act, used), returns=cpu(self.ret, used),
+                                cost_returns=cpu(self.cret, used), costs=cpu(self.cost, used),
+                                traj_start=cpu(self.traj_start, n), traj_len=cpu(self.traj_len, n)),
+                    traj_w=cpu(self._traj_w, n), cdf=cpu(self.cdf, n), start_cdf=cpu(self.start_cdf, used))
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Make this store the saved one, in the allocations it has: it then draws the same windows, and every later
+        ``append`` lands, evicts and reweights the same.  The store must have been built with the saved capacities,
+        widths, ``seq_len``, scales and ``evict`` (ValueError naming the difference, before any device work).  The
+        tables are written in place on the current stream, live word last, so an attached engine follows at its next
+        replay; ``version`` is incremented.  (A store that had no ``cdf`` / ``start_cdf`` table and gets one, or the
+        reverse, changes the gather's arguments as ``set_sample_prob`` does: re-attach it.)  What the augmentation of
+        this store's own construction left behind (``aug_info``) does not describe the loaded data and is dropped."""
+        from .ingest import Frontier
+        if self._live is None:
+            raise ValueError("this store is fixed: build it with capacity_rows= / capacity_traj= to load a saved store "
+                             "into it")
+        if sd.get("kind") != "SequenceStore" or sd.get("format") != 1:
+            raise ValueError(f"not a saved SequenceStore (kind {sd.get('kind')!r}, format {sd.get('format')!r})")
+        mine = self._config()
+        for what, theirs in sd["config"].items():
+            if mine[what] != theirs:
+                raise ValueError(f"the saved store's {what} is {theirs}, this store's {mine[what]}")
+        n, used, dev = int(sd["n_traj"]), int(sd["used_rows"]), self.device
+        tb = sd["tables"]
+        for dst, key in ((self.obs, "observations"), (self.act, "actions"), (self.ret, "returns"),
+                         (self.cret, "cost_returns"), (self.cost, "costs")):
+            dst[:used].copy_(tb[key])
+            dst[used:].zero_()
+        for dst, key in ((self.traj_start, "traj_start"), (self.traj_len, "traj_len")):
+            dst[:n].copy_(tb[key])
+            dst[n:].zero_()
+        if sd["traj_w"] is not None:
+            if self._traj_w is None:
+                self._traj_w = torch.zeros(self.capacity_traj, dtype=torch.float64, device=dev)
+            self._traj_w[:n].copy_(sd["traj_w"])
+            self._traj_w[n:].zero_()
+        else:
+            self._traj_w = None
+        for name, cap in (("cdf", self.capacity_traj), ("start_cdf", self.capacity_rows)):
+            if sd[name] is None:
+                if getattr(self, name) is not None:
+                    setattr(self, name, None)
+                    self._describe()
+            else:
+                if getattr(self, name) is not None:
+                    getattr(self, name).zero_()
+                self._set_table(name, sd[name].to(dev), cap)
+        d = sd["dist"]
+        if d is not None and d[0] == "pf":
+            f = {k: v.to(dev) for k, v in d[2].items()}
+            d = ("pf", float(d[1]), Frontier(f["coef"], f["deg"], f["pareto_idx"], f["pcount"], f["stats"]))
+        elif d is not None and d[0] == "cost":
+            d = ("cost", tuple(d[1]))
+        self._dist = None if d is None else tuple(d)
+        self._start_prob = sd["start_prob"]
+        self.cost_reverse = bool(sd["cost_reverse"])
+        self.n_traj, self.n_rows, self.tail = n, int(sd["n_rows"]), sd["tail"]
+        self.n_evicted, self.n_appended = int(sd["n_evicted"]), int(sd["n_appended"])
+        for k in ("n_original", "n_augmented"):
+            if sd[k] is not None:
+                setattr(self, k, int(sd[k]))
+        self.aug_info = None
+        if self.evict is not None:
+            self._mirror = (tb["traj_start"].numpy().astype(np.int64).reshape(-1),
+                            tb["traj_len"].numpy().astype(np.int64).reshape(-1))
+        self.version += 1
+        self._live.fill_(n)
