@@ -1352,6 +1352,55 @@ int osrl_ipc_all_gather(const osrl_ipc_t* x, const float* src, int64_t n, float*
  * Synchronous copy: for the points where the host synchronises anyway. */
 int osrl_ipc_status(const osrl_ipc_t* x, uint32_t* words4);
 
+/* ---- learned-dynamics vector environment (model_env.hip) -----------------------------------------------------------
+ * An ensemble of n_models ReLU MLPs [state_dim + action_dim, hidden.., state_dim + 2] fitted on logged transitions
+ * (osrl_amd/algorithms/dynamics.py), stepped as a vector environment with osrl_env_step's interface and bookkeeping:
+ * one launch per environment step, one workgroup per 16-episode tile, the whole ensemble with its activations in LDS
+ * (act_vec.hip's layer scheme over the packed forward weights, which the fused optimizer step keeps current: the
+ * environment follows training in place).  Every layer dimension <= 512, state_dim <= 256.
+ * Per live episode e (acc[e][3] == 0; a finished one keeps state, obs and totals):
+ *   x = [(s - mu_s) / sd_s, clip(a, +-max_action)];  y_m = net_m(x), m = 0 .. n_models - 1;
+ *   ybar = (y_0 + y_1 + ..., in that order) * (1 / n_models);
+ *   d = max_m sqrt(sum_{k < state_dim} (y_m[k] - ybar[k])^2 / state_dim)      (the members' disagreement, normalised units)
+ *   yh = ybar (MEAN) | y_member (MEMBER) | y_j (RANDOM: j = member_in[e] when member_in is given, else word x of
+ *        Philox4x32-10(counter {episode_base + e, the episode's step acc[e][2], 0, 14}, key *seed) mod n_models);
+ *        every mode evaluates every member, member k's output has the same bits in each;
+ *   s' = s + (mu_d + sd_d * yh[:state_dim]), clamped to [s_lo, s_hi] when both are given;
+ *   r = mu_r + sd_r * yh[state_dim], minus reward_penalty * d when reward_penalty != 0;
+ *   cost = yh[state_dim + 1] > 0.5 ? 1 : 0;
+ *   acc / step_out / state / obs: osrl_env_step's;  unc[e] = {max over steps of d, sum over steps of d}.
+ * An episode's trajectory is the same bits whatever `episodes` is, whichever tile row it sits in and whatever its
+ * neighbours do (no split-K, no arithmetic across rows). */
+enum { OSRL_MODEL_ENV_MEAN = 0, OSRL_MODEL_ENV_MEMBER = 1, OSRL_MODEL_ENV_RANDOM = 2 };
+#define OSRL_MODEL_ENV_MAX_WIDTH 512
+#define OSRL_MODEL_ENV_MAX_STATE 256
+typedef struct {
+  osrl_gemv_net_t net[OSRL_MAX_NETS]; /* out_scale 1, identity output */
+  const float* mu_s;  /* [state_dim] */
+  const float* sd_s;  /* [state_dim] */
+  const float* mu_d;  /* [state_dim] */
+  const float* sd_d;  /* [state_dim] */
+  const float* mu_r;  /* [1] */
+  const float* sd_r;  /* [1] */
+  const float* s_lo;  /* [state_dim] or NULL (with s_hi): no clamp */
+  const float* s_hi;
+  const uint64_t* seed;     /* [1], read in RANDOM mode without member_in */
+  const int32_t* member_in; /* [episodes] or NULL */
+  int32_t n_models, state_dim, action_dim, episode_len;
+  int32_t mode, member;
+  uint32_t episode_base;
+  int32_t pad_;
+  float max_action, cost_scale, reward_penalty, pad2_;
+} osrl_model_env_t;
+int osrl_model_env_step(const osrl_model_env_t* env, const float* act, float* state, float* obs, int32_t obs_ld,
+                        float* acc, float* unc /* [E,2] */, float* step_out /* optional [E,2] */, int32_t episodes,
+                        void* stream);
+/* The train step's preparation (engine/dynamics.py): xs[b] = (obs[b] - mu_s) / sd_s  [rows, state_dim];
+ * target[b] = {(nobs[b] - obs[b] - mu_d) / sd_d, (rew[b] - mu_r) / sd_r, cost[b]}  [rows, state_dim + 2]. */
+int osrl_dyn_prepare(const float* obs, const float* nobs, const float* rew, const float* cost, const float* mu_s,
+                     const float* sd_s, const float* mu_d, const float* sd_d, const float* mu_r, const float* sd_r,
+                     int32_t rows, int32_t state_dim, float* xs, float* target, void* stream);
+
 /* Diagnostics (diag.hip): where the HIP runtime of this process keeps kernel arguments -- *where = 1 device memory,
  * 0 host memory (every wave then fetches its launch arguments over PCIe; see osrl_args_begin), -1 unknown.  dev_scratch:
  * 8 bytes of device memory.  Synchronises `stream`; not for the hot path. */

@@ -175,6 +175,18 @@ class PolicyT(C.Structure):
 
 
 POLICY_MLP, POLICY_GAUSS, POLICY_BCQ = 0, 1, 2
+MODEL_ENV_MEAN, MODEL_ENV_MEMBER, MODEL_ENV_RANDOM = 0, 1, 2
+MODEL_ENV_MODES = {"mean": MODEL_ENV_MEAN, "member": MODEL_ENV_MEMBER, "random": MODEL_ENV_RANDOM}
+MODEL_ENV_MAX_WIDTH, MODEL_ENV_MAX_STATE = 512, 256  # OSRL_MODEL_ENV_MAX_WIDTH / _MAX_STATE: the step kernel's LDS tile
+
+
+class ModelEnvT(C.Structure):  # osrl_model_env_t
+    _fields_ = [("net", GemvNetT * MAX_NETS)] + \
+        [(n, C.c_void_p) for n in ("mu_s", "sd_s", "mu_d", "sd_d", "mu_r", "sd_r", "s_lo", "s_hi", "seed",
+                                   "member_in")] + \
+        [(n, C.c_int32) for n in ("n_models", "state_dim", "action_dim", "episode_len", "mode", "member")] + \
+        [("episode_base", C.c_uint32), ("pad_", C.c_int32), ("max_action", C.c_float), ("cost_scale", C.c_float),
+         ("reward_penalty", C.c_float), ("pad2_", C.c_float)]
 POLICY_MAX_ROWS = 4
 POLICY_MAX_ENVS = 64  # OSRL_POLICY_MAX_ENVS
 CDT_POLICY_MAX_ENVS = 64  # OSRL_CDT_POLICY_MAX_ENVS
@@ -209,6 +221,8 @@ _P = C.POINTER
 PROTOTYPES = {
     "osrl_mlp_forward": [_P(MlpT), _P(RowsT), _P(ActsT), _vp],
     "osrl_env_step": [_P(EnvT), _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp],
+    "osrl_model_env_step": [_P(ModelEnvT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
+    "osrl_dyn_prepare": [_vp] * 10 + [_i32, _i32, _vp, _vp, _vp],
     "osrl_env_collect": [_P(EnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _i32, _vp],
     "osrl_cdt_collect": [_P(EnvT), _P(CollectT), _P(CdtWindowT), _vp, _vp, _i32, _vp],
     "osrl_cdt_rollout_pick": [_vp, _i32, _i32, _i32, _i32, _vp, _f32, _vp, _vp],

@@ -99,11 +99,11 @@ class RolloutMixin:
         (gym-style) env takes the reference's episode-by-episode loop.  ``schedule`` matters for a list of environments
         only: "waves" (default) starts N episodes and waits for the longest; "refill" gives a slot whose episode ended
         the next episode at once (``rollout_jobs``)."""
-        from ..common.synthetic_env import VecSyntheticSafeEnv
+        from ..common.synthetic_env import DeviceVecEnv
         from ..engine.act import check_schedule
         check_schedule(schedule)
         self._before_evaluate()
-        if isinstance(self.env, VecSyntheticSafeEnv):
+        if isinstance(self.env, DeviceVecEnv):  # (VecSyntheticSafeEnv, or a ModelVecEnv: common/model_env.py)
             from ..engine.rollout import evaluate_batched
             cs = self._cost_scale()
             return self._scale_results(*evaluate_batched(self, self.EVAL_KIND, eval_episodes,

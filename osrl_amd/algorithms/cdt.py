@@ -300,12 +300,12 @@ class CDTTrainer:
         batch on device (engine/rollout.py ``CDTBatchedRollout``).  With a list or tuple of N host environments rollout
         ``j`` runs on environment ``j % N``, N rollouts at a time in lockstep (``rollout_many``), or with
         ``schedule="refill"`` as one job queue (``evaluate_targets``)."""
-        from ..common.synthetic_env import VecSyntheticSafeEnv
+        from ..common.synthetic_env import DeviceVecEnv
         from ..engine.act import check_schedule
         check_schedule(schedule)
         if isinstance(self.env, (list, tuple)):
             return self.evaluate_targets(num_rollouts, [(target_return, target_cost)], schedule=schedule)[0]
-        if isinstance(self.env, VecSyntheticSafeEnv):
+        if isinstance(self.env, DeviceVecEnv):
             if self.env.E != num_rollouts:
                 raise ValueError(f"the vector environment holds {self.env.E} episodes, evaluate() was asked for "
                                  f"{num_rollouts}")
@@ -403,11 +403,11 @@ class CDTTrainer:
         ``evaluate`` per pair, any other size is a ValueError.  With any other environment this is one ``evaluate`` per
         pair.  ``schedule="refill"`` (list of environments): the same jobs as one queue, where a slot
         whose episode has ended takes the next job at once (``rollout_jobs``; the run is kept as ``last_refill``)."""
-        from ..common.synthetic_env import VecSyntheticSafeEnv
+        from ..common.synthetic_env import DeviceVecEnv
         from ..engine.act import check_schedule
         check_schedule(schedule)
         targets = [(float(tr), float(tc)) for tr, tc in targets]
-        if isinstance(self.env, VecSyntheticSafeEnv):
+        if isinstance(self.env, DeviceVecEnv):
             k, G = int(num_rollouts), len(targets)
             if G > 1 and self.env.E == G * k:  # the whole grid as one batched rollout, target-major
                 ro = self._batched_rollout()

@@ -1,0 +1,171 @@
+"""A fitted ensemble dynamics model (algorithms/dynamics.py) stepped on device as a vector environment.
+
+``ModelVecEnv`` has ``VecSyntheticSafeEnv``'s interface -- ``E``, ``state_dim``, ``episode_len``, ``state``, ``acc``,
+``desc``, ``reset``, ``step`` -- so ``BatchedRollout`` and ``CDTBatchedRollout`` (engine/rollout.py) drive it unchanged:
+``evaluate`` of all six trainers, CDT's ``evaluate_targets`` grid included, on the dynamics a dataset describes.  One HIP
+launch per environment step for all episodes (csrc/model_env.hip); the model's packed weights are read in place, so the
+environment follows ``DynamicsTrainer`` steps as rollouts follow a policy.
+
+What comes out is a model's opinion: its error grows with the rollout length and with the shift between the policy and the
+data.  ``disagreement()`` -- how far the members' predictions lie apart along each episode -- is the trust signal.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .synthetic_env import DeviceVecEnv
+
+
+class ModelVecEnv(DeviceVecEnv):
+    """``episodes`` episodes of ``model`` in HBM: ``state [E, od]``, ``acc [E, 4] = (return, cost * cost_scale, length,
+    done)`` and ``unc [E, 2] = (max, sum over the steps taken)`` of the members' disagreement.
+
+    ``init_states``: ``[n, od]`` rows (tensor or array) or a ``ReplayStore(state_init=True)``, whose initial observations
+    are taken; episode ``e`` starts at row ``(base_seed + e) % n``.  ``mode``: "mean" follows the ensemble mean, "member"
+    follows member ``member``, "random" a member drawn per episode and step from ``seed`` (Philox keyed by the episode id
+    ``base_seed + e`` and the episode's own step).  ``reward_penalty`` lambda: ``r -= lambda * disagreement`` (MOPO).
+    ``clip_states``: next states are clamped to the model's ``s_lo`` / ``s_hi``.  ``seed`` lives in device memory and
+    may be set between runs; ``mode``, ``member`` and ``reward_penalty`` are launch arguments: changing them moves
+    ``launch_epoch``, on which a rollout drops its captured graph."""
+
+    def __init__(self, model, init_states, episodes: int, episode_len: int, max_action: float = 1.0, base_seed: int = 0,
+                 mode: str = "mean", member: int = 0, reward_penalty: float = 0.0, clip_states: bool = True,
+                 seed: int = 0):
+        import torch
+
+        from .. import _lib as L
+        from ..engine.core import require_cuda
+        self.model, self.E, self.base_seed = model, int(episodes), int(base_seed)
+        self.device = require_cuda(model.device)
+        L.load()
+        self.state_dim, self.action_dim, self.episode_len = model.state_dim, model.action_dim, int(episode_len)
+        self.max_action, self.clip_states = float(max_action), bool(clip_states)
+        if self.E < 1 or self.episode_len < 1:
+            raise ValueError("ModelVecEnv needs episodes >= 1 and episode_len >= 1")
+        rows = self._init_rows(init_states)
+        if rows.dim() != 2 or rows.shape[1] != self.state_dim or rows.shape[0] < 1:
+            raise ValueError(f"init_states must be [n >= 1, {self.state_dim}], got {tuple(rows.shape)}")
+        idx = (self.base_seed + torch.arange(self.E, device=self.device)) % rows.shape[0]
+        # the initial states are a function of (init_states, base_seed) only: kept in HBM, reset() is a device copy
+        self.state0 = rows.index_select(0, idx).contiguous()
+        f = dict(dtype=torch.float32, device=self.device)
+        self.state = torch.zeros(self.E, self.state_dim, **f)
+        self.acc = torch.zeros(self.E, 4, **f)
+        self.unc = torch.zeros(self.E, 2, **f)
+        self.extra_state = (self.unc,)  # what a step changes beside state / acc (BatchedRollout._snapshot)
+        self._seed = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.member_in = None  # int32 [E] on the device: injected member choices of mode "random" (tests)
+        self.launch_epoch = 0
+        self._mode, self._member, self._penalty = "mean", 0, 0.0
+        self.seed = seed
+        self.set_mode(mode, member)
+        self.reward_penalty = reward_penalty
+        model.repack()
+
+    def _init_rows(self, init_states):
+        import torch
+        if hasattr(init_states, "tables"):  # a ReplayStore
+            if not getattr(init_states, "state_init", False):
+                raise ValueError("initial states from a store: build the ReplayStore with state_init=True")
+            obs, init = init_states.live(0), init_states.live(6).reshape(-1)
+            return obs[init == 1.0].to(self.device, torch.float32).contiguous()
+        return torch.as_tensor(np.asarray(init_states) if not torch.is_tensor(init_states) else init_states).to(
+            device=self.device, dtype=torch.float32).contiguous()
+
+    # ---- what may change between runs ---------------------------------------------------------------------------------
+    @property
+    def seed(self) -> int:
+        return int(self._seed.item())
+
+    @seed.setter
+    def seed(self, v: int) -> None:
+        self._seed.fill_(int(v) & 0x7FFFFFFFFFFFFFFF)  # (device memory: a captured launch follows)
+
+    @property
+    def mode(self) -> str:
+        return self._mode
+
+    @property
+    def member(self) -> int:
+        return self._member
+
+    def set_mode(self, mode: str, member: int = 0) -> None:
+        from .. import _lib as L
+        if mode not in L.MODEL_ENV_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(L.MODEL_ENV_MODES)}")
+        if not 0 <= int(member) < self.model.num_models:
+            raise ValueError(f"member {member}: the model has {self.model.num_models} members")
+        if (mode, int(member)) != (self._mode, self._member):
+            self._mode, self._member = mode, int(member)
+            self.launch_epoch += 1
+
+    @property
+    def reward_penalty(self) -> float:
+        return self._penalty
+
+    @reward_penalty.setter
+    def reward_penalty(self, v: float) -> None:
+        if float(v) != self._penalty:
+            self._penalty = float(v)
+            self.launch_epoch += 1
+
+    def set_member_in(self, members) -> None:
+        """Inject mode "random"'s choices: one member index per episode, the same at every step (None: draw them)."""
+        import torch
+        had = self.member_in is not None
+        if members is None:
+            self.member_in = None
+        else:
+            t = torch.as_tensor(np.asarray(members, np.int32)).to(self.device).reshape(-1).contiguous()
+            if t.numel() != self.E or int(t.min()) < 0 or int(t.max()) >= self.model.num_models:
+                raise ValueError(f"member_in: {self.E} indices below {self.model.num_models}")
+            if had:
+                self.member_in.copy_(t)
+            else:
+                self.member_in = t
+        if had != (self.member_in is not None):
+            self.launch_epoch += 1
+
+    # ---- the vector-environment interface -----------------------------------------------------------------------------
+    def desc(self, episode_len: int, cost_scale: float):
+        """The by-value launch descriptor for the current mode / member / penalty, tagged with ``launch_epoch``."""
+        from .. import _lib as L
+        m = self.model
+        d = L.ModelEnvT()
+        for i, n in enumerate(m.member_descs()):
+            d.net[i] = n
+        for k in ("mu_s", "sd_s", "mu_d", "sd_d", "mu_r", "sd_r"):
+            setattr(d, k, getattr(m, k).data_ptr())
+        if self.clip_states:
+            d.s_lo, d.s_hi = m.s_lo.data_ptr(), m.s_hi.data_ptr()
+        d.seed = self._seed.data_ptr()
+        d.member_in = None if self.member_in is None else self.member_in.data_ptr()
+        d.n_models, d.state_dim, d.action_dim, d.episode_len = m.num_models, self.state_dim, self.action_dim, int(episode_len)
+        d.mode, d.member, d.episode_base = L.MODEL_ENV_MODES[self._mode], self._member, self.base_seed & 0xFFFFFFFF
+        d.max_action, d.cost_scale, d.reward_penalty = self.max_action, float(cost_scale), self._penalty
+        d.launch_epoch = self.launch_epoch
+        return d
+
+    def reset(self, obs_out) -> None:
+        """Initial states of episodes base_seed .. base_seed+E-1 -> ``state`` and ``obs_out[:, :od]``; zero totals."""
+        self.state.copy_(self.state0)
+        obs_out[:, :self.state_dim].copy_(self.state0)
+        self.acc.zero_()
+        self.unc.zero_()
+
+    def step(self, desc, actions, obs_out, step_out=None) -> None:
+        """``step_out`` (optional [E,2]) receives this step's (reward, raw cost)."""
+        import ctypes as C
+
+        from .. import _lib as L
+        from ..engine.core import cur_stream
+        L.check(L.load().osrl_model_env_step(C.byref(desc), actions.data_ptr(), self.state.data_ptr(), obs_out.data_ptr(),
+                                             obs_out.stride(0), self.acc.data_ptr(), self.unc.data_ptr(),
+                                             None if step_out is None else step_out.data_ptr(), self.E, cur_stream()),
+                "osrl_model_env_step")
+
+    def disagreement(self):
+        """Per episode ``(max, mean over the steps taken)`` of the members' disagreement (normalised units), two numpy
+        arrays.  Synchronises."""
+        u, n = self.unc.cpu().numpy().astype(np.float64), self.acc[:, 2].cpu().numpy().astype(np.float64)
+        return u[:, 0], u[:, 1] / np.maximum(n, 1.0)

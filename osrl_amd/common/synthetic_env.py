@@ -49,7 +49,15 @@ class SyntheticSafeEnv:
         return self.s.copy(), reward, False, self.t >= self.episode_len, {"cost": cost}
 
 
-class VecSyntheticSafeEnv:
+class DeviceVecEnv:
+    """Marker base of the vector environments resident in HBM and stepped by one HIP launch: what ``evaluate`` runs as a
+    batched, graph-captured rollout (engine/rollout.py).  The interface a rollout uses: ``E``, ``state_dim``,
+    ``episode_len``, ``state``, ``acc [E, 4]``, ``desc(episode_len, cost_scale)`` (with a settable ``.episode_len``),
+    ``reset(obs)``, ``step(desc, actions, obs_out, step_out)``; optionally ``extra_state`` (further tensors a step
+    changes) and ``launch_epoch`` (moves when a by-value launch argument of ``desc`` changes)."""
+
+
+class VecSyntheticSafeEnv(DeviceVecEnv):
     """E episodes of one ``SyntheticSafeEnv`` in HBM: ``state[E, od]`` plus the per-episode accumulators
     ``acc[E, 4] = (return, cost * cost_scale, length, done)``; ``step(actions, obs_out)`` is one HIP launch."""
 

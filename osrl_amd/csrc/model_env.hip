@@ -1,0 +1,338 @@
+// model_env.hip -- the learned-dynamics vector environment for gfx950 (MI355X): an ensemble of MLPs fitted on logged
+// transitions (algorithms/dynamics.py), stepped with osrl_env_step's interface (include/osrl_amd.h osrl_model_env_t).
+//
+// ONE launch per environment step for all E episodes; one workgroup (512 threads, 8 waves) per 16-episode tile runs the
+// whole ensemble with its activations in LDS:
+//   * the layers are act_vec.hip's: v_mfma_f32_16x16x4_f32 over the packed forward weights PF[k/4][n][k%4] and the canonical
+//     biases of the flat group -- what the fused Adam step keeps current, so the environment follows training in place; a
+//     layer's 16-column output tiles are dealt to the 8 waves, two per wave and pass, and a wave walks ALL of K for its
+//     tiles (no split-K, no arithmetic across rows): an episode's trajectory is the same bits whatever E is, whichever
+//     tile row it sits in and whatever its neighbours do;
+//   * the members run one after the other on the same staged input tile; thread (row = tid / 32, j = tid % 32) keeps the
+//     state columns j, j + 32, .. of every member's output in registers until the mean exists (the disagreement needs
+//     both), the running sum and the chosen member's output live in LDS;
+//   * the member a RANDOM-mode episode follows is a Philox word keyed by (seed, episode id, the episode's own step): a
+//     function of nothing else.
+#include "argmem.h"
+#include "policy_common.h"
+
+using osrl_rng::philox4x32_10;
+using osrl_rng::U4;
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kThreads = 512, kWaves = 8, kTile = 16;
+constexpr int kPad = 4;  // floats: rows 16 bytes apart in the banks (act_vec.hip)
+constexpr int kS = OSRL_MODEL_ENV_MAX_WIDTH + kPad;         // row stride of the activation tiles
+constexpr int kYS = OSRL_MODEL_ENV_MAX_STATE + 2 + 2;       // row stride of the output tiles (state_dim + 2 columns)
+constexpr int kRowThreads = kThreads / kTile;               // 32 threads share a row in the epilogue
+constexpr int kKeep = OSRL_MODEL_ENV_MAX_STATE / kRowThreads;  // state columns a thread keeps per member
+constexpr uint32_t kMemberStream = 14;                      // Philox stream of the RANDOM-mode member choice
+
+struct StepArgs {
+  osrl_model_env_t d;
+  const float* act;
+  float* state;
+  float* obs;
+  float* acc;
+  float* unc;
+  float* step_out;
+  int32_t obs_ld, episodes;
+};
+
+struct Lds {
+  __attribute__((aligned(16))) float xin[kTile * kS];     // the staged input rows: every member's layer 0 reads them
+  __attribute__((aligned(16))) float buf[2][kTile * kS];  // a member's activations, ping-pong
+  float ysum[kTile * kYS];                                // sum over the members so far, then the mean
+  float ysel[kTile * kYS];                                // the output of the member the row follows
+  int live[kTile];                                        // 1: the row's episode exists and is not finished
+  int jsel[kTile];                                        // the member the row follows (-1: the mean)
+};
+static_assert(sizeof(Lds) <= 160 * 1024, "model_env_kernel: LDS per workgroup");
+
+// y[r][n] = act(b[n] + sum_k W[n][k] x[r][k]) for the tile's 16 rows (act_vec.hip mfma_layer: the same lane layout, the same
+// k order); x, y in LDS, row stride kS.  Columns out .. round16(out) are written as zero: the next layer's k padding.
+__device__ __forceinline__ void mfma_layer(const float* __restrict__ PF, const float* __restrict__ b, int in, int out,
+                                           int act, const float* x, float* y) {
+  // (act_vec.hip runs 8 k-blocks per round; beside the 64 kept output registers that spills: 256 VGPRs + 18 in scratch
+  // against 198 and none at 4)
+  constexpr int kC = 4;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int ar = lane & 15, kq = lane >> 4;
+  const int Np = round16(out), nkb = round16(in) >> 4, nct = Np >> 4;
+  const f32x4* __restrict__ W4 = reinterpret_cast<const f32x4*>(PF);
+  const float* xr = x + ar * kS + 4 * kq;
+  for (int c0 = w; c0 < nct; c0 += 2 * kWaves) {
+    const int c1 = c0 + kWaves;
+    const bool two = c1 < nct;  // (wave-uniform)
+    const f32x4* __restrict__ p0 = W4 + (size_t)kq * Np + 16 * c0 + ar;
+    const f32x4* __restrict__ p1 = W4 + (size_t)kq * Np + 16 * (two ? c1 : c0) + ar;
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    for (int kc = 0; kc < nkb; kc += kC) {  // kC k-blocks per round: every load of the round before its first MFMA
+      f32x4 b0[kC], b1[kC], av[kC];
+#pragma unroll
+      for (int u = 0; u < kC; ++u) {
+        const int kb = kc + u;
+        b0[u] = b1[u] = av[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (kb < nkb) {
+          b0[u] = p0[(size_t)4 * kb * Np];
+          if (two) b1[u] = p1[(size_t)4 * kb * Np];
+          av[u] = *reinterpret_cast<const f32x4*>(xr + 16 * kb);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kC; ++u) {
+        if (kc + u < nkb) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][t], b0[u][t], acc0, 0, 0, 0);
+            if (two) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][t], b1[u][t], acc1, 0, 0, 0);
+          }
+        }
+      }
+    }
+    {
+      const int col = 16 * c0 + ar;
+      const float bb = col < out ? b[col] : 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) y[(4 * kq + i) * kS + col] = col < out ? act_fwd(act, acc0[i] + bb) : 0.f;
+    }
+    if (two) {
+      const int col = 16 * c1 + ar;
+      const float bb = col < out ? b[col] : 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) y[(4 * kq + i) * kS + col] = col < out ? act_fwd(act, acc1[i] + bb) : 0.f;
+    }
+  }
+  __syncthreads();
+}
+
+// AR = how the descriptor is reached: `const StepArgs&` (the kernarg segment) or `const OSRL_CAS StepArgs&` (argmem.h)
+template <class AR>
+__device__ __forceinline__ void model_env_body(AR a, Lds& l) {
+  const int tid = threadIdx.x;
+  const int od = a.d.state_dim, ad = a.d.action_dim, M = a.d.n_models, no = od + 2;
+  const int e0 = blockIdx.x * kTile;  // the tile's first episode
+  const int r = tid / kRowThreads, j = tid % kRowThreads;
+  if (tid < kTile) {
+    const int e = e0 + tid;
+    const bool lv = e < a.episodes && a.acc[(size_t)e * 4 + 3] == 0.f;
+    int js = -1;
+    if (lv && a.d.mode == OSRL_MODEL_ENV_MEMBER) js = a.d.member;
+    if (lv && a.d.mode == OSRL_MODEL_ENV_RANDOM) {
+      if (a.d.member_in) {
+        js = (int)((uint32_t)a.d.member_in[e] % (uint32_t)M);
+      } else {
+        const uint64_t seed = *a.d.seed;
+        const U4 w = philox4x32_10(U4{a.d.episode_base + (uint32_t)e, (uint32_t)a.acc[(size_t)e * 4 + 2], 0u, kMemberStream},
+                                   (uint32_t)seed, (uint32_t)(seed >> 32));
+        js = (int)(w.x % (uint32_t)M);
+      }
+    }
+    l.live[tid] = lv;
+    l.jsel[tid] = js;
+  }
+  __syncthreads();
+  const bool alive = l.live[r] != 0;
+  const int ep = e0 + r;
+  // ---- the state columns this thread advances at the end, and the staged input rows; idle rows are zero
+  float sreg[kKeep];
+#pragma unroll
+  for (int q = 0; q < kKeep; ++q) {
+    const int k = j + kRowThreads * q;
+    sreg[q] = alive && k < od ? a.state[(size_t)ep * od + k] : 0.f;
+  }
+  const int in0 = round16(od + ad);
+  for (int i = tid; i < kTile * in0; i += kThreads) {
+    const int rr = i / in0, c = i - rr * in0, e = e0 + rr;
+    float v = 0.f;
+    if (l.live[rr]) {
+      if (c < od)
+        v = (a.state[(size_t)e * od + c] - a.d.mu_s[c]) / a.d.sd_s[c];
+      else if (c < od + ad)
+        v = fminf(fmaxf(a.act[(size_t)e * ad + (c - od)], -a.d.max_action), a.d.max_action);
+    }
+    l.xin[rr * kS + c] = v;
+  }
+  __syncthreads();
+  // ---- the members, in order (the loop is unrolled: yk is indexed by constants and stays in registers)
+  float yk[OSRL_MAX_NETS][kKeep];
+#pragma unroll
+  for (int m = 0; m < OSRL_MAX_NETS; ++m) {
+#pragma unroll
+    for (int q = 0; q < kKeep; ++q) yk[m][q] = 0.f;
+    if (m < M) {  // (uniform)
+      const float* x = l.xin;
+      int cur = 0;
+      const int nl = a.d.net[m].n_layers;
+      for (int ly = 0; ly < nl; ++ly) {
+        mfma_layer(a.d.net[m].Wf[ly], a.d.net[m].b[ly], a.d.net[m].dims[ly], a.d.net[m].dims[ly + 1],
+                   a.d.net[m].acts[ly], x, l.buf[cur]);
+        x = l.buf[cur];
+        cur ^= 1;
+      }
+#pragma unroll
+      for (int q = 0; q < kKeep; ++q) {
+        const int k = j + kRowThreads * q;
+        if (k < od) yk[m][q] = x[r * kS + k];
+      }
+      for (int i = tid; i < kTile * no; i += kThreads) {  // (element i is this thread's for every member)
+        const int rr = i / no, c = i - rr * no;
+        const float v = x[rr * kS + c];
+        l.ysum[rr * kYS + c] = m == 0 ? v : l.ysum[rr * kYS + c] + v;
+        if (l.jsel[rr] == m) l.ysel[rr * kYS + c] = v;
+      }
+      __syncthreads();  // the next member's first layers write the tile this one's output sits in
+    }
+  }
+  const float inv_m = 1.0f / (float)M;
+  for (int i = tid; i < kTile * no; i += kThreads) {
+    const int rr = i / no, c = i - rr * no;
+    l.ysum[rr * kYS + c] *= inv_m;
+  }
+  __syncthreads();
+  // ---- disagreement: the row's 32 threads hold its state columns; a butterfly over them gives every one the sum
+  const float* ybar = l.ysum + r * kYS;
+  float d = 0.f;
+#pragma unroll
+  for (int m = 0; m < OSRL_MAX_NETS; ++m) {
+    if (m < M) {
+      float p = 0.f;
+#pragma unroll
+      for (int q = 0; q < kKeep; ++q) {
+        const int k = j + kRowThreads * q;
+        if (k < od) {
+          const float df = yk[m][q] - ybar[k];
+          p = fmaf(df, df, p);
+        }
+      }
+#pragma unroll
+      for (int o = kRowThreads / 2; o >= 1; o >>= 1) p += __shfl_xor(p, o);
+      d = fmaxf(d, sqrtf(p / (float)od));
+    }
+  }
+  if (!alive) return;  // finished episodes keep their state and totals
+  const float* yh = (a.d.mode == OSRL_MODEL_ENV_MEAN ? l.ysum : l.ysel) + r * kYS;
+  const bool clamp = a.d.s_lo != nullptr && a.d.s_hi != nullptr;
+#pragma unroll
+  for (int q = 0; q < kKeep; ++q) {
+    const int k = j + kRowThreads * q;
+    if (k < od) {
+      float sn = sreg[q] + fmaf(a.d.sd_d[k], yh[k], a.d.mu_d[k]);
+      if (clamp) sn = fminf(fmaxf(sn, a.d.s_lo[k]), a.d.s_hi[k]);
+      a.state[(size_t)ep * od + k] = sn;
+      a.obs[(size_t)ep * a.obs_ld + k] = sn;
+    }
+  }
+  if (j == 0) {
+    float rew = fmaf(a.d.sd_r[0], yh[od], a.d.mu_r[0]);
+    if (a.d.reward_penalty != 0.f) rew -= a.d.reward_penalty * d;
+    const float cost = yh[od + 1] > 0.5f ? 1.f : 0.f;
+    float* ac = a.acc + (size_t)ep * 4;
+    const float len = ac[2] + 1.f;  // (csrc/env.hip env_step_kernel's bookkeeping)
+    ac[0] += rew;
+    ac[1] += cost * a.d.cost_scale;
+    if (a.step_out) {
+      a.step_out[(size_t)ep * 2] = rew;
+      a.step_out[(size_t)ep * 2 + 1] = cost;
+    }
+    ac[2] = len;
+    if (len >= (float)a.d.episode_len) ac[3] = 1.f;
+    float* un = a.unc + (size_t)ep * 2;
+    un[0] = fmaxf(un[0], d);
+    un[1] += d;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void model_env_kernel(const StepArgs a) {
+  __shared__ Lds l;
+  model_env_body<const StepArgs&>(a, l);
+}
+// the same kernel with its descriptor in device memory (argmem.h)
+__global__ __launch_bounds__(kThreads) void model_env_kernel_p(const void* p) {
+  __shared__ Lds l;
+  model_env_body<const OSRL_CAS StepArgs&>(*(const OSRL_CAS StepArgs*)p, l);
+}
+
+struct PrepArgs {
+  const float *obs, *nobs, *rew, *cost, *mu_s, *sd_s, *mu_d, *sd_d, *mu_r, *sd_r;
+  float *xs, *target;
+  int32_t rows, od;
+};
+
+__global__ __launch_bounds__(256) void dyn_prepare_kernel(const PrepArgs a) {
+  const int no = a.od + 2;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)a.rows * no) return;
+  const int b = (int)(i / no), c = (int)(i - (int64_t)b * no);
+  float t;
+  if (c < a.od) {
+    const float o = a.obs[(size_t)b * a.od + c];
+    a.xs[(size_t)b * a.od + c] = (o - a.mu_s[c]) / a.sd_s[c];
+    t = (a.nobs[(size_t)b * a.od + c] - o - a.mu_d[c]) / a.sd_d[c];
+  } else if (c == a.od) {
+    t = (a.rew[b] - a.mu_r[0]) / a.sd_r[0];
+  } else {
+    t = a.cost[b];
+  }
+  a.target[i] = t;
+}
+
+bool valid_member(const osrl_gemv_net_t& n, int in, int out) {
+  if (n.n_layers < 1 || n.n_layers > OSRL_MAX_LAYERS || n.out_scale != 1.0f) return false;
+  for (int l = 0; l <= n.n_layers; ++l)
+    if (n.dims[l] < 1 || n.dims[l] > OSRL_MODEL_ENV_MAX_WIDTH) return false;
+  for (int l = 0; l < n.n_layers; ++l)
+    if (!n.Wf[l] || !n.b[l]) return false;
+  return n.dims[0] == in && n.dims[n.n_layers] == out;
+}
+
+}  // namespace
+
+extern "C" int osrl_model_env_step(const osrl_model_env_t* env, const float* act, float* state, float* obs,
+                                   int32_t obs_ld, float* acc, float* unc, float* step_out, int32_t episodes,
+                                   void* stream) {
+  if (!env || !act || !state || !obs || !acc || !unc || episodes < 1) return -1;
+  const osrl_model_env_t& d = *env;
+  if (d.n_models < 1 || d.n_models > OSRL_MAX_NETS || d.state_dim < 1 || d.state_dim > OSRL_MODEL_ENV_MAX_STATE ||
+      d.action_dim < 1 || obs_ld < d.state_dim || !d.mu_s || !d.sd_s || !d.mu_d || !d.sd_d || !d.mu_r || !d.sd_r ||
+      (d.s_lo == nullptr) != (d.s_hi == nullptr))
+    return -1;
+  if (d.mode < OSRL_MODEL_ENV_MEAN || d.mode > OSRL_MODEL_ENV_RANDOM) return -1;
+  if (d.mode == OSRL_MODEL_ENV_MEMBER && (d.member < 0 || d.member >= d.n_models)) return -1;
+  if (d.mode == OSRL_MODEL_ENV_RANDOM && !d.seed && !d.member_in) return -1;
+  for (int m = 0; m < d.n_models; ++m)
+    if (!valid_member(d.net[m], d.state_dim + d.action_dim, d.state_dim + 2)) return -1;
+  StepArgs a;
+  memset(&a, 0, sizeof a);  // (the arena finds a block by its bytes: no stray padding)
+  a.d = d;
+  for (int m = d.n_models; m < OSRL_MAX_NETS; ++m) memset(&a.d.net[m], 0, sizeof a.d.net[m]);
+  a.d.pad_ = 0;
+  a.d.pad2_ = 0.f;
+  a.act = act;
+  a.state = state;
+  a.obs = obs;
+  a.acc = acc;
+  a.unc = unc;
+  a.step_out = step_out;
+  a.obs_ld = obs_ld;
+  a.episodes = episodes;
+  const int tiles = (episodes + kTile - 1) / kTile;
+  return osrl_argmem::launch(model_env_kernel, model_env_kernel_p, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream,
+                             a);
+}
+
+extern "C" int osrl_dyn_prepare(const float* obs, const float* nobs, const float* rew, const float* cost,
+                                const float* mu_s, const float* sd_s, const float* mu_d, const float* sd_d,
+                                const float* mu_r, const float* sd_r, int32_t rows, int32_t state_dim, float* xs,
+                                float* target, void* stream) {
+  if (!obs || !nobs || !rew || !cost || !mu_s || !sd_s || !mu_d || !sd_d || !mu_r || !sd_r || !xs || !target ||
+      rows < 1 || state_dim < 1)
+    return -1;
+  const PrepArgs a{obs, nobs, rew, cost, mu_s, sd_s, mu_d, sd_d, mu_r, sd_r, xs, target, rows, state_dim};
+  const int64_t n = (int64_t)rows * (state_dim + 2);
+  return osrl_argmem::launch(dyn_prepare_kernel, nullptr, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                             (hipStream_t)stream, a);
+}

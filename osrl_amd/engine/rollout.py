@@ -29,6 +29,13 @@ _CHUNK = 20     # env steps per captured graph: one replay costs ~25 us of launc
                 # episodes that finish inside a chunk are frozen by the env kernel's done latch, so overshoot is a no-op
 
 
+def _desc_stale(venv, desc) -> bool:
+    """A model environment's mode / member / reward penalty are by-value launch arguments: when one of them has changed
+    (``launch_epoch``) the descriptor is rebuilt and the captured graph dropped, the way the collectors handle ``sample``."""
+    epoch = getattr(venv, "launch_epoch", None)
+    return epoch is not None and getattr(desc, "launch_epoch", None) != epoch
+
+
 class BatchedRollout:
     """``eval_episodes`` episodes of one vector environment driven by ``model``'s policy on device."""
 
@@ -46,6 +53,7 @@ class BatchedRollout:
         if extra_obs is not None:
             self.obs[:, od] = float(extra_obs)
         self.a = torch.zeros(E, ad, **f)
+        self.cost_scale = float(cost_scale)
         self.env_c = venv.desc(m.episode_len, cost_scale)
         self.st = StepState(dev, ["x"])
         m.repack()
@@ -91,7 +99,8 @@ class BatchedRollout:
 
     def _snapshot(self):
         """What one ``body`` changes, cloned: ``_capture`` runs the body once for real before it records."""
-        return [(t, t.clone()) for t in (self.venv.state, self.venv.acc, self.obs, self.st.state)]
+        extra = tuple(getattr(self.venv, "extra_state", ()))  # (a model environment's per-episode disagreement sums)
+        return [(t, t.clone()) for t in (self.venv.state, self.venv.acc, self.obs, self.st.state) + extra]
 
     def _capture(self) -> None:
         snap, host_step = self._snapshot(), self.st.host_step
@@ -115,6 +124,8 @@ class BatchedRollout:
         """All episodes to completion -> per-episode (return, cost * cost_scale, length) as numpy arrays."""
         self.venv.reset(self.obs)
         steps = min(self.model.episode_len, self.venv.episode_len or self.model.episode_len)
+        if _desc_stale(self.venv, self.env_c):
+            self.env_c, self.graph = self.venv.desc(steps, self.cost_scale), None
         if self.env_c.episode_len != steps:  # the env descriptor is a by-value launch argument of the captured graph
             self.env_c.episode_len, self.graph = steps, None
         if self.use_graph and self.graph is None:
@@ -131,7 +142,7 @@ class BatchedRollout:
 
 def evaluate_batched(trainer, kind: str, eval_episodes: int, cost_scale: float = 1.0,
                      extra_obs: Optional[float] = None):
-    """``Trainer.evaluate`` on a ``VecSyntheticSafeEnv``: (mean return, mean cost * cost_scale, mean length).
+    """``Trainer.evaluate`` on a ``DeviceVecEnv``: (mean return, mean cost * cost_scale, mean length).
     The rollout object (buffers + captured graph) is cached on the trainer; it reads the model's packed weights in
     place, so it stays valid across train steps."""
     venv = trainer.env
@@ -242,6 +253,8 @@ class CDTBatchedRollout:
         m = self.model
         target_return, target_cost = self._targets(target_return, target_cost)
         steps = min(m.episode_len, self.venv.episode_len or m.episode_len)
+        if _desc_stale(self.venv, self.env_c):
+            self.env_c, self.graph = self.venv.desc(steps, 1.0), None
         if self.env_c.episode_len != steps:
             self.env_c.episode_len, self.graph = steps, None
         m.repack()
