@@ -1395,6 +1395,28 @@ typedef struct {
 int osrl_model_env_step(const osrl_model_env_t* env, const float* act, float* state, float* obs, int32_t obs_ld,
                         float* acc, float* unc /* [E,2] */, float* step_out /* optional [E,2] */, int32_t episodes,
                         void* stream);
+/* osrl_model_env_step with exploration noise, recording what it does (engine/collect.py ModelCollector): the same launch
+ * shape and the same body behind a compile-time flag, plus what osrl_env_collect adds to osrl_env_step.  Episode e at its
+ * own step t = acc[e][2] (read once per launch; 0 <= t < env->episode_len and the done latch clear, otherwise the launch
+ * stores nothing for it -- so no write leaves the tables, whose rows are episodes * env->episode_len):
+ *   a = clip(fmaf(sigma[e], eps, act[e]), +-max_action) while the input tile is staged; sigma[e] == 0: eps is not read and
+ *       the step is osrl_model_env_step's bit for bit;  eps as osrl_env_collect documents it (eps_in or Philox on
+ *       rec->stream_id, keyed by (seed, episode_base + e, t, column));
+ *   row e * episode_len + t: observations = s, actions = a, next_observations = s' (after the clamp), rewards = r (after
+ *       reward_penalty: what acc[e][0] sums), costs (raw 0 / 1), terminals = 0, timeouts = (t + 1 >= episode_len);
+ *   rec->disc as osrl_env_collect keeps it;  row_unc (optional [episodes * episode_len]) receives the row's d. */
+int osrl_model_env_collect(const osrl_model_env_t* env, const osrl_collect_t* rec, const float* act, float* state,
+                           float* obs, int32_t obs_ld, float* acc, float* unc,
+                           float* row_unc /* optional [E * episode_len] */, int32_t episodes, void* stream);
+/* Branch starts: episode e starts at row idx_e of `table` ([n_rows, state_dim], a store's observations),
+ *   idx_e = umul64hi(words (x, y) of Philox4x32-10(counter {episode_base + e, 0, 0, 15}, key *seed), n)
+ * (the replay gather's uniform draw; a function of (seed, episode id) alone), n = *n_rows_dev when given (a store's live
+ * count: a launch follows append without a host sync), else n_rows; capped by n_rows and, when n_limit > 0, by n_limit.
+ * Writes state[e], obs[e, :state_dim], start_rows[e], zeros in acc[e] and unc[e], (0, 0, 1, 0) in disc[e]. */
+int osrl_model_env_branch(const float* table, int64_t n_rows, const int64_t* n_rows_dev, int64_t n_limit,
+                          int32_t state_dim, const uint64_t* seed, uint32_t episode_base, float* state, float* obs,
+                          int32_t obs_ld, float* acc, float* unc, float* disc /* [E,4] */,
+                          int64_t* start_rows /* [E] */, int32_t episodes, void* stream);
 /* The train step's preparation (engine/dynamics.py): xs[b] = (obs[b] - mu_s) / sd_s  [rows, state_dim];
  * target[b] = {(nobs[b] - obs[b] - mu_d) / sd_d, (rew[b] - mu_r) / sd_r, cost[b]}  [rows, state_dim + 2]. */
 int osrl_dyn_prepare(const float* obs, const float* nobs, const float* rew, const float* cost, const float* mu_s,

@@ -222,6 +222,8 @@ PROTOTYPES = {
     "osrl_mlp_forward": [_P(MlpT), _P(RowsT), _P(ActsT), _vp],
     "osrl_env_step": [_P(EnvT), _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp],
     "osrl_model_env_step": [_P(ModelEnvT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
+    "osrl_model_env_collect": [_P(ModelEnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
+    "osrl_model_env_branch": [_vp, _i64, _vp, _i64, _i32, _vp, _u32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
     "osrl_dyn_prepare": [_vp] * 10 + [_i32, _i32, _vp, _vp, _vp],
     "osrl_env_collect": [_P(EnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _i32, _vp],
     "osrl_cdt_collect": [_P(EnvT), _P(CollectT), _P(CdtWindowT), _vp, _vp, _i32, _vp],

@@ -143,6 +143,41 @@ class RolloutMixin:
         return collect_batched(self, self.EVAL_KIND, 1.0 if cs is None else cs, self._eval_extra(),
                                noise_std=noise_std, gamma=gamma, seed=seed, noise=noise, into=into)
 
+    def collect_model(self, menv, horizon: Optional[int] = None, start=None, noise_std=0.0,
+                      gamma: Optional[float] = None, seed: int = 0, noise=None, into=None, sample_prob=None):
+        """Rollouts of the current policy on a learned model, recorded (engine/collect.py ``ModelCollector``): every
+        episode of the ``ModelVecEnv`` ``menv`` (an argument, not ``self.env``; anything else: TypeError) runs
+        ``horizon`` steps (None: ``menv.episode_len``) with ``a = clip(pi(s) + sigma_e * eps)`` and comes back as a
+        ``Collected`` of ``E * horizon`` rows, episode-major, under the seven DSRL keys: ``rewards`` after ``menv``'s
+        ``reward_penalty``, ``terminals`` 0, ``timeouts`` 1 on each episode's last row.  It is a model's opinion.
+        ``start=None``: from ``menv``'s own initial states (a full model episode).  ``start=store`` (a ``ReplayStore``):
+        k-step branched rollouts as MOPO / MBPO make them -- every episode starts at a row drawn on device, uniformly,
+        from the store's pinned prefix (``pinned_rows > 0``: the real data) or else its live rows, keyed by ``(seed,
+        episode id)`` alone; weighted starts are out of scope.  ``noise_std``, ``gamma``, ``seed``, ``noise``
+        (``[horizon, E, action_dim]``) as ``collect`` takes them.  The policy, the appended cost limit of BC multi-task
+        and the cost scale are ``evaluate``'s.
+        ``into``: a ``ReplayStore`` built with ``capacity`` under ``collect``'s width rules; a weighted store is taken
+        with ``sample_prob`` (a scalar or ``[E * horizon]``: the new rows' weights, handed to ``append``), a
+        ``state_init`` store is refused with ``start=store`` (a branch start is not an initial state).  ValueError
+        before anything runs.  ``self.model_collector(menv)`` is the cached collector: its ``start_rows`` and
+        ``row_disagreement`` are device tensors of the last run."""
+        co = self.model_collector(menv)
+        self._before_evaluate()
+        return co.run(horizon=horizon, start=start, noise_std=noise_std, gamma=gamma, seed=seed, noise=noise, into=into,
+                      sample_prob=sample_prob)
+
+    def model_collector(self, menv):
+        """The ``ModelCollector`` of ``collect_model`` on ``menv`` (buffers, tables, captured graph), cached on the
+        trainer like ``evaluate``'s rollout."""
+        from ..engine.collect import ModelCollector
+        cs = self._cost_scale()
+        key = (id(menv), self.EVAL_KIND, 1.0 if cs is None else float(cs), self._eval_extra())
+        co = getattr(self, "_model_collector", None)
+        if co is None or co[0] != key:
+            co = (key, ModelCollector(self.model, menv, *key[1:], use_graph=getattr(self, "use_graph", True)))
+            self._model_collector = co
+        return co[1]
+
     @torch.no_grad()
     def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):
         """``rollout`` on each of the host environments ``envs`` at once, in lockstep through

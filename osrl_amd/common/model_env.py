@@ -8,6 +8,10 @@ environment follows ``DynamicsTrainer`` steps as rollouts follow a policy.
 
 What comes out is a model's opinion: its error grows with the rollout length and with the shift between the policy and the
 data.  ``disagreement()`` -- how far the members' predictions lie apart along each episode -- is the trust signal.
+
+Recording: ``collect`` / ``collect_targets`` refuse a ``ModelVecEnv``; ``Trainer.collect_model(menv, ...)`` (engine/collect.py
+``ModelCollector``, csrc/model_env.hip ``osrl_model_env_collect``) records the policy's rollouts on it, k steps from the
+initial states or from rows of a store, with the penalised reward.
 """
 from __future__ import annotations
 

@@ -48,6 +48,16 @@ def ring_spans(cursor: int, m: int, capacity: int):
     return [(dst, src, first)] + ([(0, src + first, n - first)] if n > first else [])
 
 
+def ring_spans_pinned(cursor: int, m: int, capacity: int, pinned: int):
+    """``ring_spans`` for a store whose first ``pinned`` rows are never overwritten: the ring runs over
+    ``[pinned, capacity)``, so row ``i`` of the chunk goes to ``pinned + (cursor - pinned + i) % (capacity - pinned)``.
+    ``pinned <= cursor < capacity``; the same ``(dst, src, length)`` triples, and ``pinned = 0`` is ``ring_spans``."""
+    cursor, m, capacity, pinned = int(cursor), int(m), int(capacity), int(pinned)
+    if not 0 <= pinned < capacity or not pinned <= cursor < capacity:
+        raise ValueError(f"ring_spans_pinned({cursor}, {m}, {capacity}, {pinned})")
+    return [(dst + pinned, src, n) for dst, src, n in ring_spans(cursor - pinned, m, capacity - pinned)]
+
+
 def seq_ring_plan(starts, lens, tail: int, mr: int, mt: int, capacity_rows: int, capacity_traj: int):
     """Where a chunk of ``mt`` whole trajectories in ``mr`` rows lands in a ``SequenceStore(evict="oldest")`` whose live
     trajectories, oldest first, occupy rows ``[starts[i], starts[i] + lens[i])`` and whose newest one ends at ``tail``:
@@ -110,7 +120,7 @@ def _checked_weights(weights, n: int, what: str, shard: slice = slice(None), pos
 class ReplayStore:
     def __init__(self, data: Dict[str, "np.ndarray | torch.Tensor"], device, reward_scale: float = 1.0,
                  cost_scale: float = 1.0, seed: int = 0, rank: int = 0, world: int = 1, state_init: bool = False,
-                 capacity: Optional[int] = None, sample_prob=None):
+                 capacity: Optional[int] = None, pinned_rows: int = 0, sample_prob=None):
         """``data`` uses the DSRL dataset keys (observations, next_observations, actions, rewards, costs,
         and either ``done`` or ``terminals``+``timeouts``).  ``state_init`` (TransitionDataset(state_init=True),
         dataset.py:817-820, used by COptiDICE): a 7th table ``is_init`` = ``done`` shifted by one transition with
@@ -121,11 +131,22 @@ class ReplayStore:
         ``world > 1``).  ``n_rows`` is then the LIVE row count, ``capacity`` the allocation; the launches carry the
         capacity and the address of the device word that holds the live count.  With ``state_init``,
         ``init_state_propotion`` and the two ``*_std`` are those of the construction-time data and are not updated by
-        ``append``."""
+        ``append``.
+        ``pinned_rows`` p (only with ``capacity``; ``p <= len(data)``, ``p < capacity``, ValueError otherwise): the first
+        p rows are never overwritten -- ``append``'s ring runs over ``[p, capacity)`` (``ring_spans_pinned``), so logged
+        data stays while generated rows behind it turn over.  0, the default: the store as it always was."""
         d = dict(data)
         self.state_init = bool(state_init)
         d["done"] = _done_of(d)
         n = len(d["observations"])
+        pinned_rows = int(pinned_rows)
+        if pinned_rows:
+            if capacity is None:
+                raise ValueError("pinned_rows= needs a store built with capacity=")
+            if not 0 < pinned_rows <= n or pinned_rows >= int(capacity):
+                raise ValueError(f"pinned_rows {pinned_rows} must lie in [0, {n}] (the rows of the data) and below the "
+                                 f"capacity {int(capacity)}")
+        self.pinned_rows = pinned_rows
         if capacity is not None:
             capacity = int(capacity)
             if world > 1:
@@ -157,6 +178,8 @@ class ReplayStore:
         self.capacity = capacity
         self.version = 0  # incremented by every append (caches keyed on the store's contents compare it)
         self._cursor = 0 if capacity is None else n % capacity  # the ring's next slot
+        if pinned_rows and self._cursor < pinned_rows:  # (a full store: the ring wraps to its own first row)
+            self._cursor = pinned_rows
         self._live = None if capacity is None else torch.full((1,), n, dtype=torch.int64, device=device)
         self.widths = [t.shape[1] for t in self.tables]
         self.scales = [1.0, 1.0, 1.0, float(reward_scale), float(cost_scale), 1.0] + ([1.0] if self.state_init else [])
@@ -249,7 +272,8 @@ class ReplayStore:
         """Add the transitions of ``data`` (the DSRL keys, as the constructor takes them: numpy or tensors, host or
         device) to a store built with ``capacity``.  Values are stored raw (the scales stay in the gather).  Row ``i`` of
         the chunk lands at ``(cursor + i) % capacity``: a full store overwrites its oldest rows, the live count
-        saturates at the capacity.  At most two contiguous copies per table (``ring_spans``) and one write of the live
+        saturates at the capacity (with ``pinned_rows`` the ring is ``[pinned_rows, capacity)``: the rows before it stay).
+        At most two contiguous copies per table (``ring_spans``) and one write of the live
         word, all on the current stream: a captured step that draws from this store sees the new rows at its next
         replay, and nothing is recaptured.  ``version`` is incremented.
         ``state_init`` stores: the chunk's ``is_init`` is its ``done`` shifted by one row with 1 on its first row, so a
@@ -286,7 +310,8 @@ class ReplayStore:
         d["done"] = _done_of(d)
         if self.state_init:
             d["is_init"] = _shift_done(d["done"])
-        spans = ring_spans(self._cursor, m, self.capacity)
+        p = self.pinned_rows
+        spans = ring_spans_pinned(self._cursor, m, self.capacity, p) if p else ring_spans(self._cursor, m, self.capacity)
         names = FIELDS + (("is_init",) if self.state_init else ())
         for k, table in zip(names, self.tables):
             x = d[k] if torch.is_tensor(d[k]) else torch.from_numpy(np.ascontiguousarray(np.asarray(d[k])))
@@ -296,7 +321,7 @@ class ReplayStore:
         if w_new is not None:
             for dst, src, n in spans:
                 self._w64[dst:dst + n].copy_(w_new[src:src + n], non_blocking=True)
-        self._cursor = (self._cursor + m) % self.capacity
+        self._cursor = p + (self._cursor - p + m) % (self.capacity - p)
         self.n_rows = self.n_total = min(self.n_rows + m, self.capacity)
         self._live.fill_(self.n_rows)
         self.version += 1
@@ -317,6 +342,8 @@ class ReplayStore:
                   scales=[float(x) for x in self.scales], state_init=self.state_init, n_rows=n, cursor=self._cursor,
                   weighted=bool(self.weighted), tables=[t[:n].detach().cpu().clone() for t in self.tables],
                   w64=self._w64[:n].detach().cpu().clone() if self.weighted else None)
+        if self.pinned_rows:  # (only when set: the dictionary of a store without pinned rows is what it always was)
+            sd["pinned_rows"] = self.pinned_rows
         if self.state_init:
             sd["init_state_propotion"] = float(self.init_state_propotion)
             sd["observations_std"] = torch.from_numpy(np.array(self.observations_std))
@@ -335,6 +362,7 @@ class ReplayStore:
             raise ValueError(f"not a saved ReplayStore (kind {sd.get('kind')!r}, format {sd.get('format')!r})")
         for what, mine, theirs in (("capacity", self.capacity, sd["capacity"]),
                                    ("state_init", self.state_init, sd["state_init"]),
+                                   ("pinned_rows", self.pinned_rows, int(sd.get("pinned_rows", 0))),
                                    ("widths", list(self.widths), list(sd["widths"])),
                                    ("scales", [float(x) for x in self.scales], [float(x) for x in sd["scales"]])):
             if mine != theirs:

@@ -13,6 +13,16 @@
 //     both), the running sum and the chosen member's output live in LDS;
 //   * the member a RANDOM-mode episode follows is a Philox word keyed by (seed, episode id, the episode's own step): a
 //     function of nothing else.
+//
+// The same body records (model_rec_kernel, osrl_model_env_collect): the compile-time flag kRecord adds csrc/collect.hip's
+// per-episode exploration noise on the action while it is staged, one row of a DSRL-layout dataset per episode and step,
+// and the discounted sums; with sigma == 0 the step is model_env_kernel's bit for bit.
+// Why no write can leave the tables (collect.hip's argument): a row of the tile stores only while it is live, and with
+// kRecord live means e < episodes AND the done latch acc[e][3] is clear AND 0 <= step = acc[e][2] < episode_len; then row
+// e * episode_len + step < episodes * episode_len.  A captured graph replays whole chunks of steps and overshoots the
+// episode's end: those rows are not live and return before any store.
+//
+// model_branch_kernel (osrl_model_env_branch) starts every episode at a row drawn uniformly from a store's observations.
 #include "argmem.h"
 #include "policy_common.h"
 
@@ -30,6 +40,7 @@ constexpr int kYS = OSRL_MODEL_ENV_MAX_STATE + 2 + 2;       // row stride of the
 constexpr int kRowThreads = kThreads / kTile;               // 32 threads share a row in the epilogue
 constexpr int kKeep = OSRL_MODEL_ENV_MAX_STATE / kRowThreads;  // state columns a thread keeps per member
 constexpr uint32_t kMemberStream = 14;                      // Philox stream of the RANDOM-mode member choice
+constexpr uint32_t kBranchStream = 15;                      // Philox stream of the branch starts (13: the exploration noise)
 
 struct StepArgs {
   osrl_model_env_t d;
@@ -42,6 +53,13 @@ struct StepArgs {
   int32_t obs_ld, episodes;
 };
 
+struct RecArgs {
+  StepArgs s;  // (step_out is unused: the tables carry the step's reward and cost)
+  osrl_collect_t c;
+  float* row_unc;
+};
+struct NoRec {};
+
 struct Lds {
   __attribute__((aligned(16))) float xin[kTile * kS];     // the staged input rows: every member's layer 0 reads them
   __attribute__((aligned(16))) float buf[2][kTile * kS];  // a member's activations, ping-pong
@@ -49,6 +67,8 @@ struct Lds {
   float ysel[kTile * kYS];                                // the output of the member the row follows
   int live[kTile];                                        // 1: the row's episode exists and is not finished
   int jsel[kTile];                                        // the member the row follows (-1: the mean)
+  int step[kTile];                                        // (recording) the episode's own step: its table row
+  float sig[kTile];                                       // (recording) the row's noise scale
 };
 static_assert(sizeof(Lds) <= 160 * 1024, "model_env_kernel: LDS per workgroup");
 
@@ -109,16 +129,24 @@ __device__ __forceinline__ void mfma_layer(const float* __restrict__ PF, const f
   __syncthreads();
 }
 
-// AR = how the descriptor is reached: `const StepArgs&` (the kernarg segment) or `const OSRL_CAS StepArgs&` (argmem.h)
-template <class AR>
-__device__ __forceinline__ void model_env_body(AR a, Lds& l) {
+// AR = how the descriptor is reached: `const StepArgs&` (the kernarg segment) or `const OSRL_CAS StepArgs&` (argmem.h).
+// kRecord: the step is recorded; RR reaches the RecArgs the same way (NoRec otherwise).
+template <bool kRecord, class AR, class RR>
+__device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l) {
   const int tid = threadIdx.x;
   const int od = a.d.state_dim, ad = a.d.action_dim, M = a.d.n_models, no = od + 2;
   const int e0 = blockIdx.x * kTile;  // the tile's first episode
   const int r = tid / kRowThreads, j = tid % kRowThreads;
   if (tid < kTile) {
     const int e = e0 + tid;
-    const bool lv = e < a.episodes && a.acc[(size_t)e * 4 + 3] == 0.f;
+    bool lv = e < a.episodes && a.acc[(size_t)e * 4 + 3] == 0.f;
+    int st = 0;
+    if constexpr (kRecord) {  // the step is read once, here: the member draw, the noise and the table row all use it
+      st = lv ? (int)a.acc[(size_t)e * 4 + 2] : 0;
+      lv = lv && st >= 0 && st < a.d.episode_len;
+      l.step[tid] = st;
+      l.sig[tid] = lv ? rc.c.sigma[e] : 0.f;
+    }
     int js = -1;
     if (lv && a.d.mode == OSRL_MODEL_ENV_MEMBER) js = a.d.member;
     if (lv && a.d.mode == OSRL_MODEL_ENV_RANDOM) {
@@ -126,8 +154,9 @@ __device__ __forceinline__ void model_env_body(AR a, Lds& l) {
         js = (int)((uint32_t)a.d.member_in[e] % (uint32_t)M);
       } else {
         const uint64_t seed = *a.d.seed;
-        const U4 w = philox4x32_10(U4{a.d.episode_base + (uint32_t)e, (uint32_t)a.acc[(size_t)e * 4 + 2], 0u, kMemberStream},
-                                   (uint32_t)seed, (uint32_t)(seed >> 32));
+        const uint32_t t = kRecord ? (uint32_t)st : (uint32_t)a.acc[(size_t)e * 4 + 2];
+        const U4 w = philox4x32_10(U4{a.d.episode_base + (uint32_t)e, t, 0u, kMemberStream}, (uint32_t)seed,
+                                   (uint32_t)(seed >> 32));
         js = (int)(w.x % (uint32_t)M);
       }
     }
@@ -151,8 +180,26 @@ __device__ __forceinline__ void model_env_body(AR a, Lds& l) {
     if (l.live[rr]) {
       if (c < od)
         v = (a.state[(size_t)e * od + c] - a.d.mu_s[c]) / a.d.sd_s[c];
-      else if (c < od + ad)
-        v = fminf(fmaxf(a.act[(size_t)e * ad + (c - od)], -a.d.max_action), a.d.max_action);
+      else if (c < od + ad) {
+        v = a.act[(size_t)e * ad + (c - od)];
+        if constexpr (kRecord) {
+          const float sg = l.sig[rr];
+          if (sg != 0.f) {  // (sigma == 0: the deterministic action exactly; eps is not even read)
+            const int k = c - od, st = l.step[rr];
+            float eps;
+            if (rc.c.eps_in) {
+              eps = rc.c.eps_in[((size_t)st * a.episodes + e) * ad + k];
+            } else {
+              const uint64_t seed = *rc.c.seed;
+              const U4 w = philox4x32_10(U4{rc.c.episode_base + (uint32_t)e, (uint32_t)st, (uint32_t)(k >> 2), rc.c.stream_id},
+                                         (uint32_t)seed, (uint32_t)(seed >> 32));
+              eps = osrl_rng::normal_word(w, k & 3);
+            }
+            v = fmaf(sg, eps, v);
+          }
+        }
+        v = fminf(fmaxf(v, -a.d.max_action), a.d.max_action);
+      }
     }
     l.xin[rr * kS + c] = v;
   }
@@ -216,6 +263,8 @@ __device__ __forceinline__ void model_env_body(AR a, Lds& l) {
   if (!alive) return;  // finished episodes keep their state and totals
   const float* yh = (a.d.mode == OSRL_MODEL_ENV_MEAN ? l.ysum : l.ysel) + r * kYS;
   const bool clamp = a.d.s_lo != nullptr && a.d.s_hi != nullptr;
+  size_t row = 0;  // (recording) live: ep < episodes and 0 <= step < episode_len, so row < episodes * episode_len
+  if constexpr (kRecord) row = (size_t)ep * a.d.episode_len + l.step[r];
 #pragma unroll
   for (int q = 0; q < kKeep; ++q) {
     const int k = j + kRowThreads * q;
@@ -224,7 +273,14 @@ __device__ __forceinline__ void model_env_body(AR a, Lds& l) {
       if (clamp) sn = fminf(fmaxf(sn, a.d.s_lo[k]), a.d.s_hi[k]);
       a.state[(size_t)ep * od + k] = sn;
       a.obs[(size_t)ep * a.obs_ld + k] = sn;
+      if constexpr (kRecord) {
+        rc.c.observations[row * od + k] = sreg[q];
+        rc.c.next_observations[row * od + k] = sn;
+      }
     }
+  }
+  if constexpr (kRecord) {  // the clipped action taken: what the members read
+    for (int c = j; c < ad; c += kRowThreads) rc.c.actions[row * ad + c] = l.xin[r * kS + od + c];
   }
   if (j == 0) {
     float rew = fmaf(a.d.sd_r[0], yh[od], a.d.mu_r[0]);
@@ -239,21 +295,83 @@ __device__ __forceinline__ void model_env_body(AR a, Lds& l) {
       a.step_out[(size_t)ep * 2 + 1] = cost;
     }
     ac[2] = len;
-    if (len >= (float)a.d.episode_len) ac[3] = 1.f;
+    const bool last = len >= (float)a.d.episode_len;
+    if (last) ac[3] = 1.f;
     float* un = a.unc + (size_t)ep * 2;
     un[0] = fmaxf(un[0], d);
     un[1] += d;
+    if constexpr (kRecord) {
+      rc.c.rewards[row] = rew;
+      rc.c.costs[row] = cost;
+      rc.c.terminals[row] = 0.f;
+      rc.c.timeouts[row] = last ? 1.f : 0.f;
+      if (rc.row_unc) rc.row_unc[row] = d;
+      // discounted sums (collect.hip): one rounding per step each (fmaf), gamma^t by repeated multiplication
+      float* dc = rc.c.disc + (size_t)ep * 4;
+      const float pw = dc[2];
+      dc[0] = fmaf(pw, rew, dc[0]);
+      dc[1] = fmaf(pw, cost * a.d.cost_scale, dc[1]);
+      dc[2] = pw * *rc.c.gamma;
+    }
   }
 }
 
 __global__ __launch_bounds__(kThreads) void model_env_kernel(const StepArgs a) {
   __shared__ Lds l;
-  model_env_body<const StepArgs&>(a, l);
+  model_env_body<false, const StepArgs&, NoRec>(a, NoRec{}, l);
 }
 // the same kernel with its descriptor in device memory (argmem.h)
 __global__ __launch_bounds__(kThreads) void model_env_kernel_p(const void* p) {
   __shared__ Lds l;
-  model_env_body<const OSRL_CAS StepArgs&>(*(const OSRL_CAS StepArgs*)p, l);
+  model_env_body<false, const OSRL_CAS StepArgs&, NoRec>(*(const OSRL_CAS StepArgs*)p, NoRec{}, l);
+}
+
+// the recording step (osrl_model_env_collect) and its descriptor-pointer twin
+__global__ __launch_bounds__(kThreads) void model_rec_kernel(const RecArgs a) {
+  __shared__ Lds l;
+  model_env_body<true, const StepArgs&, const RecArgs&>(a.s, a, l);
+}
+__global__ __launch_bounds__(kThreads) void model_rec_kernel_p(const void* p) {
+  __shared__ Lds l;
+  const OSRL_CAS RecArgs& a = *(const OSRL_CAS RecArgs*)p;
+  model_env_body<true, const OSRL_CAS StepArgs&, const OSRL_CAS RecArgs&>(a.s, a, l);
+}
+
+struct BranchArgs {
+  const float* table;         // [n_rows, od]
+  const int64_t* n_rows_dev;  // the store's live-count word, or nullptr
+  const uint64_t* seed;
+  float *state, *obs, *acc, *unc, *disc;
+  int64_t* start_rows;
+  int64_t n_rows, n_limit;
+  int32_t od, obs_ld, episodes;
+  uint32_t episode_base;
+};
+
+// one wave per episode; the index never leaves [0, n_rows): n is capped by the allocation and is at least 1
+__global__ __launch_bounds__(256) void model_branch_kernel(const BranchArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (e >= a.episodes) return;
+  int64_t n = a.n_rows_dev ? *a.n_rows_dev : a.n_rows;
+  if (n > a.n_rows) n = a.n_rows;
+  if (a.n_limit > 0 && n > a.n_limit) n = a.n_limit;
+  if (n < 1) n = 1;
+  const uint64_t seed = *a.seed;
+  const U4 w = philox4x32_10(U4{a.episode_base + (uint32_t)e, 0u, 0u, kBranchStream}, (uint32_t)seed,
+                             (uint32_t)(seed >> 32));
+  const int64_t idx = (int64_t)__umul64hi(((uint64_t)w.x << 32) | w.y, (uint64_t)n);  // (gather.h's uniform draw)
+  for (int k = lane; k < a.od; k += 64) {
+    const float v = a.table[(size_t)idx * a.od + k];
+    a.state[(size_t)e * a.od + k] = v;
+    a.obs[(size_t)e * a.obs_ld + k] = v;
+  }
+  if (lane < 4) {
+    a.acc[(size_t)e * 4 + lane] = 0.f;
+    a.disc[(size_t)e * 4 + lane] = lane == 2 ? 1.f : 0.f;
+  }
+  if (lane < 2) a.unc[(size_t)e * 2 + lane] = 0.f;
+  if (lane == 0) a.start_rows[e] = idx;
 }
 
 struct PrepArgs {
@@ -289,23 +407,20 @@ bool valid_member(const osrl_gemv_net_t& n, int in, int out) {
   return n.dims[0] == in && n.dims[n.n_layers] == out;
 }
 
-}  // namespace
-
-extern "C" int osrl_model_env_step(const osrl_model_env_t* env, const float* act, float* state, float* obs,
-                                   int32_t obs_ld, float* acc, float* unc, float* step_out, int32_t episodes,
-                                   void* stream) {
-  if (!env || !act || !state || !obs || !acc || !unc || episodes < 1) return -1;
+// the step's descriptor, checked (false: a bad argument)
+bool fill_step(StepArgs& a, const osrl_model_env_t* env, const float* act, float* state, float* obs, int32_t obs_ld,
+               float* acc, float* unc, float* step_out, int32_t episodes) {
+  if (!env || !act || !state || !obs || !acc || !unc || episodes < 1) return false;
   const osrl_model_env_t& d = *env;
   if (d.n_models < 1 || d.n_models > OSRL_MAX_NETS || d.state_dim < 1 || d.state_dim > OSRL_MODEL_ENV_MAX_STATE ||
       d.action_dim < 1 || obs_ld < d.state_dim || !d.mu_s || !d.sd_s || !d.mu_d || !d.sd_d || !d.mu_r || !d.sd_r ||
       (d.s_lo == nullptr) != (d.s_hi == nullptr))
-    return -1;
-  if (d.mode < OSRL_MODEL_ENV_MEAN || d.mode > OSRL_MODEL_ENV_RANDOM) return -1;
-  if (d.mode == OSRL_MODEL_ENV_MEMBER && (d.member < 0 || d.member >= d.n_models)) return -1;
-  if (d.mode == OSRL_MODEL_ENV_RANDOM && !d.seed && !d.member_in) return -1;
+    return false;
+  if (d.mode < OSRL_MODEL_ENV_MEAN || d.mode > OSRL_MODEL_ENV_RANDOM) return false;
+  if (d.mode == OSRL_MODEL_ENV_MEMBER && (d.member < 0 || d.member >= d.n_models)) return false;
+  if (d.mode == OSRL_MODEL_ENV_RANDOM && !d.seed && !d.member_in) return false;
   for (int m = 0; m < d.n_models; ++m)
-    if (!valid_member(d.net[m], d.state_dim + d.action_dim, d.state_dim + 2)) return -1;
-  StepArgs a;
+    if (!valid_member(d.net[m], d.state_dim + d.action_dim, d.state_dim + 2)) return false;
   memset(&a, 0, sizeof a);  // (the arena finds a block by its bytes: no stray padding)
   a.d = d;
   for (int m = d.n_models; m < OSRL_MAX_NETS; ++m) memset(&a.d.net[m], 0, sizeof a.d.net[m]);
@@ -319,9 +434,49 @@ extern "C" int osrl_model_env_step(const osrl_model_env_t* env, const float* act
   a.step_out = step_out;
   a.obs_ld = obs_ld;
   a.episodes = episodes;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int osrl_model_env_step(const osrl_model_env_t* env, const float* act, float* state, float* obs,
+                                   int32_t obs_ld, float* acc, float* unc, float* step_out, int32_t episodes,
+                                   void* stream) {
+  StepArgs a;
+  if (!fill_step(a, env, act, state, obs, obs_ld, acc, unc, step_out, episodes)) return -1;
   const int tiles = (episodes + kTile - 1) / kTile;
   return osrl_argmem::launch(model_env_kernel, model_env_kernel_p, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream,
                              a);
+}
+
+extern "C" int osrl_model_env_collect(const osrl_model_env_t* env, const osrl_collect_t* rec, const float* act,
+                                      float* state, float* obs, int32_t obs_ld, float* acc, float* unc, float* row_unc,
+                                      int32_t episodes, void* stream) {
+  if (!rec || !env || env->episode_len < 1) return -1;
+  if (!rec->observations || !rec->actions || !rec->next_observations || !rec->rewards || !rec->costs ||
+      !rec->terminals || !rec->timeouts || !rec->disc || !rec->sigma || !rec->gamma || (!rec->seed && !rec->eps_in))
+    return -1;
+  RecArgs a;
+  memset(&a, 0, sizeof a);
+  if (!fill_step(a.s, env, act, state, obs, obs_ld, acc, unc, nullptr, episodes)) return -1;
+  a.c = *rec;
+  a.row_unc = row_unc;
+  const int tiles = (episodes + kTile - 1) / kTile;
+  return osrl_argmem::launch(model_rec_kernel, model_rec_kernel_p, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream,
+                             a);
+}
+
+extern "C" int osrl_model_env_branch(const float* table, int64_t n_rows, const int64_t* n_rows_dev, int64_t n_limit,
+                                     int32_t state_dim, const uint64_t* seed, uint32_t episode_base, float* state,
+                                     float* obs, int32_t obs_ld, float* acc, float* unc, float* disc,
+                                     int64_t* start_rows, int32_t episodes, void* stream) {
+  if (!table || !seed || !state || !obs || !acc || !unc || !disc || !start_rows || n_rows < 1 || n_limit < 0 ||
+      state_dim < 1 || obs_ld < state_dim || episodes < 1)
+    return -1;
+  const BranchArgs a{table, n_rows_dev, seed,    state,     obs,    acc,      unc,         disc,
+                     start_rows, n_rows, n_limit, state_dim, obs_ld, episodes, episode_base};
+  return osrl_argmem::launch(model_branch_kernel, nullptr, dim3((unsigned)((episodes + 3) / 4)), dim3(256), 0,
+                             (hipStream_t)stream, a);
 }
 
 extern "C" int osrl_dyn_prepare(const float* obs, const float* nobs, const float* rew, const float* cost,

@@ -13,6 +13,11 @@ replay a step falls in.  Seed, gamma and sigma live in device memory, so a captu
 ``CDTCollector`` is the same for CDT (``CDTTrainer.collect_targets``): a ``CDTBatchedRollout`` whose step after the
 transformer forward is the one launch ``osrl_cdt_collect`` (csrc/cdt_collect.hip) instead of pick, environment, push and
 cursor, with per-episode targets and, with ``sample=True``, the Gaussian head's own standard deviation as the noise scale.
+
+``ModelCollector`` is ``Collector`` on a learned model (``Trainer.collect_model``): the step ends in
+``osrl_model_env_collect`` (csrc/model_env.hip), episodes start at the environment's initial states or at rows drawn on
+device from a store (``osrl_model_env_branch``, Philox stream 15), and run ``horizon`` steps -- MOPO's / MBPO's branched
+rollouts (DESIGN.md "Training on a learned model").
 """
 from __future__ import annotations
 
@@ -133,10 +138,13 @@ class _Tables:
                                  f"got {tuple(noise.shape)}")
         return noise
 
-    def _finish(self, into) -> Collected:
+    def _finish(self, into, sample_prob=None) -> Collected:
         """The tables into the store or out as copies, and the per-episode sums (the one host sync of the run)."""
         if into is not None:  # (every episode starts at an initial state: the chunk's is_init is right by construction)
-            into.append(self.tables)
+            if sample_prob is None:
+                into.append(self.tables)
+            else:
+                into.append(self.tables, sample_prob=sample_prob)
             data = None
         else:
             data = {k: t.clone() for k, t in self.tables.items()}
@@ -200,6 +208,159 @@ class Collector(_Tables, BatchedRollout):
         finally:
             self._eps = None
         return self._finish(into)
+
+
+def check_model_target(into, start, state_dim: int, action_dim: int, rows: int, sample_prob):
+    """``collect_model``'s ``into=`` / ``sample_prob=`` / ``start=``, judged on the host before anything runs: the new
+    rows' weights as a flat fp64 tensor (None on a uniform target).  ``_check_replay_store``'s width rules, except that a
+    weighted store is taken WITH ``sample_prob`` (a scalar or ``[rows]``); ValueError for a weighted store without it, a
+    uniform one (or no store) with it, a ``state_init`` target of branched rollouts (a branch start is not an initial
+    state: ``is_init`` and every FQE read-out would be wrong), and a ``start`` store of another observation width."""
+    from ..common.replay import _checked_weights
+    if start is not None:
+        if not hasattr(start, "tables") or not hasattr(start, "widths"):
+            raise ValueError(f"start= takes a ReplayStore (or None: the environment's own initial states), not "
+                             f"{type(start).__name__}")
+        if start.widths[0] != state_dim:
+            raise ValueError(f"start=: the store's observations have {start.widths[0]} columns, the model's states "
+                             f"{state_dim}")
+        if start.n_rows < 1:
+            raise ValueError("start=: the store is empty")
+    if into is None:
+        if sample_prob is not None:
+            raise ValueError("sample_prob= are the weights of rows appended to a store: pass into=")
+        return None
+    if getattr(into, "capacity", None) is None:
+        raise ValueError("collect_model(into=): the store is fixed, build it with capacity=")
+    if into.weighted and sample_prob is None:
+        raise ValueError("collect_model(into=): the store draws by weight, pass the new rows' sample_prob=")
+    if not into.weighted and sample_prob is not None:
+        raise ValueError("collect_model(into=): the store draws uniformly, sample_prob= has no table to go to")
+    if start is not None and getattr(into, "state_init", False):
+        raise ValueError("collect_model(start=store, into=): a branch start is not an initial state, a state_init store "
+                         "would mark it as one")
+    into.check_append_widths(observations=state_dim, next_observations=state_dim, actions=action_dim)
+    if sample_prob is None:
+        return None
+    if (sample_prob.dim() if torch.is_tensor(sample_prob) else np.ndim(sample_prob)) == 0:
+        sample_prob = np.full(rows, float(sample_prob), np.float64)
+    return _checked_weights(sample_prob, rows, "transition", positive_sum=False)
+
+
+class ModelCollector(_Tables, BatchedRollout):
+    """``Collector`` on a ``ModelVecEnv``: the evaluating rollout's policy launches, then ``osrl_model_env_collect``
+    (csrc/model_env.hip) where the evaluating rollout issues ``osrl_model_env_step`` -- the same step behind a compile-time
+    flag, so without noise a run is ``BatchedRollout.run``'s bit for bit.  ``run`` rolls every episode ``horizon`` steps
+    from the environment's initial states or from rows of a store (``osrl_model_env_branch``: one launch, drawn on
+    device from the store's live count) and records them with the penalised reward.  What comes out is a model's
+    opinion.  ``start_rows`` (int64 ``[E]``, None without a start store) and ``row_disagreement`` (``[E * horizon]``, the
+    members' disagreement at each recorded row) are device tensors of the last run."""
+
+    def __init__(self, model, venv, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None,
+                 seed: int = 0, z: Optional[torch.Tensor] = None, use_graph: bool = True):
+        from ..common.model_env import ModelVecEnv
+        if not isinstance(venv, ModelVecEnv):
+            raise TypeError(f"collect_model() records rollouts on a learned model: a ModelVecEnv, not "
+                            f"{type(venv).__name__}")
+        super().__init__(model, venv, kind, cost_scale, extra_obs, seed, z, use_graph)
+        self._init_tables()
+        self._starts = torch.zeros(venv.E, dtype=torch.int64, device=self.obs.device)
+        self.start_rows: Optional[torch.Tensor] = None
+        self.row_disagreement: Optional[torch.Tensor] = None
+        self._steps = 0
+
+    def _alloc(self, steps: int) -> None:
+        super()._alloc(steps)
+        n, g = self.venv.E * steps, _GUARD_ROWS
+        buf = torch.full((n + 2 * g,), _SENTINEL, dtype=torch.int32, device=self.obs.device).view(torch.float32)
+        self._unc_buf, self.row_disagreement, self._steps = buf, buf[g:g + n], steps
+
+    def guards_intact(self) -> bool:
+        i = self._unc_buf.view(torch.int32)
+        ok = (i[:_GUARD_ROWS] == _SENTINEL).all() & (i[-_GUARD_ROWS:] == _SENTINEL).all()
+        return super().guards_intact() and bool(ok.item())
+
+    def body(self) -> None:
+        import ctypes as C
+        act = self.policy()
+        v = self.venv
+        L.check(L.load().osrl_model_env_collect(C.byref(self.env_c), self._rec_now(), act.data_ptr(), v.state.data_ptr(),
+                                                self.obs.data_ptr(), self.obs.stride(0), v.acc.data_ptr(),
+                                                v.unc.data_ptr(), self.row_disagreement.data_ptr(), v.E, cur_stream()),
+                "osrl_model_env_collect")
+
+    def _snapshot(self):  # (venv.unc is the environment's extra_state: the base class has it)
+        return super()._snapshot() + [(self.disc, self.disc.clone())]
+
+    def _branch(self, store) -> None:
+        """One launch: a start row per episode, uniform over the store's pinned prefix when it has one, else over its
+        live rows (read from the live-count word: the draw follows ``append`` without a host sync), whatever sampling
+        weights the store carries -- weighted starts are out of scope."""
+        v = self.venv
+        fixed = store.capacity is None
+        L.check(L.load().osrl_model_env_branch(
+            store.tables[0].data_ptr(), store.n_rows if fixed else store.capacity, store._live_ptr(),
+            int(getattr(store, "pinned_rows", 0)), v.state_dim, self.seed_dev.data_ptr(), v.base_seed & 0xFFFFFFFF,
+            v.state.data_ptr(), self.obs.data_ptr(), self.obs.stride(0), v.acc.data_ptr(), v.unc.data_ptr(),
+            self.disc.data_ptr(), self._starts.data_ptr(), v.E, cur_stream()), "osrl_model_env_branch")
+        self.start_rows = self._starts
+
+    @torch.no_grad()
+    def run(self, horizon: Optional[int] = None, start=None, noise_std=0.0, gamma: Optional[float] = None,
+            seed: Optional[int] = None, noise: Optional[torch.Tensor] = None, into=None, sample_prob=None) -> Collected:
+        """``horizon`` (None: the environment's ``episode_len``) steps of every episode, from the environment's initial
+        states (``start=None``) or from rows of the ``ReplayStore`` ``start``.  ``noise_std``, ``gamma``, ``seed`` and
+        ``noise`` (``[horizon, E, action_dim]``) as ``Collector.run`` takes them; ``seed`` keys the branch starts too
+        (Philox stream 15; the noise is stream 13).  ``into`` / ``sample_prob``: ``check_model_target``.  Every refusal
+        comes before the first launch.  ``min(horizon, _CHUNK)`` steps per captured graph; the graph is dropped when the
+        horizon or a by-value argument of the environment (mode, member, penalty: ``launch_epoch``) changes."""
+        from .rollout import _desc_stale
+        v, m = self.venv, self.model
+        steps = int(v.episode_len if horizon is None else horizon)
+        if steps < 1:
+            raise ValueError(f"horizon {steps}: at least one step")
+        E, ad = v.E, m.action_dim
+        w_new = check_model_target(into, start, v.state_dim, ad, E * steps, sample_prob)
+        if start is not None and torch.device(start.device) != self.obs.device:
+            raise ValueError(f"start=: the store is on {start.device}, the environment on {self.obs.device}")
+        if (noise_std.dim() if torch.is_tensor(noise_std) else np.ndim(noise_std)) != 0:
+            k = int(torch.as_tensor(noise_std).numel())
+            if k != E:
+                raise ValueError(f"noise_std holds {k} values, the environment {E} episodes")
+        if noise is not None and tuple(torch.as_tensor(noise).shape) != (steps, E, ad):
+            raise ValueError(f"noise must be [{steps}, {E}, {ad}] (horizon, episodes, action_dim), "
+                             f"got {tuple(torch.as_tensor(noise).shape)}")
+        if _desc_stale(v, self.env_c) or self.env_c.episode_len != steps or self.rec is None:
+            self.env_c, self.graph = v.desc(steps, self.cost_scale), None  # by-value arguments of the captured launches
+            if self.rec is None or self._steps != steps:
+                self._alloc(steps)
+        if seed is not None and int(seed) != self.seed:
+            self.seed = int(seed)
+            if self.kind == "bcql" and not self.z_fixed:
+                self.graph = None  # (the decode noise's seed is a by-value argument of its launch)
+        noise = self._load_noise(noise_std, gamma, noise, steps)
+        if start is None:
+            v.reset(self.obs)
+            self.disc.zero_()
+            self.disc[:, 2] = 1.0
+            self.start_rows = None
+        else:
+            self._branch(start)
+        chunk = min(steps, _CHUNK)
+        graph = self.use_graph and noise is None
+        if graph and self.graph is None:
+            self._capture(chunk)
+        self._eps = noise
+        try:
+            if graph:
+                for _ in range((steps + chunk - 1) // chunk):
+                    self.graph.replay()
+            else:
+                for _ in range(steps):
+                    self.body()
+        finally:
+            self._eps = None
+        return self._finish(into, w_new)
 
 
 class CDTCollector(_Tables, CDTBatchedRollout):

@@ -102,7 +102,8 @@ class BatchedRollout:
         extra = tuple(getattr(self.venv, "extra_state", ()))  # (a model environment's per-episode disagreement sums)
         return [(t, t.clone()) for t in (self.venv.state, self.venv.acc, self.obs, self.st.state) + extra]
 
-    def _capture(self) -> None:
+    def _capture(self, chunk: int = _CHUNK) -> None:
+        """``chunk`` bodies in one graph (a recorded k-step branch captures k launches, not ``_CHUNK``)."""
         snap, host_step = self._snapshot(), self.st.host_step
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -111,7 +112,7 @@ class BatchedRollout:
         torch.cuda.current_stream().wait_stream(s)
         gr = torch.cuda.CUDAGraph()
         with graph_capture(gr):
-            for _ in range(_CHUNK):
+            for _ in range(chunk):
                 self.body()
         torch.cuda.synchronize()
         for t, saved in snap:
