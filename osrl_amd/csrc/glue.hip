@@ -1311,7 +1311,7 @@ int osrl_quantile_ws(const float* x, int64_t n, float q, uint32_t* ws, float* ou
 int osrl_cpq_critic_loss(const float* q_old, int32_t n_q_old, const float* qc_old, int32_t n_qc_old,
                          const float* q, int32_t n_q, const float* rew, const float* done, int32_t rows,
                          float gamma, float q_thres, int32_t rows_global, float* dq, float* stat, void* stream) {
-  if (!q_old || !qc_old || !q || !rew || !done || !dq || rows < 1) return -1;
+  if (!q_old || !qc_old || !q || !rew || !done || !dq || rows < 1 || n_q_old < 1 || n_qc_old < 1 || n_q < 1) return -1;
   CriticLossArgs a{};
   a.q_old = q_old; a.qc_old = qc_old; a.q = q; a.rew = rew; a.done = done; a.dq = dq; a.stat = stat;
   a.n_q_old = n_q_old; a.n_qc_old = n_qc_old; a.n_q = n_q; a.rows = rows;
@@ -1323,7 +1323,7 @@ int osrl_cpq_critic_loss(const float* q_old, int32_t n_q_old, const float* qc_ol
 
 int osrl_cpq_ood_mean(const float* qc_sampled, int32_t n_qc_old, const float* kl, const float* quantile,
                       int32_t n_samples, int32_t rows, int32_t rows_global, float* out, void* stream) {
-  if (!qc_sampled || !kl || !quantile || !out || rows < 1 || n_samples < 1) return -1;
+  if (!qc_sampled || !kl || !quantile || !out || rows < 1 || n_samples < 1 || n_qc_old < 1) return -1;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   const float inv = 1.0f / (float)(rows_global > 0 ? rows_global : rows);
   if (n_qc_old <= kEns)
@@ -1371,7 +1371,7 @@ int osrl_cpq_cost_loss(const float* qc_old_next, int32_t n_qc_old, const float* 
                        const float* ood_mean, const float* cost, int32_t rows, float gamma, float qc_thres,
                        float alpha_lr, int32_t rows_global, float stat_share, float* log_alpha, float* dq,
                        float* stat, void* stream) {
-  if (!qc_old_next || !qc || !cost || (ood_mean && !log_alpha) || !dq || rows < 1) return -1;
+  if (!qc_old_next || !qc || !cost || (ood_mean && !log_alpha) || !dq || rows < 1 || n_qc_old < 1 || n_qc < 1) return -1;
   CostLossArgs a{};
   a.qc_old_next = qc_old_next; a.qc = qc; a.cost = cost; a.ood_mean_p = const_cast<float*>(ood_mean);
   a.log_alpha = log_alpha; a.dq = dq; a.stat = stat;
@@ -1396,7 +1396,7 @@ int osrl_cpq_cost_loss_ood(const float* qc_sampled, int32_t n_qc_sampled, const 
                            int32_t n_qc, float* ood_mean_out, const float* cost, int32_t rows, float gamma,
                            float qc_thres, float alpha_lr, float* log_alpha, float* dq, float* stat, void* stream) {
   if (!qc_sampled || !kl || !quantile || n_samples < 1 || !qc_old_next || !qc || !ood_mean_out || !cost ||
-      !log_alpha || !dq || rows < 1)
+      !log_alpha || !dq || rows < 1 || n_qc_sampled < 1 || n_qc_old < 1 || n_qc < 1)
     return -1;
   CostLossArgs a{};
   a.qc_old_next = qc_old_next; a.qc = qc; a.cost = cost; a.ood_mean_p = ood_mean_out;
@@ -1411,7 +1411,7 @@ int osrl_cpq_cost_loss_ood(const float* qc_sampled, int32_t n_qc_sampled, const 
 
 int osrl_cpq_actor_loss(const float* q, int32_t n_q, const float* qc, int32_t n_qc, int32_t rows, float q_thres,
                         int32_t rows_global, float* dq, float* stat, void* stream) {
-  if (!q || !qc || !dq || rows < 1) return -1;
+  if (!q || !qc || !dq || rows < 1 || n_q < 1 || n_qc < 1) return -1;
   (void)hipGetLastError();  // drop stale errors of unrelated earlier runtime calls
   const float inv = 1.0f / (float)(rows_global > 0 ? rows_global : rows);
   if (n_q <= kEns && n_qc <= kEns)
@@ -1501,7 +1501,7 @@ int osrl_vae_loss_ws(const float* u, const float* act, const float* head, int32_
 
 int osrl_bcq_actor_sums(const float* q, int32_t nq1, int32_t nq2, const float* qc, int32_t nc1, int32_t nc2,
                         int32_t rows, int32_t rows_global, float* out, void* stream) {
-  if (!q || !qc || !out || rows < 1) return -1;
+  if (!q || !qc || !out || rows < 1 || nq1 < 1 || nq2 < 1 || nc1 < 1 || nc2 < 1) return -1;
   (void)hipGetLastError();
   hipLaunchKernelGGL(bcq_actor_sums_kernel, dim3(1), dim3(kRed), 0, S, q, nq1, nq2, qc, nc1, nc2, rows,
                      1.0f / (float)(rows_global > 0 ? rows_global : rows), out);
@@ -1512,7 +1512,7 @@ int osrl_bcq_actor_loss(const float* q, int32_t nq1, int32_t nq2, const float* q
                         int32_t rows, float qc_thres, float KP, float KI, float KD, int32_t rows_global,
                         const float* global_means, float stat_share, float* pid, float* dq, float* dqc, float* stat,
                         void* stream) {
-  if (!q || !qc || !pid || !dq || !dqc || rows < 1) return -1;
+  if (!q || !qc || !pid || !dq || !dqc || rows < 1 || nq1 < 1 || nq2 < 1 || nc1 < 1 || nc2 < 1) return -1;
   (void)hipGetLastError();
   hipLaunchKernelGGL(bcq_actor_loss_kernel, dim3(1), dim3(kRed), 0, S, q, nq1, nq2, qc, nc1, nc2, rows, qc_thres,
                      KP, KI, KD, 1.0f / (float)(rows_global > 0 ? rows_global : rows), global_means, stat_share, pid, dq,

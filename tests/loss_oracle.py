@@ -1,0 +1,887 @@
+"""Plain numpy restatements of the loss / glue entry points of csrc/glue.hip, csrc/bear.hip and csrc/dice.hip, and the
+comparison the CPU and GPU tests share.  TEST INFRASTRUCTURE ONLY: nothing here calls code under ``osrl_amd/``.
+
+Every ``ref_<entry point>(x, dt)`` takes the input dict of a ``loss_cases.Case`` (fp32 arrays, python scalars) and a
+dtype.  ``np.float64`` is the reference; ``np.float32`` is the "honest fp32" run of the same formula, used only to size
+the gates of outputs that go through exp / log / log1p / tanh / sqrt.  It returns a ``Ref``:
+
+* ``out[name]``    every array the launch writes (statistics, per-element gradients, state words updated in place);
+                   NaN marks a word the launch must leave alone,
+* ``scale[name]``  per element, the largest-magnitude intermediate met on the way, in the output's units,
+* ``terms[name]``  for a batch statistic, the per-row terms of its sum (a gate relative to mean|term| cannot be
+                   loosened by a sum that cancels),
+* ``kink[name]``   for every indicator (<=, >=, g > 0, w < 1, x < 0, clamp edges) the distance of each operand pair from
+                   the switch point, relative to the operands' scale; planted equalities are exactly 0.
+
+The formulas follow the reference project (net.py:61-62,191-193,236-238,376-387; cpq.py:145-195; bcql.py:138-146;
+bearl.py:254-268; coptidice.py:15-38,122-215) and torch's tie rules: ``min(dim=0)`` routes to the FIRST minimum, the
+binary ``min`` splits an exact tie 0.5 / 0.5, ``clamp`` passes the gradient at both edges.
+
+Tolerances (``compare``)
+------------------------
+Routing      which entries of a routed gradient are nonzero matches exactly.
+"arith"      elementwise values from + - * / and comparisons only (<= 6 roundings): 8 ulp (8 * 2^-23) of ``scale``.
+"astat"      batch statistics of those kernels: 2e-6 * max(1, mean|term|).  (A numpy emulation of the kernels'
+             reduction order -- 1024 strided accumulators, six butterfly steps, 16 serial adds -- on the fp32 per-row
+             terms of the cpq_critic_loss formula gave at most 1.9e-7 of that scale against fp64 for rows 1..4133 and 5
+             members; the gate is 10 x that.  Dropping the last of 2086 rows moves the statistic ~1.4e-4 of the scale.)
+"trans"      anything through expf / logf / log1pf / tanhf / sqrtf: nobody has measured the device functions on this
+             chip, so the gate of an output is 8 x the largest error (relative to ``scale``) of this oracle's own fp32
+             run against its fp64 run on the same inputs, with a floor of 4 ulp and capped at the project's loss gates
+             (2e-5 of scale for statistics -- "tstat" -- and 5e-5 relative for gradients and state).  The cap is a
+             condition: a kernel that needs more has a finding to explain.
+State words take the class of the operations that produce them.
+"""
+from __future__ import annotations
+
+import contextlib
+import math
+from typing import Dict
+
+import numpy as np
+
+from oracle.coptidice_oracle import ScalarAdam, f_div
+from oracle.osrl_oracle import PID
+
+ULP = 2.0 ** -23
+LS_MIN, LS_MAX = -20.0, 2.0     # net.py:148-149
+VLS_MIN, VLS_MAX = -4.0, 15.0   # net.py:325
+HALF_LOG_2PI = 0.9189385332046727
+F_NAMES = {0: "chi2", 1: "softchi", 2: "kl"}
+
+# ---- mutations of the oracle (tests/test_loss_oracle_cpu.py: "the gates are sharp") -------------------------------------
+_MUT: set = set()
+MUTATIONS = ("drop_last", "drop_1024", "tie_second", "split_one_side", "lt_strict", "no_grad_at_2", "rows_for_global",
+             "no_share", "skip_m4", "no_bias_corr", "no_done")
+
+
+@contextlib.contextmanager
+def mutate(name):
+    _MUT.add(name)
+    try:
+        yield
+    finally:
+        _MUT.discard(name)
+
+
+def _on(name) -> bool:
+    return name in _MUT
+
+
+class Ref:
+    def __init__(self):
+        self.out: Dict[str, np.ndarray] = {}
+        self.scale: Dict[str, np.ndarray] = {}
+        self.terms: Dict[str, np.ndarray] = {}
+        self.kink: Dict[str, np.ndarray] = {}
+        self.cls: Dict[str, str] = {}
+        self.route: set = set()
+        self.aux: Dict[str, np.ndarray] = {}
+
+    def put(self, name, val, cls, scale=None, route=False):
+        self.out[name] = np.asarray(val)
+        self.cls[name] = cls
+        if scale is not None:
+            self.scale[name] = np.broadcast_to(np.asarray(scale, np.float64), self.out[name].shape)
+        if route:
+            self.route.add(name)
+
+
+def _a(x, k, dt):
+    return np.asarray(x[k], dtype=dt)
+
+
+def _mx(*arrs):
+    m = np.abs(np.asarray(arrs[0], np.float64))
+    for a in arrs[1:]:
+        m = np.maximum(m, np.abs(np.asarray(a, np.float64)))
+    return m
+
+
+def _rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.abs(a - b) / np.maximum(np.maximum(np.abs(a), np.abs(b)), 1e-30)
+
+
+def _inv(x, dt, rows):
+    g = x.get("rows_global", 0)
+    if _on("rows_for_global"):
+        g = 0
+    return dt(1.0) / dt(g if g > 0 else rows)
+
+
+def _share(x, dt):
+    return dt(1.0) if _on("no_share") else dt(x.get("stat_share", 1.0))
+
+
+def _row_sum(t):
+    """Sum of per-row terms, under the row-dropping mutations."""
+    t = np.asarray(t)
+    if _on("drop_last") and t.shape[0] > 1:
+        t = t[:-1]
+    if _on("drop_1024") and t.shape[0] > 1024:
+        t = np.delete(t, 1024, 0)
+    return t.sum(dtype=t.dtype)
+
+
+def _le(a, b):
+    return a < b if _on("lt_strict") else a <= b
+
+
+def _ge(a, b):
+    return a > b if _on("lt_strict") else a >= b
+
+
+def _min_first(q):
+    """torch.min(dim=0): value and the index of the FIRST minimum; q [n, ...]."""
+    if _on("skip_m4") and q.shape[0] == 5:
+        q = q[:4]
+    if _on("tie_second"):
+        i = q.shape[0] - 1 - np.argmin(q[::-1], 0)
+    else:
+        i = np.argmin(q, 0)
+    return np.take_along_axis(q, i[None], 0)[0], i
+
+
+def _inside(ls, lo, hi):
+    ok = (ls >= lo) & (ls <= hi)
+    if _on("no_grad_at_2"):
+        ok = ok & (ls != hi)
+    return ok
+
+
+def _edge_kink(ls, lo, hi):
+    return np.minimum(_rel(ls, lo), _rel(ls, hi))
+
+
+def _softplus(z, dt):
+    """F.softplus: z beyond the threshold 20 passes through."""
+    with np.errstate(over="ignore"):
+        return np.where(z > 20, z, np.log1p(np.exp(np.minimum(z, dt(20.0))))).astype(dt)
+
+
+def _onehot(i, n, val):
+    """[n, ...] with val at member i, 0 elsewhere."""
+    out = np.zeros((n,) + i.shape, val.dtype)
+    np.put_along_axis(out, i[None], val[None], 0)
+    return out
+
+
+# ---- glue.hip: distribution heads --------------------------------------------------------------------------------------
+def ref_gauss_head(x, dt):
+    r = Ref()
+    ad = x["ad"]
+    head = _a(x, "head", dt)
+    mu, lsr = head[:, :ad], head[:, ad:]
+    ls = np.clip(lsr, dt(LS_MIN), dt(LS_MAX))
+    sd = np.exp(ls)
+    e = _a(x, "eps", dt) if x.get("eps") is not None else np.zeros_like(mu)
+    u = mu + sd * e
+    t = np.tanh(u)
+    sp = _softplus(dt(-2.0) * u, dt)
+    lp = (dt(-0.5) * e * e - ls - dt(HALF_LOG_2PI)) - dt(2.0) * (dt(math.log(2.0)) - u - sp)  # net.py:191-193
+    lp_scale = (0.5 * e * e + np.abs(ls) + 1 + 2 * (1 + np.abs(u) + np.abs(sp))).sum(1)
+    null = x.get("null", ())
+    if "a" not in null:
+        r.put("a", dt(x["max_action"]) * t, "trans", dt(x["max_action"]) * np.ones_like(t))
+    if "tanh_u" not in null:
+        r.put("tanh_u", t, "trans", np.ones_like(t))
+    if "logp" not in null:
+        r.put("logp", lp.sum(1, dtype=dt), "trans", lp_scale)
+    r.kink["log_std"] = _edge_kink(lsr, LS_MIN, LS_MAX)
+    r.kink["softplus"] = _rel(-2.0 * u, 20.0)
+    return r
+
+
+def ref_gauss_head_bwd(x, dt):
+    r = Ref()
+    ad = x["ad"]
+    head, e, t = _a(x, "head", dt), _a(x, "eps", dt), _a(x, "tanh_u", dt)
+    dn = _a(x, "da_nets", dt)
+    if _on("skip_m4") and dn.shape[0] == 5:
+        dn = dn[:4]
+    da = dn.sum(0, dtype=dt)
+    lsr = head[:, ad:]
+    ls = np.clip(lsr, dt(LS_MIN), dt(LS_MAX))
+    du = da * dt(x["max_action"]) * (dt(1.0) - t * t)
+    dls = np.where(_inside(lsr, LS_MIN, LS_MAX), du * e * np.exp(ls), dt(0.0))
+    s_du = np.abs(dn).sum(0) * abs(x["max_action"])
+    r.put("dhead", np.concatenate([du, dls], 1), "trans",
+          np.concatenate([s_du, s_du * np.abs(e) * np.exp(ls.astype(np.float64))], 1))
+    r.kink["log_std"] = _edge_kink(lsr, LS_MIN, LS_MAX)
+    return r
+
+
+def ref_gauss_ood_sample(x, dt):
+    r = Ref()
+    ad = x["ad"]
+    head, e = _a(x, "head", dt), _a(x, "eps", dt)  # eps [n_samples, rows, ad]
+    mu, lsr = head[:, :ad], head[:, ad:]
+    sd = np.exp(np.clip(lsr, dt(LS_MIN), dt(LS_MAX)))
+    r.put("out", mu[None] + sd[None] * e, "trans", np.abs(mu)[None] + np.abs(sd[None] * e))
+    r.kink["log_std"] = _edge_kink(lsr, LS_MIN, LS_MAX)
+    return r
+
+
+# ---- glue.hip: VAE tails -----------------------------------------------------------------------------------------------
+def ref_vae_latent(x, dt):
+    r = Ref()
+    Lz = x["L"]
+    head, e = _a(x, "head", dt), _a(x, "eps", dt)
+    mean, lsr = head[:, :Lz], head[:, Lz:]
+    sd = np.exp(np.clip(lsr, dt(VLS_MIN), dt(VLS_MAX)))
+    r.put("z", mean + sd * e, "trans", np.abs(mean) + np.abs(sd * e))
+    r.kink["log_std"] = _edge_kink(lsr, VLS_MIN, VLS_MAX)
+    return r
+
+
+def _kl_elem(mean, lsr, dt):
+    sd = np.exp(np.clip(lsr, dt(VLS_MIN), dt(VLS_MAX)))
+    return dt(-0.5) * (dt(1.0) + np.log(sd * sd) - mean * mean - sd * sd)
+
+
+def ref_vae_loss(x, dt):
+    """recon = mse(u, act); KL = -0.5 mean(1 + log var - mean^2 - var); loss = recon + beta KL."""
+    r = Ref()
+    ad, Lz = x["ad"], x["L"]
+    u, act, head = _a(x, "u", dt), _a(x, "act", dt), _a(x, "head", dt)
+    rows = u.shape[0]
+    inv = _inv(x, dt, rows)
+    d = u - act
+    kl = _kl_elem(head[:, :Lz], head[:, Lz:], dt)
+    terms = (d * d).sum(1, dtype=dt) / dt(ad) + dt(x["beta"]) * kl.sum(1, dtype=dt) / dt(Lz)
+    r.put("du", dt(2.0) * d * (inv / dt(ad)), "arith", _mx(u, act) * 2 * float(inv) / ad)
+    r.put("stat", np.array([_row_sum(terms) * inv]), "tstat")
+    r.terms["stat"] = terms
+    r.kink["log_std"] = _edge_kink(head[:, Lz:], VLS_MIN, VLS_MAX)
+    return r
+
+
+ref_vae_loss_ws = ref_vae_loss
+
+
+def ref_vae_latent_bwd(x, dt):
+    r = Ref()
+    Lz = x["L"]
+    head, e, g = _a(x, "head", dt), _a(x, "eps", dt), _a(x, "dz", dt)
+    mean, lsr = head[:, :Lz], head[:, Lz:]
+    sd = np.exp(np.clip(lsr, dt(VLS_MIN), dt(VLS_MAX)))
+    c = dt(x["beta"]) * _inv(x, dt, head.shape[0]) / dt(Lz)
+    dm = g + c * mean
+    dl = np.where(_inside(lsr, VLS_MIN, VLS_MAX), (g * e + c * (sd - dt(1.0) / sd)) * sd, dt(0.0))
+    s_dl = (np.abs(g * e) + np.abs(c) * (sd + 1 / sd)) * sd
+    r.put("dhead", np.concatenate([dm, dl], 1), "trans", np.concatenate([_mx(g, c * mean), s_dl], 1))
+    r.kink["log_std"] = _edge_kink(lsr, VLS_MIN, VLS_MAX)
+    return r
+
+
+def ref_vae_kl_rows(x, dt):
+    r = Ref()
+    Lz = x["L"]
+    head = _a(x, "head", dt)
+    kl = _kl_elem(head[:, :Lz], head[:, Lz:], dt)
+    sd = np.exp(np.clip(head[:, Lz:].astype(np.float64), VLS_MIN, VLS_MAX))
+    inter = 0.5 * (1 + np.abs(np.log(sd * sd)) + head[:, :Lz].astype(np.float64) ** 2 + sd * sd)  # the terms that cancel
+    r.put("kl", kl.sum(1, dtype=dt) / dt(Lz), "trans", inter.sum(1) / Lz)
+    r.kink["log_std"] = _edge_kink(head[:, Lz:], VLS_MIN, VLS_MAX)
+    return r
+
+
+# ---- glue.hip: CPQ ------------------------------------------------------------------------------------------------------
+def _mse_members(q, backup, inv, dt, r, stat_name="stat", dq_name="dq", extra_scale=None):
+    """sum over members of mse(q_e, backup): dq [n, rows], per-row terms, statistic."""
+    if _on("skip_m4") and q.shape[0] == 5:
+        d = q[:4] - backup[None]
+        dq = np.concatenate([dt(2.0) * d * inv, np.full((1,) + backup.shape, np.nan, dt)], 0)
+    else:
+        d = q - backup[None]
+        dq = dt(2.0) * d * inv
+    terms = (d * d).sum(0, dtype=dt)
+    sc = _mx(q, backup[None]) if extra_scale is None else np.maximum(_mx(q, backup[None]), extra_scale[None])
+    r.put(dq_name, dq, "arith", sc * 2 * float(inv))
+    r.terms[stat_name] = terms
+    return _row_sum(terms) * inv
+
+
+def ref_cpq_critic_loss(x, dt):
+    """backup = r + gamma (1 - done) [min qc_targ <= q_thres] min q_targ; loss = sum_e mse(q_e, backup)  (cpq.py:145-152)."""
+    r = Ref()
+    q_old, qc_old, q = _a(x, "q_old", dt), _a(x, "qc_old", dt), _a(x, "q", dt)
+    rew, done = _a(x, "rew", dt), _a(x, "done", dt)
+    inv = _inv(x, dt, rew.shape[0])
+    qt, _ = _min_first(q_old)
+    qct, _ = _min_first(qc_old)
+    nd = dt(1.0) if _on("no_done") else dt(1.0) - done
+    boot = dt(x["gamma"]) * nd * _le(qct, dt(x["q_thres"])).astype(dt) * qt
+    backup = rew + boot
+    stat = _mse_members(q, backup, inv, dt, r, extra_scale=_mx(rew, boot))
+    r.put("stat", np.array([stat]), "astat")
+    r.kink["qc<=thres"] = _rel(qct, x["q_thres"])
+    return r
+
+
+def _ood_rows(x, dt):
+    """per row: mean over the samples of [KL >= quantile] min_e qc_sampled  (cpq.py:183-187)."""
+    qs, kl = _a(x, "qc_sampled", dt), _a(x, "kl", dt)  # [n, n_samples, rows], [n_samples, rows]
+    quant = _a(x, "quantile", dt).reshape(())
+    v, _ = _min_first(qs)
+    return np.where(_ge(kl, quant), v, dt(0.0)).sum(0, dtype=dt) / dt(kl.shape[0]), _rel(kl, quant)
+
+
+def ref_cpq_ood_mean(x, dt):
+    r = Ref()
+    terms, kink = _ood_rows(x, dt)
+    r.put("out", np.array([_row_sum(terms) * _inv(x, dt, terms.shape[0])]), "astat")
+    r.terms["out"] = terms
+    r.kink["kl>=quantile"] = kink
+    return r
+
+
+def _dual_step(la, ood, x, dt, share):
+    """cpq.py:186-195: the -alpha (ood - thres) term of the loss, the ascent on log_alpha, its clamp."""
+    ea = np.exp(la)
+    term = share * ea * (ood - dt(x["qc_thres"]))
+    raw = la + dt(x["alpha_lr"]) * ea * (dt(x["qc_thres"]) - ood)
+    la_new = np.clip(raw, dt(-5.0), dt(5.0))
+    return term, la_new, share * np.exp(la_new), np.array([_rel(abs(float(raw)), 5.0)])
+
+
+def ref_cpq_cost_loss(x, dt):
+    """Three modes: ood_mean NULL (dual step deferred), ood_mean given, OOD mean fused (``qc_sampled`` present)."""
+    r = Ref()
+    qn, qc, cost = _a(x, "qc_old_next", dt), _a(x, "qc", dt), _a(x, "cost", dt)
+    rows = cost.shape[0]
+    inv = _inv(x, dt, rows)
+    m, _ = _min_first(qn)
+    boot = dt(x["gamma"]) * m
+    backup = cost + boot  # cpq.py:161
+    mse = _mse_members(qc, backup, inv, dt, r, extra_scale=_mx(cost, boot))
+    fused = x.get("qc_sampled") is not None
+    if not fused and x.get("ood_mean") is None:
+        r.put("stat", np.array([mse, np.nan]), "astat")
+        return r
+    if fused:
+        terms, kink = _ood_rows(x, dt)
+        ood = _row_sum(terms) * inv
+        r.put("ood_mean_out", np.array([ood]), "astat")
+        r.terms["ood_mean_out"] = terms
+        r.kink["kl>=quantile"] = kink
+    else:
+        ood = _a(x, "ood_mean", dt).reshape(())
+    la = _a(x, "log_alpha", dt).reshape(())
+    term, la_new, alpha, r.kink["log_alpha clamp"] = _dual_step(la, ood, x, dt, _share(x, dt))
+    r.put("stat", np.array([mse - term, alpha]), "tstat", np.array([max(1.0, abs(float(mse)), abs(float(term))),
+                                                                    max(1.0, float(alpha))]))
+    r.put("log_alpha", np.array([la_new]), "trans", np.array([max(abs(float(la)), abs(float(la_new - la)), 1e-30)]))
+    return r
+
+
+ref_cpq_cost_loss_ood = ref_cpq_cost_loss
+
+
+def ref_cpq_alpha_step(x, dt):
+    r = Ref()
+    la, ood = _a(x, "log_alpha", dt).reshape(()), _a(x, "ood_mean", dt).reshape(())
+    s0 = _a(x, "stat", dt)[0]
+    term, la_new, alpha, r.kink["log_alpha clamp"] = _dual_step(la, ood, x, dt, _share(x, dt))
+    r.put("stat", np.array([s0 - term, alpha]), "tstat", np.array([max(1.0, abs(float(s0)), abs(float(term))),
+                                                                   max(1.0, float(alpha))]))
+    r.put("log_alpha", np.array([la_new]), "trans", np.array([max(abs(float(la)), abs(float(la_new - la)), 1e-30)]))
+    return r
+
+
+def ref_cpq_actor_loss(x, dt):
+    """loss = mean(-[min qc_pi <= q_thres] min q_pi)  (cpq.py:203-207); the gradient goes to the FIRST minimum."""
+    r = Ref()
+    q, qc = _a(x, "q", dt), _a(x, "qc", dt)
+    rows = q.shape[1]
+    inv = _inv(x, dt, rows)
+    qm, am = _min_first(q)
+    qcm, _ = _min_first(qc)
+    mask = _le(qcm, dt(x["q_thres"])).astype(dt)
+    dq = _onehot(am, q.shape[0], -mask * inv)
+    r.put("dq", dq, "arith", np.full(dq.shape, float(inv)), route=True)
+    terms = -mask * qm
+    r.put("stat", np.array([_row_sum(terms) * inv]), "astat")
+    r.terms["stat"] = terms
+    r.kink["qc<=thres"] = _rel(qcm, x["q_thres"])
+    return r
+
+
+def ref_mse_loss(x, dt):
+    r = Ref()
+    u, t = _a(x, "u", dt), _a(x, "target", dt)
+    g = x.get("n_global", 0)
+    inv = dt(1.0) / dt(g if g > 0 and not _on("rows_for_global") else u.shape[0])
+    d = u - t
+    r.put("du", dt(2.0) * d * inv, "arith", _mx(u, t) * 2 * float(inv))
+    r.put("stat", np.array([_row_sum(d * d) * inv]), "astat")
+    r.terms["stat"] = d * d
+    return r
+
+
+def ref_clamp(x, dt):
+    r = Ref()
+    v = _a(x, "x", dt)
+    r.put("x", np.clip(v, dt(x["lo"]), dt(x["hi"])), "arith", np.abs(v))
+    return r
+
+
+# ---- glue.hip: BCQ-Lag ---------------------------------------------------------------------------------------------------
+def ref_bcq_perturb(x, dt):
+    """a = clamp(dec + phi max_a tanh-head, -max_a, max_a)  (net.py:61-62)."""
+    r = Ref()
+    dec, t = _a(x, "dec", dt), _a(x, "t", dt)
+    ma = dt(x["max_action"])
+    pre = dec + dt(x["phi"]) * ma * t
+    r.put("a", np.clip(pre, -ma, ma), "arith", _mx(dec, pre, dt(x["phi"]) * ma * t))
+    r.kink["clamp"] = _rel(np.abs(pre), ma)
+    return r
+
+
+def ref_bcq_perturb_bwd(x, dt):
+    r = Ref()
+    dec, t, dn = _a(x, "dec", dt), _a(x, "t", dt), _a(x, "da_nets", dt)
+    ma = dt(x["max_action"])
+    if _on("skip_m4") and dn.shape[0] == 5:
+        dn = dn[:4]
+    da = dn.sum(0, dtype=dt)
+    pre = dec + dt(x["phi"]) * ma * t
+    r.put("dt", np.where((pre >= -ma) & (pre <= ma), da * dt(x["phi"]) * ma, dt(0.0)), "arith",
+          np.abs(dn).sum(0) * abs(x["phi"] * x["max_action"]))
+    r.kink["clamp"] = _rel(np.abs(pre), ma)
+    return r
+
+
+def _minmin(q, n1, dt):
+    """min over each of the two groups, then the binary min: value, the two argmins, the share of group 1."""
+    m1, i1 = _min_first(q[:n1])
+    m2, i2 = _min_first(q[n1:])
+    tie = dt(1.0) if _on("split_one_side") else dt(0.5)
+    w1 = np.where(m1 < m2, dt(1.0), np.where(m1 == m2, tie, dt(0.0)))
+    return np.minimum(m1, m2), i1, i2, w1, _rel(m1, m2)
+
+
+def _minmin_grad(q, n1, i1, i2, w1, g):
+    """d/dq of sum_b g_b minmin(q)_b: [n1 + n2, rows]."""
+    return np.concatenate([_onehot(i1, n1, w1 * g), _onehot(i2, q.shape[0] - n1, (1 - w1) * g)], 0)
+
+
+def ref_bcq_critic_loss(x, dt):
+    """q_t [n1 + n2, rows, n_samples]; v = lmbda min(q1, q2) + (1 - lmbda) max(q1, q2); backup = base + gamma (1 - done)
+    max_j v  (bcql.py:138-146); loss = sum_e mse(q_e, backup)."""
+    r = Ref()
+    q_t, q_on, base = _a(x, "q_t", dt), _a(x, "q_on", dt), _a(x, "base", dt)
+    n1, lm = x["n1"], dt(x["lmbda"])
+    q1, _ = _min_first(q_t[:n1])
+    q2, _ = _min_first(q_t[n1:])
+    v = lm * np.minimum(q1, q2) + (dt(1.0) - lm) * np.maximum(q1, q2)
+    best = v.max(1)
+    nd = dt(1.0) - _a(x, "done", dt) if (x.get("done") is not None and not _on("no_done")) else dt(1.0)
+    boot = dt(x["gamma"]) * nd * best
+    stat = _mse_members(q_on, base + boot, _inv(x, dt, base.shape[0]), dt, r, extra_scale=_mx(base, boot, best))
+    r.put("stat", np.array([stat]), "astat")
+    return r
+
+
+ref_bcq_critic_loss_ws = ref_bcq_critic_loss
+
+
+def ref_bcq_actor_sums(x, dt):
+    r = Ref()
+    q, qc = _a(x, "q", dt), _a(x, "qc", dt)
+    inv = _inv(x, dt, q.shape[1])
+    mq, *_ = _minmin(q, x["nq1"], dt)
+    mc, *_ = _minmin(qc, x["nc1"], dt)
+    r.put("out", np.array([_row_sum(mq) * inv, _row_sum(mc) * inv]), "astat")
+    r.terms["out"] = np.stack([mq, mc], 1)
+    return r
+
+
+def _pid(x, dt, sqc, pid):
+    """LagrangianPIDController.control (net.py:376-387) on the state words (previous error, integral)."""
+    e_new = sqc - dt(x["qc_thres"])
+    diff = max(e_new - pid[0], dt(0.0))
+    integ = max(pid[1] + e_new, dt(0.0))
+    mult = max(dt(x["KP"]) * max(e_new, dt(0.0)) + dt(x["KI"]) * integ + dt(x["KD"]) * diff, dt(0.0))
+    if dt is np.float64:  # the same controller as the train-step oracle's
+        c = PID(x["KP"], x["KI"], x["KD"], x["qc_thres"])
+        c.error_old, c.error_integral = float(pid[0]), float(pid[1])
+        assert abs(c.control(np.array([sqc])) - mult) <= 1e-12 * max(1.0, mult)
+        assert abs(c.error_integral - integ) <= 1e-12 * max(1.0, integ)
+    raw = [float(x["KP"]) * max(float(e_new), 0.0), float(x["KI"]) * float(integ), float(x["KD"]) * float(diff)]
+    kink = np.array([_rel(sqc, x["qc_thres"]), _rel(e_new, pid[0]), _rel(pid[1], -e_new),
+                     abs(sum(raw)) / max(sum(abs(v) for v in raw), 1e-30) if any(raw) else 0.0])
+    return dt(mult), np.array([e_new, integ], dt), _mx(sqc, x["qc_thres"], pid[0], pid[1]), kink
+
+
+def ref_bcq_actor_loss(x, dt):
+    """loss = mean(-q_pi + (qc_pi - thres) mult), mult from the PID controller on mean(qc_pi)  (bcql.py:165-178)."""
+    r = Ref()
+    q, qc = _a(x, "q", dt), _a(x, "qc", dt)
+    rows = q.shape[1]
+    inv, share = _inv(x, dt, rows), _share(x, dt)
+    mq, i1, i2, w1, k1 = _minmin(q, x["nq1"], dt)
+    mc, j1, j2, v1, k2 = _minmin(qc, x["nc1"], dt)
+    if x.get("global_means") is not None:
+        sq, sqc = _a(x, "global_means", dt)[:2]
+    else:
+        sq, sqc = _row_sum(mq) * inv, _row_sum(mc) * inv
+    mult, pid, pscale, r.kink["pid clips"] = _pid(x, dt, sqc, _a(x, "pid", dt))
+    pen = (sqc - dt(x["qc_thres"])) * mult
+    ones = np.ones(rows, dt)
+    r.put("dq", _minmin_grad(q, x["nq1"], i1, i2, w1, -ones * inv), "arith", np.full(q.shape, float(inv)), route=True)
+    r.put("dqc", _minmin_grad(qc, x["nc1"], j1, j2, v1, ones * mult * inv), "arith",
+          np.full(qc.shape, max(float(mult), float(pscale) * (abs(x["KP"]) + abs(x["KI"]) + abs(x["KD"]))) * float(inv)),
+          route=bool(mult != 0))
+    r.put("stat", np.array([(-sq + pen) * share, pen * share, mult * share]), "astat")
+    r.terms["stat"] = np.stack([np.abs(mq) + np.abs(mc) * float(mult), mc * float(mult), mc * 0 + float(mult)], 1)
+    r.put("pid", pid, "astat")
+    r.terms["pid"] = np.stack([mc, mc], 1)
+    r.kink["m1==m2"] = np.concatenate([k1, k2])
+    return r
+
+
+# ---- bear.hip -------------------------------------------------------------------------------------------------------------
+def ref_bear_actor_sums(x, dt):
+    r = Ref()
+    q, qc, mmd = _a(x, "q", dt), _a(x, "qc", dt), _a(x, "mmd", dt)
+    inv = _inv(x, dt, q.shape[1])
+    mq, *_ = _minmin(q, x["nq1"], dt)
+    mc, *_ = _minmin(qc, x["nc1"], dt)
+    r.put("out", np.array([_row_sum(mq) * inv, _row_sum(mc) * inv, _row_sum(mmd) * inv]), "astat")
+    r.terms["out"] = np.stack([mq, mc, mmd], 1)
+    return r
+
+
+def ref_bear_actor_loss(x, dt):
+    """bearl.py:243-275: actor_loss = [n_train_steps >= start] mean(-q) + mean(alpha (mmd - thresh)) + qc penalty; the dual
+    step on log_alpha; ``step`` is the device step count (n_train_steps = step - 1)."""
+    r = Ref()
+    q, qc, mmd = _a(x, "q", dt), _a(x, "qc", dt), _a(x, "mmd", dt)
+    rows = q.shape[1]
+    inv, share = _inv(x, dt, rows), _share(x, dt)
+    mq, i1, i2, w1, k1 = _minmin(q, x["nq1"], dt)
+    mc, j1, j2, v1, k2 = _minmin(qc, x["nc1"], dt)
+    if x.get("global_means") is not None:
+        sq, sqc, smm = _a(x, "global_means", dt)[:3]
+    else:
+        sq, sqc, smm = _row_sum(mq) * inv, _row_sum(mc) * inv, _row_sum(mmd) * inv
+    mult, pid, pscale, r.kink["pid clips"] = _pid(x, dt, sqc, _a(x, "pid", dt))
+    pen = (sqc - dt(x["qc_thres"])) * mult
+    use_q = (x["step"] - 1) >= x["start_update_policy_step"]
+    gq = dt(1.0 if use_q else 0.0)
+    la = _a(x, "log_alpha", dt).reshape(())
+    alpha = np.exp(la)
+    gap = smm - dt(x["target_mmd_thresh"])
+    la_raw = la + dt(x["alpha_lr"]) * alpha * gap
+    la_new = np.clip(la_raw, dt(-5.0), dt(5.0))
+    r.kink["log_alpha clamp"] = np.array([_rel(abs(float(la_raw)), 5.0)])
+    ones = np.ones(rows, dt)
+    r.put("dq", _minmin_grad(q, x["nq1"], i1, i2, w1, -gq * ones * inv), "arith", np.full(q.shape, float(inv)),
+          route=True)
+    r.put("dqc", _minmin_grad(qc, x["nc1"], j1, j2, v1, ones * mult * inv), "arith",
+          np.full(qc.shape, max(float(mult), float(pscale) * (abs(x["KP"]) + abs(x["KI"]) + abs(x["KD"]))) * float(inv)),
+          route=bool(mult != 0))
+    r.put("coef", np.array([alpha * inv]), "trans")
+    r.put("log_alpha", np.array([la_new]), "trans", np.array([max(abs(float(la)), abs(float(la_new - la)), 1e-30)]))
+    stat = np.array([(gq * -sq + alpha * gap + pen) * share, smm * share, pen * share, mult * share,
+                     np.exp(la_new) * share])
+    big = max(1.0, abs(float(sq)), abs(float(alpha * gap)), abs(float(pen)))
+    r.put("stat", stat, "tstat", np.array([big, max(1.0, float(np.abs(mmd).mean())), max(1.0, abs(float(pen))),
+                                           max(1.0, float(mult)), max(1.0, float(np.exp(la_new)))]))
+    r.put("pid", pid, "astat")
+    r.terms["pid"] = np.stack([mc, mc], 1)
+    r.kink["m1==m2"] = np.concatenate([k1, k2])
+    return r
+
+
+def ref_bear_head_bwd(x, dt):
+    """d loss / d (mu, log_std) of the B * M actor rows: coef * dMMD/du on every sample, the critics' action gradient
+    through tanh on sample 0 alone (bearl.py:243-245)."""
+    r = Ref()
+    ad, M = x["ad"], x["n_samples"]
+    head, e, t = _a(x, "head", dt), _a(x, "eps", dt), _a(x, "tanh_u", dt)  # [B * M, .]
+    dm, dn = _a(x, "du_mmd", dt), _a(x, "da_nets", dt)                     # [B * M, ad], [n, B, ad]
+    coef = _a(x, "coef", dt).reshape(())
+    if _on("skip_m4") and dn.shape[0] == 5:
+        dn = dn[:4]
+    du = coef * dm
+    s = np.abs(du).astype(np.float64)
+    first = np.arange(0, head.shape[0], M)
+    du[first] = du[first] + dn.sum(0, dtype=dt) * (dt(1.0) - t[first] * t[first])
+    s[first] += np.abs(dn).sum(0)
+    lsr = head[:, ad:]
+    ls = np.clip(lsr, dt(LS_MIN), dt(LS_MAX))
+    dls = np.where(_inside(lsr, LS_MIN, LS_MAX), du * e * np.exp(ls), dt(0.0))
+    r.put("dhead", np.concatenate([du, dls], 1), "trans",
+          np.concatenate([s, s * np.abs(e) * np.exp(ls.astype(np.float64))], 1))
+    r.kink["log_std"] = _edge_kink(lsr, LS_MIN, LS_MAX)
+    return r
+
+
+# ---- dice.hip -------------------------------------------------------------------------------------------------------------
+def _f(x):
+    return f_div(F_NAMES[x["f_type"]])
+
+
+def ref_dice_optimal_w(x, dt):
+    """e = r - lambda' c + gamma (1 - d) nu(s') - nu(s); w = relu(f'^-1(e / alpha))  (coptidice.py:122-131)."""
+    r = Ref()
+    nu2 = _a(x, "nu2", dt)  # [n_nu, 2, B]
+    rew, cost, done = _a(x, "rew", dt), _a(x, "cost", dt), _a(x, "done", dt)
+    leaves, work = _a(x, "leaves", dt), _a(x, "work", dt).copy()
+    if x["use_saved_lambda"]:
+        lam = work[0]
+        work[:] = np.nan
+    else:
+        lam = _softplus(leaves[3], dt)
+        work[0], work[1] = lam, _softplus(leaves[0], dt)
+        work[2:] = np.nan
+    nu_s, _ = _min_first(nu2[:, 0])
+    nu_n, _ = _min_first(nu2[:, 1])
+    nd = dt(1.0) if _on("no_done") else dt(1.0) - done
+    boot = dt(x["gamma"]) * nd * nu_n
+    e = rew - lam * cost + boot - nu_s
+    s_e = _mx(rew, lam * cost, boot, nu_s, e)
+    g = _f(x)[2]
+    xx = e / dt(x["alpha"])
+    with np.errstate(over="ignore"):
+        w = np.maximum(g(xx), dt(0.0)).astype(dt)
+    if "e" not in x.get("null", ()):
+        r.put("e", e, "trans", s_e)
+    r.put("w", w, "trans", np.maximum(np.abs(w), s_e / x["alpha"] * np.maximum(np.abs(w), 1.0)))
+    r.put("work", work, "trans")
+    r.kink["x<0"] = _rel(xx, 0.0) if x["f_type"] == 1 else np.ones(1)
+    r.kink["g>0"] = _rel(xx, -1.0) if x["f_type"] == 0 else np.ones(1)
+    r.kink["softplus"] = _rel(leaves[[0, 3]], 20.0)
+    return r
+
+
+def _adam(leaf, g, x, dt):
+    """torch.optim.Adam on one scalar leaf (p, m, v) at optimizer step ``x['step']``, betas (0.9, 0.999)."""
+    b1, b2, t = 0.9, 0.999, x["step"]
+    m = dt(b1) * leaf[1] + dt(1 - b1) * g
+    v = dt(b2) * leaf[2] + dt(1 - b2) * g * g
+    bc1, bc2s = (dt(1.0), dt(1.0)) if _on("no_bias_corr") else (dt(1 - b1 ** t), dt(math.sqrt(1 - b2 ** t)))
+    p = leaf[0] - dt(x["scalar_lr"]) / bc1 * m / (np.sqrt(v) / bc2s + dt(1e-8))
+    if dt is np.float64 and not _on("no_bias_corr"):  # the same optimizer as the train-step oracle's
+        a = ScalarAdam(x["scalar_lr"])
+        a.t, a.m, a.v = t - 1, float(leaf[1]), float(leaf[2])
+        assert abs(a.step(float(leaf[0]), float(g)) - p) <= 1e-12 * max(1.0, abs(p))
+    return np.array([p, m, v], dt)
+
+
+def _sigmoid(z, dt):
+    return dt(1.0) / (dt(1.0) + np.exp(-z))
+
+
+def ref_dice_nu_step(x, dt):
+    """nu_loss = (1 - gamma) mean(nu(s) init / p0) + mean(w e - alpha f(w)); the lambda step  (coptidice.py:147,188-201).
+    ``e`` and ``w`` are inputs (w = 0 can be fed directly)."""
+    r = Ref()
+    nu2, e, w = _a(x, "nu2", dt), _a(x, "e", dt), _a(x, "w", dt)
+    done, init = _a(x, "done", dt), _a(x, "is_init", dt)
+    leaves, work = _a(x, "leaves", dt), _a(x, "work", dt)
+    B = e.shape[0]
+    inv, share = _inv(x, dt, B), _share(x, dt)
+    al, gam, p0 = dt(x["alpha"]), dt(x["gamma"]), dt(x["init_state_propotion"])
+    f, fp, g, gp = _f(x)
+    nu_s, i1 = _min_first(nu2[:, 0])
+    _, i2 = _min_first(nu2[:, 1])
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        fw = np.asarray(f(w), dt)
+        fpw = np.asarray(fp(w), dt)
+        xx = e / al
+        dwde = np.where(np.asarray(g(xx)) > 0, np.asarray(gp(xx), dt) / al, dt(0.0)).astype(dt)
+    t_nl = (dt(1.0) - gam) * nu_s * init / p0 + w * e - al * fw
+    de = (w + (e - al * fpw) * dwde) * inv
+    s_de = (np.abs(w) + (np.abs(e) + np.abs(al * fpw)) * np.abs(dwde)) * float(inv)
+    ds = (dt(1.0) - gam) * init * inv / p0 - de
+    nd = dt(1.0) if _on("no_done") else dt(1.0) - done
+    dn = de * gam * nd
+    s_ds = np.maximum(s_de, np.abs((1 - x["gamma"]) * init * float(inv) / x["init_state_propotion"]))
+    dnu = np.stack([_onehot(i1, nu2.shape[0], ds), _onehot(i2, nu2.shape[0], dn)], 1)
+    r.put("dnu", dnu, "trans", np.broadcast_to(np.stack([s_ds, s_de], 0)[None], dnu.shape), route=True)
+    lam, wc = work[0], work[2]
+    stat = np.full(7, np.nan, dt)
+    stat[0], stat[1], stat[2] = _row_sum(fw) * inv, _row_sum(e * e) * inv, _row_sum(t_nl) * inv
+    stat[3] = lam * (dt(x["qc_thres"]) - wc) * share
+    stat[5], stat[6] = work[1] * share, lam * share
+    mt = lambda t: max(1.0, float(np.abs(t).mean()))  # noqa: E731
+    r.put("stat", stat, "tstat", np.array([mt(fw), mt(e * e), mt(np.abs(w * e) + np.abs(al * fw) + np.abs(nu_s)),
+                                           max(1.0, abs(float(lam * x["qc_thres"])), abs(float(lam * wc))), 1.0,
+                                           max(1.0, float(work[1])), max(1.0, float(lam))]))
+    r.terms["stat"] = np.stack([fw, e * e, t_nl], 1)
+    new = leaves.copy()
+    new[3:6] = _adam(leaves[3:6], _sigmoid(leaves[3], dt) * (dt(x["qc_thres"]) - wc), x, dt)
+    new[0:3] = np.nan
+    r.put("leaves", new, "trans", np.maximum(np.abs(leaves), 1e-30))
+    r.kink["w<1"] = _rel(w, 1.0) if x["f_type"] == 1 else np.ones(1)
+    r.kink["x<0"] = _rel(xx, 0.0) if x["f_type"] == 1 else np.ones(1)
+    r.kink["g>0"] = _rel(xx, -1.0) if x["f_type"] == 0 else np.ones(1)
+    return r
+
+
+def ref_dice_chi_step(x, dt):
+    """coptidice.py:149-185: with chi2 NULL (cost_ub_epsilon == 0) weighted_c = mean(w c) and nothing else moves; else
+    the batch softmax over ell / tau', D_kl, weighted_c, chi_loss with its gradient through the NOT detached weights, and
+    the Adam step on tau."""
+    r = Ref()
+    w, cost, done, init = _a(x, "w", dt), _a(x, "cost", dt), _a(x, "done", dt), _a(x, "is_init", dt)
+    leaves, work = _a(x, "leaves", dt), _a(x, "work", dt)
+    B = w.shape[0]
+    g = x.get("rows_global", 0)
+    new_work = np.full(work.shape, np.nan, dt)
+    if x.get("chi2") is None:
+        Bg = g if (g > B and not _on("rows_for_global")) else B
+        new_work[2] = _row_sum(w * cost) / dt(Bg)
+        r.put("work", new_work, "astat")
+        r.terms["work"] = w * cost
+        r.put("stat", np.zeros(3, dt), "astat")
+        r.put("leaves", np.full(6, np.nan, dt), "arith")
+        return r
+    chi2 = _a(x, "chi2", dt)  # [n_chi, 2, B]
+    gam, p0, tau = dt(x["gamma"]), dt(x["init_state_propotion"]), work[1]
+    share = _share(x, dt)
+    cs, i1 = _min_first(chi2[:, 0])
+    cn, i2 = _min_first(chi2[:, 1])
+    nd = dt(1.0) if _on("no_done") else dt(1.0) - done
+    ell = (dt(1.0) - gam) * cs * init / p0 + w * (cost + gam * nd * cn - cs)
+    r.aux["ell"] = ell
+    # data parallel: the softmax, D_kl and chi_loss run over the all-gathered ``ell_all`` [rows_global]; this rank's rows
+    # start at ``row0``; the global scalars are written x stat_share, weighted_c is this rank's share
+    if x.get("ell_all") is not None and not _on("rows_for_global"):
+        ell_g, row0 = _a(x, "ell_all", dt), x["row0"]
+    else:
+        ell_g, row0 = ell, 0
+    Bg = ell_g.shape[0]
+    z = ell_g / tau
+    z = z - z.max()
+    lsm_g = z - np.log(np.exp(z).sum(dtype=dt))
+    wts_g = np.exp(lsm_g) * dt(Bg)
+    t_kl = wts_g * (lsm_g + dt(math.log(Bg))) - wts_g + dt(1.0)
+    dkl = _row_sum(t_kl) / dt(Bg)
+    cl = _row_sum(wts_g * ell_g) / dt(Bg)
+    ell, sm = ell_g[row0:row0 + B], np.exp(lsm_g[row0:row0 + B])
+    wts = sm * dt(Bg)
+    new_work[2] = _row_sum(wts * w * cost) / dt(Bg)
+    dl = sm * (dt(1.0) + (ell - cl) / tau)
+    ds, dn = dl * ((dt(1.0) - gam) * init / p0 - w), dl * w * gam * nd
+    dchi = np.stack([_onehot(i1, chi2.shape[0], ds), _onehot(i2, chi2.shape[0], dn)], 1)
+    s_dl = sm * (1 + (np.abs(ell) + abs(float(cl))) / float(tau))
+    s_d = np.stack([s_dl * (np.abs((1 - x["gamma"]) * init / x["init_state_propotion"]) + np.abs(w)), s_dl * np.abs(w)], 0)
+    r.put("dchi", dchi, "trans", np.broadcast_to(s_d[None], dchi.shape), route=True)
+    mt = lambda t: max(1.0, float(np.abs(t).mean()))  # noqa: E731
+    r.put("work", new_work, "tstat", np.full(work.shape, mt(wts * w * cost)))
+    r.put("stat", np.array([cl, tau * (dt(x["cost_ub_epsilon"]) - dkl), dkl]) * share, "tstat",
+          np.array([mt(wts_g * ell_g), max(1.0, float(tau)) * mt(t_kl), mt(t_kl)]))
+    r.terms["stat"] = np.stack([wts_g * ell_g, t_kl, t_kl], 1)
+    new = np.full(6, np.nan, dt)
+    new[0:3] = _adam(leaves[0:3], _sigmoid(leaves[0], dt) * (dt(x["cost_ub_epsilon"]) - dkl), x, dt)
+    r.put("leaves", new, "trans", np.maximum(np.abs(leaves), 1e-30))
+    return r
+
+
+def ref_dice_perturb(x, dt):
+    r = Ref()
+    v, e, std = _a(x, "x", dt), _a(x, "eps", dt), _a(x, "std", dt)
+    n = e * std[None] * dt(x["scale"])
+    r.put("out", v + n, "arith", _mx(v, n, v + n))
+    return r
+
+
+def ref_dice_actor_loss(x, dt):
+    """actor_loss = -mean(w sum_k Normal(mu, sigma).log_prob(a)) on the pre-tanh Gaussian  (coptidice.py:207-215)."""
+    r = Ref()
+    ad = x["ad"]
+    head, act, w = _a(x, "head", dt), _a(x, "act", dt), _a(x, "w", dt)
+    inv = _inv(x, dt, w.shape[0])
+    mu, lsr = head[:, :ad], head[:, ad:]
+    ls = np.clip(lsr, dt(LS_MIN), dt(LS_MAX))
+    with np.errstate(over="ignore"):
+        iv = np.exp(dt(-2.0) * ls)
+        d = act - mu
+        lp = dt(-0.5) * d * d * iv - ls - dt(HALF_LOG_2PI)
+        c = (-w * inv)[:, None]
+        dmu = c * d * iv
+        dls = np.where(_inside(lsr, LS_MIN, LS_MAX), c * (d * d * iv - dt(1.0)), dt(0.0))
+    s = np.abs(c) * np.concatenate([_mx(act, mu) * iv, d * d * iv + 1], 1)
+    r.put("dhead", np.concatenate([dmu, dls], 1), "trans", s)
+    terms = -w * lp.sum(1, dtype=dt)
+    r.put("stat", np.array([_row_sum(terms) * inv]), "tstat")
+    r.terms["stat"] = terms
+    r.kink["log_std"] = _edge_kink(lsr, LS_MIN, LS_MAX)
+    return r
+
+
+REFS = {k[4:]: v for k, v in list(globals().items()) if k.startswith("ref_")}
+STAT_CAP, GRAD_CAP = 2e-5, 5e-5
+
+
+# ---- the comparison ------------------------------------------------------------------------------------------------------
+def gate_parts(ref64: Ref, ref32: Ref) -> Dict[str, tuple]:
+    """Per output: (the gate relative to scale, the scale of every element)  (module docstring, Tolerances)."""
+    out = {}
+    for name, v in ref64.out.items():
+        v = np.asarray(v, np.float64)
+        cls = ref64.cls[name]
+        if name in ref64.terms and cls in ("astat", "tstat") and name not in ref64.scale:
+            t = np.abs(np.asarray(ref64.terms[name], np.float64))
+            sc = np.maximum(1.0, t.mean(0) if t.ndim > 1 else t.mean())
+            sc = np.broadcast_to(sc, v.shape) if np.ndim(sc) == 0 or np.shape(sc) == v.shape else np.full(v.shape, np.max(sc))
+        elif name in ref64.scale:
+            sc = np.maximum(ref64.scale[name], np.abs(np.nan_to_num(v)))
+        elif cls in ("astat", "tstat"):
+            sc = np.maximum(1.0, np.abs(np.nan_to_num(v)))
+        else:
+            sc = np.maximum(np.abs(np.nan_to_num(v)), 1e-30)
+        sc = np.maximum(np.asarray(sc, np.float64), 1e-30)
+        if cls == "arith":
+            rel = 8 * ULP
+        elif cls == "astat":
+            rel = 2e-6
+        else:
+            err = np.abs(np.asarray(ref32.out[name], np.float64) - v) / sc
+            worst = float(np.nanmax(err)) if np.isfinite(err).any() else 0.0
+            rel = max(4 * ULP, min(8 * worst, STAT_CAP if cls == "tstat" else GRAD_CAP))
+        out[name] = (rel, np.broadcast_to(sc, v.shape))
+    return out
+
+
+def gates(ref64: Ref, ref32: Ref) -> Dict[str, np.ndarray]:
+    """Per output, the absolute gate of every element."""
+    return {name: rel * sc for name, (rel, sc) in gate_parts(ref64, ref32).items()}
+
+
+def compare(got: Dict[str, np.ndarray], ref64: Ref, ref32: Ref):
+    """Worst |got - ref| / gate over every output (inf for a routing mismatch or a missing / non-finite value where the
+    reference has one), with the name of the output that gave it.  A pass is a ratio <= 1."""
+    g = gates(ref64, ref32)
+    worst, where = 0.0, ""
+    for name, v in ref64.out.items():
+        v = np.asarray(v, np.float64)
+        a = np.asarray(got[name], np.float64).reshape(v.shape)
+        need = ~np.isnan(v)
+        if not need.any():
+            continue
+        ratio = np.zeros(v.shape)
+        bad = need & ~np.isfinite(a)
+        ratio[need & ~bad] = (np.abs(a - v) / g[name])[need & ~bad]
+        ratio[bad] = np.inf
+        if name in ref64.route:
+            ratio[need & ~bad & ((a != 0) != (v != 0))] = np.inf
+        m = float(ratio.max())
+        if m > worst:
+            worst, where = m, f"{name}{[int(i) for i in np.unravel_index(int(ratio.argmax()), v.shape)]}"
+    return worst, where
+
+
+def reference(kernel: str, x, mutation=None):
+    """(fp64 Ref, honest-fp32 Ref) of one case's inputs."""
+    fn = REFS[kernel]
+    with np.errstate(all="ignore"):
+        if mutation is None:
+            return fn(x, np.float64), fn(x, np.float32)
+        with mutate(mutation):
+            return fn(x, np.float64), fn(x, np.float32)

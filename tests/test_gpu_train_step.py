@@ -525,6 +525,27 @@ def test_seeded_backward_launches_equal_the_loss_launches(name):
             assert abs(x[k] - y[k]) <= 2e-6 * max(1.0, abs(x[k])), (s, k, x[k], y[k])
 
 
+@pytest.mark.parametrize("num_q,num_qc", [(5, 2), (2, 5)])
+def test_seeded_path_declines_five_member_ensembles(num_q, num_qc):
+    """The seeded backward launches take at most 4 members per ensemble (``kSeedEns``, csrc/mlp.hip: the host check
+    refuses a seed with more).  With SEEDS on, a 5-member CPQ ensemble therefore keeps the loss launches -- the general
+    (counted-loop) form of the CPQ loss kernels, which tests/test_gpu_loss_kernels.py compares with fp64 -- and the step
+    still agrees with the oracle."""
+    from cases import Case
+    from osrl_amd.engine import glue as G
+    assert G.SEEDS
+    c = Case(f"cpq_five_{num_q}{num_qc}", "cpq", od=5, ad=2, B=16, hidden=[32, 32], vae_hidden=48, N=4, num_q=num_q,
+             num_qc=num_qc, steps=2, episode_len=1000, seed=77)
+    m, tr, lg = build_gpu(c)
+    o = build_oracle(c, np.float32)
+    b = gpu_batch(c)
+    for s in range(c.steps):
+        gpu_step(tr, c, b, s)
+        assert m._engine.seeds is None
+        for k, r in oracle_step(o, c, s).items():
+            assert abs(lg.last(k) - r) <= (1e-5 if s == 0 else 1e-4) * max(1.0, abs(r)), (s, k, lg.last(k), r)
+
+
 def test_an_engine_superseded_on_its_model_refuses_to_step():
     """ADVICE r3 (core.py ensure_slabs): once another engine's dW plans are attached to a model's gradient slabs, an
     engine built earlier -- its plans' split counts, its captured graph -- must not run any more; it raises instead of
