@@ -170,13 +170,11 @@ class RolloutMixin:
         """The ``ModelCollector`` of ``collect_model`` on ``menv`` (buffers, tables, captured graph), cached on the
         trainer like ``evaluate``'s rollout."""
         from ..engine.collect import ModelCollector
+        from ..engine.rollout import cached
         cs = self._cost_scale()
         key = (id(menv), self.EVAL_KIND, 1.0 if cs is None else float(cs), self._eval_extra())
-        co = getattr(self, "_model_collector", None)
-        if co is None or co[0] != key:
-            co = (key, ModelCollector(self.model, menv, *key[1:], use_graph=getattr(self, "use_graph", True)))
-            self._model_collector = co
-        return co[1]
+        return cached(self, "_model_collector", key,
+                      lambda: ModelCollector(self.model, menv, *key[1:], use_graph=getattr(self, "use_graph", True)))
 
     @torch.no_grad()
     def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):

@@ -323,12 +323,9 @@ class CDTTrainer:
 
     def _batched_rollout(self):
         """The ``CDTBatchedRollout`` on ``self.env`` (buffers + captured graph), cached on the trainer."""
-        from ..engine.rollout import CDTBatchedRollout
-        ro = getattr(self, "_rollout", None)
-        if ro is None or ro[0] != id(self.env):
-            ro = self._rollout = (id(self.env), CDTBatchedRollout(self.model, self.env, self.cost_scale,
-                                                                  self.cost_reverse, self.use_graph))
-        return ro[1]
+        from ..engine.rollout import CDTBatchedRollout, cached
+        return cached(self, "_rollout", id(self.env), lambda: CDTBatchedRollout(self.model, self.env, self.cost_scale,
+                                                                                 self.cost_reverse, self.use_graph))
 
     def collect_targets(self, target_return, target_cost, noise_std=0.0, sample: bool = False,
                         gamma: Optional[float] = None, seed: int = 0, noise=None, into=None):

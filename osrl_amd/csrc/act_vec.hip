@@ -16,11 +16,12 @@
 //   * noise drawn on the device is Philox keyed by (seed, the slot's episode id, the slot's step, element): an episode
 //     replays identically in any wave and slot;
 //   * the exploration tail (osrl_policy_act_explore_n): a = clip(a_pi + sigma[slot] * eps) on the action the kernel would
-//     publish, collect.hip's arithmetic with collect.hip's noise keys -- a run on host environments records what the
+//     publish, rollout_step.h's arithmetic with the collectors' noise keys -- a run on host environments records what the
 //     device collector would have drawn for the same (seed, episode id, step, column).
 #include <new>
 
 #include "policy_common.h"
+#include "rollout_step.h"
 
 using osrl_rng::philox4x32_10;
 using osrl_rng::U4;
@@ -134,22 +135,14 @@ __device__ __forceinline__ float draw_normal(const VecArgs& a, int32_t episode, 
       philox4x32_10(U4{(uint32_t)(idx >> 2), (uint32_t)episode, (uint32_t)step, 0xAC8u}, a.k0, a.k1), idx);
 }
 
-constexpr uint32_t kExploreStream = 13;  // engine/collect.py _EPS_STREAM
-
-// The exploration tail on element j of slot s, whose scale is sg: v = fmaf(sg, eps, v), then the clip -- collect.hip's
-// arithmetic.  eps is the pinned row's, or normal_word(philox4x32_10({episode id, step, j >> 2, stream 13}, key =
-// explore seed), j & 3): the draw osrl_env_collect documents.  sg == 0 returns v as it is and reads no eps.
+// The exploration tail on element j of slot s, whose scale is sg: csrc/rollout_step.h's draw (eps is the pinned row's, or
+// drawn with the explore seed as key) and, under noise only, the clip.  sg == 0 returns v as it is.
 __device__ __forceinline__ float explore_tail(const VecArgs& a, float sg, int s, int j, float v) {
   if (sg == 0.f) return v;
-  float eps;
-  if (a.host_eps) {
-    eps = a.io.eps[(size_t)s * a.p.act_dim + j];
-  } else {
-    const U4 r = philox4x32_10(
-        U4{(uint32_t)a.io.meta[2 * s], (uint32_t)a.io.meta[2 * s + 1], (uint32_t)(j >> 2), kExploreStream}, a.x0, a.x1);
-    eps = osrl_rng::normal_word(r, j & 3);
-  }
-  v = fmaf(sg, eps, v);
+  v = osrl_rollout::explore(v, sg, [&] {
+    return osrl_rollout::explore_eps((uint32_t)a.io.meta[2 * s], (uint32_t)a.io.meta[2 * s + 1], j, a.x0, a.x1,
+                                     a.host_eps ? a.io.eps : nullptr, (size_t)s * a.p.act_dim + j);
+  });
   return fminf(fmaxf(v, -a.p.max_action), a.p.max_action);
 }
 

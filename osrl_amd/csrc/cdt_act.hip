@@ -37,7 +37,7 @@
 // the largest count and workgroups past their episode's count exit at once.  Grids are sized by the totals: an idle
 // slot costs no rows.
 // The head launch can end in the recording collectors' exploration tail (osrl_cdt_policy_step_slots_explore): a = clip(mu
-// + s * eps) with cdt_collect.hip's arithmetic and noise keys, s a per-slot sigma or exp(log_std) of the head row; the
+// + s * eps) with rollout_step.h's arithmetic and noise keys, s a per-slot sigma or exp(log_std) of the head row; the
 // action taken is what the window records at the next step.  The calls without it read none of its arguments.
 #include <math.h>
 
@@ -46,6 +46,7 @@
 
 #include "gelu.h"
 #include "policy_common.h"
+#include "rollout_step.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -452,7 +453,8 @@ struct HeadArgs {
   int32_t nenv;
   const int32_t* tab;  // the call's table or null.  With a table srow is the episode's own and crow < 0 means "none"
   // the exploration tail (osrl_cdt_policy_step_slots_explore; explore = 0: none of this is read): a = clip(mu + s * eps),
-  // cdt_collect.hip's arithmetic and noise keys.  s = sigma[episode], or with `sample` exp(log_std) of the head row
+  // rollout_step.h's arithmetic and noise keys (cdt_collect.hip's).  s = sigma[episode], or with `sample` exp(log_std) of
+  // the head row
   const float* sigma;         // [nenv] (pinned)
   const float* eps;           // [nenv, action_dim] injected noise (pinned), read when host_eps
   const int32_t* episode_id;  // [nenv] (pinned) the episode word of the noise key; the step word is the timestep
@@ -598,18 +600,11 @@ __global__ __launch_bounds__(kHeadThreads) void cdt_act_head_kernel(const HeadAr
       } else {
         sg = a.sigma[blockIdx.x];
       }
-      if (sg != 0.f) {  // (s == 0: clip(mu) exactly; eps is not even read)
-        float eps;
-        if (a.host_eps) {
-          eps = a.eps[(size_t)blockIdx.x * ad + tid];
-        } else {
-          const int t = a.tab ? a.tab[kTabT * kTabStride + blockIdx.x] : a.t;
-          const osrl_rng::U4 r = osrl_rng::philox4x32_10(
-              osrl_rng::U4{(uint32_t)a.episode_id[blockIdx.x], (uint32_t)t, (uint32_t)(tid >> 2), 13u}, a.x0, a.x1);
-          eps = osrl_rng::normal_word(r, tid & 3);
-        }
-        v = fmaf(sg, eps, v);
-      }
+      v = osrl_rollout::explore(v, sg, [&] {  // (s == 0: clip(mu) exactly)
+        const int t = a.tab ? a.tab[kTabT * kTabStride + blockIdx.x] : a.t;
+        return osrl_rollout::explore_eps((uint32_t)a.episode_id[blockIdx.x], (uint32_t)t, tid, a.x0, a.x1,
+                                         a.host_eps ? a.eps : nullptr, (size_t)blockIdx.x * ad + tid);
+      });
     }
     v = fminf(fmaxf(v, -p.max_action), p.max_action);
     a.io.act_out[(size_t)blockIdx.x * ad + tid] = v;

@@ -7,10 +7,9 @@
 // No shared cursor: an episode's step is its own t = acc[ep][2], the window holds n = min(t + 1, T) filled positions and
 // the head row read is position n - 1.  No workgroup reads what another writes.
 //
-// Why no write can leave the tables or the window: a workgroup writes only while its done latch (acc[ep][3]) is clear AND
-// 0 <= t < episode_len; then the table row ep * episode_len + t < episodes * episode_len, every window position touched
-// is < T, and the time step written is t + 1 <= episode_len (the embedding table has episode_len + T rows).  A graph
-// replay that overshoots the episode's end returns before any store.
+// No write can leave the tables by csrc/rollout_step.h's rule (live_step), nor the window: for a live episode every window
+// position touched is < T, and the time step written is t + 1 <= episode_len (the embedding table has episode_len + T
+// rows).
 //
 // The slide of a full window is one code path for every T: chunks of kPer * nt elements go through registers, each chunk
 // read completely before any of it is written (its sources lie past everything written so far) -- cdt_push_kernel's
@@ -20,12 +19,11 @@
 #include <cstdint>
 
 #include "../../include/osrl_amd.h"
-#include "env_step.h"
-#include "philox.h"
+#include "rollout_step.h"
 
 namespace {
 
-using namespace osrl_rng;
+namespace ro = osrl_rollout;
 
 constexpr int kPer = 4;  // elements a lane carries per slide chunk
 
@@ -57,8 +55,8 @@ __global__ __launch_bounds__(256) void cdt_collect_kernel(osrl_env_t e, osrl_col
   const int od = e.state_dim, ad = e.action_dim, L = e.episode_len, T = w.seq_len;
   float* st = state + (size_t)ep * od;
   float* ac = acc + (size_t)ep * 4;
-  const int step = (int)ac[2];
-  if (ac[3] != 0.f || step < 0 || step >= L) return;  // uniform per workgroup, ahead of every barrier and every store
+  int step;
+  if (!ro::live_step(ac, L, step)) return;  // uniform per workgroup, ahead of every barrier and every store
   const int n = min(step + 1, T);                     // filled window positions; the step being taken is position n - 1
   float* S = w.states + (size_t)ep * T * od;
   float* A = w.actions + (size_t)ep * T * ad;
@@ -68,20 +66,9 @@ __global__ __launch_bounds__(256) void cdt_collect_kernel(osrl_env_t e, osrl_col
   if (t < od) l.s[t] = st[t];
   if (t < ad) {
     const float* h = w.head + ((size_t)ep * T + (n - 1)) * w.head_width;
-    float v = h[t];  // mu (cdt.py:489-493)
     const float sg = w.sample ? expf(h[ad + t]) : c.sigma[ep];  // head rows are [mu | log_std], no log-std bounds
-    if (sg != 0.f) {  // (s == 0: clip(mu) exactly; eps is not even read)
-      float eps;
-      if (c.eps_in) {
-        eps = c.eps_in[((size_t)step * E + ep) * ad + t];
-      } else {
-        const uint64_t seed = *c.seed;
-        const U4 r = philox4x32_10(U4{c.episode_base + (uint32_t)ep, (uint32_t)step, (uint32_t)(t >> 2), c.stream_id},
-                                   (uint32_t)seed, (uint32_t)(seed >> 32));
-        eps = normal_word(r, t & 3);
-      }
-      v = fmaf(sg, eps, v);
-    }
+    const float v = ro::explore(h[t] /* mu (cdt.py:489-493) */, sg,
+                                [&] { return ro::explore_eps(c, ep, step, t, ((size_t)step * E + ep) * ad + t); });
     l.a[t] = osrl_env::clip_action(v, e.max_action);
   }
   __syncthreads();
@@ -100,22 +87,7 @@ __global__ __launch_bounds__(256) void cdt_collect_kernel(osrl_env_t e, osrl_col
   if (t == 0) {
     float rew, cost;
     osrl_env::outcome(e, l, rew, cost);
-    const float len = ac[2] + 1.f;
-    ac[0] += rew;
-    ac[1] += cost * e.cost_scale;
-    ac[2] = len;
-    const bool last = len >= (float)L;
-    if (last) ac[3] = 1.f;
-    c.rewards[row] = rew;
-    c.costs[row] = cost;
-    c.terminals[row] = 0.f;
-    c.timeouts[row] = last ? 1.f : 0.f;
-    // discounted sums: osrl_env_collect's arithmetic
-    float* dc = c.disc + (size_t)ep * 4;
-    const float pw = dc[2];
-    dc[0] = fmaf(pw, rew, dc[0]);
-    dc[1] = fmaf(pw, cost * e.cost_scale, dc[1]);
-    dc[2] = pw * *c.gamma;
+    ro::record(c, row, ep, rew, cost, e.cost_scale, ro::tick(ac, rew, cost, e.cost_scale, L));
     // to-go values: cdt_push_kernel's arithmetic (cdt.py:507-508), read before the slide moves them
     const float cw = (w.cost_reverse ? 1.f - cost : cost) * w.cost_scale;
     r_new = R[n - 1] - rew;
@@ -145,12 +117,8 @@ __global__ __launch_bounds__(256) void cdt_collect_kernel(osrl_env_t e, osrl_col
 
 extern "C" int osrl_cdt_collect(const osrl_env_t* env, const osrl_collect_t* rec, const osrl_cdt_window_t* win,
                                 float* state, float* acc, int32_t episodes, void* stream) {
-  if (!env || !rec || !win || !state || !acc || episodes < 1) return -1;
-  if (env->state_dim < 1 || env->state_dim > osrl_env::kMaxDim || env->action_dim < 1 ||
-      env->action_dim > osrl_env::kMaxAct || env->episode_len < 1 || !env->At || !env->Bt || !env->w || !env->goal)
-    return -1;
-  if (!rec->observations || !rec->actions || !rec->next_observations || !rec->rewards || !rec->costs ||
-      !rec->terminals || !rec->timeouts || !rec->disc || !rec->sigma || !rec->gamma || (!rec->seed && !rec->eps_in))
+  if (!env || !win || !state || !acc || episodes < 1) return -1;
+  if (!ro::valid_env(env, env->state_dim /* no obs rows here */) || env->episode_len < 1 || !ro::valid_collect(rec))
     return -1;
   if (!win->states || !win->actions || !win->returns || !win->costs_to_go || !win->time_steps || !win->mask ||
       !win->head || win->seq_len < 1 || win->seq_len > 1024 ||

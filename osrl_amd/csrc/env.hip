@@ -8,11 +8,9 @@
 #include <cstdint>
 
 #include "../../include/osrl_amd.h"
-#include "env_step.h"
+#include "rollout_step.h"
 
 namespace {
-
-using osrl_env::kMaxDim;
 
 __global__ __launch_bounds__(256) void env_step_kernel(osrl_env_t e, const float* __restrict__ act,
                                                        float* __restrict__ state, float* __restrict__ obs,
@@ -36,15 +34,7 @@ __global__ __launch_bounds__(256) void env_step_kernel(osrl_env_t e, const float
   if (t == 0) {
     float rew, cost;
     osrl_env::outcome(e, l, rew, cost);
-    const float len = ac[2] + 1.f;
-    ac[0] += rew;
-    ac[1] += cost * e.cost_scale;
-    if (step_out) {
-      step_out[(size_t)ep * 2] = rew;
-      step_out[(size_t)ep * 2 + 1] = cost;
-    }
-    ac[2] = len;
-    if (len >= (float)e.episode_len) ac[3] = 1.f;
+    osrl_rollout::tick(ac, rew, cost, e.cost_scale, e.episode_len, step_out ? step_out + (size_t)ep * 2 : nullptr);
   }
 }
 
@@ -162,10 +152,7 @@ __global__ void cursor_inc_kernel(int* cursor, int episode_len) {
 
 extern "C" int osrl_env_step(const osrl_env_t* env, const float* act, float* state, float* obs, int32_t obs_ld,
                              float* acc, float* step_out, int32_t episodes, void* stream) {
-  if (!env || !act || !state || !obs || !acc || episodes < 1) return -1;
-  if (env->state_dim < 1 || env->state_dim > kMaxDim || env->action_dim < 1 || env->action_dim > osrl_env::kMaxAct ||
-      obs_ld < env->state_dim || !env->At || !env->Bt || !env->w || !env->goal)
-    return -1;
+  if (!osrl_rollout::valid_env(env, obs_ld) || !act || !state || !obs || !acc || episodes < 1) return -1;
   (void)hipGetLastError();
   const int threads = ((env->state_dim + 63) / 64) * 64;
   hipLaunchKernelGGL(env_step_kernel, dim3(episodes), dim3(threads), 0, (hipStream_t)stream, *env, act, state, obs,

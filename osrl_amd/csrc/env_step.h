@@ -1,5 +1,6 @@
 // env_step.h -- one step of the synthetic safe environment for one episode (= one workgroup), shared by env_step_kernel
-// (env.hip) and env_collect_kernel (collect.hip): the two must agree bit for bit, so the arithmetic exists once.
+// (env.hip), env_collect_kernel (collect.hip) and cdt_collect_kernel (cdt_collect.hip): they must agree bit for bit, so the
+// arithmetic exists once.  What a step does besides the environment's arithmetic is csrc/rollout_step.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

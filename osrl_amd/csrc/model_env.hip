@@ -14,17 +14,16 @@
 //   * the member a RANDOM-mode episode follows is a Philox word keyed by (seed, episode id, the episode's own step): a
 //     function of nothing else.
 //
-// The same body records (model_rec_kernel, osrl_model_env_collect): the compile-time flag kRecord adds csrc/collect.hip's
+// The same body records (model_rec_kernel, osrl_model_env_collect): the compile-time flag kRecord adds csrc/rollout_step.h's
 // per-episode exploration noise on the action while it is staged, one row of a DSRL-layout dataset per episode and step,
-// and the discounted sums; with sigma == 0 the step is model_env_kernel's bit for bit.
-// Why no write can leave the tables (collect.hip's argument): a row of the tile stores only while it is live, and with
-// kRecord live means e < episodes AND the done latch acc[e][3] is clear AND 0 <= step = acc[e][2] < episode_len; then row
-// e * episode_len + step < episodes * episode_len.  A captured graph replays whole chunks of steps and overshoots the
-// episode's end: those rows are not live and return before any store.
+// and the discounted sums; with sigma == 0 the step is model_env_kernel's bit for bit.  A row of the tile stores only
+// while it is live, and with kRecord live means e < episodes AND rollout_step.h's live_step: its rule keeps every write
+// inside the tables.
 //
 // model_branch_kernel (osrl_model_env_branch) starts every episode at a row drawn uniformly from a store's observations.
 #include "argmem.h"
 #include "policy_common.h"
+#include "rollout_step.h"
 
 using osrl_rng::philox4x32_10;
 using osrl_rng::U4;
@@ -139,13 +138,14 @@ __device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l) {
   const int r = tid / kRowThreads, j = tid % kRowThreads;
   if (tid < kTile) {
     const int e = e0 + tid;
-    bool lv = e < a.episodes && a.acc[(size_t)e * 4 + 3] == 0.f;
+    bool lv = e < a.episodes;
     int st = 0;
     if constexpr (kRecord) {  // the step is read once, here: the member draw, the noise and the table row all use it
-      st = lv ? (int)a.acc[(size_t)e * 4 + 2] : 0;
-      lv = lv && st >= 0 && st < a.d.episode_len;
+      lv = lv && osrl_rollout::live_step(a.acc + (size_t)e * 4, a.d.episode_len, st);
       l.step[tid] = st;
       l.sig[tid] = lv ? rc.c.sigma[e] : 0.f;
+    } else {
+      lv = lv && a.acc[(size_t)e * 4 + 3] == 0.f;
     }
     int js = -1;
     if (lv && a.d.mode == OSRL_MODEL_ENV_MEMBER) js = a.d.member;
@@ -183,20 +183,10 @@ __device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l) {
       else if (c < od + ad) {
         v = a.act[(size_t)e * ad + (c - od)];
         if constexpr (kRecord) {
-          const float sg = l.sig[rr];
-          if (sg != 0.f) {  // (sigma == 0: the deterministic action exactly; eps is not even read)
+          v = osrl_rollout::explore(v, l.sig[rr], [&] {
             const int k = c - od, st = l.step[rr];
-            float eps;
-            if (rc.c.eps_in) {
-              eps = rc.c.eps_in[((size_t)st * a.episodes + e) * ad + k];
-            } else {
-              const uint64_t seed = *rc.c.seed;
-              const U4 w = philox4x32_10(U4{rc.c.episode_base + (uint32_t)e, (uint32_t)st, (uint32_t)(k >> 2), rc.c.stream_id},
-                                         (uint32_t)seed, (uint32_t)(seed >> 32));
-              eps = osrl_rng::normal_word(w, k & 3);
-            }
-            v = fmaf(sg, eps, v);
-          }
+            return osrl_rollout::explore_eps(rc.c, e, st, k, ((size_t)st * a.episodes + e) * ad + k);
+          });
         }
         v = fminf(fmaxf(v, -a.d.max_action), a.d.max_action);
       }
@@ -263,7 +253,7 @@ __device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l) {
   if (!alive) return;  // finished episodes keep their state and totals
   const float* yh = (a.d.mode == OSRL_MODEL_ENV_MEAN ? l.ysum : l.ysel) + r * kYS;
   const bool clamp = a.d.s_lo != nullptr && a.d.s_hi != nullptr;
-  size_t row = 0;  // (recording) live: ep < episodes and 0 <= step < episode_len, so row < episodes * episode_len
+  size_t row = 0;  // (recording) the live row's: inside the tables by live_step's rule
   if constexpr (kRecord) row = (size_t)ep * a.d.episode_len + l.step[r];
 #pragma unroll
   for (int q = 0; q < kKeep; ++q) {
@@ -286,32 +276,14 @@ __device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l) {
     float rew = fmaf(a.d.sd_r[0], yh[od], a.d.mu_r[0]);
     if (a.d.reward_penalty != 0.f) rew -= a.d.reward_penalty * d;
     const float cost = yh[od + 1] > 0.5f ? 1.f : 0.f;
-    float* ac = a.acc + (size_t)ep * 4;
-    const float len = ac[2] + 1.f;  // (csrc/env.hip env_step_kernel's bookkeeping)
-    ac[0] += rew;
-    ac[1] += cost * a.d.cost_scale;
-    if (a.step_out) {
-      a.step_out[(size_t)ep * 2] = rew;
-      a.step_out[(size_t)ep * 2 + 1] = cost;
-    }
-    ac[2] = len;
-    const bool last = len >= (float)a.d.episode_len;
-    if (last) ac[3] = 1.f;
+    const bool last = osrl_rollout::tick(a.acc + (size_t)ep * 4, rew, cost, a.d.cost_scale, a.d.episode_len,
+                                         a.step_out ? a.step_out + (size_t)ep * 2 : nullptr);
     float* un = a.unc + (size_t)ep * 2;
     un[0] = fmaxf(un[0], d);
     un[1] += d;
     if constexpr (kRecord) {
-      rc.c.rewards[row] = rew;
-      rc.c.costs[row] = cost;
-      rc.c.terminals[row] = 0.f;
-      rc.c.timeouts[row] = last ? 1.f : 0.f;
       if (rc.row_unc) rc.row_unc[row] = d;
-      // discounted sums (collect.hip): one rounding per step each (fmaf), gamma^t by repeated multiplication
-      float* dc = rc.c.disc + (size_t)ep * 4;
-      const float pw = dc[2];
-      dc[0] = fmaf(pw, rew, dc[0]);
-      dc[1] = fmaf(pw, cost * a.d.cost_scale, dc[1]);
-      dc[2] = pw * *rc.c.gamma;
+      osrl_rollout::record(rc.c, row, ep, rew, cost, a.d.cost_scale, last);
     }
   }
 }
@@ -452,10 +424,7 @@ extern "C" int osrl_model_env_step(const osrl_model_env_t* env, const float* act
 extern "C" int osrl_model_env_collect(const osrl_model_env_t* env, const osrl_collect_t* rec, const float* act,
                                       float* state, float* obs, int32_t obs_ld, float* acc, float* unc, float* row_unc,
                                       int32_t episodes, void* stream) {
-  if (!rec || !env || env->episode_len < 1) return -1;
-  if (!rec->observations || !rec->actions || !rec->next_observations || !rec->rewards || !rec->costs ||
-      !rec->terminals || !rec->timeouts || !rec->disc || !rec->sigma || !rec->gamma || (!rec->seed && !rec->eps_in))
-    return -1;
+  if (!osrl_rollout::valid_collect(rec) || !env || env->episode_len < 1) return -1;
   RecArgs a;
   memset(&a, 0, sizeof a);
   if (!fill_step(a.s, env, act, state, obs, obs_ld, acc, unc, nullptr, episodes)) return -1;

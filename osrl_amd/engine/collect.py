@@ -28,7 +28,7 @@ import torch
 
 from .. import _lib as L
 from .core import cur_stream
-from .rollout import _CHUNK, BatchedRollout, CDTBatchedRollout
+from .rollout import _CHUNK, BatchedRollout, CDTBatchedRollout, cached
 
 _EPS_STREAM = 13   # Philox stream id of the exploration noise (11 / 12: the BCQL decode noise of rollout.py / fqe.py)
 _GUARD_ROWS = 4    # sentinel rows before and after every table (``Collector.guards_intact``)
@@ -59,20 +59,22 @@ def merge_datasets(datasets: List[Dict[str, torch.Tensor]]) -> Dict[str, torch.T
     return {k: torch.cat([d[k] for d in datasets], 0) for k in datasets[0]}
 
 
-def _check_replay_store(into, state_dim: int, action_dim: int) -> None:
-    """``into=`` a ``ReplayStore``: ValueError unless it grows, draws uniformly and has the environment's widths."""
+def _check_replay_store(into, state_dim: int, action_dim: int, who: str = "collect", weighted_ok: bool = False) -> None:
+    """``into=`` a ``ReplayStore``: ValueError unless it grows, draws uniformly (``weighted_ok``: the caller has its own
+    rule for weights) and has the environment's widths."""
     if into is None:
         return
     if getattr(into, "capacity", None) is None:
-        raise ValueError("collect(into=): the store is fixed, build it with capacity=")
-    if into.weighted:
+        raise ValueError(f"{who}(into=): the store is fixed, build it with capacity=")
+    if into.weighted and not weighted_ok:
         raise ValueError("collect(into=): the store draws by weight; collect a dataset and append it with sample_prob=")
     into.check_append_widths(observations=state_dim, next_observations=state_dim, actions=action_dim)
 
 
 class _Tables:
-    """What the two collectors share: the guarded tables, the ``osrl_collect_t`` descriptor, and the noise parameters
-    that live in device memory.  The host class provides ``venv``, ``model``, ``obs`` and ``seed``."""
+    """What the collectors share: the guarded tables, the ``osrl_collect_t`` descriptor, the noise parameters that live in
+    device memory, and the start (``_begin``) and the recorded loop (``_drive_recorded``) of a run.  The host class is a
+    rollout of engine/rollout.py with a ``seed``."""
 
     def _init_tables(self) -> None:
         dev, E = self.obs.device, self.venv.E
@@ -84,11 +86,12 @@ class _Tables:
         self.tables: Dict[str, torch.Tensor] = {}
         self.rec: Optional[L.CollectT] = None
         self._eps: Optional[torch.Tensor] = None  # the injected noise of the run in progress
+        self._steps = 0                           # rows per episode of the tables
 
     def _alloc(self, steps: int) -> None:
         E, od, ad, dev = self.venv.E, self.venv.state_dim, self.model.action_dim, self.obs.device
         n, g = E * steps, _GUARD_ROWS
-        self.bufs, self.tables = {}, {}
+        self.bufs, self.tables, self._steps = {}, {}, steps
         for k in KEYS:
             w = {"observations": od, "next_observations": od, "actions": ad}.get(k, 0)  # 0: a 1-D table, as DSRL's are
             buf = torch.full(((n + 2 * g) * max(w, 1),), _SENTINEL, dtype=torch.int32, device=dev).view(torch.float32)
@@ -119,24 +122,55 @@ class _Tables:
         return rec
 
     def _load_noise(self, noise_std, gamma: Optional[float], noise, steps: int) -> Optional[torch.Tensor]:
-        """sigma, gamma and ``self.seed`` into their device words; the injected noise checked and on the device."""
+        """``noise_std`` and the injected ``noise`` checked (the one place: ValueError before anything is launched), then
+        sigma, gamma and ``self.seed`` into their device words and the noise onto the device."""
         E, ad, dev = self.venv.E, self.model.action_dim, self.obs.device
-        if (noise_std.dim() if torch.is_tensor(noise_std) else np.ndim(noise_std)) == 0:
-            self.sigma.fill_(float(noise_std))
+        if (noise_std.dim() if torch.is_tensor(noise_std) else np.ndim(noise_std)) != 0:
+            noise_std = torch.as_tensor(noise_std, dtype=torch.float32).reshape(-1)
+            if noise_std.numel() != E:
+                raise ValueError(f"noise_std holds {noise_std.numel()} values, the environment {E} episodes")
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32)
+            if tuple(noise.shape) != (steps, E, ad):
+                raise ValueError(f"noise must be [{steps}, {E}, {ad}] (steps, episodes, action_dim), "
+                                 f"got {tuple(noise.shape)}")
+            noise = noise.to(dev).contiguous()
+        if torch.is_tensor(noise_std) and noise_std.dim():
+            self.sigma.copy_(noise_std, non_blocking=True)
         else:
-            sg = torch.as_tensor(noise_std, dtype=torch.float32).reshape(-1)
-            if sg.numel() != E:
-                raise ValueError(f"noise_std holds {sg.numel()} values, the environment {E} episodes")
-            self.sigma.copy_(sg, non_blocking=True)
+            self.sigma.fill_(float(noise_std))
         self.gamma.fill_(1.0 if gamma is None else float(gamma))
         s64 = self.seed & 0xFFFFFFFFFFFFFFFF
         self.seed_dev.fill_(s64 - (1 << 64) if s64 >= (1 << 63) else s64)
-        if noise is not None:
-            noise = torch.as_tensor(noise, dtype=torch.float32).to(dev).contiguous()
-            if tuple(noise.shape) != (steps, E, ad):
-                raise ValueError(f"noise must be [{steps}, {E}, {ad}] (episode_len, episodes, action_dim), "
-                                 f"got {tuple(noise.shape)}")
         return noise
+
+    def _begin(self, steps: int, seed: Optional[int], noise_std, gamma, noise) -> Optional[torch.Tensor]:
+        """The start of every recorded run, after the caller's own argument checks: the seed taken (BCQ-L's decode noise
+        has it as a by-value argument of its launch: a new one drops the graph), the noise checked and loaded, the
+        environment descriptor and the tables brought to ``steps`` (by-value arguments too).  Returns the injected noise
+        on the device, or None."""
+        if seed is not None and int(seed) != self.seed:
+            self.seed = int(seed)
+            if getattr(self, "kind", None) == "bcql" and not self.z_fixed:
+                self.graph = None
+        noise = self._load_noise(noise_std, gamma, noise, steps)
+        self._sync_desc(steps)
+        if self.rec is None or self._steps != steps:
+            self._alloc(steps)
+            self.graph = None
+        return noise
+
+    def _reset_disc(self) -> None:
+        self.disc.zero_()
+        self.disc[:, 2] = 1.0
+
+    def _drive_recorded(self, steps: int, chunk: int, noise: Optional[torch.Tensor]) -> None:
+        """``_drive`` with the injected noise, if any, visible to ``body`` while it runs (the run is then eager)."""
+        self._eps = noise
+        try:
+            self._drive(steps, chunk, self.use_graph and noise is None)
+        finally:
+            self._eps = None
 
     def _finish(self, into, sample_prob=None) -> Collected:
         """The tables into the store or out as copies, and the per-episode sums (the one host sync of the run)."""
@@ -180,33 +214,12 @@ class Collector(_Tables, BatchedRollout):
         ``ReplayStore`` built with ``capacity`` -- the tables go straight into ``into.append`` (one device copy per
         table, no clone) and the result's ``dataset`` is None; a store whose widths differ from the environment's
         (BC multi-task appends the cost return to the observations) is a ValueError before the run."""
-        v, m = self.venv, self.model
-        _check_replay_store(into, v.state_dim, m.action_dim)
-        steps = min(m.episode_len, v.episode_len or m.episode_len)
-        if self.env_c.episode_len != steps or self.rec is None:  # descriptors are by-value arguments of the graph
-            self.env_c.episode_len, self.graph = steps, None
-            self._alloc(steps)
-        if seed is not None and int(seed) != self.seed:
-            self.seed = int(seed)
-            if self.kind == "bcql" and not self.z_fixed:
-                self.graph = None  # (the decode noise's seed is a by-value argument of its launch)
-        noise = self._load_noise(noise_std, gamma, noise, steps)
-        v.reset(self.obs)
-        self.disc.zero_()
-        self.disc[:, 2] = 1.0
-        graph = self.use_graph and noise is None
-        if graph and self.graph is None:
-            self._capture()
-        self._eps = noise
-        try:
-            if graph:
-                for _ in range((steps + _CHUNK - 1) // _CHUNK):
-                    self.graph.replay()
-            else:
-                for _ in range(steps):
-                    self.body()
-        finally:
-            self._eps = None
+        _check_replay_store(into, self.venv.state_dim, self.model.action_dim)
+        steps = self._episode_steps()
+        noise = self._begin(steps, seed, noise_std, gamma, noise)
+        self.venv.reset(self.obs)
+        self._reset_disc()
+        self._drive_recorded(steps, _CHUNK, noise)
         return self._finish(into)
 
 
@@ -230,8 +243,7 @@ def check_model_target(into, start, state_dim: int, action_dim: int, rows: int, 
         if sample_prob is not None:
             raise ValueError("sample_prob= are the weights of rows appended to a store: pass into=")
         return None
-    if getattr(into, "capacity", None) is None:
-        raise ValueError("collect_model(into=): the store is fixed, build it with capacity=")
+    _check_replay_store(into, state_dim, action_dim, "collect_model", weighted_ok=True)
     if into.weighted and sample_prob is None:
         raise ValueError("collect_model(into=): the store draws by weight, pass the new rows' sample_prob=")
     if not into.weighted and sample_prob is not None:
@@ -239,7 +251,6 @@ def check_model_target(into, start, state_dim: int, action_dim: int, rows: int, 
     if start is not None and getattr(into, "state_init", False):
         raise ValueError("collect_model(start=store, into=): a branch start is not an initial state, a state_init store "
                          "would mark it as one")
-    into.check_append_widths(observations=state_dim, next_observations=state_dim, actions=action_dim)
     if sample_prob is None:
         return None
     if (sample_prob.dim() if torch.is_tensor(sample_prob) else np.ndim(sample_prob)) == 0:
@@ -267,13 +278,12 @@ class ModelCollector(_Tables, BatchedRollout):
         self._starts = torch.zeros(venv.E, dtype=torch.int64, device=self.obs.device)
         self.start_rows: Optional[torch.Tensor] = None
         self.row_disagreement: Optional[torch.Tensor] = None
-        self._steps = 0
 
     def _alloc(self, steps: int) -> None:
         super()._alloc(steps)
         n, g = self.venv.E * steps, _GUARD_ROWS
         buf = torch.full((n + 2 * g,), _SENTINEL, dtype=torch.int32, device=self.obs.device).view(torch.float32)
-        self._unc_buf, self.row_disagreement, self._steps = buf, buf[g:g + n], steps
+        self._unc_buf, self.row_disagreement = buf, buf[g:g + n]
 
     def guards_intact(self) -> bool:
         i = self._unc_buf.view(torch.int32)
@@ -314,52 +324,21 @@ class ModelCollector(_Tables, BatchedRollout):
         (Philox stream 15; the noise is stream 13).  ``into`` / ``sample_prob``: ``check_model_target``.  Every refusal
         comes before the first launch.  ``min(horizon, _CHUNK)`` steps per captured graph; the graph is dropped when the
         horizon or a by-value argument of the environment (mode, member, penalty: ``launch_epoch``) changes."""
-        from .rollout import _desc_stale
-        v, m = self.venv, self.model
+        v = self.venv
         steps = int(v.episode_len if horizon is None else horizon)
         if steps < 1:
             raise ValueError(f"horizon {steps}: at least one step")
-        E, ad = v.E, m.action_dim
-        w_new = check_model_target(into, start, v.state_dim, ad, E * steps, sample_prob)
+        w_new = check_model_target(into, start, v.state_dim, self.model.action_dim, v.E * steps, sample_prob)
         if start is not None and torch.device(start.device) != self.obs.device:
             raise ValueError(f"start=: the store is on {start.device}, the environment on {self.obs.device}")
-        if (noise_std.dim() if torch.is_tensor(noise_std) else np.ndim(noise_std)) != 0:
-            k = int(torch.as_tensor(noise_std).numel())
-            if k != E:
-                raise ValueError(f"noise_std holds {k} values, the environment {E} episodes")
-        if noise is not None and tuple(torch.as_tensor(noise).shape) != (steps, E, ad):
-            raise ValueError(f"noise must be [{steps}, {E}, {ad}] (horizon, episodes, action_dim), "
-                             f"got {tuple(torch.as_tensor(noise).shape)}")
-        if _desc_stale(v, self.env_c) or self.env_c.episode_len != steps or self.rec is None:
-            self.env_c, self.graph = v.desc(steps, self.cost_scale), None  # by-value arguments of the captured launches
-            if self.rec is None or self._steps != steps:
-                self._alloc(steps)
-        if seed is not None and int(seed) != self.seed:
-            self.seed = int(seed)
-            if self.kind == "bcql" and not self.z_fixed:
-                self.graph = None  # (the decode noise's seed is a by-value argument of its launch)
-        noise = self._load_noise(noise_std, gamma, noise, steps)
+        noise = self._begin(steps, seed, noise_std, gamma, noise)
         if start is None:
             v.reset(self.obs)
-            self.disc.zero_()
-            self.disc[:, 2] = 1.0
+            self._reset_disc()
             self.start_rows = None
         else:
             self._branch(start)
-        chunk = min(steps, _CHUNK)
-        graph = self.use_graph and noise is None
-        if graph and self.graph is None:
-            self._capture(chunk)
-        self._eps = noise
-        try:
-            if graph:
-                for _ in range((steps + chunk - 1) // chunk):
-                    self.graph.replay()
-            else:
-                for _ in range(steps):
-                    self.body()
-        finally:
-            self._eps = None
+        self._drive_recorded(steps, min(steps, _CHUNK), noise)
         return self._finish(into, w_new)
 
 
@@ -374,7 +353,7 @@ class CDTCollector(_Tables, CDTBatchedRollout):
                  use_graph: bool = True):
         super().__init__(model, venv, cost_scale, cost_reverse, use_graph)
         self.seed, self.sample = int(seed), False
-        self.env_c = venv.desc(model.episode_len, self.cost_scale)
+        self.env_c = self._desc(model.episode_len)
         self._init_tables()
         e, w = self.eng, L.CdtWindowT()
         w.states, w.actions, w.returns, w.costs_to_go = (e.states.data_ptr(), e.actions.data_ptr(), e.returns.data_ptr(),
@@ -383,6 +362,9 @@ class CDTCollector(_Tables, CDTBatchedRollout):
         w.seq_len, w.head_width, w.sample = model.seq_len, e.head.shape[1], 0
         w.cost_reverse, w.cost_scale = int(self.cost_reverse), self.cost_scale
         self.win = w
+
+    def _desc(self, steps: int):
+        return self.venv.desc(steps, self.cost_scale)
 
     def body(self) -> None:
         v = self.venv
@@ -402,37 +384,21 @@ class CDTCollector(_Tables, CDTBatchedRollout):
         v, m = self.venv, self.model
         check_sampling(m, sample, noise_std)
         target_return, target_cost = self._targets(target_return, target_cost)
-        steps = min(m.episode_len, v.episode_len or m.episode_len)
+        steps = self._episode_steps()
         if isinstance(into, SequenceStore):
             into.check_append(v.E, v.E * steps, observations=v.state_dim, actions=m.action_dim)
         else:
             _check_replay_store(into, v.state_dim, m.action_dim)
-        if self.env_c.episode_len != steps or self.rec is None:  # descriptors are by-value arguments of the graph
-            self.env_c.episode_len, self.graph = steps, None
-            self._alloc(steps)
         if bool(sample) != self.sample:
             self.sample, self.graph = bool(sample), None
             self.win.sample = int(self.sample)
-        if seed is not None:
-            self.seed = int(seed)
-        noise = self._load_noise(noise_std, gamma, noise, steps)
+        noise = self._begin(steps, seed, noise_std, gamma, noise)
         m.repack()
-        graph = self.use_graph and noise is None
-        if graph and self.graph is None:
+        if self.use_graph and noise is None and self.graph is None:
             self._capture()  # runs the body on scratch state; the reset below starts the real run
         self._reset(target_return, target_cost)
-        self.disc.zero_()
-        self.disc[:, 2] = 1.0
-        self._eps = noise
-        try:
-            if graph:
-                for _ in range((steps + _CHUNK - 1) // _CHUNK):
-                    self.graph.replay()
-            else:
-                for _ in range(steps):
-                    self.body()
-        finally:
-            self._eps = None
+        self._reset_disc()
+        self._drive_recorded(steps, _CHUNK, noise)
         return self._finish(into)
 
 
@@ -452,23 +418,17 @@ def collect_cdt_batched(trainer, **run_kw) -> Collected:
     """``CDTTrainer.collect_targets`` on a ``VecSyntheticSafeEnv``; the collector is cached on the trainer like
     ``collect_batched``'s."""
     venv = trainer.env
-    key = (id(venv), float(trainer.cost_scale), bool(trainer.cost_reverse))
-    co = getattr(trainer, "_collector", None)
-    if co is None or co[0] != key:
-        co = (key, CDTCollector(trainer.model, venv, trainer.cost_scale, trainer.cost_reverse,
-                                use_graph=getattr(trainer, "use_graph", True)))
-        trainer._collector = co
-    return co[1].run(**run_kw)
+    co = cached(trainer, "_collector", (id(venv), float(trainer.cost_scale), bool(trainer.cost_reverse)),
+                lambda: CDTCollector(trainer.model, venv, trainer.cost_scale, trainer.cost_reverse,
+                                     use_graph=getattr(trainer, "use_graph", True)))
+    return co.run(**run_kw)
 
 
 def collect_batched(trainer, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None, **run_kw) -> Collected:
     """``Trainer.collect`` on a ``VecSyntheticSafeEnv``; the collector (buffers, tables, captured graph) is cached on the
     trainer like ``evaluate``'s rollout, and reads the model's packed weights in place."""
     venv = trainer.env
-    key = (id(venv), kind, float(cost_scale), extra_obs)
-    co = getattr(trainer, "_collector", None)
-    if co is None or co[0] != key:
-        co = (key, Collector(trainer.model, venv, kind, cost_scale, extra_obs,
-                             use_graph=getattr(trainer, "use_graph", True)))
-        trainer._collector = co
-    return co[1].run(**run_kw)
+    co = cached(trainer, "_collector", (id(venv), kind, float(cost_scale), extra_obs),
+                lambda: Collector(trainer.model, venv, kind, cost_scale, extra_obs,
+                                  use_graph=getattr(trainer, "use_graph", True)))
+    return co.run(**run_kw)

@@ -36,7 +36,72 @@ def _desc_stale(venv, desc) -> bool:
     return epoch is not None and getattr(desc, "launch_epoch", None) != epoch
 
 
-class BatchedRollout:
+def cached(owner, attr: str, key, make):
+    """The ``(key, object)`` pair a trainer keeps a rollout object in (``_rollout``, ``_collector``,
+    ``_model_collector``): ``make()`` builds the object when there is none yet or the key has changed."""
+    c = getattr(owner, attr, None)
+    if c is None or c[0] != key:
+        c = (key, make())
+        setattr(owner, attr, c)
+    return c[1]
+
+
+class _Driver:
+    """The run loop every on-device rollout shares.  The host class provides ``body()`` (one env step of all episodes),
+    ``_desc(steps)`` (the environment's launch descriptor), ``venv``, ``env_c`` and ``graph``; no device work happens
+    here except through ``body``, ``graph.replay`` and ``_capture``."""
+
+    graph: Optional[torch.cuda.CUDAGraph] = None
+
+    def _snapshot(self):
+        """``(tensor, clone)`` of what one ``body`` changes: ``_capture`` runs the body once for real before it records,
+        then restores these.  Empty here: ``CDTBatchedRollout`` resets after its capture."""
+        return []
+
+    def _capture(self, chunk: int = _CHUNK) -> None:
+        """``chunk`` bodies in one graph (a recorded k-step branch captures k launches, not ``_CHUNK``)."""
+        snap = self._snapshot()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self.body()
+        torch.cuda.current_stream().wait_stream(s)
+        gr = torch.cuda.CUDAGraph()
+        with graph_capture(gr):
+            for _ in range(chunk):
+                self.body()
+        torch.cuda.synchronize()
+        for t, saved in snap:
+            t.copy_(saved)
+        self.graph = gr
+
+    def _sync_desc(self, steps: int) -> None:
+        """The environment descriptor is a by-value launch argument of the captured graph: rebuilt when the
+        environment's own by-value arguments changed (``_desc_stale``), set to ``steps``; either drops the graph."""
+        if _desc_stale(self.venv, self.env_c):
+            self.env_c, self.graph = self._desc(steps), None
+        if self.env_c.episode_len != steps:
+            self.env_c.episode_len, self.graph = steps, None
+
+    def _drive(self, steps: int, chunk: int, graph: bool) -> None:
+        """``steps`` env steps: ``ceil(steps / chunk)`` replays of the ``chunk``-step graph (captured here unless it
+        exists; the done latch makes the overshoot a no-op) or ``steps`` eager bodies."""
+        if graph:
+            if self.graph is None:
+                self._capture(chunk)
+            for _ in range((steps + chunk - 1) // chunk):
+                self.graph.replay()
+        else:
+            for _ in range(steps):
+                self.body()
+
+    def _totals(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Per-episode (return, cost sum, length) as fp64: the one host sync of a rollout."""
+        acc = self.venv.acc.cpu().numpy().astype(np.float64)
+        return acc[:, 0], acc[:, 1], acc[:, 2]
+
+
+class BatchedRollout(_Driver):
     """``eval_episodes`` episodes of one vector environment driven by ``model``'s policy on device."""
 
     def __init__(self, model, venv, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None,
@@ -54,7 +119,7 @@ class BatchedRollout:
             self.obs[:, od] = float(extra_obs)
         self.a = torch.zeros(E, ad, **f)
         self.cost_scale = float(cost_scale)
-        self.env_c = venv.desc(m.episode_len, cost_scale)
+        self.env_c = self._desc(m.episode_len)
         self.st = StepState(dev, ["x"])
         m.repack()
         if kind == "bc":
@@ -72,7 +137,9 @@ class BatchedRollout:
             if z is not None:  # fixed decode noise (parity tests); clamped like VAE.decode does (net.py:334-335)
                 self.z.copy_(torch.as_tensor(z, **f).reshape(E, Lz))
                 G.clamp_(self.z, -0.5, 0.5)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
+
+    def _desc(self, steps: int):
+        return self.venv.desc(steps, self.cost_scale)
 
     def policy(self) -> torch.Tensor:
         """The policy's launches on ``self.obs`` -> the [E, action_dim] actions (a buffer of this object)."""
@@ -98,47 +165,25 @@ class BatchedRollout:
         self.venv.step(self.env_c, self.policy(), self.obs)
 
     def _snapshot(self):
-        """What one ``body`` changes, cloned: ``_capture`` runs the body once for real before it records."""
         extra = tuple(getattr(self.venv, "extra_state", ()))  # (a model environment's per-episode disagreement sums)
         return [(t, t.clone()) for t in (self.venv.state, self.venv.acc, self.obs, self.st.state) + extra]
 
     def _capture(self, chunk: int = _CHUNK) -> None:
-        """``chunk`` bodies in one graph (a recorded k-step branch captures k launches, not ``_CHUNK``)."""
-        snap, host_step = self._snapshot(), self.st.host_step
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self.body()
-        torch.cuda.current_stream().wait_stream(s)
-        gr = torch.cuda.CUDAGraph()
-        with graph_capture(gr):
-            for _ in range(chunk):
-                self.body()
-        torch.cuda.synchronize()
-        for t, saved in snap:
-            t.copy_(saved)
+        host_step = self.st.host_step  # (the step counter's host half is part of what the warm-up body changes)
+        super()._capture(chunk)
         self.st.host_step = host_step
-        self.graph = gr
+
+    def _episode_steps(self) -> int:
+        return min(self.model.episode_len, self.venv.episode_len or self.model.episode_len)
 
     @torch.no_grad()
     def run(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """All episodes to completion -> per-episode (return, cost * cost_scale, length) as numpy arrays."""
         self.venv.reset(self.obs)
-        steps = min(self.model.episode_len, self.venv.episode_len or self.model.episode_len)
-        if _desc_stale(self.venv, self.env_c):
-            self.env_c, self.graph = self.venv.desc(steps, self.cost_scale), None
-        if self.env_c.episode_len != steps:  # the env descriptor is a by-value launch argument of the captured graph
-            self.env_c.episode_len, self.graph = steps, None
-        if self.use_graph and self.graph is None:
-            self._capture()
-        if self.use_graph:
-            for _ in range((steps + _CHUNK - 1) // _CHUNK):
-                self.graph.replay()
-        else:
-            for _ in range(steps):
-                self.body()
-        acc = self.venv.acc.cpu().numpy()  # the one host sync of the rollout
-        return acc[:, 0].astype(np.float64), acc[:, 1].astype(np.float64), acc[:, 2].astype(np.float64)
+        steps = self._episode_steps()
+        self._sync_desc(steps)
+        self._drive(steps, _CHUNK, self.use_graph)
+        return self._totals()
 
 
 def evaluate_batched(trainer, kind: str, eval_episodes: int, cost_scale: float = 1.0,
@@ -149,17 +194,14 @@ def evaluate_batched(trainer, kind: str, eval_episodes: int, cost_scale: float =
     venv = trainer.env
     if venv.E != eval_episodes:
         raise ValueError(f"the vector environment holds {venv.E} episodes, evaluate() was asked for {eval_episodes}")
-    key = (id(venv), kind, float(cost_scale), extra_obs)
-    ro = getattr(trainer, "_rollout", None)
-    if ro is None or ro[0] != key:
-        ro = (key, BatchedRollout(trainer.model, venv, kind, cost_scale, extra_obs,
-                                  use_graph=getattr(trainer, "use_graph", True)))
-        trainer._rollout = ro
-    ret, cost, length = ro[1].run()
+    ro = cached(trainer, "_rollout", (id(venv), kind, float(cost_scale), extra_obs),
+                lambda: BatchedRollout(trainer.model, venv, kind, cost_scale, extra_obs,
+                                       use_graph=getattr(trainer, "use_graph", True)))
+    ret, cost, length = ro.run()
     return float(ret.mean()), float(cost.mean()), float(length.mean())
 
 
-class CDTBatchedRollout:
+class CDTBatchedRollout(_Driver):
     """``CDTTrainer.rollout`` (cdt.py:436-518) for E episodes at once.  The reference re-slices the last ``seq_len``
     steps of a full-history buffer every env step; here an inference ``CDTEngine`` with batch = E holds the window
     in its batch buffers (left-aligned while it fills, sliding afterwards; csrc/env.hip ``cdt_push_kernel``), so one
@@ -182,8 +224,12 @@ class CDTBatchedRollout:
         self.act = torch.zeros(E, m.action_dim, **f)
         self.step_out = torch.zeros(E, 2, **f)
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.env_c = venv.desc(m.episode_len, 1.0)  # acc[:,1] = raw cost sum, as cdt.py:513 accumulates it
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.env_c = self._desc(m.episode_len)
+
+    def _desc(self, steps: int):
+        return self.venv.desc(steps, 1.0)  # acc[:,1] = raw cost sum, as cdt.py:513 accumulates it
+
+    _episode_steps = BatchedRollout._episode_steps
 
     def _targets(self, target_return, target_cost):
         """Each target as a float (one for all episodes) or as ``[E]`` fp32 values on the device; any other length is a
@@ -234,39 +280,16 @@ class CDTBatchedRollout:
                                           cur_stream()),
                 "osrl_cdt_rollout_push")
 
-    def _capture(self) -> None:
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self.body()
-        torch.cuda.current_stream().wait_stream(s)
-        gr = torch.cuda.CUDAGraph()
-        with graph_capture(gr):
-            for _ in range(_CHUNK):
-                self.body()
-        torch.cuda.synchronize()
-        self.graph = gr
-
     @torch.no_grad()
     def run(self, target_return, target_cost) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Per-episode (return, raw cost sum, length).  Each target is one value for all episodes or ``E`` of them
         (episode ``e`` conditions on its own pair); a wrong length is a ValueError before anything runs."""
-        m = self.model
         target_return, target_cost = self._targets(target_return, target_cost)
-        steps = min(m.episode_len, self.venv.episode_len or m.episode_len)
-        if _desc_stale(self.venv, self.env_c):
-            self.env_c, self.graph = self.venv.desc(steps, 1.0), None
-        if self.env_c.episode_len != steps:
-            self.env_c.episode_len, self.graph = steps, None
-        m.repack()
+        steps = self._episode_steps()
+        self._sync_desc(steps)
+        self.model.repack()
         if self.use_graph and self.graph is None:
             self._capture()  # runs the body on scratch state; _reset below starts the real rollout
         self._reset(target_return, target_cost)
-        if self.use_graph:
-            for _ in range((steps + _CHUNK - 1) // _CHUNK):
-                self.graph.replay()
-        else:
-            for _ in range(steps):
-                self.body()
-        acc = self.venv.acc.cpu().numpy()
-        return acc[:, 0].astype(np.float64), acc[:, 1].astype(np.float64), acc[:, 2].astype(np.float64)
+        self._drive(steps, _CHUNK, self.use_graph)
+        return self._totals()
