@@ -77,6 +77,8 @@ class Ref:
         self.cls: Dict[str, str] = {}
         self.route: set = set()
         self.aux: Dict[str, np.ndarray] = {}
+        self.cap: Dict[str, float] = {}         # "trans" / "tstat": a cap other than GRAD_CAP / STAT_CAP (tests/cdt_kernel_oracle.py)
+        self.gate: Dict[str, np.ndarray] = {}   # an explicit absolute gate per element (order-free sum bounds)
 
     def put(self, name, val, cls, scale=None, route=False):
         self.out[name] = np.asarray(val)
@@ -826,6 +828,9 @@ def gate_parts(ref64: Ref, ref32: Ref) -> Dict[str, tuple]:
     for name, v in ref64.out.items():
         v = np.asarray(v, np.float64)
         cls = ref64.cls[name]
+        if name in ref64.gate:
+            out[name] = (1.0, np.broadcast_to(np.maximum(np.asarray(ref64.gate[name], np.float64), 1e-45), v.shape))
+            continue
         if name in ref64.terms and cls in ("astat", "tstat") and name not in ref64.scale:
             t = np.abs(np.asarray(ref64.terms[name], np.float64))
             sc = np.maximum(1.0, t.mean(0) if t.ndim > 1 else t.mean())
@@ -844,7 +849,7 @@ def gate_parts(ref64: Ref, ref32: Ref) -> Dict[str, tuple]:
         else:
             err = np.abs(np.asarray(ref32.out[name], np.float64) - v) / sc
             worst = float(np.nanmax(err)) if np.isfinite(err).any() else 0.0
-            rel = max(4 * ULP, min(8 * worst, STAT_CAP if cls == "tstat" else GRAD_CAP))
+            rel = max(4 * ULP, min(8 * worst, ref64.cap.get(name, STAT_CAP if cls == "tstat" else GRAD_CAP)))
         out[name] = (rel, np.broadcast_to(sc, v.shape))
     return out
 

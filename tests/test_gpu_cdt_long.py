@@ -3,13 +3,13 @@ kernels (osrl_attention_*_ws), osrl_linear with K up to 4096, the 16-features-pe
 window -- against fp64 numpy and the numpy oracle (oracle/cdt_oracle.py)."""
 import ctypes as C
 import dataclasses
-import math
 
 import numpy as np
 import pytest
 import torch
 
 from cases import CDT_CASES, CDTCase, make_cdt_batch
+from cdt_kernel_oracle import attn_ref as _attn_ref  # the one fp64 restatement of the attention core
 from test_gpu_cdt import C5_SLICE, build_cdt_gpu
 
 pytestmark = pytest.mark.gpu
@@ -35,30 +35,6 @@ def _attn_problem(B, S, E, H, rep, prefix, seed):
         mk[3] = 0  # a fully padded sample: every row without a valid key
     do = rs.randn(B, S, E).astype(np.float32)
     return qkv, mk, do
-
-
-def _attn_ref(qkv, mk, do, B, S, E, H, rep, prefix, Mk):
-    d = E // H
-    key_ok = np.repeat(mk > 0, rep, 1)
-    if prefix:
-        key_ok = np.concatenate([key_ok[:, :1], key_ok], 1)
-    q64 = qkv.astype(np.float64)
-    q, k, v = (q64[..., i * E:(i + 1) * E].reshape(B, S, H, d).transpose(0, 2, 1, 3) for i in range(3))
-    blocked = np.triu(np.ones((S, S), bool), 1)[None, None] | ~key_ok[:, None, None, :]
-    sc = np.where(blocked, -np.inf, q @ k.transpose(0, 1, 3, 2) / math.sqrt(d))
-    mx = sc.max(-1, keepdims=True)
-    dead = ~np.isfinite(mx)
-    P = np.exp(sc - np.where(dead, 0.0, mx))
-    P = np.where(dead, 0.0, P / np.where(dead, 1.0, P.sum(-1, keepdims=True)))
-    Pd = P * Mk
-    oref = (Pd @ v).transpose(0, 2, 1, 3).reshape(B, S, E)
-    dO = do.astype(np.float64).reshape(B, S, H, d).transpose(0, 2, 1, 3)
-    dP = (dO @ v.transpose(0, 1, 3, 2)) * Mk
-    dv = Pd.transpose(0, 1, 3, 2) @ dO
-    dS = P * (dP - (dP * P).sum(-1, keepdims=True))
-    dq, dk = dS @ k / math.sqrt(d), dS.transpose(0, 1, 3, 2) @ q / math.sqrt(d)
-    ref = np.concatenate([x.transpose(0, 2, 1, 3).reshape(B, S, E) for x in (dq, dk, dv)], -1)
-    return oref, ref
 
 
 def _run_tiled(lib, L, qt, mt, dot, B, S, E, H, rep, prefix, drp, cur_stream):
