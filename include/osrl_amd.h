@@ -234,10 +234,19 @@ int osrl_mlp_backward_dz_tail(const osrl_mlp_t* net, int32_t rows, const osrl_ml
  *                        of the reward nets are the tile's first partial, those of the cost nets its second;
  *                          stat[0] = stat_scale sum_{e < n_a, r} (y_e - backup_e)^2,  stat2[0] = stat_scale sum_{e >= n_a, r} (.)^2
  *                        (either may be NULL) = the sum over members of the batch-mean squared error (net.py:240-242)
+ *   OSRL_SEED_GAUSS_NLL  the diagonal-Gaussian dynamics member (algorithms/dynamics.py, probabilistic=True): every net's output
+ *                        row is (od + 1 means | raw cost | od + 1 raw log-variances), NL = 2 od + 3, x0 = the target table
+ *                        [rows, od + 2], lo = gamma and hi = thres are the log-variance bounds (lo < hi).  For c < od + 1:
+ *                          lv1 = hi - softplus(hi - raw_c), lv_c = lo + softplus(lv1 - lo), raw_c = y[od + 2 + c],
+ *                          softplus(x) = max(x, 0) + log1p(exp(-|x|));
+ *                          dy[c]          = 2 (y_c - x0_c) exp(-lv_c) scale
+ *                          dy[od + 1]     = 2 (y - x0) scale                                  (the cost column: MSE)
+ *                          dy[od + 2 + c] = (1 - (y_c - x0_c)^2 exp(-lv_c)) sigmoid(hi - raw_c) sigmoid(lv1 - lo) scale
+ *                          stat = stat_scale sum_{nets, r} [ sum_{c < od + 1} ((y_c - x0_c)^2 exp(-lv_c) + lv_c) + (y_{od+1} - x0_{od+1})^2 ]
  * partials: >= 2 * n_nets * ceil(rows / 16) floats of scratch; counter: one uint32, ZERO before the first launch
  * (re-armed by the launch).  HOST struct. */
 enum { OSRL_SEED_NONE = 0, OSRL_SEED_MSE = 1, OSRL_SEED_CPQ_CRITIC = 2, OSRL_SEED_CPQ_COST = 3, OSRL_SEED_CPQ_ACTOR = 4,
-       OSRL_SEED_GAUSS_HEAD = 5, OSRL_SEED_BCQ_CRITIC = 6, OSRL_SEED_FQE = 7 };
+       OSRL_SEED_GAUSS_HEAD = 5, OSRL_SEED_BCQ_CRITIC = 6, OSRL_SEED_FQE = 7, OSRL_SEED_GAUSS_NLL = 8 };
 typedef struct {
   int32_t kind;
   int32_t n_a, n_b;
@@ -1408,6 +1417,33 @@ int osrl_model_env_step(const osrl_model_env_t* env, const float* act, float* st
 int osrl_model_env_collect(const osrl_model_env_t* env, const osrl_collect_t* rec, const float* act, float* state,
                            float* obs, int32_t obs_ld, float* acc, float* unc,
                            float* row_unc /* optional [E * episode_len] */, int32_t episodes, void* stream);
+/* The same two launches on an ensemble of diagonal Gaussians (algorithms/dynamics.py, probabilistic=True): member m's
+ * output row is (od + 1 means | raw cost | od + 1 raw log-variances), 2 od + 3 <= OSRL_MODEL_ENV_MAX_WIDTH columns; the
+ * first od + 2 are read exactly as osrl_model_env_step reads them.  With P = od + 1 and, for k < P,
+ *   lv_m[k] = lo + softplus((hi - softplus(hi - raw_m[k])) - lo),  raw_m[k] = y_m[od + 2 + k],  sg_m[k] = exp(0.5 lv_m[k]):
+ *   d = osrl_model_env_step's disagreement over the MEANS, the same expression;
+ *   a = max_m sqrt(sum_{k < od} sg_m[k]^2 / od)               (MOPO's largest predicted standard deviation)
+ *   u = d (uncertainty == OSRL_MODEL_ENV_UNC_DISAGREEMENT) | a (OSRL_MODEL_ENV_UNC_MAX_STD): u takes d's place in the
+ *       reward penalty, in unc[e] and in row_unc;
+ *   sample != 0:  v[k] = sg_f[k]^2 of the followed member f (MEMBER, RANDOM) | (sg_0[k]^2 + sg_1[k]^2 + ..) * (1 / n_models)
+ *       (MEAN);  yh[k] = fmaf(sqrt(v[k]), eps[k], yh[k]) for k < P, before s' and r are formed (the cost is never sampled);
+ *       eps[k] = noise_in[e * P + k] when noise_in is given (the same at every step), else the standard normal
+ *       osrl_rng's normal_word(Philox4x32-10(counter {episode_base + e, the episode's own step, k >> 2, 16}, key *seed), k & 3):
+ *       a function of (seed, episode id, step, column) alone.  sample == 0: neither is read.
+ * With sample == 0 and uncertainty == DISAGREEMENT the step has the bits of osrl_model_env_step on the members' first
+ * od + 2 output columns. */
+enum { OSRL_MODEL_ENV_UNC_DISAGREEMENT = 0, OSRL_MODEL_ENV_UNC_MAX_STD = 1 };
+typedef struct {
+  osrl_model_env_t env;   /* net[m].dims[n_layers] == 2 * state_dim + 3; seed is read when sample != 0 without noise_in too */
+  const float* noise_in;  /* [episodes, state_dim + 1] or NULL */
+  float logvar_min, logvar_max;
+  int32_t sample, uncertainty;
+} osrl_model_env_gauss_t;
+int osrl_model_env_step_gauss(const osrl_model_env_gauss_t* env, const float* act, float* state, float* obs,
+                              int32_t obs_ld, float* acc, float* unc, float* step_out, int32_t episodes, void* stream);
+int osrl_model_env_collect_gauss(const osrl_model_env_gauss_t* env, const osrl_collect_t* rec, const float* act,
+                                 float* state, float* obs, int32_t obs_ld, float* acc, float* unc, float* row_unc,
+                                 int32_t episodes, void* stream);
 /* Branch starts: episode e starts at row idx_e of `table` ([n_rows, state_dim], a store's observations),
  *   idx_e = umul64hi(words (x, y) of Philox4x32-10(counter {episode_base + e, 0, 0, 15}, key *seed), n)
  * (the replay gather's uniform draw; a function of (seed, episode id) alone), n = *n_rows_dev when given (a store's live

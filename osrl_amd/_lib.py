@@ -72,6 +72,7 @@ class SeedT(C.Structure):  # osrl_mlp_seed_t
 
 SEED_NONE, SEED_MSE, SEED_CPQ_CRITIC, SEED_CPQ_COST, SEED_CPQ_ACTOR, SEED_GAUSS_HEAD, SEED_BCQ_CRITIC = 0, 1, 2, 3, 4, 5, 6
 SEED_FQE = 7
+SEED_GAUSS_NLL = 8
 
 
 class VaeNsT(C.Structure):  # osrl_vae_ns_t
@@ -187,6 +188,24 @@ class ModelEnvT(C.Structure):  # osrl_model_env_t
         [(n, C.c_int32) for n in ("n_models", "state_dim", "action_dim", "episode_len", "mode", "member")] + \
         [("episode_base", C.c_uint32), ("pad_", C.c_int32), ("max_action", C.c_float), ("cost_scale", C.c_float),
          ("reward_penalty", C.c_float), ("pad2_", C.c_float)]
+
+
+MODEL_ENV_UNC = {"disagreement": 0, "max_std": 1}  # OSRL_MODEL_ENV_UNC_*
+
+
+class ModelEnvGaussT(C.Structure):  # osrl_model_env_gauss_t
+    _fields_ = [("env", ModelEnvT), ("noise_in", C.c_void_p), ("logvar_min", C.c_float), ("logvar_max", C.c_float),
+                ("sample", C.c_int32), ("uncertainty", C.c_int32)]
+
+    @property
+    def episode_len(self) -> int:  # (the rollouts set the horizon on whichever descriptor the environment hands out)
+        return self.env.episode_len
+
+    @episode_len.setter
+    def episode_len(self, v: int) -> None:
+        self.env.episode_len = v
+
+
 POLICY_MAX_ROWS = 4
 POLICY_MAX_ENVS = 64  # OSRL_POLICY_MAX_ENVS
 CDT_POLICY_MAX_ENVS = 64  # OSRL_CDT_POLICY_MAX_ENVS
@@ -223,6 +242,8 @@ PROTOTYPES = {
     "osrl_env_step": [_P(EnvT), _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp],
     "osrl_model_env_step": [_P(ModelEnvT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
     "osrl_model_env_collect": [_P(ModelEnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
+    "osrl_model_env_step_gauss": [_P(ModelEnvGaussT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
+    "osrl_model_env_collect_gauss": [_P(ModelEnvGaussT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
     "osrl_model_env_branch": [_vp, _i64, _vp, _i64, _i32, _vp, _u32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
     "osrl_dyn_prepare": [_vp] * 10 + [_i32, _i32, _vp, _vp, _vp],
     "osrl_env_collect": [_P(EnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _i32, _vp],

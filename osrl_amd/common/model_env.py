@@ -30,11 +30,19 @@ class ModelVecEnv(DeviceVecEnv):
     ``base_seed + e`` and the episode's own step).  ``reward_penalty`` lambda: ``r -= lambda * disagreement`` (MOPO).
     ``clip_states``: next states are clamped to the model's ``s_lo`` / ``s_hi``.  ``seed`` lives in device memory and
     may be set between runs; ``mode``, ``member`` and ``reward_penalty`` are launch arguments: changing them moves
-    ``launch_epoch``, on which a rollout drops its captured graph."""
+    ``launch_epoch``, on which a rollout drops its captured graph.
+
+    On a ``Dynamics(probabilistic=True)`` the step is ``osrl_model_env_step_gauss``.  ``sample``: the next state and the
+    reward are drawn from the followed member's Gaussian (mode "mean": the mean of the members' variances), the noise a
+    function of (``seed``, episode id, step, column) -- Philox stream 16 -- or ``set_noise_in``'s.  ``uncertainty``:
+    "disagreement" (the spread of the means) or "max_std", MOPO's ``max_m sqrt(mean_k sigma_m[k]^2)``; the one in use is
+    what ``reward_penalty`` weighs and what ``unc`` / ``disagreement()`` report.  Both are launch arguments too; on a
+    deterministic model either raises a ``ValueError``.  With the defaults such a model steps bit for bit like a
+    deterministic one that holds its members' first ``od + 2`` output rows."""
 
     def __init__(self, model, init_states, episodes: int, episode_len: int, max_action: float = 1.0, base_seed: int = 0,
                  mode: str = "mean", member: int = 0, reward_penalty: float = 0.0, clip_states: bool = True,
-                 seed: int = 0):
+                 seed: int = 0, sample: bool = False, uncertainty: str = "disagreement"):
         import torch
 
         from .. import _lib as L
@@ -59,11 +67,15 @@ class ModelVecEnv(DeviceVecEnv):
         self.extra_state = (self.unc,)  # what a step changes beside state / acc (BatchedRollout._snapshot)
         self._seed = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.member_in = None  # int32 [E] on the device: injected member choices of mode "random" (tests)
+        self.noise_in = None  # float32 [E, od + 1] on the device: injected draws of ``sample`` (tests)
         self.launch_epoch = 0
         self._mode, self._member, self._penalty = "mean", 0, 0.0
+        self._sample, self._uncertainty = False, "disagreement"
         self.seed = seed
         self.set_mode(mode, member)
         self.reward_penalty = reward_penalty
+        self.sample = sample
+        self.uncertainty = uncertainty
         model.repack()
 
     def _init_rows(self, init_states):
@@ -113,6 +125,57 @@ class ModelVecEnv(DeviceVecEnv):
             self._penalty = float(v)
             self.launch_epoch += 1
 
+    def _needs_gauss(self, what: str) -> None:
+        if not getattr(self.model, "probabilistic", False):
+            raise ValueError(f"{what} reads the members' predicted variance: build the Dynamics with probabilistic=True")
+
+    @property
+    def sample(self) -> bool:
+        return self._sample
+
+    @sample.setter
+    def sample(self, v: bool) -> None:
+        if bool(v):
+            self._needs_gauss("sample=True")
+        if bool(v) != self._sample:
+            self._sample = bool(v)
+            self.launch_epoch += 1
+
+    @property
+    def uncertainty(self) -> str:
+        return self._uncertainty
+
+    @uncertainty.setter
+    def uncertainty(self, v: str) -> None:
+        from .. import _lib as L
+        if v not in L.MODEL_ENV_UNC:
+            raise ValueError(f"uncertainty {v!r}: one of {sorted(L.MODEL_ENV_UNC)}")
+        if v != "disagreement":
+            self._needs_gauss(f"uncertainty={v!r}")
+        if v != self._uncertainty:
+            self._uncertainty = v
+            self.launch_epoch += 1
+
+    def set_noise_in(self, eps) -> None:
+        """Inject ``sample``'s draws: ``[E, od + 1]`` standard-normal values, one per episode and sampled column (the state
+        delta's and the reward's), the same at every step (None: draw them from ``seed``, Philox stream 16)."""
+        import torch
+        had = self.noise_in is not None
+        if eps is None:
+            self.noise_in = None
+        else:
+            self._needs_gauss("noise_in")
+            t = torch.as_tensor(np.asarray(eps.cpu() if torch.is_tensor(eps) else eps, np.float32)).to(self.device)
+            if tuple(t.shape) != (self.E, self.state_dim + 1):
+                raise ValueError(f"noise_in: [{self.E}, {self.state_dim + 1}] values, got {tuple(t.shape)}")
+            t = t.contiguous()
+            if had:
+                self.noise_in.copy_(t)
+            else:
+                self.noise_in = t
+        if had != (self.noise_in is not None):
+            self.launch_epoch += 1
+
     def set_member_in(self, members) -> None:
         """Inject mode "random"'s choices: one member index per episode, the same at every step (None: draw them)."""
         import torch
@@ -147,6 +210,13 @@ class ModelVecEnv(DeviceVecEnv):
         d.n_models, d.state_dim, d.action_dim, d.episode_len = m.num_models, self.state_dim, self.action_dim, int(episode_len)
         d.mode, d.member, d.episode_base = L.MODEL_ENV_MODES[self._mode], self._member, self.base_seed & 0xFFFFFFFF
         d.max_action, d.cost_scale, d.reward_penalty = self.max_action, float(cost_scale), self._penalty
+        if getattr(m, "probabilistic", False):  # osrl_model_env_gauss_t: the same descriptor, embedded
+            g = L.ModelEnvGaussT()
+            g.env = d
+            g.noise_in = None if self.noise_in is None else self.noise_in.data_ptr()
+            g.logvar_min, g.logvar_max = float(m.logvar_min.item()), float(m.logvar_max.item())
+            g.sample, g.uncertainty = int(self._sample), L.MODEL_ENV_UNC[self._uncertainty]
+            d = g
         d.launch_epoch = self.launch_epoch
         return d
 
@@ -163,13 +233,14 @@ class ModelVecEnv(DeviceVecEnv):
 
         from .. import _lib as L
         from ..engine.core import cur_stream
-        L.check(L.load().osrl_model_env_step(C.byref(desc), actions.data_ptr(), self.state.data_ptr(), obs_out.data_ptr(),
-                                             obs_out.stride(0), self.acc.data_ptr(), self.unc.data_ptr(),
-                                             None if step_out is None else step_out.data_ptr(), self.E, cur_stream()),
-                "osrl_model_env_step")
+        name = "osrl_model_env_step_gauss" if isinstance(desc, L.ModelEnvGaussT) else "osrl_model_env_step"
+        L.check(getattr(L.load(), name)(C.byref(desc), actions.data_ptr(), self.state.data_ptr(), obs_out.data_ptr(),
+                                        obs_out.stride(0), self.acc.data_ptr(), self.unc.data_ptr(),
+                                        None if step_out is None else step_out.data_ptr(), self.E, cur_stream()), name)
 
     def disagreement(self):
-        """Per episode ``(max, mean over the steps taken)`` of the members' disagreement (normalised units), two numpy
-        arrays.  Synchronises."""
+        """Per episode ``(max, mean over the steps taken)`` of the uncertainty signal in use (normalised units), two numpy
+        arrays: the members' disagreement over their means, or with ``uncertainty="max_std"`` the largest predicted
+        standard deviation.  Synchronises."""
         u, n = self.unc.cpu().numpy().astype(np.float64), self.acc[:, 2].cpu().numpy().astype(np.float64)
         return u[:, 0], u[:, 1] / np.maximum(n, 1.0)

@@ -769,6 +769,9 @@ __device__ __forceinline__ float seed_kl_elem(float mean, float ls_raw) {
   const float sd = expf(fminf(fmaxf(ls_raw, kTailLsMin), kTailLsMax));
   return -0.5f * (1.0f + logf(sd * sd) - mean * mean - sd * sd);
 }
+// OSRL_SEED_GAUSS_NLL's bounded log-variance (PETS' soft clamp): softplus(x) = max(x, 0) + log1p(exp(-|x|)) and its slope
+__device__ __forceinline__ float seed_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float seed_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 // element (r, c) of net e's dY; yv = that element of the net's output, yrow = the output row; l0 collects the
 // statistic's terms of valid elements
 template <class SR>
@@ -835,6 +838,26 @@ __device__ __forceinline__ float seed_dy(SR s, const int e, const int r, const i
     const float d = yv - backup;
     if (ok) l0 += d * d;  // (the caller moves a cost net's sum to the second partial)
     return 2.0f * d * s.scale;
+  }
+  if (kind == OSRL_SEED_GAUSS_NLL) {  // NL = 2 od + 3: (od + 1 means | cost | od + 1 raw log-variances); x0 [rows, od + 2]
+    const int no = (NL + 1) >> 1;     // od + 2: the target's width and the first log-variance column
+    if (c == no - 1) {                // the raw cost: MSE
+      const float d = yv - s.x0[(size_t)r * no + c];
+      if (ok) l0 += d * d;
+      return 2.0f * d * s.scale;
+    }
+    const int k = c < no ? c : c - no;
+    const float lo = s.gamma, hi = s.thres;  // the log-variance bounds
+    const float raw = yrow[no + k];
+    const float lv1 = hi - seed_softplus(hi - raw);
+    const float lv = lo + seed_softplus(lv1 - lo);
+    const float d = yrow[k] - s.x0[(size_t)r * no + k];
+    const float iv = expf(-lv);
+    if (c < no) {
+      if (ok) l0 += d * d * iv + lv;
+      return 2.0f * d * iv * s.scale;
+    }
+    return (1.0f - d * d * iv) * seed_sigmoid(hi - raw) * seed_sigmoid(lv1 - lo) * s.scale;
   }
   // OSRL_SEED_GAUSS_HEAD: yrow = (mu | log_std) of the row, NL = 2 ad
   const int ad = NL >> 1;
@@ -2556,6 +2579,8 @@ static bool seed_ok(const osrl_mlp_seed_t* s, const osrl_mlp_t* net, const osrl_
     case OSRL_SEED_FQE:
       return NL == 1 && s->a && s->b && s->x0 && s->x1 && s->n_a >= 1 && s->n_a <= kSeedEns && s->n_b >= 1 && s->n_b <= kSeedEns &&
              s->n_a + s->n_b == net->n_nets && s->kl_head == nullptr;
+    case OSRL_SEED_GAUSS_NLL:
+      return (NL & 1) == 1 && NL >= 5 && s->x0 && s->gamma < s->thres && s->kl_head == nullptr;
     case OSRL_SEED_GAUSS_HEAD:
       return (NL & 1) == 0 && net->n_nets == 1 && s->a && s->eps && s->tanh_u && s->n_a >= 1 && s->n_a <= kSeedEns && !s->partials;
     default: return false;

@@ -20,6 +20,15 @@
 // while it is live, and with kRecord live means e < episodes AND rollout_step.h's live_step: its rule keeps every write
 // inside the tables.
 //
+// A second compile-time flag, kGauss (osrl_model_env_step_gauss / osrl_model_env_collect_gauss: model_env_gauss_kernel,
+// model_rec_gauss_kernel and their twins), reads members that are diagonal Gaussians -- (od + 1 means | cost | od + 1 raw
+// log-variances), the first od + 2 columns exactly as before.  Right after a member's last layer the row's 32 threads turn
+// its raw log-variances into sigma^2 (PETS' soft clamp), add them into or copy them to ONE extra LDS tile (the mean
+// variance or the followed member's) and reduce sum_{k < od} sigma^2 into a running maximum: no per-member variance is
+// kept in registers.  The epilogue draws yh[k] += sqrt(v[k]) eps[k] (Philox stream 16, keyed by seed, episode id, the
+// episode's own step and the column, or injected) and uses max_m rms(sigma_m) in the disagreement's place when asked to.
+// With the flag off nothing of this exists: the four kernels above keep their listing.
+//
 // model_branch_kernel (osrl_model_env_branch) starts every episode at a row drawn uniformly from a store's observations.
 #include "argmem.h"
 #include "policy_common.h"
@@ -58,6 +67,36 @@ struct RecArgs {
   float* row_unc;
 };
 struct NoRec {};
+
+// what the Gaussian step adds to either descriptor (osrl_model_env_gauss_t beyond its osrl_model_env_t)
+struct GaussArgs {
+  const float* noise_in;
+  float lo, hi;
+  int32_t sample, unc;
+};
+struct GStepArgs {
+  StepArgs s;
+  GaussArgs g;
+};
+struct GRecArgs {
+  RecArgs r;
+  GaussArgs g;
+};
+struct NoGauss {};
+constexpr uint32_t kGaussStream = 16;  // Philox stream of the sampled next state and reward
+
+// (Gaussian step) beside Lds: 132 KB + 16.3 KB of the 160 KB
+struct LdsGauss {
+  float v[kTile * kYS];  // sigma^2 per row and column k < od + 1: the members' sum (MEAN) or the followed member's
+  int step[kTile];       // the episode's own step: the noise is keyed by it
+};
+
+// PETS' soft clamp of a raw log-variance to (lo, hi); softplus(x) = max(x, 0) + log1p(exp(-|x|))
+__device__ __forceinline__ float softplus_abs(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float bounded_logvar(float raw, float lo, float hi) {
+  const float lv1 = hi - softplus_abs(hi - raw);
+  return lo + softplus_abs(lv1 - lo);
+}
 
 struct Lds {
   __attribute__((aligned(16))) float xin[kTile * kS];     // the staged input rows: every member's layer 0 reads them
@@ -130,8 +169,9 @@ __device__ __forceinline__ void mfma_layer(const float* __restrict__ PF, const f
 
 // AR = how the descriptor is reached: `const StepArgs&` (the kernarg segment) or `const OSRL_CAS StepArgs&` (argmem.h).
 // kRecord: the step is recorded; RR reaches the RecArgs the same way (NoRec otherwise).
-template <bool kRecord, class AR, class RR>
-__device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l) {
+// kGauss: the members are diagonal Gaussians (osrl_model_env_gauss_t); GR reaches the GaussArgs, lg is the extra LDS.
+template <bool kRecord, class AR, class RR, bool kGauss = false, class GR = NoGauss>
+__device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l, GR g = GR{}, LdsGauss* lg = nullptr) {
   const int tid = threadIdx.x;
   const int od = a.d.state_dim, ad = a.d.action_dim, M = a.d.n_models, no = od + 2;
   const int e0 = blockIdx.x * kTile;  // the tile's first episode
@@ -162,6 +202,7 @@ __device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l) {
     }
     l.live[tid] = lv;
     l.jsel[tid] = js;
+    if constexpr (kGauss) lg->step[tid] = kRecord ? st : (lv ? (int)a.acc[(size_t)e * 4 + 2] : 0);
   }
   __syncthreads();
   const bool alive = l.live[r] != 0;
@@ -196,6 +237,7 @@ __device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l) {
   __syncthreads();
   // ---- the members, in order (the loop is unrolled: yk is indexed by constants and stays in registers)
   float yk[OSRL_MAX_NETS][kKeep];
+  float amax = 0.f;  // (Gaussian) max over the members so far of sqrt(mean_{k < od} sigma^2): no per-member variance is kept
 #pragma unroll
   for (int m = 0; m < OSRL_MAX_NETS; ++m) {
 #pragma unroll
@@ -214,6 +256,23 @@ __device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l) {
       for (int q = 0; q < kKeep; ++q) {
         const int k = j + kRowThreads * q;
         if (k < od) yk[m][q] = x[r * kS + k];
+      }
+      if constexpr (kGauss) {  // sigma^2 of columns j, j + 32, .. < od + 1 of this thread's row (element (r, k) is its own)
+        const int js = l.jsel[r];
+        float p = 0.f;
+        for (int k = j; k <= od; k += kRowThreads) {
+          const float sg = expf(0.5f * bounded_logvar(x[r * kS + no + k], g.lo, g.hi));
+          const float v2 = sg * sg;
+          if (k < od) p += v2;
+          float* vp = lg->v + r * kYS + k;
+          if (a.d.mode == OSRL_MODEL_ENV_MEAN)
+            *vp = m == 0 ? v2 : *vp + v2;
+          else if (js == m)
+            *vp = v2;
+        }
+#pragma unroll
+        for (int o = kRowThreads / 2; o >= 1; o >>= 1) p += __shfl_xor(p, o);
+        amax = fmaxf(amax, sqrtf(p / (float)od));
       }
       for (int i = tid; i < kTile * no; i += kThreads) {  // (element i is this thread's for every member)
         const int rr = i / no, c = i - rr * no;
@@ -255,11 +314,32 @@ __device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l) {
   const bool clamp = a.d.s_lo != nullptr && a.d.s_hi != nullptr;
   size_t row = 0;  // (recording) the live row's: inside the tables by live_step's rule
   if constexpr (kRecord) row = (size_t)ep * a.d.episode_len + l.step[r];
+  // (Gaussian) the signal in use, and column k's draw: mean + sqrt(v) eps, v the followed member's variance or the mean of all
+  float u = d;
+  if constexpr (kGauss) u = g.unc == OSRL_MODEL_ENV_UNC_MAX_STD ? amax : d;
+  auto drawn = [&](int k, float mean) {
+    if constexpr (kGauss) {
+      if (g.sample) {
+        float v = lg->v[r * kYS + k];
+        if (a.d.mode == OSRL_MODEL_ENV_MEAN) v *= inv_m;
+        uint32_t k0 = 0, k1 = 0;
+        if (!g.noise_in) {
+          const uint64_t seed = *a.d.seed;
+          k0 = (uint32_t)seed;
+          k1 = (uint32_t)(seed >> 32);
+        }
+        const float eps = osrl_rollout::explore_eps(a.d.episode_base + (uint32_t)ep, (uint32_t)lg->step[r], k, k0, k1,
+                                                    g.noise_in, (size_t)ep * (od + 1) + k, kGaussStream);
+        return fmaf(sqrtf(v), eps, mean);
+      }
+    }
+    return mean;
+  };
 #pragma unroll
   for (int q = 0; q < kKeep; ++q) {
     const int k = j + kRowThreads * q;
     if (k < od) {
-      float sn = sreg[q] + fmaf(a.d.sd_d[k], yh[k], a.d.mu_d[k]);
+      float sn = sreg[q] + fmaf(a.d.sd_d[k], drawn(k, yh[k]), a.d.mu_d[k]);
       if (clamp) sn = fminf(fmaxf(sn, a.d.s_lo[k]), a.d.s_hi[k]);
       a.state[(size_t)ep * od + k] = sn;
       a.obs[(size_t)ep * a.obs_ld + k] = sn;
@@ -273,16 +353,16 @@ __device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l) {
     for (int c = j; c < ad; c += kRowThreads) rc.c.actions[row * ad + c] = l.xin[r * kS + od + c];
   }
   if (j == 0) {
-    float rew = fmaf(a.d.sd_r[0], yh[od], a.d.mu_r[0]);
-    if (a.d.reward_penalty != 0.f) rew -= a.d.reward_penalty * d;
+    float rew = fmaf(a.d.sd_r[0], drawn(od, yh[od]), a.d.mu_r[0]);
+    if (a.d.reward_penalty != 0.f) rew -= a.d.reward_penalty * u;
     const float cost = yh[od + 1] > 0.5f ? 1.f : 0.f;
     const bool last = osrl_rollout::tick(a.acc + (size_t)ep * 4, rew, cost, a.d.cost_scale, a.d.episode_len,
                                          a.step_out ? a.step_out + (size_t)ep * 2 : nullptr);
     float* un = a.unc + (size_t)ep * 2;
-    un[0] = fmaxf(un[0], d);
-    un[1] += d;
+    un[0] = fmaxf(un[0], u);
+    un[1] += u;
     if constexpr (kRecord) {
-      if (rc.row_unc) rc.row_unc[row] = d;
+      if (rc.row_unc) rc.row_unc[row] = u;
       osrl_rollout::record(rc.c, row, ep, rew, cost, a.d.cost_scale, last);
     }
   }
@@ -308,6 +388,32 @@ __global__ __launch_bounds__(kThreads) void model_rec_kernel_p(const void* p) {
   const OSRL_CAS RecArgs& a = *(const OSRL_CAS RecArgs*)p;
   model_env_body<true, const OSRL_CAS StepArgs&, const OSRL_CAS RecArgs&>(a.s, a, l);
 }
+
+// the Gaussian step and recording step (osrl_model_env_step_gauss / _collect_gauss), each with its descriptor-pointer twin
+__global__ __launch_bounds__(kThreads) void model_env_gauss_kernel(const GStepArgs a) {
+  __shared__ Lds l;
+  __shared__ LdsGauss lg;
+  model_env_body<false, const StepArgs&, NoRec, true, const GaussArgs&>(a.s, NoRec{}, l, a.g, &lg);
+}
+__global__ __launch_bounds__(kThreads) void model_env_gauss_kernel_p(const void* p) {
+  __shared__ Lds l;
+  __shared__ LdsGauss lg;
+  const OSRL_CAS GStepArgs& a = *(const OSRL_CAS GStepArgs*)p;
+  model_env_body<false, const OSRL_CAS StepArgs&, NoRec, true, const OSRL_CAS GaussArgs&>(a.s, NoRec{}, l, a.g, &lg);
+}
+__global__ __launch_bounds__(kThreads) void model_rec_gauss_kernel(const GRecArgs a) {
+  __shared__ Lds l;
+  __shared__ LdsGauss lg;
+  model_env_body<true, const StepArgs&, const RecArgs&, true, const GaussArgs&>(a.r.s, a.r, l, a.g, &lg);
+}
+__global__ __launch_bounds__(kThreads) void model_rec_gauss_kernel_p(const void* p) {
+  __shared__ Lds l;
+  __shared__ LdsGauss lg;
+  const OSRL_CAS GRecArgs& a = *(const OSRL_CAS GRecArgs*)p;
+  model_env_body<true, const OSRL_CAS StepArgs&, const OSRL_CAS RecArgs&, true, const OSRL_CAS GaussArgs&>(a.r.s, a.r, l,
+                                                                                                         a.g, &lg);
+}
+static_assert(sizeof(Lds) + sizeof(LdsGauss) <= 160 * 1024, "model_env_gauss_kernel: LDS per workgroup");
 
 struct BranchArgs {
   const float* table;         // [n_rows, od]
@@ -381,7 +487,7 @@ bool valid_member(const osrl_gemv_net_t& n, int in, int out) {
 
 // the step's descriptor, checked (false: a bad argument)
 bool fill_step(StepArgs& a, const osrl_model_env_t* env, const float* act, float* state, float* obs, int32_t obs_ld,
-               float* acc, float* unc, float* step_out, int32_t episodes) {
+               float* acc, float* unc, float* step_out, int32_t episodes, bool gauss = false) {
   if (!env || !act || !state || !obs || !acc || !unc || episodes < 1) return false;
   const osrl_model_env_t& d = *env;
   if (d.n_models < 1 || d.n_models > OSRL_MAX_NETS || d.state_dim < 1 || d.state_dim > OSRL_MODEL_ENV_MAX_STATE ||
@@ -392,7 +498,7 @@ bool fill_step(StepArgs& a, const osrl_model_env_t* env, const float* act, float
   if (d.mode == OSRL_MODEL_ENV_MEMBER && (d.member < 0 || d.member >= d.n_models)) return false;
   if (d.mode == OSRL_MODEL_ENV_RANDOM && !d.seed && !d.member_in) return false;
   for (int m = 0; m < d.n_models; ++m)
-    if (!valid_member(d.net[m], d.state_dim + d.action_dim, d.state_dim + 2)) return false;
+    if (!valid_member(d.net[m], d.state_dim + d.action_dim, gauss ? 2 * d.state_dim + 3 : d.state_dim + 2)) return false;
   memset(&a, 0, sizeof a);  // (the arena finds a block by its bytes: no stray padding)
   a.d = d;
   for (int m = d.n_models; m < OSRL_MAX_NETS; ++m) memset(&a.d.net[m], 0, sizeof a.d.net[m]);
@@ -433,6 +539,48 @@ extern "C" int osrl_model_env_collect(const osrl_model_env_t* env, const osrl_co
   const int tiles = (episodes + kTile - 1) / kTile;
   return osrl_argmem::launch(model_rec_kernel, model_rec_kernel_p, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream,
                              a);
+}
+
+namespace {
+// the Gaussian additions, checked (false: a bad argument)
+bool fill_gauss(GaussArgs& g, const osrl_model_env_gauss_t* env) {
+  if (!env || !(env->logvar_min < env->logvar_max)) return false;
+  if (env->uncertainty != OSRL_MODEL_ENV_UNC_DISAGREEMENT && env->uncertainty != OSRL_MODEL_ENV_UNC_MAX_STD) return false;
+  if (env->sample && !env->noise_in && !env->env.seed) return false;
+  g.noise_in = env->sample ? env->noise_in : nullptr;
+  g.lo = env->logvar_min;
+  g.hi = env->logvar_max;
+  g.sample = env->sample ? 1 : 0;
+  g.unc = env->uncertainty;
+  return true;
+}
+}  // namespace
+
+extern "C" int osrl_model_env_step_gauss(const osrl_model_env_gauss_t* env, const float* act, float* state, float* obs,
+                                         int32_t obs_ld, float* acc, float* unc, float* step_out, int32_t episodes,
+                                         void* stream) {
+  GStepArgs a;
+  memset(&a, 0, sizeof a);
+  if (!env || !fill_step(a.s, &env->env, act, state, obs, obs_ld, acc, unc, step_out, episodes, true)) return -1;
+  if (!fill_gauss(a.g, env)) return -1;
+  const int tiles = (episodes + kTile - 1) / kTile;
+  return osrl_argmem::launch(model_env_gauss_kernel, model_env_gauss_kernel_p, dim3(tiles), dim3(kThreads), 0,
+                             (hipStream_t)stream, a);
+}
+
+extern "C" int osrl_model_env_collect_gauss(const osrl_model_env_gauss_t* env, const osrl_collect_t* rec,
+                                            const float* act, float* state, float* obs, int32_t obs_ld, float* acc,
+                                            float* unc, float* row_unc, int32_t episodes, void* stream) {
+  if (!osrl_rollout::valid_collect(rec) || !env || env->env.episode_len < 1) return -1;
+  GRecArgs a;
+  memset(&a, 0, sizeof a);
+  if (!fill_step(a.r.s, &env->env, act, state, obs, obs_ld, acc, unc, nullptr, episodes, true)) return -1;
+  if (!fill_gauss(a.g, env)) return -1;
+  a.r.c = *rec;
+  a.r.row_unc = row_unc;
+  const int tiles = (episodes + kTile - 1) / kTile;
+  return osrl_argmem::launch(model_rec_gauss_kernel, model_rec_gauss_kernel_p, dim3(tiles), dim3(kThreads), 0,
+                             (hipStream_t)stream, a);
 }
 
 extern "C" int osrl_model_env_branch(const float* table, int64_t n_rows, const int64_t* n_rows_dev, int64_t n_limit,

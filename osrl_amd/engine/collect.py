@@ -294,10 +294,11 @@ class ModelCollector(_Tables, BatchedRollout):
         import ctypes as C
         act = self.policy()
         v = self.venv
-        L.check(L.load().osrl_model_env_collect(C.byref(self.env_c), self._rec_now(), act.data_ptr(), v.state.data_ptr(),
-                                                self.obs.data_ptr(), self.obs.stride(0), v.acc.data_ptr(),
-                                                v.unc.data_ptr(), self.row_disagreement.data_ptr(), v.E, cur_stream()),
-                "osrl_model_env_collect")
+        # (a probabilistic model's descriptor: the sampled next state and the penalised reward are what is recorded)
+        name = "osrl_model_env_collect_gauss" if isinstance(self.env_c, L.ModelEnvGaussT) else "osrl_model_env_collect"
+        L.check(getattr(L.load(), name)(C.byref(self.env_c), self._rec_now(), act.data_ptr(), v.state.data_ptr(),
+                                        self.obs.data_ptr(), self.obs.stride(0), v.acc.data_ptr(), v.unc.data_ptr(),
+                                        self.row_disagreement.data_ptr(), v.E, cur_stream()), name)
 
     def _snapshot(self):  # (venv.unc is the environment's extra_state: the base class has it)
         return super()._snapshot() + [(self.disc, self.disc.clone())]

@@ -9,6 +9,14 @@ One chain on one stream, one one-step hipGraph:  prologue -> ``osrl_dyn_prepare`
 model's normaliser tables) -> the members' forward on a shared input tile -> the backward launch that computes its own dY
 (``OSRL_SEED_MSE``: every net of the launch against the one target table) -> dW + Adam.  The tables are read from the
 model's buffers in place: ``fit_normalizer`` between two replays is followed.
+
+A ``probabilistic`` model (members ``[.., 2 od + 3]``: means, cost, raw log-variances) is fitted by the Gaussian negative
+log-likelihood instead: the same chain and the same target table, the backward launch seeded with ``OSRL_SEED_GAUSS_NLL``.
+With ``s = 1 / (B (od + 2))`` and ``lv`` the bounded log-variance (algorithms/dynamics.py),
+
+    loss = sum_m s sum_rows [ sum_{c <= od} ((mu_c - t_c)^2 exp(-lv_c) + lv_c) + (y_cost - t_cost)^2 ]
+
+logged under the same key, ``loss/dynamics_loss``.
 """
 from __future__ import annotations
 
@@ -41,10 +49,10 @@ class DynamicsEngine(StepEngine):
         self.xs, self.target = z(B, od), z(B, od + 2)
         m.repack()
         self.r_f = MlpRun(net_desc_seq(list(m.members), 1.0), B, True, dev)
-        self.dy = z(E, B, od + 2)
+        self.dy = z(E, B, m.out_width)
         self.r_f.setup_backward(self.dy)
         self.plan = DwPlan(m.groups["dynamics"], self.r_f.dw_entries(), B, dev)
-        self.seed_mse = self._seed_mse(dev)
+        self.seed_mse = self._seed_nll(dev) if m.probabilistic else self._seed_mse(dev)
         self._plans_built()
 
     def _seed_mse(self, dev) -> "L.SeedT":
@@ -56,6 +64,15 @@ class DynamicsEngine(StepEngine):
         s.x0 = self.target.data_ptr()
         s.scale = s.stat_scale = float(np.float32(1.0) / np.float32(self.B * (self.model.state_dim + 2)))
         s._keep += [self.target]
+        return s
+
+    def _seed_nll(self, dev) -> "L.SeedT":
+        """``OSRL_SEED_GAUSS_NLL`` (include/osrl_amd.h): the members' Gaussian negative log-likelihood against the same
+        target table, the cost column by MSE; the statistic is the loss of the module docstring.  The log-variance
+        bounds are by-value arguments of the launch, read from the model's buffers when the engine is built."""
+        s = self._seed_mse(dev)
+        s.kind = L.SEED_GAUSS_NLL
+        s.gamma, s.thres = float(self.model.logvar_min.item()), float(self.model.logvar_max.item())
         return s
 
     def attach_replay(self, store) -> None:

@@ -8,10 +8,23 @@
 (c) the return / cost gap between the two environments, same policy, same initial states, for a model fitted (``--fit-steps``
     steps, batch 256) on data ``collect``ed from the synthetic one -- with the model's own trust signal, ``disagreement()``.
 
-Nothing is gated.  Writes profiles/model_env_bench.json (``--out``)."""
+Nothing is gated.  Writes profiles/model_env_bench.json (``--out``).
+
+``--probabilistic [--parent DIR]`` measures the Gaussian ensemble (``Dynamics(probabilistic=True)``) instead and writes
+profiles/model_env_gauss_bench.json.  Every run is a child process; runs alternate A B B A on one device; medians:
+
+(a) the untouched paths against a built checkout of the parent commit (``--parent DIR``; skipped without it): the
+    deterministic model's ``evaluate`` and ``collect_model(horizon=5)`` at (76, 2), 5 x [200, 200, 200], 1024 episodes.
+    ``ratio`` = parent median / this tree's median (below 1: this tree is slower); ``parent_spread`` = max / min of the
+    parent's own repeats; ``ok``: the ratio is not below 1 / parent_spread.
+(b) ``bench.py --gpus 1 --steps 20 --warmup 5`` (its timed region: ``--no-cpu-baseline --no-roofline --no-extras``) of
+    both trees, 'value' in grad-steps/s, the same rule -- csrc/mlp.hip gained a loss seed that this step does not take.
+(c) reported, not gated: the Gaussian path against the deterministic one in this tree -- ``evaluate``,
+    ``collect_model(horizon=5)``, sampled and not, and the NLL fit step against the MSE fit step at batch 256."""
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -46,13 +59,13 @@ def abba(a, b, rounds):
     return summary(ta), summary(tb)
 
 
-def fit_model(od, ad, data, steps, dev, seed=0):
+def fit_model(od, ad, data, steps, dev, seed=0, **model_kw):
     import torch
     from osrl_amd.algorithms import Dynamics, DynamicsTrainer
     from osrl_amd.common.replay import ReplayStore
     store = ReplayStore(data, dev, seed=seed, state_init=True)
     torch.manual_seed(seed)
-    dyn = Dynamics(od, ad, [200, 200, 200], num_models=5, device=str(dev))
+    dyn = Dynamics(od, ad, [200, 200, 200], num_models=5, device=str(dev), **model_kw)
     dyn.fit_normalizer(store)
     DynamicsTrainer(dyn, lr=1e-3, stats_mode="none")
     eng = dyn.engine(256)
@@ -119,12 +132,146 @@ def cdt_part(dev, rounds, fit_steps):
                 synthetic_env=dict(zip(("return", "cost", "length"), map(float, res_r))))
 
 
+# ---- --probabilistic ------------------------------------------------------------------------------------------------
+GAUSS_SHAPE = dict(od=76, ad=2, policy_hidden=[256, 256], members=5, model_hidden=[200, 200, 200], episodes=1024,
+                   episode_len=EL, horizon=5, fit_batch=256)
+BENCH_CMD = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-roofline", "--no-extras"]
+
+
+def _setup(dev, fit_steps, **model_kw):
+    """A CPQ policy, data collected from the synthetic environment, a model fitted on it and a trainer on the model."""
+    import torch
+    from osrl_amd.algorithms import CPQ, CPQTrainer
+    from osrl_amd.common.model_env import ModelVecEnv
+    from osrl_amd.common.synthetic_env import SyntheticSafeEnv, VecSyntheticSafeEnv
+    s = GAUSS_SHAPE
+    torch.manual_seed(0)
+    cpq = CPQ(s["od"], s["ad"], 1.0, s["policy_hidden"], s["policy_hidden"], 400, 10, episode_len=EL, device=str(dev))
+    host = SyntheticSafeEnv(s["od"], s["ad"], EL, seed=3, init_noise=0.5)
+    data = CPQTrainer(cpq, env=VecSyntheticSafeEnv(host, 256, dev), stats_mode="none").collect(noise_std=0.3, seed=1).dataset
+    dyn, fit = fit_model(s["od"], s["ad"], data, fit_steps, dev, **model_kw)
+    menv = ModelVecEnv(dyn, VecSyntheticSafeEnv(host, s["episodes"], dev).state0, s["episodes"], EL)
+    return CPQTrainer(cpq, env=menv, stats_mode="none"), menv, dyn, fit, data
+
+
+def gauss_worker(tree, what, reps, fit_steps):
+    """Runs in a child process with ``tree`` first on the path: ms per call, every repeat."""
+    sys.path.insert(0, tree)
+    import torch
+    dev = torch.device("cuda", 0)
+    E, H = GAUSS_SHAPE["episodes"], GAUSS_SHAPE["horizon"]
+    one = lambda f: timed(f)[0]  # noqa: E731
+    out = {}
+    if what == "untouched":  # only what the parent commit has too
+        tr, menv, _, _, _ = _setup(dev, 50)
+        tr.evaluate(E)
+        tr.collect_model(menv, horizon=H, noise_std=0.3, seed=0)
+        out["evaluate_ms"] = [one(lambda: tr.evaluate(E)) for _ in range(reps)]
+        out["collect_model_ms"] = [one(lambda: tr.collect_model(menv, horizon=H, noise_std=0.3, seed=1)) for _ in range(reps)]
+    else:
+        arms = {}
+        for name, kw in (("deterministic", {}), ("gaussian", dict(probabilistic=True))):
+            tr, menv, dyn, fit, data = _setup(dev, fit_steps, **kw)
+            arms[name] = (tr, menv, dyn.engine(GAUSS_SHAPE["fit_batch"]))
+            out[name + "_fit"] = fit
+        det, gau = arms["deterministic"], arms["gaussian"]
+        gau_s = _setup(dev, 50, probabilistic=True)
+        gau_s[1].sample, gau_s[1].uncertainty = True, "max_std"
+        calls = dict(
+            evaluate_ms=lambda a: a[0].evaluate(E),
+            collect_model_ms=lambda a: a[0].collect_model(a[1], horizon=H, noise_std=0.3, seed=1),
+            fit_step_ms=lambda a: [a[2].step_replay() for _ in range(100)])
+        for key, fn in calls.items():
+            sides = dict(deterministic=det, gaussian=gau, gaussian_sampled_max_std=gau_s)
+            if key == "fit_step_ms":
+                del sides["gaussian_sampled_max_std"]
+            for a in sides.values():
+                fn(a)  # (warm: capture)
+            ms = {k: [] for k in sides}
+            for _ in range(reps):  # A B B A over the sides
+                for k in list(sides) + list(sides)[::-1]:
+                    ms[k].append(one(lambda: fn(sides[k])) / (100 if key == "fit_step_ms" else 1))
+            out[key] = ms
+    print("RESULT " + json.dumps(out))
+
+
+def gauss_child(tree, what, reps, fit_steps):
+    cmd = [sys.executable, os.path.abspath(__file__), "--worker", what, "--tree", tree, "--reps", str(reps),
+           "--fit-steps", str(fit_steps)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=tree)
+    if r.returncode != 0:
+        raise RuntimeError(f"worker {what} failed in {tree}: {r.stderr[-2000:]}")
+    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+
+
+def bench_child(tree):
+    """'value' of one ``bench.py`` process of ``tree`` (its own library, its own bench.py)."""
+    r = subprocess.run([sys.executable] + BENCH_CMD, capture_output=True, text=True, timeout=900, cwd=tree)
+    if r.returncode != 0:
+        raise RuntimeError(f"bench.py failed in {tree}: {r.stderr[-2000:]}")
+    rows = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{") and '"value"' in ln]
+    return float(rows[-1]["value"])
+
+
+def gate(here, there, higher_is_better=False):
+    """this tree's repeats against the parent's: ratio > 1 = this tree is faster; ok = not slower than the parent's own
+    max / min spread allows."""
+    h, t = summary(here), summary(there)
+    ratio = h["median"] / t["median"] if higher_is_better else t["median"] / h["median"]
+    spread = t["max"] / t["min"]
+    return dict(this_tree=h, parent=t, ratio=round(ratio, 4), parent_spread=round(spread, 4), ok=bool(ratio >= 1.0 / spread))
+
+
+def gauss_main(args):
+    out = dict(shape=GAUSS_SHAPE, untouched_vs_parent=None, bench_vs_parent=None)
+    if args.parent:
+        parent = os.path.abspath(args.parent)
+        here, there = {}, {}
+        bh, bt = [], []
+        for _ in range(args.rounds):  # A B B A
+            for tree, dst, bd in ((ROOT, here, bh), (parent, there, bt), (parent, there, bt), (ROOT, here, bh)):
+                for k, v in gauss_child(tree, "untouched", args.reps, 50).items():
+                    dst.setdefault(k, []).extend(v)
+                bd.append(bench_child(tree))
+                print(f"{'this tree' if tree == ROOT else 'parent'}: bench {bd[-1]}", file=sys.stderr, flush=True)
+        out["untouched_vs_parent"] = {k: gate(here[k], there[k]) for k in here}
+        out["bench_vs_parent"] = dict(command="python " + " ".join(BENCH_CMD), unit="grad-steps/s",
+                                      **gate(bh, bt, higher_is_better=True))
+    g = gauss_child(ROOT, "gauss", args.reps, args.fit_steps)
+    rep = {k: g[k] for k in ("deterministic_fit", "gaussian_fit")}
+    for key in ("evaluate_ms", "collect_model_ms", "fit_step_ms"):
+        sides = {k: summary(v) for k, v in g[key].items()}
+        rep[key] = dict(sides, ratio_to_deterministic={k: round(v["median"] / sides["deterministic"]["median"], 4)
+                                                       for k, v in sides.items() if k != "deterministic"})
+    out["gaussian_vs_deterministic"] = rep
+    import torch  # (after the children: this process never opens the device before them)
+    out["device"] = torch.cuda.get_device_name(0)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "model_env_bench.json"))
-    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--rounds", type=int, default=None, help="A B B A rounds (default 3; 2 with --probabilistic)")
     ap.add_argument("--fit-steps", type=int, default=2000)
+    ap.add_argument("--probabilistic", action="store_true", help="the Gaussian ensemble's A/B (see the module docstring)")
+    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit (--probabilistic, parts a and b)")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--worker", default=None, choices=["untouched", "gauss"])
+    ap.add_argument("--tree", default=ROOT)
     args = ap.parse_args()
+    name = "model_env_gauss_bench.json" if args.probabilistic else "model_env_bench.json"
+    args.out = args.out or os.path.join(ROOT, "profiles", name)
+    if args.worker:
+        return gauss_worker(os.path.abspath(args.tree), args.worker, args.reps, args.fit_steps)
+    if args.probabilistic:
+        args.rounds = args.rounds or 2
+        return gauss_main(args)
+    args.rounds = args.rounds or 3
     sys.path.insert(0, ROOT)
     import torch
     dev = torch.device("cuda", 0)
