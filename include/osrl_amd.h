@@ -1444,6 +1444,45 @@ int osrl_model_env_step_gauss(const osrl_model_env_gauss_t* env, const float* ac
 int osrl_model_env_collect_gauss(const osrl_model_env_gauss_t* env, const osrl_collect_t* rec, const float* act,
                                  float* state, float* obs, int32_t obs_ld, float* acc, float* unc, float* row_unc,
                                  int32_t episodes, void* stream);
+/* The same four launches, pessimistic (model_env.hip, compile-time flag kPess): a rollout halts where the model stops
+ * knowing, and the cost is inflated by the uncertainty.  u is the signal in use (d, or a under UNC_MAX_STD), c = yh[od + 1].
+ * Per live episode e at its own step t, where the plain step forms reward and cost:
+ *   cost = (cost_penalty != 0 ? fmaf(cost_penalty, u, c) : c) > 0.5 ? 1 : 0;
+ *   halt = u > halt_threshold   (strict: +inf never halts, a NaN u does not halt);  on halt:
+ *     r = halt_reward (it replaces the model's reward, penalty included: what acc[e][0] and the discounted sum add and
+ *     what the table records), cost = halt_cost (0 or 1), the done latch acc[e][3] is set after the step is counted --
+ *     the episode is finished for every later launch -- and halt_step[e] = t (left untouched otherwise; may be NULL);
+ *     a recorded halting row has terminals = 1 and timeouts = 0, also when t + 1 == episode_len.
+ *   The next state is written on a halting step too (state, obs, next_observations); unc[e] and row_unc include its u;
+ *   sampling is unaffected.  No arithmetic of the members, the mean or the disagreement differs: with
+ *   halt_threshold = +inf and cost_penalty = 0 every output has the bits of the entry point without "_halt".
+ * -1 for a NaN threshold or reward, a halt_cost other than 0 / 1, a negative or non-finite cost_penalty. */
+typedef struct {
+  float halt_threshold, halt_reward, halt_cost, cost_penalty;
+  int32_t* halt_step; /* [episodes] or NULL */
+} osrl_model_env_pess_t;
+int osrl_model_env_step_halt(const osrl_model_env_t* env, const osrl_model_env_pess_t* pess, const float* act,
+                             float* state, float* obs, int32_t obs_ld, float* acc, float* unc, float* step_out,
+                             int32_t episodes, void* stream);
+int osrl_model_env_collect_halt(const osrl_model_env_t* env, const osrl_model_env_pess_t* pess,
+                                const osrl_collect_t* rec, const float* act, float* state, float* obs, int32_t obs_ld,
+                                float* acc, float* unc, float* row_unc, int32_t episodes, void* stream);
+int osrl_model_env_step_gauss_halt(const osrl_model_env_gauss_t* env, const osrl_model_env_pess_t* pess,
+                                   const float* act, float* state, float* obs, int32_t obs_ld, float* acc, float* unc,
+                                   float* step_out, int32_t episodes, void* stream);
+int osrl_model_env_collect_gauss_halt(const osrl_model_env_gauss_t* env, const osrl_model_env_pess_t* pess,
+                                      const osrl_collect_t* rec, const float* act, float* state, float* obs,
+                                      int32_t obs_ld, float* acc, float* unc, float* row_unc, int32_t episodes,
+                                      void* stream);
+/* Variable-length recorded rollouts made dense (compact.hip).  src / dst: the seven DSRL tables of an osrl_collect_t, whose
+ * other fields are not read, episode-major with pitch episode_len in src; row_unc optional, given for both or neither.
+ * len_e = (int)acc[e][2] clamped to [0, episode_len];  offsets[e] = sum_{i < e} len_i (int64 [episodes + 1], device
+ * memory; offsets[episodes] = the total);  dst row offsets[e] + t = src row e * episode_len + t for t < len_e, bit for
+ * bit.  Rows at and beyond offsets[episodes] of dst are not written; dst tables of episodes * episode_len rows always
+ * suffice.  Out of place (src != dst).  Two launches: a one-workgroup scan, then one span per episode and table. */
+int osrl_collect_compact(const osrl_collect_t* src, const float* src_row_unc, const osrl_collect_t* dst,
+                         float* dst_row_unc, const float* acc, int64_t* offsets, int32_t episodes, int32_t episode_len,
+                         int32_t state_dim, int32_t action_dim, void* stream);
 /* Branch starts: episode e starts at row idx_e of `table` ([n_rows, state_dim], a store's observations),
  *   idx_e = umul64hi(words (x, y) of Philox4x32-10(counter {episode_base + e, 0, 0, 15}, key *seed), n)
  * (the replay gather's uniform draw; a function of (seed, episode id) alone), n = *n_rows_dev when given (a store's live

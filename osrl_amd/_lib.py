@@ -206,6 +206,39 @@ class ModelEnvGaussT(C.Structure):  # osrl_model_env_gauss_t
         self.env.episode_len = v
 
 
+class ModelEnvPessT(C.Structure):  # osrl_model_env_pess_t
+    _fields_ = [("halt_threshold", C.c_float), ("halt_reward", C.c_float), ("halt_cost", C.c_float),
+                ("cost_penalty", C.c_float), ("halt_step", C.c_void_p)]
+
+
+class _HaltDesc:
+    """What ``ModelVecEnv.desc`` hands out when halting or the cost penalty is on: the plain descriptor (``env``) and the
+    ``osrl_model_env_pess_t`` beside it -- the two pointer arguments of the ``_halt`` entry points."""
+    env_type = None
+
+    def __init__(self, env, pess: ModelEnvPessT):
+        assert isinstance(env, self.env_type)
+        self.env, self.pess = env, pess
+
+    @property
+    def episode_len(self) -> int:
+        return self.env.episode_len
+
+    @episode_len.setter
+    def episode_len(self, v: int) -> None:
+        self.env.episode_len = v
+
+
+class ModelEnvHaltT(_HaltDesc):
+    env_type = ModelEnvT
+    step_fn, collect_fn = "osrl_model_env_step_halt", "osrl_model_env_collect_halt"
+
+
+class ModelEnvGaussHaltT(_HaltDesc):
+    env_type = ModelEnvGaussT
+    step_fn, collect_fn = "osrl_model_env_step_gauss_halt", "osrl_model_env_collect_gauss_halt"
+
+
 POLICY_MAX_ROWS = 4
 POLICY_MAX_ENVS = 64  # OSRL_POLICY_MAX_ENVS
 CDT_POLICY_MAX_ENVS = 64  # OSRL_CDT_POLICY_MAX_ENVS
@@ -244,6 +277,14 @@ PROTOTYPES = {
     "osrl_model_env_collect": [_P(ModelEnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
     "osrl_model_env_step_gauss": [_P(ModelEnvGaussT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
     "osrl_model_env_collect_gauss": [_P(ModelEnvGaussT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
+    "osrl_model_env_step_halt": [_P(ModelEnvT), _P(ModelEnvPessT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
+    "osrl_model_env_collect_halt": [_P(ModelEnvT), _P(ModelEnvPessT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                    _i32, _vp],
+    "osrl_model_env_step_gauss_halt": [_P(ModelEnvGaussT), _P(ModelEnvPessT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32,
+                                       _vp],
+    "osrl_model_env_collect_gauss_halt": [_P(ModelEnvGaussT), _P(ModelEnvPessT), _P(CollectT), _vp, _vp, _vp, _i32, _vp,
+                                          _vp, _vp, _i32, _vp],
+    "osrl_collect_compact": [_P(CollectT), _vp, _P(CollectT), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "osrl_model_env_branch": [_vp, _i64, _vp, _i64, _i32, _vp, _u32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
     "osrl_dyn_prepare": [_vp] * 10 + [_i32, _i32, _vp, _vp, _vp],
     "osrl_env_collect": [_P(EnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _i32, _vp],

@@ -160,7 +160,10 @@ class RolloutMixin:
         with ``sample_prob`` (a scalar or ``[E * horizon]``: the new rows' weights, handed to ``append``), a
         ``state_init`` store is refused with ``start=store`` (a branch start is not an initial state).  ValueError
         before anything runs.  ``self.model_collector(menv)`` is the cached collector: its ``start_rows`` and
-        ``row_disagreement`` are device tensors of the last run."""
+        ``row_disagreement`` are device tensors of the last run.
+        On a ``menv`` with a ``halt_threshold`` an episode ends where the model's uncertainty exceeds it: the result
+        holds ``sum(lengths)`` rows, dense and episode-major, a halting row has ``terminals`` 1 and ``timeouts`` 0,
+        ``sample_prob`` is a scalar, and the collector's ``row_offsets`` (``[E + 1]``) says where each episode starts."""
         co = self.model_collector(menv)
         self._before_evaluate()
         return co.run(horizon=horizon, start=start, noise_std=noise_std, gamma=gamma, seed=seed, noise=noise, into=into,

@@ -15,6 +15,9 @@ initial states or from rows of a store, with the penalised reward.
 """
 from __future__ import annotations
 
+import math
+from typing import Optional
+
 import numpy as np
 
 from .synthetic_env import DeviceVecEnv
@@ -38,11 +41,20 @@ class ModelVecEnv(DeviceVecEnv):
     "disagreement" (the spread of the means) or "max_std", MOPO's ``max_m sqrt(mean_k sigma_m[k]^2)``; the one in use is
     what ``reward_penalty`` weighs and what ``unc`` / ``disagreement()`` report.  Both are launch arguments too; on a
     deterministic model either raises a ``ValueError``.  With the defaults such a model steps bit for bit like a
-    deterministic one that holds its members' first ``od + 2`` output rows."""
+    deterministic one that holds its members' first ``od + 2`` output rows.
+
+    Pessimism beyond the reward (the ``_halt`` entry points; DESIGN.md "Halting on uncertainty").  ``halt_threshold``
+    (None: never): where the signal in use exceeds it the episode ends at that step -- MOReL's absorbing "unknown" -- with
+    ``halt_reward`` in the reward's place and ``halt_cost`` (0 or 1) as the cost; ``halt_step`` (int32 ``[E]`` on the
+    device, -1: not halted; ``halted()``) keeps the step.  ``cost_penalty`` kappa: the cost bit is
+    ``c + kappa * u > 0.5`` (CAP's inflation).  All four are launch arguments.  With the defaults ``desc()`` hands out the
+    plain descriptors and the plain entry points run."""
 
     def __init__(self, model, init_states, episodes: int, episode_len: int, max_action: float = 1.0, base_seed: int = 0,
                  mode: str = "mean", member: int = 0, reward_penalty: float = 0.0, clip_states: bool = True,
-                 seed: int = 0, sample: bool = False, uncertainty: str = "disagreement"):
+                 seed: int = 0, sample: bool = False, uncertainty: str = "disagreement",
+                 halt_threshold: Optional[float] = None, halt_reward: float = 0.0, halt_cost: float = 1.0,
+                 cost_penalty: float = 0.0):
         import torch
 
         from .. import _lib as L
@@ -64,18 +76,22 @@ class ModelVecEnv(DeviceVecEnv):
         self.state = torch.zeros(self.E, self.state_dim, **f)
         self.acc = torch.zeros(self.E, 4, **f)
         self.unc = torch.zeros(self.E, 2, **f)
-        self.extra_state = (self.unc,)  # what a step changes beside state / acc (BatchedRollout._snapshot)
+        self.halt_step = torch.full((self.E,), -1, dtype=torch.int32, device=self.device)
+        self.extra_state = (self.unc, self.halt_step)  # what a step changes beside state / acc (BatchedRollout._snapshot)
         self._seed = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.member_in = None  # int32 [E] on the device: injected member choices of mode "random" (tests)
         self.noise_in = None  # float32 [E, od + 1] on the device: injected draws of ``sample`` (tests)
         self.launch_epoch = 0
         self._mode, self._member, self._penalty = "mean", 0, 0.0
         self._sample, self._uncertainty = False, "disagreement"
+        self._halt_thr, self._halt_reward, self._halt_cost, self._cost_penalty = None, 0.0, 1.0, 0.0
         self.seed = seed
         self.set_mode(mode, member)
         self.reward_penalty = reward_penalty
         self.sample = sample
         self.uncertainty = uncertainty
+        self.halt_threshold, self.halt_reward, self.halt_cost = halt_threshold, halt_reward, halt_cost
+        self.cost_penalty = cost_penalty
         model.repack()
 
     def _init_rows(self, init_states):
@@ -156,6 +172,67 @@ class ModelVecEnv(DeviceVecEnv):
             self._uncertainty = v
             self.launch_epoch += 1
 
+    # ---- halting and the pessimistic cost (launch arguments) -----------------------------------------------------------
+    @property
+    def halt_threshold(self) -> Optional[float]:
+        return self._halt_thr
+
+    @halt_threshold.setter
+    def halt_threshold(self, v: Optional[float]) -> None:
+        v = None if v is None else float(v)
+        if v is not None and math.isnan(v):
+            raise ValueError("halt_threshold is NaN: a number (u > threshold halts) or None")
+        if v != self._halt_thr:
+            if v is None:  # nothing writes halt_step from here on: reset() and the branch starts leave it alone
+                self.halt_step.fill_(-1)
+            self._halt_thr = v
+            self.launch_epoch += 1
+
+    @property
+    def can_halt(self) -> bool:
+        """Whether a step may end an episode early: recorded rollouts are then variable-length."""
+        return self._halt_thr is not None
+
+    @property
+    def halt_reward(self) -> float:
+        return self._halt_reward
+
+    @halt_reward.setter
+    def halt_reward(self, v: float) -> None:
+        if math.isnan(float(v)):
+            raise ValueError("halt_reward is NaN")
+        if float(v) != self._halt_reward:
+            self._halt_reward = float(v)
+            self.launch_epoch += 1
+
+    @property
+    def halt_cost(self) -> float:
+        return self._halt_cost
+
+    @halt_cost.setter
+    def halt_cost(self, v: float) -> None:
+        if float(v) not in (0.0, 1.0):
+            raise ValueError(f"halt_cost {v}: the raw cost of a halting step, 0 or 1")
+        if float(v) != self._halt_cost:
+            self._halt_cost = float(v)
+            self.launch_epoch += 1
+
+    @property
+    def cost_penalty(self) -> float:
+        return self._cost_penalty
+
+    @cost_penalty.setter
+    def cost_penalty(self, v: float) -> None:
+        if not 0.0 <= float(v) < math.inf:
+            raise ValueError(f"cost_penalty {v}: a finite value >= 0")
+        if float(v) != self._cost_penalty:
+            self._cost_penalty = float(v)
+            self.launch_epoch += 1
+
+    def halted(self) -> np.ndarray:
+        """Per episode the step at which it halted, -1 where it did not (int32 numpy).  Synchronises."""
+        return self.halt_step.cpu().numpy()
+
     def set_noise_in(self, eps) -> None:
         """Inject ``sample``'s draws: ``[E, od + 1]`` standard-normal values, one per episode and sampled column (the state
         delta's and the reward's), the same at every step (None: draw them from ``seed``, Philox stream 16)."""
@@ -217,6 +294,12 @@ class ModelVecEnv(DeviceVecEnv):
             g.logvar_min, g.logvar_max = float(m.logvar_min.item()), float(m.logvar_max.item())
             g.sample, g.uncertainty = int(self._sample), L.MODEL_ENV_UNC[self._uncertainty]
             d = g
+        if self._halt_thr is not None or self._cost_penalty != 0.0:  # the same descriptor beside osrl_model_env_pess_t
+            p = L.ModelEnvPessT()
+            p.halt_threshold = math.inf if self._halt_thr is None else self._halt_thr
+            p.halt_reward, p.halt_cost, p.cost_penalty = self._halt_reward, self._halt_cost, self._cost_penalty
+            p.halt_step = self.halt_step.data_ptr()
+            d = (L.ModelEnvGaussHaltT if isinstance(d, L.ModelEnvGaussT) else L.ModelEnvHaltT)(d, p)
         d.launch_epoch = self.launch_epoch
         return d
 
@@ -226,6 +309,8 @@ class ModelVecEnv(DeviceVecEnv):
         obs_out[:, :self.state_dim].copy_(self.state0)
         self.acc.zero_()
         self.unc.zero_()
+        if self._halt_thr is not None:  # (otherwise it holds -1: nothing has written it since the threshold was None)
+            self.halt_step.fill_(-1)
 
     def step(self, desc, actions, obs_out, step_out=None) -> None:
         """``step_out`` (optional [E,2]) receives this step's (reward, raw cost)."""
@@ -233,8 +318,12 @@ class ModelVecEnv(DeviceVecEnv):
 
         from .. import _lib as L
         from ..engine.core import cur_stream
-        name = "osrl_model_env_step_gauss" if isinstance(desc, L.ModelEnvGaussT) else "osrl_model_env_step"
-        L.check(getattr(L.load(), name)(C.byref(desc), actions.data_ptr(), self.state.data_ptr(), obs_out.data_ptr(),
+        if isinstance(desc, L._HaltDesc):
+            name, head = desc.step_fn, (C.byref(desc.env), C.byref(desc.pess))
+        else:
+            name = "osrl_model_env_step_gauss" if isinstance(desc, L.ModelEnvGaussT) else "osrl_model_env_step"
+            head = (C.byref(desc),)
+        L.check(getattr(L.load(), name)(*head, actions.data_ptr(), self.state.data_ptr(), obs_out.data_ptr(),
                                         obs_out.stride(0), self.acc.data_ptr(), self.unc.data_ptr(),
                                         None if step_out is None else step_out.data_ptr(), self.E, cur_stream()), name)
 

@@ -29,6 +29,13 @@
 // episode's own step and the column, or injected) and uses max_m rms(sigma_m) in the disagreement's place when asked to.
 // With the flag off nothing of this exists: the four kernels above keep their listing.
 //
+// A third compile-time flag, kPess (osrl_model_env_step_halt / _collect_halt / _step_gauss_halt / _collect_gauss_halt:
+// halt_env_kernel, halt_rec_kernel, halt_env_gauss_kernel, halt_rec_gauss_kernel and their twins), makes the step
+// pessimistic where lane j == 0 of a row forms reward and cost: the cost threshold is applied to c + cost_penalty u
+// (CAP's inflation), and u > halt_threshold ends the episode with a fixed reward and cost (MOReL's absorbing "unknown"):
+// the done latch is set, halt_step[e] takes the step, a recorded row is terminal.  Nothing else moves; with the threshold
+// at +inf and the penalty 0 the eight kernels give the other eight's bits.  With the flag off nothing of this exists.
+//
 // model_branch_kernel (osrl_model_env_branch) starts every episode at a row drawn uniformly from a store's observations.
 #include "argmem.h"
 #include "policy_common.h"
@@ -83,6 +90,28 @@ struct GRecArgs {
   GaussArgs g;
 };
 struct NoGauss {};
+// what the pessimistic step adds to any of the four descriptors (osrl_model_env_pess_t, by value)
+struct PessArgs {
+  float halt_threshold, halt_reward, halt_cost, cost_penalty;
+  int32_t* halt_step;
+};
+struct HStepArgs {
+  StepArgs s;
+  PessArgs p;
+};
+struct HRecArgs {
+  RecArgs r;
+  PessArgs p;
+};
+struct HGStepArgs {
+  GStepArgs s;
+  PessArgs p;
+};
+struct HGRecArgs {
+  GRecArgs r;
+  PessArgs p;
+};
+struct NoPess {};
 constexpr uint32_t kGaussStream = 16;  // Philox stream of the sampled next state and reward
 
 // (Gaussian step) beside Lds: 132 KB + 16.3 KB of the 160 KB
@@ -170,8 +199,10 @@ __device__ __forceinline__ void mfma_layer(const float* __restrict__ PF, const f
 // AR = how the descriptor is reached: `const StepArgs&` (the kernarg segment) or `const OSRL_CAS StepArgs&` (argmem.h).
 // kRecord: the step is recorded; RR reaches the RecArgs the same way (NoRec otherwise).
 // kGauss: the members are diagonal Gaussians (osrl_model_env_gauss_t); GR reaches the GaussArgs, lg is the extra LDS.
-template <bool kRecord, class AR, class RR, bool kGauss = false, class GR = NoGauss>
-__device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l, GR g = GR{}, LdsGauss* lg = nullptr) {
+// kPess: the step halts where u > halt_threshold and inflates the cost by cost_penalty * u (osrl_model_env_pess_t); PR
+// reaches the PessArgs.  Only the row's lane j == 0 reads them.
+template <bool kRecord, class AR, class RR, bool kGauss = false, class GR = NoGauss, bool kPess = false, class PR = NoPess>
+__device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l, GR g = GR{}, LdsGauss* lg = nullptr, PR ps = PR{}) {
   const int tid = threadIdx.x;
   const int od = a.d.state_dim, ad = a.d.action_dim, M = a.d.n_models, no = od + 2;
   const int e0 = blockIdx.x * kTile;  // the tile's first episode
@@ -355,15 +386,39 @@ __device__ __forceinline__ void model_env_body(AR a, RR rc, Lds& l, GR g = GR{},
   if (j == 0) {
     float rew = fmaf(a.d.sd_r[0], drawn(od, yh[od]), a.d.mu_r[0]);
     if (a.d.reward_penalty != 0.f) rew -= a.d.reward_penalty * u;
-    const float cost = yh[od + 1] > 0.5f ? 1.f : 0.f;
+    float cost = yh[od + 1] > 0.5f ? 1.f : 0.f;
+    bool halt = false;
+    int t_halt = 0;
+    if constexpr (kPess) {  // the pessimistic cost, and "unknown" as an absorbing state with a fixed reward and cost
+      const float c = yh[od + 1];
+      cost = (ps.cost_penalty != 0.f ? fmaf(ps.cost_penalty, u, c) : c) > 0.5f ? 1.f : 0.f;
+      halt = u > ps.halt_threshold;  // (strict: +inf never halts, and neither does a NaN u)
+      if (halt) {
+        rew = ps.halt_reward;
+        cost = ps.halt_cost;
+        t_halt = (int)a.acc[(size_t)ep * 4 + 2];  // the episode's own step, before the tick
+      }
+    }
     const bool last = osrl_rollout::tick(a.acc + (size_t)ep * 4, rew, cost, a.d.cost_scale, a.d.episode_len,
                                          a.step_out ? a.step_out + (size_t)ep * 2 : nullptr);
+    if constexpr (kPess) {
+      if (halt) {  // the done latch: finished for every later launch, by live_step's rule
+        a.acc[(size_t)ep * 4 + 3] = 1.f;
+        if (ps.halt_step) ps.halt_step[ep] = t_halt;
+      }
+    }
     float* un = a.unc + (size_t)ep * 2;
     un[0] = fmaxf(un[0], u);
     un[1] += u;
     if constexpr (kRecord) {
       if (rc.row_unc) rc.row_unc[row] = u;
       osrl_rollout::record(rc.c, row, ep, rew, cost, a.d.cost_scale, last);
+      if constexpr (kPess) {
+        if (halt) {  // a terminal row, also at the episode's last step
+          rc.c.terminals[row] = 1.f;
+          rc.c.timeouts[row] = 0.f;
+        }
+      }
     }
   }
 }
@@ -414,6 +469,57 @@ __global__ __launch_bounds__(kThreads) void model_rec_gauss_kernel_p(const void*
                                                                                                          a.g, &lg);
 }
 static_assert(sizeof(Lds) + sizeof(LdsGauss) <= 160 * 1024, "model_env_gauss_kernel: LDS per workgroup");
+
+// the pessimistic step (osrl_model_env_step_halt / _collect_halt / _step_gauss_halt / _collect_gauss_halt): the four
+// kernels above with kPess on, each with its descriptor-pointer twin.  No LDS beside theirs.
+__global__ __launch_bounds__(kThreads) void halt_env_kernel(const HStepArgs a) {
+  __shared__ Lds l;
+  model_env_body<false, const StepArgs&, NoRec, false, NoGauss, true, const PessArgs&>(a.s, NoRec{}, l, NoGauss{}, nullptr,
+                                                                                     a.p);
+}
+__global__ __launch_bounds__(kThreads) void halt_env_kernel_p(const void* p) {
+  __shared__ Lds l;
+  const OSRL_CAS HStepArgs& a = *(const OSRL_CAS HStepArgs*)p;
+  model_env_body<false, const OSRL_CAS StepArgs&, NoRec, false, NoGauss, true, const OSRL_CAS PessArgs&>(
+      a.s, NoRec{}, l, NoGauss{}, nullptr, a.p);
+}
+__global__ __launch_bounds__(kThreads) void halt_rec_kernel(const HRecArgs a) {
+  __shared__ Lds l;
+  model_env_body<true, const StepArgs&, const RecArgs&, false, NoGauss, true, const PessArgs&>(a.r.s, a.r, l, NoGauss{},
+                                                                                             nullptr, a.p);
+}
+__global__ __launch_bounds__(kThreads) void halt_rec_kernel_p(const void* p) {
+  __shared__ Lds l;
+  const OSRL_CAS HRecArgs& a = *(const OSRL_CAS HRecArgs*)p;
+  model_env_body<true, const OSRL_CAS StepArgs&, const OSRL_CAS RecArgs&, false, NoGauss, true, const OSRL_CAS PessArgs&>(
+      a.r.s, a.r, l, NoGauss{}, nullptr, a.p);
+}
+__global__ __launch_bounds__(kThreads) void halt_env_gauss_kernel(const HGStepArgs a) {
+  __shared__ Lds l;
+  __shared__ LdsGauss lg;
+  model_env_body<false, const StepArgs&, NoRec, true, const GaussArgs&, true, const PessArgs&>(a.s.s, NoRec{}, l, a.s.g, &lg,
+                                                                                             a.p);
+}
+__global__ __launch_bounds__(kThreads) void halt_env_gauss_kernel_p(const void* p) {
+  __shared__ Lds l;
+  __shared__ LdsGauss lg;
+  const OSRL_CAS HGStepArgs& a = *(const OSRL_CAS HGStepArgs*)p;
+  model_env_body<false, const OSRL_CAS StepArgs&, NoRec, true, const OSRL_CAS GaussArgs&, true, const OSRL_CAS PessArgs&>(
+      a.s.s, NoRec{}, l, a.s.g, &lg, a.p);
+}
+__global__ __launch_bounds__(kThreads) void halt_rec_gauss_kernel(const HGRecArgs a) {
+  __shared__ Lds l;
+  __shared__ LdsGauss lg;
+  model_env_body<true, const StepArgs&, const RecArgs&, true, const GaussArgs&, true, const PessArgs&>(a.r.r.s, a.r.r, l,
+                                                                                                     a.r.g, &lg, a.p);
+}
+__global__ __launch_bounds__(kThreads) void halt_rec_gauss_kernel_p(const void* p) {
+  __shared__ Lds l;
+  __shared__ LdsGauss lg;
+  const OSRL_CAS HGRecArgs& a = *(const OSRL_CAS HGRecArgs*)p;
+  model_env_body<true, const OSRL_CAS StepArgs&, const OSRL_CAS RecArgs&, true, const OSRL_CAS GaussArgs&, true,
+                 const OSRL_CAS PessArgs&>(a.r.r.s, a.r.r, l, a.r.g, &lg, a.p);
+}
 
 struct BranchArgs {
   const float* table;         // [n_rows, od]
@@ -580,6 +686,73 @@ extern "C" int osrl_model_env_collect_gauss(const osrl_model_env_gauss_t* env, c
   a.r.row_unc = row_unc;
   const int tiles = (episodes + kTile - 1) / kTile;
   return osrl_argmem::launch(model_rec_gauss_kernel, model_rec_gauss_kernel_p, dim3(tiles), dim3(kThreads), 0,
+                             (hipStream_t)stream, a);
+}
+
+namespace {
+// the pessimistic additions, checked (false: a bad argument; +-inf thresholds are values like any other)
+bool fill_pess(PessArgs& p, const osrl_model_env_pess_t* ps) {
+  if (!ps || ps->halt_threshold != ps->halt_threshold || !(ps->halt_reward == ps->halt_reward)) return false;
+  if (ps->halt_cost != 0.f && ps->halt_cost != 1.f) return false;
+  if (!(ps->cost_penalty >= 0.f) || ps->cost_penalty > 3.0e38f) return false;
+  p.halt_threshold = ps->halt_threshold;
+  p.halt_reward = ps->halt_reward;
+  p.halt_cost = ps->halt_cost;
+  p.cost_penalty = ps->cost_penalty;
+  p.halt_step = ps->halt_step;
+  return true;
+}
+}  // namespace
+
+extern "C" int osrl_model_env_step_halt(const osrl_model_env_t* env, const osrl_model_env_pess_t* pess, const float* act,
+                                        float* state, float* obs, int32_t obs_ld, float* acc, float* unc,
+                                        float* step_out, int32_t episodes, void* stream) {
+  HStepArgs a;
+  memset(&a, 0, sizeof a);
+  if (!fill_step(a.s, env, act, state, obs, obs_ld, acc, unc, step_out, episodes) || !fill_pess(a.p, pess)) return -1;
+  const int tiles = (episodes + kTile - 1) / kTile;
+  return osrl_argmem::launch(halt_env_kernel, halt_env_kernel_p, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream, a);
+}
+
+extern "C" int osrl_model_env_collect_halt(const osrl_model_env_t* env, const osrl_model_env_pess_t* pess,
+                                           const osrl_collect_t* rec, const float* act, float* state, float* obs,
+                                           int32_t obs_ld, float* acc, float* unc, float* row_unc, int32_t episodes,
+                                           void* stream) {
+  if (!osrl_rollout::valid_collect(rec) || !env || env->episode_len < 1) return -1;
+  HRecArgs a;
+  memset(&a, 0, sizeof a);
+  if (!fill_step(a.r.s, env, act, state, obs, obs_ld, acc, unc, nullptr, episodes) || !fill_pess(a.p, pess)) return -1;
+  a.r.c = *rec;
+  a.r.row_unc = row_unc;
+  const int tiles = (episodes + kTile - 1) / kTile;
+  return osrl_argmem::launch(halt_rec_kernel, halt_rec_kernel_p, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream, a);
+}
+
+extern "C" int osrl_model_env_step_gauss_halt(const osrl_model_env_gauss_t* env, const osrl_model_env_pess_t* pess,
+                                              const float* act, float* state, float* obs, int32_t obs_ld, float* acc,
+                                              float* unc, float* step_out, int32_t episodes, void* stream) {
+  HGStepArgs a;
+  memset(&a, 0, sizeof a);
+  if (!env || !fill_step(a.s.s, &env->env, act, state, obs, obs_ld, acc, unc, step_out, episodes, true)) return -1;
+  if (!fill_gauss(a.s.g, env) || !fill_pess(a.p, pess)) return -1;
+  const int tiles = (episodes + kTile - 1) / kTile;
+  return osrl_argmem::launch(halt_env_gauss_kernel, halt_env_gauss_kernel_p, dim3(tiles), dim3(kThreads), 0,
+                             (hipStream_t)stream, a);
+}
+
+extern "C" int osrl_model_env_collect_gauss_halt(const osrl_model_env_gauss_t* env, const osrl_model_env_pess_t* pess,
+                                                 const osrl_collect_t* rec, const float* act, float* state, float* obs,
+                                                 int32_t obs_ld, float* acc, float* unc, float* row_unc,
+                                                 int32_t episodes, void* stream) {
+  if (!osrl_rollout::valid_collect(rec) || !env || env->env.episode_len < 1) return -1;
+  HGRecArgs a;
+  memset(&a, 0, sizeof a);
+  if (!fill_step(a.r.r.s, &env->env, act, state, obs, obs_ld, acc, unc, nullptr, episodes, true)) return -1;
+  if (!fill_gauss(a.r.g, env) || !fill_pess(a.p, pess)) return -1;
+  a.r.r.c = *rec;
+  a.r.r.row_unc = row_unc;
+  const int tiles = (episodes + kTile - 1) / kTile;
+  return osrl_argmem::launch(halt_rec_gauss_kernel, halt_rec_gauss_kernel_p, dim3(tiles), dim3(kThreads), 0,
                              (hipStream_t)stream, a);
 }
 

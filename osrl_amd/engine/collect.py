@@ -17,7 +17,8 @@ cursor, with per-episode targets and, with ``sample=True``, the Gaussian head's 
 ``ModelCollector`` is ``Collector`` on a learned model (``Trainer.collect_model``): the step ends in
 ``osrl_model_env_collect`` (csrc/model_env.hip), episodes start at the environment's initial states or at rows drawn on
 device from a store (``osrl_model_env_branch``, Philox stream 15), and run ``horizon`` steps -- MOPO's / MBPO's branched
-rollouts (DESIGN.md "Training on a learned model").
+rollouts (DESIGN.md "Training on a learned model").  On an environment with a ``halt_threshold`` an episode may end early:
+the run then compacts the tables on device (csrc/compact.hip ``osrl_collect_compact``) and hands out the live rows only.
 """
 from __future__ import annotations
 
@@ -38,7 +39,8 @@ KEYS = ("observations", "actions", "next_observations", "rewards", "costs", "ter
 
 class Collected(NamedTuple):
     """``dataset``: fresh device tensors under the seven DSRL keys, ``E * L`` rows, episode-major (row ``e * L + t``);
-    costs raw 0 / 1, ``terminals`` all 0, ``timeouts`` 1 on each episode's last row.  The per-episode sums are numpy
+    costs raw 0 / 1, ``terminals`` all 0, ``timeouts`` 1 on each episode's last row (``collect_model`` on an environment that
+    can halt: ``sum(lengths)`` rows, dense and episode-major, ``terminals`` 1 and ``timeouts`` 0 on a halting row).  The per-episode sums are numpy
     fp64 ``[E]``; the two cost sums carry the collector's ``cost_scale`` (as ``BatchedRollout.run``'s do), the discounted
     ones weigh step t by ``gamma ** t``.  ``dataset`` is None when the run appended its rows to a store (``into=``).
     From ``collect_jobs`` (host environments, engine/act.py): one entry per JOB, the rows job-major with each job's true
@@ -186,6 +188,17 @@ class _Tables:
         return Collected(data, tot[:, 0], tot[:, 1], tot[:, 2], tot[:, 4], tot[:, 5])
 
 
+class _DenseTables(_Tables):
+    """A second set of guarded tables as large as ``owner``'s, ``row_unc`` included: where ``osrl_collect_compact``
+    writes.  The descriptor's other words are the owner's; the compaction reads the seven tables only."""
+
+    def __init__(self, owner):
+        self.obs, self.venv, self.model = owner.obs, owner.venv, owner.model
+        self.disc, self.sigma, self.gamma, self.seed_dev = owner.disc, owner.sigma, owner.gamma, owner.seed_dev
+        self._alloc(owner._steps)
+        self._unc_buf, self._row_unc = owner._alloc_unc(owner._steps)
+
+
 class Collector(_Tables, BatchedRollout):
     """``run`` = all ``venv.E`` episodes to completion, recorded.  The tables are this object's (sized at the first run,
     again when the episode length changes); ``run`` hands out copies, or appends the tables to a store (``into=``)."""
@@ -223,13 +236,19 @@ class Collector(_Tables, BatchedRollout):
         return self._finish(into)
 
 
-def check_model_target(into, start, state_dim: int, action_dim: int, rows: int, sample_prob):
+def check_model_target(into, start, state_dim: int, action_dim: int, rows: int, sample_prob, halting: bool = False):
     """``collect_model``'s ``into=`` / ``sample_prob=`` / ``start=``, judged on the host before anything runs: the new
     rows' weights as a flat fp64 tensor (None on a uniform target).  ``_check_replay_store``'s width rules, except that a
     weighted store is taken WITH ``sample_prob`` (a scalar or ``[rows]``); ValueError for a weighted store without it, a
     uniform one (or no store) with it, a ``state_init`` target of branched rollouts (a branch start is not an initial
-    state: ``is_init`` and every FQE read-out would be wrong), and a ``start`` store of another observation width."""
+    state: ``is_init`` and every FQE read-out would be wrong), and a ``start`` store of another observation width.
+    ``halting``: the environment can end an episode early -- ``rows`` is then the worst case ``E * horizon``, and a per-row
+    ``sample_prob`` is refused: the number of rows is known only after the run."""
     from ..common.replay import _checked_weights
+    if halting and sample_prob is not None and \
+            (sample_prob.dim() if torch.is_tensor(sample_prob) else np.ndim(sample_prob)) != 0:
+        raise ValueError("collect_model(sample_prob=) on an environment that can halt: the number of rows is known only "
+                         "after the run, pass one value for all of them")
     if start is not None:
         if not hasattr(start, "tables") or not hasattr(start, "widths"):
             raise ValueError(f"start= takes a ReplayStore (or None: the environment's own initial states), not "
@@ -265,7 +284,12 @@ class ModelCollector(_Tables, BatchedRollout):
     from the environment's initial states or from rows of a store (``osrl_model_env_branch``: one launch, drawn on
     device from the store's live count) and records them with the penalised reward.  What comes out is a model's
     opinion.  ``start_rows`` (int64 ``[E]``, None without a start store) and ``row_disagreement`` (``[E * horizon]``, the
-    members' disagreement at each recorded row) are device tensors of the last run."""
+    members' disagreement at each recorded row) are device tensors of the last run.
+
+    On an environment that can halt (``venv.can_halt``) an episode may end before ``horizon``: the run then ends with
+    ``osrl_collect_compact`` (csrc/compact.hip) into a second set of guarded tables and reads the row count -- the one
+    extra host sync.  ``dataset`` / ``into=`` / ``row_disagreement`` hold the ``sum(len_e)`` live rows, episode-major and
+    dense; ``row_offsets`` (int64 ``[E + 1]`` on the device, None otherwise) says where each episode's rows start."""
 
     def __init__(self, model, venv, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None,
                  seed: int = 0, z: Optional[torch.Tensor] = None, use_graph: bool = True):
@@ -278,27 +302,76 @@ class ModelCollector(_Tables, BatchedRollout):
         self._starts = torch.zeros(venv.E, dtype=torch.int64, device=self.obs.device)
         self.start_rows: Optional[torch.Tensor] = None
         self.row_disagreement: Optional[torch.Tensor] = None
+        self.row_offsets: Optional[torch.Tensor] = None
+        self._offsets = torch.zeros(venv.E + 1, dtype=torch.int64, device=self.obs.device)
+        self._dense: Optional[_Tables] = None  # the compaction's destination: tables of the same size, guarded alike
 
     def _alloc(self, steps: int) -> None:
         super()._alloc(steps)
+        self._unc_buf, self._row_unc = self._alloc_unc(steps)
+        self.row_disagreement, self._dense = self._row_unc, None
+
+    def _alloc_unc(self, steps: int):
         n, g = self.venv.E * steps, _GUARD_ROWS
         buf = torch.full((n + 2 * g,), _SENTINEL, dtype=torch.int32, device=self.obs.device).view(torch.float32)
-        self._unc_buf, self.row_disagreement = buf, buf[g:g + n]
+        return buf, buf[g:g + n]
+
+    @staticmethod
+    def _unc_guards(buf) -> torch.Tensor:
+        i = buf.view(torch.int32)
+        return (i[:_GUARD_ROWS] == _SENTINEL).all() & (i[-_GUARD_ROWS:] == _SENTINEL).all()
 
     def guards_intact(self) -> bool:
-        i = self._unc_buf.view(torch.int32)
-        ok = (i[:_GUARD_ROWS] == _SENTINEL).all() & (i[-_GUARD_ROWS:] == _SENTINEL).all()
-        return super().guards_intact() and bool(ok.item())
+        ok = super().guards_intact() and bool(self._unc_guards(self._unc_buf).item())
+        if ok and self._dense is not None:
+            ok = self._dense.guards_intact() and bool(self._unc_guards(self._dense._unc_buf).item())
+        return ok
+
+    def _compact(self) -> int:
+        """The padded tables' live rows into the dense ones (allocated at the first halting run of this horizon):
+        ``osrl_collect_compact``, then the row count -- a host sync."""
+        v = self.venv
+        if self._dense is None:
+            self._dense = _DenseTables(self)
+        d = self._dense
+        L.check(L.load().osrl_collect_compact(self.rec, self._row_unc.data_ptr(), d.rec, d._row_unc.data_ptr(),
+                                              v.acc.data_ptr(), self._offsets.data_ptr(), v.E, self._steps, v.state_dim,
+                                              self.model.action_dim, cur_stream()), "osrl_collect_compact")
+        return int(self._offsets[v.E].item())
+
+    def _finish(self, into, sample_prob=None) -> Collected:
+        if not self.venv.can_halt:
+            self.row_disagreement, self.row_offsets = self._row_unc, None
+            return super()._finish(into, sample_prob)
+        n = self._compact()
+        tables = {k: t[:n] for k, t in self._dense.tables.items()}
+        self.row_disagreement, self.row_offsets = self._dense._row_unc[:n], self._offsets
+        if into is not None:
+            if n:
+                if sample_prob is None:
+                    into.append(tables)
+                else:  # (a scalar, spread over the worst case before the run: the live rows' share of it)
+                    into.append(tables, sample_prob=sample_prob[:n])
+            data = None
+        else:
+            data = {k: t.clone() for k, t in tables.items()}
+        tot = torch.cat([self.venv.acc, self.disc], 1).cpu().numpy().astype(np.float64)
+        return Collected(data, tot[:, 0], tot[:, 1], tot[:, 2], tot[:, 4], tot[:, 5])
 
     def body(self) -> None:
         import ctypes as C
         act = self.policy()
         v = self.venv
         # (a probabilistic model's descriptor: the sampled next state and the penalised reward are what is recorded)
-        name = "osrl_model_env_collect_gauss" if isinstance(self.env_c, L.ModelEnvGaussT) else "osrl_model_env_collect"
-        L.check(getattr(L.load(), name)(C.byref(self.env_c), self._rec_now(), act.data_ptr(), v.state.data_ptr(),
+        c = self.env_c
+        if isinstance(c, L._HaltDesc):  # halting / the pessimistic cost: the same descriptor beside osrl_model_env_pess_t
+            name, head = c.collect_fn, (C.byref(c.env), C.byref(c.pess))
+        else:
+            name = "osrl_model_env_collect_gauss" if isinstance(c, L.ModelEnvGaussT) else "osrl_model_env_collect"
+            head = (C.byref(c),)
+        L.check(getattr(L.load(), name)(*head, self._rec_now(), act.data_ptr(), v.state.data_ptr(),
                                         self.obs.data_ptr(), self.obs.stride(0), v.acc.data_ptr(), v.unc.data_ptr(),
-                                        self.row_disagreement.data_ptr(), v.E, cur_stream()), name)
+                                        self._row_unc.data_ptr(), v.E, cur_stream()), name)
 
     def _snapshot(self):  # (venv.unc is the environment's extra_state: the base class has it)
         return super()._snapshot() + [(self.disc, self.disc.clone())]
@@ -314,6 +387,8 @@ class ModelCollector(_Tables, BatchedRollout):
             int(getattr(store, "pinned_rows", 0)), v.state_dim, self.seed_dev.data_ptr(), v.base_seed & 0xFFFFFFFF,
             v.state.data_ptr(), self.obs.data_ptr(), self.obs.stride(0), v.acc.data_ptr(), v.unc.data_ptr(),
             self.disc.data_ptr(), self._starts.data_ptr(), v.E, cur_stream()), "osrl_model_env_branch")
+        if v.can_halt:  # (otherwise it holds -1 already: ModelVecEnv.reset's rule)
+            v.halt_step.fill_(-1)
         self.start_rows = self._starts
 
     @torch.no_grad()
@@ -324,12 +399,15 @@ class ModelCollector(_Tables, BatchedRollout):
         ``noise`` (``[horizon, E, action_dim]``) as ``Collector.run`` takes them; ``seed`` keys the branch starts too
         (Philox stream 15; the noise is stream 13).  ``into`` / ``sample_prob``: ``check_model_target``.  Every refusal
         comes before the first launch.  ``min(horizon, _CHUNK)`` steps per captured graph; the graph is dropped when the
-        horizon or a by-value argument of the environment (mode, member, penalty: ``launch_epoch``) changes."""
+        horizon or a by-value argument of the environment (mode, member, penalty: ``launch_epoch``) changes.  On an
+        environment that can halt the result holds the live rows only (the class docstring), ``into`` / ``sample_prob``
+        are still judged for the worst case ``E * horizon``, and ``sample_prob`` is a scalar: a per-row vector has no
+        rows to belong to before the lengths exist."""
         v = self.venv
         steps = int(v.episode_len if horizon is None else horizon)
         if steps < 1:
             raise ValueError(f"horizon {steps}: at least one step")
-        w_new = check_model_target(into, start, v.state_dim, self.model.action_dim, v.E * steps, sample_prob)
+        w_new = check_model_target(into, start, v.state_dim, self.model.action_dim, v.E * steps, sample_prob, v.can_halt)
         if start is not None and torch.device(start.device) != self.obs.device:
             raise ValueError(f"start=: the store is on {start.device}, the environment on {self.obs.device}")
         noise = self._begin(steps, seed, noise_std, gamma, noise)
