@@ -3,8 +3,8 @@ formula (tests/loss_oracle.py) on the case table of tests/loss_cases.py: both in
 5 members), the second and third pass of the 1024-thread loops, planted ties / threshold equalities / clamp edges /
 saturated tanh and softplus, the PID and log_alpha clamps, scalar Adam at step 3 with nonzero moments, the
 data-parallel arguments on a 512 + 513 split, and the host-side refusals.  Gates: tests/loss_oracle.py (module
-docstring); the equivalence tests of the suite (seeds, grid kernels, descriptor twins, fused tails) compare a launch with
-one of these launches, so they bottom out here.
+docstring); the equivalence tests of the suite (grid kernels, descriptor twins, fused tails) compare a launch with
+one of these launches, so they bottom out here; the seeded backward launches meet fp64 in tests/test_gpu_seed_kernels.py.
 
 Every output buffer is filled with NaN before the launch and carries a 64-element guard tail: the launch must write every
 word the oracle defines, leave alone every word it marks untouched, and nothing past the end.
