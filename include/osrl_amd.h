@@ -1497,6 +1497,42 @@ int osrl_model_env_branch(const float* table, int64_t n_rows, const int64_t* n_r
 int osrl_dyn_prepare(const float* obs, const float* nobs, const float* rew, const float* cost, const float* mu_s,
                      const float* sd_s, const float* mu_d, const float* sd_d, const float* mu_r, const float* sd_r,
                      int32_t rows, int32_t state_dim, float* xs, float* target, void* stream);
+/* The ensemble's per-member loss as a launch of its own (dyn_loss.hip): bootstrap-weighted output gradients, unweighted
+ * per-row losses and the logged statistic from the members' forward outputs.  For member m, row r, target row t = target[r]:
+ *   OSRL_DYN_LOSS_MSE (NL = od + 2):        l = sum_{c < od + 2} (y_c - t_c)^2,   dy_c = w 2 (y_c - t_c) scale
+ *   OSRL_DYN_LOSS_GAUSS_NLL (NL = 2 od + 3): OSRL_SEED_GAUSS_NLL's expressions above with lo / hi the log-variance bounds
+ *       (lo < hi), l = sum_{c < od + 1} ((y_c - t_c)^2 exp(-lv_c) + lv_c) + (y_{od+1} - t_{od+1})^2, every dy component times w.
+ * The bootstrap weight w = w_m(r) is a Poisson(1) count, a function of (*boot_seed, idx[r], m) alone:
+ *   word = word x of Philox4x32-10(counter {idx[r], m, 0, 17}, key = the two halves of *boot_seed),
+ *   w = #{k in 0 .. 7 : word >= T_k},  T_k = floor(2^32 sum_{j <= k} e^-1 / j!) in fp64   (w in 0 .. 8, E[w] = 1 to ~1e-6).
+ * idx[r] is the STORE row of batch row r, so each member sees one fixed resample of the dataset, not per-step noise; in a
+ * ring store the weight belongs to the physical slot (a transition that overwrites a slot inherits the slot's weight).
+ * idx == NULL: every weight is 1 (boot_seed is not read) and, for MSE, dy has the bits of OSRL_SEED_MSE's.  The loss
+ * divides by the batch (scale), never by sum w; a row with w = 0 gets dy = 0 exactly (never NaN) and adds nothing to stat.
+ *   row_loss[m, r] = l (UNWEIGHTED, unscaled);  weights_out[m, r] = w;  stat[0] = stat_scale sum_{m, r} w_m(r) l_m(r).
+ * A row's dy, row_loss and weights_out do not depend on rows, on its position or on its neighbours.  The statistic is the
+ * fixed-order sum of one partial per OSRL_DYN_LOSS_TILE rows taken by the last workgroup to arrive (no floating-point
+ * atomics): two launches on the same inputs give the same bits.  With stat: partials >= ceil(rows / OSRL_DYN_LOSS_TILE)
+ * floats, counter one uint32, ZERO before the first launch (re-armed by the launch); without stat neither is read.
+ * n_nets <= OSRL_MAX_NETS, state_dim <= OSRL_MODEL_ENV_MAX_STATE, rows >= 1, at least one output; -1 before any launch
+ * otherwise.  HOST struct; the launch goes through the argument arena (osrl_args_begin) when one is recording. */
+enum { OSRL_DYN_LOSS_MSE = 0, OSRL_DYN_LOSS_GAUSS_NLL = 1 };
+#define OSRL_DYN_LOSS_TILE 4
+typedef struct {
+  const float* y;            /* [n_nets, rows, NL]  the forward launch's output layout */
+  const float* target;       /* [rows, od + 2]      osrl_dyn_prepare's table */
+  const int32_t* idx;        /* [rows] store row of each batch row; NULL: every weight is 1 */
+  const uint64_t* boot_seed; /* device word, read only when idx != NULL */
+  float* dy;                 /* [n_nets, rows, NL] or NULL */
+  float* row_loss;           /* [n_nets, rows] or NULL */
+  float* weights_out;        /* [n_nets, rows] or NULL (tests, diagnostics) */
+  float* stat;               /* [1] or NULL */
+  float* partials;
+  uint32_t* counter;
+  int32_t n_nets, rows, state_dim, kind;
+  float lo, hi, scale, stat_scale;
+} osrl_dyn_loss_t;
+int osrl_dyn_member_loss(const osrl_dyn_loss_t* d, void* stream);
 
 /* Diagnostics (diag.hip): where the HIP runtime of this process keeps kernel arguments -- *where = 1 device memory,
  * 0 host memory (every wave then fetches its launch arguments over PCIe; see osrl_args_begin), -1 unknown.  dev_scratch:

@@ -211,6 +211,17 @@ class ModelEnvPessT(C.Structure):  # osrl_model_env_pess_t
                 ("cost_penalty", C.c_float), ("halt_step", C.c_void_p)]
 
 
+class DynLossT(C.Structure):  # osrl_dyn_loss_t
+    _fields_ = [("y", _fp), ("target", _fp), ("idx", C.c_void_p), ("boot_seed", C.c_void_p), ("dy", _fp),
+                ("row_loss", _fp), ("weights_out", _fp), ("stat", _fp), ("partials", _fp), ("counter", C.c_void_p),
+                ("n_nets", C.c_int32), ("rows", C.c_int32), ("state_dim", C.c_int32), ("kind", C.c_int32),
+                ("lo", C.c_float), ("hi", C.c_float), ("scale", C.c_float), ("stat_scale", C.c_float)]
+
+
+DYN_LOSS_MSE, DYN_LOSS_GAUSS_NLL = 0, 1  # OSRL_DYN_LOSS_*
+DYN_LOSS_TILE = 4  # OSRL_DYN_LOSS_TILE: rows per partial of osrl_dyn_member_loss's statistic
+
+
 class _HaltDesc:
     """What ``ModelVecEnv.desc`` hands out when halting or the cost penalty is on: the plain descriptor (``env``) and the
     ``osrl_model_env_pess_t`` beside it -- the two pointer arguments of the ``_halt`` entry points."""
@@ -287,6 +298,7 @@ PROTOTYPES = {
     "osrl_collect_compact": [_P(CollectT), _vp, _P(CollectT), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "osrl_model_env_branch": [_vp, _i64, _vp, _i64, _i32, _vp, _u32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
     "osrl_dyn_prepare": [_vp] * 10 + [_i32, _i32, _vp, _vp, _vp],
+    "osrl_dyn_member_loss": [_P(DynLossT), _vp],
     "osrl_env_collect": [_P(EnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _i32, _vp],
     "osrl_cdt_collect": [_P(EnvT), _P(CollectT), _P(CdtWindowT), _vp, _vp, _i32, _vp],
     "osrl_cdt_rollout_pick": [_vp, _i32, _i32, _i32, _i32, _vp, _f32, _vp, _vp],

@@ -48,7 +48,13 @@ class ModelVecEnv(DeviceVecEnv):
     ``halt_reward`` in the reward's place and ``halt_cost`` (0 or 1) as the cost; ``halt_step`` (int32 ``[E]`` on the
     device, -1: not halted; ``halted()``) keeps the step.  ``cost_penalty`` kappa: the cost bit is
     ``c + kappa * u > 0.5`` (CAP's inflation).  All four are launch arguments.  With the defaults ``desc()`` hands out the
-    plain descriptors and the plain entry points run."""
+    plain descriptors and the plain entry points run.
+
+    Elites.  On a ``Dynamics(num_elites=k)`` the environment steps the model's elite members only
+    (``model.elite_members()``, ascending): the descriptor holds those k nets and ``n_models = k``, so the mean, the spread,
+    ``max_std``, mode "random"'s draw (mod k) and the halting range over the elites.  ``member`` stays a MODEL index and
+    must be an elite in mode "member" (ValueError when the descriptor is built); ``set_member_in`` takes POSITIONS in
+    ``[0, k)``.  ``model.set_elites`` moves ``launch_epoch`` like a launch argument does."""
 
     def __init__(self, model, init_states, episodes: int, episode_len: int, max_action: float = 1.0, base_seed: int = 0,
                  mode: str = "mean", member: int = 0, reward_penalty: float = 0.0, clip_states: bool = True,
@@ -81,7 +87,7 @@ class ModelVecEnv(DeviceVecEnv):
         self._seed = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.member_in = None  # int32 [E] on the device: injected member choices of mode "random" (tests)
         self.noise_in = None  # float32 [E, od + 1] on the device: injected draws of ``sample`` (tests)
-        self.launch_epoch = 0
+        self._own_epoch = 0
         self._mode, self._member, self._penalty = "mean", 0, 0.0
         self._sample, self._uncertainty = False, "disagreement"
         self._halt_thr, self._halt_reward, self._halt_cost, self._cost_penalty = None, 0.0, 1.0, 0.0
@@ -106,6 +112,23 @@ class ModelVecEnv(DeviceVecEnv):
 
     # ---- what may change between runs ---------------------------------------------------------------------------------
     @property
+    def launch_epoch(self) -> int:
+        """Counts the changes of by-value launch arguments, the model's elite set among them (``Dynamics.elite_epoch``):
+        a rollout compares it with its descriptor's and rebuilds that, dropping its captured graph."""
+        return self._own_epoch + self._model_epoch()
+
+    @launch_epoch.setter
+    def launch_epoch(self, v: int) -> None:
+        self._own_epoch = int(v) - self._model_epoch()
+
+    def _model_epoch(self) -> int:
+        return getattr(getattr(self, "model", None), "elite_epoch", 0)
+
+    def _elites(self):
+        f = getattr(self.model, "elite_members", None)
+        return list(range(self.model.num_models)) if f is None else f()
+
+    @property
     def seed(self) -> int:
         return int(self._seed.item())
 
@@ -127,6 +150,8 @@ class ModelVecEnv(DeviceVecEnv):
             raise ValueError(f"mode {mode!r}: one of {sorted(L.MODEL_ENV_MODES)}")
         if not 0 <= int(member) < self.model.num_models:
             raise ValueError(f"member {member}: the model has {self.model.num_models} members")
+        if mode == "member" and int(member) not in self._elites():
+            raise ValueError(f"mode 'member' follows member {member}, which is not among the elites {self._elites()}")
         if (mode, int(member)) != (self._mode, self._member):
             self._mode, self._member = mode, int(member)
             self.launch_epoch += 1
@@ -254,15 +279,18 @@ class ModelVecEnv(DeviceVecEnv):
             self.launch_epoch += 1
 
     def set_member_in(self, members) -> None:
-        """Inject mode "random"'s choices: one member index per episode, the same at every step (None: draw them)."""
+        """Inject mode "random"'s choices: one member per episode, the same at every step (None: draw them).  The indices
+        are POSITIONS among the members the environment steps, ``[0, k)`` on a model with k elites (position j is member
+        ``model.elite_members()[j]``); on a model without elites positions and member indices coincide."""
         import torch
         had = self.member_in is not None
         if members is None:
             self.member_in = None
         else:
             t = torch.as_tensor(np.asarray(members, np.int32)).to(self.device).reshape(-1).contiguous()
-            if t.numel() != self.E or int(t.min()) < 0 or int(t.max()) >= self.model.num_models:
-                raise ValueError(f"member_in: {self.E} indices below {self.model.num_models}")
+            k = len(self._elites())
+            if t.numel() != self.E or int(t.min()) < 0 or int(t.max()) >= k:
+                raise ValueError(f"member_in: {self.E} indices below {k}")
             if had:
                 self.member_in.copy_(t)
             else:
@@ -276,16 +304,22 @@ class ModelVecEnv(DeviceVecEnv):
         from .. import _lib as L
         m = self.model
         d = L.ModelEnvT()
-        for i, n in enumerate(m.member_descs()):
-            d.net[i] = n
+        elites, nets = self._elites(), m.member_descs()
+        for i, e in enumerate(elites):  # (every member, in order, on a model without elites)
+            d.net[i] = nets[e]
+        member = self._member
+        if self._mode == "member":  # a model index; the launch takes its position among the nets of the descriptor
+            if member not in elites:
+                raise ValueError(f"mode 'member' follows member {member}, which is not among the elites {elites}")
+            member = elites.index(member)
         for k in ("mu_s", "sd_s", "mu_d", "sd_d", "mu_r", "sd_r"):
             setattr(d, k, getattr(m, k).data_ptr())
         if self.clip_states:
             d.s_lo, d.s_hi = m.s_lo.data_ptr(), m.s_hi.data_ptr()
         d.seed = self._seed.data_ptr()
         d.member_in = None if self.member_in is None else self.member_in.data_ptr()
-        d.n_models, d.state_dim, d.action_dim, d.episode_len = m.num_models, self.state_dim, self.action_dim, int(episode_len)
-        d.mode, d.member, d.episode_base = L.MODEL_ENV_MODES[self._mode], self._member, self.base_seed & 0xFFFFFFFF
+        d.n_models, d.state_dim, d.action_dim, d.episode_len = len(elites), self.state_dim, self.action_dim, int(episode_len)
+        d.mode, d.member, d.episode_base = L.MODEL_ENV_MODES[self._mode], member, self.base_seed & 0xFFFFFFFF
         d.max_action, d.cost_scale, d.reward_penalty = self.max_action, float(cost_scale), self._penalty
         if getattr(m, "probabilistic", False):  # osrl_model_env_gauss_t: the same descriptor, embedded
             g = L.ModelEnvGaussT()

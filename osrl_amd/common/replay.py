@@ -434,15 +434,16 @@ class ReplayStore:
                 self._live_ptr())
 
     def gather_fields(self, fields: Sequence[int], dst: Sequence[torch.Tensor], st_ptr: Optional[int],
-                      stream_id: int = 1) -> None:
+                      stream_id: int = 1, idx_out: Optional[torch.Tensor] = None) -> None:
         """The same draw as ``gather`` (the row indices are a function of (seed, step, row) only) restricted to some
-        of the tables -- (0, 2) = observations, actions is all BC reads (train_bc.py:121)."""
+        of the tables -- (0, 2) = observations, actions is all BC reads (train_bc.py:121).  ``idx_out`` (int32 ``[B]``
+        on the device, optional) receives the drawn row indices, as ``gather``'s does."""
         n, B = len(fields), dst[0].shape[0]
         src = (C.c_void_p * n)(*[self.tables[i].data_ptr() for i in fields])
         d = (C.c_void_p * n)(*[t.data_ptr() for t in dst])
         w = (C.c_int32 * n)(*[self.widths[i] for i in fields])
         sc = (C.c_float * n)(*[self.scales[i] for i in fields])
-        self._gather(n, src, d, w, sc, B, None, stream_id, st_ptr)
+        self._gather(n, src, d, w, sc, B, None if idx_out is None else idx_out.data_ptr(), stream_id, st_ptr)
 
 def synthetic_transitions(n: int, od: int, ad: int, seed: int = 1, max_action: float = 1.0) -> Dict[str, np.ndarray]:
     """Synthetic DSRL-shaped data: obs~N(0,1), act~U(-1,1), rew~N(0,1), cost~Bern(.1),

@@ -17,9 +17,20 @@ With ``s = 1 / (B (od + 2))`` and ``lv`` the bounded log-variance (algorithms/dy
     loss = sum_m s sum_rows [ sum_{c <= od} ((mu_c - t_c)^2 exp(-lv_c) + lv_c) + (y_cost - t_cost)^2 ]
 
 logged under the same key, ``loss/dynamics_loss``.
+
+A ``bootstrap`` model takes ``BootDynamicsEngine``: the loss is a launch of its own (csrc/dyn_loss.hip
+``osrl_dyn_member_loss``) between the forward and an unseeded backward launch, so that every member's output gradient can
+be scaled row by row with that member's Poisson(1) bootstrap weight.  The weight is a function of (``model.boot_seed``,
+the row's index in the store, the member): the gather writes the drawn row indices beside the batch, the loss launch
+turns them into weights.  The minibatch rows are those a default engine draws at the same seed and step; the statistic is
+the weighted loss, still divided by the batch size.  ``validate`` (algorithms/dynamics.py) uses the same launch for the
+unweighted per-row losses of a holdout set.
 """
 from __future__ import annotations
 
+import ctypes as C
+
+import numpy as np
 import torch
 
 from .. import _lib as L
@@ -92,4 +103,79 @@ class DynamicsEngine(StepEngine):
                                           self.xs.data_ptr(), self.target.data_ptr(), cur_stream()), "osrl_dyn_prepare")
         self.r_f.forward(self.xs, self.act)
         self.r_f.backward_dz(seed=self.seed_mse)
+        self._optim("dynamics", self.plan)
+
+
+def member_loss_desc(model, y: torch.Tensor, target: torch.Tensor, rows: int, idx=None, dy=None, row_loss=None,
+                     weights_out=None, stat: int = 0, ws=None, scale: float = 0.0, stat_scale: float = 0.0) -> "L.DynLossT":
+    """The ``osrl_dyn_loss_t`` of ``model``'s members on ``rows`` rows: ``y`` the forward launch's output, ``target``
+    ``osrl_dyn_prepare``'s table; ``idx`` (int32 ``[rows]``, the rows' indices in the store) turns the bootstrap weights
+    on; ``stat`` the address of the statistic with ``ws`` its ``DynLossStat`` scratch.  The log-variance bounds are
+    by-value arguments, read from the model's buffers here."""
+    d = L.DynLossT()
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    d.y, d.target, d.idx, d.dy, d.row_loss, d.weights_out = p(y), p(target), p(idx), p(dy), p(row_loss), p(weights_out)
+    if idx is not None:
+        assert idx.dtype == torch.int32 and idx.numel() >= rows
+        d.boot_seed = model.boot_seed.data_ptr()
+    if stat:
+        d.stat, d.partials, d.counter = stat, ws.partials.data_ptr(), ws.counter.data_ptr()
+    d.n_nets, d.rows, d.state_dim = model.num_models, int(rows), model.state_dim
+    d.kind = L.DYN_LOSS_GAUSS_NLL if model.probabilistic else L.DYN_LOSS_MSE
+    if model.probabilistic:
+        d.lo, d.hi = float(model.logvar_min.item()), float(model.logvar_max.item())
+    d.scale, d.stat_scale = float(scale), float(stat_scale)
+    d._keep = [y, target, idx, dy, row_loss, weights_out, ws]
+    return d
+
+
+def member_loss(d: "L.DynLossT") -> None:
+    L.check(L.load().osrl_dyn_member_loss(C.byref(d), cur_stream()), "osrl_dyn_member_loss")
+
+
+class DynLossStat:
+    """Scratch of one ``osrl_dyn_member_loss`` call site that logs a statistic: one partial per ``OSRL_DYN_LOSS_TILE``
+    rows + the arrival counter."""
+
+    def __init__(self, device, rows: int):
+        self.partials = torch.zeros((rows + L.DYN_LOSS_TILE - 1) // L.DYN_LOSS_TILE, dtype=torch.float32, device=device)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=device)
+
+
+class BootDynamicsEngine(DynamicsEngine):
+    """The train step of a ``bootstrap`` model (the module docstring): tick -> gather (+ the drawn row indices) ->
+    ``osrl_dyn_prepare`` -> forward -> ``osrl_dyn_member_loss`` -> backward -> dW + Adam, one chain, one one-step graph."""
+
+    def __init__(self, model, batch_size: int, seed: int = 0, dist=None):
+        super().__init__(model, batch_size, seed=seed, dist=dist)
+        dev = torch.device(model.device)
+        self.row_idx = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        s = float(np.float32(1.0) / np.float32(self.B * (model.state_dim + 2)))
+        self.loss_d = member_loss_desc(model, self.r_f.y, self.target, self.B, idx=self.row_idx, dy=self.dy,
+                                       stat=self.st.stat_ptr(STAT_KEYS[0]), ws=DynLossStat(dev, self.B), scale=s,
+                                       stat_scale=s)
+
+    def load_row_ids(self, row_ids) -> None:
+        """The caller batch's dataset indices (int32 ``[B]``): what the bootstrap weights are keyed by."""
+        t = torch.as_tensor(row_ids)
+        if t.numel() != self.B or t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"row_ids: {self.B} integer dataset indices, got {tuple(t.shape)} {t.dtype}")
+        self.row_idx.copy_(t.reshape(-1).to(torch.int32), non_blocking=True)
+
+    def body(self, device_noise: bool) -> None:
+        m, st = self.model, self.st
+        batch = (self.obs, self.nobs, self.act, self.rew, self.cost, self.done)
+        st.tick()
+        if self.replay is not None:  # the rows the fused prologue would draw: a function of (seed, step, row) alone
+            if self.replay.n_fields != len(batch):
+                self.replay.gather_fields(range(len(batch)), batch, st.ptr, idx_out=self.row_idx)
+            else:
+                self.replay.gather(batch, st.ptr, idx_out=self.row_idx)
+        L.check(L.load().osrl_dyn_prepare(self.obs.data_ptr(), self.nobs.data_ptr(), self.rew.data_ptr(),
+                                          self.cost.data_ptr(), m.mu_s.data_ptr(), m.sd_s.data_ptr(), m.mu_d.data_ptr(),
+                                          m.sd_d.data_ptr(), m.mu_r.data_ptr(), m.sd_r.data_ptr(), self.B, m.state_dim,
+                                          self.xs.data_ptr(), self.target.data_ptr(), cur_stream()), "osrl_dyn_prepare")
+        self.r_f.forward(self.xs, self.act)
+        member_loss(self.loss_d)
+        self.r_f.backward_dz()
         self._optim("dynamics", self.plan)
