@@ -19,7 +19,7 @@ from ..common.net import EnsembleQCritic, bind_group, check_mlp_limits, plan_gro
 from ..engine.core import FlatGroup, require_cuda
 from ._base import FlatModel
 
-MAX_NUM_Q = 4  # 2 * num_q nets share one launch (OSRL_MAX_NETS = 8); the seed reads <= 4 members per ensemble (kSeedEns)
+MAX_NUM_Q = 4  # 2 * num_q nets share one launch (OSRL_MAX_NETS = 8); the seed reads <= 4 members per ensemble (kEns)
 
 
 class FQEEstimate(NamedTuple):

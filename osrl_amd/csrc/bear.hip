@@ -11,20 +11,16 @@
 #include <cstdint>
 
 #include "../../include/osrl_amd.h"
+#include "dev_util.h"
+#include "loss_terms.h"
 
 namespace {
 
-constexpr float kLogStdMin = -20.0f, kLogStdMax = 2.0f;  // osrl/common/net.py:148-149
 constexpr int kRed = 1024;
 constexpr int kMmdWaves = 4;  // waves (= batch rows) per workgroup of bear_mmd_kernel; launch geometry as compile-time
                               // constants: `blockDim` is a load from the hidden kernarg block in every wave
 constexpr int kMaxAd = 16;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 __device__ float block_sum(float v, float* sm /*>=17*/) {
   v = wave_sum(v);

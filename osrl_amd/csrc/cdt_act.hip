@@ -44,6 +44,7 @@
 #include <new>
 #include <vector>
 
+#include "dev_util.h"
 #include "gelu.h"
 #include "policy_common.h"
 #include "rollout_step.h"
@@ -62,16 +63,6 @@ constexpr int kTabStride = OSRL_CDT_POLICY_MAX_ENVS;
 constexpr int kTabMode = 0, kTabT = 1, kTabWs = 2, kTabSrow = 3, kTabSet = 4, kTabFields = 16;
 constexpr int kIdle = 0, kStep = 1, kRestart = 2;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 
 // mean / rstd of one row of E <= 512 floats, by one wave (two passes, as the training LayerNorm)
 __device__ __forceinline__ void row_stats(const float* __restrict__ x, int E, int lane, float* mean_o, float* rstd_o) {

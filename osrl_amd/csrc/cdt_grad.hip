@@ -15,17 +15,13 @@
 #include <stdint.h>
 
 #include "../../include/osrl_amd.h"
+#include "dev_util.h"
 
 namespace {
 
 constexpr int kMaxE = 1024;  // the CDT constructor's embedding_dim limit
 constexpr int kWaves = 4;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 struct InputGradArgs {
   const float *dseq, *Ws, *Wa, *Wr, *Wc, *Wp;

@@ -12,22 +12,13 @@
 #include <cstdint>
 
 #include "../../include/osrl_amd.h"
+#include "dev_util.h"
+#include "loss_terms.h"
 
 namespace {
 
 constexpr int kRed = 1024;
-constexpr float kLogStdMin = -20.0f, kLogStdMax = 2.0f;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 template <bool MAX>
 __device__ float block_red(float v, float* sm /*>=17*/) {
   v = MAX ? wave_max(v) : wave_sum(v);
@@ -43,8 +34,6 @@ __device__ float block_red(float v, float* sm /*>=17*/) {
   __syncthreads();
   return sm[16];
 }
-__device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
-__device__ __forceinline__ float sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // get_f_div_fn (coptidice.py:15-38): f, f', g = f'^{-1}, g'
 __device__ __forceinline__ float f_fn(int t, float w) {

@@ -4,8 +4,8 @@
 //   dy          the output gradient of every member, each row scaled by that member's bootstrap weight,
 //   row_loss    the unweighted per-row loss l_m(r)                                  (holdout loss: DynamicsTrainer.validate),
 //   stat        stat_scale * sum_{m, r} w_m(r) l_m(r)                               (the logged statistic),
-// with the arithmetic of the seeded backward launch (mlp.hip, OSRL_SEED_MSE / OSRL_SEED_GAUSS_NLL; the small softplus and
-// sigmoid helpers are restated here).  The bootstrap weight w_m(r) is a Poisson(1) count that belongs to the STORE ROW
+// with the arithmetic of the seeded backward launch (mlp.hip, OSRL_SEED_MSE / OSRL_SEED_GAUSS_NLL): both call the terms of
+// loss_terms.h.  The bootstrap weight w_m(r) is a Poisson(1) count that belongs to the STORE ROW
 // idx[r] and the member m: word x of Philox4x32-10(counter {idx[r], m, 0, 17}, key *boot_seed) against the cumulative
 // table kBootT, so every member trains on one fixed resample of the dataset (include/osrl_amd.h).
 //
@@ -22,6 +22,8 @@
 
 #include "../../include/osrl_amd.h"
 #include "argmem.h"
+#include "dev_util.h"
+#include "loss_terms.h"
 #include "philox.h"
 
 namespace {
@@ -42,17 +44,6 @@ __device__ __forceinline__ float boot_weight(uint32_t word) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) w += word >= kBootT[k] ? 1 : 0;
   return (float)w;
-}
-
-// OSRL_SEED_GAUSS_NLL's bounded log-variance (PETS' soft clamp), as mlp.hip states it
-__device__ __forceinline__ float dl_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float dl_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ void coh_put(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float coh_get(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // AR = how the descriptor is reached: `const osrl_dyn_loss_t&` (the kernarg segment) or the OSRL_CAS form (argmem.h)
@@ -97,17 +88,15 @@ __device__ __forceinline__ void dyn_loss_body(AR a) {
         if (k < no) {
           const float d = y[k] - t[j];
           if (!gauss || k == no - 1) {  // MSE; the Gaussian's raw cost column
-            l += d * d;
-            const float g = 2.0f * d * scale;
+            l += sq_term(d);
+            const float g = sq_grad(d, scale);
             if (dy) dy[k] = w == 0.f ? 0.f : g * w;
           } else {
             const float raw = y[no + k];
-            const float lv1 = hi - dl_softplus(hi - raw);
-            const float lv = lo + dl_softplus(lv1 - lo);
-            const float iv = expf(-lv);
-            l += d * d * iv + lv;
-            const float g = 2.0f * d * iv * scale;
-            const float gv = (1.0f - d * d * iv) * dl_sigmoid(hi - raw) * dl_sigmoid(lv1 - lo) * scale;
+            const LogVar v = gauss_nll_logvar(raw, lo, hi);
+            l += gauss_nll_term(d, v);
+            const float g = gauss_nll_g_mean(d, v, scale);
+            const float gv = gauss_nll_g_raw(d, raw, v, lo, hi, scale);
             if (dy) {
               dy[k] = w == 0.f ? 0.f : g * w;
               dy[no + k] = w == 0.f ? 0.f : gv * w;
@@ -115,8 +104,7 @@ __device__ __forceinline__ void dyn_loss_body(AR a) {
           }
         }
       }
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) l += __shfl_xor(l, o);
+      l = wave_sum(l);
       if (a.row_loss && lane == 0) a.row_loss[(size_t)m * rows + r] = l;
       wsum += w == 0.f ? 0.f : w * l;
     }
@@ -132,19 +120,14 @@ __device__ __forceinline__ void dyn_loss_body(AR a) {
 #pragma unroll
     for (int w = 0; w < kRows; ++w) p += s_part[w];
     coh_put(a.partials + blockIdx.x, p);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the partial is acknowledged before the arrival
-    const unsigned seen = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = seen == (unsigned)n_part - 1;
-    if (last) __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed
-    s_last = last;
+    s_last = arrive_last(a.counter, n_part);  // (the partial is acknowledged before the arrival)
   }
   __syncthreads();
   if (!s_last) return;
   const int per = (n_part + kThreads - 1) / kThreads;
   float s = 0.f;
   for (int i = tid * per; i < (tid + 1) * per && i < n_part; ++i) s += coh_get(a.partials + i);
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   if (lane == 0) s_part[wave] = s;  // (tid 0 read the waves' sums before the barrier that published s_last)
   __syncthreads();
   if (tid == 0) {

@@ -15,12 +15,12 @@
 
 #include "../../include/osrl_amd.h"
 #include "argmem.h"
+#include "dev_util.h"
+#include "loss_terms.h"
 #include "trace.h"
 
 namespace {
 
-constexpr float kLogStdMin = -20.0f, kLogStdMax = 2.0f;  // net.py:148-149
-constexpr float kVaeLsMin = -4.0f, kVaeLsMax = 15.0f;    // net.py:325
 constexpr int kRed = 1024;
 // Launch geometry as compile-time constants (round 3): `blockDim` / `gridDim` are read from the hidden block behind a
 // kernel's explicit arguments, i.e. by an s_load from the kernarg segment in every wave -- a PCIe round trip at the head
@@ -28,11 +28,6 @@ constexpr int kRed = 1024;
 // hands over.  The element-wise kernels are always launched with kEw threads (GRID_1D), the batch-sum kernels with kRed.
 constexpr int kEw = 256;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 // sum over a 1024-thread block; result valid in every thread
 __device__ __forceinline__ float block_sum(float v, float* sm /*>=17 floats*/) {
   v = wave_sum(v);
@@ -47,9 +42,6 @@ __device__ __forceinline__ float block_sum(float v, float* sm /*>=17 floats*/) {
   }
   __syncthreads();
   return sm[16];
-}
-__device__ __forceinline__ float softplus(float x) {  // log(1+exp(x)), F.softplus
-  return x > 20.0f ? x : log1pf(expf(x));
 }
 
 #define GRID_1D(n) dim3((unsigned)(((n) + kEw - 1) / kEw)), dim3(kEw)
@@ -78,12 +70,6 @@ __global__ void gauss_head_kernel(const float* __restrict__ head, const float* _
   if (logp) logp[r] = lp;
 }
 
-// A loaded value that is only consumed under a condition gets its load SUNK into that branch by the compiler (and a
-// select on it turned into such a branch), where it waits alone: s_waitcnt vmcnt(0) per load, one memory round trip
-// after the other.  pin() makes the value unconditionally live at the point of the call, so a group of loads issued
-// back to back in front of a group of pin()s stays in flight together.
-__device__ __forceinline__ void pin(float& x) { asm volatile("" : "+v"(x)); }
-
 __global__ void gauss_head_bwd_kernel(const float* __restrict__ head, const float* __restrict__ eps,
                                       const float* __restrict__ tanh_u, const float* __restrict__ da_nets,
                                       int n_nets, int rows, int ad, float max_a, float* __restrict__ dhead) {
@@ -109,11 +95,9 @@ __global__ void gauss_head_bwd_kernel(const float* __restrict__ head, const floa
   pin(t);
   pin(lsr);
   pin(ev);
-  const float du = da * max_a * (1.0f - t * t);
-  const float ls = fminf(fmaxf(lsr, kLogStdMin), kLogStdMax);
-  const bool inside = lsr >= kLogStdMin && lsr <= kLogStdMax;
+  const float du = gauss_head_du(da, max_a, t);
   dhead[(size_t)r * 2 * ad + j] = du;
-  dhead[(size_t)r * 2 * ad + ad + j] = inside ? du * ev * expf(ls) : 0.f;
+  dhead[(size_t)r * 2 * ad + ad + j] = gauss_head_dls(du, lsr, ev);
 }
 
 __global__ void gauss_ood_kernel(const float* __restrict__ head, const float* __restrict__ eps, int n_samples,
@@ -139,11 +123,6 @@ __global__ void vae_latent_kernel(const float* __restrict__ head, const float* _
   const float mean = head[(size_t)r * 2 * L + k];
   const float ls = fminf(fmaxf(head[(size_t)r * 2 * L + L + k], kVaeLsMin), kVaeLsMax);
   z[i] = mean + expf(ls) * eps[i];
-}
-
-__device__ __forceinline__ float kl_elem(float mean, float ls_raw) {
-  const float sd = expf(fminf(fmaxf(ls_raw, kVaeLsMin), kVaeLsMax));
-  return -0.5f * (1.0f + logf(sd * sd) - mean * mean - sd * sd);
 }
 
 // (body + two entry kernels: by value, and "_p" = arguments in a device-resident block, csrc/argmem.h -- the three
@@ -176,8 +155,8 @@ __device__ __forceinline__ void vae_loss_body(const float* __restrict__ u, const
       const int i = i0 + k * kRed;
       if (i < n_rec) {
         const float d = uv[k] - av[k];
-        rec += d * d;
-        du[i] = 2.0f * d * ia;
+        rec += sq_term(d);
+        du[i] = sq_grad(d, ia);
       }
     }
   }
@@ -598,27 +577,14 @@ __global__ __launch_bounds__(256) void qsel_finish_kernel(int64_t n, float q, ui
 }
 
 // ---------------- CPQ ----------------
-// Ensemble outputs are [n][stride].  SMALL (n <= kEns, host-checked: every reference config) requests all members of
-// an element together as straight-line code -- members past n re-read member 0 and are dropped by a select -- so the
-// loads of one batch row (targets, online nets, reward, done) overlap; the counted loops of the general form wait for
-// each member in turn (cpq_critic_loss: 8 serial round trips per row before).  Same fminf / accumulation order, same
-// bits.
-constexpr int kEns = 4;
-template <bool SMALL>
-__device__ __forceinline__ void load_members(const float* __restrict__ q, int n, int stride, int i, float (&v)[kEns]) {
-  static_assert(SMALL, "general form: counted loops at the call site");
-#pragma unroll
-  for (int e = 0; e < kEns; ++e) v[e] = q[(size_t)(e < n ? e : 0) * stride + i];
-}
+// Ensemble outputs are [n][stride].  SMALL (n <= kEns, host-checked: every reference config) takes the straight-line
+// member loads of loss_terms.h, so the loads of one batch row (targets, online nets, reward, done) overlap; the counted
+// loops of the general form wait for each member in turn (cpq_critic_loss: 8 serial round trips per row before).  Same
+// fminf / accumulation order, same bits.
 template <bool SMALL = false>
 __device__ __forceinline__ float min_over(const float* __restrict__ q, int n, int stride, int i) {
   if constexpr (SMALL) {
-    float v[kEns];
-    load_members<true>(q, n, stride, i, v);
-    float m = v[0];
-#pragma unroll
-    for (int e = 1; e < kEns; ++e) m = e < n ? fminf(m, v[e]) : m;
-    return m;
+    return min_members(q, n, stride, i);
   } else {
     float v = q[i];
     for (int e = 1; e < n; ++e) v = fminf(v, q[(size_t)e * stride + i]);
@@ -639,24 +605,23 @@ __device__ __forceinline__ void cpq_critic_loss_body(const float* __restrict__ q
   for (int b = threadIdx.x; b < rows; b += kRed) {
     const float qt = min_over<SMALL>(q_old, n_q_old, rows, b);
     const float qct = min_over<SMALL>(qc_old, n_qc_old, rows, b);
-    // backup = r + gamma*(1-done)*(qc_targ<=q_thres)*q_targ      cpq.py:145-146
     if constexpr (SMALL) {
       float qv[kEns];
-      load_members<true>(q, n_q, rows, b, qv);
-      const float backup = rew[b] + gamma * (1.0f - done[b]) * (qct <= q_thres ? 1.0f : 0.0f) * qt;
+      load_members(q, n_q, rows, b, qv);
+      const float backup = cpq_critic_backup(rew[b], done[b], qt, qct, gamma, q_thres);
 #pragma unroll
       for (int e = 0; e < kEns; ++e)
         if (e < n_q) {
           const float d = qv[e] - backup;
-          loss += d * d;
-          dq[(size_t)e * rows + b] = 2.0f * d * inv_rows;
+          loss += sq_term(d);
+          dq[(size_t)e * rows + b] = sq_grad(d, inv_rows);
         }
     } else {
-      const float backup = rew[b] + gamma * (1.0f - done[b]) * (qct <= q_thres ? 1.0f : 0.0f) * qt;
+      const float backup = cpq_critic_backup(rew[b], done[b], qt, qct, gamma, q_thres);
       for (int e = 0; e < n_q; ++e) {
         const float d = q[(size_t)e * rows + b] - backup;
-        loss += d * d;
-        dq[(size_t)e * rows + b] = 2.0f * d * inv_rows;
+        loss += sq_term(d);
+        dq[(size_t)e * rows + b] = sq_grad(d, inv_rows);
       }
     }
   }
@@ -811,21 +776,21 @@ __device__ __forceinline__ void cpq_cost_loss_body(
   for (int b = threadIdx.x; b < rows; b += kRed) {
     if constexpr (SMALL) {
       float qv[kEns];
-      load_members<true>(qc, n_qc, rows, b, qv);
-      const float backup = cost[b] + gamma * min_over<true>(qc_old_next, n_qc_old, rows, b);  // cpq.py:161
+      load_members(qc, n_qc, rows, b, qv);
+      const float backup = cpq_cost_backup(cost[b], min_over<true>(qc_old_next, n_qc_old, rows, b), gamma);
 #pragma unroll
       for (int e = 0; e < kEns; ++e)
         if (e < n_qc) {
           const float d = qv[e] - backup;
-          loss += d * d;
-          dq[(size_t)e * rows + b] = 2.0f * d * inv_rows;
+          loss += sq_term(d);
+          dq[(size_t)e * rows + b] = sq_grad(d, inv_rows);
         }
     } else {
-      const float backup = cost[b] + gamma * min_over(qc_old_next, n_qc_old, rows, b);  // cpq.py:161
+      const float backup = cpq_cost_backup(cost[b], min_over(qc_old_next, n_qc_old, rows, b), gamma);
       for (int e = 0; e < n_qc; ++e) {
         const float d = qc[(size_t)e * rows + b] - backup;
-        loss += d * d;
-        dq[(size_t)e * rows + b] = 2.0f * d * inv_rows;
+        loss += sq_term(d);
+        dq[(size_t)e * rows + b] = sq_grad(d, inv_rows);
       }
     }
   }
@@ -893,14 +858,8 @@ __global__ __launch_bounds__(kRed) void cpq_actor_loss_kernel(const float* __res
     float qm;
     if constexpr (SMALL) {
       float qv[kEns];
-      load_members<true>(q, n_q, rows, b, qv);
-      qm = qv[0];
-#pragma unroll
-      for (int e = 1; e < kEns; ++e) {
-        const bool lt = e < n_q && qv[e] < qm;
-        qm = lt ? qv[e] : qm;
-        am = lt ? e : am;
-      }
+      load_members(q, n_q, rows, b, qv);
+      cpq_actor_argmin(qv, n_q, qm, am);
     } else {
       qm = q[b];
       for (int e = 1; e < n_q; ++e) {
@@ -908,7 +867,7 @@ __global__ __launch_bounds__(kRed) void cpq_actor_loss_kernel(const float* __res
         if (v < qm) { qm = v; am = e; }
       }
     }
-    const float mask = min_over<SMALL>(qc, n_qc, rows, b) <= q_thres ? 1.0f : 0.0f;
+    const float mask = cpq_actor_mask(min_over<SMALL>(qc, n_qc, rows, b), q_thres);
     loss -= mask * qm;
     for (int e = 0; e < n_q; ++e) dq[(size_t)e * rows + b] = e == am ? -mask * inv_rows : 0.f;
   }
@@ -923,8 +882,8 @@ __global__ __launch_bounds__(kRed) void mse_loss_kernel(const float* __restrict_
   float loss = 0.f;
   for (int i = threadIdx.x; i < n; i += kRed) {
     const float d = u[i] - act[i];
-    loss += d * d;
-    du[i] = 2.0f * d * inv_n;
+    loss += sq_term(d);
+    du[i] = sq_grad(d, inv_n);
   }
   loss = block_sum(loss, sm);
   if (threadIdx.x == 0 && stat) stat[0] = loss * inv_n;
@@ -995,15 +954,15 @@ __global__ __launch_bounds__(kRed) void bcq_critic_loss_kernel(const float* __re
       const int i = b * n_samples + j;  // repeat_interleave order, bcql.py:138,146
       const float q1 = min_over(q_t, n1, nr, i);
       const float q2 = min_over(q_t + (size_t)n1 * nr, n2, nr, i);
-      const float v = lmbda * fminf(q1, q2) + (1.0f - lmbda) * fmaxf(q1, q2);
+      const float v = bcq_mix(q1, q2, lmbda);
       best = fmaxf(best, v);
     }
     const float nd = done ? (1.0f - done[b]) : 1.0f;
-    const float backup = base[b] + gamma * nd * best;
+    const float backup = bcq_backup(base[b], nd, best, gamma);
     for (int e = 0; e < n_on; ++e) {
       const float d = q_on[(size_t)e * rows + b] - backup;
-      loss += d * d;
-      dq[(size_t)e * rows + b] = 2.0f * d * inv_rows;
+      loss += sq_term(d);
+      dq[(size_t)e * rows + b] = sq_grad(d, inv_rows);
     }
   }
   loss = block_sum(loss, sm);
@@ -1076,15 +1035,15 @@ __global__ __launch_bounds__(kGridThreads) void bcq_critic_loss_grid_kernel(
       const int i = b * n_samples + j;  // repeat_interleave order, bcql.py:138,146
       const float q1 = min_over(q_t, n1, nr, i);
       const float q2 = min_over(q_t + (size_t)n1 * nr, n2, nr, i);
-      const float v = lmbda * fminf(q1, q2) + (1.0f - lmbda) * fmaxf(q1, q2);
+      const float v = bcq_mix(q1, q2, lmbda);
       best = fmaxf(best, v);
     }
     const float nd = done ? (1.0f - done[b]) : 1.0f;
-    const float backup = base[b] + gamma * nd * best;
+    const float backup = bcq_backup(base[b], nd, best, gamma);
     for (int e = 0; e < n_on; ++e) {
       const float d = q_on[(size_t)e * rows + b] - backup;
-      loss += d * d;
-      dq[(size_t)e * rows + b] = 2.0f * d * inv_rows;
+      loss += sq_term(d);
+      dq[(size_t)e * rows + b] = sq_grad(d, inv_rows);
     }
   }
   loss = block_sum256(loss, sm);
@@ -1109,8 +1068,8 @@ __global__ __launch_bounds__(kGridThreads) void vae_loss_grid_kernel(const float
   const int stride = gridDim.x * kGridThreads;
   for (int i = blockIdx.x * kGridThreads + threadIdx.x; i < n_rec; i += stride) {
     const float d = u[i] - act[i];
-    rec += d * d;
-    du[i] = 2.0f * d * ia;
+    rec += sq_term(d);
+    du[i] = sq_grad(d, ia);
   }
   for (int i = blockIdx.x * kGridThreads + threadIdx.x; i < n_kl; i += stride) {
     const int r = i / L, c = i - r * L;

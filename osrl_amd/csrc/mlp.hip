@@ -32,6 +32,8 @@
 //     split-K (over rows) MFMA GEMM dW = dZ^T A writing per-split slabs that the Adam kernel sums
 //     in a fixed order (deterministic, no atomics).
 #include "dwt.h"
+#include "dev_util.h"
+#include "loss_terms.h"
 #include "adam.h"
 #include "gather.h"
 #include "step.h"
@@ -388,8 +390,6 @@ __device__ __forceinline__ void fwd_epilogue(float* lds, int lda, const f32x4 (&
 
 // ---- row-local tails on the LDS-resident last tile (osrl_mlp_tail_t; the arithmetic of csrc/glue.hip's
 // vae_latent_kernel / vae_latent_bwd_kernel, expression for expression) ------------------------------------------
-constexpr float kTailLsMin = -4.0f, kTailLsMax = 15.0f;  // net.py:325 (== kVaeLsMin / kVaeLsMax of glue.hip)
-
 // tile = the encoder output [BM][2L] (mean | log_std): z = mean + exp(clamp(log_std)) * eps
 template <class TR, int NT = 0>
 __device__ __forceinline__ void tail_vae_latent(const float* lds, int lda, int BM, int row0, int rows, TR t) {
@@ -399,7 +399,7 @@ __device__ __forceinline__ void tail_vae_latent(const float* lds, int lda, int B
     const int gr = row0 + r;
     if (gr < rows) {
       const float mean = lds[r * lda + k];
-      const float ls = fminf(fmaxf(lds[r * lda + Lz + k], kTailLsMin), kTailLsMax);
+      const float ls = fminf(fmaxf(lds[r * lda + Lz + k], kVaeLsMin), kVaeLsMax);
       const size_t i = (size_t)gr * Lz + k;
       t.out[i] = mean + expf(ls) * t.eps[i];
     }
@@ -419,10 +419,10 @@ __device__ __forceinline__ void tail_vae_latent_bwd(const float* lds, int lda, i
       const float lsr = t.head[(size_t)gr * 2 * Lz + Lz + k];
       const float ev = t.eps[i];
       const float g = lds[r * lda + k];
-      const float sd = expf(fminf(fmaxf(lsr, kTailLsMin), kTailLsMax));
+      const float sd = expf(fminf(fmaxf(lsr, kVaeLsMin), kVaeLsMax));
       const float c = t.beta * t.inv_rows_ / (float)Lz;
       t.out[(size_t)gr * 2 * Lz + k] = g + c * mean;
-      const bool inside = lsr >= kTailLsMin && lsr <= kTailLsMax;
+      const bool inside = lsr >= kVaeLsMin && lsr <= kVaeLsMax;
       t.out[(size_t)gr * 2 * Lz + Lz + k] = inside ? (g * ev + c * (sd - 1.0f / sd)) * sd : 0.f;
     }
   }
@@ -430,7 +430,6 @@ __device__ __forceinline__ void tail_vae_latent_bwd(const float* lds, int lda, i
 
 // tile = the actor trunk's output [BM][2 ad] (mu | log_std): the action draws of the squashed-Gaussian head
 // (glue.hip gauss_head_kernel / gauss_ood_kernel, expression for expression) while the tile is in LDS
-constexpr float kTailLogStdMin = -20.0f, kTailLogStdMax = 2.0f;  // net.py:148-149 (== kLogStdMin / kLogStdMax of glue.hip)
 template <class TR, int NT = 0>
 __device__ __forceinline__ void tail_gauss(const float* lds, int lda, int BM, int row0, int rows, TR t) {
   const int ad = t.L;
@@ -445,7 +444,7 @@ __device__ __forceinline__ void tail_gauss(const float* lds, int lda, int BM, in
     const int gr = row0 + r;
     if (gr < rows) {
       const float mu = lds[r * lda + j];
-      const float ls = fminf(fmaxf(lds[r * lda + ad + j], kTailLogStdMin), kTailLogStdMax);
+      const float ls = fminf(fmaxf(lds[r * lda + ad + j], kLogStdMin), kLogStdMax);
       const float sd = expf(ls);
       const size_t i = (size_t)gr * ad + j;
       if (e1) {
@@ -470,7 +469,7 @@ __device__ __forceinline__ void tail_gauss(const float* lds, int lda, int BM, in
       const int gr = row0 + r;
       if (gr < rows) {
         const float mu = lds[r * lda + k];
-        const float ls = fminf(fmaxf(lds[r * lda + ad + k], kTailLogStdMin), kTailLogStdMax);
+        const float ls = fminf(fmaxf(lds[r * lda + ad + k], kLogStdMin), kLogStdMax);
         const size_t i = ((size_t)smp * rows + gr) * ad + k;
         so[i] = mu + expf(ls) * eo[i];
       }
@@ -749,29 +748,9 @@ struct BwdArgs {
 };
 
 // ---- loss seeds (osrl_mlp_seed_t): dL/d(output) of the rows a tile stages, from forward outputs of the same rows --
-// the expressions of csrc/glue.hip's loss kernels, term for term (vae_loss_body, cpq_critic_loss_body,
-// cpq_cost_loss_body, cpq_actor_loss_kernel, gauss_head_bwd_kernel), so that the gradient has their bits.
-constexpr float kSeedLogStdMin = -20.0f, kSeedLogStdMax = 2.0f;  // net.py:148-149 (== kLogStdMin / kLogStdMax of glue.hip)
-constexpr int kSeedEns = 4;                                       // == kEns of glue.hip (host-checked)
-__device__ __forceinline__ void seed_members(const float* __restrict__ q, int n, int stride, int i, float (&v)[kSeedEns]) {
-#pragma unroll
-  for (int e = 0; e < kSeedEns; ++e) v[e] = q[(size_t)(e < n ? e : 0) * stride + i];  // members past n re-read member 0
-}
-__device__ __forceinline__ float seed_min(const float* __restrict__ q, int n, int stride, int i) {
-  float v[kSeedEns];
-  seed_members(q, n, stride, i, v);
-  float m = v[0];
-#pragma unroll
-  for (int e = 1; e < kSeedEns; ++e) m = e < n ? fminf(m, v[e]) : m;
-  return m;
-}
-__device__ __forceinline__ float seed_kl_elem(float mean, float ls_raw) {
-  const float sd = expf(fminf(fmaxf(ls_raw, kTailLsMin), kTailLsMax));
-  return -0.5f * (1.0f + logf(sd * sd) - mean * mean - sd * sd);
-}
-// OSRL_SEED_GAUSS_NLL's bounded log-variance (PETS' soft clamp): softplus(x) = max(x, 0) + log1p(exp(-|x|)) and its slope
-__device__ __forceinline__ float seed_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float seed_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+// the element arithmetic is loss_terms.h's, which csrc/glue.hip's loss kernels (vae_loss_body, cpq_critic_loss_body,
+// cpq_cost_loss_body, cpq_actor_loss_kernel, bcq_critic_loss_kernel, gauss_head_bwd_kernel) and dyn_loss.hip call too:
+// the gradient has their bits.  (kEns is the member bound the host checks a seed against.)
 // element (r, c) of net e's dY; yv = that element of the net's output, yrow = the output row; l0 collects the
 // statistic's terms of valid elements
 template <class SR>
@@ -780,41 +759,32 @@ __device__ __forceinline__ float seed_dy(SR s, const int e, const int r, const i
   const int kind = s.kind;
   if (kind == OSRL_SEED_MSE) {
     const float d = yv - s.x0[(size_t)r * NL + c];
-    if (ok) l0 += d * d;
-    return 2.0f * d * s.scale;
+    if (ok) l0 += sq_term(d);
+    return sq_grad(d, s.scale);
   }
   if (kind == OSRL_SEED_CPQ_CRITIC) {
-    const float qt = seed_min(s.a, s.n_a, rows, r);
-    const float qct = seed_min(s.b, s.n_b, rows, r);
-    const float backup = s.x0[r] + s.gamma * (1.0f - s.x1[r]) * (qct <= s.thres ? 1.0f : 0.0f) * qt;  // cpq.py:145-146
-    const float d = yv - backup;
-    if (ok) l0 += d * d;
-    return 2.0f * d * s.scale;
+    const float qt = min_members(s.a, s.n_a, rows, r);
+    const float qct = min_members(s.b, s.n_b, rows, r);
+    const float d = yv - cpq_critic_backup(s.x0[r], s.x1[r], qt, qct, s.gamma, s.thres);
+    if (ok) l0 += sq_term(d);
+    return sq_grad(d, s.scale);
   }
   if (kind == OSRL_SEED_CPQ_COST) {
-    const float backup = s.x0[r] + s.gamma * seed_min(s.a, s.n_a, rows, r);  // cpq.py:161
-    const float d = yv - backup;
-    if (ok) l0 += d * d;
-    return 2.0f * d * s.scale;
+    const float d = yv - cpq_cost_backup(s.x0[r], min_members(s.a, s.n_a, rows, r), s.gamma);
+    if (ok) l0 += sq_term(d);
+    return sq_grad(d, s.scale);
   }
   if (kind == OSRL_SEED_CPQ_ACTOR) {
-    float qv[kSeedEns];
-    seed_members(s.a, s.n_a, rows, r, qv);
-    float qm = qv[0];
-    int am = 0;
-#pragma unroll
-    for (int k = 1; k < kSeedEns; ++k) {
-      const bool lt = k < s.n_a && qv[k] < qm;
-      qm = lt ? qv[k] : qm;
-      am = lt ? k : am;
-    }
-    const float mask = seed_min(s.b, s.n_b, rows, r) <= s.thres ? 1.0f : 0.0f;
+    float qv[kEns], qm;
+    int am;
+    load_members(s.a, s.n_a, rows, r, qv);
+    cpq_actor_argmin(qv, s.n_a, qm, am);
+    const float mask = cpq_actor_mask(min_members(s.b, s.n_b, rows, r), s.thres);
     if (ok && e == 0) l0 -= mask * qm;
     return e == am ? -mask * s.scale : 0.f;
   }
-  if (kind == OSRL_SEED_BCQ_CRITIC) {  // glue.hip bcq_critic_loss_kernel, term for term (bcql.py:138-150)
+  if (kind == OSRL_SEED_BCQ_CRITIC) {  // the loops of glue.hip's bcq_critic_loss_kernel (bcql.py:138-150)
     const int ns = s.n_samples, nr = rows * ns;
-    const float lmbda = s.thres;
     const float* __restrict__ q2p = s.a + (size_t)s.n_a * nr;
     float best = -INFINITY;
     for (int j = 0; j < ns; ++j) {
@@ -823,41 +793,36 @@ __device__ __forceinline__ float seed_dy(SR s, const int e, const int r, const i
       for (int k = 1; k < s.n_a; ++k) q1 = fminf(q1, s.a[(size_t)k * nr + i]);
       float q2 = q2p[i];
       for (int k = 1; k < s.n_b; ++k) q2 = fminf(q2, q2p[(size_t)k * nr + i]);
-      const float v = lmbda * fminf(q1, q2) + (1.0f - lmbda) * fmaxf(q1, q2);
-      best = fmaxf(best, v);
+      best = fmaxf(best, bcq_mix(q1, q2, s.thres));
     }
     const float nd = s.x1 ? (1.0f - s.x1[r]) : 1.0f;
-    const float backup = s.x0[r] + s.gamma * nd * best;
-    const float d = yv - backup;
-    if (ok) l0 += d * d;
-    return 2.0f * d * s.scale;
+    const float d = yv - bcq_backup(s.x0[r], nd, best, s.gamma);
+    if (ok) l0 += sq_term(d);
+    return sq_grad(d, s.scale);
   }
   if (kind == OSRL_SEED_FQE) {  // net e against its own target member (e is uniform per workgroup: no divergence)
     const float* __restrict__ xs = e < s.n_a ? s.x0 : s.b;
-    const float backup = xs[r] + s.gamma * (1.0f - s.x1[r]) * s.a[(size_t)e * rows + r];
-    const float d = yv - backup;
-    if (ok) l0 += d * d;  // (the caller moves a cost net's sum to the second partial)
-    return 2.0f * d * s.scale;
+    const float d = yv - fqe_backup(xs[r], s.x1[r], s.a[(size_t)e * rows + r], s.gamma);
+    if (ok) l0 += sq_term(d);  // (the caller moves a cost net's sum to the second partial)
+    return sq_grad(d, s.scale);
   }
   if (kind == OSRL_SEED_GAUSS_NLL) {  // NL = 2 od + 3: (od + 1 means | cost | od + 1 raw log-variances); x0 [rows, od + 2]
     const int no = (NL + 1) >> 1;     // od + 2: the target's width and the first log-variance column
     if (c == no - 1) {                // the raw cost: MSE
       const float d = yv - s.x0[(size_t)r * no + c];
-      if (ok) l0 += d * d;
-      return 2.0f * d * s.scale;
+      if (ok) l0 += sq_term(d);
+      return sq_grad(d, s.scale);
     }
     const int k = c < no ? c : c - no;
     const float lo = s.gamma, hi = s.thres;  // the log-variance bounds
     const float raw = yrow[no + k];
-    const float lv1 = hi - seed_softplus(hi - raw);
-    const float lv = lo + seed_softplus(lv1 - lo);
+    const LogVar v = gauss_nll_logvar(raw, lo, hi);
     const float d = yrow[k] - s.x0[(size_t)r * no + k];
-    const float iv = expf(-lv);
     if (c < no) {
-      if (ok) l0 += d * d * iv + lv;
-      return 2.0f * d * iv * s.scale;
+      if (ok) l0 += gauss_nll_term(d, v);
+      return gauss_nll_g_mean(d, v, s.scale);
     }
-    return (1.0f - d * d * iv) * seed_sigmoid(hi - raw) * seed_sigmoid(lv1 - lo) * s.scale;
+    return gauss_nll_g_raw(d, raw, v, lo, hi, s.scale);
   }
   // OSRL_SEED_GAUSS_HEAD: yrow = (mu | log_std) of the row, NL = 2 ad
   const int ad = NL >> 1;
@@ -865,23 +830,14 @@ __device__ __forceinline__ float seed_dy(SR s, const int e, const int r, const i
   const float t = s.tanh_u[(size_t)r * ad + j];
   const float lsr = yrow[ad + j];
   const float ev = s.eps[(size_t)r * ad + j];
-  float dv[kSeedEns];
+  float dv[kEns];
 #pragma unroll
-  for (int k = 0; k < kSeedEns; ++k) dv[k] = s.a[((size_t)(k < s.n_a ? k : 0) * rows + r) * ad + j];
+  for (int k = 0; k < kEns; ++k) dv[k] = s.a[((size_t)(k < s.n_a ? k : 0) * rows + r) * ad + j];
   float da = 0.f;
 #pragma unroll
-  for (int k = 0; k < kSeedEns; ++k) da += k < s.n_a ? dv[k] : 0.f;
-  const float du = da * s.max_action * (1.0f - t * t);
-  const float ls = fminf(fmaxf(lsr, kSeedLogStdMin), kSeedLogStdMax);
-  const bool inside = lsr >= kSeedLogStdMin && lsr <= kSeedLogStdMax;
-  return c < ad ? du : (inside ? du * ev * expf(ls) : 0.f);
-}
-// device-coherent words for the statistic's partials (workgroups on different XCDs exchange them inside the launch)
-__device__ __forceinline__ void coh_put(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float coh_get(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (int k = 0; k < kEns; ++k) da += k < s.n_a ? dv[k] : 0.f;
+  const float du = gauss_head_du(da, s.max_action, t);
+  return c < ad ? du : gauss_head_dls(du, lsr, ev);
 }
 
 template <int NRB, int NCB, int NW, class AR>
@@ -955,7 +911,7 @@ __device__ __forceinline__ void mlp_bwd_dz_body(AR a, const int e, const int til
           const int r = idx / Lz, k = idx - r * Lz;
           const int gr = row0 + r;
           const int grc = gr < rows ? gr : rows - 1;
-          const float kv = seed_kl_elem(hd[(size_t)grc * 2 * Lz + k], hd[(size_t)grc * 2 * Lz + Lz + k]);
+          const float kv = kl_elem(hd[(size_t)grc * 2 * Lz + k], hd[(size_t)grc * 2 * Lz + Lz + k]);
           l1 += gr < rows ? kv : 0.f;
         }
       }
@@ -1119,13 +1075,7 @@ __device__ __forceinline__ void mlp_bwd_dz_body(AR a, const int e, const int til
     // the logged statistic: the last workgroup to get here sums every tile's partials in a fixed order (each lane a
     // contiguous chunk, lanes by the butterfly, waves in order).  Wait-free: a workgroup is the last one or leaves.
     const int n_part = a.net.n_nets * ((rows + BM - 1) / BM);
-    if (tid == 0) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this tile's partials are acknowledged
-      const unsigned seen = __hip_atomic_fetch_add(a.seed.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = seen == (unsigned)n_part - 1;
-      if (last) __hip_atomic_store(a.seed.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_seed_last = last;
-    }
+    if (tid == 0) s_seed_last = arrive_last(a.seed.counter, n_part);  // (this tile's partials acknowledged first)
     __syncthreads();
     if (s_seed_last) {
       const int per = (n_part + 64 * NW - 1) / (64 * NW);
@@ -2570,19 +2520,19 @@ static bool seed_ok(const osrl_mlp_seed_t* s, const osrl_mlp_t* net, const osrl_
   switch (s->kind) {
     case OSRL_SEED_MSE: return s->x0 && (!s->kl_head || s->kl_L >= 1);
     case OSRL_SEED_CPQ_CRITIC:
-      return NL == 1 && s->a && s->b && s->x0 && s->x1 && s->n_a >= 1 && s->n_a <= kSeedEns && s->n_b >= 1 && s->n_b <= kSeedEns;
-    case OSRL_SEED_CPQ_COST: return NL == 1 && s->a && s->x0 && s->n_a >= 1 && s->n_a <= kSeedEns;
+      return NL == 1 && s->a && s->b && s->x0 && s->x1 && s->n_a >= 1 && s->n_a <= kEns && s->n_b >= 1 && s->n_b <= kEns;
+    case OSRL_SEED_CPQ_COST: return NL == 1 && s->a && s->x0 && s->n_a >= 1 && s->n_a <= kEns;
     case OSRL_SEED_CPQ_ACTOR:
-      return NL == 1 && s->a && s->b && s->n_a >= 1 && s->n_a <= kSeedEns && s->n_b >= 1 && s->n_b <= kSeedEns;
+      return NL == 1 && s->a && s->b && s->n_a >= 1 && s->n_a <= kEns && s->n_b >= 1 && s->n_b <= kEns;
     case OSRL_SEED_BCQ_CRITIC:
       return NL == 1 && s->a && s->x0 && s->n_a >= 1 && s->n_b >= 1 && s->n_samples >= 1;
     case OSRL_SEED_FQE:
-      return NL == 1 && s->a && s->b && s->x0 && s->x1 && s->n_a >= 1 && s->n_a <= kSeedEns && s->n_b >= 1 && s->n_b <= kSeedEns &&
+      return NL == 1 && s->a && s->b && s->x0 && s->x1 && s->n_a >= 1 && s->n_a <= kEns && s->n_b >= 1 && s->n_b <= kEns &&
              s->n_a + s->n_b == net->n_nets && s->kl_head == nullptr;
     case OSRL_SEED_GAUSS_NLL:
       return (NL & 1) == 1 && NL >= 5 && s->x0 && s->gamma < s->thres && s->kl_head == nullptr;
     case OSRL_SEED_GAUSS_HEAD:
-      return (NL & 1) == 0 && net->n_nets == 1 && s->a && s->eps && s->tanh_u && s->n_a >= 1 && s->n_a <= kSeedEns && !s->partials;
+      return (NL & 1) == 0 && net->n_nets == 1 && s->a && s->eps && s->tanh_u && s->n_a >= 1 && s->n_a <= kEns && !s->partials;
     default: return false;
   }
 }

@@ -3,6 +3,7 @@
 // with the optimizer step applied by a tile's last split (mlp_dwt_adam_kernel), and one-wave-per-tile for token-matrix
 // row counts (mlp_dw_big_kernel).  Split from mlp.hip in round 4 (compile time); design notes at the kernels.
 #include "dwt.h"
+#include "dev_util.h"
 #include "adam.h"
 #include "trace.h"
 
@@ -206,14 +207,6 @@ struct DwAdamArgs {
   int32_t rows, pad_;
 };
 
-// device-coherent slab words (see the exchange in mlp_dwt_adam_body)
-__device__ __forceinline__ void slab_put(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float slab_get(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 template <int T, class AR>
 __device__ __forceinline__ void mlp_dwt_adam_body(AR a) {
   extern __shared__ __attribute__((aligned(16))) float red[];  // [4][16T][16T+1] partials + [4][16T] bias partials
@@ -275,11 +268,11 @@ __device__ __forceinline__ void mlp_dwt_adam_body(AR a) {
       for (int j = 0; j < PER; ++j) {
         const int off = offl[j];
         const float v = ((red[off] + red[TW * LD + off]) + red[2 * TW * LD + off]) + red[3 * TW * LD + off];
-        if (ok[j]) slab_put(slab + w[j], v);
+        if (ok[j]) coh_put(slab + w[j], v);
       }
       if (has_b) {
         const float* db = red + 4 * TW * LD;
-        slab_put(slab + wb, ((db[tid] + db[TW + tid]) + db[2 * TW + tid]) + db[3 * TW + tid]);
+        coh_put(slab + wb, ((db[tid] + db[TW + tid]) + db[2 * TW + tid]) + db[3 * TW + tid]);
       }
       // The slab tile is exchanged between workgroups on different XCDs (each with its own L2) INSIDE the launch.  The
       // textbook form -- release fence (write back the whole L2), count, acquire fence (invalidate the whole L2) -- cost
@@ -289,13 +282,7 @@ __device__ __forceinline__ void mlp_dwt_adam_body(AR a) {
       // XCDs share), the arrival is counted once every wave's stores are acknowledged, and no cache is touched.
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) {
-        unsigned* c = a.counters + a.tile_ids[item];
-        const unsigned seen = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = seen == (unsigned)nsp - 1;
-        if (last) __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // every split signed in: re-arm
-        s_last = last;
-      }
+      if (tid == 0) s_last = arrive_last_acked(a.counters + a.tile_ids[item], nsp);  // (every wave waited above)
       __syncthreads();
       if (!s_last) return;
     }
@@ -331,22 +318,22 @@ __device__ __forceinline__ void mlp_dwt_adam_body(AR a) {
 #pragma unroll
         for (int j = 0; j < PER; ++j)
 #pragma unroll
-          for (int q = 0; q < KS; ++q) sl[j][q] = slab_get(slabs + (size_t)(q < nsp ? q : 0) * stride + w[j]);
+          for (int q = 0; q < KS; ++q) sl[j][q] = coh_get(slabs + (size_t)(q < nsp ? q : 0) * stride + w[j]);
 #pragma unroll
-        for (int q = 0; q < KS; ++q) sb[q] = slab_get(slabs + (size_t)(q < nsp ? q : 0) * stride + wb);
+        for (int q = 0; q < KS; ++q) sb[q] = coh_get(slabs + (size_t)(q < nsp ? q : 0) * stride + wb);
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
           g[j] = sl[j][0];
 #pragma unroll
           for (int q = 1; q < KS; ++q)
             if (q < nsp) g[j] += sl[j][q];
-          for (int q = KS; q < nsp; ++q) g[j] += slab_get(slabs + (size_t)q * stride + w[j]);
+          for (int q = KS; q < nsp; ++q) g[j] += coh_get(slabs + (size_t)q * stride + w[j]);
         }
         gb = sb[0];
 #pragma unroll
         for (int q = 1; q < KS; ++q)
           if (q < nsp) gb += sb[q];
-        for (int q = KS; q < nsp; ++q) gb += slab_get(slabs + (size_t)q * stride + wb);
+        for (int q = KS; q < nsp; ++q) gb += coh_get(slabs + (size_t)q * stride + wb);
       };
       // (80 x 80 tiles carry 25 elements per lane: 8 slabs each in flight on top of their state would spill)
       if (nsp <= 4 || PER > 16)

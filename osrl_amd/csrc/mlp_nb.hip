@@ -2,6 +2,7 @@
 // Split from mlp.hip (round 4) so that the two units compile side by side; design notes at the kernel below and in
 // mlp.hip's header.
 #include "mlp_common.h"
+#include "loss_terms.h"
 #include "trace.h"
 
 namespace {
@@ -39,7 +40,6 @@ struct NbArgs {
   // no activation write-back, no 16-column MFMA pass for one real column, no partial tiles, two barriers fewer
   int32_t fuse_head;
 };
-constexpr float kNbLsMin = -4.0f, kNbLsMax = 15.0f;  // net.py:325 (== kVaeLsMin / kVaeLsMax of glue.hip)
 
 #ifndef OSRL_NB8_ADB
 #define OSRL_NB8_ADB false  // 8-wave form: activation fragments single buffered (see nb_mm)
@@ -696,7 +696,7 @@ __device__ __forceinline__ void mlp_fwd_nb_body(AR a) {
       }
     }
     if (a.kl && e == 0) {
-      // the KL rows of cpq.py:178-182 (glue.hip vae_kl_rows_kernel, term for term) from the partial tiles still in LDS:
+      // the KL rows of cpq.py:178-182 (loss_terms.h kl_elem, as glue.hip's vae_kl_rows_kernel) from the partial tiles still in LDS:
       // one launch and one read of the head off the side chain's tail
       const int Lz = a.kl_L;
       for (int r = tid; r < BM; r += 64 * NW) {
@@ -710,8 +710,7 @@ __device__ __forceinline__ void mlp_fwd_nb_body(AR a) {
           float s_ = 0.f;
           for (int k = 0; k < Lz; ++k) {
             const float mean = outv(k);
-            const float sd = expf(fminf(fmaxf(outv(Lz + k), kNbLsMin), kNbLsMax));
-            s_ += -0.5f * (1.0f + logf(sd * sd) - mean * mean - sd * sd);
+            s_ += kl_elem(mean, outv(Lz + k));
           }
           a.kl[grow(r)] = s_ / (float)Lz;
         }

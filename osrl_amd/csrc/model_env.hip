@@ -120,13 +120,6 @@ struct LdsGauss {
   int step[kTile];       // the episode's own step: the noise is keyed by it
 };
 
-// PETS' soft clamp of a raw log-variance to (lo, hi); softplus(x) = max(x, 0) + log1p(exp(-|x|))
-__device__ __forceinline__ float softplus_abs(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float bounded_logvar(float raw, float lo, float hi) {
-  const float lv1 = hi - softplus_abs(hi - raw);
-  return lo + softplus_abs(lv1 - lo);
-}
-
 struct Lds {
   __attribute__((aligned(16))) float xin[kTile * kS];     // the staged input rows: every member's layer 0 reads them
   __attribute__((aligned(16))) float buf[2][kTile * kS];  // a member's activations, ping-pong

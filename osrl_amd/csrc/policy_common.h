@@ -13,6 +13,7 @@
 #include <chrono>
 
 #include "../../include/osrl_amd.h"
+#include "loss_terms.h"
 #include "philox.h"
 
 namespace {
@@ -20,9 +21,7 @@ namespace {
 // LDS row widths (floats) of the MLP act kernels' two instantiations: 512 for nets whose layers are all <= 512 wide
 // (every net of the fused-kernel widths), 1024 = OSRL_MAX_WIDTH for the wider ones (twice the LDS)
 constexpr int kW = 512, kWideW = OSRL_MAX_WIDTH;
-constexpr float kLogStdMin = -20.0f, kLogStdMax = 2.0f;  // net.py:148-149
 
-__device__ __forceinline__ float softplus(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ float act_fwd(int act, float x) {
   if (act == OSRL_ACT_RELU) return fmaxf(x, 0.0f);
   if (act == OSRL_ACT_TANH) return tanhf(x);

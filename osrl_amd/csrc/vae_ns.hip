@@ -30,6 +30,8 @@
 
 #include "../../include/osrl_amd.h"
 #include "argmem.h"
+#include "dev_util.h"
+#include "loss_terms.h"
 #include "trace.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -46,7 +48,6 @@ constexpr int kSW = 32;                      // slab row width (floats)
 constexpr int kSL = 36;                      // row stride of the prologue's [48][<= 32] row tile
 constexpr int kPL = 68;                      // row stride of a wave's private [48][64] A region
 constexpr int kNKW = 7;                      // k-steps per wave, upper bound (H <= 448)
-constexpr float kLsMin = -4.0f, kLsMax = 15.0f;  // net.py:325
 
 // Wave priority (mlp_common.h OSRL_CHAIN_PRIO): these launches ARE the latency chain's VAE phase and run beside the N*B-row
 // cost-critic launch of the side branch (priority 0) on every CU
@@ -84,12 +85,6 @@ struct NsArgs {
 __device__ __forceinline__ int r16(int x) { return (x + 15) & ~15; }
 __device__ __forceinline__ void mfma(f32x4& acc, float a, float b) {
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void coh_put(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float coh_get(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // blockIdx -> (row tile, column group): ids with the same (id % 8) run on one XCD, so each XCD gets WHOLE row tiles (the
@@ -413,7 +408,7 @@ __device__ __forceinline__ void gen_body(AR a) {
         }
         // (explicit fma: the by-value kernel and its descriptor-in-memory twin must take the SAME contraction decisions
         // -- graph replays and eager steps are compared bit for bit)
-        const float zv = __builtin_fmaf(expf(fminf(fmaxf(ls, kLsMin), kLsMax)), a.eps[(size_t)grc * L + j], mean);
+        const float zv = __builtin_fmaf(expf(fminf(fmaxf(ls, kVaeLsMin), kVaeLsMax)), a.eps[(size_t)grc * L + j], mean);
         sv = zv;
         if (w0) {
           a.enc_head[(size_t)gr * 2 * L + j] = mean;
@@ -423,7 +418,7 @@ __device__ __forceinline__ void gen_body(AR a) {
         }
       }
     } else if (MODE == MODE_DEC_BWD) {
-      if (kk < ad) {  // u = max_action tanh(.), dY of the MSE, dZ2 = dY max_action (1 - tanh^2)  (== OSRL_SEED_MSE)
+      if (kk < ad) {  // u = max_action tanh(.), dY of the MSE, dZ2 = dY max_action (1 - tanh^2)  (loss_terms.h, as OSRL_SEED_MSE)
         float up = a.db2[kk];
         float pu[5];
 #pragma unroll
@@ -433,16 +428,18 @@ __device__ __forceinline__ void gen_body(AR a) {
         const float y = a.max_action * tanhf(up);
         const float d = y - a.act[(size_t)grc * ad + kk];
         const float tt = y * (1.0f / a.max_action);
-        sv = 2.0f * d * (a.inv_rows / (float)ad) * a.max_action * __builtin_fmaf(-tt, tt, 1.0f);
+        sv = sq_grad(d, a.inv_rows / (float)ad) * a.max_action * __builtin_fmaf(-tt, tt, 1.0f);
         if (w0) {
-          l0 = __builtin_fmaf(d, d, l0);
+          l0 = __builtin_fmaf(d, d, l0);  // (explicit fma, as the KL term below: sq_term's d * d + l0 is not contracted)
           a.dec_u[(size_t)gr * ad + kk] = y;
           a.dec_dz2[(size_t)gr * ad + kk] = sv;
         }
       }
       if (kk < L && w0) {  // the KL term of the logged loss (cpq.py:128)
+        // (this launch's KL term is written with explicit fmas -- its by-value and descriptor twins must take the same
+        // contraction decisions -- so its bits are not kl_elem's, whose sum is left uncontracted: it stays here)
         const float mean = a.enc_head[(size_t)gr * 2 * L + kk];
-        const float sd = expf(fminf(fmaxf(a.enc_head[(size_t)gr * 2 * L + L + kk], kLsMin), kLsMax));
+        const float sd = expf(fminf(fmaxf(a.enc_head[(size_t)gr * 2 * L + L + kk], kVaeLsMin), kVaeLsMax));
         l1 += -0.5f * (__builtin_fmaf(-sd, sd, __builtin_fmaf(-mean, mean, 1.0f + logf(sd * sd))));
       }
     } else {
@@ -457,9 +454,9 @@ __device__ __forceinline__ void gen_body(AR a) {
         const float mean = a.enc_head[(size_t)grc * 2 * L + k];
         const float lsr = a.enc_head[(size_t)grc * 2 * L + L + k];
         const float ev = a.eps[(size_t)grc * L + k];
-        const float sd = expf(fminf(fmaxf(lsr, kLsMin), kLsMax));
+        const float sd = expf(fminf(fmaxf(lsr, kVaeLsMin), kVaeLsMax));
         const float c = a.beta * a.inv_rows / (float)L;
-        const bool inside = lsr >= kLsMin && lsr <= kLsMax;
+        const bool inside = lsr >= kVaeLsMin && lsr <= kVaeLsMax;
         const float t_kl = c * (sd - 1.0f / sd);
         sv = kk < L ? __builtin_fmaf(c, mean, g) : (inside ? __builtin_fmaf(g, ev, t_kl) * sd : 0.f);
         if (w0) a.enc_dz2[(size_t)gr * 2 * L + kk] = sv;
@@ -639,14 +636,8 @@ __device__ __forceinline__ void gen_body(AR a) {
   NS_STAMP(11);
   if (MODE == MODE_DEC_BWD && cg == 0) {
     // the logged loss: the last first-column-group workgroup to get here sums every tile's partials in tile order
-    // (wait-free: a workgroup is the last one or leaves; protocol of mlp.hip's seeded backward)
-    if (tid == 0) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned seen = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = seen == (unsigned)a.row_tiles - 1;
-      if (last) __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = last;
-    }
+    // (dev_util.h arrive_last: a workgroup is the last one or leaves)
+    if (tid == 0) s_last = arrive_last(a.counter, a.row_tiles);
     __syncthreads();
     if (s_last && wave == 0) {
       const int per = (a.row_tiles + 63) / 64;

@@ -527,7 +527,7 @@ def test_seeded_backward_launches_equal_the_loss_launches(name):
 
 @pytest.mark.parametrize("num_q,num_qc", [(5, 2), (2, 5)])
 def test_seeded_path_declines_five_member_ensembles(num_q, num_qc):
-    """The seeded backward launches take at most 4 members per ensemble (``kSeedEns``, csrc/mlp.hip: the host check
+    """The seeded backward launches take at most 4 members per ensemble (``kEns``, csrc/loss_terms.h: the host check
     refuses a seed with more).  With SEEDS on, a 5-member CPQ ensemble therefore keeps the loss launches -- the general
     (counted-loop) form of the CPQ loss kernels, which tests/test_gpu_loss_kernels.py compares with fp64 -- and the step
     still agrees with the oracle."""

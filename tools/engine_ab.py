@@ -8,7 +8,8 @@ For each case (tests/cases.py) a fresh model is stepped along
   sequential  CPQ: the captured step with ``parallel_branches=False``
   graph_plan  BC: the captured six-launch plan (``direct=False``; "graph" takes the directly launched one-launch step)
 
-and a SHA-256 is written per group buffer (p / m / v / tgt), per scalar-state tensor and of ``read_stats_many`` over all
+and, for the dynamics fit (the shape and data of tests/dyn_ensemble_cases.py TRAIN, raw log-variances on both sides of both
+bounds), 6 ``step_replay`` calls on a store along graph and eager; a SHA-256 is written per group buffer (p / m / v / tgt), per scalar-state tensor and of ``read_stats_many`` over all
 steps.  Everything is seeded (the cases' numpy streams, store seeds 7 / 3, engine seed 0), so two trees that issue the
 same launches give the same file: run it on both and diff.  The two CDT cases are the exception: the CDT step's
 timestep-embedding scatter accumulates with fp32 atomics, so their digests differ between two runs of ONE tree -- run the
@@ -28,7 +29,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 CASES = ["bc_small", "cpq_small", "bcql_pid", "bearl_lap", "coptidice_kl", "cdt_small", "cdt_det",
-         "cpq_wide", "bcql_wide", "bearl_wide", "coptidice_wide"]
+         "cpq_wide", "bcql_wide", "bearl_wide", "coptidice_wide", "dyn_mse", "dyn_gauss", "dyn_boot_elites"]
+DYN_CASES = {"dyn_mse": dict(), "dyn_gauss": dict(probabilistic=True),
+             "dyn_boot_elites": dict(probabilistic=True, bootstrap=True, num_elites=2)}
 DEV = "cuda:0"
 STEPS, PIPE_STEPS, PIPE_SPG = 6, 8, 4
 
@@ -113,6 +116,35 @@ def run_cdt(c) -> dict:
     return out
 
 
+def run_dyn(kw) -> dict:
+    import numpy as np
+    import torch
+    import dyn_ensemble_cases as DC
+    import gauss_dynamics_cases as GC
+    from osrl_amd.algorithms import Dynamics, DynamicsTrainer
+    from osrl_amd.common.replay import ReplayStore
+    T = DC.TRAIN
+    if kw.get("bootstrap"):
+        kw = dict(kw, boot_seed=DC.BOOT_SEED)
+    data = DC.transitions(T["B"] * T["steps"] + 213, T["od"], T["ad"])
+    out = {}
+    for path, use_graph in (("graph", True), ("eager", False)):
+        torch.manual_seed(9)
+        m = Dynamics(T["od"], T["ad"], list(T["hidden"]), num_models=T["M"], device=DEV, **kw)
+        store = ReplayStore(data, torch.device(DEV), seed=5)
+        m.fit_normalizer(store)
+        if kw.get("probabilistic"):
+            sd = GC.with_logvar_rows({k: v.detach().cpu().numpy() for k, v in m.state_dict().items()}, T["od"], T["M"])
+            m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()})
+        DynamicsTrainer(m, lr=T["lr"], stats_mode="none")
+        eng = m.engine(T["B"])
+        eng.attach_replay(store)
+        for _ in range(STEPS):
+            eng.step_replay(use_graph=use_graph)
+        out[path] = digests(m, eng, STEPS)
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--case", action="append", choices=CASES, help="repeatable; default: all of them")
@@ -124,7 +156,9 @@ def main() -> None:
            "seeds": {"cases": "tests/cases.py", "synthetic_transitions": 7, "replay_store": 3, "engine": 0},
            "steps": {"graph": STEPS, "eager": STEPS, "pipelined": [PIPE_STEPS, PIPE_SPG]}, "cases": {}}
     for name in a.case or CASES:
-        if name in CDT_CASES:
+        if name in DYN_CASES:
+            res["cases"][name] = run_dyn(DYN_CASES[name])
+        elif name in CDT_CASES:
             res["cases"][name] = run_cdt(CDT_CASES[name])
         else:
             res["cases"][name] = run_mlp({**MLP, **BEARL_CASES, **COPTIDICE_CASES}[name])
