@@ -1492,6 +1492,29 @@ int osrl_model_env_branch(const float* table, int64_t n_rows, const int64_t* n_r
                           int32_t state_dim, const uint64_t* seed, uint32_t episode_base, float* state, float* obs,
                           int32_t obs_ld, float* acc, float* unc, float* disc /* [E,4] */,
                           int64_t* start_rows /* [E] */, int32_t episodes, void* stream);
+/* Planning at act time (plan.hip, engine/mpc.py ModelPlanner): `slots` real states, `candidates` imagined episodes each;
+ * episode e = n * candidates + k is candidate k of slot n.
+ * osrl_plan_fanout is the reset of a planning run, in osrl_model_env_branch's place: episode e receives states[n] as its
+ * model state and as obs[e, :state_dim] (columns beyond state_dim are left alone), zeros in acc[e] and unc[e], (0, 0, 1, 0)
+ * in disc[e] and, where halt_step is given, halt_step[e] = -1.
+ * osrl_plan_select chooses per slot among its candidates after `horizon` recorded steps.  actions: the recorder's table
+ * (row e * horizon is candidate e's first action); J_k = disc[e][0] (discounted penalised return), C_k = disc[e][1]
+ * (discounted cost, in the recorder's cost_scale units); T = *temperature (device memory: a captured launch follows it).
+ *   valid k: neither J_k nor C_k is a NaN;   F = {valid k : C_k <= budget[n]};   n_feasible[n] = |F|.
+ *   F non-empty:  k* = argmax_F J, ties to the lowest k.
+ *   F empty:      k* = argmin over the valid k of C, ties to the larger J, then to the lower k;  no valid k: k* = 0.
+ *   chosen[n] = k*.  action[n] = row k*, bit for bit -- unless F is non-empty and T > 0 (MPPI):
+ *     w_k = (J_k == J_k* ? 1 : expf((J_k - J_k*) / T)) on F,  action[n][j] = (float)(sum_k w_k a0_k[j] / sum_k w_k), both sums
+ *     in fp64 over F in ascending k by one thread (no floating-point atomics): the same inputs give the same bits.
+ * 1 <= candidates <= OSRL_PLAN_MAX_CANDIDATES, slots * candidates < 2^31; -1 before any launch otherwise. */
+#define OSRL_PLAN_MAX_CANDIDATES 1024
+int osrl_plan_fanout(const float* states /* [slots, state_dim] */, int32_t slots, int32_t candidates, int32_t state_dim,
+                     float* state, float* obs, int32_t obs_ld, float* acc, float* unc, float* disc /* [E,4] */,
+                     int32_t* halt_step /* [E] or NULL */, void* stream);
+int osrl_plan_select(const float* actions /* [E * horizon, action_dim] */, int32_t horizon, const float* disc /* [E,4] */,
+                     const float* budget /* [slots] */, const float* temperature /* [1] */, int32_t slots,
+                     int32_t candidates, int32_t action_dim, float* action /* [slots, action_dim] */,
+                     int32_t* chosen /* [slots] */, int32_t* n_feasible /* [slots] */, void* stream);
 /* The train step's preparation (engine/dynamics.py): xs[b] = (obs[b] - mu_s) / sd_s  [rows, state_dim];
  * target[b] = {(nobs[b] - obs[b] - mu_d) / sd_d, (rew[b] - mu_r) / sd_r, cost[b]}  [rows, state_dim + 2]. */
 int osrl_dyn_prepare(const float* obs, const float* nobs, const float* rew, const float* cost, const float* mu_s,

@@ -191,6 +191,7 @@ class ModelEnvT(C.Structure):  # osrl_model_env_t
 
 
 MODEL_ENV_UNC = {"disagreement": 0, "max_std": 1}  # OSRL_MODEL_ENV_UNC_*
+PLAN_MAX_CANDIDATES = 1024  # OSRL_PLAN_MAX_CANDIDATES: candidates per slot of osrl_plan_select
 
 
 class ModelEnvGaussT(C.Structure):  # osrl_model_env_gauss_t
@@ -297,6 +298,8 @@ PROTOTYPES = {
                                           _vp, _vp, _i32, _vp],
     "osrl_collect_compact": [_P(CollectT), _vp, _P(CollectT), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "osrl_model_env_branch": [_vp, _i64, _vp, _i64, _i32, _vp, _u32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
+    "osrl_plan_fanout": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "osrl_plan_select": [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "osrl_dyn_prepare": [_vp] * 10 + [_i32, _i32, _vp, _vp, _vp],
     "osrl_dyn_member_loss": [_P(DynLossT), _vp],
     "osrl_env_collect": [_P(EnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _i32, _vp],

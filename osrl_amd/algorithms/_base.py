@@ -179,6 +179,35 @@ class RolloutMixin:
         return cached(self, "_model_collector", key,
                       lambda: ModelCollector(self.model, menv, *key[1:], use_graph=getattr(self, "use_graph", True)))
 
+    def planner(self, menv, num_envs, horizon, noise_std=0.3, gamma=1.0, temperature=0.0, seed=0):
+        """A ``ModelPlanner`` (engine/mpc.py) of the current policy on the ``ModelVecEnv`` ``menv``: policy-guided
+        shooting at act time.  ``menv.E == num_envs * K``: each of the ``num_envs`` real states handed to
+        ``planner.act(states, cost_budget)`` fans out into K imagined episodes of ``horizon`` steps, candidate 0 following
+        the policy exactly, the others with ``a = clip(pi(s) + noise_std * eps)``; the action returned is the first
+        action of the candidate with the best ``gamma``-discounted penalised return among those whose discounted cost
+        (in ``cost_scale`` units) stays within the budget, of the cheapest when none does, or with ``temperature > 0``
+        the softmax-weighted mean of the feasible first actions.  The policy, the appended cost limit of BC multi-task
+        and the cost scale are ``evaluate``'s.  Anything but a ``ModelVecEnv``: TypeError; a shape that does not fit:
+        ValueError, before anything is launched.  The planner is the caller's to keep: it is not cached."""
+        from ..engine.mpc import ModelPlanner, check_plan
+        check_plan(menv, num_envs, horizon, noise_std, temperature)
+        self._before_evaluate()
+        cs = self._cost_scale()
+        return ModelPlanner(self.model, menv, self.EVAL_KIND, 1.0 if cs is None else float(cs), self._eval_extra(),
+                            num_envs=num_envs, horizon=horizon, noise_std=noise_std, gamma=gamma,
+                            temperature=temperature, seed=seed, use_graph=getattr(self, "use_graph", True))
+
+    @torch.no_grad()
+    def evaluate_planned(self, planner, envs, eval_episodes, cost_limit):
+        """``evaluate`` with every action planned: ``eval_episodes`` episodes over the host (gym-style) environments
+        ``envs`` (``planner.num_envs`` of them) on the refill schedule, each policy call one ``planner.act`` in which a
+        slot's budget is what its episode has left of ``cost_limit`` (``max(cost_limit * cost_scale - cost so far, 0)``;
+        engine/act.py ``PlanRefillAdapter``).  Returns ``evaluate``'s (mean return, mean cost, mean length)."""
+        from ..engine.act import evaluate_planned
+        self._before_evaluate()
+        means, _ = evaluate_planned(planner, envs, eval_episodes, cost_limit, self.model.episode_len, self._cost_scale())
+        return self._scale_results(*means)
+
     @torch.no_grad()
     def rollout_many(self, envs, num_slots: Optional[int] = None, episode_ids=None):
         """``rollout`` on each of the host environments ``envs`` at once, in lockstep through

@@ -349,6 +349,12 @@ class CDTTrainer:
         return collect_cdt_batched(self, target_return=target_return, target_cost=target_cost, noise_std=noise_std,
                                    sample=sample, gamma=gamma, seed=seed, noise=noise, into=into)
 
+    def planner(self, *args, **kwargs):
+        """The MLP trainers' ``planner`` (engine/mpc.py) is not built for CDT: every candidate would need a window of its
+        own.  Always a TypeError."""
+        raise TypeError("CDTTrainer has no planner: policy-guided shooting needs one transformer window per candidate, "
+                        "which is out of scope; the five MLP trainers have planner() / evaluate_planned()")
+
     @torch.no_grad()
     def rollout(self, model: CDT, env, target_return: float, target_cost: float):
         """cdt.py:436-518: autoregressive rollout on a sliding window of the last seq_len steps.  With

@@ -14,7 +14,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libosrl_amd.so")
-SOURCES = ["mlp.hip", "linear_split.hip", "mlp_nb.hip", "mlp_nb64.hip", "mlp_dw.hip", "vae_ns.hip", "optim.hip", "rng.hip", "glue.hip", "cdt.hip", "cdt_grad.hip", "env.hip", "model_env.hip", "dyn_loss.hip", "compact.hip", "collect.hip", "cdt_collect.hip", "ingest.hip", "augment.hip", "bear.hip", "dice.hip", "act.hip", "act_vec.hip", "cdt_act.hip", "ipc.hip", "seq_ring.hip", "diag.hip"]
+SOURCES = ["mlp.hip", "linear_split.hip", "mlp_nb.hip", "mlp_nb64.hip", "mlp_dw.hip", "vae_ns.hip", "optim.hip", "rng.hip", "glue.hip", "cdt.hip", "cdt_grad.hip", "env.hip", "model_env.hip", "plan.hip", "dyn_loss.hip", "compact.hip", "collect.hip", "cdt_collect.hip", "ingest.hip", "augment.hip", "bear.hip", "dice.hip", "act.hip", "act_vec.hip", "cdt_act.hip", "ipc.hip", "seq_ring.hip", "diag.hip"]
 
 
 def _hipcc() -> str:

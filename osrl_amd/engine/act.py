@@ -639,6 +639,48 @@ class MLPRefillAdapter:
         return self.pol.step(obs, active=step, restart=restart, episode_ids=ids)[0]
 
 
+class PlanRefillAdapter:
+    """``rollout_refill`` over a ``ModelPlanner`` (engine/mpc.py): every policy call is one ``planner.act`` on the slots'
+    current states, each slot with the budget its episode has left -- ``max(cost_limit * cost_scale - cost so far, 0)``,
+    the cost so far accumulated here in the planner's ``cost_scale`` units.  A slot that idles is fed its last state and
+    its action is ignored.  ``budgets`` / ``restarts``: per call the ``[N]`` budgets passed and the slots that started an
+    episode in it (host copies, for inspection)."""
+
+    def __init__(self, planner, cost_limit, cost_scale=None):
+        self.planner, self.obs_dim, self.cost_scale = planner, planner.venv.state_dim, cost_scale
+        self.limit = float(cost_limit) * (1.0 if cost_scale is None else float(cost_scale))
+        self.so_far = np.zeros(planner.num_envs, np.float64)
+        self.budgets, self.restarts = [], []
+
+    def observe(self, o):
+        return o
+
+    def costs(self, info):
+        c = info["cost"] if self.cost_scale is None else info["cost"] * self.cost_scale
+        return c, c
+
+    def act(self, obs, reward, cost, step, restart, jobs):
+        self.so_far[restart] = 0.0
+        self.so_far[step] += cost[step]
+        budget = np.maximum(self.limit - self.so_far, 0.0).astype(np.float32)
+        self.budgets.append(budget.copy())
+        self.restarts.append(restart.copy())
+        return self.planner.act(obs, budget)
+
+
+def evaluate_planned(planner, envs, eval_episodes, cost_limit, episode_len, cost_scale=None):
+    """``eval_episodes`` episodes over the host environments ``envs`` on the refill schedule, every action planned
+    (``PlanRefillAdapter``).  Returns the means (return, cost sum, length), not rescaled, and the adapter."""
+    envs = list(envs)
+    if len(envs) != planner.num_envs:
+        raise ValueError(f"the planner holds {planner.num_envs} slots, evaluate_planned was given {len(envs)} environments")
+    if int(eval_episodes) < 1:
+        raise ValueError(f"eval_episodes {eval_episodes}: at least one episode")
+    adapter = PlanRefillAdapter(planner, cost_limit, cost_scale)
+    res = _refill(adapter, envs, list(range(int(eval_episodes))), episode_len, None)
+    return (np.mean(res.returns), np.mean(res.costs), np.mean(res.lengths)), adapter
+
+
 class MLPCollectAdapter(MLPRefillAdapter):
     """``MLPRefillAdapter`` with the exploration tail: a job is ``(q, episode id, sigma)``; ``noise`` (None, or ``[J,
     episode_len, act_dim]``) is injected instead of the draw keyed by ``(seed, episode id, step, column)``."""
