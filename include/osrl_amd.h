@@ -1515,6 +1515,31 @@ int osrl_plan_select(const float* actions /* [E * horizon, action_dim] */, int32
                      const float* budget /* [slots] */, const float* temperature /* [1] */, int32_t slots,
                      int32_t candidates, int32_t action_dim, float* action /* [slots, action_dim] */,
                      int32_t* chosen /* [slots] */, int32_t* n_feasible /* [slots] */, void* stream);
+/* The terminal value of a planning run (plan_value.hip): ONE launch between the last recorded step and osrl_plan_select.
+ * For every episode e < episodes, obs[e, :obs_dim] being the state it ended in:
+ *   a = pi(obs_e), the policy's deterministic action (MLP: net0's output; GAUSS: max_action * tanh(mu), eps = 0)
+ *   Q_m = critics[m]([obs_e, a]):  m < num_q the reward members, num_q <= m < 2 num_q the cost members
+ *   OSRL_PLAN_REDUCE_MEAN:         Vr = ((Q_0 + Q_1 + ..) / num_q) * r_mul, members added in ascending order; Vc alike * c_mul
+ *   OSRL_PLAN_REDUCE_PESSIMISTIC:  Vr = min_m Q_m * r_mul over the reward members,  Vc = max_m Q_m * c_mul over the cost members
+ *   last_V[e] = (Vr, Vc);   g = disc[e][2]  (gamma^(rows recorded), as the recording step left it)
+ *   halt_step == NULL or halt_step[e] < 0:  disc[e][0] = fmaf(g, Vr, disc[e][0]),      disc[e][1] = fmaf(g, Vc, disc[e][1])
+ *   halt_step[e] >= 0 (a halted episode):   disc[e][0] = fmaf(g, halt_r, disc[e][0]),  disc[e][1] = fmaf(g, halt_c, disc[e][1])
+ * Nothing else is written.  One workgroup per 16 episodes runs the policy and all 2 num_q critics on fp32 MFMA with the
+ * activations in LDS; the action never reaches memory.  A dot product's order is fixed by the layer shapes, so an
+ * episode's values are the same bits whatever `episodes` is, whichever row it is and whatever its neighbours hold.
+ * The critics are identical in shape, input obs_dim + act_dim, ONE output (evaluated as an ordered fmaf chain, not as a
+ * layer).  Every width <= OSRL_PLAN_TERMINAL_NARROW: the members run four at a time; otherwise (<= OSRL_MAX_WIDTH) one
+ * after another, and obs_dim + act_dim <= OSRL_PLAN_TERMINAL_WIDE_INPUT (the input tile beside two 1024-wide buffers in
+ * 160 KB of LDS).  -1 before any launch for a NULL pointer (halt_step aside), num_q outside 1 .. OSRL_PLAN_TERMINAL_MAX_Q,
+ * another `reduce`, kind OSRL_POLICY_BCQ, obs_ld < obs_dim, a width beyond these limits or critics of differing shapes. */
+#define OSRL_PLAN_TERMINAL_MAX_Q 4
+#define OSRL_PLAN_TERMINAL_NARROW 256
+#define OSRL_PLAN_TERMINAL_WIDE_INPUT 448
+enum { OSRL_PLAN_REDUCE_MEAN = 0, OSRL_PLAN_REDUCE_PESSIMISTIC = 1 };
+int osrl_plan_terminal(const osrl_policy_t* policy, const osrl_gemv_net_t* critics /* [2 * num_q] */, int32_t num_q,
+                       int32_t reduce, const float* obs /* [episodes, obs_ld] */, int32_t obs_ld, int32_t episodes,
+                       float r_mul, float c_mul, float halt_r, float halt_c, const int32_t* halt_step /* [E] or NULL */,
+                       float* disc /* [E,4] */, float* last_V /* [E,2] */, void* stream);
 /* The train step's preparation (engine/dynamics.py): xs[b] = (obs[b] - mu_s) / sd_s  [rows, state_dim];
  * target[b] = {(nobs[b] - obs[b] - mu_d) / sd_d, (rew[b] - mu_r) / sd_r, cost[b]}  [rows, state_dim + 2]. */
 int osrl_dyn_prepare(const float* obs, const float* nobs, const float* rew, const float* cost, const float* mu_s,

@@ -179,7 +179,8 @@ class RolloutMixin:
         return cached(self, "_model_collector", key,
                       lambda: ModelCollector(self.model, menv, *key[1:], use_graph=getattr(self, "use_graph", True)))
 
-    def planner(self, menv, num_envs, horizon, noise_std=0.3, gamma=1.0, temperature=0.0, seed=0):
+    def planner(self, menv, num_envs, horizon, noise_std=0.3, gamma=1.0, temperature=0.0, seed=0, terminal=None,
+                value_reduce="mean"):
         """A ``ModelPlanner`` (engine/mpc.py) of the current policy on the ``ModelVecEnv`` ``menv``: policy-guided
         shooting at act time.  ``menv.E == num_envs * K``: each of the ``num_envs`` real states handed to
         ``planner.act(states, cost_budget)`` fans out into K imagined episodes of ``horizon`` steps, candidate 0 following
@@ -188,14 +189,22 @@ class RolloutMixin:
         (in ``cost_scale`` units) stays within the budget, of the cheapest when none does, or with ``temperature > 0``
         the softmax-weighted mean of the feasible first actions.  The policy, the appended cost limit of BC multi-task
         and the cost scale are ``evaluate``'s.  Anything but a ``ModelVecEnv``: TypeError; a shape that does not fit:
-        ValueError, before anything is launched.  The planner is the caller's to keep: it is not cached."""
-        from ..engine.mpc import ModelPlanner, check_plan
+        ValueError, before anything is launched.  The planner is the caller's to keep: it is not cached.
+        ``terminal``: an ``FQETrainer`` (with its ``reward_scale`` / ``cost_scale``) or an ``FQE`` (scales of 1) fitted for
+        this trainer's model at the same ``gamma``: every candidate's sums are closed with ``gamma^H Q(s_H, pi(s_H))`` of
+        its reward and cost critics -- the members' mean, or with ``value_reduce="pessimistic"`` the lowest return and
+        the highest cost -- so that the budget is compared with the whole remaining episode's cost, not with H steps of
+        it (engine/mpc.py ``check_terminal`` lists the refusals; BCQ-L: TypeError)."""
+        from ..engine.mpc import ModelPlanner, check_plan, check_terminal
         check_plan(menv, num_envs, horizon, noise_std, temperature)
+        extra = None if terminal is None else self._eval_extra()
+        check_terminal(getattr(self, "model", None), menv, self.EVAL_KIND, terminal, gamma, value_reduce, extra)
         self._before_evaluate()
         cs = self._cost_scale()
         return ModelPlanner(self.model, menv, self.EVAL_KIND, 1.0 if cs is None else float(cs), self._eval_extra(),
                             num_envs=num_envs, horizon=horizon, noise_std=noise_std, gamma=gamma,
-                            temperature=temperature, seed=seed, use_graph=getattr(self, "use_graph", True))
+                            temperature=temperature, seed=seed, use_graph=getattr(self, "use_graph", True),
+                            terminal=terminal, value_reduce=value_reduce)
 
     @torch.no_grad()
     def evaluate_planned(self, planner, envs, eval_episodes, cost_limit):

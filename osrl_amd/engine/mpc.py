@@ -8,6 +8,11 @@ eps)``, ``osrl_model_env_collect*`` with whatever pessimism the environment carr
 the best penalised return among those whose discounted cost stays inside the slot's remaining budget, the cheapest one
 when none does, or with ``temperature > 0`` the softmax average of the feasible first actions (MPPI).
 
+``terminal=`` (an ``FQE`` or ``FQETrainer`` fitted for the same policy) closes the H-step sums with a value at the horizon:
+one more launch, ``osrl_plan_terminal`` (csrc/plan_value.hip), between the last recorded step and the select adds
+``gamma^H Q_r(s_H, pi(s_H))`` to every candidate's return and ``gamma^H Q_c(s_H, pi(s_H))`` to its cost, so that ``C_k <=
+budget`` compares like with like: the whole remaining episode (DESIGN.md "Terminal value at the horizon").
+
 Candidate 0 of every slot has sigma = 0: the policy's own proposal is always among the candidates.  The noise is the
 collectors' (Philox stream 13, keyed by seed word, episode id ``base_seed + n * K + k``, the episode's step and the action
 column) and the model's steps do not depend on their tile neighbours, so a slot's action is a function of its own state
@@ -16,7 +21,7 @@ and budget, the weights, the seed and the call number -- not of N, the slot's po
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -49,6 +54,59 @@ def check_plan(venv, num_envs, horizon, noise_std=0.0, temperature=0.0) -> int:
         if not (0.0 <= float(x) < math.inf):
             raise ValueError(f"{name} {x}: a finite value >= 0")
     return K
+
+
+class Terminal(NamedTuple):
+    """What ``check_terminal`` hands the planner: the ``FQE``, the scales its critics were fitted under and the member
+    reduction as ``osrl_plan_terminal`` takes it."""
+    fqe: object
+    reward_scale: float
+    cost_scale: float
+    reduce: int
+
+
+def check_terminal(model, venv, kind: str, terminal, gamma, value_reduce: str = "mean",
+                   extra_obs: Optional[float] = None) -> Optional[Terminal]:
+    """A planner's ``terminal=`` / ``value_reduce=``, judged on the host before anything is built or launched; None
+    without a terminal.  TypeError for anything but an ``FQE`` / ``FQETrainer`` and for BCQ-L (its action at the horizon
+    needs decode noise, and the planner has no fixed ``z`` for it); ValueError for another ``value_reduce``, an FQE
+    fitted for another policy object, on another device or for other state / action widths, a ``gamma`` that is not the
+    FQE's (a value discounted at another rate cannot be added to these sums), ``gamma >= 1`` on an environment that can
+    halt (the absorbing state's tail ``1 / (1 - gamma)`` does not exist), a trainer with an extra observation column (BC
+    multi-task: FQE refuses it too), and widths the kernel does not take."""
+    from ..algorithms.fqe import FQE, FQETrainer, _device_key
+    if value_reduce not in L.PLAN_REDUCE:
+        raise ValueError(f"value_reduce {value_reduce!r}: one of {sorted(L.PLAN_REDUCE)}")
+    if terminal is None:
+        return None
+    if isinstance(terminal, FQETrainer):
+        fqe, rs, cs = terminal.model, float(terminal.reward_scale), float(terminal.cost_scale)
+    elif isinstance(terminal, FQE):
+        fqe, rs, cs = terminal, 1.0, 1.0
+    else:
+        raise TypeError(f"terminal= takes an FQE or an FQETrainer, not {type(terminal).__name__}")
+    if kind == "bcql":
+        raise TypeError("terminal= with BCQ-L: its action at the horizon needs decode noise, out of scope")
+    if extra_obs is not None:
+        raise ValueError("terminal= with an extra observation column (BC multi-task): FQE does not take such a policy")
+    if fqe.policy is not model:
+        raise ValueError("terminal=: the FQE was fitted for another policy object than the trainer's model")
+    if _device_key(fqe.device) != _device_key(model.device):
+        raise ValueError(f"terminal=: the FQE lives on {fqe.device!r}, the policy on {model.device!r}")
+    if (int(fqe.state_dim), int(fqe.action_dim)) != (int(venv.state_dim), int(model.action_dim)):
+        raise ValueError(f"terminal=: the FQE takes ({fqe.state_dim}, {fqe.action_dim})-wide states and actions, the planner "
+                         f"has ({venv.state_dim}, {model.action_dim})")
+    if float(gamma) != float(fqe.gamma):
+        raise ValueError(f"terminal=: the planner discounts at gamma = {float(gamma)}, the FQE at {float(fqe.gamma)}")
+    if float(gamma) >= 1.0 and venv.can_halt:
+        raise ValueError("terminal= on an environment that can halt needs gamma < 1: a halted candidate carries the "
+                         "absorbing state's tail 1 / (1 - gamma)")
+    if not (rs != 0.0 and cs != 0.0 and math.isfinite(rs) and math.isfinite(cs)):
+        raise ValueError(f"terminal=: reward_scale {rs} / cost_scale {cs} must be finite and non-zero")
+    if max(fqe.c_hidden_sizes) > L.PLAN_TERMINAL_NARROW and fqe.state_dim + fqe.action_dim > L.PLAN_TERMINAL_WIDE_INPUT:
+        raise ValueError(f"terminal=: critics wider than {L.PLAN_TERMINAL_NARROW} take states and actions of at most "
+                         f"{L.PLAN_TERMINAL_WIDE_INPUT} columns together")
+    return Terminal(fqe, rs, cs, L.PLAN_REDUCE[value_reduce])
 
 
 def check_budget(cost_budget, num_envs: int) -> np.ndarray:
@@ -89,12 +147,23 @@ class ModelPlanner(ModelCollector):
     Of the last call, on the device: ``last_J`` / ``last_C`` ``[N, K]`` (discounted penalised return and discounted cost
     of every candidate, the latter in ``cost_scale`` units), ``last_first_actions`` ``[N, K, ad]``, ``chosen`` ``[N]``
     (int32: the arg-best candidate, under MPPI too) and ``n_feasible`` ``[N]``.  The first three are views of the
-    planner's tables: the next call overwrites them."""
+    planner's tables: the next call overwrites them.
+
+    ``terminal`` (``check_terminal``: an ``FQE`` / ``FQETrainer`` of this very policy, same ``gamma``) adds the value at the
+    horizon in one launch before the select (csrc/plan_value.hip).  ``last_J`` / ``last_C`` then INCLUDE the terminal
+    terms: ``J += g Vr``, ``C += g Vc`` with ``g = gamma^H``, ``Vr = reduce_m Q_r,m(s_H, pi(s_H)) / reward_scale`` and ``Vc =
+    reduce_m Q_c,m(s_H, pi(s_H)) * cost_scale / FQE cost_scale`` (``value_reduce``: "mean" over the members, or
+    "pessimistic" = the lowest return and the highest cost); ``last_V`` ``[N, K, 2]`` holds ``(Vr, Vc)``.  A candidate that
+    halted carries the absorbing state's tail instead: ``halt_reward / (1 - gamma)`` and ``halt_cost * cost_scale / (1 -
+    gamma)``, times its own ``g`` -- walking into the model's ignorance must not look cheaper than staying out of it.
+    Without ``terminal`` the planner issues exactly the launches it issued before, and ``last_V`` is None."""
 
     def __init__(self, model, venv, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None,
                  num_envs: int = 1, horizon: int = 1, noise_std: float = 0.3, gamma: float = 1.0,
-                 temperature: float = 0.0, seed: int = 0, z: Optional[torch.Tensor] = None, use_graph: bool = True):
+                 temperature: float = 0.0, seed: int = 0, z: Optional[torch.Tensor] = None, use_graph: bool = True,
+                 terminal=None, value_reduce: str = "mean"):
         K = check_plan(venv, num_envs, horizon, noise_std, temperature)  # (before any device work)
+        term = check_terminal(model, venv, kind, terminal, gamma, value_reduce, extra_obs)
         super().__init__(model, venv, kind, cost_scale, extra_obs, seed, z, use_graph)
         N, od, ad, dev = int(num_envs), venv.state_dim, model.action_dim, self.obs.device
         self.num_envs, self.candidates, self.horizon = N, K, int(horizon)
@@ -110,6 +179,44 @@ class ModelPlanner(ModelCollector):
         self.action = torch.zeros(N, ad, dtype=torch.float32, device=dev)
         self.chosen = torch.zeros(N, dtype=torch.int32, device=dev)
         self.n_feasible = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.terminal, self._last_V = term, None
+        if term is not None:
+            self._build_terminal()
+
+    def _build_terminal(self) -> None:
+        """The descriptors ``osrl_plan_terminal`` reads: the policy's (the act paths' ``osrl_policy_t``) and the 2 num_q
+        online critics', reward members first.  They point at the packed copies, which the fused Adam step keeps current;
+        ``repack`` here covers parameters edited from outside a trainer."""
+        from ..common.net import net_desc_seq
+        from .act import _gemv_net, _policy_desc
+        fqe, m = self.terminal.fqe, self.model
+        fqe.repack()
+        m.repack()
+        pk, obs_dim, net0, kw = m._policy_spec()  # (max_action: the model's for "cpq", 1 for "dice", unread for "bc")
+        self._term_policy = _policy_desc(pk, obs_dim, m.action_dim, net0, kw["max_action"], None, 0, 0.0)
+        nets = [net_desc_seq([q], 1.0) for q in list(fqe.critic.q_nets) + list(fqe.cost_critic.q_nets)]
+        self._term_critics = (L.GemvNetT * len(nets))()
+        for dst, nd in zip(self._term_critics, nets):
+            _gemv_net(dst, nd)
+        self._term_keep = (net0, nets)  # the descriptors hold the parameter views alive
+        self._last_V = torch.zeros(self.venv.E, 2, dtype=torch.float32, device=self.obs.device)
+
+    @property
+    def last_V(self) -> Optional[torch.Tensor]:
+        """``[N, K, 2]``: ``(Vr, Vc)`` of every candidate at the horizon, scaled as they enter ``last_J`` / ``last_C``
+        (a halted candidate's critics' values too, though its sums took the halting tail); None without ``terminal``."""
+        return None if self._last_V is None else self._last_V.view(self.num_envs, self.candidates, 2)
+
+    def _terminal(self) -> None:
+        t, v, g = self.terminal, self.venv, self.plan_gamma
+        halt_r = halt_c = 0.0
+        if v.can_halt:
+            halt_r, halt_c = v.halt_reward / (1.0 - g), v.halt_cost * self.cost_scale / (1.0 - g)
+        L.check(L.load().osrl_plan_terminal(
+            self._term_policy, self._term_critics, t.fqe.num_q, t.reduce, self.obs.data_ptr(), self.obs.stride(0), v.E,
+            1.0 / t.reward_scale, self.cost_scale / t.cost_scale, halt_r, halt_c,
+            v.halt_step.data_ptr() if v.can_halt else None, self.disc.data_ptr(), self._last_V.data_ptr(), cur_stream()),
+            "osrl_plan_terminal")
 
     @property
     def temperature(self) -> float:
@@ -168,6 +275,8 @@ class ModelPlanner(ModelCollector):
         self._dev_in.copy_(self._host_in, non_blocking=True)
         self._fanout()
         self._drive_recorded(H, min(H, _CHUNK), None)
+        if self.terminal is not None:
+            self._terminal()
         self._select()
         self.calls += 1
         return self.action.cpu().numpy()

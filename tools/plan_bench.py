@@ -14,6 +14,12 @@ on a ``ModelVecEnv`` of 5 members with hidden [200, 200, 200].
     parent's, so that above 1 is faster in both); ``parent_spread`` = the parent's own max / min over its repeats;
     ``ok``: the ratio lies inside [1 / parent_spread, parent_spread].
 
+(c) with ``--terminal``, reported, not gated: microseconds per ``act`` without and with ``terminal=`` (an ``FQE`` of the
+    policy, [256, 256] critics, num_q = 2: one more launch, csrc/plan_value.hip) at the same N, K, H grid, and the same
+    ``Q(s, pi(s))`` taken by the existing launch chain (``PolicyForward`` + ``MlpRun`` on E = N K rows, then a stream
+    sync) for scale; the three sides interleave A B C C B A in ONE child process.  With ``--parent`` as well, the
+    untouched ``act`` (no terminal) of this tree against the parent's, child processes A B B A, gated like (b).
+
 Every repeat is kept.  Writes profiles/plan_bench.json (``--out``).  Needs an MI355X: there is no CPU path."""
 import argparse
 import json
@@ -93,6 +99,34 @@ def worker(tree, what, reps):
                         us.append((time.perf_counter() - t0) * 1e6)
                     out[f"N{n}_K{k}_H{h}"] = us
                     del p, tr, menv
+    elif what == "terminal":
+        from osrl_amd.algorithms.fqe import FQE
+        from osrl_amd.engine.core import MlpRun
+        from osrl_amd.engine.fqe import PolicyForward, _critic_descs
+        dev = torch.device("cuda:0")
+        for n in s["slots"]:
+            states = np.stack([e.reset(seed=i)[0] for i, e in enumerate(host_envs(n))]).astype(np.float32)
+            for k in s["candidates"]:
+                for h in s["horizons"]:
+                    tr, menv = make(n * k, h)
+                    fqe = FQE(tr.model, s["hidden"], 0.99, num_q=2, device="cuda:0")
+                    kw = dict(noise_std=0.3, gamma=0.99)
+                    p0, p1 = tr.planner(menv, n, h, **kw), tr.planner(menv, n, h, terminal=fqe, **kw)
+                    pi, rq = PolicyForward(tr.model, "cpq", n * k, dev), MlpRun(_critic_descs(fqe)[0], n * k, False, dev)
+
+                    def chain():
+                        rq.forward(p0.obs, pi.forward(p0.obs))
+                        torch.cuda.synchronize()
+                    sides = dict(act=lambda: p0.act(states, 5.0), act_terminal=lambda: p1.act(states, 5.0), chain=chain)
+                    us = {name: [] for name in sides}
+                    for i in range(3 + reps * 10):
+                        for name in ("act", "act_terminal", "chain", "chain", "act_terminal", "act"):
+                            t0 = time.perf_counter()
+                            sides[name]()
+                            if i >= 3:
+                                us[name].append((time.perf_counter() - t0) * 1e6)
+                    out[f"N{n}_K{k}_H{h}"] = us
+                    del p0, p1, pi, rq, fqe, tr, menv
     else:  # "policy": rollout_many of the bare policy on the same N host environments
         tr, _ = make(16, 5)
         for n in s["slots"]:
@@ -158,13 +192,36 @@ def against_parent(parent, reps, rounds):
                 bench=dict(command="python " + " ".join(BENCH_CMD), unit="grad-steps/s", **gate(bh, bt, higher_is_better=True)))
 
 
+def terminal_rows(reps, rounds):
+    got = {}
+    for _ in range(rounds):
+        for k, v in child(ROOT, "terminal", reps).items():
+            for name, us in v.items():
+                got.setdefault(k, {}).setdefault(name, []).extend(us)
+    rows = {}
+    for k, v in got.items():
+        a, b, c = summary(v["act"]), summary(v["act_terminal"]), summary(v["chain"])
+        rows[k] = dict(act_us=a, act_terminal_us=b, launch_chain_us=c, added_us=round(b["median"] - a["median"], 3))
+    return rows
+
+
+def act_against_parent(parent, reps, rounds):
+    here, there = {}, {}
+    for _ in range(rounds):  # A B B A
+        for tree, acc in ((ROOT, here), (parent, there), (parent, there), (ROOT, here)):
+            for k, v in child(tree, "plan", reps).items():
+                acc.setdefault(k, []).extend(v)
+    return {k: gate(here[k], there[k]) for k in here}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plan_bench.json"))
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit (part b)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=1, help="A B B A rounds")
-    ap.add_argument("--worker", default=None, choices=["untouched", "plan", "policy"])
+    ap.add_argument("--terminal", action="store_true", help="part c: act with and without terminal=, and the launch chain")
+    ap.add_argument("--worker", default=None, choices=["untouched", "plan", "policy", "terminal"])
     ap.add_argument("--tree", default=ROOT)
     args = ap.parse_args()
     if args.worker:
@@ -185,9 +242,13 @@ def main():
         a, b = summary(v), summary(pol[n])
         rows[k] = dict(act_us=a, rollout_many_per_call_us=b, env_step_us=round(sorted(env_us[n])[len(env_us[n]) // 2], 3),
                        ratio=round(a["median"] / b["median"], 3))
-    out = dict(shape=SHAPE, act_vs_rollout_many=rows, vs_parent=None)
+    out = dict(shape=SHAPE, act_vs_rollout_many=rows, vs_parent=None, terminal=None, act_vs_parent=None)
     if args.parent:
         out["vs_parent"] = against_parent(os.path.abspath(args.parent), args.reps, args.rounds)
+    if args.terminal:
+        out["terminal"] = terminal_rows(args.reps, args.rounds)
+        if args.parent:
+            out["act_vs_parent"] = act_against_parent(os.path.abspath(args.parent), args.reps, args.rounds)
     import torch  # (after the children: this process never opens the device before them)
     out["device"] = torch.cuda.get_device_name(0)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
