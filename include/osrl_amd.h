@@ -1582,6 +1582,51 @@ typedef struct {
 } osrl_dyn_loss_t;
 int osrl_dyn_member_loss(const osrl_dyn_loss_t* d, void* stream);
 
+/* Distributional fitted Q evaluation (fqe_quantile.hip): the quantile-Huber loss of critics with M outputs, output i the
+ * tau_i = (i + 0.5) / M quantile of the discounted return under the frozen policy (QR-DQN's loss, the policy held fixed).
+ * A launch of its own between the online forward and an unseeded backward launch.  The nets are n_r reward critics
+ * followed by n_c cost critics; for net m, row b, x = rew[b] for m < n_r and cost[b] otherwise:
+ *   T_j  = x + gamma (1 - done[b]) theta_t[m, b, j]                 (net m bootstraps from target net m alone)
+ *   u_ij = T_j - theta[m, b, i],   w_ij = |tau_i - 1[u_ij < 0]|,   L(u) = 0.5 u^2 if |u| <= kappa else kappa (|u| - 0.5 kappa)
+ *   row_loss[m, b] = sum_i (1/M) (sum_j w_ij L(u_ij)) / kappa
+ *   dy[m, b, i]    = -(scale / M) (sum_j w_ij clamp(u_ij, -kappa, kappa)) / kappa        = d(scale row_loss)/d(theta_i)
+ *   stat_r[0] = stat_scale sum_{m < n_r, b} row_loss[m, b],   stat_c[0] = the same over the cost nets
+ * Every sum over j and over i runs in ascending order.  A row's dy and row_loss do not depend on rows, on the row's position
+ * or on its neighbours.  The statistics are fixed-order sums of one pair of partials per workgroup
+ * (OSRL_FQE_QUANTILE_WAVES * (64 / M) consecutive (net, row) items), taken by the last workgroup to arrive, with no
+ * floating-point atomics: two launches on the same inputs give the same bits.  With stat_r / stat_c (both or neither):
+ * partials >= 2 ceil(n_nets rows / items per workgroup) floats, counter one uint32, ZERO before the first launch
+ * (re-armed by the launch).  2 <= M <= OSRL_FQE_MAX_QUANTILES, kappa > 0, rows >= 1, n_r + n_c <= OSRL_MAX_NETS, at least
+ * one output; -1 before any launch otherwise.  HOST struct; the launch goes through the argument arena when one is
+ * recording. */
+#define OSRL_FQE_MAX_QUANTILES 64
+#define OSRL_FQE_QUANTILE_WAVES 4
+typedef struct {
+  const float* theta;   /* [n_r + n_c, rows, M]  the online forward's output */
+  const float* theta_t; /* [n_r + n_c, rows, M]  the target forward's output on (s', pi(s')) */
+  const float* rew;     /* [rows] */
+  const float* cost;    /* [rows] */
+  const float* done;    /* [rows] */
+  float* dy;            /* [n_r + n_c, rows, M] or NULL */
+  float* row_loss;      /* [n_r + n_c, rows] or NULL */
+  float* stat_r;        /* [1] or NULL */
+  float* stat_c;        /* [1] or NULL */
+  float* partials;
+  uint32_t* counter;
+  int32_t n_r, n_c, rows, M;
+  float gamma, kappa, scale, stat_scale;
+} osrl_fqe_quantile_t;
+int osrl_fqe_quantile_loss(const osrl_fqe_quantile_t* d, void* stream);
+/* The read-out of quantile critics: theta [n_nets, rows, M], the first n_lo nets reward critics, the others cost critics.
+ * Per (net, row) the M values are sorted ascending (a bitonic network across lanes, lanes past M padded with +inf) and added
+ * in fp64 in ascending order: all M of them, and the tail -- the k_lo smallest for a reward net, the k_hi largest for a cost
+ * net.  acc[2 net] += the sum over rows of the first, acc[2 net + 1] += of the second, rows in one fixed order (acc = 2 n_nets
+ * device doubles that the caller zeroes once and then accumulates into chunk by chunk).  Equal values may sort either way;
+ * the sums do not depend on it.  Crossing (unsorted) quantiles are legal input.  n_nets <= OSRL_MAX_NETS, rows >= 1,
+ * 2 <= M <= OSRL_FQE_MAX_QUANTILES, 1 <= k_lo, k_hi <= M; -1 before any launch otherwise. */
+int osrl_fqe_quantile_sums(const float* theta, int32_t n_nets, int32_t n_lo, int32_t rows, int32_t M, int32_t k_lo,
+                           int32_t k_hi, double* acc, void* stream);
+
 /* Diagnostics (diag.hip): where the HIP runtime of this process keeps kernel arguments -- *where = 1 device memory,
  * 0 host memory (every wave then fetches its launch arguments over PCIe; see osrl_args_begin), -1 unknown.  dev_scratch:
  * 8 bytes of device memory.  Synchronises `stream`; not for the hot path. */

@@ -225,6 +225,17 @@ DYN_LOSS_MSE, DYN_LOSS_GAUSS_NLL = 0, 1  # OSRL_DYN_LOSS_*
 DYN_LOSS_TILE = 4  # OSRL_DYN_LOSS_TILE: rows per partial of osrl_dyn_member_loss's statistic
 
 
+class FqeQuantileT(C.Structure):  # osrl_fqe_quantile_t
+    _fields_ = [("theta", _fp), ("theta_t", _fp), ("rew", _fp), ("cost", _fp), ("done", _fp), ("dy", _fp),
+                ("row_loss", _fp), ("stat_r", _fp), ("stat_c", _fp), ("partials", _fp), ("counter", C.c_void_p),
+                ("n_r", C.c_int32), ("n_c", C.c_int32), ("rows", C.c_int32), ("M", C.c_int32),
+                ("gamma", C.c_float), ("kappa", C.c_float), ("scale", C.c_float), ("stat_scale", C.c_float)]
+
+
+FQE_MAX_QUANTILES = 64  # OSRL_FQE_MAX_QUANTILES
+FQE_QUANTILE_WAVES = 4  # OSRL_FQE_QUANTILE_WAVES: a workgroup of osrl_fqe_quantile_loss holds 4 * (64 // M) (net, row) items
+
+
 class _HaltDesc:
     """What ``ModelVecEnv.desc`` hands out when halting or the cost penalty is on: the plain descriptor (``env``) and the
     ``osrl_model_env_pess_t`` beside it -- the two pointer arguments of the ``_halt`` entry points."""
@@ -306,6 +317,8 @@ PROTOTYPES = {
                            _vp],
     "osrl_dyn_prepare": [_vp] * 10 + [_i32, _i32, _vp, _vp, _vp],
     "osrl_dyn_member_loss": [_P(DynLossT), _vp],
+    "osrl_fqe_quantile_loss": [_P(FqeQuantileT), _vp],
+    "osrl_fqe_quantile_sums": [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "osrl_env_collect": [_P(EnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _i32, _vp],
     "osrl_cdt_collect": [_P(EnvT), _P(CollectT), _P(CdtWindowT), _vp, _vp, _i32, _vp],
     "osrl_cdt_rollout_pick": [_vp, _i32, _i32, _i32, _i32, _vp, _f32, _vp, _vp],

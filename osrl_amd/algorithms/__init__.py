@@ -5,7 +5,8 @@ from .cdt import CDT, CDTTrainer
 from .coptidice import COptiDICE, COptiDICETrainer
 from .cpq import CPQ, CPQTrainer
 from .dynamics import Dynamics, DynamicsTrainer
-from .fqe import FQE, FQEEstimate, FQETrainer
+from .fqe import FQE, FQEEstimate, FQERiskEstimate, FQETrainer
 
 __all__ = ["BC", "BCTrainer", "BCQL", "BCQLTrainer", "BEARL", "BEARLTrainer", "CDT", "CDTTrainer", "COptiDICE",
-           "COptiDICETrainer", "CPQ", "CPQTrainer", "Dynamics", "DynamicsTrainer", "FQE", "FQEEstimate", "FQETrainer"]
+           "COptiDICETrainer", "CPQ", "CPQTrainer", "Dynamics", "DynamicsTrainer", "FQE", "FQEEstimate", "FQERiskEstimate",
+           "FQETrainer"]

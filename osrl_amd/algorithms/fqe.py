@@ -5,6 +5,12 @@ reward critics and an ensemble of cost critics for a frozen policy pi on the log
 ``x + gamma (1 - done) Q_targ(s', pi(s'))``), ``FQETrainer.estimate`` reads ``Q(s0, pi(s0))`` at the dataset's initial
 states.  The cost value is a discounted one: compare it with ``FQE.discounted_cost_limit`` (the ``q_thres`` of
 cpq.py:102-105).  The arithmetic of the step is the HIP plan in ``osrl_amd/engine/fqe.py``.
+
+``FQE(num_quantiles=M)`` is the distributional variant: every critic has ``M`` outputs, output ``i`` the
+``tau_i = (i + 0.5) / M`` quantile of the discounted return under pi, fitted by quantile regression (QR-DQN's quantile-Huber
+loss with the policy held fixed; csrc/fqe_quantile.hip).  ``FQETrainer.estimate_risk`` then reads the tail of that
+distribution, the CVaR of the reward and of the cost return, next to the mean.  Quantile crossing is not prevented, and the
+estimate inherits FQE's extrapolation error.
 """
 from __future__ import annotations
 
@@ -15,7 +21,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..common.net import EnsembleQCritic, bind_group, check_mlp_limits, plan_group
+from .. import _lib as L
+from ..common.net import EnsembleQCritic, bind_group, check_mlp_limits, mlp, plan_group
 from ..engine.core import FlatGroup, require_cuda
 from ._base import FlatModel
 
@@ -32,6 +39,31 @@ class FQEEstimate(NamedTuple):
     n_init: int
 
 
+class FQERiskEstimate(NamedTuple):
+    """``FQEEstimate``'s fields (each member's value is the mean over its quantiles) and the CVaR at level ``alpha``: the
+    mean over the initial states of the per-state tail mean, its mean and spread over the ensemble members."""
+    value: float
+    value_std: float
+    cost_value: float
+    cost_value_std: float
+    value_cvar: float
+    value_cvar_std: float
+    cost_cvar: float
+    cost_cvar_std: float
+    alpha: float
+    n_init: int
+
+
+class EnsembleQuantileCritic(nn.Module):
+    """``EnsembleQCritic``'s module layout (``q_nets.<e>.<2 l>.{weight, bias}``) with ``num_quantiles`` outputs per member.
+    It is run by the engine's launches only."""
+
+    def __init__(self, obs_dim, act_dim, hidden_sizes, num_q, num_quantiles):
+        super().__init__()
+        self.q_nets = nn.ModuleList(
+            [mlp([obs_dim + act_dim] + list(hidden_sizes) + [num_quantiles], nn.ReLU) for _ in range(num_q)])
+
+
 def _device_key(device):
     d = torch.device(device)
     idx = d.index
@@ -43,12 +75,15 @@ def _device_key(device):
 class FQE(FlatModel):
     """``policy``: a trained BC / CPQ / BEARL / COptiDICE / BCQL model on ``device``; it is read in place (its packed
     forward weights, as ``BatchedRollout`` reads them) and never written, and it is NOT part of this model's
-    ``state_dict``, which holds ``critic``, ``cost_critic`` and their targets in the reference's ``EnsembleQCritic`` layout."""
+    ``state_dict``, which holds ``critic``, ``cost_critic`` and their targets in the reference's ``EnsembleQCritic`` layout.
+    ``num_quantiles=M`` (2 .. 64): quantile critics -- the same keys, the last layer ``M`` wide -- fitted with the
+    quantile-Huber loss of threshold ``kappa`` (a constructor value, not state)."""
 
     ENGINE = "fqe.FQEEngine"
 
     def __init__(self, policy, c_hidden_sizes: list = [256, 256], gamma: float = 0.99, tau: float = 0.005,
-                 num_q: int = 2, device: str = "cuda", state_dim: Optional[int] = None):
+                 num_q: int = 2, device: str = "cuda", state_dim: Optional[int] = None,
+                 num_quantiles: Optional[int] = None, kappa: float = 1.0):
         """``state_dim``: the width of the dataset's observations, if the caller wants it checked here; a store whose
         observations are narrower than the policy's input is refused when it is attached or read in any case."""
         super().__init__()
@@ -63,13 +98,24 @@ class FQE(FlatModel):
         self.gamma, self.tau, self.num_q = float(gamma), float(tau), int(num_q)
         if not 1 <= self.num_q <= MAX_NUM_Q:
             raise ValueError(f"num_q = {num_q}: FQE runs 2 * num_q nets per launch, 1 <= num_q <= {MAX_NUM_Q}")
-        check_mlp_limits("FQE", critic=[self.state_dim + self.action_dim] + self.c_hidden_sizes + [1])
+        self.num_quantiles = None if num_quantiles is None else int(num_quantiles)
+        self.kappa = float(kappa)
+        if self.num_quantiles is not None and not 2 <= self.num_quantiles <= L.FQE_MAX_QUANTILES:
+            raise ValueError(f"num_quantiles = {num_quantiles}: 2 <= num_quantiles <= {L.FQE_MAX_QUANTILES}, or None")
+        if not (self.kappa > 0.0 and np.isfinite(self.kappa)):
+            raise ValueError(f"kappa = {kappa}: the Huber threshold is a positive number")
+        check_mlp_limits("FQE", critic=[self.state_dim + self.action_dim] + self.c_hidden_sizes +
+                         [self.num_quantiles or 1])
         self.device = str(device)
         if _device_key(policy.device) != _device_key(device):
             raise ValueError(f"the policy lives on {policy.device!r}, FQE was asked for {device!r}")
         dev = require_cuda(device)
 
         mk = lambda: EnsembleQCritic(self.state_dim, self.action_dim, self.c_hidden_sizes, nn.ReLU, num_q=self.num_q)  # noqa: E731
+        if self.num_quantiles is not None:
+            self.ENGINE = "fqe.QuantileFQEEngine"  # (this instance's; a default model keeps the class's)
+            mk = lambda: EnsembleQuantileCritic(self.state_dim, self.action_dim, self.c_hidden_sizes, self.num_q,  # noqa: E731
+                                                self.num_quantiles)
         self.critic, self.cost_critic = mk(), mk()
         self.critic_old, self.cost_critic_old = deepcopy(self.critic), deepcopy(self.cost_critic)
         for m in (self.critic_old, self.cost_critic_old):
@@ -105,10 +151,11 @@ class FQE(FlatModel):
                              f"takes ({self.state_dim}, {self.action_dim}) (BC in multi-task mode is out of scope)")
 
     def readout(self, rows: int):
-        from ..engine.fqe import ValueReadout
+        from ..engine.fqe import QuantileReadout, ValueReadout
         r = self._readouts.get(rows)
         if r is None:
-            r = self._readouts[rows] = ValueReadout(self, rows, torch.device(self.device))
+            cls = ValueReadout if self.num_quantiles is None else QuantileReadout
+            r = self._readouts[rows] = cls(self, rows, torch.device(self.device))
         return r
 
 
@@ -155,6 +202,42 @@ class FQETrainer:
         chunks of ``rows`` states; the result does not depend on ``rows``, bit for bit.  ``z`` (BCQ-Lag policies):
         the decode noise [n_init, latent_dim], injected; by default drawn from the trainer's seed, the same every call.
         FQE's error grows with the shift between the policy and the data: a tool for ranking, not a certificate."""
+        if self.model.num_quantiles is not None:  # (each member's value: the mean over its quantiles)
+            r = self.estimate_risk(store, 1.0, rows, z)
+            return FQEEstimate(r.value, r.value_std, r.cost_value, r.cost_value_std, r.n_init)
+        means, n = self._read(store, rows, z)
+        E = self.model.num_q
+        r, c = means[:E] / self.reward_scale, means[E:] / self.cost_scale
+        return FQEEstimate(float(r.mean()), float(r.std()), float(c.mean()), float(c.std()), n)
+
+    @torch.no_grad()
+    def estimate_risk(self, store, alpha: float = 0.1, rows: int = 1024, z=None) -> FQERiskEstimate:
+        """The value and the CVaR at level ``alpha`` of the policy's discounted reward and cost returns at the initial
+        states of ``store``, from a quantile model (``FQE(num_quantiles=M)``; TypeError on a scalar one).  Per member and
+        initial state the ``M`` outputs are sorted ascending and ``k = ceil(alpha M)`` (``alpha M`` within 1e-9 of an
+        integer counts as that integer); the reward CVaR is the mean of the ``k`` smallest, the cost CVaR the mean of the
+        ``k`` largest; both are averaged over the initial states and rescaled as ``estimate`` does; ``*_std`` is the spread
+        over the members.  This is the MEAN OVER s0 OF THE PER-STATE CVaR, not the CVaR of the distribution pooled over
+        initial states (which it bounds from the pessimistic side); ``alpha = 1`` gives the means.
+        Repeated calls with the same ``rows`` give the same bits; different ``rows`` agree to 1e-12 relative (the fp64
+        sums over the rows of a chunk are taken in an order that depends on the chunk's size).  ``z`` as in ``estimate``."""
+        m = self.model
+        if m.num_quantiles is None:
+            raise TypeError("estimate_risk needs quantile critics: build the model with FQE(num_quantiles=M)")
+        alpha, M, E = float(alpha), m.num_quantiles, m.num_q
+        if not 0.0 < alpha <= 1.0:
+            raise ValueError(f"alpha = {alpha}: a tail fraction in (0, 1]")
+        k = min(M, max(1, int(np.ceil(alpha * M - 1e-9))))
+        sums, n = self._read(store, rows, z, k)
+        sums = sums.reshape(2 * E, 2)
+        scale = np.repeat([self.reward_scale, self.cost_scale], E)
+        mean, cvar = sums[:, 0] / M / scale, sums[:, 1] / k / scale
+        f = lambda a: (float(a.mean()), float(a.std()))  # noqa: E731
+        return FQERiskEstimate(*f(mean[:E]), *f(mean[E:]), *f(cvar[:E]), *f(cvar[E:]), alpha, n)
+
+    def _read(self, store, rows: int, z, k: Optional[int] = None):
+        """The read-out's per-net sums over the initial states divided by their number (fp64 numpy), and that number.
+        Scalar models: [2 num_q] values; quantile models: [2 num_q, 2] (all quantiles, the ``k``-tail), flattened."""
         m = self.model
         idx = self._initial_rows(store)
         m.check_store(store)
@@ -172,12 +255,10 @@ class FQETrainer:
             else:
                 zs = torch.as_tensor(z, dtype=torch.float32).to(dev).reshape(n, Lz).clone()
                 G.clamp_(zs, -0.5, 0.5)
-        acc = torch.zeros(2 * m.num_q, dtype=torch.float64, device=dev)
+        acc = torch.zeros(2 * m.num_q * (1 if k is None else 2), dtype=torch.float64, device=dev)
         rows = max(1, min(int(rows), n))
+        kw = {} if k is None else {"k": k}
         for i0 in range(0, n, rows):
             i1 = min(i0 + rows, n)
-            m.readout(i1 - i0).accumulate(store.tables[0], idx[i0:i1], None if zs is None else zs[i0:i1], acc)
-        means = acc.cpu().numpy() / n  # the one host sync of the read-out
-        E = m.num_q
-        r, c = means[:E] / self.reward_scale, means[E:] / self.cost_scale
-        return FQEEstimate(float(r.mean()), float(r.std()), float(c.mean()), float(c.std()), n)
+            m.readout(i1 - i0).accumulate(store.tables[0], idx[i0:i1], None if zs is None else zs[i0:i1], acc, **kw)
+        return acc.cpu().numpy() / n, n  # the one host sync of the read-out

@@ -80,6 +80,32 @@ __device__ __forceinline__ float fqe_backup(float x, float done, float q_next, f
 __device__ __forceinline__ float sq_term(float d) { return d * d; }
 __device__ __forceinline__ float sq_grad(float d, float scale) { return 2.0f * d * scale; }
 
+// quantile regression of M outputs theta_i (the tau_i = (i + 0.5) / M quantiles) against M targets T_j (QR-DQN's loss with
+// the policy held fixed: fqe_quantile.hip).  One pair: u = T_j - theta_i, weight |tau_i - 1[u < 0]|, Huber term L(u) with
+// threshold kappa and its slope clamp(u, +-kappa).  QrSums holds output i's two sums over j, taken in ASCENDING j by
+// the caller's loop; qr_row_term / qr_grad turn them into output i's share of the row loss (summed over i ascending by
+// the caller) and into d(scale * row loss)/d(theta_i).
+__device__ __forceinline__ float qr_tau(int i, float inv_m) { return ((float)i + 0.5f) * inv_m; }
+__device__ __forceinline__ float qr_weight(float tau, float u) { return u < 0.f ? 1.0f - tau : tau; }
+__device__ __forceinline__ float huber_term(float u, float kappa) {
+  const float au = fabsf(u);
+  return au <= kappa ? 0.5f * u * u : kappa * (au - 0.5f * kappa);
+}
+__device__ __forceinline__ float huber_slope(float u, float kappa) { return fminf(fmaxf(u, -kappa), kappa); }
+struct QrSums {
+  float l, g;  // sum_j w_ij L(u_ij), sum_j w_ij clamp(u_ij, +-kappa)
+};
+__device__ __forceinline__ void qr_pair(QrSums& s, float theta_i, float t_j, float tau, float kappa) {
+  const float u = t_j - theta_i;
+  const float w = qr_weight(tau, u);
+  s.l += w * huber_term(u, kappa);
+  s.g += w * huber_slope(u, kappa);
+}
+__device__ __forceinline__ float qr_row_term(const QrSums s, float inv_m, float inv_kappa) { return s.l * inv_m * inv_kappa; }
+__device__ __forceinline__ float qr_grad(const QrSums s, float inv_m, float inv_kappa, float scale) {
+  return -(scale * inv_m) * (s.g * inv_kappa);
+}
+
 // PETS' soft clamp of a raw log-variance to (lo, hi): lv = lo + softplus(hi - softplus(hi - raw) - lo)
 __device__ __forceinline__ float bounded_logvar(float raw, float lo, float hi) {
   const float lv1 = hi - softplus_abs(hi - raw);

@@ -12,9 +12,15 @@ include/osrl_amd.h), the fused Adam + Polyak step, the minibatch draw inside the
 One chain on one stream:  prologue -> pi(s') (the launches of ``BatchedRollout.body`` for the policy's kind) -> the
 2 num_q target nets on [s', pi(s')] -> the 2 num_q online nets on [s, a] -> the seeded backward -> dW + Adam + Polyak.
 The policy's packed weights are read in place and never written.
+
+A quantile model (``FQE(num_quantiles=M)``) takes ``QuantileFQEEngine``: the same chain with ``M``-wide outputs, the loss
+a launch of its own (csrc/fqe_quantile.hip ``osrl_fqe_quantile_loss``) between the online forward and an UNSEEDED backward,
+as ``osrl_dyn_member_loss`` sits in the bootstrap dynamics step; ``QuantileReadout`` sorts each initial state's ``M`` outputs
+and sums them and their tail (``osrl_fqe_quantile_sums``).
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional
 
 import torch
@@ -76,6 +82,7 @@ class PolicyForward:
 
 
 def _critic_descs(model):
+    """(online, target) descriptors of the 2 num_q nets: the reward members, then the cost members."""
     seq = lambda mod: net_desc_seq(list(mod.q_nets), 1.0)  # noqa: E731
     return (concat_nets(seq(model.critic), seq(model.cost_critic)),
             concat_nets(seq(model.critic_old), seq(model.cost_critic_old)))
@@ -104,14 +111,21 @@ class FQEEngine(StepEngine):
         m.repack()
         self.r_t = MlpRun(d_tg, B, False, dev)
         self.r_q = MlpRun(d_on, B, True, dev)
-        self.dq = z(2 * E, B, 1)
+        self.dq = z(2 * E, B, m.num_quantiles or 1)
         self.r_q.setup_backward(self.dq)
         # reward and cost ensembles live in ONE group: one dW plan, one Adam + Polyak launch
         self.p_critic = DwPlan(m.groups["critic"], self.r_q.dw_entries(), B, dev)
+        self._build_loss(dev)
+        self._plans_built()
+
+    def _build_loss(self, dev) -> None:
+        m, E, B = self.model, self.model.num_q, self.B
         self.seed_fqe = G.seed_fqe(self.r_t.y, E, E, self.rew, self.cost, self.done, B, m.gamma,
                                    G.SeedStat(dev, 2 * E, B), self.st.stat_ptr(STAT_KEYS[0]),
                                    self.st.stat_ptr(STAT_KEYS[1]))
-        self._plans_built()
+
+    def _loss_backward(self) -> None:
+        self.r_q.backward_dz(seed=self.seed_fqe)
 
     def attach_replay(self, store) -> None:
         if store is not None:
@@ -131,8 +145,48 @@ class FQEEngine(StepEngine):
         a_next = self.pi.forward(self.nobs, zn)
         self.r_t.forward(self.nobs, a_next)
         self.r_q.forward(self.obs, self.act)
-        self.r_q.backward_dz(seed=self.seed_fqe)
+        self._loss_backward()
         self._optim("critic", self.p_critic, tau=m.tau)
+
+
+def quantile_loss_desc(theta, theta_t, n_r: int, n_c: int, rew, cost, done, rows: int, M: int, gamma: float, kappa: float,
+                       scale: float, dy=None, row_loss=None, stat_r: int = 0, stat_c: int = 0) -> "L.FqeQuantileT":
+    """The ``osrl_fqe_quantile_t`` of one call site; with ``stat_r`` / ``stat_c`` (addresses) it owns the partials and the
+    arrival counter of the two statistics."""
+    d = L.FqeQuantileT()
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    d.theta, d.theta_t, d.rew, d.cost, d.done, d.dy, d.row_loss = (p(theta), p(theta_t), p(rew), p(cost), p(done), p(dy),
+                                                                  p(row_loss))
+    d.n_r, d.n_c, d.rows, d.M = int(n_r), int(n_c), int(rows), int(M)
+    d.gamma, d.kappa, d.scale, d.stat_scale = float(gamma), float(kappa), float(scale), float(scale)
+    d._keep = [theta, theta_t, rew, cost, done, dy, row_loss]
+    if stat_r:
+        per_wg = L.FQE_QUANTILE_WAVES * (64 // int(M))
+        n_part = ((n_r + n_c) * int(rows) + per_wg - 1) // per_wg
+        partials = torch.zeros(2 * n_part, dtype=torch.float32, device=theta.device)
+        counter = torch.zeros(1, dtype=torch.int32, device=theta.device)
+        d.stat_r, d.stat_c, d.partials, d.counter = stat_r, stat_c, partials.data_ptr(), counter.data_ptr()
+        d._keep += [partials, counter]
+    return d
+
+
+def quantile_loss(d: "L.FqeQuantileT") -> None:
+    L.check(L.load().osrl_fqe_quantile_loss(C.byref(d), cur_stream()), "osrl_fqe_quantile_loss")
+
+
+class QuantileFQEEngine(FQEEngine):
+    """The step of a quantile model: prologue -> pi(s') -> target forward -> online forward -> ``osrl_fqe_quantile_loss``
+    -> unseeded backward -> dW + Adam + Polyak; one chain on one stream, one one-step graph."""
+
+    def _build_loss(self, dev) -> None:
+        m, E, B = self.model, self.model.num_q, self.B
+        self.loss_d = quantile_loss_desc(self.r_q.y, self.r_t.y, E, E, self.rew, self.cost, self.done, B, m.num_quantiles,
+                                         m.gamma, m.kappa, float(G._inv(B, 0)), dy=self.dq,
+                                         stat_r=self.st.stat_ptr(STAT_KEYS[0]), stat_c=self.st.stat_ptr(STAT_KEYS[1]))
+
+    def _loss_backward(self) -> None:
+        quantile_loss(self.loss_d)
+        self.r_q.backward_dz()
 
 
 class ValueReadout:
@@ -147,16 +201,34 @@ class ValueReadout:
         self.pi = PolicyForward(m.policy, m.kind, self.rows, device, tile_rows=16)
         self.r_q = MlpRun(_critic_descs(m)[0], self.rows, False, device, tile_rows=16)
 
+    def values(self, table: torch.Tensor, idx: torch.Tensor, z: Optional[torch.Tensor]) -> torch.Tensor:
+        """The online nets' outputs [2 num_q, rows, out] on rows ``idx`` (int64, contiguous) of ``table``."""
+        m, n = self.model, self.rows
+        assert idx.dtype == torch.int64 and idx.numel() == n and idx.is_contiguous()
+        L.check(L.load().osrl_gather_rows(table.data_ptr(), m.state_dim, idx.data_ptr(), n, self.s0.data_ptr(),
+                                          m.state_dim, None, cur_stream()), "osrl_gather_rows")
+        return self.r_q.forward(self.s0, self.pi.forward(self.s0, z))
+
     def accumulate(self, table: torch.Tensor, idx: torch.Tensor, z: Optional[torch.Tensor], acc: torch.Tensor) -> None:
         """``table``: the store's observations [n, od]; ``idx``: int64 [rows] row indices; ``acc``: fp64 [2 num_q]."""
         lib, m, n = L.load(), self.model, self.rows
-        assert idx.dtype == torch.int64 and idx.numel() == n and idx.is_contiguous()
         assert acc.dtype == torch.float64 and acc.numel() == 2 * m.num_q
-        L.check(lib.osrl_gather_rows(table.data_ptr(), m.state_dim, idx.data_ptr(), n, self.s0.data_ptr(), m.state_dim,
-                                     None, cur_stream()), "osrl_gather_rows")
-        q = self.r_q.forward(self.s0, self.pi.forward(self.s0, z))
+        q = self.values(table, idx, z)
         L.check(lib.osrl_fqe_value_sums(q.data_ptr(), 2 * m.num_q, n, acc.data_ptr(), cur_stream()),
                 "osrl_fqe_value_sums")
+
+
+class QuantileReadout(ValueReadout):
+    """The quantile critics' ``M`` outputs at chunks of ``rows`` initial states, sorted per (member, state) and summed in
+    fp64 -- all of them and the ``k``-tail (osrl_fqe_quantile_sums): ``acc`` is fp64 [2 num_q, 2]."""
+
+    def accumulate(self, table: torch.Tensor, idx: torch.Tensor, z: Optional[torch.Tensor], acc: torch.Tensor,
+                   k: int = 1) -> None:
+        lib, m = L.load(), self.model
+        assert acc.dtype == torch.float64 and acc.numel() == 4 * m.num_q
+        theta = self.values(table, idx, z)
+        L.check(lib.osrl_fqe_quantile_sums(theta.data_ptr(), 2 * m.num_q, m.num_q, self.rows, m.num_quantiles, int(k),
+                                           int(k), acc.data_ptr(), cur_stream()), "osrl_fqe_quantile_sums")
 
 
 def draw_decode_noise(n: int, latent_dim: int, seed: int, device) -> torch.Tensor:

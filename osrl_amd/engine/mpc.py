@@ -85,6 +85,9 @@ def check_terminal(model, venv, kind: str, terminal, gamma, value_reduce: str = 
         fqe, rs, cs = terminal, 1.0, 1.0
     else:
         raise TypeError(f"terminal= takes an FQE or an FQETrainer, not {type(terminal).__name__}")
+    if getattr(fqe, "num_quantiles", None) is not None:
+        raise TypeError("terminal= with quantile critics (FQE(num_quantiles=...)): osrl_plan_terminal evaluates one-output "
+                        "critics, a distributional terminal value is out of scope")
     if kind == "bcql":
         raise TypeError("terminal= with BCQ-L: its action at the horizon needs decode noise, out of scope")
     if extra_obs is not None:

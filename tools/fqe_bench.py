@@ -8,15 +8,24 @@ num_q = 2, a CPQ policy -- against two yardsticks taken in the same process, int
                (numpy) and copied to the device every step.
 
 Every number is steps/s over ``--steps`` steps between two device synchronisations, after ``--warmup`` steps.
-Writes profiles/fqe_bench.json (``--out``).  Needs an MI355X: there is no CPU path."""
+Writes profiles/fqe_bench.json (``--out``).  Needs an MI355X: there is no CPU path.
+
+``--quantiles M`` measures the quantile model instead (``FQE(num_quantiles=M)``, csrc/fqe_quantile.hip) and writes
+profiles/fqe_quantile_bench.json: the quantile step against the scalar step at the same shape, interleaved A B B A in one
+process; the loss launch alone (us, device events around ``--steps`` launches issued back to back: an upper bound);
+``estimate_risk`` against ``estimate`` on the same store (ms per call).  These are reported, not gated.  With ``--parent DIR`` (a built checkout of the parent
+commit) as well: the untouched scalar FQE step and ``bench.py --gpus 1 --steps 20 --warmup 5`` of this tree against the
+parent's, child processes A B B A; ``ok``: this tree's median lies inside the parent's own max / min spread."""
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# (a --worker child measures the package of --tree: this tree's or the parent checkout's)
+sys.path.insert(0, sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv else ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -75,8 +84,125 @@ class AutogradFQE:
         self.model.repack()  # the kernels read the packed copies of the parameters and of the targets
 
 
+BENCH_CMD = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"]
+
+
+def scalar_worker(args):
+    """steps/s of the scalar FQE step of the tree in ``sys.path[0]`` (only what the parent commit has as well)."""
+    from osrl_amd.algorithms import CPQ, FQE, FQETrainer
+    from osrl_amd.common.replay import ReplayStore, synthetic_transitions
+    dev = torch.device("cuda", 0)
+    store = ReplayStore(synthetic_transitions(args.rows, OD, AD, seed=1), dev, reward_scale=0.1, cost_scale=1.0, seed=1)
+    torch.manual_seed(0)
+    policy = CPQ(OD, AD, 1.0, HID, HID, 400, 10, GAMMA, TAU, 0.5, 2, 2, 1.5, 10, 1000, device=str(dev))
+    fqe = FQE(policy, HID, GAMMA, TAU, NUM_Q, device=str(dev))
+    FQETrainer(fqe, critic_lr=LR, reward_scale=0.1, stats_mode="none")
+    eng = fqe.engine(B)
+    eng.attach_replay(store)
+    step = lambda: eng.step_replay(True)  # noqa: E731
+    for _ in range(args.warmup):
+        step()
+    print("RESULT " + json.dumps([rate(step, args.steps) for _ in range(args.rounds)]))
+
+
+def child(tree, cmd):
+    env = dict(os.environ)
+    lib = os.path.join(tree, "osrl_amd", "lib", "libosrl_amd.so")
+    if os.path.exists(lib):  # each tree measures the library it was built with, whatever the files' times say
+        env["OSRL_LIB"] = lib
+    r = subprocess.run([sys.executable] + cmd, capture_output=True, text=True, timeout=900, cwd=tree, env=env)
+    if r.returncode != 0:
+        raise RuntimeError(f"{cmd[0]} failed in {tree}: {r.stderr[-2000:]}")
+    return r.stdout.splitlines()
+
+
+def gate(here, there):
+    """Higher is better on both sides; ``ok``: the ratio of the medians lies inside the parent's own max / min spread."""
+    h, t = summary(here), summary(there)
+    ratio, spread = h["median"] / t["median"], t["max"] / t["min"]
+    return dict(this_tree=h, parent=t, ratio=round(ratio, 4), parent_spread=round(spread, 4),
+                ok=bool(1.0 / spread <= ratio <= spread))
+
+
+def against_parent(parent, args):
+    me = os.path.abspath(__file__)
+    sh, st, bh, bt = [], [], [], []
+    for _ in range(args.rounds):  # A B B A
+        for tree, sc, bn in ((ROOT, sh, bh), (parent, st, bt), (parent, st, bt), (ROOT, sh, bh)):
+            out = child(tree, [me, "--worker", "--tree", tree, "--steps", str(args.steps), "--warmup", str(args.warmup),
+                               "--rounds", "3", "--rows", str(args.rows)])
+            sc += json.loads([ln for ln in out if ln.startswith("RESULT ")][-1][7:])
+            rows = [json.loads(ln) for ln in child(tree, BENCH_CMD) if ln.startswith("{") and '"value"' in ln]
+            bn.append(float(rows[-1]["value"]))
+            print(f"{'this tree' if tree == ROOT else 'parent'}: fqe {sc[-1]:.1f} bench {bn[-1]}", file=sys.stderr, flush=True)
+    return dict(scalar_fqe_steps_per_s=gate(sh, st),
+                bench=dict(command="python " + " ".join(BENCH_CMD), unit="grad-steps/s", **gate(bh, bt)))
+
+
+def quantile_main(args):
+    from osrl_amd.algorithms import CPQ, FQE, FQETrainer
+    from osrl_amd.common.replay import ReplayStore, synthetic_transitions
+    from osrl_amd.engine.fqe import quantile_loss
+    dev = torch.device("cuda", 0)
+    data = synthetic_transitions(args.rows, OD, AD, seed=1)
+    store = ReplayStore(data, dev, reward_scale=0.1, cost_scale=1.0, seed=1, state_init=True)
+    torch.manual_seed(0)
+    policy = CPQ(OD, AD, 1.0, HID, HID, 400, 10, GAMMA, TAU, 0.5, 2, 2, 1.5, 10, 1000, device=str(dev))
+    models = {}
+    for name, kw in (("scalar", {}), ("quantile", dict(num_quantiles=args.quantiles))):
+        torch.manual_seed(1)
+        m = FQE(policy, HID, GAMMA, TAU, NUM_Q, device=str(dev), **kw)
+        tr = FQETrainer(m, critic_lr=LR, reward_scale=0.1, stats_mode="none")
+        eng = m.engine(B)
+        eng.attach_replay(store)
+        models[name] = (tr, eng)
+    arms = {k: (lambda e=v[1]: e.step_replay(True)) for k, v in models.items()}
+    for f in arms.values():
+        for _ in range(args.warmup):
+            f()
+    res = {k: [] for k in arms}
+    for _ in range(args.rounds):
+        for name in ("scalar", "quantile", "quantile", "scalar"):
+            res[name].append(rate(arms[name], args.steps))
+    d = models["quantile"][1].loss_d  # the loss launch alone, on the step's own buffers
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    loss_us = []
+    for _ in range(args.rounds + 1):
+        ev[0].record()
+        for _ in range(args.steps):
+            quantile_loss(d)
+        ev[1].record()
+        torch.cuda.synchronize()
+        loss_us.append(ev[0].elapsed_time(ev[1]) * 1e3 / args.steps)
+
+    def ms(f):
+        f()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(10):
+            f()
+        return (time.perf_counter() - t0) * 1e2
+    trs, trq = models["scalar"][0], models["quantile"][0]
+    read = dict(estimate_scalar_ms=round(ms(lambda: trs.estimate(store)), 3),
+                estimate_risk_ms=round(ms(lambda: trq.estimate_risk(store, 0.1)), 3), n_init=trs.estimate(store).n_init)
+    out = dict(shape=dict(obs=OD, act=AD, batch=B, hidden=HID, num_q=NUM_Q, quantiles=args.quantiles, policy="cpq",
+                          store_rows=args.rows), device=torch.cuda.get_device_name(0), steps=args.steps,
+               warmup=args.warmup, rounds=args.rounds, order="scalar quantile quantile scalar per round",
+               steps_per_s={k: summary(v) for k, v in res.items()},
+               quantile_over_scalar=round(summary(res["quantile"])["median"] / summary(res["scalar"])["median"], 3),
+               loss_launch_us=summary(loss_us[1:]), readout=read,
+               risk_after_run=trq.estimate_risk(store, 0.1)._asdict(), vs_parent=None)
+    if args.parent:
+        out["vs_parent"] = against_parent(os.path.abspath(args.parent), args)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--quantiles", type=int, default=None, help="measure FQE(num_quantiles=M) (see the module docstring)")
+    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit (with --quantiles)")
+    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
@@ -85,6 +211,17 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("fqe_bench needs an MI355X (no CPU path): not measured")
+    if args.worker:
+        return scalar_worker(args)
+    if args.quantiles is not None:
+        out = quantile_main(args)
+        path = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "fqe_quantile_bench.json")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: out[k] for k in ("steps_per_s", "quantile_over_scalar", "loss_launch_us", "readout", "vs_parent")}))
+        return
     from osrl_amd.algorithms import CPQ, CPQTrainer, FQE, FQETrainer
     from osrl_amd.common.replay import ReplayStore, synthetic_transitions
     dev = torch.device("cuda", 0)
