@@ -1540,6 +1540,30 @@ int osrl_plan_terminal(const osrl_policy_t* policy, const osrl_gemv_net_t* criti
                        int32_t reduce, const float* obs /* [episodes, obs_ld] */, int32_t obs_ld, int32_t episodes,
                        float r_mul, float c_mul, float halt_r, float halt_c, const int32_t* halt_step /* [E] or NULL */,
                        float* disc /* [E,4] */, float* last_V /* [E,2] */, void* stream);
+/* The distributional terminal value (plan_value_quantile.hip): osrl_plan_terminal for quantile critics (the nets
+ * osrl_fqe_quantile_loss fits), in the same ONE launch at the same place.  Every critic has M outputs, output i the
+ * tau_i = (i + 0.5) / M quantile of the return from (obs_e, a), a = pi(obs_e) as above.  Per member m and episode e:
+ *   theta = critics[m]([obs_e, a]), M floats (every layer on fp32 MFMA), sorted ascending across lanes (a bitonic network,
+ *   lanes past M padded with +inf; equal values may sort either way, the sums do not depend on it; crossing quantiles are
+ *   legal input), the ranks then added in fp64 in ascending order:
+ *   mean_m = (float)(sum of all M / M),   lower_m = (float)(sum of the k_r smallest / k_r),   upper_m = (float)(sum of the
+ *   k_c largest / k_c) -- one rounding each.  A NaN among the M values makes all three NaN (the sort never sees it).
+ *   OSRL_PLAN_REDUCE_MEAN:         Vr = ((lower_0 + lower_1 + ..) / num_q) * r_mul over the reward members in ascending order,
+ *                                  Vc = ((upper_0 + ..) / num_q) * c_mul over the cost members
+ *   OSRL_PLAN_REDUCE_PESSIMISTIC:  Vr = min_m lower_m * r_mul,   Vc = max_m upper_m * c_mul
+ *   last_V[e] = (Vr, Vc), and disc[e][0..1] take them (or halt_r / halt_c) exactly as in osrl_plan_terminal.
+ *   last_V_mean[e] = the same reduction of mean_m over the reward / the cost members, times r_mul / c_mul: the
+ *   risk-neutral value, written for diagnostics and added to nothing.  k_r = k_c = M: last_V == last_V_mean, bit for bit.
+ * Nothing else is written.  An episode's values depend on the layer shapes, M, k_r, k_c and on which of the two
+ * instantiations the widths take (osrl_plan_terminal's rule, the last width M included), not on `episodes`, its row or its
+ * neighbours.  -1 before any launch for everything osrl_plan_terminal refuses (with "last width M" in place of "one
+ * output"), M outside 2 .. OSRL_FQE_MAX_QUANTILES, k_r or k_c outside 1 .. M, and a NULL last_V_mean. */
+int osrl_plan_terminal_quantile(const osrl_policy_t* policy, const osrl_gemv_net_t* critics /* [2 * num_q] */,
+                                int32_t num_q, int32_t M, int32_t k_r, int32_t k_c, int32_t reduce,
+                                const float* obs /* [episodes, obs_ld] */, int32_t obs_ld, int32_t episodes, float r_mul,
+                                float c_mul, float halt_r, float halt_c, const int32_t* halt_step /* [E] or NULL */,
+                                float* disc /* [E,4] */, float* last_V /* [E,2] */, float* last_V_mean /* [E,2] */,
+                                void* stream);
 /* The train step's preparation (engine/dynamics.py): xs[b] = (obs[b] - mu_s) / sd_s  [rows, state_dim];
  * target[b] = {(nobs[b] - obs[b] - mu_d) / sd_d, (rew[b] - mu_r) / sd_r, cost[b]}  [rows, state_dim + 2]. */
 int osrl_dyn_prepare(const float* obs, const float* nobs, const float* rew, const float* cost, const float* mu_s,

@@ -315,6 +315,8 @@ PROTOTYPES = {
     "osrl_plan_select": [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "osrl_plan_terminal": [_P(PolicyT), _P(GemvNetT), _i32, _i32, _vp, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp,
                            _vp],
+    "osrl_plan_terminal_quantile": [_P(PolicyT), _P(GemvNetT), _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _f32,
+                                    _f32, _f32, _vp, _vp, _vp, _vp, _vp],
     "osrl_dyn_prepare": [_vp] * 10 + [_i32, _i32, _vp, _vp, _vp],
     "osrl_dyn_member_loss": [_P(DynLossT), _vp],
     "osrl_fqe_quantile_loss": [_P(FqeQuantileT), _vp],

@@ -180,7 +180,7 @@ class RolloutMixin:
                       lambda: ModelCollector(self.model, menv, *key[1:], use_graph=getattr(self, "use_graph", True)))
 
     def planner(self, menv, num_envs, horizon, noise_std=0.3, gamma=1.0, temperature=0.0, seed=0, terminal=None,
-                value_reduce="mean"):
+                value_reduce="mean", risk_alpha=None):
         """A ``ModelPlanner`` (engine/mpc.py) of the current policy on the ``ModelVecEnv`` ``menv``: policy-guided
         shooting at act time.  ``menv.E == num_envs * K``: each of the ``num_envs`` real states handed to
         ``planner.act(states, cost_budget)`` fans out into K imagined episodes of ``horizon`` steps, candidate 0 following
@@ -194,17 +194,23 @@ class RolloutMixin:
         this trainer's model at the same ``gamma``: every candidate's sums are closed with ``gamma^H Q(s_H, pi(s_H))`` of
         its reward and cost critics -- the members' mean, or with ``value_reduce="pessimistic"`` the lowest return and
         the highest cost -- so that the budget is compared with the whole remaining episode's cost, not with H steps of
-        it (engine/mpc.py ``check_terminal`` lists the refusals; BCQ-L: TypeError)."""
+        it (engine/mpc.py ``check_terminal`` lists the refusals; BCQ-L: TypeError).
+        ``risk_alpha`` (a quantile ``terminal`` only, ``FQE(num_quantiles=M)``; ValueError otherwise): a float or a pair
+        ``(alpha_reward, alpha_cost)`` in (0, 1] -- the return is closed with the mean of the ``ceil(alpha_reward M)``
+        lowest quantiles at ``(s_H, pi(s_H))``, the cost with the mean of the ``ceil(alpha_cost M)`` highest, so the
+        budget bounds the upper-tail CVaR of the cost-to-go; None: the quantile means.  ``planner.risk_alpha`` may be
+        set between calls."""
         from ..engine.mpc import ModelPlanner, check_plan, check_terminal
         check_plan(menv, num_envs, horizon, noise_std, temperature)
         extra = None if terminal is None else self._eval_extra()
-        check_terminal(getattr(self, "model", None), menv, self.EVAL_KIND, terminal, gamma, value_reduce, extra)
+        check_terminal(getattr(self, "model", None), menv, self.EVAL_KIND, terminal, gamma, value_reduce, extra,
+                       risk_alpha)
         self._before_evaluate()
         cs = self._cost_scale()
         return ModelPlanner(self.model, menv, self.EVAL_KIND, 1.0 if cs is None else float(cs), self._eval_extra(),
                             num_envs=num_envs, horizon=horizon, noise_std=noise_std, gamma=gamma,
                             temperature=temperature, seed=seed, use_graph=getattr(self, "use_graph", True),
-                            terminal=terminal, value_reduce=value_reduce)
+                            terminal=terminal, value_reduce=value_reduce, risk_alpha=risk_alpha)
 
     @torch.no_grad()
     def evaluate_planned(self, planner, envs, eval_episodes, cost_limit):

@@ -54,6 +54,16 @@ class FQERiskEstimate(NamedTuple):
     n_init: int
 
 
+def tail_count(alpha: float, M: int) -> int:
+    """How many of ``M`` sorted quantiles the tail at level ``alpha`` holds: ``k = ceil(alpha M)`` (``alpha M`` within 1e-9
+    of an integer counts as that integer), at least 1; ValueError for an ``alpha`` outside (0, 1].  The one rule of
+    ``estimate_risk`` and of the planner's ``risk_alpha`` (engine/mpc.py)."""
+    alpha = float(alpha)
+    if not 0.0 < alpha <= 1.0:
+        raise ValueError(f"alpha = {alpha}: a tail fraction in (0, 1]")
+    return min(int(M), max(1, int(np.ceil(alpha * M - 1e-9))))
+
+
 class EnsembleQuantileCritic(nn.Module):
     """``EnsembleQCritic``'s module layout (``q_nets.<e>.<2 l>.{weight, bias}``) with ``num_quantiles`` outputs per member.
     It is run by the engine's launches only."""
@@ -225,9 +235,7 @@ class FQETrainer:
         if m.num_quantiles is None:
             raise TypeError("estimate_risk needs quantile critics: build the model with FQE(num_quantiles=M)")
         alpha, M, E = float(alpha), m.num_quantiles, m.num_q
-        if not 0.0 < alpha <= 1.0:
-            raise ValueError(f"alpha = {alpha}: a tail fraction in (0, 1]")
-        k = min(M, max(1, int(np.ceil(alpha * M - 1e-9))))
+        k = tail_count(alpha, M)
         sums, n = self._read(store, rows, z, k)
         sums = sums.reshape(2 * E, 2)
         scale = np.repeat([self.reward_scale, self.cost_scale], E)

@@ -11,7 +11,11 @@ when none does, or with ``temperature > 0`` the softmax average of the feasible 
 ``terminal=`` (an ``FQE`` or ``FQETrainer`` fitted for the same policy) closes the H-step sums with a value at the horizon:
 one more launch, ``osrl_plan_terminal`` (csrc/plan_value.hip), between the last recorded step and the select adds
 ``gamma^H Q_r(s_H, pi(s_H))`` to every candidate's return and ``gamma^H Q_c(s_H, pi(s_H))`` to its cost, so that ``C_k <=
-budget`` compares like with like: the whole remaining episode (DESIGN.md "Terminal value at the horizon").
+budget`` compares like with like: the whole remaining episode (DESIGN.md "Terminal value at the horizon").  A quantile
+FQE (``FQE(num_quantiles=M)``) takes ``osrl_plan_terminal_quantile`` (csrc/plan_value_quantile.hip) in that launch's place:
+with ``risk_alpha=(alpha_reward, alpha_cost)`` the return is closed with the mean of the ``ceil(alpha_reward M)`` LOWEST
+quantiles of each candidate's own end state and the cost with the mean of the ``ceil(alpha_cost M)`` HIGHEST -- the budget
+then bounds the upper-tail CVaR of the cost-to-go (DESIGN.md "A distributional terminal value").
 
 Candidate 0 of every slot has sigma = 0: the policy's own proposal is always among the candidates.  The noise is the
 collectors' (Philox stream 13, keyed by seed word, episode id ``base_seed + n * K + k``, the episode's step and the action
@@ -58,26 +62,45 @@ def check_plan(venv, num_envs, horizon, noise_std=0.0, temperature=0.0) -> int:
 
 class Terminal(NamedTuple):
     """What ``check_terminal`` hands the planner: the ``FQE``, the scales its critics were fitted under and the member
-    reduction as ``osrl_plan_terminal`` takes it."""
+    reduction as ``osrl_plan_terminal`` takes it; for a quantile FQE ``risk_alpha`` is the pair ``(alpha_reward,
+    alpha_cost)``, otherwise None."""
     fqe: object
     reward_scale: float
     cost_scale: float
     reduce: int
+    risk_alpha: Optional[tuple] = None
+
+
+def check_risk_alpha(risk_alpha, M: int):
+    """``risk_alpha`` of a quantile terminal with ``M`` quantiles as ``((alpha_reward, alpha_cost), (k_r, k_c))``: a float
+    stands for both, None for ``(1.0, 1.0)`` (the quantile means); ``k`` by ``estimate_risk``'s rule (algorithms/fqe.py
+    ``tail_count``: ValueError for an alpha outside (0, 1])."""
+    from ..algorithms.fqe import tail_count
+    if risk_alpha is None:
+        risk_alpha = 1.0
+    pair = tuple(risk_alpha) if isinstance(risk_alpha, (tuple, list)) else (risk_alpha, risk_alpha)
+    if len(pair) != 2:
+        raise ValueError(f"risk_alpha {risk_alpha!r}: a float or a pair (alpha_reward, alpha_cost)")
+    pair = (float(pair[0]), float(pair[1]))
+    return pair, (tail_count(pair[0], M), tail_count(pair[1], M))
 
 
 def check_terminal(model, venv, kind: str, terminal, gamma, value_reduce: str = "mean",
-                   extra_obs: Optional[float] = None) -> Optional[Terminal]:
-    """A planner's ``terminal=`` / ``value_reduce=``, judged on the host before anything is built or launched; None
-    without a terminal.  TypeError for anything but an ``FQE`` / ``FQETrainer`` and for BCQ-L (its action at the horizon
-    needs decode noise, and the planner has no fixed ``z`` for it); ValueError for another ``value_reduce``, an FQE
+                   extra_obs: Optional[float] = None, risk_alpha=None) -> Optional[Terminal]:
+    """A planner's ``terminal=`` / ``value_reduce=`` / ``risk_alpha=``, judged on the host before anything is built or launched; None
+    without a terminal.  TypeError for anything but an ``FQE`` / ``FQETrainer``, a ``venv`` that is no ``ModelVecEnv``
+    and BCQ-L (its action at the horizon needs decode noise, and the planner has no fixed ``z`` for it); ValueError for another ``value_reduce``, an FQE
     fitted for another policy object, on another device or for other state / action widths, a ``gamma`` that is not the
     FQE's (a value discounted at another rate cannot be added to these sums), ``gamma >= 1`` on an environment that can
     halt (the absorbing state's tail ``1 / (1 - gamma)`` does not exist), a trainer with an extra observation column (BC
-    multi-task: FQE refuses it too), and widths the kernel does not take."""
+    multi-task: FQE refuses it too), widths the kernel does not take, a ``risk_alpha`` outside (0, 1] and a ``risk_alpha``
+    without quantile critics to take a tail of (a scalar FQE, no terminal)."""
     from ..algorithms.fqe import FQE, FQETrainer, _device_key
     if value_reduce not in L.PLAN_REDUCE:
         raise ValueError(f"value_reduce {value_reduce!r}: one of {sorted(L.PLAN_REDUCE)}")
     if terminal is None:
+        if risk_alpha is not None:
+            raise ValueError("risk_alpha= without terminal=: the tail is taken over a quantile FQE's outputs")
         return None
     if isinstance(terminal, FQETrainer):
         fqe, rs, cs = terminal.model, float(terminal.reward_scale), float(terminal.cost_scale)
@@ -85,9 +108,14 @@ def check_terminal(model, venv, kind: str, terminal, gamma, value_reduce: str = 
         fqe, rs, cs = terminal, 1.0, 1.0
     else:
         raise TypeError(f"terminal= takes an FQE or an FQETrainer, not {type(terminal).__name__}")
-    if getattr(fqe, "num_quantiles", None) is not None:
-        raise TypeError("terminal= with quantile critics (FQE(num_quantiles=...)): osrl_plan_terminal evaluates one-output "
-                        "critics, a distributional terminal value is out of scope")
+    from ..common.model_env import ModelVecEnv
+    if not isinstance(venv, ModelVecEnv):  # (check_plan's refusal, for a caller that comes here alone)
+        raise TypeError(f"terminal= is judged against a ModelVecEnv, not {type(venv).__name__}")
+    alphas, M = None, getattr(fqe, "num_quantiles", None)
+    if M is not None:
+        alphas, _ = check_risk_alpha(risk_alpha, M)
+    elif risk_alpha is not None:
+        raise ValueError("risk_alpha= with a scalar FQE: build the terminal with FQE(num_quantiles=M)")
     if kind == "bcql":
         raise TypeError("terminal= with BCQ-L: its action at the horizon needs decode noise, out of scope")
     if extra_obs is not None:
@@ -109,7 +137,7 @@ def check_terminal(model, venv, kind: str, terminal, gamma, value_reduce: str = 
     if max(fqe.c_hidden_sizes) > L.PLAN_TERMINAL_NARROW and fqe.state_dim + fqe.action_dim > L.PLAN_TERMINAL_WIDE_INPUT:
         raise ValueError(f"terminal=: critics wider than {L.PLAN_TERMINAL_NARROW} take states and actions of at most "
                          f"{L.PLAN_TERMINAL_WIDE_INPUT} columns together")
-    return Terminal(fqe, rs, cs, L.PLAN_REDUCE[value_reduce])
+    return Terminal(fqe, rs, cs, L.PLAN_REDUCE[value_reduce], alphas)
 
 
 def check_budget(cost_budget, num_envs: int) -> np.ndarray:
@@ -159,14 +187,23 @@ class ModelPlanner(ModelCollector):
     "pessimistic" = the lowest return and the highest cost); ``last_V`` ``[N, K, 2]`` holds ``(Vr, Vc)``.  A candidate that
     halted carries the absorbing state's tail instead: ``halt_reward / (1 - gamma)`` and ``halt_cost * cost_scale / (1 -
     gamma)``, times its own ``g`` -- walking into the model's ignorance must not look cheaper than staying out of it.
-    Without ``terminal`` the planner issues exactly the launches it issued before, and ``last_V`` is None."""
+    Without ``terminal`` the planner issues exactly the launches it issued before, and ``last_V`` is None.
+
+    A quantile ``terminal`` (``FQE(num_quantiles=M)``) with ``risk_alpha = (alpha_reward, alpha_cost)`` (a float: both; None:
+    1.0, the quantile means): per member and candidate the ``M`` outputs at ``(s_H, pi(s_H))`` are sorted, ``Q_r,m`` above
+    becomes the mean of the ``k_r = ceil(alpha_reward M)`` smallest and ``Q_c,m`` the mean of the ``k_c = ceil(alpha_cost
+    M)`` largest (``estimate_risk``'s rule), and everything else reads as above: ``last_V`` holds these CVaR values,
+    ``last_V_mean`` ``[N, K, 2]`` the same reduction of the all-``M`` means (diagnostics; None otherwise).  A NaN among a
+    member's quantiles makes that member's values NaN, and the select skips such a candidate.  ``risk_alpha`` may be set
+    between calls: the terminal launch lies outside the captured graph, nothing is recaptured.  The H imagined steps
+    themselves stay risk-neutral; crossing quantiles are not prevented; FQE's extrapolation error applies to each."""
 
     def __init__(self, model, venv, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None,
                  num_envs: int = 1, horizon: int = 1, noise_std: float = 0.3, gamma: float = 1.0,
                  temperature: float = 0.0, seed: int = 0, z: Optional[torch.Tensor] = None, use_graph: bool = True,
-                 terminal=None, value_reduce: str = "mean"):
+                 terminal=None, value_reduce: str = "mean", risk_alpha=None):
         K = check_plan(venv, num_envs, horizon, noise_std, temperature)  # (before any device work)
-        term = check_terminal(model, venv, kind, terminal, gamma, value_reduce, extra_obs)
+        term = check_terminal(model, venv, kind, terminal, gamma, value_reduce, extra_obs, risk_alpha)
         super().__init__(model, venv, kind, cost_scale, extra_obs, seed, z, use_graph)
         N, od, ad, dev = int(num_envs), venv.state_dim, model.action_dim, self.obs.device
         self.num_envs, self.candidates, self.horizon = N, K, int(horizon)
@@ -182,12 +219,12 @@ class ModelPlanner(ModelCollector):
         self.action = torch.zeros(N, ad, dtype=torch.float32, device=dev)
         self.chosen = torch.zeros(N, dtype=torch.int32, device=dev)
         self.n_feasible = torch.zeros(N, dtype=torch.int32, device=dev)
-        self.terminal, self._last_V = term, None
+        self.terminal, self._last_V, self._last_V_mean, self._risk_alpha = term, None, None, None
         if term is not None:
             self._build_terminal()
 
     def _build_terminal(self) -> None:
-        """The descriptors ``osrl_plan_terminal`` reads: the policy's (the act paths' ``osrl_policy_t``) and the 2 num_q
+        """The descriptors ``osrl_plan_terminal`` / ``osrl_plan_terminal_quantile`` read: the policy's (the act paths' ``osrl_policy_t``) and the 2 num_q
         online critics', reward members first.  They point at the packed copies, which the fused Adam step keeps current;
         ``repack`` here covers parameters edited from outside a trainer."""
         from ..common.net import net_desc_seq
@@ -203,6 +240,9 @@ class ModelPlanner(ModelCollector):
             _gemv_net(dst, nd)
         self._term_keep = (net0, nets)  # the descriptors hold the parameter views alive
         self._last_V = torch.zeros(self.venv.E, 2, dtype=torch.float32, device=self.obs.device)
+        if fqe.num_quantiles is not None:
+            self._last_V_mean = torch.zeros_like(self._last_V)
+            self.risk_alpha = self.terminal.risk_alpha
 
     @property
     def last_V(self) -> Optional[torch.Tensor]:
@@ -210,16 +250,37 @@ class ModelPlanner(ModelCollector):
         (a halted candidate's critics' values too, though its sums took the halting tail); None without ``terminal``."""
         return None if self._last_V is None else self._last_V.view(self.num_envs, self.candidates, 2)
 
+    @property
+    def last_V_mean(self) -> Optional[torch.Tensor]:
+        """``[N, K, 2]``: ``last_V`` with every member's mean over its ``M`` quantiles in the tail mean's place (the
+        risk-neutral value; it enters no sum); None unless ``terminal`` is a quantile FQE."""
+        return None if self._last_V_mean is None else self._last_V_mean.view(self.num_envs, self.candidates, 2)
+
+    @property
+    def risk_alpha(self) -> Optional[tuple]:
+        """``(alpha_reward, alpha_cost)`` of a quantile terminal, None otherwise."""
+        return self._risk_alpha
+
+    @risk_alpha.setter
+    def risk_alpha(self, v) -> None:
+        if self._last_V_mean is None:
+            raise ValueError("risk_alpha needs a quantile terminal: planner(terminal=<FQE(num_quantiles=M)>)")
+        self._risk_alpha, self._tails = check_risk_alpha(v, self.terminal.fqe.num_quantiles)  # (by value at the launch)
+
     def _terminal(self) -> None:
         t, v, g = self.terminal, self.venv, self.plan_gamma
         halt_r = halt_c = 0.0
         if v.can_halt:
             halt_r, halt_c = v.halt_reward / (1.0 - g), v.halt_cost * self.cost_scale / (1.0 - g)
-        L.check(L.load().osrl_plan_terminal(
-            self._term_policy, self._term_critics, t.fqe.num_q, t.reduce, self.obs.data_ptr(), self.obs.stride(0), v.E,
-            1.0 / t.reward_scale, self.cost_scale / t.cost_scale, halt_r, halt_c,
-            v.halt_step.data_ptr() if v.can_halt else None, self.disc.data_ptr(), self._last_V.data_ptr(), cur_stream()),
-            "osrl_plan_terminal")
+        tail = (self.obs.data_ptr(), self.obs.stride(0), v.E, 1.0 / t.reward_scale, self.cost_scale / t.cost_scale, halt_r,
+                halt_c, v.halt_step.data_ptr() if v.can_halt else None, self.disc.data_ptr(), self._last_V.data_ptr())
+        if t.fqe.num_quantiles is None:
+            L.check(L.load().osrl_plan_terminal(self._term_policy, self._term_critics, t.fqe.num_q, t.reduce, *tail,
+                                                cur_stream()), "osrl_plan_terminal")
+        else:
+            L.check(L.load().osrl_plan_terminal_quantile(
+                self._term_policy, self._term_critics, t.fqe.num_q, t.fqe.num_quantiles, *self._tails, t.reduce, *tail,
+                self._last_V_mean.data_ptr(), cur_stream()), "osrl_plan_terminal_quantile")
 
     @property
     def temperature(self) -> float:

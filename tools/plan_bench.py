@@ -20,6 +20,13 @@ on a ``ModelVecEnv`` of 5 members with hidden [200, 200, 200].
     sync) for scale; the three sides interleave A B C C B A in ONE child process.  With ``--parent`` as well, the
     untouched ``act`` (no terminal) of this tree against the parent's, child processes A B B A, gated like (b).
 
+(d) with ``--quantiles M``, ALONE (parts a to c are not run; the output is profiles/plan_quantile_bench.json): reported, not
+    gated, microseconds per ``act`` with a quantile terminal (``FQE(num_quantiles=M)``, ``risk_alpha = 0.25``: one launch,
+    csrc/plan_value_quantile.hip), with the scalar terminal, and the same per-row CVaR by the existing launch chain
+    (``PolicyForward`` + ``MlpRun`` with M outputs, ``torch.sort`` and the tail mean on E = N K rows, then a stream sync),
+    A B C C B A in one child process.  With ``--parent``: the untouched scalar-terminal ``act`` and ``bench.py`` of this
+    tree against the parent's, child processes A B B A, gated like (b).
+
 Every repeat is kept.  Writes profiles/plan_bench.json (``--out``).  Needs an MI355X: there is no CPU path."""
 import argparse
 import json
@@ -83,13 +90,17 @@ def worker(tree, what, reps):
             torch.cuda.synchronize()
             ms.append((time.perf_counter() - t0) * 1e3)
         out["collect_model_ms"] = ms
-    elif what == "plan":
+    elif what in ("plan", "plan_terminal"):
+        from osrl_amd.algorithms.fqe import FQE
         for n in s["slots"]:
             states = np.stack([e.reset(seed=i)[0] for i, e in enumerate(host_envs(n))]).astype(np.float32)
             for k in s["candidates"]:
                 for h in s["horizons"]:
                     tr, menv = make(n * k, h)
-                    p = tr.planner(menv, n, h, noise_std=0.3)
+                    kw = {}
+                    if what == "plan_terminal":  # (the scalar terminal: what the parent commit has as well)
+                        kw = dict(gamma=0.99, terminal=FQE(tr.model, s["hidden"], 0.99, num_q=2, device="cuda:0"))
+                    p = tr.planner(menv, n, h, noise_std=0.3, **kw)
                     for _ in range(3):
                         p.act(states, 5.0)
                     us = []
@@ -127,6 +138,38 @@ def worker(tree, what, reps):
                                 us[name].append((time.perf_counter() - t0) * 1e6)
                     out[f"N{n}_K{k}_H{h}"] = us
                     del p0, p1, pi, rq, fqe, tr, menv
+    elif what.startswith("quantile"):
+        from osrl_amd.algorithms.fqe import FQE, tail_count
+        from osrl_amd.engine.core import MlpRun
+        from osrl_amd.engine.fqe import PolicyForward, _critic_descs
+        dev, M, alpha = torch.device("cuda:0"), int(what[8:]), 0.25
+        for n in s["slots"]:
+            states = np.stack([e.reset(seed=i)[0] for i, e in enumerate(host_envs(n))]).astype(np.float32)
+            for k in s["candidates"]:
+                for h in s["horizons"]:
+                    tr, menv = make(n * k, h)
+                    fs = FQE(tr.model, s["hidden"], 0.99, num_q=2, device="cuda:0")
+                    fq = FQE(tr.model, s["hidden"], 0.99, num_q=2, num_quantiles=M, device="cuda:0")
+                    kw = dict(noise_std=0.3, gamma=0.99)
+                    ps = tr.planner(menv, n, h, terminal=fs, **kw)
+                    pq = tr.planner(menv, n, h, terminal=fq, risk_alpha=alpha, **kw)
+                    pi, rq = PolicyForward(tr.model, "cpq", n * k, dev), MlpRun(_critic_descs(fq)[0], n * k, False, dev)
+                    kt = tail_count(alpha, M)
+
+                    def chain():
+                        th = torch.sort(rq.forward(ps.obs, pi.forward(ps.obs)).view(4, n * k, M), -1).values
+                        cvar = (th[:2, :, :kt].mean(-1).mean(0), th[2:, :, M - kt:].mean(-1).mean(0))  # noqa: F841
+                        torch.cuda.synchronize()
+                    sides = dict(act_scalar=lambda: ps.act(states, 5.0), act_quantile=lambda: pq.act(states, 5.0), chain=chain)
+                    us = {name: [] for name in sides}
+                    for i in range(3 + reps * 10):
+                        for name in ("act_scalar", "act_quantile", "chain", "chain", "act_quantile", "act_scalar"):
+                            t0 = time.perf_counter()
+                            sides[name]()
+                            if i >= 3:
+                                us[name].append((time.perf_counter() - t0) * 1e6)
+                    out[f"N{n}_K{k}_H{h}"] = us
+                    del ps, pq, pi, rq, fs, fq, tr, menv
     else:  # "policy": rollout_many of the bare policy on the same N host environments
         tr, _ = make(16, 5)
         for n in s["slots"]:
@@ -205,27 +248,61 @@ def terminal_rows(reps, rounds):
     return rows
 
 
-def act_against_parent(parent, reps, rounds):
+def quantile_rows(M, reps, rounds):
+    got = {}
+    for _ in range(rounds):
+        for k, v in child(ROOT, f"quantile{M}", reps).items():
+            for name, us in v.items():
+                got.setdefault(k, {}).setdefault(name, []).extend(us)
+    rows = {}
+    for k, v in got.items():
+        a, b, c = summary(v["act_scalar"]), summary(v["act_quantile"]), summary(v["chain"])
+        rows[k] = dict(act_scalar_terminal_us=a, act_quantile_terminal_us=b, launch_chain_us=c,
+                       quantile_minus_scalar_us=round(b["median"] - a["median"], 3))
+    return rows
+
+
+def bench_against_parent(parent, rounds):
+    here, there = [], []
+    for _ in range(rounds):  # A B B A
+        for tree, acc in ((ROOT, here), (parent, there), (parent, there), (ROOT, here)):
+            acc.append(bench_child(tree))
+            print(f"{'this tree' if tree == ROOT else 'parent'}: bench {acc[-1]}", file=sys.stderr, flush=True)
+    return dict(command="python " + " ".join(BENCH_CMD), unit="grad-steps/s", **gate(here, there, higher_is_better=True))
+
+
+def act_against_parent(parent, reps, rounds, what="plan"):
     here, there = {}, {}
     for _ in range(rounds):  # A B B A
         for tree, acc in ((ROOT, here), (parent, there), (parent, there), (ROOT, here)):
-            for k, v in child(tree, "plan", reps).items():
+            for k, v in child(tree, what, reps).items():
                 acc.setdefault(k, []).extend(v)
+            print(f"{'this tree' if tree == ROOT else 'parent'}: {what} done", file=sys.stderr, flush=True)
     return {k: gate(here[k], there[k]) for k in here}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plan_bench.json"))
+    ap.add_argument("--out", default=None, help="profiles/plan_bench.json, with --quantiles profiles/plan_quantile_bench.json")
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit (part b)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=1, help="A B B A rounds")
     ap.add_argument("--terminal", action="store_true", help="part c: act with and without terminal=, and the launch chain")
-    ap.add_argument("--worker", default=None, choices=["untouched", "plan", "policy", "terminal"])
+    ap.add_argument("--quantiles", type=int, default=None, metavar="M", help="part d alone: act with a quantile terminal")
+    ap.add_argument("--worker", default=None)
     ap.add_argument("--tree", default=ROOT)
     args = ap.parse_args()
     if args.worker:
         return worker(os.path.abspath(args.tree), args.worker, args.reps)
+    if args.quantiles:
+        out = dict(shape=SHAPE, quantiles=args.quantiles, risk_alpha=0.25,
+                   quantile_terminal=quantile_rows(args.quantiles, args.reps, args.rounds), scalar_terminal_act_vs_parent=None,
+                   bench_vs_parent=None)
+        if args.parent:
+            parent = os.path.abspath(args.parent)
+            out["scalar_terminal_act_vs_parent"] = act_against_parent(parent, args.reps, args.rounds, "plan_terminal")
+            out["bench_vs_parent"] = bench_against_parent(parent, args.rounds)
+        return write(out, args.out or os.path.join(ROOT, "profiles", "plan_quantile_bench.json"))
     plan, pol, env_us = {}, {}, {}
     for _ in range(args.rounds):  # A B B A: planner, policy, policy, planner
         for what in ("plan", "policy", "policy", "plan"):
@@ -249,10 +326,14 @@ def main():
         out["terminal"] = terminal_rows(args.reps, args.rounds)
         if args.parent:
             out["act_vs_parent"] = act_against_parent(os.path.abspath(args.parent), args.reps, args.rounds)
+    write(out, args.out or os.path.join(ROOT, "profiles", "plan_bench.json"))
+
+
+def write(out, path):
     import torch  # (after the children: this process never opens the device before them)
     out["device"] = torch.cuda.get_device_name(0)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
     print(json.dumps(out))
