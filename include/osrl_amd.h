@@ -1564,6 +1564,33 @@ int osrl_plan_terminal_quantile(const osrl_policy_t* policy, const osrl_gemv_net
                                 float c_mul, float halt_r, float halt_c, const int32_t* halt_step /* [E] or NULL */,
                                 float* disc /* [E,4] */, float* last_V /* [E,2] */, float* last_V_mean /* [E,2] */,
                                 void* stream);
+/* One CEM refit of a planning run's sampling distribution (plan_refine.hip), between two H-step runs on the noise table
+ * eps[horizon, E, action_dim] that the recording step reads through osrl_collect_t.eps_in (E = slots * candidates, episode
+ * e = n * candidates + k).  Two launches on `stream`, the refit and then the redraw.  Per slot n, with J_k = disc[e][0],
+ * C_k = disc[e][1] as osrl_plan_select reads them:
+ *   the order: feasible (C_k <= budget[n]) before infeasible; feasible by J descending then k ascending; infeasible by C
+ *   ascending, then J descending, then k ascending; a candidate with a NaN in J or C after all others, by k ascending.
+ *   elite_rank[n][k] = the number of candidates before k (a permutation of 0 .. candidates - 1).
+ *   n_e = min(n_elite, number of candidates without a NaN); the elites are the candidates of rank < n_e.
+ *   u_k[t][j] = (k == 0 ? 0 : eps[t][e][j])  (candidate 0 has sigma 0: its offset is 0 whatever the table holds)
+ *   m_el = (sum u) / n_e,   s_el = sqrt((sum (u - m_el)^2) / n_e): fp64, the sums over the elites in ascending rank, every
+ *   operation rounded once (no fused multiply-add);  with mom = (double)momentum:
+ *   mu'[n][t][j] = (float)(mom * mu + (1 - mom) * m_el),   sd' = (float)max(mom * sd + (1 - mom) * s_el, (double)min_std);
+ *   n_e == 0: mu and sd stay as they are.
+ *   The redraw, for every t, e, j:  k == 0: eps' = 0;   k == 1: eps' = mu' exactly (the refitted mean plan is always a
+ *   candidate);   k >= 2: eps' = fmaf(sd', z, mu'),  z = z_in[t][e][j] when z_in is given, else word j & 3 of the Box-Muller
+ *   normals (normal_word) of Philox4x32-10(counter {episode_base + e, (round << 16) | t, j >> 2, 18}, key *seed): a function
+ *   of (seed word, episode id, round, t, column) alone, on a stream no other draw uses.
+ * round == 0 starts a call: no score is read, mu = 0, sd = 1, elite_rank[n][k] = k, and the redraw as above (z for k >= 2).
+ * -1 before any launch for a NULL pointer (z_in aside; seed may be NULL beside z_in), candidates outside
+ * 1 .. OSRL_PLAN_MAX_CANDIDATES, horizon outside 1 .. 65536 and round outside 0 .. 65535 (they share one counter word),
+ * action_dim < 1, n_elite < 1, momentum outside [0, 1), min_std negative or not finite, a table of 2^31 floats or more. */
+int osrl_plan_refit(const float* disc /* [E,4] */, const float* budget /* [slots] */,
+                    float* eps /* [horizon, E, action_dim] */, float* mu /* [slots, horizon, action_dim] */,
+                    float* sd /* [slots, horizon, action_dim] */, int32_t slots, int32_t candidates, int32_t horizon,
+                    int32_t action_dim, int32_t n_elite, float momentum, float min_std, int32_t round,
+                    const uint64_t* seed, uint32_t episode_base, const float* z_in /* [horizon, E, action_dim] or NULL */,
+                    int32_t* elite_rank /* [slots, candidates] */, void* stream);
 /* The train step's preparation (engine/dynamics.py): xs[b] = (obs[b] - mu_s) / sd_s  [rows, state_dim];
  * target[b] = {(nobs[b] - obs[b] - mu_d) / sd_d, (rew[b] - mu_r) / sd_r, cost[b]}  [rows, state_dim + 2]. */
 int osrl_dyn_prepare(const float* obs, const float* nobs, const float* rew, const float* cost, const float* mu_s,

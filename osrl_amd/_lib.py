@@ -192,6 +192,7 @@ class ModelEnvT(C.Structure):  # osrl_model_env_t
 
 MODEL_ENV_UNC = {"disagreement": 0, "max_std": 1}  # OSRL_MODEL_ENV_UNC_*
 PLAN_MAX_CANDIDATES = 1024  # OSRL_PLAN_MAX_CANDIDATES: candidates per slot of osrl_plan_select
+PLAN_REFINE_MAX_HORIZON = 1 << 16  # osrl_plan_refit: the step and the round share one Philox counter word
 PLAN_REDUCE = {"mean": 0, "pessimistic": 1}  # OSRL_PLAN_REDUCE_*: how osrl_plan_terminal joins the ensemble members
 PLAN_TERMINAL_MAX_Q, PLAN_TERMINAL_NARROW, PLAN_TERMINAL_WIDE_INPUT = 4, 256, 448  # OSRL_PLAN_TERMINAL_*
 
@@ -317,6 +318,7 @@ PROTOTYPES = {
                            _vp],
     "osrl_plan_terminal_quantile": [_P(PolicyT), _P(GemvNetT), _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _f32,
                                     _f32, _f32, _vp, _vp, _vp, _vp, _vp],
+    "osrl_plan_refit": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _u32, _vp, _vp, _vp],
     "osrl_dyn_prepare": [_vp] * 10 + [_i32, _i32, _vp, _vp, _vp],
     "osrl_dyn_member_loss": [_P(DynLossT), _vp],
     "osrl_fqe_quantile_loss": [_P(FqeQuantileT), _vp],

@@ -180,7 +180,7 @@ class RolloutMixin:
                       lambda: ModelCollector(self.model, menv, *key[1:], use_graph=getattr(self, "use_graph", True)))
 
     def planner(self, menv, num_envs, horizon, noise_std=0.3, gamma=1.0, temperature=0.0, seed=0, terminal=None,
-                value_reduce="mean", risk_alpha=None):
+                value_reduce="mean", risk_alpha=None, refine_rounds=0, num_elites=None, refine_momentum=0.0, min_std=0.05):
         """A ``ModelPlanner`` (engine/mpc.py) of the current policy on the ``ModelVecEnv`` ``menv``: policy-guided
         shooting at act time.  ``menv.E == num_envs * K``: each of the ``num_envs`` real states handed to
         ``planner.act(states, cost_budget)`` fans out into K imagined episodes of ``horizon`` steps, candidate 0 following
@@ -199,9 +199,16 @@ class RolloutMixin:
         ``(alpha_reward, alpha_cost)`` in (0, 1] -- the return is closed with the mean of the ``ceil(alpha_reward M)``
         lowest quantiles at ``(s_H, pi(s_H))``, the cost with the mean of the ``ceil(alpha_cost M)`` highest, so the
         budget bounds the upper-tail CVaR of the cost-to-go; None: the quantile means.  ``planner.risk_alpha`` may be
-        set between calls."""
-        from ..engine.mpc import ModelPlanner, check_plan, check_terminal
-        check_plan(menv, num_envs, horizon, noise_std, temperature)
+        set between calls.
+        ``refine_rounds = R > 0``: CEM refinement (csrc/plan_refine.hip ``osrl_plan_refit``) -- the call imagines R + 1
+        times, between two rounds refitting each slot's sampling distribution over the H-step noise to the ``num_elites``
+        (None: ``max(1, K // 10)``) best candidates under the select's own order, mixed with ``refine_momentum`` in [0, 1)
+        and floored at ``min_std``; candidate 0 stays the policy's proposal, candidate 1 is the refitted mean plan
+        (engine/mpc.py ``check_refine`` lists the refusals: K < 3, and BCQ-L, whose decode noise is drawn per call
+        here).  0, the default: the planner as it was."""
+        from ..engine.mpc import ModelPlanner, check_plan, check_refine, check_terminal
+        K = check_plan(menv, num_envs, horizon, noise_std, temperature)
+        check_refine(K, self.EVAL_KIND, None, refine_rounds, num_elites, refine_momentum, min_std)
         extra = None if terminal is None else self._eval_extra()
         check_terminal(getattr(self, "model", None), menv, self.EVAL_KIND, terminal, gamma, value_reduce, extra,
                        risk_alpha)
@@ -210,7 +217,9 @@ class RolloutMixin:
         return ModelPlanner(self.model, menv, self.EVAL_KIND, 1.0 if cs is None else float(cs), self._eval_extra(),
                             num_envs=num_envs, horizon=horizon, noise_std=noise_std, gamma=gamma,
                             temperature=temperature, seed=seed, use_graph=getattr(self, "use_graph", True),
-                            terminal=terminal, value_reduce=value_reduce, risk_alpha=risk_alpha)
+                            terminal=terminal, value_reduce=value_reduce, risk_alpha=risk_alpha,
+                            refine_rounds=refine_rounds, num_elites=num_elites, refine_momentum=refine_momentum,
+                            min_std=min_std)
 
     @torch.no_grad()
     def evaluate_planned(self, planner, envs, eval_episodes, cost_limit):

@@ -14,7 +14,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libosrl_amd.so")
-SOURCES = ["mlp.hip", "linear_split.hip", "mlp_nb.hip", "mlp_nb64.hip", "mlp_dw.hip", "vae_ns.hip", "optim.hip", "rng.hip", "glue.hip", "cdt.hip", "cdt_grad.hip", "env.hip", "model_env.hip", "plan.hip", "plan_value.hip", "plan_value_quantile.hip", "dyn_loss.hip", "fqe_quantile.hip", "compact.hip", "collect.hip", "cdt_collect.hip", "ingest.hip", "augment.hip", "bear.hip", "dice.hip", "act.hip", "act_vec.hip", "cdt_act.hip", "ipc.hip", "seq_ring.hip", "diag.hip"]
+SOURCES = ["mlp.hip", "linear_split.hip", "mlp_nb.hip", "mlp_nb64.hip", "mlp_dw.hip", "vae_ns.hip", "optim.hip", "rng.hip", "glue.hip", "cdt.hip", "cdt_grad.hip", "env.hip", "model_env.hip", "plan.hip", "plan_value.hip", "plan_value_quantile.hip", "plan_refine.hip", "dyn_loss.hip", "fqe_quantile.hip", "compact.hip", "collect.hip", "cdt_collect.hip", "ingest.hip", "augment.hip", "bear.hip", "dice.hip", "act.hip", "act_vec.hip", "cdt_act.hip", "ipc.hip", "seq_ring.hip", "diag.hip"]
 
 
 def _hipcc() -> str:
@@ -76,6 +76,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 FILE_FLAGS = {"cdt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
               "plan_value.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "plan_value_quantile.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],  # (as plan_value.hip)
+              "plan_refine.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],  # (the redraw's four fmaf per item)
               "fqe_quantile.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}  # (as plan_value.hip)
 OPTIONAL_FLAGS = {("-mllvm", "-amdgpu-mfma-vgpr-form")}  # speed only: dropped where the compiler does not know them
 OBJDIR = os.path.join(LIBDIR, "obj")  # git-ignored (*.o); the objects are a build cache only

@@ -60,6 +60,31 @@ def check_plan(venv, num_envs, horizon, noise_std=0.0, temperature=0.0) -> int:
     return K
 
 
+def check_refine(K, kind="bc", z=None, refine_rounds=0, num_elites=None, refine_momentum=0.0, min_std=0.05) -> int:
+    """A planner's CEM keywords, judged on the host before anything is built or launched: the elite count
+    (``num_elites=None``: ``max(1, K // 10)``).  ValueError for ``refine_rounds < 0`` (or beyond the 65535 the draw's
+    counter word holds), ``num_elites`` outside ``[1, K]``, a momentum outside ``[0, 1)``, a ``min_std`` that is negative
+    or not finite, and with ``refine_rounds > 0``: ``K < 3`` (candidate 0 is the policy and candidate 1 the mean plan:
+    nothing would be drawn) and BCQ-L with unfixed ``z`` (its decode noise has the seed as a by-value launch argument, so
+    every call captures anew: the rounds would replay a graph that each call has to drop)."""
+    R, K = int(refine_rounds), int(K)
+    if not (0 <= R <= 65535):
+        raise ValueError(f"refine_rounds {refine_rounds}: 0 .. 65535")
+    ne = max(1, K // 10) if num_elites is None else int(num_elites)
+    if not (1 <= ne <= K):
+        raise ValueError(f"num_elites {num_elites}: between 1 and the {K} candidates per slot")
+    if not (0.0 <= float(refine_momentum) < 1.0):
+        raise ValueError(f"refine_momentum {refine_momentum}: in [0, 1)")
+    if not (0.0 <= float(min_std) < math.inf):
+        raise ValueError(f"min_std {min_std}: a finite value >= 0")
+    if R > 0 and K < 3:
+        raise ValueError(f"refine_rounds > 0 with {K} candidates per slot: candidate 0 is the policy's proposal and "
+                         f"candidate 1 the mean plan, at least one more has to be drawn")
+    if R > 0 and kind == "bcql" and z is None:
+        raise ValueError("refine_rounds > 0 with BCQ-L needs a fixed z: with drawn decode noise every call captures anew")
+    return ne
+
+
 class Terminal(NamedTuple):
     """What ``check_terminal`` hands the planner: the ``FQE``, the scales its critics were fitted under and the member
     reduction as ``osrl_plan_terminal`` takes it; for a quantile FQE ``risk_alpha`` is the pair ``(alpha_reward,
@@ -196,14 +221,34 @@ class ModelPlanner(ModelCollector):
     ``last_V_mean`` ``[N, K, 2]`` the same reduction of the all-``M`` means (diagnostics; None otherwise).  A NaN among a
     member's quantiles makes that member's values NaN, and the select skips such a candidate.  ``risk_alpha`` may be set
     between calls: the terminal launch lies outside the captured graph, nothing is recaptured.  The H imagined steps
-    themselves stay risk-neutral; crossing quantiles are not prevented; FQE's extrapolation error applies to each."""
+    themselves stay risk-neutral; crossing quantiles are not prevented; FQE's extrapolation error applies to each.
+
+    ``refine_rounds = R > 0`` (``check_refine``; DESIGN.md "CEM refinement"): the call looks R + 1 times.  The planner owns
+    a noise table ``eps [H, E, ad]`` that the recorded steps read in the drawn noise's place (``osrl_collect_t.eps_in``:
+    ``a = clip(pi(s) + noise_std * eps)``), and a sampling distribution ``plan_mean`` / ``plan_std`` ``[N, H, ad]`` in units
+    of ``eps``.  A call sets them to 0 and 1 and fills the table with standard normals (csrc/plan_refine.hip
+    ``osrl_plan_refit``, round 0); every round is the fan-out, the H recorded steps (the captured graph, replayed) and the
+    terminal launch; between two rounds ``osrl_plan_refit`` ranks each slot's candidates by the select's own order, fits
+    mean and standard deviation of the ``num_elites`` best ones' table entries, mixes them in with ``refine_momentum``,
+    floors the deviation at ``min_std`` and redraws the table: candidate 0 stays the policy, candidate 1 is the refitted
+    mean plan, the others ``mean + std * z``.  The select runs once, on the last round's candidates: ``last_J`` /
+    ``last_C`` / ``last_V`` / ``last_first_actions`` / ``chosen`` / ``n_feasible`` describe that round, ``last_eps`` ``[H, N,
+    K, ad]`` is its table and ``elite_rank`` ``[N, K]`` (int32, 0 = best) the last refit's ranking.  Still one upload and
+    one host sync per call; ``num_elites``, ``refine_momentum`` and ``min_std`` are by-value arguments of the refit launch,
+    outside the graph, and may be set between calls.  Not done: warm-starting the mean from the previous call's shifted
+    plan, time-correlated noise, keeping elites across rounds, CDT, data parallelism.  With ``refine_rounds=0`` the
+    planner issues exactly the launches it issued before, builds no table, and the four attributes are None."""
 
     def __init__(self, model, venv, kind: str, cost_scale: float = 1.0, extra_obs: Optional[float] = None,
                  num_envs: int = 1, horizon: int = 1, noise_std: float = 0.3, gamma: float = 1.0,
                  temperature: float = 0.0, seed: int = 0, z: Optional[torch.Tensor] = None, use_graph: bool = True,
-                 terminal=None, value_reduce: str = "mean", risk_alpha=None):
+                 terminal=None, value_reduce: str = "mean", risk_alpha=None, refine_rounds: int = 0, num_elites=None,
+                 refine_momentum: float = 0.0, min_std: float = 0.05):
         K = check_plan(venv, num_envs, horizon, noise_std, temperature)  # (before any device work)
         term = check_terminal(model, venv, kind, terminal, gamma, value_reduce, extra_obs, risk_alpha)
+        n_elite = check_refine(K, kind, z, refine_rounds, num_elites, refine_momentum, min_std)
+        if int(refine_rounds) > 0 and int(horizon) > L.PLAN_REFINE_MAX_HORIZON:
+            raise ValueError(f"refine_rounds > 0 with horizon {horizon}: at most {L.PLAN_REFINE_MAX_HORIZON}")
         super().__init__(model, venv, kind, cost_scale, extra_obs, seed, z, use_graph)
         N, od, ad, dev = int(num_envs), venv.state_dim, model.action_dim, self.obs.device
         self.num_envs, self.candidates, self.horizon = N, K, int(horizon)
@@ -222,6 +267,34 @@ class ModelPlanner(ModelCollector):
         self.terminal, self._last_V, self._last_V_mean, self._risk_alpha = term, None, None, None
         if term is not None:
             self._build_terminal()
+        self.refine_rounds, self.num_elites = int(refine_rounds), n_elite
+        self.refine_momentum, self.min_std = float(refine_momentum), float(min_std)
+        self.plan_mean = self.plan_std = self._eps_table = self.elite_rank = None
+        if self.refine_rounds > 0:  # (fixed addresses for the planner's lifetime: the graph is captured with eps_in set)
+            H = self.horizon
+            self._eps_table = torch.zeros(H, N * K, ad, dtype=torch.float32, device=dev)
+            self.plan_mean = torch.zeros(N, H, ad, dtype=torch.float32, device=dev)
+            self.plan_std = torch.ones(N, H, ad, dtype=torch.float32, device=dev)
+            self.elite_rank = torch.zeros(N, K, dtype=torch.int32, device=dev)
+
+    @property
+    def last_eps(self) -> Optional[torch.Tensor]:
+        """``[H, N, K, ad]``: the noise table the last round ran on (candidate 0's rows are unread); None without
+        ``refine_rounds``."""
+        t = self._eps_table
+        return None if t is None else t.view(self.horizon, self.num_envs, self.candidates, t.shape[-1])
+
+    def _alloc(self, steps: int) -> None:
+        super()._alloc(steps)
+        if self._eps_table is not None:  # (every recorded step of this planner, captured or not, reads the table)
+            self.rec.eps_in = self._eps_table.data_ptr()
+
+    def _refit(self, rnd: int) -> None:
+        L.check(L.load().osrl_plan_refit(
+            self.disc.data_ptr(), self._budget.data_ptr(), self._eps_table.data_ptr(), self.plan_mean.data_ptr(),
+            self.plan_std.data_ptr(), self.num_envs, self.candidates, self.horizon, self.model.action_dim, self.num_elites,
+            self.refine_momentum, self.min_std, rnd, self.seed_dev.data_ptr(), self.venv.base_seed & 0xFFFFFFFF, None,
+            self.elite_rank.data_ptr(), cur_stream()), "osrl_plan_refit")
 
     def _build_terminal(self) -> None:
         """The descriptors ``osrl_plan_terminal`` / ``osrl_plan_terminal_quantile`` read: the policy's (the act paths' ``osrl_policy_t``) and the 2 num_q
@@ -330,17 +403,25 @@ class ModelPlanner(ModelCollector):
     def act(self, states, cost_budget) -> np.ndarray:
         """``states``: ``[N, od]`` (array or tensor); ``cost_budget``: a float or ``[N]``, each slot's remaining budget in
         ``cost_scale`` units.  Every refusal comes before the first launch."""
-        N, od, H = self.num_envs, self.venv.state_dim, self.horizon
+        N, od, H, R = self.num_envs, self.venv.state_dim, self.horizon, self.refine_rounds
         s, b = check_states(states, N, od), check_budget(cost_budget, N)
+        if R > 0:  # (the three may have been set since the last call)
+            self.num_elites = check_refine(self.candidates, self.kind, True, R, self.num_elites, self.refine_momentum,
+                                           self.min_std)
         host = self._host_in.numpy()
         host[:N * od], host[N * od:] = s.reshape(-1), b
         seed = (self.base_plan_seed + self.calls) & 0xFFFFFFFFFFFFFFFF
         self._begin(H, seed, self._sigma_plan, self.plan_gamma, None)
         self._dev_in.copy_(self._host_in, non_blocking=True)
-        self._fanout()
-        self._drive_recorded(H, min(H, _CHUNK), None)
-        if self.terminal is not None:
-            self._terminal()
+        if R > 0:
+            self._refit(0)
+        for r in range(R + 1):  # (the fan-out resets the sums the recorder keeps, disc included)
+            self._fanout()
+            self._drive_recorded(H, min(H, _CHUNK), None)
+            if self.terminal is not None:
+                self._terminal()
+            if r < R:
+                self._refit(r + 1)
         self._select()
         self.calls += 1
         return self.action.cpu().numpy()

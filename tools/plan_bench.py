@@ -27,6 +27,12 @@ on a ``ModelVecEnv`` of 5 members with hidden [200, 200, 200].
     A B C C B A in one child process.  With ``--parent``: the untouched scalar-terminal ``act`` and ``bench.py`` of this
     tree against the parent's, child processes A B B A, gated like (b).
 
+(e) with ``--refine R``, ALONE (the output is profiles/plan_refine_bench.json): reported, not gated, microseconds per ``act``
+    with ``refine_rounds`` = 0, 1, .., R (csrc/plan_refine.hip: each round is one more fan-out, H-step run and refit, so
+    roughly (rounds + 1) times the R = 0 call), the sides interleaved 0 1 .. R R .. 1 0 in one child process.  With
+    ``--parent``: the untouched ``act`` (``refine_rounds=0``) and ``bench.py`` of this tree against the parent's, child
+    processes A B B A, gated like (b).
+
 Every repeat is kept.  Writes profiles/plan_bench.json (``--out``).  Needs an MI355X: there is no CPU path."""
 import argparse
 import json
@@ -138,6 +144,23 @@ def worker(tree, what, reps):
                                 us[name].append((time.perf_counter() - t0) * 1e6)
                     out[f"N{n}_K{k}_H{h}"] = us
                     del p0, p1, pi, rq, fqe, tr, menv
+    elif what.startswith("refine"):
+        rounds = list(range(int(what[6:]) + 1))
+        for n in s["slots"]:
+            states = np.stack([e.reset(seed=i)[0] for i, e in enumerate(host_envs(n))]).astype(np.float32)
+            for k in s["candidates"]:
+                for h in s["horizons"]:
+                    tr, menv = make(n * k, h)
+                    ps = [tr.planner(menv, n, h, noise_std=0.3, refine_rounds=r) for r in rounds]
+                    us = {f"R{r}": [] for r in rounds}
+                    for i in range(3 + reps * 10):
+                        for r in rounds + rounds[::-1]:  # A B C D D C B A
+                            t0 = time.perf_counter()
+                            ps[r].act(states, 5.0)
+                            if i >= 3:
+                                us[f"R{r}"].append((time.perf_counter() - t0) * 1e6)
+                    out[f"N{n}_K{k}_H{h}"] = us
+                    del ps, tr, menv
     elif what.startswith("quantile"):
         from osrl_amd.algorithms.fqe import FQE, tail_count
         from osrl_amd.engine.core import MlpRun
@@ -262,6 +285,20 @@ def quantile_rows(M, reps, rounds):
     return rows
 
 
+def refine_rows(R, reps, rounds):
+    got = {}
+    for _ in range(rounds):
+        for k, v in child(ROOT, f"refine{R}", reps).items():
+            for name, us in v.items():
+                got.setdefault(k, {}).setdefault(name, []).extend(us)
+    rows = {}
+    for k, v in got.items():
+        base = summary(v["R0"])
+        rows[k] = {f"act_{name}_us": summary(us) for name, us in v.items()}
+        rows[k]["ratio_to_R0"] = {name: round(summary(us)["median"] / base["median"], 3) for name, us in v.items()}
+    return rows
+
+
 def bench_against_parent(parent, rounds):
     here, there = [], []
     for _ in range(rounds):  # A B B A
@@ -289,6 +326,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=1, help="A B B A rounds")
     ap.add_argument("--terminal", action="store_true", help="part c: act with and without terminal=, and the launch chain")
     ap.add_argument("--quantiles", type=int, default=None, metavar="M", help="part d alone: act with a quantile terminal")
+    ap.add_argument("--refine", type=int, default=None, metavar="R", help="part e alone: act with 1 .. R refinement rounds")
     ap.add_argument("--worker", default=None)
     ap.add_argument("--tree", default=ROOT)
     args = ap.parse_args()
@@ -303,6 +341,14 @@ def main():
             out["scalar_terminal_act_vs_parent"] = act_against_parent(parent, args.reps, args.rounds, "plan_terminal")
             out["bench_vs_parent"] = bench_against_parent(parent, args.rounds)
         return write(out, args.out or os.path.join(ROOT, "profiles", "plan_quantile_bench.json"))
+    if args.refine:
+        out = dict(shape=SHAPE, refine_rounds=args.refine, refine=refine_rows(args.refine, args.reps, args.rounds),
+                   act_vs_parent=None, bench_vs_parent=None)
+        if args.parent:
+            parent = os.path.abspath(args.parent)
+            out["act_vs_parent"] = act_against_parent(parent, args.reps, args.rounds)
+            out["bench_vs_parent"] = bench_against_parent(parent, args.rounds)
+        return write(out, args.out or os.path.join(ROOT, "profiles", "plan_refine_bench.json"))
     plan, pol, env_us = {}, {}, {}
     for _ in range(args.rounds):  # A B B A: planner, policy, policy, planner
         for what in ("plan", "policy", "policy", "plan"):
