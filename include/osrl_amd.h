@@ -1474,6 +1474,27 @@ int osrl_model_env_collect_gauss_halt(const osrl_model_env_gauss_t* env, const o
                                       const osrl_collect_t* rec, const float* act, float* state, float* obs,
                                       int32_t obs_ld, float* acc, float* unc, float* row_unc, int32_t episodes,
                                       void* stream);
+/* The eight launches above in one entry, member-parallel (model_env_split.hip): a grid of ceil(episodes / 16) x n_models
+ * workgroups, one per 16-episode tile AND member, for launches of few tiles (a planner's candidates) that the one-workgroup-
+ * per-tile form runs as n_models * n_layers layers in a row.  Every workgroup stages its tile as the plain step does, runs
+ * ITS member's layers, writes the member's output tile to member_out and signs in on arrive[tile]; the last of a tile's
+ * n_models workgroups to sign in reads the tiles back in member order and finishes the step.  Nobody waits for anybody.
+ * Every output has the bits of the entry point it stands for:
+ *   exactly one of env / gauss is non-NULL (gauss: the _gauss forms);  pess non-NULL: the _halt forms;
+ *   rec non-NULL: the _collect forms (row_unc optional, step_out unread);  rec NULL: the _step forms (row_unc unread).
+ * member_out: ceil(episodes / 16) * n_models * 16 * OSRL_MODEL_ENV_SPLIT_ROW(state_dim, gauss != NULL) floats of scratch,
+ *   overwritten by every launch (per row the od + 2 output columns, then for Gaussian members od + 1 values sg_m[k]^2 and
+ *   sqrt(sum_{k < od} sg_m[k]^2 / od)).
+ * arrive: int32 [ceil(episodes / 16)], zero before the first launch; a launch that completes leaves it zero (the last
+ *   sign-in stores 0), so consecutive launches and the replays of a captured graph need no memset in between.  Two
+ *   launches that share member_out / arrive must not overlap (one stream, or ordered otherwise).
+ * -1 before any launch for whatever the entry it stands for refuses, for both or neither of env / gauss, and for a NULL
+ * member_out / arrive. */
+#define OSRL_MODEL_ENV_SPLIT_ROW(od, gauss) ((((gauss) ? 2 * (od) + 4 : (od) + 2) + 3) & ~3)
+int osrl_model_env_step_split(const osrl_model_env_t* env, const osrl_model_env_gauss_t* gauss,
+                              const osrl_model_env_pess_t* pess, const osrl_collect_t* rec, float* row_unc,
+                              const float* act, float* state, float* obs, int32_t obs_ld, float* acc, float* unc,
+                              float* step_out, int32_t episodes, float* member_out, int32_t* arrive, void* stream);
 /* Variable-length recorded rollouts made dense (compact.hip).  src / dst: the seven DSRL tables of an osrl_collect_t, whose
  * other fields are not read, episode-major with pitch episode_len in src; row_unc optional, given for both or neither.
  * len_e = (int)acc[e][2] clamped to [0, episode_len];  offsets[e] = sum_{i < e} len_i (int64 [episodes + 1], device

@@ -181,6 +181,11 @@ MODEL_ENV_MODES = {"mean": MODEL_ENV_MEAN, "member": MODEL_ENV_MEMBER, "random":
 MODEL_ENV_MAX_WIDTH, MODEL_ENV_MAX_STATE = 512, 256  # OSRL_MODEL_ENV_MAX_WIDTH / _MAX_STATE: the step kernel's LDS tile
 
 
+def model_env_split_row(od: int, gauss: bool) -> int:
+    """OSRL_MODEL_ENV_SPLIT_ROW: floats per row of ``osrl_model_env_step_split``'s ``member_out``."""
+    return ((2 * od + 4 if gauss else od + 2) + 3) & ~3
+
+
 class ModelEnvT(C.Structure):  # osrl_model_env_t
     _fields_ = [("net", GemvNetT * MAX_NETS)] + \
         [(n, C.c_void_p) for n in ("mu_s", "sd_s", "mu_d", "sd_d", "mu_r", "sd_r", "s_lo", "s_hi", "seed",
@@ -310,6 +315,8 @@ PROTOTYPES = {
                                        _vp],
     "osrl_model_env_collect_gauss_halt": [_P(ModelEnvGaussT), _P(ModelEnvPessT), _P(CollectT), _vp, _vp, _vp, _i32, _vp,
                                           _vp, _vp, _i32, _vp],
+    "osrl_model_env_step_split": [_P(ModelEnvT), _P(ModelEnvGaussT), _P(ModelEnvPessT), _P(CollectT), _vp, _vp, _vp, _vp,
+                                  _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "osrl_collect_compact": [_P(CollectT), _vp, _P(CollectT), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "osrl_model_env_branch": [_vp, _i64, _vp, _i64, _i32, _vp, _u32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
     "osrl_plan_fanout": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],

@@ -364,6 +364,8 @@ class ModelCollector(_Tables, BatchedRollout):
         v = self.venv
         # (a probabilistic model's descriptor: the sampled next state and the penalised reward are what is recorded)
         c = self.env_c
+        if v.split_members:  # the member-parallel form of the same step (csrc/model_env_split.hip), every descriptor
+            return v._step_split(c, self._rec_now(), self._row_unc.data_ptr(), act, self.obs, None)
         if isinstance(c, L._HaltDesc):  # halting / the pessimistic cost: the same descriptor beside osrl_model_env_pess_t
             name, head = c.collect_fn, (C.byref(c.env), C.byref(c.pess))
         else:

@@ -195,6 +195,48 @@ def gauss_worker(tree, what, reps, fit_steps):
     print("RESULT " + json.dumps(out))
 
 
+SPLIT_EPISODES = (64, 128, 256, 512, 1024)
+
+
+def split_main(args):
+    """``--split``: ``evaluate`` (200 steps, CPQ at C2's shape, 5 x [200, 200, 200]) on ``ModelVecEnv(split_members=True)``
+    against the plain environment, A B B A in this process, medians; ``crossover_episodes`` is the smallest measured
+    episode count at which the split form no longer wins.  Merged into profiles/model_env_split_bench.json."""
+    sys.path.insert(0, ROOT)
+    import torch
+    from osrl_amd.algorithms import CPQ, CPQTrainer, Dynamics
+    from osrl_amd.common.model_env import ModelVecEnv
+    from osrl_amd.common.replay import synthetic_transitions
+    od, ad = 76, 2
+    d = synthetic_transitions(4096, od, ad, seed=1)
+    torch.manual_seed(0)
+    dyn = Dynamics(od, ad, [200, 200, 200], num_models=5, device="cuda:0")
+    dyn.fit_normalizer(d)
+    cpq = CPQ(od, ad, 1.0, [256, 256], [256, 256], 400, 10, episode_len=EL, device="cuda:0")
+    rows, cross = {}, None
+    for E in SPLIT_EPISODES:
+        trs = [CPQTrainer(cpq, env=ModelVecEnv(dyn, d["observations"][:E], E, EL, split_members=s), stats_mode="none")
+               for s in (False, True)]
+        for tr in trs:
+            tr.evaluate(E)  # (warm: capture)
+        sp, ss = abba(lambda: trs[0].evaluate(E), lambda: trs[1].evaluate(E), args.rounds)
+        rows[f"episodes_{E}"] = dict(plain_ms=sp, split_ms=ss, plain_us_per_step=round(sp["median"] / EL * 1e3, 2),
+                                     split_us_per_step=round(ss["median"] / EL * 1e3, 2),
+                                     plain_over_split=round(sp["median"] / ss["median"], 3))
+        if cross is None and ss["median"] >= sp["median"]:
+            cross = E
+    out = {}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            out = json.load(f)
+    out.update(device=torch.cuda.get_device_name(0), evaluate_split_vs_plain=rows, crossover_episodes=cross)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def gauss_child(tree, what, reps, fit_steps):
     cmd = [sys.executable, os.path.abspath(__file__), "--worker", what, "--tree", tree, "--reps", str(reps),
            "--fit-steps", str(fit_steps)]
@@ -261,13 +303,17 @@ def main():
     ap.add_argument("--probabilistic", action="store_true", help="the Gaussian ensemble's A/B (see the module docstring)")
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit (--probabilistic, parts a and b)")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--split", action="store_true", help="evaluate on split_members=True against the plain environment")
     ap.add_argument("--worker", default=None, choices=["untouched", "gauss"])
     ap.add_argument("--tree", default=ROOT)
     args = ap.parse_args()
     name = "model_env_gauss_bench.json" if args.probabilistic else "model_env_bench.json"
-    args.out = args.out or os.path.join(ROOT, "profiles", name)
+    args.out = args.out or os.path.join(ROOT, "profiles", "model_env_split_bench.json" if args.split else name)
     if args.worker:
         return gauss_worker(os.path.abspath(args.tree), args.worker, args.reps, args.fit_steps)
+    if args.split:
+        args.rounds = args.rounds or 3
+        return split_main(args)
     if args.probabilistic:
         args.rounds = args.rounds or 2
         return gauss_main(args)

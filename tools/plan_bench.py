@@ -33,6 +33,12 @@ on a ``ModelVecEnv`` of 5 members with hidden [200, 200, 200].
     ``--parent``: the untouched ``act`` (``refine_rounds=0``) and ``bench.py`` of this tree against the parent's, child
     processes A B B A, gated like (b).
 
+(f) with ``--split``, ALONE (merged into profiles/model_env_split_bench.json, which tools/model_env_bench.py --split writes
+    too): reported, not gated, microseconds per ``act`` on ``ModelVecEnv(split_members=True)`` (csrc/model_env_split.hip:
+    one workgroup per tile and member) against the plain environment, the same policy and model, A B B A in one child
+    process.  With ``--parent``: the untouched plain ``act`` and ``bench.py`` of this tree against the parent's, child
+    processes A B B A, gated like (b).
+
 Every repeat is kept.  Writes profiles/plan_bench.json (``--out``).  Needs an MI355X: there is no CPU path."""
 import argparse
 import json
@@ -161,6 +167,25 @@ def worker(tree, what, reps):
                                 us[f"R{r}"].append((time.perf_counter() - t0) * 1e6)
                     out[f"N{n}_K{k}_H{h}"] = us
                     del ps, tr, menv
+    elif what == "split":
+        for n in s["slots"]:
+            states = np.stack([e.reset(seed=i)[0] for i, e in enumerate(host_envs(n))]).astype(np.float32)
+            for k in s["candidates"]:
+                for h in s["horizons"]:
+                    ps = {}
+                    for name in ("plain", "split"):  # (make() seeds alike: the same policy and model on both sides)
+                        tr, menv = make(n * k, h)
+                        menv.split_members = name == "split"
+                        ps[name] = (tr.planner(menv, n, h, noise_std=0.3), tr, menv)
+                    us = {name: [] for name in ps}
+                    for i in range(3 + reps * 10):
+                        for name in ("plain", "split", "split", "plain"):
+                            t0 = time.perf_counter()
+                            ps[name][0].act(states, 5.0)
+                            if i >= 3:
+                                us[name].append((time.perf_counter() - t0) * 1e6)
+                    out[f"N{n}_K{k}_H{h}"] = us
+                    del ps
     elif what.startswith("quantile"):
         from osrl_amd.algorithms.fqe import FQE, tail_count
         from osrl_amd.engine.core import MlpRun
@@ -299,6 +324,29 @@ def refine_rows(R, reps, rounds):
     return rows
 
 
+def split_rows(reps, rounds):
+    got = {}
+    for _ in range(rounds):
+        for k, v in child(ROOT, "split", reps).items():
+            for name, us in v.items():
+                got.setdefault(k, {}).setdefault(name, []).extend(us)
+    rows = {}
+    for k, v in got.items():
+        a, b = summary(v["plain"]), summary(v["split"])
+        rows[k] = dict(act_plain_us=a, act_split_us=b, plain_over_split=round(a["median"] / b["median"], 3))
+    return rows
+
+
+def merge_into(path, update):
+    """``update``'s keys into the JSON at ``path`` (tools/model_env_bench.py --split writes the same file)."""
+    out = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            out = json.load(f)
+    out.update(update)
+    return write(out, path)
+
+
 def bench_against_parent(parent, rounds):
     here, there = [], []
     for _ in range(rounds):  # A B B A
@@ -327,6 +375,7 @@ def main():
     ap.add_argument("--terminal", action="store_true", help="part c: act with and without terminal=, and the launch chain")
     ap.add_argument("--quantiles", type=int, default=None, metavar="M", help="part d alone: act with a quantile terminal")
     ap.add_argument("--refine", type=int, default=None, metavar="R", help="part e alone: act with 1 .. R refinement rounds")
+    ap.add_argument("--split", action="store_true", help="part f alone: act on a split_members environment against the plain one")
     ap.add_argument("--worker", default=None)
     ap.add_argument("--tree", default=ROOT)
     args = ap.parse_args()
@@ -349,6 +398,13 @@ def main():
             out["act_vs_parent"] = act_against_parent(parent, args.reps, args.rounds)
             out["bench_vs_parent"] = bench_against_parent(parent, args.rounds)
         return write(out, args.out or os.path.join(ROOT, "profiles", "plan_refine_bench.json"))
+    if args.split:
+        out = dict(plan_shape=SHAPE, act_split_vs_plain=split_rows(args.reps, args.rounds))
+        if args.parent:
+            parent = os.path.abspath(args.parent)
+            out["plain_act_vs_parent"] = act_against_parent(parent, args.reps, args.rounds)
+            out["bench_vs_parent"] = bench_against_parent(parent, args.rounds)
+        return merge_into(args.out or os.path.join(ROOT, "profiles", "model_env_split_bench.json"), out)
     plan, pol, env_us = {}, {}, {}
     for _ in range(args.rounds):  # A B B A: planner, policy, policy, planner
         for what in ("plan", "policy", "policy", "plan"):
