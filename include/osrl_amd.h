@@ -1401,27 +1401,27 @@ typedef struct {
   int32_t pad_;
   float max_action, cost_scale, reward_penalty, pad2_;
 } osrl_model_env_t;
-int osrl_model_env_step(const osrl_model_env_t* env, const float* act, float* state, float* obs, int32_t obs_ld,
-                        float* acc, float* unc /* [E,2] */, float* step_out /* optional [E,2] */, int32_t episodes,
-                        void* stream);
-/* osrl_model_env_step with exploration noise, recording what it does (engine/collect.py ModelCollector): the same launch
- * shape and the same body behind a compile-time flag, plus what osrl_env_collect adds to osrl_env_step.  Episode e at its
- * own step t = acc[e][2] (read once per launch; 0 <= t < env->episode_len and the done latch clear, otherwise the launch
- * stores nothing for it -- so no write leaves the tables, whose rows are episodes * env->episode_len):
+/* The step is ONE entry, osrl_model_env_step (declared below the three descriptors it takes); three optional pointers
+ * turn on what the next three comments describe, each behind a compile-time flag of the same kernel body: rec (recording),
+ * gauss in env's place (Gaussian members), pess (halting and the pessimistic cost).
+ *
+ * rec != NULL -- the step with exploration noise, recording what it does (engine/collect.py ModelCollector): the same
+ * launch shape, plus what osrl_env_collect adds to osrl_env_step.  Episode e at its own step t = acc[e][2] (read once
+ * per launch; 0 <= t < env->episode_len and the done latch clear, otherwise the launch stores nothing for it -- so no
+ * write leaves the tables, whose rows are episodes * env->episode_len):
  *   a = clip(fmaf(sigma[e], eps, act[e]), +-max_action) while the input tile is staged; sigma[e] == 0: eps is not read and
- *       the step is osrl_model_env_step's bit for bit;  eps as osrl_env_collect documents it (eps_in or Philox on
+ *       the step is the unrecorded one's bit for bit;  eps as osrl_env_collect documents it (eps_in or Philox on
  *       rec->stream_id, keyed by (seed, episode_base + e, t, column));
  *   row e * episode_len + t: observations = s, actions = a, next_observations = s' (after the clamp), rewards = r (after
  *       reward_penalty: what acc[e][0] sums), costs (raw 0 / 1), terminals = 0, timeouts = (t + 1 >= episode_len);
- *   rec->disc as osrl_env_collect keeps it;  row_unc (optional [episodes * episode_len]) receives the row's d. */
-int osrl_model_env_collect(const osrl_model_env_t* env, const osrl_collect_t* rec, const float* act, float* state,
-                           float* obs, int32_t obs_ld, float* acc, float* unc,
-                           float* row_unc /* optional [E * episode_len] */, int32_t episodes, void* stream);
-/* The same two launches on an ensemble of diagonal Gaussians (algorithms/dynamics.py, probabilistic=True): member m's
- * output row is (od + 1 means | raw cost | od + 1 raw log-variances), 2 od + 3 <= OSRL_MODEL_ENV_MAX_WIDTH columns; the
- * first od + 2 are read exactly as osrl_model_env_step reads them.  With P = od + 1 and, for k < P,
+ *   rec->disc as osrl_env_collect keeps it;  row_unc (optional [episodes * episode_len]) receives the row's d;
+ *   step_out is ignored: the tables carry the step's reward and cost.
+ *
+ * gauss != NULL (and env NULL) -- an ensemble of diagonal Gaussians (algorithms/dynamics.py, probabilistic=True): member
+ * m's output row is (od + 1 means | raw cost | od + 1 raw log-variances), 2 od + 3 <= OSRL_MODEL_ENV_MAX_WIDTH columns;
+ * the first od + 2 are read exactly as the deterministic step reads them.  With P = od + 1 and, for k < P,
  *   lv_m[k] = lo + softplus((hi - softplus(hi - raw_m[k])) - lo),  raw_m[k] = y_m[od + 2 + k],  sg_m[k] = exp(0.5 lv_m[k]):
- *   d = osrl_model_env_step's disagreement over the MEANS, the same expression;
+ *   d = the deterministic step's disagreement over the MEANS, the same expression;
  *   a = max_m sqrt(sum_{k < od} sg_m[k]^2 / od)               (MOPO's largest predicted standard deviation)
  *   u = d (uncertainty == OSRL_MODEL_ENV_UNC_DISAGREEMENT) | a (OSRL_MODEL_ENV_UNC_MAX_STD): u takes d's place in the
  *       reward penalty, in unc[e] and in row_unc;
@@ -1430,7 +1430,7 @@ int osrl_model_env_collect(const osrl_model_env_t* env, const osrl_collect_t* re
  *       eps[k] = noise_in[e * P + k] when noise_in is given (the same at every step), else the standard normal
  *       osrl_rng's normal_word(Philox4x32-10(counter {episode_base + e, the episode's own step, k >> 2, 16}, key *seed), k & 3):
  *       a function of (seed, episode id, step, column) alone.  sample == 0: neither is read.
- * With sample == 0 and uncertainty == DISAGREEMENT the step has the bits of osrl_model_env_step on the members' first
+ * With sample == 0 and uncertainty == DISAGREEMENT the step has the bits of the deterministic step on the members' first
  * od + 2 output columns. */
 enum { OSRL_MODEL_ENV_UNC_DISAGREEMENT = 0, OSRL_MODEL_ENV_UNC_MAX_STD = 1 };
 typedef struct {
@@ -1439,14 +1439,9 @@ typedef struct {
   float logvar_min, logvar_max;
   int32_t sample, uncertainty;
 } osrl_model_env_gauss_t;
-int osrl_model_env_step_gauss(const osrl_model_env_gauss_t* env, const float* act, float* state, float* obs,
-                              int32_t obs_ld, float* acc, float* unc, float* step_out, int32_t episodes, void* stream);
-int osrl_model_env_collect_gauss(const osrl_model_env_gauss_t* env, const osrl_collect_t* rec, const float* act,
-                                 float* state, float* obs, int32_t obs_ld, float* acc, float* unc, float* row_unc,
-                                 int32_t episodes, void* stream);
-/* The same four launches, pessimistic (model_env.hip, compile-time flag kPess): a rollout halts where the model stops
- * knowing, and the cost is inflated by the uncertainty.  u is the signal in use (d, or a under UNC_MAX_STD), c = yh[od + 1].
- * Per live episode e at its own step t, where the plain step forms reward and cost:
+/* pess != NULL -- any of the four combinations above, pessimistic (model_env.hip, compile-time flag kPess): a rollout
+ * halts where the model stops knowing, and the cost is inflated by the uncertainty.  u is the signal in use (d, or a
+ * under UNC_MAX_STD), c = yh[od + 1].  Per live episode e at its own step t, where the plain step forms reward and cost:
  *   cost = (cost_penalty != 0 ? fmaf(cost_penalty, u, c) : c) > 0.5 ? 1 : 0;
  *   halt = u > halt_threshold   (strict: +inf never halts, a NaN u does not halt);  on halt:
  *     r = halt_reward (it replaces the model's reward, penalty included: what acc[e][0] and the discounted sum add and
@@ -1455,41 +1450,36 @@ int osrl_model_env_collect_gauss(const osrl_model_env_gauss_t* env, const osrl_c
  *     a recorded halting row has terminals = 1 and timeouts = 0, also when t + 1 == episode_len.
  *   The next state is written on a halting step too (state, obs, next_observations); unc[e] and row_unc include its u;
  *   sampling is unaffected.  No arithmetic of the members, the mean or the disagreement differs: with
- *   halt_threshold = +inf and cost_penalty = 0 every output has the bits of the entry point without "_halt".
+ *   halt_threshold = +inf and cost_penalty = 0 every output has the bits of the same call without pess.
  * -1 for a NaN threshold or reward, a halt_cost other than 0 / 1, a negative or non-finite cost_penalty. */
 typedef struct {
   float halt_threshold, halt_reward, halt_cost, cost_penalty;
   int32_t* halt_step; /* [episodes] or NULL */
 } osrl_model_env_pess_t;
-int osrl_model_env_step_halt(const osrl_model_env_t* env, const osrl_model_env_pess_t* pess, const float* act,
-                             float* state, float* obs, int32_t obs_ld, float* acc, float* unc, float* step_out,
-                             int32_t episodes, void* stream);
-int osrl_model_env_collect_halt(const osrl_model_env_t* env, const osrl_model_env_pess_t* pess,
-                                const osrl_collect_t* rec, const float* act, float* state, float* obs, int32_t obs_ld,
-                                float* acc, float* unc, float* row_unc, int32_t episodes, void* stream);
-int osrl_model_env_step_gauss_halt(const osrl_model_env_gauss_t* env, const osrl_model_env_pess_t* pess,
-                                   const float* act, float* state, float* obs, int32_t obs_ld, float* acc, float* unc,
-                                   float* step_out, int32_t episodes, void* stream);
-int osrl_model_env_collect_gauss_halt(const osrl_model_env_gauss_t* env, const osrl_model_env_pess_t* pess,
-                                      const osrl_collect_t* rec, const float* act, float* state, float* obs,
-                                      int32_t obs_ld, float* acc, float* unc, float* row_unc, int32_t episodes,
-                                      void* stream);
-/* The eight launches above in one entry, member-parallel (model_env_split.hip): a grid of ceil(episodes / 16) x n_models
- * workgroups, one per 16-episode tile AND member, for launches of few tiles (a planner's candidates) that the one-workgroup-
- * per-tile form runs as n_models * n_layers layers in a row.  Every workgroup stages its tile as the plain step does, runs
- * ITS member's layers, writes the member's output tile to member_out and signs in on arrive[tile]; the last of a tile's
+/* The step: one launch, one of eight kernels by which of the three optional pointers are given.
+ *   exactly one of env / gauss is non-NULL;  pess optional;
+ *   rec non-NULL: a recorder osrl_env_collect would accept, and episode_len >= 1 (row_unc optional, step_out unread);
+ *   rec NULL: row_unc unread, step_out optional.
+ * -1 before any launch for both or neither of env / gauss, a rec that is not valid, a NULL act / state / obs / acc / unc,
+ * episodes < 1, obs_ld < state_dim, a descriptor outside the limits above, and what the gauss and pess comments refuse. */
+int osrl_model_env_step(const osrl_model_env_t* env, const osrl_model_env_gauss_t* gauss,
+                        const osrl_model_env_pess_t* pess, const osrl_collect_t* rec,
+                        float* row_unc /* optional [E * episode_len] */, const float* act, float* state, float* obs,
+                        int32_t obs_ld, float* acc, float* unc /* [E,2] */, float* step_out /* optional [E,2] */,
+                        int32_t episodes, void* stream);
+/* The same arguments, plus member_out and arrive: the step member-parallel (model_env_split.hip), a grid of
+ * ceil(episodes / 16) x n_models workgroups, one per 16-episode tile AND member, for launches of few tiles (a planner's
+ * candidates) that the one-workgroup-per-tile form runs as n_models * n_layers layers in a row.  Every workgroup
+ * stages its tile as the plain step does, runs ITS member's layers, writes the member's output tile to member_out and signs in on arrive[tile]; the last of a tile's
  * n_models workgroups to sign in reads the tiles back in member order and finishes the step.  Nobody waits for anybody.
- * Every output has the bits of the entry point it stands for:
- *   exactly one of env / gauss is non-NULL (gauss: the _gauss forms);  pess non-NULL: the _halt forms;
- *   rec non-NULL: the _collect forms (row_unc optional, step_out unread);  rec NULL: the _step forms (row_unc unread).
+ * Every output has the bits of osrl_model_env_step with the same env / gauss / pess / rec.
  * member_out: ceil(episodes / 16) * n_models * 16 * OSRL_MODEL_ENV_SPLIT_ROW(state_dim, gauss != NULL) floats of scratch,
  *   overwritten by every launch (per row the od + 2 output columns, then for Gaussian members od + 1 values sg_m[k]^2 and
  *   sqrt(sum_{k < od} sg_m[k]^2 / od)).
  * arrive: int32 [ceil(episodes / 16)], zero before the first launch; a launch that completes leaves it zero (the last
  *   sign-in stores 0), so consecutive launches and the replays of a captured graph need no memset in between.  Two
  *   launches that share member_out / arrive must not overlap (one stream, or ordered otherwise).
- * -1 before any launch for whatever the entry it stands for refuses, for both or neither of env / gauss, and for a NULL
- * member_out / arrive. */
+ * -1 before any launch for whatever osrl_model_env_step refuses, and for a NULL member_out / arrive. */
 #define OSRL_MODEL_ENV_SPLIT_ROW(od, gauss) ((((gauss) ? 2 * (od) + 4 : (od) + 2) + 3) & ~3)
 int osrl_model_env_step_split(const osrl_model_env_t* env, const osrl_model_env_gauss_t* gauss,
                               const osrl_model_env_pess_t* pess, const osrl_collect_t* rec, float* row_unc,

@@ -244,7 +244,7 @@ FQE_QUANTILE_WAVES = 4  # OSRL_FQE_QUANTILE_WAVES: a workgroup of osrl_fqe_quant
 
 class _HaltDesc:
     """What ``ModelVecEnv.desc`` hands out when halting or the cost penalty is on: the plain descriptor (``env``) and the
-    ``osrl_model_env_pess_t`` beside it -- the two pointer arguments of the ``_halt`` entry points."""
+    ``osrl_model_env_pess_t`` beside it -- ``osrl_model_env_step``'s ``env`` or ``gauss`` argument and its ``pess``."""
     env_type = None
 
     def __init__(self, env, pess: ModelEnvPessT):
@@ -262,12 +262,10 @@ class _HaltDesc:
 
 class ModelEnvHaltT(_HaltDesc):
     env_type = ModelEnvT
-    step_fn, collect_fn = "osrl_model_env_step_halt", "osrl_model_env_collect_halt"
 
 
 class ModelEnvGaussHaltT(_HaltDesc):
     env_type = ModelEnvGaussT
-    step_fn, collect_fn = "osrl_model_env_step_gauss_halt", "osrl_model_env_collect_gauss_halt"
 
 
 POLICY_MAX_ROWS = 4
@@ -304,17 +302,8 @@ _P = C.POINTER
 PROTOTYPES = {
     "osrl_mlp_forward": [_P(MlpT), _P(RowsT), _P(ActsT), _vp],
     "osrl_env_step": [_P(EnvT), _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp],
-    "osrl_model_env_step": [_P(ModelEnvT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
-    "osrl_model_env_collect": [_P(ModelEnvT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
-    "osrl_model_env_step_gauss": [_P(ModelEnvGaussT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
-    "osrl_model_env_collect_gauss": [_P(ModelEnvGaussT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
-    "osrl_model_env_step_halt": [_P(ModelEnvT), _P(ModelEnvPessT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
-    "osrl_model_env_collect_halt": [_P(ModelEnvT), _P(ModelEnvPessT), _P(CollectT), _vp, _vp, _vp, _i32, _vp, _vp, _vp,
-                                    _i32, _vp],
-    "osrl_model_env_step_gauss_halt": [_P(ModelEnvGaussT), _P(ModelEnvPessT), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32,
-                                       _vp],
-    "osrl_model_env_collect_gauss_halt": [_P(ModelEnvGaussT), _P(ModelEnvPessT), _P(CollectT), _vp, _vp, _vp, _i32, _vp,
-                                          _vp, _vp, _i32, _vp],
+    "osrl_model_env_step": [_P(ModelEnvT), _P(ModelEnvGaussT), _P(ModelEnvPessT), _P(CollectT), _vp, _vp, _vp, _vp, _i32,
+                            _vp, _vp, _vp, _i32, _vp],
     "osrl_model_env_step_split": [_P(ModelEnvT), _P(ModelEnvGaussT), _P(ModelEnvPessT), _P(CollectT), _vp, _vp, _vp, _vp,
                                   _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "osrl_collect_compact": [_P(CollectT), _vp, _P(CollectT), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],

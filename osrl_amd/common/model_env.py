@@ -10,7 +10,7 @@ What comes out is a model's opinion: its error grows with the rollout length and
 data.  ``disagreement()`` -- how far the members' predictions lie apart along each episode -- is the trust signal.
 
 Recording: ``collect`` / ``collect_targets`` refuse a ``ModelVecEnv``; ``Trainer.collect_model(menv, ...)`` (engine/collect.py
-``ModelCollector``, csrc/model_env.hip ``osrl_model_env_collect``) records the policy's rollouts on it, k steps from the
+``ModelCollector``, csrc/model_env.hip ``osrl_model_env_step`` with ``rec``) records the policy's rollouts on it, k steps from the
 initial states or from rows of a store, with the penalised reward.
 """
 from __future__ import annotations
@@ -35,7 +35,7 @@ class ModelVecEnv(DeviceVecEnv):
     may be set between runs; ``mode``, ``member`` and ``reward_penalty`` are launch arguments: changing them moves
     ``launch_epoch``, on which a rollout drops its captured graph.
 
-    On a ``Dynamics(probabilistic=True)`` the step is ``osrl_model_env_step_gauss``.  ``sample``: the next state and the
+    On a ``Dynamics(probabilistic=True)`` the step takes an ``osrl_model_env_gauss_t``.  ``sample``: the next state and the
     reward are drawn from the followed member's Gaussian (mode "mean": the mean of the members' variances), the noise a
     function of (``seed``, episode id, step, column) -- Philox stream 16 -- or ``set_noise_in``'s.  ``uncertainty``:
     "disagreement" (the spread of the means) or "max_std", MOPO's ``max_m sqrt(mean_k sigma_m[k]^2)``; the one in use is
@@ -43,12 +43,12 @@ class ModelVecEnv(DeviceVecEnv):
     deterministic model either raises a ``ValueError``.  With the defaults such a model steps bit for bit like a
     deterministic one that holds its members' first ``od + 2`` output rows.
 
-    Pessimism beyond the reward (the ``_halt`` entry points; DESIGN.md "Halting on uncertainty").  ``halt_threshold``
+    Pessimism beyond the reward (the step's ``pess`` argument; DESIGN.md "Halting on uncertainty").  ``halt_threshold``
     (None: never): where the signal in use exceeds it the episode ends at that step -- MOReL's absorbing "unknown" -- with
     ``halt_reward`` in the reward's place and ``halt_cost`` (0 or 1) as the cost; ``halt_step`` (int32 ``[E]`` on the
     device, -1: not halted; ``halted()``) keeps the step.  ``cost_penalty`` kappa: the cost bit is
     ``c + kappa * u > 0.5`` (CAP's inflation).  All four are launch arguments.  With the defaults ``desc()`` hands out the
-    plain descriptors and the plain entry points run.
+    plain descriptors and the step runs without ``pess``.
 
     Elites.  On a ``Dynamics(num_elites=k)`` the environment steps the model's elite members only
     (``model.elite_members()``, ascending): the descriptor holds those k nets and ``n_models = k``, so the mean, the spread,
@@ -287,9 +287,10 @@ class ModelVecEnv(DeviceVecEnv):
             self._split = bool(v)
             self.launch_epoch += 1
 
-    def _step_split(self, desc, rec, row_unc, actions, obs_out, step_out) -> None:
-        """``osrl_model_env_step_split`` for whichever descriptor ``desc()`` handed out: ``step`` (``rec`` None) and
-        ``ModelCollector.body`` (``rec``: its ``osrl_collect_t``) with ``split_members`` on."""
+    def _launch_step(self, desc, rec, row_unc, actions, obs_out, step_out) -> None:
+        """``osrl_model_env_step`` for whichever descriptor ``desc()`` handed out -- ``osrl_model_env_step_split``, the
+        same arguments plus ``member_out`` / ``arrive``, with ``split_members`` on: ``step`` (``rec`` None) and
+        ``ModelCollector.body`` (``rec``: its ``osrl_collect_t``)."""
         import ctypes as C
 
         from .. import _lib as L
@@ -298,11 +299,12 @@ class ModelVecEnv(DeviceVecEnv):
         if isinstance(desc, L._HaltDesc):
             desc, pess = desc.env, C.byref(desc.pess)
         gauss = isinstance(desc, L.ModelEnvGaussT)
-        L.check(L.load().osrl_model_env_step_split(
+        name = "osrl_model_env_step_split" if self._split else "osrl_model_env_step"
+        tail = (self.member_out.data_ptr(), self.arrive.data_ptr()) if self._split else ()
+        L.check(getattr(L.load(), name)(
             None if gauss else C.byref(desc), C.byref(desc) if gauss else None, pess, rec, row_unc, actions.data_ptr(),
             self.state.data_ptr(), obs_out.data_ptr(), obs_out.stride(0), self.acc.data_ptr(), self.unc.data_ptr(),
-            None if step_out is None else step_out.data_ptr(), self.E, self.member_out.data_ptr(),
-            self.arrive.data_ptr(), cur_stream()), "osrl_model_env_step_split")
+            None if step_out is None else step_out.data_ptr(), self.E, *tail, cur_stream()), name)
 
     def halted(self) -> np.ndarray:
         """Per episode the step at which it halted, -1 where it did not (int32 numpy).  Synchronises."""
@@ -400,20 +402,7 @@ class ModelVecEnv(DeviceVecEnv):
 
     def step(self, desc, actions, obs_out, step_out=None) -> None:
         """``step_out`` (optional [E,2]) receives this step's (reward, raw cost)."""
-        import ctypes as C
-
-        from .. import _lib as L
-        from ..engine.core import cur_stream
-        if self._split:
-            return self._step_split(desc, None, None, actions, obs_out, step_out)
-        if isinstance(desc, L._HaltDesc):
-            name, head = desc.step_fn, (C.byref(desc.env), C.byref(desc.pess))
-        else:
-            name = "osrl_model_env_step_gauss" if isinstance(desc, L.ModelEnvGaussT) else "osrl_model_env_step"
-            head = (C.byref(desc),)
-        L.check(getattr(L.load(), name)(*head, actions.data_ptr(), self.state.data_ptr(), obs_out.data_ptr(),
-                                        obs_out.stride(0), self.acc.data_ptr(), self.unc.data_ptr(),
-                                        None if step_out is None else step_out.data_ptr(), self.E, cur_stream()), name)
+        self._launch_step(desc, None, None, actions, obs_out, step_out)
 
     def disagreement(self):
         """Per episode ``(max, mean over the steps taken)`` of the uncertainty signal in use (normalised units), two numpy

@@ -14,13 +14,13 @@
 //   * the member a RANDOM-mode episode follows is a Philox word keyed by (seed, episode id, the episode's own step): a
 //     function of nothing else.
 //
-// The same body records (model_rec_kernel, osrl_model_env_collect): the compile-time flag kRecord adds csrc/rollout_step.h's
+// The same body records (model_rec_kernel, osrl_model_env_step with rec): the compile-time flag kRecord adds rollout_step.h's
 // per-episode exploration noise on the action while it is staged, one row of a DSRL-layout dataset per episode and step,
 // and the discounted sums; with sigma == 0 the step is model_env_kernel's bit for bit.  A row of the tile stores only
 // while it is live, and with kRecord live means e < episodes AND rollout_step.h's live_step: its rule keeps every write
 // inside the tables.
 //
-// A second compile-time flag, kGauss (osrl_model_env_step_gauss / osrl_model_env_collect_gauss: model_env_gauss_kernel,
+// A second compile-time flag, kGauss (osrl_model_env_step with gauss in env's place: model_env_gauss_kernel,
 // model_rec_gauss_kernel and their twins), reads members that are diagonal Gaussians -- (od + 1 means | cost | od + 1 raw
 // log-variances), the first od + 2 columns exactly as before.  Right after a member's last layer the row's 32 threads turn
 // its raw log-variances into sigma^2 (PETS' soft clamp), add them into or copy them to ONE extra LDS tile (the mean
@@ -29,8 +29,8 @@
 // episode's own step and the column, or injected) and uses max_m rms(sigma_m) in the disagreement's place when asked to.
 // With the flag off nothing of this exists: the four kernels above keep their listing.
 //
-// A third compile-time flag, kPess (osrl_model_env_step_halt / _collect_halt / _step_gauss_halt / _collect_gauss_halt:
-// halt_env_kernel, halt_rec_kernel, halt_env_gauss_kernel, halt_rec_gauss_kernel and their twins), makes the step
+// A third compile-time flag, kPess (osrl_model_env_step with pess: halt_env_kernel, halt_rec_kernel,
+// halt_env_gauss_kernel, halt_rec_gauss_kernel and their twins), makes the step
 // pessimistic where lane j == 0 of a row forms reward and cost: the cost threshold is applied to c + cost_penalty u
 // (CAP's inflation), and u > halt_threshold ends the episode with a fixed reward and cost (MOReL's absorbing "unknown"):
 // the done latch is set, halt_step[e] takes the step, a recorded row is terminal.  Nothing else moves; with the threshold
@@ -38,6 +38,7 @@
 //
 // model_branch_kernel (osrl_model_env_branch) starts every episode at a row drawn uniformly from a store's observations.
 #include "argmem.h"
+#include "model_env_args.h"
 #include "policy_common.h"
 #include "rollout_step.h"
 
@@ -57,30 +58,7 @@ constexpr int kKeep = OSRL_MODEL_ENV_MAX_STATE / kRowThreads;  // state columns 
 constexpr uint32_t kMemberStream = 14;                      // Philox stream of the RANDOM-mode member choice
 constexpr uint32_t kBranchStream = 15;                      // Philox stream of the branch starts (13: the exploration noise)
 
-struct StepArgs {
-  osrl_model_env_t d;
-  const float* act;
-  float* state;
-  float* obs;
-  float* acc;
-  float* unc;
-  float* step_out;
-  int32_t obs_ld, episodes;
-};
-
-struct RecArgs {
-  StepArgs s;  // (step_out is unused: the tables carry the step's reward and cost)
-  osrl_collect_t c;
-  float* row_unc;
-};
-struct NoRec {};
-
-// what the Gaussian step adds to either descriptor (osrl_model_env_gauss_t beyond its osrl_model_env_t)
-struct GaussArgs {
-  const float* noise_in;
-  float lo, hi;
-  int32_t sample, unc;
-};
+// the descriptors of the eight kernels: model_env_args.h's pieces, composed per combination of the flags
 struct GStepArgs {
   StepArgs s;
   GaussArgs g;
@@ -88,12 +66,6 @@ struct GStepArgs {
 struct GRecArgs {
   RecArgs r;
   GaussArgs g;
-};
-struct NoGauss {};
-// what the pessimistic step adds to any of the four descriptors (osrl_model_env_pess_t, by value)
-struct PessArgs {
-  float halt_threshold, halt_reward, halt_cost, cost_penalty;
-  int32_t* halt_step;
 };
 struct HStepArgs {
   StepArgs s;
@@ -111,7 +83,6 @@ struct HGRecArgs {
   GRecArgs r;
   PessArgs p;
 };
-struct NoPess {};
 constexpr uint32_t kGaussStream = 16;  // Philox stream of the sampled next state and reward
 
 // (Gaussian step) beside Lds: 132 KB + 16.3 KB of the 160 KB
@@ -426,7 +397,7 @@ __global__ __launch_bounds__(kThreads) void model_env_kernel_p(const void* p) {
   model_env_body<false, const OSRL_CAS StepArgs&, NoRec>(*(const OSRL_CAS StepArgs*)p, NoRec{}, l);
 }
 
-// the recording step (osrl_model_env_collect) and its descriptor-pointer twin
+// the recording step (rec given) and its descriptor-pointer twin
 __global__ __launch_bounds__(kThreads) void model_rec_kernel(const RecArgs a) {
   __shared__ Lds l;
   model_env_body<true, const StepArgs&, const RecArgs&>(a.s, a, l);
@@ -437,7 +408,7 @@ __global__ __launch_bounds__(kThreads) void model_rec_kernel_p(const void* p) {
   model_env_body<true, const OSRL_CAS StepArgs&, const OSRL_CAS RecArgs&>(a.s, a, l);
 }
 
-// the Gaussian step and recording step (osrl_model_env_step_gauss / _collect_gauss), each with its descriptor-pointer twin
+// the Gaussian step and recording step (gauss given), each with its descriptor-pointer twin
 __global__ __launch_bounds__(kThreads) void model_env_gauss_kernel(const GStepArgs a) {
   __shared__ Lds l;
   __shared__ LdsGauss lg;
@@ -463,8 +434,8 @@ __global__ __launch_bounds__(kThreads) void model_rec_gauss_kernel_p(const void*
 }
 static_assert(sizeof(Lds) + sizeof(LdsGauss) <= 160 * 1024, "model_env_gauss_kernel: LDS per workgroup");
 
-// the pessimistic step (osrl_model_env_step_halt / _collect_halt / _step_gauss_halt / _collect_gauss_halt): the four
-// kernels above with kPess on, each with its descriptor-pointer twin.  No LDS beside theirs.
+// the pessimistic step (pess given): the four kernels above with kPess on, each with its descriptor-pointer twin.  No LDS
+// beside theirs.
 __global__ __launch_bounds__(kThreads) void halt_env_kernel(const HStepArgs a) {
   __shared__ Lds l;
   model_env_body<false, const StepArgs&, NoRec, false, NoGauss, true, const PessArgs&>(a.s, NoRec{}, l, NoGauss{}, nullptr,
@@ -575,178 +546,65 @@ __global__ __launch_bounds__(256) void dyn_prepare_kernel(const PrepArgs a) {
   a.target[i] = t;
 }
 
-bool valid_member(const osrl_gemv_net_t& n, int in, int out) {
-  if (n.n_layers < 1 || n.n_layers > OSRL_MAX_LAYERS || n.out_scale != 1.0f) return false;
-  for (int l = 0; l <= n.n_layers; ++l)
-    if (n.dims[l] < 1 || n.dims[l] > OSRL_MODEL_ENV_MAX_WIDTH) return false;
-  for (int l = 0; l < n.n_layers; ++l)
-    if (!n.Wf[l] || !n.b[l]) return false;
-  return n.dims[0] == in && n.dims[n.n_layers] == out;
-}
-
-// the step's descriptor, checked (false: a bad argument)
-bool fill_step(StepArgs& a, const osrl_model_env_t* env, const float* act, float* state, float* obs, int32_t obs_ld,
-               float* acc, float* unc, float* step_out, int32_t episodes, bool gauss = false) {
-  if (!env || !act || !state || !obs || !acc || !unc || episodes < 1) return false;
-  const osrl_model_env_t& d = *env;
-  if (d.n_models < 1 || d.n_models > OSRL_MAX_NETS || d.state_dim < 1 || d.state_dim > OSRL_MODEL_ENV_MAX_STATE ||
-      d.action_dim < 1 || obs_ld < d.state_dim || !d.mu_s || !d.sd_s || !d.mu_d || !d.sd_d || !d.mu_r || !d.sd_r ||
-      (d.s_lo == nullptr) != (d.s_hi == nullptr))
-    return false;
-  if (d.mode < OSRL_MODEL_ENV_MEAN || d.mode > OSRL_MODEL_ENV_RANDOM) return false;
-  if (d.mode == OSRL_MODEL_ENV_MEMBER && (d.member < 0 || d.member >= d.n_models)) return false;
-  if (d.mode == OSRL_MODEL_ENV_RANDOM && !d.seed && !d.member_in) return false;
-  for (int m = 0; m < d.n_models; ++m)
-    if (!valid_member(d.net[m], d.state_dim + d.action_dim, gauss ? 2 * d.state_dim + 3 : d.state_dim + 2)) return false;
-  memset(&a, 0, sizeof a);  // (the arena finds a block by its bytes: no stray padding)
-  a.d = d;
-  for (int m = d.n_models; m < OSRL_MAX_NETS; ++m) memset(&a.d.net[m], 0, sizeof a.d.net[m]);
-  a.d.pad_ = 0;
-  a.d.pad2_ = 0.f;
-  a.act = act;
-  a.state = state;
-  a.obs = obs;
-  a.acc = acc;
-  a.unc = unc;
-  a.step_out = step_out;
-  a.obs_ld = obs_ld;
-  a.episodes = episodes;
-  return true;
-}
-
 }  // namespace
 
-extern "C" int osrl_model_env_step(const osrl_model_env_t* env, const float* act, float* state, float* obs,
-                                   int32_t obs_ld, float* acc, float* unc, float* step_out, int32_t episodes,
-                                   void* stream) {
-  StepArgs a;
-  if (!fill_step(a, env, act, state, obs, obs_ld, acc, unc, step_out, episodes)) return -1;
-  const int tiles = (episodes + kTile - 1) / kTile;
-  return osrl_argmem::launch(model_env_kernel, model_env_kernel_p, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream,
-                             a);
-}
-
-extern "C" int osrl_model_env_collect(const osrl_model_env_t* env, const osrl_collect_t* rec, const float* act,
-                                      float* state, float* obs, int32_t obs_ld, float* acc, float* unc, float* row_unc,
-                                      int32_t episodes, void* stream) {
-  if (!osrl_rollout::valid_collect(rec) || !env || env->episode_len < 1) return -1;
-  RecArgs a;
-  memset(&a, 0, sizeof a);
-  if (!fill_step(a.s, env, act, state, obs, obs_ld, acc, unc, nullptr, episodes)) return -1;
-  a.c = *rec;
-  a.row_unc = row_unc;
-  const int tiles = (episodes + kTile - 1) / kTile;
-  return osrl_argmem::launch(model_rec_kernel, model_rec_kernel_p, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream,
-                             a);
-}
-
-namespace {
-// the Gaussian additions, checked (false: a bad argument)
-bool fill_gauss(GaussArgs& g, const osrl_model_env_gauss_t* env) {
-  if (!env || !(env->logvar_min < env->logvar_max)) return false;
-  if (env->uncertainty != OSRL_MODEL_ENV_UNC_DISAGREEMENT && env->uncertainty != OSRL_MODEL_ENV_UNC_MAX_STD) return false;
-  if (env->sample && !env->noise_in && !env->env.seed) return false;
-  g.noise_in = env->sample ? env->noise_in : nullptr;
-  g.lo = env->logvar_min;
-  g.hi = env->logvar_max;
-  g.sample = env->sample ? 1 : 0;
-  g.unc = env->uncertainty;
-  return true;
-}
-}  // namespace
-
-extern "C" int osrl_model_env_step_gauss(const osrl_model_env_gauss_t* env, const float* act, float* state, float* obs,
-                                         int32_t obs_ld, float* acc, float* unc, float* step_out, int32_t episodes,
-                                         void* stream) {
-  GStepArgs a;
-  memset(&a, 0, sizeof a);
-  if (!env || !fill_step(a.s, &env->env, act, state, obs, obs_ld, acc, unc, step_out, episodes, true)) return -1;
-  if (!fill_gauss(a.g, env)) return -1;
-  const int tiles = (episodes + kTile - 1) / kTile;
-  return osrl_argmem::launch(model_env_gauss_kernel, model_env_gauss_kernel_p, dim3(tiles), dim3(kThreads), 0,
-                             (hipStream_t)stream, a);
-}
-
-extern "C" int osrl_model_env_collect_gauss(const osrl_model_env_gauss_t* env, const osrl_collect_t* rec,
-                                            const float* act, float* state, float* obs, int32_t obs_ld, float* acc,
-                                            float* unc, float* row_unc, int32_t episodes, void* stream) {
-  if (!osrl_rollout::valid_collect(rec) || !env || env->env.episode_len < 1) return -1;
-  GRecArgs a;
-  memset(&a, 0, sizeof a);
-  if (!fill_step(a.r.s, &env->env, act, state, obs, obs_ld, acc, unc, nullptr, episodes, true)) return -1;
-  if (!fill_gauss(a.g, env)) return -1;
-  a.r.c = *rec;
-  a.r.row_unc = row_unc;
-  const int tiles = (episodes + kTile - 1) / kTile;
-  return osrl_argmem::launch(model_rec_gauss_kernel, model_rec_gauss_kernel_p, dim3(tiles), dim3(kThreads), 0,
-                             (hipStream_t)stream, a);
-}
-
-namespace {
-// the pessimistic additions, checked (false: a bad argument; +-inf thresholds are values like any other)
-bool fill_pess(PessArgs& p, const osrl_model_env_pess_t* ps) {
-  if (!ps || ps->halt_threshold != ps->halt_threshold || !(ps->halt_reward == ps->halt_reward)) return false;
-  if (ps->halt_cost != 0.f && ps->halt_cost != 1.f) return false;
-  if (!(ps->cost_penalty >= 0.f) || ps->cost_penalty > 3.0e38f) return false;
-  p.halt_threshold = ps->halt_threshold;
-  p.halt_reward = ps->halt_reward;
-  p.halt_cost = ps->halt_cost;
-  p.cost_penalty = ps->cost_penalty;
-  p.halt_step = ps->halt_step;
-  return true;
-}
-}  // namespace
-
-extern "C" int osrl_model_env_step_halt(const osrl_model_env_t* env, const osrl_model_env_pess_t* pess, const float* act,
-                                        float* state, float* obs, int32_t obs_ld, float* acc, float* unc,
-                                        float* step_out, int32_t episodes, void* stream) {
-  HStepArgs a;
-  memset(&a, 0, sizeof a);
-  if (!fill_step(a.s, env, act, state, obs, obs_ld, acc, unc, step_out, episodes) || !fill_pess(a.p, pess)) return -1;
-  const int tiles = (episodes + kTile - 1) / kTile;
-  return osrl_argmem::launch(halt_env_kernel, halt_env_kernel_p, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream, a);
-}
-
-extern "C" int osrl_model_env_collect_halt(const osrl_model_env_t* env, const osrl_model_env_pess_t* pess,
-                                           const osrl_collect_t* rec, const float* act, float* state, float* obs,
-                                           int32_t obs_ld, float* acc, float* unc, float* row_unc, int32_t episodes,
-                                           void* stream) {
-  if (!osrl_rollout::valid_collect(rec) || !env || env->episode_len < 1) return -1;
-  HRecArgs a;
-  memset(&a, 0, sizeof a);
-  if (!fill_step(a.r.s, env, act, state, obs, obs_ld, acc, unc, nullptr, episodes) || !fill_pess(a.p, pess)) return -1;
-  a.r.c = *rec;
-  a.r.row_unc = row_unc;
-  const int tiles = (episodes + kTile - 1) / kTile;
-  return osrl_argmem::launch(halt_rec_kernel, halt_rec_kernel_p, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream, a);
-}
-
-extern "C" int osrl_model_env_step_gauss_halt(const osrl_model_env_gauss_t* env, const osrl_model_env_pess_t* pess,
-                                              const float* act, float* state, float* obs, int32_t obs_ld, float* acc,
-                                              float* unc, float* step_out, int32_t episodes, void* stream) {
-  HGStepArgs a;
-  memset(&a, 0, sizeof a);
-  if (!env || !fill_step(a.s.s, &env->env, act, state, obs, obs_ld, acc, unc, step_out, episodes, true)) return -1;
-  if (!fill_gauss(a.s.g, env) || !fill_pess(a.p, pess)) return -1;
-  const int tiles = (episodes + kTile - 1) / kTile;
-  return osrl_argmem::launch(halt_env_gauss_kernel, halt_env_gauss_kernel_p, dim3(tiles), dim3(kThreads), 0,
-                             (hipStream_t)stream, a);
-}
-
-extern "C" int osrl_model_env_collect_gauss_halt(const osrl_model_env_gauss_t* env, const osrl_model_env_pess_t* pess,
-                                                 const osrl_collect_t* rec, const float* act, float* state, float* obs,
-                                                 int32_t obs_ld, float* acc, float* unc, float* row_unc,
-                                                 int32_t episodes, void* stream) {
-  if (!osrl_rollout::valid_collect(rec) || !env || env->env.episode_len < 1) return -1;
-  HGRecArgs a;
-  memset(&a, 0, sizeof a);
-  if (!fill_step(a.r.r.s, &env->env, act, state, obs, obs_ld, acc, unc, nullptr, episodes, true)) return -1;
-  if (!fill_gauss(a.r.g, env) || !fill_pess(a.p, pess)) return -1;
-  a.r.r.c = *rec;
-  a.r.r.row_unc = row_unc;
-  const int tiles = (episodes + kTile - 1) / kTile;
-  return osrl_argmem::launch(halt_rec_gauss_kernel, halt_rec_gauss_kernel_p, dim3(tiles), dim3(kThreads), 0,
-                             (hipStream_t)stream, a);
+// The step, whichever of the three optional things it carries (include/osrl_amd.h): gauss in env's place, pess, rec.  Each
+// of the eight combinations fills the descriptor type of its own kernel, zeroed as a whole (model_env_args.h), so the arena
+// sees that kernel's bytes.  The refusals are osrl_model_env_step_split's.
+extern "C" int osrl_model_env_step(const osrl_model_env_t* env, const osrl_model_env_gauss_t* gauss,
+                                   const osrl_model_env_pess_t* pess, const osrl_collect_t* rec, float* row_unc,
+                                   const float* act, float* state, float* obs, int32_t obs_ld, float* acc, float* unc,
+                                   float* step_out, int32_t episodes, void* stream) {
+  if ((env != nullptr) == (gauss != nullptr)) return -1;
+  const osrl_model_env_t* d = gauss ? &gauss->env : env;
+  if (rec && (!osrl_rollout::valid_collect(rec) || d->episode_len < 1)) return -1;
+  // a: the kernel's descriptor; s, r, g, p: its pieces (nullptr: the combination has none)
+  auto run = [&](auto k, void (*kp)(const void*), auto& a, StepArgs& s, RecArgs* r, GaussArgs* g, PessArgs* p) {
+    memset(&a, 0, sizeof a);
+    if (!fill_step(s, d, act, state, obs, obs_ld, acc, unc, r ? nullptr : step_out, episodes, g != nullptr)) return -1;
+    if (g && !fill_gauss(*g, gauss)) return -1;
+    if (p && !fill_pess(*p, pess)) return -1;
+    if (r) {
+      r->c = *rec;
+      r->row_unc = row_unc;
+    }
+    const int tiles = (episodes + kTile - 1) / kTile;
+    return osrl_argmem::launch(k, kp, dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream, a);
+  };
+  switch ((rec ? 4 : 0) | (gauss ? 2 : 0) | (pess ? 1 : 0)) {
+    case 0: {
+      StepArgs a;
+      return run(model_env_kernel, model_env_kernel_p, a, a, nullptr, nullptr, nullptr);
+    }
+    case 1: {
+      HStepArgs a;
+      return run(halt_env_kernel, halt_env_kernel_p, a, a.s, nullptr, nullptr, &a.p);
+    }
+    case 2: {
+      GStepArgs a;
+      return run(model_env_gauss_kernel, model_env_gauss_kernel_p, a, a.s, nullptr, &a.g, nullptr);
+    }
+    case 3: {
+      HGStepArgs a;
+      return run(halt_env_gauss_kernel, halt_env_gauss_kernel_p, a, a.s.s, nullptr, &a.s.g, &a.p);
+    }
+    case 4: {
+      RecArgs a;
+      return run(model_rec_kernel, model_rec_kernel_p, a, a.s, &a, nullptr, nullptr);
+    }
+    case 5: {
+      HRecArgs a;
+      return run(halt_rec_kernel, halt_rec_kernel_p, a, a.r.s, &a.r, nullptr, &a.p);
+    }
+    case 6: {
+      GRecArgs a;
+      return run(model_rec_gauss_kernel, model_rec_gauss_kernel_p, a, a.r.s, &a.r, &a.g, nullptr);
+    }
+    default: {
+      HGRecArgs a;
+      return run(halt_rec_gauss_kernel, halt_rec_gauss_kernel_p, a, a.r.r.s, &a.r.r, &a.r.g, &a.p);
+    }
+  }
 }
 
 extern "C" int osrl_model_env_branch(const float* table, int64_t n_rows, const int64_t* n_rows_dev, int64_t n_limit,

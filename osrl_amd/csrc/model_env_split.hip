@@ -18,14 +18,16 @@
 //      its member loop -- ysum as y0, + y1, .., ysel, yk[m][q] in registers, the variance tile in member order, amax as
 //      the same fmaxf chain -- then runs the same epilogue.  Nobody writes state, acc or the tables before every member
 //      of the tile has signed in, i.e. has staged its inputs.
-// Every expression below is model_env.hip's, restated: sharing them through a header moved that file's registers (198 ->
-// 204), so it stays as it is and tests/test_gpu_model_env_split.py holds the two together bit for bit.  The serial chain
+// Every device expression below is model_env.hip's, restated: sharing them through a header moved that file's registers
+// (198 -> 204), so it stays as it is and tests/test_gpu_model_env_split.py holds the two together bit for bit.  Only the
+// host side -- the descriptor pieces and their checks -- is shared, through model_env_args.h.  The serial chain
 // is n_layers long instead of M * n_layers; the price is M times the staging and one trip of the member tiles through
 // HBM, which loses once the plain form fills the chip (README: the measured crossover).  The kernels read neither
 // blockDim nor gridDim, use no scratch, and the three compile-time flags (record, Gaussian, pessimistic) are template
 // parameters of one body: eight kernels, each with its descriptor-pointer twin (argmem.h).
 #include "argmem.h"
 #include "dev_util.h"
+#include "model_env_args.h"
 #include "policy_common.h"
 #include "rollout_step.h"
 
@@ -44,37 +46,6 @@ constexpr int kRowThreads = kThreads / kTile;               // 32 threads share 
 constexpr int kKeep = OSRL_MODEL_ENV_MAX_STATE / kRowThreads;  // state columns a thread keeps per member
 constexpr uint32_t kMemberStream = 14;                      // Philox stream of the RANDOM-mode member choice
 
-struct StepArgs {
-  osrl_model_env_t d;
-  const float* act;
-  float* state;
-  float* obs;
-  float* acc;
-  float* unc;
-  float* step_out;
-  int32_t obs_ld, episodes;
-};
-
-struct RecArgs {
-  StepArgs s;  // (step_out is unused: the tables carry the step's reward and cost)
-  osrl_collect_t c;
-  float* row_unc;
-};
-struct NoRec {};
-
-// what the Gaussian step adds to either descriptor (osrl_model_env_gauss_t beyond its osrl_model_env_t)
-struct GaussArgs {
-  const float* noise_in;
-  float lo, hi;
-  int32_t sample, unc;
-};
-struct NoGauss {};
-// what the pessimistic step adds to any of the four descriptors (osrl_model_env_pess_t, by value)
-struct PessArgs {
-  float halt_threshold, halt_reward, halt_cost, cost_penalty;
-  int32_t* halt_step;
-};
-struct NoPess {};
 constexpr uint32_t kGaussStream = 16;  // Philox stream of the sampled next state and reward
 
 // (Gaussian step) beside Lds: 132 KB + 16.3 KB of the 160 KB
@@ -493,74 +464,9 @@ int launch_split(const SplitArgs& a, hipStream_t stream) {
                              dim3(tiles, (unsigned)a.r.s.d.n_models), dim3(kThreads), 0, stream, a);
 }
 
-// ---- host side: the descriptors' checks (false: a bad argument)
-inline bool valid_member(const osrl_gemv_net_t& n, int in, int out) {
-  if (n.n_layers < 1 || n.n_layers > OSRL_MAX_LAYERS || n.out_scale != 1.0f) return false;
-  for (int l = 0; l <= n.n_layers; ++l)
-    if (n.dims[l] < 1 || n.dims[l] > OSRL_MODEL_ENV_MAX_WIDTH) return false;
-  for (int l = 0; l < n.n_layers; ++l)
-    if (!n.Wf[l] || !n.b[l]) return false;
-  return n.dims[0] == in && n.dims[n.n_layers] == out;
-}
-
-// the step's descriptor, checked
-inline bool fill_step(StepArgs& a, const osrl_model_env_t* env, const float* act, float* state, float* obs,
-                      int32_t obs_ld, float* acc, float* unc, float* step_out, int32_t episodes, bool gauss = false) {
-  if (!env || !act || !state || !obs || !acc || !unc || episodes < 1) return false;
-  const osrl_model_env_t& d = *env;
-  if (d.n_models < 1 || d.n_models > OSRL_MAX_NETS || d.state_dim < 1 || d.state_dim > OSRL_MODEL_ENV_MAX_STATE ||
-      d.action_dim < 1 || obs_ld < d.state_dim || !d.mu_s || !d.sd_s || !d.mu_d || !d.sd_d || !d.mu_r || !d.sd_r ||
-      (d.s_lo == nullptr) != (d.s_hi == nullptr))
-    return false;
-  if (d.mode < OSRL_MODEL_ENV_MEAN || d.mode > OSRL_MODEL_ENV_RANDOM) return false;
-  if (d.mode == OSRL_MODEL_ENV_MEMBER && (d.member < 0 || d.member >= d.n_models)) return false;
-  if (d.mode == OSRL_MODEL_ENV_RANDOM && !d.seed && !d.member_in) return false;
-  for (int m = 0; m < d.n_models; ++m)
-    if (!valid_member(d.net[m], d.state_dim + d.action_dim, gauss ? 2 * d.state_dim + 3 : d.state_dim + 2)) return false;
-  memset(&a, 0, sizeof a);  // (the arena finds a block by its bytes: no stray padding)
-  a.d = d;
-  for (int m = d.n_models; m < OSRL_MAX_NETS; ++m) memset(&a.d.net[m], 0, sizeof a.d.net[m]);
-  a.d.pad_ = 0;
-  a.d.pad2_ = 0.f;
-  a.act = act;
-  a.state = state;
-  a.obs = obs;
-  a.acc = acc;
-  a.unc = unc;
-  a.step_out = step_out;
-  a.obs_ld = obs_ld;
-  a.episodes = episodes;
-  return true;
-}
-
-// the Gaussian additions, checked
-inline bool fill_gauss(GaussArgs& g, const osrl_model_env_gauss_t* env) {
-  if (!env || !(env->logvar_min < env->logvar_max)) return false;
-  if (env->uncertainty != OSRL_MODEL_ENV_UNC_DISAGREEMENT && env->uncertainty != OSRL_MODEL_ENV_UNC_MAX_STD) return false;
-  if (env->sample && !env->noise_in && !env->env.seed) return false;
-  g.noise_in = env->sample ? env->noise_in : nullptr;
-  g.lo = env->logvar_min;
-  g.hi = env->logvar_max;
-  g.sample = env->sample ? 1 : 0;
-  g.unc = env->uncertainty;
-  return true;
-}
-
-// the pessimistic additions, checked (+-inf thresholds are values like any other)
-inline bool fill_pess(PessArgs& p, const osrl_model_env_pess_t* ps) {
-  if (!ps || ps->halt_threshold != ps->halt_threshold || !(ps->halt_reward == ps->halt_reward)) return false;
-  if (ps->halt_cost != 0.f && ps->halt_cost != 1.f) return false;
-  if (!(ps->cost_penalty >= 0.f) || ps->cost_penalty > 3.0e38f) return false;
-  p.halt_threshold = ps->halt_threshold;
-  p.halt_reward = ps->halt_reward;
-  p.halt_cost = ps->halt_cost;
-  p.cost_penalty = ps->cost_penalty;
-  p.halt_step = ps->halt_step;
-  return true;
-}
-
 }  // namespace
 
+// osrl_model_env_step's arguments and refusals (model_env_args.h holds the checks of both), plus member_out and arrive
 extern "C" int osrl_model_env_step_split(const osrl_model_env_t* env, const osrl_model_env_gauss_t* gauss,
                                          const osrl_model_env_pess_t* pess, const osrl_collect_t* rec, float* row_unc,
                                          const float* act, float* state, float* obs, int32_t obs_ld, float* acc,
@@ -570,7 +476,7 @@ extern "C" int osrl_model_env_step_split(const osrl_model_env_t* env, const osrl
   const osrl_model_env_t* d = gauss ? &gauss->env : env;
   if (rec && (!osrl_rollout::valid_collect(rec) || d->episode_len < 1)) return -1;
   SplitArgs a;
-  memset(&a, 0, sizeof a);  // (the arena finds a block by its bytes: no stray padding)
+  memset(&a, 0, sizeof a);
   if (!fill_step(a.r.s, d, act, state, obs, obs_ld, acc, unc, rec ? nullptr : step_out, episodes, gauss != nullptr))
     return -1;
   if (gauss && !fill_gauss(a.g, gauss)) return -1;

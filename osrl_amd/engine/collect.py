@@ -15,7 +15,7 @@ transformer forward is the one launch ``osrl_cdt_collect`` (csrc/cdt_collect.hip
 cursor, with per-episode targets and, with ``sample=True``, the Gaussian head's own standard deviation as the noise scale.
 
 ``ModelCollector`` is ``Collector`` on a learned model (``Trainer.collect_model``): the step ends in
-``osrl_model_env_collect`` (csrc/model_env.hip), episodes start at the environment's initial states or at rows drawn on
+``osrl_model_env_step`` with its recorder (csrc/model_env.hip), episodes start at the environment's initial states or at rows drawn on
 device from a store (``osrl_model_env_branch``, Philox stream 15), and run ``horizon`` steps -- MOPO's / MBPO's branched
 rollouts (DESIGN.md "Training on a learned model").  On an environment with a ``halt_threshold`` an episode may end early:
 the run then compacts the tables on device (csrc/compact.hip ``osrl_collect_compact``) and hands out the live rows only.
@@ -278,9 +278,9 @@ def check_model_target(into, start, state_dim: int, action_dim: int, rows: int, 
 
 
 class ModelCollector(_Tables, BatchedRollout):
-    """``Collector`` on a ``ModelVecEnv``: the evaluating rollout's policy launches, then ``osrl_model_env_collect``
-    (csrc/model_env.hip) where the evaluating rollout issues ``osrl_model_env_step`` -- the same step behind a compile-time
-    flag, so without noise a run is ``BatchedRollout.run``'s bit for bit.  ``run`` rolls every episode ``horizon`` steps
+    """``Collector`` on a ``ModelVecEnv``: the evaluating rollout's policy launches, then ``osrl_model_env_step``
+    (csrc/model_env.hip) with its recorder where the evaluating rollout issues it without -- the same step behind a
+    compile-time flag, so without noise a run is ``BatchedRollout.run``'s bit for bit.  ``run`` rolls every episode ``horizon`` steps
     from the environment's initial states or from rows of a store (``osrl_model_env_branch``: one launch, drawn on
     device from the store's live count) and records them with the penalised reward.  What comes out is a model's
     opinion.  ``start_rows`` (int64 ``[E]``, None without a start store) and ``row_disagreement`` (``[E * horizon]``, the
@@ -359,21 +359,9 @@ class ModelCollector(_Tables, BatchedRollout):
         return Collected(data, tot[:, 0], tot[:, 1], tot[:, 2], tot[:, 4], tot[:, 5])
 
     def body(self) -> None:
-        import ctypes as C
         act = self.policy()
-        v = self.venv
         # (a probabilistic model's descriptor: the sampled next state and the penalised reward are what is recorded)
-        c = self.env_c
-        if v.split_members:  # the member-parallel form of the same step (csrc/model_env_split.hip), every descriptor
-            return v._step_split(c, self._rec_now(), self._row_unc.data_ptr(), act, self.obs, None)
-        if isinstance(c, L._HaltDesc):  # halting / the pessimistic cost: the same descriptor beside osrl_model_env_pess_t
-            name, head = c.collect_fn, (C.byref(c.env), C.byref(c.pess))
-        else:
-            name = "osrl_model_env_collect_gauss" if isinstance(c, L.ModelEnvGaussT) else "osrl_model_env_collect"
-            head = (C.byref(c),)
-        L.check(getattr(L.load(), name)(*head, self._rec_now(), act.data_ptr(), v.state.data_ptr(),
-                                        self.obs.data_ptr(), self.obs.stride(0), v.acc.data_ptr(), v.unc.data_ptr(),
-                                        self._row_unc.data_ptr(), v.E, cur_stream()), name)
+        self.venv._launch_step(self.env_c, self._rec_now(), self._row_unc.data_ptr(), act, self.obs, None)
 
     def _snapshot(self):  # (venv.unc is the environment's extra_state: the base class has it)
         return super()._snapshot() + [(self.disc, self.disc.clone())]

@@ -3,7 +3,7 @@
 ``ModelPlanner`` is a ``ModelCollector`` (engine/collect.py) whose run starts at N REAL states instead of the environment's
 own: every state ("slot") fans out into K imagined episodes (csrc/plan.hip ``osrl_plan_fanout``; episode ``n * K + k`` is
 candidate k of slot n), the collector's recorded step runs H times -- the policy's launches, ``a = clip(pi(s) + sigma_e *
-eps)``, ``osrl_model_env_collect*`` with whatever pessimism the environment carries (``reward_penalty``, ``cost_penalty``,
+eps)``, the recording ``osrl_model_env_step`` with whatever pessimism the environment carries (``reward_penalty``, ``cost_penalty``,
 ``halt_threshold``) -- and ``osrl_plan_select`` picks one candidate per slot from the discounted sums the recorder keeps:
 the best penalised return among those whose discounted cost stays inside the slot's remaining budget, the cheapest one
 when none does, or with ``temperature > 0`` the softmax average of the feasible first actions (MPPI).

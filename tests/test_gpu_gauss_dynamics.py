@@ -1,5 +1,5 @@
 """The Gaussian dynamics ensemble on the GPU (``Dynamics(probabilistic=True)``: csrc/mlp.hip ``OSRL_SEED_GAUSS_NLL``,
-csrc/model_env.hip ``osrl_model_env_step_gauss`` / ``osrl_model_env_collect_gauss``, common/model_env.py ``sample`` /
+csrc/model_env.hip ``osrl_model_env_step`` with ``gauss``, recording or not, common/model_env.py ``sample`` /
 ``uncertainty``) against its fp64 restatement (tests/gauss_dynamics_oracle.py).
 
 Bounds.  Oracle parity: max |gpu - oracle| <= 1e-4 of each tensor's scale (scale = max |oracle tensor|), the project's
@@ -426,7 +426,7 @@ def test_step_replay_equals_train_one_step_on_the_rows_it_drew():
 @pytest.mark.parametrize("shape,mode,inject", [(GC.SHAPES[4], "random", False), (GC.SHAPES[2], "mean", True)],
                          ids=lambda x: str(x) if isinstance(x, (str, bool)) else SHAPE_IDS(x))
 def test_collected_rows_are_the_gauss_steps(shape, mode, inject):
-    """Every recorded row, fed back through ``osrl_model_env_step_gauss`` at its state, action, step and noise (drawn from
+    """Every recorded row, fed back through the unrecorded Gaussian step at its state, action, step and noise (drawn from
     the same seed, episode id and step, or injected), comes back bit for bit; ``row_disagreement`` is the signal in use."""
     from osrl_amd.engine.collect import ModelCollector
     od, ad, hidden, M = shape

@@ -1,9 +1,9 @@
-"""Recorded rollouts on the learned dynamics model (csrc/model_env.hip ``osrl_model_env_collect`` / ``osrl_model_env_branch``,
+"""Recorded rollouts on the learned dynamics model (csrc/model_env.hip ``osrl_model_env_step`` with ``rec`` / ``osrl_model_env_branch``,
 engine/collect.py ``ModelCollector``, ``Trainer.collect_model``, ``ReplayStore(pinned_rows=)``).
 
 Almost every comparison is exact: the recording kernel is the evaluating kernel's body behind a compile-time flag, an
 episode's bits do not depend on E or its tile row, and the clip is idempotent -- so a recorded row, fed back through the
-existing ``osrl_model_env_step`` as a one-step episode, must come back bit for bit.  The bounds that are not exact:
+unrecorded ``osrl_model_env_step`` as a one-step episode, must come back bit for bit.  The bounds that are not exact:
   * oracle parity (fp64, tests/model_env_oracle.py): 1e-4 of each tensor's scale, the project's bound
     (tests/test_gpu_model_env.py ``BOUND``); cost bits on the rows farther than 1e-3 from the threshold, at most 2 % left out;
   * discounted sums: gamma^t carries t - 1 roundings, the running fmaf sum one per step: h * 2^-24 * sum |gamma^t x|

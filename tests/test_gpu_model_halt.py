@@ -210,7 +210,7 @@ def test_defaults_are_the_old_step(case):
     pess = L.ModelEnvPessT()
     pess.halt_threshold, pess.halt_reward, pess.halt_cost, pess.cost_penalty = float("inf"), -7.0, 1.0, 0.0
     pess.halt_step = new.halt_step.data_ptr()
-    name = "osrl_model_env_step_gauss_halt" if case == "G" else "osrl_model_env_step_halt"
+    head = (None, C.byref(desc)) if case == "G" else (C.byref(desc), None)  # osrl_model_env_step's env, gauss
     od = old.state_dim
     obs = [torch.zeros(E, od, device=DEV) for _ in range(2)]
     so = [torch.zeros(E, 2, device=DEV) for _ in range(2)]
@@ -220,9 +220,9 @@ def test_defaults_are_the_old_step(case):
     for t in range(T + 2):  # (two launches past the end: both freeze)
         a = acts[t % T]
         old.step(desc, a, obs[0], so[0])
-        L.check(getattr(L.load(), name)(C.byref(desc), C.byref(pess), a.data_ptr(), new.state.data_ptr(),
-                                        obs[1].data_ptr(), obs[1].stride(0), new.acc.data_ptr(), new.unc.data_ptr(),
-                                        so[1].data_ptr(), E, cur_stream()), name)
+        L.check(L.load().osrl_model_env_step(*head, C.byref(pess), None, None, a.data_ptr(), new.state.data_ptr(),
+                                             obs[1].data_ptr(), obs[1].stride(0), new.acc.data_ptr(), new.unc.data_ptr(),
+                                             so[1].data_ptr(), E, cur_stream()), "osrl_model_env_step")
         for x, y in ((old.state, new.state), (obs[0], obs[1]), (old.acc, new.acc), (old.unc, new.unc), (so[0], so[1])):
             assert torch.equal(x, y), t
     assert (new.halt_step == -1).all() and (old.acc[:, 2] == T).all()
@@ -230,15 +230,15 @@ def test_defaults_are_the_old_step(case):
     for field, bad in (("halt_threshold", float("nan")), ("halt_cost", 0.5), ("cost_penalty", -1.0)):
         p2 = L.ModelEnvPessT.from_buffer_copy(pess)
         setattr(p2, field, bad)
-        assert getattr(L.load(), name)(C.byref(desc), C.byref(p2), acts[0].data_ptr(), new.state.data_ptr(),
-                                       obs[1].data_ptr(), obs[1].stride(0), new.acc.data_ptr(), new.unc.data_ptr(),
-                                       so[1].data_ptr(), E, cur_stream()) == -1, field
+        assert L.load().osrl_model_env_step(*head, C.byref(p2), None, None, acts[0].data_ptr(), new.state.data_ptr(),
+                                            obs[1].data_ptr(), obs[1].stride(0), new.acc.data_ptr(), new.unc.data_ptr(),
+                                            so[1].data_ptr(), E, cur_stream()) == -1, field
 
 
 @pytest.mark.parametrize("case", ["B", "G"])
 def test_defaults_are_the_old_collect(case):
-    """threshold +inf, penalty 0 through ``osrl_model_env_collect[_gauss]_halt`` (and the compaction, here the identity)
-    against the plain entry point: every table, ``disc``, ``acc``, ``unc``, the state and the per-row u."""
+    """threshold +inf, penalty 0 through the recording ``osrl_model_env_step`` with ``pess`` (and the compaction, here the
+    identity) against the same call without it: every table, ``disc``, ``acc``, ``unc``, the state and the per-row u."""
     from osrl_amd import _lib as L
     old = make_env(case, pess=False)
     new = make_env(case, pess=False, halt_threshold=float("inf"))

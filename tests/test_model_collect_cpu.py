@@ -156,22 +156,26 @@ def test_entry_points_refuse_bad_arguments_before_any_launch():
     lib = L.load()
     env, rec = L.ModelEnvT(), L.CollectT()
     one = 0x1000  # (never dereferenced: every call below fails a check first)
-    assert lib.osrl_model_env_collect(None, rec, one, one, one, 4, one, one, None, 1, None) == -1
-    assert lib.osrl_model_env_collect(env, None, one, one, one, 4, one, one, None, 1, None) == -1
+
+    def collect(e, r):  # the recording step: env, no gauss, no pess, rec, no row_unc | act .. episodes as before
+        return lib.osrl_model_env_step(e, None, None, r, None, one, one, one, 4, one, one, None, 1, None)
+
+    assert collect(None, rec) == -1
+    assert collect(env, None) == -1
     env.episode_len = 3
-    assert lib.osrl_model_env_collect(env, rec, one, one, one, 4, one, one, None, 1, None) == -1  # no tables
+    assert collect(env, rec) == -1  # no tables
     for k, _ in L.CollectT._fields_[:11]:
         setattr(rec, k, one)
     rec.seed = None
-    assert lib.osrl_model_env_collect(env, rec, one, one, one, 4, one, one, None, 1, None) == -1  # neither seed nor eps_in
+    assert collect(env, rec) == -1  # neither seed nor eps_in
     rec.seed = one
-    assert lib.osrl_model_env_collect(env, rec, one, one, one, 4, one, one, None, 1, None) == -1  # an empty model descriptor
+    assert collect(env, rec) == -1  # an empty model descriptor
     for k in range(11):
         rec2 = L.CollectT.from_buffer_copy(rec)
         setattr(rec2, L.CollectT._fields_[k][0], None)
         if L.CollectT._fields_[k][0] == "seed":
             continue
-        assert lib.osrl_model_env_collect(env, rec2, one, one, one, 4, one, one, None, 1, None) == -1
+        assert collect(env, rec2) == -1
     ok = [one, 8, None, 0, 4, one, 0, one, one, 4, one, one, one, one, 2, None]
     for i, badv in ((0, None), (1, 0), (3, -1), (4, 0), (5, None), (7, None), (8, None), (9, 3), (10, None), (11, None),
                     (12, None), (13, None), (14, 0)):
@@ -184,7 +188,8 @@ def test_entry_points_refuse_bad_arguments_before_any_launch():
 def _ctype_of(decl):
     from osrl_amd import _lib as L
     decl = re.sub(r"/\*.*?\*/", "", decl).strip()
-    structs = {"osrl_model_env_t": L.ModelEnvT, "osrl_collect_t": L.CollectT}
+    structs = {"osrl_model_env_t": L.ModelEnvT, "osrl_collect_t": L.CollectT, "osrl_model_env_gauss_t": L.ModelEnvGaussT,
+               "osrl_model_env_pess_t": L.ModelEnvPessT}
     if "*" in decl:
         base = decl.replace("const", "").split("*")[0].strip()
         return C.POINTER(structs[base]) if base in structs else C.c_void_p
@@ -193,7 +198,7 @@ def _ctype_of(decl):
             "float": C.c_float}[base]
 
 
-@pytest.mark.parametrize("name", ["osrl_model_env_collect", "osrl_model_env_branch"])
+@pytest.mark.parametrize("name", ["osrl_model_env_step", "osrl_model_env_branch"])
 def test_prototypes_agree_with_the_header(name):
     from osrl_amd import _lib as L
     hdr = open(os.path.join(ROOT, "include", "osrl_amd.h")).read()

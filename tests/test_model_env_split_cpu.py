@@ -9,26 +9,32 @@ from test_isa_halt_model_env_cpu import listing
 
 
 def test_entry_refuses_bad_arguments_before_any_launch():
+    """One table of refusals for ``osrl_model_env_step`` and ``osrl_model_env_step_split``: the two entries state one
+    contract (csrc/model_env_args.h), the split one with ``member_out`` / ``arrive`` appended."""
     from osrl_amd import _lib as L
     lib = L.load()
     one = 0x1000  # (never dereferenced: every call below fails a check first)
     env, gauss, pess, rec = L.ModelEnvT(), L.ModelEnvGaussT(), L.ModelEnvPessT(), L.CollectT()
     tail = [one, one, one, 40, one, one, None, 17]  # act, state, obs, obs_ld, acc, unc, step_out, episodes
 
-    def call(e=env, g=None, p=None, r=None, member_out=one, arrive=one, **kw):
-        t = list(tail)
-        for i, v in kw.items():
-            t[int(i[1:])] = v
-        return lib.osrl_model_env_step_split(None if e is None else C.byref(e), None if g is None else C.byref(g), p, r,
-                                             None, *t, member_out, arrive, None)
+    for split in (False, True):
+        def call(e=env, g=None, p=None, r=None, member_out=one, arrive=one, split=split, **kw):
+            t = list(tail)
+            for i, v in kw.items():
+                t[int(i[1:])] = v
+            head = (None if e is None else C.byref(e), None if g is None else C.byref(g), p, r, None)
+            if split:
+                return lib.osrl_model_env_step_split(*head, *t, member_out, arrive, None)
+            return lib.osrl_model_env_step(*head, *t, None)
 
-    assert call(e=None) == -1 and call(g=gauss) == -1          # neither, both
-    assert call(member_out=None) == -1 and call(arrive=None) == -1
-    assert call() == -1 and call(e=None, g=gauss) == -1        # zeroed descriptors: n_models == 0
-    assert call(r=C.byref(rec)) == -1                          # a recorder without tables
-    for i in (0, 1, 2, 4, 5):                                  # the step's own pointers
-        assert call(**{f"a{i}": None}) == -1, i
-    assert call(a7=0) == -1 and call(p=C.byref(pess)) == -1
+        assert call(e=None) == -1 and call(g=gauss) == -1          # neither, both
+        if split:
+            assert call(member_out=None) == -1 and call(arrive=None) == -1
+        assert call() == -1 and call(e=None, g=gauss) == -1        # zeroed descriptors: n_models == 0
+        assert call(r=C.byref(rec)) == -1                          # a recorder without tables
+        for i in (0, 1, 2, 4, 5):                                  # the step's own pointers
+            assert call(**{f"a{i}": None}) == -1, i
+        assert call(a7=0) == -1 and call(p=C.byref(pess)) == -1
     assert L.model_env_split_row(37, False) == 40 and L.model_env_split_row(37, True) == 80
 
 
